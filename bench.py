@@ -4,6 +4,7 @@
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (also: the last timed step's outputs as .npy)
 
 A "step" is one pass of the hot path over one synthetic registration problem:
   affinity build (scorePairwiseConsistency, EuclideanDistance) + solve() (findDenseClique)
@@ -55,7 +56,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PMC_RECORD = "profiles/pmc_r06.json"
 LDS_PEAK_TBPS = 150.0   # 256 CUs x 256 B/clk x ~2.4 GHz for ds_read_b64 / b128 (MI355X_MICROARCH.md, LDS)
 # the sources of the kernels the PMC record is about (the pass, its decision, the planner that cuts its work, the
@@ -65,6 +66,11 @@ PMC_SOURCES = ("clipper_amd/csrc/k_slices.hip.h", "clipper_amd/csrc/k_solver.hip
                "clipper_amd/csrc/k_resident.hip.h", "clipper_amd/csrc/k_rowview.hip.h", "clipper_amd/csrc/k_gemv.hip.h",
                "clipper_amd/csrc/k_subproblem.hip.h", "clipper_amd/csrc/k_matrix.hip.h", "clipper_amd/csrc/host_rv_resident.hpp",
                "clipper_amd/csrc/host_resident.hpp", "clipper_amd/csrc/host_rowview.hpp", "clipper_amd/csrc/host_subproblem.hpp")
+# --dump-outputs: at most 64 MB in all; M's column sample takes up to half of it, fetched through the dense getter
+DUMP_MAX_BYTES = 64_000_000
+DUMP_AFFINITY_BYTES = 32_000_000
+DUMP_AFFINITY_MAX_M = 20000
+DUMP_SEED = 20261015
 
 
 def kernel_sources_sha256():
@@ -100,7 +106,44 @@ def parse():
                          "clipper_hip_create_rank, ncclCommInitRank, every exchange through ncclAllGather — so that the "
                          "code path the driver's multi-GPU runs take can be exercised on a one-GPU box")
     ap.add_argument("--sources-sha", action="store_true", help="print the sha256 of the kernel sources a PMC record is tied to, and exit")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): the "
+                         "solution (u, nodes, selected associations, score, d, ifinal) and, on one GPU at m <= "
+                         f"{DUMP_AFFINITY_MAX_M}, a seeded sample of columns of the affinity matrix M")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(outdir, g, sol, with_affinity):
+    """What the timed path (affinity build + solve) hands a caller after its last step, as float64 .npy files: the
+    solution, and a fixed, seeded sample of whole columns of M (fetched dense, so only up to DUMP_AFFINITY_MAX_M).
+    Returns {name: shape}."""
+    import numpy as np
+
+    arrays = {
+        "u": sol.u,
+        "nodes": sol.nodes,
+        "selected_associations": g.get_selected_associations(),
+        "score": np.array([sol.score]),
+        "d": np.array([sol.d]),
+        "ifinal": np.array([sol.ifinal]),
+    }
+    m = g.m
+    if with_affinity and m <= DUMP_AFFINITY_MAX_M:
+        k = min(m, max(1, DUMP_AFFINITY_BYTES // (8 * m)))
+        cols = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=k, replace=False))
+        arrays["affinity_columns"] = g.get_affinity_matrix()[:, cols]   # M[:, cols], identity on the diagonal included
+        arrays["affinity_column_index"] = cols
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(problem, args):
@@ -234,6 +277,9 @@ def main():
 
     R = timed_steps(problem, args.steps, args.warmup, not args.no_profile)
     sol, tm, vstats = R["sol"], R["tm"], R["vs"]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else runs on `g`: the state of the last timed step
+        dumped = dump_outputs(args.dump_outputs, g, sol, with_affinity=N == 1 and not args.rank_path)
     aff_ms, solve_ms = R["aff_ms"], R["solve_ms"]
     ms_per_step = R["ms_per_step"]
     gemv_avg_us = R["gemv_us"] / max(1, R["gemv_n"])
@@ -487,6 +533,7 @@ def main():
             "roofline_resident": roofline_resident,
             "scaling_probe": probe,
             "scaling_probe_cfg5": probe_cfg5,
+            "dumped_outputs": dumped,
         }
         if N == 1 and not args.no_cpu_baseline:
             cb, sref = cpu_baseline(problem, args)

@@ -72,14 +72,26 @@ def _worker(rank, world, port, m, out_dir):
 
 @pytest.mark.parametrize("m", [300, 517])
 def test_world_size_2_gloo_sharded_protocol(tmp_path, m):
-    import torch.multiprocessing as mp
+    # stdlib multiprocessing, not torch.multiprocessing: torch imported into the pytest process would stay loaded for the
+    # GPU tests that follow in the same run, and its bundled librccl (same soname, bound to torch's own HIP runtime) would
+    # then be the one libclipper_hip.so's dlopen("librccl.so.1") returns; the workers import torch themselves
+    import multiprocessing as mp
 
     from clipper_amd import synth
     from oracle import clipper_ref as ref
 
     world, port = 2, _free_port()
-    mp.start_processes(_worker, args=(world, port, m, str(tmp_path)), nprocs=world, join=True,
-                       start_method="spawn")
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_worker, args=(r, world, port, m, str(tmp_path))) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    for pr in procs:
+        pr.join(timeout=240)
+    for pr in procs:
+        if pr.is_alive():
+            pr.terminate()
+            pytest.fail("a rank did not terminate")
+        assert pr.exitcode == 0
     r0, r1 = (np.load(tmp_path / f"rank{r}.npz") for r in range(world))
     assert np.array_equal(r0["u"], r1["u"]) and r0["score"] == r1["score"]
     assert np.array_equal(r0["nodes"], r1["nodes"]) and r0["npass"] == r1["npass"]
