@@ -504,7 +504,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
       double f[1] = {0.0};
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        g[e] = valid[e] ? (1 + d) * u[e] - d * s + a[e] + b[e] * d : 0.0;
+        g[e] = valid[e] ? cl_grad(d, u[e], s, a[e], b[e]) : 0.0;
         f[0] += u[e] * g[e];
       }
       block_reduce<1, RS_NWV>(f, red);
@@ -526,8 +526,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
           double al = alpha;
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            double t = u[e] + al * g[e];        // :235
-            t = (t > 0.0) ? t : 0.0;            // :236
+            const double t = cl_project(u[e], al, g[e]);
             x[e][l] = t;
             r[2 * l] += t * t;
             r[2 * l + 1] += t;
@@ -552,7 +551,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
             z += red2[w * 2 * V + 2 * l];
             t1 += red2[w * 2 * V + 2 * l + 1];
           }
-          nrm[l] = (z > 0.0) ? sqrt(z) : 1.0;  // :237 Eigen normalize()
+          nrm[l] = cl_norm(z);
           sx[l] = t1 / nrm[l];
         }
         // :238-242, :253, and the penalty terms :268-274 of candidate 0
@@ -568,7 +567,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
             const double xi = x[e][v] / nrm[v];
             double gv;
             if (v == 0) {
-              gv = (1 + d) * xi - d * sx[0] + an[e] + bn[e] * d;
+              gv = cl_grad(d, xi, sx[0], an[e], bn[e]);
               const double cbu = sx[0] - bn[e] - xi;
               if (valid[e] && cbu > P.eps && xi > P.eps) {
                 q2[2 * V] += 1.0;
@@ -576,7 +575,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
               }
             } else {
               const double gs = y[e][v] / nrm[v];
-              gv = (1 + d) * xi - d * sx[v] + gs;
+              gv = cl_grad_fused(d, xi, sx[v], gs);
             }
             gv = valid[e] ? gv : 0.0;
             gn[e][v] = gv;

@@ -490,8 +490,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
           double al = alpha;
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            double t = UR[e] + al * GR[e];
-            t = (t > 0.0) ? t : 0.0;
+            const double t = cl_project(UR[e], al, GR[e]);
             r2[2 * l] += t * t;
             r2[2 * l + 1] += t;
             al = al * P.beta;
@@ -562,8 +561,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
           double al = alpha;
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            double t = UR[e] + al * GR[e];
-            t = (t > 0.0) ? t : 0.0;
+            double t = cl_project(UR[e], al, GR[e]);
             if (kind == K_PAIR) t = (l == 0) ? UR[e] : 0.0;
             Xt[r * V + l] = t;
             al = al * P.beta;
@@ -587,7 +585,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
           t1 = wave_sum_to_lane63(t1);
         }
         if (lane == 63) {
-          const double nl = (kind == K_TRIAL && z > 0.0) ? sqrt(z) : 1.0;  // Eigen normalize(): only if squaredNorm > 0
+          const double nl = cl_norm(z, kind == K_TRIAL);  // Eigen normalize(): only if squaredNorm > 0
           nrmL[wave] = nl;
           sxL[wave] = (kind == K_TRIAL) ? t1 / nl : 0.0;
         }
@@ -624,18 +622,17 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       double al = alpha;
 #pragma unroll
       for (int v = 0; v < V; ++v) {
-        double t = u_c + al * g_c;
-        t = (t > 0.0) ? t : 0.0;
+        const double t = cl_project(u_c, al, g_c);
         const double nv = rvr_uni(nrmL + v), sv = rvr_uni(sxL + v);
         const double xi = t / nv;
         double gn;
         if (v == 0) {
           an_c = y[0] / nv;
           bn_c = y[V] / nv;
-          gn = (1 + d) * xi - d * sv + an_c + bn_c * d;
+          gn = cl_grad(d, xi, sv, an_c, bn_c);
         } else {
           const double gs = y[v] / nv;
-          gn = (1 + d) * xi - d * sv + gs;
+          gn = cl_grad_fused(d, xi, sv, gs);
         }
         gn_c[v] = gn;
         if (cown && rpos < 0 && (xi > 0.0 || gn > 0.0)) cbits |= 1u << v;
@@ -649,7 +646,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
         an_c = y[0];
         bn_c = y[V];
       } else if (cown) {  // K_BUILD (:219)
-        gn_c[0] = (1 + d) * u_c - d * s + a_c + b_c * d;
+        gn_c[0] = cl_grad(d, u_c, s, a_c, b_c);
         if (rpos < 0 && (u_c > 0.0 || gn_c[0] > 0.0)) cbits = 1u;
       }
     }
@@ -819,9 +816,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             if (e == 0 || two) {
-              double t = UR[e] + al * GR[e];
-              t = (t > 0.0) ? t : 0.0;
-              const double xi = t / nv;
+              const double xi = cl_project(UR[e], al, GR[e]) / nv;
               const double gv = gR[e][v];
               bool live = false, pen = false;
               if (rok[e]) {
@@ -830,10 +825,10 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
                 dv[1] += du * du;
                 live = xi > 0.0 || gv > 0.0;
                 if (v == 0) {
-                  const double cbu = rvr_uni(sxL) - bnR[e] - xi;
-                  if (cbu > P.eps && xi > P.eps) {
+                  const double cbu = cl_pen_cbu(rvr_uni(sxL), bnR[e], xi);
+                  if (cl_pen_in(cbu, xi, P.eps)) {
                     pen = true;
-                    dv[2] += fabs((anR[e] + xi) / cbu);
+                    dv[2] += cl_pen_ratio(anR[e], xi, cbu);
                   }
                 }
               }
@@ -864,15 +859,11 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
             lr = iv[0];
             no = iv[2];
             s = rvr_uni(sxL + v);
-            double t = u_c + al * g_c;
-            t = (t > 0.0) ? t : 0.0;
-            u_c = t / nv;
+            u_c = cl_project(u_c, al, g_c) / nv;
             g_c = gn_c[v];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-              double t2 = UR[e] + al * GR[e];
-              t2 = (t2 > 0.0) ? t2 : 0.0;
-              UR[e] = rok[e] ? t2 / nv : 0.0;
+              UR[e] = rok[e] ? cl_project(UR[e], al, GR[e]) / nv : 0.0;
               GR[e] = rok[e] ? gR[e][v] : 0.0;
             }
           }
@@ -924,7 +915,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       for (int e = 0; e < 2; ++e) {
         bool live = false;
         if (rok[e]) {
-          const double gi = (1 + d) * UR[e] - d * s + aR[e] + bR[e] * d;  // :219
+          const double gi = cl_grad(d, UR[e], s, aR[e], bR[e]);  // :219
           GR[e] = gi;
           dv[0] += UR[e] * gi;  // :220
           live = UR[e] > 0.0 || gi > 0.0;

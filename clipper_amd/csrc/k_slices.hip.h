@@ -224,11 +224,9 @@ struct SliceXStage {
         double al = W.alpha0;
 #pragma unroll
         for (int l = 0; l < XL; l += 2) {
-          double t0 = wu[i] + al * wg[i];
-          t0 = (t0 > 0.0) ? t0 : 0.0;
+          const double t0 = cl_project(wu[i], al, wg[i]);
           al = al * W.beta;
-          double t1 = wu[i] + al * wg[i];
-          t1 = (t1 > 0.0) ? t1 : 0.0;
+          const double t1 = cl_project(wu[i], al, wg[i]);
           al = al * W.beta;
           if (p < PIECES) *reinterpret_cast<double2*>(xs + p * XP + l) = make_double2(t0, t1);
         }

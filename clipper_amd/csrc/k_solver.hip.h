@@ -1,4 +1,4 @@
-// k_solver.hip.h — solver state, the decision at the head of a pass (decide), k_init, k_tail, k_scal_fold
+// k_solver.hip.h — solver state, the update rules, the decision at the head of a pass (decide), k_init, k_tail, k_scal_fold
 // Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
 #pragma once
 
@@ -196,6 +196,56 @@ struct SolverParams {
   double tol_u, tol_F, beta, eps;
   int32_t maxiniters, maxoliters, maxlsiters;
 };
+
+// ------------------------------------------------------------------------------------------
+// THE UPDATE RULES of findDenseClique (clipper.cpp:193-280)
+//
+// The streaming launches (decide, iteration_head, k_tail, the window staging of k_slices,
+// k_sub_enter), the resident solver and the resident solver on a row view must take the same
+// decisions on the same bits; they state these rules through the helpers below. The build has
+// -ffp-contract=off: each expression rounds as written here, operand order and association are
+// part of the rule. The helpers take values and hold no branches: each inlines to exactly the
+// instructions it replaced, in every kernel (checked against a device-only build, code and
+// register counts). Where routing a site through a helper changed the generated code, the site
+// still spells the rule out: the trial walk (:244-248), the end of the inner loop (:261), the
+// penalty update (:276-280) and the end-of-solve publication in every route; the penalty terms
+// under a `valid` / `rok` guard in the resident solvers; k_tail's PH_BUILD gradient; the
+// leaving window's norms in k_rv_resident.
+// ------------------------------------------------------------------------------------------
+
+// candidate step: max(u + al g, 0)                                                    (:235-236)
+__device__ __forceinline__ double cl_project(double u, double al, double g) {
+  const double t = u + al * g;
+  return (t > 0.0) ? t : 0.0;
+}
+
+// norm of a candidate from its squared norm: Eigen's normalize() divides only if squaredNorm > 0 (:237);
+// use = false: a vector that is not a window candidate, norm 1
+__device__ __forceinline__ double cl_norm(double z, bool use = true) { return (use && z > 0.0) ? sqrt(z) : 1.0; }
+
+// gradient (1 + d) x - d sum(x) + M_off x + d C_off x, with a = M_off x and b = C_off x apart (:219, :238-241) ...
+__device__ __forceinline__ double cl_grad(double d, double x, double s, double a, double b) {
+  return (1 + d) * x - d * s + a + b * d;
+}
+// ... or fused, gs = (M_off + d C_off) x: window candidates 1 .. V-1, whose a and b are never needed apart
+__device__ __forceinline__ double cl_grad_fused(double d, double x, double s, double gs) {
+  return (1 + d) * x - d * s + gs;
+}
+
+// penalty term of one element (u, a = (M_off u)_i, b = (C_off u)_i), s = sum(u): with cbu = cl_pen_cbu(s, b, u)
+// (:268) the element counts iff cl_pen_in(cbu, u, eps) (:269) and adds cl_pen_ratio(a, u, cbu) (:271-274); the
+// initial penalty (:202-208) sums the same terms without the absolute value, cl_pen_ratio_init
+__device__ __forceinline__ double cl_pen_cbu(double s, double b, double u) { return s - b - u; }
+__device__ __forceinline__ bool cl_pen_in(double cbu, double u, double eps) { return cbu > eps && u > eps; }
+__device__ __forceinline__ double cl_pen_ratio(double a, double u, double cbu) { return fabs((a + u) / cbu); }
+__device__ __forceinline__ double cl_pen_ratio_init(double a, double u, double cbu) { return (a + u) / cbu; }
+
+// The live sub-problem (k_subproblem.hip.h): no column outside it can come back to life under a candidate with raw
+// sums (z, s) = (||x||^2, sum x) while d^2 s^2 >= kappa (1 + d)^2 N z, N the stored entries among the live rows of
+// any column outside it. kappa = SUB_ENTER_MARGIN to hand the solve over, SUB_STAY_MARGIN to stay on it (any
+// factor > 1 is exact; the gap is hysteresis).
+constexpr double SUB_ENTER_MARGIN = 1.10;
+constexpr double SUB_STAY_MARGIN = 1.01;
 
 constexpr int TAIL_THREADS = 256;  // elements per tail workgroup
 constexpr int TAIL_WAVES = TAIL_THREADS / 64;
@@ -555,7 +605,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
   bool sub_ok = true;
   auto sub_bound = [&](const double* sums, int nb) {
     if (A.sub_state == 0) return;
-    const double kap = (A.sub_state == 1 ? 1.10 : 1.01) * A.sub_ncol;  // SUB_ENTER_MARGIN / SUB_STAY_MARGIN
+    const double kap = (A.sub_state == 1 ? SUB_ENTER_MARGIN : SUB_STAY_MARGIN) * A.sub_ncol;
     const double lhs = d * d, rhs = (1.0 + d) * (1.0 + d) * kap;
 #pragma unroll
     for (int l = 0; l < V; ++l) {
@@ -613,7 +663,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
         // (the live sub-problem's bound for that window, from the norms the state carries: z = nrm^2, s = sx nrm — this
         // decision may be the first one that is asked, e.g. right after a view and its sub-problem were built)
         if (A.sub_state != 0) {
-          const double kap = (A.sub_state == 1 ? 1.10 : 1.01) * A.sub_ncol;
+          const double kap = (A.sub_state == 1 ? SUB_ENTER_MARGIN : SUB_STAY_MARGIN) * A.sub_ncol;
           const double rhs = (1.0 + d) * (1.0 + d) * kap;
 #pragma unroll
           for (int l = 0; l < V; ++l) {
@@ -637,8 +687,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
         if (writer && tid == 0) {  // the norms are only recorded (for the tail): no other workgroup needs them
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            const double z = sums[V * NR + 2 * l];
-            const double nl = (z > 0.0) ? sqrt(z) : 1.0;  // Eigen normalize(): only if squaredNorm > 0
+            const double nl = cl_norm(sums[V * NR + 2 * l]);
             stash->nrm[l] = nl;
             stash->sx[l] = sums[V * NR + 2 * l + 1] / nl;
           }
@@ -679,8 +728,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
           if (writer && tid == 0) {
 #pragma unroll
             for (int l = 0; l < V; ++l) {
-              const double z = sums[jstar * NR + 2 + 2 * l];
-              const double nl = (z > 0.0) ? sqrt(z) : 1.0;
+              const double nl = cl_norm(sums[jstar * NR + 2 + 2 * l]);
               stash->nrm[l] = nl;
               stash->sx[l] = sums[jstar * NR + 3 + 2 * l] / nl;
             }
@@ -702,8 +750,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
         if (writer && tid == 0) {
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            const double z = sums[2 + 2 * l];
-            const double nl = (z > 0.0) ? sqrt(z) : 1.0;
+            const double nl = cl_norm(sums[2 + 2 * l]);
             stash->nrm[l] = nl;
             stash->sx[l] = sums[3 + 2 * l] / nl;
           }
@@ -770,10 +817,10 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
             bv[k] = cb_[i];
           }
           VEC_EACH(k, i, base) {
-            const double cbu = s - bv[k] - uv[k];  // :202
-            if (cbu > P.eps && uv[k] > P.eps) {    // :203
+            const double cbu = cl_pen_cbu(s, bv[k], uv[k]);
+            if (cl_pen_in(cbu, uv[k], P.eps)) {
               ca[0] += 1.0;
-              ca[1] += (av[k] + uv[k]) / cbu;  // :205-208
+              ca[1] += cl_pen_ratio_init(av[k], uv[k], cbu);
             }
           }
         }
@@ -794,10 +841,10 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
             bv[k] = cb_[i];
           }
           VEC_EACH(k, i, base) {
-            const double cbu = s - bv[k] - uv[k];  // :268
-            if (cbu > P.eps && uv[k] > P.eps) {    // :269
+            const double cbu = cl_pen_cbu(s, bv[k], uv[k]);
+            if (cl_pen_in(cbu, uv[k], P.eps)) {
               ca[0] += 1.0;
-              ca[1] += fabs((av[k] + uv[k]) / cbu);  // :271-274
+              ca[1] += cl_pen_ratio(av[k], uv[k], cbu);
             }
           }
         }
@@ -1045,8 +1092,7 @@ __device__ __forceinline__ bool iteration_head(const SolveArgs& A, double* lds,
           double al = L.alpha;
 #pragma unroll
           for (int l = 0; l < V; ++l) {
-            double t = ui + al * gi;  // clipper.cpp:235-236
-            t = (t > 0.0) ? t : 0.0;
+            const double t = cl_project(ui, al, gi);
             r[2 * l] += t * t;
             r[2 * l + 1] += t;
             al = al * beta;
@@ -1058,7 +1104,7 @@ __device__ __forceinline__ bool iteration_head(const SolveArgs& A, double* lds,
 #pragma unroll
         for (int l = 0; l < V; ++l) {
           const double z = (all_rows ? 0.0 : stash->nrm[l]) + r[2 * l], sm = (all_rows ? 0.0 : stash->sx[l]) + r[2 * l + 1];
-          const double nl = (z > 0.0) ? sqrt(z) : 1.0;  // Eigen normalize(): only if squaredNorm > 0 (:237)
+          const double nl = cl_norm(z);
           stash->nrm[l] = nl;
           stash->sx[l] = sm / nl;
         }
@@ -1268,8 +1314,7 @@ __global__ __launch_bounds__(TAIL_THREADS * (FUSED_REDUCE ? TAIL_SPLIT : 1)) voi
       double al = 1.0;
 #pragma unroll
       for (int l = 0; l < V; ++l) {
-        double t = ui + al * gi;
-        t = (t > 0.0) ? t : 0.0;
+        const double t = cl_project(ui, al, gi);
         row[l] = t;
         r[2 + 2 * l] = t * t;
         r[3 + 2 * l] = t;
@@ -1286,26 +1331,25 @@ __global__ __launch_bounds__(TAIL_THREADS * (FUSED_REDUCE ? TAIL_SPLIT : 1)) voi
       } else {  // candidate v of the window the pass staged: the same expression, the same bits
         double al = alpha;
         for (int l = 0; l < v; ++l) al = al * beta;
-        const double t = ui + al * pt_arr(A, V, ubp, ubv, 1)[i];
-        xraw = (t > 0.0) ? t : 0.0;
+        xraw = cl_project(ui, al, pt_arr(A, V, ubp, ubv, 1)[i]);
       }
       const double xi = xraw / nrmv;  // clipper.cpp:237
       double gn;
       if (v == 0) {
         // candidate 0: a and b apart, exactly the reference's expression (:238-241)
         const double an = p0 / nrmv, bn = p1 / nrmv;
-        gn = (1 + d) * xi - d * sxv + an + bn * d;
+        gn = cl_grad(d, xi, sxv, an, bn);
         A.cab[i] = an;  // (a, b) of the current point if candidate 0 is accepted
         A.cab[A.mp + i] = bn;
         // its penalty terms (:268-274), in case the inner loop ends with it
-        const double cbu = sxv - bn - xi;
-        if (cbu > A.prm.eps && xi > A.prm.eps) {
+        const double cbu = cl_pen_cbu(sxv, bn, xi);
+        if (cl_pen_in(cbu, xi, A.prm.eps)) {
           r[NR + 2 * V] = 1.0;
-          r[NR + 2 * V + 1] = fabs((an + xi) / cbu);
+          r[NR + 2 * V + 1] = cl_pen_ratio(an, xi, cbu);
         }
       } else {
         const double gs = p0 / nrmv;  // (M_off + d*C_off) x
-        gn = (1 + d) * xi - d * sxv + gs;
+        gn = cl_grad_fused(d, xi, sxv, gs);
       }
       pt_arr(A, V, ubp ^ 1, v, 0)[i] = xi;  // becomes (u, gradF) if candidate v is accepted
       pt_arr(A, V, ubp ^ 1, v, 1)[i] = gn;
@@ -1318,8 +1362,7 @@ __global__ __launch_bounds__(TAIL_THREADS * (FUSED_REDUCE ? TAIL_SPLIT : 1)) voi
       double al = 1.0;
 #pragma unroll
       for (int l = 0; l < V; ++l) {
-        double t = xi + al * gn;
-        t = (t > 0.0) ? t : 0.0;
+        const double t = cl_project(xi, al, gn);
         row[l] = t;
         r[2 + 2 * l] = t * t;
         r[3 + 2 * l] = t;
@@ -1336,8 +1379,7 @@ __global__ __launch_bounds__(TAIL_THREADS * (FUSED_REDUCE ? TAIL_SPLIT : 1)) voi
         for (int l = 0; l < V; ++l) al = al * beta;
 #pragma unroll
         for (int l = 0; l < V; ++l) {
-          double t = ui + al * gi;
-          t = (t > 0.0) ? t : 0.0;
+          const double t = cl_project(ui, al, gi);
           row2[l] = t;
           r[NR + 2 * l] = t * t;
           r[NR + 2 * l + 1] = t;

@@ -22,8 +22,9 @@
 // counts among its rows are read off the view's slice headers (k_sub_colcount), S = view rows + every column with
 // more than N0 = 0.4 sum(u)^2 entries (k_sub_flags; its list by k_rv_scan / k_rv_scatter), and the associations of
 // S become a CLIPPER problem of their own: their points gathered (k_sub_gather_points), M[S,S] scored by the same
-// symmetric fill, its own vectors. The decision (k_solver.hip.h: decide) then checks the inequality with
-// N = the largest count outside S for every candidate of every window it plans:
+// symmetric fill, its own vectors. The decision (k_solver.hip.h: decide, sub_bound; the margins SUB_ENTER_MARGIN /
+// SUB_STAY_MARGIN) then checks the inequality with N = the largest count outside S for every candidate of every
+// window it plans:
 //   * on the full problem, when it holds with a margin the solve goes on HOLD (hold = 2) and the host hands the
 //     solve over: a decide-only iteration leaves the pending pass prepared, k_sub_enter gathers the point and the
 //     state, and the same launches (k_gemv_slices, k_tail) continue on the sub-problem's arrays;
@@ -45,8 +46,6 @@
 namespace clipper_hip {
 
 constexpr double SUB_THETA = 0.4;          // N0 = SUB_THETA * sum(u)^2: columns with more entries among the view's rows join S
-constexpr double SUB_ENTER_MARGIN = 1.10;  // the inequality with this factor on N: hand the solve over
-constexpr double SUB_STAY_MARGIN = 1.01;   // ... and with this one: stay (any factor > 1 is exact; the gap is hysteresis)
 
 // cnt[c] = 4 x the quads column c holds in the view's slices: at least its stored entries among the view's rows.
 // One wave per column group, a lane per column, eight headers in flight.
@@ -191,8 +190,7 @@ __global__ __launch_bounds__(256) void k_sub_enter(const SolverState* __restrict
       double row[VS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       double al = pst->alpha;
       for (int l = 0; l < V; ++l) {
-        const double t = ui + al * gi;  // clipper.cpp:235-236
-        row[l] = (t > 0.0) ? t : 0.0;
+        row[l] = cl_project(ui, al, gi);
         al = al * beta;
       }
       store_row(ctab + (static_cast<int64_t>(pst->sel) * cmp + i) * VS, row);

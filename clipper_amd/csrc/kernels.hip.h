@@ -25,7 +25,9 @@
 //   k_affinity_sym: the same scores as k_affinity_*, upper block triangle + mirrored stores
 //
 // Files (all in namespace clipper_hip):
-//   k_solver.hip.h    solver state, decide (the head of every pass launch), k_init, k_tail, k_scal_fold
+//   k_solver.hip.h    solver state, the update rules of findDenseClique (cl_project, cl_norm, cl_grad, the penalty
+//                     terms, the live sub-problem's margins), decide (the head of every pass launch), k_init,
+//                     k_tail, k_scal_fold
 //   k_gemv.hip.h      the dense pass: k_gemv, k_gemv_plain, k_reduce_pass (column shards), k_reduce, k_spread
 //   k_slices.hip.h    the compressed storage: layout, the pass on it (k_gemv_slices), packers, k_slice_expand
 //   k_csc.hip.h       producers of the slices: emission from the fill kernel's LDS image, groups

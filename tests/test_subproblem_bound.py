@@ -19,8 +19,8 @@ from clipper_amd import synth
 from oracle import clipper_ref as ref
 
 THETA = 0.4       # k_subproblem.hip.h: SUB_THETA
-KAPPA_ENTER = 1.10
-KAPPA_STAY = 1.01
+KAPPA_ENTER = 1.10  # k_solver.hip.h: SUB_ENTER_MARGIN
+KAPPA_STAY = 1.01   # k_solver.hip.h: SUB_STAY_MARGIN
 
 
 def _iterate(Ms, Cs, u0, p, hook):
