@@ -737,7 +737,13 @@ int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, 
 // | ||pr-pc|| - ||qr-qc|| | for coordinates of magnitude <= maxabs in dimension d
 // (input rounding 2^-24 each, d+2 roundings in the norm, both norms, the subtraction:
 // < 50 * 2^-24 * maxabs at d = 3; 128*(d+1) * 2^-24 leaves a 10x margin), rounded up.
+// Infinite where the square-root-free form's fp32 products could overflow: its squared lengths reach 4 d maxabs^2
+// each, t and t^2 up to (8 d maxabs^2)^2 — from maxabs ~ 6e8 on at d = 3. Every pair is then scored exactly, up to
+// maxabs ~ 1e18: beyond, the fp32 squares themselves overflow, t and the strip form's root difference are NaN and
+// both forms reject. (The strip form alone would stay finite to ~1e19: there, this costs exact scores, not results.)
 float guarded_threshold(double eps, double maxabs, int d) {
+  const double smax = 8.0 * d * maxabs * maxabs;
+  if (!(smax * smax < 1.0e38)) return std::numeric_limits<float>::infinity();
   const double guard = std::ldexp(128.0 * (d + 1), -24) * maxabs;
   const double t = eps + guard;
   if (!(t < 3.0e38)) return std::numeric_limits<float>::infinity();
