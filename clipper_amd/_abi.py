@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("CLIPPER_HIP_LIB") or os.path.join(_HERE, "lib", "libc
 
 STORE_F32, STORE_F64, STORE_F32_CSC, STORE_F64_CSC = 0, 1, 2, 3
 ROUNDING_NONZERO, ROUNDING_DSD, ROUNDING_DSD_HEU = 0, 1, 2
+MC_EXACT, MC_HEU, MC_KCORE = 0, 1, 2  # CLIPPER_HIP_MC_* = maxclique::Method
 
 # every symbol include/clipper_hip.h declares (checked by tests/test_abi_exports.py)
 EXPORTED_SYMBOLS = [
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_solve_staged", "clipper_hip_debug_stamps", "clipper_hip_comm_init_callback",
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
+    "clipper_hip_max_clique", "clipper_hip_core_numbers",
 ]
 
 
@@ -105,6 +107,16 @@ class ViewStats(C.Structure):
         ("sub_entries", C.c_int64), ("sub_leaves", C.c_int64), ("sub_passes", C.c_int64),
         ("sub_rows", C.c_int64), ("sub_bytes", C.c_int64), ("sub_build_ms", C.c_double),
         ("sub_pass_avg_us", C.c_double), ("sub_pass_samples", C.c_int64), ("sub_dense", C.c_int64),
+    ]
+
+
+class MaxCliqueInfo(C.Structure):
+    """clipper_maxclique_info_t (include/clipper_hip.h): what clipper_hip_max_clique reports."""
+
+    _fields_ = [
+        ("num_nodes", C.c_int32), ("max_core", C.c_int32), ("heuristic_size", C.c_int32), ("timed_out", C.c_int32),
+        ("edges", C.c_int64), ("roots_searched", C.c_int64), ("roots_pruned", C.c_int64), ("bb_nodes", C.c_int64),
+        ("seconds", C.c_double),
     ]
 
 
@@ -196,6 +208,8 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_precision_recall.argtypes = [ip, i64, ip, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.clipper_hip_estimate_rigid_transform.argtypes = [dp, i64, dp, i64, ip, i64, dp]
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
+    L.clipper_hip_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
+    L.clipper_hip_core_numbers.argtypes = [vp, ip]
     _lib = L
     return L
 
@@ -418,6 +432,27 @@ class HipClipper:
             k = self.L.clipper_hip_densest_subgraph(self.h, _ip(Sa), len(Sa), _ip(out), len(out))
         self._check(min(k, 0))
         return out[:k].copy()
+
+    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0):
+        """maxclique::solve on the consistency graph (C != 0): MC_EXACT (ROBIN*), MC_HEU or MC_KCORE (ROBIN).
+        Returns (nodes ascending, MaxCliqueInfo); the nodes become the context's selection. time_limit in seconds
+        (<= 0: none)."""
+        info = MaxCliqueInfo()
+        self._check(self.L.clipper_hip_max_clique(self.h, int(method), float(time_limit), C.byref(info)))
+        out = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
+        k = self.L.clipper_hip_get_nodes(self.h, _ip(out), len(out))
+        self._check(min(k, 0))
+        nodes = out[:k].copy()
+        # clipper.cpp:92-96: the solution of a max-clique call
+        self.soln = Solution(t=info.seconds, ifinal=0, nodes=nodes, u=np.zeros(self.m), score=-1.0)
+        return nodes, info
+
+    def core_numbers(self) -> np.ndarray:
+        """The core number of every vertex of the consistency graph."""
+        n = int(self.L.clipper_hip_num_associations(self.h))
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.L.clipper_hip_core_numbers(self.h, _ip(out)))
+        return out[:n].copy()
 
     def set_window(self, window: int):
         """Line-search window (0 = automatic, 1 | 4 | 6 | 8); effective from the next build."""

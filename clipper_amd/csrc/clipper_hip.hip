@@ -54,6 +54,7 @@ using namespace clipper_hip;
 #include "host_rv_resident.hpp"
 #include "host_subproblem.hpp"
 #include "host_registration.hpp"
+#include "host_maxclique.hpp"
 
 // ============================================================================================
 // brute-force nearest neighbours: launch of the two kernels for one (K, D)
@@ -1233,6 +1234,18 @@ int clipper_hip_densest_subgraph(clipper_hip_t* h, const int32_t* S, int32_t k, 
   if (capacity < n) return fail(CLIPPER_HIP_E_INVALID, "capacity %d < %d nodes", capacity, n);
   if (n) std::memcpy(nodes_out, nodes.data(), static_cast<size_t>(n) * sizeof(int32_t));
   return n;
+} CLIPPER_HIP_GUARD_INT
+
+// ---- maximum clique of the consistency graph (maxclique::solve, host_maxclique.hpp) ---------------------------
+
+int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, clipper_maxclique_info_t* info) try {
+  if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return clipper_hip_max_clique_impl(h, method, time_limit_s, info);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out) try {
+  if (!h || !core_out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return clipper_hip_core_numbers_impl(h, core_out);
 } CLIPPER_HIP_GUARD_INT
 
 // ---- putative associations (before the path): brute-force nearest neighbours -------------------

@@ -333,14 +333,26 @@ void CLIPPER::solve(const VectorXd& _u0) {
   stats_.d = info.d;
 }
 
-// Without PMC the reference prints a warning and returns an empty clique
-// (maxclique.cpp:141-145); this build never has PMC.
-void CLIPPER::solveAsMaximumClique(const maxclique::Params&) {
-  std::cout << "PMC is not built. Maximum clique solver is unavailable." << std::endl;
-  soln_.t = 0;
+// clipper.cpp:82-97 + maxclique::solve (maxclique.cpp): the maximum clique of the consistency graph C - I, on the
+// device (clipper_hip_max_clique). params.threads is accepted and ignored (the device decides
+// its own parallelism); params.time_limit bounds the search (seconds).
+void CLIPPER::solveAsMaximumClique(const maxclique::Params& params) {
+  const int method = params.method == maxclique::Method::EXACT ? CLIPPER_HIP_MC_EXACT
+                     : params.method == maxclique::Method::HEU ? CLIPPER_HIP_MC_HEU
+                                                               : CLIPPER_HIP_MC_KCORE;
+  clipper_maxclique_info_t info{};
+  check(clipper_hip_max_clique(handle(), method, static_cast<double>(params.time_limit), &info), "solveAsMaximumClique");
+  std::vector<int> nodes(static_cast<size_t>(info.num_nodes));
+  if (info.num_nodes > 0) check(clipper_hip_get_nodes(h_, nodes.data(), info.num_nodes), "solveAsMaximumClique (nodes)");
+  if (params.verbose)
+    std::cout << "maxclique: m = " << clipper_hip_num_associations(h_) << ", edges = " << info.edges
+              << ", K = " << info.max_core << ", heuristic = " << info.heuristic_size << ", clique = " << info.num_nodes
+              << (info.timed_out ? " (time limit)" : "") << ", roots searched / pruned = " << info.roots_searched
+              << " / " << info.roots_pruned << ", " << info.seconds * 1e3 << " ms" << std::endl;
+  soln_.t = info.seconds;
   soln_.ifinal = 0;
-  soln_.nodes.clear();
-  soln_.u = VectorXd::Zero(clipper_hip_num_associations(handle()));
+  std::swap(soln_.nodes, nodes);
+  soln_.u = VectorXd::Zero(clipper_hip_num_associations(h_));
   soln_.score = -1;
 }
 

@@ -1,0 +1,471 @@
+// k_maxclique.hip.h — the maximum-clique solver behind CLIPPER::solveAsMaximumClique:
+// the adjacency of the consistency graph as row bitsets, its core numbers, the greedy clique (HEU) and the
+// bitset branch and bound (EXACT). Host side: host_maxclique.hpp.
+// Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
+//
+// The graph: vertices 0..m-1, edge (i, j), i != j, exactly when C(i, j) != 0. G[i][w] bit b = edge (i, 64 w + b),
+// nw = ceil(m / 64) words per row, bits at or past m are zero.
+//
+// Every launch does a bounded amount of work (a budget in row-word operations per wave, or per workgroup for the
+// peel) and leaves its state in device memory: the host loop resumes it with the next launch and checks the
+// caller's time limit between launches. No workgroup ever waits for another: work is taken through an atomicAdd
+// head, the incumbent is one atomicMax word.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "k_slices.hip.h"
+
+namespace clipper_hip {
+
+// device state of one max-clique call (zeroed by the host before each phase uses its fields)
+struct McCtl {
+  int32_t k;            // core peel: the current level
+  int32_t removed;      // core peel: vertices peeled so far
+  int32_t head;         // HEU seeds / EXACT roots taken
+  int32_t active;       // EXACT: slots that left a root unfinished at the end of the launch
+  unsigned long long key;  // incumbent: size << 32 | tie field (HEU: ~seed; EXACT: 0xFFFFFFFE - pos, HEU's clique 0xFFFFFFFF)
+  unsigned long long roots_pruned, roots_searched, bb_nodes;
+  int32_t overflow;     // EXACT: a branch deeper than the clique-size bound (cannot happen; checked, never silent)
+  int32_t pad[3];
+};
+
+// one EXACT wave's resumable state
+struct McSlot {
+  int32_t root;    // vertex being searched, -1 = none
+  int32_t depth;   // top level of its stack
+  int32_t pad0, pad1;
+  unsigned long long rec_key;  // the key of the clique this slot recorded last (0: none)
+};
+
+constexpr int MC_PEEL_THREADS = 1024;
+constexpr int MC_PEEL_FCAP = 2048;  // vertices peeled per round at most (the rest wait for the next round)
+
+// ---- wave helpers (one wave = one workgroup of 64 lanes in the HEU / EXACT kernels) ---------------------------
+__device__ __forceinline__ unsigned long long mc_wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int mc_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int mc_wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const int t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long mc_load_key(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int mc_load_i32(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// First non-zero word of X[lo, hi) (LDS, one wave), or -1. The word index is wave-uniform.
+__device__ __forceinline__ int mc_first_word(const uint64_t* X, int lo, int hi, int lane) {
+  for (int base = lo; base < hi; base += 64) {
+    const int w = base + lane;
+    const uint64_t x = (w < hi) ? X[w] : 0ull;
+    const uint64_t msk = __ballot(x != 0ull);
+    if (msk) return base + __ffsll(static_cast<unsigned long long>(msk)) - 1;
+  }
+  return -1;
+}
+
+// ---- adjacency ---------------------------------------------------------------------------------------------
+// From the slices of a one-shard store (k_slices.hip.h): one wave per slice, lane = column c. Both triangles are
+// stored, so column c's entries are row c of the graph. G is zeroed by the caller; a lane writes only words of
+// its own row, the atomic OR keeps the chunks of one column group (other waves, other words) independent.
+template <typename VT, int H>
+__global__ __launch_bounds__(256) void k_mc_adj_slices(SliceView M, uint64_t* __restrict__ G, int64_t nw,
+                                                       int64_t m) {
+  constexpr int QB = 4 * static_cast<int>(sizeof(VT));
+  constexpr int R = SL_SUB * H;
+  const int lane = threadIdx.x & 63;
+  const int64_t s = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (s >= static_cast<int64_t>(M.ncg) * M.nchunks) return;
+  const int cg = static_cast<int>(s / M.nchunks), k = static_cast<int>(s - static_cast<int64_t>(cg) * M.nchunks);
+  const int64_t c = static_cast<int64_t>(cg) * SL_W + lane;
+  const int64_t r0 = static_cast<int64_t>(k) * R;
+  SliceHead<H> hd;
+  hd.load(static_cast<gbytes_t>((gbytes_t)M.data + 16 * M.Pre[s]), lane);
+  const int maxq = __builtin_amdgcn_readfirstlane(hd.maxq);
+  int tot = 0;
+#pragma unroll
+  for (int h = 0; h < H; ++h) tot += hd.nq[h];
+  gbytes_t fbase = hd.sp + 16 + H * 64 + sl_so_bytes(maxq);
+  for (int q = 0; q < maxq; ++q) {
+    const bool active = q < tot;
+    const uint64_t mask = __ballot(active);
+    const int cnt = __popcll(mask);
+    if (active && c < m) {
+      const uint32_t rank = sl_lane_rank(mask);
+      SliceQuad<VT> vq;
+      vq.load(fbase + rank * QB);
+      const uint32_t rq = *reinterpret_cast<const CLIPPER_GLOBAL uint32_t*>(fbase + cnt * QB + rank * 4);
+      int rowbase = 0, edge = hd.nq[0];
+#pragma unroll
+      for (int h = 1; h < H; ++h) {
+        rowbase = (q >= edge) ? h * SL_SUB : rowbase;
+        edge += hd.nq[h];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (vq.v[e] != VT(0)) {
+          const int64_t row = r0 + rowbase + ((rq >> (8 * e)) & 255u);
+          if (row < m && row != c)
+            atomicOr(reinterpret_cast<unsigned long long*>(G + c * nw + (row >> 6)), 1ull << (row & 63));
+        }
+    }
+    fbase += cnt * QB + ((cnt * 4 + 15) & ~15);
+  }
+}
+
+// From a dense one-shard store S[j][c] (row pitch ld; M's values or the explicit C): thread = (row c, word w),
+// bit b set when S[64 w + b][c] != 0. The loads of one j are coalesced over c. Writes every word of G.
+template <typename T>
+__global__ __launch_bounds__(256) void k_mc_adj_dense(const T* __restrict__ S, int64_t ld, int64_t m, int64_t nw,
+                                                      uint64_t* __restrict__ G) {
+  const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (c >= m) return;
+  for (int64_t w = blockIdx.y; w < nw; w += gridDim.y) {
+    uint64_t word = 0;
+    const int64_t j0 = w * 64;
+    const int nb = static_cast<int>((m - j0) < 64 ? (m - j0) : 64);
+    for (int b = 0; b < nb; ++b)
+      if (S[(j0 + b) * ld + c] != T(0) && j0 + b != c) word |= 1ull << b;
+    G[c * nw + w] = word;
+  }
+}
+
+// degree of every vertex: one wave per row
+__global__ __launch_bounds__(256) void k_mc_degree(const uint64_t* __restrict__ G, int64_t nw, int64_t m,
+                                                   int32_t* __restrict__ deg) {
+  const int lane = threadIdx.x & 63;
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (v >= m) return;
+  int d = 0;
+  for (int64_t w = lane; w < nw; w += 64) d += __popcll(G[v * nw + w]);
+  d = mc_wave_sum(d);
+  if (lane == 0) deg[v] = d;
+}
+
+// ---- core numbers: level-synchronous peeling (Batagelj-Zaversnik levels), one workgroup -------------------------
+// Round: every alive vertex with degree <= k is peeled with core number k (at most MC_PEEL_FCAP of them; the rest
+// in the next round), the degrees of its alive neighbours drop by one; a round that peels nothing raises k to the
+// least alive degree. The result is the core number of every vertex, whatever the order within a round. The
+// alive set lives in LDS for the launch and in `alive_g` between launches; `deg` is the working degree (updated
+// by atomics, read with L1-bypassing loads); the launch returns after `budget` row-word operations at a round's end.
+__global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(const uint64_t* __restrict__ G, int64_t nw,
+                                                                  int32_t m, int32_t* deg,
+                                                                  int32_t* __restrict__ core,
+                                                                  uint64_t* __restrict__ alive_g, McCtl* ctl,
+                                                                  long long budget) {
+  extern __shared__ uint64_t mc_alive[];
+  __shared__ int32_t fr[MC_PEEL_FCAP];
+  __shared__ int32_t nf_s, mindeg_s;
+  const int tid = threadIdx.x;
+  for (int64_t w = tid; w < nw; w += MC_PEEL_THREADS) mc_alive[w] = alive_g[w];
+  int k = ctl->k, removed = ctl->removed;
+  long long work = 0;
+  __syncthreads();
+  while (removed < m && work < budget) {
+    if (tid == 0) {
+      nf_s = 0;
+      mindeg_s = 0x7fffffff;
+    }
+    __syncthreads();
+    for (int v = tid; v < m; v += MC_PEEL_THREADS) {
+      if (!((mc_alive[v >> 6] >> (v & 63)) & 1ull)) continue;
+      const int d = mc_load_i32(deg + v);
+      if (d <= k) {
+        const int slot = atomicAdd(&nf_s, 1);
+        if (slot < MC_PEEL_FCAP) {
+          fr[slot] = v;
+          core[v] = k;
+          continue;
+        }
+      }
+      atomicMin(&mindeg_s, d);
+    }
+    __syncthreads();
+    const int n = nf_s < MC_PEEL_FCAP ? nf_s : MC_PEEL_FCAP;
+    if (n == 0) {
+      k = mindeg_s > k ? mindeg_s : k;  // (nothing alive at or below k)
+      __syncthreads();
+      continue;
+    }
+    for (int i = tid; i < n; i += MC_PEEL_THREADS)
+      atomicAnd(reinterpret_cast<unsigned long long*>(&mc_alive[fr[i] >> 6]), ~(1ull << (fr[i] & 63)));
+    __syncthreads();
+    const int64_t items = static_cast<int64_t>(n) * nw;
+    for (int64_t it = tid; it < items; it += MC_PEEL_THREADS) {
+      const int f = fr[it / nw];
+      const int64_t w = it - (it / nw) * nw;
+      uint64_t bits = G[static_cast<int64_t>(f) * nw + w] & mc_alive[w];
+      while (bits) {
+        const int b = __ffsll(static_cast<unsigned long long>(bits)) - 1;
+        bits &= bits - 1;
+        atomicSub(deg + (w * 64 + b), 1);
+      }
+    }
+    removed += n;
+    work += items + n;
+    __threadfence();  // the decrements (L2 atomics) complete before the next round reads the degrees
+    __syncthreads();
+  }
+  for (int64_t w = tid; w < nw; w += MC_PEEL_THREADS) alive_g[w] = mc_alive[w];
+  if (tid == 0) {
+    ctl->k = k;
+    ctl->removed = removed;
+  }
+}
+
+// ---- HEU: the greedy clique of one seed (one wave; C = the candidate bitset in LDS) ------------------------------
+// Candidates: N(v) minus the vertices with core + 1 < thr; step: take the candidate of largest core number (ties:
+// smallest index), intersect with its row. Every pick's core is at most the previous one's, so with thr <= the
+// final best size the clique of every seed that can reach that size is the one thr = 0 gives.
+// Returns the size; `out` (may be null, lane 0 writes) receives the clique in pick order. Adds the row-word
+// operations to `work`.
+__device__ int mc_greedy(const uint64_t* __restrict__ G, int64_t nw, const int32_t* __restrict__ core, int v,
+                         int thr, uint64_t* C, int32_t* out, long long& work, int lane) {
+  int size = 1;
+  if (out && lane == 0) out[0] = v;
+  int u = v;
+  while (true) {
+    unsigned long long bk = 0;
+    const uint64_t* row = G + static_cast<int64_t>(u) * nw;
+    for (int64_t w = lane; w < nw; w += 64) {
+      uint64_t word = (u == v ? ~0ull : C[w]) & row[w];
+      uint64_t bits = word;
+      while (bits) {
+        const int b = __ffsll(static_cast<unsigned long long>(bits)) - 1;
+        bits &= bits - 1;
+        const int x = static_cast<int>(w * 64 + b);
+        const int cx = core[x];
+        if (cx + 1 < thr) {
+          word &= ~(1ull << b);
+          continue;
+        }
+        const unsigned long long kx = (static_cast<unsigned long long>(cx + 1) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(x));
+        bk = kx > bk ? kx : bk;
+      }
+      C[w] = word;
+    }
+    work += nw / 64 + 1;
+    bk = mc_wave_max_u64(bk);
+    __syncthreads();
+    if (bk == 0) break;
+    u = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(bk & 0xFFFFFFFFull));
+    if (out && lane == 0) out[size] = u;
+    ++size;
+  }
+  return size;
+}
+
+// Seeds (the host's order: core descending) taken through ctl->head; a seed whose core + 1 is below the best size
+// so far is skipped. ctl->key = max over seeds of size << 32 | ~seed.
+__global__ __launch_bounds__(64) void k_mc_heu(const uint64_t* __restrict__ G, int64_t nw,
+                                               const int32_t* __restrict__ core, const int32_t* __restrict__ seeds,
+                                               int32_t nseeds, McCtl* ctl, long long budget) {
+  extern __shared__ uint64_t mc_cand[];
+  const int lane = threadIdx.x;
+  long long work = 0;
+  while (work < budget) {
+    int idx = 0;
+    if (lane == 0) idx = atomicAdd(&ctl->head, 1);
+    idx = __shfl(idx, 0, 64);
+    if (idx >= nseeds) break;
+    const int v = seeds[idx];
+    const int best = static_cast<int>(mc_load_key(&ctl->key) >> 32);
+    if (core[v] + 1 < best) continue;
+    const int size = mc_greedy(G, nw, core, v, best, mc_cand, nullptr, work, lane);
+    if (lane == 0)
+      atomicMax(&ctl->key, (static_cast<unsigned long long>(size) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(v)));
+  }
+}
+
+// the clique of one seed (thr = 0), written to out[0..size)
+__global__ __launch_bounds__(64) void k_mc_heu_one(const uint64_t* __restrict__ G, int64_t nw,
+                                                   const int32_t* __restrict__ core, int32_t v, int32_t* out) {
+  extern __shared__ uint64_t mc_cand[];
+  long long work = 0;
+  mc_greedy(G, nw, core, v, 0, mc_cand, out, work, threadIdx.x);
+}
+
+// ---- EXACT: bitset branch and bound, one wave per root ----------------------------------------------------------
+// Root r (vertices ordered by (core, degree, index): pos[]) searches the cliques {r} + K, K inside
+// P0 = N(r) & {pos > pos[r]} & {core >= heu}. A stack level L holds the candidate bitset P_L of the clique
+// {r, path[0..L-1]} (c = L + 1 vertices). A step at level L colours P_L greedily (vertices in index order, each
+// colour class an independent set; BBMC): k colours bound the clique by c + k. If the key (c + k, rk) does not beat
+// the incumbent the level is popped; else the LAST vertex coloured, v, is branched on: v leaves P_L, P_{L+1} =
+// P_L & N(v). An empty P_{L+1} is a maximal clique of c + 1 vertices, offered to the incumbent. A level is
+// coloured again every time the search returns to it (the bound of what is left, and no per-level list to keep:
+// the stack is one bitset per level).
+// Tie rule: rk = 0xFFFFFFFE - pos[r]; a branch is cut only when (bound, rk) <= the incumbent key, so the first
+// clique of the final size in the DFS order of the first root (in pos order) that holds one is always found.
+// The incumbent starts at (heu, 0xFFFFFFFF): only cliques larger than HEU's are searched for.
+// A slot (= workgroup) keeps its root, depth, path and stack between launches; recs[slot] holds the clique of the
+// last key it raised. LDS: Q, R (the colouring's bitsets).
+__global__ __launch_bounds__(64) void k_mc_exact(const uint64_t* __restrict__ G, int64_t nw,
+                                                 const int32_t* __restrict__ core, const int32_t* __restrict__ pos,
+                                                 const int32_t* __restrict__ roots, int32_t nroots, int32_t heu,
+                                                 McCtl* ctl, McSlot* slots, uint64_t* __restrict__ arena,
+                                                 int32_t* __restrict__ paths, int32_t* __restrict__ recs, int32_t D,
+                                                 long long budget) {
+  extern __shared__ uint64_t mc_lds[];
+  uint64_t* Q = mc_lds;
+  uint64_t* R = mc_lds + nw;
+  const int lane = threadIdx.x;
+  const int slot = blockIdx.x;
+  McSlot* sl = slots + slot;
+  uint64_t* stk = arena + static_cast<int64_t>(slot) * D * nw;
+  int32_t* path = paths + static_cast<int64_t>(slot) * (D + 1);  // path[0] = root, path[1 + L] = branch of level L
+  int root = sl->root, L = sl->depth;
+  unsigned long long rk = root >= 0 ? 0xFFFFFFFEull - static_cast<unsigned>(pos[root]) : 0;
+  long long work = 0;
+  unsigned long long nodes = 0, searched = 0, pruned = 0;
+  while (work < budget) {
+    if (root < 0) {
+      int idx = 0;
+      if (lane == 0) idx = atomicAdd(&ctl->head, 1);
+      idx = __shfl(idx, 0, 64);
+      if (idx >= nroots) break;
+      const int r = roots[idx];
+      rk = 0xFFFFFFFEull - static_cast<unsigned>(pos[r]);
+      unsigned long long inc = mc_load_key(&ctl->key);
+      if (((static_cast<unsigned long long>(core[r] + 1) << 32) | rk) <= inc) {
+        ++pruned;
+        continue;
+      }
+      const int pr = pos[r];
+      int cnt = 0;
+      for (int64_t w = lane; w < nw; w += 64) {
+        uint64_t bits = G[static_cast<int64_t>(r) * nw + w], keep = 0;
+        while (bits) {
+          const int b = __ffsll(static_cast<unsigned long long>(bits)) - 1;
+          bits &= bits - 1;
+          const int x = static_cast<int>(w * 64 + b);
+          if (pos[x] > pr && core[x] >= heu) keep |= 1ull << b;
+        }
+        stk[w] = keep;
+        cnt += __popcll(keep);
+      }
+      cnt = mc_wave_sum(cnt);
+      work += nw / 64 + 1;
+      inc = mc_load_key(&ctl->key);
+      if (((static_cast<unsigned long long>(cnt + 1) << 32) | rk) <= inc) {
+        ++pruned;
+        continue;
+      }
+      ++searched;
+      root = r;
+      L = 0;
+      if (lane == 0) path[0] = r;
+      __threadfence_block();
+    }
+    // ---- one step at level L: colour P_L (stk + L * nw) into Q / R
+    uint64_t* P = stk + static_cast<int64_t>(L) * nw;
+    int hi = 0;
+    for (int64_t w = lane; w < nw; w += 64) {
+      const uint64_t x = P[w];
+      Q[w] = x;
+      if (x) hi = static_cast<int>(w) + 1;
+    }
+    hi = mc_wave_max(hi);
+    __syncthreads();
+    int ncol = 0, last = -1, qlo = 0;
+    ++nodes;
+    while (true) {
+      const int f = mc_first_word(Q, qlo, hi, lane);
+      if (f < 0) break;
+      qlo = f;
+      ++ncol;
+      for (int w = f + lane; w < hi; w += 64) R[w] = Q[w];
+      __syncthreads();
+      int rlo = f;
+      while (true) {
+        const int f2 = mc_first_word(R, rlo, hi, lane);
+        if (f2 < 0) break;
+        rlo = f2;
+        const uint64_t word = R[f2];
+        const int b = __ffsll(static_cast<unsigned long long>(word)) - 1;
+        const int v = f2 * 64 + b;
+        last = v;
+        __syncthreads();
+        const uint64_t* gv = G + static_cast<int64_t>(v) * nw;
+        for (int w = f2 + lane; w < hi; w += 64) {
+          uint64_t rw = R[w] & ~gv[w];
+          uint64_t qw = Q[w];
+          if (w == f2) {
+            rw &= ~(1ull << b);
+            qw &= ~(1ull << b);
+          }
+          R[w] = rw;
+          Q[w] = qw;
+        }
+        work += (hi - f2) / 64 + 1;
+        __syncthreads();
+      }
+    }
+    const unsigned long long inc = mc_load_key(&ctl->key);
+    if (ncol == 0 || ((static_cast<unsigned long long>(L + 1 + ncol) << 32) | rk) <= inc) {
+      if (L == 0) root = -1;
+      else --L;
+      continue;
+    }
+    // branch on `last`: it leaves P_L; P_{L+1} = P_L & N(last)
+    const uint64_t* gv = G + static_cast<int64_t>(last) * nw;
+    int cnt = 0;
+    const bool room = L + 1 < D;
+    for (int64_t w = lane; w < hi; w += 64) {
+      uint64_t x = P[w];
+      if (w == (last >> 6)) x &= ~(1ull << (last & 63));
+      P[w] = x;
+      const uint64_t y = x & gv[w];
+      if (room) P[nw + w] = y;
+      cnt += __popcll(y);
+    }
+    if (room)
+      for (int64_t w = hi + lane; w < nw; w += 64) P[nw + w] = 0;
+    cnt = mc_wave_sum(cnt);
+    if (lane == 0) path[1 + L] = last;
+    __threadfence_block();
+    if (cnt == 0) {
+      const unsigned long long key = (static_cast<unsigned long long>(L + 2) << 32) | rk;
+      if (lane == 0) {
+        // only the slot that raised the key to this value writes it: the record with the final key is its clique
+        if (atomicMax(&ctl->key, key) < key) {
+          int32_t* rec = recs + static_cast<int64_t>(slot) * (D + 1);
+          for (int i = 0; i < L + 2; ++i) rec[i] = path[i];
+          sl->rec_key = key;
+        }
+      }
+    } else if (!room) {
+      if (lane == 0) atomicAdd(&ctl->overflow, 1);
+      root = -1;  // (not reachable: a clique of more than K + 1 vertices)
+    } else {
+      ++L;
+    }
+  }
+  if (lane == 0) {
+    sl->root = root;
+    sl->depth = L;
+    if (root >= 0) atomicAdd(&ctl->active, 1);
+    atomicAdd(&ctl->bb_nodes, nodes);
+    atomicAdd(&ctl->roots_searched, searched);
+    atomicAdd(&ctl->roots_pruned, pruned);
+  }
+}
+
+}  // namespace clipper_hip

@@ -38,6 +38,7 @@
 //   k_rowview.hip.h   the row list of a row view of M (the live rows of the solver's current points)
 //   k_subproblem.hip.h  the live sub-problem: column counts of a view, the selection, the hand-over and the way back
 //   k_knn.hip.h       brute-force k-nearest neighbours (putative associations)
+//   k_maxclique.hip.h the maximum clique of the consistency graph: adjacency bitsets, core numbers, HEU, EXACT
 #pragma once
 
 #include "k_solver.hip.h"
@@ -50,3 +51,4 @@
 #include "k_rowview.hip.h"
 #include "k_subproblem.hip.h"
 #include "k_knn.hip.h"
+#include "k_maxclique.hip.h"

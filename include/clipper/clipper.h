@@ -13,8 +13,11 @@
  *     there is deliberately NO silent CPU fallback for the built-in invariants);
  *   - Rounding::DSD (clipper.cpp:294-300) is supported: the exact densest subgraph of the
  *     sub-matrix induced by nnz(u), gathered from the device (include/clipper/dsd.h);
- *   - solveAsMaximumClique / solveAsMSRCSDR are outside this build and report so, exactly
- *     like a reference build without PMC / SCS (maxclique.cpp:141-145, sdp.cpp:298-302).
+ *   - solveAsMaximumClique runs on the device (clipper_hip_max_clique: adjacency bitsets, core
+ *     numbers, the greedy clique, a bitset branch and bound) instead of
+ *     PMC; one-shard contexts only (column shards throw std::runtime_error);
+ *   - solveAsMSRCSDR is outside this build and reports so, exactly like a reference build
+ *     without SCS (sdp.cpp:298-302).
  */
 #pragma once
 
@@ -32,7 +35,9 @@ struct clipper_hip_ctx;  // opaque handle of the C ABI
 namespace clipper {
 
 namespace maxclique {
-/// Mirror of the reference maxclique::Method / Params (maxclique.h:15-23); solver not built here.
+/// Mirror of the reference maxclique::Method / Params (maxclique.h:15-23). EXACT = ROBIN* (a maximum clique), HEU = the
+/// greedy clique of DESIGN.md 9, KCORE = ROBIN (the vertices of maximum core number). `threads` is accepted and
+/// ignored (the device decides); `time_limit` (seconds) bounds HEU's and EXACT's search.
 enum class Method { EXACT, HEU, KCORE };
 struct Params {
   Method method = Method::EXACT;
@@ -101,7 +106,7 @@ class CLIPPER {
   /// Graduated projected gradient ascent (clipper.cpp:69-78, 172-323). Random u0 if empty.
   void solve(const VectorXd& u0 = VectorXd());
 
-  void solveAsMaximumClique(const maxclique::Params& params = {});  ///< not built (PMC)
+  void solveAsMaximumClique(const maxclique::Params& params = {});  ///< on the device (clipper_hip_max_clique)
   void solveAsMSRCSDR(const sdp::Params& params = {});              ///< not built (SCS)
 
   const Solution& getSolution() const { return soln_; }

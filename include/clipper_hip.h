@@ -252,6 +252,38 @@ int clipper_hip_get_selected_associations(const clipper_hip_t* h, int32_t* A_out
 int clipper_hip_densest_subgraph(clipper_hip_t* h, const int32_t* S, int32_t k,
                                  int32_t* nodes_out, int32_t capacity);
 
+/* ---- maximum clique of the consistency graph (maxclique::solve, maxclique.cpp:23-150) ------------------ */
+
+/* The graph: vertices 0..m-1, edge (i, j), i != j, exactly when C(i, j) != 0 — the pattern of M for a scored
+ * problem, the stored C after set_matrix / set_sparse with an explicit C; every storage gives the same graph.
+ * Methods (= maxclique::Method, maxclique.h:15-19):
+ *   EXACT  (ROBIN*) a maximum clique; the same list on every call, storage and launch geometry.
+ *          HEU's clique when its size reaches the core bound K + 1.
+ *   HEU    the greedy clique of DESIGN.md 9: every vertex seeds one (largest core number first), the largest wins
+ *          (ties: the smallest seed).
+ *   KCORE  (ROBIN) every vertex whose core number is the maximum K (an edgeless graph: all of them).
+ * EXACT and HEU return no vertex on an edgeless graph (maxclique.cpp:114-118). The clique (ascending) becomes the
+ * context's node list (clipper_hip_get_nodes, clipper_hip_get_selected_associations); nothing the solver keeps is
+ * touched. time_limit_s > 0 bounds HEU's and EXACT's launches (checked between launches, each of which is a
+ * bounded amount of work): when it runs out the best clique so far is returned and info->timed_out = 1; <= 0: no
+ * limit. One-shard contexts only: column shards return CLIPPER_HIP_E_SCOPE. The adjacency bitsets take m^2 / 8
+ * bytes of device memory for the call (CLIPPER_HIP_E_NOMEM when they do not fit). */
+enum { CLIPPER_HIP_MC_EXACT = 0, CLIPPER_HIP_MC_HEU = 1, CLIPPER_HIP_MC_KCORE = 2 }; /* = maxclique::Method */
+typedef struct clipper_maxclique_info_t {
+  int32_t num_nodes;       /* vertices of the returned list                                               */
+  int32_t max_core;        /* K                                                                            */
+  int32_t heuristic_size;  /* HEU's clique (EXACT, HEU; 0 for KCORE / an edgeless graph)                    */
+  int32_t timed_out;       /* 1: the time limit stopped the search                                         */
+  int64_t edges;           /* undirected edges                                                             */
+  int64_t roots_searched;  /* EXACT: roots whose branch and bound ran                                      */
+  int64_t roots_pruned;    /* EXACT: roots their core number or neighbourhood size ruled out               */
+  int64_t bb_nodes;        /* EXACT: branch-and-bound nodes (colourings)                                   */
+  double seconds;          /* wall time of the call                                                        */
+} clipper_maxclique_info_t;
+int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, clipper_maxclique_info_t* info);
+/* The core number of every vertex of the same graph (Batagelj-Zaversnik): m int32. */
+int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out /* m */);
+
 /* ---- before the path: putative associations ------------------------------------------------ */
 
 /* k nearest neighbours in P1 of every point of P0 (both d x n column-major as `clipper::Data`:
