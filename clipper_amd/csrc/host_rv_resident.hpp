@@ -124,7 +124,7 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
     hipError_t e = hipErrorUnknown;
     dispatch_vt(h, [&](auto tag) {
       using VT = decltype(tag);
-      auto kern = (h->V == 6) ? k_solve_view_resident<VT, 6> : k_solve_view_resident<VT, 4>;
+      auto kern = (h->V == 6) ? k_solve_view_resident<VT, 6, false> : k_solve_view_resident<VT, 4, false>;
       if (raise_dynamic_lds(reinterpret_cast<const void*>(kern), s.device, static_cast<int>(RS_LDS_MAX)))
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), RVR_NT, RS_LDS_MAX);
     });
@@ -215,7 +215,8 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
 
 template <typename VT, int V>
 int rvr_launch_t(Ctx* h, Shard& s, const RvrArgs& a) {
-  auto kern = k_solve_view_resident<VT, V>;
+  // (the instance with the finer stamps only when stamps are on: same launch bounds and LDS, so the same residency)
+  auto kern = a.stamps ? k_solve_view_resident<VT, V, true> : k_solve_view_resident<VT, V, false>;
   if (!raise_dynamic_lds(reinterpret_cast<const void*>(kern), s.device, static_cast<int>(RS_LDS_MAX))) return 1;
   hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(a.nunits)), dim3(RVR_NT), RS_LDS_MAX, s.stream, a);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {

@@ -89,10 +89,20 @@ struct RvrArgs {
   int max_exchanges;            // leave to the streaming launches after this many
   ViewPolicy rvp;
   int rv_rows;
-  long long* stamps;            // measurement only (may be null): unit 0, [iteration][8] wall-clock stamps
+  long long* stamps;            // measurement only (may be null): unit 0, [iteration][8] wall-clock stamps, and from
+                                // RVR_FINE0 on [iteration][32] the finer ones of a turn (RVR_F_* below)
   const uint8_t* marks;         // profiling only (may be null): the streaming iterations' marks (SolveArgs::marks) and
   uint8_t* kind;                // their pinned copy — a launch that ENDS the solve hands them over, as decide() does
   int64_t marks_n;              // the iterations queued before this launch
+};
+// The finer stamps of unit 0's turn t < RVR_FINE_TURNS, at stamps[RVR_FINE0 + 32 t + RVR_F_*] (measurement only:
+// tools/rvr_timeline.py). Wall clock, except KIND (K_TRIAL 0 / K_PAIR 1 / K_BUILD 2) and ROUNDS (decision rounds).
+constexpr int RVR_FINE0 = 5120, RVR_FINE_TURNS = 96;
+enum : int {
+  RVR_F_KIND = 0, RVR_F_ROUNDS = 1, RVR_F_XT = 2 /* X table written */, RVR_F_NORMS = 3 /* norms done */,
+  RVR_F_SUMS = 4 /* the column sums combined */, RVR_F_TAIL = 5 /* tail done, counts not yet published */,
+  RVR_F_ROUND = 8 /* [8 .. 8 + V) end of decision round v */,
+  RVR_F_DECIDED = 14 /* decision end */, RVR_F_WAVE = 16 /* [16 .. 24) wave w's rs_wave_pass done */
 };
 enum : uint32_t { RVR_ERR_LDS = 1, RVR_ERR_TIMEOUT = 2, RVR_ERR_STATE = 3, RVR_ERR_PEER = 4 /* host: another rank's launch gave up */ };
 
@@ -179,7 +189,10 @@ __device__ __forceinline__ int wave_isum_to_lane63(int v) {
   return v;
 }
 
-template <typename VT, int V>
+// FINE: the instance that also writes the finer stamps (RVR_F_*; launched only when A.stamps is set). Their guards alone
+// cost registers across the turn — the spills of the loop grew from 8 to 18 scratch operations (tools/spill_report.py) —,
+// so the instance the solves run carries none of them.
+template <typename VT, int V, bool FINE>
 __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rvr_lds[];
   constexpr int NS = V + 1;
@@ -422,10 +435,24 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       row[3] = stamp_row;
     }
   };
+  int trow = 0;  // the turn being stamped (stamp_row counts the exchanges: it moves on before the decision)
   auto stamp = [&](int c) {  // unit 0: every turn; every unit: turn 6 (rows behind the first 512 x 8 words)
     if (A.stamps && tid == 0) {
-      if (unit == 0 && stamp_row < 500) A.stamps[stamp_row * 8 + c] = wall_clock64();
-      if (stamp_row == 6 && c < 4 && unit < RVR_MAXUNITS) A.stamps[4096 + unit * 4 + c] = wall_clock64();
+      if (unit == 0 && trow < 500) A.stamps[trow * 8 + c] = wall_clock64();
+      if (trow == 6 && c < 4 && unit < RVR_MAXUNITS) A.stamps[4096 + unit * 4 + c] = wall_clock64();
+    }
+  };
+  // unit 0, thread 0: the finer stamps of this turn (RVR_F_*; the FINE instance only). The clock is read behind the
+  // guard. `dep` ties the stamp to a value the stamped step produced.
+  auto fstamp = [&](int c, double dep = 0.0) {
+    if constexpr (FINE) {
+      if (A.stamps && unit == 0 && tid == 0 && trow < RVR_FINE_TURNS)
+        A.stamps[RVR_FINE0 + trow * 32 + c] = wall_clock64() + (dep > 1e300 ? 1 : 0);
+    }
+  };
+  auto fstamp_value = [&](int c, long long v) {  // the same slot, a count instead of a clock (KIND, ROUNDS)
+    if constexpr (FINE) {
+      if (A.stamps && unit == 0 && tid == 0 && trow < RVR_FINE_TURNS) A.stamps[RVR_FINE0 + trow * 32 + c] = v;
     }
   };
   unsigned long long* const xb0 = A.xb;
@@ -472,6 +499,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
   int kind = (e_resume == 2) ? K_PAIR : K_TRIAL;
   bool want_out = false;  // a prepared pass is the next thing: leave it to the streaming launches
   for (;;) {
+    trow = stamp_row;
     stamp(0);
     // ---- leave? (only ever in front of a pass: what goes out is a PREPARED pass) ----------------------
     const bool out_now = kind != K_BUILD && (exchanges >= A.max_exchanges || (kind == K_TRIAL ? want_out : nout != 0));
@@ -548,6 +576,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       return;
     }
 
+    fstamp_value(RVR_F_KIND, kind);
     // ---- the pass: X table (raw candidates of the view's rows) -> the COMPLETE sums y[0 .. V] of this
     // thread's own column (acc[0] = a, acc[1 .. V-1] = g_v, acc[V] = b: rs_wave_pass) ---------------------
     double y[NS];
@@ -569,8 +598,13 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
         }
       }
       __syncthreads();
+      fstamp(RVR_F_XT);
       double acc[NS];
       rs_wave_pass<VT, V>(sl, toff, pc, np, 0, Xt, (kind == K_TRIAL) ? d : 0.0, acc, G, lgrp * SL_SUB);
+      if constexpr (FINE) {
+        if (A.stamps && unit == 0 && lane == 0 && trow < RVR_FINE_TURNS)
+          A.stamps[RVR_FINE0 + trow * 32 + RVR_F_WAVE + wave] = wall_clock64() + (acc[0] > 1e300 ? 1 : 0);  // (after the pass)
+      }
       // the window's norms (:237): wave l sums candidate l over the rows of the X table (64 rows per step, one
       // DPP sum of two numbers: the thread-per-row sums of all 2 V numbers cost six times that in every wave)
       if (wave < V) {
@@ -591,6 +625,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
         }
       }
       __syncthreads();  // the X table is dead: its memory becomes the waves' sums
+      fstamp(RVR_F_NORMS);
       if (packed) {  // a column sits in one lane of every lane group: their sums meet in a butterfly (fixed order)
         for (int o = Wd; o < 64; o <<= 1) {
 #pragma unroll
@@ -600,15 +635,26 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
 #pragma unroll
       for (int v = 0; v < NS; ++v) scr[(wave * NS + v) * 64 + lane] = acc[v];
       __syncthreads();
+      if (wave < U.ncgs) {  // (uniform) only the waves that own columns in the tail need the sums
+        // the waves that worked for this thread's column group, in wave order. Every wave's sum is loaded and a
+        // foreign one adds +0.0 — an exact no-op, as a sum that starts at +0.0 is never -0.0 —: the eight loads of a
+        // sum fly together instead of one per branch on the uniform wave_cg
+        uint32_t mine = 0;
 #pragma unroll
-      for (int v = 0; v < NS; ++v) {
-        double sum = 0.0;
+        for (int w = 0; w < RVR_NWV; ++w) mine |= (static_cast<int>((wcg >> (8 * w)) & 255ull) == wave) ? (1u << w) : 0u;
 #pragma unroll
-        for (int w = 0; w < RVR_NWV; ++w)  // the waves that worked for this thread's column group, in wave order
-          if (static_cast<int>((wcg >> (8 * w)) & 255ull) == wave) sum += scr[(w * NS + v) * 64 + lane];
-        y[v] = sum;
+        for (int v = 0; v < NS; ++v) {
+          double sum = 0.0;
+#pragma unroll
+          for (int w = 0; w < RVR_NWV; ++w) {
+            const double t = scr[(w * NS + v) * 64 + lane];
+            sum += ((mine >> w) & 1u) ? t : 0.0;
+          }
+          y[v] = sum;
+        }
       }
-      __syncthreads();  // (the next X table overwrites the sums)
+      fstamp(RVR_F_SUMS, y[0]);
+      // (no barrier: the next X table is written after the exchange's barrier)
     }
     stamp(1);
     // ---- the tail of this thread's own column (k_tail's expressions, :237-242), what it publishes -----------
@@ -658,7 +704,18 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
     // read only when they are the current point's (penalty update, start of an outer iteration)
     a_c = an_c;
     b_c = bn_c;
-    {  // the unit's counts, 10 bits per candidate, as one value
+    fstamp(RVR_F_TAIL, a_c + gn_c[V - 1]);
+    if (U.ncgs == 1) {  // (uniform) the unit's counts, 10 bits per candidate, as one value: wave 0 holds all its columns
+      if (wave == 0) {
+        unsigned long long pk = 0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) pk |= static_cast<unsigned long long>(__popcll(__ballot((cbits >> v) & 1u))) << (10 * v);
+        if (lane == 0) rvr_publish(sec_c(par, unit), tag, __longlong_as_double(static_cast<long long>(pk)));
+      }
+      // (this barrier stays: the other waves must not poll before the unit's own stores are out — 246 units' sweeps of
+      // 64 KB each held the tails' stores up by 2 us and more, profiles/r07_rvr_turn_breakdown_after.txt)
+      __syncthreads();
+    } else {  // the same over the waves that own columns
       unsigned long long w = 0;
 #pragma unroll
       for (int v = 0; v < V; ++v) w |= static_cast<unsigned long long>(__popcll(__ballot((cbits >> v) & 1u))) << (7 * v);
@@ -765,6 +822,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
     //   round buffers: rbuf[round][wave][4] doubles, ibuf[round][wave][4] ints (a round never reuses one within a turn)
     double* rbuf = red;
     int* ibuf = reinterpret_cast<int*>(red + V * RVR_NWV * 4);
+    int nrounds = 0;
     auto round_sums = [&](int rd, double (&dv)[3], int (&iv)[3]) __attribute__((always_inline)) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) dv[q] = wave_sum_to_lane63(dv[q]);
@@ -789,6 +847,13 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
                                  __builtin_amdgcn_readfirstlane(__double2loint(acc)));
         iv[q] = __builtin_amdgcn_readfirstlane(iacc);
       }
+      fstamp(RVR_F_ROUND + rd);
+      ++nrounds;
+    };
+    auto stamp_decided = [&]() {
+      stamp(4);
+      fstamp(RVR_F_DECIDED);
+      fstamp_value(RVR_F_ROUNDS, nrounds);
     };
     ++n_iters;
     if (kind != K_BUILD) {
@@ -870,7 +935,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
         }
         al = al * P.beta;
       }
-      stamp(4);
+      stamp_decided();
       if (jstar < 0) continue;  // all V rejected: V more factors of beta are in alpha, the point is unchanged
       const double deltau = sqrt(du2);
       F = Fnew;
@@ -907,7 +972,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       pen_rs = dv[2];
       pen_cnt = iv[1];
       penalty = true;
-      stamp(4);
+      stamp_decided();
     } else {  // K_BUILD (:219-220): the first window of the outer iteration is pending
       double dv[3] = {0.0, 0.0, 0.0};
       int iv[3] = {0, 0, 0};
@@ -924,7 +989,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       }
       iv[2] = (tid < A.nunits) ? static_cast<int>(cpk & 1023ull) : 0;
       round_sums(0, dv, iv);
-      stamp(4);
+      stamp_decided();
       if (cown) g_c = gn_c[0];
       F = dv[0];
       nout = iv[2];

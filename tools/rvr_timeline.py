@@ -2,7 +2,9 @@
 """Where a turn of the resident solver on a row view goes (unit 0): wall-clock stamps inside the kernel
 (csrc/k_rv_resident.hip.h), on the headline problem.
   CLIPPER_HIP_STAMPS=1 python tools/rvr_timeline.py [--m 10000] [--rho 0.95]
-columns (us, medians over the turns): candidates + pass | tail + publish | exchange | scalars | decide
+columns (us, medians over the turns): candidates + pass | tail + publish | exchange | decide
+then the finer breakdown of a turn (RVR_F_* in the kernel): medians per segment, and the turn time by the turn's kind
+and by its number of decision rounds
 """
 import argparse
 import os
@@ -15,6 +17,63 @@ import numpy as np  # noqa: E402
 
 from clipper_amd import _abi as abi  # noqa: E402
 from clipper_amd import synth  # noqa: E402
+
+
+FINE0, FINE_TURNS = 5120, 96  # csrc/k_rv_resident.hip.h: RVR_FINE0, RVR_FINE_TURNS, RVR_F_*
+F_KIND, F_ROUNDS, F_XT, F_NORMS, F_SUMS, F_TAIL, F_ROUND, F_DECIDED, F_WAVE = 0, 1, 2, 3, 4, 5, 8, 14, 16
+KINDS = ("trial", "pair", "build")
+
+
+def fine_breakdown(raw, rows, n):
+    """Unit 0's turns at the finer stamps: medians per segment, turn time by kind and by decision rounds."""
+    nt = min(n, FINE_TURNS)
+    f = raw[FINE0:FINE0 + 32 * FINE_TURNS].reshape(FINE_TURNS, 32)[:nt].astype(np.float64)
+    s = rows[:n + 1, :5].astype(np.float64)
+    s[n, 0] = rows[500, 2]  # (the last turn ends the launch: no turn stamps row n)
+    kind = f[:, F_KIND].astype(int)
+    rounds = f[:, F_ROUNDS].astype(int)
+    turn = (s[1:nt + 1, 0] - s[:nt, 0]) / 100.0  # turn t: its start to the next turn's start
+    pas = kind != 2
+    seg = {}
+
+    def add(name, a, b, sel=None):
+        sel = pas if sel is None else sel
+        v = (b - a)[sel] / 100.0
+        if len(v):
+            seg[name] = v
+
+    wv = f[:, F_WAVE:F_WAVE + 8]
+    wmax = wv.max(axis=1)
+    add("X table", s[:nt, 0], f[:, F_XT])
+    add("pass, wave 0", f[:, F_XT], wv[:, 0])
+    add("pass, slowest wave", f[:, F_XT], wmax)
+    add("norms + barrier", wmax, f[:, F_NORMS])
+    add("cross-wave sums", f[:, F_NORMS], f[:, F_SUMS])
+    add("barrier after sums", f[:, F_SUMS], s[:nt, 1])
+    add("tail", s[:nt, 1], f[:, F_TAIL], np.ones(nt, bool))
+    add("counts published", f[:, F_TAIL], s[:nt, 2], np.ones(nt, bool))
+    add("exchange", s[:nt, 2], s[:nt, 3], np.ones(nt, bool))
+    add("decision round 1", s[:nt, 3], f[:, F_ROUND], np.ones(nt, bool))
+    later = rounds >= 2
+    if later.any():
+        last = f[np.arange(nt), F_ROUND + np.maximum(rounds, 1) - 1]
+        add("later rounds (per round)", f[:, F_ROUND], f[:, F_ROUND] + (last - f[:, F_ROUND]) / np.maximum(rounds - 1, 1), later)
+    else:
+        last = f[:, F_ROUND]
+    add("after the last round", last, f[:, F_DECIDED], np.ones(nt, bool))
+    add("decided to next turn", f[:, F_DECIDED], s[1:nt + 1, 0], np.ones(nt, bool))
+    print(f"   finer breakdown of unit 0's turns (us; median / mean over the turns that have the segment):")
+    for k, v in seg.items():
+        print(f"      {k:26s} {np.median(v):6.2f} / {v.mean():6.2f}   ({len(v)} turns)")
+    for k in range(3):
+        sel = kind == k
+        if sel.any():
+            print(f"   turn time, {KINDS[k]:5s}: {sel.sum():3d} turns, median {np.median(turn[sel]):6.2f}, mean {turn[sel].mean():6.2f} us")
+    for r in sorted(set(rounds[kind == 0].tolist())):
+        sel = (kind == 0) & (rounds == r)
+        print(f"   turn time, trial with {r} round(s): {sel.sum():3d} turns, median {np.median(turn[sel]):6.2f}, "
+              f"mean {turn[sel].mean():6.2f} us")
+    print("   turns: " + " ".join(f"{KINDS[k][0]}{r}:{t:.1f}" for k, r, t in zip(kind, rounds, turn)))
 
 
 def main():
@@ -43,7 +102,7 @@ def main():
     n = int(end[3])
     t = rows[:n, :5].astype(np.float64)
     d = np.diff(t, axis=1) / 100.0
-    turn = np.diff(t[:, 0]) / 100.0
+    turn = np.diff(np.append(t[:, 0], end[2])) / 100.0
     if n < 2:
         print(f"m={a.m}: solve {np.median(ts):.3f} ms (min {min(ts):.3f}); passes {sol.n_passes}, no resident launch")
         g.close()
@@ -51,8 +110,9 @@ def main():
     med = np.median(d, axis=0)
     print(f"m={a.m} wgs={os.environ.get('CLIPPER_HIP_VIEW_RESIDENT_WGS', 'auto')}: solve {np.median(ts):.3f} ms (min {min(ts):.3f}); "
           f"passes {sol.n_passes} ({st.view_passes} on a view of {st.rows} rows), resident launches {st.resident_launches}, turns {n}")
-    print(f"   per turn: candidates+pass {med[0]:.2f} | tail+publish {med[1]:.2f} | exchange {med[2]:.2f} | scalars {med[3]:.2f} "
-          f"| turn to turn {np.median(turn):.2f} (p90 {np.percentile(turn, 90):.2f}) us")
+    print(f"   per turn: candidates+pass {med[0]:.2f} | tail+publish {med[1]:.2f} | exchange {med[2]:.2f} | decide {med[3]:.2f} "
+          f"| turn to turn {np.median(turn):.2f} (mean {turn.mean():.2f}, p90 {np.percentile(turn, 90):.2f}) us")
+    fine_breakdown(raw, rows, n)
     per = raw[4096:4096 + 4 * 256].reshape(256, 4).astype(np.float64)
     per = per[per[:, 0] > 0]
     if len(per) and n > 6:
