@@ -44,6 +44,10 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
     "clipper_hip_max_clique", "clipper_hip_core_numbers",
+    "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
+    "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
+    "clipper_hip_batch_get_selected_associations", "clipper_hip_batch_route", "clipper_hip_batch_get_stats",
+    "clipper_hip_batch_get_split",
 ]
 
 
@@ -117,6 +121,17 @@ class MaxCliqueInfo(C.Structure):
         ("num_nodes", C.c_int32), ("max_core", C.c_int32), ("heuristic_size", C.c_int32), ("timed_out", C.c_int32),
         ("edges", C.c_int64), ("roots_searched", C.c_int64), ("roots_pruned", C.c_int64), ("bb_nodes", C.c_int64),
         ("seconds", C.c_double),
+    ]
+
+
+class BatchProblem(C.Structure):
+    """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
+
+    _fields_ = [
+        ("D1", C.POINTER(C.c_double)), ("n1", C.c_int64),
+        ("D2", C.POINTER(C.c_double)), ("n2", C.c_int64),
+        ("A", C.POINTER(C.c_int32)), ("m", C.c_int64),
+        ("u0", C.POINTER(C.c_double)),
     ]
 
 
@@ -210,6 +225,19 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
     L.clipper_hip_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_core_numbers.argtypes = [vp, ip]
+    L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
+    L.clipper_hip_batch_destroy.argtypes = [vp]
+    L.clipper_hip_batch_destroy.restype = None
+    L.clipper_hip_batch_solve_euclidean.argtypes = [vp, C.POINTER(BatchProblem), C.c_int32, C.c_int] + \
+        [C.c_double] * 3 + [C.POINTER(Params)]
+    L.clipper_hip_batch_solve_pointnormal.argtypes = [vp, C.POINTER(BatchProblem), C.c_int32] + \
+        [C.c_double] * 4 + [C.POINTER(Params)]
+    L.clipper_hip_batch_get_solution.argtypes = [vp, C.c_int32, dp, C.POINTER(SolveInfo)]
+    L.clipper_hip_batch_get_nodes.argtypes = [vp, C.c_int32, ip, C.c_int32]
+    L.clipper_hip_batch_get_selected_associations.argtypes = [vp, C.c_int32, ip, C.c_int32]
+    L.clipper_hip_batch_route.argtypes = [vp, C.c_int32]
+    L.clipper_hip_batch_get_stats.argtypes = [vp, ip, ip, ip]
+    L.clipper_hip_batch_get_split.argtypes = [vp, dp, dp, dp, dp]
     _lib = L
     return L
 
@@ -648,3 +676,112 @@ def distance_based_correspondences(P0, P1, knn: int, radius: float, enforce_1to1
         raise RuntimeError(f"clipper_hip error {n}: {_last_error()}")
     n = int(n)
     return np.stack([buf[:n], buf[n:2 * n]], axis=1).astype(np.int32)
+
+
+class HipBatch:
+    """Many independent problems solved in one call (clipper_hip_batch_*). Each problem is a tuple
+    (D1, D2, A[, u0]) as HipClipper.score_pairwise_consistency_* and HipClipper.solve take them; A = () means
+    all-to-all. A missing u0 is an error (the batch does not draw one). Per problem the result equals a lone
+    HipClipper solve of the same storage on the same route (route(i) == that solve's last_solver), bit for bit,
+    except Solution.t: the wall time of the whole call."""
+
+    def __init__(self, storage: int = STORE_F32_CSC, device: int = 0):
+        self.L = load_library()
+        h = C.c_void_p()
+        self.b = None
+        if self.L.clipper_hip_batch_create(device, storage, C.byref(h)) < 0 or not h.value:
+            raise ClipperError(f"clipper_hip_batch_create failed: {_last_error()}")
+        self.b = h.value
+        self.n = 0
+
+    def close(self):
+        if getattr(self, "b", None):
+            self.L.clipper_hip_batch_destroy(self.b)
+            self.b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+        return rc
+
+    def _problems(self, problems, rows=None):
+        keep, arr = [], (BatchProblem * max(len(problems), 1))()
+        d = None
+        for i, pr in enumerate(problems):
+            if len(pr) not in (3, 4):
+                raise ValueError(f"problem {i}: expected (D1, D2, A[, u0])")
+            D1, D2 = _f64_colmajor(pr[0]), _f64_colmajor(pr[1])
+            Ac, m = _assoc_colmajor(pr[2])
+            u0 = np.ascontiguousarray(pr[3], dtype=np.float64) if len(pr) == 4 and pr[3] is not None else None
+            if D1.shape[0] != D2.shape[0]:
+                raise ValueError(f"problem {i}: D1 and D2 must have the same number of rows")
+            if d is None:
+                d = D1.shape[0]
+            elif D1.shape[0] != d:
+                raise ValueError(f"problem {i}: every problem of a batch has the same dimension")
+            mm = m if (Ac is not None and m > 0) else D1.shape[1] * D2.shape[1]
+            if u0 is not None and u0.shape != (mm,):
+                raise ValueError(f"problem {i}: u0 must have shape ({mm},)")
+            keep.append((D1, D2, Ac, u0))
+            arr[i] = BatchProblem(_dp(D1), D1.shape[1], _dp(D2), D2.shape[1],
+                                  _ip(Ac) if Ac is not None else None, m, _dp(u0) if u0 is not None else None)
+        return arr, keep, (d if d is not None else (rows or 3))
+
+    def _collect(self, n, keep):
+        out = []
+        for i in range(n):
+            info = SolveInfo()
+            m = self._check(self.L.clipper_hip_batch_get_solution(self.b, i, None, C.byref(info)))
+            u = np.zeros(max(m, 1))[:m]
+            self._check(self.L.clipper_hip_batch_get_solution(self.b, i, _dp(u), C.byref(info)))
+            nodes = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
+            k = self._check(self.L.clipper_hip_batch_get_nodes(self.b, i, _ip(nodes), nodes.size))
+            u0 = keep[i][3] if keep[i][3] is not None else np.zeros(0)
+            out.append(Solution(t=info.seconds, ifinal=info.ifinal, nodes=nodes[:k].copy(), u0=u0, u=u,
+                                score=info.score, d=info.d, n_passes=info.n_passes, n_trials=info.n_trials))
+        self.n = n
+        return out
+
+    def solve_euclidean(self, problems, sigma=0.01, epsilon=0.06, mindist=0.0, params: Params | None = None):
+        params = params or Params()
+        arr, keep, d = self._problems(problems)
+        self._check(self.L.clipper_hip_batch_solve_euclidean(self.b, arr, len(problems), d, sigma, epsilon, mindist,
+                                                             C.byref(params)))
+        return self._collect(len(problems), keep)
+
+    def solve_pointnormal(self, problems, sigp=0.5, epsp=0.5, sign=0.10, epsn=0.35, params: Params | None = None):
+        params = params or Params()
+        arr, keep, _ = self._problems(problems, rows=6)
+        self._check(self.L.clipper_hip_batch_solve_pointnormal(self.b, arr, len(problems), sigp, epsp, sign, epsn,
+                                                               C.byref(params)))
+        return self._collect(len(problems), keep)
+
+    def route(self, i: int) -> int:
+        """1 = solved in a batched resident launch, 0 = solved alone on its child context"""
+        return self._check(self.L.clipper_hip_batch_route(self.b, i))
+
+    def selected_associations(self, i: int):
+        info = SolveInfo()
+        self._check(self.L.clipper_hip_batch_get_solution(self.b, i, None, C.byref(info)))
+        k = max(info.num_nodes, 1)
+        buf = np.zeros(2 * k, dtype=np.int32)
+        kk = self._check(self.L.clipper_hip_batch_get_selected_associations(self.b, i, _ip(buf), k))
+        return np.stack([buf[:kk], buf[kk:2 * kk]], axis=1)
+
+    def stats(self):
+        """(launches, problems solved batched, problems solved alone) of the last call"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.L.clipper_hip_batch_get_stats(self.b, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def split(self):
+        """host wall time of the last call (ms): staging + fills + plans, batched launches, solved alone, rounding"""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self.L.clipper_hip_batch_get_split(self.b, *[C.byref(x) for x in v]))
+        return dict(zip(("fill_ms", "launch_ms", "alone_ms", "round_ms"), (x.value for x in v)))

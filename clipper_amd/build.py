@@ -43,7 +43,8 @@ def build_hip(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, "clipper_hip.hip"), os.path.join(CSRC, "kernels.hip.h"),
             *[os.path.join(CSRC, f) for f in ("k_solver.hip.h", "k_gemv.hip.h", "k_csc.hip.h", "k_slices.hip.h", "k_resident.hip.h", "host_resident.hpp", "k_rv_resident.hip.h", "host_rv_resident.hpp",
                                               "k_affinity.hip.h", "k_matrix.hip.h", "k_rowview.hip.h", "k_subproblem.hip.h", "k_knn.hip.h", "k_maxclique.hip.h")],
-            *[os.path.join(CSRC, f) for f in ("host_state.hpp", "host_solver.hpp", "host_matrix.hpp", "host_plan.hpp", "host_batch.hpp", "host_rowview.hpp", "host_subproblem.hpp", "host_registration.hpp", "host_maxclique.hpp")],
+            *[os.path.join(CSRC, f) for f in ("host_state.hpp", "host_solver.hpp", "host_matrix.hpp", "host_plan.hpp", "host_batch.hpp", "host_rowview.hpp", "host_subproblem.hpp", "host_registration.hpp", "host_maxclique.hpp",
+                                              "host_batchsolve.hpp", "host_batchpack.hpp")],
             os.path.join(CSRC, "dsd_host.h"),
             os.path.join(ROOT, "include", "clipper_hip.h"),
             os.path.join(ROOT, "include", "clipper_abi.h")]
@@ -65,7 +66,7 @@ def build_pymodule(force: bool = False) -> str | None:
         return None
     import pybind11
     out = pymodule_path()
-    srcs = [src, os.path.join(host, "clipper.cpp")] + [
+    srcs = [src, os.path.join(host, "clipper.cpp"), os.path.join(host, "batch.cpp")] + [
         os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(ROOT, "include")) for f in fs]
     if force or not _newer(out, srcs + [HIP_LIB]):
         _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fopenmp",
@@ -74,7 +75,7 @@ def build_pymodule(force: bool = False) -> str | None:
               "-DCLIPPER_NO_EIGEN",
               "-I", os.path.join(ROOT, "include"), "-I", pybind11.get_include(),
               "-I", sysconfig.get_paths()["include"],
-              src, os.path.join(host, "clipper.cpp"),
+              src, os.path.join(host, "clipper.cpp"), os.path.join(host, "batch.cpp"),
               "-L", LIBDIR, "-lclipper_hip", "-Wl,-rpath,$ORIGIN", "-o", out])
     return out
 

@@ -70,7 +70,45 @@ int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S,
   return 0;
 }
 
+// the pinned staging of the final u (the device writes it), large enough for this context's m
+int ensure_u_pinned(Ctx* h) {
+  const size_t vbytes = static_cast<size_t>(h->m) * sizeof(double);
+  if (h->u_pinned_cap >= vbytes) return 0;
+  if (h->u_pinned) hipHostFree(h->u_pinned);
+  h->u_pinned = nullptr;
+  h->u_pinned_dev = nullptr;
+  h->u_pinned_cap = 0;
+  HIPCHK(hipSetDevice(h->sh[0].device));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->u_pinned), vbytes,
+                       hipHostMallocMapped | hipHostMallocCoherent));
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->u_pinned_dev), h->u_pinned, 0));
+  h->u_pinned_cap = vbytes;
+  return 0;
+}
+
+// rounding — clipper.cpp:287-310 with utils.cpp:33-68, on the host (a lone solve and every problem of a batch)
+int round_nodes(Ctx* h, int rounding, const std::vector<double>& u, double F, std::vector<int32_t>& nodes) {
+  const int64_t m = static_cast<int64_t>(u.size());
+  nodes.clear();
+  if (rounding == CLIPPER_ROUNDING_NONZERO) {
+    for (int64_t i = 0; i < m; ++i)
+      if (u[static_cast<size_t>(i)] > 0.0) nodes.push_back(static_cast<int32_t>(i));
+  } else if (rounding == CLIPPER_ROUNDING_DSD) {
+    // :294-300 — exact densest subgraph of the graph induced by the non-zero entries of u
+    std::vector<int32_t> S;
+    for (int64_t i = 0; i < m; ++i)
+      if (u[static_cast<size_t>(i)] > 0.0) S.push_back(static_cast<int32_t>(i));
+    if (int rc = densest_subgraph_of(h, S, nodes)) return rc;
+  } else {
+    const int omega = static_cast<int>(std::round(F));  // :305
+    nodes = indices_of_k_largest(u, omega);             // :308
+  }
+  return 0;
+}
+
 }  // namespace
+
+#include "host_batchsolve.hpp"
 
 extern "C" {
 
@@ -158,7 +196,7 @@ void clipper_hip_destroy(clipper_hip_t* h) try {
     free_shard_buffers(s);
     if (s.ev_reduced) hipEventDestroy(s.ev_reduced);
     if (s.ev_copied) hipEventDestroy(s.ev_copied);
-    if (s.stream) hipStreamDestroy(s.stream);
+    if (s.stream && !h->borrowed_stream) hipStreamDestroy(s.stream);
   }
   if (!h->sh.empty()) hipSetDevice(h->sh[0].device);
   for (hipEvent_t e : h->ev_pairs) hipEventDestroy(e);
@@ -849,24 +887,14 @@ int clipper_hip_solve_staged(clipper_hip_t* h, const clipper_params_t* P, double
   rvr_begin_solve(h);
   sub_begin_solve(h);
   h->rvp = rowview_policy(h);
+  int rc = 0;
   // with rescaling the first iteration runs the pair pass on u0; without, it only normalises
   init.phase = P->rescale_u0 ? PH_RESCALE : PH_NORMALIZE;
   init.stage = P->rescale_u0 ? ST_PASS : ST_RESULTS;
-  if (h->u_pinned_cap < vbytes) {
-    if (h->u_pinned) hipHostFree(h->u_pinned);
-    h->u_pinned = nullptr;
-    h->u_pinned_dev = nullptr;
-    h->u_pinned_cap = 0;
-    HIPCHK(hipSetDevice(h->sh[0].device));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->u_pinned), vbytes,
-                         hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->u_pinned_dev), h->u_pinned, 0));
-    h->u_pinned_cap = vbytes;
-  }
+  if ((rc = ensure_u_pinned(h))) return rc;
   Shard& s0 = h->sh[0];
   SolveShared fin;
   std::memset(&fin, 0, sizeof(fin));
-  int rc = 0;
   bool resident = false;
   if ((rc = resident_solve(h, prm, P->rescale_u0 != 0, fin, resident))) return rc;
   h->last_solver = resident ? 1 : 0;
@@ -1070,21 +1098,8 @@ int clipper_hip_solve_staged(clipper_hip_t* h, const clipper_params_t* P, double
   std::vector<double>& u = h->u_host;  // (kept from solve to solve: no allocation on the way out)
   u.assign(h->u_pinned, h->u_pinned + m);
 
-  // rounding — clipper.cpp:287-310 with utils.cpp:33-68, on the host
   std::vector<int32_t> nodes;
-  if (P->rounding == CLIPPER_ROUNDING_NONZERO) {
-    for (int64_t i = 0; i < m; ++i)
-      if (u[static_cast<size_t>(i)] > 0.0) nodes.push_back(static_cast<int32_t>(i));
-  } else if (P->rounding == CLIPPER_ROUNDING_DSD) {
-    // :294-300 — exact densest subgraph of the graph induced by the non-zero entries of u
-    std::vector<int32_t> S;
-    for (int64_t i = 0; i < m; ++i)
-      if (u[static_cast<size_t>(i)] > 0.0) S.push_back(static_cast<int32_t>(i));
-    if ((rc = densest_subgraph_of(h, S, nodes))) return rc;
-  } else {
-    const int omega = static_cast<int>(std::round(fin.F));  // :305
-    nodes = indices_of_k_largest(u, omega);                 // :308
-  }
+  if ((rc = round_nodes(h, P->rounding, u, fin.F, nodes))) return rc;
   h->nodes = nodes;
   if (u_out) std::memcpy(u_out, u.data(), vbytes);
   mark_t("rounded");
@@ -1598,6 +1613,111 @@ int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int6
   }
   if (cus) *cus = prop.multiProcessorCount;
   if (hbm_bytes) *hbm_bytes = static_cast<int64_t>(prop.totalGlobalMem);
+  return 0;
+} CLIPPER_HIP_GUARD_INT
+
+// ---- batched solves (host_batchsolve.hpp) --------------------------------------------------------------------------
+
+int clipper_hip_batch_create(int device, int storage, clipper_hip_batch_t** out) try {
+  if (!out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range (%d visible)", device, ndev);
+  if (storage != CLIPPER_HIP_STORE_F32 && storage != CLIPPER_HIP_STORE_F64 && storage != CLIPPER_HIP_STORE_F32_CSC &&
+      storage != CLIPPER_HIP_STORE_F64_CSC)
+    return fail(CLIPPER_HIP_E_INVALID, "storage must be CLIPPER_HIP_STORE_F32, _F64, _F32_CSC or _F64_CSC");
+  clipper_hip_batch_t* b = new clipper_hip_batch_t();
+  b->device = device;
+  b->storage = storage;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete b;
+    return fail(CLIPPER_HIP_E_HIP, "cannot create a stream on device %d", device);
+  }
+  *out = b;
+  return 0;
+} CLIPPER_HIP_GUARD_INT
+
+void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
+  if (!b) return;
+  hipSetDevice(b->device);
+  if (b->stream) hipStreamSynchronize(b->stream);
+  for (Ctx* c : b->kids) clipper_hip_destroy(c);  // (they borrow the batch's stream: it goes last)
+  if (b->hstage) hipHostFree(b->hstage);
+  if (b->dstage) hipFree(b->dstage);
+  if (b->stream) hipStreamDestroy(b->stream);
+  delete b;
+} CLIPPER_HIP_GUARD_VOID
+
+int clipper_hip_batch_solve_euclidean(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n, int d,
+                                      double sigma, double epsilon, double mindist, const clipper_params_t* prm) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  const double f[3] = {sigma, epsilon, mindist};
+  return batch_solve(b, p, n, d, 1, f, prm);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_solve_pointnormal(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n,
+                                        double sigp, double epsp, double sign, double epsn,
+                                        const clipper_params_t* prm) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  const double f[4] = {sigp, epsp, sign, epsn};
+  return batch_solve(b, p, n, 6, 2, f, prm);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_solution(const clipper_hip_batch_t* b, int32_t i, double* u_out,
+                                   clipper_solve_info_t* info) try {
+  if (!b || i < 0 || static_cast<size_t>(i) >= b->res.size())
+    return fail(CLIPPER_HIP_E_INVALID, "no problem %d in the last batch", i);
+  const auto& R = b->res[static_cast<size_t>(i)];
+  if (u_out && !R.u.empty()) std::memcpy(u_out, R.u.data(), R.u.size() * sizeof(double));
+  if (info) *info = R.info;
+  return static_cast<int>(R.u.size());
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_nodes(const clipper_hip_batch_t* b, int32_t i, int32_t* nodes_out, int32_t capacity) try {
+  if (!b || !nodes_out || i < 0 || static_cast<size_t>(i) >= b->res.size())
+    return fail(CLIPPER_HIP_E_INVALID, "invalid argument (problem %d)", i);
+  const auto& nodes = b->res[static_cast<size_t>(i)].nodes;
+  const int32_t k = static_cast<int32_t>(nodes.size());
+  if (capacity < k) return fail(CLIPPER_HIP_E_INVALID, "capacity %d < %d nodes", capacity, k);
+  if (k) std::memcpy(nodes_out, nodes.data(), static_cast<size_t>(k) * sizeof(int32_t));
+  return k;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_selected_associations(const clipper_hip_batch_t* b, int32_t i, int32_t* A_out,
+                                                int32_t capacity) try {
+  if (!b || !A_out || i < 0 || static_cast<size_t>(i) >= b->res.size())
+    return fail(CLIPPER_HIP_E_INVALID, "invalid argument (problem %d)", i);
+  const auto& sel = b->res[static_cast<size_t>(i)].sel;
+  const int32_t k = static_cast<int32_t>(sel.size() / 2);
+  if (capacity < k) return fail(CLIPPER_HIP_E_INVALID, "capacity %d < %d nodes", capacity, k);
+  if (k) std::memcpy(A_out, sel.data(), sel.size() * sizeof(int32_t));
+  return k;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_route(const clipper_hip_batch_t* b, int32_t i) try {
+  if (!b || i < 0 || static_cast<size_t>(i) >= b->res.size())
+    return fail(CLIPPER_HIP_E_INVALID, "no problem %d in the last batch", i);
+  return b->res[static_cast<size_t>(i)].route;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched,
+                                int32_t* n_alone) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  if (launches) *launches = b->launches;
+  if (n_batched) *n_batched = b->n_batched;
+  if (n_alone) *n_alone = b->n_alone;
+  return 0;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_split(const clipper_hip_batch_t* b, double* fill_ms, double* launch_ms, double* alone_ms,
+                                double* round_ms) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  if (fill_ms) *fill_ms = b->t_fill;
+  if (launch_ms) *launch_ms = b->t_launch;
+  if (alone_ms) *alone_ms = b->t_alone;
+  if (round_ms) *round_ms = b->t_round;
   return 0;
 } CLIPPER_HIP_GUARD_INT
 

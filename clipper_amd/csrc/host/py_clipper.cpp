@@ -13,6 +13,7 @@
 #include <cstring>
 #include <sstream>
 
+#include "clipper/batch.h"
 #include "clipper/clipper.h"
 #include "clipper/utils.h"
 
@@ -317,4 +318,34 @@ PYBIND11_MODULE(clipperpy, m) {
         return py::dict("n_passes"_a = s.n_passes, "n_trials"_a = s.n_trials,
                         "affinity_kernel_ms"_a = s.affinity_kernel_ms, "d"_a = s.d);
       });
+
+  // an addition of this build: many problems in one call (include/clipper/batch.h)
+  py::class_<clipper::CLIPPERBatch>(m, "CLIPPERBatch")
+      .def(py::init<const clipper::invariants::PairwiseInvariantPtr&, const clipper::Params&>(), "invariant"_a,
+           "params"_a, py::keep_alive<1, 2>())
+      .def("__repr__", [](const clipper::CLIPPERBatch&) { return "<CLIPPERBatch>"; })
+      .def("set_device", &clipper::CLIPPERBatch::setDevice, "device"_a)
+      .def("set_storage", &clipper::CLIPPERBatch::setStorage, "storage"_a)
+      // problems: a list of (D1, D2, A[, u0]) with the dtypes score_pairwise_consistency / solve take (no conversion)
+      .def("solve", [](clipper::CLIPPERBatch& b, const py::sequence& problems) {
+        std::vector<clipper::BatchProblem> ps(problems.size());
+        auto load = [](const py::handle& h, auto& out, size_t i, const char* what) {
+          py::detail::make_caster<std::decay_t<decltype(out)>> c;
+          if (!c.load(h, false))
+            throw py::type_error("problem " + std::to_string(i) + ": " + what + " has the wrong type or dtype");
+          out = py::detail::cast_op<std::decay_t<decltype(out)>>(std::move(c));
+        };
+        for (size_t i = 0; i < ps.size(); ++i) {
+          const py::tuple t = problems[i].cast<py::tuple>();
+          if (t.size() != 3 && t.size() != 4)
+            throw py::value_error("problem " + std::to_string(i) + ": expected (D1, D2, A[, u0])");
+          load(t[0], ps[i].D1, i, "D1");
+          load(t[1], ps[i].D2, i, "D2");
+          load(t[2], ps[i].A, i, "A");
+          if (t.size() == 4 && !t[3].is_none()) load(t[3], ps[i].u0, i, "u0");
+        }
+        return b.solve(ps);
+      }, "problems"_a)
+      .def("get_selected_associations", &clipper::CLIPPERBatch::getSelectedAssociations, "i"_a)
+      .def("solved_batched", &clipper::CLIPPERBatch::solvedBatched, "i"_a);
 }

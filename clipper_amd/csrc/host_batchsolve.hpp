@@ -1,0 +1,373 @@
+// host_batchsolve.hpp — batched solves: many independent small problems in one call.
+// Part of clipper_hip.hip (one translation unit; included there, after the context's helpers).
+//
+// A batch owns one child context per problem slot, all on the batch's device and ONE stream (the children borrow it).
+// A call
+//   1. checks every problem (nothing reaches the device if one is invalid),
+//   2. stages all inputs (D1, D2, the association lists, u0) in one pinned buffer and copies it with ONE H2D copy,
+//   3. queues every child's fill back to back (run_affinity in its deferred mode) and waits ONCE; children whose
+//      slice arenas overflowed (the first use of a size) fill again, in a second round of their own,
+//   4. plans each child exactly as a lone solve would (the fill's own slices_plan -> resident_plan): the unit split,
+//      hence the order of every addition, is the lone solve's,
+//   5. packs the resident plans into launches of k_solve_resident_batch (host_batchpack.hpp), queues them back to
+//      back and waits once,
+//   6. solves alone, on its child context's ordinary path, every problem with no resident plan or whose launch gave
+//      up or was refused,
+//   7. rounds each problem on the host with the lone solve's code.
+// Per problem the results are bit for bit those of a lone context on the same route; only `seconds` differs (the
+// wall time of the whole call).
+#pragma once
+
+#include "host_batchpack.hpp"
+
+struct clipper_hip_batch {
+  int device = 0;
+  int storage = CLIPPER_HIP_STORE_F32_CSC;
+  hipStream_t stream = nullptr;
+  std::vector<Ctx*> kids;  // one per problem slot, kept from call to call
+  struct Result {
+    std::vector<double> u;
+    std::vector<int32_t> nodes;
+    std::vector<int32_t> sel;  // selected associations, column-major k x 2
+    clipper_solve_info_t info{};
+    int route = 0;
+  };
+  std::vector<Result> res;  // of the last call
+  int launches = 0, n_batched = 0, n_alone = 0;
+  double t_fill = 0.0, t_launch = 0.0, t_alone = 0.0, t_round = 0.0;
+  uint8_t* hstage = nullptr;  // pinned staging of the inputs, then of the launch tables
+  size_t hstage_cap = 0;
+  uint8_t* dstage = nullptr;  // its device copy
+  size_t dstage_cap = 0;
+};
+
+namespace {
+
+using Batch = clipper_hip_batch;
+
+int batch_grow(Batch* b, size_t bytes) {
+  if (bytes > b->hstage_cap) {
+    if (b->hstage) HIPCHK(hipHostFree(b->hstage));
+    b->hstage = nullptr;
+    b->hstage_cap = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b->hstage), bytes, hipHostMallocDefault));
+    b->hstage_cap = bytes;
+  }
+  if (bytes > b->dstage_cap) {
+    if (b->dstage) HIPCHK(hipFree(b->dstage));
+    b->dstage = nullptr;
+    b->dstage_cap = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&b->dstage), bytes));
+    b->dstage_cap = bytes;
+  }
+  return 0;
+}
+
+template <typename VT, int V, int E>
+int batch_launch_t(Batch* b, unsigned grid, const ResidentLaunchEntry* table, const ResidentArgs* args) {
+  auto kern = k_solve_resident_batch<VT, V, E>;
+  static std::atomic<bool> attr_set[64] = {};  // per instantiation and device
+  const int dv = (b->device >= 0 && b->device < 64) ? b->device : 0;
+  if (!attr_set[dv]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(RS_LDS_MAX)) != hipSuccess) {
+      (void)hipGetLastError();
+      return 1;  // no 159 KB of LDS for a workgroup on this device: the problems are solved alone
+    }
+    attr_set[dv] = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_NT), RS_LDS_MAX, b->stream, table, args);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+    if (rs_debug()) std::fprintf(stderr, "[batch] launch failed: %s\n", hipGetErrorString(e));
+    return 1;
+  }
+  return 0;
+}
+
+// key = VT (0: float, 1: double) * 100 + V * 10 + E
+int batch_launch(Batch* b, int key, unsigned grid, const ResidentLaunchEntry* table, const ResidentArgs* args) {
+  const bool f64 = key >= 100;
+  switch (key % 100) {
+#define BATCH_CASE(V, E)                                                                            \
+  case V * 10 + E:                                                                                  \
+    return f64 ? batch_launch_t<double, V, E>(b, grid, table, args) : batch_launch_t<float, V, E>(b, grid, table, args);
+    BATCH_CASE(1, 1)
+    BATCH_CASE(1, 2)
+    BATCH_CASE(1, 4)
+    BATCH_CASE(2, 1)
+    BATCH_CASE(2, 2)
+    BATCH_CASE(2, 4)
+#undef BATCH_CASE
+    default: return 1;
+  }
+}
+
+// kind 1: EuclideanDistance (f = {sigma, epsilon, mindist}), 2: PointNormalDistance (f = {sigp, epsp, sign, epsn})
+int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, int kind, const double* f,
+                const clipper_params_t* P) {
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  b->res.clear();
+  b->launches = b->n_batched = b->n_alone = 0;
+  b->t_fill = b->t_launch = b->t_alone = b->t_round = 0.0;
+  // ---- 1. every problem checked before any device work -------------------------------------------------------------
+  if (!P) return fail(CLIPPER_HIP_E_INVALID, "params are required");
+  if (P->rounding != CLIPPER_ROUNDING_NONZERO && P->rounding != CLIPPER_ROUNDING_DSD_HEU &&
+      P->rounding != CLIPPER_ROUNDING_DSD)
+    return fail(CLIPPER_HIP_E_INVALID, "unknown rounding mode %d", P->rounding);
+  if (P->maxlsiters < 1) return fail(CLIPPER_HIP_E_INVALID, "maxlsiters must be >= 1");
+  if (n < 0 || (n > 0 && !p)) return fail(CLIPPER_HIP_E_INVALID, "invalid problem list");
+  if (kind == 2 && d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance data are 6 x n");
+  if (d < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid dimension d = %d", d);
+  std::vector<int64_t> ms(static_cast<size_t>(n));
+  size_t bytes = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const clipper_batch_problem_t& q = p[i];
+    if (!q.D1 || !q.D2 || q.n1 < 1 || q.n2 < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %d: invalid point data", i);
+    if (!q.u0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: u0 is required", i);
+    if (q.m < 0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: m = %lld", i, static_cast<long long>(q.m));
+    const bool all = q.A == nullptr || q.m == 0;  // clipper.cpp:24 -> utils::createAllToAll, as stage_inputs
+    const int64_t m = all ? q.n1 * q.n2 : q.m;
+    if (m > 0x7fffffff) return fail(CLIPPER_HIP_E_INVALID, "problem %d: %lld associations", i, static_cast<long long>(m));
+    if (!all)
+      for (int64_t r = 0; r < m; ++r) {
+        const int32_t a0 = q.A[r], a1 = q.A[m + r];
+        if (a0 < 0 || a0 >= q.n1 || a1 < 0 || a1 >= q.n2)
+          return fail(CLIPPER_HIP_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", i,
+                      static_cast<long long>(r), a0, a1);
+      }
+    ms[static_cast<size_t>(i)] = m;
+    bytes += static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
+  }
+  b->res.resize(static_cast<size_t>(n));
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  while (b->kids.size() < static_cast<size_t>(n)) {
+    Ctx* c = make_ctx(&b->device, 1, b->storage, 1, 0, false);
+    if (!c) return CLIPPER_HIP_E_HIP;
+    hipStreamDestroy(c->sh[0].stream);
+    c->sh[0].stream = b->stream;
+    c->borrowed_stream = true;
+    b->kids.push_back(c);
+  }
+
+  // ---- 2. the inputs: one pinned buffer, one copy ------------------------------------------------------------------
+  if (int rc = batch_grow(b, bytes)) return rc;
+  std::vector<StagedInputs> dev(static_cast<size_t>(n));
+  std::vector<std::vector<int32_t>> Afull(static_cast<size_t>(n));
+  std::vector<size_t> off_u0(static_cast<size_t>(n));
+  {
+    size_t o = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      const clipper_batch_problem_t& q = p[i];
+      const int64_t m = ms[static_cast<size_t>(i)];
+      const size_t b1 = static_cast<size_t>(d) * q.n1 * 8, b2 = static_cast<size_t>(d) * q.n2 * 8;
+      const size_t o0 = o;
+      std::memcpy(b->hstage + o, q.D1, b1);
+      dev[static_cast<size_t>(i)].D1 = reinterpret_cast<const double*>(b->dstage + o);
+      o += b1;
+      std::memcpy(b->hstage + o, q.D2, b2);
+      dev[static_cast<size_t>(i)].D2 = reinterpret_cast<const double*>(b->dstage + o);
+      o += b2;
+      std::memcpy(b->hstage + o, q.u0, static_cast<size_t>(m) * 8);
+      off_u0[static_cast<size_t>(i)] = o;
+      o += static_cast<size_t>(m) * 8;
+      std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];  // the list as stage_inputs holds it
+      if (q.A == nullptr || q.m == 0) {
+        A.assign(static_cast<size_t>(2 * m), 0);
+        for (int64_t a = 0; a < q.n1; ++a)
+          for (int64_t c = 0; c < q.n2; ++c) {
+            A[static_cast<size_t>(c + a * q.n2)] = static_cast<int32_t>(a);
+            A[static_cast<size_t>(m + c + a * q.n2)] = static_cast<int32_t>(c);
+          }
+      } else {
+        A.assign(q.A, q.A + 2 * m);
+      }
+      std::memcpy(b->hstage + o, A.data(), static_cast<size_t>(m) * 8);
+      dev[static_cast<size_t>(i)].A = reinterpret_cast<const int32_t*>(b->dstage + o);
+      o = o0 + static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
+    }
+    HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, o, hipMemcpyHostToDevice, b->stream));
+  }
+
+  // ---- 3. the fills, queued back to back; one wait; the overflowed ones again ----------------------------------------
+  auto fill = [&](Ctx* c) -> int {
+    c->fill_deferred = true;
+    const int rc = kind == 1 ? clipper_hip_affinity_euclidean_staged(c, f[0], f[1], f[2], P->affinityeps)
+                             : clipper_hip_affinity_pointnormal_staged(c, f[0], f[1], f[2], f[3], P->affinityeps);
+    c->fill_deferred = false;
+    return rc;
+  };
+  for (int32_t i = 0; i < n; ++i) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    const clipper_batch_problem_t& q = p[i];
+    const int64_t m = ms[static_cast<size_t>(i)];
+    const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
+    if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
+    if (int rc = fill(c)) return rc;
+    HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
+                          hipMemcpyDeviceToDevice, b->stream));
+    c->u0_staged = true;
+  }
+  std::vector<int32_t> todo;
+  for (int32_t i = 0; i < n; ++i) todo.push_back(i);
+  for (int round = 0; !todo.empty(); ++round) {
+    HIPCHK(hipStreamSynchronize(b->stream));
+    std::vector<int32_t> again_list;
+    for (int32_t i : todo) {
+      bool again = false;
+      if (int rc = fill_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
+      if (again) again_list.push_back(i);
+    }
+    if (again_list.empty()) break;
+    if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+    for (int32_t i : again_list)
+      if (int rc = fill(b->kids[static_cast<size_t>(i)])) return rc;
+    todo.swap(again_list);
+  }
+  const auto t1 = std::chrono::high_resolution_clock::now();
+  b->t_fill = std::chrono::duration<double, std::milli>(t1 - t0).count();
+
+  // ---- 4./5. the resident plans, packed into launches ----------------------------------------------------------------
+  SolverParams prm;
+  prm.tol_u = P->tol_u;
+  prm.tol_F = P->tol_F;
+  prm.beta = P->beta;
+  prm.eps = P->eps;
+  prm.maxiniters = P->maxiniters;
+  prm.maxoliters = P->maxoliters;
+  prm.maxlsiters = P->maxlsiters;
+  long long timeout_override = 0;  // (the lone solve's test knob)
+  if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
+  std::vector<int32_t> batched, alone;
+  std::vector<ResidentArgs> args;
+  std::vector<clipper_batch::PackItem> items;
+  for (int32_t i = 0; i < n; ++i) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    if (!resident_applies(c)) {
+      alone.push_back(i);
+      continue;
+    }
+    if (int rc = ensure_u_pinned(c)) return rc;
+    ResidentArgs a = resident_args(c, prm, P->rescale_u0 != 0);
+    // the lone solve's placement-free wait: 5 ms for one pass's sums, ten times as long on a context's first launch
+    a.timeout_ticks = timeout_override ? timeout_override : 500000ll * (c->res.epoch == 0 ? 10 : 1);
+    std::memset(c->mirror, 0, sizeof(HostMirror));
+    batched.push_back(i);
+    args.push_back(a);
+    items.push_back({(c->esize() == 8 ? 100 : 0) + c->res.V * 10 + c->res.E, c->res.nunits});
+  }
+  std::atomic_thread_fence(std::memory_order_seq_cst);
+  const int cap = std::max(1, b->kids[0]->cus - 8);
+  std::vector<int> rejected;
+  const std::vector<clipper_batch::PackLaunch> L = clipper_batch::pack_launches(items, cap, &rejected);
+  std::vector<char> launched(batched.size(), 0);
+  for (int k : rejected) b->kids[static_cast<size_t>(batched[static_cast<size_t>(k)])]->res.failed = true;
+  if (!L.empty()) {
+    // launch tables behind the argument array, one copy for all launches
+    const size_t args_bytes = static_cast<size_t>(round_up(static_cast<int64_t>(args.size() * sizeof(ResidentArgs)), 256));
+    size_t nent = 0;
+    for (const auto& l : L) nent += static_cast<size_t>(l.workgroups);
+    const size_t tb = args_bytes + nent * sizeof(ResidentLaunchEntry);
+    HIPCHK(hipStreamSynchronize(b->stream));  // (the staging buffers are reused: the inputs' copy is through)
+    if (int rc = batch_grow(b, tb)) return rc;
+    std::memcpy(b->hstage, args.data(), args.size() * sizeof(ResidentArgs));
+    ResidentLaunchEntry* tab = reinterpret_cast<ResidentLaunchEntry*>(b->hstage + args_bytes);
+    size_t e = 0;
+    for (const auto& l : L)
+      for (int k : l.items)
+        for (int u = 0; u < items[static_cast<size_t>(k)].units; ++u) tab[e++] = ResidentLaunchEntry{k, u};
+    HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, tb, hipMemcpyHostToDevice, b->stream));
+    const ResidentArgs* dargs = reinterpret_cast<const ResidentArgs*>(b->dstage);
+    const ResidentLaunchEntry* dtab = reinterpret_cast<const ResidentLaunchEntry*>(b->dstage + args_bytes);
+    size_t e0 = 0;
+    for (const auto& l : L) {
+      if (batch_launch(b, l.key, static_cast<unsigned>(l.workgroups), dtab + e0, dargs) == 0) {
+        ++b->launches;
+        for (int k : l.items) launched[static_cast<size_t>(k)] = 1;
+      } else {
+        for (int k : l.items) b->kids[static_cast<size_t>(batched[static_cast<size_t>(k)])]->res.failed = true;
+      }
+      e0 += static_cast<size_t>(l.workgroups);
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  for (size_t k = 0; k < batched.size(); ++k) {
+    const int32_t i = batched[k];
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    Resident& r = c->res;
+    volatile HostMirror* hm = c->mirror;
+    if (launched[k] && hm->done) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      Batch::Result& R = b->res[static_cast<size_t>(i)];
+      R.route = 1;
+      R.info.score = hm->F;
+      R.info.d = hm->d;
+      R.info.ifinal = hm->ifinal;
+      R.info.n_passes = hm->n_passes;
+      R.info.n_trials = hm->n_trials;
+      // the epochs as the lone solve moves them
+      r.epoch += static_cast<unsigned long long>(hm->iters) + 8ull;
+      if ((r.epoch & 0xffffffffull) > 0xf0000000ull) {
+        HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, b->stream));
+        r.epoch = (r.epoch & ~0xffffffffull) + (1ull << 32);
+      }
+      c->last_solver = 1;
+      continue;
+    }
+    if (launched[k]) {  // gave up (a time-out, an LDS plan the device refused): as the lone solve does
+      uint32_t err = 0;
+      HIPCHK(hipMemcpy(&err, r.ctl, sizeof(err), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), b->stream));
+      HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, b->stream));
+      r.epoch += 1ull << 20;
+      r.last_error = static_cast<int>(err);
+      r.failed = true;  // until the next build
+      if (rs_debug()) std::fprintf(stderr, "[batch] problem %d gave up: error %u\n", i, err);
+    }
+    alone.push_back(i);
+  }
+  std::sort(alone.begin(), alone.end());
+  const auto t2 = std::chrono::high_resolution_clock::now();
+  b->t_launch = std::chrono::duration<double, std::milli>(t2 - t1).count();
+
+  // ---- 6. the others alone, on their child's ordinary path ---------------------------------------------------------
+  for (int32_t i : alone) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    Batch::Result& R = b->res[static_cast<size_t>(i)];
+    if (int rc = clipper_hip_solve_staged(c, P, nullptr, &R.info)) return rc;
+    R.route = 0;
+    R.u = c->u_host;
+    R.nodes = c->nodes;
+  }
+  const auto t3 = std::chrono::high_resolution_clock::now();
+  b->t_alone = std::chrono::duration<double, std::milli>(t3 - t2).count();
+
+  // ---- 7. rounding of the batched ones, with the lone solve's code ----------------------------------------------------
+  for (int32_t i = 0; i < n; ++i) {
+    Batch::Result& R = b->res[static_cast<size_t>(i)];
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    if (R.route == 1) {
+      c->u_host.assign(c->u_pinned, c->u_pinned + c->m);
+      if (int rc = round_nodes(c, P->rounding, c->u_host, R.info.score, R.nodes)) return rc;
+      c->nodes = R.nodes;
+      R.u = c->u_host;
+      R.info.num_nodes = static_cast<int32_t>(R.nodes.size());
+    }
+    const size_t k = R.nodes.size();  // utils::selectInlierAssociations
+    R.sel.assign(2 * k, 0);
+    for (size_t r = 0; r < k; ++r) {
+      const size_t a = static_cast<size_t>(R.nodes[r]);
+      R.sel[r] = c->A[a];
+      R.sel[k + r] = c->A[static_cast<size_t>(c->m) + a];
+    }
+  }
+  const auto t4 = std::chrono::high_resolution_clock::now();
+  b->t_round = std::chrono::duration<double, std::milli>(t4 - t3).count();
+  const double secs = std::chrono::duration<double>(t4 - t0).count();
+  for (auto& R : b->res) R.info.seconds = secs;
+  b->n_batched = static_cast<int>(std::count_if(b->res.begin(), b->res.end(), [](const Batch::Result& R) { return R.route == 1; }));
+  b->n_alone = n - b->n_batched;
+  return 0;
+}
+
+}  // namespace

@@ -536,8 +536,11 @@ int run_affinity_rect(Ctx* h, double& kernel_ms) {
 
 // `emits`: the fill kernel `launch` starts writes the slices itself when asked to
 // (k_affinity_sym, fp32) — then neither a dense store nor groups are needed
+int fill_done(Ctx* h, double build_ms);
+
 template <typename Launch>
 int run_affinity(Ctx* h, bool emits, Launch launch) {
+  h->fill_pending = false;
   h->has_matrix = false;  // until the build has succeeded (a failed rebuild leaves no matrix)
   h->csc_valid = false;
   h->total_slice_bytes = 0.0;  // (column shards: gathered again once this build's slices exist)
@@ -598,6 +601,10 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
     }
     HIPCHK(hipSetDevice(s0.device));
     HIPCHK(hipEventRecord(e1, s0.stream));
+    if (emit && h->fill_deferred) {  // a batch's fill: the batch waits once for all its problems, then fill_complete()
+      h->fill_pending = true;
+      return 0;
+    }
     const auto th0 = std::chrono::high_resolution_clock::now();
     rc = sync_all(h);
     if (rc) return rc;
@@ -628,14 +635,32 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
     }
     if (attempt >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
   }
+  return fill_done(h, build_ms);
+}
+
+// the end of a fill through run_affinity: timings, the matrix is held
+int fill_done(Ctx* h, double build_ms) {
   float ms = 0.f;
-  HIPCHK(hipSetDevice(s0.device));
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  HIPCHK(hipSetDevice(h->sh[0].device));
+  HIPCHK(hipEventElapsedTime(&ms, h->ev_aff[0], h->ev_aff[1]));
   h->tm.affinity_kernel_ms = ms + (h->csc_valid ? build_ms : 0.0);
   h->tm.affinity_bytes = h->csc_valid ? static_cast<double>(h->sh[0].s_bytes)
                                       : static_cast<double>(h->sh[0].bytes_S);
   h->has_matrix = true;
   return 0;
+}
+
+// A deferred fill (fill_pending), once the stream has drained: the directory's check and the plans, as
+// run_affinity makes them after its own wait. again = true: an arena overflowed (they have been grown) — the
+// caller repeats the fill.
+int fill_complete(Ctx* h, bool& again) {
+  again = false;
+  if (!h->fill_pending) return 0;
+  h->fill_pending = false;
+  if (int rc = emit_check(h, h->sh[0], again)) return rc;
+  if (again) return 0;
+  h->csc_valid = true;
+  return fill_done(h, 0.0);
 }
 
 constexpr int AFF_ROWS_PER_BLK = 32;

@@ -152,17 +152,17 @@ int resident_launch_v(Ctx* h, Shard& s, const ResidentArgs& a) {
   }
 }
 
-// Runs the whole solve as one launch. ran = false: the resident solver did not apply or gave up
-// (nothing of the solver state was touched: the caller runs the streaming solver).
-int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& fin, bool& ran) {
-  ran = false;
+// the current slices have a resident plan the next solve may launch
+bool resident_applies(const Ctx* h) {
+  const Resident& r = h->res;
+  return r.ready && !r.failed && h->csc_valid && h->resident_mode != 1 && h->V_forced == 0;
+}
+
+// The arguments of a resident launch of the current plan (placement-free; the caller sets the mode, the
+// home XCD and the time-out). The lone solve (below) and the batched one (host_batchsolve.hpp) both start here.
+ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   Resident& r = h->res;
-  if (rs_debug())
-    std::fprintf(stderr, "[resident] solve: ready=%d failed=%d csc_valid=%d mode=%d Vf=%d\n", r.ready, r.failed,
-                 h->csc_valid, h->resident_mode, h->V_forced);
-  if (!r.ready || r.failed || !h->csc_valid || h->resident_mode == 1 || h->V_forced != 0) return 0;
   Shard& s = h->sh[0];
-  HIPCHK(hipSetDevice(s.device));
   ResidentArgs a;
   a.M = slice_view(h, s);
   a.units = reinterpret_cast<const ResidentUnit*>(r.host_plan_dev);
@@ -187,6 +187,24 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
   a.shared = s.shared;
   a.stamps = h->stamps_dev;
   a.ctrs = r.ctl + 1;
+  a.xcd_mode = 0;
+  a.home = 0;
+  a.timeout_ticks = 0;
+  return a;
+}
+
+// Runs the whole solve as one launch. ran = false: the resident solver did not apply or gave up
+// (nothing of the solver state was touched: the caller runs the streaming solver).
+int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& fin, bool& ran) {
+  ran = false;
+  Resident& r = h->res;
+  if (rs_debug())
+    std::fprintf(stderr, "[resident] solve: ready=%d failed=%d csc_valid=%d mode=%d Vf=%d\n", r.ready, r.failed,
+                 h->csc_valid, h->resident_mode, h->V_forced);
+  if (!resident_applies(h)) return 0;
+  Shard& s = h->sh[0];
+  HIPCHK(hipSetDevice(s.device));
+  ResidentArgs a = resident_args(h, prm, rescale);
   // contexts take their home XCD in turn, so that concurrent solves of several contexts do not
   // queue for the 32 CUs of one XCD
   static std::atomic<int> next_home{0};

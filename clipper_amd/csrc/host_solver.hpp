@@ -652,8 +652,10 @@ int ensure_cap(T*& p, size_t& cap, size_t bytes) {
   return 0;
 }
 
+// dev != null: the same inputs already on the device (a batch's staging, host_batchsolve.hpp) — copied in stream
+// order, no wait
 int upload_points(Ctx* h, Shard& s, const double* D1, const double* D2, int d, int64_t n1,
-                  int64_t n2, int64_t pstride) {
+                  int64_t n2, int64_t pstride, const StagedInputs* dev = nullptr) {
   const size_t b1 = static_cast<size_t>(d) * n1 * sizeof(double);
   const size_t b2 = static_cast<size_t>(d) * n2 * sizeof(double);
   const size_t bp = static_cast<size_t>(d) * pstride * sizeof(double);
@@ -668,21 +670,27 @@ int upload_points(Ctx* h, Shard& s, const double* D1, const double* D2, int d, i
   size_t capPf2 = s.capPf;
   if ((rc = ensure_cap(s.P1f, s.capPf, bp / 2))) return rc;
   if ((rc = ensure_cap(s.P2f, capPf2, bp / 2))) return rc;
-  HIPCHK(hipMemcpyAsync(s.dD1, D1, b1, hipMemcpyHostToDevice, s.stream));
-  HIPCHK(hipMemcpyAsync(s.dD2, D2, b2, hipMemcpyHostToDevice, s.stream));
-  HIPCHK(hipMemcpyAsync(s.Adev, h->A.data(), ba, hipMemcpyHostToDevice, s.stream));
+  if (dev) {
+    HIPCHK(hipMemcpyAsync(s.dD1, dev->D1, b1, hipMemcpyDeviceToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(s.dD2, dev->D2, b2, hipMemcpyDeviceToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(s.Adev, dev->A, ba, hipMemcpyDeviceToDevice, s.stream));
+  } else {
+    HIPCHK(hipMemcpyAsync(s.dD1, D1, b1, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(s.dD2, D2, b2, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(s.Adev, h->A.data(), ba, hipMemcpyHostToDevice, s.stream));
+  }
   dim3 grid(static_cast<unsigned>(ceil_div(pstride, 256))), block(256);
   hipLaunchKernelGGL(k_gather_points, grid, block, 0, s.stream, s.dD1, d, s.Adev, h->m, pstride,
                      s.P1, s.P1f);
   hipLaunchKernelGGL(k_gather_points, grid, block, 0, s.stream, s.dD2, d, s.Adev + h->m, h->m,
                      pstride, s.P2, s.P2f);
-  HIPCHK(hipStreamSynchronize(s.stream));
+  if (!dev) HIPCHK(hipStreamSynchronize(s.stream));  // (the caller's buffers may go once this returns)
   return 0;
 }
 
 // common front part of both affinity entry points: A handling + allocation + point tables
 int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, int64_t n2,
-                 const int32_t* A, int64_t m_in) {
+                 const int32_t* A, int64_t m_in, const StagedInputs* dev = nullptr) {
   if (!h || !D1 || !D2 || d < 1 || n1 < 1 || n2 < 1)
     return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   int64_t m = m_in;
@@ -718,7 +726,7 @@ int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, 
     return fail(CLIPPER_HIP_E_SCOPE, "point tables of %d x %lld doubles exceed 4 GiB", d, static_cast<long long>(pstride));
   for (auto& s : h->sh) {
     HIPCHK(hipSetDevice(s.device));
-    rc = upload_points(h, s, D1, D2, d, n1, n2, pstride);
+    rc = upload_points(h, s, D1, D2, d, n1, n2, pstride, dev);
     if (rc) return rc;
   }
   h->staged_d = d;

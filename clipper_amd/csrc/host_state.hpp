@@ -194,6 +194,14 @@ struct Shard : SliceStore {
   RowView rv;
 };
 
+// inputs of a problem that are on the device already (a batch stages all its problems with one copy): D1, D2 as the
+// caller gave them, A as stage_inputs holds it (m x 2, column-major)
+struct StagedInputs {
+  const double* D1 = nullptr;
+  const double* D2 = nullptr;
+  const int32_t* A = nullptr;
+};
+
 // the resident solver (k_resident.hip.h): plan of the current slices and its buffers
 struct Resident {
   bool ready = false;    // the current slices fit: `plan` is valid
@@ -341,6 +349,9 @@ struct clipper_hip_ctx {
                                      // build uses it to queue the decide-only iteration behind its fill, host_rowview.hpp)
   bool early_decide_done = false;    // ... and did: the hold is lifted, the decide-only iteration is in the stream
   int resident_mode = 0;   // 0 = use the resident solver where the slices fit, 1 = never
+  bool borrowed_stream = false;  // sh[0].stream is a batch's (host_batchsolve.hpp): not this context's to destroy
+  bool fill_deferred = false;    // a batch's fill: run_affinity queues the fill and returns before the wait ...
+  bool fill_pending = false;     // ... and this says it did (fill_complete() finishes it once the stream has drained)
   int last_solver = 0;     // what the last solve ran on: 0 = streaming launches, 1 = resident
 
   // what built the matrix, kept so that a row view can be filled from the same points later:

@@ -193,8 +193,11 @@ __device__ __forceinline__ void rs_wave_pass(const uint8_t* sl, const uint32_t* 
   }
 }
 
-template <typename VT, int V, int E>
-__global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
+// The whole solve of one unit: what a workgroup of k_solve_resident (its own problem, unit = its index or, in the one-XCD
+// mode, the unit it claims) and of k_solve_resident_batch (a problem and unit from the launch table) runs. XCD: the one-XCD
+// mode's claim and its L2-only granule stores are compiled in (k_solve_resident only; the batch is placement-free).
+template <typename VT, int V, int E, bool XCD>
+__device__ __forceinline__ void rs_solve(const ResidentArgs& A, int unit) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rs_lds[];
   constexpr int NS = V + 1;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -220,8 +223,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
 
   // ---- this workgroup's unit; its slices -> LDS ----------------------------------------------
   const long long ts0 = A.stamps ? wall_clock64() : 0;
-  int unit = blockIdx.x;
-  if (A.xcd_mode) {
+  if (XCD && A.xcd_mode) {
     if (tid == 0) {
       // HW_REG_XCC_ID (id 20), bits [3:0]: which XCD this workgroup runs on
       const int xcc = static_cast<int>(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11))) & 15;
@@ -350,7 +352,7 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
         } else {  // two self-describing granules {epoch, half of the value}: the data IS the flag
           const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(sum));
           unsigned long long* gq = A.xb + ((((static_cast<int64_t>(par) * A.maxslots + U.slot) * NS + v) * mp + col) << 1);
-          if (A.xcd_mode) {  // every reader sits behind the same L2: the granules stay there
+          if (XCD && A.xcd_mode) {  // every reader sits behind the same L2: the granules stay there
             __hip_atomic_store(gq, tag | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_store(gq + 1, tag | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           } else {           // write-through: readers may sit behind another XCD's L2
@@ -719,6 +721,30 @@ __global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
       }
     }
   }
+}
+
+template <typename VT, int V, int E>
+__global__ __launch_bounds__(RS_NT) void k_solve_resident(ResidentArgs A) {
+  rs_solve<VT, V, E, true>(A, blockIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------
+// BATCHED resident solves (host_batchsolve.hpp): the units of many independent problems in one grid.
+// Workgroup b runs unit table[b].unit of problem table[b].problem with that problem's arguments;
+// problems share nothing — each has its own granules, error word, progress record, epochs and
+// time-out —, and the host never splits a problem over two launches, so no problem waits for a
+// workgroup that is not dispatched yet. Placement-free only (ResidentArgs::xcd_mode is 0).
+// ------------------------------------------------------------------------------------------
+struct ResidentLaunchEntry {
+  int problem;  // index into the launch's argument array
+  int unit;     // unit of that problem's plan
+};
+
+template <typename VT, int V, int E>
+__global__ __launch_bounds__(RS_NT) void k_solve_resident_batch(const ResidentLaunchEntry* __restrict__ table,
+                                                                const ResidentArgs* __restrict__ args) {
+  const ResidentLaunchEntry t = table[blockIdx.x];
+  rs_solve<VT, V, E, false>(args[t.problem], t.unit);
 }
 
 }  // namespace clipper_hip

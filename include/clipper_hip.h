@@ -413,6 +413,52 @@ int clipper_hip_debug_occupy(int device, int workgroups, int lds_bytes, double m
 
 int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int64_t* hbm_bytes);
 
+/* ---- batched solves: many independent small problems in one call -----------------
+ * A batch owns one child context per problem slot (kept and reused from call to call) on one device
+ * and ONE stream. A call scores every problem (the fills queued back to back, one wait for all of
+ * them), plans each problem exactly as a lone context would, runs every problem whose plan is resident
+ * (m <= 2048 on the slice storages) side by side in a few launches of k_solve_resident_batch, and solves
+ * the others — no resident plan, a dense storage, a launch that gave up or was refused — alone on their
+ * child context afterwards. Per problem the results are bit for bit those of clipper_hip_solve on a lone
+ * context of the same storage with the same inputs, u0 and params whenever both took the same route
+ * (clipper_hip_batch_route(i) == clipper_hip_last_solver of the lone context); only
+ * clipper_solve_info_t::seconds differs: it is the wall time of the whole batched call.
+ * Not a batch: explicit matrices (set_matrix / set_sparse), column shards, multi-process ranks. */
+typedef struct clipper_hip_batch clipper_hip_batch_t;
+typedef struct {                /* one problem; host buffers, read during the call only */
+  const double* D1; int64_t n1;  /* d x n1 column-major */
+  const double* D2; int64_t n2;  /* d x n2 column-major */
+  const int32_t* A; int64_t m;   /* m x 2 column-major; NULL or m = 0: all-to-all (n1 * n2) */
+  const double* u0;              /* m doubles (n1 * n2 when all-to-all), required */
+} clipper_batch_problem_t;
+/* storage: CLIPPER_HIP_STORE_* (the slice storages are the ones with a resident route). The batch is returned in
+ * *out (a status like every other entry point: the handle type is not one the C ABI's guards return). */
+int clipper_hip_batch_create(int device, int storage, clipper_hip_batch_t** out);
+void clipper_hip_batch_destroy(clipper_hip_batch_t* b);
+/* Invalid input in any problem (d, sizes, an association out of range, a missing u0) fails the whole
+ * call with CLIPPER_HIP_E_INVALID before any device work; the message names the problem's index and the
+ * batch stays usable. n = 0 is valid. The results of the previous call are dropped either way. */
+int clipper_hip_batch_solve_euclidean(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n,
+                                      int d, double sigma, double epsilon, double mindist, const clipper_params_t* prm);
+/* PointNormalDistance: every D is 6 x n (xyz + unit normal). */
+int clipper_hip_batch_solve_pointnormal(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n,
+                                        double sigp, double epsp, double sign, double epsn, const clipper_params_t* prm);
+/* Problem i of the last call: u (its m doubles; may be NULL) and the solve info; returns m. */
+int clipper_hip_batch_get_solution(const clipper_hip_batch_t* b, int32_t i, double* u_out, clipper_solve_info_t* info);
+/* Its selected nodes (ascending as the rounding leaves them, as clipper_hip_get_nodes); returns their count. */
+int clipper_hip_batch_get_nodes(const clipper_hip_batch_t* b, int32_t i, int32_t* nodes_out, int32_t capacity);
+/* Its selected associations, column-major k x 2 (as clipper_hip_get_selected_associations); returns k. */
+int clipper_hip_batch_get_selected_associations(const clipper_hip_batch_t* b, int32_t i, int32_t* A_out, int32_t capacity);
+/* 1 = solved in a batched resident launch, 0 = solved alone on its child context. */
+int clipper_hip_batch_route(const clipper_hip_batch_t* b, int32_t i);
+/* The last call: launches of k_solve_resident_batch, problems solved batched, problems solved alone.
+ * Any pointer may be NULL. */
+int clipper_hip_batch_get_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched, int32_t* n_alone);
+/* The last call's host wall time split (ms): staging + fills + plans, the batched launches (queued to
+ * finished), the problems solved alone, rounding. Any pointer may be NULL. */
+int clipper_hip_batch_get_split(const clipper_hip_batch_t* b, double* fill_ms, double* launch_ms, double* alone_ms,
+                                double* round_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,10 @@ M Monte-Carlo trials of
     within the noise bound) -> synthetic putative set -> scorePairwiseConsistency -> solve ->
     precision / recall
 with affinity and dense-clique times as the reference brackets them (main.cpp:176-188: host
-buffers in, result out). `--cpu` runs the oracle on the same inputs beside it.
-  python tools/bm_table.py [--trials 20] [--cpu] [--md out.md]
+buffers in, result out). `--cpu` runs the oracle on the same inputs beside it. `--batch` solves each
+cell's trials as ONE batch (HipBatch, DESIGN.md 10: scoring and solving of all of them in one call;
+the table then reports the batch's time per problem in both time columns' place).
+  python tools/bm_table.py [--trials 20] [--cpu] [--batch] [--md out.md]
 """
 import argparse
 import json
@@ -35,19 +37,22 @@ def main():
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--warm", type=int, default=1, help="unrecorded trials per cell")
     ap.add_argument("--md", default=None)
+    ap.add_argument("--batch", action="store_true", help="each cell's trials as one batched call")
     a = ap.parse_args()
     abi.load_library()
     pts = np.fromfile(os.path.join(ROOT, "tests", "golden", "bunny_points_4096.f32"), "<f4").reshape(-1, 3)
     pcd0 = reg.scale_to_cube(pts.astype(np.float64), 1.0)
     rng = np.random.default_rng(2022)
     g = abi.HipClipper(storage=abi.STORE_F32_CSC)
+    hb = abi.HipBatch(storage=abi.STORE_F32_CSC) if a.batch else None
     if a.cpu:
         from oracle import clipper_ref as cref
     rows = []
     t_nn = []
     for rho in OUTRATS:
         for m in NUM_ASSOCS:
-            acc = {k: [] for k in ("aff", "sol", "p", "r", "caff", "csol", "same")}
+            acc = {k: [] for k in ("aff", "sol", "p", "r", "caff", "csol", "same", "batch")}
+            cell = []  # --batch: the recorded trials' (A, Agt, pcd1, u0)
             for trial in range(-a.warm, a.trials):   # trial < 0: not recorded (first use of a size
                 pcd1 = pcd0 + reg.bounded_normal_noise(rng, len(pcd0), SIGMA, BETA)
                 t0 = time.perf_counter()
@@ -58,6 +63,9 @@ def main():
                     continue
                 A, Agt = out
                 u0 = rng.random(m)
+                if hb is not None:
+                    cell.append((A, Agt, pcd1, u0, trial))
+                    continue
                 t0 = time.perf_counter()
                 g.score_pairwise_consistency_euclidean(pcd0.T, pcd1.T, A, **INV)
                 t1 = time.perf_counter()
@@ -82,7 +90,24 @@ def main():
                     # as SETS: with a thousand near-equal entries of u the ORDER of the heap selection
                     # (utils.cpp:33-55) depends on their last bits
                     acc["same"].append(sorted(sc.nodes.tolist()) == sorted(s.nodes.tolist()))
+            if hb is not None and cell:
+                probs = [(pcd0.T, c[2].T, c[0], c[3]) for c in cell]
+                hb.solve_euclidean(probs, **INV)          # warm-up: the first use of the sizes allocates
+                rec = [k for k, c in enumerate(cell) if c[4] >= 0]
+                t0 = time.perf_counter()
+                sols = hb.solve_euclidean([probs[k] for k in rec], **INV)
+                t1 = time.perf_counter()
+                acc["batch"].append((t1 - t0) * 1e3)
+                for k, s in zip(rec, sols):
+                    p, r = reg.precision_recall(cell[k][0][s.nodes], cell[k][1])
+                    acc["p"].append(p)
+                    acc["r"].append(r)
+                    acc["aff"].append(0.0)
+                    acc["sol"].append((t1 - t0) * 1e3 / len(rec))
             row = dict(rho=rho, m=m, trials=len(acc["aff"]))
+            if acc["batch"]:
+                row["batch_ms"] = acc["batch"][0]
+                row["launches"], row["n_batched"], row["n_alone"] = hb.stats()
             for k in ("aff", "sol", "p", "r", "caff", "csol"):
                 if acc[k]:
                     row[k] = float(np.mean(acc[k]))
