@@ -1,18 +1,8 @@
-// clipper_hip.hip — host side of the C ABI declared in include/clipper_hip.h.
-//
-// Owns device memory, streams and the solve loop; all arithmetic runs in the kernels of
-// kernels.hip.h. One translation unit: host_state.hpp (context, shards, RCCL binding),
-// host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity
-// driver) are included below, then the extern "C" entry points. There is no CPU fallback anywhere in this file: if HIP is unusable the
-// entry points return an error.
-//
-// Solve loop (CLIPPER::solve -> findDenseClique, /root/reference/src/clipper.cpp:172-323):
-// the whole state machine — windowed line search, convergence tests, penalty homotopy — lives
-// in device memory (SolverState). One solver iteration = k_gemv (every workgroup decides what
-// the previous iteration's results mean, then streams M against a window of V candidate
-// vectors), then k_tail (grid: blocks x V). The host only enqueues iterations, a few ahead of
-// what the device reports as started in a pinned progress record, and stops when `done` shows
-// up there; kernels launched after convergence return immediately.
+// clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_state.hpp (context, shards,
+// RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity fills),
+// host_solve.hpp (the solve of one context) and the other host_*.hpp, then the extern "C" entry points, which check
+// their arguments and call the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no
+// CPU fallback anywhere: if HIP is unusable the entry points return an error.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -55,6 +45,8 @@ using namespace clipper_hip;
 #include "host_subproblem.hpp"
 #include "host_registration.hpp"
 #include "host_maxclique.hpp"
+#include "host_solve.hpp"
+#include "host_batchsolve.hpp"
 
 // ============================================================================================
 // brute-force nearest neighbours: launch of the two kernels for one (K, D)
@@ -70,45 +62,126 @@ int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S,
   return 0;
 }
 
-// the pinned staging of the final u (the device writes it), large enough for this context's m
-int ensure_u_pinned(Ctx* h) {
-  const size_t vbytes = static_cast<size_t>(h->m) * sizeof(double);
-  if (h->u_pinned_cap >= vbytes) return 0;
-  if (h->u_pinned) hipHostFree(h->u_pinned);
-  h->u_pinned = nullptr;
-  h->u_pinned_dev = nullptr;
-  h->u_pinned_cap = 0;
-  HIPCHK(hipSetDevice(h->sh[0].device));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->u_pinned), vbytes,
-                       hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->u_pinned_dev), h->u_pinned, 0));
-  h->u_pinned_cap = vbytes;
-  return 0;
+
+// The two fills (declared in host_matrix.hpp): defined here, behind the batch, the fill kernels keep their place in the
+// code object.
+// EuclideanDistance over the staged points: the matrix of this context
+int fill_euclidean(Ctx* h, const EuclidParams& prm) {
+  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
+  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+  const int d = h->staged_d;
+  h->fill_kind = 1;  // what a row view of this matrix is filled with later (host_rowview.hpp)
+  h->fill_e = prm;
+  h->fill_n = PointNormalParams{};
+  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsilon, h->staged_maxabs, d));
+  return run_affinity(h, use_sym_fill(h) && (d == 2 || d == 3), [&](Shard& s) {
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
+              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
+        block(256);
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    const int32_t* A0 = s.Adev;
+    const int32_t* A1 = s.Adev + mm;
+#define LAUNCH_EUCLID(T, D)                                                                 \
+  hipLaunchKernelGGL((k_affinity_euclid<T, D>), grid, block, 0, s.stream,                   \
+                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, \
+                     A0, A1, prm)
+#define LAUNCH_EUCLID_COMPACT(T, D)                                                         \
+  hipLaunchKernelGGL((k_affinity_euclid_compact<T, D>), grid, block, 0, s.stream,           \
+                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f,  \
+                     s.P2f, pstride, A0, A1, prm, thr)
+    const float thr = guarded_threshold(prm.epsilon, h->staged_maxabs, d);
+    if (use_sym_fill(h) && (d == 2 || d == 3)) {
+      const int nT = static_cast<int>(ceil_div(mm, AT));
+      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
+      const PointNormalParams none{};
+      const float E2 = guarded_threshold_sq(thr);
+      if (h->storage == CLIPPER_HIP_STORE_F64) {  // (slices with fp64 values: no dense store on this route)
+        if (d == 3)
+          launch_sym<double>(k_affinity_sym<3, false, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
+                             pstride, A0, A1, prm, none, E2, h->csc_out);
+        else
+          launch_sym<double>(k_affinity_sym<2, false, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
+                             pstride, A0, A1, prm, none, E2, h->csc_out);
+      } else if (d == 3)
+        launch_sym<float>(k_affinity_sym<3, false>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
+                          pstride, A0, A1, prm, none, E2, h->csc_out);
+      else
+        launch_sym<float>(k_affinity_sym<2, false>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
+                          pstride, A0, A1, prm, none, E2, h->csc_out);
+      h->csc_emitted = (h->csc_out.Pre != nullptr);
+      return;
+    }
+    const bool compact = !h->plain_affinity && (d == 2 || d == 3);
+    if (h->storage == CLIPPER_HIP_STORE_F64) {
+      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(double, 3);
+      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(double, 2);
+      else if (d == 3) LAUNCH_EUCLID(double, 3);
+      else if (d == 2) LAUNCH_EUCLID(double, 2);
+      else LAUNCH_EUCLID(double, 0);
+    } else {
+      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(float, 3);
+      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(float, 2);
+      else if (d == 3) LAUNCH_EUCLID(float, 3);
+      else if (d == 2) LAUNCH_EUCLID(float, 2);
+      else LAUNCH_EUCLID(float, 0);
+    }
+#undef LAUNCH_EUCLID_COMPACT
+#undef LAUNCH_EUCLID
+  });
 }
 
-// rounding — clipper.cpp:287-310 with utils.cpp:33-68, on the host (a lone solve and every problem of a batch)
-int round_nodes(Ctx* h, int rounding, const std::vector<double>& u, double F, std::vector<int32_t>& nodes) {
-  const int64_t m = static_cast<int64_t>(u.size());
-  nodes.clear();
-  if (rounding == CLIPPER_ROUNDING_NONZERO) {
-    for (int64_t i = 0; i < m; ++i)
-      if (u[static_cast<size_t>(i)] > 0.0) nodes.push_back(static_cast<int32_t>(i));
-  } else if (rounding == CLIPPER_ROUNDING_DSD) {
-    // :294-300 — exact densest subgraph of the graph induced by the non-zero entries of u
-    std::vector<int32_t> S;
-    for (int64_t i = 0; i < m; ++i)
-      if (u[static_cast<size_t>(i)] > 0.0) S.push_back(static_cast<int32_t>(i));
-    if (int rc = densest_subgraph_of(h, S, nodes)) return rc;
-  } else {
-    const int omega = static_cast<int>(std::round(F));  // :305
-    nodes = indices_of_k_largest(u, omega);             // :308
-  }
-  return 0;
+
+// PointNormalDistance over the staged points: the matrix of this context
+int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
+  if (h->staged_d != 6)
+    return fail(CLIPPER_HIP_E_STATE, "PointNormalDistance needs staged inputs with d == 6");
+  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+  h->fill_kind = 2;
+  h->fill_e = EuclidParams{};
+  h->fill_n = prm;
+  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsp, h->staged_maxabs, 3));
+  return run_affinity(h, use_sym_fill(h), [&](Shard& s) {
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
+              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
+        block(256);
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    const float thr = guarded_threshold(prm.epsp, h->staged_maxabs, 3);
+    if (use_sym_fill(h)) {
+      const int nT = static_cast<int>(ceil_div(mm, AT));
+      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
+      const EuclidParams none{};
+      if (h->storage == CLIPPER_HIP_STORE_F64)
+        launch_sym<double>(k_affinity_sym<3, true, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
+                           pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
+      else
+        launch_sym<float>(k_affinity_sym<3, true>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
+                          pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
+      h->csc_emitted = (h->csc_out.Pre != nullptr);
+      return;
+    }
+    if (h->plain_affinity) {
+      if (h->storage == CLIPPER_HIP_STORE_F64)
+        hipLaunchKernelGGL((k_affinity_pointnormal<double>), grid, block, 0, s.stream,
+                           static_cast<double*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
+                           pstride, s.Adev, s.Adev + mm, prm);
+      else
+        hipLaunchKernelGGL((k_affinity_pointnormal<float>), grid, block, 0, s.stream,
+                           static_cast<float*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
+                           pstride, s.Adev, s.Adev + mm, prm);
+    } else {
+      if (h->storage == CLIPPER_HIP_STORE_F64)
+        hipLaunchKernelGGL((k_affinity_pointnormal_compact<double>), grid, block, 0, s.stream,
+                           static_cast<double*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
+                           s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
+      else
+        hipLaunchKernelGGL((k_affinity_pointnormal_compact<float>), grid, block, 0, s.stream,
+                           static_cast<float*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
+                           s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
+    }
+  });
 }
 
 }  // namespace
-
-#include "host_batchsolve.hpp"
 
 extern "C" {
 
@@ -185,42 +258,7 @@ int clipper_hip_comm_init_callback(clipper_hip_t* h, clipper_hip_allgather_fn fn
 } CLIPPER_HIP_GUARD_INT
 
 void clipper_hip_destroy(clipper_hip_t* h) try {
-  if (!h) return;
-  for (auto& s : h->sh) {
-    hipSetDevice(s.device);
-    if (s.stream) hipStreamSynchronize(s.stream);
-  }
-  if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-  sub_free(h);  // (the live sub-problem's context borrows this one's stream: before the stream goes)
-  for (auto& s : h->sh) {
-    free_shard_buffers(s);
-    if (s.ev_reduced) hipEventDestroy(s.ev_reduced);
-    if (s.ev_copied) hipEventDestroy(s.ev_copied);
-    if (s.stream && !h->borrowed_stream) hipStreamDestroy(s.stream);
-  }
-  if (!h->sh.empty()) hipSetDevice(h->sh[0].device);
-  for (hipEvent_t e : h->ev_pairs) hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_xchg) hipEventDestroy(e);
-  if (h->ev_poll[0]) hipEventDestroy(h->ev_poll[0]);
-  if (h->ev_poll[1]) hipEventDestroy(h->ev_poll[1]);
-  if (h->host_state) hipHostFree(h->host_state);
-  if (h->mirror) hipHostFree(h->mirror);
-  if (h->kind) hipHostFree(h->kind);
-  if (h->u_pinned) hipHostFree(h->u_pinned);
-  if (h->stamps_dev) hipFree(h->stamps_dev);
-  if (h->xchg_send) hipHostFree(h->xchg_send);
-  if (h->xchg_recv) hipHostFree(h->xchg_recv);
-  if (h->ev_aff[0]) hipEventDestroy(h->ev_aff[0]);
-  if (h->ev_aff[1]) hipEventDestroy(h->ev_aff[1]);
-  if (h->csc_hLq) hipHostFree(h->csc_hLq);
-  if (h->csc_hctl) hipHostFree(h->csc_hctl);
-  if (h->csc_htotal) hipHostFree(h->csc_htotal);
-  resident_free(h);
-  rvr_free(h);
-  if (h->csc_hwork) hipHostFree(h->csc_hwork);
-  if (h->rv_count) hipHostFree(h->rv_count);
-  if (h->rv_desc_host) hipHostFree(h->rv_desc_host);
-  delete h;
+  destroy_ctx(h);
 } CLIPPER_HIP_GUARD_VOID
 
 // ---- affinity --------------------------------------------------------------------------
@@ -233,135 +271,20 @@ int clipper_hip_stage_inputs(clipper_hip_t* h, const double* D1, int d, int64_t 
 int clipper_hip_affinity_euclidean_staged(clipper_hip_t* h, double sigma, double epsilon,
                                           double mindist, double affinityeps) try {
   if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
-  const EuclidParams prm{sigma, epsilon, mindist, affinityeps};
-  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
-  const int d = h->staged_d;
-  h->fill_kind = 1;  // what a row view of this matrix is filled with later (host_rowview.hpp)
-  h->fill_e = prm;
-  h->fill_n = PointNormalParams{};
-  h->fill_E2 = guarded_threshold_sq(guarded_threshold(epsilon, h->staged_maxabs, d));
-  return run_affinity(h, use_sym_fill(h) && (d == 2 || d == 3), [&](Shard& s) {
-    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
-              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
-        block(256);
-    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
-    const int32_t* A0 = s.Adev;
-    const int32_t* A1 = s.Adev + mm;
-#define LAUNCH_EUCLID(T, D)                                                                 \
-  hipLaunchKernelGGL((k_affinity_euclid<T, D>), grid, block, 0, s.stream,                   \
-                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, \
-                     A0, A1, prm)
-#define LAUNCH_EUCLID_COMPACT(T, D)                                                         \
-  hipLaunchKernelGGL((k_affinity_euclid_compact<T, D>), grid, block, 0, s.stream,           \
-                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f,  \
-                     s.P2f, pstride, A0, A1, prm, thr)
-    const float thr = guarded_threshold(epsilon, h->staged_maxabs, d);
-    if (use_sym_fill(h) && (d == 2 || d == 3)) {
-      const int nT = static_cast<int>(ceil_div(mm, AT));
-      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
-      const PointNormalParams none{};
-      const float E2 = guarded_threshold_sq(thr);
-      if (h->storage == CLIPPER_HIP_STORE_F64) {  // (slices with fp64 values: no dense store on this route)
-        if (d == 3)
-          launch_sym<double>(k_affinity_sym<3, false, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
-                             pstride, A0, A1, prm, none, E2, h->csc_out);
-        else
-          launch_sym<double>(k_affinity_sym<2, false, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
-                             pstride, A0, A1, prm, none, E2, h->csc_out);
-      } else if (d == 3)
-        launch_sym<float>(k_affinity_sym<3, false>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
-                          pstride, A0, A1, prm, none, E2, h->csc_out);
-      else
-        launch_sym<float>(k_affinity_sym<2, false>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
-                          pstride, A0, A1, prm, none, E2, h->csc_out);
-      h->csc_emitted = (h->csc_out.Pre != nullptr);
-      return;
-    }
-    const bool compact = !h->plain_affinity && (d == 2 || d == 3);
-    if (h->storage == CLIPPER_HIP_STORE_F64) {
-      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(double, 3);
-      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(double, 2);
-      else if (d == 3) LAUNCH_EUCLID(double, 3);
-      else if (d == 2) LAUNCH_EUCLID(double, 2);
-      else LAUNCH_EUCLID(double, 0);
-    } else {
-      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(float, 3);
-      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(float, 2);
-      else if (d == 3) LAUNCH_EUCLID(float, 3);
-      else if (d == 2) LAUNCH_EUCLID(float, 2);
-      else LAUNCH_EUCLID(float, 0);
-    }
-#undef LAUNCH_EUCLID_COMPACT
-#undef LAUNCH_EUCLID
-  });
+  return fill_euclidean(h, EuclidParams{sigma, epsilon, mindist, affinityeps});
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_affinity_pointnormal_staged(clipper_hip_t* h, double sigp, double epsp,
                                             double sign, double epsn, double affinityeps) try {
   if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  if (h->staged_d != 6)
-    return fail(CLIPPER_HIP_E_STATE, "PointNormalDistance needs staged inputs with d == 6");
-  const PointNormalParams prm{sigp, epsp, sign, epsn, affinityeps};
-  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
-  h->fill_kind = 2;
-  h->fill_e = EuclidParams{};
-  h->fill_n = prm;
-  h->fill_E2 = guarded_threshold_sq(guarded_threshold(epsp, h->staged_maxabs, 3));
-  return run_affinity(h, use_sym_fill(h), [&](Shard& s) {
-    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
-              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
-        block(256);
-    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
-    const float thr = guarded_threshold(epsp, h->staged_maxabs, 3);
-    if (use_sym_fill(h)) {
-      const int nT = static_cast<int>(ceil_div(mm, AT));
-      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
-      const EuclidParams none{};
-      if (h->storage == CLIPPER_HIP_STORE_F64)
-        launch_sym<double>(k_affinity_sym<3, true, double>, g, s.stream, static_cast<double*>(nullptr), W, mm, nT, s,
-                           pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
-      else
-        launch_sym<float>(k_affinity_sym<3, true>, g, s.stream, static_cast<float*>(s.S), W, mm, nT, s,
-                          pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
-      h->csc_emitted = (h->csc_out.Pre != nullptr);
-      return;
-    }
-    if (h->plain_affinity) {
-      if (h->storage == CLIPPER_HIP_STORE_F64)
-        hipLaunchKernelGGL((k_affinity_pointnormal<double>), grid, block, 0, s.stream,
-                           static_cast<double*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
-                           pstride, s.Adev, s.Adev + mm, prm);
-      else
-        hipLaunchKernelGGL((k_affinity_pointnormal<float>), grid, block, 0, s.stream,
-                           static_cast<float*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
-                           pstride, s.Adev, s.Adev + mm, prm);
-    } else {
-      if (h->storage == CLIPPER_HIP_STORE_F64)
-        hipLaunchKernelGGL((k_affinity_pointnormal_compact<double>), grid, block, 0, s.stream,
-                           static_cast<double*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
-                           s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
-      else
-        hipLaunchKernelGGL((k_affinity_pointnormal_compact<float>), grid, block, 0, s.stream,
-                           static_cast<float*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2,
-                           s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
-    }
-  });
+  return fill_pointnormal(h, PointNormalParams{sigp, epsp, sign, epsn, affinityeps});
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_affinity_euclidean(clipper_hip_t* h, const double* D1, int d, int64_t n1,
                                    const double* D2, int64_t n2, const int32_t* A, int64_t m,
                                    double sigma, double epsilon, double mindist,
                                    double affinityeps) try {
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  int rc = stage_inputs(h, D1, d, n1, D2, n2, A, m);
-  if (rc) return rc;
-  rc = clipper_hip_affinity_euclidean_staged(h, sigma, epsilon, mindist, affinityeps);
-  if (rc) return rc;
-  h->tm.affinity_total_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0)
-          .count();
-  return 0;
+  return stage_and_fill(h, D1, d, n1, D2, n2, A, m, fill_euclidean, EuclidParams{sigma, epsilon, mindist, affinityeps});
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_affinity_pointnormal(clipper_hip_t* h, const double* D1, int d, int64_t n1,
@@ -369,15 +292,7 @@ int clipper_hip_affinity_pointnormal(clipper_hip_t* h, const double* D1, int d, 
                                      double sigp, double epsp, double sign, double epsn,
                                      double affinityeps) try {
   if (d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance needs d == 6");
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  int rc = stage_inputs(h, D1, d, n1, D2, n2, A, m);
-  if (rc) return rc;
-  rc = clipper_hip_affinity_pointnormal_staged(h, sigp, epsp, sign, epsn, affinityeps);
-  if (rc) return rc;
-  h->tm.affinity_total_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0)
-          .count();
-  return 0;
+  return stage_and_fill(h, D1, d, n1, D2, n2, A, m, fill_pointnormal, PointNormalParams{sigp, epsp, sign, epsn, affinityeps});
 } CLIPPER_HIP_GUARD_INT
 
 int64_t clipper_hip_num_associations(const clipper_hip_t* h) try {
@@ -802,404 +717,19 @@ int clipper_hip_get_matrix(clipper_hip_t* h, double* M_out, double* C_out) try {
 
 int clipper_hip_stage_u0(clipper_hip_t* h, const double* u0) try {
   if (!h || !u0) return fail(CLIPPER_HIP_E_INVALID, "u0 is required");
-  if (!h->has_matrix) return fail(CLIPPER_HIP_E_STATE, "no matrix has been built or set");
-  const size_t vbytes = static_cast<size_t>(h->m) * sizeof(double);
-  for (auto& s : h->sh) {
-    HIPCHK(hipSetDevice(s.device));
-    HIPCHK(hipMemcpyAsync(s.u0, u0, vbytes, hipMemcpyHostToDevice, s.stream));
-  }
-  int rc = sync_all(h);
-  if (rc) return rc;
-  h->u0_staged = true;
-  return 0;
+  return stage_u0(h, u0);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_solve(clipper_hip_t* h, const double* u0, const clipper_params_t* P,
                       double* u_out, clipper_solve_info_t* info) try {
   if (!h || !u0 || !P) return fail(CLIPPER_HIP_E_INVALID, "u0 and params are required");
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  int rc = clipper_hip_stage_u0(h, u0);
-  if (rc) return rc;
-  rc = clipper_hip_solve_staged(h, P, u_out, info);
-  if (rc) return rc;
-  const double secs =
-      std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-  h->tm.solve_total_ms = secs * 1e3;
-  if (info) info->seconds = secs;
-  return 0;
+  return solve(h, u0, P, u_out, info);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_solve_staged(clipper_hip_t* h, const clipper_params_t* P, double* u_out,
                              clipper_solve_info_t* info) try {
   if (!h || !P) return fail(CLIPPER_HIP_E_INVALID, "params are required");
-  if (!h->has_matrix) return fail(CLIPPER_HIP_E_STATE, "no matrix has been built or set");
-  if (!h->u0_staged) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_u0 not called");
-  if (P->rounding == CLIPPER_ROUNDING_DSD && h->multiproc)
-    return fail(CLIPPER_HIP_E_SCOPE,
-                "Rounding::DSD needs the induced sub-matrix on one host: not available on a "
-                "multi-process shard");
-  if (P->rounding != CLIPPER_ROUNDING_NONZERO && P->rounding != CLIPPER_ROUNDING_DSD_HEU &&
-      P->rounding != CLIPPER_ROUNDING_DSD)
-    return fail(CLIPPER_HIP_E_INVALID, "unknown rounding mode %d", P->rounding);
-  if (P->maxlsiters < 1) return fail(CLIPPER_HIP_E_INVALID, "maxlsiters must be >= 1");
-
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  const int64_t m = h->m;
-  const size_t vbytes = static_cast<size_t>(m) * sizeof(double);
-  // CLIPPER_HIP_HOST_TIMING: where the host side of a solve goes (us since entry, to stderr)
-  static const bool host_timing = std::getenv("CLIPPER_HIP_HOST_TIMING") != nullptr;
-  std::vector<std::pair<const char*, double>> marks_t;
-  auto mark_t = [&](const char* what) {
-    if (host_timing)
-      marks_t.emplace_back(what, std::chrono::duration<double, std::micro>(std::chrono::high_resolution_clock::now() - t0).count());
-  };
-
-  h->rv_stats = clipper_hip_view_stats_t{};
-  h->ev_used = 0;
-  std::fill(h->ev_xchg_used.begin(), h->ev_xchg_used.end(), 0);
-  if (h->profiling)  // marks of the previous solve
-  {
-    const size_t n = static_cast<size_t>(std::min<int64_t>(h->launch_counter + 1, KIND_CAP));
-    std::memset(h->kind, 0, n);
-    HIPCHK(hipSetDevice(h->sh[0].device));
-    HIPCHK(hipMemsetAsync(h->sh[0].marks, 0, n, h->sh[0].stream));
-  }
-  h->launch_counter = 0;
-
-  SolverParams prm;
-  prm.tol_u = P->tol_u;
-  prm.tol_F = P->tol_F;
-  prm.beta = P->beta;
-  prm.eps = P->eps;
-  prm.maxiniters = P->maxiniters;
-  prm.maxoliters = P->maxoliters;
-  prm.maxlsiters = P->maxlsiters;
-
-  SolverState init;
-  std::memset(&init, 0, sizeof(init));
-  init.alpha = 1.0;
-  for (int l = 0; l < VS; ++l) init.nrm[l] = 1.0;
-  init.nlive = init.nout = static_cast<int32_t>(std::min<int64_t>(m, 0x7fffffff));  // unknown until a tail counts
-  init.rv_last = -100;
-  init.weff = 0;
-  init.zero_run = 2;  // (no line search has rejected anything yet: the first windows multiply candidate 0 alone)
-  rowview_drop(h);  // a solve starts without a view: what it builds is a function of this solve alone
-  rvr_begin_solve(h);
-  sub_begin_solve(h);
-  h->rvp = rowview_policy(h);
-  int rc = 0;
-  // with rescaling the first iteration runs the pair pass on u0; without, it only normalises
-  init.phase = P->rescale_u0 ? PH_RESCALE : PH_NORMALIZE;
-  init.stage = P->rescale_u0 ? ST_PASS : ST_RESULTS;
-  if ((rc = ensure_u_pinned(h))) return rc;
-  Shard& s0 = h->sh[0];
-  SolveShared fin;
-  std::memset(&fin, 0, sizeof(fin));
-  bool resident = false;
-  if ((rc = resident_solve(h, prm, P->rescale_u0 != 0, fin, resident))) return rc;
-  h->last_solver = resident ? 1 : 0;
-  if (!resident) {
-  // prologue, one launch per shard: pending vector = u0 (T pair 0, nrm = 1), state, counters
-  h->par = 0;
-  std::memset(h->mirror, 0, sizeof(HostMirror));
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-  for (auto& s : h->sh) {
-    HIPCHK(hipSetDevice(s.device));
-    const SolveArgs a = solve_args(h, s, prm, 0);
-    hipLaunchKernelGGL(k_init, dim3(static_cast<unsigned>(ceil_div(m, 256))), dim3(256), 0,
-                       s.stream, a, init, s.st, s.X[0]);
-  }
-  mark_t("init queued");
-  if (!h->multiproc) {
-    // One process: the deciding workgroup reports progress into pinned host memory; the host
-    // keeps RUN_AHEAD iterations queued ahead of what the device has retired and stops
-    // queueing the moment `done` shows up — no memcpy, no event, no host wait in the loop.
-    volatile HostMirror* hm = h->mirror;
-    int64_t queued = 0;
-    uint64_t spins = 0;
-    h->rv_fresh = false;
-    constexpr int run_ahead = RUN_AHEAD;
-    h->enqueue_one = [h, &prm]() { return enqueue_iteration(h, prm); };
-    // (while the solve runs on the live sub-problem the same launches go out with the child context's arguments)
-    auto enqueue_next = [&]() { return enqueue_iteration(h->sub.active ? h->sub.use : h, prm); };
-    auto sub_account = [&]() {  // the passes since the hand-over ran on the sub-problem
-      h->sub.sub_passes += std::max<int64_t>(0, hm->n_passes - h->sub.passes_at_entry);
-    };
-    struct ClearEnqueue {
-      Ctx* c;
-      ~ClearEnqueue() { c->enqueue_one = nullptr; }
-    } clear_enqueue{h};
-    while (!hm->done) {
-      if (hm->hold) {
-        // The decision asked for a row view (k_solver.hip.h, LIVE ROWS) and put the solve on hold:
-        // whatever was queued behind it does nothing. Drain, build the view from exactly the state
-        // that asked, lift the hold, go on.
-        mark_t("hold seen");
-        if (host_timing)
-          std::fprintf(stderr, "[solve] hold: iters %lld passes %lld trials %lld view passes %lld live %d of which outside the view %d\n",
-                       static_cast<long long>(hm->iters), static_cast<long long>(hm->n_passes), static_cast<long long>(hm->n_trials),
-                       static_cast<long long>(hm->n_view_passes), static_cast<int>(hm->hold_nlive), static_cast<int>(hm->nout));
-        // (No drain: the iterations queued behind the hold do nothing but move the state between its two
-        // copies, in stream order — the build's launches queue behind them and read copy h->par, where the last
-        // of them leaves it; the build itself waits for the stream once. An in-process GROUP holds on every
-        // shard: its streams are drained, the shards' builds are not ordered with each other otherwise.)
-        if (h->sh.size() > 1 && (rc = sync_all(h))) return rc;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const int hold_reason = hm->hold;
-        hm->hold = 0;
-        queued = hm->iters;              // the iterations that did nothing never counted
-        h->launch_counter = hm->iters;   // (profiling: launch index = the device's iteration count)
-        while (h->ev_used > 0 && h->ev_launch_index[static_cast<size_t>(h->ev_used - 1)] >= hm->iters)
-          --h->ev_used;                  // event pairs around launches that did nothing
-        if (hold_reason == 2) {  // the hand-over to the live sub-problem (host_subproblem.hpp)
-          if ((rc = sub_enter(h, prm))) return rc;
-          ++queued;  // (its decide-only iteration)
-          mark_t("sub-problem entered");
-          continue;
-        }
-        if (hold_reason == 3) {  // ... and the way back
-          sub_account();
-          if ((rc = sub_leave(h))) return rc;
-          mark_t("sub-problem left");
-          continue;
-        }
-        bool built = false;
-        if ((rc = rowview_build(h, built))) return rc;
-        mark_t("view built");
-        const bool early = h->early_decide_done;  // the decide-only iteration went out behind the fill (host_rowview.hpp):
-        h->early_decide_done = false;             // the hold is lifted, rv_fresh was used by it
-        if (early) ++queued;
-        else h->rv_fresh = built;
-        if (built && h->vres.ready) {
-          // The view fits the LDS of the chip: the iterations on it run as ONE launch (k_rv_resident.hip.h).
-          // A decide-only iteration turns the held decision into a prepared pass; the resident launch starts
-          // from it and leaves a prepared pass (or the end of the solve) for whatever is queued behind it.
-          if (!early) {
-            h->decide_only = true;
-            rc = enqueue_iteration(h, prm);
-            h->decide_only = false;
-            if (rc) return rc;
-            ++queued;
-          }
-          bool launched = false;
-          if ((rc = rvr_enqueue(h, prm, launched))) return rc;
-          mark_t("resident queued");
-        }
-        if ((rc = rowview_finish_plan(h))) return rc;  // (a work list put off while the resident launch was prepared)
-        // a view the resident solver does not take: the live sub-problem of its rows is prepared now, and entered
-        // when the decision finds that nothing outside it can come back to life
-        if (built && !h->vres.ready && !early) {
-          // (an optimisation: if it cannot be prepared — no memory for the child's buffers — the solve goes on without)
-          if (int r2 = sub_prepare(h)) {
-            if (r2 != CLIPPER_HIP_E_NOMEM) return r2;
-            (void)hipGetLastError();
-            h->sub.ready = false;
-          }
-          mark_t("sub-problem prepared");
-        }
-        continue;
-      }
-      if (hm->iters > queued) queued = hm->iters;  // (a resident launch retired many iterations at once)
-      if (queued - hm->iters < run_ahead) {
-        if ((rc = enqueue_next())) return rc;
-        ++queued;
-        spins = 0;
-      } else if ((++spins & 0xfffff) == 0) {
-        // the device has not retired an iteration for a long time: make sure it is still alive
-        hipError_t q = hipStreamQuery(s0.stream);
-        if (q != hipSuccess && q != hipErrorNotReady)
-          return fail(CLIPPER_HIP_E_HIP, "solver stream failed: %s", hipGetErrorString(q));
-        if (q == hipSuccess && !hm->done && queued - hm->iters >= run_ahead)
-          return fail(CLIPPER_HIP_E_HIP, "solver made no progress (iters %lld of %lld queued)",
-                      static_cast<long long>(hm->iters), static_cast<long long>(queued));
-      }
-    }
-    mark_t("done seen");
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (h->sub.active) {  // the solve ended on the live sub-problem (its deciding workgroup wrote u through the list of S)
-      sub_account();
-      h->sub.active = false;
-    }
-    fin.F = hm->F;
-    fin.d = hm->d;
-    fin.n_passes = hm->n_passes;
-    fin.n_trials = hm->n_trials;
-    fin.ifinal = hm->ifinal;
-    fin.ubp = hm->ubp;
-    fin.ubv = hm->ubv;
-    h->rv_stats.view_passes = hm->n_view_passes;
-  } else {
-    // Multi-process: every rank must queue the same number of iterations (each holds a
-    // collective), so the decision to stop rests on state snapshots only, which are
-    // bit-identical on all ranks. Batch n+1 is queued before the snapshot after batch n is read.
-    int batch = SOLVE_BATCH;
-    if (const char* e = std::getenv("CLIPPER_HIP_SOLVE_BATCH")) batch = std::max(1, std::atoi(e));  // tuning knob, same on every rank
-    HIPCHK(hipSetDevice(s0.device));
-    h->rv_fresh = false;
-    rc = run_batched_with_holds(
-        batch, [&]() { return enqueue_iteration(h, prm); },
-        [&](int slot) -> int {
-          HIPCHK(hipSetDevice(s0.device));
-          HIPCHK(hipMemcpyAsync(&h->host_state[slot], s0.shared, sizeof(SolveShared),
-                                hipMemcpyDeviceToHost, s0.stream));
-          HIPCHK(hipEventRecord(h->ev_poll[slot], s0.stream));
-          return 0;
-        },
-        [&](int slot, int& st) -> int {
-          HIPCHK(hipEventSynchronize(h->ev_poll[slot]));
-          st = h->host_state[slot].done != 0 ? 1 : (h->host_state[slot].hold != 0 ? 2 : 0);
-          return 0;
-        },
-        [&]() -> int {
-          // every rank reads the hold from the same snapshot: all of them have queued the same
-          // iterations, so draining cannot wait for a peer; then each builds its columns of the view
-          if (int r2 = sync_all(h)) return r2;
-          h->mirror->hold = 0;
-          h->launch_counter = h->mirror->iters;
-          while (h->ev_used > 0 && h->ev_launch_index[static_cast<size_t>(h->ev_used - 1)] >= h->mirror->iters)
-            --h->ev_used;  // event pairs around launches that did nothing
-          bool built = false;
-          if (int r2 = rowview_build(h, built)) return r2;
-          h->rv_fresh = built;
-          // a view small enough for the resident solver: every rank runs it on a replica of the view (no exchange
-          // for the iterations inside the launch; host_rv_resident.hpp)
-          if (built)
-            if (int r2 = rvr_replica_handover(h, prm)) return r2;
-          return 0;
-        },
-        nullptr);
-    if (rc) return rc;
-    if ((rc = sync_all(h))) return rc;
-    HIPCHK(hipSetDevice(s0.device));
-    HIPCHK(hipMemcpy(&fin, s0.shared, sizeof(fin), hipMemcpyDeviceToHost));
-    h->rv_stats.view_passes = h->mirror->n_view_passes;
-  }
-
-  rvr_end_solve(h);  // (launches of the resident solver on a view that gave up: counted, the context backs off)
-  }  // !resident
-
-  // final u
-  HIPCHK(hipSetDevice(s0.device));
-  if (h->multiproc) {
-    const double* u_dev =
-        s0.pt + ((static_cast<int64_t>(fin.ubp & 1) * h->V + fin.ubv) * 2 + 0) * h->mp;
-    HIPCHK(hipMemcpyAsync(h->u_pinned, u_dev, vbytes, hipMemcpyDeviceToHost, s0.stream));
-    if (h->profiling)
-      HIPCHK(hipMemcpyAsync(h->kind, s0.marks,
-                            static_cast<size_t>(std::min<int64_t>(h->launch_counter, KIND_CAP)),
-                            hipMemcpyDeviceToHost, s0.stream));
-    if ((rc = sync_all(h))) return rc;
-  } else {
-    // one process: the deciding workgroup wrote u into the pinned buffer before it raised `done`;
-    // the few no-op launches still queued drain behind the caller's back (stream order keeps
-    // every later call behind them)
-    HIPCHK(hipGetLastError());
-  }
-  std::vector<double>& u = h->u_host;  // (kept from solve to solve: no allocation on the way out)
-  u.assign(h->u_pinned, h->u_pinned + m);
-
-  std::vector<int32_t> nodes;
-  if ((rc = round_nodes(h, P->rounding, u, fin.F, nodes))) return rc;
-  h->nodes = nodes;
-  if (u_out) std::memcpy(u_out, u.data(), vbytes);
-  mark_t("rounded");
-  if (host_timing) {
-    std::fprintf(stderr, "[solve]");
-    for (const auto& mk : marks_t) std::fprintf(stderr, " %s %.1f |", mk.first, mk.second);
-    std::fprintf(stderr, "\n");
-  }
-
-  const double secs =
-      std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-  h->tm.solve_total_ms = secs * 1e3;
-  if (info) {
-    info->score = fin.F;
-    info->seconds = secs;
-    info->d = fin.d;
-    info->ifinal = fin.ifinal;
-    info->num_nodes = static_cast<int32_t>(nodes.size());
-    info->n_passes = fin.n_passes;
-    info->n_trials = fin.n_trials;
-  }
-  h->rv_stats.passes = fin.n_passes;
-  h->rv_stats.sub_leaves = h->sub.leaves;
-  h->rv_stats.sub_passes = h->sub.sub_passes;
-  h->rv_stats.sub_build_ms = h->sub.build_ms;
-  if (h->rv_stats.sub_entries > 0 && h->sub.use) {
-    h->rv_stats.sub_rows = h->sub.nS;
-    // what a pass on it streams: the slices, or (a mostly non-zero sub-problem) the dense fp32 store
-    h->rv_stats.sub_bytes = h->sub.use->csc_valid ? static_cast<int64_t>(h->sub.use->sh[0].s_bytes)
-                                                   : static_cast<int64_t>(algorithmic_gemv_bytes(h->sub.use));
-    h->rv_stats.sub_dense = h->sub.use->csc_valid ? 0 : 1;
-  }
-
-  // mat-vec timings from the event pairs
-  h->tm.gemv_avg_us = h->tm.gemv_min_us = 0.0;
-  h->tm.gemv_launches = 0;
-  h->tm.gemv_bytes = algorithmic_gemv_bytes(h);
-  h->tm.gemv_useful_bytes = h->csc_valid ? static_cast<double>(h->sh[0].s_entries) * (h->esize() + 1.0) : h->tm.gemv_bytes;
-  if (h->profiling && h->ev_used > 0) {
-    // only launches that streamed M count: the device marked every iteration as pass (1) or
-    // transition (0); launches queued past convergence have no mark
-    const uint8_t* kind = h->kind;
-    const int64_t iters_run = std::min<int64_t>(h->launch_counter, KIND_CAP);
-    double sum = 0.0, mn = 1e30, vsum = 0.0, ssum = 0.0;
-    int64_t nreal = 0, nview = 0, nsub = 0;
-    for (int k = 0; k < h->ev_used; ++k) {
-      const int64_t li = h->ev_launch_index[static_cast<size_t>(k)];
-      if (li >= iters_run || !kind[static_cast<size_t>(li)]) continue;
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, h->ev_pairs[2 * k], h->ev_pairs[2 * k + 1]));
-      if (kind[static_cast<size_t>(li)] == 2) {  // the launch streamed the row view, not M
-        vsum += ms;
-        ++nview;
-        continue;
-      }
-      if (kind[static_cast<size_t>(li)] == 4) {  // a window pass on the live sub-problem
-        ssum += ms;
-        ++nsub;
-        continue;
-      }
-      if (kind[static_cast<size_t>(li)] == 3 || kind[static_cast<size_t>(li)] == 5) continue;  // a pair-mode pass (one vector): not the window pass the roofline is about
-      sum += ms;
-      mn = std::min<double>(mn, ms);
-      ++nreal;
-    }
-    // the exchanges of the same iterations (column shards)
-    h->tm.exchange_avg_us = 0.0;
-    h->tm.exchange_samples = 0;
-    h->tm.exchange_bytes = static_cast<double>(nslot(h->V)) * static_cast<double>(h->W) * sizeof(double);
-    {
-      double xs = 0.0;
-      int64_t nx = 0;
-      for (int k = 0; k < h->ev_used; ++k) {
-        const int64_t li = h->ev_launch_index[static_cast<size_t>(k)];
-        if (!h->ev_xchg_used[static_cast<size_t>(k)] || li >= iters_run || !kind[static_cast<size_t>(li)]) continue;
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev_xchg[2 * k], h->ev_xchg[2 * k + 1]));
-        xs += ms;
-        ++nx;
-      }
-      if (nx > 0) {
-        h->tm.exchange_avg_us = xs / static_cast<double>(nx) * 1e3;
-        h->tm.exchange_samples = nx;
-      }
-    }
-    if (nview > 0) {
-      h->rv_stats.view_pass_avg_us = vsum / static_cast<double>(nview) * 1e3;
-      h->rv_stats.view_pass_samples = nview;
-    }
-    if (nsub > 0) {
-      h->rv_stats.sub_pass_avg_us = ssum / static_cast<double>(nsub) * 1e3;
-      h->rv_stats.sub_pass_samples = nsub;
-    }
-    if (nreal > 0) {
-      h->tm.gemv_avg_us = sum / static_cast<double>(nreal) * 1e3;
-      h->tm.gemv_min_us = mn * 1e3;
-      h->tm.gemv_launches = nreal;
-    }
-  }
-  return 0;
+  return solve_staged(h, P, u_out, info);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_get_nodes(const clipper_hip_t* h, int32_t* out, int32_t capacity) try {
@@ -1255,12 +785,12 @@ int clipper_hip_densest_subgraph(clipper_hip_t* h, const int32_t* S, int32_t k, 
 
 int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, clipper_maxclique_info_t* info) try {
   if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  return clipper_hip_max_clique_impl(h, method, time_limit_s, info);
+  return max_clique_impl(h, method, time_limit_s, info);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out) try {
   if (!h || !core_out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  return clipper_hip_core_numbers_impl(h, core_out);
+  return core_numbers_impl(h, core_out);
 } CLIPPER_HIP_GUARD_INT
 
 // ---- putative associations (before the path): brute-force nearest neighbours -------------------
@@ -1643,7 +1173,7 @@ void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
   if (!b) return;
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  for (Ctx* c : b->kids) clipper_hip_destroy(c);  // (they borrow the batch's stream: it goes last)
+  for (Ctx* c : b->kids) destroy_ctx(c);  // (they borrow the batch's stream: it goes last)
   if (b->hstage) hipHostFree(b->hstage);
   if (b->dstage) hipFree(b->dstage);
   if (b->stream) hipStreamDestroy(b->stream);

@@ -110,32 +110,22 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   b->launches = b->n_batched = b->n_alone = 0;
   b->t_fill = b->t_launch = b->t_alone = b->t_round = 0.0;
   // ---- 1. every problem checked before any device work -------------------------------------------------------------
-  if (!P) return fail(CLIPPER_HIP_E_INVALID, "params are required");
-  if (P->rounding != CLIPPER_ROUNDING_NONZERO && P->rounding != CLIPPER_ROUNDING_DSD_HEU &&
-      P->rounding != CLIPPER_ROUNDING_DSD)
-    return fail(CLIPPER_HIP_E_INVALID, "unknown rounding mode %d", P->rounding);
-  if (P->maxlsiters < 1) return fail(CLIPPER_HIP_E_INVALID, "maxlsiters must be >= 1");
+  SolverParams prm;
+  if (int rc = solver_params(P, prm)) return rc;
   if (n < 0 || (n > 0 && !p)) return fail(CLIPPER_HIP_E_INVALID, "invalid problem list");
   if (kind == 2 && d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance data are 6 x n");
   if (d < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid dimension d = %d", d);
-  std::vector<int64_t> ms(static_cast<size_t>(n));
+  std::vector<std::vector<int32_t>> Afull(static_cast<size_t>(n));  // the lists as stage_inputs holds them
   size_t bytes = 0;
   for (int32_t i = 0; i < n; ++i) {
     const clipper_batch_problem_t& q = p[i];
     if (!q.D1 || !q.D2 || q.n1 < 1 || q.n2 < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %d: invalid point data", i);
     if (!q.u0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: u0 is required", i);
     if (q.m < 0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: m = %lld", i, static_cast<long long>(q.m));
-    const bool all = q.A == nullptr || q.m == 0;  // clipper.cpp:24 -> utils::createAllToAll, as stage_inputs
-    const int64_t m = all ? q.n1 * q.n2 : q.m;
+    const int64_t m = (q.A == nullptr || q.m == 0) ? q.n1 * q.n2 : q.m;  // (all pairs: association_list)
     if (m > 0x7fffffff) return fail(CLIPPER_HIP_E_INVALID, "problem %d: %lld associations", i, static_cast<long long>(m));
-    if (!all)
-      for (int64_t r = 0; r < m; ++r) {
-        const int32_t a0 = q.A[r], a1 = q.A[m + r];
-        if (a0 < 0 || a0 >= q.n1 || a1 < 0 || a1 >= q.n2)
-          return fail(CLIPPER_HIP_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", i,
-                      static_cast<long long>(r), a0, a1);
-      }
-    ms[static_cast<size_t>(i)] = m;
+    if (association_list(q.A, q.m, q.n1, q.n2, Afull[static_cast<size_t>(i)]))
+      return fail(CLIPPER_HIP_E_INVALID, "problem %d: %s", i, std::string(g_err).c_str());
     bytes += static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
   }
   b->res.resize(static_cast<size_t>(n));
@@ -153,13 +143,12 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   // ---- 2. the inputs: one pinned buffer, one copy ------------------------------------------------------------------
   if (int rc = batch_grow(b, bytes)) return rc;
   std::vector<StagedInputs> dev(static_cast<size_t>(n));
-  std::vector<std::vector<int32_t>> Afull(static_cast<size_t>(n));
   std::vector<size_t> off_u0(static_cast<size_t>(n));
   {
     size_t o = 0;
     for (int32_t i = 0; i < n; ++i) {
       const clipper_batch_problem_t& q = p[i];
-      const int64_t m = ms[static_cast<size_t>(i)];
+      const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
       const size_t b1 = static_cast<size_t>(d) * q.n1 * 8, b2 = static_cast<size_t>(d) * q.n2 * 8;
       const size_t o0 = o;
       std::memcpy(b->hstage + o, q.D1, b1);
@@ -171,18 +160,7 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
       std::memcpy(b->hstage + o, q.u0, static_cast<size_t>(m) * 8);
       off_u0[static_cast<size_t>(i)] = o;
       o += static_cast<size_t>(m) * 8;
-      std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];  // the list as stage_inputs holds it
-      if (q.A == nullptr || q.m == 0) {
-        A.assign(static_cast<size_t>(2 * m), 0);
-        for (int64_t a = 0; a < q.n1; ++a)
-          for (int64_t c = 0; c < q.n2; ++c) {
-            A[static_cast<size_t>(c + a * q.n2)] = static_cast<int32_t>(a);
-            A[static_cast<size_t>(m + c + a * q.n2)] = static_cast<int32_t>(c);
-          }
-      } else {
-        A.assign(q.A, q.A + 2 * m);
-      }
-      std::memcpy(b->hstage + o, A.data(), static_cast<size_t>(m) * 8);
+      std::memcpy(b->hstage + o, Afull[static_cast<size_t>(i)].data(), static_cast<size_t>(m) * 8);
       dev[static_cast<size_t>(i)].A = reinterpret_cast<const int32_t*>(b->dstage + o);
       o = o0 + static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
     }
@@ -192,15 +170,15 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   // ---- 3. the fills, queued back to back; one wait; the overflowed ones again ----------------------------------------
   auto fill = [&](Ctx* c) -> int {
     c->fill_deferred = true;
-    const int rc = kind == 1 ? clipper_hip_affinity_euclidean_staged(c, f[0], f[1], f[2], P->affinityeps)
-                             : clipper_hip_affinity_pointnormal_staged(c, f[0], f[1], f[2], f[3], P->affinityeps);
+    const int rc = kind == 1 ? fill_euclidean(c, EuclidParams{f[0], f[1], f[2], P->affinityeps})
+                             : fill_pointnormal(c, PointNormalParams{f[0], f[1], f[2], f[3], P->affinityeps});
     c->fill_deferred = false;
     return rc;
   };
   for (int32_t i = 0; i < n; ++i) {
     Ctx* c = b->kids[static_cast<size_t>(i)];
     const clipper_batch_problem_t& q = p[i];
-    const int64_t m = ms[static_cast<size_t>(i)];
+    const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
     const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
     if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
     if (int rc = fill(c)) return rc;
@@ -228,14 +206,6 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   b->t_fill = std::chrono::duration<double, std::milli>(t1 - t0).count();
 
   // ---- 4./5. the resident plans, packed into launches ----------------------------------------------------------------
-  SolverParams prm;
-  prm.tol_u = P->tol_u;
-  prm.tol_F = P->tol_F;
-  prm.beta = P->beta;
-  prm.eps = P->eps;
-  prm.maxiniters = P->maxiniters;
-  prm.maxoliters = P->maxoliters;
-  prm.maxlsiters = P->maxlsiters;
   long long timeout_override = 0;  // (the lone solve's test knob)
   if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
   std::vector<int32_t> batched, alone;
@@ -294,34 +264,20 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   for (size_t k = 0; k < batched.size(); ++k) {
     const int32_t i = batched[k];
     Ctx* c = b->kids[static_cast<size_t>(i)];
-    Resident& r = c->res;
     volatile HostMirror* hm = c->mirror;
     if (launched[k] && hm->done) {
       std::atomic_thread_fence(std::memory_order_acquire);
       Batch::Result& R = b->res[static_cast<size_t>(i)];
       R.route = 1;
-      R.info.score = hm->F;
-      R.info.d = hm->d;
-      R.info.ifinal = hm->ifinal;
-      R.info.n_passes = hm->n_passes;
-      R.info.n_trials = hm->n_trials;
-      // the epochs as the lone solve moves them
-      r.epoch += static_cast<unsigned long long>(hm->iters) + 8ull;
-      if ((r.epoch & 0xffffffffull) > 0xf0000000ull) {
-        HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, b->stream));
-        r.epoch = (r.epoch & ~0xffffffffull) + (1ull << 32);
-      }
+      solve_info(R.info, mirror_result(hm));
+      if (int rc = resident_finished(c, hm->iters)) return rc;  // (the epochs as the lone solve moves them)
       c->last_solver = 1;
       continue;
     }
     if (launched[k]) {  // gave up (a time-out, an LDS plan the device refused): as the lone solve does
       uint32_t err = 0;
-      HIPCHK(hipMemcpy(&err, r.ctl, sizeof(err), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), b->stream));
-      HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, b->stream));
-      r.epoch += 1ull << 20;
-      r.last_error = static_cast<int>(err);
-      r.failed = true;  // until the next build
+      if (int rc = resident_gave_up(c, err)) return rc;
+      c->res.failed = true;  // until the next build
       if (rs_debug()) std::fprintf(stderr, "[batch] problem %d gave up: error %u\n", i, err);
     }
     alone.push_back(i);
@@ -334,7 +290,7 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   for (int32_t i : alone) {
     Ctx* c = b->kids[static_cast<size_t>(i)];
     Batch::Result& R = b->res[static_cast<size_t>(i)];
-    if (int rc = clipper_hip_solve_staged(c, P, nullptr, &R.info)) return rc;
+    if (int rc = solve_staged(c, P, nullptr, &R.info)) return rc;
     R.route = 0;
     R.u = c->u_host;
     R.nodes = c->nodes;

@@ -762,4 +762,18 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
   return 0;
 }
 
+int fill_euclidean(Ctx* h, const EuclidParams& prm);  // the matrix from the staged points (clipper_hip.hip)
+int fill_pointnormal(Ctx* h, const PointNormalParams& prm);
+
+// stage_inputs, then the fill: affinity_total_ms counts both
+template <typename Params>
+int stage_and_fill(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, int64_t n2, const int32_t* A,
+                   int64_t m, int (*fill)(Ctx*, const Params&), const Params& prm) {
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  int rc = stage_inputs(h, D1, d, n1, D2, n2, A, m);
+  if (rc || (rc = fill(h, prm))) return rc;
+  h->tm.affinity_total_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+  return 0;
+}
+
 }  // namespace

@@ -104,7 +104,7 @@ int mc_graph_and_cores(Ctx* h, McBufs& b, int64_t nw, std::vector<int32_t>& deg,
   return 0;
 }
 
-int clipper_hip_max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_info_t* info) {
+int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_info_t* info) {
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   auto elapsed = [&] { return std::chrono::duration<double>(clk::now() - t0).count(); };
@@ -247,7 +247,7 @@ int clipper_hip_max_clique_impl(Ctx* h, int method, double time_limit_s, clipper
   return 0;
 }
 
-int clipper_hip_core_numbers_impl(Ctx* h, int32_t* core_out) {
+int core_numbers_impl(Ctx* h, int32_t* core_out) {
   if (int rc = mc_check_scope(h)) return rc;
   McBufs b;
   std::vector<int32_t> deg, core;

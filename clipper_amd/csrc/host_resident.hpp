@@ -193,6 +193,37 @@ ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   return a;
 }
 
+// The epochs of the exchange granules (xb). Each clear is queued on the context's stream, ahead of the next launch
+// that reads the buffer: all of them go out on that stream (a batch's children borrow the batch's).
+// The granules carry the low 32 bits of the epoch: long before they wrap, start over on a clean buffer
+int epoch_wrap(unsigned long long& epoch, void* xb, size_t bytes, hipStream_t stream) {
+  if ((epoch & 0xffffffffull) > 0xf0000000ull) {
+    HIPCHK(hipMemsetAsync(xb, 0, bytes, stream));
+    epoch = (epoch & ~0xffffffffull) + (1ull << 32);
+  }
+  return 0;
+}
+
+// a launch that finished the solve after `iters` iterations
+int resident_finished(Ctx* h, int64_t iters) {
+  Resident& r = h->res;
+  r.epoch += static_cast<unsigned long long>(iters) + 8ull;
+  return epoch_wrap(r.epoch, r.xb, r.xb_cap, h->sh[0].stream);
+}
+
+// a launch that gave up (the stream has drained): its error word; the word, the counters and the granules cleared.
+// Whether the context tries again (r.failed) is the caller's.
+int resident_gave_up(Ctx* h, uint32_t& err) {
+  Resident& r = h->res;
+  err = 0;
+  HIPCHK(hipMemcpy(&err, r.ctl, sizeof(err), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), h->sh[0].stream));
+  HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, h->sh[0].stream));
+  r.epoch += 1ull << 20;
+  r.last_error = static_cast<int>(err);
+  return 0;
+}
+
 // Runs the whole solve as one launch. ran = false: the resident solver did not apply or gave up
 // (nothing of the solver state was touched: the caller runs the streaming solver).
 int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& fin, bool& ran) {
@@ -258,11 +289,7 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
     }
     if (finished) break;
     uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, a.err, sizeof(err), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(r.ctl, 0, 4 * sizeof(unsigned long long)));  // error word, counters
-    HIPCHK(hipMemset(r.xb, 0, r.xb_cap));  // granules of the abandoned solve
-    r.epoch += 1ull << 20;
-    r.last_error = static_cast<int>(err);
+    if (int rc = resident_gave_up(h, err)) return rc;
     if (rs_debug()) std::fprintf(stderr, "[resident] gave up: error %u (one-XCD mode %d)\n", err, a.xcd_mode);
     if ((err == RS_ERR_PLAN || err == RS_ERR_TIMEOUT) && a.xcd_mode && attempt == 0 && timeout_override == 0) {
       r.xcd_off = true;  // placement-free mode from now on
@@ -272,19 +299,8 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
     return 0;
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  fin.F = hm->F;
-  fin.d = hm->d;
-  fin.n_passes = hm->n_passes;
-  fin.n_trials = hm->n_trials;
-  fin.ifinal = hm->ifinal;
-  fin.ubp = 0;
-  fin.ubv = 0;
-  r.epoch += static_cast<unsigned long long>(hm->iters) + 8ull;
-  // the granules carry the low 32 bits of the epoch: long before they wrap, start over on a clean buffer
-  if ((r.epoch & 0xffffffffull) > 0xf0000000ull) {
-    HIPCHK(hipMemset(r.xb, 0, r.xb_cap));
-    r.epoch = (r.epoch & ~0xffffffffull) + (1ull << 32);
-  }
+  fin = mirror_result(hm);
+  if (int rc = resident_finished(h, hm->iters)) return rc;
   if (rs_debug()) std::fprintf(stderr, "[resident] solved: units=%d one-XCD mode=%d passes=%lld\n", r.nunits, a.xcd_mode,
                                static_cast<long long>(fin.n_passes));
   ran = true;

@@ -336,7 +336,7 @@ int rowview_build_shard(Ctx* h, Shard& s, bool& built) {
   bool counted = false;
   bool store_gone = false;  // the store of the view in use was overwritten by this build
   bool early_done = false;  // the hold was lifted and the decide-only iteration queued behind the first fill (below)
-  const bool early_ok = h->enqueue_one != nullptr && h->sh.size() == 1 && !h->multiproc;
+  const bool early_ok = h->solve_prm != nullptr && h->sh.size() == 1 && !h->multiproc;
   h->early_decide_done = false;
   if (asked <= 0 || asked > m) {
     HIPCHK(hipStreamSynchronize(s.stream));
@@ -395,10 +395,7 @@ int rowview_build_shard(Ctx* h, Shard& s, bool& built) {
       if ((rc = rowview_put_descriptor(h, s))) return rc;
       hipLaunchKernelGGL(k_rv_resume, dim3(1), dim3(64), 0, s.stream, s.st + h->par, s.shared, 0, rvr_ctl_block(h));
       h->rv_fresh = true;
-      h->decide_only = true;
-      rc = h->enqueue_one ? h->enqueue_one() : CLIPPER_HIP_E_INTERNAL;
-      h->decide_only = false;
-      if (rc) return rc;
+      if ((rc = enqueue_iteration(h, *h->solve_prm, true))) return rc;
       early_done = true;
       v.valid = false;
       v.cur = cur0;

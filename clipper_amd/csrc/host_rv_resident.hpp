@@ -263,11 +263,7 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
   a.mp = h->mp;
   a.pt = s.pt;
   a.xb = r.xb;
-  // the granules carry the low 32 bits of the epoch: long before they wrap, start over on a clean buffer
-  if ((r.epoch & 0xffffffffull) > 0xf0000000ull) {
-    HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_bytes, s.stream));
-    r.epoch = (r.epoch & ~0xffffffffull) + (1ull << 32);
-  }
+  if (int rc = epoch_wrap(r.epoch, r.xb, r.xb_bytes, s.stream)) return rc;
   a.epoch0 = r.epoch;
   r.epoch += 1ull << 20;  // whatever this launch publishes (even if it gives up half-way) lies below the next one's
   const bool own_ctl = r.launches_this_solve < RVR_GIVEUP_SLOTS;  // (its block was zeroed by the build's k_rv_resume)
@@ -413,10 +409,7 @@ int rvr_replica_handover(Ctx* h, const SolverParams& prm) {
     r.ready = false;
     return 0;
   }
-  h->decide_only = true;
-  rc = enqueue_iteration(h, prm);
-  h->decide_only = false;
-  if (rc) return rc;
+  if ((rc = enqueue_iteration(h, prm, true))) return rc;
   HIPCHK(hipSetDevice(s.device));
   HIPCHK(hipMemcpyAsync(r.backup, s.st + h->par, sizeof(SolverState), hipMemcpyDeviceToDevice, s.stream));
   HIPCHK(hipMemcpyAsync(r.backup + sizeof(SolverState), s.shared, sizeof(SolveShared), hipMemcpyDeviceToDevice, s.stream));

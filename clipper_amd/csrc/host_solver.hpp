@@ -331,7 +331,7 @@ int exchange(Ctx* h, int nslots) {
 // arguments of the launches of ONE solver iteration: starts from state copy / table set `par`,
 // records what it decided in state copy `par ^ 1` and writes the windows of every outcome to
 // table set `par ^ 1`
-SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par) {
+SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par, bool decide_only) {
   SolveArgs a;
   a.st_cur = s.st + par;
   a.st_next = s.st + (par ^ 1);
@@ -371,7 +371,7 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par) {
   a.rv_fresh = (view && h->rv_fresh) ? 1 : 0;
   a.rv_rows = view ? static_cast<int>(s.rv.nrows) : 0;
   a.rvp = h->rvp;
-  a.decide_only = h->decide_only ? 1 : 0;
+  a.decide_only = decide_only ? 1 : 0;
   // the window in use (SolverState::weff): the pass on the slices of one shard may multiply candidate 0 alone
   a.adaptive_window = (h->csc_valid && h->world == 1 && !h->multiproc && h->sh.size() == 1 && h->adaptive_window) ? 1 : 0;
   // the live sub-problem (host_subproblem.hpp)
@@ -393,7 +393,7 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par) {
     // holds 1e300 entries — its decision, if it plans a window, hands the solve back)
     static const int test_leave = std::getenv("CLIPPER_HIP_SUB_TEST_LEAVE") ? std::atoi(std::getenv("CLIPPER_HIP_SUB_TEST_LEAVE")) : 0;
     if (test_leave > 0 && p->sub.launches_since_entry >= test_leave) a.sub_ncol = 1e300;
-  } else if (h->sub.ready && !h->sub.active && !h->decide_only) {
+  } else if (h->sub.ready && !h->sub.active && !decide_only) {
     a.sub_state = 1;
     a.sub_ncol = h->sub.ncol;
   }
@@ -403,8 +403,9 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par) {
 // One full solver iteration:
 //   one shard : k_gemv[_csc] (decision + pass) -> k_tail<V, true> (adds the tile partials itself)
 //   sharded   : k_gemv[_csc] -> k_reduce_pass (tile partials -> own block) -> exchange -> k_tail<V, false>
+// decide_only: the G launch only decides (the hand-over to the resident solver on a view or to the sub-problem)
 template <int V>
-int enqueue_iteration_v(Ctx* h, const SolverParams& prm) {
+int enqueue_iteration_v(Ctx* h, const SolverParams& prm, bool decide_only) {
   const int par = h->par;
   h->par ^= 1;
   const bool sharded = !(h->world == 1 && !h->multiproc);
@@ -419,7 +420,7 @@ int enqueue_iteration_v(Ctx* h, const SolverParams& prm) {
                     hp->ev_used < MAX_EVENT_PAIRS;
   for (auto& s : h->sh) {
     HIPCHK(hipSetDevice(s.device));
-    const SolveArgs a = solve_args(h, s, prm, par);
+    const SolveArgs a = solve_args(h, s, prm, par, decide_only);
     if (prof && &s == &s0) HIPCHK(hipEventRecord(hp->ev_pairs[2 * hp->ev_used], s.stream));
     if (h->csc_valid) launch_pass_csc<V>(h, s, a);
     else launch_pass<V>(h, s, a);
@@ -437,7 +438,7 @@ int enqueue_iteration_v(Ctx* h, const SolverParams& prm) {
   if (sharded) {
     for (auto& s : h->sh) {  // the tile partials of the pass -> this shard's block of `ab`
       HIPCHK(hipSetDevice(s.device));
-      const SolveArgs a = solve_args(h, s, prm, par);
+      const SolveArgs a = solve_args(h, s, prm, par, decide_only);
       const int64_t n = static_cast<int64_t>(nslot(V)) * h->W;
       hipLaunchKernelGGL(k_reduce_pass, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0,
                          s.stream, a, nslot(V));
@@ -452,7 +453,7 @@ int enqueue_iteration_v(Ctx* h, const SolverParams& prm) {
   }
   for (auto& s : h->sh) {
     HIPCHK(hipSetDevice(s.device));
-    const SolveArgs a = solve_args(h, s, prm, par);
+    const SolveArgs a = solve_args(h, s, prm, par, decide_only);
     dim3 grid(static_cast<unsigned>(a.nwg), V);
     // the pass on the slices builds its window from the point slot: no candidate tables to write
     const bool tables = !h->csc_valid;
@@ -472,9 +473,9 @@ int enqueue_iteration_v(Ctx* h, const SolverParams& prm) {
   return 0;
 }
 
-int enqueue_iteration(Ctx* h, const SolverParams& prm) {
+int enqueue_iteration(Ctx* h, const SolverParams& prm, bool decide_only) {
   int rc = 0;
-  dispatch_window(h, [&](auto v) { rc = enqueue_iteration_v<decltype(v)::value>(h, prm); });
+  dispatch_window(h, [&](auto v) { rc = enqueue_iteration_v<decltype(v)::value>(h, prm, decide_only); });
   return rc;
 }
 
@@ -503,6 +504,11 @@ int sync_all(Ctx* h) {
   }
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// what the deciding workgroup published at the end of a solve (HostMirror), as the solve's result
+SolveShared mirror_result(const volatile HostMirror* hm) {
+  return SolveShared{hm->F, hm->d, hm->n_passes, hm->n_trials, hm->ifinal, hm->ubp, hm->ubv, 0, 0, 0};
 }
 
 // utils::findIndicesOfkLargest (utils.cpp:33-55): min-heap of (value,index), strict '<'
@@ -541,6 +547,7 @@ std::vector<int32_t> indices_of_k_largest(const std::vector<double>& x, int k) {
   return out;
 }
 
+void destroy_ctx(Ctx* h);  // (host_solve.hpp)
 Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_slot,
               bool multiproc) {
   int ndev = 0;
@@ -566,7 +573,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
     s.slot = first_slot + p;
     if (s.device < 0 || s.device >= ndev) {
       fail(CLIPPER_HIP_E_INVALID, "device %d out of range (%d visible)", s.device, ndev);
-      clipper_hip_destroy(h);
+      destroy_ctx(h);
       return nullptr;
     }
     if (hipSetDevice(s.device) != hipSuccess ||
@@ -574,7 +581,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
         hipEventCreateWithFlags(&s.ev_reduced, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming) != hipSuccess) {
       fail(CLIPPER_HIP_E_HIP, "cannot create stream/events on device %d", s.device);
-      clipper_hip_destroy(h);
+      destroy_ctx(h);
       return nullptr;
     }
   }
@@ -600,7 +607,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
       hipEventCreateWithFlags(&h->ev_poll[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_poll[1], hipEventDisableTiming) != hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate pinned solver state");
-    clipper_hip_destroy(h);
+    destroy_ctx(h);
     return nullptr;
   }
   // progress record the deciding workgroup writes straight into host memory (coherent, mapped)
@@ -609,7 +616,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
       hipHostGetDevicePointer(reinterpret_cast<void**>(&h->mirror_dev), h->mirror, 0) !=
           hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate the pinned progress record");
-    clipper_hip_destroy(h);
+    destroy_ctx(h);
     return nullptr;
   }
   std::memset(h->mirror, 0, sizeof(HostMirror));
@@ -617,7 +624,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&h->kind_dev), h->kind, 0) != hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate the pinned iteration marks");
-    clipper_hip_destroy(h);
+    destroy_ctx(h);
     return nullptr;
   }
   std::memset(h->kind, 0, KIND_CAP);
@@ -688,29 +695,36 @@ int upload_points(Ctx* h, Shard& s, const double* D1, const double* D2, int d, i
   return 0;
 }
 
+// The association list as a context holds it (column-major m x 2): A as given, or every pair when A is null or
+// m_in is 0 (clipper.cpp:24 -> utils::createAllToAll, utils.h:61-71); each pair checked against the point counts.
+int association_list(const int32_t* A, int64_t m_in, int64_t n1, int64_t n2, std::vector<int32_t>& out) {
+  const bool all = A == nullptr || m_in == 0;
+  const int64_t m = all ? n1 * n2 : m_in;
+  if (all) {
+    out.assign(static_cast<size_t>(2 * m), 0);
+    for (int64_t i = 0; i < n1; ++i)
+      for (int64_t j = 0; j < n2; ++j) {
+        out[static_cast<size_t>(j + i * n2)] = static_cast<int32_t>(i);
+        out[static_cast<size_t>(m + j + i * n2)] = static_cast<int32_t>(j);
+      }
+  } else {
+    out.assign(A, A + 2 * m);
+  }
+  for (int64_t r = 0; r < m; ++r) {
+    const int32_t a0 = out[static_cast<size_t>(r)], a1 = out[static_cast<size_t>(m + r)];
+    if (a0 < 0 || a0 >= n1 || a1 < 0 || a1 >= n2)
+      return fail(CLIPPER_HIP_E_INVALID, "association %lld = (%d,%d) out of range", static_cast<long long>(r), a0, a1);
+  }
+  return 0;
+}
+
 // common front part of both affinity entry points: A handling + allocation + point tables
 int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, int64_t n2,
                  const int32_t* A, int64_t m_in, const StagedInputs* dev = nullptr) {
   if (!h || !D1 || !D2 || d < 1 || n1 < 1 || n2 < 1)
     return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  int64_t m = m_in;
-  if (A == nullptr || m_in == 0) {  // clipper.cpp:24 -> utils::createAllToAll (utils.h:61-71)
-    m = n1 * n2;
-    h->A.assign(static_cast<size_t>(2 * m), 0);
-    for (int64_t i = 0; i < n1; ++i)
-      for (int64_t j = 0; j < n2; ++j) {
-        h->A[static_cast<size_t>(j + i * n2)] = static_cast<int32_t>(i);
-        h->A[static_cast<size_t>(m + j + i * n2)] = static_cast<int32_t>(j);
-      }
-  } else {
-    h->A.assign(A, A + 2 * m);
-  }
-  for (int64_t r = 0; r < m; ++r) {
-    const int32_t a0 = h->A[static_cast<size_t>(r)], a1 = h->A[static_cast<size_t>(m + r)];
-    if (a0 < 0 || a0 >= n1 || a1 < 0 || a1 >= n2)
-      return fail(CLIPPER_HIP_E_INVALID, "association %lld = (%d,%d) out of range",
-                  static_cast<long long>(r), a0, a1);
-  }
+  if (int rc = association_list(A, m_in, n1, n2, h->A)) return rc;
+  const int64_t m = static_cast<int64_t>(h->A.size() / 2);
   h->nodes.clear();
   // The point tables are about to be replaced. A matrix that is still held was scored from the OLD
   // points: a row view of it must no longer be re-scored from what is staged (it would mix two point

@@ -19,7 +19,7 @@ int fail(int code, const char* fmt, ...) {
 // ---- no exception crosses the C ABI (SURVEY 8b "Error conventions") -------------------------------
 // Every entry point is a function-try-block closed by one of these: std::bad_alloc (host vectors sized by
 // the caller's nnz / m / k) becomes CLIPPER_HIP_E_NOMEM, anything else CLIPPER_HIP_E_INTERNAL, with the
-// message in clipper_hip_last_error(). tests/test_abi_exports.py scans the sources for the pairing.
+// message in clipper_hip_last_error. tests/test_abi_exports.py scans the sources for the pairing.
 int guard_fail(int code, const char* what) noexcept {
   try {
     g_err = what;
@@ -344,10 +344,8 @@ struct clipper_hip_ctx {
   int par = 0;             // which table set the next launch reads
   Resident res;
   ViewResident vres;
-  bool decide_only = false;  // the next iteration's G launch only decides (hand-over to the resident solver on a view)
-  std::function<int()> enqueue_one;  // set by a one-process solve while it runs: queues one solver iteration (the view
-                                     // build uses it to queue the decide-only iteration behind its fill, host_rowview.hpp)
-  bool early_decide_done = false;    // ... and did: the hold is lifted, the decide-only iteration is in the stream
+  const SolverParams* solve_prm = nullptr;  // while a one-process solve loops: the view build may queue its decide-only
+  bool early_decide_done = false;           // iteration (host_rowview.hpp) ... and did: the hold is lifted, it is queued
   int resident_mode = 0;   // 0 = use the resident solver where the slices fit, 1 = never
   bool borrowed_stream = false;  // sh[0].stream is a batch's (host_batchsolve.hpp): not this context's to destroy
   bool fill_deferred = false;    // a batch's fill: run_affinity queues the fill and returns before the wait ...

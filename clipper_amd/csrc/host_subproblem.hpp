@@ -33,7 +33,7 @@ void sub_free(Ctx* h) {
   for (Ctx** pc : {&sp.ctx, &sp.ctx_dense}) {
     if (*pc) {
       (*pc)->sh[0].stream = nullptr;  // (the parent's: not the child's to destroy)
-      clipper_hip_destroy(*pc);
+      destroy_ctx(*pc);
       *pc = nullptr;
     }
   }
@@ -56,7 +56,7 @@ void sub_free(Ctx* h) {
 }
 
 // the child's point tables and association pairs, gathered on the device from the parent's (stage_inputs without
-// host data); everything else of the child as after clipper_hip_stage_inputs
+// host data); everything else of the child as after stage_inputs
 int sub_stage(Ctx* h, Ctx* c, int64_t nS) {
   Shard& s = h->sh[0];
   Shard& cs = c->sh[0];
@@ -158,10 +158,7 @@ int sub_prepare_v(Ctx* h) {
       c->parent = h;
     }
     if (int r2 = sub_stage(h, c, nS)) return r2;
-    if (h->fill_kind == 1)
-      return clipper_hip_affinity_euclidean_staged(c, h->fill_e.sigma, h->fill_e.epsilon, h->fill_e.mindist, h->fill_e.affinityeps);
-    return clipper_hip_affinity_pointnormal_staged(c, h->fill_n.sigp, h->fill_n.epsp, h->fill_n.sign, h->fill_n.epsn,
-                                                   h->fill_n.affinityeps);
+    return h->fill_kind == 1 ? fill_euclidean(c, h->fill_e) : fill_pointnormal(c, h->fill_n);
   };
   const int storage = h->compressed ? (h->storage == CLIPPER_HIP_STORE_F64 ? CLIPPER_HIP_STORE_F64_CSC : CLIPPER_HIP_STORE_F32_CSC)
                                     : h->storage;
@@ -207,9 +204,7 @@ int sub_prepare(Ctx* h) {
   return rc;
 }
 
-int enqueue_iteration(Ctx* h, const SolverParams& prm);
-
-// hold = 2: the decision on the full problem found that no column outside S can come back to life. The hold is lifted,
+// HOLD_SUB_ENTER: the decision on the full problem found that no column outside S can come back to life. The hold is lifted,
 // a decide-only iteration turns the held decision into a prepared pass, the point and the state move over.
 int sub_enter(Ctx* h, const SolverParams& prm) {
   SubProblem& sp = h->sub;
@@ -219,10 +214,7 @@ int sub_enter(Ctx* h, const SolverParams& prm) {
   Shard& cs = c->sh[0];
   HIPCHK(hipSetDevice(s.device));
   hipLaunchKernelGGL(k_sub_resume, dim3(1), dim3(64), 0, s.stream, s.st + h->par, s.shared);
-  h->decide_only = true;  // (solve_args: a decide-only launch does not ask for the hand-over again)
-  int rc = enqueue_iteration(h, prm);
-  h->decide_only = false;
-  if (rc) return rc;
+  if (int rc = enqueue_iteration(h, prm, true)) return rc;  // (decide-only: it does not ask for the hand-over again)
   // the final u is written through the list of S: the rest is zero
   std::memset(h->u_pinned, 0, static_cast<size_t>(h->m) * sizeof(double));
   std::atomic_thread_fence(std::memory_order_seq_cst);
@@ -230,7 +222,6 @@ int sub_enter(Ctx* h, const SolverParams& prm) {
                      s.cab, h->mp, h->V, sp.colmap, sp.nS, cs.st, cs.shared, cs.pt, cs.cab, c->mp,
                      c->csc_valid ? static_cast<double*>(nullptr) : cs.X[0], prm.beta);
   c->par = 0;
-  c->decide_only = false;
   c->rv_fresh = false;
   sp.active = true;
   sp.entries += 1;
@@ -240,7 +231,7 @@ int sub_enter(Ctx* h, const SolverParams& prm) {
   return 0;
 }
 
-// hold = 3: the decision on the sub-problem left its pass prepared — a column outside S could come back to life under
+// HOLD_SUB_LEAVE: the decision on the sub-problem left its pass prepared — a column outside S could come back to life under
 // one of the pending candidates. The point and the state go back; the full problem's launches run that pass.
 int sub_leave(Ctx* h) {
   SubProblem& sp = h->sub;

@@ -192,6 +192,12 @@ struct HostMirror {
   int32_t hold_nlive;     // ... of this many rows (SolverState::hold_nlive)
 };
 
+// HostMirror::hold / SolverState::hold (0: none): a row view of the decided point's live rows, the hand-over to the live
+// sub-problem, the way back. SolveArgs::marks (profiling): what an iteration streamed — nothing, a window pass on M, a
+// pass on the view, a pair-mode pass on M (one vector), a window / pair-mode pass on the sub-problem.
+enum HoldReason : int32_t { HOLD_ROW_VIEW = 1, HOLD_SUB_ENTER = 2, HOLD_SUB_LEAVE = 3 };
+enum PassMark : uint8_t { MARK_NONE = 0, MARK_WINDOW = 1, MARK_VIEW = 2, MARK_PAIR = 3, MARK_SUB_WINDOW = 4, MARK_SUB_PAIR = 5 };
+
 struct SolverParams {
   double tol_u, tol_F, beta, eps;
   int32_t maxiniters, maxoliters, maxlsiters;
@@ -305,9 +311,9 @@ struct SolveArgs {
   int adaptive_window;     // 1: the decision may plan a pass on candidate 0 alone (SolverState::weff; the pass on the slices of
                            // one shard); 0: every window pass multiplies all V candidates
   // the live sub-problem (k_subproblem.hip.h)
-  int sub_state;           // 0: none. 1: a sub-problem stands ready — the decision puts the solve on hold (hold = 2)
+  int sub_state;           // 0: none. 1: a sub-problem stands ready — the decision puts the solve on hold (HOLD_SUB_ENTER)
                            // for the hand-over once no column outside it can come back to life. 2: these launches
-                           // RUN on the sub-problem — the decision hands the solve back (hold = 3) when one could
+                           // RUN on the sub-problem — the decision hands the solve back (HOLD_SUB_LEAVE) when one could
   double sub_ncol;         // stored entries among the live rows of any column outside the sub-problem, at most
   const int32_t* colmap;   // sub_state == 2: element i of the vectors is association colmap[i] of the full problem
 };
@@ -883,7 +889,6 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
   // which ran before the view existed, counted)
   if (A.rv_fresh != 0 && action != ACT_SLOW) nout = 0;
   // HOLD: this iteration decides nothing — the state it read goes on unchanged, marked with what the host is asked for
-  // (1: a row view of the decided point's live rows; 2: the hand-over to the live sub-problem)
   auto put_on_hold = [&](int reason) {
     if (writer) {  // (block-uniform; word by word: a struct copy by one thread is 66 registers)
       copy_state(A.st_next, st, tid, NT);
@@ -903,7 +908,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
   // Is it time to build a (smaller) row view? A function of the state alone; see LIVE ROWS.
   if (action == ACT_PASS && next_phase == PH_TRIAL && A.rvp.on != 0 && A.rv_fresh == 0 && A.sub_state != 2 &&
       view_wanted(A, nlive, nout, n_iters - (L.n_redo + (redo ? 1 : 0)), L.rv_builds, L.rv_last, L.rv_backoff)) {
-    put_on_hold(1);
+    put_on_hold(HOLD_ROW_VIEW);
     return false;
   }
   const bool on_view = A.in_view != nullptr && nout == 0 && action == ACT_PASS &&
@@ -911,7 +916,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
   // The live sub-problem stands ready and the window this decision leaves pending cannot bring a column outside it back
   // to life (and the view covers the live rows: they all lie inside it): hold for the hand-over.
   if (A.sub_state == 1 && A.decide_only == 0 && on_view && next_phase == PH_TRIAL && !need_pair && sub_ok) {
-    put_on_hold(2);
+    put_on_hold(HOLD_SUB_ENTER);
     return false;
   }
   // ... or these launches run ON it and the pending window could: the pass is left prepared and the solve goes back
@@ -977,9 +982,9 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
       stash->n_passes = n_passes;
       stash->view = 0;
       stash->n_view_passes = L.n_view_passes;
-      if (sub_leave) {  // (hold = 3: the host scatters the point back and goes on with the full problem's launches)
-        stash->hold = 3;
-        A.shared->hold = 3;
+      if (sub_leave) {  // (the host scatters the point back and goes on with the full problem's launches)
+        stash->hold = HOLD_SUB_LEAVE;
+        A.shared->hold = HOLD_SUB_LEAVE;
       }
     }
     if (action == ACT_DONE) {
@@ -1011,7 +1016,7 @@ __device__ __forceinline__ bool decide(const SolveArgs& A, const HeadLoads& L, d
         __hip_atomic_store(&hm->nlive, nlive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(&hm->nout, nout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(&hm->iters, n_iters, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (sub_leave) __hip_atomic_store(&hm->hold, 3, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (sub_leave) __hip_atomic_store(&hm->hold, HOLD_SUB_LEAVE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
@@ -1131,11 +1136,11 @@ __device__ __forceinline__ void flush_state(const SolveArgs& A, const SolverStat
   copy_state(A.st_next, stash, threadIdx.x, blockDim.x);
   if (threadIdx.x == 0) {
     const int64_t n_iters = stash->n_iters;
-    // what this launch streamed: 1 = a window pass on M, 2 = a pass on the row view, 3 = a pair-mode pass
-    // on M (one vector: initialisation, penalty update), 4 / 5 = a window / pair-mode pass on the live
-    // sub-problem — the pass timings keep them apart
+    // what this launch streamed (PassMark): the pass timings keep them apart
     if (A.marks != nullptr && n_iters <= KIND_CAP)
-      A.marks[n_iters - 1] = A.sub_state == 2 ? (stash->phase == PH_TRIAL ? 4 : 5) : stash->view ? 2 : (stash->phase == PH_TRIAL ? 1 : 3);
+      A.marks[n_iters - 1] = A.sub_state == 2 ? (stash->phase == PH_TRIAL ? MARK_SUB_WINDOW : MARK_SUB_PAIR)
+                             : stash->view   ? MARK_VIEW
+                                             : (stash->phase == PH_TRIAL ? MARK_WINDOW : MARK_PAIR);
     if (A.host != nullptr) {
       __hip_atomic_store(&A.host->nlive, stash->nlive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&A.host->nout, stash->nout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
