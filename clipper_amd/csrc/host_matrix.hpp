@@ -8,55 +8,35 @@ namespace {
 bool csc_applies(const Ctx* h) { return csc_possible(h) && !h->explicitC; }
 constexpr int SL_H = 1;  // sub-blocks per chunk (R = 256 rows): see k_slices.hip.h / DESIGN.md
 
-SliceView slice_view(const Ctx* h, const Shard& s) {
-  SliceView M;
-  M.data = s.sdata;
-  M.Pre = s.sPre;
-  M.work = s.swork;
-  M.nchunks = s.s_nchunks;
-  M.ncg = s.s_ncg;
-  M.nwork = s.s_nwork;
-  M.rowmap = nullptr;
-  M.nrows = h->m;
-  M.pad = 0;
-  return M;
+// the descriptor of the slices in `st` for `nrows` rows through `rowmap` (null: the rows of M)
+SliceView store_view(const SliceStore& st, const int32_t* rowmap, int64_t nrows) {
+  SliceView v{};
+  v.data = st.sdata;
+  v.Pre = st.sPre;
+  v.work = st.swork;
+  v.nchunks = st.s_nchunks;
+  v.ncg = st.s_ncg;
+  v.nwork = st.s_nwork;
+  v.rowmap = rowmap;
+  v.nrows = nrows;
+  return v;
 }
+
+SliceView slice_view(const Ctx* h, const Shard& s) { return store_view(s, nullptr, h->m); }
 
 // the row view of this shard's columns (data == null: none in use)
 SliceView row_view(const Ctx* h, const Shard& s) {
-  SliceView R{};
-  if (!s.rv.valid || !h->csc_valid) return R;
-  R.data = s.rv.st.sdata;
-  R.Pre = s.rv.st.sPre;
-  R.work = s.rv.st.swork;
-  R.nchunks = s.rv.st.s_nchunks;
-  R.ncg = s.rv.st.s_ncg;
-  R.nwork = s.rv.st.s_nwork;
-  R.rowmap = s.rv.rowmap[s.rv.cur];
-  R.nrows = s.rv.nrows;
-  return R;
+  if (!s.rv.valid || !h->csc_valid) return SliceView{};
+  return store_view(s.rv.st, s.rv.rowmap[s.rv.cur], s.rv.nrows);
 }
 
-// the replica of the view over ALL columns (column shards; data == null: none)
+// the replica of the view over ALL columns (column shards; data == null: none). No work list: nothing streams it.
 SliceView row_view_full(const Ctx* h, const Shard& s) {
-  SliceView R{};
-  if (!s.rv.valid || !s.rv.full_valid || !h->csc_valid) return R;
-  R.data = s.rv.full.sdata;
-  R.Pre = s.rv.full.sPre;
+  if (!s.rv.valid || !s.rv.full_valid || !h->csc_valid) return SliceView{};
+  SliceView R = store_view(s.rv.full, s.rv.rowmap[s.rv.cur], s.rv.nrows);
   R.work = nullptr;
-  R.nchunks = s.rv.full.s_nchunks;
-  R.ncg = s.rv.full.s_ncg;
   R.nwork = 0;
-  R.rowmap = s.rv.rowmap[s.rv.cur];
-  R.nrows = s.rv.nrows;
   return R;
-}
-
-// calls f(value type tag) for the storage's element type
-template <typename F>
-void dispatch_vt(const Ctx* h, F&& f) {
-  if (h->storage == CLIPPER_HIP_STORE_F64) f(double{});
-  else f(float{});
 }
 
 // The dense store of every local shard, allocated if it is not; with `from_csc` its content is
@@ -85,6 +65,16 @@ int ensure_dense(Ctx* h, bool from_csc) {
   return 0;
 }
 
+// the explicit constraint store of every local shard (C != pattern(M)) released
+void drop_explicit_c(Ctx* h) {
+  for (auto& s : h->sh) {
+    if (!s.Cs) continue;
+    hipSetDevice(s.device);
+    hipFree(s.Cs);
+    s.Cs = nullptr;
+  }
+}
+
 void drop_dense(Ctx* h) {
   for (auto& s : h->sh) {
     if (!s.S) continue;
@@ -94,16 +84,35 @@ void drop_dense(Ctx* h) {
   }
 }
 
+// a device array of at least `need` elements: reallocated (contents lost) when `cap` is smaller
 template <typename T>
-int grow_dev(T*& p, size_t& cap, size_t need, size_t elem = sizeof(T)) {
+int grow_dev(T*& p, size_t& cap, size_t need) {
   if (need <= cap && p) return 0;
   if (p) hipFree(p);
   p = nullptr;
   cap = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(need, 1) * elem));
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(need, 1) * sizeof(T)));
   cap = need;
   return 0;
 }
+
+// A small copy between pinned host memory and the device: a k_copy_words launch of `grid` workgroups through the
+// mapped pointer of `pinned` (a launch beats a DMA copy at these sizes), hipMemcpyAsync when the copy is larger than
+// `max_bytes` or the pointer is not mapped. `bytes` is a multiple of 16.
+int copy_small(hipStream_t st, void* pinned, void* dev, size_t bytes, bool to_dev, unsigned grid, size_t max_bytes) {
+  void* mapped = nullptr;
+  if (bytes <= max_bytes && hipHostGetDevicePointer(&mapped, pinned, 0) == hipSuccess && mapped) {
+    hipLaunchKernelGGL(k_copy_words, dim3(grid), dim3(256), 0, st, static_cast<const uint4*>(to_dev ? mapped : dev),
+                       static_cast<uint4*>(to_dev ? dev : mapped), static_cast<int64_t>(bytes / 16));
+  } else {
+    (void)hipGetLastError();
+    HIPCHK(hipMemcpyAsync(to_dev ? dev : pinned, to_dev ? pinned : dev, bytes,
+                          to_dev ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+// the grid of a copy_small of `bytes`: a 256-lane workgroup per 4 KB, at most 64
+unsigned copy_grid(size_t bytes) { return static_cast<unsigned>(std::min<size_t>(ceil_div(bytes / 16, 256), 64)); }
 
 // the per-slice arrays (directory, sizes, costs) of the store `st` (this shard's columns x `nrows`
 // rows) and the pinned staging of this build
@@ -144,6 +153,18 @@ int slices_arrays(Ctx* h, Shard& sh, SliceStore& s, int64_t nrows, int64_t wcols
 }
 int slices_arrays(Ctx* h, Shard& s) { return slices_arrays(h, s, s, h->m); }
 
+// the arenas' start values, `units` split evenly, in the second half of the pinned counters (what the device starts from)
+CscBuildCtl* arena_init(Ctx* h, size_t units) {
+  CscBuildCtl* init = h->csc_hctl + CSC_ARENAS;
+  for (int k = 0; k < CSC_ARENAS; ++k) {
+    init[k].cursor = 0;
+    init[k].capacity = units / CSC_ARENAS;
+    init[k].origin = static_cast<unsigned long long>(k) * (units / CSC_ARENAS);
+    init[k].overflow = 0;
+  }
+  return init;
+}
+
 // Before a fill that writes the slices itself (k_affinity_sym): the arenas of the slice store
 // reset. out.Pre == null: compressed storage not in use.
 int emit_prepare(Ctx* h, Shard& sh, SliceStore& s, int64_t nrows, SliceOut& out, int64_t wcols = -1) {
@@ -151,24 +172,12 @@ int emit_prepare(Ctx* h, Shard& sh, SliceStore& s, int64_t nrows, SliceOut& out,
   if (!csc_applies(h)) return 0;
   if (int rc = slices_arrays(h, sh, s, nrows, wcols)) return rc;
   const size_t units = s.scap_bytes >= SL_TAILPAD ? (s.scap_bytes - SL_TAILPAD) / 16 : 0;
-  CscBuildCtl* init = h->csc_hctl + CSC_ARENAS;  // second half: what the device starts from
-  for (int k = 0; k < CSC_ARENAS; ++k) {
-    init[k].cursor = 0;
-    init[k].capacity = units / CSC_ARENAS;
-    init[k].origin = static_cast<unsigned long long>(k) * (units / CSC_ARENAS);
-    init[k].overflow = 0;
-  }
+  CscBuildCtl* init = arena_init(h, units);
   // the counters live right behind this build's directory words: both come back in ONE copy
   CscBuildCtl* ectl = reinterpret_cast<CscBuildCtl*>(
       s.sLq + round_up(static_cast<int64_t>(s.s_ncg) * s.s_nchunks, 32));
-  void* idev = nullptr;
-  if (hipHostGetDevicePointer(&idev, init, 0) == hipSuccess && idev) {  // 2 KB: a launch beats a DMA copy
-    hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(256), 0, sh.stream, reinterpret_cast<const uint4*>(idev),
-                       reinterpret_cast<uint4*>(ectl), static_cast<int64_t>(CSC_ARENAS * sizeof(CscBuildCtl) / 16));
-  } else {
-    (void)hipGetLastError();
-    HIPCHK(hipMemcpyAsync(ectl, init, CSC_ARENAS * sizeof(CscBuildCtl), hipMemcpyHostToDevice, sh.stream));
-  }
+  // (the arenas' start values, 8 KB: one workgroup, whatever the size)
+  if (int rc = copy_small(sh.stream, init, ectl, CSC_ARENAS * sizeof(CscBuildCtl), true, 1, SIZE_MAX)) return rc;
   out.Pre = s.sPre;
   out.Lq = s.sLq;
   out.data = s.sdata;
@@ -190,17 +199,7 @@ int emit_enqueue(Ctx* h, Shard& sh, SliceStore& s) {
   HIPCHK(hipSetDevice(sh.device));
   const size_t nsl8 = static_cast<size_t>(round_up(static_cast<int64_t>(s.s_ncg) * s.s_nchunks, 32));
   const size_t bytes = nsl8 * sizeof(uint32_t) + CSC_ARENAS * sizeof(CscBuildCtl);
-  void* hdev = nullptr;
-  if (bytes <= (1u << 20) && hipHostGetDevicePointer(&hdev, h->csc_hLq, 0) == hipSuccess && hdev) {
-    const int64_t n16 = static_cast<int64_t>(bytes / 16);  // (both terms are multiples of 32 bytes)
-    hipLaunchKernelGGL(k_copy_words, dim3(static_cast<unsigned>(std::min<int64_t>(ceil_div(n16, 256), 64))),
-                       dim3(256), 0, sh.stream, reinterpret_cast<const uint4*>(s.sLq),
-                       reinterpret_cast<uint4*>(hdev), n16);
-  } else {
-    (void)hipGetLastError();
-    HIPCHK(hipMemcpyAsync(h->csc_hLq, s.sLq, bytes, hipMemcpyDeviceToHost, sh.stream));
-  }
-  return 0;
+  return copy_small(sh.stream, h->csc_hLq, s.sLq, bytes, false, copy_grid(bytes), 1u << 20);
 }
 int emit_enqueue(Ctx* h, Shard& s) { return emit_enqueue(h, s, s); }
 
@@ -266,14 +265,7 @@ int groups_prepare(Ctx* h, Shard& s, GroupOut<VT>& out) {
     s.gcap_groups = G;
   }
   if (int rc = slices_arrays(h, s)) return rc;
-  CscBuildCtl* init = h->csc_hctl + CSC_ARENAS;  // second half: what the device starts from
-  for (int k = 0; k < CSC_ARENAS; ++k) {
-    init[k].cursor = 0;
-    init[k].capacity = s.gcap_units / CSC_ARENAS;
-    init[k].origin = static_cast<unsigned long long>(k) * (s.gcap_units / CSC_ARENAS);
-    init[k].overflow = 0;
-  }
-  HIPCHK(hipMemcpyAsync(s.cctl, init, CSC_ARENAS * sizeof(CscBuildCtl), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(s.cctl, arena_init(h, s.gcap_units), CSC_ARENAS * sizeof(CscBuildCtl), hipMemcpyHostToDevice,
                         s.stream));
   out.Goff = s.gOff;
   out.Gpre = s.gPre;
@@ -363,22 +355,12 @@ int slices_plan(Ctx* h, Shard& sh, SliceStore& s, bool whole) {
   HIPCHK(hipSetDevice(sh.device));
   int rc = grow_dev(s.swork, s.scap_work, nw);
   if (rc) return rc;
-  {
-    void* wdev = nullptr;
-    const size_t bytes = nw * sizeof(SliceWork);  // 32 bytes each
-    if (bytes <= (1u << 20) && hipHostGetDevicePointer(&wdev, h->csc_hwork, 0) == hipSuccess && wdev) {
-      hipLaunchKernelGGL(k_copy_words, dim3(static_cast<unsigned>(std::min<size_t>(ceil_div(bytes / 16, 256), 64))),
-                         dim3(256), 0, sh.stream, reinterpret_cast<const uint4*>(wdev),
-                         reinterpret_cast<uint4*>(s.swork), static_cast<int64_t>(bytes / 16));
-    } else {
-      (void)hipGetLastError();
-      HIPCHK(hipMemcpyAsync(s.swork, h->csc_hwork, bytes, hipMemcpyHostToDevice, sh.stream));
-    }
-    // the pinned staging is shared by every store and shard of the context: the copy has to be
-    // through before the next plan overwrites it (one shard's own builds are ordered by its stream
-    // and by the wait that precedes every plan)
-    if (h->sh.size() > 1) HIPCHK(hipStreamSynchronize(sh.stream));
-  }
+  const size_t bytes = nw * sizeof(SliceWork);  // 32 bytes each
+  if ((rc = copy_small(sh.stream, h->csc_hwork, s.swork, bytes, true, copy_grid(bytes), 1u << 20))) return rc;
+  // the pinned staging is shared by every store and shard of the context: the copy has to be
+  // through before the next plan overwrites it (one shard's own builds are ordered by its stream
+  // and by the wait that precedes every plan)
+  if (h->sh.size() > 1) HIPCHK(hipStreamSynchronize(sh.stream));
   const size_t NSLOT = static_cast<size_t>(nslot(h->V));
   if (static_cast<size_t>(nslots) > sh.part_tiles) {
     HIPCHK(hipStreamSynchronize(sh.stream));
@@ -439,6 +421,25 @@ int slices_check(Ctx* h, Shard& s, bool with_groups, bool& again) {
 
 int gather_slice_bytes(Ctx* h);
 
+// Slices for one shard from what `enqueue(O)` queues into the arrays groups_prepare() sized (groups it emits, or a
+// source of its own): the build is repeated, the buffers grown, until everything fits, `rounds` builds at most.
+// `what` heads the message of a failed wait.
+template <typename VT, typename Enqueue>
+int pack_until_fits(Ctx* h, Shard& s, bool with_groups, int rounds, const char* what, Enqueue enqueue) {
+  bool again = true;
+  for (int round = 0; again; ++round) {
+    if (round >= rounds) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+    GroupOut<VT> O;
+    int rc;
+    if ((rc = groups_prepare<VT>(h, s, O))) return rc;
+    if ((rc = enqueue(O))) return rc;
+    if (hipStreamSynchronize(s.stream) != hipSuccess)
+      return fail(CLIPPER_HIP_E_HIP, "%s: %s", what, hipGetErrorString(hipGetLastError()));
+    if ((rc = slices_check<VT>(h, s, with_groups, again))) return rc;
+  }
+  return 0;
+}
+
 // groups from the dense store(s) + pack + wait + plan: the setMatrixData paths, and every fill
 // that went through a dense store. Shard by shard (the pinned staging is shared).
 int csc_rebuild(Ctx* h) {
@@ -449,25 +450,13 @@ int csc_rebuild(Ctx* h) {
   dispatch_vt(h, [&](auto t) {
     using VT = decltype(t);
     for (auto& s : h->sh) {
-      bool again = true;
-      for (int attempt = 0; again; ++attempt) {
-        if (attempt >= 3) {
-          rc = fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
-          return;
-        }
-        GroupOut<VT> O;
-        if ((rc = groups_prepare<VT>(h, s, O))) return;
+      rc = pack_until_fits<VT>(h, s, true, 3, "compressed storage: build failed", [&](const GroupOut<VT>& O) {
         dim3 grid(h->csc_nstrips, static_cast<unsigned>(ceil_div(h->csc_nblocks, 2))), block(256);
         hipLaunchKernelGGL((k_groups_from_dense<VT>), grid, block, 0, s.stream,
                            static_cast<const VT*>(s.S), h->W, h->m, O);
-        if ((rc = slices_enqueue<VT>(h, s, group_source<VT>(h, s), s.cctl))) return;
-        if (hipStreamSynchronize(s.stream) != hipSuccess) {
-          rc = fail(CLIPPER_HIP_E_HIP, "compressed storage: build failed: %s",
-                    hipGetErrorString(hipGetLastError()));
-          return;
-        }
-        if ((rc = slices_check<VT>(h, s, true, again))) return;
-      }
+        return slices_enqueue<VT>(h, s, group_source<VT>(h, s), s.cctl);
+      });
+      if (rc) return;
     }
   });
   if (rc) return rc;
@@ -480,6 +469,25 @@ int csc_rebuild(Ctx* h) {
 bool rect_fill_possible(const Ctx* h);
 int gather_slice_bytes(Ctx* h);
 int launch_rect(Ctx* h, Shard& s, const int32_t* rowmap, int64_t nrows, const SliceOut& O, int64_t col0 = -1, int64_t wcols = -1);
+
+// The slices of M[rows, columns] into `st` by the rectangular fill, repeated (the arenas grown) until they fit, `rounds`
+// fills at most. (col0, wcols) = (-1, -1): this shard's columns. `plan`: the streamed pass's work list as well.
+int emit_rect(Ctx* h, Shard& s, SliceStore& st, const int32_t* rowmap, int64_t nrows, int64_t col0, int64_t wcols,
+              bool plan, int rounds, const char* what) {
+  for (int round = 1;; ++round) {
+    SliceOut O{};
+    int rc;
+    if ((rc = emit_prepare(h, s, st, nrows, O, wcols))) return rc;
+    if ((rc = launch_rect(h, s, rowmap, nrows, O, col0, wcols))) return rc;
+    if ((rc = emit_enqueue(h, s, st))) return rc;
+    HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipGetLastError());
+    bool again = false;
+    if ((rc = emit_check(h, s, st, false, again, plan))) return rc;
+    if (!again) return 0;
+    if (round >= rounds) return fail(CLIPPER_HIP_E_HIP, "%s: the build keeps overflowing", what);
+  }
+}
 
 // Every compressed build the symmetric kernel cannot serve (fp64 values, column shards): the
 // rectangular tile kernel writes each shard's slices straight from its LDS images — no dense store, no
@@ -546,14 +554,7 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
   h->total_slice_bytes = 0.0;  // (column shards: gathered again once this build's slices exist)
   for (auto& s : h->sh) s.rv.valid = false;  // a row view of the previous matrix
   h->nodes.clear();
-  // explicit constraint storage is not needed on this path: C == pattern(M)
-  for (auto& s : h->sh) {
-    if (s.Cs) {
-      hipSetDevice(s.device);
-      hipFree(s.Cs);
-      s.Cs = nullptr;
-    }
-  }
+  drop_explicit_c(h);  // not needed on this path: C == pattern(M)
   h->explicitC = false;
   plan_tiles(h);
   int rc = 0;
@@ -730,12 +731,11 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
       });
     } else {
       dim3 grid(static_cast<unsigned>(ceil_div(static_cast<int64_t>(k) * k, 256))), block(256);
-      if (h->storage == CLIPPER_HIP_STORE_F64)
-        hipLaunchKernelGGL((k_gather_sub<double>), grid, block, 0, s.stream,
-                           static_cast<const double*>(s.S), h->W, c0, h->W, didx, k, dout);
-      else
-        hipLaunchKernelGGL((k_gather_sub<float>), grid, block, 0, s.stream,
-                           static_cast<const float*>(s.S), h->W, c0, h->W, didx, k, dout);
+      dispatch_vt(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_gather_sub<T>), grid, block, 0, s.stream, static_cast<const T*>(s.S), h->W, c0, h->W, didx,
+                           k, dout);
+      });
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(tmp.data(), dout, tmp.size() * sizeof(double), hipMemcpyDeviceToHost,

@@ -1,0 +1,595 @@
+// host_matrix_io.hpp — the matrix in and out of a context: the two affinity fills, the dense and sparse setters, the
+// getter, the mat-vecs of the test API, and the nearest-neighbour search that puts associations together before any
+// context exists. Part of clipper_hip.hip (one translation unit; included there, last). The order of the bodies here
+// is the order in which the code object holds their kernels.
+#pragma once
+
+namespace {
+
+// brute-force nearest neighbours: launch of the two kernels for one (K, D)
+template <int K, int D>
+int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S, int64_t chunk,
+            double* pd, int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
+  dim3 g(static_cast<unsigned>(ceil_div(n0, 256)), static_cast<unsigned>(S));
+  hipLaunchKernelGGL((k_knn_partial<K, D>), g, dim3(256), 0, st, dP0, n0, dP1, n1, chunk, pd, pi);
+  hipLaunchKernelGGL((k_knn_merge<K>), dim3(static_cast<unsigned>(ceil_div(n0, 256))), dim3(256), 0,
+                     st, pd, pi, n0, S, od, oi);
+  return 0;
+}
+
+
+// The two fills (declared in host_matrix.hpp): defined here, behind the batch, so that the fill kernels keep their place
+// in the code object.
+// EuclideanDistance over the staged points: the matrix of this context
+int fill_euclidean(Ctx* h, const EuclidParams& prm) {
+  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
+  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+  const int d = h->staged_d;
+  h->fill_kind = 1;  // what a row view of this matrix is filled with later (host_rowview.hpp)
+  h->fill_e = prm;
+  h->fill_n = PointNormalParams{};
+  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsilon, h->staged_maxabs, d));
+  return run_affinity(h, use_sym_fill(h) && (d == 2 || d == 3), [&](Shard& s) {
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
+              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
+        block(256);
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    const int32_t* A0 = s.Adev;
+    const int32_t* A1 = s.Adev + mm;
+#define LAUNCH_EUCLID(T, D)                                                                 \
+  hipLaunchKernelGGL((k_affinity_euclid<T, D>), grid, block, 0, s.stream,                   \
+                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, \
+                     A0, A1, prm)
+#define LAUNCH_EUCLID_COMPACT(T, D)                                                         \
+  hipLaunchKernelGGL((k_affinity_euclid_compact<T, D>), grid, block, 0, s.stream,           \
+                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f,  \
+                     s.P2f, pstride, A0, A1, prm, thr)
+    const float thr = guarded_threshold(prm.epsilon, h->staged_maxabs, d);
+    if (use_sym_fill(h) && (d == 2 || d == 3)) {
+      const int nT = static_cast<int>(ceil_div(mm, AT));
+      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
+      const PointNormalParams none{};
+      const float E2 = guarded_threshold_sq(thr);
+      dispatch_vt(h, [&](auto t) {
+        using T = decltype(t);
+        T* S = static_cast<T*>(sizeof(T) == 8 ? nullptr : s.S);  // (slices with fp64 values: no dense store on this route)
+        if (d == 3) launch_sym<T>(k_affinity_sym<3, false, T>, g, s.stream, S, W, mm, nT, s, pstride, A0, A1, prm, none, E2, h->csc_out);
+        else launch_sym<T>(k_affinity_sym<2, false, T>, g, s.stream, S, W, mm, nT, s, pstride, A0, A1, prm, none, E2, h->csc_out);
+      });
+      h->csc_emitted = (h->csc_out.Pre != nullptr);
+      return;
+    }
+    const bool compact = !h->plain_affinity && (d == 2 || d == 3);
+    dispatch_vt(h, [&](auto t) {
+      using T = decltype(t);
+      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(T, 3);
+      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(T, 2);
+      else if (d == 3) LAUNCH_EUCLID(T, 3);
+      else if (d == 2) LAUNCH_EUCLID(T, 2);
+      else LAUNCH_EUCLID(T, 0);
+    });
+#undef LAUNCH_EUCLID_COMPACT
+#undef LAUNCH_EUCLID
+  });
+}
+
+
+// PointNormalDistance over the staged points: the matrix of this context
+int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
+  if (h->staged_d != 6)
+    return fail(CLIPPER_HIP_E_STATE, "PointNormalDistance needs staged inputs with d == 6");
+  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+  h->fill_kind = 2;
+  h->fill_e = EuclidParams{};
+  h->fill_n = prm;
+  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsp, h->staged_maxabs, 3));
+  return run_affinity(h, use_sym_fill(h), [&](Shard& s) {
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
+              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
+        block(256);
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    const float thr = guarded_threshold(prm.epsp, h->staged_maxabs, 3);
+    if (use_sym_fill(h)) {
+      const int nT = static_cast<int>(ceil_div(mm, AT));
+      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
+      const EuclidParams none{};
+      dispatch_vt(h, [&](auto t) {
+        using T = decltype(t);
+        launch_sym<T>(k_affinity_sym<3, true, T>, g, s.stream, static_cast<T*>(sizeof(T) == 8 ? nullptr : s.S), W, mm, nT, s,
+                      pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
+      });
+      h->csc_emitted = (h->csc_out.Pre != nullptr);
+      return;
+    }
+    if (h->plain_affinity)
+      dispatch_vt(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_affinity_pointnormal<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
+                           AFF_ROWS_PER_BLK, s.P1, s.P2, pstride, s.Adev, s.Adev + mm, prm);
+      });
+    else
+      dispatch_vt(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_affinity_pointnormal_compact<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, mm,
+                           c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
+      });
+  });
+}
+
+// device temporaries of one call, released on every path (by release(), or when it goes out of scope)
+struct DevTemps {
+  std::vector<std::pair<int, void*>> v;
+  ~DevTemps() { release(); }
+  void release() {
+    for (auto& p : v) {
+      hipSetDevice(p.first);
+      hipFree(p.second);
+    }
+    v.clear();
+  }
+  template <typename T>
+  int alloc(int dev, T*& p, size_t n) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16)));
+    v.emplace_back(dev, p);
+    return 0;
+  }
+};
+
+// A matrix the caller hands over replaces the one held: no nodes, no row view, no points behind it, no explicit C
+// store; the problem sized for m. has_matrix stays false until the new matrix is complete.
+int begin_matrix(Ctx* h, int64_t m) {
+  if (h->A.size() != static_cast<size_t>(2 * m)) h->A.clear();
+  h->nodes.clear();
+  h->has_matrix = false;
+  h->csc_valid = false;
+  h->total_slice_bytes = 0.0;
+  h->fill_kind = 0;
+  rowview_drop(h);
+  drop_explicit_c(h);
+  return ensure_problem(h, m);
+}
+
+// a CSC matrix of m columns to the device of shard s, its arrays held by `tmp`: `d` points at them
+int upload_csc(DevTemps& tmp, Shard& s, int64_t m, const clipper_csc::CscRef& a, clipper_csc::CscRef& d) {
+  const int64_t nnz = a.cp[m];
+  int64_t* dcp = nullptr;
+  int32_t* dri = nullptr;
+  double* dva = nullptr;
+  int rc;
+  if ((rc = tmp.alloc(s.device, dcp, static_cast<size_t>(m + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = tmp.alloc(s.device, dri, static_cast<size_t>(nnz) * sizeof(int32_t)))) return rc;
+  if ((rc = tmp.alloc(s.device, dva, static_cast<size_t>(nnz) * sizeof(double)))) return rc;
+  HIPCHK(hipMemcpyAsync(dcp, a.cp, static_cast<size_t>(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s.stream));
+  if (nnz > 0) {
+    HIPCHK(hipMemcpyAsync(dri, a.ri, static_cast<size_t>(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(dva, a.va, static_cast<size_t>(nnz) * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  }
+  d = clipper_csc::CscRef{dcp, dri, dva};
+  return 0;
+}
+
+// setMatrixData with dense (M, C), column-major m x m: pass 1 fills the store and finds out whether C is anything
+// other than pattern(M); only then does an explicit C get a store of its own (pass 2).
+int set_dense(Ctx* h, const double* M, const double* C, int64_t m) {
+  int rc;
+  if ((rc = begin_matrix(h, m))) return rc;
+  if ((rc = ensure_dense(h, false))) return rc;
+  const size_t bytes = static_cast<size_t>(m) * m * sizeof(double);
+  const int64_t W = h->W;
+  DevTemps tmp;
+  std::vector<double*> dM(h->sh.size(), nullptr), dC(h->sh.size(), nullptr);
+  std::vector<int*> dflag(h->sh.size(), nullptr);
+  const unsigned gy = static_cast<unsigned>(std::min<int64_t>(m, 65535));
+  auto from_dense = [&](size_t k, void* Cs, int* flag) {
+    Shard& s = h->sh[k];
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 256)), gy), block(256);
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    dispatch_vt(h, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_from_dense_upper<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, m, c0, dM[k],
+                         dC[k], static_cast<T*>(Cs), flag);
+    });
+  };
+  int mismatch = 0;
+  for (size_t k = 0; k < h->sh.size(); ++k) {
+    Shard& s = h->sh[k];
+    HIPCHK(hipSetDevice(s.device));
+    if ((rc = tmp.alloc(s.device, dM[k], bytes))) return rc;
+    if ((rc = tmp.alloc(s.device, dC[k], bytes))) return rc;
+    if ((rc = tmp.alloc(s.device, dflag[k], sizeof(int)))) return rc;
+    HIPCHK(hipMemsetAsync(dflag[k], 0, sizeof(int), s.stream));
+    HIPCHK(hipMemcpyAsync(dM[k], M, bytes, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(hipMemcpyAsync(dC[k], C, bytes, hipMemcpyHostToDevice, s.stream));
+    from_dense(k, nullptr, dflag[k]);
+    int f = 0;
+    HIPCHK(hipMemcpyAsync(&f, dflag[k], sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipGetLastError());
+    mismatch |= f;
+  }
+  // NOTE: in multi-process mode every rank sees the whole (M, C), so `mismatch` agrees.
+  // The full upper triangle must be inspected, not only owned columns: do it on the host
+  // cheaply when sharded (owned columns cover all (lo,hi) pairs with hi or lo owned only).
+  if (h->world > 1 && !mismatch) {
+    for (int64_t hi = 1; hi < m && !mismatch; ++hi)
+      for (int64_t lo = 0; lo < hi; ++lo) {
+        const double mv = M[lo + hi * m], cv = C[lo + hi * m];
+        if (cv != ((mv != 0.0) ? 1.0 : 0.0)) {
+          mismatch = 1;
+          break;
+        }
+      }
+  }
+  h->explicitC = (mismatch != 0);
+  plan_tiles(h);
+  if (h->explicitC) {
+    for (size_t k = 0; k < h->sh.size(); ++k) {
+      Shard& s = h->sh[k];
+      HIPCHK(hipSetDevice(s.device));
+      HIPCHK(hipMalloc(&s.Cs, s.bytes_S));
+      from_dense(k, s.Cs, nullptr);
+    }
+  }
+  if ((rc = sync_all(h))) return rc;
+  if ((rc = csc_rebuild(h))) return rc;
+  h->has_matrix = true;
+  return 0;
+}
+
+// set_sparse with compressed storage and C == pattern(M): the slices packed straight from the symmetric lists (no
+// dense intermediate: O(nnz) memory)
+int sparse_to_slices(Ctx* h, const clipper_csc::CscRef& M) {
+  const int64_t m = h->m, W = h->W;
+  drop_dense(h);
+  clipper_csc::CscLists L;
+  const std::string err = clipper_csc::symmetric_lists(m, M, L);
+  if (!err.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s", err.c_str());
+  DevTemps tmp;
+  int rc = 0;
+  for (auto& s : h->sh) {
+    HIPCHK(hipSetDevice(s.device));
+    clipper_csc::CscRef d{};
+    if ((rc = upload_csc(tmp, s, m, clipper_csc::CscRef{L.cp.data(), L.ri.data(), L.va.data()}, d))) return rc;
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    dispatch_vt(h, [&](auto t) {
+      using VT = decltype(t);
+      rc = pack_until_fits<VT>(h, s, false, 3, "set_sparse", [&](const GroupOut<VT>&) {  // (the groups go unused)
+        CscSource<VT> src{};
+        src.colptr = d.cp + std::min<int64_t>(c0, m);
+        src.rowidx = d.ri;
+        src.values = d.va;
+        src.ncols = std::max<int64_t>(0, std::min<int64_t>(W, m - c0));
+        return slices_enqueue<VT>(h, s, src, nullptr);
+      });
+    });
+    if (rc) return rc;
+  }
+  if ((rc = sync_all(h))) return rc;
+  h->csc_valid = true;
+  if ((rc = gather_slice_bytes(h))) return rc;  // column shards: the row-view policy's cost model
+  h->has_matrix = true;
+  return 0;
+}
+
+// set_sparse through the dense store (dense storage modes, or an explicit C): the lists scattered into it
+int sparse_to_dense(Ctx* h, const clipper_csc::CscRef& M, const clipper_csc::CscRef& C) {
+  int rc;
+  if ((rc = ensure_dense(h, false))) return rc;
+  const int64_t m = h->m, W = h->W;
+  DevTemps tmp;
+  auto scatter = [&](Shard& s, void* dst, const clipper_csc::CscRef& a) -> int {
+    clipper_csc::CscRef d{};
+    if (int r = upload_csc(tmp, s, m, a, d)) return r;
+    HIPCHK(hipMemsetAsync(dst, 0, s.bytes_S, s.stream));
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    dim3 grid(static_cast<unsigned>(std::min<int64_t>(m, 1 << 20))), block(256);
+    dispatch_vt(h, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_from_csc<T>), grid, block, 0, s.stream, static_cast<T*>(dst), W, m, c0, W, d.cp, d.ri, d.va);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s.stream));
+    return 0;
+  };
+  for (auto& s : h->sh) {
+    HIPCHK(hipSetDevice(s.device));
+    if ((rc = scatter(s, s.S, M))) return rc;
+    if (h->explicitC) {
+      HIPCHK(hipMalloc(&s.Cs, s.bytes_S));
+      if ((rc = scatter(s, s.Cs, C))) return rc;
+    }
+  }
+  if ((rc = csc_rebuild(h))) return rc;
+  h->has_matrix = true;
+  return 0;
+}
+
+// setSparseMatrixData (clipper.cpp:162-166). Every stored (i, j) with i < j stands for the symmetric pair, as
+// selfadjointView<Upper> reads it; entries below the diagonal are not read (the reference never does); the diagonal is
+// implicit (host_csc_input.hpp). With compressed storage and C == pattern(M) the slices are packed straight from the
+// lists; otherwise through the dense store. A call refused before begin_matrix leaves the matrix held as it was.
+int set_sparse(Ctx* h, int64_t m, const int64_t* Mcolptr, const int32_t* Mrow, const double* Mval,
+               const int64_t* Ccolptr, const int32_t* Crow, const double* Cval) {
+  clipper_csc::CscRef M{Mcolptr, Mrow, Mval}, C{Ccolptr, Crow, Cval};
+  clipper_csc::CscLists Mup, Cup;
+  int64_t dropped_below = 0;  // entries below the diagonal, which the reference never reads: dropped, and reported
+  std::string err = clipper_csc::check_csc("M", m, M);
+  if (err.empty()) err = clipper_csc::check_csc("C", m, C);
+  if (err.empty()) err = clipper_csc::upper_only("M", m, M, Mup, dropped_below);
+  if (err.empty()) err = clipper_csc::upper_only("C", m, C, Cup, dropped_below);
+  if (!err.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s", err.c_str());
+  // (a warning, not an error — the call goes on and returns 0 unless something else fails: clipper_hip_last_error()
+  // tells a caller who handed over both triangles, or only the lower one, what became of them)
+  if (dropped_below > 0)
+    (void)fail(0, "warning: %lld stored entries below the diagonal were ignored (the matrices are read through their upper "
+                  "triangle, as the reference's selfadjointView<Upper> does: clipper.cpp:194-271)", static_cast<long long>(dropped_below));
+  if (int rc = begin_matrix(h, m)) return rc;
+  h->explicitC = !clipper_csc::is_pattern(m, M, C);
+  plan_tiles(h);
+  return csc_applies(h) ? sparse_to_slices(h, M) : sparse_to_dense(h, M, C);
+}
+
+// getMatrixData / getConstraintData: the dense (M, C), column-major m x m, identity on the diagonal
+int get_dense(Ctx* h, double* M_out, double* C_out) {
+  if (!h->has_matrix) return fail(CLIPPER_HIP_E_STATE, "no matrix has been built or set");
+  if (h->multiproc)
+    return fail(CLIPPER_HIP_E_STATE, "get_matrix is not available on a multi-process shard");
+  const int64_t m = h->m, W = h->W;
+  const bool f64 = (h->storage == CLIPPER_HIP_STORE_F64);
+  if (int rc = ensure_dense(h, true)) return rc;
+  std::vector<unsigned char> buf;
+  auto fetch = [&](Shard& s, const void* src, double* out, bool as_pattern) -> int {
+    buf.resize(s.bytes_S);
+    HIPCHK(hipSetDevice(s.device));
+    HIPCHK(hipMemcpy(buf.data(), src, s.bytes_S, hipMemcpyDeviceToHost));
+    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+    for (int64_t c = 0; c < W; ++c) {
+      const int64_t g = c0 + c;
+      if (g >= m) break;
+      for (int64_t j = 0; j < m; ++j) {
+        const double v = f64 ? reinterpret_cast<const double*>(buf.data())[j * W + c]
+                             : static_cast<double>(reinterpret_cast<const float*>(buf.data())[j * W + c]);
+        double o = as_pattern ? ((v != 0.0) ? 1.0 : 0.0) : v;
+        if (j == g) o += 1.0;  // clipper.cpp:133-134, 142-143: identity added
+        out[j + g * m] = o;
+      }
+    }
+    return 0;
+  };
+  for (auto& s : h->sh) {
+    int rc;
+    if (M_out && (rc = fetch(s, s.S, M_out, false))) return rc;
+    if (C_out) {
+      rc = h->explicitC ? fetch(s, s.Cs, C_out, false) : fetch(s, s.S, C_out, true);
+      if (rc) return rc;
+    }
+  }
+  if (h->csc_valid) drop_dense(h);  // the copy was materialised for this call only: M lives in the slices
+  return 0;
+}
+
+// ---- putative associations (before the path): brute-force nearest neighbours -------------------
+
+template <int K>
+void knn_launch(int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S, int64_t chunk, double* pd,
+                int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
+  if (d == 3) knn_run<K, 3>(dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st);
+  else knn_run<K, 2>(dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st);
+}
+
+// the knn nearest points of pcd1 (P1) to every point of pcd0 (P0), nearest first: indices, squared distances
+int knn_search(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d, int knn, int32_t* idx_out,
+        double* sqd_out) {
+  if (!P0 || !P1 || !idx_out || n0 < 1 || n1 < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  if (d != 2 && d != 3) return fail(CLIPPER_HIP_E_INVALID, "points must have 2 or 3 coordinates");
+  if (knn < 1 || knn > 16) return fail(CLIPPER_HIP_E_INVALID, "knn must be in 1..16");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
+  HIPCHK(hipSetDevice(device));
+  const int K = knn <= 1 ? 1 : (knn <= 2 ? 2 : (knn <= 4 ? 4 : (knn <= 8 ? 8 : 16)));
+  // enough workgroups to fill the chip: split pcd1 into S chunks of whole tiles
+  const int64_t qblocks = ceil_div(n0, 256);
+  const int64_t tiles = ceil_div(n1, KNN_TILE);
+  const int S = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, ceil_div(512, qblocks))));
+  const int64_t chunk = ceil_div(tiles, S) * KNN_TILE;
+  double *dP0 = nullptr, *dP1 = nullptr, *pd = nullptr, *od = nullptr;
+  int32_t *pi = nullptr, *oi = nullptr;
+  const size_t b0 = static_cast<size_t>(n0) * d * sizeof(double), b1 = static_cast<size_t>(n1) * d * sizeof(double);
+  const size_t np = static_cast<size_t>(S) * n0 * K, no = static_cast<size_t>(n0) * K;
+  DevTemps tmp;
+  if (tmp.alloc(device, dP0, b0) || tmp.alloc(device, dP1, b1) || tmp.alloc(device, pd, np * sizeof(double)) ||
+      tmp.alloc(device, pi, np * sizeof(int32_t)) || tmp.alloc(device, od, no * sizeof(double)) ||
+      tmp.alloc(device, oi, no * sizeof(int32_t))) {
+    tmp.release();
+    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  }
+  hipStream_t st = nullptr;  // the default stream: a stand-alone call
+  bool ok = hipMemcpyAsync(dP0, P0, b0, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemcpyAsync(dP1, P1, b1, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    switch (K) {
+      case 1: knn_launch<1>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
+      case 2: knn_launch<2>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
+      case 4: knn_launch<4>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
+      case 8: knn_launch<8>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
+      default: knn_launch<16>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
+    }
+    std::vector<double> hd(no);
+    std::vector<int32_t> hi(no);
+    ok = hipMemcpy(hd.data(), od, no * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(hi.data(), oi, no * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+         hipGetLastError() == hipSuccess;
+    if (ok) {
+      for (int64_t i = 0; i < n0; ++i)
+        for (int k = 0; k < knn; ++k) {
+          idx_out[i * knn + k] = hi[static_cast<size_t>(i) * K + k];
+          if (sqd_out) sqd_out[i * knn + k] = hd[static_cast<size_t>(i) * K + k];
+        }
+    }
+  }
+  tmp.release();
+  if (!ok) return fail(CLIPPER_HIP_E_HIP, "nearest-neighbour search failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+// bm_utils::get_putative_associations (bm_utils.cpp:187-229) on the GPU's nearest neighbours: the associations, n x 2
+// column-major; the count comes back
+int64_t distance_based_correspondences(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d,
+                                       int knn, double radius, int enforce_1to1, int32_t* A_out, int64_t capacity) {
+  std::vector<int32_t> idx(static_cast<size_t>(std::max<int64_t>(n0, 0)) * std::max(knn, 0));
+  std::vector<double> sqd(idx.size());
+  int rc = knn_search(device, P0, n0, P1, n1, d, knn, idx.data(), sqd.data());
+  if (rc) return rc;
+  // bm_utils.cpp:187-229: rows (i, nn_j(i)) for i ascending, neighbours by distance, kept if within
+  // the radius; one-to-one: per point of pcd1 (ascending) the FIRST closest of its claimants
+  const double r2 = radius * radius;
+  std::vector<std::pair<int32_t, int32_t>> rows;
+  std::map<int32_t, std::vector<std::pair<int32_t, double>>> claim;
+  for (int64_t i = 0; i < n0; ++i)
+    for (int k = 0; k < knn; ++k) {
+      const int32_t c1 = idx[static_cast<size_t>(i) * knn + k];
+      const double sd = sqd[static_cast<size_t>(i) * knn + k];
+      if (c1 < 0) continue;  // fewer than knn points in pcd1
+      if (sd <= r2) {
+        rows.emplace_back(static_cast<int32_t>(i), c1);
+        if (enforce_1to1) claim[c1].emplace_back(static_cast<int32_t>(i), sd);
+      }
+    }
+  if (enforce_1to1) {
+    rows.clear();
+    for (const auto& it : claim) {
+      size_t best = 0;
+      for (size_t q = 1; q < it.second.size(); ++q)
+        if (it.second[q].second < it.second[best].second) best = q;  // std::min_element: first minimum
+      rows.emplace_back(it.second[best].first, it.first);
+    }
+  }
+  const int64_t n = static_cast<int64_t>(rows.size());
+  if (n > capacity) return fail(CLIPPER_HIP_E_INVALID, "capacity %lld < %lld associations",
+                                static_cast<long long>(capacity), static_cast<long long>(n));
+  for (int64_t r = 0; r < n; ++r) {  // column-major n x 2, as clipper::Association
+    A_out[r] = rows[static_cast<size_t>(r)].first;
+    A_out[n + r] = rows[static_cast<size_t>(r)].second;
+  }
+  return n;
+}
+
+// x -> candidate 0 of table 0 of a shard (staged through the u0 buffer)
+int stage_x(Ctx* h, Shard& s, const double* x) {
+  HIPCHK(hipMemcpyAsync(s.u0, x, static_cast<size_t>(h->m) * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  hipLaunchKernelGGL(k_spread, dim3(static_cast<unsigned>(ceil_div(h->m, 256))), dim3(256), 0, s.stream, s.u0, h->m,
+                     s.X[0]);
+  h->u0_staged = false;
+  return 0;
+}
+
+// yM = M_off x, yC = C_off x (the identity left out): one pair-mode mat-vec
+int matvec(Ctx* h, const double* x, double* yM, double* yC) {
+  if (!h->has_matrix) return fail(CLIPPER_HIP_E_STATE, "no matrix has been built or set");
+  const int64_t m = h->m, W = h->W;
+  int rc;
+  for (auto& s : h->sh) {
+    HIPCHK(hipSetDevice(s.device));
+    if ((rc = stage_x(h, s, x))) return rc;
+  }
+  rc = h->csc_valid ? 0 : ensure_dense(h, true);
+  if (rc) return rc;
+  if ((rc = enqueue_gemv_plain(h))) return rc;
+  if ((rc = enqueue_reduce_exchange(h))) return rc;
+  if ((rc = sync_all(h))) return rc;
+  std::vector<double> ab(static_cast<size_t>(h->world) * 2 * W);
+  Shard& s0 = h->sh[0];
+  HIPCHK(hipSetDevice(s0.device));
+  HIPCHK(hipMemcpy(ab.data(), s0.ab, ab.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < m; ++i) {
+    const int64_t p = i / W, off = i - p * W;
+    if (yM) yM[i] = ab[static_cast<size_t>(p * 2 * W + off)];
+    if (yC) yC[i] = ab[static_cast<size_t>(p * 2 * W + W + off)];
+  }
+  return 0;
+}
+
+// The products of matvec through a ROW VIEW of the given rows: yM = M_off[:, rows] x[rows], yC likewise — what a pass
+// of the solver computes when it streams the view instead of M. Builds the slices of M[rows, :] with the rectangular
+// fill kernel from the staged points (the view of a later solve is built anew). For tests: equal to matvec of x with
+// every other entry zeroed, up to the order of the partial sums.
+int view_matvec(Ctx* h, const int32_t* rows, int64_t nrows, const double* x, double* yM, double* yC) {
+  if (!h->has_matrix || !h->csc_valid || !csc_single(h) || !rect_fill_possible(h))
+    return fail(CLIPPER_HIP_E_STATE, "a row view needs slices of a matrix scored from staged points on one device");
+  const int64_t m = h->m, W = h->W;
+  for (int64_t r = 0; r < nrows; ++r)
+    if (rows[r] < 0 || rows[r] >= m || (r > 0 && rows[r] <= rows[r - 1]))
+      return fail(CLIPPER_HIP_E_INVALID, "rows must be ascending association indices");
+  Shard& s = h->sh[0];
+  RowView& v = s.rv;
+  HIPCHK(hipSetDevice(s.device));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  v.valid = false;
+  int rc;
+  {
+    size_t r0 = v.cap_rows, r1 = v.cap_rows;
+    if ((rc = grow_dev(v.rowmap[0], r0, static_cast<size_t>(h->mp)))) return rc;
+    if ((rc = grow_dev(v.rowmap[1], r1, static_cast<size_t>(h->mp)))) return rc;
+    v.cap_rows = static_cast<size_t>(h->mp);
+  }
+  HIPCHK(hipMemcpyAsync(v.rowmap[0], rows, static_cast<size_t>(nrows) * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
+  if ((rc = emit_rect(h, s, v.st, v.rowmap[0], nrows, -1, -1, true, 3, "row view"))) return rc;
+  if ((rc = stage_x(h, s, x))) return rc;
+  launch_slices_plain(h, s, store_view(v.st, v.rowmap[0], nrows), s.X[0]);
+  hipLaunchKernelGGL(k_reduce, dim3(static_cast<unsigned>(ceil_div(2 * W, 256))), dim3(256), 0, s.stream, s.part,
+                     v.st.s_nslots, 2, W, s.ab);
+  std::vector<double> ab(static_cast<size_t>(2 * W));
+  HIPCHK(hipMemcpyAsync(ab.data(), s.ab, ab.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  HIPCHK(hipGetLastError());
+  for (int64_t i = 0; i < m; ++i) {
+    if (yM) yM[i] = ab[static_cast<size_t>(i)];
+    if (yC) yC[i] = ab[static_cast<size_t>(W + i)];
+  }
+  return 0;
+}
+
+// ---- measurement ---------------------------------------------------------------------------
+
+// the mean time of one pair-mode mat-vec on shard 0 over `reps` launches (after 3 unmeasured ones)
+int bench_matvec(Ctx* h, int reps, double* avg_us) {
+  if (!h->has_matrix) return fail(CLIPPER_HIP_E_STATE, "no matrix has been built or set");
+  if (!h->csc_valid)
+    if (int rc = ensure_dense(h, true)) return rc;
+  Shard& s = h->sh[0];
+  HIPCHK(hipSetDevice(s.device));
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0));
+  HIPCHK(hipEventCreate(&e1));
+  for (int w = 0; w < 3; ++w) launch_plain(h, s, s.X[0]);
+  HIPCHK(hipEventRecord(e0, s.stream));
+  for (int r = 0; r < reps; ++r) launch_plain(h, s, s.X[0]);
+  HIPCHK(hipEventRecord(e1, s.stream));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  *avg_us = static_cast<double>(ms) * 1e3 / reps;
+  h->tm.gemv_bytes = algorithmic_gemv_bytes(h, /*dense=*/!h->csc_valid);
+  return 0;
+}
+
+// `workgroups` workgroups of one wave, each holding `lds_bytes` of LDS, spinning for `milliseconds` on their own stream
+int debug_occupy(int device, int workgroups, int lds_bytes, double milliseconds) {
+  HIPCHK(hipSetDevice(device));
+  if (!raise_dynamic_lds(reinterpret_cast<const void*>(k_debug_occupy), device, static_cast<int>(RS_LDS_MAX)))
+    return fail(CLIPPER_HIP_E_HIP, "the device refuses %u bytes of dynamic LDS", RS_LDS_MAX);
+  hipStream_t st = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  hipLaunchKernelGGL(k_debug_occupy, dim3(static_cast<unsigned>(workgroups)), dim3(64), static_cast<size_t>(lds_bytes), st,
+                     static_cast<long long>(milliseconds * 1e5));
+  const hipError_t e = hipStreamSynchronize(st);
+  hipStreamDestroy(st);
+  HIPCHK(e);
+  return 0;
+}
+
+}  // namespace

@@ -66,18 +66,17 @@ int mc_graph_and_cores(Ctx* h, McBufs& b, int64_t nw, std::vector<int32_t>& deg,
     HIPCHK(hipMemsetAsync(b.G, 0, gbytes, s.stream));
     const int64_t nsl = static_cast<int64_t>(s.s_ncg) * s.s_nchunks;
     dim3 grid(static_cast<unsigned>(ceil_div(nsl, 4))), block(256);
-    if (h->storage == CLIPPER_HIP_STORE_F64)  // (the value type; h->compressed says slices)
-      hipLaunchKernelGGL((k_mc_adj_slices<double, SL_H>), grid, block, 0, s.stream, slice_view(h, s), b.G, nw, m);
-    else
-      hipLaunchKernelGGL((k_mc_adj_slices<float, SL_H>), grid, block, 0, s.stream, slice_view(h, s), b.G, nw, m);
+    dispatch_vt(h, [&](auto t) {  // (the value type; h->compressed says slices)
+      hipLaunchKernelGGL((k_mc_adj_slices<decltype(t), SL_H>), grid, block, 0, s.stream, slice_view(h, s), b.G, nw, m);
+    });
   } else {
     const void* src = h->explicitC ? s.Cs : s.S;
     if (!src) return fail(CLIPPER_HIP_E_STATE, "max clique: the store of C is not on the device");
     dim3 grid(static_cast<unsigned>(ceil_div(m, 256)), static_cast<unsigned>(std::min<int64_t>(nw, 65535))), block(256);
-    if (h->storage == CLIPPER_HIP_STORE_F64)
-      hipLaunchKernelGGL(k_mc_adj_dense<double>, grid, block, 0, s.stream, static_cast<const double*>(src), h->W, m, nw, b.G);
-    else
-      hipLaunchKernelGGL(k_mc_adj_dense<float>, grid, block, 0, s.stream, static_cast<const float*>(src), h->W, m, nw, b.G);
+    dispatch_vt(h, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_mc_adj_dense<T>, grid, block, 0, s.stream, static_cast<const T*>(src), h->W, m, nw, b.G);
+    });
   }
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_mc_degree, dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256), 0, s.stream, b.G, nw, m, b.deg);

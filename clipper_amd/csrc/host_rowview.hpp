@@ -238,17 +238,6 @@ ViewPolicy rowview_policy(const Ctx* h) {
   return p;
 }
 
-template <typename T>
-int rv_grow(T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return 0;
-  if (p) hipFree(p);
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(need, 1) * sizeof(T)));
-  cap = need;
-  return 0;
-}
-
 // Builds the view from the state the NEXT iteration decides from (state copy h->par). The stream need not be
 // idle: whatever is queued behind the hold only moves the state between its two copies, and the build's launches
 // queue behind that. built = false: the live rows were too many to be worth it — the view in use, if any, stays
@@ -290,15 +279,15 @@ int rowview_build_shard(Ctx* h, Shard& s, bool& built) {
   int rc;
   {
     size_t c0 = v.cap_flags, c1 = v.cap_flags;
-    if ((rc = rv_grow(v.in_view[0], c0, static_cast<size_t>(mp)))) return rc;
-    if ((rc = rv_grow(v.in_view[1], c1, static_cast<size_t>(mp)))) return rc;
+    if ((rc = grow_dev(v.in_view[0], c0, static_cast<size_t>(mp)))) return rc;
+    if ((rc = grow_dev(v.in_view[1], c1, static_cast<size_t>(mp)))) return rc;
     v.cap_flags = static_cast<size_t>(mp);
     size_t r0 = v.cap_rows, r1 = v.cap_rows;
-    if ((rc = rv_grow(v.rowmap[0], r0, static_cast<size_t>(mp)))) return rc;
-    if ((rc = rv_grow(v.rowmap[1], r1, static_cast<size_t>(mp)))) return rc;
+    if ((rc = grow_dev(v.rowmap[0], r0, static_cast<size_t>(mp)))) return rc;
+    if ((rc = grow_dev(v.rowmap[1], r1, static_cast<size_t>(mp)))) return rc;
     v.cap_rows = static_cast<size_t>(mp);
-    if ((rc = rv_grow(v.blk, v.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
-    if ((rc = rv_grow(v.viewpos, v.cap_pos, static_cast<size_t>(mp)))) return rc;
+    if ((rc = grow_dev(v.blk, v.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
+    if ((rc = grow_dev(v.viewpos, v.cap_pos, static_cast<size_t>(mp)))) return rc;
   }
   if (!h->rv_count) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->rv_count), 64, hipHostMallocMapped | hipHostMallocCoherent));

@@ -340,20 +340,9 @@ int rvr_build_replica(Ctx* h, Shard& s) {
   RowView& v = s.rv;
   v.full_valid = false;
   if (!v.valid) return 0;
-  const int64_t wfull = round_up(h->m, 64);
-  for (int attempt = 0;; ++attempt) {
-    SliceOut O{};
-    int rc;
-    if ((rc = emit_prepare(h, s, v.full, v.nrows, O, wfull))) return rc;
-    if ((rc = launch_rect(h, s, v.rowmap[v.cur], v.nrows, O, 0, wfull))) return rc;
-    if ((rc = emit_enqueue(h, s, v.full))) return rc;
-    HIPCHK(hipStreamSynchronize(s.stream));
-    HIPCHK(hipGetLastError());
-    bool again = false;
-    if ((rc = emit_check(h, s, v.full, false, again, false))) return rc;  // (no work list: nothing streams the replica)
-    if (!again) break;
-    if (attempt >= 3) return fail(CLIPPER_HIP_E_HIP, "row view replica: the build keeps overflowing");
-  }
+  // (no work list: nothing streams the replica)
+  if (int rc = emit_rect(h, s, v.full, v.rowmap[v.cur], v.nrows, 0, round_up(h->m, 64), false, 4, "row view replica"))
+    return rc;
   v.full_valid = true;
   return 0;
 }

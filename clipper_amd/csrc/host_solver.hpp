@@ -183,6 +183,13 @@ void launch_plain_t(Ctx* h, Shard& s, const double* X) {
                      h->rows_per_tile, X, s.part);
 }
 
+// calls f(value type tag) for the storage's element type
+template <typename F>
+void dispatch_vt(const Ctx* h, F&& f) {
+  if (h->storage == CLIPPER_HIP_STORE_F64) f(double{});
+  else f(float{});
+}
+
 // calls f(type tag, HASC tag) for the context's storage type and constraint mode
 template <typename F>
 void dispatch_storage(Ctx* h, F&& f) {
@@ -206,35 +213,32 @@ void launch_pass(Ctx* h, Shard& s, const SolveArgs& a) {
 SliceView slice_view(const Ctx* h, const Shard& s);
 SliceView row_view(const Ctx* h, const Shard& s);
 
+// the pair-mode mat-vec alone on table X over slices: of M, or of a row view (the matvec API)
+void launch_slices_plain(Ctx* h, Shard& s, const SliceView& M, const double* X) {
+  dim3 grid(static_cast<unsigned>(M.nwork)), block(SL_NW * 64);
+  dispatch_vt(h, [&](auto t) {
+    hipLaunchKernelGGL((k_gemv_slices_plain<decltype(t), 1>), grid, block, 0, s.stream, M, h->W, h->m, X, s.part);
+  });
+}
+
 // the pair-mode mat-vec alone on table X (matvec API, micro-benchmark)
 void launch_plain(Ctx* h, Shard& s, const double* X) {
-  if (h->csc_valid) {  // on the slices: part[slot][2][W]
-    const SliceView M = slice_view(h, s);
-    dim3 grid(static_cast<unsigned>(s.s_nwork)), block(SL_NW * 64);
-    if (h->storage == CLIPPER_HIP_STORE_F64)
-      hipLaunchKernelGGL((k_gemv_slices_plain<double, 1>), grid, block, 0, s.stream, M, h->W, h->m, X, s.part);
-    else
-      hipLaunchKernelGGL((k_gemv_slices_plain<float, 1>), grid, block, 0, s.stream, M, h->W, h->m, X, s.part);
-    return;
-  }
+  if (h->csc_valid) return launch_slices_plain(h, s, slice_view(h, s), X);  // on the slices: part[slot][2][W]
   dispatch_storage(h, [&](auto t, auto c) {
     launch_plain_t<decltype(t), decltype(c)::value>(h, s, X);
   });
 }
 
 // G on the slices of M (one shard, C == pattern(M))
-SliceView slice_view(const Ctx* h, const Shard& s);
-
 template <int V>
 void launch_pass_csc(Ctx* h, Shard& s, const SolveArgs& a) {
   const SliceView M = slice_view(h, s), R = row_view(h, s);
   // (the LAST workgroup records the decided state: on M it is the one with the least to stream)
   dim3 grid(static_cast<unsigned>(std::max(M.nwork, R.nwork))), block(SL_NW * 64);
   const SliceView* rdev = s.rv.desc;  // (read only while a.in_view says there is a view)
-  if (h->storage == CLIPPER_HIP_STORE_F64)
-    hipLaunchKernelGGL((k_gemv_slices<double, 1, V>), grid, block, 0, s.stream, M, rdev, a);
-  else
-    hipLaunchKernelGGL((k_gemv_slices<float, 1, V>), grid, block, 0, s.stream, M, rdev, a);
+  dispatch_vt(h, [&](auto t) {
+    hipLaunchKernelGGL((k_gemv_slices<decltype(t), 1, V>), grid, block, 0, s.stream, M, rdev, a);
+  });
 }
 
 // calls f(integral_constant<V>) for the context's window size

@@ -118,7 +118,7 @@ int sub_prepare_v(Ctx* h) {
     HIPCHK(hipMalloc(&sp.pos, static_cast<size_t>(mp) * sizeof(int32_t)));
     sp.cap = static_cast<size_t>(mp);
   }
-  if ((rc = rv_grow(sp.blk, sp.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
+  if ((rc = grow_dev(sp.blk, sp.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
   if (!sp.nout_acc) HIPCHK(hipMalloc(&sp.nout_acc, 8 * sizeof(int32_t)));
   if (!sp.rec) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&sp.rec), 64, hipHostMallocMapped | hipHostMallocCoherent));
