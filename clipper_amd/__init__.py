@@ -17,6 +17,6 @@ def load_clipperpy():
 
     mod = importlib.import_module("clipper_amd.lib.clipperpy")
     sys.modules.setdefault("clipperpy", mod)
-    for sub in ("invariants", "utils", "dsd"):
+    for sub in ("invariants", "utils", "dsd", "sdp"):
         sys.modules.setdefault(f"clipperpy.{sub}", getattr(mod, sub))
     return mod

@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("CLIPPER_HIP_LIB") or os.path.join(_HERE, "lib", "libc
 STORE_F32, STORE_F64, STORE_F32_CSC, STORE_F64_CSC = 0, 1, 2, 3
 ROUNDING_NONZERO, ROUNDING_DSD, ROUNDING_DSD_HEU = 0, 1, 2
 MC_EXACT, MC_HEU, MC_KCORE = 0, 1, 2  # CLIPPER_HIP_MC_* = maxclique::Method
+SDP_MAX_N = 128  # CLIPPER_HIP_SDP_MAX_N
 
 # every symbol include/clipper_hip.h declares (checked by tests/test_abi_exports.py)
 EXPORTED_SYMBOLS = [
@@ -43,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_solve_staged", "clipper_hip_debug_stamps", "clipper_hip_comm_init_callback",
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
-    "clipper_hip_max_clique", "clipper_hip_core_numbers",
+    "clipper_hip_max_clique", "clipper_hip_core_numbers", "clipper_hip_sdp", "clipper_hip_sdp_solve",
     "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
     "clipper_hip_batch_get_selected_associations", "clipper_hip_batch_route", "clipper_hip_batch_get_stats",
@@ -122,6 +123,56 @@ class MaxCliqueInfo(C.Structure):
         ("edges", C.c_int64), ("roots_searched", C.c_int64), ("roots_pruned", C.c_int64), ("bb_nodes", C.c_int64),
         ("seconds", C.c_double),
     ]
+
+
+class SdpParams(C.Structure):
+    """clipper_sdp_params_t (include/clipper_hip.h) = sdp::Params. acceleration_interval, acceleration_lookback and
+    eps_infeas are accepted and ignored."""
+
+    _fields_ = [
+        ("verbose", C.c_int32), ("max_iters", C.c_int32), ("acceleration_interval", C.c_int32),
+        ("acceleration_lookback", C.c_int32), ("eps_abs", C.c_float), ("eps_rel", C.c_float),
+        ("eps_infeas", C.c_float), ("time_limit_secs", C.c_float),
+    ]
+
+    def __init__(self, **kw):
+        base = dict(verbose=0, max_iters=2000, acceleration_interval=10, acceleration_lookback=10, eps_abs=1e-3,
+                    eps_rel=1e-3, eps_infeas=1e-7, time_limit_secs=0.0)
+        base.update(kw)
+        super().__init__(**base)
+
+
+class SdpInfo(C.Structure):
+    """clipper_sdp_info_t (include/clipper_hip.h): what clipper_hip_sdp / clipper_hip_sdp_solve report."""
+
+    _fields_ = [
+        ("iters", C.c_int32), ("converged", C.c_int32), ("timed_out", C.c_int32), ("num_nodes", C.c_int32),
+        ("sweeps", C.c_int32), ("pad", C.c_int32),
+        ("pobj", C.c_double), ("dobj", C.c_double), ("r_prim", C.c_double), ("r_dual", C.c_double),
+        ("rho", C.c_double), ("thr", C.c_double), ("t_total", C.c_double), ("t_setup", C.c_double),
+        ("t_solve", C.c_double), ("t_extract", C.c_double),
+    ]
+
+
+@dataclass
+class SdpResult:
+    """sdp::Solution (sdp.h:15-37) plus the certificate: Y (the dual of the constraints of C) and SdpInfo."""
+
+    X: np.ndarray
+    Y: np.ndarray
+    lambdas: np.ndarray
+    evec1: np.ndarray
+    thr: float
+    nodes: np.ndarray
+    iters: int
+    pobj: float
+    dobj: float
+    info: SdpInfo
+
+
+def _sdp_result(n, X, Y, lam, ev, nodes, info) -> SdpResult:
+    return SdpResult(X=X, Y=Y, lambdas=lam, evec1=ev, thr=info.thr, nodes=nodes, iters=info.iters, pobj=info.pobj,
+                     dobj=info.dobj, info=info)
 
 
 class BatchProblem(C.Structure):
@@ -225,6 +276,9 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
     L.clipper_hip_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_core_numbers.argtypes = [vp, ip]
+    L.clipper_hip_sdp.argtypes = [vp, C.POINTER(SdpParams), dp, dp, dp, dp, C.POINTER(SdpInfo)]
+    L.clipper_hip_sdp_solve.argtypes = [C.c_int, dp, dp, C.c_int64, C.POINTER(SdpParams), dp, dp, dp, dp, ip,
+                                        C.POINTER(SdpInfo)]
     L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     L.clipper_hip_batch_destroy.argtypes = [vp]
     L.clipper_hip_batch_destroy.restype = None
@@ -475,6 +529,23 @@ class HipClipper:
         self.soln = Solution(t=info.seconds, ifinal=0, nodes=nodes, u=np.zeros(self.m), score=-1.0)
         return nodes, info
 
+    def sdp(self, params: SdpParams | None = None):
+        """sdp::solve on the context's M and C (identity diagonals): CLIPPER::solveAsMSRCSDR on the device.
+        Returns (nodes ascending, SdpResult); the nodes become the context's selection."""
+        params = params if params is not None else SdpParams()
+        n = int(self.m)
+        X, Y = np.zeros((n, n)), np.zeros((n, n))
+        lam, ev = np.zeros(n), np.zeros(n)
+        info = SdpInfo()
+        self._check(self.L.clipper_hip_sdp(self.h, C.byref(params), _dp(X), _dp(Y), _dp(lam), _dp(ev), C.byref(info)))
+        out = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
+        k = self.L.clipper_hip_get_nodes(self.h, _ip(out), len(out))
+        self._check(min(k, 0))
+        nodes = out[:k].copy()
+        # clipper.cpp:108-112: the solution of an SDP call
+        self.soln = Solution(t=info.t_total, ifinal=0, nodes=nodes, u=np.zeros(self.m), score=-1.0)
+        return nodes, _sdp_result(n, X, Y, lam, ev, nodes, info)
+
     def core_numbers(self) -> np.ndarray:
         """The core number of every vertex of the consistency graph."""
         n = int(self.L.clipper_hip_num_associations(self.h))
@@ -657,6 +728,26 @@ def knn(P0, P1, knn: int, device: int = 0):
     if rc != 0:
         raise RuntimeError(f"clipper_hip error {rc}: {_last_error()}")
     return idx, sqd
+
+
+def sdp_solve(M, C_, params: SdpParams | None = None, device: int = 0) -> SdpResult:
+    """sdp::solve(M, C, params) on the device: n x n M and C (n <= 128), only their lower triangles read."""
+    L = load_library()
+    Mc = np.asfortranarray(np.asarray(M, dtype=np.float64))
+    Cc = np.asfortranarray(np.asarray(C_, dtype=np.float64))
+    n = Mc.shape[0]
+    if Mc.shape != (n, n) or Cc.shape != (n, n):
+        raise ValueError("M and C must be square and of the same size")
+    params = params if params is not None else SdpParams()
+    X, Y = np.zeros((n, n)), np.zeros((n, n))
+    lam, ev = np.zeros(n), np.zeros(n)
+    nodes = np.zeros(max(n, 1), dtype=np.int32)
+    info = SdpInfo()
+    k = L.clipper_hip_sdp_solve(device, _dp(Mc), _dp(Cc), n, C.byref(params), _dp(X), _dp(Y), _dp(lam), _dp(ev),
+                                _ip(nodes), C.byref(info))
+    if k < 0:
+        raise ClipperError(f"clipper_hip error {k}: {_last_error()}")
+    return _sdp_result(n, X, Y, lam, ev, nodes[:k].copy(), info)
 
 
 def distance_based_correspondences(P0, P1, knn: int, radius: float, enforce_1to1: bool,

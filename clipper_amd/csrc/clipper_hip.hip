@@ -48,6 +48,7 @@ using namespace clipper_hip;
 #include "host_subproblem.hpp"
 #include "host_registration.hpp"
 #include "host_maxclique.hpp"
+#include "host_sdp.hpp"
 #include "host_solve.hpp"
 #include "host_batchsolve.hpp"
 #include "host_matrix_io.hpp"
@@ -273,6 +274,20 @@ int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, cl
 int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out) try {
   if (!h || !core_out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   return core_numbers_impl(h, core_out);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- the semidefinite relaxation (sdp::solve, host_sdp.hpp) ------------------------------------------------------
+
+int clipper_hip_sdp(clipper_hip_t* h, const clipper_sdp_params_t* params, double* X_out, double* Y_out,
+                    double* lambdas_out, double* evec1_out, clipper_sdp_info_t* info) try {
+  if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return sdp_ctx_impl(h, params, X_out, Y_out, lambdas_out, evec1_out, info);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t n, const clipper_sdp_params_t* params,
+                          double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
+                          clipper_sdp_info_t* info) try {
+  return sdp_solve_impl(device, M, C, n, params, X_out, Y_out, lambdas_out, evec1_out, nodes_out, info);
 } CLIPPER_HIP_GUARD_INT
 
 // ---- putative associations (before the path): brute-force nearest neighbours -------------------

@@ -5,6 +5,7 @@
 // is a call into libclipper_hip.so. Nothing here is a CPU implementation of that path:
 // if the GPU library reports an error, the facade throws.
 #include "clipper/clipper.h"
+#include "clipper/sdp.h"
 
 #include <cmath>
 #include <cstring>
@@ -356,13 +357,78 @@ void CLIPPER::solveAsMaximumClique(const maxclique::Params& params) {
   soln_.score = -1;
 }
 
-// Without SCS the reference prints a warning and returns an empty solution (sdp.cpp:298-302).
-void CLIPPER::solveAsMSRCSDR(const sdp::Params&) {
-  std::cout << "SCS is not built. SDP solver is unavailable." << std::endl;
-  soln_.t = 0;
+namespace sdp {
+namespace detail {
+static clipper_sdp_params_t abi_params(const Params& p) {
+  clipper_sdp_params_t a{};
+  a.verbose = p.verbose ? 1 : 0;
+  a.max_iters = p.max_iters;
+  a.acceleration_interval = p.acceleration_interval;
+  a.acceleration_lookback = p.acceleration_lookback;
+  a.eps_abs = p.eps_abs;
+  a.eps_rel = p.eps_rel;
+  a.eps_infeas = p.eps_infeas;
+  a.time_limit_secs = p.time_limit_secs;
+  return a;
+}
+}  // namespace detail
+
+// sdp.cpp:109-303 on the device (clipper_hip_sdp_solve on device 0): only the lower triangles of M and C are read
+Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params) {
+  const std::ptrdiff_t n = M.rows();
+  if (M.cols() != n || C.rows() != n || C.cols() != n) throw std::runtime_error("sdp::solve: M and C must be n x n");
+  const clipper_sdp_params_t p = detail::abi_params(params);
+  Solution s;
+  s.X = MatrixXd::Zero(n, n);
+  MatrixXd Y = MatrixXd::Zero(n, n);
+  s.lambdas = VectorXd::Zero(n);
+  s.evec1 = VectorXd::Zero(n);
+  std::vector<int32_t> nodes(static_cast<size_t>(std::max<std::ptrdiff_t>(n, 1)));
+  clipper_sdp_info_t info{};
+  const MatrixXd Mc = M, Cc = C;  // (column-major, contiguous)
+  const int k = clipper_hip_sdp_solve(0, Mc.data(), Cc.data(), n, &p, s.X.data(), Y.data(), s.lambdas.data(),
+                                      s.evec1.data(), nodes.data(), &info);
+  if (k < 0) throw std::runtime_error(std::string("sdp::solve: ") + clipper_hip_last_error());
+  s.nodes.assign(nodes.begin(), nodes.begin() + k);
+  s.thr = info.thr;
+  s.iters = info.iters;
+  s.pobj = static_cast<float>(info.pobj);
+  s.dobj = static_cast<float>(info.dobj);
+  s.t = info.t_total;
+  s.t_parse = info.t_setup;
+  s.t_scs = info.t_solve;  // the device solver's share of the SCS fields: all of it is the projection (the cone)
+  s.t_scs_setup = 0;
+  s.t_scs_solve = info.t_solve;
+  s.t_scs_linsys = 0;
+  s.t_scs_cone = info.t_solve;
+  s.t_scs_accel = 0;
+  s.t_extract = info.t_extract;
+  return s;
+}
+}  // namespace sdp
+
+// Without SCS the reference prints a warning and returns an empty solution (sdp.cpp:298-302). With setDeviceSdp(true):
+// sdp::solve on getAffinityMatrix() / getConstraintMatrix(), on the device (clipper_hip_sdp),
+// and the solution clipper.cpp:108-112 makes of it.
+void CLIPPER::solveAsMSRCSDR(const sdp::Params& params) {
+  if (!device_sdp_) {
+    std::cout << "SCS is not built. SDP solver is unavailable." << std::endl;
+    soln_.t = 0;
+    soln_.ifinal = 0;
+    soln_.nodes.clear();
+    soln_.u = VectorXd::Zero(clipper_hip_num_associations(handle()));
+    soln_.score = -1;
+    return;
+  }
+  const clipper_sdp_params_t p = sdp::detail::abi_params(params);
+  clipper_sdp_info_t info{};
+  check(clipper_hip_sdp(handle(), &p, nullptr, nullptr, nullptr, nullptr, &info), "solveAsMSRCSDR");
+  std::vector<int> nodes(static_cast<size_t>(info.num_nodes));
+  if (info.num_nodes > 0) check(clipper_hip_get_nodes(h_, nodes.data(), info.num_nodes), "solveAsMSRCSDR (nodes)");
+  soln_.t = info.t_total;
   soln_.ifinal = 0;
-  soln_.nodes.clear();
-  soln_.u = VectorXd::Zero(clipper_hip_num_associations(handle()));
+  std::swap(soln_.nodes, nodes);
+  soln_.u = VectorXd::Zero(clipper_hip_num_associations(h_));
   soln_.score = -1;
 }
 

@@ -15,6 +15,7 @@
 
 #include "clipper/batch.h"
 #include "clipper/clipper.h"
+#include "clipper/sdp.h"
 #include "clipper/utils.h"
 
 namespace py = pybind11;
@@ -233,6 +234,30 @@ PYBIND11_MODULE(clipperpy, m) {
       .def_readwrite("eps_infeas", &clipper::sdp::Params::eps_infeas)
       .def_readwrite("time_limit_secs", &clipper::sdp::Params::time_limit_secs);
 
+  // clipperpy.sdp: sdp::solve (sdp.h) on the device, and its Solution
+  py::class_<clipper::sdp::Solution>(m, "SDPSolution")
+      .def(py::init<>())
+      .def("__repr__", [](const clipper::sdp::Solution&) { return "<CLIPPER SDP Solution>"; })
+      .def_readwrite("X", &clipper::sdp::Solution::X)
+      .def_readwrite("lambdas", &clipper::sdp::Solution::lambdas)
+      .def_readwrite("evec1", &clipper::sdp::Solution::evec1)
+      .def_readwrite("thr", &clipper::sdp::Solution::thr)
+      .def_readwrite("nodes", &clipper::sdp::Solution::nodes)
+      .def_readwrite("iters", &clipper::sdp::Solution::iters)
+      .def_readwrite("pobj", &clipper::sdp::Solution::pobj)
+      .def_readwrite("dobj", &clipper::sdp::Solution::dobj)
+      .def_readwrite("t", &clipper::sdp::Solution::t)
+      .def_readwrite("t_parse", &clipper::sdp::Solution::t_parse)
+      .def_readwrite("t_scs", &clipper::sdp::Solution::t_scs)
+      .def_readwrite("t_scs_setup", &clipper::sdp::Solution::t_scs_setup)
+      .def_readwrite("t_scs_solve", &clipper::sdp::Solution::t_scs_solve)
+      .def_readwrite("t_scs_linsys", &clipper::sdp::Solution::t_scs_linsys)
+      .def_readwrite("t_scs_cone", &clipper::sdp::Solution::t_scs_cone)
+      .def_readwrite("t_scs_accel", &clipper::sdp::Solution::t_scs_accel)
+      .def_readwrite("t_extract", &clipper::sdp::Solution::t_extract);
+  py::module m_sdp = m.def_submodule("sdp");
+  m_sdp.def("solve", &clipper::sdp::solve, "M"_a, "C"_a, "params"_a = clipper::sdp::Params{});
+
   py::enum_<clipper::Params::Rounding>(m, "Rounding")
       .value("NONZERO", clipper::Params::Rounding::NONZERO)
       .value("DSD", clipper::Params::Rounding::DSD)
@@ -296,6 +321,7 @@ PYBIND11_MODULE(clipperpy, m) {
       .def("solve_as_maximum_clique", &clipper::CLIPPER::solveAsMaximumClique,
            "params"_a = clipper::maxclique::Params{})
       .def("solve_as_msrc_sdr", &clipper::CLIPPER::solveAsMSRCSDR, "params"_a = clipper::sdp::Params{})
+      .def("set_device_sdp", &clipper::CLIPPER::setDeviceSdp, "on"_a)
       .def("get_initial_associations", &clipper::CLIPPER::getInitialAssociations)
       .def("get_selected_associations", &clipper::CLIPPER::getSelectedAssociations)
       .def("get_solution", &clipper::CLIPPER::getSolution)

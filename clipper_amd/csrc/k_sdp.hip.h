@@ -1,0 +1,400 @@
+// k_sdp.hip.h — the semidefinite relaxation behind CLIPPER::solveAsMSRCSDR and sdp::solve:
+// ADMM on X = Z with X in the spectraplex and Z in the polyhedral set of C, one workgroup per problem, fp64
+// throughout. Host side: host_sdp.hpp.
+// Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
+//
+// Layout of one problem (n <= SDP_MAX_N, np = n rounded up to even): M, the mask of C (1.0 / 0.0), X, Z and U are
+// n x n row-major in global memory (all symmetric); Q (the eigenbasis of the last projection) and T (the warm
+// start's product) are np x np; mu holds the np simplex weights of the last projection (the pad index: 0). The
+// working matrix of the eigensolver is np x np in LDS (128 KiB at np = 128); Q cannot join it there and stays in
+// global memory, where the L2 holds it (128 KiB).
+//
+// Eigensolver: cyclic Jacobi in round-robin (circle) order: in each of the np - 1 steps of a sweep the np / 2
+// disjoint pairs rotate together, every 2 x 2 block of the working matrix is rotated on both sides by one work
+// item (which writes its transpose too: the matrix stays exactly symmetric), and the pad index (odd n) keeps a zero
+// row, so its rotations are the identity. Each projection starts from Q_prev^T W Q_prev, nearly diagonal once the
+// iteration settles, and sweeps until the off-diagonal mass is below SDP_JACOBI_TOL of the whole.
+//
+// Every launch runs at most `budget` iterations and leaves X, Z, U, Q, mu and SdpCtl in device memory; the host
+// checks the convergence flag and the time limit between launches. No grid barrier, no atomics across workgroups.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace clipper_hip {
+
+constexpr int SDP_MAX_N = 128;          // the working matrix: SDP_MAX_N^2 doubles of LDS
+constexpr int SDP_THREADS = 1024;
+constexpr int SDP_MAX_SWEEPS = 40;
+constexpr double SDP_JACOBI_TOL = 1e-13;  // stop sweeping when off(A) <= tol * ||A||_F
+constexpr double SDP_RHO0 = 1.0;
+constexpr int SDP_ADAPT_EVERY = 10;       // residual balancing: every 10 iterations,
+constexpr double SDP_ADAPT_MU = 10.0;     // when one residual exceeds 10 times the other,
+constexpr double SDP_ADAPT_TAU = 2.0;     // rho is multiplied or divided by 2 and U divided or multiplied
+
+enum { SDP_MODE_INIT = 0, SDP_MODE_ITERATE = 1, SDP_MODE_CERTIFY = 2 };
+
+// device state of one problem (the host reads it after every launch)
+struct SdpCtl {
+  double rho;
+  double r_prim, r_dual;  // ||X - Z||_F, rho ||Z - Z_prev||_F of the last iteration
+  double pval;            // <M, X>
+  double dval;            // lambda_max(M - rho U): the dual bound of the last check (or certification)
+  int32_t iters;
+  int32_t converged;
+  int32_t infeasible;     // no diagonal entry of C is nonzero
+  int32_t sweeps;         // Jacobi sweeps so far (all projections and checks)
+};
+
+struct SdpArgs {
+  const double* M;
+  const double* mask;
+  double *X, *Z, *U, *Q, *T, *mu;
+  SdpCtl* ctl;
+  int32_t n, np;
+  double eps_abs, eps_rel;
+};
+
+// Dense fp64 M and the mask of C from stores where element (r, c) sits at src[r * rs + c * cs]; only the lower
+// triangle (r >= c) is read. `ident` is added to the diagonal of both (the context's identity, clipper.cpp:133-143).
+template <typename T>
+__global__ void k_sdp_gather(const T* __restrict__ srcM, const T* __restrict__ srcC, bool c_pattern_of_m, int64_t rs,
+                             int64_t cs, int32_t n, double ident, double* __restrict__ M, double* __restrict__ mask) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (idx >= static_cast<int64_t>(n) * n) return;
+  const int32_t a = static_cast<int32_t>(idx / n), b = static_cast<int32_t>(idx % n);
+  const int32_t r = a > b ? a : b, c = a > b ? b : a;
+  const double d = (a == b) ? ident : 0.0;
+  const double mv = static_cast<double>(srcM[r * rs + c * cs]) + d;
+  const double cv = c_pattern_of_m ? mv : static_cast<double>(srcC[r * rs + c * cs]) + d;
+  M[idx] = mv;
+  mask[idx] = (cv != 0.0) ? 1.0 : 0.0;
+}
+
+// sum of one double over the workgroup, the same order on every call; every thread gets the result
+__device__ inline double sdp_block_sum(double v, double* red) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int i = 0; i < SDP_THREADS / 64; ++i) s += red[i];
+  return s;
+}
+
+// the pair k of step t of the circle order over np indices (np even): index np - 1 stays put, the others turn
+__device__ inline void sdp_pair(int k, int t, int np, int& p, int& q) {
+  const int m = np - 1;
+  if (k == 0) {
+    p = t;
+    q = m;
+  } else {
+    p = (t + k) % m;
+    q = (t - k + m) % m;
+  }
+}
+
+// A (LDS) <- Q^T A Q, through T (global); Q is np x np
+__device__ void sdp_warm_start(double* A, const double* __restrict__ Q, double* __restrict__ T, int np) {
+  const int j = threadIdx.x & 127, g = threadIdx.x >> 7;  // column j, rows g, g + 8, ...
+  double acc[16];
+  if (j < np) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0;
+    for (int k = 0; k < np; ++k) {
+      const double qv = Q[k * np + j];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = g + 8 * r;
+        if (i < np) acc[r] = fma(A[i * np + k], qv, acc[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = g + 8 * r;
+      if (i < np) T[i * np + j] = acc[r];
+    }
+  }
+  __syncthreads();
+  if (j < np) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0;
+    for (int k = 0; k < np; ++k) {
+      const double tv = T[k * np + j];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = g + 8 * r;
+        if (i < np) acc[r] = fma(Q[k * np + i], tv, acc[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = g + 8 * r;
+      if (i < np) A[i * np + j] = acc[r];
+    }
+  }
+  __syncthreads();
+}
+
+// Cyclic Jacobi on the symmetric A (LDS, np x np) until off(A) <= SDP_JACOBI_TOL ||A||_F; with Q != nullptr the
+// rotations are accumulated into Q (Q <- Q J). Returns the sweeps run.
+__device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc, double* rs, double* rt,
+                          double* red) {
+  const int tid = threadIdx.x, h = np / 2;
+  int sweep = 0;
+  for (; sweep < SDP_MAX_SWEEPS; ++sweep) {
+    double off = 0.0, all = 0.0;
+    for (int idx = tid; idx < np * np; idx += SDP_THREADS) {
+      const double v = A[idx];
+      all += v * v;
+      if (idx / np != idx % np) off += v * v;
+    }
+    off = sdp_block_sum(off, red);
+    all = sdp_block_sum(all, red + SDP_THREADS / 64);
+    if (!(off > SDP_JACOBI_TOL * SDP_JACOBI_TOL * all)) break;
+    for (int t = 0; t < np - 1; ++t) {
+      if (tid < h) {
+        int p, q;
+        sdp_pair(tid, t, np, p, q);
+        const double apq = A[p * np + q];
+        double c = 1.0, s = 0.0, tn = 0.0;
+        if (apq != 0.0) {
+          const double theta = (A[q * np + q] - A[p * np + p]) / (2.0 * apq);
+          const double at = fabs(theta);
+          tn = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(theta * theta + 1.0));
+          if (theta < 0.0) tn = -tn;
+          c = 1.0 / sqrt(tn * tn + 1.0);
+          s = tn * c;
+        }
+        rc[tid] = c;
+        rs[tid] = s;
+        rt[tid] = tn;
+      }
+      __syncthreads();
+      // both sides of every 2 x 2 block (k, l), k <= l
+      for (int idx = tid; idx < h * h; idx += SDP_THREADS) {
+        const int k = idx / h, l = idx % h;
+        if (k > l) continue;
+        int p, q;
+        sdp_pair(k, t, np, p, q);
+        if (k == l) {
+          const double apq = A[p * np + q];
+          A[p * np + p] = A[p * np + p] - rt[k] * apq;
+          A[q * np + q] = A[q * np + q] + rt[k] * apq;
+          A[p * np + q] = 0.0;
+          A[q * np + p] = 0.0;
+          continue;
+        }
+        int r, s2;
+        sdp_pair(l, t, np, r, s2);
+        const double c1 = rc[k], s1 = rs[k], c2 = rc[l], sn2 = rs[l];
+        const double apr = A[p * np + r], aps = A[p * np + s2], aqr = A[q * np + r], aqs = A[q * np + s2];
+        const double bpr = apr * c2 - aps * sn2, bps = apr * sn2 + aps * c2;  // columns (l)
+        const double bqr = aqr * c2 - aqs * sn2, bqs = aqr * sn2 + aqs * c2;
+        const double npr = c1 * bpr - s1 * bqr, nps = c1 * bps - s1 * bqs;  // rows (k)
+        const double nqr = s1 * bpr + c1 * bqr, nqs = s1 * bps + c1 * bqs;
+        A[p * np + r] = npr;
+        A[p * np + s2] = nps;
+        A[q * np + r] = nqr;
+        A[q * np + s2] = nqs;
+        A[r * np + p] = npr;
+        A[s2 * np + p] = nps;
+        A[r * np + q] = nqr;
+        A[s2 * np + q] = nqs;
+      }
+      if (Q) {
+        for (int idx = tid; idx < np * h; idx += SDP_THREADS) {
+          const int i = idx / h, k = idx % h;
+          int p, q;
+          sdp_pair(k, t, np, p, q);
+          const double c = rc[k], s = rs[k];
+          const double qp = Q[i * np + p], qq = Q[i * np + q];
+          Q[i * np + p] = c * qp - s * qq;
+          Q[i * np + q] = s * qp + c * qq;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  return sweep;
+}
+
+// d = lambda_max(M - rho U) (the pad index excluded); A and T are overwritten, Q is read
+__device__ double sdp_dual_bound(const SdpArgs& g, double rho, double* A, bool warm, double* rc, double* rs,
+                                 double* rt, double* red, int& sweeps) {
+  const int n = g.n, np = g.np;
+  for (int idx = threadIdx.x; idx < np * np; idx += SDP_THREADS) {
+    const int a = idx / np, b = idx % np;
+    A[idx] = (a < n && b < n) ? g.M[a * n + b] - rho * g.U[a * n + b] : 0.0;
+  }
+  __syncthreads();
+  if (warm) sdp_warm_start(A, g.Q, g.T, np);
+  sweeps += sdp_jacobi(A, nullptr, np, rc, rs, rt, red);
+  double d = A[0];
+  for (int i = 1; i < n; ++i) d = fmax(d, A[i * np + i]);
+  __syncthreads();
+  return d;
+}
+
+__global__ void __launch_bounds__(SDP_THREADS) k_sdp(SdpArgs g, int32_t mode, int32_t budget, int32_t max_iters) {
+  extern __shared__ double A[];  // np x np
+  __shared__ double rc[SDP_MAX_N / 2], rs[SDP_MAX_N / 2], rt[SDP_MAX_N / 2];
+  __shared__ double lam[SDP_MAX_N], red[2 * SDP_THREADS / 64];
+  __shared__ int32_t pos_list[SDP_MAX_N];
+  __shared__ int32_t kmax, npos;
+  __shared__ double tau;
+  __shared__ SdpCtl c;
+  const int tid = threadIdx.x, n = g.n, np = g.np, nn = n * n;
+  if (tid == 0) c = *g.ctl;
+  __syncthreads();
+
+  if (mode == SDP_MODE_INIT) {
+    // X = Z = diag(mask) / #diag(mask), U = 0, Q = I, mu = diag(X)
+    if (tid == 0) {
+      int cnt = 0;
+      for (int i = 0; i < n; ++i) cnt += g.mask[i * n + i] != 0.0;
+      kmax = cnt;
+      c = SdpCtl{SDP_RHO0, 0.0, 0.0, 0.0, 0.0, 0, 0, cnt == 0, 0};
+    }
+    __syncthreads();
+    const double w = kmax ? 1.0 / kmax : 0.0;
+    for (int idx = tid; idx < nn; idx += SDP_THREADS) {
+      const int a = idx / n, b = idx % n;
+      const double x = (a == b && g.mask[idx] != 0.0) ? w : 0.0;
+      g.X[idx] = x;
+      g.Z[idx] = x;
+      g.U[idx] = 0.0;
+    }
+    for (int idx = tid; idx < np * np; idx += SDP_THREADS) g.Q[idx] = (idx / np == idx % np) ? 1.0 : 0.0;
+    for (int i = tid; i < np; i += SDP_THREADS) g.mu[i] = (i < n && g.mask[i * n + i] != 0.0) ? w : 0.0;
+  } else if (mode == SDP_MODE_CERTIFY) {
+    int sw = 0;
+    const double d = sdp_dual_bound(g, c.rho, A, c.iters > 0, rc, rs, rt, red, sw);
+    if (tid == 0) {
+      c.dval = d;
+      c.sweeps += sw;
+    }
+  } else {
+    for (int it = 0; it < budget; ++it) {
+      if (c.converged || c.iters >= max_iters) break;
+      const double rho = c.rho;
+      int sw = 0;
+      // ---- X+ = proj_S(Z - U + M / rho)
+      for (int idx = tid; idx < np * np; idx += SDP_THREADS) {
+        const int a = idx / np, b = idx % np;
+        double w = 0.0;
+        if (a < n && b < n) {
+          const int e = a * n + b;
+          w = g.Z[e] - g.U[e] + g.M[e] / rho;
+        }
+        A[idx] = w;
+      }
+      __syncthreads();
+      if (c.iters > 0) sdp_warm_start(A, g.Q, g.T, np);
+      sw += sdp_jacobi(A, g.Q, np, rc, rs, rt, red);
+      // simplex projection of the eigenvalues: tau of the largest valid support
+      if (tid < n) lam[tid] = A[tid * np + tid];
+      if (tid == 0) kmax = 0;
+      __syncthreads();
+      int cnt = 0;
+      double sum = 0.0;
+      bool ok = false;
+      if (tid < n) {
+        const double li = lam[tid];
+        for (int j = 0; j < n; ++j)
+          if (lam[j] >= li) {
+            ++cnt;
+            sum += lam[j];
+          }
+        ok = li > (sum - 1.0) / cnt;
+        if (ok) atomicMax(&kmax, cnt);
+      }
+      __syncthreads();
+      if (ok && cnt == kmax) tau = (sum - 1.0) / cnt;  // (equal sets: equal sums, the same bits)
+      __syncthreads();
+      if (tid < np) {
+        const double m = tid < n ? fmax(lam[tid] - tau, 0.0) : 0.0;
+        g.mu[tid] = m;
+        lam[tid] = m;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int k = 0;
+        for (int i = 0; i < n; ++i)
+          if (lam[i] > 0.0) pos_list[k++] = i;
+        npos = k;
+      }
+      __syncthreads();
+      // the positive eigenvectors into LDS (A is free): P[r][a] = Q[a][pos_list[r]]
+      const int K = npos;
+      for (int idx = tid; idx < K * n; idx += SDP_THREADS) {
+        const int r = idx / n, a = idx % n;
+        A[idx] = g.Q[a * np + pos_list[r]];
+      }
+      __syncthreads();
+      // ---- X = sum mu_r q_r q_r^T; Z+ = proj_P(X + U); U+ = U + X - Z+; the sums of the stopping rule
+      double rp2 = 0.0, rd2 = 0.0, xx = 0.0, zz = 0.0, uu = 0.0, mx = 0.0;
+      for (int idx = tid; idx < nn; idx += SDP_THREADS) {
+        const int a = idx / n, b = idx % n;
+        double x = 0.0;
+        for (int r = 0; r < K; ++r) x += lam[pos_list[r]] * (A[r * n + a] * A[r * n + b]);
+        const double u = g.U[idx], zo = g.Z[idx];
+        const double v = x + u;
+        const double zn = g.mask[idx] != 0.0 ? fmax(v, 0.0) : 0.0;
+        const double un = v - zn;
+        g.X[idx] = x;
+        g.Z[idx] = zn;
+        g.U[idx] = un;
+        rp2 += (x - zn) * (x - zn);
+        rd2 += (zn - zo) * (zn - zo);
+        xx += x * x;
+        zz += zn * zn;
+        uu += un * un;
+        mx += g.M[idx] * x;
+      }
+      rp2 = sdp_block_sum(rp2, red);
+      rd2 = sdp_block_sum(rd2, red + SDP_THREADS / 64);
+      xx = sdp_block_sum(xx, red);
+      zz = sdp_block_sum(zz, red + SDP_THREADS / 64);
+      uu = sdp_block_sum(uu, red);
+      mx = sdp_block_sum(mx, red + SDP_THREADS / 64);
+      const double r_p = sqrt(rp2), r_d = rho * sqrt(rd2);
+      const double e_pri = n * g.eps_abs + g.eps_rel * fmax(sqrt(xx), sqrt(zz));
+      const double e_dual = n * g.eps_abs + g.eps_rel * rho * sqrt(uu);
+      bool conv = false;
+      if (r_p <= e_pri && r_d <= e_dual) {
+        __syncthreads();  // U+ of every thread is written
+        const double d = sdp_dual_bound(g, rho, A, true, rc, rs, rt, red, sw);
+        conv = fabs(d - mx) <= g.eps_abs + g.eps_rel * fmax(fabs(d), fabs(mx));
+        if (tid == 0) c.dval = d;
+      }
+      // residual balancing; every thread rescales the entries of U it wrote
+      double f = 1.0;
+      const int32_t done = c.iters + 1;
+      if (!conv && done % SDP_ADAPT_EVERY == 0) {
+        if (r_p > SDP_ADAPT_MU * r_d) f = SDP_ADAPT_TAU;
+        else if (r_d > SDP_ADAPT_MU * r_p) f = 1.0 / SDP_ADAPT_TAU;
+      }
+      if (f != 1.0)
+        for (int idx = tid; idx < nn; idx += SDP_THREADS) g.U[idx] = f == SDP_ADAPT_TAU ? g.U[idx] / SDP_ADAPT_TAU
+                                                                                         : g.U[idx] * SDP_ADAPT_TAU;
+      __syncthreads();
+      if (tid == 0) {
+        c.iters = done;
+        c.r_prim = r_p;
+        c.r_dual = r_d;
+        c.pval = mx;
+        c.converged = conv;
+        c.rho = rho * f;
+        c.sweeps += sw;
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (tid == 0) *g.ctl = c;
+}
+
+}  // namespace clipper_hip

@@ -16,8 +16,10 @@
  *   - solveAsMaximumClique runs on the device (clipper_hip_max_clique: adjacency bitsets, core
  *     numbers, the greedy clique, a bitset branch and bound) instead of
  *     PMC; one-shard contexts only (column shards throw std::runtime_error);
- *   - solveAsMSRCSDR is outside this build and reports so, exactly like a reference build
- *     without SCS (sdp.cpp:298-302).
+ *   - solveAsMSRCSDR reports that SCS is not built, exactly like a reference build without SCS
+ *     (sdp.cpp:298-302), unless setDeviceSdp(true): then it solves the semidefinite relaxation on the
+ *     device (clipper_hip_sdp: ADMM with a Jacobi eigensolver; m <= 128,
+ *     one-shard contexts). sdp::solve (include/clipper/sdp.h) always runs on the device.
  */
 #pragma once
 
@@ -48,7 +50,9 @@ struct Params {
 }  // namespace maxclique
 
 namespace sdp {
-/// Mirror of the reference sdp::Params (sdp.h:40-52); solver not built here.
+/// Mirror of the reference sdp::Params (sdp.h:40-52). The device solver reads max_iters, eps_abs,
+/// eps_rel, time_limit_secs and verbose; acceleration_interval, acceleration_lookback and eps_infeas are accepted and
+/// ignored (no Anderson acceleration; the problem is always feasible).
 struct Params {
   bool verbose = false;
   int max_iters = 2000;
@@ -107,7 +111,7 @@ class CLIPPER {
   void solve(const VectorXd& u0 = VectorXd());
 
   void solveAsMaximumClique(const maxclique::Params& params = {});  ///< on the device (clipper_hip_max_clique)
-  void solveAsMSRCSDR(const sdp::Params& params = {});              ///< not built (SCS)
+  void solveAsMSRCSDR(const sdp::Params& params = {});              ///< the stub, or the device (setDeviceSdp)
 
   const Solution& getSolution() const { return soln_; }
   Affinity getAffinityMatrix();      ///< dense symmetric + identity (clipper.cpp:131-136)
@@ -147,6 +151,8 @@ class CLIPPER {
   /// associations that can still be selected — provably the same result. false = the passes keep streaming the view. Any time.
   void setLiveSubproblem(bool on);
   long long lastSolvePassesOnTheSubproblem() const;
+  /// solveAsMSRCSDR on the device (clipper_hip_sdp) instead of the stub of a build without SCS. Default off. Any time.
+  void setDeviceSdp(bool on) { device_sdp_ = on; }
   struct PathStats {
     long long n_passes = 0, n_trials = 0;
     double affinity_kernel_ms = 0, d = 0;
@@ -166,6 +172,7 @@ class CLIPPER {
   Storage storage_ = Storage::F32_CSC;
   bool resident_ = true;
   bool row_views_ = true;
+  bool device_sdp_ = false;
   clipper_hip_ctx* h_ = nullptr;
 
   clipper_hip_ctx* handle();

@@ -1,0 +1,50 @@
+/**
+ * @file sdp.h
+ * @brief clipper::sdp — the semidefinite relaxation of CLIPPER (MSRC-SDR), the reference's
+ *        include/clipper/sdp.h:15-55 with the same names and fields, solved on the device
+ *        (clipper_hip_sdp_solve: ADMM with a Jacobi eigensolver) instead of SCS.
+ *
+ *   maximize <M, X>  s.t.  tr X = 1, X psd, X_ij = 0 where C_ij = 0, X_ij >= 0 elsewhere
+ *
+ * Only the lower triangles of M and C (diagonal included) are read. n <= 128. pobj / dobj keep SCS's
+ * sign (minimisation): pobj = -<M, X>, dobj = -lambda_max(M - Y), a certified bound on the optimum.
+ * The t_scs_* fields keep their names: t_scs = t_scs_solve = t_scs_cone = the device iteration, the
+ * others 0. sdp::Params lives in clipper.h (as the facade's solveAsMSRCSDR needs it).
+ */
+#pragma once
+
+#include <vector>
+
+#include "clipper/clipper.h"
+
+namespace clipper {
+namespace sdp {
+
+struct Solution {
+  MatrixXd X;
+  VectorXd lambdas;  ///< the eigenvalues of X, ascending
+  VectorXd evec1;    ///< the eigenvector of the largest; its largest-magnitude entry is positive
+
+  double thr = 0;          ///< threshold for selecting nodes: max |evec1| / 2
+  std::vector<int> nodes;  ///< indices of selected nodes: |evec1_i| > thr
+
+  int iters = 0;   ///< number of iterations
+  float pobj = 0;  ///< primal objective value
+  float dobj = 0;  ///< dual objective value
+
+  double t = 0;             ///< total time: parsing, solving, extraction
+  double t_parse = 0;       ///< time spent setting up the problem data
+  double t_scs = 0;         ///< total solver time
+  double t_scs_setup = 0;   ///< solver setup time
+  double t_scs_solve = 0;   ///< solver solve time
+  double t_scs_linsys = 0;  ///< time in a linear system solver (none here)
+  double t_scs_cone = 0;    ///< time in the cone projections
+  double t_scs_accel = 0;   ///< time in the acceleration routine (none here)
+  double t_extract = 0;     ///< time spent extracting which nodes to select
+};
+
+/// sdp.cpp:109-303 on HIP device 0; throws std::runtime_error when the device solver refuses (n > 128, no device).
+Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params = Params{});
+
+}  // namespace sdp
+}  // namespace clipper

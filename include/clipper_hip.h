@@ -284,6 +284,60 @@ int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, cl
 /* The core number of every vertex of the same graph (Batagelj-Zaversnik): m int32. */
 int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out /* m */);
 
+/* ---- the semidefinite relaxation (sdp::solve, sdp.cpp:109-303; CLIPPER::solveAsMSRCSDR, clipper.cpp:100-112) ---- */
+
+/* maximize <M, X>  s.t.  tr X = 1, X psd, X_ij = 0 where C_ij = 0, X_ij >= 0 elsewhere; only the lower triangle of
+ * M and C (diagonal included) is read and taken as symmetric. ADMM with a Jacobi eigensolver on the device, fp64,
+ * one workgroup; n <= CLIPPER_HIP_SDP_MAX_N, larger problems return CLIPPER_HIP_E_SCOPE.
+ * Stops when the primal residual ||X - Z||_F, the dual residual rho ||Z - Z_prev||_F and the gap between <M, X> and
+ * the dual bound lambda_max(M - Y) are all within the Boyd tolerances of eps_abs / eps_rel, at max_iters, or when
+ * time_limit_secs > 0 runs out (checked between launches). pobj / dobj follow SCS's sign (minimisation):
+ * pobj = -<M, X>, dobj = -lambda_max(M - Y), a certified bound on the optimum in every outcome.
+ * acceleration_interval, acceleration_lookback and eps_infeas are accepted and ignored (there is no Anderson
+ * acceleration, and the problem is always feasible: e_i e_i^T with C(i, i) != 0; a C without a nonzero diagonal
+ * entry is refused with CLIPPER_HIP_E_INVALID). */
+#define CLIPPER_HIP_SDP_MAX_N 128
+typedef struct clipper_sdp_params_t { /* = sdp::Params (sdp.h:40-52) */
+  int32_t verbose;
+  int32_t max_iters;               /* >= 1 */
+  int32_t acceleration_interval;   /* ignored */
+  int32_t acceleration_lookback;   /* ignored */
+  float eps_abs;
+  float eps_rel;
+  float eps_infeas;                /* ignored */
+  float time_limit_secs;           /* <= 0: none */
+} clipper_sdp_params_t;
+typedef struct clipper_sdp_info_t {
+  int32_t iters;        /* ADMM iterations                                                          */
+  int32_t converged;    /* 1: all three tolerances met                                               */
+  int32_t timed_out;    /* 1: time_limit_secs stopped the iteration                                  */
+  int32_t num_nodes;    /* rounded selection: |evec1_i| > thr                                        */
+  int32_t sweeps;       /* Jacobi sweeps, all projections and certificates together                  */
+  int32_t pad;
+  double pobj;          /* -<M, X>                                                                   */
+  double dobj;          /* -lambda_max(M - Y)                                                        */
+  double r_prim;        /* ||X - Z||_F                                                               */
+  double r_dual;        /* rho ||Z - Z_prev||_F                                                      */
+  double rho;           /* the final penalty                                                         */
+  double thr;           /* max |evec1| / 2                                                           */
+  double t_total;       /* seconds: the whole call                                                   */
+  double t_setup;       /* seconds: gather / upload and initialisation                               */
+  double t_solve;       /* seconds: the iteration and the final certificate                          */
+  double t_extract;     /* seconds: the rounding and the copies out                                  */
+} clipper_sdp_info_t;
+/* On the context's M and C (each with its identity diagonal: what getAffinityMatrix / getConstraintMatrix return),
+ * read from whichever device store holds them. The selected nodes (ascending) become the context's node list.
+ * Optional outputs (NULL allowed), m = the context's size: X and Y (m x m), lambdas (m, ascending: the eigenvalues
+ * of X), evec1 (m: the eigenvector of the largest, its largest-magnitude entry positive). One-shard contexts only:
+ * column shards and multi-process contexts return CLIPPER_HIP_E_SCOPE. */
+int clipper_hip_sdp(clipper_hip_t* h, const clipper_sdp_params_t* params, double* X_out, double* Y_out,
+                    double* lambdas_out, double* evec1_out, clipper_sdp_info_t* info);
+/* Stand-alone: M and C column-major n x n (host), lower triangles read. nodes_out (capacity n, may be NULL)
+ * receives the selection; returns its size or <0. Other outputs as clipper_hip_sdp. */
+int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t n, const clipper_sdp_params_t* params,
+                          double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
+                          clipper_sdp_info_t* info);
+
 /* ---- before the path: putative associations ------------------------------------------------ */
 
 /* k nearest neighbours in P1 of every point of P0 (both d x n column-major as `clipper::Data`:
@@ -413,7 +467,7 @@ int clipper_hip_debug_occupy(int device, int workgroups, int lds_bytes, double m
 
 int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int64_t* hbm_bytes);
 
-/* ---- batched solves: many independent small problems in one call (DESIGN.md 10) -----------------
+/* ---- batched solves: many independent small problems in one call (DESIGN.md 11) -----------------
  * A batch owns one child context per problem slot (kept and reused from call to call) on one device
  * and ONE stream. A call scores every problem (the fills queued back to back, one wait for all of
  * them), plans each problem exactly as a lone context would, runs every problem whose plan is resident
