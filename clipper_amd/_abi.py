@@ -24,6 +24,7 @@ STORE_F32, STORE_F64, STORE_F32_CSC, STORE_F64_CSC = 0, 1, 2, 3
 ROUNDING_NONZERO, ROUNDING_DSD, ROUNDING_DSD_HEU = 0, 1, 2
 MC_EXACT, MC_HEU, MC_KCORE = 0, 1, 2  # CLIPPER_HIP_MC_* = maxclique::Method
 SDP_MAX_N = 128  # CLIPPER_HIP_SDP_MAX_N
+INVARIANT_MAX_D, INVARIANT_MAX_PARAMS = 32, 16  # CLIPPER_HIP_INVARIANT_MAX_D / _MAX_PARAMS
 
 # every symbol include/clipper_hip.h declares (checked by tests/test_abi_exports.py)
 EXPORTED_SYMBOLS = [
@@ -48,7 +49,8 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
     "clipper_hip_batch_get_selected_associations", "clipper_hip_batch_route", "clipper_hip_batch_get_stats",
-    "clipper_hip_batch_get_split",
+    "clipper_hip_batch_get_split", "clipper_hip_invariant_create", "clipper_hip_invariant_destroy",
+    "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom",
 ]
 
 
@@ -292,6 +294,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_batch_route.argtypes = [vp, C.c_int32]
     L.clipper_hip_batch_get_stats.argtypes = [vp, ip, ip, ip]
     L.clipper_hip_batch_get_split.argtypes = [vp, dp, dp, dp, dp]
+    L.clipper_hip_invariant_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.clipper_hip_invariant_destroy.argtypes = [vp]
+    L.clipper_hip_affinity_custom_staged.argtypes = [vp, vp, dp, C.c_int, C.c_double]
+    L.clipper_hip_affinity_custom.argtypes = [vp, vp, dp, C.c_int, i64, dp, i64, ip, i64, dp, C.c_int, C.c_double]
     _lib = L
     return L
 
@@ -320,6 +326,44 @@ def _assoc_colmajor(A):
     if A.ndim != 2 or A.shape[1] != 2:
         raise ValueError("A must be m x 2")
     return A, A.shape[0]
+
+
+def _params_array(params):
+    p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+    return p, (_dp(p) if p.size else None)
+
+
+class HipInvariant:
+    """A user-defined invariant compiled for datum dimension d (clipper_hip_invariant_create): HIP device source that
+    defines `__device__ double clipper_invariant(const double* ai, const double* aj, const double* bi,
+    const double* bj, const double* params)`. Needs no device; a compile error raises ClipperError with the compiler's
+    log. Usable as a context manager; close() releases the code object and its modules."""
+
+    def __init__(self, source: str, d: int):
+        self.L = load_library()
+        self.source, self.d = source, int(d)
+        h = C.c_void_p()
+        rc = self.L.clipper_hip_invariant_create(source.encode(), self.d, C.byref(h))
+        if rc < 0:
+            raise ClipperError(f"clipper_hip error {rc}: {self.L.clipper_hip_last_error().decode()}")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.clipper_hip_invariant_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HipClipper:
@@ -411,6 +455,21 @@ class HipClipper:
     def affinity_pointnormal_staged(self, sigp=0.5, epsp=0.5, sign=0.10, epsn=0.35):
         self._check(self.L.clipper_hip_affinity_pointnormal_staged(
             self.h, sigp, epsp, sign, epsn, self.params.affinityeps))
+
+    def affinity_custom(self, inv: HipInvariant, D1, D2, A=(), params=()):
+        """scorePairwiseConsistency with a user-defined invariant (clipper_hip_affinity_custom)"""
+        D1, D2 = _f64_colmajor(D1), _f64_colmajor(D2)
+        if D1.shape[0] != D2.shape[0]:
+            raise ValueError("D1 and D2 must have the same number of rows")
+        Ac, m = _assoc_colmajor(A)
+        p, pp = _params_array(params)
+        self._check(self.L.clipper_hip_affinity_custom(
+            self.h, inv.h, _dp(D1), D1.shape[0], D1.shape[1], _dp(D2), D2.shape[1],
+            _ip(Ac) if Ac is not None else None, m, pp, p.size, self.params.affinityeps))
+
+    def affinity_custom_staged(self, inv: HipInvariant, params=()):
+        p, pp = _params_array(params)
+        self._check(self.L.clipper_hip_affinity_custom_staged(self.h, inv.h, pp, p.size, self.params.affinityeps))
 
     def stage_u0(self, u0):
         u0 = np.ascontiguousarray(u0, dtype=np.float64)

@@ -6,6 +6,7 @@
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
 #include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>
 #include <rccl/rccl.h>
 
 #include <dlfcn.h>
@@ -32,6 +33,7 @@
 
 #include "../../include/clipper_hip.h"
 #include "kernels.hip.h"
+#include "k_custom_invariant_src.h"
 #include "dsd_host.h"
 #include "host_batch.hpp"
 #include "host_plan.hpp"
@@ -51,6 +53,7 @@ using namespace clipper_hip;
 #include "host_sdp.hpp"
 #include "host_solve.hpp"
 #include "host_batchsolve.hpp"
+#include "host_custom_invariant.hpp"
 #include "host_matrix_io.hpp"
 
 extern "C" {
@@ -163,6 +166,46 @@ int clipper_hip_affinity_pointnormal(clipper_hip_t* h, const double* D1, int d, 
                                      double affinityeps) try {
   if (d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance needs d == 6");
   return stage_and_fill(h, D1, d, n1, D2, n2, A, m, fill_pointnormal, PointNormalParams{sigp, epsp, sign, epsn, affinityeps});
+} CLIPPER_HIP_GUARD_INT
+
+// ---- user-defined invariants -------------------------------------------------------------
+
+int clipper_hip_invariant_create(const char* source, int d, clipper_hip_invariant_t** out) try {
+  if (out) *out = nullptr;
+  if (!source || !out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  if (d < 1 || d > CLIPPER_HIP_INVARIANT_MAX_D)
+    return fail(CLIPPER_HIP_E_INVALID, "invariant dimension d = %d outside [1, %d]", d, CLIPPER_HIP_INVARIANT_MAX_D);
+  auto* inv = new clipper_hip_invariant;
+  inv->d = d;
+  if (int rc = compile_custom(source, d, inv->code)) {
+    delete inv;
+    return rc;
+  }
+  *out = inv;
+  return 0;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_invariant_destroy(clipper_hip_invariant_t* inv) try {
+  if (inv) destroy_invariant(inv);
+  return 0;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_affinity_custom_staged(clipper_hip_t* h, const clipper_hip_invariant_t* inv, const double* params,
+                                       int nparams, double affinityeps) try {
+  if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  CustomFill f;
+  if (int rc = custom_fill_args(inv, params, nparams, affinityeps, f)) return rc;
+  return fill_custom(h, f);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_affinity_custom(clipper_hip_t* h, const clipper_hip_invariant_t* inv, const double* D1, int d,
+                                int64_t n1, const double* D2, int64_t n2, const int32_t* A, int64_t m,
+                                const double* params, int nparams, double affinityeps) try {
+  CustomFill f;
+  if (int rc = custom_fill_args(inv, params, nparams, affinityeps, f)) return rc;
+  if (d != inv->d)
+    return fail(CLIPPER_HIP_E_INVALID, "the invariant is compiled for d = %d, the data have d = %d", inv->d, d);
+  return stage_and_fill(h, D1, d, n1, D2, n2, A, m, fill_custom, f);
 } CLIPPER_HIP_GUARD_INT
 
 int64_t clipper_hip_num_associations(const clipper_hip_t* h) try {

@@ -5,6 +5,7 @@
 // is a call into libclipper_hip.so. Nothing here is a CPU implementation of that path:
 // if the GPU library reports an error, the facade throws.
 #include "clipper/clipper.h"
+#include "clipper/invariants/device.h"
 #include "clipper/sdp.h"
 
 #include <cmath>
@@ -64,6 +65,33 @@ double PointNormalDistance::operator()(const Datum& ai, const Datum& aj, const D
     return sp * sn;
   }
   return 0.0;
+}
+
+// a user-defined invariant in device source (include/clipper/invariants/device.h): compiled per dimension, on demand
+DeviceInvariant::DeviceInvariant(std::string source, std::vector<double> params)
+    : source_(std::move(source)), params_(std::move(params)) {
+  if (params_.size() > CLIPPER_HIP_INVARIANT_MAX_PARAMS)
+    throw std::invalid_argument("clipper: DeviceInvariant takes at most " +
+                                std::to_string(CLIPPER_HIP_INVARIANT_MAX_PARAMS) + " parameters");
+}
+
+DeviceInvariant::~DeviceInvariant() {
+  for (auto& kv : compiled_) clipper_hip_invariant_destroy(kv.second);
+}
+
+double DeviceInvariant::operator()(const Datum&, const Datum&, const Datum&, const Datum&) {
+  throw std::logic_error("clipper: a DeviceInvariant is evaluated on the GPU only (CLIPPER::scorePairwiseConsistency)");
+}
+
+clipper_hip_invariant* DeviceInvariant::handle(int d) const {
+  std::lock_guard<std::mutex> lock(mutex_);
+  auto it = compiled_.find(d);
+  if (it != compiled_.end()) return it->second;
+  clipper_hip_invariant* h = nullptr;
+  if (clipper_hip_invariant_create(source_.c_str(), d, &h) < 0)
+    throw std::runtime_error(std::string("clipper: DeviceInvariant: ") + clipper_hip_last_error());
+  compiled_.emplace(d, h);
+  return h;
 }
 
 }  // namespace invariants
@@ -236,6 +264,8 @@ void CLIPPER::scorePairwiseConsistency(const invariants::Data& D1, const invaria
   const bool exact_euclid = euclid && typeid(*invariant_) == typeid(invariants::EuclideanDistance);
   const bool exact_pointn =
       pointn && typeid(*invariant_) == typeid(invariants::PointNormalDistance);
+  auto device = std::dynamic_pointer_cast<invariants::DeviceInvariant>(invariant_);
+  const bool exact_device = device && typeid(*invariant_) == typeid(invariants::DeviceInvariant);
 
   if (exact_euclid) {
     const auto& p = euclid->params();
@@ -249,6 +279,13 @@ void CLIPPER::scorePairwiseConsistency(const invariants::Data& D1, const invaria
                                            D1.cols(), D2.data(), D2.cols(), A_.data(), m, p.sigp,
                                            p.epsp, p.sign, p.epsn, params_.affinityeps),
           "scorePairwiseConsistency[PointNormalDistance]");
+  } else if (exact_device) {
+    const int d = static_cast<int>(D1.rows());
+    clipper_hip_invariant* inv = device->handle(d);
+    const auto& p = device->params();
+    check(clipper_hip_affinity_custom(handle(), inv, D1.data(), d, D1.cols(), D2.data(), D2.cols(), A_.data(), m,
+                                      p.empty() ? nullptr : p.data(), static_cast<int>(p.size()), params_.affinityeps),
+          "scorePairwiseConsistency[DeviceInvariant]");
   } else {
     scoreCustomInvariantOnHost(D1, D2);
   }

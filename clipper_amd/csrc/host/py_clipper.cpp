@@ -15,6 +15,7 @@
 
 #include "clipper/batch.h"
 #include "clipper/clipper.h"
+#include "clipper/invariants/device.h"
 #include "clipper/sdp.h"
 #include "clipper/utils.h"
 
@@ -183,6 +184,12 @@ void pybind_invariants(py::module& m) {
   py::class_<PointNormalDistance, PairwiseInvariant, PyBuiltinInvariant<PointNormalDistance>,
              std::shared_ptr<PointNormalDistance>>(m, "PointNormalDistance")
       .def(py::init<const PointNormalDistance::Params&>());
+
+  // HIP device source, compiled at run time and evaluated on the GPU (include/clipper/invariants/device.h)
+  py::class_<DeviceInvariant, PairwiseInvariant, std::shared_ptr<DeviceInvariant>>(m, "DeviceInvariant")
+      .def(py::init<std::string, std::vector<double>>(), "source"_a, "params"_a = std::vector<double>())
+      .def_property_readonly("source", &DeviceInvariant::source)
+      .def_property_readonly("params", &DeviceInvariant::params);
 }
 
 void pybind_utils(py::module& m) {

@@ -116,6 +116,49 @@ int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
   });
 }
 
+// A user-defined invariant over the staged points (host_custom_invariant.hpp): every shard's dense store from the
+// invariant's own fill kernel, then the slices from it as for any dense store. No rectangular fill exists for it
+// (rect_fill_possible is false for kind 3): row views are built by filter, the live sub-problem stays off.
+int fill_custom(Ctx* h, const CustomFill& f) {
+  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
+  if (h->staged_d != f.inv->d)
+    return fail(CLIPPER_HIP_E_INVALID, "the invariant is compiled for d = %d, the staged inputs have d = %d", f.inv->d,
+                h->staged_d);
+  // every device's module before the build starts: a failed load leaves the matrix held untouched
+  const bool f64 = h->storage == CLIPPER_HIP_STORE_F64;  // the dense store's value type (dispatch_vt)
+  std::vector<hipFunction_t> fn(h->sh.size());
+  for (size_t k = 0; k < h->sh.size(); ++k) {
+    HIPCHK(hipSetDevice(h->sh[k].device));
+    if (int rc = custom_function(f.inv, h->sh[k].device, f64, fn[k])) return rc;
+  }
+  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+  h->fill_kind = 3;
+  h->fill_e = EuclidParams{};
+  h->fill_n = PointNormalParams{};
+  h->fill_E2 = 0.f;
+  int launch_rc = 0;
+  int rc = run_affinity(h, false, [&](Shard& s) {
+    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)), static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK)));
+    long long ld = W, m = mm, c0 = static_cast<int64_t>(s.slot) * W, ps = pstride;
+    int rows = AFF_ROWS_PER_BLK;
+    void* S = s.S;
+    const double *P1 = s.P1, *P2 = s.P2;
+    const int32_t *A0 = s.Adev, *A1 = s.Adev + mm;
+    CustomParams prm = f.prm;
+    void* args[] = {&S, &ld, &m, &c0, &rows, &P1, &P2, &ps, &A0, &A1, &prm};
+    const hipFunction_t k = fn[static_cast<size_t>(&s - h->sh.data())];
+    const hipError_t e = hipModuleLaunchKernel(k, grid.x, grid.y, 1, 256, 1, 1, 0, s.stream, args, nullptr);
+    if (e != hipSuccess && !launch_rc)
+      launch_rc = fail(CLIPPER_HIP_E_HIP, "hipModuleLaunchKernel (user-defined invariant): %s", hipGetErrorString(e));
+  });
+  if (launch_rc) {  // (run_affinity went on with a store the kernel never wrote)
+    h->has_matrix = false;
+    h->csc_valid = false;
+    return launch_rc;
+  }
+  return rc;
+}
+
 // device temporaries of one call, released on every path (by release(), or when it goes out of scope)
 struct DevTemps {
   std::vector<std::pair<int, void*>> v;

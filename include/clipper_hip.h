@@ -191,6 +191,42 @@ int clipper_hip_affinity_euclidean_staged(clipper_hip_t* h, double sigma, double
 int clipper_hip_affinity_pointnormal_staged(clipper_hip_t* h, double sigp, double epsp,
                                             double sign, double epsn, double affinityeps);
 
+/* ---- user-defined invariants ------------------------------------------- */
+
+/* A PairwiseInvariant written as HIP device source and compiled at run time (hiprtc, gfx950).
+ * The source defines
+ *   __device__ double clipper_invariant(const double* ai, const double* aj,
+ *                                       const double* bi, const double* bj,
+ *                                       const double* params);
+ * ai, aj, bi, bj point to CLIPPER_D doubles each (the library defines `constexpr int CLIPPER_D = d;`
+ * before the source); params to the up to CLIPPER_HIP_INVARIANT_MAX_PARAMS doubles of the fill.
+ * Helper functions and the math of <hip/hip_runtime.h> may be used. The matrix is the host loop's
+ * (clipper.cpp:31-64) for the same function: it is called for i < j with ai = D1[:, A(i,0)],
+ * aj = D1[:, A(j,0)], bi = D2[:, A(i,1)], bj = D2[:, A(j,1)], never for two associations that share
+ * an index; a score is kept only if score > affinityeps (NaN is not); M is symmetric, C = pattern(M). */
+#define CLIPPER_HIP_INVARIANT_MAX_D 32
+#define CLIPPER_HIP_INVARIANT_MAX_PARAMS 16
+typedef struct clipper_hip_invariant clipper_hip_invariant_t;
+
+/* Compiles `source` for datum dimension d (1 <= d <= CLIPPER_HIP_INVARIANT_MAX_D); needs no device.
+ * A compile error returns CLIPPER_HIP_E_INVALID with the compiler's log (line numbers relative to
+ * `source`, file name "invariant") in clipper_hip_last_error(); a library without libhiprtc returns
+ * CLIPPER_HIP_E_SCOPE. The handle keeps the code object and loads it on a device at its first fill
+ * there; it may serve any number of contexts (not concurrently with its own destruction). */
+int clipper_hip_invariant_create(const char* source, int d, clipper_hip_invariant_t** out);
+int clipper_hip_invariant_destroy(clipper_hip_invariant_t* inv);
+
+/* The pair loop of clipper.cpp:31-56 + :61-64 with the compiled invariant over the staged inputs
+ * (their d must be the invariant's: CLIPPER_HIP_E_INVALID otherwise). params: nparams doubles
+ * (0 <= nparams <= CLIPPER_HIP_INVARIANT_MAX_PARAMS; the rest of the block reads 0), passed at fill
+ * time, so that changing them compiles nothing. */
+int clipper_hip_affinity_custom_staged(clipper_hip_t* h, const clipper_hip_invariant_t* inv,
+                                       const double* params, int nparams, double affinityeps);
+/* = clipper_hip_stage_inputs(...) then clipper_hip_affinity_custom_staged(...) */
+int clipper_hip_affinity_custom(clipper_hip_t* h, const clipper_hip_invariant_t* inv, const double* D1, int d,
+                                int64_t n1, const double* D2, int64_t n2, const int32_t* A, int64_t m,
+                                const double* params, int nparams, double affinityeps);
+
 /* rows of A_ (= dimension of M_); CLIPPER::getInitialAssociations (clipper.cpp:117-120) */
 int64_t clipper_hip_num_associations(const clipper_hip_t* h);
 int clipper_hip_get_associations(const clipper_hip_t* h, int32_t* A_out /* col-major m x 2 */);
