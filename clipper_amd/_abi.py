@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
     "clipper_hip_batch_get_selected_associations", "clipper_hip_batch_route", "clipper_hip_batch_get_stats",
     "clipper_hip_batch_get_split", "clipper_hip_invariant_create", "clipper_hip_invariant_destroy",
-    "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom",
+    "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom", "clipper_hip_batch_solve_custom",
 ]
 
 
@@ -288,6 +288,8 @@ def load_library(path: str = LIB_PATH):
         [C.c_double] * 3 + [C.POINTER(Params)]
     L.clipper_hip_batch_solve_pointnormal.argtypes = [vp, C.POINTER(BatchProblem), C.c_int32] + \
         [C.c_double] * 4 + [C.POINTER(Params)]
+    L.clipper_hip_batch_solve_custom.argtypes = [vp, vp, C.POINTER(BatchProblem), C.c_int32, dp, C.c_int,
+                                                 C.POINTER(Params)]
     L.clipper_hip_batch_get_solution.argtypes = [vp, C.c_int32, dp, C.POINTER(SolveInfo)]
     L.clipper_hip_batch_get_nodes.argtypes = [vp, C.c_int32, ip, C.c_int32]
     L.clipper_hip_batch_get_selected_associations.argtypes = [vp, C.c_int32, ip, C.c_int32]
@@ -903,6 +905,19 @@ class HipBatch:
         arr, keep, d = self._problems(problems)
         self._check(self.L.clipper_hip_batch_solve_euclidean(self.b, arr, len(problems), d, sigma, epsilon, mindist,
                                                              C.byref(params)))
+        return self._collect(len(problems), keep)
+
+    def solve_custom(self, inv: HipInvariant, problems, params=(), solver_params: Params | None = None):
+        """the problems scored by a user-defined invariant (clipper_hip_batch_solve_custom): every D is inv.d x n;
+        params: the invariant's parameters (at most INVARIANT_MAX_PARAMS doubles)"""
+        solver_params = solver_params or Params()
+        arr, keep, _ = self._problems(problems, rows=inv.d)
+        for i, k in enumerate(keep):
+            if k[0].shape[0] != inv.d:
+                raise ValueError(f"problem {i}: the invariant is compiled for d = {inv.d}, D1 has {k[0].shape[0]} rows")
+        p, pp = _params_array(params)
+        self._check(self.L.clipper_hip_batch_solve_custom(self.b, inv.h, arr, len(problems), pp, p.size,
+                                                          C.byref(solver_params)))
         return self._collect(len(problems), keep)
 
     def solve_pointnormal(self, problems, sigp=0.5, epsp=0.5, sign=0.10, epsn=0.35, params: Params | None = None):

@@ -52,8 +52,8 @@ using namespace clipper_hip;
 #include "host_maxclique.hpp"
 #include "host_sdp.hpp"
 #include "host_solve.hpp"
-#include "host_batchsolve.hpp"
 #include "host_custom_invariant.hpp"
+#include "host_batchsolve.hpp"
 #include "host_matrix_io.hpp"
 
 extern "C" {
@@ -501,6 +501,10 @@ void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
   for (Ctx* c : b->kids) destroy_ctx(c);  // (they borrow the batch's stream: it goes last)
   if (b->hstage) hipHostFree(b->hstage);
   if (b->dstage) hipFree(b->dstage);
+  if (b->hfill) hipHostFree(b->hfill);
+  if (b->dfill) hipFree(b->dfill);
+  for (hipEvent_t e : b->ev_fill)
+    if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);
   delete b;
 } CLIPPER_HIP_GUARD_VOID
@@ -518,6 +522,15 @@ int clipper_hip_batch_solve_pointnormal(clipper_hip_batch_t* b, const clipper_ba
   if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   const double f[4] = {sigp, epsp, sign, epsn};
   return batch_solve(b, p, n, 6, 2, f, prm);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_solve_custom(clipper_hip_batch_t* b, const clipper_hip_invariant_t* inv,
+                                   const clipper_batch_problem_t* p, int32_t n, const double* params, int nparams,
+                                   const clipper_params_t* prm) try {
+  CustomFill f;  // (inv and nparams first, as clipper_hip_affinity_custom checks them)
+  if (int rc = custom_fill_args(inv, params, nparams, prm ? prm->affinityeps : 0.0, f)) return rc;
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return batch_solve(b, p, n, inv->d, 3, nullptr, prm, &f);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_batch_get_solution(const clipper_hip_batch_t* b, int32_t i, double* u_out,

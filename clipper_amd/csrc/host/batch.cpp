@@ -18,6 +18,15 @@ CLIPPERBatch::CLIPPERBatch(const invariants::PairwiseInvariantPtr& invariant, co
   else throw std::invalid_argument("clipper: CLIPPERBatch takes EuclideanDistance or PointNormalDistance only");
 }
 
+std::unique_ptr<CLIPPERBatch> CLIPPERBatch::withDeviceInvariant(const invariants::DeviceInvariantPtr& invariant,
+                                                                const Params& params) {
+  if (!invariant) throw std::invalid_argument("clipper: CLIPPERBatch::withDeviceInvariant needs an invariant");
+  std::unique_ptr<CLIPPERBatch> b(new CLIPPERBatch(params));
+  b->invariant_ = invariant;
+  b->kind_ = 3;
+  return b;
+}
+
 CLIPPERBatch::~CLIPPERBatch() {
   if (b_) clipper_hip_batch_destroy(b_);
 }
@@ -81,9 +90,14 @@ std::vector<Solution> CLIPPERBatch::solve(const std::vector<BatchProblem>& probl
   if (kind_ == 1) {
     const auto& e = std::static_pointer_cast<invariants::EuclideanDistance>(invariant_)->params();
     check(clipper_hip_batch_solve_euclidean(b_, p.data(), nn, d, e.sigma, e.epsilon, e.mindist, &prm), "batch solve");
-  } else {
+  } else if (kind_ == 2) {
     const auto& e = std::static_pointer_cast<invariants::PointNormalDistance>(invariant_)->params();
     check(clipper_hip_batch_solve_pointnormal(b_, p.data(), nn, e.sigp, e.epsp, e.sign, e.epsn, &prm), "batch solve");
+  } else {
+    const auto inv = std::static_pointer_cast<invariants::DeviceInvariant>(invariant_);
+    const std::vector<double>& f = inv->params();
+    check(clipper_hip_batch_solve_custom(b_, inv->handle(d), p.data(), nn, f.data(), static_cast<int>(f.size()), &prm),
+          "batch solve");
   }
   std::vector<Solution> out(n);
   for (size_t i = 0; i < n; ++i) {

@@ -356,6 +356,9 @@ PYBIND11_MODULE(clipperpy, m) {
   py::class_<clipper::CLIPPERBatch>(m, "CLIPPERBatch")
       .def(py::init<const clipper::invariants::PairwiseInvariantPtr&, const clipper::Params&>(), "invariant"_a,
            "params"_a, py::keep_alive<1, 2>())
+      // a batch scored by a DeviceInvariant (the constructor takes the built-ins only)
+      .def_static("with_device_invariant", &clipper::CLIPPERBatch::withDeviceInvariant, "invariant"_a, "params"_a,
+                  py::keep_alive<0, 1>())
       .def("__repr__", [](const clipper::CLIPPERBatch&) { return "<CLIPPERBatch>"; })
       .def("set_device", &clipper::CLIPPERBatch::setDevice, "device"_a)
       .def("set_storage", &clipper::CLIPPERBatch::setStorage, "storage"_a)

@@ -6,7 +6,9 @@
 //   1. checks every problem (nothing reaches the device if one is invalid),
 //   2. stages all inputs (D1, D2, the association lists, u0) in one pinned buffer and copies it with ONE H2D copy,
 //   3. queues every child's fill back to back (run_affinity in its deferred mode) and waits ONCE; children whose
-//      slice arenas overflowed (the first use of a size) fill again, in a second round of their own,
+//      slice arenas overflowed (the first use of a size) fill again, in a second round of their own. A user-defined
+//      invariant (kind 3, batch_fill_custom) fills every child's dense store in ONE launch instead, then queues the
+//      children's slice builds back to back and waits once per round of builds,
 //   4. plans each child exactly as a lone solve would (the fill's own slices_plan -> resident_plan): the unit split,
 //      hence the order of every addition, is the lone solve's,
 //   5. packs the resident plans into launches of k_solve_resident_batch (host_batchpack.hpp), queues them back to
@@ -39,27 +41,140 @@ struct clipper_hip_batch {
   size_t hstage_cap = 0;
   uint8_t* dstage = nullptr;  // its device copy
   size_t dstage_cap = 0;
+  uint8_t* hfill = nullptr;  // pinned staging of a custom fill's problems and tiles (kind 3)
+  size_t hfill_cap = 0;
+  uint8_t* dfill = nullptr;  // its device copy
+  size_t dfill_cap = 0;
+  hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around a custom fill's launch
+  double t_fill_begin = 0.0, t_fill_launch = 0.0, t_fill_build = 0.0;  // kind 3: the parts of t_fill (ms)
 };
 
 namespace {
 
 using Batch = clipper_hip_batch;
 
-int batch_grow(Batch* b, size_t bytes) {
-  if (bytes > b->hstage_cap) {
-    if (b->hstage) HIPCHK(hipHostFree(b->hstage));
-    b->hstage = nullptr;
-    b->hstage_cap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b->hstage), bytes, hipHostMallocDefault));
-    b->hstage_cap = bytes;
+// a pinned buffer and its device copy of at least `bytes` each (contents lost when they grow)
+int stage_grow(uint8_t*& hbuf, size_t& hcap, uint8_t*& dbuf, size_t& dcap, size_t bytes) {
+  if (bytes > hcap) {
+    if (hbuf) HIPCHK(hipHostFree(hbuf));
+    hbuf = nullptr;
+    hcap = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hbuf), bytes, hipHostMallocDefault));
+    hcap = bytes;
   }
-  if (bytes > b->dstage_cap) {
-    if (b->dstage) HIPCHK(hipFree(b->dstage));
-    b->dstage = nullptr;
-    b->dstage_cap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&b->dstage), bytes));
-    b->dstage_cap = bytes;
+  if (bytes > dcap) {
+    if (dbuf) HIPCHK(hipFree(dbuf));
+    dbuf = nullptr;
+    dcap = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dbuf), bytes));
+    dcap = bytes;
   }
+  return 0;
+}
+
+int batch_grow(Batch* b, size_t bytes) { return stage_grow(b->hstage, b->hstage_cap, b->dstage, b->dstage_cap, bytes); }
+
+// Step 3 for a user-defined invariant (kind 3). Every child: its inputs staged, then fill_custom's and run_affinity's
+// steps before a launch (custom_fill_begin, affinity_begin: the dense store allocated). Then ONE launch of the
+// batched fill kernel over every child's tiles (the lone kernel's grid, problem after problem), whose descriptors and
+// tile table reach the device in one copy of their own. Then csc_rebuild in its deferred form: every compressed child's
+// build queued back to back, one wait, the checks; children that overflowed build again (three builds at most, as
+// pack_until_fits allows). Dense storages keep their store. A child's affinity_kernel_ms is the batched launch's time
+// (shared by every problem of the call), without the build.
+int batch_fill_custom(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d,
+                      const std::vector<std::vector<int32_t>>& Afull, const std::vector<StagedInputs>& dev,
+                      const std::vector<size_t>& off_u0, const CustomFill& cf) {
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  hipFunction_t fn = nullptr;
+  size_t ntiles = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    const clipper_batch_problem_t& q = p[i];
+    const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
+    const int64_t m = static_cast<int64_t>(A.size() / 2);
+    if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
+    std::vector<hipFunction_t> f;
+    if (int rc = custom_fill_begin(c, cf, true, f)) return rc;
+    fn = f[0];
+    bool emit = false, rect = false;
+    if (int rc = affinity_begin(c, false, emit, rect)) return rc;
+    if (emit || rect) return fail(CLIPPER_HIP_E_INTERNAL, "problem %d: a custom fill goes through the dense store", i);
+    c->csc_emitted = false;  // (as run_affinity's launch loop leaves a fill that does not emit)
+    c->csc_out = CscOut{};
+    HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
+                          hipMemcpyDeviceToDevice, b->stream));
+    c->u0_staged = true;
+    ntiles += static_cast<size_t>(ceil_div(c->W, 1024) * ceil_div(m, AFF_ROWS_PER_BLK));
+  }
+  if (ntiles > 0x7fffffffu) return fail(CLIPPER_HIP_E_SCOPE, "a batched fill of %zu workgroups", ntiles);
+
+  // the problems and the tile table: one copy, one launch
+  const size_t pbytes = static_cast<size_t>(round_up(static_cast<int64_t>(n) * sizeof(CustomFillProblem), 256));
+  if (int rc = stage_grow(b->hfill, b->hfill_cap, b->dfill, b->dfill_cap, pbytes + ntiles * sizeof(CustomFillTile)))
+    return rc;
+  CustomFillProblem* probs = reinterpret_cast<CustomFillProblem*>(b->hfill);
+  CustomFillTile* tiles = reinterpret_cast<CustomFillTile*>(b->hfill + pbytes);
+  size_t t = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const Ctx* c = b->kids[static_cast<size_t>(i)];
+    const Shard& s = c->sh[0];
+    probs[i] = CustomFillProblem{s.S, c->W, c->m, s.P1, s.P2, c->staged_pstride, s.Adev, s.Adev + c->m};
+    const int nc = static_cast<int>(ceil_div(c->W, 1024)), nr = static_cast<int>(ceil_div(c->m, AFF_ROWS_PER_BLK));
+    for (int y = 0; y < nr; ++y)
+      for (int x = 0; x < nc; ++x) tiles[t++] = CustomFillTile{i, x, y};
+  }
+  HIPCHK(hipMemcpyAsync(b->dfill, b->hfill, pbytes + ntiles * sizeof(CustomFillTile), hipMemcpyHostToDevice, b->stream));
+  if (!b->ev_fill[0]) {
+    HIPCHK(hipEventCreate(&b->ev_fill[0]));
+    HIPCHK(hipEventCreate(&b->ev_fill[1]));
+  }
+  const auto t1 = std::chrono::high_resolution_clock::now();
+  {
+    const CustomFillProblem* dprobs = reinterpret_cast<const CustomFillProblem*>(b->dfill);
+    const CustomFillTile* dtiles = reinterpret_cast<const CustomFillTile*>(b->dfill + pbytes);
+    int rows = AFF_ROWS_PER_BLK;
+    CustomParams prm = cf.prm;
+    void* args[] = {&dprobs, &dtiles, &rows, &prm};
+    HIPCHK(hipEventRecord(b->ev_fill[0], b->stream));
+    const hipError_t e = hipModuleLaunchKernel(fn, static_cast<unsigned>(ntiles), 1, 1, 256, 1, 1, 0, b->stream, args,
+                                               nullptr);
+    if (e != hipSuccess)
+      return fail(CLIPPER_HIP_E_HIP, "hipModuleLaunchKernel (user-defined invariant, batched): %s", hipGetErrorString(e));
+    HIPCHK(hipEventRecord(b->ev_fill[1], b->stream));
+  }
+
+  // the slice builds: queued back to back, one wait per round
+  std::vector<int32_t> todo;
+  for (int32_t i = 0; i < n; ++i)
+    if (csc_applies(b->kids[static_cast<size_t>(i)])) todo.push_back(i);
+  float kms = 0.f;
+  int rounds = 0;
+  for (int round = 0;; ++round) {
+    rounds = round + 1;
+    for (int32_t i : todo)
+      if (int rc = csc_build_enqueue(b->kids[static_cast<size_t>(i)])) return rc;
+    if (hipStreamSynchronize(b->stream) != hipSuccess)
+      return fail(CLIPPER_HIP_E_HIP, "batched custom fill: %s", hipGetErrorString(hipGetLastError()));
+    if (round == 0) HIPCHK(hipEventElapsedTime(&kms, b->ev_fill[0], b->ev_fill[1]));
+    std::vector<int32_t> again_list;
+    for (int32_t i : todo) {
+      bool again = false;
+      if (int rc = csc_build_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
+      if (again) again_list.push_back(i);
+    }
+    if (again_list.empty()) break;
+    if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+    todo.swap(again_list);
+  }
+  for (int32_t i = 0; i < n; ++i) fill_held(b->kids[static_cast<size_t>(i)], kms);
+  const auto t2 = std::chrono::high_resolution_clock::now();
+  b->t_fill_begin = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  b->t_fill_launch = kms;
+  b->t_fill_build = std::chrono::duration<double, std::milli>(t2 - t1).count();
+  if (std::getenv("CLIPPER_HIP_HOST_TIMING"))
+    std::fprintf(stderr, "[batch-custom] n = %d: stage + begin (dense stores) %.3f ms, %zu tiles %.3f ms (events), "
+                 "launch + builds %.3f ms, %d build round%s\n", n, b->t_fill_begin, ntiles, b->t_fill_launch,
+                 b->t_fill_build, rounds, rounds == 1 ? "" : "s");
   return 0;
 }
 
@@ -102,18 +217,21 @@ int batch_launch(Batch* b, int key, unsigned grid, const ResidentLaunchEntry* ta
   }
 }
 
-// kind 1: EuclideanDistance (f = {sigma, epsilon, mindist}), 2: PointNormalDistance (f = {sigp, epsp, sign, epsn})
+// kind 1: EuclideanDistance (f = {sigma, epsilon, mindist}), 2: PointNormalDistance (f = {sigp, epsp, sign, epsn}),
+// 3: a user-defined invariant (cf; d = its dimension)
 int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, int kind, const double* f,
-                const clipper_params_t* P) {
+                const clipper_params_t* P, const CustomFill* cf = nullptr) {
   const auto t0 = std::chrono::high_resolution_clock::now();
   b->res.clear();
   b->launches = b->n_batched = b->n_alone = 0;
   b->t_fill = b->t_launch = b->t_alone = b->t_round = 0.0;
+  b->t_fill_begin = b->t_fill_launch = b->t_fill_build = 0.0;
   // ---- 1. every problem checked before any device work -------------------------------------------------------------
   SolverParams prm;
   if (int rc = solver_params(P, prm)) return rc;
   if (n < 0 || (n > 0 && !p)) return fail(CLIPPER_HIP_E_INVALID, "invalid problem list");
   if (kind == 2 && d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance data are 6 x n");
+  if (kind == 3 && (!cf || d != cf->inv->d)) return fail(CLIPPER_HIP_E_INVALID, "no invariant of dimension d = %d", d);
   if (d < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid dimension d = %d", d);
   std::vector<std::vector<int32_t>> Afull(static_cast<size_t>(n));  // the lists as stage_inputs holds them
   size_t bytes = 0;
@@ -168,39 +286,43 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   }
 
   // ---- 3. the fills, queued back to back; one wait; the overflowed ones again ----------------------------------------
-  auto fill = [&](Ctx* c) -> int {
-    c->fill_deferred = true;
-    const int rc = kind == 1 ? fill_euclidean(c, EuclidParams{f[0], f[1], f[2], P->affinityeps})
-                             : fill_pointnormal(c, PointNormalParams{f[0], f[1], f[2], f[3], P->affinityeps});
-    c->fill_deferred = false;
-    return rc;
-  };
-  for (int32_t i = 0; i < n; ++i) {
-    Ctx* c = b->kids[static_cast<size_t>(i)];
-    const clipper_batch_problem_t& q = p[i];
-    const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
-    const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
-    if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
-    if (int rc = fill(c)) return rc;
-    HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
-                          hipMemcpyDeviceToDevice, b->stream));
-    c->u0_staged = true;
-  }
-  std::vector<int32_t> todo;
-  for (int32_t i = 0; i < n; ++i) todo.push_back(i);
-  for (int round = 0; !todo.empty(); ++round) {
-    HIPCHK(hipStreamSynchronize(b->stream));
-    std::vector<int32_t> again_list;
-    for (int32_t i : todo) {
-      bool again = false;
-      if (int rc = fill_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
-      if (again) again_list.push_back(i);
+  if (kind == 3) {
+    if (int rc = batch_fill_custom(b, p, n, d, Afull, dev, off_u0, *cf)) return rc;
+  } else {
+    auto fill = [&](Ctx* c) -> int {
+      c->fill_deferred = true;
+      const int rc = kind == 1 ? fill_euclidean(c, EuclidParams{f[0], f[1], f[2], P->affinityeps})
+                               : fill_pointnormal(c, PointNormalParams{f[0], f[1], f[2], f[3], P->affinityeps});
+      c->fill_deferred = false;
+      return rc;
+    };
+    for (int32_t i = 0; i < n; ++i) {
+      Ctx* c = b->kids[static_cast<size_t>(i)];
+      const clipper_batch_problem_t& q = p[i];
+      const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
+      const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
+      if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
+      if (int rc = fill(c)) return rc;
+      HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
+                            hipMemcpyDeviceToDevice, b->stream));
+      c->u0_staged = true;
     }
-    if (again_list.empty()) break;
-    if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
-    for (int32_t i : again_list)
-      if (int rc = fill(b->kids[static_cast<size_t>(i)])) return rc;
-    todo.swap(again_list);
+    std::vector<int32_t> todo;
+    for (int32_t i = 0; i < n; ++i) todo.push_back(i);
+    for (int round = 0; !todo.empty(); ++round) {
+      HIPCHK(hipStreamSynchronize(b->stream));
+      std::vector<int32_t> again_list;
+      for (int32_t i : todo) {
+        bool again = false;
+        if (int rc = fill_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
+        if (again) again_list.push_back(i);
+      }
+      if (again_list.empty()) break;
+      if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+      for (int32_t i : again_list)
+        if (int rc = fill(b->kids[static_cast<size_t>(i)])) return rc;
+      todo.swap(again_list);
+    }
   }
   const auto t1 = std::chrono::high_resolution_clock::now();
   b->t_fill = std::chrono::duration<double, std::milli>(t1 - t0).count();

@@ -1,7 +1,8 @@
 // host_custom_invariant.hpp — user-defined invariants: the hiprtc binding (loaded at run time, as RCCL
 // is), the compile of one invariant's program (k_custom_invariant_src.h around the user's source) and the handle that
 // keeps its code object and the modules loaded from it, one per device. The fill itself is fill_custom
-// (host_matrix_io.hpp). Part of clipper_hip.hip (one translation unit; included there, in order).
+// (host_matrix_io.hpp), a batch's fill batch_fill_custom (host_batchsolve.hpp). Part of clipper_hip.hip (one
+// translation unit; included there, in order).
 #pragma once
 
 namespace {
@@ -58,7 +59,8 @@ struct clipper_hip_invariant {
   std::vector<char> code;
   struct Loaded {
     hipModule_t module = nullptr;
-    hipFunction_t fill[2] = {nullptr, nullptr};  // fp32, fp64 dense store
+    hipFunction_t fill[2] = {nullptr, nullptr};   // fp32, fp64 dense store
+    hipFunction_t batch[2] = {nullptr, nullptr};  // the same, a batch's fill (one launch for every problem)
   };
   mutable std::mutex mutex;
   mutable std::map<int, Loaded> loaded;  // by device
@@ -119,21 +121,24 @@ int compile_custom(const char* source, int d, std::vector<char>& code) {
   return rc;
 }
 
-// the fill kernel of `inv` for this device and value type, its module loaded on first use (the caller has set the device)
-int custom_function(const Invariant* inv, int device, bool f64, hipFunction_t& fn) {
+// the fill kernel of `inv` for this device and value type, lone or a batch's, its module loaded on first use (the
+// caller has set the device)
+int custom_function(const Invariant* inv, int device, bool f64, hipFunction_t& fn, bool batched = false) {
   std::lock_guard<std::mutex> lock(inv->mutex);
   auto it = inv->loaded.find(device);
   if (it == inv->loaded.end()) {
     Invariant::Loaded l;
     HIPCHK(hipModuleLoadData(&l.module, inv->code.data()));
     if (hipModuleGetFunction(&l.fill[0], l.module, "clipper_custom_fill_f32") != hipSuccess ||
-        hipModuleGetFunction(&l.fill[1], l.module, "clipper_custom_fill_f64") != hipSuccess) {
+        hipModuleGetFunction(&l.fill[1], l.module, "clipper_custom_fill_f64") != hipSuccess ||
+        hipModuleGetFunction(&l.batch[0], l.module, "clipper_custom_fill_batch_f32") != hipSuccess ||
+        hipModuleGetFunction(&l.batch[1], l.module, "clipper_custom_fill_batch_f64") != hipSuccess) {
       (void)hipModuleUnload(l.module);
       return fail(CLIPPER_HIP_E_HIP, "the invariant's code object lacks its fill kernels");
     }
     it = inv->loaded.emplace(device, l).first;
   }
-  fn = it->second.fill[f64 ? 1 : 0];
+  fn = batched ? it->second.batch[f64 ? 1 : 0] : it->second.fill[f64 ? 1 : 0];
   return 0;
 }
 
@@ -147,6 +152,27 @@ int custom_fill_args(const Invariant* inv, const double* params, int nparams, do
   f.prm = CustomParams{};
   for (int k = 0; k < nparams; ++k) f.prm.p[k] = params[k];
   f.prm.affinityeps = affinityeps;
+  return 0;
+}
+
+// A fill's steps with a user-defined invariant before run_affinity (fill_custom, host_matrix_io.hpp; a batch's fill,
+// host_batchsolve.hpp): the staged dimension checked, every shard's fill kernel (lone or batched) loaded before the
+// build starts — a failed load leaves the matrix held untouched — then the fill's kind set.
+int custom_fill_begin(Ctx* h, const CustomFill& f, bool batched, std::vector<hipFunction_t>& fn) {
+  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
+  if (h->staged_d != f.inv->d)
+    return fail(CLIPPER_HIP_E_INVALID, "the invariant is compiled for d = %d, the staged inputs have d = %d", f.inv->d,
+                h->staged_d);
+  const bool f64 = h->storage == CLIPPER_HIP_STORE_F64;  // the dense store's value type (dispatch_vt)
+  fn.assign(h->sh.size(), nullptr);
+  for (size_t k = 0; k < h->sh.size(); ++k) {
+    HIPCHK(hipSetDevice(h->sh[k].device));
+    if (int rc = custom_function(f.inv, h->sh[k].device, f64, fn[k], batched)) return rc;
+  }
+  h->fill_kind = 3;
+  h->fill_e = EuclidParams{};
+  h->fill_n = PointNormalParams{};
+  h->fill_E2 = 0.f;
   return 0;
 }
 

@@ -440,6 +440,23 @@ int pack_until_fits(Ctx* h, Shard& s, bool with_groups, int rounds, const char* 
   return 0;
 }
 
+// groups from shard s's dense store, then the slices from the groups, queued on its stream (O: groups_prepare's)
+template <typename VT>
+int groups_enqueue(Ctx* h, Shard& s, const GroupOut<VT>& O) {
+  dim3 grid(h->csc_nstrips, static_cast<unsigned>(ceil_div(h->csc_nblocks, 2))), block(256);
+  hipLaunchKernelGGL((k_groups_from_dense<VT>), grid, block, 0, s.stream, static_cast<const VT*>(s.S), h->W, h->m, O);
+  return slices_enqueue<VT>(h, s, group_source<VT>(h, s), s.cctl);
+}
+
+// the end of a build from the dense store(s), once every shard's slices fit: M lives in the slices from here on
+// (getters materialise a dense copy on demand)
+int csc_rebuilt(Ctx* h) {
+  h->csc_valid = true;
+  drop_dense(h);
+  if (int rc = sync_all(h)) return rc;
+  return gather_slice_bytes(h);  // column shards: the row-view policy's cost model is about THIS matrix
+}
+
 // groups from the dense store(s) + pack + wait + plan: the setMatrixData paths, and every fill
 // that went through a dense store. Shard by shard (the pinned staging is shared).
 int csc_rebuild(Ctx* h) {
@@ -450,20 +467,39 @@ int csc_rebuild(Ctx* h) {
   dispatch_vt(h, [&](auto t) {
     using VT = decltype(t);
     for (auto& s : h->sh) {
-      rc = pack_until_fits<VT>(h, s, true, 3, "compressed storage: build failed", [&](const GroupOut<VT>& O) {
-        dim3 grid(h->csc_nstrips, static_cast<unsigned>(ceil_div(h->csc_nblocks, 2))), block(256);
-        hipLaunchKernelGGL((k_groups_from_dense<VT>), grid, block, 0, s.stream,
-                           static_cast<const VT*>(s.S), h->W, h->m, O);
-        return slices_enqueue<VT>(h, s, group_source<VT>(h, s), s.cctl);
-      });
+      rc = pack_until_fits<VT>(h, s, true, 3, "compressed storage: build failed",
+                               [&](const GroupOut<VT>& O) { return groups_enqueue<VT>(h, s, O); });
       if (rc) return;
     }
   });
   if (rc) return rc;
-  h->csc_valid = true;
-  drop_dense(h);  // M lives in the slices from here on (getters materialise a dense copy on demand)
-  if ((rc = sync_all(h))) return rc;
-  return gather_slice_bytes(h);  // column shards: the row-view policy's cost model is about THIS matrix
+  return csc_rebuilt(h);
+}
+
+// csc_rebuild in two halves, for a batch that queues many contexts' builds and waits once (one shard, its stream
+// shared): csc_build_enqueue queues the build; once the stream has drained, csc_build_complete checks it (again = true:
+// the buffers were grown, enqueue again; pack_until_fits allows three builds) or ends it as csc_rebuild ends.
+int csc_build_enqueue(Ctx* h) {
+  h->csc_valid = false;
+  h->total_slice_bytes = 0.0;
+  if (!csc_applies(h)) return 0;
+  int rc = 0;
+  dispatch_vt(h, [&](auto t) {
+    using VT = decltype(t);
+    GroupOut<VT> O;
+    if ((rc = groups_prepare<VT>(h, h->sh[0], O))) return;
+    rc = groups_enqueue<VT>(h, h->sh[0], O);
+  });
+  return rc;
+}
+
+int csc_build_complete(Ctx* h, bool& again) {
+  again = false;
+  if (!csc_applies(h)) return 0;
+  int rc = 0;
+  dispatch_vt(h, [&](auto t) { rc = slices_check<decltype(t)>(h, h->sh[0], true, again); });
+  if (rc || again) return rc;
+  return csc_rebuilt(h);
 }
 
 bool rect_fill_possible(const Ctx* h);
@@ -546,8 +582,10 @@ int run_affinity_rect(Ctx* h, double& kernel_ms) {
 // (k_affinity_sym, fp32) — then neither a dense store nor groups are needed
 int fill_done(Ctx* h, double build_ms);
 
-template <typename Launch>
-int run_affinity(Ctx* h, bool emits, Launch launch) {
+// What a fill through run_affinity does before it launches anything: the matrix held is given up, the tiles planned,
+// the route chosen (emit: the fill kernel writes the slices; rect: the rectangular fill builds them, no dense store) and,
+// on the dense-store route, the store allocated. A batch's custom fill (host_batchsolve.hpp) starts with it too.
+int affinity_begin(Ctx* h, bool emits, bool& emit, bool& rect) {
   h->fill_pending = false;
   h->has_matrix = false;  // until the build has succeeded (a failed rebuild leaves no matrix)
   h->csc_valid = false;
@@ -557,9 +595,20 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
   drop_explicit_c(h);  // not needed on this path: C == pattern(M)
   h->explicitC = false;
   plan_tiles(h);
-  int rc = 0;
-  const bool emit = csc_applies(h) && csc_single(h) && emits;  // (fp32 values, or fp64 values: k_affinity_sym<.., VT>)
-  if (!emit && csc_applies(h) && rect_fill_possible(h) && !h->plain_affinity && !h->strip_affinity) {
+  emit = csc_applies(h) && csc_single(h) && emits;  // (fp32 values, or fp64 values: k_affinity_sym<.., VT>)
+  rect = !emit && csc_applies(h) && rect_fill_possible(h) && !h->plain_affinity && !h->strip_affinity;
+  if (rect) return 0;
+  if (emit) drop_dense(h);  // a materialised copy would be stale
+  else if (int rc = ensure_dense(h, false)) return rc;
+  return 0;
+}
+
+template <typename Launch>
+int run_affinity(Ctx* h, bool emits, Launch launch) {
+  bool emit = false, rect = false;
+  int rc = affinity_begin(h, emits, emit, rect);
+  if (rc) return rc;
+  if (rect) {
     double kms = 0.0;
     if ((rc = run_affinity_rect(h, kms))) return rc;
     h->csc_valid = true;
@@ -570,8 +619,6 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
     h->has_matrix = true;
     return 0;
   }
-  if (emit) drop_dense(h);  // a materialised copy would be stale
-  else if ((rc = ensure_dense(h, false))) return rc;
   Shard& s0 = h->sh[0];
   HIPCHK(hipSetDevice(s0.device));
   if (!h->ev_aff[0]) {
@@ -639,15 +686,20 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
   return fill_done(h, build_ms);
 }
 
+// the matrix is held: its fill's timings recorded (kernel_ms: the fill kernel's time, and the build's if any)
+void fill_held(Ctx* h, double kernel_ms) {
+  h->tm.affinity_kernel_ms = kernel_ms;
+  h->tm.affinity_bytes = h->csc_valid ? static_cast<double>(h->sh[0].s_bytes)
+                                      : static_cast<double>(h->sh[0].bytes_S);
+  h->has_matrix = true;
+}
+
 // the end of a fill through run_affinity: timings, the matrix is held
 int fill_done(Ctx* h, double build_ms) {
   float ms = 0.f;
   HIPCHK(hipSetDevice(h->sh[0].device));
   HIPCHK(hipEventElapsedTime(&ms, h->ev_aff[0], h->ev_aff[1]));
-  h->tm.affinity_kernel_ms = ms + (h->csc_valid ? build_ms : 0.0);
-  h->tm.affinity_bytes = h->csc_valid ? static_cast<double>(h->sh[0].s_bytes)
-                                      : static_cast<double>(h->sh[0].bytes_S);
-  h->has_matrix = true;
+  fill_held(h, ms + (h->csc_valid ? build_ms : 0.0));
   return 0;
 }
 

@@ -120,22 +120,9 @@ int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
 // invariant's own fill kernel, then the slices from it as for any dense store. No rectangular fill exists for it
 // (rect_fill_possible is false for kind 3): row views are built by filter, the live sub-problem stays off.
 int fill_custom(Ctx* h, const CustomFill& f) {
-  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
-  if (h->staged_d != f.inv->d)
-    return fail(CLIPPER_HIP_E_INVALID, "the invariant is compiled for d = %d, the staged inputs have d = %d", f.inv->d,
-                h->staged_d);
-  // every device's module before the build starts: a failed load leaves the matrix held untouched
-  const bool f64 = h->storage == CLIPPER_HIP_STORE_F64;  // the dense store's value type (dispatch_vt)
-  std::vector<hipFunction_t> fn(h->sh.size());
-  for (size_t k = 0; k < h->sh.size(); ++k) {
-    HIPCHK(hipSetDevice(h->sh[k].device));
-    if (int rc = custom_function(f.inv, h->sh[k].device, f64, fn[k])) return rc;
-  }
+  std::vector<hipFunction_t> fn;
+  if (int rc = custom_fill_begin(h, f, false, fn)) return rc;
   const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
-  h->fill_kind = 3;
-  h->fill_e = EuclidParams{};
-  h->fill_n = PointNormalParams{};
-  h->fill_E2 = 0.f;
   int launch_rc = 0;
   int rc = run_affinity(h, false, [&](Shard& s) {
     dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)), static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK)));

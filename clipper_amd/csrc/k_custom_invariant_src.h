@@ -7,6 +7,8 @@
 // come from one call on the same arguments; the rest of the contract is the host loop's (clipper.cpp:31-64).
 #pragma once
 
+#include <cstddef>
+
 namespace clipper_hip {
 
 constexpr int CUSTOM_MAX_PARAMS = 16;  // doubles a fill hands to clipper_invariant (CLIPPER_HIP_INVARIANT_MAX_PARAMS)
@@ -19,6 +21,37 @@ struct CustomParams {
   double affinityeps;
 };
 
+// One problem of a batched fill (clipper_custom_fill_batch_*): its dense store S (pitch ld, columns from 0), m, its
+// gathered point tables and its association list's two columns. Twin of the epilogue's clipper_fill_problem: the two
+// layouts must stay identical (the asserts pin this one).
+struct CustomFillProblem {
+  void* S;
+  long long ld;
+  long long m;
+  const double* P1;
+  const double* P2;
+  long long pstride;
+  const int* A0;
+  const int* A1;
+};
+static_assert(sizeof(CustomFillProblem) == 64, "CustomFillProblem: layout of clipper_fill_problem");
+static_assert(offsetof(CustomFillProblem, ld) == 8 && offsetof(CustomFillProblem, m) == 16 &&
+                  offsetof(CustomFillProblem, P1) == 24 && offsetof(CustomFillProblem, P2) == 32 &&
+                  offsetof(CustomFillProblem, pstride) == 40 && offsetof(CustomFillProblem, A0) == 48 &&
+                  offsetof(CustomFillProblem, A1) == 56,
+              "CustomFillProblem: layout of clipper_fill_problem");
+
+// One workgroup of a batched fill: which problem, and which tile of it the lone fill's (blockIdx.x, blockIdx.y) would
+// be. Twin of the epilogue's clipper_fill_tile.
+struct CustomFillTile {
+  int problem;
+  int cblk;    // column block: 1024 columns
+  int rstrip;  // row strip: rows_per_blk rows
+};
+static_assert(sizeof(CustomFillTile) == 12 && offsetof(CustomFillTile, cblk) == 4 &&
+                  offsetof(CustomFillTile, rstrip) == 8,
+              "CustomFillTile: layout of clipper_fill_tile");
+
 // what precedes the user's text: %d is the datum's dimension
 constexpr const char* kCustomPrelude = R"CLIPPER(#line 1 "clipper_prelude"
 constexpr int CLIPPER_D = %d;
@@ -30,7 +63,8 @@ struct clipper_fill_params {
 #line 1 "invariant"
 )CLIPPER";
 
-// what follows it: the signature check, then the fill kernels (extern "C": host_custom_invariant.hpp looks them up by name)
+// what follows it: the signature check, then the fill kernels, lone and batched (extern "C": host_custom_invariant.hpp
+// looks them up by name)
 constexpr const char* kCustomEpilogue = R"CLIPPER(
 #line 1 "clipper_fill"
 typedef double (*clipper_invariant_signature)(const double*, const double*, const double*, const double*, const double*);
@@ -56,17 +90,18 @@ __device__ __forceinline__ void clipper_store4(double* p, double a, double b, do
 }
 
 // S: the shard's dense store (ld = its pitch, a multiple of 4), columns [c0, c0 + ld) of M; P1, P2: the gathered point
-// tables [CLIPPER_D][pstride] (column i = D1[:, A(i, 0)], D2[:, A(i, 1)]); A0, A1: the association list's two columns
+// tables [CLIPPER_D][pstride] (column i = D1[:, A(i, 0)], D2[:, A(i, 1)]); A0, A1: the association list's two columns;
+// (cblk, rstrip): this workgroup's block of 1024 columns and strip of rows_per_blk rows
 template <typename T>
 __device__ __forceinline__ void clipper_custom_fill(T* __restrict__ S, long long ld, long long m, long long c0,
                                                     int rows_per_blk, const double* __restrict__ P1,
                                                     const double* __restrict__ P2, long long pstride,
                                                     const int* __restrict__ A0, const int* __restrict__ A1,
-                                                    const clipper_fill_params& prm) {
+                                                    const clipper_fill_params& prm, long long cblk, long long rstrip) {
   constexpr int D = CLIPPER_D;
-  const long long c = (static_cast<long long>(blockIdx.x) * 256 + threadIdx.x) * 4;
+  const long long c = (cblk * 256 + threadIdx.x) * 4;
   if (c >= ld) return;
-  const long long r0 = static_cast<long long>(blockIdx.y) * rows_per_blk;
+  const long long r0 = rstrip * rows_per_blk;
   const long long r1 = (r0 + rows_per_blk < m) ? r0 + rows_per_blk : m;
 
   long long gc[4];
@@ -124,14 +159,56 @@ extern "C" __global__ __launch_bounds__(256) void clipper_custom_fill_f32(
     float* __restrict__ S, long long ld, long long m, long long c0, int rows_per_blk, const double* __restrict__ P1,
     const double* __restrict__ P2, long long pstride, const int* __restrict__ A0, const int* __restrict__ A1,
     clipper_fill_params prm) {
-  clipper_custom_fill<float>(S, ld, m, c0, rows_per_blk, P1, P2, pstride, A0, A1, prm);
+  clipper_custom_fill<float>(S, ld, m, c0, rows_per_blk, P1, P2, pstride, A0, A1, prm, blockIdx.x, blockIdx.y);
 }
 
 extern "C" __global__ __launch_bounds__(256) void clipper_custom_fill_f64(
     double* __restrict__ S, long long ld, long long m, long long c0, int rows_per_blk, const double* __restrict__ P1,
     const double* __restrict__ P2, long long pstride, const int* __restrict__ A0, const int* __restrict__ A1,
     clipper_fill_params prm) {
-  clipper_custom_fill<double>(S, ld, m, c0, rows_per_blk, P1, P2, pstride, A0, A1, prm);
+  clipper_custom_fill<double>(S, ld, m, c0, rows_per_blk, P1, P2, pstride, A0, A1, prm, blockIdx.x, blockIdx.y);
+}
+
+// A batch's fill (host_batchsolve.hpp): one launch for every problem. Workgroup b reads its (problem, column block,
+// row strip) from tiles[b] and fills that tile of the problem's dense store exactly as the lone kernel's workgroup
+// (cblk, rstrip) does (c0 = 0): every element is the same call on the same arguments, so the stores are the same bits.
+// Twins of CustomFillProblem / CustomFillTile (k_custom_invariant_src.h).
+struct clipper_fill_problem {
+  void* S;
+  long long ld;
+  long long m;
+  const double* P1;
+  const double* P2;
+  long long pstride;
+  const int* A0;
+  const int* A1;
+};
+struct clipper_fill_tile {
+  int problem;
+  int cblk;
+  int rstrip;
+};
+
+template <typename T>
+__device__ __forceinline__ void clipper_custom_fill_tile(const clipper_fill_problem* __restrict__ probs,
+                                                         const clipper_fill_tile* __restrict__ tiles, int rows_per_blk,
+                                                         const clipper_fill_params& prm) {
+  const clipper_fill_tile t = tiles[blockIdx.x];
+  const clipper_fill_problem q = probs[t.problem];
+  clipper_custom_fill<T>(static_cast<T*>(q.S), q.ld, q.m, 0, rows_per_blk, q.P1, q.P2, q.pstride, q.A0, q.A1, prm,
+                         t.cblk, t.rstrip);
+}
+
+extern "C" __global__ __launch_bounds__(256) void clipper_custom_fill_batch_f32(
+    const clipper_fill_problem* __restrict__ probs, const clipper_fill_tile* __restrict__ tiles, int rows_per_blk,
+    clipper_fill_params prm) {
+  clipper_custom_fill_tile<float>(probs, tiles, rows_per_blk, prm);
+}
+
+extern "C" __global__ __launch_bounds__(256) void clipper_custom_fill_batch_f64(
+    const clipper_fill_problem* __restrict__ probs, const clipper_fill_tile* __restrict__ tiles, int rows_per_blk,
+    clipper_fill_params prm) {
+  clipper_custom_fill_tile<double>(probs, tiles, rows_per_blk, prm);
 }
 )CLIPPER";
 

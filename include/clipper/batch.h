@@ -5,14 +5,17 @@
  * call into the C ABI's clipper_hip_batch_* — the problems the resident solver takes run side by side on the chip,
  * the others are solved one after the other as CLIPPER::solve would. Per problem the Solution is that of a lone
  * CLIPPER with the same invariant, params, storage, inputs and u0 (bit for bit on the same route), except Solution::t:
- * the wall time of the whole batch. Only the built-in invariants (EuclideanDistance, PointNormalDistance) are
- * accepted; no explicit matrices, one device.
+ * the wall time of the whole batch. The constructor takes the built-in invariants (EuclideanDistance,
+ * PointNormalDistance); withDeviceInvariant makes a batch scored by a DeviceInvariant (invariants/device.h), one fill
+ * launch for all its problems. No explicit matrices, one device.
  */
 #pragma once
 
+#include <memory>
 #include <vector>
 
 #include "clipper/clipper.h"
+#include "clipper/invariants/device.h"
 
 struct clipper_hip_batch;
 
@@ -29,6 +32,10 @@ class CLIPPERBatch {
   /// throws std::invalid_argument for anything but an EuclideanDistance or a PointNormalDistance
   CLIPPERBatch(const invariants::PairwiseInvariantPtr& invariant, const Params& params);
   ~CLIPPERBatch();
+  /// a batch scored by a user-defined invariant on the device: every problem's D1, D2 have the same number of rows,
+  /// the dimension the invariant is compiled for (DeviceInvariant::handle) at solve time
+  static std::unique_ptr<CLIPPERBatch> withDeviceInvariant(const invariants::DeviceInvariantPtr& invariant,
+                                                           const Params& params);
   CLIPPERBatch(const CLIPPERBatch&) = delete;
   CLIPPERBatch& operator=(const CLIPPERBatch&) = delete;
 
@@ -42,11 +49,12 @@ class CLIPPERBatch {
  private:
   Params params_;
   invariants::PairwiseInvariantPtr invariant_;
-  int kind_ = 0;  ///< 1 = EuclideanDistance, 2 = PointNormalDistance
+  int kind_ = 0;  ///< 1 = EuclideanDistance, 2 = PointNormalDistance, 3 = DeviceInvariant
   int device_ = 0;
   CLIPPER::Storage storage_ = CLIPPER::Storage::F32_CSC;
   clipper_hip_batch* b_ = nullptr;
   void check(int rc, const char* what) const;
+  explicit CLIPPERBatch(const Params& params) : params_(params) {}
 };
 
 }  // namespace clipper

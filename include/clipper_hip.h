@@ -513,6 +513,8 @@ int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int6
  * context of the same storage with the same inputs, u0 and params whenever both took the same route
  * (clipper_hip_batch_route(i) == clipper_hip_last_solver of the lone context); only
  * clipper_solve_info_t::seconds differs: it is the wall time of the whole batched call.
+ * The invariant is a built-in one (EuclideanDistance, PointNormalDistance) or a user-defined one
+ * (clipper_hip_batch_solve_custom: one launch of its batched fill kernel scores every problem).
  * Not a batch: explicit matrices (set_matrix / set_sparse), column shards, multi-process ranks. */
 typedef struct clipper_hip_batch clipper_hip_batch_t;
 typedef struct {                /* one problem; host buffers, read during the call only */
@@ -533,6 +535,13 @@ int clipper_hip_batch_solve_euclidean(clipper_hip_batch_t* b, const clipper_batc
 /* PointNormalDistance: every D is 6 x n (xyz + unit normal). */
 int clipper_hip_batch_solve_pointnormal(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n,
                                         double sigp, double epsp, double sign, double epsn, const clipper_params_t* prm);
+/* A user-defined invariant (clipper_hip_invariant_create): every problem's D1, D2 are inv->d x n; params: nparams
+ * doubles (0..CLIPPER_HIP_INVARIANT_MAX_PARAMS). Contract, checks and results as clipper_hip_batch_solve_euclidean's,
+ * against a lone clipper_hip_affinity_custom + clipper_hip_solve. inv == NULL or nparams out of range is refused
+ * before the batch is looked at. */
+int clipper_hip_batch_solve_custom(clipper_hip_batch_t* b, const clipper_hip_invariant_t* inv,
+                                   const clipper_batch_problem_t* p, int32_t n, const double* params, int nparams,
+                                   const clipper_params_t* prm);
 /* Problem i of the last call: u (its m doubles; may be NULL) and the solve info; returns m. */
 int clipper_hip_batch_get_solution(const clipper_hip_batch_t* b, int32_t i, double* u_out, clipper_solve_info_t* info);
 /* Its selected nodes (ascending as the rounding leaves them, as clipper_hip_get_nodes); returns their count. */
