@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_batch_get_selected_associations", "clipper_hip_batch_route", "clipper_hip_batch_get_stats",
     "clipper_hip_batch_get_split", "clipper_hip_invariant_create", "clipper_hip_invariant_destroy",
     "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom", "clipper_hip_batch_solve_custom",
+    "clipper_hip_sdp_solve_batch", "clipper_hip_batch_sdp", "clipper_hip_batch_get_sdp",
 ]
 
 
@@ -153,6 +154,16 @@ class SdpInfo(C.Structure):
         ("pobj", C.c_double), ("dobj", C.c_double), ("r_prim", C.c_double), ("r_dual", C.c_double),
         ("rho", C.c_double), ("thr", C.c_double), ("t_total", C.c_double), ("t_setup", C.c_double),
         ("t_solve", C.c_double), ("t_extract", C.c_double),
+    ]
+
+
+class SdpProblem(C.Structure):
+    """clipper_sdp_problem_t (include/clipper_hip.h): one problem of clipper_hip_sdp_solve_batch (host buffers)."""
+
+    _fields_ = [
+        ("M", C.POINTER(C.c_double)), ("C", C.POINTER(C.c_double)), ("n", C.c_int64),
+        ("X_out", C.POINTER(C.c_double)), ("Y_out", C.POINTER(C.c_double)), ("lambdas_out", C.POINTER(C.c_double)),
+        ("evec1_out", C.POINTER(C.c_double)), ("nodes_out", C.POINTER(C.c_int32)),
     ]
 
 
@@ -281,6 +292,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_sdp.argtypes = [vp, C.POINTER(SdpParams), dp, dp, dp, dp, C.POINTER(SdpInfo)]
     L.clipper_hip_sdp_solve.argtypes = [C.c_int, dp, dp, C.c_int64, C.POINTER(SdpParams), dp, dp, dp, dp, ip,
                                         C.POINTER(SdpInfo)]
+    L.clipper_hip_sdp_solve_batch.argtypes = [C.c_int, C.POINTER(SdpProblem), C.c_int32, C.POINTER(SdpParams),
+                                              C.POINTER(SdpInfo)]
+    L.clipper_hip_batch_sdp.argtypes = [vp, C.POINTER(SdpParams), C.POINTER(SdpInfo)]
+    L.clipper_hip_batch_get_sdp.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
     L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     L.clipper_hip_batch_destroy.argtypes = [vp]
     L.clipper_hip_batch_destroy.restype = None
@@ -811,6 +826,39 @@ def sdp_solve(M, C_, params: SdpParams | None = None, device: int = 0) -> SdpRes
     return _sdp_result(n, X, Y, lam, ev, nodes[:k].copy(), info)
 
 
+def sdp_solve_batch(problems, params: SdpParams | None = None, device: int = 0, want_xy: bool = True) -> list:
+    """sdp::solve on every (M, C) of `problems` in one call, one workgroup per problem (clipper_hip_sdp_solve_batch):
+    per problem the SdpResult of sdp_solve on it alone, bit for bit (the times excepted: they are the call's).
+    want_xy = False leaves X and Y on the device (empty arrays in the results)."""
+    L = load_library()
+    params = params if params is not None else SdpParams()
+    count = len(problems)
+    arr = (SdpProblem * max(count, 1))()
+    keep = []
+    for i, pr in enumerate(problems):
+        if len(pr) != 2:
+            raise ValueError(f"problem {i}: expected (M, C)")
+        Mc = np.asfortranarray(np.asarray(pr[0], dtype=np.float64))
+        Cc = np.asfortranarray(np.asarray(pr[1], dtype=np.float64))
+        n = Mc.shape[0] if Mc.ndim == 2 else -1
+        if Mc.ndim != 2 or Mc.shape != (n, n) or Cc.shape != (n, n):
+            raise ValueError(f"problem {i}: M and C must be square and of the same size")
+        X, Y = (np.zeros((n, n)), np.zeros((n, n))) if want_xy else (np.zeros((0, 0)), np.zeros((0, 0)))
+        lam, ev, nodes = np.zeros(n), np.zeros(n), np.zeros(max(n, 1), dtype=np.int32)
+        keep.append((Mc, Cc, X, Y, lam, ev, nodes))
+        arr[i] = SdpProblem(_dp(Mc), _dp(Cc), n, _dp(X) if want_xy else None, _dp(Y) if want_xy else None, _dp(lam),
+                            _dp(ev), _ip(nodes))
+    infos = (SdpInfo * max(count, 1))()
+    rc = L.clipper_hip_sdp_solve_batch(device, arr, count, C.byref(params), infos)
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    out = []
+    for i, (Mc, Cc, X, Y, lam, ev, nodes) in enumerate(keep):
+        info = SdpInfo.from_buffer_copy(infos[i])
+        out.append(_sdp_result(Mc.shape[0], X, Y, lam, ev, nodes[:info.num_nodes].copy(), info))
+    return out
+
+
 def distance_based_correspondences(P0, P1, knn: int, radius: float, enforce_1to1: bool,
                                    device: int = 0) -> np.ndarray:
     """utils::distance_based_correspondences of the reference benchmark (bm_utils.cpp:147-232) on
@@ -926,6 +974,26 @@ class HipBatch:
         self._check(self.L.clipper_hip_batch_solve_pointnormal(self.b, arr, len(problems), sigp, epsp, sign, epsn,
                                                                C.byref(params)))
         return self._collect(len(problems), keep)
+
+    def sdp(self, params: SdpParams | None = None, want_xy: bool = True) -> list:
+        """The semidefinite relaxation of every problem of the last solve call, in one batched call
+        (clipper_hip_batch_sdp): per problem the SdpResult HipClipper.sdp gives on a lone context, bit for bit. Each
+        problem's selection becomes its node list (selected_associations(i) follows it)."""
+        params = params if params is not None else SdpParams()
+        infos = (SdpInfo * max(self.n, 1))()
+        self._check(self.L.clipper_hip_batch_sdp(self.b, C.byref(params), infos))
+        out = []
+        for i in range(self.n):
+            info = SdpInfo.from_buffer_copy(infos[i])
+            n = self._check(self.L.clipper_hip_batch_get_sdp(self.b, i, None, None, None, None))
+            X, Y = (np.zeros((n, n)), np.zeros((n, n))) if want_xy else (np.zeros((0, 0)), np.zeros((0, 0)))
+            lam, ev = np.zeros(n), np.zeros(n)
+            self._check(self.L.clipper_hip_batch_get_sdp(self.b, i, _dp(X) if want_xy else None,
+                                                         _dp(Y) if want_xy else None, _dp(lam), _dp(ev)))
+            nodes = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
+            k = self._check(self.L.clipper_hip_batch_get_nodes(self.b, i, _ip(nodes), nodes.size))
+            out.append(_sdp_result(n, X, Y, lam, ev, nodes[:k].copy(), info))
+        return out
 
     def route(self, i: int) -> int:
         """1 = solved in a batched resident launch, 0 = solved alone on its child context"""

@@ -51,6 +51,7 @@ using namespace clipper_hip;
 #include "host_registration.hpp"
 #include "host_maxclique.hpp"
 #include "host_sdp.hpp"
+#include "host_sdpbatch.hpp"
 #include "host_solve.hpp"
 #include "host_custom_invariant.hpp"
 #include "host_batchsolve.hpp"
@@ -333,6 +334,11 @@ int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t 
   return sdp_solve_impl(device, M, C, n, params, X_out, Y_out, lambdas_out, evec1_out, nodes_out, info);
 } CLIPPER_HIP_GUARD_INT
 
+int clipper_hip_sdp_solve_batch(int device, const clipper_sdp_problem_t* problems, int32_t count,
+                                const clipper_sdp_params_t* params, clipper_sdp_info_t* infos) try {
+  return sdp_solve_batch_impl(device, problems, count, params, infos);
+} CLIPPER_HIP_GUARD_INT
+
 // ---- putative associations (before the path): brute-force nearest neighbours -------------------
 
 int clipper_hip_knn(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d,
@@ -562,6 +568,20 @@ int clipper_hip_batch_get_selected_associations(const clipper_hip_batch_t* b, in
   if (capacity < k) return fail(CLIPPER_HIP_E_INVALID, "capacity %d < %d nodes", capacity, k);
   if (k) std::memcpy(A_out, sel.data(), sel.size() * sizeof(int32_t));
   return k;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* params, clipper_sdp_info_t* infos) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return batch_sdp(b, params, infos);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_get_sdp(const clipper_hip_batch_t* b, int32_t i, double* X_out, double* Y_out,
+                              double* lambdas_out, double* evec1_out) try {
+  if (!b || !b->sdp) return fail(CLIPPER_HIP_E_STATE, "sdp: no relaxation of this batch is held");
+  if (i < 0 || static_cast<size_t>(i) >= b->sdp->count())
+    return fail(CLIPPER_HIP_E_INVALID, "no problem %d in the last relaxation of the batch", i);
+  if (int rc = sdp_batch_outputs(*b->sdp, static_cast<size_t>(i), X_out, Y_out, lambdas_out, evec1_out)) return rc;
+  return b->sdp->n[static_cast<size_t>(i)];
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_batch_route(const clipper_hip_batch_t* b, int32_t i) try {

@@ -1,6 +1,7 @@
 // batch.cpp — clipper::CLIPPERBatch (include/clipper/batch.h) over the C ABI's clipper_hip_batch_*.
 #include "clipper/batch.h"
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <typeinfo>
@@ -9,6 +10,13 @@
 #include "clipper_hip.h"
 
 namespace clipper {
+
+namespace sdp {
+namespace detail {  // clipper.cpp
+clipper_sdp_params_t abi_params(const Params& p);
+void fill_solution(Solution& s, const clipper_sdp_info_t& info);
+}  // namespace detail
+}  // namespace sdp
 
 CLIPPERBatch::CLIPPERBatch(const invariants::PairwiseInvariantPtr& invariant, const Params& params)
     : params_(params), invariant_(invariant) {
@@ -99,6 +107,8 @@ std::vector<Solution> CLIPPERBatch::solve(const std::vector<BatchProblem>& probl
     check(clipper_hip_batch_solve_custom(b_, inv->handle(d), p.data(), nn, f.data(), static_cast<int>(f.size()), &prm),
           "batch solve");
   }
+  n_ = n;
+  sdp_.clear();
   std::vector<Solution> out(n);
   for (size_t i = 0; i < n; ++i) {
     clipper_solve_info_t info;
@@ -114,6 +124,38 @@ std::vector<Solution> CLIPPERBatch::solve(const std::vector<BatchProblem>& probl
     s.ifinal = info.ifinal;
     s.u0 = u0[i];
     s.score = info.score;
+  }
+  return out;
+}
+
+// clipper_hip_batch_sdp on the problems of the last solve; per problem what CLIPPER::solveAsMSRCSDR leaves
+std::vector<Solution> CLIPPERBatch::solveAsMSRCSDR(const sdp::Params& params) {
+  if (!b_) throw std::logic_error("clipper: no batch has been solved");
+  const clipper_sdp_params_t p = sdp::detail::abi_params(params);
+  const int32_t count = static_cast<int32_t>(n_);
+  std::vector<clipper_sdp_info_t> info(static_cast<size_t>(std::max<int32_t>(count, 1)));
+  sdp_.clear();
+  check(clipper_hip_batch_sdp(b_, &p, info.data()), "batch solveAsMSRCSDR");
+  std::vector<Solution> out(static_cast<size_t>(count));
+  sdp_.resize(static_cast<size_t>(count));
+  for (int32_t i = 0; i < count; ++i) {
+    const clipper_sdp_info_t& I = info[static_cast<size_t>(i)];
+    sdp::Solution& s = sdp_[static_cast<size_t>(i)];
+    const int m = clipper_hip_batch_get_sdp(b_, i, nullptr, nullptr, nullptr, nullptr);
+    check(m, "batch solveAsMSRCSDR (sizes)");
+    s.X = MatrixXd::Zero(m, m);
+    s.lambdas = VectorXd::Zero(m);
+    s.evec1 = VectorXd::Zero(m);
+    check(clipper_hip_batch_get_sdp(b_, i, s.X.data(), nullptr, s.lambdas.data(), s.evec1.data()), "batch solveAsMSRCSDR (X)");
+    s.nodes.resize(static_cast<size_t>(I.num_nodes));
+    if (I.num_nodes > 0) check(clipper_hip_batch_get_nodes(b_, i, s.nodes.data(), I.num_nodes), "batch solveAsMSRCSDR (nodes)");
+    sdp::detail::fill_solution(s, I);
+    Solution& o = out[static_cast<size_t>(i)];  // clipper.cpp:108-112
+    o.t = I.t_total;
+    o.ifinal = 0;
+    o.nodes = s.nodes;
+    o.u = VectorXd::Zero(m);
+    o.score = -1;
   }
   return out;
 }

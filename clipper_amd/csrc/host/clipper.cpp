@@ -395,8 +395,8 @@ void CLIPPER::solveAsMaximumClique(const maxclique::Params& params) {
 }
 
 namespace sdp {
-namespace detail {
-static clipper_sdp_params_t abi_params(const Params& p) {
+namespace detail {  // (batch.cpp declares and uses both)
+clipper_sdp_params_t abi_params(const Params& p) {
   clipper_sdp_params_t a{};
   a.verbose = p.verbose ? 1 : 0;
   a.max_iters = p.max_iters;
@@ -407,6 +407,22 @@ static clipper_sdp_params_t abi_params(const Params& p) {
   a.eps_infeas = p.eps_infeas;
   a.time_limit_secs = p.time_limit_secs;
   return a;
+}
+// thr, the counters and the times of a Solution from the device solver's report
+void fill_solution(Solution& s, const clipper_sdp_info_t& info) {
+  s.thr = info.thr;
+  s.iters = info.iters;
+  s.pobj = static_cast<float>(info.pobj);
+  s.dobj = static_cast<float>(info.dobj);
+  s.t = info.t_total;
+  s.t_parse = info.t_setup;
+  s.t_scs = info.t_solve;  // the device solver's share of the SCS fields: all of it is the projection (the cone)
+  s.t_scs_setup = 0;
+  s.t_scs_solve = info.t_solve;
+  s.t_scs_linsys = 0;
+  s.t_scs_cone = info.t_solve;
+  s.t_scs_accel = 0;
+  s.t_extract = info.t_extract;
 }
 }  // namespace detail
 
@@ -427,20 +443,38 @@ Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params) {
                                       s.evec1.data(), nodes.data(), &info);
   if (k < 0) throw std::runtime_error(std::string("sdp::solve: ") + clipper_hip_last_error());
   s.nodes.assign(nodes.begin(), nodes.begin() + k);
-  s.thr = info.thr;
-  s.iters = info.iters;
-  s.pobj = static_cast<float>(info.pobj);
-  s.dobj = static_cast<float>(info.dobj);
-  s.t = info.t_total;
-  s.t_parse = info.t_setup;
-  s.t_scs = info.t_solve;  // the device solver's share of the SCS fields: all of it is the projection (the cone)
-  s.t_scs_setup = 0;
-  s.t_scs_solve = info.t_solve;
-  s.t_scs_linsys = 0;
-  s.t_scs_cone = info.t_solve;
-  s.t_scs_accel = 0;
-  s.t_extract = info.t_extract;
+  detail::fill_solution(s, info);
   return s;
+}
+
+// the same for many problems in one call (clipper_hip_sdp_solve_batch on device 0)
+std::vector<Solution> solve(const std::vector<MatrixXd>& M, const std::vector<MatrixXd>& C, const Params& params) {
+  if (M.size() != C.size()) throw std::invalid_argument("sdp::solve: as many C as M");
+  const size_t count = M.size();
+  const clipper_sdp_params_t p = detail::abi_params(params);
+  std::vector<Solution> out(count);
+  std::vector<std::vector<int32_t>> nodes(count);
+  std::vector<clipper_sdp_problem_t> prob(count);
+  std::vector<clipper_sdp_info_t> info(count);
+  for (size_t i = 0; i < count; ++i) {
+    const std::ptrdiff_t n = M[i].rows();
+    if (M[i].cols() != n || C[i].rows() != n || C[i].cols() != n)
+      throw std::invalid_argument("sdp::solve: problem " + std::to_string(i) + ": M and C must be n x n");
+    Solution& s = out[i];
+    s.X = MatrixXd::Zero(n, n);
+    s.lambdas = VectorXd::Zero(n);
+    s.evec1 = VectorXd::Zero(n);
+    nodes[i].assign(static_cast<size_t>(std::max<std::ptrdiff_t>(n, 1)), 0);
+    prob[i] = clipper_sdp_problem_t{M[i].data(), C[i].data(), n, s.X.data(), nullptr, s.lambdas.data(), s.evec1.data(),
+                                    nodes[i].data()};
+  }
+  if (clipper_hip_sdp_solve_batch(0, prob.data(), static_cast<int32_t>(count), &p, info.data()) < 0)
+    throw std::runtime_error(std::string("sdp::solve: ") + clipper_hip_last_error());
+  for (size_t i = 0; i < count; ++i) {
+    out[i].nodes.assign(nodes[i].begin(), nodes[i].begin() + info[i].num_nodes);
+    detail::fill_solution(out[i], info[i]);
+  }
+  return out;
 }
 }  // namespace sdp
 

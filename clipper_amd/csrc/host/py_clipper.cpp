@@ -263,7 +263,14 @@ PYBIND11_MODULE(clipperpy, m) {
       .def_readwrite("t_scs_accel", &clipper::sdp::Solution::t_scs_accel)
       .def_readwrite("t_extract", &clipper::sdp::Solution::t_extract);
   py::module m_sdp = m.def_submodule("sdp");
-  m_sdp.def("solve", &clipper::sdp::solve, "M"_a, "C"_a, "params"_a = clipper::sdp::Params{});
+  m_sdp.def("solve", py::overload_cast<const clipper::MatrixXd&, const clipper::MatrixXd&, const clipper::sdp::Params&>(
+                         &clipper::sdp::solve),
+            "M"_a, "C"_a, "params"_a = clipper::sdp::Params{});
+  // many problems in one call: lists of M and of C ("Batches")
+  m_sdp.def("solve_batch",
+            py::overload_cast<const std::vector<clipper::MatrixXd>&, const std::vector<clipper::MatrixXd>&,
+                              const clipper::sdp::Params&>(&clipper::sdp::solve),
+            "Ms"_a, "Cs"_a, "params"_a = clipper::sdp::Params{});
 
   py::enum_<clipper::Params::Rounding>(m, "Rounding")
       .value("NONZERO", clipper::Params::Rounding::NONZERO)
@@ -383,5 +390,8 @@ PYBIND11_MODULE(clipperpy, m) {
         return b.solve(ps);
       }, "problems"_a)
       .def("get_selected_associations", &clipper::CLIPPERBatch::getSelectedAssociations, "i"_a)
-      .def("solved_batched", &clipper::CLIPPERBatch::solvedBatched, "i"_a);
+      .def("solved_batched", &clipper::CLIPPERBatch::solvedBatched, "i"_a)
+      // the semidefinite relaxation of every problem of the last solve, in one batched call
+      .def("solve_as_msrc_sdr", &clipper::CLIPPERBatch::solveAsMSRCSDR, "params"_a = clipper::sdp::Params{})
+      .def("sdp_solutions", &clipper::CLIPPERBatch::sdpSolutions);
 }

@@ -18,6 +18,8 @@
 //   7. rounds each problem on the host with the lone solve's code.
 // Per problem the results are bit for bit those of a lone context on the same route; only `seconds` differs (the
 // wall time of the whole call).
+// batch_sdp (at the end) runs the semidefinite relaxation of every problem of the last call in one batched call
+// (host_sdpbatch.hpp) on the children's stores.
 #pragma once
 
 #include "host_batchpack.hpp"
@@ -47,6 +49,8 @@ struct clipper_hip_batch {
   size_t dfill_cap = 0;
   hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around a custom fill's launch
   double t_fill_begin = 0.0, t_fill_launch = 0.0, t_fill_build = 0.0;  // kind 3: the parts of t_fill (ms)
+  bool solved = false;                  // a solve call has succeeded: `res` and the children describe its problems
+  std::unique_ptr<SdpBatchState> sdp;   // the last clipper_hip_batch_sdp (host_sdpbatch.hpp), until the next call
 };
 
 namespace {
@@ -223,6 +227,8 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
                 const clipper_params_t* P, const CustomFill* cf = nullptr) {
   const auto t0 = std::chrono::high_resolution_clock::now();
   b->res.clear();
+  b->solved = false;
+  b->sdp.reset();
   b->launches = b->n_batched = b->n_alone = 0;
   b->t_fill = b->t_launch = b->t_alone = b->t_round = 0.0;
   b->t_fill_begin = b->t_fill_launch = b->t_fill_build = 0.0;
@@ -247,7 +253,10 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
     bytes += static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
   }
   b->res.resize(static_cast<size_t>(n));
-  if (n == 0) return 0;
+  if (n == 0) {
+    b->solved = true;
+    return 0;
+  }
   HIPCHK(hipSetDevice(b->device));
   while (b->kids.size() < static_cast<size_t>(n)) {
     Ctx* c = make_ctx(&b->device, 1, b->storage, 1, 0, false);
@@ -445,6 +454,73 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   for (auto& R : b->res) R.info.seconds = secs;
   b->n_batched = static_cast<int>(std::count_if(b->res.begin(), b->res.end(), [](const Batch::Result& R) { return R.route == 1; }));
   b->n_alone = n - b->n_batched;
+  b->solved = true;
+  return 0;
+}
+
+// clipper_hip_batch_sdp: the relaxation of every problem of the last solve call, on each child's M and C with their
+// identity diagonals (what sdp_ctx_impl gathers for a lone context), in the launches of one sdp_batch_run. A child's
+// store is read where it lives: the dense store, or a dense copy of its slices made for this call only. Each
+// problem's selection becomes its node list (the child's, and the batch's results); nothing the solver keeps is
+// touched.
+int batch_sdp(Batch* b, const clipper_sdp_params_t* P, clipper_sdp_info_t* infos) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!b->solved) return fail(CLIPPER_HIP_E_STATE, "sdp: no batch has been solved");
+  if (int rc = sdp_check_params(P, 1)) return rc;
+  const size_t count = b->res.size();
+  for (size_t i = 0; i < count; ++i) {
+    const Ctx* c = b->kids[i];
+    if (!c->has_matrix) return fail(CLIPPER_HIP_E_STATE, "problem %zu: no matrix has been built", i);
+    if (c->m < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: empty problem", i);
+    if (c->m > SDP_MAX_N)
+      return fail(CLIPPER_HIP_E_SCOPE, "problem %zu: sdp: n = %lld is above the device solver's limit of %d", i,
+                  (long long)c->m, SDP_MAX_N);
+  }
+  b->sdp.reset();
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  std::unique_ptr<SdpBatchState> S(new SdpBatchState());
+  S->device = b->device;
+  S->n.resize(count);
+  for (size_t i = 0; i < count; ++i) S->n[i] = static_cast<int32_t>(b->kids[i]->m);
+  auto drop_copies = [&] {
+    for (size_t i = 0; i < count; ++i)
+      if (b->kids[i]->csc_valid) drop_dense(b->kids[i]);
+  };
+  auto source = [&](size_t i, SdpGatherSrc& g) -> int {
+    Ctx* c = b->kids[i];
+    if (int rc = ensure_dense(c, true)) return rc;  // (a copy of the slices for this call only)
+    const Shard& s = c->sh[0];
+    g.srcM = s.S;
+    g.srcC = c->explicitC ? s.Cs : s.S;
+    if (!g.srcM || !g.srcC) return fail(CLIPPER_HIP_E_STATE, "problem %zu: sdp: the store of M or C is not on the device", i);
+    g.rs = c->W;
+    g.cs = 1;
+    g.ident = 1.0;
+    g.f64 = c->storage == CLIPPER_HIP_STORE_F64;
+    g.c_pattern_of_m = !c->explicitC;
+    return 0;
+  };
+  bool dropped = false;
+  const int rc = sdp_batch_run(*S, b->stream, P, false, source, [](uint8_t*) {}, [&] { drop_copies(); dropped = true; }, t0);
+  if (!dropped) drop_copies();
+  if (rc) return rc;
+  for (size_t i = 0; i < count; ++i) {
+    Ctx* c = b->kids[i];
+    Batch::Result& R = b->res[i];
+    const size_t k = static_cast<size_t>(S->round(i).count);
+    R.nodes.assign(S->nodes(i), S->nodes(i) + k);
+    c->nodes = R.nodes;
+    R.info.num_nodes = static_cast<int32_t>(k);  // (what the getters size their buffers by)
+    R.sel.assign(2 * k, 0);  // utils::selectInlierAssociations
+    for (size_t r = 0; r < k; ++r) {
+      const size_t a = static_cast<size_t>(R.nodes[r]);
+      R.sel[r] = c->A[a];
+      R.sel[k + r] = c->A[static_cast<size_t>(c->m) + a];
+    }
+    if (infos) infos[i] = S->info[i];
+  }
+  b->sdp = std::move(S);
   return 0;
 }
 

@@ -1,6 +1,8 @@
 // k_sdp.hip.h — the semidefinite relaxation behind CLIPPER::solveAsMSRCSDR and sdp::solve:
 // ADMM on X = Z with X in the spectraplex and Z in the polyhedral set of C, one workgroup per problem, fp64
-// throughout. Host side: host_sdp.hpp.
+// throughout; k_sdp runs one problem, k_sdp_batch many side by side (a work list, one workgroup per entry) with the
+// same body, and k_sdp_gather_batch / k_sdp_round_batch build the inputs and round the results of a batch. Host side:
+// host_sdp.hpp, host_sdpbatch.hpp.
 // Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
 //
 // Layout of one problem (n <= SDP_MAX_N, np = n rounded up to even): M, the mask of C (1.0 / 0.0), X, Z and U are
@@ -238,14 +240,26 @@ __device__ double sdp_dual_bound(const SdpArgs& g, double rho, double* A, bool w
   return d;
 }
 
-__global__ void __launch_bounds__(SDP_THREADS) k_sdp(SdpArgs g, int32_t mode, int32_t budget, int32_t max_iters) {
-  extern __shared__ double A[];  // np x np
-  __shared__ double rc[SDP_MAX_N / 2], rs[SDP_MAX_N / 2], rt[SDP_MAX_N / 2];
-  __shared__ double lam[SDP_MAX_N], red[2 * SDP_THREADS / 64];
-  __shared__ int32_t pos_list[SDP_MAX_N];
-  __shared__ int32_t kmax, npos;
-  __shared__ double tau;
-  __shared__ SdpCtl c;
+// LDS of one workgroup besides the working matrix (every kernel that runs sdp_body declares one)
+struct SdpShared {
+  double rc[SDP_MAX_N / 2], rs[SDP_MAX_N / 2], rt[SDP_MAX_N / 2];
+  double lam[SDP_MAX_N], red[2 * SDP_THREADS / 64];
+  int32_t pos_list[SDP_MAX_N];
+  int32_t kmax, npos;
+  double tau;
+  SdpCtl c;
+};
+
+// One launch's work on one problem, by one workgroup of SDP_THREADS: INIT, at most `budget` iterations, or the
+// certificate. A: the working matrix (np x np doubles of LDS). Stated once for k_sdp and k_sdp_batch: the order of
+// every sum depends on the geometry alone, so both give the same bits.
+__device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t budget, int32_t max_iters, double* A,
+                                         SdpShared& sh) {
+  double *rc = sh.rc, *rs = sh.rs, *rt = sh.rt, *lam = sh.lam, *red = sh.red;
+  int32_t* pos_list = sh.pos_list;
+  int32_t &kmax = sh.kmax, &npos = sh.npos;
+  double& tau = sh.tau;
+  SdpCtl& c = sh.c;
   const int tid = threadIdx.x, n = g.n, np = g.np, nn = n * n;
   if (tid == 0) c = *g.ctl;
   __syncthreads();
@@ -395,6 +409,147 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdp(SdpArgs g, int32_t mode, in
   }
   __syncthreads();
   if (tid == 0) *g.ctl = c;
+}
+
+__global__ void __launch_bounds__(SDP_THREADS) k_sdp(SdpArgs g, int32_t mode, int32_t budget, int32_t max_iters) {
+  extern __shared__ double sdp_A[];  // np x np
+  __shared__ SdpShared sh;
+  sdp_body(g, mode, budget, max_iters, sdp_A, sh);
+}
+
+// ---- a batch: one workgroup per problem ("Batches") ---------------------------------------------------
+//
+// Workgroup b works on problem list[b] of the table, with the lone kernel's body and geometry: per problem the bits
+// are k_sdp's, whatever else the launch holds and however the host cuts the launches. The dynamic LDS is that of the
+// largest problem of the launch. No workgroup reads or writes another problem's buffers; there is no barrier, no
+// atomic and no flag between workgroups.
+__global__ void __launch_bounds__(SDP_THREADS) k_sdp_batch(const SdpArgs* __restrict__ table,
+                                                           const int32_t* __restrict__ list, int32_t mode,
+                                                           int32_t budget, int32_t max_iters) {
+  extern __shared__ double sdp_A[];  // np x np of the launch's largest problem
+  __shared__ SdpShared sh;
+  const SdpArgs g = table[list[blockIdx.x]];
+  if (mode == SDP_MODE_ITERATE) {  // (uniform over the workgroup: nothing to do, nothing written)
+    const SdpCtl* c = g.ctl;
+    if (c->converged || c->iters >= max_iters) return;
+  }
+  sdp_body(g, mode, budget, max_iters, sdp_A, sh);
+}
+
+// Where one problem's M and C come from (k_sdp_gather_batch): element (r, c) of the lower triangle sits at
+// src[r * rs + c * cs], floats or doubles; `ident` is added to the diagonal of both (a context's identity).
+struct SdpGatherSrc {
+  const void* srcM;
+  const void* srcC;  // unused with c_pattern_of_m
+  int64_t rs, cs;
+  double ident;
+  double* M;
+  double* mask;
+  int32_t n;
+  int32_t f64;             // 1: doubles, 0: floats
+  int32_t c_pattern_of_m;  // C = pattern(M + ident I)
+  int32_t pad;
+};
+
+// k_sdp_gather for every problem of a batch in one launch: grid (ceil(max n^2 / 256), problems)
+__global__ void k_sdp_gather_batch(const SdpGatherSrc* __restrict__ table) {
+  const SdpGatherSrc g = table[blockIdx.y];
+  const int32_t n = g.n;
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (idx >= static_cast<int64_t>(n) * n) return;
+  const int32_t a = static_cast<int32_t>(idx / n), b = static_cast<int32_t>(idx % n);
+  const int32_t r = a > b ? a : b, c = a > b ? b : a;
+  const int64_t e = r * g.rs + c * g.cs;
+  const double d = (a == b) ? g.ident : 0.0;
+  const double mv = (g.f64 ? static_cast<const double*>(g.srcM)[e]
+                           : static_cast<double>(static_cast<const float*>(g.srcM)[e])) + d;
+  double cv = mv;
+  if (!g.c_pattern_of_m)
+    cv = (g.f64 ? static_cast<const double*>(g.srcC)[e] : static_cast<double>(static_cast<const float*>(g.srcC)[e])) + d;
+  g.M[idx] = mv;
+  g.mask[idx] = (cv != 0.0) ? 1.0 : 0.0;
+}
+
+// What the rounding leaves per problem besides evec1 and the node list
+struct SdpRound {
+  double thr;
+  int32_t count;  // nodes selected
+  int32_t top;    // the index of the largest mu
+};
+
+struct SdpRoundDst {
+  double* ev;      // n doubles: evec1
+  int32_t* nodes;  // n int32: the selection, ascending
+};
+
+// The rounding (sdp.cpp:244-261), one wave per problem: `top` = the first index of the largest mu, evec1 = that column
+// of Q with its first largest-magnitude entry made positive, thr = half that magnitude, the nodes |evec1_i| > thr
+// ascending. "First index of the largest" = what a sequential scan with a strict > finds: each lane scans its indices
+// in ascending order with >, the lanes are merged by (larger value, then lower index).
+__device__ inline void sdp_wave_argmax(double& v, int& i) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) k_sdp_round_batch(const SdpArgs* __restrict__ table,
+                                                        const SdpRoundDst* __restrict__ dst,
+                                                        SdpRound* __restrict__ round_out) {
+  const SdpArgs g = table[blockIdx.x];
+  const int lane = threadIdx.x, n = g.n, np = g.np;
+  double* ev = dst[blockIdx.x].ev;
+  int32_t* nodes = dst[blockIdx.x].nodes;
+  double bv = 0.0;
+  int bi = 0x7fffffff;
+  for (int i = lane; i < n; i += 64) {
+    const double m = g.mu[i];
+    if (bi == 0x7fffffff || m > bv) {
+      bv = m;
+      bi = i;
+    }
+  }
+  if (bi == 0x7fffffff) bv = -__builtin_huge_val();  // (a lane without an index never wins)
+  sdp_wave_argmax(bv, bi);
+  const int top = bi;
+  double e[(SDP_MAX_N + 63) / 64];
+  double av = -1.0;  // (magnitudes are >= 0)
+  int ai = 0x7fffffff;
+#pragma unroll
+  for (int k = 0; k < (SDP_MAX_N + 63) / 64; ++k) {
+    const int i = lane + 64 * k;
+    e[k] = i < n ? g.Q[i * np + top] : 0.0;
+    if (i < n && fabs(e[k]) > av) {
+      av = fabs(e[k]);
+      ai = i;
+    }
+  }
+  sdp_wave_argmax(av, ai);
+  const int big = ai;
+  double ebig = 0.0;
+#pragma unroll
+  for (int k = 0; k < (SDP_MAX_N + 63) / 64; ++k) {
+    const double t = __shfl(e[k], big & 63, 64);
+    if (k == (big >> 6)) ebig = t;
+  }
+  const bool flip = ebig < 0;
+  const double thr = fabs(ebig) / 2.0;
+  int base = 0;
+#pragma unroll
+  for (int k = 0; k < (SDP_MAX_N + 63) / 64; ++k) {
+    const int i = lane + 64 * k;
+    const double v = flip ? -e[k] : e[k];
+    const bool sel = i < n && fabs(v) > thr;
+    if (i < n) ev[i] = v;
+    const unsigned long long bal = __ballot(sel);
+    if (sel) nodes[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+    base += __popcll(bal);
+  }
+  if (lane == 0) round_out[blockIdx.x] = SdpRound{thr, base, top};
 }
 
 }  // namespace clipper_hip

@@ -8,6 +8,11 @@
  * the wall time of the whole batch. The constructor takes the built-in invariants (EuclideanDistance,
  * PointNormalDistance); withDeviceInvariant makes a batch scored by a DeviceInvariant (invariants/device.h), one fill
  * launch for all its problems. No explicit matrices, one device.
+ *
+ * solveAsMSRCSDR runs the semidefinite relaxation of every problem of the last solve in one batched call
+ * (clipper_hip_batch_sdp, DESIGN.md 11 "Batches"; every problem needs m <= 128). Its dual bound certifies the
+ * dense-cluster answers: -sdpSolutions()[i].dobj is an upper bound on the optimum of the problem solve() attacks
+ * locally.
  */
 #pragma once
 
@@ -16,6 +21,7 @@
 
 #include "clipper/clipper.h"
 #include "clipper/invariants/device.h"
+#include "clipper/sdp.h"
 
 struct clipper_hip_batch;
 
@@ -46,6 +52,14 @@ class CLIPPERBatch {
   Association getSelectedAssociations(int i) const;  ///< of problem i of the last solve (clipper.cpp:124-127)
   bool solvedBatched(int i) const;                   ///< problem i ran in a batched resident launch
 
+  /// CLIPPER::solveAsMSRCSDR (with setDeviceSdp) for every problem of the last solve(), in one batched call. Solution i
+  /// is what clipper.cpp:108-112 makes of the relaxation (nodes, u = 0, score = -1, ifinal = 0; t: the whole call's);
+  /// getSelectedAssociations(i) follows it. The solver state is untouched: a later solve() gives the same results.
+  /// Throws std::logic_error before any solve, std::runtime_error when a problem has m > 128 (the message names it).
+  std::vector<Solution> solveAsMSRCSDR(const sdp::Params& params = sdp::Params{});
+  /// the relaxations of the last solveAsMSRCSDR (X, lambdas, evec1, thr, nodes, iters, pobj, dobj, times)
+  const std::vector<sdp::Solution>& sdpSolutions() const { return sdp_; }
+
  private:
   Params params_;
   invariants::PairwiseInvariantPtr invariant_;
@@ -53,6 +67,8 @@ class CLIPPERBatch {
   int device_ = 0;
   CLIPPER::Storage storage_ = CLIPPER::Storage::F32_CSC;
   clipper_hip_batch* b_ = nullptr;
+  size_t n_ = 0;  ///< problems of the last solve
+  std::vector<sdp::Solution> sdp_;
   void check(int rc, const char* what) const;
   explicit CLIPPERBatch(const Params& params) : params_(params) {}
 };

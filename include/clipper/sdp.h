@@ -46,5 +46,11 @@ struct Solution {
 /// sdp.cpp:109-303 on HIP device 0; throws std::runtime_error when the device solver refuses (n > 128, no device).
 Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params = Params{});
 
+/// Many problems in one call (clipper_hip_sdp_solve_batch, DESIGN.md section 11 "Batches"): one workgroup per problem,
+/// all side by side on the device. Solution i is solve(M[i], C[i], params), bit for bit; only the times differ: they
+/// are the whole call's. time_limit_secs bounds the whole call. Throws std::invalid_argument when the lists' sizes
+/// differ, std::runtime_error when the device solver refuses (the message names the problem).
+std::vector<Solution> solve(const std::vector<MatrixXd>& M, const std::vector<MatrixXd>& C, const Params& params = Params{});
+
 }  // namespace sdp
 }  // namespace clipper

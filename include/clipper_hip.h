@@ -373,6 +373,31 @@ int clipper_hip_sdp(clipper_hip_t* h, const clipper_sdp_params_t* params, double
 int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t n, const clipper_sdp_params_t* params,
                           double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
                           clipper_sdp_info_t* info);
+/* Many relaxations in one call, one workgroup per problem ("Batches"): the problems run side by side
+ * on the chip in launches over the list of those still iterating. Per problem every output and every field of its
+ * info but the times is bit for bit what clipper_hip_sdp_solve returns for it alone with the same params, whatever
+ * else the batch holds and wherever the problem stands in it. M and C: host, column-major n x n, lower triangles
+ * read. Outputs optional (NULL allowed) as in clipper_hip_sdp_solve; nodes_out has capacity n and receives
+ * infos[i].num_nodes nodes. Only evec1, the eigenvalues, the nodes and the control records come back from the device
+ * unless a problem asks for X or Y.
+ * The whole call is refused on the first bad problem, its index in the message, before anything touches the device:
+ * count < 0, a NULL M or C, n < 1 -> CLIPPER_HIP_E_INVALID; n > CLIPPER_HIP_SDP_MAX_N -> CLIPPER_HIP_E_SCOPE; params
+ * as clipper_hip_sdp_solve. count == 0 succeeds and does nothing. A C without a nonzero diagonal entry fails the call
+ * with CLIPPER_HIP_E_INVALID. time_limit_secs > 0 bounds the whole call (checked between rounds of launches): every
+ * problem still iterating then reports timed_out = 1 and a certified dobj. t_total / t_setup / t_solve / t_extract of
+ * every info are the call's. infos (count records) may be NULL. Returns 0 or <0. */
+typedef struct clipper_sdp_problem_t {
+  const double* M;
+  const double* C;
+  int64_t n;
+  double* X_out;        /* n x n */
+  double* Y_out;        /* n x n */
+  double* lambdas_out;  /* n, ascending */
+  double* evec1_out;    /* n */
+  int32_t* nodes_out;   /* capacity n */
+} clipper_sdp_problem_t;
+int clipper_hip_sdp_solve_batch(int device, const clipper_sdp_problem_t* problems, int32_t count,
+                                const clipper_sdp_params_t* params, clipper_sdp_info_t* infos);
 
 /* ---- before the path: putative associations ------------------------------------------------ */
 
@@ -557,6 +582,19 @@ int clipper_hip_batch_get_stats(const clipper_hip_batch_t* b, int32_t* launches,
  * finished), the problems solved alone, rounding. Any pointer may be NULL. */
 int clipper_hip_batch_get_split(const clipper_hip_batch_t* b, double* fill_ms, double* launch_ms, double* alone_ms,
                                 double* round_ms);
+/* The semidefinite relaxation (clipper_hip_sdp) of every problem of the batch's last solve call, all in the launches
+ * of one batched call (clipper_hip_sdp_solve_batch's): each child's M and C with their identity diagonals, read from
+ * the store that holds them. infos: one record per problem of that solve (may be NULL). Per problem the results are
+ * bit for bit those of clipper_hip_sdp on a lone context scored from the same inputs on the same storage. Each
+ * problem's selection becomes its node list: clipper_hip_batch_get_nodes / _get_selected_associations return it
+ * (and clipper_hip_batch_get_solution's num_nodes is its size); the solver state of the children is untouched.
+ * CLIPPER_HIP_E_STATE before any solve; CLIPPER_HIP_E_SCOPE naming the first problem with m > CLIPPER_HIP_SDP_MAX_N
+ * (nothing has run then, and the batch stays usable). */
+int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* params, clipper_sdp_info_t* infos);
+/* Problem i of the last clipper_hip_batch_sdp: X and Y (m x m), lambdas (m, ascending), evec1 (m); any may be NULL.
+ * X and Y stay on the device until the next solve or relaxation of the batch. Returns m or <0. */
+int clipper_hip_batch_get_sdp(const clipper_hip_batch_t* b, int32_t i, double* X_out, double* Y_out,
+                              double* lambdas_out, double* evec1_out);
 
 #ifdef __cplusplus
 }
