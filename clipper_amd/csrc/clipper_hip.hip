@@ -267,7 +267,6 @@ int clipper_hip_get_nodes(const clipper_hip_t* h, int32_t* out, int32_t capacity
   return k;
 } CLIPPER_HIP_GUARD_INT
 
-// utils::selectInlierAssociations — utils.cpp:101-108
 int clipper_hip_get_selected_associations(const clipper_hip_t* h, int32_t* A_out,
                                           int32_t capacity) try {
   if (!h || !A_out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
@@ -276,11 +275,7 @@ int clipper_hip_get_selected_associations(const clipper_hip_t* h, int32_t* A_out
   if (k == 0) return 0;
   if (h->A.size() != static_cast<size_t>(2 * h->m))
     return fail(CLIPPER_HIP_E_STATE, "no association list is held");
-  for (int32_t r = 0; r < k; ++r) {
-    const size_t n = static_cast<size_t>(h->nodes[static_cast<size_t>(r)]);
-    A_out[r] = h->A[n];
-    A_out[k + r] = h->A[static_cast<size_t>(h->m) + n];
-  }
+  selected_associations(h, h->nodes, A_out);
   return k;
 } CLIPPER_HIP_GUARD_INT
 

@@ -5,7 +5,7 @@
 // A call
 //   1. checks every problem (nothing reaches the device if one is invalid),
 //   2. stages all inputs (D1, D2, the association lists, u0) in one pinned buffer and copies it with ONE H2D copy,
-//   3. queues every child's fill back to back (run_affinity in its deferred mode) and waits ONCE; children whose
+//   3. queues every child's fill back to back (fill_X_enqueue: run_affinity with `queued`) and waits ONCE; children whose
 //      slice arenas overflowed (the first use of a size) fill again, in a second round of their own. A user-defined
 //      invariant (kind 3, batch_fill_custom) fills every child's dense store in ONE launch instead, then queues the
 //      children's slice builds back to back and waits once per round of builds,
@@ -78,37 +78,66 @@ int stage_grow(uint8_t*& hbuf, size_t& hcap, uint8_t*& dbuf, size_t& dcap, size_
 
 int batch_grow(Batch* b, size_t bytes) { return stage_grow(b->hstage, b->hstage_cap, b->dstage, b->dstage_cap, bytes); }
 
+// what lives for one batch_solve call: its arguments, and
+struct BatchCall {
+  const clipper_batch_problem_t* p;
+  int32_t n;
+  int d, kind;
+  const double* f;
+  const clipper_params_t* P;
+  const CustomFill* cf;
+  SolverParams prm;
+  std::vector<std::vector<int32_t>> Afull;  // the association lists as stage_inputs holds them
+  std::vector<size_t> off;                  // where each problem's inputs start in the staging buffer ...
+  size_t bytes = 0;                         // ... and where they end
+  std::vector<StagedInputs> dev;            // where each problem's inputs lie on the device ...
+  std::vector<size_t> off_u0;               // ... and its u0
+  std::vector<int32_t> batched, alone;      // problems with a resident plan (in launch-table order); the others
+  std::vector<char> launched;               // per batched problem: its launch went out
+};
+
+// problem i's staged inputs handed to its child (step 3, before its fill) ...
+int batch_stage_child(Batch* b, const BatchCall& K, size_t i) {
+  const clipper_batch_problem_t& q = K.p[i];
+  return stage_inputs(b->kids[i], q.D1, K.d, q.n1, q.D2, q.n2, K.Afull[i].data(),
+                      static_cast<int64_t>(K.Afull[i].size() / 2), &K.dev[i]);
+}
+
+// ... and its u0 (behind the fill)
+int batch_stage_u0(Batch* b, const BatchCall& K, size_t i) {
+  Ctx* c = b->kids[i];
+  HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + K.off_u0[i], static_cast<size_t>(c->m) * 8, hipMemcpyDeviceToDevice,
+                        b->stream));
+  c->u0_staged = true;
+  return 0;
+}
+
 // Step 3 for a user-defined invariant (kind 3). Every child: its inputs staged, then fill_custom's and run_affinity's
 // steps before a launch (custom_fill_begin, affinity_begin: the dense store allocated). Then ONE launch of the
 // batched fill kernel over every child's tiles (the lone kernel's grid, problem after problem), whose descriptors and
-// tile table reach the device in one copy of their own. Then csc_rebuild in its deferred form: every compressed child's
-// build queued back to back, one wait, the checks; children that overflowed build again (three builds at most, as
-// pack_until_fits allows). Dense storages keep their store. A child's affinity_kernel_ms is the batched launch's time
-// (shared by every problem of the call), without the build.
-int batch_fill_custom(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d,
-                      const std::vector<std::vector<int32_t>>& Afull, const std::vector<StagedInputs>& dev,
-                      const std::vector<size_t>& off_u0, const CustomFill& cf) {
+// tile table reach the device in one copy of their own. Then csc_rebuild's pair over the children: every compressed
+// child's build queued back to back (csc_shard_enqueue), one wait, the checks (csc_shard_complete); children that
+// overflowed build again (until_fits, as many builds as csc_rebuild allows). Dense storages keep their store. A child's
+// affinity_kernel_ms is the batched launch's time (shared by every problem of the call), without the build.
+int batch_fill_custom(Batch* b, const BatchCall& K) {
+  const int32_t n = K.n;
+  const CustomFill& cf = *K.cf;
   const auto t0 = std::chrono::high_resolution_clock::now();
   hipFunction_t fn = nullptr;
   size_t ntiles = 0;
   for (int32_t i = 0; i < n; ++i) {
     Ctx* c = b->kids[static_cast<size_t>(i)];
-    const clipper_batch_problem_t& q = p[i];
-    const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
-    const int64_t m = static_cast<int64_t>(A.size() / 2);
-    if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
+    if (int rc = batch_stage_child(b, K, static_cast<size_t>(i))) return rc;
     std::vector<hipFunction_t> f;
     if (int rc = custom_fill_begin(c, cf, true, f)) return rc;
     fn = f[0];
     bool emit = false, rect = false;
     if (int rc = affinity_begin(c, false, emit, rect)) return rc;
     if (emit || rect) return fail(CLIPPER_HIP_E_INTERNAL, "problem %d: a custom fill goes through the dense store", i);
-    c->csc_emitted = false;  // (as run_affinity's launch loop leaves a fill that does not emit)
+    c->csc_emitted = false;  // (as fill_enqueue leaves a fill that does not emit)
     c->csc_out = CscOut{};
-    HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
-                          hipMemcpyDeviceToDevice, b->stream));
-    c->u0_staged = true;
-    ntiles += static_cast<size_t>(ceil_div(c->W, 1024) * ceil_div(m, AFF_ROWS_PER_BLK));
+    if (int rc = batch_stage_u0(b, K, static_cast<size_t>(i))) return rc;
+    ntiles += static_cast<size_t>(ceil_div(c->W, 1024) * ceil_div(c->m, AFF_ROWS_PER_BLK));
   }
   if (ntiles > 0x7fffffffu) return fail(CLIPPER_HIP_E_SCOPE, "a batched fill of %zu workgroups", ntiles);
 
@@ -148,28 +177,26 @@ int batch_fill_custom(Batch* b, const clipper_batch_problem_t* p, int32_t n, int
   }
 
   // the slice builds: queued back to back, one wait per round
-  std::vector<int32_t> todo;
+  std::vector<Ctx*> todo;
   for (int32_t i = 0; i < n; ++i)
-    if (csc_applies(b->kids[static_cast<size_t>(i)])) todo.push_back(i);
+    if (csc_applies(b->kids[static_cast<size_t>(i)])) todo.push_back(b->kids[static_cast<size_t>(i)]);
   float kms = 0.f;
   int rounds = 0;
-  for (int round = 0;; ++round) {
-    rounds = round + 1;
-    for (int32_t i : todo)
-      if (int rc = csc_build_enqueue(b->kids[static_cast<size_t>(i)])) return rc;
+  auto wait = [&]() -> int {
     if (hipStreamSynchronize(b->stream) != hipSuccess)
       return fail(CLIPPER_HIP_E_HIP, "batched custom fill: %s", hipGetErrorString(hipGetLastError()));
-    if (round == 0) HIPCHK(hipEventElapsedTime(&kms, b->ev_fill[0], b->ev_fill[1]));
-    std::vector<int32_t> again_list;
-    for (int32_t i : todo) {
-      bool again = false;
-      if (int rc = csc_build_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
-      if (again) again_list.push_back(i);
-    }
-    if (again_list.empty()) break;
-    if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
-    todo.swap(again_list);
-  }
+    if (rounds++ == 0) HIPCHK(hipEventElapsedTime(&kms, b->ev_fill[0], b->ev_fill[1]));
+    return 0;
+  };
+  // (no compressed child: nothing to build, but the fill's events are read only once it is through)
+  const int rc = todo.empty() ? wait() : clipper_fits::until_fits(
+      todo.size(), clipper_fits::MAX_BUILDS, [&](size_t k) { return csc_shard_enqueue(todo[k], todo[k]->sh[0]); }, wait,
+      [&](size_t k, bool& again) {
+        if (int rcc = csc_shard_complete(todo[k], todo[k]->sh[0], again)) return rcc;
+        return again ? 0 : csc_rebuilt(todo[k]);
+      },
+      [] { return build_overflows(); });
+  if (rc) return rc;
   for (int32_t i = 0; i < n; ++i) fill_held(b->kids[static_cast<size_t>(i)], kms);
   const auto t2 = std::chrono::high_resolution_clock::now();
   b->t_fill_begin = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -221,6 +248,211 @@ int batch_launch(Batch* b, int key, unsigned grid, const ResidentLaunchEntry* ta
   }
 }
 
+// ---- 1. every problem checked before any device work; the children made ----------------------------------------------
+int batch_check(Batch* b, BatchCall& K) {
+  const int32_t n = K.n;
+  const int d = K.d;
+  if (int rc = solver_params(K.P, K.prm)) return rc;
+  if (n < 0 || (n > 0 && !K.p)) return fail(CLIPPER_HIP_E_INVALID, "invalid problem list");
+  if (K.kind == 2 && d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance data are 6 x n");
+  if (K.kind == 3 && (!K.cf || d != K.cf->inv->d)) return fail(CLIPPER_HIP_E_INVALID, "no invariant of dimension d = %d", d);
+  if (d < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid dimension d = %d", d);
+  K.Afull.resize(static_cast<size_t>(n));
+  for (int32_t i = 0; i < n; ++i) {
+    const clipper_batch_problem_t& q = K.p[i];
+    if (!q.D1 || !q.D2 || q.n1 < 1 || q.n2 < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %d: invalid point data", i);
+    if (!q.u0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: u0 is required", i);
+    if (q.m < 0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: m = %lld", i, static_cast<long long>(q.m));
+    const int64_t m = (q.A == nullptr || q.m == 0) ? q.n1 * q.n2 : q.m;  // (all pairs: association_list)
+    if (m > 0x7fffffff) return fail(CLIPPER_HIP_E_INVALID, "problem %d: %lld associations", i, static_cast<long long>(m));
+    if (association_list(q.A, q.m, q.n1, q.n2, K.Afull[static_cast<size_t>(i)]))
+      return fail(CLIPPER_HIP_E_INVALID, "problem %d: %s", i, std::string(g_err).c_str());
+    K.off.push_back(K.bytes);
+    K.bytes += static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
+  }
+  b->res.resize(static_cast<size_t>(n));
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  while (b->kids.size() < static_cast<size_t>(n)) {
+    Ctx* c = make_ctx(&b->device, 1, b->storage, 1, 0, false);
+    if (!c) return CLIPPER_HIP_E_HIP;
+    hipStreamDestroy(c->sh[0].stream);
+    c->sh[0].stream = b->stream;
+    c->borrowed_stream = true;
+    b->kids.push_back(c);
+  }
+  return 0;
+}
+
+// ---- 2. the inputs: one pinned buffer, one copy ----------------------------------------------------------------------
+int batch_stage(Batch* b, BatchCall& K) {
+  if (int rc = batch_grow(b, K.bytes)) return rc;
+  const size_t n = static_cast<size_t>(K.n);
+  K.dev.resize(n);
+  K.off_u0.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const clipper_batch_problem_t& q = K.p[i];
+    const size_t bm = K.Afull[i].size() * 4;  // u0 (m doubles) and the list (2 m indices) alike
+    size_t o = K.off[i];
+    auto put = [&](const void* src, size_t bytes) {  // -> where it lies on the device
+      std::memcpy(b->hstage + o, src, bytes);
+      o += bytes;
+      return b->dstage + o - bytes;
+    };
+    K.dev[i].D1 = reinterpret_cast<const double*>(put(q.D1, static_cast<size_t>(K.d) * q.n1 * 8));
+    K.dev[i].D2 = reinterpret_cast<const double*>(put(q.D2, static_cast<size_t>(K.d) * q.n2 * 8));
+    K.off_u0[i] = static_cast<size_t>(put(q.u0, bm) - b->dstage);
+    K.dev[i].A = reinterpret_cast<const int32_t*>(put(K.Afull[i].data(), bm));
+  }
+  HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, K.bytes, hipMemcpyHostToDevice, b->stream));
+  return 0;
+}
+
+// ---- 3. the fills, queued back to back; one wait; the overflowed ones again (the built-in invariants) -----------------
+// A child whose route cannot be queued (d not 2 or 3, dense storage, the rectangular route) has run its fill to the
+// end inside its turn: it is not `queued`, and nothing is left to complete.
+int batch_fill(Batch* b, const BatchCall& K) {
+  const double* f = K.f;
+  const double aeps = K.P->affinityeps;
+  std::vector<char> queued(static_cast<size_t>(K.n), 0);
+  bool first = true;  // round 0 hands every child its inputs as well
+  return clipper_fits::until_fits(
+      queued.size(), clipper_fits::MAX_BUILDS,
+      [&](size_t i) -> int {
+        if (first)
+          if (int rc = batch_stage_child(b, K, i)) return rc;
+        bool q = false;
+        if (int rc = K.kind == 1 ? fill_euclidean_enqueue(b->kids[i], EuclidParams{f[0], f[1], f[2], aeps}, q)
+                                 : fill_pointnormal_enqueue(b->kids[i], PointNormalParams{f[0], f[1], f[2], f[3], aeps}, q))
+          return rc;
+        queued[i] = q;
+        return first ? batch_stage_u0(b, K, i) : 0;
+      },
+      [&]() -> int {
+        first = false;
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return 0;
+      },
+      [&](size_t i, bool& again) { return queued[i] ? fill_complete(b->kids[i], again) : 0; },
+      [] { return build_overflows(); });
+}
+
+// ---- 4./5. the resident plans, packed into launches; one wait --------------------------------------------------------
+int batch_launch_resident(Batch* b, BatchCall& K) {
+  long long timeout_override = 0;  // (the lone solve's test knob)
+  if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
+  std::vector<ResidentArgs> args;
+  std::vector<clipper_batch::PackItem> items;
+  for (int32_t i = 0; i < K.n; ++i) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    if (!resident_applies(c)) {
+      K.alone.push_back(i);
+      continue;
+    }
+    if (int rc = ensure_u_pinned(c)) return rc;
+    ResidentArgs a = resident_args(c, K.prm, K.P->rescale_u0 != 0);
+    // the lone solve's placement-free wait: 5 ms for one pass's sums, ten times as long on a context's first launch
+    a.timeout_ticks = timeout_override ? timeout_override : 500000ll * (c->res.epoch == 0 ? 10 : 1);
+    std::memset(c->mirror, 0, sizeof(HostMirror));
+    K.batched.push_back(i);
+    args.push_back(a);
+    items.push_back({(c->esize() == 8 ? 100 : 0) + c->res.V * 10 + c->res.E, c->res.nunits});
+  }
+  std::atomic_thread_fence(std::memory_order_seq_cst);
+  const int cap = std::max(1, b->kids[0]->cus - 8);
+  std::vector<int> rejected;
+  const std::vector<clipper_batch::PackLaunch> L = clipper_batch::pack_launches(items, cap, &rejected);
+  K.launched.assign(K.batched.size(), 0);
+  for (int k : rejected) b->kids[static_cast<size_t>(K.batched[static_cast<size_t>(k)])]->res.failed = true;
+  if (L.empty()) return 0;
+  // launch tables behind the argument array, one copy for all launches
+  const size_t args_bytes = static_cast<size_t>(round_up(static_cast<int64_t>(args.size() * sizeof(ResidentArgs)), 256));
+  size_t nent = 0;
+  for (const auto& l : L) nent += static_cast<size_t>(l.workgroups);
+  const size_t tb = args_bytes + nent * sizeof(ResidentLaunchEntry);
+  HIPCHK(hipStreamSynchronize(b->stream));  // (the staging buffers are reused: the inputs' copy is through)
+  if (int rc = batch_grow(b, tb)) return rc;
+  std::memcpy(b->hstage, args.data(), args.size() * sizeof(ResidentArgs));
+  ResidentLaunchEntry* tab = reinterpret_cast<ResidentLaunchEntry*>(b->hstage + args_bytes);
+  size_t e = 0;
+  for (const auto& l : L)
+    for (int k : l.items)
+      for (int u = 0; u < items[static_cast<size_t>(k)].units; ++u) tab[e++] = ResidentLaunchEntry{k, u};
+  HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, tb, hipMemcpyHostToDevice, b->stream));
+  const ResidentArgs* dargs = reinterpret_cast<const ResidentArgs*>(b->dstage);
+  const ResidentLaunchEntry* dtab = reinterpret_cast<const ResidentLaunchEntry*>(b->dstage + args_bytes);
+  size_t e0 = 0;
+  for (const auto& l : L) {
+    if (batch_launch(b, l.key, static_cast<unsigned>(l.workgroups), dtab + e0, dargs) == 0) {
+      ++b->launches;
+      for (int k : l.items) K.launched[static_cast<size_t>(k)] = 1;
+    } else {
+      for (int k : l.items) b->kids[static_cast<size_t>(K.batched[static_cast<size_t>(k)])]->res.failed = true;
+    }
+    e0 += static_cast<size_t>(l.workgroups);
+  }
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+// ---- 5. (its end) the progress records read back; a problem that gave up or never went out joins `alone` -------------
+int batch_read_back(Batch* b, BatchCall& K) {
+  for (size_t k = 0; k < K.batched.size(); ++k) {
+    const int32_t i = K.batched[k];
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    volatile HostMirror* hm = c->mirror;
+    if (K.launched[k] && hm->done) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      Batch::Result& R = b->res[static_cast<size_t>(i)];
+      R.route = 1;
+      solve_info(R.info, mirror_result(hm));
+      if (int rc = resident_finished(c, hm->iters)) return rc;  // (the epochs as the lone solve moves them)
+      c->last_solver = 1;
+      continue;
+    }
+    if (K.launched[k]) {  // gave up (a time-out, an LDS plan the device refused): as the lone solve does
+      uint32_t err = 0;
+      if (int rc = resident_gave_up(c, err)) return rc;
+      c->res.failed = true;  // until the next build
+      if (rs_debug()) std::fprintf(stderr, "[batch] problem %d gave up: error %u\n", i, err);
+    }
+    K.alone.push_back(i);
+  }
+  std::sort(K.alone.begin(), K.alone.end());
+  return 0;
+}
+
+// ---- 6. the others alone, on their child's ordinary path -------------------------------------------------------------
+int batch_solve_alone(Batch* b, const BatchCall& K) {
+  for (int32_t i : K.alone) {
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    Batch::Result& R = b->res[static_cast<size_t>(i)];
+    if (int rc = solve_staged(c, K.P, nullptr, &R.info)) return rc;
+    R.route = 0;
+    R.u = c->u_host;
+    R.nodes = c->nodes;
+  }
+  return 0;
+}
+
+// ---- 7. rounding of the batched ones, with the lone solve's code; every problem's selected associations --------------
+int batch_round(Batch* b, const BatchCall& K) {
+  for (int32_t i = 0; i < K.n; ++i) {
+    Batch::Result& R = b->res[static_cast<size_t>(i)];
+    Ctx* c = b->kids[static_cast<size_t>(i)];
+    if (R.route == 1) {
+      c->u_host.assign(c->u_pinned, c->u_pinned + c->m);
+      if (int rc = round_nodes(c, K.P->rounding, c->u_host, R.info.score, R.nodes)) return rc;
+      c->nodes = R.nodes;
+      R.u = c->u_host;
+      R.info.num_nodes = static_cast<int32_t>(R.nodes.size());
+    }
+    R.sel.assign(2 * R.nodes.size(), 0);
+    selected_associations(c, R.nodes, R.sel.data());
+  }
+  return 0;
+}
+
 // kind 1: EuclideanDistance (f = {sigma, epsilon, mindist}), 2: PointNormalDistance (f = {sigp, epsp, sign, epsn}),
 // 3: a user-defined invariant (cf; d = its dimension)
 int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, int kind, const double* f,
@@ -232,222 +464,22 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
   b->launches = b->n_batched = b->n_alone = 0;
   b->t_fill = b->t_launch = b->t_alone = b->t_round = 0.0;
   b->t_fill_begin = b->t_fill_launch = b->t_fill_build = 0.0;
-  // ---- 1. every problem checked before any device work -------------------------------------------------------------
-  SolverParams prm;
-  if (int rc = solver_params(P, prm)) return rc;
-  if (n < 0 || (n > 0 && !p)) return fail(CLIPPER_HIP_E_INVALID, "invalid problem list");
-  if (kind == 2 && d != 6) return fail(CLIPPER_HIP_E_INVALID, "PointNormalDistance data are 6 x n");
-  if (kind == 3 && (!cf || d != cf->inv->d)) return fail(CLIPPER_HIP_E_INVALID, "no invariant of dimension d = %d", d);
-  if (d < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid dimension d = %d", d);
-  std::vector<std::vector<int32_t>> Afull(static_cast<size_t>(n));  // the lists as stage_inputs holds them
-  size_t bytes = 0;
-  for (int32_t i = 0; i < n; ++i) {
-    const clipper_batch_problem_t& q = p[i];
-    if (!q.D1 || !q.D2 || q.n1 < 1 || q.n2 < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %d: invalid point data", i);
-    if (!q.u0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: u0 is required", i);
-    if (q.m < 0) return fail(CLIPPER_HIP_E_INVALID, "problem %d: m = %lld", i, static_cast<long long>(q.m));
-    const int64_t m = (q.A == nullptr || q.m == 0) ? q.n1 * q.n2 : q.m;  // (all pairs: association_list)
-    if (m > 0x7fffffff) return fail(CLIPPER_HIP_E_INVALID, "problem %d: %lld associations", i, static_cast<long long>(m));
-    if (association_list(q.A, q.m, q.n1, q.n2, Afull[static_cast<size_t>(i)]))
-      return fail(CLIPPER_HIP_E_INVALID, "problem %d: %s", i, std::string(g_err).c_str());
-    bytes += static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
+  BatchCall K{p, n, d, kind, f, P, cf};
+  int rc = batch_check(b, K);
+  if (rc || n == 0) {
+    b->solved = !rc;
+    return rc;
   }
-  b->res.resize(static_cast<size_t>(n));
-  if (n == 0) {
-    b->solved = true;
-    return 0;
-  }
-  HIPCHK(hipSetDevice(b->device));
-  while (b->kids.size() < static_cast<size_t>(n)) {
-    Ctx* c = make_ctx(&b->device, 1, b->storage, 1, 0, false);
-    if (!c) return CLIPPER_HIP_E_HIP;
-    hipStreamDestroy(c->sh[0].stream);
-    c->sh[0].stream = b->stream;
-    c->borrowed_stream = true;
-    b->kids.push_back(c);
-  }
-
-  // ---- 2. the inputs: one pinned buffer, one copy ------------------------------------------------------------------
-  if (int rc = batch_grow(b, bytes)) return rc;
-  std::vector<StagedInputs> dev(static_cast<size_t>(n));
-  std::vector<size_t> off_u0(static_cast<size_t>(n));
-  {
-    size_t o = 0;
-    for (int32_t i = 0; i < n; ++i) {
-      const clipper_batch_problem_t& q = p[i];
-      const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
-      const size_t b1 = static_cast<size_t>(d) * q.n1 * 8, b2 = static_cast<size_t>(d) * q.n2 * 8;
-      const size_t o0 = o;
-      std::memcpy(b->hstage + o, q.D1, b1);
-      dev[static_cast<size_t>(i)].D1 = reinterpret_cast<const double*>(b->dstage + o);
-      o += b1;
-      std::memcpy(b->hstage + o, q.D2, b2);
-      dev[static_cast<size_t>(i)].D2 = reinterpret_cast<const double*>(b->dstage + o);
-      o += b2;
-      std::memcpy(b->hstage + o, q.u0, static_cast<size_t>(m) * 8);
-      off_u0[static_cast<size_t>(i)] = o;
-      o += static_cast<size_t>(m) * 8;
-      std::memcpy(b->hstage + o, Afull[static_cast<size_t>(i)].data(), static_cast<size_t>(m) * 8);
-      dev[static_cast<size_t>(i)].A = reinterpret_cast<const int32_t*>(b->dstage + o);
-      o = o0 + static_cast<size_t>(round_up(static_cast<int64_t>(d) * (q.n1 + q.n2) * 8 + m * 16 + m * 8, 256));
-    }
-    HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, o, hipMemcpyHostToDevice, b->stream));
-  }
-
-  // ---- 3. the fills, queued back to back; one wait; the overflowed ones again ----------------------------------------
-  if (kind == 3) {
-    if (int rc = batch_fill_custom(b, p, n, d, Afull, dev, off_u0, *cf)) return rc;
-  } else {
-    auto fill = [&](Ctx* c) -> int {
-      c->fill_deferred = true;
-      const int rc = kind == 1 ? fill_euclidean(c, EuclidParams{f[0], f[1], f[2], P->affinityeps})
-                               : fill_pointnormal(c, PointNormalParams{f[0], f[1], f[2], f[3], P->affinityeps});
-      c->fill_deferred = false;
-      return rc;
-    };
-    for (int32_t i = 0; i < n; ++i) {
-      Ctx* c = b->kids[static_cast<size_t>(i)];
-      const clipper_batch_problem_t& q = p[i];
-      const int64_t m = static_cast<int64_t>(Afull[static_cast<size_t>(i)].size() / 2);
-      const std::vector<int32_t>& A = Afull[static_cast<size_t>(i)];
-      if (int rc = stage_inputs(c, q.D1, d, q.n1, q.D2, q.n2, A.data(), m, &dev[static_cast<size_t>(i)])) return rc;
-      if (int rc = fill(c)) return rc;
-      HIPCHK(hipMemcpyAsync(c->sh[0].u0, b->dstage + off_u0[static_cast<size_t>(i)], static_cast<size_t>(m) * 8,
-                            hipMemcpyDeviceToDevice, b->stream));
-      c->u0_staged = true;
-    }
-    std::vector<int32_t> todo;
-    for (int32_t i = 0; i < n; ++i) todo.push_back(i);
-    for (int round = 0; !todo.empty(); ++round) {
-      HIPCHK(hipStreamSynchronize(b->stream));
-      std::vector<int32_t> again_list;
-      for (int32_t i : todo) {
-        bool again = false;
-        if (int rc = fill_complete(b->kids[static_cast<size_t>(i)], again)) return rc;
-        if (again) again_list.push_back(i);
-      }
-      if (again_list.empty()) break;
-      if (round >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
-      for (int32_t i : again_list)
-        if (int rc = fill(b->kids[static_cast<size_t>(i)])) return rc;
-      todo.swap(again_list);
-    }
-  }
+  if ((rc = batch_stage(b, K)) || (rc = kind == 3 ? batch_fill_custom(b, K) : batch_fill(b, K))) return rc;
   const auto t1 = std::chrono::high_resolution_clock::now();
   b->t_fill = std::chrono::duration<double, std::milli>(t1 - t0).count();
-
-  // ---- 4./5. the resident plans, packed into launches ----------------------------------------------------------------
-  long long timeout_override = 0;  // (the lone solve's test knob)
-  if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
-  std::vector<int32_t> batched, alone;
-  std::vector<ResidentArgs> args;
-  std::vector<clipper_batch::PackItem> items;
-  for (int32_t i = 0; i < n; ++i) {
-    Ctx* c = b->kids[static_cast<size_t>(i)];
-    if (!resident_applies(c)) {
-      alone.push_back(i);
-      continue;
-    }
-    if (int rc = ensure_u_pinned(c)) return rc;
-    ResidentArgs a = resident_args(c, prm, P->rescale_u0 != 0);
-    // the lone solve's placement-free wait: 5 ms for one pass's sums, ten times as long on a context's first launch
-    a.timeout_ticks = timeout_override ? timeout_override : 500000ll * (c->res.epoch == 0 ? 10 : 1);
-    std::memset(c->mirror, 0, sizeof(HostMirror));
-    batched.push_back(i);
-    args.push_back(a);
-    items.push_back({(c->esize() == 8 ? 100 : 0) + c->res.V * 10 + c->res.E, c->res.nunits});
-  }
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-  const int cap = std::max(1, b->kids[0]->cus - 8);
-  std::vector<int> rejected;
-  const std::vector<clipper_batch::PackLaunch> L = clipper_batch::pack_launches(items, cap, &rejected);
-  std::vector<char> launched(batched.size(), 0);
-  for (int k : rejected) b->kids[static_cast<size_t>(batched[static_cast<size_t>(k)])]->res.failed = true;
-  if (!L.empty()) {
-    // launch tables behind the argument array, one copy for all launches
-    const size_t args_bytes = static_cast<size_t>(round_up(static_cast<int64_t>(args.size() * sizeof(ResidentArgs)), 256));
-    size_t nent = 0;
-    for (const auto& l : L) nent += static_cast<size_t>(l.workgroups);
-    const size_t tb = args_bytes + nent * sizeof(ResidentLaunchEntry);
-    HIPCHK(hipStreamSynchronize(b->stream));  // (the staging buffers are reused: the inputs' copy is through)
-    if (int rc = batch_grow(b, tb)) return rc;
-    std::memcpy(b->hstage, args.data(), args.size() * sizeof(ResidentArgs));
-    ResidentLaunchEntry* tab = reinterpret_cast<ResidentLaunchEntry*>(b->hstage + args_bytes);
-    size_t e = 0;
-    for (const auto& l : L)
-      for (int k : l.items)
-        for (int u = 0; u < items[static_cast<size_t>(k)].units; ++u) tab[e++] = ResidentLaunchEntry{k, u};
-    HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, tb, hipMemcpyHostToDevice, b->stream));
-    const ResidentArgs* dargs = reinterpret_cast<const ResidentArgs*>(b->dstage);
-    const ResidentLaunchEntry* dtab = reinterpret_cast<const ResidentLaunchEntry*>(b->dstage + args_bytes);
-    size_t e0 = 0;
-    for (const auto& l : L) {
-      if (batch_launch(b, l.key, static_cast<unsigned>(l.workgroups), dtab + e0, dargs) == 0) {
-        ++b->launches;
-        for (int k : l.items) launched[static_cast<size_t>(k)] = 1;
-      } else {
-        for (int k : l.items) b->kids[static_cast<size_t>(batched[static_cast<size_t>(k)])]->res.failed = true;
-      }
-      e0 += static_cast<size_t>(l.workgroups);
-    }
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  for (size_t k = 0; k < batched.size(); ++k) {
-    const int32_t i = batched[k];
-    Ctx* c = b->kids[static_cast<size_t>(i)];
-    volatile HostMirror* hm = c->mirror;
-    if (launched[k] && hm->done) {
-      std::atomic_thread_fence(std::memory_order_acquire);
-      Batch::Result& R = b->res[static_cast<size_t>(i)];
-      R.route = 1;
-      solve_info(R.info, mirror_result(hm));
-      if (int rc = resident_finished(c, hm->iters)) return rc;  // (the epochs as the lone solve moves them)
-      c->last_solver = 1;
-      continue;
-    }
-    if (launched[k]) {  // gave up (a time-out, an LDS plan the device refused): as the lone solve does
-      uint32_t err = 0;
-      if (int rc = resident_gave_up(c, err)) return rc;
-      c->res.failed = true;  // until the next build
-      if (rs_debug()) std::fprintf(stderr, "[batch] problem %d gave up: error %u\n", i, err);
-    }
-    alone.push_back(i);
-  }
-  std::sort(alone.begin(), alone.end());
+  if ((rc = batch_launch_resident(b, K)) || (rc = batch_read_back(b, K))) return rc;
   const auto t2 = std::chrono::high_resolution_clock::now();
   b->t_launch = std::chrono::duration<double, std::milli>(t2 - t1).count();
-
-  // ---- 6. the others alone, on their child's ordinary path ---------------------------------------------------------
-  for (int32_t i : alone) {
-    Ctx* c = b->kids[static_cast<size_t>(i)];
-    Batch::Result& R = b->res[static_cast<size_t>(i)];
-    if (int rc = solve_staged(c, P, nullptr, &R.info)) return rc;
-    R.route = 0;
-    R.u = c->u_host;
-    R.nodes = c->nodes;
-  }
+  if ((rc = batch_solve_alone(b, K))) return rc;
   const auto t3 = std::chrono::high_resolution_clock::now();
   b->t_alone = std::chrono::duration<double, std::milli>(t3 - t2).count();
-
-  // ---- 7. rounding of the batched ones, with the lone solve's code ----------------------------------------------------
-  for (int32_t i = 0; i < n; ++i) {
-    Batch::Result& R = b->res[static_cast<size_t>(i)];
-    Ctx* c = b->kids[static_cast<size_t>(i)];
-    if (R.route == 1) {
-      c->u_host.assign(c->u_pinned, c->u_pinned + c->m);
-      if (int rc = round_nodes(c, P->rounding, c->u_host, R.info.score, R.nodes)) return rc;
-      c->nodes = R.nodes;
-      R.u = c->u_host;
-      R.info.num_nodes = static_cast<int32_t>(R.nodes.size());
-    }
-    const size_t k = R.nodes.size();  // utils::selectInlierAssociations
-    R.sel.assign(2 * k, 0);
-    for (size_t r = 0; r < k; ++r) {
-      const size_t a = static_cast<size_t>(R.nodes[r]);
-      R.sel[r] = c->A[a];
-      R.sel[k + r] = c->A[static_cast<size_t>(c->m) + a];
-    }
-  }
+  if ((rc = batch_round(b, K))) return rc;
   const auto t4 = std::chrono::high_resolution_clock::now();
   b->t_round = std::chrono::duration<double, std::milli>(t4 - t3).count();
   const double secs = std::chrono::duration<double>(t4 - t0).count();
@@ -512,12 +544,8 @@ int batch_sdp(Batch* b, const clipper_sdp_params_t* P, clipper_sdp_info_t* infos
     R.nodes.assign(S->nodes(i), S->nodes(i) + k);
     c->nodes = R.nodes;
     R.info.num_nodes = static_cast<int32_t>(k);  // (what the getters size their buffers by)
-    R.sel.assign(2 * k, 0);  // utils::selectInlierAssociations
-    for (size_t r = 0; r < k; ++r) {
-      const size_t a = static_cast<size_t>(R.nodes[r]);
-      R.sel[r] = c->A[a];
-      R.sel[k + r] = c->A[static_cast<size_t>(c->m) + a];
-    }
+    R.sel.assign(2 * k, 0);
+    selected_associations(c, R.nodes, R.sel.data());
     if (infos) infos[i] = S->info[i];
   }
   b->sdp = std::move(S);

@@ -2,6 +2,8 @@
 // Part of clipper_hip.hip (one translation unit; included there, in order).
 #pragma once
 
+#include "host_fits.hpp"
+
 namespace {
 
 // ---- the compressed storage (CLIPPER_HIP_STORE_F32_CSC / _F64_CSC): groups -> slices ----------
@@ -421,22 +423,14 @@ int slices_check(Ctx* h, Shard& s, bool with_groups, bool& again) {
 
 int gather_slice_bytes(Ctx* h);
 
-// Slices for one shard from what `enqueue(O)` queues into the arrays groups_prepare() sized (groups it emits, or a
-// source of its own): the build is repeated, the buffers grown, until everything fits, `rounds` builds at most.
-// `what` heads the message of a failed wait.
-template <typename VT, typename Enqueue>
-int pack_until_fits(Ctx* h, Shard& s, bool with_groups, int rounds, const char* what, Enqueue enqueue) {
-  bool again = true;
-  for (int round = 0; again; ++round) {
-    if (round >= rounds) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
-    GroupOut<VT> O;
-    int rc;
-    if ((rc = groups_prepare<VT>(h, s, O))) return rc;
-    if ((rc = enqueue(O))) return rc;
-    if (hipStreamSynchronize(s.stream) != hipSuccess)
-      return fail(CLIPPER_HIP_E_HIP, "%s: %s", what, hipGetErrorString(hipGetLastError()));
-    if ((rc = slices_check<VT>(h, s, with_groups, again))) return rc;
-  }
+int build_overflows(const char* what = "compressed storage") {
+  return fail(CLIPPER_HIP_E_HIP, "%s: the build keeps overflowing", what);
+}
+
+// the wait of a lone build on shard s (`what` heads the message if it fails)
+int build_wait(Shard& s, const char* what) {
+  if (hipStreamSynchronize(s.stream) != hipSuccess)
+    return fail(CLIPPER_HIP_E_HIP, "%s: %s", what, hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
@@ -457,72 +451,63 @@ int csc_rebuilt(Ctx* h) {
   return gather_slice_bytes(h);  // column shards: the row-view policy's cost model is about THIS matrix
 }
 
+// One build of shard s's slices from its dense store: queued; checked once the stream has drained (again = true: the
+// buffers were grown, enqueue again). csc_rebuild runs the pair shard by shard, a batch over its children.
+int csc_shard_enqueue(Ctx* h, Shard& s) {
+  int rc = 0;
+  dispatch_vt(h, [&](auto t) {
+    using VT = decltype(t);
+    GroupOut<VT> O;
+    if ((rc = groups_prepare<VT>(h, s, O))) return;
+    rc = groups_enqueue<VT>(h, s, O);
+  });
+  return rc;
+}
+
+int csc_shard_complete(Ctx* h, Shard& s, bool& again) {
+  int rc = 0;
+  dispatch_vt(h, [&](auto t) { rc = slices_check<decltype(t)>(h, s, true, again); });
+  return rc;
+}
+
 // groups from the dense store(s) + pack + wait + plan: the setMatrixData paths, and every fill
 // that went through a dense store. Shard by shard (the pinned staging is shared).
 int csc_rebuild(Ctx* h) {
   h->csc_valid = false;
   h->total_slice_bytes = 0.0;
   if (!csc_applies(h)) return 0;
-  int rc = 0;
-  dispatch_vt(h, [&](auto t) {
-    using VT = decltype(t);
-    for (auto& s : h->sh) {
-      rc = pack_until_fits<VT>(h, s, true, 3, "compressed storage: build failed",
-                               [&](const GroupOut<VT>& O) { return groups_enqueue<VT>(h, s, O); });
-      if (rc) return;
-    }
-  });
-  if (rc) return rc;
-  return csc_rebuilt(h);
-}
-
-// csc_rebuild in two halves, for a batch that queues many contexts' builds and waits once (one shard, its stream
-// shared): csc_build_enqueue queues the build; once the stream has drained, csc_build_complete checks it (again = true:
-// the buffers were grown, enqueue again; pack_until_fits allows three builds) or ends it as csc_rebuild ends.
-int csc_build_enqueue(Ctx* h) {
-  h->csc_valid = false;
-  h->total_slice_bytes = 0.0;
-  if (!csc_applies(h)) return 0;
-  int rc = 0;
-  dispatch_vt(h, [&](auto t) {
-    using VT = decltype(t);
-    GroupOut<VT> O;
-    if ((rc = groups_prepare<VT>(h, h->sh[0], O))) return;
-    rc = groups_enqueue<VT>(h, h->sh[0], O);
-  });
-  return rc;
-}
-
-int csc_build_complete(Ctx* h, bool& again) {
-  again = false;
-  if (!csc_applies(h)) return 0;
-  int rc = 0;
-  dispatch_vt(h, [&](auto t) { rc = slices_check<decltype(t)>(h, h->sh[0], true, again); });
-  if (rc || again) return rc;
+  for (auto& s : h->sh) {
+    const int rc = clipper_fits::until_fits(
+        1, clipper_fits::MAX_BUILDS, [&](size_t) { return csc_shard_enqueue(h, s); },
+        [&] { return build_wait(s, "compressed storage: build failed"); },
+        [&](size_t, bool& again) { return csc_shard_complete(h, s, again); }, [] { return build_overflows(); });
+    if (rc) return rc;
+  }
   return csc_rebuilt(h);
 }
 
 bool rect_fill_possible(const Ctx* h);
-int gather_slice_bytes(Ctx* h);
 int launch_rect(Ctx* h, Shard& s, const int32_t* rowmap, int64_t nrows, const SliceOut& O, int64_t col0 = -1, int64_t wcols = -1);
 
 // The slices of M[rows, columns] into `st` by the rectangular fill, repeated (the arenas grown) until they fit, `rounds`
 // fills at most. (col0, wcols) = (-1, -1): this shard's columns. `plan`: the streamed pass's work list as well.
 int emit_rect(Ctx* h, Shard& s, SliceStore& st, const int32_t* rowmap, int64_t nrows, int64_t col0, int64_t wcols,
               bool plan, int rounds, const char* what) {
-  for (int round = 1;; ++round) {
-    SliceOut O{};
-    int rc;
-    if ((rc = emit_prepare(h, s, st, nrows, O, wcols))) return rc;
-    if ((rc = launch_rect(h, s, rowmap, nrows, O, col0, wcols))) return rc;
-    if ((rc = emit_enqueue(h, s, st))) return rc;
-    HIPCHK(hipStreamSynchronize(s.stream));
-    HIPCHK(hipGetLastError());
-    bool again = false;
-    if ((rc = emit_check(h, s, st, false, again, plan))) return rc;
-    if (!again) return 0;
-    if (round >= rounds) return fail(CLIPPER_HIP_E_HIP, "%s: the build keeps overflowing", what);
-  }
+  return clipper_fits::until_fits(
+      1, rounds,
+      [&](size_t) {
+        SliceOut O{};
+        int rc;
+        if ((rc = emit_prepare(h, s, st, nrows, O, wcols))) return rc;
+        if ((rc = launch_rect(h, s, rowmap, nrows, O, col0, wcols))) return rc;
+        return emit_enqueue(h, s, st);
+      },
+      [&] {
+        HIPCHK(hipStreamSynchronize(s.stream));
+        HIPCHK(hipGetLastError());
+        return 0;
+      },
+      [&](size_t, bool& again) { return emit_check(h, s, st, false, again, plan); }, [&] { return build_overflows(what); });
 }
 
 // Every compressed build the symmetric kernel cannot serve (fp64 values, column shards): the
@@ -540,7 +525,8 @@ int run_affinity_rect(Ctx* h, double& kernel_ms) {
   std::vector<char> pending(h->sh.size(), 1);
   kernel_ms = 0.0;
   for (int attempt = 0;; ++attempt) {
-    if (attempt >= 3) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+    if (attempt >= clipper_fits::MAX_BUILDS)
+      return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
     HIPCHK(hipSetDevice(s0.device));
     HIPCHK(hipEventRecord(h->ev_aff[0], s0.stream));
     std::vector<SliceOut> outs(h->sh.size());
@@ -586,7 +572,6 @@ int fill_done(Ctx* h, double build_ms);
 // the route chosen (emit: the fill kernel writes the slices; rect: the rectangular fill builds them, no dense store) and,
 // on the dense-store route, the store allocated. A batch's custom fill (host_batchsolve.hpp) starts with it too.
 int affinity_begin(Ctx* h, bool emits, bool& emit, bool& rect) {
-  h->fill_pending = false;
   h->has_matrix = false;  // until the build has succeeded (a failed rebuild leaves no matrix)
   h->csc_valid = false;
   h->total_slice_bytes = 0.0;  // (column shards: gathered again once this build's slices exist)
@@ -603,8 +588,39 @@ int affinity_begin(Ctx* h, bool emits, bool& emit, bool& rect) {
   return 0;
 }
 
+int fill_complete(Ctx* h, bool& again);
+
+// One run of a fill's kernel, queued between the two events. emit: the arenas prepared before it, the directory's way
+// back queued behind it; fill_complete() finishes such a build once the stream has drained.
 template <typename Launch>
-int run_affinity(Ctx* h, bool emits, Launch launch) {
+int fill_enqueue(Ctx* h, bool emit, Launch& launch) {
+  Shard& s0 = h->sh[0];
+  CscOut O{};
+  if (emit) {
+    if (int rc = emit_prepare(h, s0, O)) return rc;
+  } else {
+    h->csc_valid = false;
+    h->csc_emitted = false;
+  }
+  h->csc_out = O;
+  HIPCHK(hipSetDevice(s0.device));
+  HIPCHK(hipEventRecord(h->ev_aff[0], s0.stream));
+  for (auto& s : h->sh) {
+    HIPCHK(hipSetDevice(s.device));
+    launch(s);  // k_affinity_sym writes the slices itself and sets csc_emitted
+  }
+  if (emit)
+    if (int rc = emit_enqueue(h, s0)) return rc;
+  HIPCHK(hipSetDevice(s0.device));
+  HIPCHK(hipEventRecord(h->ev_aff[1], s0.stream));
+  return 0;
+}
+
+// `queued` null: the fill runs to its end. Otherwise (a batch's fill) a fill that emits is only queued — the batch waits
+// once for all its problems, then fill_complete() — and *queued says so; every other route runs to its end all the same.
+template <typename Launch>
+int run_affinity(Ctx* h, bool emits, Launch launch, bool* queued = nullptr) {
+  if (queued) *queued = false;
   bool emit = false, rect = false;
   int rc = affinity_begin(h, emits, emit, rect);
   if (rc) return rc;
@@ -625,65 +641,40 @@ int run_affinity(Ctx* h, bool emits, Launch launch) {
     HIPCHK(hipEventCreate(&h->ev_aff[0]));
     HIPCHK(hipEventCreate(&h->ev_aff[1]));
   }
-  hipEvent_t e0 = h->ev_aff[0], e1 = h->ev_aff[1];
-  double build_ms = 0.0;
-  for (int attempt = 0;; ++attempt) {
-    CscOut O{};
-    if (emit) {
-      rc = emit_prepare(h, s0, O);
-      if (rc) return rc;
-    } else {
-      h->csc_valid = false;
-      h->csc_emitted = false;
-    }
-    h->csc_out = O;
-    HIPCHK(hipSetDevice(s0.device));
-    HIPCHK(hipEventRecord(e0, s0.stream));
-    for (auto& s : h->sh) {
-      HIPCHK(hipSetDevice(s.device));
-      launch(s);  // k_affinity_sym writes the slices itself and sets csc_emitted
-    }
-    if (emit) {
-      rc = emit_enqueue(h, s0);
-      if (rc) return rc;
-    }
-    HIPCHK(hipSetDevice(s0.device));
-    HIPCHK(hipEventRecord(e1, s0.stream));
-    if (emit && h->fill_deferred) {  // a batch's fill: the batch waits once for all its problems, then fill_complete()
-      h->fill_pending = true;
-      return 0;
-    }
-    const auto th0 = std::chrono::high_resolution_clock::now();
-    rc = sync_all(h);
-    if (rc) return rc;
-    const auto th1 = std::chrono::high_resolution_clock::now();
-    if (!emit) {
-      // dense slices (column shards, the other fill kernels, fp64 storage): slices from them
-      const auto t0 = std::chrono::high_resolution_clock::now();
-      rc = csc_rebuild(h);
-      if (rc) return rc;
-      build_ms = std::chrono::duration<double, std::milli>(
-                     std::chrono::high_resolution_clock::now() - t0).count();
-      break;
-    }
-    bool again = false;
-    rc = emit_check(h, s0, again);
-    if (rc) return rc;
-    if (std::getenv("CLIPPER_HIP_HOST_TIMING")) {
-      const auto th2 = std::chrono::high_resolution_clock::now();
-      float kms = 0.f;
-      (void)hipEventElapsedTime(&kms, e0, e1);
-      std::fprintf(stderr, "[affinity] enqueue->synced %.1f us (events %.1f us), check+plan %.1f us\n",
-                   std::chrono::duration<double, std::micro>(th1 - th0).count(), kms * 1e3,
-                   std::chrono::duration<double, std::micro>(th2 - th1).count());
-    }
-    if (!again) {
-      h->csc_valid = true;
-      break;
-    }
-    if (attempt >= 2) return fail(CLIPPER_HIP_E_HIP, "compressed storage: the build keeps overflowing");
+  if (emit && queued) {
+    *queued = true;
+    return fill_enqueue(h, true, launch);
   }
-  return fill_done(h, build_ms);
+  if (emit) {
+    std::chrono::high_resolution_clock::time_point th0, th1;
+    return clipper_fits::until_fits(
+        1, clipper_fits::MAX_BUILDS, [&](size_t) { return fill_enqueue(h, true, launch); },
+        [&] {
+          th0 = std::chrono::high_resolution_clock::now();
+          const int rcw = sync_all(h);
+          th1 = std::chrono::high_resolution_clock::now();
+          return rcw;
+        },
+        [&](size_t, bool& again) {
+          const int rcc = fill_complete(h, again);
+          if (!rcc && std::getenv("CLIPPER_HIP_HOST_TIMING")) {
+            const auto th2 = std::chrono::high_resolution_clock::now();
+            float kms = 0.f;
+            (void)hipEventElapsedTime(&kms, h->ev_aff[0], h->ev_aff[1]);
+            std::fprintf(stderr, "[affinity] enqueue->synced %.1f us (events %.1f us), check+plan %.1f us\n",
+                         std::chrono::duration<double, std::micro>(th1 - th0).count(), kms * 1e3,
+                         std::chrono::duration<double, std::micro>(th2 - th1).count());
+          }
+          return rcc;
+        },
+        [] { return build_overflows(); });
+  }
+  // dense slices (column shards, the other fill kernels, fp64 storage): the store filled, slices from it
+  if ((rc = fill_enqueue(h, false, launch))) return rc;
+  if ((rc = sync_all(h))) return rc;
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  if ((rc = csc_rebuild(h))) return rc;
+  return fill_done(h, std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count());
 }
 
 // the matrix is held: its fill's timings recorded (kernel_ms: the fill kernel's time, and the build's if any)
@@ -703,13 +694,9 @@ int fill_done(Ctx* h, double build_ms) {
   return 0;
 }
 
-// A deferred fill (fill_pending), once the stream has drained: the directory's check and the plans, as
-// run_affinity makes them after its own wait. again = true: an arena overflowed (they have been grown) — the
-// caller repeats the fill.
+// The second half of fill_enqueue, once the stream has drained: the directory's check, the plans, the timings.
+// again = true: an arena overflowed (they have been grown) — the caller repeats the fill.
 int fill_complete(Ctx* h, bool& again) {
-  again = false;
-  if (!h->fill_pending) return 0;
-  h->fill_pending = false;
   if (int rc = emit_check(h, h->sh[0], again)) return rc;
   if (again) return 0;
   h->csc_valid = true;
@@ -816,6 +803,9 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
 
 int fill_euclidean(Ctx* h, const EuclidParams& prm);  // the matrix from the staged points (clipper_hip.hip)
 int fill_pointnormal(Ctx* h, const PointNormalParams& prm);
+// a batch's: as run_affinity with `queued`
+int fill_euclidean_enqueue(Ctx* h, const EuclidParams& prm, bool& queued);
+int fill_pointnormal_enqueue(Ctx* h, const PointNormalParams& prm, bool& queued);
 
 // stage_inputs, then the fill: affinity_total_ms counts both
 template <typename Params>

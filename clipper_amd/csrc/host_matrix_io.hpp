@@ -19,9 +19,10 @@ int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S,
 
 
 // The two fills (declared in host_matrix.hpp): defined here, behind the batch, so that the fill kernels keep their place
-// in the code object.
+// in the code object. Each has one body, reached through fill_X (the fill runs to its end) and fill_X_enqueue (a
+// batch's: see run_affinity's `queued`).
 // EuclideanDistance over the staged points: the matrix of this context
-int fill_euclidean(Ctx* h, const EuclidParams& prm) {
+int euclidean_fill(Ctx* h, const EuclidParams& prm, bool* queued) {
   if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
   const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
   const int d = h->staged_d;
@@ -70,12 +71,14 @@ int fill_euclidean(Ctx* h, const EuclidParams& prm) {
     });
 #undef LAUNCH_EUCLID_COMPACT
 #undef LAUNCH_EUCLID
-  });
+  }, queued);
 }
+int fill_euclidean(Ctx* h, const EuclidParams& prm) { return euclidean_fill(h, prm, nullptr); }
+int fill_euclidean_enqueue(Ctx* h, const EuclidParams& prm, bool& queued) { return euclidean_fill(h, prm, &queued); }
 
 
 // PointNormalDistance over the staged points: the matrix of this context
-int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
+int pointnormal_fill(Ctx* h, const PointNormalParams& prm, bool* queued) {
   if (h->staged_d != 6)
     return fail(CLIPPER_HIP_E_STATE, "PointNormalDistance needs staged inputs with d == 6");
   const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
@@ -113,8 +116,10 @@ int fill_pointnormal(Ctx* h, const PointNormalParams& prm) {
         hipLaunchKernelGGL((k_affinity_pointnormal_compact<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, mm,
                            c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
       });
-  });
+  }, queued);
 }
+int fill_pointnormal(Ctx* h, const PointNormalParams& prm) { return pointnormal_fill(h, prm, nullptr); }
+int fill_pointnormal_enqueue(Ctx* h, const PointNormalParams& prm, bool& queued) { return pointnormal_fill(h, prm, &queued); }
 
 // A user-defined invariant over the staged points (host_custom_invariant.hpp): every shard's dense store from the
 // invariant's own fill kernel, then the slices from it as for any dense store. No rectangular fill exists for it
@@ -283,14 +288,20 @@ int sparse_to_slices(Ctx* h, const clipper_csc::CscRef& M) {
     const int64_t c0 = static_cast<int64_t>(s.slot) * W;
     dispatch_vt(h, [&](auto t) {
       using VT = decltype(t);
-      rc = pack_until_fits<VT>(h, s, false, 3, "set_sparse", [&](const GroupOut<VT>&) {  // (the groups go unused)
-        CscSource<VT> src{};
-        src.colptr = d.cp + std::min<int64_t>(c0, m);
-        src.rowidx = d.ri;
-        src.values = d.va;
-        src.ncols = std::max<int64_t>(0, std::min<int64_t>(W, m - c0));
-        return slices_enqueue<VT>(h, s, src, nullptr);
-      });
+      rc = clipper_fits::until_fits(
+          1, clipper_fits::MAX_BUILDS,
+          [&](size_t) {
+            GroupOut<VT> O;  // (the groups go unused: groups_prepare sizes the slices' arrays as well)
+            if (int r = groups_prepare<VT>(h, s, O)) return r;
+            CscSource<VT> src{};
+            src.colptr = d.cp + std::min<int64_t>(c0, m);
+            src.rowidx = d.ri;
+            src.values = d.va;
+            src.ncols = std::max<int64_t>(0, std::min<int64_t>(W, m - c0));
+            return slices_enqueue<VT>(h, s, src, nullptr);
+          },
+          [&] { return build_wait(s, "set_sparse"); },
+          [&](size_t, bool& again) { return slices_check<VT>(h, s, false, again); }, [] { return build_overflows(); });
     });
     if (rc) return rc;
   }

@@ -56,6 +56,16 @@ int ensure_u_pinned(Ctx* h) {
   return 0;
 }
 
+// utils::selectInlierAssociations (utils.cpp:101-108): the associations of `nodes`, column-major k x 2, into `out`
+void selected_associations(const Ctx* h, const std::vector<int32_t>& nodes, int32_t* out) {
+  const size_t k = nodes.size();
+  for (size_t r = 0; r < k; ++r) {
+    const size_t a = static_cast<size_t>(nodes[r]);
+    out[r] = h->A[a];
+    out[k + r] = h->A[static_cast<size_t>(h->m) + a];
+  }
+}
+
 // rounding — clipper.cpp:287-310 with utils.cpp:33-68, on the host (a lone solve and every problem of a batch)
 int round_nodes(Ctx* h, int rounding, const std::vector<double>& u, double F, std::vector<int32_t>& nodes) {
   const int64_t m = static_cast<int64_t>(u.size());

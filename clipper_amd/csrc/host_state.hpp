@@ -348,8 +348,6 @@ struct clipper_hip_ctx {
   bool early_decide_done = false;           // iteration (host_rowview.hpp) ... and did: the hold is lifted, it is queued
   int resident_mode = 0;   // 0 = use the resident solver where the slices fit, 1 = never
   bool borrowed_stream = false;  // sh[0].stream is a batch's (host_batchsolve.hpp): not this context's to destroy
-  bool fill_deferred = false;    // a batch's fill: run_affinity queues the fill and returns before the wait ...
-  bool fill_pending = false;     // ... and this says it did (fill_complete() finishes it once the stream has drained)
   int last_solver = 0;     // what the last solve ran on: 0 = streaming launches, 1 = resident
 
   // what built the matrix, kept so that a row view can be filled from the same points later:

@@ -1,5 +1,5 @@
-"""CPU checks of the batched solves: the launch packer (g++ only), the ctypes layout of
-clipper_batch_problem_t, and the Python surfaces. The GPU side is tests/test_gpu_batch.py."""
+"""CPU checks of the batched solves: the launch packer and the build-until-it-fits driver (g++ only),
+the ctypes layout of clipper_batch_problem_t, and the Python surfaces. The GPU side is tests/test_gpu_batch.py."""
 import ctypes as C
 import os
 import subprocess
@@ -13,6 +13,14 @@ def test_launch_packer(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "test_batch_pack.cpp"), "-o", exe])
     out = subprocess.check_output([exe], timeout=300).decode()
     assert "batch pack ok" in out
+
+
+def test_until_fits_driver(tmp_path):
+    exe = str(tmp_path / "test_until_fits")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "clipper_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "test_until_fits.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], timeout=300).decode()
+    assert "until fits ok" in out
 
 
 def test_batch_problem_layout():

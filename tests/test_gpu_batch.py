@@ -1,6 +1,7 @@
 """Batched solves (clipper_hip_batch_*, HipBatch): every problem of a batch gives, bit for bit, what a
 lone HipClipper of the same storage gives with the same inputs, u0 and params whenever both took the same route;
 problems the resident solver does not take, or whose batched launch gave up, are solved alone and still match."""
+import dataclasses
 import os
 import subprocess
 
@@ -181,6 +182,53 @@ def test_batch_reuse_and_edges():
     probs2 = [synth.make_euclidean_problem(m, 0.9, seed=14 + m) for m in (90, 700)]
     sols = b.solve_euclidean([(p.D1, p.D2, p.A, p.u0) for p in probs2], **INV)
     _check_against_lone(b, sols, probs2, abi.STORE_F32_CSC)
+    b.close()
+
+
+def _check_against_fresh_lone(batch, sols, probs, storage):
+    """every problem against a lone context of its own: every route must agree, and every bit"""
+    for i, (p, sb) in enumerate(zip(probs, sols)):
+        g, sl, last, sel = _lone(storage, p)
+        what = f"problem {i} (m={len(p.u0)}, d={p.D1.shape[0]}, storage {storage}, route {batch.route(i)}, lone {last})"
+        assert batch.route(i) == last, what
+        _assert_bits(sb, sl, what)
+        assert np.array_equal(batch.selected_associations(i), sel), f"{what}: selected associations differ"
+        g.close()
+
+
+def _sized(sizes, seed0):
+    # m = 130: two 128-row chunks, three 64-column groups; m = 700 next to it
+    return [synth.make_euclidean_problem(m, 0.9, seed=seed0 + k) for k, m in enumerate(sizes)]
+
+
+def test_batch_fill_that_cannot_be_queued_d4():
+    # d = 4 on slices: the fill cannot emit (dense store -> groups -> slices), so it runs to its end inside the
+    # child's turn and the batch has nothing left to complete for it. A fourth coordinate of zeros: the 3-D distances.
+    probs = [dataclasses.replace(p, D1=np.vstack([p.D1, np.zeros((1, p.D1.shape[1]))]),
+                                 D2=np.vstack([p.D2, np.zeros((1, p.D2.shape[1]))])) for p in _sized((130, 700), 5000)]
+    b = abi.HipBatch(storage=abi.STORE_F32_CSC)
+    sols = b.solve_euclidean([(p.D1, p.D2, p.A, p.u0) for p in probs], **INV)
+    _check_against_fresh_lone(b, sols, probs, abi.STORE_F32_CSC)
+    b.close()
+
+
+def test_batch_fill_that_cannot_be_queued_rect():
+    # d = 3 with fp64 values in the slices: the rectangular fill, which runs to its end inside the child's turn too
+    probs = _sized((130, 700), 5100)
+    b = abi.HipBatch(storage=abi.STORE_F64_CSC)
+    sols = b.solve_euclidean([(p.D1, p.D2, p.A, p.u0) for p in probs], **INV)
+    _check_against_fresh_lone(b, sols, probs, abi.STORE_F64_CSC)
+    b.close()
+
+
+def test_batch_three_calls_grow_then_reuse():
+    b = abi.HipBatch(storage=abi.STORE_F32_CSC)
+    # fresh children: every arena overflows once; the same sizes again: nothing does; the sizes swapped: each child
+    # meets the other size, one grows and one reuses
+    for call, sizes in enumerate([(130, 700), (130, 700), (700, 130)]):
+        probs = _sized(sizes, 5200 + 10 * call)
+        sols = b.solve_euclidean([(p.D1, p.D2, p.A, p.u0) for p in probs], **INV)
+        _check_against_fresh_lone(b, sols, probs, abi.STORE_F32_CSC)
     b.close()
 
 

@@ -3,6 +3,7 @@ CLIPPERBatch::withDeviceInvariant; DESIGN.md 10, 12): one launch of the invarian
 problem, and every problem then gives, bit for bit, what a lone HipClipper of the same storage gives with
 affinity_custom + solve on the same inputs, u0 and params, whenever both took the same route."""
 import os
+import re
 import subprocess
 import sys
 
@@ -108,6 +109,23 @@ def test_pointnormal_restated(storage):
         routes = _check_against_lone(b, sols, probs, storage, inv, PPRM)
         assert all(r == last for r, last in routes), routes
         b.close()
+
+
+def test_dense_storage_has_no_build_rounds(euclid_inv, capfd, monkeypatch):
+    # dense fp32 storage: no compressed child, so the build rounds run over an empty list — the batch still waits for
+    # the fill before it reads the fill's events. One problem, m = 130 (more than one 128-row chunk).
+    monkeypatch.setenv("CLIPPER_HIP_HOST_TIMING", "1")
+    p = synth.make_euclidean_problem(130, 0.9, seed=1300)
+    b = abi.HipBatch(storage=abi.STORE_F32)
+    sols = b.solve_custom(euclid_inv, _tuples([p]), EPRM)
+    err = capfd.readouterr().err
+    routes = _check_against_lone(b, sols, [p], abi.STORE_F32, euclid_inv, EPRM)
+    assert routes == [(0, 0)]
+    # the children's affinity_kernel_ms: the event time of one small launch, not a pair read before it was through
+    mt = re.search(r"\[batch-custom\] n = 1:.* (\d+) tiles ([0-9.]+) ms \(events\)", err)
+    assert mt and int(mt.group(1)) >= 1 and 0.0 < float(mt.group(2)) < 1000.0, err
+    assert b.split()["fill_ms"] > 0
+    b.close()
 
 
 @pytest.mark.parametrize("nan", [False, True])
