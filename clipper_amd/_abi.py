@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_batch_get_split", "clipper_hip_invariant_create", "clipper_hip_invariant_destroy",
     "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom", "clipper_hip_batch_solve_custom",
     "clipper_hip_sdp_solve_batch", "clipper_hip_batch_sdp", "clipper_hip_batch_get_sdp",
+    "clipper_hip_batch_max_clique", "clipper_hip_batch_max_clique_stats",
 ]
 
 
@@ -296,6 +297,8 @@ def load_library(path: str = LIB_PATH):
                                               C.POINTER(SdpInfo)]
     L.clipper_hip_batch_sdp.argtypes = [vp, C.POINTER(SdpParams), C.POINTER(SdpInfo)]
     L.clipper_hip_batch_get_sdp.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
+    L.clipper_hip_batch_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
+    L.clipper_hip_batch_max_clique_stats.argtypes = [vp, ip, ip, ip]
     L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     L.clipper_hip_batch_destroy.argtypes = [vp]
     L.clipper_hip_batch_destroy.restype = None
@@ -994,6 +997,30 @@ class HipBatch:
             k = self._check(self.L.clipper_hip_batch_get_nodes(self.b, i, _ip(nodes), nodes.size))
             out.append(_sdp_result(n, X, Y, lam, ev, nodes[:k].copy(), info))
         return out
+
+    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0) -> list:
+        """The maximum clique (HipClipper.max_clique) of every problem of the last solve call, in one batched call
+        (clipper_hip_batch_max_clique): per problem (nodes ascending, MaxCliqueInfo), the nodes and max_core,
+        heuristic_size, edges, num_nodes those of a lone context. Each clique becomes its problem's node list
+        (get_nodes(i), selected_associations(i)). time_limit in seconds bounds the whole call (<= 0: none)."""
+        infos = (MaxCliqueInfo * max(self.n, 1))()
+        self._check(self.L.clipper_hip_batch_max_clique(self.b, int(method), float(time_limit), infos))
+        return [(self.get_nodes(i), MaxCliqueInfo.from_buffer_copy(infos[i])) for i in range(self.n)]
+
+    def max_clique_stats(self):
+        """(kernel launches of the batched route, problems that ran in them, problems that ran alone) of the last
+        max_clique call"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.L.clipper_hip_batch_max_clique_stats(self.b, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def get_nodes(self, i: int):
+        """problem i's node list as the last solve, relaxation or clique call left it (ascending)"""
+        info = SolveInfo()
+        self._check(self.L.clipper_hip_batch_get_solution(self.b, i, None, C.byref(info)))
+        nodes = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
+        k = self._check(self.L.clipper_hip_batch_get_nodes(self.b, i, _ip(nodes), nodes.size))
+        return nodes[:k].copy()
 
     def route(self, i: int) -> int:
         """1 = solved in a batched resident launch, 0 = solved alone on its child context"""

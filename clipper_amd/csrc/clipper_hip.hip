@@ -1,7 +1,8 @@
 // clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_state.hpp (context, shards,
 // RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver),
-// host_solve.hpp (the solve of one context), host_matrix_io.hpp (the fills, matrix set / get, mat-vecs, nearest
-// neighbours; included last: it holds its kernels' place in the code object), host_csc_input.hpp (the sparse input's
+// host_solve.hpp (the solve of one context), host_mcbatch.hpp (the maximum cliques of a batch), host_matrix_io.hpp
+// (the fills, matrix set / get, mat-vecs, nearest neighbours; included last: it holds its kernels' place in the code
+// object), host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
@@ -55,6 +56,7 @@ using namespace clipper_hip;
 #include "host_solve.hpp"
 #include "host_custom_invariant.hpp"
 #include "host_batchsolve.hpp"
+#include "host_mcbatch.hpp"
 #include "host_matrix_io.hpp"
 
 extern "C" {
@@ -504,6 +506,7 @@ void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
   if (b->dstage) hipFree(b->dstage);
   if (b->hfill) hipHostFree(b->hfill);
   if (b->dfill) hipFree(b->dfill);
+  if (b->hmc) hipHostFree(b->hmc);
   for (hipEvent_t e : b->ev_fill)
     if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);
@@ -577,6 +580,21 @@ int clipper_hip_batch_get_sdp(const clipper_hip_batch_t* b, int32_t i, double* X
     return fail(CLIPPER_HIP_E_INVALID, "no problem %d in the last relaxation of the batch", i);
   if (int rc = sdp_batch_outputs(*b->sdp, static_cast<size_t>(i), X_out, Y_out, lambdas_out, evec1_out)) return rc;
   return b->sdp->n[static_cast<size_t>(i)];
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_max_clique(clipper_hip_batch_t* b, int method, double time_limit_s,
+                                 clipper_maxclique_info_t* infos) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return batch_max_clique(b, method, time_limit_s, infos);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_max_clique_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched,
+                                       int32_t* n_alone) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  if (launches) *launches = b->mc_launches;
+  if (n_batched) *n_batched = b->mc_batched;
+  if (n_alone) *n_alone = b->mc_alone;
+  return 0;
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_batch_route(const clipper_hip_batch_t* b, int32_t i) try {

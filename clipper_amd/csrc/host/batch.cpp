@@ -2,6 +2,7 @@
 #include "clipper/batch.h"
 
 #include <algorithm>
+#include <iostream>
 #include <stdexcept>
 #include <string>
 #include <typeinfo>
@@ -156,6 +157,38 @@ std::vector<Solution> CLIPPERBatch::solveAsMSRCSDR(const sdp::Params& params) {
     o.nodes = s.nodes;
     o.u = VectorXd::Zero(m);
     o.score = -1;
+  }
+  return out;
+}
+
+// clipper_hip_batch_max_clique on the problems of the last solve; per problem what CLIPPER::solveAsMaximumClique leaves
+std::vector<Solution> CLIPPERBatch::solveAsMaximumClique(const maxclique::Params& params) {
+  if (!b_) throw std::logic_error("clipper: no batch has been solved");
+  const int method = params.method == maxclique::Method::EXACT ? CLIPPER_HIP_MC_EXACT
+                     : params.method == maxclique::Method::HEU ? CLIPPER_HIP_MC_HEU
+                                                               : CLIPPER_HIP_MC_KCORE;
+  const int32_t count = static_cast<int32_t>(n_);
+  std::vector<clipper_maxclique_info_t> info(static_cast<size_t>(std::max<int32_t>(count, 1)));
+  check(clipper_hip_batch_max_clique(b_, method, static_cast<double>(params.time_limit), info.data()),
+        "batch solveAsMaximumClique");
+  std::vector<Solution> out(static_cast<size_t>(count));
+  for (int32_t i = 0; i < count; ++i) {
+    const clipper_maxclique_info_t& I = info[static_cast<size_t>(i)];
+    const int m = clipper_hip_batch_get_solution(b_, i, nullptr, nullptr);
+    check(m, "batch solveAsMaximumClique (sizes)");
+    Solution& o = out[static_cast<size_t>(i)];  // clipper.cpp:92-96
+    o.nodes.resize(static_cast<size_t>(I.num_nodes));
+    if (I.num_nodes > 0)
+      check(clipper_hip_batch_get_nodes(b_, i, o.nodes.data(), I.num_nodes), "batch solveAsMaximumClique (nodes)");
+    o.t = I.seconds;
+    o.ifinal = 0;
+    o.u = VectorXd::Zero(m);
+    o.score = -1;
+    if (params.verbose)
+      std::cout << "maxclique: problem " << i << ": m = " << m << ", edges = " << I.edges << ", max core = " << I.max_core
+                << ", heuristic = " << I.heuristic_size << ", clique = " << I.num_nodes
+                << (I.timed_out ? " (timed out)" : "") << ", bb nodes = " << I.bb_nodes << ", " << I.seconds << " s"
+                << std::endl;
   }
   return out;
 }

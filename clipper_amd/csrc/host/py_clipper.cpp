@@ -393,5 +393,8 @@ PYBIND11_MODULE(clipperpy, m) {
       .def("solved_batched", &clipper::CLIPPERBatch::solvedBatched, "i"_a)
       // the semidefinite relaxation of every problem of the last solve, in one batched call
       .def("solve_as_msrc_sdr", &clipper::CLIPPERBatch::solveAsMSRCSDR, "params"_a = clipper::sdp::Params{})
-      .def("sdp_solutions", &clipper::CLIPPERBatch::sdpSolutions);
+      .def("sdp_solutions", &clipper::CLIPPERBatch::sdpSolutions)
+      // the maximum clique of every problem of the last solve, in one batched call
+      .def("solve_as_maximum_clique", &clipper::CLIPPERBatch::solveAsMaximumClique,
+           "params"_a = clipper::maxclique::Params{});
 }

@@ -4,6 +4,8 @@
 // Part of clipper_hip.hip (one translation unit; included there, in order).
 #pragma once
 
+#include "host_mcplan.hpp"
+
 namespace {
 
 constexpr int64_t MC_MAX_M = 655360;           // the EXACT kernel's two LDS bitsets: 2 x 8 x ceil(m / 64) <= 160 KiB
@@ -28,6 +30,26 @@ struct McBufs {
       if (p) hipFree(p);
   }
 };
+
+// the one descriptor of a lone call (k_maxclique.hip.h): the buffers allocated so far
+McProb mc_prob(const McBufs& b, int64_t nw, int64_t m) {
+  McProb p{};
+  p.G = b.G;
+  p.nw = nw;
+  p.m = static_cast<int32_t>(m);
+  p.degw = b.degw;
+  p.core = b.core;
+  p.alive = b.alive;
+  p.pos = b.pos;
+  p.list = b.list;
+  p.out = b.out;
+  p.ctl = b.ctl;
+  p.slots = b.slots;
+  p.arena = b.arena;
+  p.paths = b.paths;
+  p.recs = b.recs;
+  return p;
+}
 
 template <typename T>
 int mc_alloc(T*& p, size_t count) {
@@ -90,8 +112,7 @@ int mc_graph_and_cores(Ctx* h, McBufs& b, int64_t nw, std::vector<int32_t>& deg,
   int64_t launches = 0;
   do {
     if (++launches > m + 1) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: the core peel made no progress");
-    hipLaunchKernelGGL(k_mc_core_peel, dim3(1), dim3(MC_PEEL_THREADS), lds, s.stream, b.G, nw, static_cast<int32_t>(m),
-                       b.degw, b.core, b.alive, b.ctl, MC_PEEL_BUDGET);
+    hipLaunchKernelGGL(k_mc_core_peel, dim3(1), dim3(MC_PEEL_THREADS), lds, s.stream, mc_prob(b, nw, m), MC_PEEL_BUDGET);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
     HIPCHK(hipStreamSynchronize(s.stream));
@@ -135,8 +156,7 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
   } else if (I.edges > 0) {
     // ---- HEU: seeds by core descending, index ascending
     std::vector<int32_t> seeds(static_cast<size_t>(m));
-    for (int64_t v = 0; v < m; ++v) seeds[static_cast<size_t>(v)] = static_cast<int32_t>(v);
-    std::stable_sort(seeds.begin(), seeds.end(), [&](int32_t a, int32_t c) { return core[a] > core[c]; });
+    clipper_mc_plan::seed_order(core.data(), m, seeds.data());
     if (int rc = mc_alloc(b.list, static_cast<size_t>(m))) return rc;
     if (int rc = mc_alloc(b.out, static_cast<size_t>(K) + 2)) return rc;
     HIPCHK(hipMemcpy(b.list, seeds.data(), static_cast<size_t>(m) * 4, hipMemcpyHostToDevice));
@@ -146,9 +166,10 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
       raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_heu_one), s.device, lds1);
     }
     McCtl c{};
+    McProb pr = mc_prob(b, nw, m);
+    pr.nlist = static_cast<int32_t>(m);
     do {
-      hipLaunchKernelGGL(k_mc_heu, dim3(static_cast<unsigned>(nwaves)), dim3(64), lds1, s.stream, b.G, nw, b.core, b.list,
-                         static_cast<int32_t>(m), b.ctl, MC_WAVE_BUDGET);
+      hipLaunchKernelGGL(k_mc_heu, dim3(static_cast<unsigned>(nwaves)), dim3(64), lds1, s.stream, pr, MC_WAVE_BUDGET);
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
       HIPCHK(hipStreamSynchronize(s.stream));
@@ -161,7 +182,8 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
     const int seed = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(c.key & 0xFFFFFFFFull));
     if (heu < 2 || heu > K + 1 || seed < 0 || seed >= m)
       return fail(CLIPPER_HIP_E_INTERNAL, "max clique: HEU's record (size %d, seed %d) is not valid", heu, seed);
-    hipLaunchKernelGGL(k_mc_heu_one, dim3(1), dim3(64), lds1, s.stream, b.G, nw, b.core, seed, b.out);
+    pr.seed = seed;
+    hipLaunchKernelGGL(k_mc_heu_one, dim3(1), dim3(64), lds1, s.stream, pr);
     HIPCHK(hipGetLastError());
     nodes.resize(static_cast<size_t>(heu));
     HIPCHK(hipMemcpyAsync(nodes.data(), b.out, static_cast<size_t>(heu) * 4, hipMemcpyDeviceToHost, s.stream));
@@ -170,17 +192,8 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
     if (method == CLIPPER_HIP_MC_EXACT && heu < K + 1 && !I.timed_out) {
       // ---- EXACT: roots ordered by (core, degree, index); those that can hold a clique larger than HEU's,
       // taken from the end of that order (the largest bound first)
-      std::vector<int32_t> order(static_cast<size_t>(m)), pos(static_cast<size_t>(m));
-      for (int64_t v = 0; v < m; ++v) order[static_cast<size_t>(v)] = static_cast<int32_t>(v);
-      std::sort(order.begin(), order.end(), [&](int32_t a, int32_t c2) {
-        if (core[a] != core[c2]) return core[a] < core[c2];
-        if (deg[a] != deg[c2]) return deg[a] < deg[c2];
-        return a < c2;
-      });
-      for (int64_t i = 0; i < m; ++i) pos[static_cast<size_t>(order[static_cast<size_t>(i)])] = static_cast<int32_t>(i);
-      std::vector<int32_t> roots;
-      for (int64_t i = m - 1; i >= 0; --i)
-        if (core[order[static_cast<size_t>(i)]] >= heu) roots.push_back(order[static_cast<size_t>(i)]);
+      std::vector<int32_t> pos(static_cast<size_t>(m)), roots;
+      clipper_mc_plan::root_order(core.data(), deg.data(), m, heu, pos.data(), roots);
       I.roots_pruned = m - static_cast<int64_t>(roots.size());
       const int D = K + 1;  // stack levels: a clique has at most K + 1 vertices
       size_t freeb = 0, totalb = 0;
@@ -207,11 +220,13 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
       const int lds2 = 2 * lds1;
       if (lds2 > 64 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_exact), s.device, lds2);
       const int32_t nroots = static_cast<int32_t>(roots.size());
+      pr = mc_prob(b, nw, m);
+      pr.nlist = nroots;
+      pr.heu = static_cast<int32_t>(heu);
+      pr.D = static_cast<int32_t>(D);
       while (true) {
         HIPCHK(hipMemsetAsync(&b.ctl->active, 0, sizeof(int32_t), s.stream));
-        hipLaunchKernelGGL(k_mc_exact, dim3(static_cast<unsigned>(nslots)), dim3(64), lds2, s.stream, b.G, nw, b.core,
-                           b.pos, b.list, nroots, static_cast<int32_t>(heu), b.ctl, b.slots, b.arena, b.paths, b.recs,
-                           static_cast<int32_t>(D), MC_WAVE_BUDGET);
+        hipLaunchKernelGGL(k_mc_exact, dim3(static_cast<unsigned>(nslots)), dim3(64), lds2, s.stream, pr, MC_WAVE_BUDGET);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
         HIPCHK(hipStreamSynchronize(s.stream));

@@ -39,6 +39,32 @@ struct McSlot {
   unsigned long long rec_key;  // the key of the clique this slot recorded last (0: none)
 };
 
+// One problem as the device functions below see it: a lone call passes its one descriptor as a kernel argument, a
+// batched call (k_maxclique_batch.hip.h) keeps a table of them on the device. The host fills the fields a phase
+// reads: the peel G, nw, m, degw, core, alive, ctl; HEU also list (seeds), nlist; the regeneration seed, out;
+// EXACT list (roots), nlist, pos, heu, D and the slots' state.
+struct McProb {
+  const uint64_t* G;     // m rows of nw words
+  int64_t nw;
+  int32_t m;
+  int32_t nlist;         // seeds (HEU) / roots (EXACT) in `list`
+  int32_t* degw;         // the peel's working degrees
+  int32_t* core;
+  uint64_t* alive;       // nw words: the peel's alive set between launches
+  const int32_t* pos;    // EXACT: the (core, degree, index) order
+  const int32_t* list;
+  int32_t heu;           // EXACT: HEU's size
+  int32_t D;             // EXACT: stack levels of a slot
+  int32_t seed;          // the regeneration of HEU's clique: its seed ...
+  int32_t nslots;        // EXACT: the problem's slots (read by the batch's collection of the record only)
+  int32_t* out;          // ... and where it goes
+  McCtl* ctl;
+  McSlot* slots;         // EXACT, per slot: state, D x nw words of stack, D + 1 path entries, D + 1 record entries
+  uint64_t* arena;
+  int32_t* paths;
+  int32_t* recs;
+};
+
 constexpr int MC_PEEL_THREADS = 1024;
 constexpr int MC_PEEL_FCAP = 2048;  // vertices peeled per round at most (the rest wait for the next round)
 
@@ -87,12 +113,10 @@ __device__ __forceinline__ int mc_first_word(const uint64_t* X, int lo, int hi, 
 // stored, so column c's entries are row c of the graph. G is zeroed by the caller; a lane writes only words of
 // its own row, the atomic OR keeps the chunks of one column group (other waves, other words) independent.
 template <typename VT, int H>
-__global__ __launch_bounds__(256) void k_mc_adj_slices(SliceView M, uint64_t* __restrict__ G, int64_t nw,
-                                                       int64_t m) {
+__device__ __forceinline__ void mc_adj_slice(const SliceView& M, uint64_t* __restrict__ G, int64_t nw, int64_t m,
+                                             int64_t s, int lane) {
   constexpr int QB = 4 * static_cast<int>(sizeof(VT));
   constexpr int R = SL_SUB * H;
-  const int lane = threadIdx.x & 63;
-  const int64_t s = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (s >= static_cast<int64_t>(M.ncg) * M.nchunks) return;
   const int cg = static_cast<int>(s / M.nchunks), k = static_cast<int>(s - static_cast<int64_t>(cg) * M.nchunks);
   const int64_t c = static_cast<int64_t>(cg) * SL_W + lane;
@@ -131,33 +155,46 @@ __global__ __launch_bounds__(256) void k_mc_adj_slices(SliceView M, uint64_t* __
   }
 }
 
+template <typename VT, int H>
+__global__ __launch_bounds__(256) void k_mc_adj_slices(SliceView M, uint64_t* __restrict__ G, int64_t nw,
+                                                       int64_t m) {
+  mc_adj_slice<VT, H>(M, G, nw, m, static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
+
 // From a dense one-shard store S[j][c] (row pitch ld; M's values or the explicit C): thread = (row c, word w),
 // bit b set when S[64 w + b][c] != 0. The loads of one j are coalesced over c. Writes every word of G.
+template <typename T>
+__device__ __forceinline__ uint64_t mc_adj_dense_word(const T* __restrict__ S, int64_t ld, int64_t m, int64_t c,
+                                                      int64_t w) {
+  uint64_t word = 0;
+  const int64_t j0 = w * 64;
+  const int nb = static_cast<int>((m - j0) < 64 ? (m - j0) : 64);
+  for (int b = 0; b < nb; ++b)
+    if (S[(j0 + b) * ld + c] != T(0) && j0 + b != c) word |= 1ull << b;
+  return word;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_mc_adj_dense(const T* __restrict__ S, int64_t ld, int64_t m, int64_t nw,
                                                       uint64_t* __restrict__ G) {
   const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (c >= m) return;
-  for (int64_t w = blockIdx.y; w < nw; w += gridDim.y) {
-    uint64_t word = 0;
-    const int64_t j0 = w * 64;
-    const int nb = static_cast<int>((m - j0) < 64 ? (m - j0) : 64);
-    for (int b = 0; b < nb; ++b)
-      if (S[(j0 + b) * ld + c] != T(0) && j0 + b != c) word |= 1ull << b;
-    G[c * nw + w] = word;
-  }
+  for (int64_t w = blockIdx.y; w < nw; w += gridDim.y) G[c * nw + w] = mc_adj_dense_word(S, ld, m, c, w);
 }
 
 // degree of every vertex: one wave per row
-__global__ __launch_bounds__(256) void k_mc_degree(const uint64_t* __restrict__ G, int64_t nw, int64_t m,
-                                                   int32_t* __restrict__ deg) {
-  const int lane = threadIdx.x & 63;
-  const int64_t v = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (v >= m) return;
+__device__ __forceinline__ void mc_degree_row(const uint64_t* __restrict__ G, int64_t nw, int64_t v,
+                                              int32_t* __restrict__ deg, int lane) {
   int d = 0;
   for (int64_t w = lane; w < nw; w += 64) d += __popcll(G[v * nw + w]);
   d = mc_wave_sum(d);
   if (lane == 0) deg[v] = d;
+}
+__global__ __launch_bounds__(256) void k_mc_degree(const uint64_t* __restrict__ G, int64_t nw, int64_t m,
+                                                   int32_t* __restrict__ deg) {
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (v >= m) return;
+  mc_degree_row(G, nw, v, deg, threadIdx.x & 63);
 }
 
 // ---- core numbers: level-synchronous peeling (Batagelj-Zaversnik levels), one workgroup -------------------------
@@ -166,14 +203,17 @@ __global__ __launch_bounds__(256) void k_mc_degree(const uint64_t* __restrict__ 
 // least alive degree. The result is the core number of every vertex, whatever the order within a round. The
 // alive set lives in LDS for the launch and in `alive_g` between launches; `deg` is the working degree (updated
 // by atomics, read with L1-bypassing loads); the launch returns after `budget` row-word operations at a round's end.
-__global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(const uint64_t* __restrict__ G, int64_t nw,
-                                                                  int32_t m, int32_t* deg,
-                                                                  int32_t* __restrict__ core,
-                                                                  uint64_t* __restrict__ alive_g, McCtl* ctl,
-                                                                  long long budget) {
-  extern __shared__ uint64_t mc_alive[];
-  __shared__ int32_t fr[MC_PEEL_FCAP];
-  __shared__ int32_t nf_s, mindeg_s;
+// The workgroup's LDS: mc_alive (nw words, dynamic), fr (MC_PEEL_FCAP entries), sc (nf, mindeg).
+__device__ __forceinline__ void mc_peel(const McProb& P, long long budget, uint64_t* mc_alive, int32_t* fr, int32_t* sc) {
+  const uint64_t* __restrict__ G = P.G;
+  const int64_t nw = P.nw;
+  const int32_t m = P.m;
+  int32_t* deg = P.degw;
+  int32_t* __restrict__ core = P.core;
+  uint64_t* __restrict__ alive_g = P.alive;
+  McCtl* ctl = P.ctl;
+  int32_t& nf_s = sc[0];
+  int32_t& mindeg_s = sc[1];
   const int tid = threadIdx.x;
   for (int64_t w = tid; w < nw; w += MC_PEEL_THREADS) mc_alive[w] = alive_g[w];
   int k = ctl->k, removed = ctl->removed;
@@ -231,6 +271,13 @@ __global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(const uint64_t
   }
 }
 
+__global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(McProb P, long long budget) {
+  extern __shared__ uint64_t mc_alive[];
+  __shared__ int32_t fr[MC_PEEL_FCAP];
+  __shared__ int32_t sc[2];
+  mc_peel(P, budget, mc_alive, fr, sc);
+}
+
 // ---- HEU: the greedy clique of one seed (one wave; C = the candidate bitset in LDS) ------------------------------
 // Candidates: N(v) minus the vertices with core + 1 < thr; step: take the candidate of largest core number (ties:
 // smallest index), intersect with its row. Every pick's core is at most the previous one's, so with thr <= the
@@ -275,10 +322,13 @@ __device__ int mc_greedy(const uint64_t* __restrict__ G, int64_t nw, const int32
 
 // Seeds (the host's order: core descending) taken through ctl->head; a seed whose core + 1 is below the best size
 // so far is skipped. ctl->key = max over seeds of size << 32 | ~seed.
-__global__ __launch_bounds__(64) void k_mc_heu(const uint64_t* __restrict__ G, int64_t nw,
-                                               const int32_t* __restrict__ core, const int32_t* __restrict__ seeds,
-                                               int32_t nseeds, McCtl* ctl, long long budget) {
-  extern __shared__ uint64_t mc_cand[];
+__device__ __forceinline__ void mc_heu(const McProb& P, long long budget, uint64_t* mc_cand) {
+  const uint64_t* __restrict__ G = P.G;
+  const int64_t nw = P.nw;
+  const int32_t* __restrict__ core = P.core;
+  const int32_t* __restrict__ seeds = P.list;
+  const int32_t nseeds = P.nlist;
+  McCtl* ctl = P.ctl;
   const int lane = threadIdx.x;
   long long work = 0;
   while (work < budget) {
@@ -295,12 +345,20 @@ __global__ __launch_bounds__(64) void k_mc_heu(const uint64_t* __restrict__ G, i
   }
 }
 
-// the clique of one seed (thr = 0), written to out[0..size)
-__global__ __launch_bounds__(64) void k_mc_heu_one(const uint64_t* __restrict__ G, int64_t nw,
-                                                   const int32_t* __restrict__ core, int32_t v, int32_t* out) {
+__global__ __launch_bounds__(64) void k_mc_heu(McProb P, long long budget) {
   extern __shared__ uint64_t mc_cand[];
+  mc_heu(P, budget, mc_cand);
+}
+
+// the clique of one seed (thr = 0), written to out[0..size)
+__device__ __forceinline__ void mc_heu_one(const McProb& P, uint64_t* mc_cand) {
   long long work = 0;
-  mc_greedy(G, nw, core, v, 0, mc_cand, out, work, threadIdx.x);
+  mc_greedy(P.G, P.nw, P.core, P.seed, 0, mc_cand, P.out, work, threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_mc_heu_one(McProb P) {
+  extern __shared__ uint64_t mc_cand[];
+  mc_heu_one(P, mc_cand);
 }
 
 // ---- EXACT: bitset branch and bound, one wave per root ----------------------------------------------------------
@@ -317,18 +375,22 @@ __global__ __launch_bounds__(64) void k_mc_heu_one(const uint64_t* __restrict__ 
 // The incumbent starts at (heu, 0xFFFFFFFF): only cliques larger than HEU's are searched for.
 // A slot (= workgroup) keeps its root, depth, path and stack between launches; recs[slot] holds the clique of the
 // last key it raised. LDS: Q, R (the colouring's bitsets).
-__global__ __launch_bounds__(64) void k_mc_exact(const uint64_t* __restrict__ G, int64_t nw,
-                                                 const int32_t* __restrict__ core, const int32_t* __restrict__ pos,
-                                                 const int32_t* __restrict__ roots, int32_t nroots, int32_t heu,
-                                                 McCtl* ctl, McSlot* slots, uint64_t* __restrict__ arena,
-                                                 int32_t* __restrict__ paths, int32_t* __restrict__ recs, int32_t D,
-                                                 long long budget) {
-  extern __shared__ uint64_t mc_lds[];
+// `slot` is the slot's index among its problem's; mc_lds holds 2 nw words.
+__device__ __forceinline__ void mc_exact(const McProb& P_, int slot, long long budget, uint64_t* mc_lds) {
+  const uint64_t* __restrict__ G = P_.G;
+  const int64_t nw = P_.nw;
+  const int32_t* __restrict__ core = P_.core;
+  const int32_t* __restrict__ pos = P_.pos;
+  const int32_t* __restrict__ roots = P_.list;
+  const int32_t nroots = P_.nlist, heu = P_.heu, D = P_.D;
+  McCtl* ctl = P_.ctl;
+  uint64_t* __restrict__ arena = P_.arena;
+  int32_t* __restrict__ paths = P_.paths;
+  int32_t* __restrict__ recs = P_.recs;
   uint64_t* Q = mc_lds;
   uint64_t* R = mc_lds + nw;
   const int lane = threadIdx.x;
-  const int slot = blockIdx.x;
-  McSlot* sl = slots + slot;
+  McSlot* sl = P_.slots + slot;
   uint64_t* stk = arena + static_cast<int64_t>(slot) * D * nw;
   int32_t* path = paths + static_cast<int64_t>(slot) * (D + 1);  // path[0] = root, path[1 + L] = branch of level L
   int root = sl->root, L = sl->depth;
@@ -466,6 +528,11 @@ __global__ __launch_bounds__(64) void k_mc_exact(const uint64_t* __restrict__ G,
     atomicAdd(&ctl->roots_searched, searched);
     atomicAdd(&ctl->roots_pruned, pruned);
   }
+}
+
+__global__ __launch_bounds__(64) void k_mc_exact(McProb P, long long budget) {
+  extern __shared__ uint64_t mc_lds[];
+  mc_exact(P, static_cast<int>(blockIdx.x), budget, mc_lds);
 }
 
 }  // namespace clipper_hip

@@ -12,7 +12,8 @@
  * solveAsMSRCSDR runs the semidefinite relaxation of every problem of the last solve in one batched call
  * (clipper_hip_batch_sdp, DESIGN.md 11 "Batches"; every problem needs m <= 128). Its dual bound certifies the
  * dense-cluster answers: -sdpSolutions()[i].dobj is an upper bound on the optimum of the problem solve() attacks
- * locally.
+ * locally. solveAsMaximumClique finds the maximum clique of every problem's consistency graph in one batched call
+ * (clipper_hip_batch_max_clique, DESIGN.md 9 "Batches").
  */
 #pragma once
 
@@ -57,6 +58,13 @@ class CLIPPERBatch {
   /// getSelectedAssociations(i) follows it. The solver state is untouched: a later solve() gives the same results.
   /// Throws std::logic_error before any solve, std::runtime_error when a problem has m > 128 (the message names it).
   std::vector<Solution> solveAsMSRCSDR(const sdp::Params& params = sdp::Params{});
+  /// CLIPPER::solveAsMaximumClique for every problem of the last solve(), in one batched call
+  /// (clipper_hip_batch_max_clique, DESIGN.md 9 "Batches"): problems up to m = 2048 side by side, larger ones one by
+  /// one afterwards. Solution i is what clipper.cpp:92-96 leaves (nodes ascending, u = 0, score = -1, ifinal = 0; t:
+  /// the whole call's), its nodes those of a lone CLIPPER::solveAsMaximumClique; getSelectedAssociations(i) follows it.
+  /// params.time_limit bounds the whole call; params.threads is ignored; params.verbose prints one line per problem.
+  /// The solver state is untouched. Throws std::logic_error before any solve.
+  std::vector<Solution> solveAsMaximumClique(const maxclique::Params& params = maxclique::Params{});
   /// the relaxations of the last solveAsMSRCSDR (X, lambdas, evec1, thr, nodes, iters, pobj, dobj, times)
   const std::vector<sdp::Solution>& sdpSolutions() const { return sdp_; }
 

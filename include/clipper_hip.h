@@ -591,6 +591,31 @@ int clipper_hip_batch_get_split(const clipper_hip_batch_t* b, double* fill_ms, d
  * CLIPPER_HIP_E_STATE before any solve; CLIPPER_HIP_E_SCOPE naming the first problem with m > CLIPPER_HIP_SDP_MAX_N
  * (nothing has run then, and the batch stays usable). */
 int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* params, clipper_sdp_info_t* infos);
+/* The maximum clique (clipper_hip_max_clique, DESIGN.md 9 "Batches") of every problem of the batch's last solve call,
+ * side by side in a handful of launches: the graph of problem i is the pattern of its child's M, read from the store
+ * that holds it (the slices where they are valid, else the dense store). infos: one record per problem of that solve
+ * (may be NULL). Per problem and for every method the node list, max_core, heuristic_size, edges and num_nodes equal
+ * those of clipper_hip_max_clique on a lone context scored from the same inputs on the same storage, whatever else
+ * the batch holds, wherever the problem stands in it and however the launches are cut; roots_searched, roots_pruned
+ * and bb_nodes depend on the schedule and are only reported; seconds is the wall time of the whole call. The clique
+ * (ascending) becomes the problem's node list: clipper_hip_batch_get_nodes / _get_selected_associations return it,
+ * clipper_hip_batch_get_solution's num_nodes is its size; nothing the solver keeps is touched.
+ * Routes: problems with m <= 2048 (the batch's resident limit, on all four storages) run in the batched launches,
+ * out of ONE device slab whose size is checked against the free memory before anything runs (CLIPPER_HIP_E_NOMEM
+ * with the figure; the batch stays usable); larger problems run afterwards, one by one, as clipper_hip_max_clique on
+ * their child context.
+ * time_limit_s > 0 bounds the whole call, checked between launches: problems still searching when it runs out return
+ * their best clique so far with timed_out = 1 (HEU's first launch always leaves one, as in the lone call), problems
+ * that had finished keep timed_out = 0 and their exact result. A problem of the lone route gets the time that remains; when
+ * none remains it still builds its graph and core numbers and makes ONE launch of HEU (the least a call does) and
+ * returns that launch's best clique with timed_out = 1 (unless that launch finished HEU and no search was left).
+ * CLIPPER_HIP_E_STATE before any solve, CLIPPER_HIP_E_INVALID for an unknown method; a batch of 0 problems returns 0. */
+int clipper_hip_batch_max_clique(clipper_hip_batch_t* b, int method, double time_limit_s,
+                                 clipper_maxclique_info_t* infos /* one per problem of the last solve, or NULL */);
+/* The last clipper_hip_batch_max_clique: kernel launches of the batched route, problems that ran in them, problems
+ * that ran alone. Any pointer may be NULL. */
+int clipper_hip_batch_max_clique_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched,
+                                       int32_t* n_alone);
 /* Problem i of the last clipper_hip_batch_sdp: X and Y (m x m), lambdas (m, ascending), evec1 (m); any may be NULL.
  * X and Y stay on the device until the next solve or relaxation of the batch. Returns m or <0. */
 int clipper_hip_batch_get_sdp(const clipper_hip_batch_t* b, int32_t i, double* X_out, double* Y_out,
