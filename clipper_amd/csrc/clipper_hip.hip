@@ -1,6 +1,6 @@
 // clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_state.hpp (context, shards,
 // RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver),
-// host_solve.hpp (the solve of one context), host_mcbatch.hpp (the maximum cliques of a batch), host_matrix_io.hpp
+// host_solve.hpp (the solve of one context), host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp
 // (the fills, matrix set / get, mat-vecs, nearest neighbours; included last: it holds its kernels' place in the code
 // object), host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
@@ -50,13 +50,12 @@ using namespace clipper_hip;
 #include "host_rv_resident.hpp"
 #include "host_subproblem.hpp"
 #include "host_registration.hpp"
-#include "host_maxclique.hpp"
 #include "host_sdp.hpp"
 #include "host_sdpbatch.hpp"
 #include "host_solve.hpp"
 #include "host_custom_invariant.hpp"
 #include "host_batchsolve.hpp"
-#include "host_mcbatch.hpp"
+#include "host_maxclique.hpp"
 #include "host_matrix_io.hpp"
 
 extern "C" {
@@ -506,7 +505,7 @@ void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
   if (b->dstage) hipFree(b->dstage);
   if (b->hfill) hipHostFree(b->hfill);
   if (b->dfill) hipFree(b->dfill);
-  if (b->hmc) hipHostFree(b->hmc);
+  if (b->hmc.p) hipHostFree(b->hmc.p);
   for (hipEvent_t e : b->ev_fill)
     if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);

@@ -51,9 +51,8 @@ struct clipper_hip_batch {
   double t_fill_begin = 0.0, t_fill_launch = 0.0, t_fill_build = 0.0;  // kind 3: the parts of t_fill (ms)
   bool solved = false;                  // a solve call has succeeded: `res` and the children describe its problems
   std::unique_ptr<SdpBatchState> sdp;   // the last clipper_hip_batch_sdp (host_sdpbatch.hpp), until the next call
-  int mc_launches = 0, mc_batched = 0, mc_alone = 0;  // the last clipper_hip_batch_max_clique (host_mcbatch.hpp)
-  uint8_t* hmc = nullptr;  // its pinned staging buffer, kept from call to call
-  size_t hmc_cap = 0;
+  int mc_launches = 0, mc_batched = 0, mc_alone = 0;  // the last clipper_hip_batch_max_clique (host_maxclique.hpp)
+  PinnedBuf hmc;  // its staging buffer, kept from call to call
 };
 
 namespace {

@@ -1,7 +1,19 @@
-// host_maxclique.hpp — the maximum-clique solver (clipper_hip_max_clique, clipper_hip_core_numbers; kernels in
-// k_maxclique.hip.h, semantics in DESIGN.md section 9): the source store of C, the buffers of one call, the launch
-// loops with the time limit between launches, the node list.
-// Part of clipper_hip.hip (one translation unit; included there, in order).
+// host_maxclique.hpp — the maximum-clique solver (clipper_hip_max_clique, clipper_hip_core_numbers,
+// clipper_hip_batch_max_clique; kernels in k_maxclique.hip.h, the plan in host_mcplan.hpp, semantics in DESIGN.md
+// section 9). Part of clipper_hip.hip (one translation unit; included there, after host_batchsolve.hpp).
+//
+// mc_run is the one driver: a lone call is a call on one problem. It
+//   1. plans the graph part for all its problems (G, alive, deg, degw, core, pos, lists, out, McCtl and the tables),
+//      checks it against the free memory and allocates it as ONE slab; the host's side of it is the caller's pinned
+//      staging buffer,
+//   2. builds every adjacency from the store that holds C, the degrees, and peels: ONE workgroup per unfinished
+//      problem and launch,
+//   3. reads all deg and core back in ONE copy, sorts seeds and roots, writes all lists in ONE copy per phase,
+//   4. runs HEU and the regeneration of the winning cliques; then, for the problems that go on to EXACT, plans and
+//      allocates the search part from each one's K and roots, and runs EXACT over its slot table. After each launch
+//      ONE copy of the McCtl array, the compaction of the work list to the unfinished problems, and the time limit.
+// The number of copies and resets between launches does not depend on the number of problems, and per problem the
+// results are a function of the graph alone.
 #pragma once
 
 #include "host_mcplan.hpp"
@@ -12,52 +24,42 @@ constexpr int64_t MC_MAX_M = 655360;           // the EXACT kernel's two LDS bit
 constexpr long long MC_PEEL_BUDGET = 1ll << 24;  // row-word operations per peel launch (~ms)
 constexpr long long MC_WAVE_BUDGET = 1ll << 18;  // row-word operations per wave and HEU / EXACT launch (~tens of ms)
 constexpr int MC_WAVES_PER_CU = 8;
+constexpr int MC_PEEL_ONLY = -1;  // mc_run's method for clipper_hip_core_numbers: stop after the peel, keep `core`
 
-// Device buffers of one call (freed when it returns: the adjacency alone is m^2 / 8 bytes).
-struct McBufs {
-  uint64_t* G = nullptr;
-  uint64_t* alive = nullptr;
-  int32_t *deg = nullptr, *degw = nullptr, *core = nullptr, *pos = nullptr, *list = nullptr, *out = nullptr;
-  McCtl* ctl = nullptr;
-  McSlot* slots = nullptr;
-  uint64_t* arena = nullptr;
-  int32_t *paths = nullptr, *recs = nullptr;
-  ~McBufs() {
-    for (void* p : {static_cast<void*>(G), static_cast<void*>(alive), static_cast<void*>(deg), static_cast<void*>(degw),
-                    static_cast<void*>(core), static_cast<void*>(pos), static_cast<void*>(list), static_cast<void*>(out),
-                    static_cast<void*>(ctl), static_cast<void*>(slots), static_cast<void*>(arena),
-                    static_cast<void*>(paths), static_cast<void*>(recs)})
-      if (p) hipFree(p);
+static_assert(sizeof(McItem) == sizeof(clipper_mc_plan::Item), "the plan's table rows are the kernels'");
+static_assert(sizeof(McProb) % 8 == 0 && sizeof(McCtl) % 8 == 0 && sizeof(McSlot) % 8 == 0 && sizeof(McAdjSrc) % 8 == 0,
+              "8-byte tables");
+
+// a device slab and the pinned mirror of its host-visible tail [host_begin, bytes)
+struct McSlab {
+  uint8_t *dev = nullptr, *host = nullptr;
+  size_t host_begin = 0;
+  ~McSlab() {
+    if (dev) hipFree(dev);
   }
+  int alloc(size_t bytes) {
+    if (hipMalloc(reinterpret_cast<void**>(&dev), std::max<size_t>(bytes, 8)) != hipSuccess) {
+      dev = nullptr;
+      (void)hipGetLastError();
+      return fail(CLIPPER_HIP_E_NOMEM, "max clique: device allocation of %zu bytes failed", bytes);
+    }
+    return 0;
+  }
+  template <typename T>
+  T* D(size_t off) const { return reinterpret_cast<T*>(dev + off); }
+  template <typename T>
+  T* H(size_t off) const { return reinterpret_cast<T*>(host + (off - host_begin)); }  // (off >= host_begin)
 };
 
-// the one descriptor of a lone call (k_maxclique.hip.h): the buffers allocated so far
-McProb mc_prob(const McBufs& b, int64_t nw, int64_t m) {
-  McProb p{};
-  p.G = b.G;
-  p.nw = nw;
-  p.m = static_cast<int32_t>(m);
-  p.degw = b.degw;
-  p.core = b.core;
-  p.alive = b.alive;
-  p.pos = b.pos;
-  p.list = b.list;
-  p.out = b.out;
-  p.ctl = b.ctl;
-  p.slots = b.slots;
-  p.arena = b.arena;
-  p.paths = b.paths;
-  p.recs = b.recs;
-  return p;
-}
+struct McResult {
+  clipper_maxclique_info_t info{};
+  std::vector<int32_t> nodes;  // ascending
+  std::vector<int32_t> core;   // MC_PEEL_ONLY
+};
 
-template <typename T>
-int mc_alloc(T*& p, size_t count) {
-  if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    p = nullptr;
-    (void)hipGetLastError();
-    return fail(CLIPPER_HIP_E_NOMEM, "max clique: device allocation of %zu bytes failed", count * sizeof(T));
-  }
+int mc_check_method(int method) {  // (a caller's method; the driver is also run with MC_PEEL_ONLY)
+  if (method != CLIPPER_HIP_MC_EXACT && method != CLIPPER_HIP_MC_HEU && method != CLIPPER_HIP_MC_KCORE)
+    return fail(CLIPPER_HIP_E_INVALID, "max clique: unknown method %d", method);
   return 0;
 }
 
@@ -69,204 +71,420 @@ int mc_check_scope(const Ctx* h) {
   return 0;
 }
 
-// The adjacency bitsets from the store that holds C, the degrees, and the core numbers (device) of one call.
-int mc_graph_and_cores(Ctx* h, McBufs& b, int64_t nw, std::vector<int32_t>& deg, std::vector<int32_t>& core) {
-  Shard& s = h->sh[0];
-  const int64_t m = h->m;
-  HIPCHK(hipSetDevice(s.device));
-  size_t freeb = 0, totalb = 0;
-  HIPCHK(hipMemGetInfo(&freeb, &totalb));
-  const size_t gbytes = static_cast<size_t>(m) * static_cast<size_t>(nw) * 8;
-  if (gbytes + (64u << 20) > freeb)
-    return fail(CLIPPER_HIP_E_NOMEM, "max clique: the adjacency bitsets need %zu bytes, %zu are free", gbytes, freeb);
-  if (int rc = mc_alloc(b.G, static_cast<size_t>(m) * nw)) return rc;
-  if (int rc = mc_alloc(b.alive, static_cast<size_t>(nw))) return rc;
-  for (int32_t** p : {&b.deg, &b.degw, &b.core}) if (int rc = mc_alloc(*p, static_cast<size_t>(m))) return rc;
-  if (int rc = mc_alloc(b.ctl, 1)) return rc;
-  // C: the slices of M (pattern), else the explicit dense C, else the dense store of M (pattern)
-  if (h->csc_valid && !h->explicitC) {
-    HIPCHK(hipMemsetAsync(b.G, 0, gbytes, s.stream));
-    const int64_t nsl = static_cast<int64_t>(s.s_ncg) * s.s_nchunks;
-    dim3 grid(static_cast<unsigned>(ceil_div(nsl, 4))), block(256);
-    dispatch_vt(h, [&](auto t) {  // (the value type; h->compressed says slices)
-      hipLaunchKernelGGL((k_mc_adj_slices<decltype(t), SL_H>), grid, block, 0, s.stream, slice_view(h, s), b.G, nw, m);
-    });
-  } else {
-    const void* src = h->explicitC ? s.Cs : s.S;
-    if (!src) return fail(CLIPPER_HIP_E_STATE, "max clique: the store of C is not on the device");
-    dim3 grid(static_cast<unsigned>(ceil_div(m, 256)), static_cast<unsigned>(std::min<int64_t>(nw, 65535))), block(256);
-    dispatch_vt(h, [&](auto t) {
-      using T = decltype(t);
-      hipLaunchKernelGGL(k_mc_adj_dense<T>, grid, block, 0, s.stream, static_cast<const T*>(src), h->W, m, nw, b.G);
-    });
-  }
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_mc_degree, dim3(static_cast<unsigned>(ceil_div(m, 4))), dim3(256), 0, s.stream, b.G, nw, m, b.deg);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(b.degw, b.deg, static_cast<size_t>(m) * 4, hipMemcpyDeviceToDevice, s.stream));
-  HIPCHK(hipMemsetAsync(b.alive, 0xff, static_cast<size_t>(nw) * 8, s.stream));
-  HIPCHK(hipMemsetAsync(b.ctl, 0, sizeof(McCtl), s.stream));
-  const int lds = static_cast<int>(nw * 8);
-  if (lds > 64 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_core_peel), s.device, lds);
-  McCtl c{};
-  int64_t launches = 0;
-  do {
-    if (++launches > m + 1) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: the core peel made no progress");
-    hipLaunchKernelGGL(k_mc_core_peel, dim3(1), dim3(MC_PEEL_THREADS), lds, s.stream, mc_prob(b, nw, m), MC_PEEL_BUDGET);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
-    HIPCHK(hipStreamSynchronize(s.stream));
-  } while (c.removed < m);
-  deg.resize(static_cast<size_t>(m));
-  core.resize(static_cast<size_t>(m));
-  HIPCHK(hipMemcpy(deg.data(), b.deg, static_cast<size_t>(m) * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(core.data(), b.core, static_cast<size_t>(m) * 4, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_info_t* info) {
+// The maximum cliques (or, MC_PEEL_ONLY, the core numbers) of the problems of `cs`, which passed mc_check_scope (and
+// `method` mc_check_method) and share a device, a value type and the stream `st`. R[k] is cs[k]'s result; `launches`
+// counts the kernel launches. An error that is one problem's leaves its index in `fault`.
+int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStream_t st, int device, PinnedBuf& stage,
+           int& launches, std::vector<McResult>& R, size_t& fault) {
+  namespace plan = clipper_mc_plan;
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   auto elapsed = [&] { return std::chrono::duration<double>(clk::now() - t0).count(); };
   auto out_of_time = [&] { return time_limit_s > 0 && elapsed() >= time_limit_s; };
-  if (method != CLIPPER_HIP_MC_EXACT && method != CLIPPER_HIP_MC_HEU && method != CLIPPER_HIP_MC_KCORE)
-    return fail(CLIPPER_HIP_E_INVALID, "max clique: unknown method %d", method);
-  if (int rc = mc_check_scope(h)) return rc;
-  Shard& s = h->sh[0];
-  const int64_t m = h->m, nw = ceil_div(m, 64);
-  clipper_maxclique_info_t I{};
-  McBufs b;
-  std::vector<int32_t> deg, core;
-  if (int rc = mc_graph_and_cores(h, b, nw, deg, core)) return rc;
-  int64_t dsum = 0;
-  int K = 0;
-  for (int64_t v = 0; v < m; ++v) {
-    dsum += deg[static_cast<size_t>(v)];
-    K = std::max(K, core[static_cast<size_t>(v)]);
-  }
-  I.edges = dsum / 2;
-  I.max_core = K;
-  std::vector<int32_t> nodes;
-  const int lds1 = static_cast<int>(nw * 8);
-  const int nwaves = std::max(1, h->cus) * MC_WAVES_PER_CU;
-  if (method == CLIPPER_HIP_MC_KCORE) {
-    // ROBIN: every vertex of core number K (an edgeless graph: all of them)
-    for (int64_t v = 0; v < m; ++v)
-      if (core[static_cast<size_t>(v)] == K) nodes.push_back(static_cast<int32_t>(v));
-  } else if (I.edges > 0) {
-    // ---- HEU: seeds by core descending, index ascending
-    std::vector<int32_t> seeds(static_cast<size_t>(m));
-    clipper_mc_plan::seed_order(core.data(), m, seeds.data());
-    if (int rc = mc_alloc(b.list, static_cast<size_t>(m))) return rc;
-    if (int rc = mc_alloc(b.out, static_cast<size_t>(K) + 2)) return rc;
-    HIPCHK(hipMemcpy(b.list, seeds.data(), static_cast<size_t>(m) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(b.ctl, 0, sizeof(McCtl)));
-    if (lds1 > 64 * 1024) {
-      raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_heu), s.device, lds1);
-      raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_heu_one), s.device, lds1);
-    }
-    McCtl c{};
-    McProb pr = mc_prob(b, nw, m);
-    pr.nlist = static_cast<int32_t>(m);
-    do {
-      hipLaunchKernelGGL(k_mc_heu, dim3(static_cast<unsigned>(nwaves)), dim3(64), lds1, s.stream, pr, MC_WAVE_BUDGET);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
-      HIPCHK(hipStreamSynchronize(s.stream));
-      if (c.head < m && out_of_time()) {
-        I.timed_out = 1;
-        break;
-      }
-    } while (c.head < m);
-    const int heu = static_cast<int>(c.key >> 32);
-    const int seed = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(c.key & 0xFFFFFFFFull));
-    if (heu < 2 || heu > K + 1 || seed < 0 || seed >= m)
-      return fail(CLIPPER_HIP_E_INTERNAL, "max clique: HEU's record (size %d, seed %d) is not valid", heu, seed);
-    pr.seed = seed;
-    hipLaunchKernelGGL(k_mc_heu_one, dim3(1), dim3(64), lds1, s.stream, pr);
+  const size_t nb = cs.size();
+  fault = nb;
+  R.assign(nb, McResult{});
+  if (nb == 0) return 0;
+  HIPCHK(hipSetDevice(device));
+
+  // ---- 1. the graph part -----------------------------------------------------------------------------------------
+  std::vector<int32_t> ms(nb);
+  for (size_t k = 0; k < nb; ++k) ms[k] = static_cast<int32_t>(cs[k]->m);
+  const int64_t cap = static_cast<int64_t>(std::max(1, cs[0]->cus)) * MC_WAVES_PER_CU;
+  const plan::GraphPlan L = plan::make_graph_plan(ms, cap, sizeof(McProb), sizeof(McCtl), sizeof(McAdjSrc));
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  if (L.bytes + (64u << 20) > free_b)
+    return fail(CLIPPER_HIP_E_NOMEM, "max clique: %zu problems need a slab of %zu bytes, %zu are free", nb, L.bytes, free_b);
+  McSlab g, x;  // the graph part, the search part
+  if (int rc = g.alloc(L.bytes)) return rc;
+  const size_t ghost = L.bytes - L.host_begin;
+  if (int rc = pinned_grow(stage, ghost + plan::search_host_bound(cap, nb, sizeof(McSlot)))) return rc;
+  g.host = stage.p;
+  g.host_begin = L.host_begin;
+  x.host = stage.p + ghost;
+  auto up = [&](const McSlab& s, size_t begin, size_t end) -> int {    // host -> device, [begin, end)
+    if (end > begin)
+      HIPCHK(hipMemcpyAsync(s.D<uint8_t>(begin), s.H<uint8_t>(begin), end - begin, hipMemcpyHostToDevice, st));
+    return 0;
+  };
+  auto down = [&](const McSlab& s, size_t begin, size_t end) -> int {  // device -> host, and wait
+    if (end > begin)
+      HIPCHK(hipMemcpyAsync(s.H<uint8_t>(begin), s.D<uint8_t>(begin), end - begin, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  };
+  McProb* probs = g.H<McProb>(L.probs);
+  McCtl* ctl = g.H<McCtl>(L.ctl);
+  const McProb* dprobs = g.D<McProb>(L.probs);
+  McCtl* dctl = g.D<McCtl>(L.ctl);
+  const McAdjSrc* dsrc = g.D<McAdjSrc>(L.src);
+  const int32_t* dwork = g.D<int32_t>(L.work);
+  const size_t ctl_end = L.ctl + nb * sizeof(McCtl);
+  const int lds1 = static_cast<int>(L.nw_max * 8);
+  if (lds1 > 64 * 1024)
+    for (const void* f : {reinterpret_cast<const void*>(k_mc_core_peel), reinterpret_cast<const void*>(k_mc_heu),
+                          reinterpret_cast<const void*>(k_mc_heu_one)})
+      raise_dynamic_lds(f, device, lds1);
+  if (2 * lds1 > 64 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_exact), device, 2 * lds1);
+  auto launched = [&]() -> int {
     HIPCHK(hipGetLastError());
-    nodes.resize(static_cast<size_t>(heu));
-    HIPCHK(hipMemcpyAsync(nodes.data(), b.out, static_cast<size_t>(heu) * 4, hipMemcpyDeviceToHost, s.stream));
-    HIPCHK(hipStreamSynchronize(s.stream));
-    I.heuristic_size = heu;
-    if (method == CLIPPER_HIP_MC_EXACT && heu < K + 1 && !I.timed_out) {
-      // ---- EXACT: roots ordered by (core, degree, index); those that can hold a clique larger than HEU's,
-      // taken from the end of that order (the largest bound first)
-      std::vector<int32_t> pos(static_cast<size_t>(m)), roots;
-      clipper_mc_plan::root_order(core.data(), deg.data(), m, heu, pos.data(), roots);
-      I.roots_pruned = m - static_cast<int64_t>(roots.size());
-      const int D = K + 1;  // stack levels: a clique has at most K + 1 vertices
-      size_t freeb = 0, totalb = 0;
-      HIPCHK(hipMemGetInfo(&freeb, &totalb));
-      const size_t per_slot = static_cast<size_t>(D) * nw * 8 + 2 * static_cast<size_t>(D + 1) * 4 + sizeof(McSlot);
-      const size_t room = std::min<size_t>(freeb / 4, size_t(4) << 30);
-      const int nslots = static_cast<int>(std::min<size_t>(static_cast<size_t>(nwaves), room / per_slot));
-      if (nslots < 1)
-        return fail(CLIPPER_HIP_E_NOMEM, "max clique: one search stack needs %zu bytes, %zu are free", per_slot, freeb);
-      if (int rc = mc_alloc(b.pos, static_cast<size_t>(m))) return rc;
-      if (int rc = mc_alloc(b.slots, static_cast<size_t>(nslots))) return rc;
-      if (int rc = mc_alloc(b.arena, static_cast<size_t>(nslots) * D * nw)) return rc;
-      if (int rc = mc_alloc(b.paths, static_cast<size_t>(nslots) * (D + 1))) return rc;
-      if (int rc = mc_alloc(b.recs, static_cast<size_t>(nslots) * (D + 1))) return rc;
-      HIPCHK(hipMemcpy(b.pos, pos.data(), static_cast<size_t>(m) * 4, hipMemcpyHostToDevice));
-      if (!roots.empty())
-        HIPCHK(hipMemcpy(b.list, roots.data(), roots.size() * 4, hipMemcpyHostToDevice));
-      std::vector<McSlot> hs(static_cast<size_t>(nslots));
-      for (auto& x : hs) x = McSlot{-1, 0, 0, 0, 0ull};
-      HIPCHK(hipMemcpy(b.slots, hs.data(), hs.size() * sizeof(McSlot), hipMemcpyHostToDevice));
-      McCtl c0{};
-      c0.key = (static_cast<unsigned long long>(heu) << 32) | 0xFFFFFFFFull;
-      HIPCHK(hipMemcpy(b.ctl, &c0, sizeof(McCtl), hipMemcpyHostToDevice));
-      const int lds2 = 2 * lds1;
-      if (lds2 > 64 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_exact), s.device, lds2);
-      const int32_t nroots = static_cast<int32_t>(roots.size());
-      pr = mc_prob(b, nw, m);
-      pr.nlist = nroots;
-      pr.heu = static_cast<int32_t>(heu);
-      pr.D = static_cast<int32_t>(D);
-      while (true) {
-        HIPCHK(hipMemsetAsync(&b.ctl->active, 0, sizeof(int32_t), s.stream));
-        hipLaunchKernelGGL(k_mc_exact, dim3(static_cast<unsigned>(nslots)), dim3(64), lds2, s.stream, pr, MC_WAVE_BUDGET);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(McCtl), hipMemcpyDeviceToHost, s.stream));
-        HIPCHK(hipStreamSynchronize(s.stream));
-        if (c.head >= nroots && c.active == 0) break;
-        if (out_of_time()) {
-          I.timed_out = 1;
-          break;
-        }
+    ++launches;
+    return 0;
+  };
+
+  // ---- 2. descriptors (one copy), adjacency, degrees, the peel -------------------------------------------------------
+  std::memset(g.H<uint8_t>(L.up_begin), 0, L.up_end - L.up_begin);
+  int64_t nslices = 0;  // the most slices a problem has
+  bool any_slices = false, any_dense = false;
+  for (size_t k = 0; k < nb; ++k) {
+    const Ctx* c = cs[k];
+    const Shard& s = c->sh[0];
+    const plan::GraphRegions& r = L.at[k];
+    McProb p{};
+    p.G = g.D<uint64_t>(r.G);
+    p.nw = r.nw;
+    p.m = ms[k];
+    p.degw = g.D<int32_t>(r.degw);
+    p.core = g.D<int32_t>(r.core);
+    p.alive = g.D<uint64_t>(r.alive);
+    p.pos = g.D<int32_t>(r.pos);
+    p.list = g.D<int32_t>(r.list);
+    p.out = g.D<int32_t>(r.out) + 1;  // (out[-1]: the count k_mc_collect leaves)
+    p.ctl = dctl + k;
+    probs[k] = p;
+    // C: the slices of M (pattern), else the explicit dense C, else the dense store of M (pattern)
+    McAdjSrc a{};
+    if (c->csc_valid && !c->explicitC) {
+      a.M = slice_view(c, s);
+      any_slices = true;
+      nslices = std::max<int64_t>(nslices, static_cast<int64_t>(s.s_ncg) * s.s_nchunks);
+    } else {
+      a.S = c->explicitC ? s.Cs : s.S;
+      any_dense = true;
+      if (!a.S) {
+        fault = k;
+        return fail(CLIPPER_HIP_E_STATE, "max clique: the store of C is not on the device");
       }
-      if (c.overflow) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: a branch went deeper than the core bound");
-      I.roots_pruned += static_cast<int64_t>(c.roots_pruned);
-      I.roots_searched = static_cast<int64_t>(c.roots_searched);
-      I.bb_nodes = static_cast<int64_t>(c.bb_nodes);
-      const int omega = static_cast<int>(c.key >> 32);
-      if (omega > heu) {
-        HIPCHK(hipMemcpy(hs.data(), b.slots, hs.size() * sizeof(McSlot), hipMemcpyDeviceToHost));
-        int who = -1;
-        for (int i = 0; i < nslots; ++i)
-          if (hs[static_cast<size_t>(i)].rec_key == c.key) who = i;
-        if (who < 0) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: no record holds the incumbent");
-        nodes.resize(static_cast<size_t>(omega));
-        HIPCHK(hipMemcpy(nodes.data(), b.recs + static_cast<size_t>(who) * (D + 1), static_cast<size_t>(omega) * 4,
-                         hipMemcpyDeviceToHost));
+    }
+    a.ld = c->W;
+    a.G = g.D<uint64_t>(r.G);
+    a.nw = r.nw;
+    a.m = ms[k];
+    a.deg = g.D<int32_t>(r.deg);
+    g.H<McAdjSrc>(L.src)[k] = a;
+  }
+  if (int rc = up(g, L.up_begin, ctl_end)) return rc;  // (descriptors, sources, control words; the lists come later)
+  HIPCHK(hipMemsetAsync(g.D<uint8_t>(L.alive_begin), 0xff, L.alive_bytes, st));
+  const int32_t np = static_cast<int32_t>(nb);
+  const unsigned gp = static_cast<unsigned>(std::min<size_t>(nb, 65535));  // the grid's problem dimension
+  if (any_slices) HIPCHK(hipMemsetAsync(g.D<uint8_t>(L.G_begin), 0, L.G_bytes, st));  // (the slices' ORs need it)
+  if (nslices > 0) {
+    dispatch_vt(cs[0], [&](auto t) {  // (the call's value type)
+      hipLaunchKernelGGL((k_mc_adj_slices<decltype(t), SL_H>), dim3(static_cast<unsigned>(ceil_div(nslices, 4)), gp),
+                         dim3(256), 0, st, dsrc, np);
+    });
+    if (int rc = launched()) return rc;
+  }
+  if (any_dense) {
+    dim3 grid(static_cast<unsigned>(ceil_div(L.m_max, 256)), static_cast<unsigned>(std::min<int64_t>(L.nw_max, 65535)), gp);
+    dispatch_vt(cs[0], [&](auto t) { hipLaunchKernelGGL(k_mc_adj_dense<decltype(t)>, grid, dim3(256), 0, st, dsrc, np); });
+    if (int rc = launched()) return rc;
+  }
+  hipLaunchKernelGGL(k_mc_degree, dim3(static_cast<unsigned>(ceil_div(L.m_max, 4)), gp), dim3(256), 0, st, dsrc, np);
+  if (int rc = launched()) return rc;
+  HIPCHK(hipMemcpyAsync(g.D<uint8_t>(L.degw_begin), g.D<uint8_t>(L.deg_begin), L.deg_bytes, hipMemcpyDeviceToDevice, st));
+
+  std::vector<int32_t> on_device;  // the work list the device holds
+  auto put_work = [&](const std::vector<int32_t>& list) -> int {
+    if (list == on_device) return 0;
+    std::memcpy(g.H<int32_t>(L.work), list.data(), list.size() * sizeof(int32_t));
+    on_device = list;
+    return up(g, L.work, L.work + list.size() * sizeof(int32_t));
+  };
+  std::vector<int32_t> work(nb);
+  std::iota(work.begin(), work.end(), 0);
+  for (int64_t rounds = 0; !work.empty(); ++rounds) {
+    if (rounds > L.m_max) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: the core peel made no progress");
+    if (int rc = put_work(work)) return rc;
+    hipLaunchKernelGGL(k_mc_core_peel, dim3(static_cast<unsigned>(work.size())), dim3(MC_PEEL_THREADS), lds1, st, dprobs,
+                       dwork, MC_PEEL_BUDGET);
+    if (int rc = launched()) return rc;
+    if (int rc = down(g, L.ctl, ctl_end)) return rc;
+    work = plan::compact(work, [&](int32_t k) { return ctl[k].removed >= ms[static_cast<size_t>(k)]; });
+  }
+
+  // ---- 3. deg and core in one copy; KCORE's lists, HEU's seeds ------------------------------------------------------
+  if (int rc = down(g, L.deg_begin, L.bytes)) return rc;
+  std::vector<int32_t> Kmax(nb, 0), heu(nb, 0), searching;
+  std::vector<int64_t> weight(nb, 0);
+  for (size_t k = 0; k < nb; ++k) {
+    const int32_t m = ms[k];
+    const int32_t* deg = g.H<int32_t>(L.at[k].deg);
+    const int32_t* core = g.H<int32_t>(L.at[k].core);
+    int64_t dsum = 0;
+    int K = 0;
+    for (int32_t v = 0; v < m; ++v) {
+      dsum += deg[v];
+      K = std::max(K, core[v]);
+    }
+    R[k].info.edges = dsum / 2;
+    R[k].info.max_core = Kmax[k] = K;
+    if (method == MC_PEEL_ONLY) {
+      R[k].core.assign(core, core + m);
+    } else if (method == CLIPPER_HIP_MC_KCORE) {
+      // ROBIN: every vertex of core number K (an edgeless graph: all of them)
+      for (int32_t v = 0; v < m; ++v)
+        if (core[v] == K) R[k].nodes.push_back(v);
+    } else if (dsum > 0) {
+      // HEU's seeds: by core descending, index ascending
+      plan::seed_order(core, m, g.H<int32_t>(L.at[k].list));
+      probs[k].nlist = m;
+      weight[k] = m;
+      searching.push_back(static_cast<int32_t>(k));
+    }
+  }
+
+  // one launch over the slot table of `list` (kept in `s` at `tab`), then the copy of the control array
+  std::vector<int32_t> tabled;  // the list whose slot table the device holds
+  auto launch_slots = [&](const McSlab& s, size_t tab, const std::vector<int32_t>& list, const std::vector<int32_t>& ns,
+                          bool exact) -> int {
+    size_t rows = 0;
+    for (int32_t k : list) rows += static_cast<size_t>(ns[static_cast<size_t>(k)]);
+    if (list != tabled) {
+      const std::vector<plan::Item> rws = plan::slot_rows(list, ns);
+      std::memcpy(s.H<plan::Item>(tab), rws.data(), rws.size() * sizeof(plan::Item));
+      tabled = list;
+      if (int rc = up(s, tab, tab + rws.size() * sizeof(plan::Item))) return rc;
+    }
+    if (exact) {
+      // `active` of every problem: one call
+      HIPCHK(hipMemset2DAsync(&dctl[0].active, sizeof(McCtl), 0, sizeof(int32_t), nb, st));
+      hipLaunchKernelGGL(k_mc_exact, dim3(static_cast<unsigned>(rows)), dim3(64), 2 * lds1, st, dprobs, s.D<McItem>(tab),
+                         MC_WAVE_BUDGET);
+    } else {
+      hipLaunchKernelGGL(k_mc_heu, dim3(static_cast<unsigned>(rows)), dim3(64), lds1, st, dprobs, s.D<McItem>(tab),
+                         MC_WAVE_BUDGET);
+    }
+    if (int rc = launched()) return rc;
+    return down(g, L.ctl, ctl_end);
+  };
+  auto time_out = [&](const std::vector<int32_t>& list) {  // the time limit between launches
+    if (list.empty() || !out_of_time()) return false;
+    for (int32_t k : list) R[static_cast<size_t>(k)].info.timed_out = 1;
+    return true;
+  };
+  // the cliques `out` holds after a launch over the work list `list`
+  auto take_out = [&](const std::vector<int32_t>& list, const std::vector<int32_t>& size) -> int {
+    if (int rc = down(g, L.out_begin, L.out_begin + L.out_bytes)) return rc;
+    for (int32_t k : list) {
+      const int32_t* out = g.H<int32_t>(L.at[static_cast<size_t>(k)].out) + 1;
+      R[static_cast<size_t>(k)].nodes.assign(out, out + size[static_cast<size_t>(k)]);
+    }
+    return 0;
+  };
+
+  if (!searching.empty()) {
+    // ---- 4a. HEU ---------------------------------------------------------------------------------------------------
+    std::memset(ctl, 0, nb * sizeof(McCtl));
+    if (int rc = up(g, L.up_begin, L.up_end)) return rc;
+    const std::vector<int32_t> hslots = plan::deal_slots(weight, cap);
+    std::vector<int32_t> active = searching;
+    while (!active.empty()) {
+      if (int rc = launch_slots(g, L.slot_tab, active, hslots, false)) return rc;
+      active = plan::compact(active, [&](int32_t k) { return ctl[k].head >= ms[static_cast<size_t>(k)]; });
+      if (time_out(active)) break;
+    }
+    std::vector<int32_t> exact;
+    std::vector<plan::Search> sr(nb, plan::Search{0, 0, 0});
+    std::vector<std::vector<int32_t>> roots(nb);
+    const std::vector<McCtl> after_heu(ctl, ctl + nb);
+    std::memset(ctl, 0, nb * sizeof(McCtl));
+    for (int32_t k : searching) {
+      const size_t ku = static_cast<size_t>(k);
+      clipper_maxclique_info_t& Ik = R[ku].info;
+      const int32_t m = ms[ku];
+      const unsigned long long key = after_heu[ku].key;
+      const int h = static_cast<int>(key >> 32);
+      const int seed = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key & 0xFFFFFFFFull));
+      // (every launch finishes the seeds it takes, the first of which has the largest core number, so after one
+      // launch the record holds a clique of two vertices or more, time limit or not)
+      if (h < 2 || h > Kmax[ku] + 1 || seed < 0 || seed >= m) {
+        fault = ku;
+        return fail(CLIPPER_HIP_E_INTERNAL, "max clique: HEU's record (size %d, seed %d) is not valid", h, seed);
+      }
+      heu[ku] = h;
+      Ik.heuristic_size = h;
+      probs[ku].seed = seed;
+      if (method == CLIPPER_HIP_MC_EXACT && h < Kmax[ku] + 1 && !Ik.timed_out) {
+        // EXACT: roots ordered by (core, degree, index); those that can hold a clique larger than HEU's, taken from
+        // the end of that order (the largest bound first). They replace the seeds; the incumbent starts at HEU's clique.
+        plan::root_order(g.H<int32_t>(L.at[ku].core), g.H<int32_t>(L.at[ku].deg), m, h, g.H<int32_t>(L.at[ku].pos), roots[ku]);
+        std::memcpy(g.H<int32_t>(L.at[ku].list), roots[ku].data(), roots[ku].size() * sizeof(int32_t));
+        Ik.roots_pruned = m - static_cast<int64_t>(roots[ku].size());
+        probs[ku].nlist = static_cast<int32_t>(roots[ku].size());
+        probs[ku].heu = h;
+        ctl[ku].key = (static_cast<unsigned long long>(h) << 32) | 0xFFFFFFFFull;
+        sr[ku] = plan::Search{m, Kmax[ku], static_cast<int64_t>(roots[ku].size())};
+        if (!roots[ku].empty()) exact.push_back(k);
+      }
+    }
+
+    // ---- 4b. the search part: slots dealt by roots, stacks of K + 1 levels ----------------------------------------------
+    std::vector<int32_t> xslots(nb, 0);
+    plan::SearchPlan X;
+    if (!exact.empty()) {
+      HIPCHK(hipMemGetInfo(&free_b, &total_b));
+      X = plan::make_search_plan(sr, cap, std::min<size_t>(free_b / 4, size_t(4) << 30), sizeof(McSlot));
+      if (!X.fits && nb == 1) {  // (several problems go on with one slot each)
+        fault = static_cast<size_t>(exact[0]);
+        return fail(CLIPPER_HIP_E_NOMEM, "max clique: one search stack needs %zu bytes, %zu are free",
+                    plan::slot_bytes(sr[0], sizeof(McSlot)), free_b);
+      }
+      if (x.alloc(X.bytes))
+        return fail(CLIPPER_HIP_E_NOMEM, "max clique: the search stacks of %zu problems need %zu bytes, %zu are free",
+                    exact.size(), X.bytes, free_b);
+      x.host_begin = X.host_begin;
+      for (int32_t k : exact) {
+        const size_t ku = static_cast<size_t>(k);
+        const plan::SearchRegions& r = X.at[ku];
+        probs[ku].D = r.D;
+        probs[ku].nslots = xslots[ku] = r.nslots;
+        probs[ku].slots = x.D<McSlot>(r.slots);
+        probs[ku].arena = x.D<uint64_t>(r.arena);
+        probs[ku].paths = x.D<int32_t>(r.paths);
+        probs[ku].recs = x.D<int32_t>(r.recs);
+        for (int32_t j = 0; j < r.nslots; ++j) x.H<McSlot>(r.slots)[j] = McSlot{-1, 0, 0, 0, 0ull};
+      }
+      if (int rc = up(x, X.host_begin, X.slot_tab)) return rc;
+    }
+    if (int rc = up(g, L.up_begin, L.up_end)) return rc;
+
+    // ---- 4c. the winning cliques of HEU ---------------------------------------------------------------------------------
+    if (int rc = put_work(searching)) return rc;
+    hipLaunchKernelGGL(k_mc_heu_one, dim3(static_cast<unsigned>(searching.size())), dim3(64), lds1, st, dprobs, dwork);
+    if (int rc = launched()) return rc;
+    if (int rc = take_out(searching, heu)) return rc;
+
+    // ---- 4d. EXACT -----------------------------------------------------------------------------------------------------
+    if (!exact.empty()) {
+      active = exact;
+      tabled.clear();
+      while (!active.empty()) {
+        if (int rc = launch_slots(x, X.slot_tab, active, xslots, true)) return rc;
+        active = plan::compact(active, [&](int32_t k) { return ctl[k].head >= probs[k].nlist && ctl[k].active == 0; });
+        if (time_out(active)) break;
+      }
+      std::vector<int32_t> better, omega(nb, 0);
+      for (int32_t k : exact) {
+        const size_t ku = static_cast<size_t>(k);
+        clipper_maxclique_info_t& Ik = R[ku].info;
+        if (ctl[ku].overflow) {
+          fault = ku;
+          return fail(CLIPPER_HIP_E_INTERNAL, "max clique: a branch went deeper than the core bound");
+        }
+        Ik.roots_pruned += static_cast<int64_t>(ctl[ku].roots_pruned);
+        Ik.roots_searched = static_cast<int64_t>(ctl[ku].roots_searched);
+        Ik.bb_nodes = static_cast<int64_t>(ctl[ku].bb_nodes);
+        omega[ku] = static_cast<int32_t>(ctl[ku].key >> 32);
+        if (omega[ku] > heu[ku]) better.push_back(k);
+      }
+      if (!better.empty()) {
+        if (int rc = put_work(better)) return rc;
+        hipLaunchKernelGGL(k_mc_collect, dim3(static_cast<unsigned>(better.size())), dim3(64), 0, st, dprobs, dwork);
+        if (int rc = launched()) return rc;
+        if (int rc = take_out(better, omega)) return rc;
+        for (int32_t k : better)
+          if (g.H<int32_t>(L.at[static_cast<size_t>(k)].out)[0] != omega[static_cast<size_t>(k)]) {
+            fault = static_cast<size_t>(k);
+            return fail(CLIPPER_HIP_E_INTERNAL, "max clique: no record holds the incumbent");
+          }
       }
     }
   }
-  std::sort(nodes.begin(), nodes.end());
-  h->nodes = nodes;
-  I.num_nodes = static_cast<int32_t>(nodes.size());
-  I.seconds = elapsed();
-  if (info) *info = I;
+  for (McResult& r : R) {
+    std::sort(r.nodes.begin(), r.nodes.end());
+    r.info.num_nodes = static_cast<int32_t>(r.nodes.size());
+    r.info.seconds = elapsed();
+  }
+  return 0;
+}
+
+// a lone call: the driver on {h}, with h's stream, device and staging buffer
+int mc_run_one(Ctx* h, int method, double time_limit_s, McResult& r) {
+  if (int rc = mc_check_scope(h)) return rc;
+  std::vector<McResult> R;
+  int launches = 0;
+  size_t fault = 0;
+  if (int rc = mc_run({h}, method, time_limit_s, h->sh[0].stream, h->sh[0].device, h->mc_stage, launches, R, fault)) return rc;
+  r = std::move(R[0]);
+  return 0;
+}
+
+int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_info_t* info) {
+  if (int rc = mc_check_method(method)) return rc;
+  McResult r;
+  if (int rc = mc_run_one(h, method, time_limit_s, r)) return rc;
+  h->nodes = r.nodes;
+  if (info) *info = r.info;
   return 0;
 }
 
 int core_numbers_impl(Ctx* h, int32_t* core_out) {
-  if (int rc = mc_check_scope(h)) return rc;
-  McBufs b;
-  std::vector<int32_t> deg, core;
-  if (int rc = mc_graph_and_cores(h, b, ceil_div(h->m, 64), deg, core)) return rc;
-  if (!core.empty()) std::memcpy(core_out, core.data(), core.size() * sizeof(int32_t));
+  McResult r;
+  if (int rc = mc_run_one(h, MC_PEEL_ONLY, 0.0, r)) return rc;
+  if (!r.core.empty()) std::memcpy(core_out, r.core.data(), r.core.size() * sizeof(int32_t));
+  return 0;
+}
+
+// The maximum cliques of every problem of a batch's last solve: the problems up to BATCH_MAX_M in one driver call, then
+// the larger ones one by one, each with the time that remains (a batch never holds several m^2 / 8 adjacencies at once).
+int batch_max_clique(Batch* b, int method, double time_limit_s, clipper_maxclique_info_t* infos) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  auto elapsed = [&] { return std::chrono::duration<double>(clk::now() - t0).count(); };
+  if (!b->solved) return fail(CLIPPER_HIP_E_STATE, "max clique: no batch has been solved");
+  if (int rc = mc_check_method(method)) return rc;
+  b->mc_launches = b->mc_batched = b->mc_alone = 0;
+  const size_t count = b->res.size();
+  std::vector<std::vector<int32_t>> calls(1);  // the problems of each driver call: the batched route first
+  for (size_t i = 0; i < count; ++i) {
+    if (int rc = mc_check_scope(b->kids[i])) return fail(rc, "problem %zu: %s", i, std::string(g_err).c_str());
+    if (b->kids[i]->m > clipper_mc_plan::BATCH_MAX_M) calls.push_back({static_cast<int32_t>(i)});
+    else calls[0].push_back(static_cast<int32_t>(i));
+  }
+  std::vector<McResult> all(count);
+  for (size_t c = 0; c < calls.size(); ++c) {
+    std::vector<Ctx*> cs;
+    for (int32_t i : calls[c]) cs.push_back(b->kids[static_cast<size_t>(i)]);
+    // (no time left: the smallest positive limit, so that the call stops after its first launch)
+    const double rem = time_limit_s > 0 ? std::max(time_limit_s - elapsed(), 1e-9) : 0.0;
+    std::vector<McResult> R;
+    int launches = 0;
+    size_t fault = 0;
+    if (int rc = mc_run(cs, method, rem, b->stream, b->device, b->hmc, launches, R, fault))
+      return c > 0 || fault < cs.size()  // (a larger problem's call is all its own)
+                 ? fail(rc, "problem %d: %s", calls[c][c > 0 ? 0 : fault], std::string(g_err).c_str()) : rc;
+    for (size_t k = 0; k < cs.size(); ++k) all[static_cast<size_t>(calls[c][k])] = std::move(R[k]);
+    if (c == 0) {
+      b->mc_launches = launches;
+      b->mc_batched = static_cast<int>(cs.size());
+    } else {
+      ++b->mc_alone;
+    }
+  }
+  const double secs = elapsed();
+  for (size_t i = 0; i < count; ++i) {
+    Ctx* c = b->kids[i];
+    Batch::Result& R = b->res[i];
+    R.nodes = all[i].nodes;
+    c->nodes = R.nodes;
+    R.info.num_nodes = static_cast<int32_t>(R.nodes.size());  // (what the getters size their buffers by)
+    R.sel.assign(2 * R.nodes.size(), 0);
+    selected_associations(c, R.nodes, R.sel.data());
+    all[i].info.seconds = secs;
+    if (infos) infos[i] = all[i].info;
+  }
   return 0;
 }
 

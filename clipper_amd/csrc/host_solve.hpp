@@ -32,7 +32,8 @@ void destroy_ctx(Ctx* h) {
   for (hipEvent_t e : {h->ev_poll[0], h->ev_poll[1], h->ev_aff[0], h->ev_aff[1]})
     if (e) hipEventDestroy(e);
   for (void* p : std::initializer_list<void*>{h->host_state, h->mirror, h->kind, h->u_pinned, h->xchg_send, h->xchg_recv,
-                                              h->csc_hLq, h->csc_hctl, h->csc_htotal, h->csc_hwork, h->rv_count, h->rv_desc_host})
+                                              h->csc_hLq, h->csc_hctl, h->csc_htotal, h->csc_hwork, h->rv_count, h->rv_desc_host,
+                                              h->mc_stage.p})
     if (p) hipHostFree(p);
   if (h->stamps_dev) hipFree(h->stamps_dev);
   resident_free(h);

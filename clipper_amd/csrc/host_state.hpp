@@ -50,6 +50,21 @@ int guard_fail(int code, const char* what) noexcept {
                   __LINE__);                                                          \
   } while (0)
 
+// a pinned host buffer that only grows (contents lost when it does); freed by whoever owns it
+struct PinnedBuf {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+};
+int pinned_grow(PinnedBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return 0;
+  if (b.p) HIPCHK(hipHostFree(b.p));
+  b.p = nullptr;
+  b.cap = 0;
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b.p), bytes, hipHostMallocDefault));
+  b.cap = bytes;
+  return 0;
+}
+
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -327,6 +342,7 @@ struct clipper_hip_ctx {
   std::vector<int32_t> A;  // column-major m x 2 (host copy)
   std::vector<int32_t> nodes;
   std::vector<double> u_host;  // the last solve's u on the host (rounding works on it)
+  PinnedBuf mc_stage;          // the staging buffer of this context's maximum-clique calls (host_maxclique.hpp)
 
   SolveShared* host_state = nullptr;  // pinned, 2 slots (multi-process snapshots)
   hipEvent_t ev_poll[2] = {nullptr, nullptr};

@@ -1,6 +1,6 @@
 // k_maxclique.hip.h — the maximum-clique solver behind CLIPPER::solveAsMaximumClique:
 // the adjacency of the consistency graph as row bitsets, its core numbers, the greedy clique (HEU) and the
-// bitset branch and bound (EXACT). Host side: host_maxclique.hpp.
+// bitset branch and bound (EXACT), for every problem of a call. Host side: host_maxclique.hpp, host_mcplan.hpp.
 // Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
 //
 // The graph: vertices 0..m-1, edge (i, j), i != j, exactly when C(i, j) != 0. G[i][w] bit b = edge (i, 64 w + b),
@@ -39,10 +39,10 @@ struct McSlot {
   unsigned long long rec_key;  // the key of the clique this slot recorded last (0: none)
 };
 
-// One problem as the device functions below see it: a lone call passes its one descriptor as a kernel argument, a
-// batched call (k_maxclique_batch.hip.h) keeps a table of them on the device. The host fills the fields a phase
-// reads: the peel G, nw, m, degw, core, alive, ctl; HEU also list (seeds), nlist; the regeneration seed, out;
-// EXACT list (roots), nlist, pos, heu, D and the slots' state.
+// One problem as the device functions below see it. A call keeps a table of them on the device, one row per problem
+// (a lone call: one row), and every kernel fetches its problem's row. The host fills the fields a phase reads: the
+// peel G, nw, m, degw, core, alive, ctl; HEU also list (seeds), nlist; the regeneration seed, out; EXACT list (roots),
+// nlist, pos, heu, D and the slots' state.
 struct McProb {
   const uint64_t* G;     // m rows of nw words
   int64_t nw;
@@ -56,13 +56,27 @@ struct McProb {
   int32_t heu;           // EXACT: HEU's size
   int32_t D;             // EXACT: stack levels of a slot
   int32_t seed;          // the regeneration of HEU's clique: its seed ...
-  int32_t nslots;        // EXACT: the problem's slots (read by the batch's collection of the record only)
-  int32_t* out;          // ... and where it goes
+  int32_t nslots;        // EXACT: the problem's slots (read by the collection of the record only)
+  int32_t* out;          // ... and where it goes (out[-1]: the count k_mc_collect leaves)
   McCtl* ctl;
   McSlot* slots;         // EXACT, per slot: state, D x nw words of stack, D + 1 path entries, D + 1 record entries
   uint64_t* arena;
   int32_t* paths;
   int32_t* recs;
+};
+
+struct McItem {  // a row of a launch table (= clipper_mc_plan::Item)
+  int32_t prob, idx;
+};
+
+// where a problem's adjacency is read from and written to
+struct McAdjSrc {
+  SliceView M;     // the slices of its store (S == null)
+  const void* S;   // else a dense store S[j][c], row pitch ld: the explicit C or M's values
+  int64_t ld;
+  uint64_t* G;
+  int64_t nw, m;
+  int32_t* deg;
 };
 
 constexpr int MC_PEEL_THREADS = 1024;
@@ -155,12 +169,6 @@ __device__ __forceinline__ void mc_adj_slice(const SliceView& M, uint64_t* __res
   }
 }
 
-template <typename VT, int H>
-__global__ __launch_bounds__(256) void k_mc_adj_slices(SliceView M, uint64_t* __restrict__ G, int64_t nw,
-                                                       int64_t m) {
-  mc_adj_slice<VT, H>(M, G, nw, m, static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
-}
-
 // From a dense one-shard store S[j][c] (row pitch ld; M's values or the explicit C): thread = (row c, word w),
 // bit b set when S[64 w + b][c] != 0. The loads of one j are coalesced over c. Writes every word of G.
 template <typename T>
@@ -174,14 +182,6 @@ __device__ __forceinline__ uint64_t mc_adj_dense_word(const T* __restrict__ S, i
   return word;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_mc_adj_dense(const T* __restrict__ S, int64_t ld, int64_t m, int64_t nw,
-                                                      uint64_t* __restrict__ G) {
-  const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (c >= m) return;
-  for (int64_t w = blockIdx.y; w < nw; w += gridDim.y) G[c * nw + w] = mc_adj_dense_word(S, ld, m, c, w);
-}
-
 // degree of every vertex: one wave per row
 __device__ __forceinline__ void mc_degree_row(const uint64_t* __restrict__ G, int64_t nw, int64_t v,
                                               int32_t* __restrict__ deg, int lane) {
@@ -189,12 +189,6 @@ __device__ __forceinline__ void mc_degree_row(const uint64_t* __restrict__ G, in
   for (int64_t w = lane; w < nw; w += 64) d += __popcll(G[v * nw + w]);
   d = mc_wave_sum(d);
   if (lane == 0) deg[v] = d;
-}
-__global__ __launch_bounds__(256) void k_mc_degree(const uint64_t* __restrict__ G, int64_t nw, int64_t m,
-                                                   int32_t* __restrict__ deg) {
-  const int64_t v = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (v >= m) return;
-  mc_degree_row(G, nw, v, deg, threadIdx.x & 63);
 }
 
 // ---- core numbers: level-synchronous peeling (Batagelj-Zaversnik levels), one workgroup -------------------------
@@ -271,13 +265,6 @@ __device__ __forceinline__ void mc_peel(const McProb& P, long long budget, uint6
   }
 }
 
-__global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(McProb P, long long budget) {
-  extern __shared__ uint64_t mc_alive[];
-  __shared__ int32_t fr[MC_PEEL_FCAP];
-  __shared__ int32_t sc[2];
-  mc_peel(P, budget, mc_alive, fr, sc);
-}
-
 // ---- HEU: the greedy clique of one seed (one wave; C = the candidate bitset in LDS) ------------------------------
 // Candidates: N(v) minus the vertices with core + 1 < thr; step: take the candidate of largest core number (ties:
 // smallest index), intersect with its row. Every pick's core is at most the previous one's, so with thr <= the
@@ -345,20 +332,10 @@ __device__ __forceinline__ void mc_heu(const McProb& P, long long budget, uint64
   }
 }
 
-__global__ __launch_bounds__(64) void k_mc_heu(McProb P, long long budget) {
-  extern __shared__ uint64_t mc_cand[];
-  mc_heu(P, budget, mc_cand);
-}
-
 // the clique of one seed (thr = 0), written to out[0..size)
 __device__ __forceinline__ void mc_heu_one(const McProb& P, uint64_t* mc_cand) {
   long long work = 0;
   mc_greedy(P.G, P.nw, P.core, P.seed, 0, mc_cand, P.out, work, threadIdx.x);
-}
-
-__global__ __launch_bounds__(64) void k_mc_heu_one(McProb P) {
-  extern __shared__ uint64_t mc_cand[];
-  mc_heu_one(P, mc_cand);
 }
 
 // ---- EXACT: bitset branch and bound, one wave per root ----------------------------------------------------------
@@ -530,9 +507,129 @@ __device__ __forceinline__ void mc_exact(const McProb& P_, int slot, long long b
   }
 }
 
-__global__ __launch_bounds__(64) void k_mc_exact(McProb P, long long budget) {
+// ---- the launches -----------------------------------------------------------------------------------------------------
+// Every kernel fetches its problem's row of the descriptor table, so a lone call and a batch run the same code. In the
+// adjacency and degree launches the grid's last dimension is the problem (strided when the call holds more problems
+// than a grid dimension does) and x the slice or row, up to the call's largest count: a wave or thread past its
+// problem's count has nothing to do. No workgroup waits for another (more workgroups than the chip holds is fine), no
+// launch is cooperative, and the only words workgroups share are a problem's head, incumbent key and counters.
+
+// A pointer read from a device table is a generic one to the compiler, and every access through it a FLAT
+// instruction, which also waits on the LDS counter. All buffers of a call are global memory: the fetches below say
+// so, and the bodies get the global loads, stores and atomics that pointers passed as kernel arguments get.
+template <typename T>
+__device__ __forceinline__ T* mc_global(T* const& field) {  // the table's field, read as a pointer to global memory
+  return (T*)(*static_cast<CLIPPER_GLOBAL T* const*>(static_cast<const void*>(&field)));
+}
+__device__ __forceinline__ McProb mc_fetch(const McProb* __restrict__ probs, int i) {
+  const McProb& t = probs[i];
+  McProb P = t;
+  P.G = mc_global(t.G);
+  P.degw = mc_global(t.degw);
+  P.core = mc_global(t.core);
+  P.alive = mc_global(t.alive);
+  P.pos = mc_global(t.pos);
+  P.list = mc_global(t.list);
+  P.out = mc_global(t.out);
+  P.ctl = mc_global(t.ctl);
+  P.slots = mc_global(t.slots);
+  P.arena = mc_global(t.arena);
+  P.paths = mc_global(t.paths);
+  P.recs = mc_global(t.recs);
+  return P;
+}
+__device__ __forceinline__ McAdjSrc mc_fetch(const McAdjSrc* __restrict__ src, int i) {
+  const McAdjSrc& t = src[i];
+  McAdjSrc a = t;
+  a.S = mc_global(t.S);
+  a.G = mc_global(t.G);
+  a.deg = mc_global(t.deg);
+  return a;
+}
+
+// one wave per (slice, problem); G zeroed by the caller. A problem read from a dense store is k_mc_adj_dense's.
+template <typename VT, int H>
+__global__ __launch_bounds__(256) void k_mc_adj_slices(const McAdjSrc* __restrict__ src, int32_t nprob) {
+  const int64_t s = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  for (int32_t p = blockIdx.y; p < nprob; p += gridDim.y) {
+    const McAdjSrc a = mc_fetch(src, p);
+    if (!a.S) mc_adj_slice<VT, H>(a.M, a.G, a.nw, a.m, s, threadIdx.x & 63);  // (s past its slices: returns)
+  }
+}
+
+// one thread per (row, word, problem): y = the word, z = the problem (both strided when the grid is smaller)
+template <typename T>
+__global__ __launch_bounds__(256) void k_mc_adj_dense(const McAdjSrc* __restrict__ src, int32_t nprob) {
+  const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  for (int32_t p = blockIdx.z; p < nprob; p += gridDim.z) {
+    const McAdjSrc a = mc_fetch(src, p);
+    if (!a.S || c >= a.m) continue;
+    for (int64_t w = blockIdx.y; w < a.nw; w += gridDim.y)
+      a.G[c * a.nw + w] = mc_adj_dense_word(static_cast<const T*>(a.S), a.ld, a.m, c, w);
+  }
+}
+
+// one wave per (row, problem)
+__global__ __launch_bounds__(256) void k_mc_degree(const McAdjSrc* __restrict__ src, int32_t nprob) {
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  for (int32_t p = blockIdx.y; p < nprob; p += gridDim.y) {
+    const McAdjSrc a = mc_fetch(src, p);
+    if (v < a.m) mc_degree_row(a.G, a.nw, v, a.deg, threadIdx.x & 63);
+  }
+}
+
+// one workgroup per unfinished problem (work[blockIdx.x]); dynamic LDS: the largest nw of the call, in words
+__global__ __launch_bounds__(MC_PEEL_THREADS) void k_mc_core_peel(const McProb* __restrict__ probs,
+                                                                  const int32_t* __restrict__ work, long long budget) {
+  extern __shared__ uint64_t mc_alive[];
+  __shared__ int32_t fr[MC_PEEL_FCAP];
+  __shared__ int32_t sc[2];
+  const McProb P = mc_fetch(probs, work[blockIdx.x]);
+  mc_peel(P, budget, mc_alive, fr, sc);
+}
+
+// one wave per slot; a slot takes its problem's seeds through that problem's head
+__global__ __launch_bounds__(64) void k_mc_heu(const McProb* __restrict__ probs, const McItem* __restrict__ slots,
+                                               long long budget) {
+  extern __shared__ uint64_t mc_cand[];
+  const McProb P = mc_fetch(probs, slots[blockIdx.x].prob);
+  if (mc_load_i32(&P.ctl->head) >= P.nlist) return;  // (its problem is finished)
+  mc_heu(P, budget, mc_cand);
+}
+
+// one wave per problem of the work list: the clique of its winning seed
+__global__ __launch_bounds__(64) void k_mc_heu_one(const McProb* __restrict__ probs, const int32_t* __restrict__ work) {
+  extern __shared__ uint64_t mc_cand[];
+  const McProb P = mc_fetch(probs, work[blockIdx.x]);
+  mc_heu_one(P, mc_cand);
+}
+
+// one wave per slot, with the stack, path and record it keeps between launches
+__global__ __launch_bounds__(64) void k_mc_exact(const McProb* __restrict__ probs, const McItem* __restrict__ slots,
+                                                 long long budget) {
   extern __shared__ uint64_t mc_lds[];
-  mc_exact(P, static_cast<int>(blockIdx.x), budget, mc_lds);
+  const McItem it = slots[blockIdx.x];
+  const McProb P = mc_fetch(probs, it.prob);
+  if (P.slots[it.idx].root < 0 && mc_load_i32(&P.ctl->head) >= P.nlist) return;  // (nothing left for this slot)
+  mc_exact(P, it.idx, budget, mc_lds);
+}
+
+// one wave per problem of the work list whose incumbent beat HEU's clique: the record of the slot that raised the
+// final key goes to out[0 .. omega), its length to out[-1] (-1: no slot holds it)
+__global__ __launch_bounds__(64) void k_mc_collect(const McProb* __restrict__ probs, const int32_t* __restrict__ work) {
+  const McProb P = mc_fetch(probs, work[blockIdx.x]);
+  const int lane = threadIdx.x;
+  const unsigned long long key = P.ctl->key;
+  int who = -1;
+  for (int j = lane; j < P.nslots; j += 64)
+    if (P.slots[j].rec_key == key) who = j;
+  who = mc_wave_max(who);
+  const int omega = static_cast<int>(key >> 32);
+  if (who >= 0) {
+    const int32_t* rec = P.recs + static_cast<int64_t>(who) * (P.D + 1);
+    for (int i = lane; i < omega; i += 64) P.out[i] = rec[i];
+  }
+  if (lane == 0) P.out[-1] = who >= 0 ? omega : -1;
 }
 
 }  // namespace clipper_hip

@@ -39,7 +39,6 @@
 //   k_subproblem.hip.h  the live sub-problem: column counts of a view, the selection, the hand-over and the way back
 //   k_knn.hip.h       brute-force k-nearest neighbours (putative associations)
 //   k_maxclique.hip.h the maximum clique of the consistency graph: adjacency bitsets, core numbers, HEU, EXACT
-//   k_maxclique_batch.hip.h  the same solver over a table of problems: the launches of a batched call
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
 #pragma once
 
@@ -54,5 +53,4 @@
 #include "k_subproblem.hip.h"
 #include "k_knn.hip.h"
 #include "k_maxclique.hip.h"
-#include "k_maxclique_batch.hip.h"
 #include "k_sdp.hip.h"

@@ -601,9 +601,9 @@ int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* pa
  * (ascending) becomes the problem's node list: clipper_hip_batch_get_nodes / _get_selected_associations return it,
  * clipper_hip_batch_get_solution's num_nodes is its size; nothing the solver keeps is touched.
  * Routes: problems with m <= 2048 (the batch's resident limit, on all four storages) run in the batched launches,
- * out of ONE device slab whose size is checked against the free memory before anything runs (CLIPPER_HIP_E_NOMEM
- * with the figure; the batch stays usable); larger problems run afterwards, one by one, as clipper_hip_max_clique on
- * their child context.
+ * their graphs out of ONE device slab whose size is checked against the free memory before anything runs
+ * (CLIPPER_HIP_E_NOMEM with the figures; the batch stays usable); larger problems run afterwards, one by one, each as
+ * clipper_hip_max_clique runs a lone context.
  * time_limit_s > 0 bounds the whole call, checked between launches: problems still searching when it runs out return
  * their best clique so far with timed_out = 1 (HEU's first launch always leaves one, as in the lone call), problems
  * that had finished keep timed_out = 0 and their exact result. A problem of the lone route gets the time that remains; when

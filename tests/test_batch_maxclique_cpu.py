@@ -53,8 +53,9 @@ def test_plan_header_has_no_hip():
 
 def test_new_sources_are_in_the_build_lists():
     text = open(os.path.join(ROOT, "clipper_amd", "build.py")).read()
-    for f in ("k_maxclique_batch.hip.h", "host_mcbatch.hpp", "host_mcplan.hpp"):
+    for f in ("k_maxclique.hip.h", "host_maxclique.hpp", "host_mcplan.hpp"):
         assert f in text, f
+        assert os.path.exists(os.path.join(ROOT, "clipper_amd", "csrc", f)), f
 
 
 def test_facade_surfaces():

@@ -171,6 +171,37 @@ def test_explicit_constraint_matrix_dense_and_sparse(m, p, seed):
     assert len(lists) == 1, lists
 
 
+def test_staging_kept_by_a_context():
+    """One context, matrices of m = 300, 65 and 300 again: its staging buffer is reused with other offsets and a
+    smaller need; every call equals the model, and the third round the first, list for list."""
+    g = abi.HipClipper(storage=abi.STORE_F32_CSC)
+    rounds = []
+    for m, seed in ((300, 1), (65, 2), (300, 1)):
+        M, Cm = _random_pair(m, 0.3, seed)
+        g.set_matrix_data(M, Cm)
+        adj = mm.adjacency_from_matrix(Cm)
+        _check_all_methods(g, adj)
+        rounds.append([g.core_numbers().tolist()] + [g.max_clique(meth)[0].tolist() for meth in METHODS])
+    g.close()
+    assert rounds[2] == rounds[0] and len(rounds[1][0]) == 65
+
+
+def test_explicit_c_on_slices_and_on_a_dense_store():
+    """m = 129 (two words per row and one bit): with an explicit C of another pattern than M's the graph is C's, on a
+    slice storage (where the slices hold M) as on a dense one."""
+    M, Cm = _random_pair(129, 0.3, 4)
+    adj = mm.adjacency_from_matrix(Cm)
+    assert not np.array_equal(adj, mm.adjacency_from_matrix(M))
+    core = mm.core_numbers(adj)
+    lists = set()
+    for storage in (abi.STORE_F32_CSC, abi.STORE_F64):
+        g = abi.HipClipper(storage=storage)
+        g.set_matrix_data(M, Cm)
+        lists.add(tuple(_check_all_methods(g, adj, core)))
+        g.close()
+    assert len(lists) == 1, lists
+
+
 def test_bench_problem_exact():
     p = synth.make_euclidean_problem(10000, 0.95, seed=12345)
     gs = abi.HipClipper(storage=abi.STORE_F32_CSC)
