@@ -24,6 +24,8 @@ STORE_F32, STORE_F64, STORE_F32_CSC, STORE_F64_CSC = 0, 1, 2, 3
 ROUNDING_NONZERO, ROUNDING_DSD, ROUNDING_DSD_HEU = 0, 1, 2
 MC_EXACT, MC_HEU, MC_KCORE = 0, 1, 2  # CLIPPER_HIP_MC_* = maxclique::Method
 SDP_MAX_N = 128  # CLIPPER_HIP_SDP_MAX_N
+SDP_WIDE_MAX_N = 1024  # CLIPPER_HIP_SDP_WIDE_MAX_N
+SDP_ROUTE_WORKGROUP, SDP_ROUTE_AUTO, SDP_ROUTE_WIDE = 0, 1, 2  # CLIPPER_HIP_SDP_ROUTE_*
 INVARIANT_MAX_D, INVARIANT_MAX_PARAMS = 32, 16  # CLIPPER_HIP_INVARIANT_MAX_D / _MAX_PARAMS
 
 # every symbol include/clipper_hip.h declares (checked by tests/test_abi_exports.py)
@@ -53,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom", "clipper_hip_batch_solve_custom",
     "clipper_hip_sdp_solve_batch", "clipper_hip_batch_sdp", "clipper_hip_batch_get_sdp",
     "clipper_hip_batch_max_clique", "clipper_hip_batch_max_clique_stats",
+    "clipper_hip_sdp_set_route", "clipper_hip_sdp_route",
 ]
 
 
@@ -151,7 +154,7 @@ class SdpInfo(C.Structure):
 
     _fields_ = [
         ("iters", C.c_int32), ("converged", C.c_int32), ("timed_out", C.c_int32), ("num_nodes", C.c_int32),
-        ("sweeps", C.c_int32), ("pad", C.c_int32),
+        ("sweeps", C.c_int32), ("route", C.c_int32),
         ("pobj", C.c_double), ("dobj", C.c_double), ("r_prim", C.c_double), ("r_dual", C.c_double),
         ("rho", C.c_double), ("thr", C.c_double), ("t_total", C.c_double), ("t_setup", C.c_double),
         ("t_solve", C.c_double), ("t_extract", C.c_double),
@@ -297,6 +300,8 @@ def load_library(path: str = LIB_PATH):
                                               C.POINTER(SdpInfo)]
     L.clipper_hip_batch_sdp.argtypes = [vp, C.POINTER(SdpParams), C.POINTER(SdpInfo)]
     L.clipper_hip_batch_get_sdp.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
+    L.clipper_hip_sdp_set_route.argtypes = [C.c_int]
+    L.clipper_hip_sdp_route.argtypes = []
     L.clipper_hip_batch_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_batch_max_clique_stats.argtypes = [vp, ip, ip, ip]
     L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
@@ -809,8 +814,23 @@ def knn(P0, P1, knn: int, device: int = 0):
     return idx, sqd
 
 
+def sdp_set_route(route: int) -> int:
+    """clipper_hip_sdp_set_route: the process-wide route of the sdp entry points (SDP_ROUTE_*); returns the previous
+    setting. SDP_ROUTE_AUTO and SDP_ROUTE_WIDE open n <= SDP_WIDE_MAX_N through the wide route."""
+    prev = load_library().clipper_hip_sdp_set_route(int(route))
+    if prev < 0:
+        raise ClipperError(f"clipper_hip error {prev}: {_last_error()}")
+    return prev
+
+
+def sdp_route() -> int:
+    """clipper_hip_sdp_route: the current setting."""
+    return load_library().clipper_hip_sdp_route()
+
+
 def sdp_solve(M, C_, params: SdpParams | None = None, device: int = 0) -> SdpResult:
-    """sdp::solve(M, C, params) on the device: n x n M and C (n <= 128), only their lower triangles read."""
+    """sdp::solve(M, C, params) on the device: n x n M and C (n <= 128, or <= 1024 under sdp_set_route), only their
+    lower triangles read."""
     L = load_library()
     Mc = np.asfortranarray(np.asarray(M, dtype=np.float64))
     Cc = np.asfortranarray(np.asarray(C_, dtype=np.float64))

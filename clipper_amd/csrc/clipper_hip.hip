@@ -50,6 +50,7 @@ using namespace clipper_hip;
 #include "host_rv_resident.hpp"
 #include "host_subproblem.hpp"
 #include "host_registration.hpp"
+#include "host_sdpwide.hpp"
 #include "host_sdp.hpp"
 #include "host_sdpbatch.hpp"
 #include "host_solve.hpp"
@@ -328,6 +329,16 @@ int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t 
                           double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
                           clipper_sdp_info_t* info) try {
   return sdp_solve_impl(device, M, C, n, params, X_out, Y_out, lambdas_out, evec1_out, nodes_out, info);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_sdp_set_route(int route) try {
+  if (route != CLIPPER_HIP_SDP_ROUTE_WORKGROUP && route != CLIPPER_HIP_SDP_ROUTE_AUTO && route != CLIPPER_HIP_SDP_ROUTE_WIDE)
+    return fail(CLIPPER_HIP_E_INVALID, "sdp: unknown route %d", route);
+  return g_sdp_route.exchange(route);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_sdp_route(void) try {
+  return g_sdp_route.load();
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_sdp_solve_batch(int device, const clipper_sdp_problem_t* problems, int32_t count,

@@ -426,6 +426,13 @@ void fill_solution(Solution& s, const clipper_sdp_info_t& info) {
 }
 }  // namespace detail
 
+void setRoute(Route route) {
+  if (clipper_hip_sdp_set_route(static_cast<int>(route)) < 0)
+    throw std::invalid_argument(std::string("sdp::setRoute: ") + clipper_hip_last_error());
+}
+
+Route route() { return static_cast<Route>(clipper_hip_sdp_route()); }
+
 // sdp.cpp:109-303 on the device (clipper_hip_sdp_solve on device 0): only the lower triangles of M and C are read
 Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params) {
   const std::ptrdiff_t n = M.rows();

@@ -266,6 +266,13 @@ PYBIND11_MODULE(clipperpy, m) {
   m_sdp.def("solve", py::overload_cast<const clipper::MatrixXd&, const clipper::MatrixXd&, const clipper::sdp::Params&>(
                          &clipper::sdp::solve),
             "M"_a, "C"_a, "params"_a = clipper::sdp::Params{});
+  // the route of the device solver ("The wide route"): process-wide
+  py::enum_<clipper::sdp::Route>(m_sdp, "Route")
+      .value("Workgroup", clipper::sdp::Route::Workgroup)
+      .value("Auto", clipper::sdp::Route::Auto)
+      .value("Wide", clipper::sdp::Route::Wide);
+  m_sdp.def("set_route", &clipper::sdp::setRoute, "route"_a);
+  m_sdp.def("route", &clipper::sdp::route);
   // many problems in one call: lists of M and of C ("Batches")
   m_sdp.def("solve_batch",
             py::overload_cast<const std::vector<clipper::MatrixXd>&, const std::vector<clipper::MatrixXd>&,

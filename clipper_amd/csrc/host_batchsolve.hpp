@@ -500,15 +500,16 @@ int batch_solve(Batch* b, const clipper_batch_problem_t* p, int32_t n, int d, in
 int batch_sdp(Batch* b, const clipper_sdp_params_t* P, clipper_sdp_info_t* infos) {
   const auto t0 = std::chrono::steady_clock::now();
   if (!b->solved) return fail(CLIPPER_HIP_E_STATE, "sdp: no batch has been solved");
-  if (int rc = sdp_check_params(P, 1)) return rc;
+  const int route = g_sdp_route.load();
+  if (int rc = sdp_check_params(P, 1, route)) return rc;
   const size_t count = b->res.size();
   for (size_t i = 0; i < count; ++i) {
     const Ctx* c = b->kids[i];
     if (!c->has_matrix) return fail(CLIPPER_HIP_E_STATE, "problem %zu: no matrix has been built", i);
     if (c->m < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: empty problem", i);
-    if (c->m > SDP_MAX_N)
+    if (c->m > clipper_sdpw_plan::route_limit(route))
       return fail(CLIPPER_HIP_E_SCOPE, "problem %zu: sdp: n = %lld is above the device solver's limit of %d", i,
-                  (long long)c->m, SDP_MAX_N);
+                  (long long)c->m, clipper_sdpw_plan::route_limit(route));
   }
   b->sdp.reset();
   if (count == 0) return 0;
@@ -536,7 +537,7 @@ int batch_sdp(Batch* b, const clipper_sdp_params_t* P, clipper_sdp_info_t* infos
     return 0;
   };
   bool dropped = false;
-  const int rc = sdp_batch_run(*S, b->stream, P, false, source, [](uint8_t*) {}, [&] { drop_copies(); dropped = true; }, t0);
+  const int rc = sdp_batch_run(*S, b->stream, P, route, false, source, [](uint8_t*) {}, [&] { drop_copies(); dropped = true; }, t0);
   if (!dropped) drop_copies();
   if (rc) return rc;
   for (size_t i = 0; i < count; ++i) {

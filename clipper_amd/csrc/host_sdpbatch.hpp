@@ -14,6 +14,9 @@
 //      back in ONE copy; X and Y cross only for the problems whose caller asked.
 // Per problem every result is bit for bit the lone entry point's (the kernel body and its geometry are the lone
 // kernel's; the host decides only WHEN a problem's next launch happens, which the iteration does not see).
+// The problems that take the wide route (host_sdpwide.hpp; by the route setting and n) keep their regions of the slab
+// but stay out of steps 4 and 5: after the others' certificates they run one after another on the same stream through
+// the lone call's driver and tail, sharing one work slab, and their results take their places among the others'.
 #pragma once
 
 #include <memory>
@@ -25,6 +28,7 @@ namespace {
 struct SdpBatchState {
   int device = 0;
   uint8_t* slab = nullptr;  // the plan's regions, then the launch tables
+  uint8_t* work = nullptr;  // the wide route's work regions, shared by its problems in turn
   SdpCtl* ctl = nullptr;    // device, one per problem
   clipper_sdp_plan::Plan plan;
   std::vector<int32_t> n;
@@ -39,8 +43,9 @@ struct SdpBatchState {
   template <typename T>
   T* dev(size_t off) const { return reinterpret_cast<T*>(slab + off); }
   ~SdpBatchState() {
-    if (slab || ctl) hipSetDevice(device);
+    if (slab || ctl || work) hipSetDevice(device);
     if (slab) hipFree(slab);
+    if (work) hipFree(work);
     if (ctl) hipFree(ctl);
   }
 };
@@ -69,7 +74,7 @@ int sdp_batch_outputs(const SdpBatchState& S, size_t i, double* X_out, double* Y
 // from (g.M, g.mask and g.n are set here); stage(dst): fills the host copy of the plan's src region (called only
 // when src_bytes > 0). after_gather(): called once the gather has finished (its sources may go).
 template <class Source, class Stage, class AfterGather>
-int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* P, bool with_src, Source&& source,
+int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* P, int route, bool with_src, Source&& source,
                   Stage&& stage, AfterGather&& after_gather, std::chrono::steady_clock::time_point t0) {
   using clk = std::chrono::steady_clock;
   namespace plan = clipper_sdp_plan;
@@ -79,6 +84,16 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   if (count == 0) return 0;
   S.plan = plan::make_plan(S.n, with_src);
   const plan::Plan& L = S.plan;
+  const clipper_sdpw_plan::Split routes = clipper_sdpw_plan::split(S.n, route);
+  std::vector<char> is_wide(count, 0);
+  size_t work_bytes = 0;
+  for (int32_t i : routes.wide) {
+    is_wide[static_cast<size_t>(i)] = 1;
+    const clipper_sdpw_plan::Regions r = clipper_sdpw_plan::make_regions(S.n[static_cast<size_t>(i)]);
+    work_bytes = std::max(work_bytes, r.bytes - r.work_begin);
+  }
+  // the work list of the workgroup route, in the plan's order
+  const std::vector<int32_t> order = plan::compact(L.order, [&](int32_t i) { return is_wide[static_cast<size_t>(i)] != 0; });
 
   // ---- 2. one slab (the launch tables behind the plan's regions), one control array ---------------------------------
   const size_t off_round = L.bytes, off_args = off_round + count * sizeof(SdpRound),
@@ -89,12 +104,13 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   const size_t ctl_bytes = count * sizeof(SdpCtl);
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  if (slab_bytes + ctl_bytes > free_b)
+  if (slab_bytes + ctl_bytes + work_bytes > free_b)
     return fail(CLIPPER_HIP_E_NOMEM, "sdp batch: %zu problems need %zu bytes of device memory, %zu are free", count,
-                slab_bytes + ctl_bytes, free_b);
+                slab_bytes + ctl_bytes + work_bytes, free_b);
   for (auto pr : {std::make_pair(reinterpret_cast<void**>(&S.slab), slab_bytes),
-                  std::make_pair(reinterpret_cast<void**>(&S.ctl), ctl_bytes)})
-    if (hipMalloc(pr.first, pr.second) != hipSuccess) {
+                  std::make_pair(reinterpret_cast<void**>(&S.ctl), ctl_bytes),
+                  std::make_pair(reinterpret_cast<void**>(&S.work), work_bytes)})
+    if (pr.second && hipMalloc(pr.first, pr.second) != hipSuccess) {
       *pr.first = nullptr;
       (void)hipGetLastError();
       return fail(CLIPPER_HIP_E_NOMEM, "sdp batch: device allocation of %zu bytes failed", pr.second);
@@ -113,7 +129,7 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     args[i] = SdpArgs{S.dev<double>(r.M), S.dev<double>(r.mask), S.dev<double>(r.X), S.dev<double>(r.Z),
                       S.dev<double>(r.U), S.dev<double>(r.Q), S.dev<double>(r.T), S.dev<double>(r.mu), S.ctl + i,
                       n, plan::padded(n), static_cast<double>(P->eps_abs), static_cast<double>(P->eps_rel)};
-    rdst[i] = SdpRoundDst{S.dev<double>(r.ev), S.dev<int32_t>(r.nodes)};
+    rdst[i] = SdpRoundDst{is_wide[i] ? nullptr : S.dev<double>(r.ev), S.dev<int32_t>(r.nodes)};
     SdpGatherSrc g{};
     g.M = S.dev<double>(r.M);
     g.mask = S.dev<double>(r.mask);
@@ -139,11 +155,14 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   }
 
   // ---- 4. INIT, the rounds of ITERATE over the active list, CERTIFY -----------------------------------------------
-  if (plan::launch_lds_bytes(L.order, S.n) > 64 * 1024 &&
+  if (plan::launch_lds_bytes(order, S.n) > 64 * 1024 &&
       !raise_dynamic_lds(reinterpret_cast<const void*>(k_sdp_batch), S.device, SDP_MAX_N * SDP_MAX_N * 8))
     return fail(CLIPPER_HIP_E_HIP, "sdp: cannot raise the kernel's LDS to %d bytes", SDP_MAX_N * SDP_MAX_N * 8);
   std::vector<int32_t> on_device;  // the list the device holds
   S.c.assign(count, SdpCtl{});
+  // (every launch copies the whole control array back: zeros, not stale bytes, for the wide route's problems, whose
+  // records are the driver's and reach S.c with their solve)
+  HIPCHK(hipMemsetAsync(S.ctl, 0, ctl_bytes, st));
   // one launch over `list` and the copy of the control array that follows it
   auto launch = [&](const std::vector<int32_t>& list, int mode, int budget) -> int {
     if (list.empty()) return 0;
@@ -160,15 +179,22 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     HIPCHK(hipStreamSynchronize(st));
     return 0;
   };
-  if (int rc = launch(L.order, SDP_MODE_INIT, 0)) return rc;
+  if (int rc = launch(order, SDP_MODE_INIT, 0)) return rc;
+  if (order.empty()) HIPCHK(hipStreamSynchronize(st));  // (the gather has read its sources)
   after_gather();
+  for (int32_t i : routes.wide) {  // (their INIT proper runs with their solve: the work slab is shared)
+    bool bad = false;
+    if (int rc = sdpw_infeasible(st, sdpw_view(args[static_cast<size_t>(i)], S.work), bad)) return rc;
+    S.c[static_cast<size_t>(i)] = SdpCtl{};
+    S.c[static_cast<size_t>(i)].infeasible = bad;
+  }
   for (size_t i = 0; i < count; ++i)
     if (S.c[i].infeasible)
       return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: no diagonal entry of C is nonzero (the problem is infeasible)", i);
   const double t_setup = since(t0);
   const auto t1 = clk::now();
   auto finished = [&](int32_t i) { return S.c[static_cast<size_t>(i)].converged || S.c[static_cast<size_t>(i)].iters >= P->max_iters; };
-  std::vector<int32_t> active = plan::compact(L.order, finished);
+  std::vector<int32_t> active = plan::compact(order, finished);
   int rounds = 0;
   while (!active.empty()) {
     if (P->time_limit_secs > 0 && since(t0) >= static_cast<double>(P->time_limit_secs)) {
@@ -180,9 +206,33 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     ++rounds;
   }
   // a certified bound in every outcome: lambda_max(M - Y) of the final Y
-  if (int rc = launch(plan::compact(L.order, [&](int32_t i) { return S.c[static_cast<size_t>(i)].converged != 0; }),
+  if (int rc = launch(plan::compact(order, [&](int32_t i) { return S.c[static_cast<size_t>(i)].converged != 0; }),
                       SDP_MODE_CERTIFY, 0))
     return rc;
+  // the wide route's problems, in the caller's order; what their tails return waits for the out region's copy
+  struct WideOut {
+    std::vector<double> mu, ev;
+    std::vector<int32_t> nodes;
+  };
+  std::vector<WideOut> wide_out(routes.wide.size());
+  for (size_t k = 0; k < routes.wide.size(); ++k) {
+    const size_t i = static_cast<size_t>(routes.wide[k]);
+    const int64_t n = S.n[i];
+    const SdpWide w = sdpw_view(args[i], S.work);
+    bool infeasible = false;
+    double ts = 0.0, tv = 0.0;
+    if (int rc = sdpw_solve(st, w, P, t0, S.c[i], S.info[i].timed_out, infeasible, ts, tv)) return rc;
+    if (infeasible)
+      return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: no diagonal entry of C is nonzero (the problem is infeasible)", i);
+    WideOut& o = wide_out[k];
+    o.mu.resize(static_cast<size_t>(plan::padded(S.n[i])));
+    o.ev.resize(static_cast<size_t>(n));
+    clipper_sdp_params_t quiet = *P;
+    quiet.verbose = 0;
+    if (int rc = sdp_tail(w.a.mu, w.a.Q, w.a.X, w.a.U, n, S.c[i], &quiet, CLIPPER_HIP_SDP_ROUTE_WIDE, t0, ts, tv, clk::now(),
+                          o.nodes, nullptr, nullptr, nullptr, o.ev.data(), o.mu.data(), S.info[i]))
+      return rc;
+  }
   const double t_solve = since(t1);
   const auto t2 = clk::now();
 
@@ -193,7 +243,18 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   S.out.resize(L.out_bytes + count * sizeof(SdpRound));  // (contiguous on the device: out region, rounding records)
   HIPCHK(hipMemcpyAsync(S.out.data(), S.slab + L.out_begin, S.out.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < routes.wide.size(); ++k) {  // the wide route's results into the host copy
+    const size_t i = static_cast<size_t>(routes.wide[k]);
+    const WideOut& o = wide_out[k];
+    uint8_t* out = S.out.data();
+    std::memcpy(out + (L.at[i].mu - L.out_begin), o.mu.data(), o.mu.size() * sizeof(double));
+    std::memcpy(out + (L.at[i].ev - L.out_begin), o.ev.data(), o.ev.size() * sizeof(double));
+    if (!o.nodes.empty()) std::memcpy(out + (L.at[i].nodes - L.out_begin), o.nodes.data(), o.nodes.size() * sizeof(int32_t));
+    const int32_t top = static_cast<int32_t>(std::max_element(o.mu.begin(), o.mu.begin() + S.n[i]) - o.mu.begin());
+    reinterpret_cast<SdpRound*>(S.out.data() + L.out_bytes)[i] = SdpRound{S.info[i].thr, static_cast<int32_t>(o.nodes.size()), top};
+  }
   for (size_t i = 0; i < count; ++i) {
+    if (is_wide[i]) continue;  // (filled by its tail)
     const SdpCtl& c = S.c[i];
     clipper_sdp_info_t& I = S.info[i];
     I.iters = c.iters;
@@ -218,8 +279,8 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     std::printf("sdp batch: %zu problems, %d rounds of %d iterations, %.3f s\n", count, rounds, SDP_ITERS_PER_LAUNCH, t_total);
     for (size_t i = 0; i < count; ++i) {
       const clipper_sdp_info_t& I = S.info[i];
-      std::printf("  problem %zu: n = %d, %d iterations (%d Jacobi sweeps), %s, pobj %.6g, dobj %.6g\n", i, S.n[i],
-                  I.iters, I.sweeps, I.converged ? "converged" : (I.timed_out ? "timed out" : "max_iters"), I.pobj, I.dobj);
+      std::printf("  problem %zu%s: n = %d, %d iterations (%d Jacobi sweeps), %s, pobj %.6g, dobj %.6g\n", i,
+                  I.route == CLIPPER_HIP_SDP_ROUTE_WIDE ? " (wide route)" : "", S.n[i], I.iters, I.sweeps, I.converged ? "converged" : (I.timed_out ? "timed out" : "max_iters"), I.pobj, I.dobj);
     }
   }
   return 0;
@@ -232,13 +293,14 @@ int sdp_solve_batch_impl(int device, const clipper_sdp_problem_t* p, int32_t cou
   if (count < 0) return fail(CLIPPER_HIP_E_INVALID, "sdp batch: count = %d", count);
   if (count == 0) return 0;
   if (!p) return fail(CLIPPER_HIP_E_INVALID, "sdp batch: the problem list is required");
-  if (int rc = sdp_check_params(P, 1)) return rc;
+  const int route = g_sdp_route.load();
+  if (int rc = sdp_check_params(P, 1, route)) return rc;
   for (int32_t i = 0; i < count; ++i) {
     if (!p[i].M || !p[i].C) return fail(CLIPPER_HIP_E_INVALID, "problem %d: sdp: M and C are required", i);
     if (p[i].n < 1) return fail(CLIPPER_HIP_E_INVALID, "problem %d: sdp: empty problem (n = %lld)", i, (long long)p[i].n);
-    if (p[i].n > SDP_MAX_N)
+    if (p[i].n > clipper_sdpw_plan::route_limit(route))
       return fail(CLIPPER_HIP_E_SCOPE, "problem %d: sdp: n = %lld is above the device solver's limit of %d", i,
-                  (long long)p[i].n, SDP_MAX_N);
+                  (long long)p[i].n, clipper_sdpw_plan::route_limit(route));
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -267,7 +329,7 @@ int sdp_solve_batch_impl(int device, const clipper_sdp_problem_t* p, int32_t cou
       std::memcpy(dst + (S.plan.at[i].srcC - S.plan.src_begin), p[i].C, nn);
     }
   };
-  if (int rc = sdp_batch_run(S, st, P, true, source, stage, [] {}, t0)) return rc;
+  if (int rc = sdp_batch_run(S, st, P, route, true, source, stage, [] {}, t0)) return rc;
   const auto t2 = std::chrono::steady_clock::now();
   for (size_t i = 0; i < S.count(); ++i) {
     const clipper_sdp_problem_t& q = p[i];

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sdp_circle.hpp"
+
 namespace clipper_hip {
 
 constexpr int SDP_MAX_N = 128;          // the working matrix: SDP_MAX_N^2 doubles of LDS
@@ -87,15 +89,33 @@ __device__ inline double sdp_block_sum(double v, double* red) {
 }
 
 // the pair k of step t of the circle order over np indices (np even): index np - 1 stays put, the others turn
-__device__ inline void sdp_pair(int k, int t, int np, int& p, int& q) {
-  const int m = np - 1;
-  if (k == 0) {
-    p = t;
-    q = m;
-  } else {
-    p = (t + k) % m;
-    q = (t - k + m) % m;
+// (stated in sdp_circle.hpp, where the host can walk it too)
+__device__ inline void sdp_pair(int k, int t, int np, int& p, int& q) { clipper_sdp_circle::circle_pair(k, t, np, p, q); }
+
+// The rotation that annihilates a_pq of the pair (p, q): c, s and the tangent tn (identity when a_pq = 0)
+__device__ inline void sdp_rotation(double apq, double app, double aqq, double& c, double& s, double& tn) {
+  c = 1.0;
+  s = 0.0;
+  tn = 0.0;
+  if (apq != 0.0) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double at = fabs(theta);
+    tn = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(theta * theta + 1.0));
+    if (theta < 0.0) tn = -tn;
+    c = 1.0 / sqrt(tn * tn + 1.0);
+    s = tn * c;
   }
+}
+
+// Both sides of the 2 x 2 block (rows p, q of a pair with c1, s1; columns r, s of another with c2, sn2)
+__device__ inline void sdp_rotate_block(double apr, double aps, double aqr, double aqs, double c1, double s1, double c2,
+                                        double sn2, double& npr, double& nps, double& nqr, double& nqs) {
+  const double bpr = apr * c2 - aps * sn2, bps = apr * sn2 + aps * c2;  // columns (l)
+  const double bqr = aqr * c2 - aqs * sn2, bqs = aqr * sn2 + aqs * c2;
+  npr = c1 * bpr - s1 * bqr;  // rows (k)
+  nps = c1 * bps - s1 * bqs;
+  nqr = s1 * bpr + c1 * bqr;
+  nqs = s1 * bps + c1 * bqs;
 }
 
 // A (LDS) <- Q^T A Q, through T (global); Q is np x np
@@ -160,16 +180,8 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
       if (tid < h) {
         int p, q;
         sdp_pair(tid, t, np, p, q);
-        const double apq = A[p * np + q];
-        double c = 1.0, s = 0.0, tn = 0.0;
-        if (apq != 0.0) {
-          const double theta = (A[q * np + q] - A[p * np + p]) / (2.0 * apq);
-          const double at = fabs(theta);
-          tn = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(theta * theta + 1.0));
-          if (theta < 0.0) tn = -tn;
-          c = 1.0 / sqrt(tn * tn + 1.0);
-          s = tn * c;
-        }
+        double c, s, tn;
+        sdp_rotation(A[p * np + q], A[p * np + p], A[q * np + q], c, s, tn);
         rc[tid] = c;
         rs[tid] = s;
         rt[tid] = tn;
@@ -193,10 +205,8 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
         sdp_pair(l, t, np, r, s2);
         const double c1 = rc[k], s1 = rs[k], c2 = rc[l], sn2 = rs[l];
         const double apr = A[p * np + r], aps = A[p * np + s2], aqr = A[q * np + r], aqs = A[q * np + s2];
-        const double bpr = apr * c2 - aps * sn2, bps = apr * sn2 + aps * c2;  // columns (l)
-        const double bqr = aqr * c2 - aqs * sn2, bqs = aqr * sn2 + aqs * c2;
-        const double npr = c1 * bpr - s1 * bqr, nps = c1 * bps - s1 * bqs;  // rows (k)
-        const double nqr = s1 * bpr + c1 * bqr, nqs = s1 * bps + c1 * bqs;
+        double npr, nps, nqr, nqs;
+        sdp_rotate_block(apr, aps, aqr, aqs, c1, s1, c2, sn2, npr, nps, nqr, nqs);
         A[p * np + r] = npr;
         A[p * np + s2] = nps;
         A[q * np + r] = nqr;
@@ -478,7 +488,7 @@ struct SdpRound {
 };
 
 struct SdpRoundDst {
-  double* ev;      // n doubles: evec1
+  double* ev;      // n doubles: evec1 (nullptr: the problem is not rounded here)
   int32_t* nodes;  // n int32: the selection, ascending
 };
 
@@ -503,6 +513,7 @@ __global__ void __launch_bounds__(64) k_sdp_round_batch(const SdpArgs* __restric
   const SdpArgs g = table[blockIdx.x];
   const int lane = threadIdx.x, n = g.n, np = g.np;
   double* ev = dst[blockIdx.x].ev;
+  if (!ev) return;  // a problem of the wide route: rounded by the lone call's tail (host_sdp.hpp)
   int32_t* nodes = dst[blockIdx.x].nodes;
   double bv = 0.0;
   int bi = 0x7fffffff;

@@ -40,6 +40,7 @@
 //   k_knn.hip.h       brute-force k-nearest neighbours (putative associations)
 //   k_maxclique.hip.h the maximum clique of the consistency graph: adjacency bitsets, core numbers, HEU, EXACT
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
+//   k_sdp_wide.hip.h  the same relaxation for one problem over the whole chip, a launch per Jacobi step (n <= 1024)
 #pragma once
 
 #include "k_solver.hip.h"
@@ -54,3 +55,4 @@
 #include "k_knn.hip.h"
 #include "k_maxclique.hip.h"
 #include "k_sdp.hip.h"
+#include "k_sdp_wide.hip.h"

@@ -6,7 +6,8 @@
  *
  *   maximize <M, X>  s.t.  tr X = 1, X psd, X_ij = 0 where C_ij = 0, X_ij >= 0 elsewhere
  *
- * Only the lower triangles of M and C (diagonal included) are read. n <= 128. pobj / dobj keep SCS's
+ * Only the lower triangles of M and C (diagonal included) are read. n <= 128, or n <= 1024 after
+ * setRoute(Route::Auto) (the wide route). pobj / dobj keep SCS's
  * sign (minimisation): pobj = -<M, X>, dobj = -lambda_max(M - Y), a certified bound on the optimum.
  * The t_scs_* fields keep their names: t_scs = t_scs_solve = t_scs_cone = the device iteration, the
  * others 0. sdp::Params lives in clipper.h (as the facade's solveAsMSRCSDR needs it).
@@ -43,7 +44,16 @@ struct Solution {
   double t_extract = 0;     ///< time spent extracting which nodes to select
 };
 
-/// sdp.cpp:109-303 on HIP device 0; throws std::runtime_error when the device solver refuses (n > 128, no device).
+/// The route of the device solver (clipper_hip_sdp_set_route): Workgroup, the default, serves n <= 128 with one
+/// workgroup per problem; Auto adds the wide route for n up to 1024 (one problem at a time over the whole chip);
+/// Wide takes the wide route at every n <= 1024. Process-wide; solve (both overloads), CLIPPER::solveAsMSRCSDR with
+/// setDeviceSdp(true) and CLIPPERBatch::solveAsMSRCSDR follow it.
+enum class Route { Workgroup = 0, Auto = 1, Wide = 2 };
+void setRoute(Route route);
+Route route();
+
+/// sdp.cpp:109-303 on HIP device 0; throws std::runtime_error when the device solver refuses (n above the route's
+/// limit: 128 by default; no device).
 Solution solve(const MatrixXd& M, const MatrixXd& C, const Params& params = Params{});
 
 /// Many problems in one call (clipper_hip_sdp_solve_batch, DESIGN.md section 11 "Batches"): one workgroup per problem,

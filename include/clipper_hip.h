@@ -324,7 +324,9 @@ int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out /* m */);
 
 /* maximize <M, X>  s.t.  tr X = 1, X psd, X_ij = 0 where C_ij = 0, X_ij >= 0 elsewhere; only the lower triangle of
  * M and C (diagonal included) is read and taken as symmetric. ADMM with a Jacobi eigensolver on the device, fp64,
- * one workgroup; n <= CLIPPER_HIP_SDP_MAX_N, larger problems return CLIPPER_HIP_E_SCOPE.
+ * one workgroup; by default n <= CLIPPER_HIP_SDP_MAX_N, larger problems return CLIPPER_HIP_E_SCOPE.
+ * clipper_hip_sdp_set_route (below) opens n <= CLIPPER_HIP_SDP_WIDE_MAX_N through the wide route: the same
+ * iteration, stopping rule and certificate for one problem at a time over the whole chip.
  * Stops when the primal residual ||X - Z||_F, the dual residual rho ||Z - Z_prev||_F and the gap between <M, X> and
  * the dual bound lambda_max(M - Y) are all within the Boyd tolerances of eps_abs / eps_rel, at max_iters, or when
  * time_limit_secs > 0 runs out (checked between launches). pobj / dobj follow SCS's sign (minimisation):
@@ -332,7 +334,19 @@ int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out /* m */);
  * acceleration_interval, acceleration_lookback and eps_infeas are accepted and ignored (there is no Anderson
  * acceleration, and the problem is always feasible: e_i e_i^T with C(i, i) != 0; a C without a nonzero diagonal
  * entry is refused with CLIPPER_HIP_E_INVALID). */
-#define CLIPPER_HIP_SDP_MAX_N 128
+#define CLIPPER_HIP_SDP_MAX_N 128       /* the workgroup route: the working matrix is one workgroup's LDS */
+#define CLIPPER_HIP_SDP_WIDE_MAX_N 1024 /* the wide route: the working matrix is in device memory        */
+enum { CLIPPER_HIP_SDP_ROUTE_WORKGROUP = 0,   /* default: n <= CLIPPER_HIP_SDP_MAX_N, one workgroup per problem           */
+       CLIPPER_HIP_SDP_ROUTE_AUTO      = 1,   /* workgroup route for n <= 128, wide route up to CLIPPER_HIP_SDP_WIDE_MAX_N */
+       CLIPPER_HIP_SDP_ROUTE_WIDE      = 2 }; /* wide route at every n <= CLIPPER_HIP_SDP_WIDE_MAX_N (tests and probes)   */
+/* The route of clipper_hip_sdp, clipper_hip_sdp_solve, clipper_hip_sdp_solve_batch and clipper_hip_batch_sdp: one
+ * process-wide atomic setting, read once at the start of a call. Under AUTO or WIDE the scope limit of those calls is
+ * CLIPPER_HIP_SDP_WIDE_MAX_N. set_route returns the previous setting, or CLIPPER_HIP_E_INVALID for an unknown route
+ * (the setting is then unchanged). The wide route needs 8 (5 n^2 + 5 np^2) bytes of device memory and a little more
+ * (80 MB at n = 1024, np = n rounded up to even); CLIPPER_HIP_E_NOMEM when they are not free. Two calls on the same
+ * input under the same setting give the same bits; the two routes agree to rounding, not bit for bit. */
+int clipper_hip_sdp_set_route(int route);
+int clipper_hip_sdp_route(void);
 typedef struct clipper_sdp_params_t { /* = sdp::Params (sdp.h:40-52) */
   int32_t verbose;
   int32_t max_iters;               /* >= 1 */
@@ -349,7 +363,7 @@ typedef struct clipper_sdp_info_t {
   int32_t timed_out;    /* 1: time_limit_secs stopped the iteration                                  */
   int32_t num_nodes;    /* rounded selection: |evec1_i| > thr                                        */
   int32_t sweeps;       /* Jacobi sweeps, all projections and certificates together                  */
-  int32_t pad;
+  int32_t route;        /* the route this problem took: CLIPPER_HIP_SDP_ROUTE_WORKGROUP or _WIDE     */
   double pobj;          /* -<M, X>                                                                   */
   double dobj;          /* -lambda_max(M - Y)                                                        */
   double r_prim;        /* ||X - Z||_F                                                               */
@@ -374,14 +388,17 @@ int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t 
                           double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
                           clipper_sdp_info_t* info);
 /* Many relaxations in one call, one workgroup per problem ("Batches"): the problems run side by side
- * on the chip in launches over the list of those still iterating. Per problem every output and every field of its
- * info but the times is bit for bit what clipper_hip_sdp_solve returns for it alone with the same params, whatever
- * else the batch holds and wherever the problem stands in it. M and C: host, column-major n x n, lower triangles
+ * on the chip in launches over the list of those still iterating. The problems that take the wide route (under
+ * CLIPPER_HIP_SDP_ROUTE_AUTO those above CLIPPER_HIP_SDP_MAX_N, under _WIDE all) run after them, one after another on
+ * the same stream, each with the chip to itself. Per problem every output and every field of its
+ * info but the times is bit for bit what clipper_hip_sdp_solve returns for it alone with the same params and the same
+ * route setting, whatever else the batch holds and wherever the problem stands in it. M and C: host, column-major n x n, lower triangles
  * read. Outputs optional (NULL allowed) as in clipper_hip_sdp_solve; nodes_out has capacity n and receives
  * infos[i].num_nodes nodes. Only evec1, the eigenvalues, the nodes and the control records come back from the device
  * unless a problem asks for X or Y.
  * The whole call is refused on the first bad problem, its index in the message, before anything touches the device:
- * count < 0, a NULL M or C, n < 1 -> CLIPPER_HIP_E_INVALID; n > CLIPPER_HIP_SDP_MAX_N -> CLIPPER_HIP_E_SCOPE; params
+ * count < 0, a NULL M or C, n < 1 -> CLIPPER_HIP_E_INVALID; n above the route setting's limit (CLIPPER_HIP_SDP_MAX_N by
+ * default) -> CLIPPER_HIP_E_SCOPE; params
  * as clipper_hip_sdp_solve. count == 0 succeeds and does nothing. A C without a nonzero diagonal entry fails the call
  * with CLIPPER_HIP_E_INVALID. time_limit_secs > 0 bounds the whole call (checked between rounds of launches): every
  * problem still iterating then reports timed_out = 1 and a certified dobj. t_total / t_setup / t_solve / t_extract of
@@ -588,7 +605,8 @@ int clipper_hip_batch_get_split(const clipper_hip_batch_t* b, double* fill_ms, d
  * bit for bit those of clipper_hip_sdp on a lone context scored from the same inputs on the same storage. Each
  * problem's selection becomes its node list: clipper_hip_batch_get_nodes / _get_selected_associations return it
  * (and clipper_hip_batch_get_solution's num_nodes is its size); the solver state of the children is untouched.
- * CLIPPER_HIP_E_STATE before any solve; CLIPPER_HIP_E_SCOPE naming the first problem with m > CLIPPER_HIP_SDP_MAX_N
+ * CLIPPER_HIP_E_STATE before any solve; CLIPPER_HIP_E_SCOPE naming the first problem with m above the route setting's
+ * limit (CLIPPER_HIP_SDP_MAX_N by default; the problems above it take the wide route under CLIPPER_HIP_SDP_ROUTE_AUTO)
  * (nothing has run then, and the batch stays usable). */
 int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* params, clipper_sdp_info_t* infos);
 /* The maximum clique (clipper_hip_max_clique, DESIGN.md 9 "Batches") of every problem of the batch's last solve call,
