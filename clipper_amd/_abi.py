@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("CLIPPER_HIP_LIB") or os.path.join(_HERE, "lib", "libc
 STORE_F32, STORE_F64, STORE_F32_CSC, STORE_F64_CSC = 0, 1, 2, 3
 ROUNDING_NONZERO, ROUNDING_DSD, ROUNDING_DSD_HEU = 0, 1, 2
 MC_EXACT, MC_HEU, MC_KCORE = 0, 1, 2  # CLIPPER_HIP_MC_* = maxclique::Method
+MC_SEED_ONLY = 3  # CLIPPER_HIP_MC_SEED_ONLY: the seeded entry points only
 SDP_MAX_N = 128  # CLIPPER_HIP_SDP_MAX_N
 SDP_WIDE_MAX_N = 1024  # CLIPPER_HIP_SDP_WIDE_MAX_N
 SDP_ROUTE_WORKGROUP, SDP_ROUTE_AUTO, SDP_ROUTE_WIDE = 0, 1, 2  # CLIPPER_HIP_SDP_ROUTE_*
@@ -55,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_affinity_custom_staged", "clipper_hip_affinity_custom", "clipper_hip_batch_solve_custom",
     "clipper_hip_sdp_solve_batch", "clipper_hip_batch_sdp", "clipper_hip_batch_get_sdp",
     "clipper_hip_batch_max_clique", "clipper_hip_batch_max_clique_stats",
+    "clipper_hip_max_clique_seeded", "clipper_hip_batch_max_clique_seeded",
     "clipper_hip_sdp_set_route", "clipper_hip_sdp_route",
 ]
 
@@ -130,6 +132,12 @@ class MaxCliqueInfo(C.Structure):
         ("edges", C.c_int64), ("roots_searched", C.c_int64), ("roots_pruned", C.c_int64), ("bb_nodes", C.c_int64),
         ("seconds", C.c_double),
     ]
+
+
+class MaxCliqueSeedInfo(C.Structure):
+    """clipper_maxclique_seed_info_t (include/clipper_hip.h): what a seeded max-clique call reports of its seed."""
+
+    _fields_ = [("seed_given", C.c_int32), ("seed_kept", C.c_int32), ("seed_size", C.c_int32), ("winner", C.c_int32)]
 
 
 class SdpParams(C.Structure):
@@ -304,6 +312,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_sdp_route.argtypes = []
     L.clipper_hip_batch_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_batch_max_clique_stats.argtypes = [vp, ip, ip, ip]
+    L.clipper_hip_max_clique_seeded.argtypes = [vp, C.c_int, C.c_double, ip, C.c_int32, C.POINTER(MaxCliqueInfo),
+                                                C.POINTER(MaxCliqueSeedInfo)]
+    L.clipper_hip_batch_max_clique_seeded.argtypes = [vp, C.c_int, C.c_double, ip, C.POINTER(C.c_int64),
+                                                      C.POINTER(MaxCliqueInfo), C.POINTER(MaxCliqueSeedInfo)]
     L.clipper_hip_batch_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     L.clipper_hip_batch_destroy.argtypes = [vp]
     L.clipper_hip_batch_destroy.restype = None
@@ -599,19 +611,34 @@ class HipClipper:
         self._check(min(k, 0))
         return out[:k].copy()
 
-    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0):
+    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0, seed=None):
         """maxclique::solve on the consistency graph (C != 0): MC_EXACT (ROBIN*), MC_HEU or MC_KCORE (ROBIN).
         Returns (nodes ascending, MaxCliqueInfo); the nodes become the context's selection. time_limit in seconds
-        (<= 0: none)."""
+        (<= 0: none). seed: a list of distinct vertices the search starts from (clipper_hip_max_clique_seeded;
+        "solution": the context's node list, e.g. the last solve's); with one the call returns
+        (nodes, MaxCliqueInfo, MaxCliqueSeedInfo), and method may be MC_SEED_ONLY."""
         info = MaxCliqueInfo()
-        self._check(self.L.clipper_hip_max_clique(self.h, int(method), float(time_limit), C.byref(info)))
+        sinfo = None
+        if seed is None:
+            self._check(self.L.clipper_hip_max_clique(self.h, int(method), float(time_limit), C.byref(info)))
+        else:
+            sinfo = MaxCliqueSeedInfo()
+            if isinstance(seed, str):
+                if seed != "solution":
+                    raise ValueError('seed: a vertex list or "solution"')
+                sp, ns = None, -1
+            else:
+                sa = np.ascontiguousarray(seed, dtype=np.int32).ravel()
+                sp, ns = _ip(sa), int(sa.size)
+            self._check(self.L.clipper_hip_max_clique_seeded(self.h, int(method), float(time_limit), sp, ns,
+                                                             C.byref(info), C.byref(sinfo)))
         out = np.zeros(max(info.num_nodes, 1), dtype=np.int32)
         k = self.L.clipper_hip_get_nodes(self.h, _ip(out), len(out))
         self._check(min(k, 0))
         nodes = out[:k].copy()
         # clipper.cpp:92-96: the solution of a max-clique call
         self.soln = Solution(t=info.seconds, ifinal=0, nodes=nodes, u=np.zeros(self.m), score=-1.0)
-        return nodes, info
+        return (nodes, info) if sinfo is None else (nodes, info, sinfo)
 
     def sdp(self, params: SdpParams | None = None):
         """sdp::solve on the context's M and C (identity diagonals): CLIPPER::solveAsMSRCSDR on the device.
@@ -1018,14 +1045,35 @@ class HipBatch:
             out.append(_sdp_result(n, X, Y, lam, ev, nodes[:k].copy(), info))
         return out
 
-    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0) -> list:
+    def max_clique(self, method: int = MC_EXACT, time_limit: float = 0.0, seeds=None) -> list:
         """The maximum clique (HipClipper.max_clique) of every problem of the last solve call, in one batched call
         (clipper_hip_batch_max_clique): per problem (nodes ascending, MaxCliqueInfo), the nodes and max_core,
         heuristic_size, edges, num_nodes those of a lone context. Each clique becomes its problem's node list
-        (get_nodes(i), selected_associations(i)). time_limit in seconds bounds the whole call (<= 0: none)."""
+        (get_nodes(i), selected_associations(i)). time_limit in seconds bounds the whole call (<= 0: none).
+        seeds: one vertex list per problem (an empty one: that problem runs unseeded) or "solution" (every problem's own
+        node list); with them (clipper_hip_batch_max_clique_seeded) each problem's tuple ends with its
+        MaxCliqueSeedInfo, and method may be MC_SEED_ONLY."""
         infos = (MaxCliqueInfo * max(self.n, 1))()
-        self._check(self.L.clipper_hip_batch_max_clique(self.b, int(method), float(time_limit), infos))
-        return [(self.get_nodes(i), MaxCliqueInfo.from_buffer_copy(infos[i])) for i in range(self.n)]
+        if seeds is None:
+            self._check(self.L.clipper_hip_batch_max_clique(self.b, int(method), float(time_limit), infos))
+            return [(self.get_nodes(i), MaxCliqueInfo.from_buffer_copy(infos[i])) for i in range(self.n)]
+        sinfos = (MaxCliqueSeedInfo * max(self.n, 1))()
+        if isinstance(seeds, str):
+            if seeds != "solution":
+                raise ValueError('seeds: one vertex list per problem or "solution"')
+            sp, op = None, None
+        else:
+            if len(seeds) != self.n:
+                raise ValueError(f"{len(seeds)} seed lists for {self.n} problems")
+            lists = [np.asarray(s, dtype=np.int32).ravel() for s in seeds]
+            flat = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]))
+            offs = np.zeros(self.n + 1, dtype=np.int64)
+            offs[1:] = np.cumsum([len(s) for s in lists])
+            sp, op = _ip(flat), offs.ctypes.data_as(C.POINTER(C.c_int64))
+        self._check(self.L.clipper_hip_batch_max_clique_seeded(self.b, int(method), float(time_limit), sp, op, infos,
+                                                               sinfos))
+        return [(self.get_nodes(i), MaxCliqueInfo.from_buffer_copy(infos[i]),
+                 MaxCliqueSeedInfo.from_buffer_copy(sinfos[i])) for i in range(self.n)]
 
     def max_clique_stats(self):
         """(kernel launches of the batched route, problems that ran in them, problems that ran alone) of the last

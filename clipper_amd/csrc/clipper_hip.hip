@@ -312,6 +312,12 @@ int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, cl
   return max_clique_impl(h, method, time_limit_s, info);
 } CLIPPER_HIP_GUARD_INT
 
+int clipper_hip_max_clique_seeded(clipper_hip_t* h, int method, double time_limit_s, const int32_t* seed, int32_t nseed,
+                                  clipper_maxclique_info_t* info, clipper_maxclique_seed_info_t* seed_info) try {
+  if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return max_clique_seeded_impl(h, method, time_limit_s, seed, nseed, info, seed_info);
+} CLIPPER_HIP_GUARD_INT
+
 int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out) try {
   if (!h || !core_out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   return core_numbers_impl(h, core_out);
@@ -596,6 +602,13 @@ int clipper_hip_batch_max_clique(clipper_hip_batch_t* b, int method, double time
                                  clipper_maxclique_info_t* infos) try {
   if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   return batch_max_clique(b, method, time_limit_s, infos);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_batch_max_clique_seeded(clipper_hip_batch_t* b, int method, double time_limit_s, const int32_t* seeds,
+                                        const int64_t* offsets, clipper_maxclique_info_t* infos,
+                                        clipper_maxclique_seed_info_t* seed_infos) try {
+  if (!b) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return batch_max_clique(b, method, time_limit_s, infos, true, seeds, offsets, seed_infos);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_batch_max_clique_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched,

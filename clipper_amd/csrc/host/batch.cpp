@@ -169,8 +169,14 @@ std::vector<Solution> CLIPPERBatch::solveAsMaximumClique(const maxclique::Params
                                                                : CLIPPER_HIP_MC_KCORE;
   const int32_t count = static_cast<int32_t>(n_);
   std::vector<clipper_maxclique_info_t> info(static_cast<size_t>(std::max<int32_t>(count, 1)));
-  check(clipper_hip_batch_max_clique(b_, method, static_cast<double>(params.time_limit), info.data()),
-        "batch solveAsMaximumClique");
+  std::vector<clipper_maxclique_seed_info_t> sinfo(info.size());
+  if (params.warm_start)  // every problem from its own node list (DESIGN.md 9 "Seeded calls")
+    check(clipper_hip_batch_max_clique_seeded(b_, method, static_cast<double>(params.time_limit), nullptr, nullptr,
+                                              info.data(), sinfo.data()),
+          "batch solveAsMaximumClique");
+  else
+    check(clipper_hip_batch_max_clique(b_, method, static_cast<double>(params.time_limit), info.data()),
+          "batch solveAsMaximumClique");
   std::vector<Solution> out(static_cast<size_t>(count));
   for (int32_t i = 0; i < count; ++i) {
     const clipper_maxclique_info_t& I = info[static_cast<size_t>(i)];
@@ -184,11 +190,16 @@ std::vector<Solution> CLIPPERBatch::solveAsMaximumClique(const maxclique::Params
     o.ifinal = 0;
     o.u = VectorXd::Zero(m);
     o.score = -1;
-    if (params.verbose)
+    if (params.verbose) {
       std::cout << "maxclique: problem " << i << ": m = " << m << ", edges = " << I.edges << ", max core = " << I.max_core
                 << ", heuristic = " << I.heuristic_size << ", clique = " << I.num_nodes
-                << (I.timed_out ? " (timed out)" : "") << ", bb nodes = " << I.bb_nodes << ", " << I.seconds << " s"
-                << std::endl;
+                << (I.timed_out ? " (timed out)" : "") << ", bb nodes = " << I.bb_nodes;
+      if (params.warm_start) {
+        const clipper_maxclique_seed_info_t& S = sinfo[static_cast<size_t>(i)];
+        std::cout << ", seed given / kept / clique = " << S.seed_given << " / " << S.seed_kept << " / " << S.seed_size;
+      }
+      std::cout << ", " << I.seconds << " s" << std::endl;
+    }
   }
   return out;
 }

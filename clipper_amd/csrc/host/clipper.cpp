@@ -374,19 +374,46 @@ void CLIPPER::solve(const VectorXd& _u0) {
 // clipper.cpp:82-97 + maxclique::solve (maxclique.cpp): the maximum clique of the consistency graph C - I, on the
 // device (clipper_hip_max_clique). params.threads is accepted and ignored (the device decides
 // its own parallelism); params.time_limit bounds the search (seconds).
+// With params.warm_start the call is seeded from the context's node list (clipper_hip_max_clique_seeded).
 void CLIPPER::solveAsMaximumClique(const maxclique::Params& params) {
+  if (!params.warm_start) return maxClique(params, nullptr);
+  const int64_t m = clipper_hip_num_associations(handle());
+  std::vector<int> seed(static_cast<size_t>(std::max<int64_t>(m, 1)));
+  const int k = clipper_hip_get_nodes(h_, seed.data(), static_cast<int32_t>(seed.size()));
+  if (k <= 0) throw std::invalid_argument("solveAsMaximumClique: warm_start needs a node list (solve() first)");
+  seed.resize(static_cast<size_t>(k));
+  maxClique(params, &seed);
+}
+
+void CLIPPER::solveAsMaximumClique(const maxclique::Params& params, const std::vector<int>& seed) {
+  maxClique(params, &seed);
+}
+
+// seed: null for the unseeded call
+void CLIPPER::maxClique(const maxclique::Params& params, const std::vector<int>* seed) {
   const int method = params.method == maxclique::Method::EXACT ? CLIPPER_HIP_MC_EXACT
                      : params.method == maxclique::Method::HEU ? CLIPPER_HIP_MC_HEU
                                                                : CLIPPER_HIP_MC_KCORE;
   clipper_maxclique_info_t info{};
-  check(clipper_hip_max_clique(handle(), method, static_cast<double>(params.time_limit), &info), "solveAsMaximumClique");
+  clipper_maxclique_seed_info_t sinfo{};
+  if (seed)
+    check(clipper_hip_max_clique_seeded(handle(), method, static_cast<double>(params.time_limit), seed->data(),
+                                        static_cast<int32_t>(seed->size()), &info, &sinfo),
+          "solveAsMaximumClique");
+  else
+    check(clipper_hip_max_clique(handle(), method, static_cast<double>(params.time_limit), &info), "solveAsMaximumClique");
   std::vector<int> nodes(static_cast<size_t>(info.num_nodes));
   if (info.num_nodes > 0) check(clipper_hip_get_nodes(h_, nodes.data(), info.num_nodes), "solveAsMaximumClique (nodes)");
-  if (params.verbose)
+  if (params.verbose) {
     std::cout << "maxclique: m = " << clipper_hip_num_associations(h_) << ", edges = " << info.edges
               << ", K = " << info.max_core << ", heuristic = " << info.heuristic_size << ", clique = " << info.num_nodes
               << (info.timed_out ? " (time limit)" : "") << ", roots searched / pruned = " << info.roots_searched
-              << " / " << info.roots_pruned << ", " << info.seconds * 1e3 << " ms" << std::endl;
+              << " / " << info.roots_pruned;
+    if (seed)
+      std::cout << ", seed given / kept / clique = " << sinfo.seed_given << " / " << sinfo.seed_kept << " / "
+                << sinfo.seed_size;
+    std::cout << ", " << info.seconds * 1e3 << " ms" << std::endl;
+  }
   soln_.t = info.seconds;
   soln_.ifinal = 0;
   std::swap(soln_.nodes, nodes);

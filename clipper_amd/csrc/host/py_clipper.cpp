@@ -227,7 +227,8 @@ PYBIND11_MODULE(clipperpy, m) {
       .def_readwrite("method", &clipper::maxclique::Params::method)
       .def_readwrite("threads", &clipper::maxclique::Params::threads)
       .def_readwrite("time_limit", &clipper::maxclique::Params::time_limit)
-      .def_readwrite("verbose", &clipper::maxclique::Params::verbose);
+      .def_readwrite("verbose", &clipper::maxclique::Params::verbose)
+      .def_readwrite("warm_start", &clipper::maxclique::Params::warm_start);
 
   py::class_<clipper::sdp::Params>(m, "SDPParams")
       .def(py::init<>())
@@ -339,8 +340,12 @@ PYBIND11_MODULE(clipperpy, m) {
       .def("score_pairwise_consistency", &clipper::CLIPPER::scorePairwiseConsistency,
            "D1"_a.noconvert(), "D2"_a.noconvert(), "A"_a.noconvert())
       .def("solve", &clipper::CLIPPER::solve, "u0"_a.noconvert() = clipper::VectorXd())
-      .def("solve_as_maximum_clique", &clipper::CLIPPER::solveAsMaximumClique,
-           "params"_a = clipper::maxclique::Params{})
+      .def("solve_as_maximum_clique",
+           [](clipper::CLIPPER& c, const clipper::maxclique::Params& params, const py::object& seed) {
+             if (seed.is_none()) c.solveAsMaximumClique(params);
+             else c.solveAsMaximumClique(params, seed.cast<std::vector<int>>());
+           },
+           "params"_a = clipper::maxclique::Params{}, "seed"_a = py::none())
       .def("solve_as_msrc_sdr", &clipper::CLIPPER::solveAsMSRCSDR, "params"_a = clipper::sdp::Params{})
       .def("set_device_sdp", &clipper::CLIPPER::setDeviceSdp, "on"_a)
       .def("get_initial_associations", &clipper::CLIPPER::getInitialAssociations)

@@ -14,6 +14,10 @@
 //      ONE copy of the McCtl array, the compaction of the work list to the unfinished problems, and the time limit.
 // The number of copies and resets between launches does not depend on the number of problems, and per problem the
 // results are a function of the graph alone.
+// A seeded call (DESIGN.md 9 "Seeded calls") hands mc_run a vertex list per problem. The lists travel in the graph
+// part's first copy; after step 3 ONE launch of k_mc_seed turns each into its seed clique Q0 in `out`, and ONE copy of
+// the McCtl array brings the sizes s; HEU's and EXACT's incumbents start at s, and where Q0 wins it is taken from
+// `out` as it lies. A problem without a list, and a call without lists, takes the steps above and no other.
 #pragma once
 
 #include "host_mcplan.hpp"
@@ -25,6 +29,7 @@ constexpr long long MC_PEEL_BUDGET = 1ll << 24;  // row-word operations per peel
 constexpr long long MC_WAVE_BUDGET = 1ll << 18;  // row-word operations per wave and HEU / EXACT launch (~tens of ms)
 constexpr int MC_WAVES_PER_CU = 8;
 constexpr int MC_PEEL_ONLY = -1;  // mc_run's method for clipper_hip_core_numbers: stop after the peel, keep `core`
+using McSeeds = std::vector<std::vector<int32_t>>;  // a seeded call's vertex list per problem (empty: not seeded)
 
 static_assert(sizeof(McItem) == sizeof(clipper_mc_plan::Item), "the plan's table rows are the kernels'");
 static_assert(sizeof(McProb) % 8 == 0 && sizeof(McCtl) % 8 == 0 && sizeof(McSlot) % 8 == 0 && sizeof(McAdjSrc) % 8 == 0,
@@ -53,14 +58,27 @@ struct McSlab {
 
 struct McResult {
   clipper_maxclique_info_t info{};
+  clipper_maxclique_seed_info_t seed{};  // a seeded call
   std::vector<int32_t> nodes;  // ascending
   std::vector<int32_t> core;   // MC_PEEL_ONLY
 };
 
-int mc_check_method(int method) {  // (a caller's method; the driver is also run with MC_PEEL_ONLY)
-  if (method != CLIPPER_HIP_MC_EXACT && method != CLIPPER_HIP_MC_HEU && method != CLIPPER_HIP_MC_KCORE)
+// (a caller's method; the driver is also run with MC_PEEL_ONLY). seeded: an entry point that takes vertex lists
+int mc_check_method(int method, bool seeded = false) {
+  if (method != CLIPPER_HIP_MC_EXACT && method != CLIPPER_HIP_MC_HEU && method != CLIPPER_HIP_MC_KCORE &&
+      !(seeded && method == CLIPPER_HIP_MC_SEED_ONLY))
     return fail(CLIPPER_HIP_E_INVALID, "max clique: unknown method %d", method);
   return 0;
+}
+
+// a caller's vertex list for a problem of m vertices: distinct and in range
+int mc_check_seed(const int32_t* seed, int64_t n, int64_t m) {
+  const int64_t bad = clipper_mc_plan::first_bad_seed(seed, n, static_cast<int32_t>(m));
+  if (bad < 0) return 0;
+  const int32_t v = seed[bad];
+  if (v < 0 || v >= m)
+    return fail(CLIPPER_HIP_E_INVALID, "max clique: seed[%lld] = %d is no vertex of 0..%lld", (long long)bad, v, (long long)m - 1);
+  return fail(CLIPPER_HIP_E_INVALID, "max clique: seed[%lld] = %d repeats an earlier entry", (long long)bad, v);
 }
 
 int mc_check_scope(const Ctx* h) {
@@ -73,9 +91,10 @@ int mc_check_scope(const Ctx* h) {
 
 // The maximum cliques (or, MC_PEEL_ONLY, the core numbers) of the problems of `cs`, which passed mc_check_scope (and
 // `method` mc_check_method) and share a device, a value type and the stream `st`. R[k] is cs[k]'s result; `launches`
-// counts the kernel launches. An error that is one problem's leaves its index in `fault`.
+// counts the kernel launches. An error that is one problem's leaves its index in `fault`. seeds: null, or a checked
+// vertex list per problem (mc_check_seed) and `method` may be CLIPPER_HIP_MC_SEED_ONLY.
 int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStream_t st, int device, PinnedBuf& stage,
-           int& launches, std::vector<McResult>& R, size_t& fault) {
+           int& launches, std::vector<McResult>& R, size_t& fault, const McSeeds* seeds = nullptr) {
   namespace plan = clipper_mc_plan;
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
@@ -91,7 +110,14 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
   std::vector<int32_t> ms(nb);
   for (size_t k = 0; k < nb; ++k) ms[k] = static_cast<int32_t>(cs[k]->m);
   const int64_t cap = static_cast<int64_t>(std::max(1, cs[0]->cus)) * MC_WAVES_PER_CU;
-  const plan::GraphPlan L = plan::make_graph_plan(ms, cap, sizeof(McProb), sizeof(McCtl), sizeof(McAdjSrc));
+  std::vector<int32_t> ngiven;  // (stays empty in an unseeded call)
+  for (size_t k = 0; seeds && k < nb; ++k)
+    if (!(*seeds)[k].empty()) {
+      ngiven.resize(nb, 0);
+      ngiven[k] = static_cast<int32_t>((*seeds)[k].size());
+      R[k].seed.seed_given = ngiven[k];
+    }
+  const plan::GraphPlan L = plan::make_graph_plan(ms, cap, sizeof(McProb), sizeof(McCtl), sizeof(McAdjSrc), ngiven);
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   if (L.bytes + (64u << 20) > free_b)
@@ -152,6 +178,11 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     p.list = g.D<int32_t>(r.list);
     p.out = g.D<int32_t>(r.out) + 1;  // (out[-1]: the count k_mc_collect leaves)
     p.ctl = dctl + k;
+    if (!ngiven.empty() && ngiven[k] > 0) {
+      p.given = g.D<int32_t>(r.given);
+      p.ngiven = ngiven[k];
+      std::memcpy(g.H<int32_t>(r.given), (*seeds)[k].data(), static_cast<size_t>(ngiven[k]) * sizeof(int32_t));
+    }
     probs[k] = p;
     // C: the slices of M (pattern), else the explicit dense C, else the dense store of M (pattern)
     McAdjSrc a{};
@@ -174,7 +205,8 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     a.deg = g.D<int32_t>(r.deg);
     g.H<McAdjSrc>(L.src)[k] = a;
   }
-  if (int rc = up(g, L.up_begin, ctl_end)) return rc;  // (descriptors, sources, control words; the lists come later)
+  // (descriptors, sources, control words, a seeded call's vertex lists; HEU's and EXACT's lists come later)
+  if (int rc = up(g, L.up_begin, ngiven.empty() ? ctl_end : L.given_end)) return rc;
   HIPCHK(hipMemsetAsync(g.D<uint8_t>(L.alive_begin), 0xff, L.alive_bytes, st));
   const int32_t np = static_cast<int32_t>(nb);
   const unsigned gp = static_cast<unsigned>(std::min<size_t>(nb, 65535));  // the grid's problem dimension
@@ -245,6 +277,29 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     }
   }
 
+  // ---- 3s. a seeded call: the seed cliques, one wave per seeded problem with an edge; their sizes with the McCtl copy -----
+  std::vector<int32_t> seeded, s0(nb, 0);
+  if (!ngiven.empty())
+    for (int32_t k : searching)
+      if (ngiven[static_cast<size_t>(k)] > 0) seeded.push_back(k);
+  if (!seeded.empty()) {
+    if (2 * lds1 > 64 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_mc_seed), device, 2 * lds1);
+    if (int rc = put_work(seeded)) return rc;
+    hipLaunchKernelGGL(k_mc_seed, dim3(static_cast<unsigned>(seeded.size())), dim3(64), 2 * lds1, st, dprobs, dwork);
+    if (int rc = launched()) return rc;
+    if (int rc = down(g, L.ctl, ctl_end)) return rc;
+    for (int32_t k : seeded) {
+      const size_t ku = static_cast<size_t>(k);
+      const int32_t s = ctl[ku].seed_size, kept = ctl[ku].seed_kept;
+      if (kept < 1 || kept > ngiven[ku] || s < kept || s > Kmax[ku] + 1) {
+        fault = ku;
+        return fail(CLIPPER_HIP_E_INTERNAL, "max clique: the seed clique's record (size %d, kept %d) is not valid", s, kept);
+      }
+      R[ku].seed.seed_kept = kept;
+      R[ku].seed.seed_size = s0[ku] = s;
+    }
+  }
+
   // one launch over the slot table of `list` (kept in `s` at `tab`), then the copy of the control array
   std::vector<int32_t> tabled;  // the list whose slot table the device holds
   auto launch_slots = [&](const McSlab& s, size_t tab, const std::vector<int32_t>& list, const std::vector<int32_t>& ns,
@@ -284,9 +339,16 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     return 0;
   };
 
-  if (!searching.empty()) {
-    // ---- 4a. HEU ---------------------------------------------------------------------------------------------------
+  if (method == CLIPPER_HIP_MC_SEED_ONLY) {
+    if (!seeded.empty())
+      if (int rc = take_out(seeded, s0)) return rc;
+    for (int32_t k : seeded) R[static_cast<size_t>(k)].seed.winner = 2;
+  } else if (!searching.empty()) {
+    // ---- 4a. HEU (a seed clique of two vertices or more is the incumbent it has to beat: ties go to the seed clique) ----
     std::memset(ctl, 0, nb * sizeof(McCtl));
+    for (int32_t k : seeded)
+      if (s0[static_cast<size_t>(k)] >= 2)
+        ctl[k].key = (static_cast<unsigned long long>(s0[static_cast<size_t>(k)]) << 32) | 0xFFFFFFFFull;
     if (int rc = up(g, L.up_begin, L.up_end)) return rc;
     const std::vector<int32_t> hslots = plan::deal_slots(weight, cap);
     std::vector<int32_t> active = searching;
@@ -295,7 +357,7 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
       active = plan::compact(active, [&](int32_t k) { return ctl[k].head >= ms[static_cast<size_t>(k)]; });
       if (time_out(active)) break;
     }
-    std::vector<int32_t> exact;
+    std::vector<int32_t> exact, heu_won;  // heu_won: the problems whose clique so far is HEU's, not the seed clique
     std::vector<plan::Search> sr(nb, plan::Search{0, 0, 0});
     std::vector<std::vector<int32_t>> roots(nb);
     const std::vector<McCtl> after_heu(ctl, ctl + nb);
@@ -306,16 +368,20 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
       const int32_t m = ms[ku];
       const unsigned long long key = after_heu[ku].key;
       const int h = static_cast<int>(key >> 32);
-      const int seed = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key & 0xFFFFFFFFull));
+      // (the size alone says whether HEU beat the seed clique: seed 0 leaves the tie field of the preload)
+      const bool from_seed = s0[ku] >= 2 && h == s0[ku];
+      const int seed = from_seed ? 0 : static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key & 0xFFFFFFFFull));
       // (every launch finishes the seeds it takes, the first of which has the largest core number, so after one
       // launch the record holds a clique of two vertices or more, time limit or not)
-      if (h < 2 || h > Kmax[ku] + 1 || seed < 0 || seed >= m) {
+      if (h < 2 || h < s0[ku] || h > Kmax[ku] + 1 || seed < 0 || seed >= m) {
         fault = ku;
         return fail(CLIPPER_HIP_E_INTERNAL, "max clique: HEU's record (size %d, seed %d) is not valid", h, seed);
       }
       heu[ku] = h;
       Ik.heuristic_size = h;
       probs[ku].seed = seed;
+      if (!from_seed) heu_won.push_back(k);
+      R[ku].seed.winner = plan::seeded_winner(s0[ku], h, h);
       if (method == CLIPPER_HIP_MC_EXACT && h < Kmax[ku] + 1 && !Ik.timed_out) {
         // EXACT: roots ordered by (core, degree, index); those that can hold a clique larger than HEU's, taken from
         // the end of that order (the largest bound first). They replace the seeds; the incumbent starts at HEU's clique.
@@ -361,9 +427,12 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     if (int rc = up(g, L.up_begin, L.up_end)) return rc;
 
     // ---- 4c. the winning cliques of HEU ---------------------------------------------------------------------------------
-    if (int rc = put_work(searching)) return rc;
-    hipLaunchKernelGGL(k_mc_heu_one, dim3(static_cast<unsigned>(searching.size())), dim3(64), lds1, st, dprobs, dwork);
-    if (int rc = launched()) return rc;
+    // (a seed clique that HEU did not beat lies in `out` since k_mc_seed)
+    if (!heu_won.empty()) {
+      if (int rc = put_work(heu_won)) return rc;
+      hipLaunchKernelGGL(k_mc_heu_one, dim3(static_cast<unsigned>(heu_won.size())), dim3(64), lds1, st, dprobs, dwork);
+      if (int rc = launched()) return rc;
+    }
     if (int rc = take_out(searching, heu)) return rc;
 
     // ---- 4d. EXACT -----------------------------------------------------------------------------------------------------
@@ -387,6 +456,7 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
         Ik.roots_searched = static_cast<int64_t>(ctl[ku].roots_searched);
         Ik.bb_nodes = static_cast<int64_t>(ctl[ku].bb_nodes);
         omega[ku] = static_cast<int32_t>(ctl[ku].key >> 32);
+        R[ku].seed.winner = plan::seeded_winner(s0[ku], heu[ku], omega[ku]);
         if (omega[ku] > heu[ku]) better.push_back(k);
       }
       if (!better.empty()) {
@@ -411,12 +481,15 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
 }
 
 // a lone call: the driver on {h}, with h's stream, device and staging buffer
-int mc_run_one(Ctx* h, int method, double time_limit_s, McResult& r) {
+int mc_run_one(Ctx* h, int method, double time_limit_s, McResult& r, const McSeeds* seeds = nullptr) {
   if (int rc = mc_check_scope(h)) return rc;
+  if (seeds)
+    if (int rc = mc_check_seed((*seeds)[0].data(), static_cast<int64_t>((*seeds)[0].size()), h->m)) return rc;
   std::vector<McResult> R;
   int launches = 0;
   size_t fault = 0;
-  if (int rc = mc_run({h}, method, time_limit_s, h->sh[0].stream, h->sh[0].device, h->mc_stage, launches, R, fault)) return rc;
+  if (int rc = mc_run({h}, method, time_limit_s, h->sh[0].stream, h->sh[0].device, h->mc_stage, launches, R, fault, seeds))
+    return rc;
   r = std::move(R[0]);
   return 0;
 }
@@ -430,6 +503,22 @@ int max_clique_impl(Ctx* h, int method, double time_limit_s, clipper_maxclique_i
   return 0;
 }
 
+// the seeded call: seed == null and nseed == -1 stand for the context's node list
+int max_clique_seeded_impl(Ctx* h, int method, double time_limit_s, const int32_t* seed, int32_t nseed,
+                           clipper_maxclique_info_t* info, clipper_maxclique_seed_info_t* sinfo) {
+  if (int rc = mc_check_method(method, true)) return rc;
+  const bool own = !seed && nseed == -1;
+  if (!own && (nseed < 0 || (nseed > 0 && !seed)))
+    return fail(CLIPPER_HIP_E_INVALID, "max clique: a seed of %d entries at %s", nseed, seed ? "an address" : "NULL");
+  const McSeeds seeds{own ? h->nodes : std::vector<int32_t>(seed, seed + nseed)};
+  McResult r;
+  if (int rc = mc_run_one(h, method, time_limit_s, r, &seeds)) return rc;
+  h->nodes = r.nodes;
+  if (info) *info = r.info;
+  if (sinfo) *sinfo = r.seed;
+  return 0;
+}
+
 int core_numbers_impl(Ctx* h, int32_t* core_out) {
   McResult r;
   if (int rc = mc_run_one(h, MC_PEEL_ONLY, 0.0, r)) return rc;
@@ -439,12 +528,18 @@ int core_numbers_impl(Ctx* h, int32_t* core_out) {
 
 // The maximum cliques of every problem of a batch's last solve: the problems up to BATCH_MAX_M in one driver call, then
 // the larger ones one by one, each with the time that remains (a batch never holds several m^2 / 8 adjacencies at once).
-int batch_max_clique(Batch* b, int method, double time_limit_s, clipper_maxclique_info_t* infos) {
+// A seeded call hands in `seeds` and `offsets` (problem i's vertex list: seeds[offsets[i] .. offsets[i + 1])), or
+// seeded = true and neither: every problem's own node list.
+int batch_max_clique(Batch* b, int method, double time_limit_s, clipper_maxclique_info_t* infos, bool seeded = false,
+                     const int32_t* seeds = nullptr, const int64_t* offsets = nullptr,
+                     clipper_maxclique_seed_info_t* sinfos = nullptr) {
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   auto elapsed = [&] { return std::chrono::duration<double>(clk::now() - t0).count(); };
   if (!b->solved) return fail(CLIPPER_HIP_E_STATE, "max clique: no batch has been solved");
-  if (int rc = mc_check_method(method)) return rc;
+  if (int rc = mc_check_method(method, seeded)) return rc;
+  if (seeded && ((seeds == nullptr) != (offsets == nullptr)))
+    return fail(CLIPPER_HIP_E_INVALID, "max clique: seeds and offsets come together, or neither");
   b->mc_launches = b->mc_batched = b->mc_alone = 0;
   const size_t count = b->res.size();
   std::vector<std::vector<int32_t>> calls(1);  // the problems of each driver call: the batched route first
@@ -453,16 +548,32 @@ int batch_max_clique(Batch* b, int method, double time_limit_s, clipper_maxcliqu
     if (b->kids[i]->m > clipper_mc_plan::BATCH_MAX_M) calls.push_back({static_cast<int32_t>(i)});
     else calls[0].push_back(static_cast<int32_t>(i));
   }
+  McSeeds given(seeded ? count : 0);
+  for (size_t i = 0; i < given.size(); ++i) {
+    if (!offsets) {
+      given[i] = b->res[i].nodes;
+    } else {
+      if (offsets[i] < 0 || offsets[i + 1] < offsets[i])
+        return fail(CLIPPER_HIP_E_INVALID, "problem %zu: seed offsets %lld, %lld", i, (long long)offsets[i], (long long)offsets[i + 1]);
+      given[i].assign(seeds + offsets[i], seeds + offsets[i + 1]);
+    }
+    if (int rc = mc_check_seed(given[i].data(), static_cast<int64_t>(given[i].size()), b->kids[i]->m))
+      return fail(rc, "problem %zu: %s", i, std::string(g_err).c_str());
+  }
   std::vector<McResult> all(count);
   for (size_t c = 0; c < calls.size(); ++c) {
     std::vector<Ctx*> cs;
-    for (int32_t i : calls[c]) cs.push_back(b->kids[static_cast<size_t>(i)]);
+    McSeeds sc;
+    for (int32_t i : calls[c]) {
+      cs.push_back(b->kids[static_cast<size_t>(i)]);
+      if (seeded) sc.push_back(std::move(given[static_cast<size_t>(i)]));
+    }
     // (no time left: the smallest positive limit, so that the call stops after its first launch)
     const double rem = time_limit_s > 0 ? std::max(time_limit_s - elapsed(), 1e-9) : 0.0;
     std::vector<McResult> R;
     int launches = 0;
     size_t fault = 0;
-    if (int rc = mc_run(cs, method, rem, b->stream, b->device, b->hmc, launches, R, fault))
+    if (int rc = mc_run(cs, method, rem, b->stream, b->device, b->hmc, launches, R, fault, seeded ? &sc : nullptr))
       return c > 0 || fault < cs.size()  // (a larger problem's call is all its own)
                  ? fail(rc, "problem %d: %s", calls[c][c > 0 ? 0 : fault], std::string(g_err).c_str()) : rc;
     for (size_t k = 0; k < cs.size(); ++k) all[static_cast<size_t>(calls[c][k])] = std::move(R[k]);
@@ -484,6 +595,7 @@ int batch_max_clique(Batch* b, int method, double time_limit_s, clipper_maxcliqu
     selected_associations(c, R.nodes, R.sel.data());
     all[i].info.seconds = secs;
     if (infos) infos[i] = all[i].info;
+    if (sinfos) sinfos[i] = all[i].seed;
   }
   return 0;
 }

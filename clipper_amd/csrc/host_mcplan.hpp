@@ -8,8 +8,9 @@
 // all of them): G (m rows of nw = ceil(m / 64) words), alive (nw words), degw (mp = m rounded up to even int32). From
 // `host_begin` on what the host reads or writes, mirrored at the same relative offsets by the caller's pinned staging
 // buffer:
-//   up    [up_begin, up_end): the descriptor table, the adjacency sources, the McCtl array, every problem's list and
-//         pos — written by the host before a phase, ONE copy
+//   up    [up_begin, up_end): the descriptor table, the adjacency sources, the McCtl array, the vertex lists of a
+//         seeded call (none otherwise: the offsets after them are those of an unseeded call), every problem's list
+//         and pos — written by the host before a phase, ONE copy
 //   tab   the work list (one int32 per problem) and HEU's slot table ((problem, slot) per dealt slot)
 //   out   per problem m + 2 int32 (count, then the clique), ONE copy back
 //   deg, core   (mp int32 each per problem; deg of all problems, then core of all), ONE copy back
@@ -37,6 +38,7 @@ struct GraphRegions {  // byte offsets into the graph slab
   size_t G, alive, degw, list, pos, out, deg, core;
   int64_t nw;
   int32_t mp;  // m rounded up to even
+  size_t given = 0;  // a seeded call: the caller's vertex list
 };
 
 struct GraphPlan {
@@ -44,6 +46,7 @@ struct GraphPlan {
   size_t bytes = 0, host_begin = 0;
   size_t G_begin = 0, G_bytes = 0, alive_begin = 0, alive_bytes = 0, degw_begin = 0, deg_bytes = 0;
   size_t probs = 0, src = 0, ctl = 0, up_begin = 0, up_end = 0;
+  size_t given_end = 0;  // the end of the seeded problems' vertex lists (no list: the end of the McCtl array)
   size_t work = 0, slot_tab = 0;
   size_t out_begin = 0, out_bytes = 0, deg_begin = 0, core_begin = 0;
   int64_t slot_rows = 0;  // rows HEU's slot table has room for: max(slot_cap, problems)
@@ -96,9 +99,10 @@ inline std::vector<int32_t> deal_slots(const std::vector<int64_t>& weight, int64
 }
 
 // prob_bytes, ctl_bytes, src_bytes: sizeof(McProb), McCtl, McAdjSrc (multiples of 8). slot_cap: slots of the whole
-// call at most (the chip's waves).
+// call at most (the chip's waves). ngiven: the length of each problem's vertex list in a seeded call (empty: no
+// problem has one).
 inline GraphPlan make_graph_plan(const std::vector<int32_t>& m, int64_t slot_cap, size_t prob_bytes, size_t ctl_bytes,
-                                 size_t src_bytes) {
+                                 size_t src_bytes, const std::vector<int32_t>& ngiven = {}) {
   GraphPlan P;
   const size_t count = m.size();
   P.at.resize(count);
@@ -134,6 +138,13 @@ inline GraphPlan make_graph_plan(const std::vector<int32_t>& m, int64_t slot_cap
   P.probs = take(count * prob_bytes);
   P.src = take(count * src_bytes);
   P.ctl = take(count * ctl_bytes);
+  P.given_end = o;
+  for (size_t i = 0; i < ngiven.size() && i < count; ++i)
+    if (ngiven[i] > 0) {
+      o = up_array(o);
+      P.at[i].given = array(static_cast<size_t>(ngiven[i]) * 4);
+      P.given_end = o;
+    }
   o = up_array(o);
   for (size_t i = 0; i < count; ++i) {
     P.at[i].list = array(static_cast<size_t>(P.at[i].mp) * 4);
@@ -257,6 +268,27 @@ inline void root_order(const int32_t* core, const int32_t* deg, int64_t m, int h
   roots.clear();
   for (int64_t i = m - 1; i >= 0; --i)
     if (core[order[static_cast<size_t>(i)]] >= heu) roots.push_back(order[static_cast<size_t>(i)]);
+}
+
+// ---- seeded calls (DESIGN.md 9 "Seeded calls") ----------------------------------------------------------------------
+// The position of the first entry of a caller's vertex list that is out of range or repeats an earlier one, -1 when
+// the list is a set of vertices of 0..m-1.
+inline int64_t first_bad_seed(const int32_t* seed, int64_t n, int32_t m) {
+  std::vector<uint8_t> seen(static_cast<size_t>(std::max<int32_t>(m, 0)), 0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (seed[i] < 0 || seed[i] >= m || seen[static_cast<size_t>(seed[i])]) return i;
+    seen[static_cast<size_t>(seed[i])] = 1;
+  }
+  return -1;
+}
+
+// Whose clique a seeded call returns (clipper_maxclique_seed_info_t::winner): the search's (0) when it raised the
+// incumbent above b = max(s, HEU); else the seed clique's (2) when HEU did not beat its s vertices (ties go to the
+// seed clique; s < 2: the call ran unseeded), else HEU's (1). `found` is the incumbent's size at the end, b for a
+// call that did not search.
+inline int seeded_winner(int s, int b, int found) {
+  if (found > b) return 0;
+  return s >= 2 && b == s ? 2 : 1;
 }
 
 }  // namespace clipper_mc_plan

@@ -1,6 +1,7 @@
 // k_maxclique.hip.h — the maximum-clique solver behind CLIPPER::solveAsMaximumClique:
-// the adjacency of the consistency graph as row bitsets, its core numbers, the greedy clique (HEU) and the
-// bitset branch and bound (EXACT), for every problem of a call. Host side: host_maxclique.hpp, host_mcplan.hpp.
+// the adjacency of the consistency graph as row bitsets, its core numbers, the seed clique of a seeded call, the greedy
+// clique (HEU) and the bitset branch and bound (EXACT), for every problem of a call. Host side: host_maxclique.hpp,
+// host_mcplan.hpp.
 // Part of kernels.hip.h (include that one): hand-written gfx950 device code of the CLIPPER hot path.
 //
 // The graph: vertices 0..m-1, edge (i, j), i != j, exactly when C(i, j) != 0. G[i][w] bit b = edge (i, 64 w + b),
@@ -28,7 +29,9 @@ struct McCtl {
   unsigned long long key;  // incumbent: size << 32 | tie field (HEU: ~seed; EXACT: 0xFFFFFFFE - pos, HEU's clique 0xFFFFFFFF)
   unsigned long long roots_pruned, roots_searched, bb_nodes;
   int32_t overflow;     // EXACT: a branch deeper than the clique-size bound (cannot happen; checked, never silent)
-  int32_t pad[3];
+  int32_t seed_size;    // a seeded call: the vertices of the seed clique Q0 ...
+  int32_t seed_kept;    // ... and how many of them the caller's list gave (k_mc_seed writes both)
+  int32_t pad;
 };
 
 // one EXACT wave's resumable state
@@ -41,8 +44,8 @@ struct McSlot {
 
 // One problem as the device functions below see it. A call keeps a table of them on the device, one row per problem
 // (a lone call: one row), and every kernel fetches its problem's row. The host fills the fields a phase reads: the
-// peel G, nw, m, degw, core, alive, ctl; HEU also list (seeds), nlist; the regeneration seed, out; EXACT list (roots),
-// nlist, pos, heu, D and the slots' state.
+// peel G, nw, m, degw, core, alive, ctl; the seed clique of a seeded call also given, ngiven, out; HEU also list
+// (seeds), nlist; the regeneration seed, out; EXACT list (roots), nlist, pos, heu, D and the slots' state.
 struct McProb {
   const uint64_t* G;     // m rows of nw words
   int64_t nw;
@@ -58,6 +61,9 @@ struct McProb {
   int32_t seed;          // the regeneration of HEU's clique: its seed ...
   int32_t nslots;        // EXACT: the problem's slots (read by the collection of the record only)
   int32_t* out;          // ... and where it goes (out[-1]: the count k_mc_collect leaves)
+  const int32_t* given;  // a seeded call: the caller's vertex list (distinct, in range) ...
+  int32_t ngiven;        // ... and its length (0: the problem is not seeded)
+  int32_t pad;
   McCtl* ctl;
   McSlot* slots;         // EXACT, per slot: state, D x nw words of stack, D + 1 path entries, D + 1 record entries
   uint64_t* arena;
@@ -271,11 +277,12 @@ __device__ __forceinline__ void mc_peel(const McProb& P, long long budget, uint6
 // final best size the clique of every seed that can reach that size is the one thr = 0 gives.
 // Returns the size; `out` (may be null, lane 0 writes) receives the clique in pick order. Adds the row-word
 // operations to `work`.
-__device__ int mc_greedy(const uint64_t* __restrict__ G, int64_t nw, const int32_t* __restrict__ core, int v,
-                         int thr, uint64_t* C, int32_t* out, long long& work, int lane) {
-  int size = 1;
-  if (out && lane == 0) out[0] = v;
-  int u = v;
+// The loop is entered after `size` picks, the last of which is u: with v = u = the seed and size = 1 by mc_greedy,
+// where the candidates are the seed's row; with v = -1 by mc_seed_clique, where C already holds the common
+// neighbourhood of the picks so far (the first intersection with u's row then changes nothing).
+__device__ __forceinline__ int mc_greedy_loop(const uint64_t* __restrict__ G, int64_t nw,
+                                              const int32_t* __restrict__ core, int v, int u, int size, int thr,
+                                              uint64_t* C, int32_t* out, long long& work, int lane) {
   while (true) {
     unsigned long long bk = 0;
     const uint64_t* row = G + static_cast<int64_t>(u) * nw;
@@ -305,6 +312,79 @@ __device__ int mc_greedy(const uint64_t* __restrict__ G, int64_t nw, const int32
     ++size;
   }
   return size;
+}
+
+__device__ int mc_greedy(const uint64_t* __restrict__ G, int64_t nw, const int32_t* __restrict__ core, int v,
+                         int thr, uint64_t* C, int32_t* out, long long& work, int lane) {
+  if (out && lane == 0) out[0] = v;
+  return mc_greedy_loop(G, nw, core, v, v, 1, thr, C, out, work, lane);
+}
+
+// ---- the seed clique Q0 of a seeded call (DESIGN.md 9 "Seeded calls"; one wave) --------------------------------------
+// Reduce: degS(v) = |N(v) & S| for the vertices of the caller's list S, computed once; the candidates start as S;
+// take the candidate of largest degS (ties: smallest index), intersect the candidates with its row, until none is
+// left. Extend: the candidates become the common neighbourhood of the vertices taken, over all vertices, and
+// mc_greedy's loop goes on from there (largest core number, ties smallest index, no threshold). Q0, in pick order,
+// goes to P.out, its size to out[-1] and ctl->seed_size, the vertices the reduction took to ctl->seed_kept.
+// LDS: S, C (nw words each). degS is kept by the position in the list, in P.degw (dead after the peel), so that a
+// pick reads the list and its degS in order; it is written and read through L2 like the peel's degrees.
+__device__ __forceinline__ void mc_seed_clique(const McProb& P, uint64_t* mc_lds) {
+  const uint64_t* __restrict__ G = P.G;
+  const int64_t nw = P.nw;
+  const int32_t* __restrict__ given = P.given;
+  const int32_t n = P.ngiven;
+  int32_t* degS = P.degw;
+  uint64_t* S = mc_lds;
+  uint64_t* C = mc_lds + nw;
+  const int lane = threadIdx.x;
+  if (n <= 0) return;  // (the host lists seeded problems only; with a vertex in S the reduction takes one)
+  for (int64_t w = lane; w < nw; w += 64) {
+    S[w] = 0ull;
+    C[w] = ~0ull;
+  }
+  __syncthreads();
+  for (int i = lane; i < n; i += 64)
+    atomicOr(reinterpret_cast<unsigned long long*>(&S[given[i] >> 6]), 1ull << (given[i] & 63));
+  __syncthreads();
+  for (int i = 0; i < n; ++i) {
+    const uint64_t* row = G + static_cast<int64_t>(given[i]) * nw;
+    int d = 0;
+    for (int64_t w = lane; w < nw; w += 64) d += __popcll(row[w] & S[w]);
+    d = mc_wave_sum(d);
+    if (lane == 0) __hip_atomic_store(degS + i, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __threadfence();
+  __syncthreads();
+  int kept = 0, u = -1;
+  while (true) {
+    unsigned long long bk = 0;
+    for (int i = lane; i < n; i += 64) {
+      const int x = given[i];
+      if (!((S[x >> 6] >> (x & 63)) & 1ull)) continue;
+      const unsigned long long kx =
+          (static_cast<unsigned long long>(mc_load_i32(degS + i) + 1) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(x));
+      bk = kx > bk ? kx : bk;
+    }
+    bk = mc_wave_max_u64(bk);
+    if (bk == 0) break;
+    u = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(bk & 0xFFFFFFFFull));
+    if (lane == 0) P.out[kept] = u;
+    ++kept;
+    const uint64_t* row = G + static_cast<int64_t>(u) * nw;
+    __syncthreads();
+    for (int64_t w = lane; w < nw; w += 64) {
+      S[w] &= row[w];
+      C[w] &= row[w];
+    }
+    __syncthreads();
+  }
+  long long work = 0;
+  const int size = mc_greedy_loop(G, nw, P.core, -1, u, kept, 0, C, P.out, work, lane);
+  if (lane == 0) {
+    P.out[-1] = size;
+    P.ctl->seed_size = size;
+    P.ctl->seed_kept = kept;
+  }
 }
 
 // Seeds (the host's order: core descending) taken through ctl->head; a seed whose core + 1 is below the best size
@@ -531,6 +611,7 @@ __device__ __forceinline__ McProb mc_fetch(const McProb* __restrict__ probs, int
   P.pos = mc_global(t.pos);
   P.list = mc_global(t.list);
   P.out = mc_global(t.out);
+  P.given = mc_global(t.given);
   P.ctl = mc_global(t.ctl);
   P.slots = mc_global(t.slots);
   P.arena = mc_global(t.arena);
@@ -602,6 +683,13 @@ __global__ __launch_bounds__(64) void k_mc_heu_one(const McProb* __restrict__ pr
   extern __shared__ uint64_t mc_cand[];
   const McProb P = mc_fetch(probs, work[blockIdx.x]);
   mc_heu_one(P, mc_cand);
+}
+
+// one wave per seeded problem of the work list: its seed clique; dynamic LDS: two bitsets of the call's largest nw
+__global__ __launch_bounds__(64) void k_mc_seed(const McProb* __restrict__ probs, const int32_t* __restrict__ work) {
+  extern __shared__ uint64_t mc_lds[];
+  const McProb P = mc_fetch(probs, work[blockIdx.x]);
+  mc_seed_clique(P, mc_lds);
 }
 
 // one wave per slot, with the stack, path and record it keeps between launches

@@ -63,6 +63,7 @@ class CLIPPERBatch {
   /// one afterwards. Solution i is what clipper.cpp:92-96 leaves (nodes ascending, u = 0, score = -1, ifinal = 0; t:
   /// the whole call's), its nodes those of a lone CLIPPER::solveAsMaximumClique; getSelectedAssociations(i) follows it.
   /// params.time_limit bounds the whole call; params.threads is ignored; params.verbose prints one line per problem.
+  /// params.warm_start starts every problem's search from its own node list (clipper_hip_batch_max_clique_seeded).
   /// The solver state is untouched. Throws std::logic_error before any solve.
   std::vector<Solution> solveAsMaximumClique(const maxclique::Params& params = maxclique::Params{});
   /// the relaxations of the last solveAsMSRCSDR (X, lambdas, evec1, thr, nodes, iters, pobj, dobj, times)

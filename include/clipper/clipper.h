@@ -39,13 +39,16 @@ namespace clipper {
 namespace maxclique {
 /// Mirror of the reference maxclique::Method / Params (maxclique.h:15-23). EXACT = ROBIN* (a maximum clique), HEU = the
 /// greedy clique of DESIGN.md 9, KCORE = ROBIN (the vertices of maximum core number). `threads` is accepted and
-/// ignored (the device decides); `time_limit` (seconds) bounds HEU's and EXACT's search.
+/// ignored (the device decides); `time_limit` (seconds) bounds HEU's and EXACT's search. `warm_start` (not in the
+/// reference; the last field, so the reference's aggregate initialisers keep compiling) starts HEU and EXACT from the
+/// current node list, e.g. the last solve()'s (clipper_hip_max_clique_seeded, DESIGN.md 9 "Seeded calls").
 enum class Method { EXACT, HEU, KCORE };
 struct Params {
   Method method = Method::EXACT;
   size_t threads = 24;
   int time_limit = 3600;
   bool verbose = false;
+  bool warm_start = false;
 };
 }  // namespace maxclique
 
@@ -110,7 +113,12 @@ class CLIPPER {
   /// Graduated projected gradient ascent (clipper.cpp:69-78, 172-323). Random u0 if empty.
   void solve(const VectorXd& u0 = VectorXd());
 
-  void solveAsMaximumClique(const maxclique::Params& params = {});  ///< on the device (clipper_hip_max_clique)
+  /// On the device (clipper_hip_max_clique). With params.warm_start the search starts from the current node list (the
+  /// last solve()'s, or an earlier clique's): std::invalid_argument when there is none.
+  void solveAsMaximumClique(const maxclique::Params& params = {});
+  /// The same, started from the vertex list `seed` (distinct indices of associations, in any order, which need not
+  /// form a clique; an empty list: the unseeded call). params.warm_start is not looked at.
+  void solveAsMaximumClique(const maxclique::Params& params, const std::vector<int>& seed);
   void solveAsMSRCSDR(const sdp::Params& params = {});              ///< the stub, or the device (setDeviceSdp)
 
   const Solution& getSolution() const { return soln_; }
@@ -160,6 +168,7 @@ class CLIPPER {
   PathStats getPathStats() const { return stats_; }
 
  private:
+  void maxClique(const maxclique::Params& params, const std::vector<int>* seed);  ///< seed: null for the unseeded call
   Params params_;
   invariants::PairwiseInvariantPtr invariant_;
   bool parallelize_ = true;  ///< OpenMP for user-defined (host-evaluated) invariants only

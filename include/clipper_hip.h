@@ -317,6 +317,27 @@ typedef struct clipper_maxclique_info_t {
   double seconds;          /* wall time of the call                                                        */
 } clipper_maxclique_info_t;
 int clipper_hip_max_clique(clipper_hip_t* h, int method, double time_limit_s, clipper_maxclique_info_t* info);
+/* The seeded call (DESIGN.md 9 "Seeded calls"): clipper_hip_max_clique started from a clique the caller already has
+ * good reason to believe in, such as the node list clipper_hip_solve left. seed: nseed distinct vertices in any order,
+ * which need not form a clique (seed = NULL and nseed = -1: the context's node list); an index out of range or a
+ * repeated one returns CLIPPER_HIP_E_INVALID naming its position, before any device work. The list is turned into a
+ * maximal clique Q0 on the device: its vertices are taken by the number of neighbours they have in the list (ties:
+ * smallest index) while they are adjacent to all taken so far, then the clique is extended over all vertices as HEU
+ * extends one. HEU and EXACT start from Q0 as their incumbent: HEU returns its own clique only when it is larger than
+ * Q0 (heuristic_size reports the larger size), EXACT a larger clique than both when there is one, and then the very
+ * list clipper_hip_max_clique returns. The result is a function of the graph and of the list as a set. An empty list,
+ * an edgeless graph and a Q0 of one (isolated) vertex give the unseeded call's result; KCORE ignores the list.
+ * CLIPPER_HIP_MC_SEED_ONLY returns Q0 and runs neither HEU nor EXACT (no list or an edgeless graph: no vertex).
+ * clipper_hip_max_clique and clipper_hip_batch_max_clique refuse that method. */
+typedef struct clipper_maxclique_seed_info_t {
+  int32_t seed_given;   /* distinct vertices handed in                    */
+  int32_t seed_kept;    /* of them, in the seed clique                    */
+  int32_t seed_size;    /* s = |Q0|                                       */
+  int32_t winner;       /* 0: the search, 1: HEU's clique, 2: the seed clique */
+} clipper_maxclique_seed_info_t;
+enum { CLIPPER_HIP_MC_SEED_ONLY = 3 };  /* seeded entry points only: return Q0, run neither HEU nor EXACT */
+int clipper_hip_max_clique_seeded(clipper_hip_t* h, int method, double time_limit_s, const int32_t* seed, int32_t nseed,
+                                  clipper_maxclique_info_t* info, clipper_maxclique_seed_info_t* seed_info);
 /* The core number of every vertex of the same graph (Batagelj-Zaversnik): m int32. */
 int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out /* m */);
 
@@ -630,6 +651,16 @@ int clipper_hip_batch_sdp(clipper_hip_batch_t* b, const clipper_sdp_params_t* pa
  * CLIPPER_HIP_E_STATE before any solve, CLIPPER_HIP_E_INVALID for an unknown method; a batch of 0 problems returns 0. */
 int clipper_hip_batch_max_clique(clipper_hip_batch_t* b, int method, double time_limit_s,
                                  clipper_maxclique_info_t* infos /* one per problem of the last solve, or NULL */);
+/* clipper_hip_max_clique_seeded for every problem of the batch's last solve call, in the same launches as the
+ * unseeded batched call plus one for the seed cliques. Problem i's vertex list is seeds[offsets[i] .. offsets[i + 1])
+ * (offsets: one entry per problem and one more; an empty list: that problem runs unseeded); seeds = offsets = NULL:
+ * every problem's own node list, as the last solve (or a later relaxation or clique call) left it. Per problem the list
+ * and both records' fields are those of the lone seeded call on a lone context, the schedule-dependent counters
+ * excepted. An invalid index returns CLIPPER_HIP_E_INVALID naming the problem and the position before any device
+ * work; the batch stays usable. seed_infos: one record per problem, or NULL. */
+int clipper_hip_batch_max_clique_seeded(clipper_hip_batch_t* b, int method, double time_limit_s, const int32_t* seeds,
+                                        const int64_t* offsets, clipper_maxclique_info_t* infos,
+                                        clipper_maxclique_seed_info_t* seed_infos);
 /* The last clipper_hip_batch_max_clique: kernel launches of the batched route, problems that ran in them, problems
  * that ran alone. Any pointer may be NULL. */
 int clipper_hip_batch_max_clique_stats(const clipper_hip_batch_t* b, int32_t* launches, int32_t* n_batched,
