@@ -75,10 +75,14 @@ int round_nodes(Ctx* h, int rounding, const std::vector<double>& u, double F, st
     for (int64_t i = 0; i < m; ++i)
       if (u[static_cast<size_t>(i)] > 0.0) nodes.push_back(static_cast<int32_t>(i));
   } else if (rounding == CLIPPER_ROUNDING_DSD) {
-    // :294-300 — exact densest subgraph of the graph induced by the non-zero entries of u
+    // :294-300 — exact densest subgraph of the graph induced by the non-zero entries of u; where u == 0 (every pair
+    // forbidden: the iteration ends at the zero vector) the list is empty, which dsd::solve reads as EVERY node
+    // (dsd.cpp:278-284) — as clipper_hip_densest_subgraph does with k <= 0
     std::vector<int32_t> S;
     for (int64_t i = 0; i < m; ++i)
       if (u[static_cast<size_t>(i)] > 0.0) S.push_back(static_cast<int32_t>(i));
+    if (S.empty())
+      for (int64_t i = 0; i < m; ++i) S.push_back(static_cast<int32_t>(i));
     if (int rc = densest_subgraph_of(h, S, nodes)) return rc;
   } else {
     const int omega = static_cast<int>(std::round(F));  // :305

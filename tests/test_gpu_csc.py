@@ -319,6 +319,11 @@ def test_set_sparse_equals_set_matrix(m, storage):
     assert np.array_equal(r.get_affinity_matrix(), np.eye(m))
     yM, yC = r.matvec(u0)
     assert not yM.any() and not yC.any()
+    # ... and solved as the graph without edges it is: one node, the oracle's (slices that hold no entry at all)
+    se, sr = c.solve(u0), r.solve(u0)
+    assert se.nodes.tolist() == sr.nodes.tolist() and len(sr.nodes) == 1 and se.ifinal == sr.ifinal
+    assert abs(se.score - sr.score) <= 1e-6 * max(1.0, abs(sr.score)) and np.all(np.isfinite(se.u))
+    assert np.max(np.abs(se.u - sr.u)) <= 1e-7 and (storage != abi.STORE_F64_CSC or se.n_trials == sr.n_trials)
     # ... and a stored diagonal, which the reference would count once on top of the identity, is refused
     D = sp.csc_matrix(np.triu(M, 1) + np.diag(np.full(m, 0.25)))
     D.sort_indices()
