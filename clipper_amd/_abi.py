@@ -57,7 +57,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_sdp_solve_batch", "clipper_hip_batch_sdp", "clipper_hip_batch_get_sdp",
     "clipper_hip_batch_max_clique", "clipper_hip_batch_max_clique_stats",
     "clipper_hip_max_clique_seeded", "clipper_hip_batch_max_clique_seeded",
-    "clipper_hip_sdp_set_route", "clipper_hip_sdp_route",
+    "clipper_hip_sdp_set_route", "clipper_hip_sdp_route", "clipper_hip_match_descriptors",
 ]
 
 
@@ -200,6 +200,11 @@ def _sdp_result(n, X, Y, lam, ev, nodes, info) -> SdpResult:
                      dobj=info.dobj, info=info)
 
 
+class MatchParams(C.Structure):
+    """clipper_match_params_t"""
+    _fields_ = [("knn", C.c_int32), ("mutual", C.c_int32), ("ratio", C.c_double), ("max_sqdist", C.c_double)]
+
+
 class BatchProblem(C.Structure):
     """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
 
@@ -286,6 +291,9 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_distance_based_correspondences.argtypes = [
         C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, ip, C.c_int64]
     L.clipper_hip_distance_based_correspondences.restype = C.c_int64
+    L.clipper_hip_match_descriptors.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(MatchParams),
+                                                ip, dp, C.c_int64, ip, dp]
+    L.clipper_hip_match_descriptors.restype = C.c_int64
     L.clipper_hip_set_profiling.argtypes = [vp, C.c_int]
     L.clipper_hip_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.clipper_hip_bench_matvec.argtypes = [vp, C.c_int, dp]
@@ -926,6 +934,35 @@ def distance_based_correspondences(P0, P1, knn: int, radius: float, enforce_1to1
         raise RuntimeError(f"clipper_hip error {n}: {_last_error()}")
     n = int(n)
     return np.stack([buf[:n], buf[n:2 * n]], axis=1).astype(np.int32)
+
+
+def match_descriptors(F0, F1, knn: int = 1, mutual: bool = True, ratio: float = 0.0, max_sqdist: float = 0.0,
+                      device: int = 0, return_lists: bool = False):
+    """clipper_hip_match_descriptors: putative associations from feature descriptors on the device. F0: d x n0,
+    F1: d x n1 (columns = descriptors, as `clipper::Data`), 1 <= d <= 64. Every point of F0 is matched to its knn
+    nearest descriptors of F1; `mutual` keeps a pair only if it is also found the other way round, `ratio` (0 = off,
+    needs knn == 1) is Lowe's test sqd_0 < ratio^2 sqd_1, `max_sqdist` (<= 0 = off) bounds the squared distance.
+    Returns (A n x 2 int32, sqd n), and with return_lists also the forward lists (idx n0 x knn int32, sqd n0 x knn)
+    before the filters."""
+    L = load_library()
+    F0c, F1c = _f64_colmajor(F0), _f64_colmajor(F1)
+    if F0c.ndim != 2 or F1c.ndim != 2 or F0c.shape[0] != F1c.shape[0]:
+        raise ValueError("F0 and F1 must be d x n0 and d x n1")
+    d, n0 = F0c.shape
+    n1 = F1c.shape[1]
+    prm = MatchParams(int(knn), int(bool(mutual)), float(ratio), float(max_sqdist))
+    cap = max(n0 * max(int(knn), 0), 0)
+    buf = np.zeros(2 * max(cap, 1), dtype=np.int32)
+    sqd = np.zeros(max(cap, 1), dtype=np.float64)
+    idx = np.zeros((n0, max(int(knn), 0)), dtype=np.int32) if return_lists else None
+    lsq = np.zeros((n0, max(int(knn), 0)), dtype=np.float64) if return_lists else None
+    n = L.clipper_hip_match_descriptors(device, _dp(F0c), n0, _dp(F1c), n1, d, C.byref(prm), _ip(buf), _dp(sqd), cap,
+                                        _ip(idx) if return_lists else None, _dp(lsq) if return_lists else None)
+    if n < 0:
+        raise ClipperError(f"clipper_hip error {n}: {_last_error()}")
+    n = int(n)
+    A = np.stack([buf[:n], buf[n:2 * n]], axis=1).astype(np.int32)
+    return (A, sqd[:n].copy(), idx, lsq) if return_lists else (A, sqd[:n].copy())
 
 
 class HipBatch:

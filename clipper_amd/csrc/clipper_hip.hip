@@ -2,7 +2,7 @@
 // RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver),
 // host_solve.hpp (the solve of one context), host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp
 // (the fills, matrix set / get, mat-vecs, nearest neighbours; included last: it holds its kernels' place in the code
-// object), host_csc_input.hpp (the sparse input's
+// object), host_match.hpp (putative associations from feature descriptors; behind it), host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
@@ -58,6 +58,7 @@ using namespace clipper_hip;
 #include "host_batchsolve.hpp"
 #include "host_maxclique.hpp"
 #include "host_matrix_io.hpp"
+#include "host_match.hpp"
 
 extern "C" {
 
@@ -365,6 +366,14 @@ int64_t clipper_hip_distance_based_correspondences(int device, const double* P0,
                                                    int64_t capacity) try {
   if (!A_out && capacity > 0) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   return distance_based_correspondences(device, P0, n0, P1, n1, d, knn, radius, enforce_1to1, A_out, capacity);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- putative associations from feature descriptors (host_match.hpp) ---------------------------
+
+int64_t clipper_hip_match_descriptors(int device, const double* F0, int64_t n0, const double* F1, int64_t n1, int d,
+                                      const clipper_match_params_t* params, int32_t* A_out, double* sqd_out,
+                                      int64_t capacity, int32_t* nn_idx_out, double* nn_sqd_out) try {
+  return match_descriptors(device, F0, n0, F1, n1, d, params, A_out, sqd_out, capacity, nn_idx_out, nn_sqd_out);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_set_window(clipper_hip_t* h, int window) try {

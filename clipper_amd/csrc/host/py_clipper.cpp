@@ -16,6 +16,7 @@
 #include "clipper/batch.h"
 #include "clipper/clipper.h"
 #include "clipper/invariants/device.h"
+#include "clipper/registration.h"
 #include "clipper/sdp.h"
 #include "clipper/utils.h"
 
@@ -210,6 +211,21 @@ PYBIND11_MODULE(clipperpy, m) {
 
   py::module m_utils = m.def_submodule("utils");
   pybind_utils(m_utils);
+  // putative associations from feature descriptors, on the device (include/clipper/registration.h)
+  m_utils.def(
+      "match_descriptors",
+      [](const clipper::MatrixXd& F0, const clipper::MatrixXd& F1, int knn, bool mutual, double ratio,
+         double max_sqdist) {
+        clipper::registration::MatchParams prm;
+        prm.knn = knn;
+        prm.mutual = mutual;
+        prm.ratio = ratio;
+        prm.max_sqdist = max_sqdist;
+        return clipper::registration::match_descriptors(F0, F1, prm);
+      },
+      "F0"_a, "F1"_a, "knn"_a = 1, "mutual"_a = true, "ratio"_a = 0.0, "max_sqdist"_a = 0.0,
+      "Match feature descriptors (d x n0 and d x n1, one per column, d <= 64) into putative associations on the GPU: "
+      "brute-force nearest neighbours with an optional mutual check, ratio test and distance bound.");
 
   // The reference fills `clipperpy.dsd` with pybind_utils (py_clipper.cpp:127-128; pybind_dsd is
   // never called), so that is what existing scripts see; the exact DSD solver is out of scope.

@@ -38,6 +38,7 @@
 //   k_rowview.hip.h   the row list of a row view of M (the live rows of the solver's current points)
 //   k_subproblem.hip.h  the live sub-problem: column counts of a view, the selection, the hand-over and the way back
 //   k_knn.hip.h       brute-force k-nearest neighbours (putative associations)
+//   k_match.hip.h     the same search in descriptor space, up to 64 coordinates (putative associations from features)
 //   k_maxclique.hip.h the maximum clique of the consistency graph: adjacency bitsets, core numbers, HEU, EXACT
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
 //   k_sdp_wide.hip.h  the same relaxation for one problem over the whole chip, a launch per Jacobi step (n <= 1024)
@@ -53,6 +54,7 @@
 #include "k_rowview.hip.h"
 #include "k_subproblem.hip.h"
 #include "k_knn.hip.h"
+#include "k_match.hip.h"
 #include "k_maxclique.hip.h"
 #include "k_sdp.hip.h"
 #include "k_sdp_wide.hip.h"

@@ -1,7 +1,8 @@
 """Host-side pieces either side of the hot path for the 3-D registration use case:
 a PLY point reader, the putative-association generator of the reference's bunny example, and the
-rigid-transform estimate that consumes the selected associations. Plain numpy; nothing here
-touches the device — the path between them is clipper_hip_affinity_* / clipper_hip_solve.
+rigid-transform estimate that consumes the selected associations. Plain numpy, except for the two association generators that
+search nearest neighbours on the device (ground_truth_associations, match_descriptors) — the path
+between them is clipper_hip_affinity_* / clipper_hip_solve.
 
 Reference sites (relative to /root/reference): the data-set recipe restates
 examples/python/ex4_bunny.ipynb cell 2 (sample the model, ground-truth transform, uniform noise in
@@ -187,6 +188,16 @@ def ground_truth_associations(pcd0: np.ndarray, pcd1: np.ndarray, radius: float,
     (clipper_hip_distance_based_correspondences). pcd*: n x 3, rows = points."""
     from . import _abi as abi
     return abi.distance_based_correspondences(pcd0.T, pcd1.T, 1, radius, True, device=device)
+
+
+def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool = True, ratio: float = 0.0,
+                      max_sqdist: float = 0.0, device: int = 0):
+    """Putative associations from feature descriptors, on the GPU (clipper_hip_match_descriptors).
+    F0: n0 x d, F1: n1 x d, rows = descriptors (the layout feature extractors produce), d <= 64.
+    Returns (A n x 2 int32, sqd n): see clipper_amd._abi.match_descriptors."""
+    from . import _abi as abi
+    return abi.match_descriptors(np.asarray(F0, dtype=np.float64).T, np.asarray(F1, dtype=np.float64).T, knn=knn,
+                                 mutual=mutual, ratio=ratio, max_sqdist=max_sqdist, device=device)
 
 
 def generate_synthetic_correspondences(n0: int, n1: int, Agood: np.ndarray, m: int, rho: float,

@@ -3,8 +3,9 @@
  * @brief The host-side neighbours of the CLIPPER hot path that the reference keeps in its
  *        benchmark utilities (benchmarks/bm_utils.h: namespace utils): PLY vertex reader, synthetic
  *        putative associations, precision / recall — plus the closed-form rigid transform that
- *        consumes the selected associations (examples/python/ex4_bunny.ipynb). Thin C++ wrappers
- *        over the C ABI (include/clipper_hip.h); no device work.
+ *        consumes the selected associations (examples/python/ex4_bunny.ipynb) and the feature
+ *        matcher that produces the putative ones. Thin C++ wrappers over the C ABI
+ *        (include/clipper_hip.h); only match_descriptors works on the device.
  */
 #pragma once
 
@@ -64,6 +65,35 @@ inline void estimate_rigid_transform(const invariants::Data& D1, const invariant
   if (D1.rows() != 3 || D2.rows() != 3) throw std::invalid_argument("points must be 3 x n");
   if (clipper_hip_estimate_rigid_transform(D1.data(), D1.cols(), D2.data(), D2.cols(), A.data(), A.rows(), T))
     throw std::invalid_argument(clipper_hip_last_error());
+}
+
+/// The filters of match_descriptors (clipper_match_params_t)
+struct MatchParams {
+  int knn = 1;              ///< 1..8 nearest descriptors of F1 per point of F0
+  bool mutual = true;       ///< keep (i, j) only if i is among the knn nearest descriptors of F0 to j
+  double ratio = 0.0;       ///< 0 = off; else Lowe's test sqd_0 < ratio^2 sqd_1, in (0, 1), needs knn == 1
+  double max_sqdist = 0.0;  ///< <= 0 = off; else the largest squared descriptor distance kept
+};
+
+/// Putative associations from feature descriptors, by brute-force nearest neighbours on the device
+/// (clipper_hip_match_descriptors). F0: d x n0, F1: d x n1, one descriptor per column, d <= 64. Rows (i, j) with
+/// i ascending, then by distance: what scorePairwiseConsistency takes.
+inline Association match_descriptors(const invariants::Data& F0, const invariants::Data& F1,
+                                     const MatchParams& params = {}, int device = 0) {
+  if (F0.rows() != F1.rows()) throw std::invalid_argument("descriptors of different length");
+  const clipper_match_params_t prm{params.knn, params.mutual ? 1 : 0, params.ratio, params.max_sqdist};
+  const int64_t cap = static_cast<int64_t>(F0.cols()) * (params.knn > 0 ? params.knn : 0);
+  Association buf(cap > 0 ? cap : 1, 2);
+  const int64_t n = clipper_hip_match_descriptors(device, F0.data(), F0.cols(), F1.data(), F1.cols(),
+                                                  static_cast<int>(F0.rows()), &prm, buf.data(), nullptr, cap,
+                                                  nullptr, nullptr);
+  if (n < 0) throw std::invalid_argument(clipper_hip_last_error());
+  Association A(n, 2);
+  for (int64_t r = 0; r < n; ++r) {
+    A(r, 0) = buf.data()[r];
+    A(r, 1) = buf.data()[n + r];
+  }
+  return A;
 }
 
 }  // namespace registration

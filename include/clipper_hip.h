@@ -456,6 +456,29 @@ int64_t clipper_hip_distance_based_correspondences(int device, const double* P0,
                                                    double radius, int enforce_1to1,
                                                    int32_t* A_out, int64_t capacity);
 
+/* Putative associations from FEATURE DESCRIPTORS (FPFH 33, FCGF / SpinNet / Predator 32 numbers per point): every
+ * point of F0 is matched to its knn nearest descriptors of F1 by brute force on the device, with the same contract
+ * as clipper_hip_knn (fp64 squared L2 distances added in coordinate order, ascending, the lower index first among
+ * equal distances), for 1 <= d <= 64. Row (i, nn_k(i)), k < knn, is kept iff all of: nn_k(i) exists; max_sqdist <= 0
+ * or sqd_k(i) <= max_sqdist; ratio <= 0 or F1 has a single point or sqd_0(i) < ratio^2 * sqd_1(i) (Lowe's test on
+ * squared distances, strict); mutual == 0 or i is among the knn nearest descriptors of F0 to nn_k(i). */
+typedef struct {
+  int32_t knn;          /* 1..8 neighbours per point of F0 */
+  int32_t mutual;       /* 0 | 1 */
+  double  ratio;        /* 0 = off; else in (0, 1), needs knn == 1 */
+  double  max_sqdist;   /* <= 0 = off */
+} clipper_match_params_t;
+
+/* F0: d x n0, F1: d x n1 column-major as `clipper::Data` (each descriptor contiguous); every value finite. A_out:
+ * column-major n x 2 as `clipper::Association` with n = the return value (<0: error), i ascending then k ascending —
+ * clipper_hip_stage_inputs takes it unchanged; capacity in rows (n0*knn always suffices). sqd_out (may be NULL): the
+ * squared distance of each row. nn_idx_out / nn_sqd_out (may be NULL): the forward lists before the filters, n0 x knn
+ * row-major, -1 / 1e300 where F1 has fewer points. Stand-alone: needs no context. */
+int64_t clipper_hip_match_descriptors(int device, const double* F0, int64_t n0, const double* F1, int64_t n1, int d,
+                                      const clipper_match_params_t* params,
+                                      int32_t* A_out, double* sqd_out, int64_t capacity,
+                                      int32_t* nn_idx_out, double* nn_sqd_out);
+
 /* Line-search window: how many consecutive step sizes alpha, alpha*beta, ... of the
  * backtracking line search (clipper.cpp:234-251) one pass over M evaluates at once. The
  * trial sequence, the accepted trial and the result are those of the reference for every
