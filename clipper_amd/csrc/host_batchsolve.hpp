@@ -5,7 +5,7 @@
 // A call
 //   1. checks every problem (nothing reaches the device if one is invalid),
 //   2. stages all inputs (D1, D2, the association lists, u0) in one pinned buffer and copies it with ONE H2D copy,
-//   3. queues every child's fill back to back (fill_X_enqueue: run_affinity with `queued`) and waits ONCE; children whose
+//   3. queues every child's fill back to back (fill_builtin with `queued`: run_affinity's) and waits ONCE; children whose
 //      slice arenas overflowed (the first use of a size) fill again, in a second round of their own. A user-defined
 //      invariant (kind 3, batch_fill_custom) fills every child's dense store in ONE launch instead, then queues the
 //      children's slice builds back to back and waits once per round of builds,
@@ -314,8 +314,7 @@ int batch_stage(Batch* b, BatchCall& K) {
 // A child whose route cannot be queued (d not 2 or 3, dense storage, the rectangular route) has run its fill to the
 // end inside its turn: it is not `queued`, and nothing is left to complete.
 int batch_fill(Batch* b, const BatchCall& K) {
-  const double* f = K.f;
-  const double aeps = K.P->affinityeps;
+  const FillInvariant inv = FillInvariant::from_list(K.kind, K.f, K.P->affinityeps);
   std::vector<char> queued(static_cast<size_t>(K.n), 0);
   bool first = true;  // round 0 hands every child its inputs as well
   return clipper_fits::until_fits(
@@ -324,9 +323,7 @@ int batch_fill(Batch* b, const BatchCall& K) {
         if (first)
           if (int rc = batch_stage_child(b, K, i)) return rc;
         bool q = false;
-        if (int rc = K.kind == 1 ? fill_euclidean_enqueue(b->kids[i], EuclidParams{f[0], f[1], f[2], aeps}, q)
-                                 : fill_pointnormal_enqueue(b->kids[i], PointNormalParams{f[0], f[1], f[2], f[3], aeps}, q))
-          return rc;
+        if (int rc = fill_builtin(b->kids[i], inv, &q)) return rc;
         queued[i] = q;
         return first ? batch_stage_u0(b, K, i) : 0;
       },

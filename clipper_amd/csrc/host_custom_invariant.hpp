@@ -169,10 +169,8 @@ int custom_fill_begin(Ctx* h, const CustomFill& f, bool batched, std::vector<hip
     HIPCHK(hipSetDevice(h->sh[k].device));
     if (int rc = custom_function(f.inv, h->sh[k].device, f64, fn[k], batched)) return rc;
   }
-  h->fill_kind = 3;
-  h->fill_e = EuclidParams{};
-  h->fill_n = PointNormalParams{};
-  h->fill_E2 = 0.f;
+  h->fill = FillInvariant{};
+  h->fill.kind = 3;
   return 0;
 }
 

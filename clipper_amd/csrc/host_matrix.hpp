@@ -803,9 +803,9 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
 
 int fill_euclidean(Ctx* h, const EuclidParams& prm);  // the matrix from the staged points (clipper_hip.hip)
 int fill_pointnormal(Ctx* h, const PointNormalParams& prm);
-// a batch's: as run_affinity with `queued`
-int fill_euclidean_enqueue(Ctx* h, const EuclidParams& prm, bool& queued);
-int fill_pointnormal_enqueue(Ctx* h, const PointNormalParams& prm, bool& queued);
+// the body behind both, for callers that hold the invariant as a record (the live sub-problem's child, a batch's
+// children: `queued` as run_affinity's)
+int fill_builtin(Ctx* h, const FillInvariant& inv, bool* queued);
 
 // stage_inputs, then the fill: affinity_total_ms counts both
 template <typename Params>

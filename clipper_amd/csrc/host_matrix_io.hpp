@@ -1,7 +1,7 @@
-// host_matrix_io.hpp — the matrix in and out of a context: the two affinity fills, the dense and sparse setters, the
+// host_matrix_io.hpp — the matrix in and out of a context: the affinity fill, the dense and sparse setters, the
 // getter, the mat-vecs of the test API, and the nearest-neighbour search that puts associations together before any
 // context exists. Part of clipper_hip.hip (one translation unit; included there, last). The order of the bodies here
-// is the order in which the code object holds their kernels.
+// is the order in which the code object holds their kernels (the fill's: with_builtin_invariant's order of invariants).
 #pragma once
 
 namespace {
@@ -18,108 +18,63 @@ int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S,
 }
 
 
-// The two fills (declared in host_matrix.hpp): defined here, behind the batch, so that the fill kernels keep their place
-// in the code object. Each has one body, reached through fill_X (the fill runs to its end) and fill_X_enqueue (a
-// batch's: see run_affinity's `queued`).
-// EuclideanDistance over the staged points: the matrix of this context
-int euclidean_fill(Ctx* h, const EuclidParams& prm, bool* queued) {
-  if (h->staged_d < 1) return fail(CLIPPER_HIP_E_STATE, "clipper_hip_stage_inputs not called");
-  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
-  const int d = h->staged_d;
-  h->fill_kind = 1;  // what a row view of this matrix is filled with later (host_rowview.hpp)
-  h->fill_e = prm;
-  h->fill_n = PointNormalParams{};
-  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsilon, h->staged_maxabs, d));
-  return run_affinity(h, use_sym_fill(h) && (d == 2 || d == 3), [&](Shard& s) {
-    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
-              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
-        block(256);
-    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
-    const int32_t* A0 = s.Adev;
-    const int32_t* A1 = s.Adev + mm;
-#define LAUNCH_EUCLID(T, D)                                                                 \
-  hipLaunchKernelGGL((k_affinity_euclid<T, D>), grid, block, 0, s.stream,                   \
-                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, \
-                     A0, A1, prm)
-#define LAUNCH_EUCLID_COMPACT(T, D)                                                         \
-  hipLaunchKernelGGL((k_affinity_euclid_compact<T, D>), grid, block, 0, s.stream,           \
-                     static_cast<T*>(s.S), W, mm, c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f,  \
-                     s.P2f, pstride, A0, A1, prm, thr)
-    const float thr = guarded_threshold(prm.epsilon, h->staged_maxabs, d);
-    if (use_sym_fill(h) && (d == 2 || d == 3)) {
-      const int nT = static_cast<int>(ceil_div(mm, AT));
-      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
-      const PointNormalParams none{};
-      const float E2 = guarded_threshold_sq(thr);
+// The fill with a built-in invariant (declared in host_matrix.hpp): defined here, behind the batch, so that the fill
+// kernels keep their place in the code object. One body for every invariant, reached with `queued` null (the fill runs
+// to its end) or not (a batch's: see run_affinity's `queued`). `inv`: the kind and its parameters; the matrix of this
+// context is then the one scored with it over the staged points, and a row view of it is filled from them later.
+int fill_builtin(Ctx* h, const FillInvariant& inv, bool* queued) {
+  // refused before anything changes: the matrix held stays, and the record of what it was scored with
+  if (!with_builtin_invariant(inv, h->staged_d, [](auto, const auto&) {}))
+    return fail(inv.kind == 1 || inv.kind == 2 ? CLIPPER_HIP_E_STATE : CLIPPER_HIP_E_INVALID,
+                inv.kind == 1   ? "clipper_hip_stage_inputs not called"
+                : inv.kind == 2 ? "PointNormalDistance needs staged inputs with d == 6"
+                                : "not a built-in invariant");
+  h->fill = inv;
+  int rc = 0;
+  with_builtin_invariant(h, [&](auto tag, const auto& prm) {
+    using Inv = decltype(tag);
+    const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
+    const int d = h->staged_d;
+    h->fill.E = guarded_threshold(Inv::threshold(prm), h->staged_maxabs, Inv::prefilter_dim(d));
+    h->fill.E2 = guarded_threshold_sq(h->fill.E);
+    const float thr = h->fill.E, E2 = h->fill.E2;
+    // the route: the symmetric tiles, else the compacting strips, else the plain kernel (the only one without a
+    // prefilter: run-time dimensions, CLIPPER_HIP_AFFINITY=plain)
+    const bool sym = Inv::PD > 0 && use_sym_fill(h);
+    const bool compact = Inv::PD > 0 && !h->plain_affinity;
+    rc = run_affinity(h, sym, [&](Shard& s) {
+      const int64_t c0 = static_cast<int64_t>(s.slot) * W;
+      const int32_t* A0 = s.Adev;
+      const int32_t* A1 = s.Adev + mm;
       dispatch_vt(h, [&](auto t) {
         using T = decltype(t);
-        T* S = static_cast<T*>(sizeof(T) == 8 ? nullptr : s.S);  // (slices with fp64 values: no dense store on this route)
-        if (d == 3) launch_sym<T>(k_affinity_sym<3, false, T>, g, s.stream, S, W, mm, nT, s, pstride, A0, A1, prm, none, E2, h->csc_out);
-        else launch_sym<T>(k_affinity_sym<2, false, T>, g, s.stream, S, W, mm, nT, s, pstride, A0, A1, prm, none, E2, h->csc_out);
+        if constexpr (Inv::PD > 0) {
+          if (sym) {
+            const int nT = static_cast<int>(ceil_div(mm, AT));
+            const dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
+            T* S = static_cast<T*>(sizeof(T) == 8 ? nullptr : s.S);  // (slices with fp64 values: no dense store on this route)
+            launch_sym<T>(k_affinity_sym<Inv, T>, g, s.stream, S, W, mm, nT, s, pstride, A0, A1, prm, E2, h->csc_out);
+            return;
+          }
+        }
+        const dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)), static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK)));
+        if constexpr (Inv::PD > 0) {
+          if (compact) {
+            hipLaunchKernelGGL((k_affinity_compact<T, Inv>), grid, dim3(256), 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
+                               AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f, s.P2f, pstride, A0, A1, prm, thr);
+            return;
+          }
+        }
+        hipLaunchKernelGGL((k_affinity_plain<T, Inv>), grid, dim3(256), 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
+                           AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, A0, A1, prm);
       });
-      h->csc_emitted = (h->csc_out.Pre != nullptr);
-      return;
-    }
-    const bool compact = !h->plain_affinity && (d == 2 || d == 3);
-    dispatch_vt(h, [&](auto t) {
-      using T = decltype(t);
-      if (compact && d == 3) LAUNCH_EUCLID_COMPACT(T, 3);
-      else if (compact && d == 2) LAUNCH_EUCLID_COMPACT(T, 2);
-      else if (d == 3) LAUNCH_EUCLID(T, 3);
-      else if (d == 2) LAUNCH_EUCLID(T, 2);
-      else LAUNCH_EUCLID(T, 0);
-    });
-#undef LAUNCH_EUCLID_COMPACT
-#undef LAUNCH_EUCLID
-  }, queued);
+      if (sym) h->csc_emitted = (h->csc_out.Pre != nullptr);
+    }, queued);
+  });
+  return rc;
 }
-int fill_euclidean(Ctx* h, const EuclidParams& prm) { return euclidean_fill(h, prm, nullptr); }
-int fill_euclidean_enqueue(Ctx* h, const EuclidParams& prm, bool& queued) { return euclidean_fill(h, prm, &queued); }
-
-
-// PointNormalDistance over the staged points: the matrix of this context
-int pointnormal_fill(Ctx* h, const PointNormalParams& prm, bool* queued) {
-  if (h->staged_d != 6)
-    return fail(CLIPPER_HIP_E_STATE, "PointNormalDistance needs staged inputs with d == 6");
-  const int64_t mm = h->m, W = h->W, pstride = h->staged_pstride;
-  h->fill_kind = 2;
-  h->fill_e = EuclidParams{};
-  h->fill_n = prm;
-  h->fill_E2 = guarded_threshold_sq(guarded_threshold(prm.epsp, h->staged_maxabs, 3));
-  return run_affinity(h, use_sym_fill(h), [&](Shard& s) {
-    dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)),
-              static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK))),
-        block(256);
-    const int64_t c0 = static_cast<int64_t>(s.slot) * W;
-    const float thr = guarded_threshold(prm.epsp, h->staged_maxabs, 3);
-    if (use_sym_fill(h)) {
-      const int nT = static_cast<int>(ceil_div(mm, AT));
-      dim3 g(static_cast<unsigned>(static_cast<int64_t>(nT) * (nT + 1) / 2));
-      const EuclidParams none{};
-      dispatch_vt(h, [&](auto t) {
-        using T = decltype(t);
-        launch_sym<T>(k_affinity_sym<3, true, T>, g, s.stream, static_cast<T*>(sizeof(T) == 8 ? nullptr : s.S), W, mm, nT, s,
-                      pstride, s.Adev, s.Adev + mm, none, prm, guarded_threshold_sq(thr), h->csc_out);
-      });
-      h->csc_emitted = (h->csc_out.Pre != nullptr);
-      return;
-    }
-    if (h->plain_affinity)
-      dispatch_vt(h, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((k_affinity_pointnormal<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
-                           AFF_ROWS_PER_BLK, s.P1, s.P2, pstride, s.Adev, s.Adev + mm, prm);
-      });
-    else
-      dispatch_vt(h, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((k_affinity_pointnormal_compact<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, mm,
-                           c0, AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f, s.P2f, pstride, s.Adev, s.Adev + mm, prm, thr);
-      });
-  }, queued);
-}
-int fill_pointnormal(Ctx* h, const PointNormalParams& prm) { return pointnormal_fill(h, prm, nullptr); }
-int fill_pointnormal_enqueue(Ctx* h, const PointNormalParams& prm, bool& queued) { return pointnormal_fill(h, prm, &queued); }
+int fill_euclidean(Ctx* h, const EuclidParams& prm) { return fill_builtin(h, FillInvariant::euclid(prm), nullptr); }
+int fill_pointnormal(Ctx* h, const PointNormalParams& prm) { return fill_builtin(h, FillInvariant::pointnormal(prm), nullptr); }
 
 // A user-defined invariant over the staged points (host_custom_invariant.hpp): every shard's dense store from the
 // invariant's own fill kernel, then the slices from it as for any dense store. No rectangular fill exists for it
@@ -178,7 +133,7 @@ int begin_matrix(Ctx* h, int64_t m) {
   h->has_matrix = false;
   h->csc_valid = false;
   h->total_slice_bytes = 0.0;
-  h->fill_kind = 0;
+  h->fill.kind = 0;
   rowview_drop(h);
   drop_explicit_c(h);
   return ensure_problem(h, m);

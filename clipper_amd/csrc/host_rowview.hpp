@@ -15,18 +15,20 @@
 namespace {
 
 // ---- k_affinity_rect for the invariant the current matrix was scored with -------------------------
-template <typename K>
+template <typename K, typename Params>
 void launch_rect_kernel(K kernel, int lds_bytes, dim3 grid, hipStream_t stream, const RectGeom& G,
                         const Shard& s, int64_t pstride, const int32_t* A0, const int32_t* A1,
-                        const EuclidParams& e, const PointNormalParams& n, float E2, const SliceOut& O) {
+                        const Params& prm, float E2, const SliceOut& O) {
   raise_dynamic_lds(reinterpret_cast<const void*>(kernel), s.device, lds_bytes);
   hipLaunchKernelGGL(kernel, grid, dim3(AT_WAVES * 64), lds_bytes, stream, G, s.P1, s.P2, s.P1f, s.P2f,
-                     pstride, A0, A1, e, n, E2, O);
+                     pstride, A0, A1, prm, E2, O);
 }
 
+// a built-in invariant with a prefilter (the tile kernels work on its fp32 squared lengths)
 bool rect_fill_possible(const Ctx* h) {
-  return (h->fill_kind == 1 && (h->staged_d == 2 || h->staged_d == 3)) ||
-         (h->fill_kind == 2 && h->staged_d == 6);
+  bool tiled = false;
+  with_builtin_invariant(h, [&](auto inv, const auto&) { tiled = decltype(inv)::PD > 0; });
+  return tiled;
 }
 
 // The slices of M[rows, this shard's columns] into the store O describes. rowmap == null: all rows.
@@ -47,31 +49,30 @@ int launch_rect(Ctx* h, Shard& s, const int32_t* rowmap, int64_t nrows, const Sl
   const int64_t ps = h->staged_pstride;
   // a thin view (fewer 128-wide tiles than two per CU): 64-wide tiles — see k_affinity_rect
   const bool thin = nTr * ceil_div(W, 128) <= 2 * static_cast<int64_t>(h->cus);
-  dispatch_vt(h, [&](auto t) {
-    using VT = decltype(t);
-    auto run = [&](auto twc) {
-      constexpr int TW = decltype(twc)::value;
-      G.nTc = static_cast<int>(ceil_div(W, TW));
-      const int64_t ntiles = nTr * G.nTc;
-      constexpr int64_t PER_LAUNCH = int64_t(1) << 22;  // x 512 threads < 2^32 work-items per dispatch
-      constexpr int L = rect_lds_bytes<VT, TW>();
-      for (int64_t t0 = 0; t0 < ntiles; t0 += PER_LAUNCH) {
-        G.tile0 = t0;
-        const dim3 grid(static_cast<unsigned>(std::min<int64_t>(PER_LAUNCH, ntiles - t0)));
-        if (h->fill_kind == 2)
-          launch_rect_kernel(k_affinity_rect<3, true, VT, TW>, L, grid, s.stream, G, s, ps, A0, A1, h->fill_e, h->fill_n, h->fill_E2, O);
-        else if (h->staged_d == 3)
-          launch_rect_kernel(k_affinity_rect<3, false, VT, TW>, L, grid, s.stream, G, s, ps, A0, A1, h->fill_e, h->fill_n, h->fill_E2, O);
-        else
-          launch_rect_kernel(k_affinity_rect<2, false, VT, TW>, L, grid, s.stream, G, s, ps, A0, A1, h->fill_e, h->fill_n, h->fill_E2, O);
-      }
-    };
-    if constexpr (rect_tw<VT>() == 64) {
-      run(std::integral_constant<int, 64>{});
-    } else {
-      if (thin) run(std::integral_constant<int, 64>{});
-      else run(std::integral_constant<int, 128>{});
-    }
+  with_builtin_invariant(h, [&](auto inv, const auto& prm) {
+    using Inv = decltype(inv);
+    if constexpr (Inv::PD > 0)
+      dispatch_vt(h, [&](auto t) {
+        using VT = decltype(t);
+        auto run = [&](auto twc) {
+          constexpr int TW = decltype(twc)::value;
+          G.nTc = static_cast<int>(ceil_div(W, TW));
+          const int64_t ntiles = nTr * G.nTc;
+          constexpr int64_t PER_LAUNCH = int64_t(1) << 22;  // x 512 threads < 2^32 work-items per dispatch
+          constexpr int L = rect_lds_bytes<VT, TW>();
+          for (int64_t t0 = 0; t0 < ntiles; t0 += PER_LAUNCH) {
+            G.tile0 = t0;
+            const dim3 grid(static_cast<unsigned>(std::min<int64_t>(PER_LAUNCH, ntiles - t0)));
+            launch_rect_kernel(k_affinity_rect<Inv, VT, TW>, L, grid, s.stream, G, s, ps, A0, A1, prm, h->fill.E2, O);
+          }
+        };
+        if constexpr (rect_tw<VT>() == 64) {
+          run(std::integral_constant<int, 64>{});
+        } else {
+          if (thin) run(std::integral_constant<int, 64>{});
+          else run(std::integral_constant<int, 128>{});
+        }
+      });
   });
   HIPCHK(hipGetLastError());
   return 0;

@@ -734,7 +734,7 @@ int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, 
   // points: a row view of it must no longer be re-scored from what is staged (it would mix two point
   // sets, and the device-side coverage check looks at rows, not at values) — from here on it is
   // viewed through the filter of its own slices, until an affinity call scores the new points.
-  h->fill_kind = 0;
+  h->fill.kind = 0;
   rowview_drop(h);
   int rc = ensure_problem(h, m);
   if (rc) return rc;
@@ -809,14 +809,37 @@ bool raise_dynamic_lds(const void* fn, int device, int bytes) {
 }
 
 // k_affinity_sym needs more dynamic LDS than the 64 KiB a kernel gets by default
-template <typename VT, typename K>
+template <typename VT, typename K, typename Params>
 void launch_sym(K kernel, dim3 grid, hipStream_t stream, VT* S, int64_t W, int64_t mm, int nT,
                 const Shard& s, int64_t pstride, const int32_t* A0, const int32_t* A1,
-                const EuclidParams& e, const PointNormalParams& n, float E2, const CscOut& O) {
+                const Params& prm, float E2, const CscOut& O) {
   constexpr int L = at_sym_lds_bytes<VT>();
   raise_dynamic_lds(reinterpret_cast<const void*>(kernel), s.device, L);
   hipLaunchKernelGGL(kernel, grid, dim3(AT_WAVES * 64), L, stream, S, W, mm, nT, s.P1, s.P2,
-                     s.P1f, s.P2f, pstride, A0, A1, e, n, E2, O);
+                     s.P1f, s.P2f, pstride, A0, A1, prm, E2, O);
+}
+
+// The built-in invariant a context's matrix is scored with, as its policy type (k_affinity.hip.h) and parameters:
+// f(Inv{}, prm). The one place that maps (fill.kind, staged_d) to a kernel family — EuclideanDistance at d = 3 or 2 has
+// every route, at any other d the plain kernel alone (Inv::PD == 0); PointNormalDistance needs d == 6. False, and f
+// not called: no built-in invariant (kinds 0 and 3), or one the staged points do not fit.
+template <typename F>
+bool with_builtin_invariant(const FillInvariant& inv, int staged_d, F&& f) {
+  if (inv.kind == 1 && staged_d >= 1) {
+    if (staged_d == 3) f(EuclidInv<3>{}, inv.e);
+    else if (staged_d == 2) f(EuclidInv<2>{}, inv.e);
+    else f(EuclidInv<0>{}, inv.e);
+    return true;
+  }
+  if (inv.kind == 2 && staged_d == 6) {
+    f(PointNormalInv{}, inv.n);
+    return true;
+  }
+  return false;
+}
+template <typename F>
+bool with_builtin_invariant(const Ctx* h, F&& f) {
+  return with_builtin_invariant(h->fill, h->staged_d, std::forward<F>(f));
 }
 
 

@@ -299,6 +299,35 @@ struct SubProblem {
   double build_ms = 0.0;
 };
 
+// The invariant a context's matrix was scored with. kind: 0 = none (a matrix handed over, or the points replaced since:
+// no rectangular fill, no live sub-problem, views by filter), 1 = EuclideanDistance (e), 2 = PointNormalDistance (n),
+// 3 = a user-defined one (as 0). with_builtin_invariant (host_solver.hpp) turns kinds 1 and 2 into a policy type.
+struct FillInvariant {
+  int kind = 0;
+  union {
+    EuclidParams e;
+    PointNormalParams n{};
+  };
+  float E = 0.f, E2 = 0.f;  // the fp32 prefilter's guarded threshold and its square (set by the fill)
+  static FillInvariant euclid(const EuclidParams& p) {
+    FillInvariant f;
+    f.kind = 1;
+    f.e = p;
+    return f;
+  }
+  static FillInvariant pointnormal(const PointNormalParams& p) {
+    FillInvariant f;
+    f.kind = 2;
+    f.n = p;
+    return f;
+  }
+  // from the batch ABI's (kind, parameter list): f = {sigma, epsilon, mindist} or {sigp, epsp, sign, epsn}
+  static FillInvariant from_list(int kind, const double* f, double affinityeps) {
+    return kind == 1 ? euclid(EuclidParams{f[0], f[1], f[2], affinityeps})
+                     : pointnormal(PointNormalParams{f[0], f[1], f[2], f[3], affinityeps});
+  }
+};
+
 }  // namespace
 
 struct clipper_hip_ctx {
@@ -366,12 +395,8 @@ struct clipper_hip_ctx {
   bool borrowed_stream = false;  // sh[0].stream is a batch's (host_batchsolve.hpp): not this context's to destroy
   int last_solver = 0;     // what the last solve ran on: 0 = streaming launches, 1 = resident
 
-  // what built the matrix, kept so that a row view can be filled from the same points later:
-  // 0 = nothing (setMatrixData: no view), 1 = EuclideanDistance, 2 = PointNormalDistance
-  int fill_kind = 0;
-  EuclidParams fill_e{};
-  PointNormalParams fill_n{};
-  float fill_E2 = 0.f;
+  // what built the matrix, kept so that a row view can be filled from the same points later
+  FillInvariant fill;
   // row-view policy (host_rowview.hpp)
   double total_slice_bytes = 0.0;  // column shards: bytes of all shards' slices (gather_slice_bytes)
   ViewPolicy rvp{};           // the cost model the device-side policy works with (host_rowview.hpp)

@@ -64,7 +64,7 @@ int sub_stage(Ctx* h, Ctx* c, int64_t nS) {
   c->resident_mode = 1;    // (a solve that is handed over mid-way never starts on the resident solver)
   c->rv_mode = 1;          // no views inside it: its rows are the live rows
   c->nodes.clear();
-  c->fill_kind = 0;
+  c->fill.kind = 0;
   rowview_drop(c);
   int rc = ensure_problem(c, nS);
   if (rc) return rc;
@@ -158,7 +158,7 @@ int sub_prepare_v(Ctx* h) {
       c->parent = h;
     }
     if (int r2 = sub_stage(h, c, nS)) return r2;
-    return h->fill_kind == 1 ? fill_euclidean(c, h->fill_e) : fill_pointnormal(c, h->fill_n);
+    return fill_builtin(c, h->fill, nullptr);
   };
   const int storage = h->compressed ? (h->storage == CLIPPER_HIP_STORE_F64 ? CLIPPER_HIP_STORE_F64_CSC : CLIPPER_HIP_STORE_F32_CSC)
                                     : h->storage;

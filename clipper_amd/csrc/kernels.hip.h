@@ -33,7 +33,7 @@
 //   k_csc.hip.h       producers of the slices: emission from the fill kernel's LDS image, groups
 //   k_resident.hip.h  the resident solver: findDenseClique as one launch for problems that fit on chip
 //   k_rv_resident.hip.h  the resident solver on a row view: the iterations that stream a view, as one launch
-//   k_affinity.hip.h  k_gather_points, k_affinity_* (plain, compacting strips, symmetric tiles + emission)
+//   k_affinity.hip.h  k_gather_points, EuclidInv / PointNormalInv, k_affinity_* (plain, compacting strips, tiles + emission)
 //   k_matrix.hip.h    k_from_dense_upper, k_from_csc, k_gather_sub
 //   k_rowview.hip.h   the row list of a row view of M (the live rows of the solver's current points)
 //   k_subproblem.hip.h  the live sub-problem: column counts of a view, the selection, the hand-over and the way back

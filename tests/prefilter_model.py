@@ -4,9 +4,9 @@ infrastructure: tests/test_prefilter_model.py checks on the CPU that neither pre
 exact fp64 rule |l1 - l2| < eps keeps (the promise behind C == pattern(M)); the kernels themselves are checked on the
 GPU (tests/test_gpu_fill_boundaries.py).
 
-  strip form     (k_affinity_euclid_compact, k_affinity_pointnormal_compact):
+  strip form     (k_affinity_compact):
                  keep  <=>  |sqrt(s1) - sqrt(s2)| < E                       (raw v_sqrt_f32)
-  sqrt-free form (k_affinity_sym, k_affinity_rect):
+  sqrt-free form (prefilter_close: k_affinity_sym and k_affinity_rect through tile_score_rows):
                  keep  <=>  t <= 0  or  t*t < (4 * 1.0000038147f) * (s1*s2),  t = (s1 + s2) - E^2
 
 s1, s2 are the squared lengths, summed in fp32 by a sequential fmaf chain from the fp32 copies of the points
@@ -30,7 +30,7 @@ THRESHOLD_INF = 3.0e38
 SQUARES_INF = 1.0e38
 # host_solver.hpp, guarded_threshold_sq: `if (!(E < 1.0e19f)) return infinity`
 THRESHOLD_SQ_INF = np.float32(1.0e19)
-# k_affinity.hip.h, k_affinity_sym / k_affinity_rect: `t * t < (4.0f * 1.0000038147f) * (s1 * s2)`
+# k_affinity.hip.h, prefilter_close (the one place in device code): `t * t < (4.0f * 1.0000038147f) * (s1 * s2)`
 MARGIN = np.float32(1.0000038147)  # = 1 + 2^-18
 
 
@@ -149,7 +149,7 @@ def keep_strip(s1: np.ndarray, s2: np.ndarray, E) -> np.ndarray:
 
 
 def keep_sqrt_free(s1: np.ndarray, s2: np.ndarray, E2) -> np.ndarray:
-    """k_affinity_sym / k_affinity_rect: `t <= 0 || t * t < (4.0f * 1.0000038147f) * (s1 * s2)`."""
+    """prefilter_close (k_affinity_sym, k_affinity_rect): `t <= 0 || t * t < (4.0f * 1.0000038147f) * (s1 * s2)`."""
     s1, s2 = np.asarray(s1, np.float32), np.asarray(s2, np.float32)
     t = (s1 + s2) - np.asarray(E2, np.float32)
     k = np.float32(4.0) * MARGIN

@@ -118,7 +118,7 @@ def test_set_matrix_paths(m):
 
 
 def test_pointnormal_and_other_fill_kernels(monkeypatch):
-    """PointNormalDistance through k_affinity_sym<3, true>; the strip / plain fill kernels
+    """PointNormalDistance through k_affinity_sym<PointNormalInv>; the strip / plain fill kernels
     through k_csc_build (CLIPPER_HIP_AFFINITY)."""
     p = synth.make_pointnormal_problem(900, 0.8, seed=9)
     inv = p.meta["invariant"]

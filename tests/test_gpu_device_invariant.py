@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STORAGES = [abi.STORE_F32, abi.STORE_F64, abi.STORE_F32_CSC, abi.STORE_F64_CSC]
 
-# EuclideanDistance in euclidean_distance.cpp's order with k_affinity_euclid's fma chain; params = {sigma, epsilon, mindist}
+# EuclideanDistance in euclidean_distance.cpp's order with EuclidInv::score's fma chain (k_affinity.hip.h); params = {sigma, epsilon, mindist}
 EUCLID_SRC = r"""
 #include <hip/hip_runtime.h>
 __device__ double clipper_invariant(const double* ai, const double* aj, const double* bi, const double* bj,

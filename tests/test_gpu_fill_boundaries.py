@@ -3,13 +3,14 @@ grid step either side, epsilon one ulp either side of c, mindist exactly at / on
 origin and around large dyadic offsets, where the fp32 copies the prefilter works on lose the grid's low bits. Every
 route must keep exactly the pairs the oracle keeps (C == pattern(M)): the fp32 prefilter may never reject a pair the
 fp64 rule keeps. Routes (CLIPPER_HIP_AFFINITY, storage, shards -> fill kernel):
-  default, one shard, fp32 values or fp64 slices, d in {2, 3}  k_affinity_sym<d, PN, float | double>
-  default, one shard, dense fp64                               k_affinity_euclid_compact / _pointnormal_compact
-  default, column shards, slices                               k_affinity_rect (run_affinity_rect)
-  default, column shards, dense                                k_affinity_euclid_compact / _pointnormal_compact
-  strip                                                        k_affinity_euclid_compact / _pointnormal_compact
-  plain, or d not in {2, 3}                                    k_affinity_euclid / _pointnormal
-  row view of M[rows, :] (clipper_hip_view_matvec, solve)      k_affinity_rect
+  default, one shard, fp32 values or fp64 slices, d in {2, 3}  k_affinity_sym<Inv, float | double>
+  default, one shard, dense fp64                               k_affinity_compact<T, Inv>
+  default, column shards, slices                               k_affinity_rect<Inv, VT, TW> (run_affinity_rect)
+  default, column shards, dense                                k_affinity_compact<T, Inv>
+  strip                                                        k_affinity_compact<T, Inv>
+  plain, or d not in {2, 3}                                    k_affinity_plain<T, Inv>
+  row view of M[rows, :] (clipper_hip_view_matvec, solve)      k_affinity_rect<Inv, VT, TW>
+(Inv: the invariant's policy type of k_affinity.hip.h — EuclidInv<2 | 3>, EuclidInv<0> for any other d, PointNormalInv.)
 The live sub-problem's child fill (k_affinity_sym on the points k_sub_gather_points gathers) runs in the staged test
 below, but on no boundary pair: on the problems whose selected set holds the boundary pairs the solve does not hand over.
 """
@@ -38,9 +39,9 @@ PN_PRM = dict(sigp=gen.EPS, sign=0.10, epsn=0.35)
 
 def _route(storage, nshards, mode, d):
     if mode == "plain" or d not in (2, 3):
-        return "k_affinity_euclid/pointnormal"
+        return "k_affinity_plain"
     if mode == "strip" or storage == abi.STORE_F64 or (nshards > 1 and storage not in CSCS):
-        return "k_affinity_*_compact"
+        return "k_affinity_compact"
     return "k_affinity_sym" if nshards == 1 else "k_affinity_rect"
 
 
