@@ -1,10 +1,12 @@
 // host_csc_input.hpp — the caller's sparse (M, C) as clipper_hip_set_sparse reads them: the structure checks, the upper
-// triangle, the C == pattern(M) test and the symmetric lists the slices are packed from. Pure host code (no HIP):
+// triangle, the C == pattern(M) test and the symmetric lists the slices are packed from; and the value check of both
+// setters (check_values_csc, check_values_dense_upper). Pure host code (no HIP):
 // tests/cpp/test_csc_input.cpp compiles it with g++ alone. A refusal comes back as its message (empty: accepted); the
 // caller hands it to fail(). Nothing here catches std::bad_alloc: it reaches the entry point's guard.
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -83,6 +85,41 @@ std::string upper_only(const char* what, int64_t m, CscRef& a, CscLists& out, in
     out.cp[static_cast<size_t>(j) + 1] = static_cast<int64_t>(out.ri.size());
   }
   a = CscRef{out.cp.data(), out.ri.data(), out.va.data()};
+  return {};
+}
+
+// The values of a handed-over matrix, refused before anything is touched: a non-finite value anywhere in the strict
+// upper triangle (every later product would be NaN), and — when the storage asked for holds fp32 values (`f32`) — a
+// finite value whose float cast is infinite. The round-to-nearest-even cast gives infinity from FLT_MAX plus half its
+// last place on: 0x1.ffffffp+127. Entries on or below the diagonal are never read, so they are not looked at.
+std::string check_value(const char* what, int64_t i, int64_t j, double v, bool f32) {
+  if (!std::isfinite(v))
+    return format("%s: entry (%lld,%lld) is not finite (%g)", what, static_cast<long long>(i), static_cast<long long>(j), v);
+  if (f32 && std::fabs(v) >= 0x1.ffffffp+127)
+    return format("%s: entry (%lld,%lld) = %.17g rounds to infinity in fp32 storage", what, static_cast<long long>(i),
+                  static_cast<long long>(j), v);
+  return {};
+}
+
+// a CSC matrix whose structure check_csc has accepted
+std::string check_values_csc(const char* what, int64_t m, const CscRef& a, bool f32) {
+  for (int64_t j = 0; j < m; ++j)
+    for (int64_t p = a.cp[j]; p < a.cp[j + 1]; ++p) {
+      if (a.ri[p] >= j) continue;
+      std::string err = check_value(what, a.ri[p], j, a.va[p], f32);
+      if (!err.empty()) return err;
+    }
+  return {};
+}
+
+// a dense column-major m x m matrix, read as the dense setter reads it: A[i + j * m] for i < j
+std::string check_values_dense_upper(const char* what, int64_t m, const double* A, bool f32) {
+  for (int64_t j = 1; j < m; ++j)
+    for (int64_t i = 0; i < j; ++i) {
+      const double v = A[i + j * m];
+      if (std::isfinite(v) && !(f32 && std::fabs(v) >= 0x1.ffffffp+127)) continue;
+      return check_value(what, i, j, v, f32);
+    }
   return {};
 }
 

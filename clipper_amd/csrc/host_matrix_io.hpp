@@ -162,6 +162,11 @@ int upload_csc(DevTemps& tmp, Shard& s, int64_t m, const clipper_csc::CscRef& a,
 // other than pattern(M); only then does an explicit C get a store of its own (pass 2).
 int set_dense(Ctx* h, const double* M, const double* C, int64_t m) {
   int rc;
+  {  // refused before anything changes: the matrix held stays (host_csc_input.hpp; C is 0 / 1: no range to leave)
+    std::string err = clipper_csc::check_values_dense_upper("M", m, M, h->storage != CLIPPER_HIP_STORE_F64);
+    if (err.empty()) err = clipper_csc::check_values_dense_upper("C", m, C, false);
+    if (!err.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s", err.c_str());
+  }
   if ((rc = begin_matrix(h, m))) return rc;
   if ((rc = ensure_dense(h, false))) return rc;
   const size_t bytes = static_cast<size_t>(m) * m * sizeof(double);
@@ -313,6 +318,8 @@ int set_sparse(Ctx* h, int64_t m, const int64_t* Mcolptr, const int32_t* Mrow, c
   if (err.empty()) err = clipper_csc::check_csc("C", m, C);
   if (err.empty()) err = clipper_csc::upper_only("M", m, M, Mup, dropped_below);
   if (err.empty()) err = clipper_csc::upper_only("C", m, C, Cup, dropped_below);
+  if (err.empty()) err = clipper_csc::check_values_csc("M", m, M, h->storage != CLIPPER_HIP_STORE_F64);
+  if (err.empty()) err = clipper_csc::check_values_csc("C", m, C, false);
   if (!err.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s", err.c_str());
   // (a warning, not an error — the call goes on and returns 0 unless something else fails: clipper_hip_last_error()
   // tells a caller who handed over both triangles, or only the lower one, what became of them)

@@ -32,14 +32,23 @@ __global__ __launch_bounds__(256) void k_gather_points(const double* __restrict_
   }
 }
 
+// THE stored-value rule, for every route on which a double becomes an entry of M (the fills through store_score, the
+// dense setter, the sparse setter's two routes): the cast to T — a value that rounds to an fp32 subnormal stays that
+// subnormal — except that a non-zero value never becomes 0: C == pattern(M) is implicit in every store, so an fp32
+// underflow keeps the smallest normal, with the sign of the value, instead of leaving the pattern.
+// (k_custom_invariant_src.h restates it: a source string of its own.)
+template <typename T>
+__device__ __forceinline__ T store_value(double v) {
+  const T s = static_cast<T>(v);
+  if (s == T(0) && v != 0.0) return static_cast<T>(v > 0.0 ? 1.17549435e-38 : -1.17549435e-38);
+  return s;
+}
+
 template <typename T>
 __device__ __forceinline__ T store_score(double scr, double affinityeps) {
   // clipper.cpp:53-55 — keep the score only when it exceeds affinityeps.
   if (!(scr > affinityeps)) return T(0);
-  T v = static_cast<T>(scr);
-  // an fp32 underflow must not erase an entry from the pattern (C == pattern(M))
-  if (v == T(0)) v = static_cast<T>(1.17549435e-38);
-  return v;
+  return store_value<T>(scr);
 }
 
 template <typename T>

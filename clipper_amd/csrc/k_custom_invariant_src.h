@@ -73,7 +73,9 @@ typedef double (*clipper_invariant_signature)(const double*, const double*, cons
 __device__ inline clipper_invariant_signature clipper_invariant_required() { return &clipper_invariant; }
 
 // clipper.cpp:53-55: a score is kept only when it exceeds affinityeps (NaN is not); an fp32 underflow stays in the
-// pattern as the smallest normal (store_score, k_affinity.hip.h)
+// pattern as the smallest normal. This is a copy of the stored-value rule (store_value / store_score, k_affinity.hip.h:
+// stated there; restated here only because this source is compiled on its own at run time — a kept score is positive,
+// so the sign of the rule never shows)
 template <typename T>
 __device__ __forceinline__ T clipper_store_score(double scr, double affinityeps) {
   if (!(scr > affinityeps)) return T(0);

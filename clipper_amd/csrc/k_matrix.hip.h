@@ -36,10 +36,7 @@ __global__ __launch_bounds__(256) void k_from_dense_upper(T* __restrict__ S, int
         if (cv != want) *mismatch = 1;
       }
     }
-    T sv = static_cast<T>(mv);
-    if (mv != 0.0 && sv == T(0)) sv = (mv > 0) ? static_cast<T>(1.17549435e-38)
-                                               : static_cast<T>(-1.17549435e-38);
-    S[j * ld + c] = sv;
+    S[j * ld + c] = store_value<T>(mv);
     if (Cs != nullptr) Cs[j * ld + c] = static_cast<T>(cv);
   }
 }
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(256) void k_from_csc(T* __restrict__ S, int64_t ld,
     for (int64_t p = colptr[j] + threadIdx.x; p < colptr[j + 1]; p += 256) {
       const int64_t i = row[p];
       if (i == j) continue;  // the solver treats the diagonal as implicit identity
-      const T v = static_cast<T>(val[p]);
+      const T v = store_value<T>(val[p]);  // (a plain cast let an fp32 underflow leave the pattern)
       // element (i,j): lives at S[i][j-c0] if j is an owned column, and at S[j][i-c0] if i is
       if (j >= c0 && j < c0 + W) S[i * ld + (j - c0)] = v;
       if (i >= c0 && i < c0 + W) S[j * ld + (i - c0)] = v;

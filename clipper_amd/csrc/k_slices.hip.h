@@ -605,6 +605,9 @@ struct GroupSource {
   }
 };
 
+template <typename T>
+__device__ __forceinline__ T store_value(double v);  // the stored-value rule: k_affinity.hip.h, next to store_score
+
 // Source 2: full symmetric CSC (both triangles, rows ascending per column) of this shard's
 // columns — clipper_hip_set_sparse (the reference's setSparseMatrixData, clipper.cpp:162-166)
 template <typename VT>
@@ -640,9 +643,7 @@ struct CscSource {
     const int64_t a = valid ? start + i : 0;
     const double x = values[a];
     const int32_t r = rowidx[a];
-    VT t = static_cast<VT>(x);
-    if (t == VT(0) && x != 0.0) t = static_cast<VT>(1.17549435e-38);  // an underflow keeps the pattern
-    v = valid ? t : VT(0);
+    v = valid ? store_value<VT>(x) : VT(0);
     row = valid ? static_cast<uint32_t>(r - r0_) : 0u;
   }
 };

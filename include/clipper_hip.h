@@ -247,7 +247,10 @@ int clipper_hip_set_matrix(clipper_hip_t* h, const double* M, const double* C, i
  * non-zero diagonal entry (outside the reference's contract, clipper.h:137-138; it would count once
  * on top of the identity there) is refused with CLIPPER_HIP_E_INVALID; explicit zeros are dropped.
  * When entries below the diagonal were ignored the call still returns 0 and clipper_hip_last_error() holds a
- * warning that says how many (a caller that stored both triangles, or only the lower one, can tell). */
+ * warning that says how many (a caller that stored both triangles, or only the lower one, can tell).
+ * Values (both setters): a non-finite value above the diagonal of M or C, and with an fp32 storage a finite value of M
+ * whose float cast is infinite, is refused with CLIPPER_HIP_E_INVALID naming the matrix and the entry (i, j); the matrix
+ * held stays intact. A non-zero value that underflows in fp32 is held as FLT_MIN with its sign: C == pattern(M). */
 int clipper_hip_set_sparse(clipper_hip_t* h, int64_t m, const int64_t* Mcolptr,
                            const int32_t* Mrow, const double* Mval, const int64_t* Ccolptr,
                            const int32_t* Crow, const double* Cval);

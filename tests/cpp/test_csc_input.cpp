@@ -1,9 +1,12 @@
 // CPU test of the sparse input checks (clipper_amd/csrc/host_csc_input.hpp): every refusal of check_csc / upper_only /
 // symmetric_lists with its message, the count of entries below the diagonal, the strictly upper input that is not
-// copied, the C == pattern(M) test, and the symmetric lists of small matrices against answers written by hand.
+// copied, the C == pattern(M) test, the symmetric lists of small matrices against answers written by hand, and the
+// value checks of both setters (non-finite values, values that round to fp32 infinity).
 //   g++ -std=c++17 -O1 -I clipper_amd/csrc tests/cpp/test_csc_input.cpp -o /tmp/t && /tmp/t
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -130,7 +133,57 @@ static void test_symmetric_lists() {
   REQUIRE(symmetric_lists(m, D.ref(), L4) == "entry (1,0) is stored more than once");
 }
 
+static void test_check_values() {
+  const int64_t m = 3;
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const double first_inf = 0x1.ffffffp+127;  // FLT_MAX plus half its last place: the tie goes to even, which is infinity
+  const double last_finite = std::nextafter(first_inf, 0.0);
+  REQUIRE(std::isinf(static_cast<float>(first_inf)) && static_cast<float>(last_finite) == std::numeric_limits<float>::max());
+  // CSC, strictly upper: (0,1) (0,2) (1,2)
+  Mat ok{{0, 0, 1, 3}, {0, 0, 1}, {5e-324, -1e-50, last_finite}};
+  for (bool f32 : {false, true}) REQUIRE(check_values_csc("M", m, ok.ref(), f32).empty());
+  Mat a = ok;
+  a.va[1] = nan;
+  for (bool f32 : {false, true}) REQUIRE(check_values_csc("M", m, a.ref(), f32) == "M: entry (0,2) is not finite (nan)");
+  a.va[1] = inf;
+  REQUIRE(check_values_csc("C", m, a.ref(), false) == "C: entry (0,2) is not finite (inf)");
+  a.va[1] = -inf;
+  REQUIRE(check_values_csc("M", m, a.ref(), true) == "M: entry (0,2) is not finite (-inf)");
+  a = ok;
+  a.va[2] = first_inf;
+  REQUIRE(check_values_csc("M", m, a.ref(), false).empty());  // an fp64 storage holds it
+  REQUIRE(check_values_csc("M", m, a.ref(), true) ==
+          "M: entry (1,2) = 3.4028235677973366e+38 rounds to infinity in fp32 storage");
+  a.va[2] = -first_inf;
+  REQUIRE(check_values_csc("M", m, a.ref(), true) ==
+          "M: entry (1,2) = -3.4028235677973366e+38 rounds to infinity in fp32 storage");
+  a.va[2] = -last_finite;
+  REQUIRE(check_values_csc("M", m, a.ref(), true).empty());
+  // entries on and below the diagonal are never read: whatever they hold (column 0: rows 1, 2; column 1: row 1)
+  Mat low{{0, 2, 4, 4}, {1, 2, 0, 1}, {nan, inf, 0.5, nan}};
+  REQUIRE(check_values_csc("M", m, low.ref(), true).empty());
+  // dense, column-major 3 x 3: A[i + j * m] is read for i < j only
+  std::vector<double> D{nan, nan, inf, 5e-324, nan, -inf, -1e-50, last_finite, nan};
+  for (bool f32 : {false, true}) REQUIRE(check_values_dense_upper("M", m, D.data(), f32).empty());
+  std::vector<double> E = D;
+  E[0 + 2 * 3] = nan;
+  REQUIRE(check_values_dense_upper("M", m, E.data(), true) == "M: entry (0,2) is not finite (nan)");
+  E[0 + 2 * 3] = -inf;
+  REQUIRE(check_values_dense_upper("C", m, E.data(), false) == "C: entry (0,2) is not finite (-inf)");
+  E = D;
+  E[0 + 1 * 3] = inf;
+  REQUIRE(check_values_dense_upper("M", m, E.data(), false) == "M: entry (0,1) is not finite (inf)");
+  E = D;
+  E[1 + 2 * 3] = first_inf;
+  REQUIRE(check_values_dense_upper("M", m, E.data(), false).empty());
+  REQUIRE(check_values_dense_upper("M", m, E.data(), true) ==
+          "M: entry (1,2) = 3.4028235677973366e+38 rounds to infinity in fp32 storage");
+  const double one = 1.0;
+  REQUIRE(check_values_dense_upper("M", 1, &one, true).empty());  // m = 1: no pair
+}
+
 int main() {
+  test_check_values();
   test_check_csc();
   test_upper_only();
   test_is_pattern();

@@ -94,9 +94,10 @@ class Case:
         return self._ops[0] @ x, self._ops[1] @ x
 
     def rounded_f32(self) -> "Case":
-        """the matrix an fp32 storage holds of this case"""
+        """the matrix an fp32 storage holds of this case (value_edges.held: the cast, and a non-zero value never 0)"""
         import dataclasses
-        return dataclasses.replace(self, name=self.name + "/f32", Mv=self.Mv.astype(np.float32).astype(np.float64))
+        from tests.value_edges import STORE_F32, held
+        return dataclasses.replace(self, name=self.name + "/f32", Mv=held(self.Mv, STORE_F32))
 
 
 def _lists(mask_or_values):
