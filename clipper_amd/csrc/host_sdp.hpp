@@ -83,13 +83,37 @@ int sdp_alloc(SdpBufs& b, int64_t n, const clipper_sdp_params_t* P, int taken, b
   return 0;
 }
 
+// What every refusal of an infeasible problem says (a batch puts "problem i: " in front)
+constexpr const char* SDP_INFEASIBLE = "sdp: no diagonal entry of C is nonzero (the problem is infeasible)";
+
+// What SdpCtl says, into the info (num_nodes, route, thr and the times are the caller's)
+void sdp_info_from_ctl(clipper_sdp_info_t& I, const SdpCtl& c) {
+  I.iters = c.iters;
+  I.converged = c.converged;
+  I.sweeps = c.sweeps;
+  I.pobj = -c.pval;
+  I.dobj = -c.dval;
+  I.r_prim = c.r_prim;
+  I.r_dual = c.r_dual;
+  I.rho = c.rho;
+}
+
+// The verbose line of one result: `head`, the route, the counts, the outcome and the objectives; no line end
+void sdp_print_result(const char* head, long long n, const clipper_sdp_info_t& I) {
+  std::printf("%s%s: n = %lld, %d iterations (%d Jacobi sweeps), %s, pobj %.6g, dobj %.6g", head,
+              I.route == CLIPPER_HIP_SDP_ROUTE_WIDE ? " (wide route)" : "", n, I.iters, I.sweeps,
+              I.converged ? "converged" : (I.timed_out ? "timed out" : "max_iters"), I.pobj, I.dobj);
+}
+
 // The tail of every solve, whichever route it took: the rounding (sdp.cpp:244-261; the eigenpairs of X are those of the
 // last projection, mu and Q on the device), the copies out and the info. I.timed_out is the caller's; t2: when the
-// iteration ended. mu_out (np doubles, may be NULL): the weights as the device holds them.
+// iteration ended. mu_out (np doubles, may be NULL): the weights as the device holds them; top_out (may be NULL): the
+// first index of the largest weight.
 int sdp_tail(const double* d_mu, const double* d_Q, const double* d_X, const double* d_U, int64_t n, const SdpCtl& c,
              const clipper_sdp_params_t* P, int taken, std::chrono::steady_clock::time_point t0, double t_setup,
              double t_solve, std::chrono::steady_clock::time_point t2, std::vector<int32_t>& nodes, double* X_out,
-             double* Y_out, double* lambdas_out, double* evec1_out, double* mu_out, clipper_sdp_info_t& I) {
+             double* Y_out, double* lambdas_out, double* evec1_out, double* mu_out, int32_t* top_out,
+             clipper_sdp_info_t& I) {
   using clk = std::chrono::steady_clock;
   auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
   const int32_t np = static_cast<int32_t>(n + (n & 1));
@@ -113,6 +137,7 @@ int sdp_tail(const double* d_mu, const double* d_Q, const double* d_X, const dou
     if (std::fabs(ev[static_cast<size_t>(i)]) > thr) nodes.push_back(static_cast<int32_t>(i));
   if (evec1_out) std::memcpy(evec1_out, ev.data(), ev.size() * sizeof(double));
   if (mu_out) std::memcpy(mu_out, mu.data(), mu.size() * sizeof(double));
+  if (top_out) *top_out = static_cast<int32_t>(top);
   if (lambdas_out) {
     std::vector<double> l(mu.begin(), mu.begin() + n);
     std::stable_sort(l.begin(), l.end());
@@ -124,25 +149,18 @@ int sdp_tail(const double* d_mu, const double* d_Q, const double* d_X, const dou
     HIPCHK(hipMemcpy(Y_out, d_U, nn * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < nn; ++i) Y_out[i] = c.rho * Y_out[i];
   }
-  I.iters = c.iters;
-  I.converged = c.converged;
+  sdp_info_from_ctl(I, c);
   I.num_nodes = static_cast<int32_t>(nodes.size());
-  I.sweeps = c.sweeps;
   I.route = taken;
-  I.pobj = -c.pval;
-  I.dobj = -c.dval;
-  I.r_prim = c.r_prim;
-  I.r_dual = c.r_dual;
-  I.rho = c.rho;
   I.thr = thr;
   I.t_setup = t_setup;
   I.t_solve = t_solve;
   I.t_extract = since(t2);
   I.t_total = since(t0);
-  if (P->verbose)
-    std::printf("sdp%s: n = %lld, %d iterations (%d Jacobi sweeps), %s, pobj %.6g, dobj %.6g, %.3f s\n",
-                taken == CLIPPER_HIP_SDP_ROUTE_WIDE ? " (wide route)" : "", (long long)n, I.iters, I.sweeps,
-                I.converged ? "converged" : (I.timed_out ? "timed out" : "max_iters"), I.pobj, I.dobj, I.t_total);
+  if (P->verbose) {
+    sdp_print_result("sdp", (long long)n, I);
+    std::printf(", %.3f s\n", I.t_total);
+  }
   return 0;
 }
 
@@ -158,7 +176,7 @@ int sdp_run(int device, hipStream_t st, SdpBufs& b, int64_t n, const clipper_sdp
   if (taken == CLIPPER_HIP_SDP_ROUTE_WIDE) {
     bool infeasible = false;
     if (int rc = sdpw_solve(st, b.wide, P, t0, c, I.timed_out, infeasible, t_setup, t_solve)) return rc;
-    if (infeasible) return fail(CLIPPER_HIP_E_INVALID, "sdp: no diagonal entry of C is nonzero (the problem is infeasible)");
+    if (infeasible) return fail(CLIPPER_HIP_E_INVALID, "%s", SDP_INFEASIBLE);
   } else {
     const int32_t np = static_cast<int32_t>(n + (n & 1));
     const int lds = np * np * static_cast<int>(sizeof(double));
@@ -174,7 +192,7 @@ int sdp_run(int device, hipStream_t st, SdpBufs& b, int64_t n, const clipper_sdp
     if (int rc = launch(SDP_MODE_INIT, 0)) return rc;
     HIPCHK(hipMemcpyAsync(&c, b.ctl, sizeof(SdpCtl), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (c.infeasible) return fail(CLIPPER_HIP_E_INVALID, "sdp: no diagonal entry of C is nonzero (the problem is infeasible)");
+    if (c.infeasible) return fail(CLIPPER_HIP_E_INVALID, "%s", SDP_INFEASIBLE);
     t_setup = since(t0);
     const auto t1 = clk::now();
     while (!c.converged && c.iters < P->max_iters) {
@@ -194,7 +212,7 @@ int sdp_run(int device, hipStream_t st, SdpBufs& b, int64_t n, const clipper_sdp
     t_solve = since(t1);
   }
   if (int rc = sdp_tail(b.mu, b.Q, b.X, b.U, n, c, P, taken, t0, t_setup, t_solve, clk::now(), nodes, X_out, Y_out,
-                        lambdas_out, evec1_out, nullptr, I))
+                        lambdas_out, evec1_out, nullptr, nullptr, I))
     return rc;
   if (info) *info = I;
   return 0;

@@ -190,7 +190,7 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   }
   for (size_t i = 0; i < count; ++i)
     if (S.c[i].infeasible)
-      return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: no diagonal entry of C is nonzero (the problem is infeasible)", i);
+      return fail(CLIPPER_HIP_E_INVALID, "problem %zu: %s", i, SDP_INFEASIBLE);
   const double t_setup = since(t0);
   const auto t1 = clk::now();
   auto finished = [&](int32_t i) { return S.c[static_cast<size_t>(i)].converged || S.c[static_cast<size_t>(i)].iters >= P->max_iters; };
@@ -213,6 +213,7 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   struct WideOut {
     std::vector<double> mu, ev;
     std::vector<int32_t> nodes;
+    int32_t top = 0;
   };
   std::vector<WideOut> wide_out(routes.wide.size());
   for (size_t k = 0; k < routes.wide.size(); ++k) {
@@ -223,14 +224,14 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     double ts = 0.0, tv = 0.0;
     if (int rc = sdpw_solve(st, w, P, t0, S.c[i], S.info[i].timed_out, infeasible, ts, tv)) return rc;
     if (infeasible)
-      return fail(CLIPPER_HIP_E_INVALID, "problem %zu: sdp: no diagonal entry of C is nonzero (the problem is infeasible)", i);
+      return fail(CLIPPER_HIP_E_INVALID, "problem %zu: %s", i, SDP_INFEASIBLE);
     WideOut& o = wide_out[k];
     o.mu.resize(static_cast<size_t>(plan::padded(S.n[i])));
     o.ev.resize(static_cast<size_t>(n));
     clipper_sdp_params_t quiet = *P;
     quiet.verbose = 0;
     if (int rc = sdp_tail(w.a.mu, w.a.Q, w.a.X, w.a.U, n, S.c[i], &quiet, CLIPPER_HIP_SDP_ROUTE_WIDE, t0, ts, tv, clk::now(),
-                          o.nodes, nullptr, nullptr, nullptr, o.ev.data(), o.mu.data(), S.info[i]))
+                          o.nodes, nullptr, nullptr, nullptr, o.ev.data(), o.mu.data(), &o.top, S.info[i]))
       return rc;
   }
   const double t_solve = since(t1);
@@ -250,22 +251,13 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
     std::memcpy(out + (L.at[i].mu - L.out_begin), o.mu.data(), o.mu.size() * sizeof(double));
     std::memcpy(out + (L.at[i].ev - L.out_begin), o.ev.data(), o.ev.size() * sizeof(double));
     if (!o.nodes.empty()) std::memcpy(out + (L.at[i].nodes - L.out_begin), o.nodes.data(), o.nodes.size() * sizeof(int32_t));
-    const int32_t top = static_cast<int32_t>(std::max_element(o.mu.begin(), o.mu.begin() + S.n[i]) - o.mu.begin());
-    reinterpret_cast<SdpRound*>(S.out.data() + L.out_bytes)[i] = SdpRound{S.info[i].thr, static_cast<int32_t>(o.nodes.size()), top};
+    reinterpret_cast<SdpRound*>(S.out.data() + L.out_bytes)[i] = SdpRound{S.info[i].thr, static_cast<int32_t>(o.nodes.size()), o.top};
   }
   for (size_t i = 0; i < count; ++i) {
     if (is_wide[i]) continue;  // (filled by its tail)
-    const SdpCtl& c = S.c[i];
     clipper_sdp_info_t& I = S.info[i];
-    I.iters = c.iters;
-    I.converged = c.converged;
+    sdp_info_from_ctl(I, S.c[i]);
     I.num_nodes = S.round(i).count;
-    I.sweeps = c.sweeps;
-    I.pobj = -c.pval;
-    I.dobj = -c.dval;
-    I.r_prim = c.r_prim;
-    I.r_dual = c.r_dual;
-    I.rho = c.rho;
     I.thr = S.round(i).thr;
   }
   const double t_extract = since(t2), t_total = since(t0);
@@ -278,9 +270,8 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   if (P->verbose) {
     std::printf("sdp batch: %zu problems, %d rounds of %d iterations, %.3f s\n", count, rounds, SDP_ITERS_PER_LAUNCH, t_total);
     for (size_t i = 0; i < count; ++i) {
-      const clipper_sdp_info_t& I = S.info[i];
-      std::printf("  problem %zu%s: n = %d, %d iterations (%d Jacobi sweeps), %s, pobj %.6g, dobj %.6g\n", i,
-                  I.route == CLIPPER_HIP_SDP_ROUTE_WIDE ? " (wide route)" : "", S.n[i], I.iters, I.sweeps, I.converged ? "converged" : (I.timed_out ? "timed out" : "max_iters"), I.pobj, I.dobj);
+      sdp_print_result(("  problem " + std::to_string(i)).c_str(), S.n[i], S.info[i]);
+      std::printf("\n");
     }
   }
   return 0;

@@ -156,7 +156,7 @@ int sdpw_solve(hipStream_t st, const SdpWide& w, const clipper_sdp_params_t* P,
       decide(SDPW_AFTER_DUAL, sw);
       if (int rc = read_state()) return rc;
     }
-    if (hs.rescale != SDPW_RESCALE_NONE) hipLaunchKernelGGL(k_sdpw_scale_u, over_nn, wgw, 0, st, a, hs.rescale);
+    if (hs.rescale != SDP_RESCALE_NONE) hipLaunchKernelGGL(k_sdpw_scale_u, over_nn, wgw, 0, st, a, hs.rescale);
     c = hs.c;
   }
   if (!c.converged) {  // a certified bound in every outcome: lambda_max(M - Y) of the final Y

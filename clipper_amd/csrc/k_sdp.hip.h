@@ -19,37 +19,33 @@
 //
 // Every launch runs at most `budget` iterations and leaves X, Z, U, Q, mu and SdpCtl in device memory; the host
 // checks the convergence flag and the time limit between launches. No grid barrier, no atomics across workgroups.
+//
+// The arithmetic of the iteration (constants, SdpCtl, INIT values, the formed matrices, the rotations, the simplex
+// rule, one entry's update, the stopping rule, the balancing) is stated in sdp_rules.hpp, and the circle order in
+// sdp_circle.hpp, for this route and the wide one (k_sdp_wide.hip.h); this file adds what a workgroup does with them:
+// which work item holds which entry, and the order of every sum. The device helpers that both routes call live here
+// too: sdp_block_sum, sdp_gather_entry.
+// k_sdp and k_sdp_batch are one inlined function each that spills, and their register allocation moves as a whole
+// when some rules are inlined from the header instead of written in place (0.7 % of the solve at n = 128). Those
+// rules stay spelled out here, each marked with the name of its statement in sdp_rules.hpp, so that both kernels keep
+// the instruction stream they had: sdp_norms_add, sdp_rotate_diag, sdp_init_entry, sdp_support / sdp_support_tau,
+// the terms of sdp_update_entry (Z+ itself comes from sdp_z_plus), sdp_residuals, sdp_balance_factor and
+// sdp_close_iteration. A change to one of them in the header is made here too; tests/test_gpu_sdp_wide.py holds the
+// two routes to each other.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sdp_circle.hpp"
+#include "sdp_rules.hpp"
 
 namespace clipper_hip {
 
 constexpr int SDP_MAX_N = 128;          // the working matrix: SDP_MAX_N^2 doubles of LDS
 constexpr int SDP_THREADS = 1024;
-constexpr int SDP_MAX_SWEEPS = 40;
-constexpr double SDP_JACOBI_TOL = 1e-13;  // stop sweeping when off(A) <= tol * ||A||_F
-constexpr double SDP_RHO0 = 1.0;
-constexpr int SDP_ADAPT_EVERY = 10;       // residual balancing: every 10 iterations,
-constexpr double SDP_ADAPT_MU = 10.0;     // when one residual exceeds 10 times the other,
-constexpr double SDP_ADAPT_TAU = 2.0;     // rho is multiplied or divided by 2 and U divided or multiplied
 
 enum { SDP_MODE_INIT = 0, SDP_MODE_ITERATE = 1, SDP_MODE_CERTIFY = 2 };
-
-// device state of one problem (the host reads it after every launch)
-struct SdpCtl {
-  double rho;
-  double r_prim, r_dual;  // ||X - Z||_F, rho ||Z - Z_prev||_F of the last iteration
-  double pval;            // <M, X>
-  double dval;            // lambda_max(M - rho U): the dual bound of the last check (or certification)
-  int32_t iters;
-  int32_t converged;
-  int32_t infeasible;     // no diagonal entry of C is nonzero
-  int32_t sweeps;         // Jacobi sweeps so far (all projections and checks)
-};
 
 struct SdpArgs {
   const double* M;
@@ -60,23 +56,36 @@ struct SdpArgs {
   double eps_abs, eps_rel;
 };
 
-// Dense fp64 M and the mask of C from stores where element (r, c) sits at src[r * rs + c * cs]; only the lower
-// triangle (r >= c) is read. `ident` is added to the diagonal of both (the context's identity, clipper.cpp:133-143).
+// Entry (a, b) of the dense fp64 M and of the mask of C, from stores of doubles (f64) or floats where element (r, c)
+// sits at src[r * rs + c * cs]; only the lower triangle (r >= c) is read. `ident` is added to the diagonal of both (the
+// context's identity, clipper.cpp:133-143); with c_pattern_of_m, C = pattern(M + ident I) and srcC is not read.
+__device__ inline void sdp_gather_entry(const void* srcM, const void* srcC, int f64, int c_pattern_of_m, int64_t rs,
+                                        int64_t cs, int32_t a, int32_t b, double ident, double& mv, double& mask) {
+  const int32_t r = a > b ? a : b, c = a > b ? b : a;
+  const int64_t e = r * rs + c * cs;
+  const double d = (a == b) ? ident : 0.0;
+  mv = (f64 ? static_cast<const double*>(srcM)[e] : static_cast<double>(static_cast<const float*>(srcM)[e])) + d;
+  double cv = mv;
+  if (!c_pattern_of_m)
+    cv = (f64 ? static_cast<const double*>(srcC)[e] : static_cast<double>(static_cast<const float*>(srcC)[e])) + d;
+  mask = (cv != 0.0) ? 1.0 : 0.0;
+}
+
+// Dense fp64 M and the mask of C of one problem from stores of T (float or double)
 template <typename T>
 __global__ void k_sdp_gather(const T* __restrict__ srcM, const T* __restrict__ srcC, bool c_pattern_of_m, int64_t rs,
                              int64_t cs, int32_t n, double ident, double* __restrict__ M, double* __restrict__ mask) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (idx >= static_cast<int64_t>(n) * n) return;
-  const int32_t a = static_cast<int32_t>(idx / n), b = static_cast<int32_t>(idx % n);
-  const int32_t r = a > b ? a : b, c = a > b ? b : a;
-  const double d = (a == b) ? ident : 0.0;
-  const double mv = static_cast<double>(srcM[r * rs + c * cs]) + d;
-  const double cv = c_pattern_of_m ? mv : static_cast<double>(srcC[r * rs + c * cs]) + d;
+  double mv, mk;
+  sdp_gather_entry(srcM, srcC, sizeof(T) == sizeof(double), c_pattern_of_m, rs, cs, static_cast<int32_t>(idx / n),
+                   static_cast<int32_t>(idx % n), ident, mv, mk);
   M[idx] = mv;
-  mask[idx] = (cv != 0.0) ? 1.0 : 0.0;
+  mask[idx] = mk;
 }
 
-// sum of one double over the workgroup, the same order on every call; every thread gets the result
+// sum of one double over a workgroup of THREADS, the same order on every call; every thread gets the result
+template <int THREADS>
 __device__ inline double sdp_block_sum(double v, double* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -84,39 +93,13 @@ __device__ inline double sdp_block_sum(double v, double* red) {
   if (lane == 0) red[w] = v;
   __syncthreads();
   double s = 0.0;
-  for (int i = 0; i < SDP_THREADS / 64; ++i) s += red[i];
+  for (int i = 0; i < THREADS / 64; ++i) s += red[i];
   return s;
 }
 
 // the pair k of step t of the circle order over np indices (np even): index np - 1 stays put, the others turn
 // (stated in sdp_circle.hpp, where the host can walk it too)
 __device__ inline void sdp_pair(int k, int t, int np, int& p, int& q) { clipper_sdp_circle::circle_pair(k, t, np, p, q); }
-
-// The rotation that annihilates a_pq of the pair (p, q): c, s and the tangent tn (identity when a_pq = 0)
-__device__ inline void sdp_rotation(double apq, double app, double aqq, double& c, double& s, double& tn) {
-  c = 1.0;
-  s = 0.0;
-  tn = 0.0;
-  if (apq != 0.0) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double at = fabs(theta);
-    tn = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(theta * theta + 1.0));
-    if (theta < 0.0) tn = -tn;
-    c = 1.0 / sqrt(tn * tn + 1.0);
-    s = tn * c;
-  }
-}
-
-// Both sides of the 2 x 2 block (rows p, q of a pair with c1, s1; columns r, s of another with c2, sn2)
-__device__ inline void sdp_rotate_block(double apr, double aps, double aqr, double aqs, double c1, double s1, double c2,
-                                        double sn2, double& npr, double& nps, double& nqr, double& nqs) {
-  const double bpr = apr * c2 - aps * sn2, bps = apr * sn2 + aps * c2;  // columns (l)
-  const double bqr = aqr * c2 - aqs * sn2, bqs = aqr * sn2 + aqs * c2;
-  npr = c1 * bpr - s1 * bqr;  // rows (k)
-  nps = c1 * bps - s1 * bqs;
-  nqr = s1 * bpr + c1 * bqr;
-  nqs = s1 * bps + c1 * bqs;
-}
 
 // A (LDS) <- Q^T A Q, through T (global); Q is np x np
 __device__ void sdp_warm_start(double* A, const double* __restrict__ Q, double* __restrict__ T, int np) {
@@ -169,13 +152,13 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
   for (; sweep < SDP_MAX_SWEEPS; ++sweep) {
     double off = 0.0, all = 0.0;
     for (int idx = tid; idx < np * np; idx += SDP_THREADS) {
-      const double v = A[idx];
+      const double v = A[idx];  // sdp_norms_add, spelled out (see the file comment)
       all += v * v;
       if (idx / np != idx % np) off += v * v;
     }
-    off = sdp_block_sum(off, red);
-    all = sdp_block_sum(all, red + SDP_THREADS / 64);
-    if (!(off > SDP_JACOBI_TOL * SDP_JACOBI_TOL * all)) break;
+    off = sdp_block_sum<SDP_THREADS>(off, red);
+    all = sdp_block_sum<SDP_THREADS>(all, red + SDP_THREADS / 64);
+    if (!sdp_sweep_again(off, all)) break;
     for (int t = 0; t < np - 1; ++t) {
       if (tid < h) {
         int p, q;
@@ -194,7 +177,7 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
         int p, q;
         sdp_pair(k, t, np, p, q);
         if (k == l) {
-          const double apq = A[p * np + q];
+          const double apq = A[p * np + q];  // sdp_rotate_diag, spelled out (see the file comment)
           A[p * np + p] = A[p * np + p] - rt[k] * apq;
           A[q * np + q] = A[q * np + q] + rt[k] * apq;
           A[p * np + q] = 0.0;
@@ -207,14 +190,7 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
         const double apr = A[p * np + r], aps = A[p * np + s2], aqr = A[q * np + r], aqs = A[q * np + s2];
         double npr, nps, nqr, nqs;
         sdp_rotate_block(apr, aps, aqr, aqs, c1, s1, c2, sn2, npr, nps, nqr, nqs);
-        A[p * np + r] = npr;
-        A[p * np + s2] = nps;
-        A[q * np + r] = nqr;
-        A[q * np + s2] = nqs;
-        A[r * np + p] = npr;
-        A[s2 * np + p] = nps;
-        A[r * np + q] = nqr;
-        A[s2 * np + q] = nqs;
+        sdp_store_block(A, np, p, q, r, s2, npr, nps, nqr, nqs);
       }
       if (Q) {
         for (int idx = tid; idx < np * h; idx += SDP_THREADS) {
@@ -223,8 +199,10 @@ __device__ int sdp_jacobi(double* A, double* __restrict__ Q, int np, double* rc,
           sdp_pair(k, t, np, p, q);
           const double c = rc[k], s = rs[k];
           const double qp = Q[i * np + p], qq = Q[i * np + q];
-          Q[i * np + p] = c * qp - s * qq;
-          Q[i * np + q] = s * qp + c * qq;
+          double nqp, nqq;
+          sdp_rotate_q(qp, qq, c, s, nqp, nqq);
+          Q[i * np + p] = nqp;
+          Q[i * np + q] = nqq;
         }
       }
       __syncthreads();
@@ -239,12 +217,12 @@ __device__ double sdp_dual_bound(const SdpArgs& g, double rho, double* A, bool w
   const int n = g.n, np = g.np;
   for (int idx = threadIdx.x; idx < np * np; idx += SDP_THREADS) {
     const int a = idx / np, b = idx % np;
-    A[idx] = (a < n && b < n) ? g.M[a * n + b] - rho * g.U[a * n + b] : 0.0;
+    A[idx] = (a < n && b < n) ? sdp_form_dual(g.M[a * n + b], g.U[a * n + b], rho) : 0.0;
   }
   __syncthreads();
   if (warm) sdp_warm_start(A, g.Q, g.T, np);
   sweeps += sdp_jacobi(A, nullptr, np, rc, rs, rt, red);
-  double d = A[0];
+  double d = A[0];  // lambda_max off the diagonal: every work item scans it (k_sdpw_decide reduces it; max is exact)
   for (int i = 1; i < n; ++i) d = fmax(d, A[i * np + i]);
   __syncthreads();
   return d;
@@ -280,18 +258,18 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       int cnt = 0;
       for (int i = 0; i < n; ++i) cnt += g.mask[i * n + i] != 0.0;
       kmax = cnt;
-      c = SdpCtl{SDP_RHO0, 0.0, 0.0, 0.0, 0.0, 0, 0, cnt == 0, 0};
+      sdp_init_ctl(c, cnt);
     }
     __syncthreads();
-    const double w = kmax ? 1.0 / kmax : 0.0;
+    const double w = sdp_init_weight(kmax);
     for (int idx = tid; idx < nn; idx += SDP_THREADS) {
       const int a = idx / n, b = idx % n;
-      const double x = (a == b && g.mask[idx] != 0.0) ? w : 0.0;
+      const double x = (a == b && g.mask[idx] != 0.0) ? w : 0.0;  // sdp_init_entry, spelled out (here and for mu)
       g.X[idx] = x;
       g.Z[idx] = x;
       g.U[idx] = 0.0;
     }
-    for (int idx = tid; idx < np * np; idx += SDP_THREADS) g.Q[idx] = (idx / np == idx % np) ? 1.0 : 0.0;
+    for (int idx = tid; idx < np * np; idx += SDP_THREADS) g.Q[idx] = sdp_init_q(idx / np, idx % np);
     for (int i = tid; i < np; i += SDP_THREADS) g.mu[i] = (i < n && g.mask[i * n + i] != 0.0) ? w : 0.0;
   } else if (mode == SDP_MODE_CERTIFY) {
     int sw = 0;
@@ -311,14 +289,15 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
         double w = 0.0;
         if (a < n && b < n) {
           const int e = a * n + b;
-          w = g.Z[e] - g.U[e] + g.M[e] / rho;
+          w = sdp_form_primal(g.Z[e], g.U[e], g.M[e], rho);
         }
         A[idx] = w;
       }
       __syncthreads();
       if (c.iters > 0) sdp_warm_start(A, g.Q, g.T, np);
       sw += sdp_jacobi(A, g.Q, np, rc, rs, rt, red);
-      // simplex projection of the eigenvalues: tau of the largest valid support
+      // simplex projection of the eigenvalues: tau of the largest valid support; sdp_support and
+      // sdp_support_tau, spelled out (see the file comment; k_sdpw_project runs the same steps through them)
       if (tid < n) lam[tid] = A[tid * np + tid];
       if (tid == 0) kmax = 0;
       __syncthreads();
@@ -339,7 +318,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       if (ok && cnt == kmax) tau = (sum - 1.0) / cnt;  // (equal sets: equal sums, the same bits)
       __syncthreads();
       if (tid < np) {
-        const double m = tid < n ? fmax(lam[tid] - tau, 0.0) : 0.0;
+        const double m = tid < n ? sdp_simplex_weight(lam[tid], tau) : 0.0;
         g.mu[tid] = m;
         lam[tid] = m;
       }
@@ -359,6 +338,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       }
       __syncthreads();
       // ---- X = sum mu_r q_r q_r^T; Z+ = proj_P(X + U); U+ = U + X - Z+; the sums of the stopping rule
+      // (sdp_update_entry's terms, sdp_residuals, sdp_balance_factor and sdp_close_iteration, spelled out below)
       double rp2 = 0.0, rd2 = 0.0, xx = 0.0, zz = 0.0, uu = 0.0, mx = 0.0;
       for (int idx = tid; idx < nn; idx += SDP_THREADS) {
         const int a = idx / n, b = idx % n;
@@ -366,7 +346,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
         for (int r = 0; r < K; ++r) x += lam[pos_list[r]] * (A[r * n + a] * A[r * n + b]);
         const double u = g.U[idx], zo = g.Z[idx];
         const double v = x + u;
-        const double zn = g.mask[idx] != 0.0 ? fmax(v, 0.0) : 0.0;
+        const double zn = sdp_z_plus(v, g.mask[idx] != 0.0);
         const double un = v - zn;
         g.X[idx] = x;
         g.Z[idx] = zn;
@@ -378,12 +358,12 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
         uu += un * un;
         mx += g.M[idx] * x;
       }
-      rp2 = sdp_block_sum(rp2, red);
-      rd2 = sdp_block_sum(rd2, red + SDP_THREADS / 64);
-      xx = sdp_block_sum(xx, red);
-      zz = sdp_block_sum(zz, red + SDP_THREADS / 64);
-      uu = sdp_block_sum(uu, red);
-      mx = sdp_block_sum(mx, red + SDP_THREADS / 64);
+      rp2 = sdp_block_sum<SDP_THREADS>(rp2, red);
+      rd2 = sdp_block_sum<SDP_THREADS>(rd2, red + SDP_THREADS / 64);
+      xx = sdp_block_sum<SDP_THREADS>(xx, red);
+      zz = sdp_block_sum<SDP_THREADS>(zz, red + SDP_THREADS / 64);
+      uu = sdp_block_sum<SDP_THREADS>(uu, red);
+      mx = sdp_block_sum<SDP_THREADS>(mx, red + SDP_THREADS / 64);
       const double r_p = sqrt(rp2), r_d = rho * sqrt(rd2);
       const double e_pri = n * g.eps_abs + g.eps_rel * fmax(sqrt(xx), sqrt(zz));
       const double e_dual = n * g.eps_abs + g.eps_rel * rho * sqrt(uu);
@@ -391,7 +371,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       if (r_p <= e_pri && r_d <= e_dual) {
         __syncthreads();  // U+ of every thread is written
         const double d = sdp_dual_bound(g, rho, A, true, rc, rs, rt, red, sw);
-        conv = fabs(d - mx) <= g.eps_abs + g.eps_rel * fmax(fabs(d), fabs(mx));
+        conv = sdp_gap_closed(d, mx, g.eps_abs, g.eps_rel);
         if (tid == 0) c.dval = d;
       }
       // residual balancing; every thread rescales the entries of U it wrote
@@ -401,9 +381,9 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
         if (r_p > SDP_ADAPT_MU * r_d) f = SDP_ADAPT_TAU;
         else if (r_d > SDP_ADAPT_MU * r_p) f = 1.0 / SDP_ADAPT_TAU;
       }
-      if (f != 1.0)
-        for (int idx = tid; idx < nn; idx += SDP_THREADS) g.U[idx] = f == SDP_ADAPT_TAU ? g.U[idx] / SDP_ADAPT_TAU
-                                                                                         : g.U[idx] * SDP_ADAPT_TAU;
+      const int rescale = sdp_rescale_of(f);
+      if (rescale != SDP_RESCALE_NONE)
+        for (int idx = tid; idx < nn; idx += SDP_THREADS) g.U[idx] = sdp_rescale_u(g.U[idx], rescale);
       __syncthreads();
       if (tid == 0) {
         c.iters = done;
@@ -468,16 +448,10 @@ __global__ void k_sdp_gather_batch(const SdpGatherSrc* __restrict__ table) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (idx >= static_cast<int64_t>(n) * n) return;
   const int32_t a = static_cast<int32_t>(idx / n), b = static_cast<int32_t>(idx % n);
-  const int32_t r = a > b ? a : b, c = a > b ? b : a;
-  const int64_t e = r * g.rs + c * g.cs;
-  const double d = (a == b) ? g.ident : 0.0;
-  const double mv = (g.f64 ? static_cast<const double*>(g.srcM)[e]
-                           : static_cast<double>(static_cast<const float*>(g.srcM)[e])) + d;
-  double cv = mv;
-  if (!g.c_pattern_of_m)
-    cv = (g.f64 ? static_cast<const double*>(g.srcC)[e] : static_cast<double>(static_cast<const float*>(g.srcC)[e])) + d;
+  double mv, mk;
+  sdp_gather_entry(g.srcM, g.srcC, g.f64, g.c_pattern_of_m, g.rs, g.cs, a, b, g.ident, mv, mk);
   g.M[idx] = mv;
-  g.mask[idx] = (cv != 0.0) ? 1.0 : 0.0;
+  g.mask[idx] = mk;
 }
 
 // What the rounding leaves per problem besides evec1 and the node list

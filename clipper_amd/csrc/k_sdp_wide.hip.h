@@ -8,12 +8,15 @@
 // point, no workgroup that waits for another. Every grid and every reduction tree is a function of n alone, so two
 // calls give the same bits on any device.
 //
-// The eigensolver is sdp_jacobi's: cyclic Jacobi in the circle order with the same rotations (sdp_rotation,
-// sdp_rotate_block). One step is ONE launch, k_sdpw_step: the np / 2 pairs of a step partition the indices, so every
-// entry of A lies in exactly one 2 x 2 block (pair k, pair l) and every entry of Q in exactly one (row, pair); the
-// launch reads A_src, Q_src and rewrites A_dst, Q_dst completely (ping-pong), and never reads what it writes. Each
-// workgroup computes the rotations of the pairs its tile needs from A_src into LDS: redundant across workgroups, and
-// cheaper than a launch of its own.
+// Every rule of the iteration is the workgroup route's, read from the same place: the arithmetic from sdp_rules.hpp,
+// the circle order from sdp_circle.hpp, and sdp_block_sum and SdpArgs from k_sdp.hip.h. What
+// this file states is how the work is cut into launches and tiles.
+//
+// The eigensolver is sdp_jacobi's: cyclic Jacobi in the circle order with the same rotations. One step is ONE launch,
+// k_sdpw_step: the np / 2 pairs of a step partition the indices, so every entry of A lies in exactly one 2 x 2 block
+// (pair k, pair l) and every entry of Q in exactly one (row, pair); the launch reads A_src, Q_src and rewrites A_dst,
+// Q_dst completely (ping-pong), and never reads what it writes. Each workgroup computes the rotations of the pairs its
+// tile needs from A_src into LDS: redundant across workgroups, and cheaper than a launch of its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,31 +33,18 @@ static_assert(SDPW_MAX_N <= SDP_THREADS, "the one-workgroup launches hold an ind
 
 enum { SDPW_FORM_PRIMAL = 0, SDPW_FORM_DUAL = 1 };
 enum { SDPW_DECIDE = 0, SDPW_AFTER_DUAL = 1, SDPW_CERTIFY = 2 };
-enum { SDPW_RESCALE_NONE = 0, SDPW_RESCALE_DIVIDE = 1, SDPW_RESCALE_MULTIPLY = 2 };
 
 // device state of one problem: SdpCtl and what the driver reads between launches (one copy)
 struct SdpWideState {
   SdpCtl c;
   int32_t again;      // k_sdpw_norms: the eigensolver sweeps again
   int32_t want_dual;  // k_sdpw_decide: both residuals pass, the dual bound is wanted
-  int32_t rescale;    // k_sdpw_decide: SDPW_RESCALE_* of U
+  int32_t rescale;    // k_sdpw_decide: SDP_RESCALE_* of U
   int32_t npos;       // k_sdpw_project: positive simplex weights
   double w;           // k_sdpw_init: 1 / #diag(mask)
   double r_p, r_d, mx;  // carried from SDPW_DECIDE to SDPW_AFTER_DUAL
 };
 static_assert(sizeof(SdpWideState) <= clipper_sdpw_plan::STATE_BYTES && sizeof(SdpWideState) % 8 == 0, "the plan's state region");
-
-// sum of one double over a workgroup of SDPW_THREADS, the same order on every call; every thread gets the result
-__device__ inline double sdpw_block_sum(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < SDPW_THREADS / 64; ++i) s += red[i];
-  return s;
-}
 
 // ---- INIT: X = Z = diag(mask) / #diag(mask), U = 0, Q = I, mu = diag(X) -------------------------------------------
 __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_init(SdpArgs g, SdpWideState* __restrict__ st) {
@@ -66,8 +56,8 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_init(SdpArgs g, SdpWideSta
   __syncthreads();
   if (tid == 0) {
     SdpWideState s{};
-    s.c = SdpCtl{SDP_RHO0, 0.0, 0.0, 0.0, 0.0, 0, 0, cnt == 0, 0};
-    s.w = cnt ? 1.0 / cnt : 0.0;
+    sdp_init_ctl(s.c, cnt);
+    s.w = sdp_init_weight(cnt);
     *st = s;
   }
 }
@@ -78,15 +68,15 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_init_fill(SdpArgs g, cons
   if (idx >= np * np) return;
   const double w = st->w;
   const int a = idx / np, b = idx % np;
-  g.Q[idx] = (a == b) ? 1.0 : 0.0;
+  g.Q[idx] = sdp_init_q(a, b);
   if (a < n && b < n) {
     const int e = a * n + b;
-    const double x = (a == b && g.mask[e] != 0.0) ? w : 0.0;
+    const double x = sdp_init_entry(a == b && g.mask[e] != 0.0, w);
     g.X[e] = x;
     g.Z[e] = x;
     g.U[e] = 0.0;
   }
-  if (idx < np) g.mu[idx] = (idx < n && g.mask[idx * n + idx] != 0.0) ? w : 0.0;
+  if (idx < np) g.mu[idx] = sdp_init_entry(idx < n && g.mask[idx * n + idx] != 0.0, w);
 }
 
 // ---- form: A <- pad(Z - U + M / rho), or pad(M - rho U) for the dual bound; rho from the device's SdpCtl ----------
@@ -99,7 +89,7 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_form(SdpArgs g, double* _
   double w = 0.0;
   if (a < n && b < n) {
     const int e = a * n + b;
-    w = what == SDPW_FORM_DUAL ? g.M[e] - rho * g.U[e] : g.Z[e] - g.U[e] + g.M[e] / rho;
+    w = what == SDPW_FORM_DUAL ? sdp_form_dual(g.M[e], g.U[e], rho) : sdp_form_primal(g.Z[e], g.U[e], g.M[e], rho);
   }
   A[idx] = w;
 }
@@ -164,14 +154,10 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_norms(const double* __rest
                                                             SdpWideState* __restrict__ st) {
   __shared__ double red[2 * SDP_THREADS / 64];
   double off = 0.0, all = 0.0;
-  for (int idx = threadIdx.x; idx < np * np; idx += SDP_THREADS) {
-    const double v = A[idx];
-    all += v * v;
-    if (idx / np != idx % np) off += v * v;
-  }
-  off = sdp_block_sum(off, red);
-  all = sdp_block_sum(all, red + SDP_THREADS / 64);
-  if (threadIdx.x == 0) st->again = off > SDP_JACOBI_TOL * SDP_JACOBI_TOL * all;
+  for (int idx = threadIdx.x; idx < np * np; idx += SDP_THREADS) sdp_norms_add(A[idx], idx / np == idx % np, off, all);
+  off = sdp_block_sum<SDP_THREADS>(off, red);
+  all = sdp_block_sum<SDP_THREADS>(all, red + SDP_THREADS / 64);
+  if (threadIdx.x == 0) st->again = sdp_sweep_again(off, all);
 }
 
 // ---- one Jacobi step (geometry: clipper_sdpw_plan::step_geom; Q_src == nullptr: no accumulation) -------------------
@@ -208,11 +194,7 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_step(const double* __rest
     int p, q;
     sdp_pair(k, t, np, p, q);
     if (k == l) {
-      const double apq = As[p * np + q];
-      Ad[p * np + p] = As[p * np + p] - rt[i] * apq;
-      Ad[q * np + q] = As[q * np + q] + rt[i] * apq;
-      Ad[p * np + q] = 0.0;
-      Ad[q * np + p] = 0.0;
+      sdp_rotate_diag(As, Ad, np, p, q, rt[i]);
       return;
     }
     int r, s2;
@@ -220,14 +202,7 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_step(const double* __rest
     double npr, nps, nqr, nqs;
     sdp_rotate_block(As[p * np + r], As[p * np + s2], As[q * np + r], As[q * np + s2], rc[i], rs[i], rc[j], rs[j], npr,
                      nps, nqr, nqs);
-    Ad[p * np + r] = npr;
-    Ad[p * np + s2] = nps;
-    Ad[q * np + r] = nqr;
-    Ad[q * np + s2] = nqs;
-    Ad[r * np + p] = npr;
-    Ad[s2 * np + p] = nps;
-    Ad[r * np + q] = nqr;
-    Ad[s2 * np + q] = nqs;
+    sdp_store_block(Ad, np, p, q, r, s2, npr, nps, nqr, nqs);
   } else {
     int row, k;
     if (!plan::q_item(g, wg - g.a_tiles, tid, row, k)) return;
@@ -236,12 +211,15 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_step(const double* __rest
     sdp_pair(k, t, np, p, q);
     const double c = rc[j], s = rs[j];
     const double qp = Qs[row * np + p], qq = Qs[row * np + q];
-    Qd[row * np + p] = c * qp - s * qq;
-    Qd[row * np + q] = s * qp + c * qq;
+    double nqp, nqq;
+    sdp_rotate_q(qp, qq, c, s, nqp, nqq);
+    Qd[row * np + p] = nqp;
+    Qd[row * np + q] = nqq;
   }
 }
 
-// ---- project: the eigenvalues from the diagonal, the simplex rule of sdp_body (the largest valid support) ----------
+// ---- project: the eigenvalues from the diagonal, the simplex rule (the largest valid support): mu, the indices of
+// the positive weights ascending in pos_list and their number in st->npos (n <= SDP_THREADS: an index per work item)
 __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_project(SdpArgs g, const double* __restrict__ A,
                                                               int32_t* __restrict__ pos_list,
                                                               SdpWideState* __restrict__ st) {
@@ -256,25 +234,17 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_project(SdpArgs g, const d
   double sum = 0.0;
   bool ok = false;
   if (tid < n) {
-    const double li = lam[tid];
-    for (int j = 0; j < n; ++j)
-      if (lam[j] >= li) {
-        ++cnt;
-        sum += lam[j];
-      }
-    ok = li > (sum - 1.0) / cnt;
+    ok = sdp_support(lam, n, lam[tid], cnt, sum);
     if (ok) atomicMax(&kmax, cnt);
   }
   __syncthreads();
-  if (ok && cnt == kmax) tau = (sum - 1.0) / cnt;  // (equal sets: equal sums, the same bits)
+  if (ok && cnt == kmax) tau = sdp_support_tau(sum, cnt);  // (equal sets: equal sums, the same bits)
   __syncthreads();
-  double m = 0.0;
   if (tid < np) {
-    m = tid < n ? fmax(lam[tid] - tau, 0.0) : 0.0;
+    const double m = tid < n ? sdp_simplex_weight(lam[tid], tau) : 0.0;
     g.mu[tid] = m;
+    lam[tid] = m;
   }
-  __syncthreads();
-  if (tid < n) lam[tid] = m;
   __syncthreads();
   if (tid == 0) {
     int k = 0;
@@ -317,113 +287,87 @@ __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_update(SdpArgs g, const d
     __syncthreads();
     for (int rr = 0; rr < cnt; ++rr) x += mus[rr] * (Pa[tid / UT][rr] * Pb[tid % UT][rr]);
   }
-  double rp2 = 0.0, rd2 = 0.0, xx = 0.0, zz = 0.0, uu = 0.0, mx = 0.0;
+  SdpSums t{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (a < n && b < n) {
     const int e = a * n + b;
-    const double u = g.U[e], zo = g.Z[e];
-    const double v = x + u;
-    const double zn = g.mask[e] != 0.0 ? fmax(v, 0.0) : 0.0;
-    const double un = v - zn;
+    double zn, un;
+    sdp_update_entry(x, g.U[e], g.Z[e], g.mask[e] != 0.0, g.M[e], zn, un, t);
     g.X[e] = x;
     g.Z[e] = zn;
     g.U[e] = un;
-    rp2 = (x - zn) * (x - zn);
-    rd2 = (zn - zo) * (zn - zo);
-    xx = x * x;
-    zz = zn * zn;
-    uu = un * un;
-    mx = g.M[e] * x;
   }
   const int tiles = gridDim.x;
-  const double sums[6] = {rp2, rd2, xx, zz, uu, mx};
+  const double sums[6] = {t.rp2, t.rd2, t.xx, t.zz, t.uu, t.mx};
 #pragma unroll
   for (int s = 0; s < 6; ++s) {
-    const double v = sdpw_block_sum(sums[s], red);
+    const double v = sdp_block_sum<SDPW_THREADS>(sums[s], red);
     if (tid == 0) part[s * tiles + blockIdx.x] = v;
   }
 }
 
-// ---- decide / finish, one workgroup -----------------------------------------------------------------------------------
-// SDPW_DECIDE: reduce the partials in fixed order and apply the Boyd tolerances; when both residuals pass, ask for the
-// dual bound (want_dual) and leave the rest to SDPW_AFTER_DUAL, which reads lambda_max off the diagonal of A;
-// otherwise finish the iteration here: convergence, residual balancing (the factor of U in `rescale`), SdpCtl.
+// ---- decide, one workgroup ------------------------------------------------------------------------------------------
+// SDPW_DECIDE: reduce the partials in fixed order and apply the tolerances (sdp_residuals); when both residuals pass,
+// ask for the dual bound (want_dual) and leave the rest to SDPW_AFTER_DUAL, which reads lambda_max off the diagonal of
+// A; otherwise close the iteration here: convergence, residual balancing (what it does to U in `rescale`), SdpCtl.
 // SDPW_CERTIFY: dval = lambda_max. `sw`: the Jacobi sweeps since SdpCtl was last written.
-__device__ inline void sdpw_finish(const SdpArgs& g, SdpWideState* st, double r_p, double r_d, double mx, bool pass,
-                                   double d, int32_t sw) {
-  SdpCtl c = st->c;
-  const double rho = c.rho;
-  bool conv = false;
-  if (pass) {
-    conv = fabs(d - mx) <= g.eps_abs + g.eps_rel * fmax(fabs(d), fabs(mx));
-    c.dval = d;
-  }
-  double f = 1.0;
-  const int32_t done = c.iters + 1;
-  if (!conv && done % SDP_ADAPT_EVERY == 0) {
-    if (r_p > SDP_ADAPT_MU * r_d) f = SDP_ADAPT_TAU;
-    else if (r_d > SDP_ADAPT_MU * r_p) f = 1.0 / SDP_ADAPT_TAU;
-  }
-  c.iters = done;
-  c.r_prim = r_p;
-  c.r_dual = r_d;
-  c.pval = mx;
-  c.converged = conv;
-  c.rho = rho * f;
-  c.sweeps += sw;
-  st->c = c;
-  st->want_dual = 0;
-  st->rescale = f == 1.0 ? SDPW_RESCALE_NONE : (f == SDP_ADAPT_TAU ? SDPW_RESCALE_DIVIDE : SDPW_RESCALE_MULTIPLY);
-}
-
 __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_decide(SdpArgs g, SdpWideState* __restrict__ st,
                                                              const double* __restrict__ part, int32_t tiles,
                                                              const double* __restrict__ A, int32_t phase, int32_t sw) {
   __shared__ double red[2 * SDP_THREADS / 64];
   const int tid = threadIdx.x, n = g.n, np = g.np;
+  double r_p, r_d, mx;
+  bool conv = false;
   if (phase == SDPW_DECIDE) {
     double s[6];
     for (int k = 0; k < 6; ++k) {
       double v = 0.0;
       for (int i = tid; i < tiles; i += SDP_THREADS) v += part[k * tiles + i];
-      s[k] = sdp_block_sum(v, red + (k & 1) * (SDP_THREADS / 64));
+      s[k] = sdp_block_sum<SDP_THREADS>(v, red + (k & 1) * (SDP_THREADS / 64));
     }
     if (tid != 0) return;
-    const double rho = st->c.rho;
-    const double r_p = sqrt(s[0]), r_d = rho * sqrt(s[1]);
-    const double e_pri = n * g.eps_abs + g.eps_rel * fmax(sqrt(s[2]), sqrt(s[3]));
-    const double e_dual = n * g.eps_abs + g.eps_rel * rho * sqrt(s[4]);
-    if (r_p <= e_pri && r_d <= e_dual) {
+    mx = s[5];
+    if (sdp_residuals(SdpSums{s[0], s[1], s[2], s[3], s[4], s[5]}, st->c.rho, n, g.eps_abs, g.eps_rel, r_p, r_d)) {
       st->want_dual = 1;
-      st->rescale = SDPW_RESCALE_NONE;
+      st->rescale = SDP_RESCALE_NONE;
       st->r_p = r_p;
       st->r_d = r_d;
-      st->mx = s[5];
-    } else {
-      sdpw_finish(g, st, r_p, r_d, s[5], false, 0.0, sw);
+      st->mx = mx;
+      return;
     }
-    return;
-  }
-  // lambda_max(M - rho U) off the diagonal of the eigensolver's A (the pad index excluded)
-  double d = -__builtin_huge_val();
-  if (tid < n) d = A[tid * np + tid];
-  for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_xor(d, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = d;
-  __syncthreads();
-  if (tid != 0) return;
-  for (int i = 1; i < SDP_THREADS / 64; ++i) d = fmax(d, red[i]);
-  if (phase == SDPW_AFTER_DUAL) {
-    sdpw_finish(g, st, st->r_p, st->r_d, st->mx, true, d, sw);
   } else {
+    // lambda_max(M - rho U) off the diagonal of the eigensolver's A (the pad index excluded); sdp_dual_bound scans
+    // the same diagonal in sequence (max is exact: the order does not show)
+    double d = -__builtin_huge_val();
+    if (tid < n) d = A[tid * np + tid];
+    for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_xor(d, o, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = d;
+    __syncthreads();
+    if (tid != 0) return;
+    for (int i = 1; i < SDP_THREADS / 64; ++i) d = fmax(d, red[i]);
     st->c.dval = d;
-    st->c.sweeps += sw;
+    if (phase == SDPW_CERTIFY) {
+      st->c.sweeps += sw;
+      return;
+    }
+    r_p = st->r_p;
+    r_d = st->r_d;
+    mx = st->mx;
+    conv = sdp_gap_closed(d, mx, g.eps_abs, g.eps_rel);
   }
+  // the iteration ends here (work item 0)
+  SdpCtl c = st->c;
+  const double f = sdp_balance_factor(c.iters + 1, conv, r_p, r_d);
+  sdp_close_iteration(c, r_p, r_d, mx, conv, f, sw);
+  st->c = c;
+  st->want_dual = 0;
+  st->rescale = sdp_rescale_of(f);
 }
 
 // ---- residual balancing: U <- U / tau or U * tau (launched only when k_sdpw_decide asked for it) --------------------
 __global__ void __launch_bounds__(SDPW_THREADS) k_sdpw_scale_u(SdpArgs g, int32_t rescale) {
   const int idx = blockIdx.x * SDPW_THREADS + threadIdx.x;
   if (idx >= g.n * g.n) return;
-  g.U[idx] = rescale == SDPW_RESCALE_DIVIDE ? g.U[idx] / SDP_ADAPT_TAU : g.U[idx] * SDP_ADAPT_TAU;
+  g.U[idx] = sdp_rescale_u(g.U[idx], rescale);
 }
 
 }  // namespace clipper_hip

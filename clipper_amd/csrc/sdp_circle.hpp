@@ -1,6 +1,7 @@
 // sdp_circle.hpp — the circle (round-robin) order of the Jacobi pairs of the semidefinite relaxation's eigensolver
 // (DESIGN.md section 11), stated once for both routes' kernels (k_sdp.hip.h, k_sdp_wide.hip.h) and for the host, which
-// walks it in tests/cpp/test_sdp_wide_plan.cpp. No HIP: builds with g++ as well.
+// walks it in tests/cpp/test_sdp_wide_plan.cpp. No HIP: builds with g++ as well. SDP_HD (host + device inline) is
+// defined here; sdp_rules.hpp, the arithmetic of the iteration, uses it too.
 #pragma once
 
 #if defined(__HIPCC__)

@@ -147,6 +147,41 @@ def test_routes_agree_on_scored_problems(m, rho, seed):
     _certificate(M, Cm, wide, 1e-5, 1e-5)
 
 
+def _scaled_explicit(n, scale):
+    """test_explicit_constraint_matrix's generator with seed 3; the scale covers the diagonal of M too"""
+    rng = np.random.default_rng(3)
+    up = np.triu(rng.random((n, n)) < 0.4, 1)
+    M = np.where(up, rng.uniform(0.1, 1.0, (n, n)), 0.0)
+    M = (M + M.T + np.eye(n)) * scale
+    cu = np.triu(rng.random((n, n)) < 0.5, 1)
+    Cm = (cu | cu.T).astype(float) + np.eye(n)
+    return M, Cm
+
+
+def test_penalty_moves_both_ways_on_both_routes():
+    """Every branch of the decision that ends an iteration, on both routes: the penalty goes down, it goes up, the dual
+    bound is reached after both residuals pass, and the certificate runs at max_iters. The figures are the model's
+    (tests/sdp_model.py, on the CPU)."""
+    prm = _params(eps_abs=1e-6, eps_rel=1e-6, max_iters=60)
+    # n = 9, M small against the penalty: the model halves rho at iterations 10, 20, 30, 40 and 50 (r_p / r_d < 1e-4
+    # at each, against 0.1) and converges at iteration 55 with nodes [0, 4] (rounding margin 0.5). 55 is not pinned:
+    # the gap test at 1e-6 may fall one iteration either way between Jacobi and eigh; rho does not depend on it.
+    M, Cm = _scaled_explicit(9, 0.01)
+    for r in _both_routes(M, Cm, prm):
+        print(f"n = 9 route {r.info.route}: rho {r.info.rho!r}, iters {r.iters}, converged {r.info.converged}, "
+              f"nodes {r.nodes.tolist()}")
+        assert r.info.rho == 2.0 ** -5 and r.info.converged == 1 and 50 <= r.iters < 60
+    # n = 33, M large against the penalty: the model doubles rho at iterations 10 to 50 (r_p / r_d = 4517, 1107, 266,
+    # 60.7, 12.3 against 10), leaves it at iteration 60 (1.65) and stops unconverged: the certificate runs. (The
+    # rounding margin is 0.012: _both_routes leaves the nodes out below 0.05.)
+    M, Cm = _scaled_explicit(33, 100.0)
+    wg, wide = _both_routes(M, Cm, prm)
+    for r in (wg, wide):
+        print(f"n = 33 route {r.info.route}: rho {r.info.rho!r}, iters {r.iters}, converged {r.info.converged}")
+        assert r.info.rho == 32.0 and r.iters == 60 and r.info.converged == 0
+    _certificate(M, Cm, wide, 1e-6, 1e-6)
+
+
 # ---- 2. above 128 against the model, under AUTO --------------------------------------------------------------------
 # (model iterations and the margin of the rounding, computed on the CPU with tests/sdp_model.py: 48 / 0.17, 117 / 0.23,
 # 47 / 0.11, 95 / 0.14; none of the four sits on a stopping threshold)

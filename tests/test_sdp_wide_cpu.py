@@ -91,6 +91,24 @@ def test_plan_header(tmp_path):
     assert "sdp wide plan ok" in out
 
 
+def test_rules_header(tmp_path):
+    """the scalar rules of the iteration (sdp_rules.hpp) on the host, and their constants against the model's"""
+    from tests import sdp_model as sm
+    exe = str(tmp_path / "test_sdp_rules")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "clipper_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "test_sdp_rules.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], timeout=300).decode()
+    assert "sdp rules ok" in out
+    line = [ln for ln in out.splitlines() if ln.startswith("constants:")]
+    assert len(line) == 1
+    words = line[0].split()[1:]
+    got = dict(zip(words[0::2], words[1::2]))
+    assert float(got["RHO0"]) == sm.RHO0 and int(got["ADAPT_EVERY"]) == sm.ADAPT_EVERY
+    assert float(got["ADAPT_MU"]) == sm.ADAPT_MU and float(got["ADAPT_TAU"]) == sm.ADAPT_TAU
+    text = open(os.path.join(ROOT, "clipper_amd", "csrc", "sdp_rules.hpp")).read()
+    assert "#include <hip" not in text and "__global__" not in text
+
+
 def test_plan_header_has_no_hip():
     text = open(os.path.join(ROOT, "clipper_amd", "csrc", "host_sdpwide_plan.hpp")).read()
     assert "#include <hip" not in text and "hipMalloc" not in text
