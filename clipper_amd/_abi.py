@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_batch_max_clique", "clipper_hip_batch_max_clique_stats",
     "clipper_hip_max_clique_seeded", "clipper_hip_batch_max_clique_seeded",
     "clipper_hip_sdp_set_route", "clipper_hip_sdp_route", "clipper_hip_match_descriptors",
+    "clipper_hip_estimate_normals", "clipper_hip_compute_fpfh", "clipper_hip_fpfh_from_points",
 ]
 
 
@@ -205,6 +206,18 @@ class MatchParams(C.Structure):
     _fields_ = [("knn", C.c_int32), ("mutual", C.c_int32), ("ratio", C.c_double), ("max_sqdist", C.c_double)]
 
 
+class Neighborhood(C.Structure):
+    """clipper_neighborhood_t: the first knn entries of a point's nearest-neighbour list in its own cloud (the point
+    included), with radius > 0 only those within it"""
+    _fields_ = [("knn", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double)]
+
+    def __init__(self, knn=16, radius=0.0):
+        super().__init__(int(knn), 0, float(radius))
+
+
+FPFH_DIM = 33  # numbers per FPFH descriptor
+
+
 class BatchProblem(C.Structure):
     """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
 
@@ -294,6 +307,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_match_descriptors.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(MatchParams),
                                                 ip, dp, C.c_int64, ip, dp]
     L.clipper_hip_match_descriptors.restype = C.c_int64
+    nbp = C.POINTER(Neighborhood)
+    L.clipper_hip_estimate_normals.argtypes = [C.c_int, dp, C.c_int64, nbp, dp, dp, ip]
+    L.clipper_hip_compute_fpfh.argtypes = [C.c_int, dp, dp, C.c_int64, nbp, dp, dp, ip]
+    L.clipper_hip_fpfh_from_points.argtypes = [C.c_int, dp, C.c_int64, nbp, dp, nbp, dp, dp]
     L.clipper_hip_set_profiling.argtypes = [vp, C.c_int]
     L.clipper_hip_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.clipper_hip_bench_matvec.argtypes = [vp, C.c_int, dp]
@@ -963,6 +980,78 @@ def match_descriptors(F0, F1, knn: int = 1, mutual: bool = True, ratio: float = 
     n = int(n)
     A = np.stack([buf[:n], buf[n:2 * n]], axis=1).astype(np.int32)
     return (A, sqd[:n].copy(), idx, lsq) if return_lists else (A, sqd[:n].copy())
+
+
+def _cloud(P, what="P"):
+    Pc = _f64_colmajor(P)
+    if Pc.ndim != 2 or Pc.shape[0] != 3:
+        raise ValueError(f"{what} must be 3 x n")
+    return Pc
+
+
+def _viewpoint(viewpoint):
+    if viewpoint is None:
+        return None, None
+    v = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float64).reshape(-1))
+    if v.size != 3:
+        raise ValueError("viewpoint must have 3 coordinates")
+    return v, _dp(v)
+
+
+def estimate_normals(P, knn: int = 16, radius: float = 0.0, viewpoint=None, device: int = 0, return_counts: bool = False):
+    """clipper_hip_estimate_normals: unit surface normals of the cloud P (3 x n, columns = points as `clipper::Data`) on
+    the device. A point's neighbourhood is the first knn (3..32) entries of its nearest-neighbour list in P, itself
+    included, with radius > 0 only those within it; fewer than 3 neighbours give (0, 0, 1). The sign points towards
+    `viewpoint` (3 numbers), or without one makes the largest component positive. Returns N (3 x n), with
+    return_counts also the neighbours kept per point (n int32)."""
+    L = load_library()
+    Pc = _cloud(P)
+    n = Pc.shape[1]
+    nb = Neighborhood(knn, radius)
+    v, vptr = _viewpoint(viewpoint)
+    N = np.zeros((3, n), dtype=np.float64, order="F")
+    cnt = np.zeros(max(n, 1), dtype=np.int32)
+    rc = L.clipper_hip_estimate_normals(device, _dp(Pc), n, C.byref(nb), vptr, _dp(N), _ip(cnt))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return (N, cnt[:n]) if return_counts else N
+
+
+def compute_fpfh(P, N, knn: int = 32, radius: float = 0.0, device: int = 0, return_spfh: bool = False):
+    """clipper_hip_compute_fpfh: FPFH descriptors of the cloud P with unit normals N (both 3 x n) on the device, over
+    the neighbourhood (knn, radius) as estimate_normals defines it. Returns F (33 x n, columns = descriptors: what
+    match_descriptors takes), with return_spfh also (SPFH 33 x n, the neighbours kept per point n int32)."""
+    L = load_library()
+    Pc, Nc = _cloud(P), _cloud(N, "N")
+    n = Pc.shape[1]
+    if Nc.shape[1] != n:
+        raise ValueError("P and N must hold the same number of points")
+    nb = Neighborhood(knn, radius)
+    F = np.zeros((FPFH_DIM, n), dtype=np.float64, order="F")
+    S = np.zeros((FPFH_DIM, n), dtype=np.float64, order="F") if return_spfh else None
+    cnt = np.zeros(max(n, 1), dtype=np.int32) if return_spfh else None
+    rc = L.clipper_hip_compute_fpfh(device, _dp(Pc), _dp(Nc), n, C.byref(nb), _dp(F), _dp(S) if return_spfh else None,
+                                    _ip(cnt) if return_spfh else None)
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return (F, S, cnt[:n]) if return_spfh else F
+
+
+def fpfh_from_points(P, normal_knn: int = 16, normal_radius: float = 0.0, viewpoint=None, knn: int = 32,
+                     radius: float = 0.0, device: int = 0):
+    """clipper_hip_fpfh_from_points: estimate_normals and compute_fpfh in one call (one upload, one search at the
+    larger knn, the normals stay on the device). Returns (F 33 x n, N 3 x n): the two calls' bits."""
+    L = load_library()
+    Pc = _cloud(P)
+    n = Pc.shape[1]
+    nnb, fnb = Neighborhood(normal_knn, normal_radius), Neighborhood(knn, radius)
+    v, vptr = _viewpoint(viewpoint)
+    F = np.zeros((FPFH_DIM, n), dtype=np.float64, order="F")
+    N = np.zeros((3, n), dtype=np.float64, order="F")
+    rc = L.clipper_hip_fpfh_from_points(device, _dp(Pc), n, C.byref(nnb), vptr, C.byref(fnb), _dp(F), _dp(N))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return F, N
 
 
 class HipBatch:

@@ -59,6 +59,7 @@ using namespace clipper_hip;
 #include "host_maxclique.hpp"
 #include "host_matrix_io.hpp"
 #include "host_match.hpp"
+#include "host_features.hpp"
 
 extern "C" {
 
@@ -374,6 +375,24 @@ int64_t clipper_hip_match_descriptors(int device, const double* F0, int64_t n0, 
                                       const clipper_match_params_t* params, int32_t* A_out, double* sqd_out,
                                       int64_t capacity, int32_t* nn_idx_out, double* nn_sqd_out) try {
   return match_descriptors(device, F0, n0, F1, n1, d, params, A_out, sqd_out, capacity, nn_idx_out, nn_sqd_out);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- normals and FPFH descriptors of a point cloud (host_features.hpp) -------------------------
+
+int clipper_hip_estimate_normals(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb,
+                                 const double* viewpoint, double* N_out, int32_t* count_out) try {
+  return estimate_normals(device, P, n, nb, viewpoint, N_out, count_out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_compute_fpfh(int device, const double* P, const double* N, int64_t n, const clipper_neighborhood_t* nb,
+                             double* F_out, double* spfh_out, int32_t* count_out) try {
+  return compute_fpfh(device, P, N, n, nb, F_out, spfh_out, count_out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const clipper_neighborhood_t* normal_nb,
+                                 const double* viewpoint, const clipper_neighborhood_t* feature_nb, double* F_out,
+                                 double* N_out) try {
+  return fpfh_from_points(device, P, n, normal_nb, viewpoint, feature_nb, F_out, N_out);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_set_window(clipper_hip_t* h, int window) try {

@@ -227,6 +227,27 @@ PYBIND11_MODULE(clipperpy, m) {
       "Match feature descriptors (d x n0 and d x n1, one per column, d <= 64) into putative associations on the GPU: "
       "brute-force nearest neighbours with an optional mutual check, ratio test and distance bound.");
 
+  // the stage in front of the matcher: raw cloud -> normals -> FPFH descriptors, on the device
+  m_utils.def(
+      "estimate_normals",
+      [](const clipper::MatrixXd& P, int knn, double radius, const std::vector<double>& viewpoint) {
+        if (!viewpoint.empty() && viewpoint.size() != 3) throw std::invalid_argument("viewpoint must have 3 coordinates");
+        return clipper::registration::estimate_normals(P, clipper::registration::Neighborhood{knn, radius},
+                                                       viewpoint.empty() ? nullptr : viewpoint.data());
+      },
+      "P"_a, "knn"_a = 16, "radius"_a = 0.0, "viewpoint"_a = std::vector<double>{},
+      "Unit surface normals (3 x n) of the cloud P (3 x n, one point per column) on the GPU: per point the smallest "
+      "eigenvector of the covariance of its knn nearest points (itself included; with radius > 0 only those within it), "
+      "signed towards the viewpoint, or without one with its largest component positive.");
+  m_utils.def(
+      "compute_fpfh",
+      [](const clipper::MatrixXd& P, const clipper::MatrixXd& N, int knn, double radius) {
+        return clipper::registration::compute_fpfh(P, N, clipper::registration::Neighborhood{knn, radius});
+      },
+      "P"_a, "N"_a, "knn"_a = 32, "radius"_a = 0.0,
+      "FPFH descriptors (33 x n, one per column: what match_descriptors takes) of the cloud P with unit normals N "
+      "(both 3 x n) on the GPU.");
+
   // The reference fills `clipperpy.dsd` with pybind_utils (py_clipper.cpp:127-128; pybind_dsd is
   // never called), so that is what existing scripts see; the exact DSD solver is out of scope.
   py::module m_dsd = m.def_submodule("dsd");

@@ -1,7 +1,8 @@
 """Host-side pieces either side of the hot path for the 3-D registration use case:
 a PLY point reader, the putative-association generator of the reference's bunny example, and the
-rigid-transform estimate that consumes the selected associations. Plain numpy, except for the two association generators that
-search nearest neighbours on the device (ground_truth_associations, match_descriptors) — the path
+rigid-transform estimate that consumes the selected associations. Plain numpy, except for what searches nearest
+neighbours on the device: the two association generators (ground_truth_associations, match_descriptors) and the
+stage in front of them, raw cloud -> normals -> FPFH descriptors (estimate_normals, compute_fpfh) — the path
 between them is clipper_hip_affinity_* / clipper_hip_solve.
 
 Reference sites (relative to /root/reference): the data-set recipe restates
@@ -198,6 +199,30 @@ def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool
     from . import _abi as abi
     return abi.match_descriptors(np.asarray(F0, dtype=np.float64).T, np.asarray(F1, dtype=np.float64).T, knn=knn,
                                  mutual=mutual, ratio=ratio, max_sqdist=max_sqdist, device=device)
+
+
+def estimate_normals(P: np.ndarray, knn: int = 16, radius: float = 0.0, viewpoint=None, device: int = 0) -> np.ndarray:
+    """Unit surface normals of a cloud, on the GPU (clipper_hip_estimate_normals). P: n x 3, rows = points. A point's
+    neighbourhood is its knn (3..32) nearest points, itself included, with radius > 0 only those within it; the sign
+    points towards `viewpoint`, or without one makes the largest component positive. Returns n x 3."""
+    from . import _abi as abi
+    N = abi.estimate_normals(np.asarray(P, dtype=np.float64).T, knn=knn, radius=radius, viewpoint=viewpoint, device=device)
+    return np.ascontiguousarray(N.T)
+
+
+def compute_fpfh(P: np.ndarray, N: np.ndarray | None = None, knn: int = 32, radius: float = 0.0, normal_knn: int = 16,
+                 normal_radius: float = 0.0, viewpoint=None, device: int = 0) -> np.ndarray:
+    """FPFH descriptors of a cloud, on the GPU. P: n x 3, rows = points; N: their unit normals n x 3, or None to
+    estimate them in the same call over (normal_knn, normal_radius, viewpoint) (clipper_hip_fpfh_from_points; with N
+    given: clipper_hip_compute_fpfh). Returns n x 33, rows = descriptors: what match_descriptors takes."""
+    from . import _abi as abi
+    Pt = np.asarray(P, dtype=np.float64).T
+    if N is None:
+        F, _ = abi.fpfh_from_points(Pt, normal_knn=normal_knn, normal_radius=normal_radius, viewpoint=viewpoint, knn=knn,
+                                    radius=radius, device=device)
+    else:
+        F = abi.compute_fpfh(Pt, np.asarray(N, dtype=np.float64).T, knn=knn, radius=radius, device=device)
+    return np.ascontiguousarray(F.T)
 
 
 def generate_synthetic_correspondences(n0: int, n1: int, Agood: np.ndarray, m: int, rho: float,

@@ -3,9 +3,10 @@
  * @brief The host-side neighbours of the CLIPPER hot path that the reference keeps in its
  *        benchmark utilities (benchmarks/bm_utils.h: namespace utils): PLY vertex reader, synthetic
  *        putative associations, precision / recall — plus the closed-form rigid transform that
- *        consumes the selected associations (examples/python/ex4_bunny.ipynb) and the feature
- *        matcher that produces the putative ones. Thin C++ wrappers over the C ABI
- *        (include/clipper_hip.h); only match_descriptors works on the device.
+ *        consumes the selected associations (examples/python/ex4_bunny.ipynb), the feature
+ *        matcher that produces the putative ones, and the stage in front of it: raw cloud ->
+ *        normals -> FPFH descriptors. Thin C++ wrappers over the C ABI (include/clipper_hip.h);
+ *        match_descriptors, estimate_normals and compute_fpfh work on the device.
  */
 #pragma once
 
@@ -94,6 +95,50 @@ inline Association match_descriptors(const invariants::Data& F0, const invariant
     A(r, 1) = buf.data()[n + r];
   }
   return A;
+}
+
+/// Which points form a point's neighbourhood (clipper_neighborhood_t): the first knn entries of its
+/// nearest-neighbour list in its own cloud, itself included, with radius > 0 only those within it
+struct Neighborhood {
+  int knn = 16;         ///< 3..32
+  double radius = 0.0;  ///< <= 0 = off
+};
+
+/// Unit surface normals of the cloud P (3 x n) on the device (clipper_hip_estimate_normals): 3 x n. The sign points
+/// towards `viewpoint` (3 doubles), or with nullptr makes the largest component positive. Stacked under the points
+/// (rows 0-2 the point, rows 3-5 the normal) they are the 6 x n data of invariants::PointNormalDistance.
+inline invariants::Data estimate_normals(const invariants::Data& P, const Neighborhood& nb = {},
+                                         const double* viewpoint = nullptr, int device = 0) {
+  if (P.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const clipper_neighborhood_t h{nb.knn, 0, nb.radius};
+  invariants::Data N(3, P.cols());
+  if (clipper_hip_estimate_normals(device, P.data(), P.cols(), &h, viewpoint, N.data(), nullptr))
+    throw std::invalid_argument(clipper_hip_last_error());
+  return N;
+}
+
+/// FPFH descriptors of the cloud P with unit normals N (both 3 x n) on the device (clipper_hip_compute_fpfh): 33 x n,
+/// one descriptor per column: what match_descriptors takes.
+inline invariants::Data compute_fpfh(const invariants::Data& P, const invariants::Data& N,
+                                     const Neighborhood& nb = {32, 0.0}, int device = 0) {
+  if (P.rows() != 3 || N.rows() != 3 || P.cols() != N.cols()) throw std::invalid_argument("points and normals must be 3 x n");
+  const clipper_neighborhood_t h{nb.knn, 0, nb.radius};
+  invariants::Data F(33, P.cols());
+  if (clipper_hip_compute_fpfh(device, P.data(), N.data(), P.cols(), &h, F.data(), nullptr, nullptr))
+    throw std::invalid_argument(clipper_hip_last_error());
+  return F;
+}
+
+/// Both stages in one call (clipper_hip_fpfh_from_points): the descriptors of compute_fpfh(P, estimate_normals(P,
+/// normal_nb, viewpoint), feature_nb), bit for bit, with one upload and one search.
+inline invariants::Data compute_fpfh(const invariants::Data& P, const Neighborhood& normal_nb, const double* viewpoint,
+                                     const Neighborhood& feature_nb, int device = 0) {
+  if (P.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const clipper_neighborhood_t hn{normal_nb.knn, 0, normal_nb.radius}, hf{feature_nb.knn, 0, feature_nb.radius};
+  invariants::Data F(33, P.cols());
+  if (clipper_hip_fpfh_from_points(device, P.data(), P.cols(), &hn, viewpoint, &hf, F.data(), nullptr))
+    throw std::invalid_argument(clipper_hip_last_error());
+  return F;
 }
 
 }  // namespace registration

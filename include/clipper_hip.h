@@ -482,6 +482,40 @@ int64_t clipper_hip_match_descriptors(int device, const double* F0, int64_t n0, 
                                       int32_t* A_out, double* sqd_out, int64_t capacity,
                                       int32_t* nn_idx_out, double* nn_sqd_out);
 
+/* SURFACE NORMALS and FPFH DESCRIPTORS of a point cloud on the device: the two inputs at the front of the pipeline
+ * (the normals for PointNormalDistance, the 33-number descriptors for the matcher above). The neighbourhood of point i of the
+ * cloud P (3 x n column-major as `clipper::Data`) is the first knn entries of the list the nearest-neighbour search above
+ * gives for i in P itself (fp64, ascending by (distance, index)): the point is in its own list, recognised by its
+ * index. With radius > 0 only entries with sqd <= radius * radius are kept (the product evaluated once in fp64: a
+ * point exactly on the radius is kept). cnt(i) is the number of kept entries. */
+typedef struct {
+  int32_t knn;       /* 3..32 entries of the list, the point itself included */
+  int32_t reserved;
+  double  radius;    /* <= 0 = off; finite */
+} clipper_neighborhood_t;
+
+/* N_out (3 x n): per point the unit eigenvector of the smallest eigenvalue of the two-pass centred covariance of its
+ * kept neighbours (cyclic Jacobi in fp64); (0, 0, 1) where cnt < 3. Sign: towards `viewpoint` (3 doubles,
+ * n . (v - p) >= 0), or with viewpoint NULL the component of largest magnitude positive. count_out (n, may be NULL):
+ * cnt. Every coordinate must be finite. Stand-alone: needs no context. 0, or <0: error. */
+int clipper_hip_estimate_normals(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb,
+                                 const double* viewpoint, double* N_out, int32_t* count_out);
+
+/* Fast Point Feature Histograms (Rusu et al. 2009) from points and unit normals N (3 x n; squared length within
+ * [0.99, 1.01]). F_out: 33 x n column-major (each descriptor contiguous: what the matcher above takes with
+ * d = 33): three groups of 11 bins (theta, alpha, phi of the Darboux frame), SPFH(i) plus the SPFH of the kept
+ * neighbours weighted by 1 / sqd in list order, each group of the weighted part scaled to 100. spfh_out (33 x n, may
+ * be NULL): SPFH, integer counts times 100 / (cnt - 1). count_out (n, may be NULL): cnt. The contract in full:
+ * DESIGN.md section 9. */
+int clipper_hip_compute_fpfh(int device, const double* P, const double* N, int64_t n, const clipper_neighborhood_t* nb,
+                             double* F_out, double* spfh_out, int32_t* count_out);
+
+/* Both stages in one call: one upload, one search at the larger knn, the normals stay on the device. F_out and N_out
+ * (3 x n, may be NULL) equal those of the two calls above bit for bit. */
+int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const clipper_neighborhood_t* normal_nb,
+                                 const double* viewpoint, const clipper_neighborhood_t* feature_nb,
+                                 double* F_out, double* N_out);
+
 /* Line-search window: how many consecutive step sizes alpha, alpha*beta, ... of the
  * backtracking line search (clipper.cpp:234-251) one pass over M evaluates at once. The
  * trial sequence, the accepted trial and the result are those of the reference for every
