@@ -27,6 +27,7 @@ MC_SEED_ONLY = 3  # CLIPPER_HIP_MC_SEED_ONLY: the seeded entry points only
 SDP_MAX_N = 128  # CLIPPER_HIP_SDP_MAX_N
 SDP_WIDE_MAX_N = 1024  # CLIPPER_HIP_SDP_WIDE_MAX_N
 SDP_ROUTE_WORKGROUP, SDP_ROUTE_AUTO, SDP_ROUTE_WIDE = 0, 1, 2  # CLIPPER_HIP_SDP_ROUTE_*
+KNN_BRUTE, KNN_GRID, KNN_AUTO = 0, 1, 2  # CLIPPER_HIP_KNN_*: the route of the d = 3 nearest-neighbour search
 INVARIANT_MAX_D, INVARIANT_MAX_PARAMS = 32, 16  # CLIPPER_HIP_INVARIANT_MAX_D / _MAX_PARAMS
 
 # every symbol include/clipper_hip.h declares (checked by tests/test_abi_exports.py)
@@ -59,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_max_clique_seeded", "clipper_hip_batch_max_clique_seeded",
     "clipper_hip_sdp_set_route", "clipper_hip_sdp_route", "clipper_hip_match_descriptors",
     "clipper_hip_estimate_normals", "clipper_hip_compute_fpfh", "clipper_hip_fpfh_from_points",
+    "clipper_hip_knn_set_search", "clipper_hip_knn_search", "clipper_hip_knn_last_search",
 ]
 
 
@@ -201,6 +203,13 @@ def _sdp_result(n, X, Y, lam, ev, nodes, info) -> SdpResult:
                      dobj=info.dobj, info=info)
 
 
+class KnnStats(C.Structure):
+    """clipper_hip_knn_stats_t (include/clipper_hip.h): the calling thread's last nearest-neighbour search."""
+
+    _fields_ = [("route", C.c_int32), ("dim", C.c_int32 * 3), ("queries", C.c_int64), ("candidates", C.c_int64),
+                ("auto_min_n", C.c_int64), ("kernels_ms", C.c_double)]
+
+
 class MatchParams(C.Structure):
     """clipper_match_params_t"""
     _fields_ = [("knn", C.c_int32), ("mutual", C.c_int32), ("ratio", C.c_double), ("max_sqdist", C.c_double)]
@@ -335,6 +344,9 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_batch_get_sdp.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
     L.clipper_hip_sdp_set_route.argtypes = [C.c_int]
     L.clipper_hip_sdp_route.argtypes = []
+    L.clipper_hip_knn_set_search.argtypes = [C.c_int]
+    L.clipper_hip_knn_search.argtypes = []
+    L.clipper_hip_knn_last_search.argtypes = [C.POINTER(KnnStats)]
     L.clipper_hip_batch_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_batch_max_clique_stats.argtypes = [vp, ip, ip, ip]
     L.clipper_hip_max_clique_seeded.argtypes = [vp, C.c_int, C.c_double, ip, C.c_int32, C.POINTER(MaxCliqueInfo),
@@ -864,6 +876,34 @@ def knn(P0, P1, knn: int, device: int = 0):
     if rc != 0:
         raise RuntimeError(f"clipper_hip error {rc}: {_last_error()}")
     return idx, sqd
+
+
+def knn_set_search(mode: int) -> int:
+    """clipper_hip_knn_set_search: the process-wide route of the d = 3 nearest-neighbour search behind knn,
+    distance_based_correspondences, estimate_normals, compute_fpfh and fpfh_from_points (KNN_BRUTE, the default;
+    KNN_GRID; KNN_AUTO). Returns the previous mode. Every route returns the same lists, bit for bit; d = 2 searches
+    run brute force in every mode."""
+    prev = load_library().clipper_hip_knn_set_search(int(mode))
+    if prev < 0:
+        raise ClipperError(f"clipper_hip error {prev}: {_last_error()}")
+    return prev
+
+
+def knn_search() -> int:
+    """clipper_hip_knn_search: the current mode."""
+    return load_library().clipper_hip_knn_search()
+
+
+def knn_last_search() -> KnnStats:
+    """clipper_hip_knn_last_search: the route the calling thread's last search took, the grid's cells per axis, the
+    number of queries and the candidates visited (0 for brute force); route is -1 before the first search.
+    auto_min_n: the searched-cloud size from which KNN_AUTO takes the grid; kernels_ms: the device time between two
+    events around the search's kernels."""
+    st = KnnStats()
+    rc = load_library().clipper_hip_knn_last_search(C.byref(st))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return st
 
 
 def sdp_set_route(route: int) -> int:

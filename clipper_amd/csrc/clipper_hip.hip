@@ -2,7 +2,8 @@
 // RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver),
 // host_solve.hpp (the solve of one context), host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp
 // (the fills, matrix set / get, mat-vecs, nearest neighbours; included last: it holds its kernels' place in the code
-// object), host_match.hpp (putative associations from feature descriptors; behind it), host_csc_input.hpp (the sparse input's
+// object), host_match.hpp (putative associations from feature descriptors; behind it), host_knn_grid.hpp (the seam of the
+// nearest-neighbour search and its grid route), host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
@@ -59,6 +60,7 @@ using namespace clipper_hip;
 #include "host_maxclique.hpp"
 #include "host_matrix_io.hpp"
 #include "host_match.hpp"
+#include "host_knn_grid.hpp"
 #include "host_features.hpp"
 
 extern "C" {
@@ -354,7 +356,24 @@ int clipper_hip_sdp_solve_batch(int device, const clipper_sdp_problem_t* problem
   return sdp_solve_batch_impl(device, problems, count, params, infos);
 } CLIPPER_HIP_GUARD_INT
 
-// ---- putative associations (before the path): brute-force nearest neighbours -------------------
+// ---- putative associations (before the path): nearest neighbours -------------------------------
+
+int clipper_hip_knn_set_search(int mode) try {
+  if (mode != CLIPPER_HIP_KNN_BRUTE && mode != CLIPPER_HIP_KNN_GRID && mode != CLIPPER_HIP_KNN_AUTO)
+    return fail(CLIPPER_HIP_E_INVALID, "knn: unknown search mode %d", mode);
+  return g_knn_search.exchange(mode);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_knn_search(void) try {
+  return g_knn_search.load();
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_knn_last_search(clipper_hip_knn_stats_t* out) try {
+  if (!out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  knn_events_read();
+  *out = g_knn_stats;
+  return 0;
+} CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_knn(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d,
                     int knn, int32_t* idx_out, double* sqd_out) try {

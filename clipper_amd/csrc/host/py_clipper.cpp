@@ -248,6 +248,16 @@ PYBIND11_MODULE(clipperpy, m) {
       "FPFH descriptors (33 x n, one per column: what match_descriptors takes) of the cloud P with unit normals N "
       "(both 3 x n) on the GPU.");
 
+  // the route of the d = 3 nearest-neighbour search behind them ("The grid route of the search"): process-wide
+  py::enum_<clipper::registration::KnnSearch>(m_utils, "KnnSearch")
+      .value("Brute", clipper::registration::KnnSearch::Brute)
+      .value("Grid", clipper::registration::KnnSearch::Grid)
+      .value("Auto", clipper::registration::KnnSearch::Auto);
+  m_utils.def("set_knn_search", &clipper::registration::setKnnSearch, "search"_a,
+              "Select the route of the 3-D nearest-neighbour search: brute force (default), a uniform grid on the GPU, or "
+              "the grid from a measured cloud size on. Every route returns the same lists, bit for bit.");
+  m_utils.def("knn_search", &clipper::registration::knnSearch);
+
   // The reference fills `clipperpy.dsd` with pybind_utils (py_clipper.cpp:127-128; pybind_dsd is
   // never called), so that is what existing scripts see; the exact DSD solver is out of scope.
   py::module m_dsd = m.def_submodule("dsd");

@@ -3,24 +3,14 @@
 // the three: the cloud goes to the device once, the cloud is searched against itself once at the larger knn (nearest-K
 // lists are nested: the shorter neighbourhood is a prefix of the longer list), the normals stage and the feature stage
 // are queued on one stream with no host wait in between (the normals stay on the device), and what the caller asked
-// for comes back behind the one wait of the call. Stand-alone: needs no context. The checks are
+// for comes back behind the one wait of the call (the grid route of the search waits twice more inside it: host_knn_grid.hpp).
+// Stand-alone: needs no context. The checks are
 // host_features_check.hpp's. Part of clipper_hip.hip (one translation unit; included there after host_match.hpp).
 #pragma once
 
 #include "host_features_check.hpp"
 
 namespace {
-
-// the cloud's nearest-neighbour lists in itself: k_knn's two kernels at K in {4, 8, 16, 32}
-void feat_search(int K, const double* dP, int64_t n, const MatchGeom& g, double* pd, int32_t* pi, double* od, int32_t* oi,
-                 hipStream_t st) {
-  switch (K) {
-    case 4: knn_run<4, 3>(dP, n, dP, n, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 8: knn_run<8, 3>(dP, n, dP, n, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 16: knn_run<16, 3>(dP, n, dP, n, g.S, g.chunk, pd, pi, od, oi, st); break;
-    default: knn_run<32, 3>(dP, n, dP, n, g.S, g.chunk, pd, pi, od, oi, st); break;
-  }
-}
 
 template <int SLOTS>
 void feat_spfh_run(const double* dP, const double* dN, int64_t n, const int32_t* oi, const double* od, int stride, int knn,
@@ -42,15 +32,13 @@ int features_run(int device, const double* P, const double* N_in, int64_t n, con
   HIPCHK(hipSetDevice(device));
 
   const int K = cf::list_k(std::max(nnb ? nnb->knn : 0, fnb ? fnb->knn : 0));
-  const MatchGeom g = match_geom(n, n);
   const size_t n3 = static_cast<size_t>(n) * 3, nf = fnb ? static_cast<size_t>(n) * FEAT_DIM : 0;
-  const size_t no = static_cast<size_t>(n) * K, np = static_cast<size_t>(g.S) * no;
-  double *dP = nullptr, *dN = nullptr, *dV = nullptr, *pd = nullptr, *od = nullptr, *dS = nullptr, *dF = nullptr;
-  int32_t *pi = nullptr, *oi = nullptr, *dcn = nullptr, *dcf = nullptr;
+  const size_t no = static_cast<size_t>(n) * K;
+  double *dP = nullptr, *dN = nullptr, *dV = nullptr, *od = nullptr, *dS = nullptr, *dF = nullptr;
+  int32_t *oi = nullptr, *dcn = nullptr, *dcf = nullptr;
   DevTemps tmp;
   if (tmp.alloc(device, dP, n3 * sizeof(double)) || tmp.alloc(device, dN, n3 * sizeof(double)) ||
-      tmp.alloc(device, dV, 3 * sizeof(double)) || tmp.alloc(device, pd, np * sizeof(double)) ||
-      tmp.alloc(device, pi, np * sizeof(int32_t)) || tmp.alloc(device, od, no * sizeof(double)) ||
+      tmp.alloc(device, dV, 3 * sizeof(double)) || tmp.alloc(device, od, no * sizeof(double)) ||
       tmp.alloc(device, oi, no * sizeof(int32_t)) || tmp.alloc(device, dS, nf * sizeof(double)) ||
       tmp.alloc(device, dF, nf * sizeof(double)) || tmp.alloc(device, dcn, static_cast<size_t>(n) * sizeof(int32_t)) ||
       tmp.alloc(device, dcf, static_cast<size_t>(n) * sizeof(int32_t))) {
@@ -66,7 +54,8 @@ int features_run(int device, const double* P, const double* N_in, int64_t n, con
   };
   bool ok = up(dP, P, n3) && (nnb || up(dN, N_in, n3)) && (!(nnb && view) || up(dV, view, 3));
   if (ok) {
-    feat_search(K, dP, n, g, pd, pi, od, oi, st);
+    // the cloud's nearest-neighbour lists in itself, K in {4, 8, 16, 32}, by the route of the process-wide mode
+    if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
     if (nnb) {
       const int use_r = nnb->radius > 0.0;
       hipLaunchKernelGGL(k_feat_normals<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,

@@ -371,7 +371,11 @@ int get_dense(Ctx* h, double* M_out, double* C_out) {
   return 0;
 }
 
-// ---- putative associations (before the path): brute-force nearest neighbours -------------------
+// ---- putative associations (before the path): nearest neighbours ---------------------------------
+
+// the seam every d = 2 | 3 search goes through (host_knn_grid.hpp): picks the route, the lists land in od / oi
+int knn_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
+              int32_t* oi, hipStream_t st, DevTemps& tmp);
 
 template <int K>
 void knn_launch(int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S, int64_t chunk, double* pd,
@@ -392,18 +396,12 @@ int knn_search(int device, const double* P0, int64_t n0, const double* P1, int64
   if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
   HIPCHK(hipSetDevice(device));
   const int K = knn <= 1 ? 1 : (knn <= 2 ? 2 : (knn <= 4 ? 4 : (knn <= 8 ? 8 : 16)));
-  // enough workgroups to fill the chip: split pcd1 into S chunks of whole tiles
-  const int64_t qblocks = ceil_div(n0, 256);
-  const int64_t tiles = ceil_div(n1, KNN_TILE);
-  const int S = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, ceil_div(512, qblocks))));
-  const int64_t chunk = ceil_div(tiles, S) * KNN_TILE;
-  double *dP0 = nullptr, *dP1 = nullptr, *pd = nullptr, *od = nullptr;
-  int32_t *pi = nullptr, *oi = nullptr;
+  double *dP0 = nullptr, *dP1 = nullptr, *od = nullptr;
+  int32_t* oi = nullptr;
   const size_t b0 = static_cast<size_t>(n0) * d * sizeof(double), b1 = static_cast<size_t>(n1) * d * sizeof(double);
-  const size_t np = static_cast<size_t>(S) * n0 * K, no = static_cast<size_t>(n0) * K;
+  const size_t no = static_cast<size_t>(n0) * K;
   DevTemps tmp;
-  if (tmp.alloc(device, dP0, b0) || tmp.alloc(device, dP1, b1) || tmp.alloc(device, pd, np * sizeof(double)) ||
-      tmp.alloc(device, pi, np * sizeof(int32_t)) || tmp.alloc(device, od, no * sizeof(double)) ||
+  if (tmp.alloc(device, dP0, b0) || tmp.alloc(device, dP1, b1) || tmp.alloc(device, od, no * sizeof(double)) ||
       tmp.alloc(device, oi, no * sizeof(int32_t))) {
     tmp.release();
     return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
@@ -412,13 +410,8 @@ int knn_search(int device, const double* P0, int64_t n0, const double* P1, int64
   bool ok = hipMemcpyAsync(dP0, P0, b0, hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemcpyAsync(dP1, P1, b1, hipMemcpyHostToDevice, st) == hipSuccess;
   if (ok) {
-    switch (K) {
-      case 1: knn_launch<1>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
-      case 2: knn_launch<2>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
-      case 4: knn_launch<4>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
-      case 8: knn_launch<8>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
-      default: knn_launch<16>(d, dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st); break;
-    }
+    // the route under the process-wide mode (host_knn_grid.hpp): its temporaries join tmp
+    if (int rc = knn_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp)) return rc;
     std::vector<double> hd(no);
     std::vector<int32_t> hi(no);
     ok = hipMemcpy(hd.data(), od, no * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&

@@ -42,6 +42,7 @@
 //   k_maxclique.hip.h the maximum clique of the consistency graph: adjacency bitsets, core numbers, HEU, EXACT
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
 //   k_sdp_wide.hip.h  the same relaxation for one problem over the whole chip, a launch per Jacobi step (n <= 1024)
+//   k_knn_grid.hip.h  the same lists as k_knn.hip.h through a uniform grid over the searched cloud (d = 3)
 //   k_features.hip.h  surface normals and FPFH descriptors of a point cloud (what the matcher and PointNormalDistance take)
 #pragma once
 
@@ -60,3 +61,4 @@
 #include "k_sdp.hip.h"
 #include "k_sdp_wide.hip.h"
 #include "k_features.hip.h"
+#include "k_knn_grid.hip.h"

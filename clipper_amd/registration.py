@@ -13,6 +13,7 @@ TransformationEstimationPointToPoint and benchmarks/bm_utils.cpp uses through Ei
 (without scaling); the error measures are cell 7's."""
 from __future__ import annotations
 
+import contextlib
 import struct
 
 import numpy as np
@@ -184,11 +185,33 @@ def bounded_normal_noise(rng: np.random.Generator, n: int, sigma: float, beta: f
     return eta
 
 
-def ground_truth_associations(pcd0: np.ndarray, pcd1: np.ndarray, radius: float, device: int = 0):
-    """main.cpp:85-91: one-to-one nearest-neighbour associations within `radius`, on the GPU
-    (clipper_hip_distance_based_correspondences). pcd*: n x 3, rows = points."""
+_KNN_SEARCH = {"brute": 0, "grid": 1, "auto": 2}  # clipper_amd._abi.KNN_*
+
+
+@contextlib.contextmanager
+def _knn_search(search):
+    """The process-wide route of the 3-D nearest-neighbour search (clipper_amd._abi.knn_set_search) set to `search`
+    ("brute", "grid", "auto", or None to leave it alone) around one call, and put back as it was found."""
     from . import _abi as abi
-    return abi.distance_based_correspondences(pcd0.T, pcd1.T, 1, radius, True, device=device)
+    if search is None:
+        yield
+        return
+    if search not in _KNN_SEARCH:
+        raise ValueError(f"search must be one of {sorted(_KNN_SEARCH)} or None")
+    prev = abi.knn_set_search(_KNN_SEARCH[search])
+    try:
+        yield
+    finally:
+        abi.knn_set_search(prev)
+
+
+def ground_truth_associations(pcd0: np.ndarray, pcd1: np.ndarray, radius: float, device: int = 0, search: str | None = None):
+    """main.cpp:85-91: one-to-one nearest-neighbour associations within `radius`, on the GPU
+    (clipper_hip_distance_based_correspondences). pcd*: n x 3, rows = points. search: the route of the search for
+    this call ("brute", "grid" or "auto"; None: the process's setting); the result does not depend on it."""
+    from . import _abi as abi
+    with _knn_search(search):
+        return abi.distance_based_correspondences(pcd0.T, pcd1.T, 1, radius, True, device=device)
 
 
 def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool = True, ratio: float = 0.0,
@@ -201,27 +224,32 @@ def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool
                                  mutual=mutual, ratio=ratio, max_sqdist=max_sqdist, device=device)
 
 
-def estimate_normals(P: np.ndarray, knn: int = 16, radius: float = 0.0, viewpoint=None, device: int = 0) -> np.ndarray:
+def estimate_normals(P: np.ndarray, knn: int = 16, radius: float = 0.0, viewpoint=None, device: int = 0,
+                     search: str | None = None) -> np.ndarray:
     """Unit surface normals of a cloud, on the GPU (clipper_hip_estimate_normals). P: n x 3, rows = points. A point's
     neighbourhood is its knn (3..32) nearest points, itself included, with radius > 0 only those within it; the sign
-    points towards `viewpoint`, or without one makes the largest component positive. Returns n x 3."""
+    points towards `viewpoint`, or without one makes the largest component positive. Returns n x 3. search: as in
+    ground_truth_associations."""
     from . import _abi as abi
-    N = abi.estimate_normals(np.asarray(P, dtype=np.float64).T, knn=knn, radius=radius, viewpoint=viewpoint, device=device)
+    with _knn_search(search):
+        N = abi.estimate_normals(np.asarray(P, dtype=np.float64).T, knn=knn, radius=radius, viewpoint=viewpoint, device=device)
     return np.ascontiguousarray(N.T)
 
 
 def compute_fpfh(P: np.ndarray, N: np.ndarray | None = None, knn: int = 32, radius: float = 0.0, normal_knn: int = 16,
-                 normal_radius: float = 0.0, viewpoint=None, device: int = 0) -> np.ndarray:
+                 normal_radius: float = 0.0, viewpoint=None, device: int = 0, search: str | None = None) -> np.ndarray:
     """FPFH descriptors of a cloud, on the GPU. P: n x 3, rows = points; N: their unit normals n x 3, or None to
     estimate them in the same call over (normal_knn, normal_radius, viewpoint) (clipper_hip_fpfh_from_points; with N
-    given: clipper_hip_compute_fpfh). Returns n x 33, rows = descriptors: what match_descriptors takes."""
+    given: clipper_hip_compute_fpfh). Returns n x 33, rows = descriptors: what match_descriptors takes. search: as in
+    ground_truth_associations."""
     from . import _abi as abi
     Pt = np.asarray(P, dtype=np.float64).T
-    if N is None:
-        F, _ = abi.fpfh_from_points(Pt, normal_knn=normal_knn, normal_radius=normal_radius, viewpoint=viewpoint, knn=knn,
-                                    radius=radius, device=device)
-    else:
-        F = abi.compute_fpfh(Pt, np.asarray(N, dtype=np.float64).T, knn=knn, radius=radius, device=device)
+    with _knn_search(search):
+        if N is None:
+            F, _ = abi.fpfh_from_points(Pt, normal_knn=normal_knn, normal_radius=normal_radius, viewpoint=viewpoint, knn=knn,
+                                        radius=radius, device=device)
+        else:
+            F = abi.compute_fpfh(Pt, np.asarray(N, dtype=np.float64).T, knn=knn, radius=radius, device=device)
     return np.ascontiguousarray(F.T)
 
 

@@ -97,6 +97,17 @@ inline Association match_descriptors(const invariants::Data& F0, const invariant
   return A;
 }
 
+/// The route of the d = 3 nearest-neighbour search behind estimate_normals, compute_fpfh and the distance-based
+/// correspondences (clipper_hip_knn_set_search): one process-wide setting. Brute, the default, evaluates every pair;
+/// Grid bins the searched cloud into a uniform grid on the device; Auto takes the grid from
+/// CLIPPER_HIP_KNN_AUTO_MIN_N searched points on. Every route returns the same lists, bit for bit.
+enum class KnnSearch { Brute = 0, Grid = 1, Auto = 2 };
+inline void setKnnSearch(KnnSearch search) {
+  if (clipper_hip_knn_set_search(static_cast<int>(search)) < 0)
+    throw std::invalid_argument(std::string("registration::setKnnSearch: ") + clipper_hip_last_error());
+}
+inline KnnSearch knnSearch() { return static_cast<KnnSearch>(clipper_hip_knn_search()); }
+
 /// Which points form a point's neighbourhood (clipper_neighborhood_t): the first knn entries of its
 /// nearest-neighbour list in its own cloud, itself included, with radius > 0 only those within it
 struct Neighborhood {

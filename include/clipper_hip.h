@@ -450,6 +450,36 @@ int clipper_hip_sdp_solve_batch(int device, const clipper_sdp_problem_t* problem
 int clipper_hip_knn(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d,
                     int knn, int32_t* idx_out, double* sqd_out);
 
+/* The route of the d = 3 nearest-neighbour search behind clipper_hip_knn, clipper_hip_distance_based_correspondences,
+ * clipper_hip_estimate_normals, clipper_hip_compute_fpfh and clipper_hip_fpfh_from_points ("The grid
+ * route of the search"): one process-wide atomic setting, read once at the start of a search. The grid route bins the
+ * searched cloud into a uniform grid on the device and visits rings of cells around each query; every list it returns
+ * equals the brute-force route's entry for entry and bit for bit, for every finite input, so the setting changes the
+ * time of a call and nothing else. d = 2 searches run brute force in every mode; clipper_hip_match_descriptors is not
+ * concerned. set_search returns the previous mode, or CLIPPER_HIP_E_INVALID for an unknown one (the setting is then
+ * unchanged); neither function needs a device. The grid route reports a device allocation failure as
+ * CLIPPER_HIP_E_NOMEM. */
+enum { CLIPPER_HIP_KNN_BRUTE = 0,   /* default: n0 * n1 distance evaluations                                    */
+       CLIPPER_HIP_KNN_GRID  = 1,   /* the uniform grid wherever d == 3                                         */
+       CLIPPER_HIP_KNN_AUTO  = 2 }; /* the grid when d == 3 and n1 >= CLIPPER_HIP_KNN_AUTO_MIN_N, else brute force */
+#define CLIPPER_HIP_KNN_AUTO_MIN_N 24000 /* the smallest measured n1 at which the grid route is faster */
+int clipper_hip_knn_set_search(int mode);
+int clipper_hip_knn_search(void);
+/* The calling thread's last search: the route it took, the grid's cells per axis, the number of queries and the
+ * candidates visited, summed over the queries (all 0 but the route and the queries for brute force). route is -1
+ * before the thread's first search. auto_min_n is CLIPPER_HIP_KNN_AUTO_MIN_N as the library was built. kernels_ms is
+ * the device time between two events around the search's kernels (the grid route's includes the host's wait for the
+ * bounding box in their middle); it is read when this function is called, after the searching call has returned. */
+typedef struct clipper_hip_knn_stats_t {
+  int32_t route;       /* CLIPPER_HIP_KNN_BRUTE or CLIPPER_HIP_KNN_GRID */
+  int32_t dim[3];      /* cells along x, y, z                           */
+  int64_t queries;     /* n0                                            */
+  int64_t candidates;  /* distance evaluations of the grid route        */
+  int64_t auto_min_n;
+  double kernels_ms;
+} clipper_hip_knn_stats_t;
+int clipper_hip_knn_last_search(clipper_hip_knn_stats_t* out);
+
 /* utils::distance_based_correspondences (benchmarks/bm_utils.cpp:147-232): associations
  * (i, nn_k(i)) within `radius`, i ascending / neighbours by distance; with enforce_1to1 one row
  * per point of P1 (ascending) — its closest claimant. A_out: column-major n x 2 with n = the
