@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_sdp_set_route", "clipper_hip_sdp_route", "clipper_hip_match_descriptors",
     "clipper_hip_estimate_normals", "clipper_hip_compute_fpfh", "clipper_hip_fpfh_from_points",
     "clipper_hip_knn_set_search", "clipper_hip_knn_search", "clipper_hip_knn_last_search",
+    "clipper_hip_icp", "clipper_hip_evaluate_registration",
 ]
 
 
@@ -226,6 +227,28 @@ class Neighborhood(C.Structure):
 
 FPFH_DIM = 33  # numbers per FPFH descriptor
 
+ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1  # CLIPPER_ICP_*: clipper_icp_params_t.method
+ICP_CONVERGED, ICP_MAX_ITERATIONS, ICP_TOO_FEW, ICP_DEGENERATE = 0, 1, 2, 3  # clipper_icp_info_t.status
+
+
+class IcpParams(C.Structure):
+    """clipper_icp_params_t"""
+    _fields_ = [("method", C.c_int32), ("max_iterations", C.c_int32), ("max_distance", C.c_double),
+                ("rel_fitness", C.c_double), ("rel_rmse", C.c_double)]
+
+    def __init__(self, method=ICP_POINT_TO_POINT, max_distance=0.0, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6):
+        super().__init__(int(method), int(max_iterations), float(max_distance), float(rel_fitness), float(rel_rmse))
+
+
+class IcpInfo(C.Structure):
+    """clipper_icp_info_t: how an ICP ended (status: ICP_*), the alignment's count / fitness / inlier_rmse under T_out,
+    the search route taken with the target grid's cells per axis and the candidates visited over all iterations, and
+    the device time of the loop. `history` is attached by the Python facade: (iterations + 1) x 3 rows of (count,
+    fitness, rmse)."""
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("count", C.c_int64), ("fitness", C.c_double),
+                ("inlier_rmse", C.c_double), ("route", C.c_int32), ("dim", C.c_int32 * 3), ("candidates", C.c_int64),
+                ("device_ms", C.c_double)]
+
 
 class BatchProblem(C.Structure):
     """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
@@ -320,6 +343,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_estimate_normals.argtypes = [C.c_int, dp, C.c_int64, nbp, dp, dp, ip]
     L.clipper_hip_compute_fpfh.argtypes = [C.c_int, dp, dp, C.c_int64, nbp, dp, dp, ip]
     L.clipper_hip_fpfh_from_points.argtypes = [C.c_int, dp, C.c_int64, nbp, dp, nbp, dp, dp]
+    L.clipper_hip_icp.argtypes = [C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams), dp,
+                                  C.POINTER(IcpInfo), dp]
+    L.clipper_hip_evaluate_registration.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, dp, C.c_double,
+                                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
     L.clipper_hip_set_profiling.argtypes = [vp, C.c_int]
     L.clipper_hip_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.clipper_hip_bench_matvec.argtypes = [vp, C.c_int, dp]
@@ -1092,6 +1119,60 @@ def fpfh_from_points(P, normal_knn: int = 16, normal_radius: float = 0.0, viewpo
     if rc < 0:
         raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
     return F, N
+
+
+def _transform_arg(T, name):
+    """a 4 x 4 transform as the column-major 16 doubles of the C ABI (None: NULL, the identity)"""
+    if T is None:
+        return None, None
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError(f"{name} must be 4 x 4")
+    t = np.ascontiguousarray(T.T).reshape(-1)
+    return t, _dp(t)
+
+
+def icp(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None, max_distance: float = 0.0,
+        max_iterations: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0):
+    """clipper_hip_icp: refine the alignment T_init (4 x 4, None = identity) of the source cloud P_src onto the target
+    P_tgt (both 3 x n, columns = points as `clipper::Data`) on the device. method: ICP_POINT_TO_POINT, or
+    ICP_POINT_TO_PLANE over the target's unit normals N_tgt (3 x n_tgt). A correspondence is the nearest target point
+    of a moved source point, an inlier within max_distance. Returns (T 4 x 4, info): info.status is ICP_*,
+    info.history the (iterations + 1) x 3 rows of (count, fitness, rmse), one per evaluated T."""
+    L = load_library()
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Nt = None if N_tgt is None else _cloud(N_tgt, "N_tgt")
+    if Nt is not None and Nt.shape[1] != Pt.shape[1]:
+        raise ValueError("P_tgt and N_tgt must hold the same number of points")
+    t0, t0p = _transform_arg(T_init, "T_init")
+    prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
+    T = np.zeros(16, dtype=np.float64)
+    info = IcpInfo()
+    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+    rc = L.clipper_hip_icp(device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1], t0p,
+                           C.byref(prm), _dp(T), C.byref(info), _dp(hist))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    info.history = hist[:info.iterations + 1].copy()
+    return T.reshape(4, 4).T.copy(), info
+
+
+def evaluate_registration(P_src, P_tgt, T=None, max_distance: float = 0.0, device: int = 0, return_correspondences: bool = False):
+    """clipper_hip_evaluate_registration: (fitness, inlier_rmse, count) of the alignment T (4 x 4, None = identity) of
+    P_src onto P_tgt (3 x n), as iteration 0 of icp computes them; with return_correspondences also the target index
+    of every source point's correspondence (n_src int32, -1 = no inlier)."""
+    L = load_library()
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    t, tp = _transform_arg(T, "T")
+    fit, rmse, cnt = C.c_double(), C.c_double(), C.c_int64()
+    corr = np.zeros(max(Ps.shape[1], 1), dtype=np.int32) if return_correspondences else None
+    rc = L.clipper_hip_evaluate_registration(device, _dp(Ps), Ps.shape[1], _dp(Pt), Pt.shape[1], tp, float(max_distance),
+                                             C.byref(fit), C.byref(rmse), C.byref(cnt),
+                                             _ip(corr) if return_correspondences else None)
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    out = (fit.value, rmse.value, cnt.value)
+    return out + (corr[:Ps.shape[1]],) if return_correspondences else out
 
 
 class HipBatch:

@@ -62,6 +62,7 @@ using namespace clipper_hip;
 #include "host_match.hpp"
 #include "host_knn_grid.hpp"
 #include "host_features.hpp"
+#include "host_icp.hpp"
 
 extern "C" {
 
@@ -412,6 +413,20 @@ int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const c
                                  const double* viewpoint, const clipper_neighborhood_t* feature_nb, double* F_out,
                                  double* N_out) try {
   return fpfh_from_points(device, P, n, normal_nb, viewpoint, feature_nb, F_out, N_out);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- ICP over a kept search grid, and the evaluation of a registration (host_icp.hpp) ----------
+
+int clipper_hip_icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
+                    int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
+                    clipper_icp_info_t* info, double* history) try {
+  return icp(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init, params, T_out, info, history);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n_src, const double* P_tgt, int64_t n_tgt,
+                                      const double* T, double max_distance, double* fitness, double* inlier_rmse,
+                                      int64_t* count, int32_t* corr_out) try {
+  return evaluate_registration(device, P_src, n_src, P_tgt, n_tgt, T, max_distance, fitness, inlier_rmse, count, corr_out);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_set_window(clipper_hip_t* h, int window) try {

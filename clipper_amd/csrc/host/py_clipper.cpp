@@ -248,6 +248,54 @@ PYBIND11_MODULE(clipperpy, m) {
       "FPFH descriptors (33 x n, one per column: what match_descriptors takes) of the cloud P with unit normals N "
       "(both 3 x n) on the GPU.");
 
+  // the step behind the solve: local refinement of the closed-form transform over the whole clouds, on the device
+  m_utils.def(
+      "icp",
+      [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T_init, const std::string& method,
+         const clipper::MatrixXd& normals, double max_distance, int max_iterations, double rel_fitness, double rel_rmse) {
+        namespace reg = clipper::registration;
+        if (method != "point" && method != "plane") throw std::invalid_argument("method must be \"point\" or \"plane\"");
+        if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
+        reg::IcpParams prm;
+        prm.method = method == "plane" ? reg::IcpMethod::PointToPlane : reg::IcpMethod::PointToPoint;
+        prm.max_distance = max_distance;
+        prm.max_iterations = max_iterations;
+        prm.rel_fitness = rel_fitness;
+        prm.rel_rmse = rel_rmse;
+        const reg::IcpResult r = reg::icp(src, tgt, prm, T_init.data(), normals);
+        clipper::MatrixXd T(4, 4), H(3, static_cast<std::ptrdiff_t>(r.history.size()));
+        for (int i = 0; i < 16; ++i) T.data()[i] = r.T[i];
+        for (size_t k = 0; k < r.history.size(); ++k)
+          for (int c = 0; c < 3; ++c) H.data()[3 * k + c] = r.history[k][c];
+        py::dict info;
+        info["iterations"] = r.iterations;
+        info["status"] = static_cast<int>(r.status);
+        info["count"] = r.count;
+        info["fitness"] = r.fitness;
+        info["inlier_rmse"] = r.inlier_rmse;
+        info["route"] = static_cast<int>(r.route);
+        info["candidates"] = r.candidates;
+        info["device_ms"] = r.device_ms;
+        info["history"] = py::cast(H).attr("T");  // (iterations + 1) x 3: count, fitness, rmse
+        return py::make_tuple(T, info);
+      },
+      "src"_a, "tgt"_a, "T_init"_a, "method"_a = "point", "normals"_a = clipper::MatrixXd(3, 0), "max_distance"_a = 0.0,
+      "max_iterations"_a = 30, "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6,
+      "ICP on the GPU: refine the alignment T_init (4 x 4) of the cloud src onto tgt (3 x n, one point per column). method "
+      "\"point\", or \"plane\" over the target's unit normals (3 x n_tgt). Returns (T, info): info holds iterations, status "
+      "(0 converged, 1 max iterations, 2 too few inliers, 3 degenerate), count, fitness, inlier_rmse, route, candidates, "
+      "device_ms and history ((iterations + 1) x 3: count, fitness, rmse).");
+  m_utils.def(
+      "evaluate_registration",
+      [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T, double max_distance) {
+        if (T.rows() != 4 || T.cols() != 4) throw std::invalid_argument("T must be 4 x 4");
+        const clipper::registration::RegistrationQuality q = clipper::registration::evaluate_registration(src, tgt, T.data(), max_distance);
+        return py::make_tuple(q.fitness, q.inlier_rmse, q.count);
+      },
+      "src"_a, "tgt"_a, "T"_a, "max_distance"_a,
+      "(fitness, inlier_rmse, count) of the alignment T (4 x 4) of src onto tgt (3 x n) on the GPU: a source point is an "
+      "inlier when its nearest target point lies within max_distance.");
+
   // the route of the d = 3 nearest-neighbour search behind them ("The grid route of the search"): process-wide
   py::enum_<clipper::registration::KnnSearch>(m_utils, "KnnSearch")
       .value("Brute", clipper::registration::KnnSearch::Brute)

@@ -1,0 +1,206 @@
+// host_icp.hpp — the driver of clipper_hip_icp and clipper_hip_evaluate_registration ("ICP over a
+// kept search grid"). Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
+// built once and queried every iteration with k_knn_grid<1>; the source is binned by the target's grid once, at
+// T_init, and keeps that order for all iterations (a locality hint, never a correctness input: the lists go to the
+// rows of the original indices). T, the sums, the history and the candidate count stay on the device during the loop;
+// the host reads the 64-byte status record once per iteration through pinned memory to decide whether to queue the
+// next round: the only host wait of an iteration. The brute-force route runs k_knn's two kernels per iteration.
+// Stand-alone: needs no context. The checks are host_icp_check.hpp's, the arithmetic icp_rules.hpp's. Part of
+// clipper_hip.hip (one translation unit; included there last, after host_features.hpp).
+#pragma once
+
+#include "host_icp_check.hpp"
+
+namespace {
+
+// what the loop needs besides device memory: a pinned record and two events, released on every path
+struct IcpHostState {
+  IcpRecord* rec = nullptr;
+  hipEvent_t a = nullptr, b = nullptr;
+  ~IcpHostState() {
+    if (rec) hipHostFree(rec);
+    if (a) hipEventDestroy(a);
+    if (b) hipEventDestroy(b);
+  }
+};
+
+template <int METHOD>
+void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt, int32_t nt,
+               double d2, const double (&o)[3], double* dpart, int32_t nb, const IcpStop& stop, int k, double* dsums, double* dT,
+               IcpRecord* drec, double* dhist, hipStream_t st) {
+  hipLaunchKernelGGL((k_icp_accumulate<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt, dNt, nt,
+                     d2, o[0], o[1], o[2], dpart);
+  hipLaunchKernelGGL((k_icp_step<METHOD>), dim3(1), dim3(256), 0, st, dpart, nb, stop, k, o[0], o[1], o[2], dsums, dT, drec,
+                     dhist);
+}
+
+// Every argument has been checked. T0: column-major 4 x 4. history: (max_iterations + 1) x 3 or null; corr_out: ns or null.
+int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, int64_t nt_, const double* T0,
+            const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info, double* history, int32_t* corr_out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
+  HIPCHK(hipSetDevice(device));
+
+  const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
+  const bool plane = prm.method == ICP_POINT_TO_PLANE;
+  const int terms = icp_terms(prm.method);
+  const int32_t nb = static_cast<int32_t>(ceil_div(ns, ICP_BLOCK));
+  const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
+  const size_t nrows = static_cast<size_t>(prm.max_iterations) + 1;
+  const int route = knn_route(g_knn_search.load(), 3, ns, nt);
+  const MatchGeom geom = match_geom(ns, nt);  // (the brute-force route's chunks: k_knn's own rule)
+  const size_t np = route == CLIPPER_HIP_KNN_BRUTE ? static_cast<size_t>(geom.S) * ns : 0;
+
+  double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr,
+         *dT = nullptr, *dhist = nullptr, *pd = nullptr;
+  int32_t *oi = nullptr, *pi = nullptr, *perm = nullptr, *visited = nullptr;
+  unsigned long long* dsum = nullptr;
+  IcpRecord* drec = nullptr;
+  DevTemps tmp;
+  IcpHostState hs;
+  if (tmp.alloc(device, dPs, s3 * sizeof(double)) || tmp.alloc(device, dPt, t3 * sizeof(double)) ||
+      tmp.alloc(device, dNt, (plane ? t3 : 0) * sizeof(double)) || tmp.alloc(device, dq, s3 * sizeof(double)) ||
+      tmp.alloc(device, od, static_cast<size_t>(ns) * sizeof(double)) || tmp.alloc(device, oi, static_cast<size_t>(ns) * sizeof(int32_t)) ||
+      tmp.alloc(device, dpart, static_cast<size_t>(nb) * terms * sizeof(double)) ||
+      tmp.alloc(device, dsums, static_cast<size_t>(ICP_PLANE_TERMS) * sizeof(double)) || tmp.alloc(device, dT, 16 * sizeof(double)) ||
+      tmp.alloc(device, dhist, nrows * 3 * sizeof(double)) || tmp.alloc(device, drec, sizeof(IcpRecord)) ||
+      tmp.alloc(device, pd, np * sizeof(double)) || tmp.alloc(device, pi, np * sizeof(int32_t)) ||
+      tmp.alloc(device, perm, static_cast<size_t>(ns) * sizeof(int32_t)) ||
+      tmp.alloc(device, visited, static_cast<size_t>(ns) * sizeof(int32_t)) || tmp.alloc(device, dsum, sizeof(unsigned long long)))
+    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hs.rec), sizeof(IcpRecord)));
+  HIPCHK(hipEventCreate(&hs.a));
+  HIPCHK(hipEventCreate(&hs.b));
+
+  hipStream_t st = nullptr;  // the default stream: a stand-alone call
+  IcpRecord first{};
+  first.status = ICP_RUNNING;
+  *hs.rec = first;
+  HIPCHK(hipMemcpyAsync(dPs, Ps, s3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dPt, Pt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (plane) HIPCHK(hipMemcpyAsync(dNt, Nt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dT, T0, 16 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(drec, hs.rec, sizeof(IcpRecord), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(dhist, 0, nrows * 3 * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(dsum, 0, sizeof(unsigned long long), st));
+
+  // the target's index (grid route) or its bounding box alone: the origin of the sums is the box's centre on both routes
+  KnnGridIndex ix;
+  double lo[3], hi[3], o[3];
+  if (route == CLIPPER_HIP_KNN_GRID) {
+    if (int rc = knn_grid_build(device, dPt, nt, ix, st, tmp)) return rc;
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = ix.lo[a];
+      hi[a] = ix.hi[a];
+    }
+  } else if (int rc = knn_grid_bounds(device, dPt, nt, lo, hi, st, tmp)) {
+    return rc;
+  }
+  icp_origin(lo, hi, o);
+
+  const double d2 = prm.max_distance * prm.max_distance;
+  const IcpStop stop{prm.max_iterations, static_cast<int64_t>(ns), prm.rel_fitness, prm.rel_rmse};
+  const dim3 sb(static_cast<unsigned>(ceil_div(ns, 256)));
+  // CLIPPER_HIP_ICP_REBIN=1 (measurement only: tools/icp_probe.py) bins the moved source anew every iteration
+  const char* rebin_env = std::getenv("CLIPPER_HIP_ICP_REBIN");
+  const bool rebin = rebin_env && rebin_env[0] == '1';
+  KnnGridQueries gq;
+  if (route == CLIPPER_HIP_KNN_GRID)
+    if (int rc = knn_grid_alloc_queries(device, ix, ns, gq, tmp)) return rc;
+  KgPoint* const Q = gq.Q;  // (null on the brute-force route)
+  HIPCHK(hipEventRecord(hs.a, st));
+  int k = 0;
+  for (;; ++k) {
+    // the source under the current T: to q, and on the grid route to its place in the query order
+    const bool ordered = k > 0 && Q && !rebin;
+    hipLaunchKernelGGL(k_icp_transform<>, sb, dim3(256), 0, st, dT, dPs, ns, ordered ? perm : nullptr, dq, ordered ? Q : nullptr);
+    if (route == CLIPPER_HIP_KNN_GRID) {
+      if (!ordered) {  // the query order: the source at T_init in the cells of the target's grid, kept from here on
+        knn_grid_bin_queries(ix, dq, ns, gq, st);
+        if (!rebin) hipLaunchKernelGGL(k_icp_order<>, sb, dim3(256), 0, st, Q, ns, perm);
+      }
+      knn_grid_query_lists(ix, 1, Q, ns, od, oi, visited, st);
+      knn_grid_sum_visited(visited, ns, dsum, st);
+    } else {
+      knn_run<1, 3>(dq, ns, dPt, nt, geom.S, geom.chunk, pd, pi, od, oi, st);
+    }
+    if (plane)
+      icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    else
+      icp_round<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    HIPCHK(hipMemcpyAsync(hs.rec, drec, sizeof(IcpRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // the one wait of an iteration
+    if (hs.rec->status != ICP_RUNNING || k >= prm.max_iterations) break;
+  }
+  HIPCHK(hipEventRecord(hs.b, st));
+  HIPCHK(hipGetLastError());
+  if (hs.rec->status == ICP_RUNNING || hs.rec->iterations != k)
+    return fail(CLIPPER_HIP_E_INTERNAL, "icp: the status record of iteration %d was not written", k);
+
+  unsigned long long cand = 0;
+  HIPCHK(hipMemcpyAsync(&cand, dsum, sizeof(cand), hipMemcpyDeviceToHost, st));
+  if (T_out) HIPCHK(hipMemcpyAsync(T_out, dT, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (history) HIPCHK(hipMemcpyAsync(history, dhist, nrows * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  std::vector<int32_t> hi_(corr_out ? static_cast<size_t>(ns) : 0);
+  std::vector<double> hd_(hi_.size());
+  if (corr_out) {
+    HIPCHK(hipMemcpyAsync(hi_.data(), oi, hi_.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hd_.data(), od, hd_.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, hs.a, hs.b));
+  for (size_t i = 0; i < hi_.size(); ++i) corr_out[i] = icp_inlier(hi_[i], hd_[i], d2) ? hi_[i] : -1;
+  if (info) {
+    info->iterations = hs.rec->iterations;
+    info->status = hs.rec->status;
+    info->count = hs.rec->count;
+    info->fitness = hs.rec->fitness;
+    info->inlier_rmse = hs.rec->rmse;
+    info->route = route;
+    for (int a = 0; a < 3; ++a) info->dim[a] = route == CLIPPER_HIP_KNN_GRID ? ix.g.dim[a] : 0;
+    info->candidates = static_cast<int64_t>(cand);
+    info->device_ms = static_cast<double>(ms);
+  }
+  return 0;
+}
+
+const double ICP_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
+int icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt, int64_t n_tgt,
+        const double* T_init, const clipper_icp_params_t* params, double* T_out, clipper_icp_info_t* info, double* history) {
+  namespace ci = clipper_icp;
+  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
+                                           params->rel_rmse}
+                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  std::string why = !T_out ? "null T_out" : "";
+  if (why.empty()) why = ci::check_params(params ? &h : nullptr);
+  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
+  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
+  if (why.empty()) why = ci::check_transform("T_init", T_init);
+  if (why.empty()) why = ci::check_target_normals(h.method, N_tgt, n_tgt);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp: %s", why.c_str());
+  return icp_run(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info, history, nullptr);
+}
+
+int evaluate_registration(int device, const double* P_src, int64_t n_src, const double* P_tgt, int64_t n_tgt, const double* T,
+                          double max_distance, double* fitness, double* inlier_rmse, int64_t* count, int32_t* corr_out) {
+  namespace ci = clipper_icp;
+  std::string why = ci::check_max_distance(max_distance);
+  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
+  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
+  if (why.empty()) why = ci::check_transform("T", T);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "evaluate_registration: %s", why.c_str());
+  const ci::Params h{ICP_POINT_TO_POINT, 0, max_distance, 0.0, 0.0};
+  clipper_icp_info_t info{};
+  if (int rc = icp_run(device, P_src, n_src, P_tgt, nullptr, n_tgt, T ? T : ICP_IDENTITY, h, nullptr, &info, nullptr, corr_out))
+    return rc;
+  if (fitness) *fitness = info.fitness;
+  if (inlier_rmse) *inlier_rmse = info.inlier_rmse;
+  if (count) *count = info.count;
+  return 0;
+}
+
+}  // namespace

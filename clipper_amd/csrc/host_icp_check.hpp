@@ -1,0 +1,73 @@
+// host_icp_check.hpp — ICP and the evaluation of a registration, the part that needs no device: the argument checks of
+// clipper_hip_icp and clipper_hip_evaluate_registration. Pure host code (no HIP): tests/cpp/test_icp_rules.cpp compiles
+// it with g++ alone. A refusal comes back as its message (empty: accepted) and names the offending value; the caller
+// hands it to fail(). Every check runs before any device work.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "host_features_check.hpp"
+#include "icp_rules.hpp"
+
+namespace clipper_icp {
+
+using clipper_match::format;
+
+// clipper_icp_params_t, as the checks read it
+struct Params {
+  int method, max_iterations;
+  double max_distance, rel_fitness, rel_rmse;
+};
+
+// `what` names the cloud in the message ("source", "target")
+inline std::string check_cloud(const char* what, const double* P, int64_t n) {
+  if (!P) return format("null %s point array", what);
+  if (n < 1) return format("%s: a cloud needs at least one point (n = %lld)", what, static_cast<long long>(n));
+  if (n > INT32_MAX) return format("%s: more than 2^31 - 1 points in a cloud (n = %lld)", what, static_cast<long long>(n));
+  for (int64_t p = 0; p < n; ++p)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(P[p * 3 + k]))
+        return format("%s: non-finite value at coordinate %d of point %lld", what, k, static_cast<long long>(p));
+  return {};
+}
+
+// T: column-major 4 x 4, or null for the identity. `what`: "T_init", "T"
+inline std::string check_transform(const char* what, const double* T) {
+  if (!T) return {};
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r)
+      if (!std::isfinite(T[c * 4 + r])) return format("%s: non-finite value at entry (%d, %d)", what, r, c);
+  for (int c = 0; c < 4; ++c)
+    if (T[c * 4 + 3] != (c == 3 ? 1.0 : 0.0))
+      return format("%s: the bottom row must be 0 0 0 1 (entry (3, %d) = %.17g)", what, c, T[c * 4 + 3]);
+  return {};
+}
+
+inline std::string check_max_distance(double d) {
+  if (!(std::isfinite(d) && d > 0.0)) return format("max_distance must be positive and finite (max_distance = %g)", d);
+  return {};
+}
+
+inline std::string check_params(const Params* p) {
+  if (!p) return "null params";
+  if (p->method != clipper_hip::ICP_POINT_TO_POINT && p->method != clipper_hip::ICP_POINT_TO_PLANE)
+    return format("unknown method %d", p->method);
+  std::string why = check_max_distance(p->max_distance);
+  if (!why.empty()) return why;
+  if (p->max_iterations < 0 || p->max_iterations > clipper_hip::ICP_MAX_ITERATIONS_LIMIT)
+    return format("max_iterations must be in 0..%d (max_iterations = %d)", clipper_hip::ICP_MAX_ITERATIONS_LIMIT, p->max_iterations);
+  if (!(p->rel_fitness >= 0.0)) return format("rel_fitness must be at least 0 (rel_fitness = %g)", p->rel_fitness);
+  if (!(p->rel_rmse >= 0.0)) return format("rel_rmse must be at least 0 (rel_rmse = %g)", p->rel_rmse);
+  return {};
+}
+
+// the target's normals: needed by point-to-plane alone, and then unit (host_features_check.hpp's rule)
+inline std::string check_target_normals(int method, const double* N, int64_t n) {
+  if (method != clipper_hip::ICP_POINT_TO_PLANE) return {};
+  if (!N) return "point-to-plane needs the target's normals (N_tgt is null)";
+  return clipper_features::check_normals(N, n);
+}
+
+}  // namespace clipper_icp

@@ -2,7 +2,9 @@
 // three feature entry points reach the nearest-neighbour search (knn_lists), and the driver of its grid route
 // ("The grid route of the search"). The seam reads the process-wide mode once, picks the route,
 // allocates that route's temporaries (the brute-force route's partial lists, or the grid's tables) and queues the
-// kernels on the caller's stream; the lists are on the device when it returns. Part of clipper_hip.hip (one
+// kernels on the caller's stream; the lists are on the device when it returns. The grid route is a build
+// (knn_grid_build: a KnnGridIndex, kept by callers that search one cloud many times) followed by a query
+// (knn_grid_query_lists). Part of clipper_hip.hip (one
 // translation unit; included there after host_match.hpp, whose match_geom it shares, and before host_features.hpp).
 #pragma once
 
@@ -75,70 +77,137 @@ void knn_grid_bin(const double* P, int32_t n, const KnnGrid& g, int32_t ncells, 
   hipLaunchKernelGGL(k_kg_scatter<>, pb, dim3(256), 0, st, P, n, cell, cursor, out);
 }
 
-// The grid route: dP1 binned, dP0 binned by the same grid (skipped when the cloud is searched in itself), the query
-// kernel, the statistics. One host wait in the middle (the bounding box comes back for the plan) and one at the end
-// (the candidate count). Temporaries are tmp's: released by the caller on every path.
-int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const double* dP1, int64_t n1_, double* od, int32_t* oi,
-                   hipStream_t st, DevTemps& tmp) {
-  const int32_t n0 = static_cast<int32_t>(n0_), n1 = static_cast<int32_t>(n1_);
-  const bool self = dP0 == dP1 && n0 == n1;
-  const int nb = static_cast<int>(std::min<int64_t>(KG_BOUNDS_BLOCKS, ceil_div(n1, 256)));
+// The index of a searched cloud: the cloud in cell order (S), the cells' first places (start), the grid and the slab
+// tables. Built once (bounds, plan, bin, slabs: one host wait, for the bounding box), queried any number of times; its
+// arrays are tmp's. lo / hi: the exact bounding box (min and max do not depend on the order of reduction).
+struct KnnGridIndex {
+  KgPoint* S = nullptr;
+  int32_t* start = nullptr;
+  double *smin = nullptr, *pmax = nullptr;
+  KnnGrid g{};
+  int32_t n1 = 0, ncells = 0;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+};
+
+// the exact bounding box of the cloud dP (n x 3): k_kg_bounds' partials folded on the host. One host wait.
+int knn_grid_bounds(int device, const double* dP, int32_t n, double (&lo)[3], double (&hi)[3], hipStream_t st, DevTemps& tmp) {
+  const int nb = static_cast<int>(std::min<int64_t>(KG_BOUNDS_BLOCKS, ceil_div(n, 256)));
   double* dpart = nullptr;
   if (tmp.alloc(device, dpart, static_cast<size_t>(nb) * 6 * sizeof(double)))
     return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  hipLaunchKernelGGL(k_kg_bounds<>, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, dP1, static_cast<int64_t>(n1), dpart);
+  hipLaunchKernelGGL(k_kg_bounds<>, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, dP, static_cast<int64_t>(n), dpart);
   std::vector<double> part(static_cast<size_t>(nb) * 6);
   HIPCHK(hipMemcpyAsync(part.data(), dpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = INFINITY;
+    hi[a] = -INFINITY;
+  }
   for (int b = 0; b < nb; ++b)
     for (int a = 0; a < 3; ++a) {
       lo[a] = std::min(lo[a], part[static_cast<size_t>(b) * 6 + a]);
       hi[a] = std::max(hi[a], part[static_cast<size_t>(b) * 6 + 3 + a]);
     }
-  const KnnGrid g = knn_grid_plan(lo, hi, n1);
-  const int32_t ncells = static_cast<int32_t>(knn_grid_cells(g));
-  const int32_t nslab = g.dim[0] + g.dim[1] + g.dim[2];
+  return 0;
+}
 
-  const size_t ne = static_cast<size_t>(ncells) + 1;
-  KgPoint *S = nullptr, *Q = nullptr;
-  int32_t *cell = nullptr, *counts = nullptr, *start = nullptr, *cursor = nullptr, *visited = nullptr;
-  unsigned long long *kmin = nullptr, *kmax = nullptr, *dsum = nullptr;
-  double *smin = nullptr, *pmax = nullptr;
-  if (tmp.alloc(device, S, static_cast<size_t>(n1) * sizeof(KgPoint)) ||
-      (!self && tmp.alloc(device, Q, static_cast<size_t>(n0) * sizeof(KgPoint))) ||
-      tmp.alloc(device, cell, static_cast<size_t>(std::max(n0, n1)) * sizeof(int32_t)) ||
-      tmp.alloc(device, counts, 2 * ne * sizeof(int32_t)) || tmp.alloc(device, start, ne * sizeof(int32_t)) ||
-      tmp.alloc(device, cursor, ne * sizeof(int32_t)) || tmp.alloc(device, visited, static_cast<size_t>(n0) * sizeof(int32_t)) ||
+// The build: bounds, plan, bin, slabs of the searched cloud dP1. The kernels behind the one wait are queued on st.
+int knn_grid_build(int device, const double* dP1, int32_t n1, KnnGridIndex& ix, hipStream_t st, DevTemps& tmp) {
+  if (int rc = knn_grid_bounds(device, dP1, n1, ix.lo, ix.hi, st, tmp)) return rc;
+  ix.g = knn_grid_plan(ix.lo, ix.hi, n1);
+  ix.n1 = n1;
+  ix.ncells = static_cast<int32_t>(knn_grid_cells(ix.g));
+  const int32_t nslab = ix.g.dim[0] + ix.g.dim[1] + ix.g.dim[2];
+  const size_t ne = static_cast<size_t>(ix.ncells) + 1;
+  int32_t *cell = nullptr, *counts = nullptr, *cursor = nullptr;
+  unsigned long long *kmin = nullptr, *kmax = nullptr;
+  if (tmp.alloc(device, ix.S, static_cast<size_t>(n1) * sizeof(KgPoint)) ||
+      tmp.alloc(device, cell, static_cast<size_t>(n1) * sizeof(int32_t)) || tmp.alloc(device, counts, ne * sizeof(int32_t)) ||
+      tmp.alloc(device, ix.start, ne * sizeof(int32_t)) || tmp.alloc(device, cursor, ne * sizeof(int32_t)) ||
       tmp.alloc(device, kmin, static_cast<size_t>(nslab) * sizeof(unsigned long long)) ||
       tmp.alloc(device, kmax, static_cast<size_t>(nslab) * sizeof(unsigned long long)) ||
-      tmp.alloc(device, smin, static_cast<size_t>(nslab) * sizeof(double)) ||
-      tmp.alloc(device, pmax, static_cast<size_t>(nslab) * sizeof(double)) || tmp.alloc(device, dsum, sizeof(unsigned long long)))
+      tmp.alloc(device, ix.smin, static_cast<size_t>(nslab) * sizeof(double)) ||
+      tmp.alloc(device, ix.pmax, static_cast<size_t>(nslab) * sizeof(double)))
     return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  if (self) Q = S;
+  hipLaunchKernelGGL(k_kg_init<>, dim3(static_cast<unsigned>(std::min<int64_t>(1024, ceil_div(static_cast<int64_t>(ne), 256)))),
+                     dim3(256), 0, st, counts, static_cast<int64_t>(ne), kmin, kmax, static_cast<int64_t>(nslab), nullptr);
+  knn_grid_bin(dP1, n1, ix.g, ix.ncells, cell, counts, ix.start, cursor, kmin, kmax, ix.S, st);
+  hipLaunchKernelGGL(k_kg_slabs<>, dim3(6), dim3(256), 0, st, ix.g, kmin, kmax, ix.smin, ix.pmax);
+  return 0;
+}
 
-  // (counts: the searched cloud's, and behind them the queries')
-  hipLaunchKernelGGL(k_kg_init<>, dim3(static_cast<unsigned>(std::min<int64_t>(1024, ceil_div(2 * static_cast<int64_t>(ne), 256)))),
-                     dim3(256), 0, st, counts, static_cast<int64_t>(2 * ne), kmin, kmax, static_cast<int64_t>(nslab), dsum);
-  knn_grid_bin(dP1, n1, g, ncells, cell, counts, start, cursor, kmin, kmax, S, st);
-  hipLaunchKernelGGL(k_kg_slabs<>, dim3(6), dim3(256), 0, st, g, kmin, kmax, smin, pmax);
-  if (!self) knn_grid_bin(dP0, n0, g, ncells, cell, counts + ne, nullptr, cursor, nullptr, nullptr, Q, st);
+// The queries dP0 (n0 x 3) in the cell order of the index's grid: Q (n0 places) and the binning's scratch, tmp's;
+// knn_grid_bin_queries bins into them, any number of times. No host wait.
+struct KnnGridQueries {
+  KgPoint* Q = nullptr;
+  int32_t *cell = nullptr, *counts = nullptr, *cursor = nullptr;
+};
+
+int knn_grid_alloc_queries(int device, const KnnGridIndex& ix, int32_t n0, KnnGridQueries& q, DevTemps& tmp) {
+  const size_t ne = static_cast<size_t>(ix.ncells) + 1;
+  if (tmp.alloc(device, q.Q, static_cast<size_t>(n0) * sizeof(KgPoint)) ||
+      tmp.alloc(device, q.cell, static_cast<size_t>(n0) * sizeof(int32_t)) || tmp.alloc(device, q.counts, ne * sizeof(int32_t)) ||
+      tmp.alloc(device, q.cursor, ne * sizeof(int32_t)))
+    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  return 0;
+}
+
+void knn_grid_bin_queries(const KnnGridIndex& ix, const double* dP0, int32_t n0, const KnnGridQueries& q, hipStream_t st) {
+  const int64_t ne = static_cast<int64_t>(ix.ncells) + 1;
+  hipLaunchKernelGGL(k_kg_init<>, dim3(static_cast<unsigned>(std::min<int64_t>(1024, ceil_div(ne, 256)))), dim3(256), 0, st, q.counts,
+                     ne, nullptr, nullptr, static_cast<int64_t>(0), nullptr);
+  knn_grid_bin(dP0, n0, ix.g, ix.ncells, q.cell, q.counts, nullptr, q.cursor, nullptr, nullptr, q.Q, st);
+}
+
+// The query against an index: Q in the cell order of its grid (Q == ix.S for a cloud searched in itself), the lists to
+// od / oi (n0 x K, rows by original index), the candidates each query visited to visited (n0). No host wait.
+void knn_grid_query_lists(const KnnGridIndex& ix, int K, const KgPoint* Q, int32_t n0, double* od, int32_t* oi, int32_t* visited,
+                          hipStream_t st) {
   switch (K) {
-    case 1: knn_grid_launch<1>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
-    case 2: knn_grid_launch<2>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
-    case 4: knn_grid_launch<4>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
-    case 8: knn_grid_launch<8>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
-    case 16: knn_grid_launch<16>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
-    default: knn_grid_launch<32>(Q, n0, S, n1, start, g, smin, pmax, od, oi, visited, st); break;
+    case 1: knn_grid_launch<1>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
+    case 2: knn_grid_launch<2>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
+    case 4: knn_grid_launch<4>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
+    case 8: knn_grid_launch<8>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
+    case 16: knn_grid_launch<16>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
+    default: knn_grid_launch<32>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
   }
+}
+
+// visited (n0) added to *dsum on the device (integer adds: the order does not matter)
+void knn_grid_sum_visited(const int32_t* visited, int32_t n0, unsigned long long* dsum, hipStream_t st) {
   hipLaunchKernelGGL(k_kg_sum<>, dim3(static_cast<unsigned>(std::min<int64_t>(256, ceil_div(n0, 256)))), dim3(256), 0, st,
                      visited, static_cast<int64_t>(n0), dsum);
+}
+
+// The grid route: the build over dP1, dP0 binned by the same grid (skipped when the cloud is searched in itself), the
+// query, the statistics. One host wait in the build (the bounding box comes back for the plan) and one at the end
+// (the candidate count). Temporaries are tmp's: released by the caller on every path.
+int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const double* dP1, int64_t n1_, double* od, int32_t* oi,
+                   hipStream_t st, DevTemps& tmp) {
+  const int32_t n0 = static_cast<int32_t>(n0_), n1 = static_cast<int32_t>(n1_);
+  const bool self = dP0 == dP1 && n0 == n1;
+  KnnGridIndex ix;
+  if (int rc = knn_grid_build(device, dP1, n1, ix, st, tmp)) return rc;
+  KgPoint* Q = ix.S;
+  if (!self) {
+    KnnGridQueries q;
+    if (int rc = knn_grid_alloc_queries(device, ix, n0, q, tmp)) return rc;
+    knn_grid_bin_queries(ix, dP0, n0, q, st);
+    Q = q.Q;
+  }
+  int32_t* visited = nullptr;
+  unsigned long long* dsum = nullptr;
+  if (tmp.alloc(device, visited, static_cast<size_t>(n0) * sizeof(int32_t)) || tmp.alloc(device, dsum, sizeof(unsigned long long)))
+    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  HIPCHK(hipMemsetAsync(dsum, 0, sizeof(unsigned long long), st));
+  knn_grid_query_lists(ix, K, Q, n0, od, oi, visited, st);
+  knn_grid_sum_visited(visited, n0, dsum, st);
   unsigned long long sum = 0;
   HIPCHK(hipMemcpyAsync(&sum, dsum, sizeof(sum), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   g_knn_stats.route = CLIPPER_HIP_KNN_GRID;
-  for (int a = 0; a < 3; ++a) g_knn_stats.dim[a] = g.dim[a];
+  for (int a = 0; a < 3; ++a) g_knn_stats.dim[a] = ix.g.dim[a];
   g_knn_stats.candidates = static_cast<int64_t>(sum);
   return 0;
 }

@@ -12,6 +12,8 @@
 #include <sstream>
 #include <unordered_set>
 
+#include "icp_rules.hpp"
+
 namespace {
 
 struct PlyProp {
@@ -153,67 +155,8 @@ int read_ply_vertices(const char* path, std::vector<double>& pts, int64_t& n) {
   return 0;
 }
 
-// 3x3 SVD by one-sided Jacobi on H = U S V^T (columns of U, V); returns det(U V^T)'s sign through R
-// Horn / Arun: R = U diag(1, 1, det(U V^T)) V^T maximises trace(R^T H).
-void rotation_from_cross_covariance(const double H[9], double R[9]) {
-  // one-sided Jacobi: rotate the columns of A = H until they are orthogonal; V accumulates
-  double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  std::memcpy(A, H, sizeof(A));
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double offn = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double a = 0, b = 0, c = 0;
-        for (int i = 0; i < 3; ++i) {
-          a += A[i * 3 + p] * A[i * 3 + p];
-          b += A[i * 3 + q] * A[i * 3 + q];
-          c += A[i * 3 + p] * A[i * 3 + q];
-        }
-        offn = std::max(offn, std::fabs(c) / (std::sqrt(a * b) + 1e-300));
-        if (std::fabs(c) <= 1e-300) continue;
-        const double zeta = (b - a) / (2.0 * c);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-        const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
-        for (int i = 0; i < 3; ++i) {
-          const double ap = A[i * 3 + p], aq = A[i * 3 + q];
-          A[i * 3 + p] = cs * ap - sn * aq;
-          A[i * 3 + q] = sn * ap + cs * aq;
-          const double vp = V[i * 3 + p], vq = V[i * 3 + q];
-          V[i * 3 + p] = cs * vp - sn * vq;
-          V[i * 3 + q] = sn * vp + cs * vq;
-        }
-      }
-    if (offn < 1e-15) break;
-  }
-  // singular values = column norms of A, U = A / s; order does not matter for U V^T, but the
-  // reflection fix must act on the SMALLEST singular direction
-  double s[3], U[9];
-  int smallest = 0;
-  for (int j = 0; j < 3; ++j) {
-    s[j] = std::sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
-    if (s[j] < s[smallest]) smallest = j;
-  }
-  for (int j = 0; j < 3; ++j)
-    for (int i = 0; i < 3; ++i) U[i * 3 + j] = s[j] > 1e-300 ? A[i * 3 + j] / s[j] : 0.0;
-  // a vanishing singular value leaves its column of U undetermined: complete it by a cross product
-  if (s[smallest] <= 1e-300 * (s[0] + s[1] + s[2]) || s[smallest] == 0.0) {
-    const int a = (smallest + 1) % 3, b = (smallest + 2) % 3;
-    U[0 * 3 + smallest] = U[1 * 3 + a] * U[2 * 3 + b] - U[2 * 3 + a] * U[1 * 3 + b];
-    U[1 * 3 + smallest] = U[2 * 3 + a] * U[0 * 3 + b] - U[0 * 3 + a] * U[2 * 3 + b];
-    U[2 * 3 + smallest] = U[0 * 3 + a] * U[1 * 3 + b] - U[1 * 3 + a] * U[0 * 3 + b];
-  }
-  auto det3 = [](const double* M) {
-    return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) +
-           M[2] * (M[3] * M[7] - M[4] * M[6]);
-  };
-  const double sgn = det3(U) * det3(V) < 0 ? -1.0 : 1.0;  // det(U V^T)
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double r = 0.0;
-      for (int k = 0; k < 3; ++k) r += U[i * 3 + k] * (k == smallest ? sgn : 1.0) * V[j * 3 + k];
-      R[i * 3 + j] = r;
-    }
-}
+// (the rotation of a 3 x 3 cross-covariance, rotation_from_cross_covariance, is icp_rules.hpp's: the ICP step on the
+// device and clipper_hip_estimate_rigid_transform here share it)
 
 }  // namespace
 

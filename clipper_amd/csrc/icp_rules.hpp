@@ -1,0 +1,370 @@
+// icp_rules.hpp — the rules of the ICP refinement ("ICP over a kept search grid"), stated once for
+// the kernels (k_icp.hip.h), the driver (host_icp.hpp) and the host: the transform of a point, which list entry is an
+// inlier, the origin the sums are taken about, the terms one source point adds (point-to-point: 17, point-to-plane: 30),
+// the order in which they are added, the step of either method (the rotation of a 3 x 3 cross-covariance; LDL^T of the
+// 6 x 6 normal equations and the Cayley map), the update of T and the stop rule. Plain sequential functions of one
+// point, one set of sums or one iteration: which work item holds what belongs to the kernels. Every expression rounds as
+// written (the build runs with -ffp-contract=off), no floating-point atomics anywhere, so that T_out and the history
+// are functions of the inputs alone. No HIP: builds with g++ as well (tests/cpp/test_icp_rules.cpp runs whole ICPs over
+// this header); tests/icp_model.py restates the same contract in numpy.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#include "features_rules.hpp"
+
+#define ICP_HD FEAT_HD
+
+namespace clipper_hip {
+
+constexpr int ICP_POINT_TO_POINT = 0, ICP_POINT_TO_PLANE = 1;                             // clipper_icp_params_t.method
+constexpr int ICP_RUNNING = -1;                                                            // the record's status between rounds
+constexpr int ICP_CONVERGED = 0, ICP_MAX_ITERATIONS = 1, ICP_TOO_FEW = 2, ICP_DEGENERATE = 3;  // clipper_icp_info_t.status
+constexpr int ICP_MAX_ITERATIONS_LIMIT = 1000;
+constexpr int ICP_BLOCK = 256;  // source points per workgroup of the sums: one partial each
+
+// count, sum(q - o) 3, sum(b - o) 3, sum (b - o)(q - o)^T 9 row-major, sum sqd
+constexpr int ICP_POINT_TERMS = 17;
+// count, the 21 upper entries of J^T J row by row, the 6 of J^T r, sum r^2, sum sqd. (1 + 21 + 6 + 1 + 1 = 30.)
+constexpr int ICP_PLANE_TERMS = 30;
+constexpr int icp_terms(int method) { return method == ICP_POINT_TO_PLANE ? ICP_PLANE_TERMS : ICP_POINT_TERMS; }
+constexpr int icp_min_count(int method) { return method == ICP_POINT_TO_PLANE ? 6 : 3; }
+
+// The rank threshold of the point-to-plane system: DEGENERATE when a pivot of LDL^T is <= ICP_RANK_TOL times the largest
+// diagonal entry of J^T J. The sums carry a relative rounding noise of about n * 2^-53 (1e-16 .. 1e-12 for the clouds
+// this serves): 1e-10 sits above that noise and far below the smallest pivot ratio of any scan that constrains all six
+// degrees of freedom (1e-4 and more).
+constexpr double ICP_RANK_TOL = 1e-10;
+// The point-to-point step is refused (DEGENERATE) when the fitted matrix is not a rotation: |det - 1| beyond this
+// (a cross-covariance of rank < 2 leaves the fit undetermined).
+constexpr double ICP_DET_TOL = 1e-9;
+
+// ---- the transform of a point ---------------------------------------------------------------------------------------
+// T: column-major 4 x 4 (entry (r, c) at T[c * 4 + r]); q_a = ((T_a0 x + T_a1 y) + T_a2 z) + T_a3
+ICP_HD void icp_transform_point(const double* T, const double (&p)[3], double (&q)[3]) {
+  for (int a = 0; a < 3; ++a) q[a] = ((T[0 * 4 + a] * p[0] + T[1 * 4 + a] * p[1]) + T[2 * 4 + a] * p[2]) + T[3 * 4 + a];
+}
+
+// ---- correspondence -------------------------------------------------------------------------------------------------
+// (j, sqd): the K = 1 entry of the search contract for q in the target. d2 = max_distance * max_distance, evaluated
+// once by the caller.
+ICP_HD bool icp_inlier(int32_t j, double sqd, double d2) { return feat_kept(j, sqd, true, d2); }
+
+// ---- the origin: the centre of the target's bounding box ------------------------------------------------------------
+ICP_HD void icp_origin(const double (&lo)[3], const double (&hi)[3], double (&o)[3]) {
+  for (int a = 0; a < 3; ++a) o[a] = (lo[a] + hi[a]) * 0.5;
+}
+
+// ---- the terms of one inlier (a non-inlier adds +0.0 to every sum) --------------------------------------------------
+ICP_HD void icp_point_terms(const double (&q)[3], const double (&b)[3], double sqd, const double (&o)[3],
+                            double (&t)[ICP_POINT_TERMS]) {
+  const double qo[3] = {q[0] - o[0], q[1] - o[1], q[2] - o[2]};
+  const double bo[3] = {b[0] - o[0], b[1] - o[1], b[2] - o[2]};
+  t[0] = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    t[1 + a] = qo[a];
+    t[4 + a] = bo[a];
+  }
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) t[7 + r * 3 + c] = bo[r] * qo[c];
+  t[16] = sqd;
+}
+
+// J = [(q - o) x n, n], r = (q - b) . n
+ICP_HD void icp_plane_terms(const double (&q)[3], const double (&b)[3], const double (&n)[3], double sqd,
+                            const double (&o)[3], double (&t)[ICP_PLANE_TERMS]) {
+  const double qo[3] = {q[0] - o[0], q[1] - o[1], q[2] - o[2]};
+  const double d[3] = {q[0] - b[0], q[1] - b[1], q[2] - b[2]};
+  double c[3];
+  feat_cross(qo, n, c);
+  const double J[6] = {c[0], c[1], c[2], n[0], n[1], n[2]};
+  const double r = feat_dot(d, n);
+  t[0] = 1.0;
+  int at = 1;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) t[at++] = J[i] * J[j];
+  for (int i = 0; i < 6; ++i) t[22 + i] = J[i] * r;
+  t[28] = r * r;
+  t[29] = sqd;
+}
+
+// ---- the order of addition ------------------------------------------------------------------------------------------
+// Work item i of a workgroup of ICP_BLOCK holds source point (block * ICP_BLOCK + i) in its original order (+0.0 past
+// the end); the workgroup folds by the halving tree, stride 128 down to 1: v[i] = v[i] + v[i + s] for i < s; v[0] is
+// its partial. One workgroup folds the partials: item t starts from +0.0 and adds partials t, t + 256, ... in that
+// order; then the same tree. icp_tree is that tree written sequentially over ICP_BLOCK values with stride `pitch`
+// (the host's copy: tests/cpp/test_icp_rules.cpp).
+ICP_HD void icp_tree(double* v, int pitch) {
+  for (int s = ICP_BLOCK / 2; s > 0; s >>= 1)
+    for (int i = 0; i < s; ++i) v[i * pitch] = v[i * pitch] + v[(i + s) * pitch];
+}
+
+// ---- the rotation of a cross-covariance (Horn / Arun) ---------------------------------------------------------------
+// 3 x 3 SVD by one-sided Jacobi on H = U S V^T (row-major); R = U diag(1, 1, det(U V^T)) V^T maximises trace(R^T H),
+// the reflection fix acting on the smallest singular direction. Also behind clipper_hip_estimate_rigid_transform.
+ICP_HD double icp_det3(const double* M) {
+  return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+}
+
+ICP_HD void rotation_from_cross_covariance(const double* H, double* R) {
+  // one-sided Jacobi: rotate the columns of A = H until they are orthogonal; V accumulates
+  double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  for (int i = 0; i < 9; ++i) A[i] = H[i];
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double offn = 0.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int p = 0; p < 2; ++p)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int q = p + 1; q < 3; ++q) {
+        double a = 0, b = 0, c = 0;
+        for (int i = 0; i < 3; ++i) {
+          a += A[i * 3 + p] * A[i * 3 + p];
+          b += A[i * 3 + q] * A[i * 3 + q];
+          c += A[i * 3 + p] * A[i * 3 + q];
+        }
+        const double rel = fabs(c) / (sqrt(a * b) + 1e-300);
+        offn = offn < rel ? rel : offn;
+        if (fabs(c) <= 1e-300) continue;
+        const double zeta = (b - a) / (2.0 * c);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+        for (int i = 0; i < 3; ++i) {
+          const double ap = A[i * 3 + p], aq = A[i * 3 + q];
+          A[i * 3 + p] = cs * ap - sn * aq;
+          A[i * 3 + q] = sn * ap + cs * aq;
+          const double vp = V[i * 3 + p], vq = V[i * 3 + q];
+          V[i * 3 + p] = cs * vp - sn * vq;
+          V[i * 3 + q] = sn * vp + cs * vq;
+        }
+      }
+    if (offn < 1e-15) break;
+  }
+  // singular values = column norms of A, U = A / s; the reflection fix must act on the SMALLEST singular direction
+  // (the first among equal ones)
+  double s[3], U[9];
+  for (int j = 0; j < 3; ++j) s[j] = sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
+  int smallest = 0;
+  double least = s[0];
+  if (s[1] < least) {
+    smallest = 1;
+    least = s[1];
+  }
+  if (s[2] < least) {
+    smallest = 2;
+    least = s[2];
+  }
+  for (int j = 0; j < 3; ++j)
+    for (int i = 0; i < 3; ++i) U[i * 3 + j] = s[j] > 1e-300 ? A[i * 3 + j] / s[j] : 0.0;
+  // a vanishing singular value leaves its column of U undetermined: complete it by a cross product
+  if (least <= 1e-300 * (s[0] + s[1] + s[2]) || least == 0.0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int m = 0; m < 3; ++m)
+      if (m == smallest) {
+        const int a = (m + 1) % 3, b = (m + 2) % 3;
+        U[0 * 3 + m] = U[1 * 3 + a] * U[2 * 3 + b] - U[2 * 3 + a] * U[1 * 3 + b];
+        U[1 * 3 + m] = U[2 * 3 + a] * U[0 * 3 + b] - U[0 * 3 + a] * U[2 * 3 + b];
+        U[2 * 3 + m] = U[0 * 3 + a] * U[1 * 3 + b] - U[1 * 3 + a] * U[0 * 3 + b];
+      }
+  }
+  const double sgn = icp_det3(U) * icp_det3(V) < 0 ? -1.0 : 1.0;  // det(U V^T)
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double r = 0.0;
+      for (int k = 0; k < 3; ++k) r += U[i * 3 + k] * (k == smallest ? sgn : 1.0) * V[j * 3 + k];
+      R[i * 3 + j] = r;
+    }
+}
+
+// dT (column-major 4 x 4) of the rotation R (row-major 3 x 3) about the origin o followed by the shift v:
+// x -> R (x - o) + o + v, so the translation is v_a + (o_a - (R o)_a)
+ICP_HD void icp_about_origin(const double* R, const double (&v)[3], const double (&o)[3], double* dT) {
+  for (int a = 0; a < 3; ++a) {
+    const double Ro = (R[a * 3 + 0] * o[0] + R[a * 3 + 1] * o[1]) + R[a * 3 + 2] * o[2];
+    for (int c = 0; c < 3; ++c) dT[c * 4 + a] = R[a * 3 + c];
+    dT[3 * 4 + a] = v[a] + (o[a] - Ro);
+    dT[a * 4 + 3] = 0.0;
+  }
+  dT[15] = 1.0;
+}
+
+// ---- the step, point-to-point ---------------------------------------------------------------------------------------
+// S: the 17 sums. Centroids mq = sum(q - o) / n, mb = sum(b - o) / n; H_rc = S_rc - sum(b - o)_r * mq_c (the centred
+// cross-covariance sum (b - mb)(q - mq)^T); dR = its rotation; the shift is mb - dR mq, about o. false: DEGENERATE.
+ICP_HD bool icp_step_point(const double* S, const double (&o)[3], double* dT) {
+  const double n = S[0];
+  const double mq[3] = {S[1] / n, S[2] / n, S[3] / n};
+  const double mb[3] = {S[4] / n, S[5] / n, S[6] / n};
+  double H[9], R[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) H[r * 3 + c] = S[7 + r * 3 + c] - S[4 + r] * mq[c];
+  rotation_from_cross_covariance(H, R);
+  double v[3];
+  for (int a = 0; a < 3; ++a) v[a] = mb[a] - ((R[a * 3 + 0] * mq[0] + R[a * 3 + 1] * mq[1]) + R[a * 3 + 2] * mq[2]);
+  icp_about_origin(R, v, o, dT);
+  return fabs(icp_det3(R) - 1.0) <= ICP_DET_TOL;
+}
+
+// ---- the step, point-to-plane ---------------------------------------------------------------------------------------
+// the Cayley map of the rotation vector w: a = w / 2, K = skew(a), R = I + 2 / (1 + |a|^2) (K + K^2), K^2 = a a^T - |a|^2 I.
+// An exact rotation for every w, and no sin or cos.
+ICP_HD void icp_cayley(const double (&w)[3], double* R) {
+  const double a[3] = {w[0] * 0.5, w[1] * 0.5, w[2] * 0.5};
+  const double aa = feat_dot(a, a);
+  const double s = 2.0 / (1.0 + aa);
+  const double K[9] = {0.0, -a[2], a[1], a[2], 0.0, -a[0], -a[1], a[0], 0.0};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      R[r * 3 + c] = (r == c ? 1.0 : 0.0) + s * (K[r * 3 + c] + (a[r] * a[c] - (r == c ? aa : 0.0)));
+}
+
+// S: the 30 sums. J^T J xi = -J^T r by LDL^T without pivoting; every loop runs in ascending order of its index.
+// false: DEGENERATE (a pivot <= ICP_RANK_TOL * the largest diagonal entry, or not a number).
+ICP_HD bool icp_step_plane(const double* S, const double (&o)[3], double* dT) {
+  double A[6][6], L[6][6], D[6], y[6], x[6];
+  int at = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 6; ++i)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = i; j < 6; ++j) {
+      A[i][j] = S[at];
+      A[j][i] = S[at];
+      ++at;
+    }
+  double big = A[0][0];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 1; i < 6; ++i) big = A[i][i] > big ? A[i][i] : big;
+  bool ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < j; ++k) d = d - L[j][k] * (L[j][k] * D[k]);
+    ok = ok && d > ICP_RANK_TOL * big;
+    D[j] = d;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int k = 0; k < j; ++k) s = s - L[i][k] * (L[j][k] * D[k]);
+      L[i][j] = s / d;
+    }
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 6; ++i) {
+    double s = -S[22 + i];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+    y[i] = s;
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i] / D[i];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
+    x[i] = s;
+  }
+  const double w[3] = {x[0], x[1], x[2]}, v[3] = {x[3], x[4], x[5]};
+  double R[9];
+  icp_cayley(w, R);
+  icp_about_origin(R, v, o, dT);
+  return ok;
+}
+
+// ---- the update: T <- dT T, nothing re-orthonormalised --------------------------------------------------------------
+ICP_HD void icp_compose(const double* dT, double* T) {
+  double N[16];
+  for (int c = 0; c < 4; ++c) {
+    for (int r = 0; r < 3; ++r) {
+      const double v = (dT[0 * 4 + r] * T[c * 4 + 0] + dT[1 * 4 + r] * T[c * 4 + 1]) + dT[2 * 4 + r] * T[c * 4 + 2];
+      N[c * 4 + r] = c == 3 ? v + dT[3 * 4 + r] : v;
+    }
+    N[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
+  }
+  for (int i = 0; i < 16; ++i) T[i] = N[i];
+}
+
+// ---- one iteration behind the sums ----------------------------------------------------------------------------------
+// the record the step kernel leaves (64 bytes); the host reads it once per iteration
+struct alignas(64) IcpRecord {
+  int32_t iterations;  // k: T has been updated k times when the last history row was taken
+  int32_t status;      // ICP_RUNNING, or why the loop ended
+  int64_t count;
+  double fitness, rmse;  // of the last history row
+  double pad[4];
+};
+static_assert(sizeof(IcpRecord) == 64, "the status record is 64 bytes");
+
+struct IcpStop {
+  int max_iterations;
+  int64_t n_src;
+  double rel_fitness, rel_rmse;
+};
+
+// Iteration k from its sums S (the last of them sum sqd): fitness = count / n_src, rmse = sqrt(sum sqd / count) (0
+// without inliers), the history row (count, fitness, rmse), then the first that holds of: CONVERGED (k >= 1, both
+// changes below their bounds), TOO_FEW, MAX_ITERATIONS (k == max_iterations), DEGENERATE (the step refuses, or the
+// updated T would hold a value that is not finite); else T <- dT T and the loop goes on. rec carries iteration k - 1's
+// fitness and rmse in, and this iteration's out. T is touched only where the loop goes on.
+template <int METHOD>
+ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (&o)[3], double* T, IcpRecord& rec, double* row) {
+  const double cnt = S[0];
+  const double fitness = cnt / static_cast<double>(p.n_src);
+  const double rmse = cnt > 0.0 ? sqrt(S[icp_terms(METHOD) - 1] / cnt) : 0.0;
+  if (row) {
+    row[0] = cnt;
+    row[1] = fitness;
+    row[2] = rmse;
+  }
+  int status = ICP_RUNNING;
+  if (k >= 1 && fabs(fitness - rec.fitness) < p.rel_fitness && fabs(rmse - rec.rmse) < p.rel_rmse) status = ICP_CONVERGED;
+  else if (cnt < static_cast<double>(icp_min_count(METHOD))) status = ICP_TOO_FEW;
+  else if (k >= p.max_iterations) status = ICP_MAX_ITERATIONS;
+  else {
+    double dT[16], N[16];
+    const bool ok = METHOD == ICP_POINT_TO_PLANE ? icp_step_plane(S, o, dT) : icp_step_point(S, o, dT);
+    for (int i = 0; i < 16; ++i) N[i] = T[i];
+    icp_compose(dT, N);
+    bool finite = true;
+    for (int i = 0; i < 16; ++i) finite = finite && fabs(N[i]) <= 1.7976931348623157e308;
+    if (ok && finite)
+      for (int i = 0; i < 16; ++i) T[i] = N[i];
+    else
+      status = ICP_DEGENERATE;
+  }
+  rec.iterations = k;
+  rec.status = status;
+  rec.count = static_cast<int64_t>(cnt);
+  rec.fitness = fitness;
+  rec.rmse = rmse;
+}
+
+}  // namespace clipper_hip

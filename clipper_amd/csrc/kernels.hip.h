@@ -43,6 +43,7 @@
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
 //   k_sdp_wide.hip.h  the same relaxation for one problem over the whole chip, a launch per Jacobi step (n <= 1024)
 //   k_knn_grid.hip.h  the same lists as k_knn.hip.h through a uniform grid over the searched cloud (d = 3)
+//   k_icp.hip.h       the ICP refinement over that grid: transform, the sums of either metric, the step on one thread
 //   k_features.hip.h  surface normals and FPFH descriptors of a point cloud (what the matcher and PointNormalDistance take)
 #pragma once
 
@@ -62,3 +63,4 @@
 #include "k_sdp_wide.hip.h"
 #include "k_features.hip.h"
 #include "k_knn_grid.hip.h"
+#include "k_icp.hip.h"

@@ -253,6 +253,41 @@ def compute_fpfh(P: np.ndarray, N: np.ndarray | None = None, knn: int = 32, radi
     return np.ascontiguousarray(F.T)
 
 
+_ICP_METHODS = {"point": 0, "plane": 1}  # clipper_amd._abi.ICP_POINT_TO_POINT / ICP_POINT_TO_PLANE
+
+
+def icp(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None, method: str = "point",
+        normals: np.ndarray | None = None, max_distance: float = 0.0, max_iterations: int = 30, rel_fitness: float = 1e-6,
+        rel_rmse: float = 1e-6, device: int = 0, search: str | None = None):
+    """Local refinement of a registration, on the GPU (clipper_hip_icp): ICP from the alignment T_init (4 x 4, None =
+    identity) of the cloud src onto tgt (n x 3, rows = points), e.g. the estimate_rigid_transform of a solve's selected
+    associations. method "point" (point-to-point) or "plane" (point-to-plane over `normals`, the target's unit normals
+    n_tgt x 3, e.g. estimate_normals(tgt)). A moved source point corresponds to its nearest target point and counts as
+    an inlier within max_distance. Returns (T 4 x 4, info): info.status (clipper_amd._abi.ICP_*), info.iterations,
+    info.count, info.fitness, info.inlier_rmse, info.history ((iterations + 1) x 3: count, fitness, rmse), info.route.
+    search: as in ground_truth_associations; the result does not depend on it."""
+    from . import _abi as abi
+    if method not in _ICP_METHODS:
+        raise ValueError(f"method must be one of {sorted(_ICP_METHODS)}")
+    with _knn_search(search):
+        return abi.icp(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T_init=T_init,
+                       method=_ICP_METHODS[method], N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T,
+                       max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
+                       device=device)
+
+
+def evaluate_registration(src: np.ndarray, tgt: np.ndarray, T: np.ndarray | None = None, max_distance: float = 0.0,
+                          device: int = 0, search: str | None = None, return_correspondences: bool = False):
+    """How good the alignment T (4 x 4, None = identity) of src onto tgt (n x 3) is, on the GPU
+    (clipper_hip_evaluate_registration): (fitness, inlier_rmse, count) over all source points, with
+    return_correspondences also each source point's target index (-1: no target point within max_distance)."""
+    from . import _abi as abi
+    with _knn_search(search):
+        return abi.evaluate_registration(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T=T,
+                                         max_distance=max_distance, device=device,
+                                         return_correspondences=return_correspondences)
+
+
 def generate_synthetic_correspondences(n0: int, n1: int, Agood: np.ndarray, m: int, rho: float,
                                        rng: np.random.Generator):
     """bm_utils.cpp:277-341: m putative associations with outlier ratio rho — round(m (1 - rho))

@@ -5,14 +5,17 @@
  *        putative associations, precision / recall — plus the closed-form rigid transform that
  *        consumes the selected associations (examples/python/ex4_bunny.ipynb), the feature
  *        matcher that produces the putative ones, and the stage in front of it: raw cloud ->
- *        normals -> FPFH descriptors. Thin C++ wrappers over the C ABI (include/clipper_hip.h);
- *        match_descriptors, estimate_normals and compute_fpfh work on the device.
+ *        normals -> FPFH descriptors, and the step behind it: ICP over the whole clouds (icp,
+ *        evaluate_registration). Thin C++ wrappers over the C ABI (include/clipper_hip.h);
+ *        match_descriptors, estimate_normals, compute_fpfh, icp and evaluate_registration work on the device.
  */
 #pragma once
 
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../clipper_hip.h"
 #include <cstdio>
@@ -150,6 +153,85 @@ inline invariants::Data compute_fpfh(const invariants::Data& P, const Neighborho
   if (clipper_hip_fpfh_from_points(device, P.data(), P.cols(), &hn, viewpoint, &hf, F.data(), nullptr))
     throw std::invalid_argument(clipper_hip_last_error());
   return F;
+}
+
+/// The two metrics of icp
+enum class IcpMethod { PointToPoint = 0, PointToPlane = 1 };
+/// How an icp ended (clipper_icp_info_t.status)
+enum class IcpStatus { Converged = 0, MaxIterations = 1, TooFew = 2, Degenerate = 3 };
+
+/// clipper_icp_params_t with the defaults of the facades; max_distance has none
+struct IcpParams {
+  IcpMethod method = IcpMethod::PointToPoint;
+  double max_distance = 0.0;  ///< positive and finite: a correspondence beyond it is no inlier
+  int max_iterations = 30;    ///< 0..1000; 0 = evaluate only
+  double rel_fitness = 1e-6;  ///< stop when fitness and rmse both change by less than these
+  double rel_rmse = 1e-6;
+};
+
+/// What icp returns: the refined transform (column-major 4 x 4), how it ended, how good it is, and the rows
+/// (count, fitness, rmse) of every evaluated T
+struct IcpResult {
+  double T[16];
+  IcpStatus status;
+  int iterations;
+  int64_t count;
+  double fitness, inlier_rmse;
+  KnnSearch route;
+  int64_t candidates;
+  double device_ms;
+  std::vector<std::array<double, 3>> history;
+};
+
+/// Local refinement of a registration on the device (clipper_hip_icp): ICP of the cloud src onto tgt (3 x n) from the
+/// alignment T_init (column-major 4 x 4; nullptr = identity), e.g. estimate_rigid_transform's. PointToPlane needs the
+/// target's unit normals (3 x n_tgt, e.g. estimate_normals(tgt)); pass an empty matrix otherwise. The result is the
+/// same on every search route and from run to run.
+inline IcpResult icp(const invariants::Data& src, const invariants::Data& tgt, const IcpParams& params,
+                     const double* T_init = nullptr, const invariants::Data& normals = invariants::Data(), int device = 0) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const bool has_normals = normals.cols() > 0;
+  if (has_normals && (normals.rows() != 3 || normals.cols() != tgt.cols()))
+    throw std::invalid_argument("normals must be 3 x n, one per target point");
+  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
+                                 params.rel_fitness, params.rel_rmse};
+  IcpResult r{};
+  clipper_icp_info_t info{};
+  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
+  if (clipper_hip_icp(device, src.data(), src.cols(), tgt.data(), has_normals ? normals.data() : nullptr, tgt.cols(), T_init,
+                      &prm, r.T, &info, hist.data()))
+    throw std::invalid_argument(clipper_hip_last_error());
+  r.status = static_cast<IcpStatus>(info.status);
+  r.iterations = info.iterations;
+  r.count = info.count;
+  r.fitness = info.fitness;
+  r.inlier_rmse = info.inlier_rmse;
+  r.route = static_cast<KnnSearch>(info.route);
+  r.candidates = info.candidates;
+  r.device_ms = info.device_ms;
+  for (int k = 0; k <= info.iterations; ++k) r.history.push_back({hist[3 * k], hist[3 * k + 1], hist[3 * k + 2]});
+  return r;
+}
+
+/// fitness, inlier rmse and inlier count of an alignment (clipper_hip_evaluate_registration)
+struct RegistrationQuality {
+  double fitness, inlier_rmse;
+  int64_t count;
+};
+
+/// How good the alignment T (column-major 4 x 4; nullptr = identity) of src onto tgt (3 x n) is, over all source points.
+/// correspondences (may be nullptr): per source point the index of its nearest target point, -1 beyond max_distance.
+inline RegistrationQuality evaluate_registration(const invariants::Data& src, const invariants::Data& tgt, const double* T,
+                                                 double max_distance, std::vector<int32_t>* correspondences = nullptr,
+                                                 int device = 0) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  RegistrationQuality q{};
+  if (correspondences) correspondences->assign(static_cast<size_t>(src.cols() > 0 ? src.cols() : 1), -1);
+  if (clipper_hip_evaluate_registration(device, src.data(), src.cols(), tgt.data(), tgt.cols(), T, max_distance, &q.fitness,
+                                        &q.inlier_rmse, &q.count, correspondences ? correspondences->data() : nullptr))
+    throw std::invalid_argument(clipper_hip_last_error());
+  if (correspondences) correspondences->resize(static_cast<size_t>(src.cols()));
+  return q;
 }
 
 }  // namespace registration

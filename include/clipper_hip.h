@@ -546,6 +546,57 @@ int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const c
                                  const double* viewpoint, const clipper_neighborhood_t* feature_nb,
                                  double* F_out, double* N_out);
 
+/* ICP: the LOCAL REFINEMENT of a registration on the device, and how good an alignment is. The source cloud P_src
+ * (3 x n_src column-major as `clipper::Data`) is moved by T (column-major 4 x 4) onto the target P_tgt (3 x n_tgt);
+ * the correspondence of a moved point q is the K = 1 entry of the nearest-neighbour search above in the target (fp64,
+ * ties by (distance, index); the route of clipper_hip_knn_set_search, with the target's grid built once per call and
+ * kept over the iterations); it is an inlier iff sqd <= max_distance * max_distance. fitness = inliers / n_src,
+ * inlier_rmse = sqrt(sum sqd / inliers). Every sum has one fixed order of addition and nothing is fused, so the results
+ * are functions of the inputs alone: the same on both search routes and from run to run (the rules in full:
+ * clipper_amd/csrc/icp_rules.hpp). Stand-alone: needs no context. */
+enum { CLIPPER_ICP_POINT_TO_POINT = 0,   /* Arun / Horn on the inliers                                            */
+       CLIPPER_ICP_POINT_TO_PLANE = 1 }; /* linearised (q - b) . n over the target's normals, Cayley rotation      */
+enum { CLIPPER_ICP_CONVERGED      = 0,   /* fitness and rmse both changed by less than their bounds               */
+       CLIPPER_ICP_MAX_ITERATIONS = 1,
+       CLIPPER_ICP_TOO_FEW        = 2,   /* fewer than 3 (point-to-point) or 6 (point-to-plane) inliers           */
+       CLIPPER_ICP_DEGENERATE     = 3 }; /* the inliers do not determine the step (rank-deficient system)         */
+typedef struct clipper_icp_params_t {
+  int32_t method;          /* CLIPPER_ICP_POINT_TO_POINT | CLIPPER_ICP_POINT_TO_PLANE */
+  int32_t max_iterations;  /* 0..1000 (facades default to 30); 0 = evaluate only */
+  double  max_distance;    /* positive and finite */
+  double  rel_fitness;     /* >= 0 (facades default to 1e-6) */
+  double  rel_rmse;        /* >= 0 (facades default to 1e-6) */
+} clipper_icp_params_t;
+typedef struct clipper_icp_info_t {
+  int32_t iterations;   /* updates of T behind the last history row */
+  int32_t status;       /* CLIPPER_ICP_* */
+  int64_t count;        /* inliers, fitness and inlier_rmse under T_out */
+  double  fitness;
+  double  inlier_rmse;
+  int32_t route;        /* CLIPPER_HIP_KNN_BRUTE or CLIPPER_HIP_KNN_GRID: the search route taken */
+  int32_t dim[3];       /* cells per axis of the target's grid (0 0 0 for brute force) */
+  int64_t candidates;   /* points visited by the grid's queries, summed over all iterations (0 for brute force) */
+  double  device_ms;    /* between two events around the loop */
+} clipper_icp_info_t;
+
+/* N_tgt (3 x n_tgt unit normals; squared length within [0.99, 1.01]): NULL unless point-to-plane. T_init: NULL =
+ * identity; finite, bottom row 0 0 0 1. Iteration k evaluates (count, fitness, rmse) under the current T, writes row k of
+ * `history` (max_iterations + 1 rows of 3 doubles, may be NULL; rows never reached are 0) and stops CONVERGED when
+ * k >= 1 and |fitness_k - fitness_(k-1)| < rel_fitness and |rmse_k - rmse_(k-1)| < rel_rmse, else TOO_FEW, else
+ * MAX_ITERATIONS at k == max_iterations, else DEGENERATE when the step is undetermined; otherwise T <- dT T. T_out is
+ * the T the last row was evaluated under. Every status returns 0 with a finite T_out; <0: error (bad arguments are
+ * refused before any device work). info may be NULL. */
+int clipper_hip_icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
+                    int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
+                    clipper_icp_info_t* info, double* history);
+
+/* fitness, inlier_rmse and count of the alignment T (NULL = identity), as iteration 0 of clipper_hip_icp computes them
+ * (any of the three may be NULL). corr_out (n_src, may be NULL): the target index of each source point's
+ * correspondence, -1 where it is no inlier. */
+int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n_src, const double* P_tgt, int64_t n_tgt,
+                                      const double* T, double max_distance, double* fitness, double* inlier_rmse,
+                                      int64_t* count, int32_t* corr_out);
+
 /* Line-search window: how many consecutive step sizes alpha, alpha*beta, ... of the
  * backtracking line search (clipper.cpp:234-251) one pass over M evaluates at once. The
  * trial sequence, the accepted trial and the result are those of the reference for every
