@@ -38,21 +38,16 @@ def _run(cmd: list[str]):
     subprocess.check_call(cmd)
 
 
+def hip_sources() -> list[str]:
+    """every source the one translation unit can include, taken from the tree: a new header is never left out"""
+    return [os.path.join(dp, f) for top in (CSRC, os.path.join(ROOT, "include")) for dp, _, fs in os.walk(top)
+            for f in fs if f.endswith((".hip", ".h", ".hpp"))]
+
+
 def build_hip(force: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, "clipper_hip.hip"), os.path.join(CSRC, "kernels.hip.h"),
-            *[os.path.join(CSRC, f) for f in ("k_solver.hip.h", "k_gemv.hip.h", "k_csc.hip.h", "k_slices.hip.h", "k_resident.hip.h", "host_resident.hpp", "k_rv_resident.hip.h", "host_rv_resident.hpp",
-                                              "k_affinity.hip.h", "k_matrix.hip.h", "k_rowview.hip.h", "k_subproblem.hip.h", "k_knn.hip.h", "k_match.hip.h", "k_maxclique.hip.h", "k_sdp.hip.h", "k_sdp_wide.hip.h", "k_features.hip.h", "k_knn_grid.hip.h", "k_icp.hip.h")],
-            *[os.path.join(CSRC, f) for f in ("host_state.hpp", "host_custom_invariant.hpp", "k_custom_invariant_src.h", "host_solver.hpp", "host_matrix.hpp", "host_plan.hpp", "host_batch.hpp", "host_rowview.hpp", "host_subproblem.hpp", "host_registration.hpp", "host_maxclique.hpp", "host_mcplan.hpp", "host_sdp.hpp", "host_sdpbatch.hpp", "host_sdpplan.hpp", "host_sdpwide.hpp", "host_sdpwide_plan.hpp", "sdp_circle.hpp", "sdp_rules.hpp",
-                                              "host_solve.hpp", "host_batchsolve.hpp", "host_batchpack.hpp", "host_csc_input.hpp", "host_matrix_io.hpp", "host_match.hpp", "host_match_select.hpp",
-                                              "host_features.hpp", "host_features_check.hpp", "features_rules.hpp",
-                                              "host_knn_grid.hpp", "host_knn_grid_plan.hpp", "knn_grid_rules.hpp",
-                                              "host_icp.hpp", "host_icp_check.hpp", "icp_rules.hpp")],
-            os.path.join(CSRC, "dsd_host.h"),
-            os.path.join(ROOT, "include", "clipper_hip.h"),
-            os.path.join(ROOT, "include", "clipper_abi.h")]
-    if force or not _newer(HIP_LIB, srcs):
-        _run([HIPCC, *HIP_FLAGS, "-o", HIP_LIB, srcs[0], "-ldl"])
+    if force or not _newer(HIP_LIB, hip_sources()):
+        _run([HIPCC, *HIP_FLAGS, "-o", HIP_LIB, os.path.join(CSRC, "clipper_hip.hip"), "-ldl"])
     return HIP_LIB
 
 

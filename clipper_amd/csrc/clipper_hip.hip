@@ -1,9 +1,10 @@
 // clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_state.hpp (context, shards,
-// RCCL binding), host_solver.hpp (planning, dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver),
-// host_solve.hpp (the solve of one context), host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp
-// (the fills, matrix set / get, mat-vecs, nearest neighbours; included last: it holds its kernels' place in the code
-// object), host_match.hpp (putative associations from feature descriptors; behind it), host_knn_grid.hpp (the seam of the
-// nearest-neighbour search and its grid route), host_csc_input.hpp (the sparse input's
+// RCCL binding), host_call.hpp (the frame of a stand-alone call: device, temporaries, copies), host_solver.hpp (planning,
+// dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver), host_solve.hpp (the solve of one context),
+// host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp (the fills, matrix set / get,
+// mat-vecs; the last driver of a context: it holds its kernels' place in the code object), behind it the stand-alone
+// searches: host_knn.hpp (nearest neighbours: both routes and their seam), host_match.hpp (putative associations from
+// feature descriptors), host_features.hpp, host_icp.hpp; host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
@@ -44,6 +45,7 @@
 using namespace clipper_hip;
 
 #include "host_state.hpp"
+#include "host_call.hpp"
 #include "host_solver.hpp"
 #include "host_matrix.hpp"
 #include "host_rowview.hpp"
@@ -59,8 +61,8 @@ using namespace clipper_hip;
 #include "host_batchsolve.hpp"
 #include "host_maxclique.hpp"
 #include "host_matrix_io.hpp"
+#include "host_knn.hpp"
 #include "host_match.hpp"
-#include "host_knn_grid.hpp"
 #include "host_features.hpp"
 #include "host_icp.hpp"
 
@@ -557,17 +559,14 @@ int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int6
 int clipper_hip_batch_create(int device, int storage, clipper_hip_batch_t** out) try {
   if (!out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range (%d visible)", device, ndev);
+  if (int rc = use_device(device)) return rc;
   if (storage != CLIPPER_HIP_STORE_F32 && storage != CLIPPER_HIP_STORE_F64 && storage != CLIPPER_HIP_STORE_F32_CSC &&
       storage != CLIPPER_HIP_STORE_F64_CSC)
     return fail(CLIPPER_HIP_E_INVALID, "storage must be CLIPPER_HIP_STORE_F32, _F64, _F32_CSC or _F64_CSC");
   clipper_hip_batch_t* b = new clipper_hip_batch_t();
   b->device = device;
   b->storage = storage;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
     delete b;
     return fail(CLIPPER_HIP_E_HIP, "cannot create a stream on device %d", device);
   }

@@ -4,8 +4,8 @@
 // lists are nested: the shorter neighbourhood is a prefix of the longer list), the normals stage and the feature stage
 // are queued on one stream with no host wait in between (the normals stay on the device), and what the caller asked
 // for comes back behind the one wait of the call (the grid route of the search waits twice more inside it: host_knn_grid.hpp).
-// Stand-alone: needs no context. The checks are
-// host_features_check.hpp's. Part of clipper_hip.hip (one translation unit; included there after host_match.hpp).
+// Stand-alone: needs no context. The checks are host_features_check.hpp's, the frame host_call.hpp's. Part of
+// clipper_hip.hip (one translation unit; included there after host_match.hpp).
 #pragma once
 
 #include "host_features_check.hpp"
@@ -24,62 +24,49 @@ void feat_spfh_run(const double* dP, const double* dN, int64_t n, const int32_t*
 int features_run(int device, const double* P, const double* N_in, int64_t n, const clipper_features::Neighborhood* nnb,
                  const double* view, const clipper_features::Neighborhood* fnb, double* N_out, int32_t* ncnt_out,
                  double* F_out, double* spfh_out, int32_t* fcnt_out) {
-  namespace cf = clipper_features;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
 
-  const int K = cf::list_k(std::max(nnb ? nnb->knn : 0, fnb ? fnb->knn : 0));
+  const int K = clipper_features::list_k(std::max(nnb ? nnb->knn : 0, fnb ? fnb->knn : 0));
   const size_t n3 = static_cast<size_t>(n) * 3, nf = fnb ? static_cast<size_t>(n) * FEAT_DIM : 0;
-  const size_t no = static_cast<size_t>(n) * K;
+  const size_t no = static_cast<size_t>(n) * K, nn = static_cast<size_t>(n);
   double *dP = nullptr, *dN = nullptr, *dV = nullptr, *od = nullptr, *dS = nullptr, *dF = nullptr;
   int32_t *oi = nullptr, *dcn = nullptr, *dcf = nullptr;
   DevTemps tmp;
-  if (tmp.alloc(device, dP, n3 * sizeof(double)) || tmp.alloc(device, dN, n3 * sizeof(double)) ||
-      tmp.alloc(device, dV, 3 * sizeof(double)) || tmp.alloc(device, od, no * sizeof(double)) ||
-      tmp.alloc(device, oi, no * sizeof(int32_t)) || tmp.alloc(device, dS, nf * sizeof(double)) ||
-      tmp.alloc(device, dF, nf * sizeof(double)) || tmp.alloc(device, dcn, static_cast<size_t>(n) * sizeof(int32_t)) ||
-      tmp.alloc(device, dcf, static_cast<size_t>(n) * sizeof(int32_t))) {
-    tmp.release();
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  }
+  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dN, n3 * sizeof(double), dV, 3 * sizeof(double),
+                         od, no * sizeof(double), oi, no * sizeof(int32_t), dS, nf * sizeof(double), dF, nf * sizeof(double),
+                         dcn, nn * sizeof(int32_t), dcf, nn * sizeof(int32_t)))
+    return rc;
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
-  auto up = [&](double* dst, const double* src, size_t count) {
-    return hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-  };
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
-  bool ok = up(dP, P, n3) && (nnb || up(dN, N_in, n3)) && (!(nnb && view) || up(dV, view, 3));
-  if (ok) {
-    // the cloud's nearest-neighbour lists in itself, K in {4, 8, 16, 32}, by the route of the process-wide mode
-    if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
-    if (nnb) {
-      const int use_r = nnb->radius > 0.0;
-      hipLaunchKernelGGL(k_feat_normals<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
-                         nnb->knn, use_r, nnb->radius * nnb->radius, view ? dV : nullptr, dN, dcn);
-      ok = down(N_out, dN, n3 * sizeof(double)) && down(ncnt_out, dcn, static_cast<size_t>(n) * sizeof(int32_t));
-    }
-    if (ok && fnb) {
-      const int use_r = fnb->radius > 0.0;
-      const double r2 = fnb->radius * fnb->radius;
-      switch (cf::list_k(fnb->knn)) {
-        case 4: feat_spfh_run<4>(dP, dN, n, oi, od, K, fnb->knn, use_r, r2, dS, dcf, st); break;
-        case 8: feat_spfh_run<8>(dP, dN, n, oi, od, K, fnb->knn, use_r, r2, dS, dcf, st); break;
-        case 16: feat_spfh_run<16>(dP, dN, n, oi, od, K, fnb->knn, use_r, r2, dS, dcf, st); break;
-        default: feat_spfh_run<32>(dP, dN, n, oi, od, K, fnb->knn, use_r, r2, dS, dcf, st); break;
-      }
-      hipLaunchKernelGGL(k_feat_fpfh<>, dim3(static_cast<unsigned>(ceil_div(n, FEAT_FPFH_POINTS))), dim3(256), 0, st, dS, n,
-                         oi, od, K, fnb->knn, use_r, r2, dF);
-      ok = down(F_out, dF, nf * sizeof(double)) && down(spfh_out, dS, nf * sizeof(double)) &&
-           down(fcnt_out, dcf, static_cast<size_t>(n) * sizeof(int32_t));
-    }
-    ok = hipStreamSynchronize(st) == hipSuccess && ok && hipGetLastError() == hipSuccess;  // the one wait of the call
+  if (int rc = copy_up(dP, P, n3, st)) return rc;
+  if (!nnb)
+    if (int rc = copy_up(dN, N_in, n3, st)) return rc;
+  if (nnb && view)
+    if (int rc = copy_up(dV, view, 3, st)) return rc;
+  // the cloud's nearest-neighbour lists in itself, K in {4, 8, 16, 32}, by the route of the process-wide mode
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
+  if (nnb) {
+    const int use_r = nnb->radius > 0.0;
+    hipLaunchKernelGGL(k_feat_normals<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
+                       nnb->knn, use_r, nnb->radius * nnb->radius, view ? dV : nullptr, dN, dcn);
+    if (int rc = copy_down(N_out, dN, n3, st)) return rc;
+    if (int rc = copy_down(ncnt_out, dcn, nn, st)) return rc;
   }
-  tmp.release();
-  if (!ok) return fail(CLIPPER_HIP_E_HIP, "point-cloud features failed: %s", hipGetErrorString(hipGetLastError()));
+  if (fnb) {
+    const int use_r = fnb->radius > 0.0;
+    const double r2 = fnb->radius * fnb->radius;
+    const int slots = clipper_features::list_k(fnb->knn);
+    if (!dispatch_k<4, 8, 16, 32>(slots, [&](auto k) {
+          feat_spfh_run<decltype(k)::value>(dP, dN, n, oi, od, K, fnb->knn, use_r, r2, dS, dcf, st);
+        }))
+      return fail(CLIPPER_HIP_E_INTERNAL, "no SPFH kernel for %d slots", slots);
+    hipLaunchKernelGGL(k_feat_fpfh<>, dim3(static_cast<unsigned>(ceil_div(n, FEAT_FPFH_POINTS))), dim3(256), 0, st, dS, n,
+                       oi, od, K, fnb->knn, use_r, r2, dF);
+    if (int rc = copy_down(F_out, dF, nf, st)) return rc;
+    if (int rc = copy_down(spfh_out, dS, nf, st)) return rc;
+    if (int rc = copy_down(fcnt_out, dcf, nn, st)) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st));  // the one wait of the call
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

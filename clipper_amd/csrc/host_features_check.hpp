@@ -1,7 +1,8 @@
 // host_features_check.hpp — normals and FPFH, the part that needs no device: the argument checks of
 // clipper_hip_estimate_normals, clipper_hip_compute_fpfh and clipper_hip_fpfh_from_points, and which list length serves
-// a neighbourhood. Pure host code (no HIP): tests/cpp/test_features_rules.cpp compiles it with g++ alone. A refusal
-// comes back as its message (empty: accepted); the caller hands it to fail(). Every check runs before any device work.
+// a neighbourhood (host_knn_k.hpp's rule between 4 and 32). Pure host code (no HIP):
+// tests/cpp/test_features_rules.cpp compiles it with g++ alone. A refusal comes back as its message (empty: accepted);
+// the caller hands it to fail(). Every check runs before any device work.
 #pragma once
 
 #include <cmath>
@@ -9,6 +10,7 @@
 #include <string>
 
 #include "features_rules.hpp"
+#include "host_knn_k.hpp"
 #include "host_match_select.hpp"
 
 namespace clipper_features {
@@ -65,7 +67,7 @@ inline std::string check_normals(const double* N, int64_t n) {
   return {};
 }
 
-// the instantiation of the search that serves knn neighbours: nearest-K lists are nested, a longer one holds the shorter
-inline int list_k(int knn) { return knn <= 4 ? 4 : (knn <= 8 ? 8 : (knn <= 16 ? 16 : 32)); }
+// the instantiation of the search that serves knn neighbours: the shared rule between the features' 4 and 32
+inline int list_k(int knn) { return clipper_hip::knn_list_k(knn, 4, 32); }
 
 }  // namespace clipper_features

@@ -4,7 +4,7 @@
 // T_init, and keeps that order for all iterations (a locality hint, never a correctness input: the lists go to the
 // rows of the original indices). T, the sums, the history and the candidate count stay on the device during the loop;
 // the host reads the 64-byte status record once per iteration through pinned memory to decide whether to queue the
-// next round: the only host wait of an iteration. The brute-force route runs k_knn's two kernels per iteration.
+// next round: the only host wait of an iteration. The brute-force route queries one kept scratch (host_knn.hpp).
 // Stand-alone: needs no context. The checks are host_icp_check.hpp's, the arithmetic icp_rules.hpp's. Part of
 // clipper_hip.hip (one translation unit; included there last, after host_features.hpp).
 #pragma once
@@ -37,11 +37,7 @@ void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns
 // Every argument has been checked. T0: column-major 4 x 4. history: (max_iterations + 1) x 3 or null; corr_out: ns or null.
 int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, int64_t nt_, const double* T0,
             const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info, double* history, int32_t* corr_out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
 
   const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
   const bool plane = prm.method == ICP_POINT_TO_PLANE;
@@ -50,26 +46,25 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
   const size_t nrows = static_cast<size_t>(prm.max_iterations) + 1;
   const int route = knn_route(g_knn_search.load(), 3, ns, nt);
-  const MatchGeom geom = match_geom(ns, nt);  // (the brute-force route's chunks: k_knn's own rule)
-  const size_t np = route == CLIPPER_HIP_KNN_BRUTE ? static_cast<size_t>(geom.S) * ns : 0;
 
   double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr,
-         *dT = nullptr, *dhist = nullptr, *pd = nullptr;
-  int32_t *oi = nullptr, *pi = nullptr, *perm = nullptr, *visited = nullptr;
+         *dT = nullptr, *dhist = nullptr;
+  int32_t *oi = nullptr, *perm = nullptr, *visited = nullptr;
   unsigned long long* dsum = nullptr;
   IcpRecord* drec = nullptr;
   DevTemps tmp;
   IcpHostState hs;
-  if (tmp.alloc(device, dPs, s3 * sizeof(double)) || tmp.alloc(device, dPt, t3 * sizeof(double)) ||
-      tmp.alloc(device, dNt, (plane ? t3 : 0) * sizeof(double)) || tmp.alloc(device, dq, s3 * sizeof(double)) ||
-      tmp.alloc(device, od, static_cast<size_t>(ns) * sizeof(double)) || tmp.alloc(device, oi, static_cast<size_t>(ns) * sizeof(int32_t)) ||
-      tmp.alloc(device, dpart, static_cast<size_t>(nb) * terms * sizeof(double)) ||
-      tmp.alloc(device, dsums, static_cast<size_t>(ICP_PLANE_TERMS) * sizeof(double)) || tmp.alloc(device, dT, 16 * sizeof(double)) ||
-      tmp.alloc(device, dhist, nrows * 3 * sizeof(double)) || tmp.alloc(device, drec, sizeof(IcpRecord)) ||
-      tmp.alloc(device, pd, np * sizeof(double)) || tmp.alloc(device, pi, np * sizeof(int32_t)) ||
-      tmp.alloc(device, perm, static_cast<size_t>(ns) * sizeof(int32_t)) ||
-      tmp.alloc(device, visited, static_cast<size_t>(ns) * sizeof(int32_t)) || tmp.alloc(device, dsum, sizeof(unsigned long long)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  const size_t s1 = static_cast<size_t>(ns);
+  if (int rc = tmp.alloc(device, dPs, s3 * sizeof(double), dPt, t3 * sizeof(double), dNt, (plane ? t3 : 0) * sizeof(double),
+                         dq, s3 * sizeof(double), od, s1 * sizeof(double), oi, s1 * sizeof(int32_t),
+                         dpart, static_cast<size_t>(nb) * terms * sizeof(double), dsums, ICP_PLANE_TERMS * sizeof(double),
+                         dT, 16 * sizeof(double), dhist, nrows * 3 * sizeof(double), drec, sizeof(IcpRecord)))
+    return rc;
+  KnnBruteScratch bs;  // (the brute-force route's partial lists: in their place among the call's buffers)
+  if (route == CLIPPER_HIP_KNN_BRUTE)
+    if (int rc = knn_brute_alloc(device, 1, ns, nt, bs, tmp)) return rc;
+  if (int rc = tmp.alloc(device, perm, s1 * sizeof(int32_t), visited, s1 * sizeof(int32_t), dsum, sizeof(unsigned long long)))
+    return rc;
   HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hs.rec), sizeof(IcpRecord)));
   HIPCHK(hipEventCreate(&hs.a));
   HIPCHK(hipEventCreate(&hs.b));
@@ -121,10 +116,10 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
         knn_grid_bin_queries(ix, dq, ns, gq, st);
         if (!rebin) hipLaunchKernelGGL(k_icp_order<>, sb, dim3(256), 0, st, Q, ns, perm);
       }
-      knn_grid_query_lists(ix, 1, Q, ns, od, oi, visited, st);
+      if (int rc = knn_grid_query_lists(ix, 1, Q, ns, od, oi, visited, st)) return rc;
       knn_grid_sum_visited(visited, ns, dsum, st);
-    } else {
-      knn_run<1, 3>(dq, ns, dPt, nt, geom.S, geom.chunk, pd, pi, od, oi, st);
+    } else if (int rc = knn_brute_query(1, 3, dq, ns, dPt, nt, bs, od, oi, st)) {
+      return rc;
     }
     if (plane)
       icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);

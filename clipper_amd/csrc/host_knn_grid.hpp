@@ -1,14 +1,12 @@
-// host_knn_grid.hpp — the one seam through which clipper_hip_knn, clipper_hip_distance_based_correspondences and the
-// three feature entry points reach the nearest-neighbour search (knn_lists), and the driver of its grid route
-// ("The grid route of the search"). The seam reads the process-wide mode once, picks the route,
-// allocates that route's temporaries (the brute-force route's partial lists, or the grid's tables) and queues the
-// kernels on the caller's stream; the lists are on the device when it returns. The grid route is a build
+// host_knn_grid.hpp — the grid route of the nearest-neighbour search ("The grid route of the
+// search"), the process-wide mode that picks the route and the statistics of the last search. The route is a build
 // (knn_grid_build: a KnnGridIndex, kept by callers that search one cloud many times) followed by a query
-// (knn_grid_query_lists). Part of clipper_hip.hip (one
-// translation unit; included there after host_match.hpp, whose match_geom it shares, and before host_features.hpp).
+// (knn_grid_query_lists); its tables are the caller's DevTemps'. Part of clipper_hip.hip (one translation unit;
+// included by host_knn.hpp, which holds the brute-force route and the seam over the two).
 #pragma once
 
 #include "host_knn_grid_plan.hpp"
+#include "host_knn_k.hpp"
 
 namespace {
 
@@ -93,8 +91,7 @@ struct KnnGridIndex {
 int knn_grid_bounds(int device, const double* dP, int32_t n, double (&lo)[3], double (&hi)[3], hipStream_t st, DevTemps& tmp) {
   const int nb = static_cast<int>(std::min<int64_t>(KG_BOUNDS_BLOCKS, ceil_div(n, 256)));
   double* dpart = nullptr;
-  if (tmp.alloc(device, dpart, static_cast<size_t>(nb) * 6 * sizeof(double)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  if (int rc = tmp.alloc(device, dpart, static_cast<size_t>(nb) * 6 * sizeof(double))) return rc;
   hipLaunchKernelGGL(k_kg_bounds<>, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, dP, static_cast<int64_t>(n), dpart);
   std::vector<double> part(static_cast<size_t>(nb) * 6);
   HIPCHK(hipMemcpyAsync(part.data(), dpart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -121,14 +118,11 @@ int knn_grid_build(int device, const double* dP1, int32_t n1, KnnGridIndex& ix, 
   const size_t ne = static_cast<size_t>(ix.ncells) + 1;
   int32_t *cell = nullptr, *counts = nullptr, *cursor = nullptr;
   unsigned long long *kmin = nullptr, *kmax = nullptr;
-  if (tmp.alloc(device, ix.S, static_cast<size_t>(n1) * sizeof(KgPoint)) ||
-      tmp.alloc(device, cell, static_cast<size_t>(n1) * sizeof(int32_t)) || tmp.alloc(device, counts, ne * sizeof(int32_t)) ||
-      tmp.alloc(device, ix.start, ne * sizeof(int32_t)) || tmp.alloc(device, cursor, ne * sizeof(int32_t)) ||
-      tmp.alloc(device, kmin, static_cast<size_t>(nslab) * sizeof(unsigned long long)) ||
-      tmp.alloc(device, kmax, static_cast<size_t>(nslab) * sizeof(unsigned long long)) ||
-      tmp.alloc(device, ix.smin, static_cast<size_t>(nslab) * sizeof(double)) ||
-      tmp.alloc(device, ix.pmax, static_cast<size_t>(nslab) * sizeof(double)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  const size_t np = static_cast<size_t>(n1), ns = static_cast<size_t>(nslab);
+  if (int rc = tmp.alloc(device, ix.S, np * sizeof(KgPoint), cell, np * sizeof(int32_t), counts, ne * sizeof(int32_t),
+                         ix.start, ne * sizeof(int32_t), cursor, ne * sizeof(int32_t), kmin, ns * sizeof(unsigned long long),
+                         kmax, ns * sizeof(unsigned long long), ix.smin, ns * sizeof(double), ix.pmax, ns * sizeof(double)))
+    return rc;
   hipLaunchKernelGGL(k_kg_init<>, dim3(static_cast<unsigned>(std::min<int64_t>(1024, ceil_div(static_cast<int64_t>(ne), 256)))),
                      dim3(256), 0, st, counts, static_cast<int64_t>(ne), kmin, kmax, static_cast<int64_t>(nslab), nullptr);
   knn_grid_bin(dP1, n1, ix.g, ix.ncells, cell, counts, ix.start, cursor, kmin, kmax, ix.S, st);
@@ -145,11 +139,8 @@ struct KnnGridQueries {
 
 int knn_grid_alloc_queries(int device, const KnnGridIndex& ix, int32_t n0, KnnGridQueries& q, DevTemps& tmp) {
   const size_t ne = static_cast<size_t>(ix.ncells) + 1;
-  if (tmp.alloc(device, q.Q, static_cast<size_t>(n0) * sizeof(KgPoint)) ||
-      tmp.alloc(device, q.cell, static_cast<size_t>(n0) * sizeof(int32_t)) || tmp.alloc(device, q.counts, ne * sizeof(int32_t)) ||
-      tmp.alloc(device, q.cursor, ne * sizeof(int32_t)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  return 0;
+  return tmp.alloc(device, q.Q, static_cast<size_t>(n0) * sizeof(KgPoint), q.cell, static_cast<size_t>(n0) * sizeof(int32_t),
+                   q.counts, ne * sizeof(int32_t), q.cursor, ne * sizeof(int32_t));
 }
 
 void knn_grid_bin_queries(const KnnGridIndex& ix, const double* dP0, int32_t n0, const KnnGridQueries& q, hipStream_t st) {
@@ -161,16 +152,13 @@ void knn_grid_bin_queries(const KnnGridIndex& ix, const double* dP0, int32_t n0,
 
 // The query against an index: Q in the cell order of its grid (Q == ix.S for a cloud searched in itself), the lists to
 // od / oi (n0 x K, rows by original index), the candidates each query visited to visited (n0). No host wait.
-void knn_grid_query_lists(const KnnGridIndex& ix, int K, const KgPoint* Q, int32_t n0, double* od, int32_t* oi, int32_t* visited,
-                          hipStream_t st) {
-  switch (K) {
-    case 1: knn_grid_launch<1>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-    case 2: knn_grid_launch<2>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-    case 4: knn_grid_launch<4>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-    case 8: knn_grid_launch<8>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-    case 16: knn_grid_launch<16>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-    default: knn_grid_launch<32>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st); break;
-  }
+int knn_grid_query_lists(const KnnGridIndex& ix, int K, const KgPoint* Q, int32_t n0, double* od, int32_t* oi, int32_t* visited,
+                         hipStream_t st) {
+  if (!dispatch_k<1, 2, 4, 8, 16, 32>(K, [&](auto k) {
+        knn_grid_launch<decltype(k)::value>(Q, n0, ix.S, ix.n1, ix.start, ix.g, ix.smin, ix.pmax, od, oi, visited, st);
+      }))
+    return fail(CLIPPER_HIP_E_INTERNAL, "no grid search kernel for K = %d", K);
+  return 0;
 }
 
 // visited (n0) added to *dsum on the device (integer adds: the order does not matter)
@@ -181,7 +169,7 @@ void knn_grid_sum_visited(const int32_t* visited, int32_t n0, unsigned long long
 
 // The grid route: the build over dP1, dP0 binned by the same grid (skipped when the cloud is searched in itself), the
 // query, the statistics. One host wait in the build (the bounding box comes back for the plan) and one at the end
-// (the candidate count). Temporaries are tmp's: released by the caller on every path.
+// (the candidate count). Temporaries are tmp's.
 int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const double* dP1, int64_t n1_, double* od, int32_t* oi,
                    hipStream_t st, DevTemps& tmp) {
   const int32_t n0 = static_cast<int32_t>(n0_), n1 = static_cast<int32_t>(n1_);
@@ -197,10 +185,9 @@ int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const doub
   }
   int32_t* visited = nullptr;
   unsigned long long* dsum = nullptr;
-  if (tmp.alloc(device, visited, static_cast<size_t>(n0) * sizeof(int32_t)) || tmp.alloc(device, dsum, sizeof(unsigned long long)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
+  if (int rc = tmp.alloc(device, visited, static_cast<size_t>(n0) * sizeof(int32_t), dsum, sizeof(unsigned long long))) return rc;
   HIPCHK(hipMemsetAsync(dsum, 0, sizeof(unsigned long long), st));
-  knn_grid_query_lists(ix, K, Q, n0, od, oi, visited, st);
+  if (int rc = knn_grid_query_lists(ix, K, Q, n0, od, oi, visited, st)) return rc;
   knn_grid_sum_visited(visited, n0, dsum, st);
   unsigned long long sum = 0;
   HIPCHK(hipMemcpyAsync(&sum, dsum, sizeof(sum), hipMemcpyDeviceToHost, st));
@@ -210,42 +197,6 @@ int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const doub
   for (int a = 0; a < 3; ++a) g_knn_stats.dim[a] = ix.g.dim[a];
   g_knn_stats.candidates = static_cast<int64_t>(sum);
   return 0;
-}
-
-// the brute-force route: k_knn's two kernels over S chunks of the searched cloud (match_geom: k_knn's own rule)
-int knn_brute_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
-                    int32_t* oi, hipStream_t st, DevTemps& tmp) {
-  const MatchGeom g = match_geom(n0, n1);
-  const size_t np = static_cast<size_t>(g.S) * n0 * K;
-  double* pd = nullptr;
-  int32_t* pi = nullptr;
-  if (tmp.alloc(device, pd, np * sizeof(double)) || tmp.alloc(device, pi, np * sizeof(int32_t)))
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  switch (K) {
-    case 1: knn_launch<1>(d, dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 2: knn_launch<2>(d, dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 4: knn_launch<4>(d, dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 8: knn_launch<8>(d, dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st); break;
-    case 16: knn_launch<16>(d, dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st); break;
-    default:
-      if (d != 3) return fail(CLIPPER_HIP_E_INTERNAL, "no search kernel for K = %d, d = %d", K, d);
-      knn_run<32, 3>(dP0, n0, dP1, n1, g.S, g.chunk, pd, pi, od, oi, st);
-      break;
-  }
-  return 0;
-}
-
-// The seam. dP0: n0 x d, dP1: n1 x d on the device; od / oi: n0 x K, the caller's; K in {1, 2, 4, 8, 16, 32}. The
-// route's temporaries join tmp. Returns 0 with the kernels queued on st (the grid route has waited for them), or <0.
-int knn_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
-              int32_t* oi, hipStream_t st, DevTemps& tmp) {
-  const int route = knn_route(g_knn_search.load(), d, n0, n1);
-  g_knn_stats = clipper_hip_knn_stats_t{route, {0, 0, 0}, n0, 0, CLIPPER_HIP_KNN_AUTO_MIN_N, 0.0};
-  const bool timed = knn_events_begin(device, st);
-  const int rc = route == CLIPPER_HIP_KNN_GRID ? knn_grid_lists(device, K, dP0, n0, dP1, n1, od, oi, st, tmp)
-                                               : knn_brute_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp);
-  knn_events_end(timed && rc == 0, st);
-  return rc;
 }
 
 }  // namespace

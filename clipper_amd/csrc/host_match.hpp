@@ -3,29 +3,17 @@
 // of 8 coordinates; the forward search (F0 -> F1) and, for the mutual check, the backward search (F1 -> F0) are queued
 // on one stream with no host wait in between; the lists (n x K entries) come back and the filters of
 // host_match_select.hpp run on the host, as distance_based_correspondences does with its lists. Stand-alone: needs no
-// context. Part of clipper_hip.hip (one translation unit; included there after host_matrix_io.hpp, so that the search
-// kernels come last in the code object).
+// context. Part of clipper_hip.hip (one translation unit; included there after host_knn.hpp, whose chunk rule and
+// merge kernel it shares).
 #pragma once
 
 #include "host_match_select.hpp"
 
 namespace {
 
-// the chunks the candidate set of one search is split into: k_knn's rule (enough workgroups to fill the chip, whole tiles)
-struct MatchGeom {
-  int S;
-  int64_t chunk;
-};
-MatchGeom match_geom(int64_t nq, int64_t nc) {
-  const int64_t qblocks = ceil_div(nq, 256);
-  const int64_t tiles = ceil_div(nc, KNN_TILE);
-  const int S = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, ceil_div(512, qblocks))));
-  return {S, ceil_div(tiles, S) * KNN_TILE};
-}
-
 // one search: the partial lists of every chunk, then their merge. Q: nq x 8 G, C: nc x 8 G (padded rows)
 template <int K, int G>
-void match_run(const double* Q, int64_t nq, const double* C, int64_t nc, const MatchGeom& g, double* pd, int32_t* pi,
+void match_run(const double* Q, int64_t nq, const double* C, int64_t nc, const KnnGeom& g, double* pd, int32_t* pi,
                double* od, int32_t* oi, hipStream_t st) {
   const unsigned qb = static_cast<unsigned>(ceil_div(nq, 256));
   hipLaunchKernelGGL((k_match_partial<K, G>), dim3(qb, static_cast<unsigned>(g.S)), dim3(256), 0, st, Q, nq, C, nc,
@@ -39,29 +27,17 @@ inline int match_groups(int d) {
   return g <= 2 ? g : (g <= 4 ? 4 : (g == 5 ? 5 : 8));
 }
 
-template <int K>
-void match_launch(int G, const double* Q, int64_t nq, const double* C, int64_t nc, const MatchGeom& g, double* pd,
-                  int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
-  switch (G) {
-    case 1: match_run<K, 1>(Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    case 2: match_run<K, 2>(Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    case 4: match_run<K, 4>(Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    case 5: match_run<K, 5>(Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    default: match_run<K, 8>(Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-  }
+// one search at a run-time (K, G): 0, or CLIPPER_HIP_E_INTERNAL for a pair that is not instantiated
+int match_search(int K, int G, const double* Q, int64_t nq, const double* C, int64_t nc, const KnnGeom& g, double* pd,
+                 int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
+  bool found = false;
+  dispatch_k<1, 2, 4, 8>(K, [&](auto k) {
+    found = dispatch_k<1, 2, 4, 5, 8>(G, [&](auto gr) {
+      match_run<decltype(k)::value, decltype(gr)::value>(Q, nq, C, nc, g, pd, pi, od, oi, st);
+    });
+  });
+  return found ? 0 : fail(CLIPPER_HIP_E_INTERNAL, "no descriptor search kernel for K = %d, G = %d", K, G);
 }
-
-void match_search(int K, int G, const double* Q, int64_t nq, const double* C, int64_t nc, const MatchGeom& g, double* pd,
-                  int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
-  switch (K) {
-    case 1: match_launch<1>(G, Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    case 2: match_launch<2>(G, Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    case 4: match_launch<4>(G, Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-    default: match_launch<8>(G, Q, nq, C, nc, g, pd, pi, od, oi, st); break;
-  }
-}
-
-inline int match_list_k(int len) { return len <= 1 ? 1 : (len <= 2 ? 2 : (len <= 4 ? 4 : 8)); }
 
 // F0: d x n0, F1: d x n1 column-major (each descriptor contiguous). The number of associations comes back; A_out is
 // column-major n x 2, sqd_out (may be null) one squared distance per row; nn_idx_out / nn_sqd_out (may be null) the
@@ -75,47 +51,39 @@ int64_t match_descriptors(int device, const double* F0, int64_t n0, const double
   if (why.empty()) why = cm::check_finite("F0", F0, n0, d);
   if (why.empty()) why = cm::check_finite("F1", F1, n1, d);
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s", why.c_str());
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
 
   const int G = match_groups(d), dp = G * MATCH_GROUP;
   const bool mutual = prm.mutual != 0;
-  const int Kf = match_list_k(cm::forward_len(prm)), Kb = match_list_k(prm.knn);
-  const MatchGeom gf = match_geom(n0, n1), gb = match_geom(n1, n0);
+  const int Kf = knn_list_k(cm::forward_len(prm), 1, 8), Kb = knn_list_k(prm.knn, 1, 8);
+  const KnnGeom gf = knn_geom(n0, n1), gb = knn_geom(n1, n0);
   const std::vector<double> h0 = cm::pad_rows(F0, n0, d, dp), h1 = cm::pad_rows(F1, n1, d, dp);
   const size_t nof = static_cast<size_t>(n0) * Kf, nob = mutual ? static_cast<size_t>(n1) * Kb : 0;
   // the partial lists of the backward search reuse the forward search's (the stream orders them)
   const size_t np = std::max(static_cast<size_t>(gf.S) * nof, static_cast<size_t>(gb.S) * nob);
   double *d0 = nullptr, *d1 = nullptr, *pd = nullptr, *odf = nullptr, *odb = nullptr;
   int32_t *pi = nullptr, *oif = nullptr, *oib = nullptr;
-  DevTemps tmp;
-  if (tmp.alloc(device, d0, h0.size() * sizeof(double)) || tmp.alloc(device, d1, h1.size() * sizeof(double)) ||
-      tmp.alloc(device, pd, np * sizeof(double)) || tmp.alloc(device, pi, np * sizeof(int32_t)) ||
-      tmp.alloc(device, odf, nof * sizeof(double)) || tmp.alloc(device, oif, nof * sizeof(int32_t)) ||
-      tmp.alloc(device, odb, nob * sizeof(double)) || tmp.alloc(device, oib, nob * sizeof(int32_t))) {
-    tmp.release();
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  }
-  std::vector<double> fd(nof), bd(nob);
+  std::vector<double> fd(nof), bd(nob);  // (declared before tmp: its release waits for the device, so they outlive every copy)
   std::vector<int32_t> fi(nof), bi(nob);
+  DevTemps tmp;
+  if (int rc = tmp.alloc(device, d0, h0.size() * sizeof(double), d1, h1.size() * sizeof(double), pd, np * sizeof(double),
+                         pi, np * sizeof(int32_t), odf, nof * sizeof(double), oif, nof * sizeof(int32_t),
+                         odb, nob * sizeof(double), oib, nob * sizeof(int32_t)))
+    return rc;
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
-  bool ok = hipMemcpyAsync(d0, h0.data(), h0.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d1, h1.data(), h1.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    match_search(Kf, G, d0, n0, d1, n1, gf, pd, pi, odf, oif, st);
-    if (mutual) match_search(Kb, G, d1, n1, d0, n0, gb, pd, pi, odb, oib, st);
-    ok = hipMemcpyAsync(fd.data(), odf, nof * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipMemcpyAsync(fi.data(), oif, nof * sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (ok && mutual)
-      ok = hipMemcpyAsync(bd.data(), odb, nob * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-           hipMemcpyAsync(bi.data(), oib, nob * sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-    ok = hipStreamSynchronize(st) == hipSuccess && ok && hipGetLastError() == hipSuccess;  // the one wait of the call
+  if (int rc = copy_up(d0, h0.data(), h0.size(), st)) return rc;
+  if (int rc = copy_up(d1, h1.data(), h1.size(), st)) return rc;
+  if (int rc = match_search(Kf, G, d0, n0, d1, n1, gf, pd, pi, odf, oif, st)) return rc;
+  if (mutual)
+    if (int rc = match_search(Kb, G, d1, n1, d0, n0, gb, pd, pi, odb, oib, st)) return rc;
+  if (int rc = copy_down(fd.data(), odf, nof, st)) return rc;
+  if (int rc = copy_down(fi.data(), oif, nof, st)) return rc;
+  if (mutual) {
+    if (int rc = copy_down(bd.data(), odb, nob, st)) return rc;
+    if (int rc = copy_down(bi.data(), oib, nob, st)) return rc;
   }
-  tmp.release();
-  if (!ok) return fail(CLIPPER_HIP_E_HIP, "descriptor search failed: %s", hipGetErrorString(hipGetLastError()));
+  HIPCHK(hipStreamSynchronize(st));  // the one wait of the call
+  HIPCHK(hipGetLastError());
 
   const cm::Lists fwd{fi.data(), fd.data(), n0, Kf}, bwd{bi.data(), bd.data(), n1, Kb};
   const cm::Rows rows = cm::select(prm, fwd, bwd);

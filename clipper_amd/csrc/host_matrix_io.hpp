@@ -1,22 +1,11 @@
 // host_matrix_io.hpp — the matrix in and out of a context: the affinity fill, the dense and sparse setters, the
-// getter, the mat-vecs of the test API, and the nearest-neighbour search that puts associations together before any
-// context exists. Part of clipper_hip.hip (one translation unit; included there, last). The order of the bodies here
-// is the order in which the code object holds their kernels (the fill's: with_builtin_invariant's order of invariants).
+// getter and the mat-vecs of the test API. Part of clipper_hip.hip (one translation unit; included there behind every
+// other driver of a context and in front of the stand-alone searches: host_knn.hpp and what follows it). The order of
+// the bodies here is the order in which the code object holds their kernels (the fill's: with_builtin_invariant's
+// order of invariants).
 #pragma once
 
 namespace {
-
-// brute-force nearest neighbours: launch of the two kernels for one (K, D)
-template <int K, int D>
-int knn_run(const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S, int64_t chunk,
-            double* pd, int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
-  dim3 g(static_cast<unsigned>(ceil_div(n0, 256)), static_cast<unsigned>(S));
-  hipLaunchKernelGGL((k_knn_partial<K, D>), g, dim3(256), 0, st, dP0, n0, dP1, n1, chunk, pd, pi);
-  hipLaunchKernelGGL((k_knn_merge<K>), dim3(static_cast<unsigned>(ceil_div(n0, 256))), dim3(256), 0,
-                     st, pd, pi, n0, S, od, oi);
-  return 0;
-}
-
 
 // The fill with a built-in invariant (declared in host_matrix.hpp): defined here, behind the batch, so that the fill
 // kernels keep their place in the code object. One body for every invariant, reached with `queued` null (the fill runs
@@ -105,25 +94,6 @@ int fill_custom(Ctx* h, const CustomFill& f) {
   }
   return rc;
 }
-
-// device temporaries of one call, released on every path (by release(), or when it goes out of scope)
-struct DevTemps {
-  std::vector<std::pair<int, void*>> v;
-  ~DevTemps() { release(); }
-  void release() {
-    for (auto& p : v) {
-      hipSetDevice(p.first);
-      hipFree(p.second);
-    }
-    v.clear();
-  }
-  template <typename T>
-  int alloc(int dev, T*& p, size_t n) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16)));
-    v.emplace_back(dev, p);
-    return 0;
-  }
-};
 
 // A matrix the caller hands over replaces the one held: no nodes, no row view, no points behind it, no explicit C
 // store; the problem sized for m. has_matrix stays false until the new matrix is complete.
@@ -369,107 +339,6 @@ int get_dense(Ctx* h, double* M_out, double* C_out) {
   }
   if (h->csc_valid) drop_dense(h);  // the copy was materialised for this call only: M lives in the slices
   return 0;
-}
-
-// ---- putative associations (before the path): nearest neighbours ---------------------------------
-
-// the seam every d = 2 | 3 search goes through (host_knn_grid.hpp): picks the route, the lists land in od / oi
-int knn_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
-              int32_t* oi, hipStream_t st, DevTemps& tmp);
-
-template <int K>
-void knn_launch(int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, int S, int64_t chunk, double* pd,
-                int32_t* pi, double* od, int32_t* oi, hipStream_t st) {
-  if (d == 3) knn_run<K, 3>(dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st);
-  else knn_run<K, 2>(dP0, n0, dP1, n1, S, chunk, pd, pi, od, oi, st);
-}
-
-// the knn nearest points of pcd1 (P1) to every point of pcd0 (P0), nearest first: indices, squared distances
-int knn_search(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d, int knn, int32_t* idx_out,
-        double* sqd_out) {
-  if (!P0 || !P1 || !idx_out || n0 < 1 || n1 < 1) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
-  if (d != 2 && d != 3) return fail(CLIPPER_HIP_E_INVALID, "points must have 2 or 3 coordinates");
-  if (knn < 1 || knn > 16) return fail(CLIPPER_HIP_E_INVALID, "knn must be in 1..16");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
-  const int K = knn <= 1 ? 1 : (knn <= 2 ? 2 : (knn <= 4 ? 4 : (knn <= 8 ? 8 : 16)));
-  double *dP0 = nullptr, *dP1 = nullptr, *od = nullptr;
-  int32_t* oi = nullptr;
-  const size_t b0 = static_cast<size_t>(n0) * d * sizeof(double), b1 = static_cast<size_t>(n1) * d * sizeof(double);
-  const size_t no = static_cast<size_t>(n0) * K;
-  DevTemps tmp;
-  if (tmp.alloc(device, dP0, b0) || tmp.alloc(device, dP1, b1) || tmp.alloc(device, od, no * sizeof(double)) ||
-      tmp.alloc(device, oi, no * sizeof(int32_t))) {
-    tmp.release();
-    return fail(CLIPPER_HIP_E_NOMEM, "device allocation failed");
-  }
-  hipStream_t st = nullptr;  // the default stream: a stand-alone call
-  bool ok = hipMemcpyAsync(dP0, P0, b0, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(dP1, P1, b1, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    // the route under the process-wide mode (host_knn_grid.hpp): its temporaries join tmp
-    if (int rc = knn_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp)) return rc;
-    std::vector<double> hd(no);
-    std::vector<int32_t> hi(no);
-    ok = hipMemcpy(hd.data(), od, no * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(hi.data(), oi, no * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
-         hipGetLastError() == hipSuccess;
-    if (ok) {
-      for (int64_t i = 0; i < n0; ++i)
-        for (int k = 0; k < knn; ++k) {
-          idx_out[i * knn + k] = hi[static_cast<size_t>(i) * K + k];
-          if (sqd_out) sqd_out[i * knn + k] = hd[static_cast<size_t>(i) * K + k];
-        }
-    }
-  }
-  tmp.release();
-  if (!ok) return fail(CLIPPER_HIP_E_HIP, "nearest-neighbour search failed: %s", hipGetErrorString(hipGetLastError()));
-  return 0;
-}
-
-// bm_utils::get_putative_associations (bm_utils.cpp:187-229) on the GPU's nearest neighbours: the associations, n x 2
-// column-major; the count comes back
-int64_t distance_based_correspondences(int device, const double* P0, int64_t n0, const double* P1, int64_t n1, int d,
-                                       int knn, double radius, int enforce_1to1, int32_t* A_out, int64_t capacity) {
-  std::vector<int32_t> idx(static_cast<size_t>(std::max<int64_t>(n0, 0)) * std::max(knn, 0));
-  std::vector<double> sqd(idx.size());
-  int rc = knn_search(device, P0, n0, P1, n1, d, knn, idx.data(), sqd.data());
-  if (rc) return rc;
-  // bm_utils.cpp:187-229: rows (i, nn_j(i)) for i ascending, neighbours by distance, kept if within
-  // the radius; one-to-one: per point of pcd1 (ascending) the FIRST closest of its claimants
-  const double r2 = radius * radius;
-  std::vector<std::pair<int32_t, int32_t>> rows;
-  std::map<int32_t, std::vector<std::pair<int32_t, double>>> claim;
-  for (int64_t i = 0; i < n0; ++i)
-    for (int k = 0; k < knn; ++k) {
-      const int32_t c1 = idx[static_cast<size_t>(i) * knn + k];
-      const double sd = sqd[static_cast<size_t>(i) * knn + k];
-      if (c1 < 0) continue;  // fewer than knn points in pcd1
-      if (sd <= r2) {
-        rows.emplace_back(static_cast<int32_t>(i), c1);
-        if (enforce_1to1) claim[c1].emplace_back(static_cast<int32_t>(i), sd);
-      }
-    }
-  if (enforce_1to1) {
-    rows.clear();
-    for (const auto& it : claim) {
-      size_t best = 0;
-      for (size_t q = 1; q < it.second.size(); ++q)
-        if (it.second[q].second < it.second[best].second) best = q;  // std::min_element: first minimum
-      rows.emplace_back(it.second[best].first, it.first);
-    }
-  }
-  const int64_t n = static_cast<int64_t>(rows.size());
-  if (n > capacity) return fail(CLIPPER_HIP_E_INVALID, "capacity %lld < %lld associations",
-                                static_cast<long long>(capacity), static_cast<long long>(n));
-  for (int64_t r = 0; r < n; ++r) {  // column-major n x 2, as clipper::Association
-    A_out[r] = rows[static_cast<size_t>(r)].first;
-    A_out[n + r] = rows[static_cast<size_t>(r)].second;
-  }
-  return n;
 }
 
 // x -> candidate 0 of table 0 of a shard (staged through the u0 buffer)

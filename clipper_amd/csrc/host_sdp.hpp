@@ -262,11 +262,7 @@ int sdp_solve_impl(int device, const double* M, const double* C, int64_t n, cons
   const int route = g_sdp_route.load();
   if (int rc = sdp_check_params(P, n, route)) return rc;
   const int taken = clipper_sdpw_plan::route_of(route, n);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   SdpBufs b;
   if (int rc = sdp_alloc(b, n, P, taken, true)) return rc;
   const size_t nn = static_cast<size_t>(n * n);

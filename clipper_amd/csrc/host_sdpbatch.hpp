@@ -293,11 +293,7 @@ int sdp_solve_batch_impl(int device, const clipper_sdp_problem_t* p, int32_t cou
       return fail(CLIPPER_HIP_E_SCOPE, "problem %d: sdp: n = %lld is above the device solver's limit of %d", i,
                   (long long)p[i].n, clipper_sdpw_plan::route_limit(route));
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(CLIPPER_HIP_E_INVALID, "device %d out of range", device);
-  HIPCHK(hipSetDevice(device));
+  if (int rc = use_device(device)) return rc;
   SdpBatchState S;
   S.device = device;
   S.n.resize(static_cast<size_t>(count));

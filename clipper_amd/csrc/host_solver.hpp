@@ -555,10 +555,7 @@ void destroy_ctx(Ctx* h);  // (host_solve.hpp)
 Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_slot,
               bool multiproc) {
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    fail(CLIPPER_HIP_E_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-    return nullptr;
-  }
+  if (visible_devices(ndev)) return nullptr;
   if (storage != CLIPPER_HIP_STORE_F32 && storage != CLIPPER_HIP_STORE_F64 &&
       storage != CLIPPER_HIP_STORE_F32_CSC && storage != CLIPPER_HIP_STORE_F64_CSC) {
     fail(CLIPPER_HIP_E_INVALID, "storage must be CLIPPER_HIP_STORE_F32, _F64, _F32_CSC or _F64_CSC");
@@ -575,13 +572,11 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
     Shard& s = h->sh[static_cast<size_t>(p)];
     s.device = devices[p];
     s.slot = first_slot + p;
-    if (s.device < 0 || s.device >= ndev) {
-      fail(CLIPPER_HIP_E_INVALID, "device %d out of range (%d visible)", s.device, ndev);
+    if (use_device(s.device)) {
       destroy_ctx(h);
       return nullptr;
     }
-    if (hipSetDevice(s.device) != hipSuccess ||
-        hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s.ev_reduced, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming) != hipSuccess) {
       fail(CLIPPER_HIP_E_HIP, "cannot create stream/events on device %d", s.device);

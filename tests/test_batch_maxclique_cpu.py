@@ -52,10 +52,13 @@ def test_plan_header_has_no_hip():
 
 
 def test_new_sources_are_in_the_build_lists():
-    text = open(os.path.join(ROOT, "clipper_amd", "build.py")).read()
-    for f in ("k_maxclique.hip.h", "host_maxclique.hpp", "host_mcplan.hpp"):
-        assert f in text, f
+    """the library is rebuilt when one of them changes: the staleness check takes its sources from the tree"""
+    from clipper_amd import build
+    srcs = build.hip_sources()
+    for f in ("k_maxclique.hip.h", "host_maxclique.hpp", "host_mcplan.hpp", "clipper_hip.hip"):
+        assert os.path.join(ROOT, "clipper_amd", "csrc", f) in srcs, f
         assert os.path.exists(os.path.join(ROOT, "clipper_amd", "csrc", f)), f
+    assert os.path.join(ROOT, "include", "clipper_hip.h") in srcs
 
 
 def test_facade_surfaces():

@@ -115,7 +115,8 @@ def test_refusals_leave_the_library_usable():
         (L.clipper_hip_fpfh_from_points, (0, dp(P), n, ok, None, C.byref(abi.Neighborhood(3, np.inf)), dp(F), None),
          "feature neighbourhood: radius must be finite (radius = inf)"),
         (L.clipper_hip_fpfh_from_points, (0, dp(P), 0, ok, None, ok, dp(F), None), "a cloud needs at least one point (n = 0)"),
-        (L.clipper_hip_estimate_normals, (99, dp(P), n, ok, None, dp(out), None), "device 99 out of range"),
+        (L.clipper_hip_estimate_normals, (99, dp(P), n, ok, None, dp(out), None),
+             f"device 99 out of range ({abi.device_count()} visible)"),
     ]
     for fn, args, msg in cases:
         rc = fn(*args)

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
   std::vector<double> P(static_cast<size_t>(n) * 3);
   for (auto& x : P) x = uni(gen);
 
-  const int64_t qblocks = ceil_div(n, 256), tiles = ceil_div(n, KNN_TILE);  // host_match.hpp: match_geom
+  const int64_t qblocks = ceil_div(n, 256), tiles = ceil_div(n, KNN_TILE);  // host_knn.hpp: knn_geom
   const int S = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, ceil_div(512, qblocks))));
   const int64_t chunk = ceil_div(tiles, S) * KNN_TILE;
   const size_t no = static_cast<size_t>(n) * K, np = static_cast<size_t>(S) * no, nf = static_cast<size_t>(n) * FEAT_DIM;

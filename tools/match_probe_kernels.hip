@@ -39,7 +39,7 @@ struct Geom {
   int S;
   int64_t chunk;
 };
-static Geom geom(int64_t nq, int64_t nc) {  // host_match.hpp: match_geom
+static Geom geom(int64_t nq, int64_t nc) {  // host_knn.hpp: knn_geom
   const int64_t qblocks = ceil_div(nq, 256), tiles = ceil_div(nc, KNN_TILE);
   const int S = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, ceil_div(512, qblocks))));
   return {S, ceil_div(tiles, S) * KNN_TILE};
