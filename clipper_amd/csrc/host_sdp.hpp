@@ -43,6 +43,21 @@ int sdp_check_params(const clipper_sdp_params_t* P, int64_t n, int route) {
   return 0;
 }
 
+// The values of a host matrix (column-major, n x n), refused before the device is touched: only the lower triangle is
+// read, so only it is checked. `what`: "M" or "C"; problem >= 0: a batch names the problem in front.
+int sdp_check_finite(const double* A, int64_t n, const char* what, long long problem) {
+  for (int64_t c = 0; c < n; ++c)
+    for (int64_t r = c; r < n; ++r)
+      if (!std::isfinite(A[r + c * n])) {
+        if (problem >= 0)
+          return fail(CLIPPER_HIP_E_INVALID, "problem %lld: sdp: %s: non-finite value at row %lld, column %lld", problem,
+                      what, (long long)r, (long long)c);
+        return fail(CLIPPER_HIP_E_INVALID, "sdp: %s: non-finite value at row %lld, column %lld", what, (long long)r,
+                    (long long)c);
+      }
+  return 0;
+}
+
 // `taken`: the route of this problem (clipper_sdpw_plan::route_of); with_src: room for the uploaded M and C
 // (2 n^2 doubles) too
 int sdp_alloc(SdpBufs& b, int64_t n, const clipper_sdp_params_t* P, int taken, bool with_src) {
@@ -262,6 +277,8 @@ int sdp_solve_impl(int device, const double* M, const double* C, int64_t n, cons
   const int route = g_sdp_route.load();
   if (int rc = sdp_check_params(P, n, route)) return rc;
   const int taken = clipper_sdpw_plan::route_of(route, n);
+  if (int rc = sdp_check_finite(M, n, "M", -1)) return rc;
+  if (int rc = sdp_check_finite(C, n, "C", -1)) return rc;
   if (int rc = use_device(device)) return rc;
   SdpBufs b;
   if (int rc = sdp_alloc(b, n, P, taken, true)) return rc;

@@ -292,6 +292,8 @@ int sdp_solve_batch_impl(int device, const clipper_sdp_problem_t* p, int32_t cou
     if (p[i].n > clipper_sdpw_plan::route_limit(route))
       return fail(CLIPPER_HIP_E_SCOPE, "problem %d: sdp: n = %lld is above the device solver's limit of %d", i,
                   (long long)p[i].n, clipper_sdpw_plan::route_limit(route));
+    if (int rc = sdp_check_finite(p[i].M, p[i].n, "M", i)) return rc;
+    if (int rc = sdp_check_finite(p[i].C, p[i].n, "C", i)) return rc;
   }
   if (int rc = use_device(device)) return rc;
   SdpBatchState S;

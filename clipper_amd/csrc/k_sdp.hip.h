@@ -30,8 +30,9 @@
 // rules stay spelled out here, each marked with the name of its statement in sdp_rules.hpp, so that both kernels keep
 // the instruction stream they had: sdp_norms_add, sdp_rotate_diag, sdp_init_entry, sdp_support / sdp_support_tau,
 // the terms of sdp_update_entry (Z+ itself comes from sdp_z_plus), sdp_residuals, sdp_balance_factor and
-// sdp_close_iteration. A change to one of them in the header is made here too; tests/test_gpu_sdp_wide.py holds the
-// two routes to each other.
+// sdp_close_iteration (its schedule step, sdp_balance_advance, and the no-valid-support rule, sdp_fallback_index /
+// sdp_fallback_weight, are called: one work item, off the hot path). A change to one of them in the header is made
+// here too; tests/test_gpu_sdp_wide.py holds the two routes to each other.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -234,6 +235,7 @@ struct SdpShared {
   double lam[SDP_MAX_N], red[2 * SDP_THREADS / 64];
   int32_t pos_list[SDP_MAX_N];
   int32_t kmax, npos;
+  int32_t top;  // the index that takes weight 1 when no support is valid (sdp_fallback_index)
   double tau;
   SdpCtl c;
 };
@@ -245,7 +247,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
                                          SdpShared& sh) {
   double *rc = sh.rc, *rs = sh.rs, *rt = sh.rt, *lam = sh.lam, *red = sh.red;
   int32_t* pos_list = sh.pos_list;
-  int32_t &kmax = sh.kmax, &npos = sh.npos;
+  int32_t &kmax = sh.kmax, &npos = sh.npos, &top = sh.top;
   double& tau = sh.tau;
   SdpCtl& c = sh.c;
   const int tid = threadIdx.x, n = g.n, np = g.np, nn = n * n;
@@ -316,9 +318,11 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       }
       __syncthreads();
       if (ok && cnt == kmax) tau = (sum - 1.0) / cnt;  // (equal sets: equal sums, the same bits)
+      if (tid == 0 && kmax == 0) top = sdp_fallback_index(lam, n);  // no valid support: no tau is written, none read
       __syncthreads();
       if (tid < np) {
-        const double m = tid < n ? sdp_simplex_weight(lam[tid], tau) : 0.0;
+        const double m =
+            tid < n ? (kmax == 0 ? sdp_fallback_weight(tid, top) : sdp_simplex_weight(lam[tid], tau)) : 0.0;
         g.mu[tid] = m;
         lam[tid] = m;
       }
@@ -377,7 +381,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
       // residual balancing; every thread rescales the entries of U it wrote
       double f = 1.0;
       const int32_t done = c.iters + 1;
-      if (!conv && done % SDP_ADAPT_EVERY == 0) {
+      if (!conv && done == c.adapt_next) {
         if (r_p > SDP_ADAPT_MU * r_d) f = SDP_ADAPT_TAU;
         else if (r_d > SDP_ADAPT_MU * r_p) f = 1.0 / SDP_ADAPT_TAU;
       }
@@ -386,6 +390,7 @@ __device__ __forceinline__ void sdp_body(const SdpArgs& g, int32_t mode, int32_t
         for (int idx = tid; idx < nn; idx += SDP_THREADS) g.U[idx] = sdp_rescale_u(g.U[idx], rescale);
       __syncthreads();
       if (tid == 0) {
+        sdp_balance_advance(c, done, conv, f);
         c.iters = done;
         c.r_prim = r_p;
         c.r_dual = r_d;

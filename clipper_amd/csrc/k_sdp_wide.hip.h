@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_project(SdpArgs g, const d
                                                               int32_t* __restrict__ pos_list,
                                                               SdpWideState* __restrict__ st) {
   __shared__ double lam[SDPW_MAX_N];
-  __shared__ int32_t kmax;
+  __shared__ int32_t kmax, top;
   __shared__ double tau;
   const int tid = threadIdx.x, n = g.n, np = g.np;
   if (tid < n) lam[tid] = A[tid * np + tid];
@@ -239,9 +239,10 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_project(SdpArgs g, const d
   }
   __syncthreads();
   if (ok && cnt == kmax) tau = sdp_support_tau(sum, cnt);  // (equal sets: equal sums, the same bits)
+  if (tid == 0 && kmax == 0) top = sdp_fallback_index(lam, n);  // no valid support: no tau is written, none read
   __syncthreads();
   if (tid < np) {
-    const double m = tid < n ? sdp_simplex_weight(lam[tid], tau) : 0.0;
+    const double m = tid < n ? (kmax == 0 ? sdp_fallback_weight(tid, top) : sdp_simplex_weight(lam[tid], tau)) : 0.0;
     g.mu[tid] = m;
     lam[tid] = m;
   }
@@ -356,7 +357,7 @@ __global__ void __launch_bounds__(SDP_THREADS) k_sdpw_decide(SdpArgs g, SdpWideS
   }
   // the iteration ends here (work item 0)
   SdpCtl c = st->c;
-  const double f = sdp_balance_factor(c.iters + 1, conv, r_p, r_d);
+  const double f = sdp_balance_factor(c, c.iters + 1, conv, r_p, r_d);
   sdp_close_iteration(c, r_p, r_d, mx, conv, f, sw);
   st->c = c;
   st->want_dual = 0;

@@ -2,7 +2,7 @@
 // once for the workgroup route (k_sdp.hip.h), the wide route (k_sdp_wide.hip.h) and the host: the constants, the
 // control record, the INIT values, the matrices that are eigendecomposed, the Jacobi rotation and what it does to a
 // block, the simplex rule of the eigenvalues, one entry's update with the six sums of the stopping rule, the
-// tolerances, the gap test, the residual balancing and the record an iteration leaves. Plain sequential functions of
+// tolerances, the gap test, the residual balancing with its schedule and the record an iteration leaves. Plain sequential functions of
 // one entry, one block or one support (sdp_store_block writes a block's eight entries, sdp_support walks the
 // eigenvalues): which work item holds what and in what order a sum is reduced across work items belong to the kernels.
 // Every expression rounds as written (the build runs with -ffp-contract=off): changing an expression's shape here
@@ -19,9 +19,10 @@ namespace clipper_hip {
 constexpr int SDP_MAX_SWEEPS = 40;
 constexpr double SDP_JACOBI_TOL = 1e-13;  // stop sweeping when off(A) <= tol * ||A||_F
 constexpr double SDP_RHO0 = 1.0;
-constexpr int SDP_ADAPT_EVERY = 10;       // residual balancing: every 10 iterations,
+constexpr int SDP_ADAPT_EVERY = 10;       // residual balancing: checked every 10 iterations at first;
 constexpr double SDP_ADAPT_MU = 10.0;     // when one residual exceeds 10 times the other,
-constexpr double SDP_ADAPT_TAU = 2.0;     // rho is multiplied or divided by 2 and U divided or multiplied
+constexpr double SDP_ADAPT_TAU = 2.0;     // rho is multiplied or divided by 2 and U divided or multiplied;
+constexpr int32_t SDP_ADAPT_MAX_EVERY = 1 << 30;  // the interval doubles with every reversal of the moves, up to this
 
 // device state of one problem (the host reads it after every launch)
 struct SdpCtl {
@@ -33,11 +34,18 @@ struct SdpCtl {
   int32_t converged;
   int32_t infeasible;     // no diagonal entry of C is nonzero
   int32_t sweeps;         // Jacobi sweeps so far (all projections and checks)
+  int32_t adapt_next;     // the schedule of the residual balancing: the iteration of the next check,
+  int32_t adapt_every;    // the interval between checks,
+  int32_t adapt_dir;      // the direction of the last move of rho (+1 up, -1 down, 0 none yet)
+  int32_t pad;
 };
+static_assert(sizeof(SdpCtl) == 72, "five doubles and eight int32: the hosts copy the record as it is");
 
 // ---- INIT: X = Z = diag(mask) / #diag(mask), U = 0, Q = I, mu = diag(X) ---------------------------------------------
 // cnt: the nonzero diagonal entries of the mask
-SDP_HD void sdp_init_ctl(SdpCtl& c, int cnt) { c = SdpCtl{SDP_RHO0, 0.0, 0.0, 0.0, 0.0, 0, 0, cnt == 0, 0}; }
+SDP_HD void sdp_init_ctl(SdpCtl& c, int cnt) {
+  c = SdpCtl{SDP_RHO0, 0.0, 0.0, 0.0, 0.0, 0, 0, cnt == 0, 0, SDP_ADAPT_EVERY, SDP_ADAPT_EVERY, 0, 0};
+}
 SDP_HD double sdp_init_weight(int cnt) { return cnt ? 1.0 / cnt : 0.0; }
 // an entry of X, Z or mu; on_masked_diag: a diagonal entry that the mask keeps
 SDP_HD double sdp_init_entry(bool on_masked_diag, double w) { return on_masked_diag ? w : 0.0; }
@@ -129,6 +137,21 @@ SDP_HD bool sdp_support(const double* lam, int n, double li, int& cnt, double& s
 
 SDP_HD double sdp_simplex_weight(double lam, double tau) { return fmax(lam - tau, 0.0); }
 
+// No valid support. In exact arithmetic the support of the largest eigenvalue alone is always valid (l > l - 1), but
+// in fp64 l - 1 rounds back to l once l passes 2^53 (W = Z - U + M / rho grows with M and as rho halves), and a comparison
+// with a NaN fails: then sdp_support is false for every index and no tau exists. The projection is then the limit of
+// the rule: weight 1 on the first index of the largest eigenvalue (what a scan from index 0 with a strict > finds; a
+// NaN gives way to the first number after it and is never chosen over one) and 0 elsewhere. Both routes take this
+// when the largest valid support counts 0, and read no tau.
+SDP_HD int sdp_fallback_index(const double* lam, int n) {
+  int top = 0;
+  for (int j = 1; j < n; ++j)
+    if (lam[j] > lam[top] || (lam[top] != lam[top] && lam[j] == lam[j])) top = j;
+  return top;
+}
+
+SDP_HD double sdp_fallback_weight(int i, int top) { return i == top ? 1.0 : 0.0; }
+
 // ---- one entry's update: Z+ = proj_P(X + U), U+ = U + X - Z+, and its terms of the six sums of the stopping rule ----
 struct SdpSums {
   double rp2, rd2, xx, zz, uu, mx;  // ||X - Z+||^2, ||Z+ - Z||^2, ||X||^2, ||Z+||^2, ||U+||^2, <M, X>
@@ -167,13 +190,28 @@ SDP_HD bool sdp_gap_closed(double d, double mx, double eps_abs, double eps_rel) 
 }
 
 // ---- residual balancing: the factor of rho after iteration `done`; U is rescaled by its inverse ---------------------
-SDP_HD double sdp_balance_factor(int32_t done, bool conv, double r_p, double r_d) {
+// A check is due at iteration c.adapt_next (10, 20, 30, ... while the moves keep one direction).
+SDP_HD double sdp_balance_factor(const SdpCtl& c, int32_t done, bool conv, double r_p, double r_d) {
   double f = 1.0;
-  if (!conv && done % SDP_ADAPT_EVERY == 0) {
+  if (!conv && done == c.adapt_next) {
     if (r_p > SDP_ADAPT_MU * r_d) f = SDP_ADAPT_TAU;
     else if (r_d > SDP_ADAPT_MU * r_p) f = 1.0 / SDP_ADAPT_TAU;
   }
   return f;
+}
+
+// The schedule after iteration `done` with factor f: a move that reverses the last one (up after down,
+// down after up) doubles the interval between checks, so the penalty cannot go up and down for ever (the star graph's
+// limit cycle); a check that moves nothing changes neither the interval nor the remembered direction, and a run whose
+// moves keep one direction is checked every SDP_ADAPT_EVERY iterations, as before the schedule had a memory.
+SDP_HD void sdp_balance_advance(SdpCtl& c, int32_t done, bool conv, double f) {
+  if (conv || done != c.adapt_next) return;
+  const int32_t dir = f > 1.0 ? 1 : (f < 1.0 ? -1 : 0);
+  if (dir != 0) {
+    if (c.adapt_dir == -dir && c.adapt_every <= SDP_ADAPT_MAX_EVERY / 2) c.adapt_every *= 2;
+    c.adapt_dir = dir;
+  }
+  c.adapt_next = done > INT32_MAX - c.adapt_every ? INT32_MAX : done + c.adapt_every;
 }
 
 enum { SDP_RESCALE_NONE = 0, SDP_RESCALE_DIVIDE = 1, SDP_RESCALE_MULTIPLY = 2 };  // what a factor does to U
@@ -189,6 +227,7 @@ SDP_HD double sdp_rescale_u(double u, int rescale) {
 
 // The record an iteration leaves (dval is written where the dual bound is computed); f: sdp_balance_factor's
 SDP_HD void sdp_close_iteration(SdpCtl& c, double r_p, double r_d, double mx, bool conv, double f, int32_t sw) {
+  sdp_balance_advance(c, c.iters + 1, conv, f);
   c.iters = c.iters + 1;
   c.r_prim = r_p;
   c.r_dual = r_d;

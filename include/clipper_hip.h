@@ -407,7 +407,9 @@ typedef struct clipper_sdp_info_t {
 int clipper_hip_sdp(clipper_hip_t* h, const clipper_sdp_params_t* params, double* X_out, double* Y_out,
                     double* lambdas_out, double* evec1_out, clipper_sdp_info_t* info);
 /* Stand-alone: M and C column-major n x n (host), lower triangles read. nodes_out (capacity n, may be NULL)
- * receives the selection; returns its size or <0. Other outputs as clipper_hip_sdp. */
+ * receives the selection; returns its size or <0. Other outputs as clipper_hip_sdp. A NaN or an infinity in the
+ * lower triangle of M or C is refused with CLIPPER_HIP_E_INVALID before the device is touched, its row and column in
+ * the message. */
 int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t n, const clipper_sdp_params_t* params,
                           double* X_out, double* Y_out, double* lambdas_out, double* evec1_out, int32_t* nodes_out,
                           clipper_sdp_info_t* info);
@@ -421,7 +423,7 @@ int clipper_hip_sdp_solve(int device, const double* M, const double* C, int64_t 
  * infos[i].num_nodes nodes. Only evec1, the eigenvalues, the nodes and the control records come back from the device
  * unless a problem asks for X or Y.
  * The whole call is refused on the first bad problem, its index in the message, before anything touches the device:
- * count < 0, a NULL M or C, n < 1 -> CLIPPER_HIP_E_INVALID; n above the route setting's limit (CLIPPER_HIP_SDP_MAX_N by
+ * count < 0, a NULL M or C, n < 1, a non-finite value in a lower triangle -> CLIPPER_HIP_E_INVALID; n above the route setting's limit (CLIPPER_HIP_SDP_MAX_N by
  * default) -> CLIPPER_HIP_E_SCOPE; params
  * as clipper_hip_sdp_solve. count == 0 succeeds and does nothing. A C without a nonzero diagonal entry fails the call
  * with CLIPPER_HIP_E_INVALID. time_limit_secs > 0 bounds the whole call (checked between rounds of launches): every

@@ -1,5 +1,6 @@
 // The scalar rules of the semidefinite relaxation's iteration (clipper_amd/csrc/sdp_rules.hpp), host only: the simplex
-// rule against its sort-and-cumulate definition, the residual balancing, the gap test and the tolerances at their
+// rule against its sort-and-cumulate definition and where no support is valid, the residual balancing and its schedule
+// (a reversal doubles the interval, a one-way run keeps it), the gap test and the tolerances at their
 // boundaries, the Jacobi rotation, and the constants (printed for tests/test_sdp_wide_cpu.py, which holds them to
 // tests/sdp_model.py). The checks the rules are held to are exact; two side checks (the weights sum to 1,
 // c^2 + s^2 = 1) allow a few roundings. Built with g++ by tests/test_sdp_wide_cpu.py.
@@ -118,14 +119,22 @@ static void check_balancing() {
   const double above10 = std::nextafter(10.0, inf);
   const int dones[] = {9, 10, 11, 20};
   for (int done : dones) {
+    SdpCtl k;
+    sdp_init_ctl(k, 3);
+    CHECK(k.adapt_next == 10 && k.adapt_every == 10 && k.adapt_dir == 0);
+    // the record of a run whose moves kept one direction up to `done`: its checks fall on the multiples of 10, as the
+    // schedule without memory had them (check_schedule walks such a run through the rules themselves)
+    for (int it = 1; it < done; ++it)
+      sdp_close_iteration(k, 20.0, 1.0, 0.0, false, sdp_balance_factor(k, it, false, 20.0, 1.0), 0);
+    CHECK(k.iters == done - 1 && k.adapt_every == 10 && k.adapt_next == (done + 9) / 10 * 10);
     const bool due = done % 10 == 0;
-    CHECK(sdp_balance_factor(done, false, 10.0, 1.0) == 1.0);             // r_p / r_d = 10 exactly: no change
-    CHECK(sdp_balance_factor(done, false, above10, 1.0) == (due ? 2.0 : 1.0));
-    CHECK(sdp_balance_factor(done, false, 1.0, 10.0) == 1.0);             // 1 / 10 exactly: no change
-    CHECK(sdp_balance_factor(done, false, 1.0, above10) == (due ? 0.5 : 1.0));
-    CHECK(sdp_balance_factor(done, false, 3.0, 3.0) == 1.0);
-    CHECK(sdp_balance_factor(done, true, above10, 1.0) == 1.0);           // converged: no change
-    CHECK(sdp_balance_factor(done, true, 1.0, above10) == 1.0);
+    CHECK(sdp_balance_factor(k, done, false, 10.0, 1.0) == 1.0);             // r_p / r_d = 10 exactly: no change
+    CHECK(sdp_balance_factor(k, done, false, above10, 1.0) == (due ? 2.0 : 1.0));
+    CHECK(sdp_balance_factor(k, done, false, 1.0, 10.0) == 1.0);             // 1 / 10 exactly: no change
+    CHECK(sdp_balance_factor(k, done, false, 1.0, above10) == (due ? 0.5 : 1.0));
+    CHECK(sdp_balance_factor(k, done, false, 3.0, 3.0) == 1.0);
+    CHECK(sdp_balance_factor(k, done, true, above10, 1.0) == 1.0);           // converged: no change
+    CHECK(sdp_balance_factor(k, done, true, 1.0, above10) == 1.0);
   }
   CHECK(sdp_rescale_of(1.0) == SDP_RESCALE_NONE && sdp_rescale_of(2.0) == SDP_RESCALE_DIVIDE &&
         sdp_rescale_of(0.5) == SDP_RESCALE_MULTIPLY);
@@ -140,11 +149,118 @@ static void check_balancing() {
   CHECK(c0.infeasible == 1 && sdp_init_weight(0) == 0.0 && sdp_init_weight(4) == 0.25);
   c.iters = 9;
   c.sweeps = 5;
-  sdp_close_iteration(c, 20.0, 1.0, -7.0, false, sdp_balance_factor(10, false, 20.0, 1.0), 3);
+  sdp_close_iteration(c, 20.0, 1.0, -7.0, false, sdp_balance_factor(c, 10, false, 20.0, 1.0), 3);
   CHECK(c.iters == 10 && c.rho == 2.0 && c.r_prim == 20.0 && c.r_dual == 1.0 && c.pval == -7.0 && c.converged == 0 &&
         c.sweeps == 8);
-  sdp_close_iteration(c, 1.0, 1.0, -7.5, true, sdp_balance_factor(11, true, 1.0, 1.0), 2);
+  CHECK(c.adapt_next == 20 && c.adapt_every == 10 && c.adapt_dir == 1);
+  sdp_close_iteration(c, 1.0, 1.0, -7.5, true, sdp_balance_factor(c, 11, true, 1.0, 1.0), 2);
   CHECK(c.iters == 11 && c.rho == 2.0 && c.converged == 1 && c.sweeps == 10 && c.pval == -7.5);
+  CHECK(c.adapt_next == 20 && c.adapt_every == 10 && c.adapt_dir == 1);
+}
+
+// ---- the schedule of the residual balancing -------------------------------------------------------------------------
+// One iteration with the residuals r_p, r_d through the rules, as k_sdpw_decide closes it; returns the factor
+static double run_iteration(SdpCtl& c, double r_p, double r_d) {
+  const double f = sdp_balance_factor(c, c.iters + 1, false, r_p, r_d);
+  sdp_close_iteration(c, r_p, r_d, 0.0, false, f, 0);
+  return f;
+}
+
+static void check_schedule() {
+  const double UP[2] = {20.0, 1.0}, DOWN[2] = {1.0, 20.0}, NONE[2] = {3.0, 3.0};
+  // a one-way run keeps the schedule: a move at every multiple of 10 and nowhere else, the interval stays 10
+  for (const double* way : {UP, DOWN}) {
+    SdpCtl c;
+    sdp_init_ctl(c, 3);
+    double rho = 1.0;
+    for (int it = 1; it <= 100; ++it) {
+      const double f = run_iteration(c, way[0], way[1]);
+      CHECK(f == (it % 10 == 0 ? (way == UP ? 2.0 : 0.5) : 1.0));
+      rho *= f;
+      CHECK(c.rho == rho && c.adapt_every == 10 && c.adapt_next == (it / 10 + 1) * 10);
+      CHECK(c.adapt_dir == (it < 10 ? 0 : (way == UP ? 1 : -1)));
+    }
+    CHECK(c.rho == (way == UP ? 1024.0 : 1.0 / 1024.0));
+  }
+  // a reversal doubles the interval; a check that moves nothing changes neither the interval nor the direction
+  SdpCtl c;
+  sdp_init_ctl(c, 3);
+  struct Step { int at; const double* r; double f; int every, next, dir; };
+  const Step steps[] = {
+      {10, UP, 2.0, 10, 20, 1},      // the first move: nothing to reverse
+      {20, NONE, 1.0, 10, 30, 1},    // no move: the interval and the direction stay
+      {30, DOWN, 0.5, 20, 50, -1},   // down after up: 10 -> 20
+      {50, DOWN, 0.5, 20, 70, -1},   // the same way again: stays 20
+      {70, NONE, 1.0, 20, 90, -1},
+      {90, UP, 2.0, 40, 130, 1},     // up after down (the check without a move in between does not hide it): 20 -> 40
+      {130, DOWN, 0.5, 80, 210, -1},
+  };
+  int it = 0;
+  for (const Step& s : steps) {
+    for (++it; it < s.at; ++it) CHECK(run_iteration(c, UP[0], UP[1]) == 1.0);  // between checks nothing moves
+    CHECK(run_iteration(c, s.r[0], s.r[1]) == s.f);
+    CHECK(c.iters == s.at && c.adapt_every == s.every && c.adapt_next == s.next && c.adapt_dir == s.dir);
+  }
+  // a cycle like the star's (up at one check, down at the next, for ever): the moves thin out geometrically, so
+  // 100 000 iterations hold at most log2(100 000 / 10) + 2 of them
+  sdp_init_ctl(c, 3);
+  int moves = 0;
+  for (int k = 1; k <= 100000; ++k) {
+    const bool up = c.adapt_dir <= 0;
+    moves += run_iteration(c, up ? UP[0] : DOWN[0], up ? UP[1] : DOWN[1]) != 1.0;
+  }
+  CHECK(moves <= 15 && c.rho <= 2.0 && c.rho >= 0.5);
+  // the interval stops doubling at SDP_ADAPT_MAX_EVERY and the next check never passes INT32_MAX
+  sdp_init_ctl(c, 3);
+  c.adapt_every = SDP_ADAPT_MAX_EVERY;
+  c.adapt_dir = 1;
+  c.adapt_next = INT32_MAX - 5;
+  c.iters = INT32_MAX - 6;
+  CHECK(run_iteration(c, DOWN[0], DOWN[1]) == 0.5);
+  CHECK(c.adapt_every == SDP_ADAPT_MAX_EVERY && c.adapt_next == INT32_MAX && c.adapt_dir == -1);
+}
+
+// ---- no valid support -----------------------------------------------------------------------------------------------
+static void check_fallback() {
+  // (2^53 itself still passes: 2^53 - 1 is a double. From 2^54 on l - 1 rounds back to l for every power of two.)
+  const double two53 = 9007199254740992.0, two54 = 2.0 * two53;
+  int cnt;
+  double sum;
+  // every eigenvalue above 2^53: l - 1 rounds to l, and no index has a valid support
+  const std::vector<std::vector<double>> none = {
+      {two54},
+      {two54, two54 * 2, two54 * 4},
+      {two54 * 8, two54 * 8, two54},                      // the largest twice: the first of them
+      {1e30, 1e300, 1e300, 1e299},
+      {NAN},                                              // a NaN: every comparison with it fails
+      {NAN, two54, two54 * 2, NAN, two54 * 2},            // ... and it is never chosen over a number
+      {NAN, NAN},
+  };
+  const int want[] = {0, 2, 0, 1, 0, 2, 0};
+  for (size_t k = 0; k < none.size(); ++k) {
+    const std::vector<double>& v = none[k];
+    const int n = static_cast<int>(v.size());
+    for (int i = 0; i < n; ++i) CHECK(!sdp_support(v.data(), n, v[static_cast<size_t>(i)], cnt, sum));
+    const int top = sdp_fallback_index(v.data(), n);
+    CHECK(top == want[k]);
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double w = sdp_fallback_weight(i, top);
+      CHECK(w == (i == top ? 1.0 : 0.0));
+      total += w;
+    }
+    CHECK(total == 1.0);
+  }
+  // a NaN among eigenvalues the rule can handle lies outside every support and takes weight 0: the rule applies
+  const double mixed[] = {1.0, NAN, 0.5};
+  CHECK(sdp_support(mixed, 3, 1.0, cnt, sum) && cnt == 1 && sum == 1.0);
+  CHECK(sdp_simplex_weight(mixed[1], sdp_support_tau(sum, cnt)) == 0.0);
+  // just below: at 2^53 l - 1 is exact, the eigenvalue is its own valid support and the rule, not the fallback, applies
+  CHECK(sdp_support(&two53, 1, two53, cnt, sum) && cnt == 1);
+  // where the rule applies and the largest eigenvalue stands alone by more than 1, both give the same weights
+  const double lone[] = {0.25, 3.0, -1.0};
+  CHECK(sdp_support(lone, 3, 3.0, cnt, sum) && cnt == 1 && sdp_fallback_index(lone, 3) == 1);
+  for (int i = 0; i < 3; ++i) CHECK(sdp_simplex_weight(lone[i], sdp_support_tau(sum, cnt)) == sdp_fallback_weight(i, 1));
 }
 
 // ---- the gap test and the tolerances, by hand -----------------------------------------------------------------------
@@ -248,6 +364,8 @@ static void check_rotation() {
 int main() {
   check_simplex_rule();
   check_balancing();
+  check_schedule();
+  check_fallback();
   check_stopping_rule();
   check_rotation();
   std::printf("simplex cases: %d\n", g_simplex_cases);

@@ -21,9 +21,12 @@ from __future__ import annotations
 import numpy as np
 
 RHO0 = 1.0          # the initial penalty
-ADAPT_EVERY = 10    # residual balancing: every ADAPT_EVERY iterations ...
+ADAPT_EVERY = 10    # residual balancing: checked every ADAPT_EVERY iterations at first ...
 ADAPT_MU = 10.0     # ... when one residual exceeds ADAPT_MU times the other ...
-ADAPT_TAU = 2.0     # ... rho is multiplied or divided by ADAPT_TAU (and U divided or multiplied)
+ADAPT_TAU = 2.0     # ... rho is multiplied or divided by ADAPT_TAU (and U divided or multiplied);
+# the interval between checks doubles each time a move reverses the last one (up after down, down after up), so the
+# penalty cannot cycle; a check that moves nothing changes neither the interval nor the remembered direction
+ADAPT_MAX_EVERY = 1 << 30   # (the interval's cap)
 
 
 def symmetric_lower(A: np.ndarray) -> np.ndarray:
@@ -33,11 +36,23 @@ def symmetric_lower(A: np.ndarray) -> np.ndarray:
 
 
 def project_simplex(v: np.ndarray) -> np.ndarray:
-    """tau: the largest k with v_(k) > (sum_{j<=k} v_(j) - 1) / k (v sorted descending); x = max(v - tau, 0)."""
+    """tau: the largest k with v_(k) > (sum_{j<=k} v_(j) - 1) / k (v sorted descending); x = max(v - tau, 0).
+    In exact arithmetic k = 1 always passes (v > v - 1). In fp64 it fails once v - 1 rounds back to v (v past 2^53) or
+    v is not a number; then no k passes, and the projection is weight 1 on the first index of the largest entry (what
+    a scan with a strict > from index 0 finds; a NaN gives way to the first number after it) and 0 elsewhere."""
     u = np.sort(v)[::-1]
     cs = np.cumsum(u)
     k = np.arange(1, v.size + 1)
-    ok = u > (cs - 1.0) / k
+    with np.errstate(invalid="ignore"):
+        ok = u > (cs - 1.0) / k
+    if not ok.any():
+        top = 0
+        for j in range(1, v.size):
+            if v[j] > v[top] or (np.isnan(v[top]) and not np.isnan(v[j])):
+                top = j
+        x = np.zeros(v.size)
+        x[top] = 1.0
+        return x
     K = int(k[ok][-1])
     tau = (cs[K - 1] - 1.0) / K
     return np.maximum(v - tau, 0.0)
@@ -68,6 +83,7 @@ def solve(M, C, max_iters=2000, eps_abs=1e-3, eps_rel=1e-3):
     r_p = r_d = np.inf
     converged = False
     it = 0
+    next_check, interval, last_dir = ADAPT_EVERY, ADAPT_EVERY, 0
     while it < max_iters:
         W = Z - U + M / rho
         lam, Q = np.linalg.eigh(W)
@@ -87,13 +103,19 @@ def solve(M, C, max_iters=2000, eps_abs=1e-3, eps_rel=1e-3):
             if abs(d - p) <= eps_abs + eps_rel * max(abs(d), abs(p)):
                 converged = True
                 break
-        if it % ADAPT_EVERY == 0:
-            if r_p > ADAPT_MU * r_d:
+        if it == next_check:
+            move = 1 if r_p > ADAPT_MU * r_d else (-1 if r_d > ADAPT_MU * r_p else 0)
+            if move > 0:
                 rho *= ADAPT_TAU
                 U /= ADAPT_TAU
-            elif r_d > ADAPT_MU * r_p:
+            elif move < 0:
                 rho /= ADAPT_TAU
                 U *= ADAPT_TAU
+            if move != 0:
+                if last_dir == -move and interval <= ADAPT_MAX_EVERY // 2:
+                    interval *= 2
+                last_dir = move
+            next_check = it + interval
     if not converged:
         d = np.linalg.eigvalsh(M - rho * U)[-1]
     p = float(np.sum(M * X))
