@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_sdp_set_route", "clipper_hip_sdp_route", "clipper_hip_match_descriptors",
     "clipper_hip_estimate_normals", "clipper_hip_compute_fpfh", "clipper_hip_fpfh_from_points",
     "clipper_hip_knn_set_search", "clipper_hip_knn_search", "clipper_hip_knn_last_search",
-    "clipper_hip_icp", "clipper_hip_evaluate_registration",
+    "clipper_hip_icp", "clipper_hip_evaluate_registration", "clipper_hip_voxel_downsample",
 ]
 
 
@@ -250,6 +250,14 @@ class IcpInfo(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class VoxelInfo(C.Structure):
+    """clipper_voxel_info_t: the grid of a voxel_down_sample (voxels per axis), the 8-bit passes of its radix sort, the
+    pairs per workgroup of a pass, the chunk length of the sums (512), the members of the fullest voxel, the device time
+    between two events around the kernels and, of that, the time of the sort's passes."""
+    _fields_ = [("dim", C.c_int32 * 3), ("passes", C.c_int32), ("sort_tile", C.c_int32), ("chunk", C.c_int32),
+                ("max_count", C.c_int32), ("reserved", C.c_int32), ("kernels_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
 class BatchProblem(C.Structure):
     """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
 
@@ -347,6 +355,8 @@ def load_library(path: str = LIB_PATH):
                                   C.POINTER(IcpInfo), dp]
     L.clipper_hip_evaluate_registration.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, dp, C.c_double,
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
+    L.clipper_hip_voxel_downsample.argtypes = [C.c_int, dp, dp, C.c_int64, C.c_double, dp, dp, ip, ip,
+                                               C.POINTER(C.c_int64), C.POINTER(VoxelInfo)]
     L.clipper_hip_set_profiling.argtypes = [vp, C.c_int]
     L.clipper_hip_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.clipper_hip_bench_matvec.argtypes = [vp, C.c_int, dp]
@@ -1173,6 +1183,44 @@ def evaluate_registration(P_src, P_tgt, T=None, max_distance: float = 0.0, devic
         raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
     out = (fit.value, rmse.value, cnt.value)
     return out + (corr[:Ps.shape[1]],) if return_correspondences else out
+
+
+def voxel_down_sample(P, voxel_size: float, N=None, device: int = 0, return_counts: bool = False,
+                      return_trace: bool = False, return_info: bool = False):
+    """clipper_hip_voxel_downsample: one point per occupied voxel of edge voxel_size of the cloud P (3 x n, columns =
+    points as `clipper::Data`), on the device: the centroid of the voxel's points, in ascending cell number
+    (lexicographic in z, y, x; the grid's origin is the cloud's minimum corner). With normals N (3 x n) also the
+    normalised sum of each voxel's normals, (0, 0, 1) where they cancel. Returns P_out (3 x n_out), then in this order
+    N_out (3 x n_out, when N is given), the members per voxel (n_out int32, with return_counts), for every input point
+    its output column (n int32, with return_trace) and the VoxelInfo (with return_info); a tuple when more than one.
+    The result is a function of the inputs alone: tests/voxel_model.py reproduces its bits."""
+    L = load_library()
+    Pc = _cloud(P)
+    n = Pc.shape[1]
+    Nc = None if N is None else _cloud(N, "N")
+    if Nc is not None and Nc.shape[1] != n:
+        raise ValueError("P and N must hold the same number of points")
+    Po = np.zeros((3, max(n, 1)), dtype=np.float64, order="F")
+    No = np.zeros((3, max(n, 1)), dtype=np.float64, order="F") if Nc is not None else None
+    cnt = np.zeros(max(n, 1), dtype=np.int32) if return_counts else None
+    trace = np.zeros(max(n, 1), dtype=np.int32) if return_trace else None
+    n_out, info = C.c_int64(0), VoxelInfo()
+    rc = L.clipper_hip_voxel_downsample(device, _dp(Pc), None if Nc is None else _dp(Nc), n, float(voxel_size), _dp(Po),
+                                        None if No is None else _dp(No), None if cnt is None else _ip(cnt),
+                                        None if trace is None else _ip(trace), C.byref(n_out), C.byref(info))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    m = int(n_out.value)
+    out = [np.asfortranarray(Po[:, :m])]
+    if No is not None:
+        out.append(np.asfortranarray(No[:, :m]))
+    if return_counts:
+        out.append(cnt[:m].copy())
+    if return_trace:
+        out.append(trace[:n].copy())
+    if return_info:
+        out.append(info)
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 class HipBatch:

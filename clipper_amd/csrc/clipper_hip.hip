@@ -4,7 +4,7 @@
 // host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp (the fills, matrix set / get,
 // mat-vecs; the last driver of a context: it holds its kernels' place in the code object), behind it the stand-alone
 // searches: host_knn.hpp (nearest neighbours: both routes and their seam), host_match.hpp (putative associations from
-// feature descriptors), host_features.hpp, host_icp.hpp; host_csc_input.hpp (the sparse input's
+// feature descriptors), host_features.hpp, host_icp.hpp, host_voxel.hpp; host_csc_input.hpp (the sparse input's
 // host-only checks) and the other host_*.hpp, then the extern "C" entry points, which check their arguments and call
 // the internal functions. All arithmetic runs in the kernels of kernels.hip.h; there is no CPU fallback anywhere: if
 // HIP is unusable the entry points return an error.
@@ -65,6 +65,7 @@ using namespace clipper_hip;
 #include "host_match.hpp"
 #include "host_features.hpp"
 #include "host_icp.hpp"
+#include "host_voxel.hpp"
 
 extern "C" {
 
@@ -429,6 +430,14 @@ int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n
                                       const double* T, double max_distance, double* fitness, double* inlier_rmse,
                                       int64_t* count, int32_t* corr_out) try {
   return evaluate_registration(device, P_src, n_src, P_tgt, n_tgt, T, max_distance, fitness, inlier_rmse, count, corr_out);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- voxel down-sampling of a point cloud (host_voxel.hpp) --------------------------------------
+
+int clipper_hip_voxel_downsample(int device, const double* P, const double* N, int64_t n, double voxel_size,
+                                 double* P_out, double* N_out, int32_t* count_out, int32_t* trace_out, int64_t* n_out,
+                                 clipper_voxel_info_t* info) try {
+  return voxel_downsample(device, P, N, n, voxel_size, P_out, N_out, count_out, trace_out, n_out, info);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_set_window(clipper_hip_t* h, int window) try {

@@ -227,6 +227,25 @@ PYBIND11_MODULE(clipperpy, m) {
       "Match feature descriptors (d x n0 and d x n1, one per column, d <= 64) into putative associations on the GPU: "
       "brute-force nearest neighbours with an optional mutual check, ratio test and distance bound.");
 
+  // the step in front of the normals: one point per occupied voxel, on the device
+  m_utils.def(
+      "voxel_down_sample",
+      [](const clipper::MatrixXd& P, double voxel_size, const clipper::MatrixXd& normals, bool return_counts, bool return_trace) {
+        const clipper::registration::VoxelDownSampled r =
+            clipper::registration::voxel_down_sample(P, voxel_size, normals, return_trace);
+        py::list out;
+        out.append(r.points);
+        if (normals.cols() > 0) out.append(r.normals);
+        if (return_counts) out.append(py::array_t<int32_t>(static_cast<py::ssize_t>(r.counts.size()), r.counts.data()));
+        if (return_trace) out.append(py::array_t<int32_t>(static_cast<py::ssize_t>(r.trace.size()), r.trace.data()));
+        return out.size() == 1 ? py::object(out[0]) : py::object(py::tuple(out));
+      },
+      "P"_a, "voxel_size"_a, "normals"_a = clipper::MatrixXd(3, 0), "return_counts"_a = false, "return_trace"_a = false,
+      "One point per occupied voxel of edge voxel_size of the cloud P (3 x n, one point per column) on the GPU: the "
+      "centroid of the voxel's points, in ascending cell number (z, y, x; the origin is the cloud's minimum corner). With "
+      "normals (3 x n) also their normalised sum per voxel; with return_counts the points per voxel, with return_trace "
+      "every input point's output column. The same bits from run to run.");
+
   // the stage in front of the matcher: raw cloud -> normals -> FPFH descriptors, on the device
   m_utils.def(
       "estimate_normals",

@@ -224,6 +224,24 @@ def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool
                                  mutual=mutual, ratio=ratio, max_sqdist=max_sqdist, device=device)
 
 
+def voxel_down_sample(P: np.ndarray, voxel_size: float, normals: np.ndarray | None = None, return_counts: bool = False,
+                      return_trace: bool = False, device: int = 0):
+    """One point per occupied voxel of edge voxel_size, on the GPU (clipper_hip_voxel_downsample): the step in front of
+    estimate_normals. P: n x 3, rows = points. Returns the centroids of the occupied voxels (n_out x 3, in ascending
+    cell number: lexicographic in z, y, x over a grid whose origin is the cloud's minimum corner), then in this order:
+    with `normals` (n x 3) the normalised sum of each voxel's normals (n_out x 3; (0, 0, 1) where they cancel), with
+    return_counts the points per voxel (n_out int32), with return_trace every input point's output row (n int32); a
+    tuple when more than one. The result is a function of the inputs alone: the same bits from run to run."""
+    from . import _abi as abi
+    out = abi.voxel_down_sample(np.asarray(P, dtype=np.float64).T, voxel_size,
+                                N=None if normals is None else np.asarray(normals, dtype=np.float64).T, device=device,
+                                return_counts=return_counts, return_trace=return_trace)
+    out = list(out) if isinstance(out, tuple) else [out]
+    for k in range(1 if normals is None else 2):
+        out[k] = np.ascontiguousarray(out[k].T)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def estimate_normals(P: np.ndarray, knn: int = 16, radius: float = 0.0, viewpoint=None, device: int = 0,
                      search: str | None = None) -> np.ndarray:
     """Unit surface normals of a cloud, on the GPU (clipper_hip_estimate_normals). P: n x 3, rows = points. A point's

@@ -7,7 +7,8 @@
  *        matcher that produces the putative ones, and the stage in front of it: raw cloud ->
  *        normals -> FPFH descriptors, and the step behind it: ICP over the whole clouds (icp,
  *        evaluate_registration). Thin C++ wrappers over the C ABI (include/clipper_hip.h);
- *        match_descriptors, estimate_normals, compute_fpfh, icp and evaluate_registration work on the device.
+ *        match_descriptors, voxel_down_sample, estimate_normals, compute_fpfh, icp and evaluate_registration work on
+ *        the device.
  */
 #pragma once
 
@@ -153,6 +154,54 @@ inline invariants::Data compute_fpfh(const invariants::Data& P, const Neighborho
   if (clipper_hip_fpfh_from_points(device, P.data(), P.cols(), &hn, viewpoint, &hf, F.data(), nullptr))
     throw std::invalid_argument(clipper_hip_last_error());
   return F;
+}
+
+/// What voxel_down_sample returns: one column per occupied voxel, in ascending cell number (lexicographic in z, y, x)
+struct VoxelDownSampled {
+  invariants::Data points;      ///< 3 x n_out: the centroid of each voxel's points
+  invariants::Data normals;     ///< 3 x n_out with normals given (3 x 0 otherwise): the voxel's normals summed and normalised
+  std::vector<int32_t> counts;  ///< n_out: the points per voxel
+  std::vector<int32_t> trace;   ///< n with with_trace (empty otherwise): for every input point its output column
+  int dim[3];                   ///< voxels along x, y, z
+  int passes;                   ///< 8-bit passes of the radix sort
+  int max_count;                ///< the points of the fullest voxel
+  double kernels_ms, sort_ms;   ///< device time of the kernels, and of the sort's passes among them
+};
+
+/// The cloud P (3 x n) cut to one point per occupied voxel of edge voxel_size, on the device
+/// (clipper_hip_voxel_downsample): the step in front of estimate_normals. The grid's origin is the cloud's own minimum
+/// corner. `normals` (3 x n, or empty) are summed per voxel and normalised, (0, 0, 1) where they cancel. The result is
+/// a function of the inputs alone: the same bits from run to run.
+inline VoxelDownSampled voxel_down_sample(const invariants::Data& P, double voxel_size,
+                                          const invariants::Data& normals = invariants::Data(), bool with_trace = false,
+                                          int device = 0) {
+  if (P.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const bool has_normals = normals.cols() > 0;
+  if (has_normals && (normals.rows() != 3 || normals.cols() != P.cols()))
+    throw std::invalid_argument("normals must be 3 x n, one per point");
+  const size_t n = static_cast<size_t>(P.cols()), room = n > 0 ? n : 1;
+  std::vector<double> po(3 * room), no(has_normals ? 3 * room : 0);
+  VoxelDownSampled r{};
+  r.counts.assign(room, 0);
+  if (with_trace) r.trace.assign(room, 0);
+  int64_t n_out = 0;
+  clipper_voxel_info_t info{};
+  if (clipper_hip_voxel_downsample(device, P.data(), has_normals ? normals.data() : nullptr, P.cols(), voxel_size, po.data(),
+                                   has_normals ? no.data() : nullptr, r.counts.data(), with_trace ? r.trace.data() : nullptr,
+                                   &n_out, &info))
+    throw std::invalid_argument(clipper_hip_last_error());
+  r.points = invariants::Data(3, n_out);
+  r.normals = invariants::Data(3, has_normals ? n_out : 0);
+  for (int64_t k = 0; k < 3 * n_out; ++k) r.points.data()[k] = po[static_cast<size_t>(k)];
+  for (int64_t k = 0; has_normals && k < 3 * n_out; ++k) r.normals.data()[k] = no[static_cast<size_t>(k)];
+  r.counts.resize(static_cast<size_t>(n_out));
+  if (with_trace) r.trace.resize(n);
+  for (int a = 0; a < 3; ++a) r.dim[a] = info.dim[a];
+  r.passes = info.passes;
+  r.max_count = info.max_count;
+  r.kernels_ms = info.kernels_ms;
+  r.sort_ms = info.sort_ms;
+  return r;
 }
 
 /// The two metrics of icp

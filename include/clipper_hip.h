@@ -599,6 +599,33 @@ int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n
                                       const double* T, double max_distance, double* fitness, double* inlier_rmse,
                                       int64_t* count, int32_t* corr_out);
 
+/* VOXEL DOWN-SAMPLING: the step in front of the normals, on the device. The cloud P (3 x n column-major as
+ * `clipper::Data`, n >= 0) is cut into cubes of edge voxel_size whose origin is the cloud's own minimum corner lo (the
+ * exact per-axis minimum; not Open3D's min - voxel_size / 2): the voxel of x on axis a is floor((x_a - lo_a) * inv)
+ * with inv = 1.0 / voxel_size, the cell number (v_z * dim_y + v_y) * dim_x + v_x. One output row per occupied voxel, in
+ * ascending cell number (lexicographic in z, y, x): the centroid of the voxel's points and, with normals N (3 x n, may
+ * be NULL; finite), the sum of their normals made a unit vector, (0, 0, 1) where they cancel. Every sum takes a
+ * voxel's members in ascending original index, in chunks of 512 added up one after the other from +0.0 over
+ * (x - lo), the chunk sums in chunk order, and nothing is fused or atomic: the result is a function of the inputs
+ * alone, the same from run to run (the rules in full: clipper_amd/csrc/voxel_rules.hpp).
+ * P_out, N_out (3 x n), count_out (n): room for n rows, the first *n_out are written (count_out: the members per
+ * row); trace_out (n): for every input point its output row. Every output but n_out may be NULL; N_out needs N.
+ * Refused (CLIPPER_HIP_E_INVALID, before any device work): a voxel_size that is not finite and > 0, a non-finite
+ * coordinate or normal, more than 2^21 voxels along an axis, n >= 2^31. Stand-alone: needs no context. */
+typedef struct clipper_voxel_info_t {
+  int32_t dim[3];      /* voxels along x, y, z                                                     */
+  int32_t passes;      /* 8-bit passes of the radix sort: ceil(bitlength(dim_x dim_y dim_z - 1) / 8) */
+  int32_t sort_tile;   /* pairs per workgroup of a sort pass                                       */
+  int32_t chunk;       /* 512                                                                      */
+  int32_t max_count;   /* the members of the fullest voxel                                         */
+  int32_t reserved;
+  double  kernels_ms;  /* between two events around the kernels                                    */
+  double  sort_ms;     /* of that, between two events around the passes of the sort (0 without one) */
+} clipper_voxel_info_t;
+int clipper_hip_voxel_downsample(int device, const double* P, const double* N, int64_t n, double voxel_size,
+                                 double* P_out, double* N_out, int32_t* count_out, int32_t* trace_out, int64_t* n_out,
+                                 clipper_voxel_info_t* info);
+
 /* Line-search window: how many consecutive step sizes alpha, alpha*beta, ... of the
  * backtracking line search (clipper.cpp:234-251) one pass over M evaluates at once. The
  * trial sequence, the accepted trial and the result are those of the reference for every
