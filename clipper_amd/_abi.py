@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_estimate_normals", "clipper_hip_compute_fpfh", "clipper_hip_fpfh_from_points",
     "clipper_hip_knn_set_search", "clipper_hip_knn_search", "clipper_hip_knn_last_search",
     "clipper_hip_icp", "clipper_hip_evaluate_registration", "clipper_hip_voxel_downsample",
+    "clipper_hip_icp_generalized", "clipper_hip_estimate_covariances",
 ]
 
 
@@ -227,7 +228,7 @@ class Neighborhood(C.Structure):
 
 FPFH_DIM = 33  # numbers per FPFH descriptor
 
-ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1  # CLIPPER_ICP_*: clipper_icp_params_t.method
+ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE, ICP_GENERALIZED = 0, 1, 2  # CLIPPER_ICP_*: clipper_icp_params_t.method
 ICP_CONVERGED, ICP_MAX_ITERATIONS, ICP_TOO_FEW, ICP_DEGENERATE = 0, 1, 2, 3  # clipper_icp_info_t.status
 
 
@@ -353,6 +354,9 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_fpfh_from_points.argtypes = [C.c_int, dp, C.c_int64, nbp, dp, nbp, dp, dp]
     L.clipper_hip_icp.argtypes = [C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams), dp,
                                   C.POINTER(IcpInfo), dp]
+    L.clipper_hip_icp_generalized.argtypes = [C.c_int, dp, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams), dp,
+                                              C.POINTER(IcpInfo), dp]
+    L.clipper_hip_estimate_covariances.argtypes = [C.c_int, dp, C.c_int64, nbp, C.c_double, dp, ip]
     L.clipper_hip_evaluate_registration.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, dp, C.c_double,
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
     L.clipper_hip_voxel_downsample.argtypes = [C.c_int, dp, dp, C.c_int64, C.c_double, dp, dp, ip, ip,
@@ -1161,6 +1165,56 @@ def icp(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None,
     hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
     rc = L.clipper_hip_icp(device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1], t0p,
                            C.byref(prm), _dp(T), C.byref(info), _dp(hist))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    info.history = hist[:info.iterations + 1].copy()
+    return T.reshape(4, 4).T.copy(), info
+
+
+def _covariances(Cv, name, n):
+    """per-point covariances as the 6 x n column-major array of the C ABI (each point's six numbers contiguous)"""
+    Cv = np.asarray(Cv, dtype=np.float64)
+    if Cv.ndim != 2 or Cv.shape[0] != 6:
+        raise ValueError(f"{name} must be 6 x n (xx, xy, xz, yy, yz, zz per column)")
+    if Cv.shape[1] != n:
+        raise ValueError(f"{name} must hold one matrix per point")
+    return np.asfortranarray(Cv)
+
+
+def estimate_covariances(P, knn: int = 20, radius: float = 0.0, epsilon: float = 1e-3, device: int = 0,
+                         return_counts: bool = False):
+    """clipper_hip_estimate_covariances: the per-point covariances of generalized ICP for the cloud P (3 x n, columns =
+    points) on the device: I - (1 - epsilon) nv nv^T (eigenvalues epsilon, 1, 1) with nv the normal estimate_normals
+    finds over the same neighbourhood (knn 3..32 the point included, radius > 0 keeps only those within it); the
+    identity below 3 neighbours. Returns C (6 x n: xx, xy, xz, yy, yz, zz per column), with return_counts also the
+    neighbours kept per point (n int32)."""
+    L = load_library()
+    Pc = _cloud(P)
+    n = Pc.shape[1]
+    nb = Neighborhood(knn, radius)
+    Cv = np.zeros((6, n), dtype=np.float64, order="F")
+    cnt = np.zeros(max(n, 1), dtype=np.int32)
+    rc = L.clipper_hip_estimate_covariances(device, _dp(Pc), n, C.byref(nb), float(epsilon), _dp(Cv), _ip(cnt))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return (Cv, cnt[:n]) if return_counts else Cv
+
+
+def icp_generalized(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance: float = 0.0, max_iterations: int = 30,
+                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0):
+    """clipper_hip_icp_generalized: icp with the plane-to-plane metric of generalized ICP over the per-point
+    covariances C_src (6 x n_src) and C_tgt (6 x n_tgt), e.g. estimate_covariances' (positive definite, else refused).
+    P_src, P_tgt: 3 x n, columns = points. Returns (T 4 x 4, info) as icp does."""
+    L = load_library()
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Cs, Ct = _covariances(C_src, "C_src", Ps.shape[1]), _covariances(C_tgt, "C_tgt", Pt.shape[1])
+    t0, t0p = _transform_arg(T_init, "T_init")
+    prm = IcpParams(ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse)
+    T = np.zeros(16, dtype=np.float64)
+    info = IcpInfo()
+    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+    rc = L.clipper_hip_icp_generalized(device, _dp(Ps), _dp(Cs), Ps.shape[1], _dp(Pt), _dp(Ct), Pt.shape[1], t0p,
+                                       C.byref(prm), _dp(T), C.byref(info), _dp(hist))
     if rc < 0:
         raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
     info.history = hist[:info.iterations + 1].copy()

@@ -202,6 +202,25 @@ void pybind_utils(py::module& m) {
         "Maps a flat index k to coordinate of a square nxn symmetric matrix");
 }
 
+// what utils.icp and utils.icp_generalized return: (T 4 x 4, info)
+static py::tuple icp_tuple(const clipper::registration::IcpResult& r) {
+  clipper::MatrixXd T(4, 4), H(3, static_cast<std::ptrdiff_t>(r.history.size()));
+  for (int i = 0; i < 16; ++i) T.data()[i] = r.T[i];
+  for (size_t k = 0; k < r.history.size(); ++k)
+    for (int c = 0; c < 3; ++c) H.data()[3 * k + c] = r.history[k][c];
+  py::dict info;
+  info["iterations"] = r.iterations;
+  info["status"] = static_cast<int>(r.status);
+  info["count"] = r.count;
+  info["fitness"] = r.fitness;
+  info["inlier_rmse"] = r.inlier_rmse;
+  info["route"] = static_cast<int>(r.route);
+  info["candidates"] = r.candidates;
+  info["device_ms"] = r.device_ms;
+  info["history"] = py::cast(H).attr("T");  // (iterations + 1) x 3: count, fitness, rmse
+  return py::make_tuple(T, info);
+}
+
 PYBIND11_MODULE(clipperpy, m) {
   m.doc() = "A graph-theoretic framework for robust data association (MI355X hot path)";
   m.attr("__version__") = CLIPPER_VERSION;
@@ -282,21 +301,7 @@ PYBIND11_MODULE(clipperpy, m) {
         prm.rel_fitness = rel_fitness;
         prm.rel_rmse = rel_rmse;
         const reg::IcpResult r = reg::icp(src, tgt, prm, T_init.data(), normals);
-        clipper::MatrixXd T(4, 4), H(3, static_cast<std::ptrdiff_t>(r.history.size()));
-        for (int i = 0; i < 16; ++i) T.data()[i] = r.T[i];
-        for (size_t k = 0; k < r.history.size(); ++k)
-          for (int c = 0; c < 3; ++c) H.data()[3 * k + c] = r.history[k][c];
-        py::dict info;
-        info["iterations"] = r.iterations;
-        info["status"] = static_cast<int>(r.status);
-        info["count"] = r.count;
-        info["fitness"] = r.fitness;
-        info["inlier_rmse"] = r.inlier_rmse;
-        info["route"] = static_cast<int>(r.route);
-        info["candidates"] = r.candidates;
-        info["device_ms"] = r.device_ms;
-        info["history"] = py::cast(H).attr("T");  // (iterations + 1) x 3: count, fitness, rmse
-        return py::make_tuple(T, info);
+        return icp_tuple(r);
       },
       "src"_a, "tgt"_a, "T_init"_a, "method"_a = "point", "normals"_a = clipper::MatrixXd(3, 0), "max_distance"_a = 0.0,
       "max_iterations"_a = 30, "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6,
@@ -304,6 +309,36 @@ PYBIND11_MODULE(clipperpy, m) {
       "\"point\", or \"plane\" over the target's unit normals (3 x n_tgt). Returns (T, info): info holds iterations, status "
       "(0 converged, 1 max iterations, 2 too few inliers, 3 degenerate), count, fitness, inlier_rmse, route, candidates, "
       "device_ms and history ((iterations + 1) x 3: count, fitness, rmse).");
+  // generalized ICP: the covariances of a cloud, and the refinement over them
+  m_utils.def(
+      "estimate_covariances",
+      [](const clipper::MatrixXd& P, int knn, double radius, double epsilon) {
+        return clipper::registration::estimate_covariances(P, clipper::registration::Neighborhood{knn, radius}, epsilon);
+      },
+      "P"_a, "knn"_a = 20, "radius"_a = 0.0, "epsilon"_a = 1e-3,
+      "Per-point covariances (6 x n: xx, xy, xz, yy, yz, zz per column) of the cloud P (3 x n) on the GPU for "
+      "icp_generalized: I - (1 - epsilon) n n^T over the normal n of the point's knn nearest points (itself included; "
+      "with radius > 0 only those within it); the identity below 3 neighbours.");
+  m_utils.def(
+      "icp_generalized",
+      [](const clipper::MatrixXd& src, const clipper::MatrixXd& src_cov, const clipper::MatrixXd& tgt,
+         const clipper::MatrixXd& tgt_cov, const clipper::MatrixXd& T_init, double max_distance, int max_iterations,
+         double rel_fitness, double rel_rmse) {
+        namespace reg = clipper::registration;
+        if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
+        reg::IcpParams prm;
+        prm.method = reg::IcpMethod::Generalized;
+        prm.max_distance = max_distance;
+        prm.max_iterations = max_iterations;
+        prm.rel_fitness = rel_fitness;
+        prm.rel_rmse = rel_rmse;
+        const reg::IcpResult r = reg::icp_generalized(src, src_cov, tgt, tgt_cov, prm, T_init.data());
+        return icp_tuple(r);
+      },
+      "src"_a, "src_cov"_a, "tgt"_a, "tgt_cov"_a, "T_init"_a, "max_distance"_a = 0.0, "max_iterations"_a = 30,
+      "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6,
+      "Generalized ICP on the GPU: refine the alignment T_init (4 x 4) of src onto tgt (3 x n) with the plane-to-plane "
+      "metric over the clouds' covariances (6 x n, e.g. estimate_covariances'). Returns (T, info) as icp does.");
   m_utils.def(
       "evaluate_registration",
       [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T, double max_distance) {

@@ -1,5 +1,6 @@
-// host_icp.hpp — the driver of clipper_hip_icp and clipper_hip_evaluate_registration ("ICP over a
-// kept search grid"). Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
+// host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized and clipper_hip_evaluate_registration
+// ("ICP over a kept search grid" and "Generalized ICP"), and of clipper_hip_estimate_covariances,
+// the stage that makes the generalized metric's covariances. Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
 // built once and queried every iteration with k_knn_grid<1>; the source is binned by the target's grid once, at
 // T_init, and keeps that order for all iterations (a locality hint, never a correctness input: the lists go to the
 // rows of the original indices). T, the sums, the history and the candidate count stay on the device during the loop;
@@ -25,29 +26,32 @@ struct IcpHostState {
 };
 
 template <int METHOD>
-void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt, int32_t nt,
-               double d2, const double (&o)[3], double* dpart, int32_t nb, const IcpStop& stop, int k, double* dsums, double* dT,
-               IcpRecord* drec, double* dhist, hipStream_t st) {
-  hipLaunchKernelGGL((k_icp_accumulate<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt, dNt, nt,
-                     d2, o[0], o[1], o[2], dpart);
+void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt,
+               const double* dCs, const double* dCt, int32_t nt, double d2, const double (&o)[3], double* dpart, int32_t nb,
+               const IcpStop& stop, int k, double* dsums, double* dT, IcpRecord* drec, double* dhist, hipStream_t st) {
+  hipLaunchKernelGGL((k_icp_accumulate<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt, dNt,
+                     dCs, dCt, dT, nt, d2, o[0], o[1], o[2], dpart);
   hipLaunchKernelGGL((k_icp_step<METHOD>), dim3(1), dim3(256), 0, st, dpart, nb, stop, k, o[0], o[1], o[2], dsums, dT, drec,
                      dhist);
 }
 
 // Every argument has been checked. T0: column-major 4 x 4. history: (max_iterations + 1) x 3 or null; corr_out: ns or null.
-int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, int64_t nt_, const double* T0,
-            const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info, double* history, int32_t* corr_out) {
+// Nt: the target's normals (point-to-plane alone); Cs, Ct: the covariances of the source and the target, 6 x n
+// (generalized alone): uploaded once each.
+int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, const double* Cs, const double* Ct,
+            int64_t nt_, const double* T0, const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info,
+            double* history, int32_t* corr_out) {
   if (int rc = use_device(device)) return rc;
 
   const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
-  const bool plane = prm.method == ICP_POINT_TO_PLANE;
+  const bool plane = prm.method == ICP_POINT_TO_PLANE, gen = prm.method == ICP_GENERALIZED;
   const int terms = icp_terms(prm.method);
   const int32_t nb = static_cast<int32_t>(ceil_div(ns, ICP_BLOCK));
   const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
   const size_t nrows = static_cast<size_t>(prm.max_iterations) + 1;
   const int route = knn_route(g_knn_search.load(), 3, ns, nt);
 
-  double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr,
+  double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dCs = nullptr, *dCt = nullptr, *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr,
          *dT = nullptr, *dhist = nullptr;
   int32_t *oi = nullptr, *perm = nullptr, *visited = nullptr;
   unsigned long long* dsum = nullptr;
@@ -65,6 +69,8 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     if (int rc = knn_brute_alloc(device, 1, ns, nt, bs, tmp)) return rc;
   if (int rc = tmp.alloc(device, perm, s1 * sizeof(int32_t), visited, s1 * sizeof(int32_t), dsum, sizeof(unsigned long long)))
     return rc;
+  if (gen)  // (behind the buffers every method has: theirs keep their places)
+    if (int rc = tmp.alloc(device, dCs, s1 * 6 * sizeof(double), dCt, static_cast<size_t>(nt) * 6 * sizeof(double))) return rc;
   HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hs.rec), sizeof(IcpRecord)));
   HIPCHK(hipEventCreate(&hs.a));
   HIPCHK(hipEventCreate(&hs.b));
@@ -76,6 +82,10 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   HIPCHK(hipMemcpyAsync(dPs, Ps, s3 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dPt, Pt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
   if (plane) HIPCHK(hipMemcpyAsync(dNt, Nt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (gen) {
+    HIPCHK(hipMemcpyAsync(dCs, Cs, s1 * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dCt, Ct, static_cast<size_t>(nt) * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipMemcpyAsync(dT, T0, 16 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(drec, hs.rec, sizeof(IcpRecord), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dhist, 0, nrows * 3 * sizeof(double), st));
@@ -121,10 +131,12 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     } else if (int rc = knn_brute_query(1, 3, dq, ns, dPt, nt, bs, od, oi, st)) {
       return rc;
     }
-    if (plane)
-      icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    if (gen)
+      icp_round<ICP_GENERALIZED>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    else if (plane)
+      icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
     else
-      icp_round<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+      icp_round<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
     HIPCHK(hipMemcpyAsync(hs.rec, drec, sizeof(IcpRecord), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));  // the one wait of an iteration
     if (hs.rec->status != ICP_RUNNING || k >= prm.max_iterations) break;
@@ -171,13 +183,76 @@ int icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, con
                                            params->rel_rmse}
                               : ci::Params{0, 0, 0.0, 0.0, 0.0};
   std::string why = !T_out ? "null T_out" : "";
+  if (why.empty()) why = ci::check_not_generalized(params ? &h : nullptr);
   if (why.empty()) why = ci::check_params(params ? &h : nullptr);
   if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
   if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
   if (why.empty()) why = ci::check_transform("T_init", T_init);
   if (why.empty()) why = ci::check_target_normals(h.method, N_tgt, n_tgt);
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp: %s", why.c_str());
-  return icp_run(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info, history, nullptr);
+  return icp_run(device, P_src, n_src, P_tgt, N_tgt, nullptr, nullptr, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
+                 history, nullptr);
+}
+
+int icp_generalized(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt, const double* C_tgt,
+                    int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
+                    clipper_icp_info_t* info, double* history) {
+  namespace ci = clipper_icp;
+  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
+                                           params->rel_rmse}
+                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  std::string why = !T_out ? "null T_out" : "";
+  if (why.empty()) why = ci::check_generalized_params(params ? &h : nullptr);
+  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
+  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
+  if (why.empty()) why = ci::check_transform("T_init", T_init);
+  if (why.empty()) why = ci::check_covariances("source", C_src, n_src);
+  if (why.empty()) why = ci::check_covariances("target", C_tgt, n_tgt);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_generalized: %s", why.c_str());
+  return icp_run(device, P_src, n_src, P_tgt, nullptr, C_src, C_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
+                 history, nullptr);
+}
+
+// The covariances of the generalized metric: host_features.hpp's features_run with the one kernel behind the search
+// changed. Every argument has been checked.
+int covariances_run(int device, const double* P, int64_t n, const clipper_features::Neighborhood& nb, double epsilon,
+                    double* C_out, int32_t* count_out) {
+  if (int rc = use_device(device)) return rc;
+
+  const int K = clipper_features::list_k(nb.knn);
+  const size_t n3 = static_cast<size_t>(n) * 3, n6 = static_cast<size_t>(n) * 6;
+  const size_t no = static_cast<size_t>(n) * K, nn = static_cast<size_t>(n);
+  double *dP = nullptr, *dC = nullptr, *od = nullptr;
+  int32_t *oi = nullptr, *dcn = nullptr;
+  DevTemps tmp;
+  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dC, n6 * sizeof(double), od, no * sizeof(double),
+                         oi, no * sizeof(int32_t), dcn, nn * sizeof(int32_t)))
+    return rc;
+  hipStream_t st = nullptr;  // the default stream: a stand-alone call
+  if (int rc = copy_up(dP, P, n3, st)) return rc;
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
+  const int use_r = nb.radius > 0.0;
+  const double w = 1.0 - epsilon;
+  hipLaunchKernelGGL(k_icp_covariances<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
+                     nb.knn, use_r, nb.radius * nb.radius, w, dC, dcn);
+  if (int rc = copy_down(C_out, dC, n6, st)) return rc;
+  if (int rc = copy_down(count_out, dcn, nn, st)) return rc;
+  HIPCHK(hipStreamSynchronize(st));  // the one wait of the call
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int estimate_covariances(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb, double epsilon,
+                         double* C_out, int32_t* count_out) {
+  namespace cf = clipper_features;
+  const cf::Neighborhood h = feat_nb(nb);
+  std::string why = !P ? "null point array" : (!C_out ? "null covariance output array" : "");
+  if (why.empty()) why = cf::check_neighborhood("neighbourhood", nb ? &h : nullptr);
+  if (why.empty()) why = clipper_icp::check_epsilon(epsilon);
+  if (why.empty()) why = cf::check_count(n);
+  if (why.empty()) why = cf::check_points(P, n);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "estimate_covariances: %s", why.c_str());
+  return covariances_run(device, P, n, h, epsilon, C_out, count_out);
 }
 
 int evaluate_registration(int device, const double* P_src, int64_t n_src, const double* P_tgt, int64_t n_tgt, const double* T,
@@ -190,7 +265,8 @@ int evaluate_registration(int device, const double* P_src, int64_t n_src, const 
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "evaluate_registration: %s", why.c_str());
   const ci::Params h{ICP_POINT_TO_POINT, 0, max_distance, 0.0, 0.0};
   clipper_icp_info_t info{};
-  if (int rc = icp_run(device, P_src, n_src, P_tgt, nullptr, n_tgt, T ? T : ICP_IDENTITY, h, nullptr, &info, nullptr, corr_out))
+  if (int rc = icp_run(device, P_src, n_src, P_tgt, nullptr, nullptr, nullptr, n_tgt, T ? T : ICP_IDENTITY, h, nullptr, &info,
+                       nullptr, corr_out))
     return rc;
   if (fitness) *fitness = info.fitness;
   if (inlier_rmse) *inlier_rmse = info.inlier_rmse;

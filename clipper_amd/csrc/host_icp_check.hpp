@@ -1,6 +1,6 @@
 // host_icp_check.hpp — ICP and the evaluation of a registration, the part that needs no device: the argument checks of
-// clipper_hip_icp and clipper_hip_evaluate_registration. Pure host code (no HIP): tests/cpp/test_icp_rules.cpp compiles
-// it with g++ alone. A refusal comes back as its message (empty: accepted) and names the offending value; the caller
+// clipper_hip_icp, clipper_hip_icp_generalized, clipper_hip_estimate_covariances and clipper_hip_evaluate_registration.
+// Pure host code (no HIP): tests/cpp/test_icp_rules.cpp and tests/cpp/test_gicp_rules.cpp compile it with g++ alone. A refusal comes back as its message (empty: accepted) and names the offending value; the caller
 // hands it to fail(). Every check runs before any device work.
 #pragma once
 
@@ -50,16 +50,64 @@ inline std::string check_max_distance(double d) {
   return {};
 }
 
-inline std::string check_params(const Params* p) {
-  if (!p) return "null params";
-  if (p->method != clipper_hip::ICP_POINT_TO_POINT && p->method != clipper_hip::ICP_POINT_TO_PLANE)
-    return format("unknown method %d", p->method);
+// what every method asks of the parameters besides the method itself
+inline std::string check_loop_params(const Params* p) {
   std::string why = check_max_distance(p->max_distance);
   if (!why.empty()) return why;
   if (p->max_iterations < 0 || p->max_iterations > clipper_hip::ICP_MAX_ITERATIONS_LIMIT)
     return format("max_iterations must be in 0..%d (max_iterations = %d)", clipper_hip::ICP_MAX_ITERATIONS_LIMIT, p->max_iterations);
   if (!(p->rel_fitness >= 0.0)) return format("rel_fitness must be at least 0 (rel_fitness = %g)", p->rel_fitness);
   if (!(p->rel_rmse >= 0.0)) return format("rel_rmse must be at least 0 (rel_rmse = %g)", p->rel_rmse);
+  return {};
+}
+
+// the parameters of clipper_hip_icp and clipper_hip_evaluate_registration: point-to-point or point-to-plane
+inline std::string check_params(const Params* p) {
+  if (!p) return "null params";
+  if (p->method != clipper_hip::ICP_POINT_TO_POINT && p->method != clipper_hip::ICP_POINT_TO_PLANE)
+    return format("unknown method %d", p->method);
+  return check_loop_params(p);
+}
+
+// clipper_hip_icp has no covariances to give the generalized metric: it names the call that takes them
+inline std::string check_not_generalized(const Params* p) {
+  if (p && p->method == clipper_hip::ICP_GENERALIZED)
+    return "method 2 (generalized) takes per-point covariances: call clipper_hip_icp_generalized";
+  return {};
+}
+
+// the parameters of clipper_hip_icp_generalized: that method alone
+inline std::string check_generalized_params(const Params* p) {
+  if (!p) return "null params";
+  if (p->method != clipper_hip::ICP_GENERALIZED)
+    return format("method must be CLIPPER_ICP_GENERALIZED (2) (method = %d)", p->method);
+  return check_loop_params(p);
+}
+
+// epsilon of clipper_hip_estimate_covariances: the eigenvalue along the normal, in (0, 1]
+inline std::string check_epsilon(double epsilon) {
+  if (!(epsilon > 0.0 && epsilon <= 1.0)) return format("epsilon must be in (0, 1] (epsilon = %g)", epsilon);
+  return {};
+}
+
+// C: 6 x n (xx, xy, xz, yy, yz, zz per point), every entry finite and every matrix positive definite: its three leading
+// minors > 0, evaluated in fp64 as written (the third is the determinant of icp_generalized_terms). `what`: "source",
+// "target"
+inline std::string check_covariances(const char* what, const double* C, int64_t n) {
+  if (!C) return format("null %s covariance array", what);
+  for (int64_t p = 0; p < n; ++p) {
+    const double* c = C + p * 6;
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(c[k]))
+        return format("%s covariances: non-finite value at entry %d of point %lld", what, k, static_cast<long long>(p));
+    const double s00 = c[0], s01 = c[1], s02 = c[2], s11 = c[3], s12 = c[4], s22 = c[5];
+    const double k00 = s11 * s22 - s12 * s12, k01 = s02 * s12 - s01 * s22, k02 = s01 * s12 - s02 * s11;
+    const double minor[3] = {s00, s00 * s11 - s01 * s01, (s00 * k00 + s01 * k01) + s02 * k02};
+    for (int k = 0; k < 3; ++k)
+      if (!(minor[k] > 0.0))
+        return format("%s covariances: the matrix of point %lld is not positive definite (leading minor %d = %.17g)", what,
+                      static_cast<long long>(p), k + 1, minor[k]);
+  }
   return {};
 }
 

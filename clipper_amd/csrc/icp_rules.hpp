@@ -1,12 +1,14 @@
 // icp_rules.hpp — the rules of the ICP refinement ("ICP over a kept search grid"), stated once for
 // the kernels (k_icp.hip.h), the driver (host_icp.hpp) and the host: the transform of a point, which list entry is an
-// inlier, the origin the sums are taken about, the terms one source point adds (point-to-point: 17, point-to-plane: 30),
-// the order in which they are added, the step of either method (the rotation of a 3 x 3 cross-covariance; LDL^T of the
-// 6 x 6 normal equations and the Cayley map), the update of T and the stop rule. Plain sequential functions of one
+// inlier, the origin the sums are taken about, the terms one source point adds (point-to-point: 17, point-to-plane and
+// generalized: 30), the order in which they are added, the step of each method (the rotation of a 3 x 3 cross-covariance;
+// LDL^T of the 6 x 6 normal equations and the Cayley map), the update of T and the stop rule; for the generalized
+// (plane-to-plane) metric also the regularised covariance of a point. Plain sequential functions of one
 // point, one set of sums or one iteration: which work item holds what belongs to the kernels. Every expression rounds as
 // written (the build runs with -ffp-contract=off), no floating-point atomics anywhere, so that T_out and the history
 // are functions of the inputs alone. No HIP: builds with g++ as well (tests/cpp/test_icp_rules.cpp runs whole ICPs over
-// this header); tests/icp_model.py restates the same contract in numpy.
+// this header, tests/cpp/test_gicp_rules.cpp generalized ones); tests/icp_model.py and tests/gicp_model.py restate the
+// same contract in numpy.
 #pragma once
 
 #include <math.h>
@@ -18,7 +20,7 @@
 
 namespace clipper_hip {
 
-constexpr int ICP_POINT_TO_POINT = 0, ICP_POINT_TO_PLANE = 1;                             // clipper_icp_params_t.method
+constexpr int ICP_POINT_TO_POINT = 0, ICP_POINT_TO_PLANE = 1, ICP_GENERALIZED = 2;        // clipper_icp_params_t.method
 constexpr int ICP_RUNNING = -1;                                                            // the record's status between rounds
 constexpr int ICP_CONVERGED = 0, ICP_MAX_ITERATIONS = 1, ICP_TOO_FEW = 2, ICP_DEGENERATE = 3;  // clipper_icp_info_t.status
 constexpr int ICP_MAX_ITERATIONS_LIMIT = 1000;
@@ -28,7 +30,11 @@ constexpr int ICP_BLOCK = 256;  // source points per workgroup of the sums: one 
 constexpr int ICP_POINT_TERMS = 17;
 // count, the 21 upper entries of J^T J row by row, the 6 of J^T r, sum r^2, sum sqd. (1 + 21 + 6 + 1 + 1 = 30.)
 constexpr int ICP_PLANE_TERMS = 30;
-constexpr int icp_terms(int method) { return method == ICP_POINT_TO_PLANE ? ICP_PLANE_TERMS : ICP_POINT_TERMS; }
+// the generalized metric fills point-to-plane's positions: count, the 21 upper entries of J^T M J row by row, the 6 of
+// J^T M d, d^T M d, sum sqd
+constexpr int ICP_GENERALIZED_TERMS = ICP_PLANE_TERMS;
+constexpr int icp_terms(int method) { return method == ICP_POINT_TO_POINT ? ICP_POINT_TERMS : ICP_PLANE_TERMS; }
+// (generalized: 3, every pair gives three equations; the pivot test decides the rest)
 constexpr int icp_min_count(int method) { return method == ICP_POINT_TO_PLANE ? 6 : 3; }
 
 // The rank threshold of the point-to-plane system: DEGENERATE when a pivot of LDL^T is <= ICP_RANK_TOL times the largest
@@ -86,6 +92,122 @@ ICP_HD void icp_plane_terms(const double (&q)[3], const double (&b)[3], const do
     for (int j = i; j < 6; ++j) t[at++] = J[i] * J[j];
   for (int i = 0; i < 6; ++i) t[22 + i] = J[i] * r;
   t[28] = r * r;
+  t[29] = sqd;
+}
+
+// ---- the generalized metric: the covariance of a point ---------------------------------------------------------------
+// C = I - (1 - epsilon) nv nv^T of the unit vector nv: the eigenvalues (epsilon, 1, 1), epsilon along nv (Segal et
+// al.'s plane-to-plane regularisation). w = 1.0 - epsilon, evaluated once by the caller. c = (xx, xy, xz, yy, yz, zz),
+// feat_covariance's order. The sign of nv cancels in every product.
+ICP_HD void icp_covariance_of_normal(const double (&nv)[3], double w, double (&c)[6]) {
+  c[0] = 1.0 - w * (nv[0] * nv[0]);
+  c[1] = 0.0 - w * (nv[0] * nv[1]);
+  c[2] = 0.0 - w * (nv[0] * nv[2]);
+  c[3] = 1.0 - w * (nv[1] * nv[1]);
+  c[4] = 0.0 - w * (nv[1] * nv[2]);
+  c[5] = 1.0 - w * (nv[2] * nv[2]);
+}
+
+// The covariance of a point from its cnt kept neighbours (features_rules.hpp's neighbourhood, covariance and smallest
+// eigenvector; no sign rule): the identity below three, under which the point weighs as in point-to-point.
+template <class Get>
+ICP_HD void icp_point_covariance(int cnt, Get get, double w, double (&c)[6]) {
+  if (cnt < 3) {
+    c[0] = 1.0;
+    c[1] = 0.0;
+    c[2] = 0.0;
+    c[3] = 1.0;
+    c[4] = 0.0;
+    c[5] = 1.0;
+    return;
+  }
+  double s[6], nv[3];
+  feat_covariance(cnt, get, s);
+  feat_smallest_eigenvector(s, nv, nullptr);
+  icp_covariance_of_normal(nv, w, c);
+}
+
+// ---- the generalized metric: the terms of one inlier ---------------------------------------------------------------------
+// ca: the covariance of the source point, cb: of its target point (xx, xy, xz, yy, yz, zz); T: the current transform
+// (column-major 4 x 4), R its upper-left 3 x 3. In this order, every sum of three products (u0 v0 + u1 v1) + u2 v2:
+//   X = R C_a (9 entries), Y = X R^T (the upper triangle), S = C_b + Y (six entries: symmetric by construction);
+//   M = S^-1 by the adjugate: the six cofactors k, det = (s00 k00 + s01 k01) + s02 k02, m = k / det (six divisions);
+//   d = q - b, qo = q - o, J = [-[qo]x, I3] (3 x 6): the same xi = (w, v) about o as point-to-plane, whose row is n^T J;
+//   G = M J (3 x 6): row r is (qo x m_r, m_r), m_r the row r of M;
+//   H = J^T G (6 x 6, the upper entries): column j of H is (qo x g_j, g_j), g_j the column j of G;
+//   e = M d, J^T e = (qo x e, e), d^T M d = d . e.
+// A singular S needs no rule of its own: det rounds to 0 (or is not a number), the divisions leave non-numbers in the
+// sums, and the pivot test of icp_step_plane (d > tol * big is false for a non-number) ends the call DEGENERATE with
+// the previous T.
+ICP_HD void icp_generalized_terms(const double (&q)[3], const double (&b)[3], const double (&ca)[6], const double (&cb)[6],
+                                  const double* T, double sqd, const double (&o)[3], double (&t)[ICP_GENERALIZED_TERMS]) {
+  const double R[3][3] = {{T[0], T[4], T[8]}, {T[1], T[5], T[9]}, {T[2], T[6], T[10]}};
+  const double A[3][3] = {{ca[0], ca[1], ca[2]}, {ca[1], ca[3], ca[4]}, {ca[2], ca[4], ca[5]}};
+  double X[3][3];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int r = 0; r < 3; ++r)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 0; c < 3; ++c) X[r][c] = (R[r][0] * A[0][c] + R[r][1] * A[1][c]) + R[r][2] * A[2][c];
+  const double s00 = cb[0] + ((X[0][0] * R[0][0] + X[0][1] * R[0][1]) + X[0][2] * R[0][2]);
+  const double s01 = cb[1] + ((X[0][0] * R[1][0] + X[0][1] * R[1][1]) + X[0][2] * R[1][2]);
+  const double s02 = cb[2] + ((X[0][0] * R[2][0] + X[0][1] * R[2][1]) + X[0][2] * R[2][2]);
+  const double s11 = cb[3] + ((X[1][0] * R[1][0] + X[1][1] * R[1][1]) + X[1][2] * R[1][2]);
+  const double s12 = cb[4] + ((X[1][0] * R[2][0] + X[1][1] * R[2][1]) + X[1][2] * R[2][2]);
+  const double s22 = cb[5] + ((X[2][0] * R[2][0] + X[2][1] * R[2][1]) + X[2][2] * R[2][2]);
+  const double k00 = s11 * s22 - s12 * s12, k01 = s02 * s12 - s01 * s22, k02 = s01 * s12 - s02 * s11;
+  const double k11 = s00 * s22 - s02 * s02, k12 = s01 * s02 - s00 * s12, k22 = s00 * s11 - s01 * s01;
+  const double det = (s00 * k00 + s01 * k01) + s02 * k02;
+  const double m00 = k00 / det, m01 = k01 / det, m02 = k02 / det, m11 = k11 / det, m12 = k12 / det, m22 = k22 / det;
+  const double M[3][3] = {{m00, m01, m02}, {m01, m11, m12}, {m02, m12, m22}};
+  const double qo[3] = {q[0] - o[0], q[1] - o[1], q[2] - o[2]};
+  const double d[3] = {q[0] - b[0], q[1] - b[1], q[2] - b[2]};
+  double G[3][6];  // M J
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int r = 0; r < 3; ++r) {
+    double x[3];
+    feat_cross(qo, M[r], x);
+    for (int a = 0; a < 3; ++a) {
+      G[r][a] = x[a];
+      G[r][3 + a] = M[r][a];
+    }
+  }
+  double H[6][6];  // J^T (M J): the entries with i <= j are used
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < 6; ++j) {
+    const double g[3] = {G[0][j], G[1][j], G[2][j]};
+    double x[3];
+    feat_cross(qo, g, x);
+    for (int a = 0; a < 3; ++a) {
+      H[a][j] = x[a];
+      H[3 + a][j] = g[a];
+    }
+  }
+  const double e[3] = {feat_dot(M[0], d), feat_dot(M[1], d), feat_dot(M[2], d)};
+  double x[3];
+  feat_cross(qo, e, x);
+  t[0] = 1.0;
+  int at = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 6; ++i)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = i; j < 6; ++j) t[at++] = H[i][j];
+  for (int a = 0; a < 3; ++a) {
+    t[22 + a] = x[a];
+    t[25 + a] = e[a];
+  }
+  t[28] = feat_dot(d, e);
   t[29] = sqd;
 }
 
@@ -211,7 +333,7 @@ ICP_HD bool icp_step_point(const double* S, const double (&o)[3], double* dT) {
   return fabs(icp_det3(R) - 1.0) <= ICP_DET_TOL;
 }
 
-// ---- the step, point-to-plane ---------------------------------------------------------------------------------------
+// ---- the step, point-to-plane and generalized: the 6 x 6 step ----------------------------------------------------------
 // the Cayley map of the rotation vector w: a = w / 2, K = skew(a), R = I + 2 / (1 + |a|^2) (K + K^2), K^2 = a a^T - |a|^2 I.
 // An exact rotation for every w, and no sin or cos.
 ICP_HD void icp_cayley(const double (&w)[3], double* R) {
@@ -224,8 +346,9 @@ ICP_HD void icp_cayley(const double (&w)[3], double* R) {
       R[r * 3 + c] = (r == c ? 1.0 : 0.0) + s * (K[r * 3 + c] + (a[r] * a[c] - (r == c ? aa : 0.0)));
 }
 
-// S: the 30 sums. J^T J xi = -J^T r by LDL^T without pivoting; every loop runs in ascending order of its index.
-// false: DEGENERATE (a pivot <= ICP_RANK_TOL * the largest diagonal entry, or not a number).
+// S: the 30 sums. J^T J xi = -J^T r (generalized: J^T M J xi = -J^T M d, in the same positions) by LDL^T without
+// pivoting; every loop runs in ascending order of its index. false: DEGENERATE (a pivot <= ICP_RANK_TOL * the largest
+// diagonal entry, or not a number).
 ICP_HD bool icp_step_plane(const double* S, const double (&o)[3], double* dT) {
   double A[6][6], L[6][6], D[6], y[6], x[6];
   int at = 1;
@@ -350,7 +473,7 @@ ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (
   else if (k >= p.max_iterations) status = ICP_MAX_ITERATIONS;
   else {
     double dT[16], N[16];
-    const bool ok = METHOD == ICP_POINT_TO_PLANE ? icp_step_plane(S, o, dT) : icp_step_point(S, o, dT);
+    const bool ok = METHOD == ICP_POINT_TO_POINT ? icp_step_point(S, o, dT) : icp_step_plane(S, o, dT);
     for (int i = 0; i < 16; ++i) N[i] = T[i];
     icp_compose(dT, N);
     bool finite = true;

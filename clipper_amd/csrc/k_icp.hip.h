@@ -6,12 +6,14 @@
 //                        T, to row idx of q (n x 3) and, for the grid route, to place `place` of the binned queries
 //   k_icp_order          the permutation of a binned cloud (place -> original index), taken once at T_init
 //   k_icp_accumulate<M>  thread = source point i in its original order: the list entry, q, the target point (and
-//                        normal), the terms, the halving tree in LDS, one partial per workgroup. The tree runs over
-//                        LDS rows of one term each, 8 terms at a time, so that a workgroup holds 16 KiB of LDS whatever
-//                        the method.
+//                        normal; generalized: the two covariances and the rotation of the device's T), the terms,
+//                        the halving tree in LDS, one partial per workgroup. The tree runs over LDS rows of one term
+//                        each, 8 terms at a time, so that a workgroup holds 16 KiB of LDS whatever the method.
 //   k_icp_step<M>        one workgroup: thread t adds partials t, t + 256, ... per term, the same tree; thread 0 runs
 //                        icp_iterate (the step, the stop test, the update of T) and writes the record and the
 //                        history row. T stays on the device.
+//   k_icp_covariances    thread = one point, as k_feat_normals: the neighbourhood's covariance, its smallest
+//                        eigenvector in registers, the six entries of I - (1 - epsilon) nv nv^T
 // No floating-point atomics: every sum has one order.
 #pragma once
 
@@ -85,13 +87,15 @@ __device__ inline void icp_block_fold(const double (&v)[TERMS], double* __restri
 }
 
 // oi / od: the K = 1 lists (n_src entries); q: the transformed source (n_src x 3); B / Nb: the target and its normals
-// (n_tgt x 3; Nb unused for point-to-point); part: gridDim.x x TERMS
+// (n_tgt x 3; Nb for point-to-plane alone); Ca / Cb / T: the covariances of the source and the target (n x 6) and the
+// current transform (generalized alone); part: gridDim.x x TERMS
 template <int METHOD>
 __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restrict__ oi, const double* __restrict__ od,
                                                          const double* __restrict__ q, int32_t n_src,
                                                          const double* __restrict__ B, const double* __restrict__ Nb,
-                                                         int32_t n_tgt, double d2, double o0, double o1, double o2,
-                                                         double* __restrict__ part) {
+                                                         const double* __restrict__ Ca, const double* __restrict__ Cb,
+                                                         const double* __restrict__ T, int32_t n_tgt, double d2, double o0,
+                                                         double o1, double o2, double* __restrict__ part) {
   constexpr int TERMS = icp_terms(METHOD);
   const int32_t i = static_cast<int32_t>(blockIdx.x) * 256 + static_cast<int32_t>(threadIdx.x);
   double t[TERMS];
@@ -107,6 +111,16 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restric
       if constexpr (METHOD == ICP_POINT_TO_PLANE) {
         const double nn[3] = {Nb[static_cast<int64_t>(j) * 3], Nb[static_cast<int64_t>(j) * 3 + 1], Nb[static_cast<int64_t>(j) * 3 + 2]};
         icp_plane_terms(qq, b, nn, sqd, o, t);
+      } else if constexpr (METHOD == ICP_GENERALIZED) {
+        double ca[6], cb[6], Tl[12];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          ca[a] = Ca[static_cast<int64_t>(i) * 6 + a];
+          cb[a] = Cb[static_cast<int64_t>(j) * 6 + a];
+        }
+#pragma unroll
+        for (int a = 0; a < 12; ++a) Tl[a] = T[a];  // (the rotation: entries 0..2, 4..6, 8..10)
+        icp_generalized_terms(qq, b, ca, cb, Tl, sqd, o, t);
       } else {
         icp_point_terms(qq, b, sqd, o, t);
       }
@@ -148,6 +162,33 @@ __global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ par
     history[static_cast<int64_t>(k) * 3 + 1] = row[1];
     history[static_cast<int64_t>(k) * 3 + 2] = row[2];
   }
+}
+
+// C[i] = the regularised covariance of point i (six doubles: xx, xy, xz, yy, yz, zz) over the first knn entries of its
+// list that are kept, w = 1.0 - epsilon; cnt_out (may be null): how many. The lists are k_feat_normals'.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_icp_covariances(const double* __restrict__ P, int64_t n,
+                                                          const int32_t* __restrict__ li, const double* __restrict__ ld,
+                                                          int stride, int knn, int use_r, double r2, double w,
+                                                          double* __restrict__ C, int32_t* __restrict__ cnt_out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* row = li + i * stride;
+  int cnt = 0;
+  while (cnt < knn && feat_kept(row[cnt], ld[i * stride + cnt], use_r != 0, r2)) ++cnt;
+  double c[6];
+  icp_point_covariance(
+      cnt,
+      [&](int k, double (&p)[3]) {
+        const int64_t j = row[k];
+        p[0] = P[j * 3];
+        p[1] = P[j * 3 + 1];
+        p[2] = P[j * 3 + 2];
+      },
+      w, c);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) C[i * 6 + a] = c[a];
+  if (cnt_out) cnt_out[i] = cnt;
 }
 
 }  // namespace clipper_hip

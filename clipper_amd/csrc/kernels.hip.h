@@ -43,7 +43,8 @@
 //   k_sdp.hip.h       the semidefinite relaxation (MSRC-SDR): ADMM with a warm-started parallel Jacobi eigensolver
 //   k_sdp_wide.hip.h  the same relaxation for one problem over the whole chip, a launch per Jacobi step (n <= 1024)
 //   k_knn_grid.hip.h  the same lists as k_knn.hip.h through a uniform grid over the searched cloud (d = 3)
-//   k_icp.hip.h       the ICP refinement over that grid: transform, the sums of either metric, the step on one thread
+//   k_icp.hip.h       the ICP refinement over that grid: transform, the sums of each metric, the step on one thread; the
+//                     per-point covariances of the generalized metric
 //   k_features.hip.h  surface normals and FPFH descriptors of a point cloud (what the matcher and PointNormalDistance take)
 //   k_sort.hip.h      a stable LSD radix sort of (u64 key, i32 index) pairs, 8-bit digits
 //   k_voxel.hip.h     voxel down-sampling over that sort: one centroid (and normal) per occupied voxel, bit for bit

@@ -294,6 +294,44 @@ def icp(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None, meth
                        device=device)
 
 
+def estimate_covariances(P: np.ndarray, knn: int = 20, radius: float = 0.0, epsilon: float = 1e-3, device: int = 0,
+                         search: str | None = None) -> np.ndarray:
+    """The per-point covariances of generalized ICP, on the GPU (clipper_hip_estimate_covariances). P: n x 3, rows =
+    points. Per point I - (1 - epsilon) nv nv^T, nv the normal of estimate_normals' neighbourhood (knn, radius): a disc
+    of thickness epsilon in the surface; the identity where fewer than 3 neighbours are kept. Returns n x 6: xx, xy,
+    xz, yy, yz, zz per row. search: as in ground_truth_associations."""
+    from . import _abi as abi
+    if not (0.0 < epsilon <= 1.0):
+        raise ValueError(f"epsilon must be in (0, 1] (epsilon = {epsilon})")
+    with _knn_search(search):
+        Cv = abi.estimate_covariances(np.asarray(P, dtype=np.float64).T, knn=knn, radius=radius, epsilon=epsilon, device=device)
+    return np.ascontiguousarray(Cv.T)
+
+
+def icp_generalized(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None,
+                    source_covariances: np.ndarray | None = None, target_covariances: np.ndarray | None = None,
+                    covariance_knn: int = 20, epsilon: float = 1e-3, max_distance: float = 0.0, max_iterations: int = 30,
+                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0, search: str | None = None):
+    """Generalized ICP (the plane-to-plane metric), on the GPU (clipper_hip_icp_generalized): icp's loop, correspondences
+    and stop rule, with every inlier pair weighed by the inverse of the sum of its two covariances: what refines
+    voxel-down-sampled scans, where no source point has an exact partner. src, tgt: n x 3, rows = points. The
+    covariances (n x 6 rows of xx, xy, xz, yy, yz, zz) left None are estimated in the call by
+    estimate_covariances(cloud, covariance_knn, epsilon=epsilon). Returns (T 4 x 4, info) as icp does."""
+    from . import _abi as abi
+    src, tgt = np.asarray(src, dtype=np.float64), np.asarray(tgt, dtype=np.float64)
+    covs = []
+    for name, cloud, cv in (("source_covariances", src, source_covariances), ("target_covariances", tgt, target_covariances)):
+        if cv is None:
+            cv = estimate_covariances(cloud, knn=covariance_knn, epsilon=epsilon, device=device, search=search)
+        cv = np.asarray(cv, dtype=np.float64)
+        if cv.ndim != 2 or cv.shape != (len(cloud), 6):
+            raise ValueError(f"{name} must be n x 6, one row per point")
+        covs.append(cv.T)
+    with _knn_search(search):
+        return abi.icp_generalized(src.T, covs[0], tgt.T, covs[1], T_init=T_init, max_distance=max_distance,
+                                   max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, device=device)
+
+
 def evaluate_registration(src: np.ndarray, tgt: np.ndarray, T: np.ndarray | None = None, max_distance: float = 0.0,
                           device: int = 0, search: str | None = None, return_correspondences: bool = False):
     """How good the alignment T (4 x 4, None = identity) of src onto tgt (n x 3) is, on the GPU

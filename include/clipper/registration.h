@@ -7,8 +7,8 @@
  *        matcher that produces the putative ones, and the stage in front of it: raw cloud ->
  *        normals -> FPFH descriptors, and the step behind it: ICP over the whole clouds (icp,
  *        evaluate_registration). Thin C++ wrappers over the C ABI (include/clipper_hip.h);
- *        match_descriptors, voxel_down_sample, estimate_normals, compute_fpfh, icp and evaluate_registration work on
- *        the device.
+ *        match_descriptors, voxel_down_sample, estimate_normals, compute_fpfh, icp, estimate_covariances,
+ *        icp_generalized and evaluate_registration work on the device.
  */
 #pragma once
 
@@ -204,8 +204,8 @@ inline VoxelDownSampled voxel_down_sample(const invariants::Data& P, double voxe
   return r;
 }
 
-/// The two metrics of icp
-enum class IcpMethod { PointToPoint = 0, PointToPlane = 1 };
+/// The metrics of icp, and the one of icp_generalized
+enum class IcpMethod { PointToPoint = 0, PointToPlane = 1, Generalized = 2 };
 /// How an icp ended (clipper_icp_info_t.status)
 enum class IcpStatus { Converged = 0, MaxIterations = 1, TooFew = 2, Degenerate = 3 };
 
@@ -232,6 +232,21 @@ struct IcpResult {
   std::vector<std::array<double, 3>> history;
 };
 
+namespace detail {
+/// what an ICP call left in its info and history (rows of 3 doubles), into r (T is already there)
+inline void fill_icp_result(const clipper_icp_info_t& info, const std::vector<double>& hist, IcpResult& r) {
+  r.status = static_cast<IcpStatus>(info.status);
+  r.iterations = info.iterations;
+  r.count = info.count;
+  r.fitness = info.fitness;
+  r.inlier_rmse = info.inlier_rmse;
+  r.route = static_cast<KnnSearch>(info.route);
+  r.candidates = info.candidates;
+  r.device_ms = info.device_ms;
+  for (int k = 0; k <= info.iterations; ++k) r.history.push_back({hist[3 * k], hist[3 * k + 1], hist[3 * k + 2]});
+}
+}  // namespace detail
+
 /// Local refinement of a registration on the device (clipper_hip_icp): ICP of the cloud src onto tgt (3 x n) from the
 /// alignment T_init (column-major 4 x 4; nullptr = identity), e.g. estimate_rigid_transform's. PointToPlane needs the
 /// target's unit normals (3 x n_tgt, e.g. estimate_normals(tgt)); pass an empty matrix otherwise. The result is the
@@ -250,15 +265,41 @@ inline IcpResult icp(const invariants::Data& src, const invariants::Data& tgt, c
   if (clipper_hip_icp(device, src.data(), src.cols(), tgt.data(), has_normals ? normals.data() : nullptr, tgt.cols(), T_init,
                       &prm, r.T, &info, hist.data()))
     throw std::invalid_argument(clipper_hip_last_error());
-  r.status = static_cast<IcpStatus>(info.status);
-  r.iterations = info.iterations;
-  r.count = info.count;
-  r.fitness = info.fitness;
-  r.inlier_rmse = info.inlier_rmse;
-  r.route = static_cast<KnnSearch>(info.route);
-  r.candidates = info.candidates;
-  r.device_ms = info.device_ms;
-  for (int k = 0; k <= info.iterations; ++k) r.history.push_back({hist[3 * k], hist[3 * k + 1], hist[3 * k + 2]});
+  detail::fill_icp_result(info, hist, r);
+  return r;
+}
+
+/// The per-point covariances of generalized ICP for the cloud P (3 x n) on the device
+/// (clipper_hip_estimate_covariances): 6 x n, per column xx, xy, xz, yy, yz, zz of I - (1 - epsilon) nv nv^T, nv the
+/// normal estimate_normals finds over the same neighbourhood; the identity where fewer than 3 neighbours are kept.
+inline invariants::Data estimate_covariances(const invariants::Data& P, const Neighborhood& nb = {20, 0.0},
+                                             double epsilon = 1e-3, int device = 0) {
+  if (P.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const clipper_neighborhood_t h{nb.knn, 0, nb.radius};
+  invariants::Data C(6, P.cols());
+  if (clipper_hip_estimate_covariances(device, P.data(), P.cols(), &h, epsilon, C.data(), nullptr))
+    throw std::invalid_argument(clipper_hip_last_error());
+  return C;
+}
+
+/// Generalized ICP on the device (clipper_hip_icp_generalized): icp's loop with the plane-to-plane metric over the
+/// covariances of both clouds (6 x n each, e.g. estimate_covariances'). params.method is taken as given and must be
+/// IcpMethod::Generalized. The result is the same on every search route and from run to run.
+inline IcpResult icp_generalized(const invariants::Data& src, const invariants::Data& src_cov, const invariants::Data& tgt,
+                                 const invariants::Data& tgt_cov, const IcpParams& params, const double* T_init = nullptr,
+                                 int device = 0) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  if (src_cov.rows() != 6 || src_cov.cols() != src.cols() || tgt_cov.rows() != 6 || tgt_cov.cols() != tgt.cols())
+    throw std::invalid_argument("covariances must be 6 x n, one column per point");
+  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
+                                 params.rel_fitness, params.rel_rmse};
+  IcpResult r{};
+  clipper_icp_info_t info{};
+  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
+  if (clipper_hip_icp_generalized(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(), tgt.cols(),
+                                  T_init, &prm, r.T, &info, hist.data()))
+    throw std::invalid_argument(clipper_hip_last_error());
+  detail::fill_icp_result(info, hist, r);
   return r;
 }
 

@@ -557,13 +557,14 @@ int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const c
  * are functions of the inputs alone: the same on both search routes and from run to run (the rules in full:
  * clipper_amd/csrc/icp_rules.hpp). Stand-alone: needs no context. */
 enum { CLIPPER_ICP_POINT_TO_POINT = 0,   /* Arun / Horn on the inliers                                            */
-       CLIPPER_ICP_POINT_TO_PLANE = 1 }; /* linearised (q - b) . n over the target's normals, Cayley rotation      */
+       CLIPPER_ICP_POINT_TO_PLANE = 1,   /* linearised (q - b) . n over the target's normals, Cayley rotation      */
+       CLIPPER_ICP_GENERALIZED    = 2 }; /* plane-to-plane over per-point covariances: clipper_hip_icp_generalized */
 enum { CLIPPER_ICP_CONVERGED      = 0,   /* fitness and rmse both changed by less than their bounds               */
        CLIPPER_ICP_MAX_ITERATIONS = 1,
-       CLIPPER_ICP_TOO_FEW        = 2,   /* fewer than 3 (point-to-point) or 6 (point-to-plane) inliers           */
+       CLIPPER_ICP_TOO_FEW        = 2,   /* fewer than 3 (point-to-point, generalized) or 6 (point-to-plane) inliers */
        CLIPPER_ICP_DEGENERATE     = 3 }; /* the inliers do not determine the step (rank-deficient system)         */
 typedef struct clipper_icp_params_t {
-  int32_t method;          /* CLIPPER_ICP_POINT_TO_POINT | CLIPPER_ICP_POINT_TO_PLANE */
+  int32_t method;          /* CLIPPER_ICP_POINT_TO_POINT | CLIPPER_ICP_POINT_TO_PLANE; clipper_hip_icp_generalized: CLIPPER_ICP_GENERALIZED */
   int32_t max_iterations;  /* 0..1000 (facades default to 30); 0 = evaluate only */
   double  max_distance;    /* positive and finite */
   double  rel_fitness;     /* >= 0 (facades default to 1e-6) */
@@ -587,10 +588,31 @@ typedef struct clipper_icp_info_t {
  * k >= 1 and |fitness_k - fitness_(k-1)| < rel_fitness and |rmse_k - rmse_(k-1)| < rel_rmse, else TOO_FEW, else
  * MAX_ITERATIONS at k == max_iterations, else DEGENERATE when the step is undetermined; otherwise T <- dT T. T_out is
  * the T the last row was evaluated under. Every status returns 0 with a finite T_out; <0: error (bad arguments are
- * refused before any device work). info may be NULL. */
+ * refused before any device work; CLIPPER_ICP_GENERALIZED is refused with the name of the call below). info may be NULL. */
 int clipper_hip_icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
                     int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
                     clipper_icp_info_t* info, double* history);
+
+/* GENERALIZED ICP (Segal et al.: the plane-to-plane metric) over per-point covariances: the correspondence, the inlier
+ * test, the history, the stop rule and every status are clipper_hip_icp's; an inlier pair (q, b) with the covariances
+ * C_a of its source point and C_b of its target point weighs its difference d = q - b by M = (C_b + R C_a R^T)^-1, R the
+ * rotation of the current T, and the step solves J^T M J xi = -J^T M d for the rotation and shift of point-to-plane
+ * (the order of every product: clipper_amd/csrc/icp_rules.hpp). C_src (6 x n_src) and C_tgt (6 x n_tgt): per point
+ * xx, xy, xz, yy, yz, zz, contiguous per point, e.g. from clipper_hip_estimate_covariances; every entry finite and every
+ * matrix positive definite (its three leading minors > 0 in fp64), else refused before any device work with the point
+ * named. params->method must be CLIPPER_ICP_GENERALIZED. TOO_FEW: fewer than 3 inliers. A pair whose C_b + R C_a R^T
+ * rounds to a singular matrix leaves a non-number in the sums, which ends the call DEGENERATE with the previous T. */
+int clipper_hip_icp_generalized(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt,
+                                const double* C_tgt, int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
+                                double* T_out, clipper_icp_info_t* info, double* history);
+
+/* The covariances clipper_hip_icp_generalized takes: C_out (6 x n), per point of the cloud P (3 x n) the matrix
+ * I - (1 - epsilon) nv nv^T (eigenvalues epsilon, 1, 1) as xx, xy, xz, yy, yz, zz, nv being the unit eigenvector of the
+ * smallest eigenvalue of the covariance of the point's neighbourhood: clipper_hip_estimate_normals' neighbourhood and
+ * eigenvector, without its sign rule (the sign cancels). The identity where cnt < 3. epsilon in (0, 1] (facades
+ * default to 1e-3). count_out (n, may be NULL): cnt. Stand-alone: needs no context. 0, or <0: error. */
+int clipper_hip_estimate_covariances(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb, double epsilon,
+                                     double* C_out, int32_t* count_out);
 
 /* fitness, inlier_rmse and count of the alignment T (NULL = identity), as iteration 0 of clipper_hip_icp computes them
  * (any of the three may be NULL). corr_out (n_src, may be NULL): the target index of each source point's
