@@ -498,9 +498,13 @@ __device__ __forceinline__ void prefilter_squares(const float* p1r, const float*
 
 // The sqrt-free form of the prefilter (tests/prefilter_model.py): |l1 - l2| < E  <=>  t <= 0  or  t^2 < 4 s1 s2 with
 // t = s1 + s2 - E^2; the right-hand side carries a 2^-18 relative margin for the fp32 roundings of t, t^2 and s1 s2.
-__device__ __forceinline__ bool prefilter_close(float s1, float s2, float E2) {
+// `wave`: the same over the wave's lanes, every compare balloted on its own and the masks joined with scalar logic (a
+// ballot of the joined predicate makes the compiler write it into a register as 0 / 1 and compare that again).
+__device__ __forceinline__ bool prefilter_close(float s1, float s2, float E2, uint64_t& wave) {
   const float t = (s1 + s2) - E2;
-  return (t <= 0.f) || (t * t < (4.0f * 1.0000038147f) * (s1 * s2));
+  const bool inside = t <= 0.f, near = t * t < (4.0f * 1.0000038147f) * (s1 * s2);
+  wave = __builtin_amdgcn_ballot_w64(inside) | __builtin_amdgcn_ballot_w64(near);
+  return inside | near;
 }
 
 // This wave's AT_ROWS_PER_WAVE rows of a tile against the lane's NC columns: the survivors of the fp32 prefilter go
@@ -519,32 +523,41 @@ __device__ __forceinline__ void tile_score_rows(const TileColumns<PD, NC>& col, 
     }
   };
   uint32_t head = 0, tail = 0;  // wave-uniform
-  for (int rr = 0; rr < AT_ROWS_PER_WAVE; ++rr) {
-    const int rl = wave * AT_ROWS_PER_WAVE + rr;  // tile row
-    if (r0 + rl < nrows) {  // uniform
-      int32_t a0r, a1r;
-      float p1r[PD], p2r[PD];
-      row.broadcast(rr, a0r, a1r, p1r, p2r);
+  uint64_t valid[NC];           // col.valid over the wave
 #pragma unroll
-      for (int q = 0; q < NC; ++q) {
-        float s1, s2;
-        prefilter_squares<PD>(p1r, col.p1[q], p2r, col.p2[q], s1, s2);
-        // clipper.cpp:35-38 distinctness (also removes the diagonal) + conservative c < eps
-        const bool cand = col.valid[q] && (a0r != col.a0[q]) && (a1r != col.a1[q]) && prefilter_close(s1, s2, E2);
-        const uint64_t mask = __ballot(cand);
-        if (mask != 0) {  // uniform
-          if (cand) queue[(tail + lane_prefix(mask)) & (AT_QUEUE - 1)] =
-              (static_cast<uint32_t>(rl) << 8) | static_cast<uint32_t>(NC * lane + q);
-          tail += static_cast<uint32_t>(__popcll(mask));
-        }
+  for (int q = 0; q < NC; ++q) valid[q] = __builtin_amdgcn_ballot_w64(col.valid[q]);
+  // the wave's rows that exist: a scalar loop bound (tested per row against the 64-bit nrows it was a vector compare)
+  const int64_t left = nrows - (r0 + wave * AT_ROWS_PER_WAVE);
+  const int live = __builtin_amdgcn_readfirstlane(left < AT_ROWS_PER_WAVE ? (left > 0 ? static_cast<int>(left) : 0)
+                                                                          : AT_ROWS_PER_WAVE);
+  for (int rr = 0; rr < live; ++rr) {
+    const int rl = wave * AT_ROWS_PER_WAVE + rr;  // tile row
+    int32_t a0r, a1r;
+    float p1r[PD], p2r[PD];
+    row.broadcast(rr, a0r, a1r, p1r, p2r);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      float s1, s2;
+      prefilter_squares<PD>(p1r, col.p1[q], p2r, col.p2[q], s1, s2);
+      // clipper.cpp:35-38 distinctness (also removes the diagonal) + conservative c < eps
+      // (no `&&`: the packed arithmetic runs for every pair — an exec region around it costs more. `cand` is the lane's
+      // own bit of `mask`, kept beside it: the queue write's exec mask)
+      const bool d0 = a0r != col.a0[q], d1 = a1r != col.a1[q];
+      uint64_t close;
+      const bool cand = col.valid[q] & d0 & d1 & prefilter_close(s1, s2, E2, close);
+      const uint64_t mask = valid[q] & __builtin_amdgcn_ballot_w64(d0) & __builtin_amdgcn_ballot_w64(d1) & close;
+      if (mask != 0) {  // uniform
+        if (cand) queue[(tail + lane_prefix(mask)) & (AT_QUEUE - 1)] =
+            (static_cast<uint32_t>(rl) << 8) | static_cast<uint32_t>(NC * lane + q);
+        tail += static_cast<uint32_t>(__popcll(mask));
       }
-      if (tail - head >= 64) {  // uniform
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        while (tail - head >= 64) {
-          drain(head, 64);
-          head += 64;
-        }
+    }
+    if (tail - head >= 64) {  // uniform
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      while (tail - head >= 64) {
+        drain(head, 64);
+        head += 64;
       }
     }
   }
@@ -635,13 +648,11 @@ __global__ __launch_bounds__(AT_WAVES * 64, AT_WAVES / 2) void k_affinity_sym(
     // element q of the lane's column: tile (q, 64 e + lane), or (64 e + lane, q) of the mirror
     const VT* col = mirror ? img + (64 * e + lane) * AT_PITCH : img + 64 * e + lane;
     const uint4 mk = *reinterpret_cast<const uint4*>((mirror ? rowmask : colmask) + (64 * e + lane) * 4);
-    const uint64_t mlo = static_cast<uint64_t>(mk.x) | (static_cast<uint64_t>(mk.y) << 32);
-    const uint64_t mhi = static_cast<uint64_t>(mk.z) | (static_cast<uint64_t>(mk.w) << 32);
     const int cg = 2 * (mirror ? I : J) + e;
     const int k = mirror ? J : I;
     const int64_t s = (cg < O.ncg && k < O.nchunks && !(mirror && I == J))
                           ? static_cast<int64_t>(cg) * O.nchunks + k : -1;
-    slice_emit_lds(col, mirror ? 1 : AT_PITCH, mlo, mhi, s, sl, half, O, base_s, stamp ? ts + 2 : nullptr);
+    slice_emit_lds(col, mirror ? 1 : AT_PITCH, mk, s, sl, half, O, base_s, stamp ? ts + 2 : nullptr);
     if (stamp) {
       ts[4] = wall_clock64();
       for (int i = 0; i < 5; ++i) O.stamps[blockIdx.x * 5 + i] = ts[i];
@@ -768,11 +779,9 @@ __global__ __launch_bounds__(AT_WAVES * 64, AT_WAVES / 2) void k_affinity_rect(
   const int e = sl < CPL ? sl : 0;
   const VT* col = img + 64 * e + lane;
   const uint4 mk = *reinterpret_cast<const uint4*>(colmask + (64 * e + lane) * 4);
-  const uint64_t mlo = static_cast<uint64_t>(mk.x) | (static_cast<uint64_t>(mk.y) << 32);
-  const uint64_t mhi = static_cast<uint64_t>(mk.z) | (static_cast<uint64_t>(mk.w) << 32);
   const int cg = static_cast<int>(cl0 / 64) + e;
   const int64_t s = (sl < CPL && cg < O.ncg && I < O.nchunks) ? static_cast<int64_t>(cg) * O.nchunks + I : -1;
-  slice_emit_lds<VT>(col, PITCH, mlo, mhi, s, sl, half, O, base_s, nullptr);
+  slice_emit_lds<VT>(col, PITCH, mk, s, sl, half, O, base_s, nullptr);
 }
 
 }  // namespace clipper_hip

@@ -117,25 +117,60 @@ __device__ __forceinline__ void gr_emit(const VT (&v)[GR_RB], int64_t g, const G
     }
 }
 
+// A lane's walk over the nonzero rows of its column, ascending: the four 32-bit words of the column's
+// row mask, the empty ones taken out once, as a queue of (word, first row of the word). The word in
+// front is never empty while the column has rows left, so taking a row is find-first-bit, clear, and
+// one step of the queue where the word ran out: selects only, no 64-bit integer arithmetic and no
+// branch. What the queue shifts in behind the last word is stale: a caller counts the rows it takes.
+struct MaskWalk {
+  uint32_t w0, w1, w2, w3;
+  int b0, b1, b2, b3;
+  __device__ __forceinline__ static void close_up(uint32_t& wa, uint32_t& wb, int& ba, int& bb) {
+    const bool gap = wa == 0u;
+    wa = gap ? wb : wa;
+    ba = gap ? bb : ba;
+    wb = gap ? 0u : wb;
+  }
+  __device__ __forceinline__ explicit MaskWalk(uint4 mk)
+      : w0(mk.x), w1(mk.y), w2(mk.z), w3(mk.w), b0(0), b1(32), b2(64), b3(96) {
+    close_up(w0, w1, b0, b1); close_up(w1, w2, b1, b2); close_up(w2, w3, b2, b3);
+    close_up(w0, w1, b0, b1); close_up(w1, w2, b1, b2);
+    close_up(w0, w1, b0, b1);
+  }
+  // drop the row in front
+  __device__ __forceinline__ void skip() {
+    w0 &= w0 - 1u;
+    const bool out = w0 == 0u;
+    w0 = out ? w1 : w0; w1 = out ? w2 : w1; w2 = out ? w3 : w2;
+    b0 = out ? b1 : b0; b1 = out ? b2 : b1; b2 = out ? b3 : b2;
+  }
+  // the row in front, and drop it (a column that has none left: anything)
+  __device__ __forceinline__ int take() {
+    const int row = b0 + __builtin_ctz(w0);
+    skip();
+    return row;
+  }
+};
+
 // Emission of one slice (k_slices.hip.h) by TWO waves of a workgroup straight from an LDS image:
-// lane = column, col[q * stride] = its entry of row q of the tile (q < SL_SUB = 128), (mlo, mhi) =
-// the bit mask of its nonzero rows (set with LDS atomics while the image was filled: sweeping the
-// 128 rows of every column for them cost more than the writing). Both waves
+// lane = column, col[q * stride] = its entry of row q of the tile (q < SL_SUB = 128), mk = the
+// bit mask of its nonzero rows, four 32-bit words (set with LDS atomics while the image was filled:
+// sweeping the 128 rows of every column for them cost more than the writing). Both waves
 // know where every step starts (the lanes' lengths: ALU only); wave `half` writes the steps of
-// its parity. `s` = slice id cg * nchunks + k, or -1 (nothing to emit: both waves, uniformly).
+// its parity and only steps its walk (MaskWalk) over the four entries of a step of the other wave.
+// `s` = slice id cg * nchunks + k, or -1 (nothing to emit: both waves, uniformly).
 // Space is claimed with one atomic per slice on one of the arena cursors; a slice that does not fit
 // only records its size and maxq (the host grows the arena and repeats the fill).
 // Contains ONE __syncthreads (every wave of the workgroup must call it). `base_s`: LDS, one
 // unsigned long long per slice of the workgroup, this slice's at index `sl`.
 template <typename VT>
-__device__ __forceinline__ void slice_emit_lds(const VT* col, int stride, uint64_t mlo,
-                                               uint64_t mhi, int64_t s, int sl, int half,
-                                               const SliceOut& O, unsigned long long* base_s,
+__device__ __forceinline__ void slice_emit_lds(const VT* col, int stride, uint4 mk, int64_t s, int sl,
+                                               int half, const SliceOut& O, unsigned long long* base_s,
                                                long long* tstamp) {
   static_assert(SL_SUB == 128, "a slice is as tall as a tile of the fill kernels");
   constexpr int QB = 4 * static_cast<int>(sizeof(VT));
   const int lane = threadIdx.x & 63;
-  const int n = __popcll(mlo) + __popcll(mhi);
+  const int n = __popc(mk.x) + __popc(mk.y) + __popc(mk.z) + __popc(mk.w);
   const int tot = (n + 3) >> 2;
   const int maxq = sl_wave_max(tot);
   const uint32_t bytes = 16 + 64 + sl_so_bytes(maxq) + sl_steps_bytes(tot, maxq, QB);
@@ -177,38 +212,33 @@ __device__ __forceinline__ void slice_emit_lds(const VT* col, int stride, uint64
     if (lane * 4 < sob && lane >= (maxq + SL_SO - 1) / SL_SO) so[lane] = 0;  // the table's padding
   }
   uint32_t off = 16 + 64 + sob;
+  MaskWalk walk(mk);
   for (int q = 0; q < maxq; ++q) {
     const bool active = q < tot;
-    const uint64_t mask = __ballot(active);
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(active);
     const int cnt = __popcll(mask);
-    const bool own = (q & 1) == half;  // uniform
-    if (own && (q % SL_SO) == 0 && lane == 0) so[q / SL_SO] = off;
-    if (active) {
-      SliceQuad<VT> vq;
-      vq.v[0] = vq.v[1] = vq.v[2] = vq.v[3] = VT(0);
-      uint32_t rq = 0;
+    if ((q & 1) != half) {  // uniform: the other wave's step
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        int row = -1;
-        if (mlo) {
-          row = __ffsll(static_cast<unsigned long long>(mlo)) - 1;
-          mlo &= mlo - 1;
-        } else if (mhi) {
-          row = 64 + __ffsll(static_cast<unsigned long long>(mhi)) - 1;
-          mhi &= mhi - 1;
-        }
-        if (own && row >= 0) {
-          vq.v[e] = col[row * stride];
+      for (int e = 0; e < 4; ++e) walk.skip();
+    } else {
+      if ((q % SL_SO) == 0 && lane == 0) so[q / SL_SO] = off;
+      if (active) {
+        SliceQuad<VT> vq;
+        uint32_t rq = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool have = 4 * q + e < n;  // (the lane's last quad is filled up with zeros)
+          const int next = walk.take();
+          const int row = have ? next : 0;
+          const VT v = col[__mul24(row, stride)];  // (row < 128, stride <= 129)
+          vq.v[e] = have ? v : VT(0);
           rq |= static_cast<uint32_t>(row) << (8 * e);
         }
-      }
-      if (own) {
         const uint32_t rank = sl_lane_rank(mask);
         vq.store(sp + off + rank * QB);
         *reinterpret_cast<uint32_t*>(sp + off + cnt * QB + rank * 4) = rq;
       }
-    }
-    if (own) {  // zero the step's padding (the row quads are padded to 16 bytes)
+      // zero the step's padding (the row quads are padded to 16 bytes)
       const int padw = (((cnt * 4 + 15) & ~15) - cnt * 4) >> 2;
       if (lane < padw) *reinterpret_cast<uint32_t*>(sp + off + cnt * QB + cnt * 4 + lane * 4) = 0;
     }

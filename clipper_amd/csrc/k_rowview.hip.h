@@ -300,10 +300,8 @@ __global__ __launch_bounds__(AT_WAVES * 64, AT_WAVES / 2) void k_slice_filter_ro
   const int sl = wave & 3, half = wave >> 2;
   const VT* col = img + lane;
   const uint4 mk = *reinterpret_cast<const uint4*>(colmask + lane * 4);
-  const uint64_t mlo = static_cast<uint64_t>(mk.x) | (static_cast<uint64_t>(mk.y) << 32);
-  const uint64_t mhi = static_cast<uint64_t>(mk.z) | (static_cast<uint64_t>(mk.w) << 32);
   const int64_t s = (sl == 0 && cg < O.ncg && I < O.nchunks) ? static_cast<int64_t>(cg) * O.nchunks + I : -1;
-  slice_emit_lds<VT>(col, PITCH, mlo, mhi, s, sl, half, O, base_s, nullptr);
+  slice_emit_lds<VT>(col, PITCH, mk, s, sl, half, O, base_s, nullptr);
 }
 
 // the host has built the view the state asked for (or refused: too many rows once the pending
