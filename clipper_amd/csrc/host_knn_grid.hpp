@@ -71,7 +71,7 @@ void knn_grid_bin(const double* P, int32_t n, const KnnGrid& g, int32_t ncells, 
                   int32_t* cursor, unsigned long long* kmin, unsigned long long* kmax, KgPoint* out, hipStream_t st) {
   const dim3 pb(static_cast<unsigned>(ceil_div(n, 256)));
   hipLaunchKernelGGL(k_kg_count<>, pb, dim3(256), 0, st, P, n, g, cell, counts, kmin, kmax);
-  hipLaunchKernelGGL(k_kg_scan<>, dim3(1), dim3(KG_SCAN_THREADS), 0, st, counts, ncells, start, cursor);
+  hipLaunchKernelGGL(k_row_scan<>, dim3(1), dim3(ROW_SCAN_THREADS), 0, st, counts, ncells, cursor, start, 1);
   hipLaunchKernelGGL(k_kg_scatter<>, pb, dim3(256), 0, st, P, n, cell, cursor, out);
 }
 

@@ -69,7 +69,7 @@ int voxel_run(int device, const double* P, const double* N, int64_t n_, const cl
   for (int pass = 0; pass < plan.passes; ++pass, cur ^= 1) {
     int32_t* const tot = totals + pass * SORT_RADIX;
     hipLaunchKernelGGL(k_sort_hist<>, per_tile, dim3(SORT_THREADS), 0, st, keys[cur], n, pass, ntiles, table, tot);
-    hipLaunchKernelGGL(k_sort_scan<>, dim3(SORT_RADIX), dim3(SORT_SCAN_THREADS), 0, st, table, ntiles, first, 0);
+    hipLaunchKernelGGL(k_row_scan<>, dim3(SORT_RADIX), dim3(ROW_SCAN_THREADS), 0, st, table, ntiles, first, nullptr, 0);
     hipLaunchKernelGGL(k_sort_scatter<>, per_tile, dim3(SORT_THREADS), 0, st, keys[cur], idx[cur], n, pass, ntiles, first, tot,
                        keys[cur ^ 1], idx[cur ^ 1]);
   }
@@ -77,7 +77,7 @@ int voxel_run(int device, const double* P, const double* N, int64_t n_, const cl
   const unsigned long long* sk = keys[cur];
   const int32_t* si = idx[cur];
   hipLaunchKernelGGL(k_vx_heads<>, per_tile, dim3(SORT_THREADS), 0, st, sk, n, heads);
-  hipLaunchKernelGGL(k_sort_scan<>, dim3(1), dim3(SORT_SCAN_THREADS), 0, st, heads, ntiles, tile_first, 1);
+  hipLaunchKernelGGL(k_row_scan<>, dim3(1), dim3(ROW_SCAN_THREADS), 0, st, heads, ntiles, tile_first, nullptr, 1);
   hipLaunchKernelGGL(k_vx_rows<>, per_tile, dim3(SORT_THREADS), 0, st, sk, si, n, tile_first, row, start,
                      trace_out ? dtrace : nullptr);
   hipLaunchKernelGGL(k_vx_partials<>, per_point, dim3(256), 0, st, dP, N ? dN : nullptr, n, plan.g, si, row, start, dpart);

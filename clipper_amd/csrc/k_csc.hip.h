@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_slices.hip.h"
 
 namespace clipper_hip {
@@ -62,12 +63,7 @@ __device__ __forceinline__ bool gr_claim(int cnt, int64_t g, const GroupOut<VT>&
                                          unsigned long long* base_s, int& off,
                                          unsigned long long& base) {
   const int t = threadIdx.x, gi = t >> 7, cl = t & 127;
-  int inc = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o);
-    if ((t & 63) >= o) inc += v;
-  }
+  const int inc = wave_scan_incl(cnt);
   if ((t & 63) == 63) red[t >> 6] = inc;
   __syncthreads();
   const int first = red[2 * gi], total = first + red[2 * gi + 1];
@@ -172,11 +168,11 @@ __device__ __forceinline__ void slice_emit_lds(const VT* col, int stride, uint4 
   const int lane = threadIdx.x & 63;
   const int n = __popc(mk.x) + __popc(mk.y) + __popc(mk.z) + __popc(mk.w);
   const int tot = (n + 3) >> 2;
-  const int maxq = sl_wave_max(tot);
+  const int maxq = wave_max(tot);
   const uint32_t bytes = 16 + 64 + sl_so_bytes(maxq) + sl_steps_bytes(tot, maxq, QB);
   if (tstamp) tstamp[0] = wall_clock64() + (bytes == 1 ? 1 : 0);
   if (half == 0 && s >= 0) {
-    const int nquads = sl_wave_sum(tot), entries = sl_wave_sum(n);
+    const int nquads = wave_sum(tot), entries = wave_sum(n);
     if (lane == 0) {
       const unsigned long long U = bytes >> 4;
       CscArena* ar = O.ctl + static_cast<int>((s * 11 + (s >> 6)) & (CSC_ARENAS - 1));

@@ -23,12 +23,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_grid_rules.hpp"
+
 namespace clipper_hip {
 
 constexpr int KNN_TILE = 1024;   // granularity of the chunks pcd1 is split into
 constexpr int KNN_UNR = 8;       // points of pcd1 fetched per batch of scalar loads
 constexpr int KNN_DMAX = 8;      // coordinates per point
-constexpr double KNN_INF = 1.0e300;
+constexpr double KNN_INF = KNN_GRID_EMPTY;  // (knn_grid_rules.hpp: one empty distance for both routes)
 
 template <int K, int D>
 __global__ __launch_bounds__(256) void k_knn_partial(const double* __restrict__ P0, int64_t n0,
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void k_knn_partial(const double* __restrict__ 
   double bd[K];
   int32_t bi[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
+  for (int k = 0; k < K; ++k) {  // (not knn_grid_clear: through the call the insertions below compile to branches, not selects)
     bd[k] = KNN_INF;
     bi[k] = -1;
   }
@@ -60,22 +62,7 @@ __global__ __launch_bounds__(256) void k_knn_partial(const double* __restrict__ 
       const double df = q[k] - p[k];
       dist = dist + df * df;
     }
-    if (dist < bd[K - 1]) {  // sorted insertion; equal distances keep the earlier (lower) index
-      const int32_t jj = static_cast<int32_t>(t);
-#pragma unroll
-      for (int k = K - 1; k >= 0; --k) {
-        const bool here = (k == 0) || !(dist < bd[k - 1]);
-        if (dist < bd[k]) {
-          if (here) {
-            bd[k] = dist;
-            bi[k] = jj;
-          } else {
-            bd[k] = bd[k - 1];
-            bi[k] = bi[k - 1];
-          }
-        }
-      }
-    }
+    knn_insert_first<K>(bd, bi, dist, static_cast<int32_t>(t));  // equal distances keep the earlier (lower) index
   };
   int64_t t = j0;
   for (; t + KNN_UNR <= j1; t += KNN_UNR) {
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256) void k_knn_merge(const double* __restrict__ pd
   double bd[K];
   int32_t bi[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
+  for (int k = 0; k < K; ++k) {  // (not knn_grid_clear: through the call the insertions below compile to branches, not selects)
     bd[k] = KNN_INF;
     bi[k] = -1;
   }
@@ -124,6 +111,7 @@ __global__ __launch_bounds__(256) void k_knn_merge(const double* __restrict__ pd
       const double dist = pd[o + c];
       const int32_t jj = pi[o + c];
       if (jj < 0 || !(dist < bd[K - 1])) break;  // the list is sorted: nothing better follows
+      // knn_insert_first's loop, kept here: through the call K = 32 takes 176 VGPRs for 110 and halves its occupancy
 #pragma unroll
       for (int k = K - 1; k >= 0; --k) {
         const bool here = (k == 0) || !(dist < bd[k - 1]);

@@ -12,10 +12,12 @@
 //                 slab minima / maxima through 64-bit integer atomics on an order-preserving key of the double
 //                 (a count, a minimum and a maximum do not depend on arrival order); a point that cannot improve
 //                 the value it reads skips its atomic, so a slab that every point shares is not hammered
-//   k_kg_scan     exclusive scan of the counts, one workgroup: start[] (kept) and cursor[] (used up by the scatter)
+//   k_row_scan    (k_wave.hip.h) exclusive scan of the counts, one workgroup: cursor[] (used up by the scatter) and
+//                 start[] (kept), ncells + 1 entries each
 //   k_kg_scatter  thread = point: (x, y, z, original index) to its cell's next free place: 32 bytes, two 16-byte
 //                 stores. The order of points inside a cell differs from run to run; the lists do not.
-//   k_kg_slabs    six workgroups: suffix minimum / prefix maximum of the slab keys, as doubles
+//   k_kg_slabs    six workgroups: suffix minimum / prefix maximum of the slab keys (block_scan_excl over the threads'
+//                 stretches), as doubles
 // Query:
 //   k_knn_grid<K> thread = one query, in the cell order of the searched grid (the 64 lanes of a wave walk
 //                 neighbouring cells: their loads hit the same lines), K best in registers as in k_knn_partial,
@@ -28,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "knn_grid_rules.hpp"
 
 namespace clipper_hip {
@@ -40,7 +43,6 @@ struct alignas(16) KgPoint {
 static_assert(sizeof(KgPoint) == 32, "a binned point is two 16-byte words");
 
 constexpr int KG_BOUNDS_BLOCKS = 256;  // partials of k_kg_bounds
-constexpr int KG_SCAN_THREADS = 1024;
 
 // order-preserving key of a double for unsigned 64-bit min / max (every finite value and both infinities)
 __device__ inline unsigned long long kg_key(double v) {
@@ -125,39 +127,6 @@ __global__ __launch_bounds__(256) void k_kg_count(const double* __restrict__ P, 
   }
 }
 
-// start[i] = cursor[i] = counts[0] + ... + counts[i - 1], i = 0..n (n + 1 entries; either output may be null). One
-// workgroup: a thread adds up its own stretch, the stretches' sums are scanned in LDS, the thread writes its stretch.
-template <int = 0>
-__global__ __launch_bounds__(KG_SCAN_THREADS) void k_kg_scan(const int32_t* __restrict__ counts, int32_t n, int32_t* __restrict__ start,
-                                                              int32_t* __restrict__ cursor) {
-  __shared__ int32_t part[KG_SCAN_THREADS];
-  const int32_t t = static_cast<int32_t>(threadIdx.x);
-  const int32_t len = (n + KG_SCAN_THREADS - 1) / KG_SCAN_THREADS;
-  const int64_t b64 = static_cast<int64_t>(t) * len;
-  const int32_t b = b64 < n ? static_cast<int32_t>(b64) : n, e = b64 + len < n ? static_cast<int32_t>(b64 + len) : n;
-  int32_t s = 0;
-  for (int32_t i = b; i < e; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < KG_SCAN_THREADS; o <<= 1) {
-    const int32_t v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int32_t run = part[t] - s;
-  for (int32_t i = b; i < e; ++i) {
-    const int32_t v = counts[i];
-    if (start) start[i] = run;
-    if (cursor) cursor[i] = run;
-    run += v;
-  }
-  if (t == KG_SCAN_THREADS - 1) {
-    if (start) start[n] = part[t];
-    if (cursor) cursor[n] = part[t];
-  }
-}
-
 template <int = 0>
 __global__ __launch_bounds__(256) void k_kg_scatter(const double* __restrict__ P, int32_t n, const int32_t* __restrict__ cell,
                                                      int32_t* __restrict__ cursor, KgPoint* __restrict__ out) {
@@ -179,7 +148,7 @@ template <int = 0>
 __global__ __launch_bounds__(256) void k_kg_slabs(KnnGrid g, const unsigned long long* __restrict__ kmin,
                                                    const unsigned long long* __restrict__ kmax, double* __restrict__ smin,
                                                    double* __restrict__ pmax) {
-  __shared__ unsigned long long part[256];
+  __shared__ unsigned long long wsum[4];
   const int a = static_cast<int>(blockIdx.x) >> 1;
   const bool suffix = (blockIdx.x & 1) == 0;
   const int32_t n = g.dim[a], off = g.off[a], t = static_cast<int32_t>(threadIdx.x);
@@ -193,15 +162,7 @@ __global__ __launch_bounds__(256) void k_kg_slabs(KnnGrid g, const unsigned long
   const int32_t b = b64 < n ? static_cast<int32_t>(b64) : n, e = b64 + len < n ? static_cast<int32_t>(b64 + len) : n;
   unsigned long long s = unit;
   for (int32_t i = b; i < e; ++i) s = op(s, in[at(i)]);
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const unsigned long long v = t >= o ? part[t - o] : unit;
-    __syncthreads();
-    part[t] = op(part[t], v);
-    __syncthreads();
-  }
-  unsigned long long run = t > 0 ? part[t - 1] : unit;
+  unsigned long long run = block_scan_excl<4>(s, wsum, op, unit);  // the stretches in front of this thread's
   for (int32_t i = b; i < e; ++i) {
     run = op(run, in[at(i)]);
     out[at(i)] = kg_unkey(run);
@@ -248,17 +209,14 @@ __global__ __launch_bounds__(256) void k_knn_grid(const KgPoint* __restrict__ Q,
 
 template <int = 0>
 __global__ __launch_bounds__(256) void k_kg_sum(const int32_t* __restrict__ v, int64_t n, unsigned long long* __restrict__ sum) {
-  __shared__ unsigned long long red[256];
+  __shared__ unsigned long long red[4];
   unsigned long long s = 0;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256)
     s += static_cast<unsigned long long>(v[i]);
-  red[threadIdx.x] = s;
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(sum, red[0]);
+  if (threadIdx.x == 0) atomicAdd(sum, red[0] + red[1] + red[2] + red[3]);
 }
 
 }  // namespace clipper_hip

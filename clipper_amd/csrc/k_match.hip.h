@@ -55,28 +55,12 @@ __global__ __launch_bounds__(256) void k_match_partial(const double* __restrict_
   double bd[K];
   int32_t bi[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
+  for (int k = 0; k < K; ++k) {  // (not knn_grid_clear: through the call the insertions below compile to branches, not selects)
     bd[k] = KNN_INF;
     bi[k] = -1;
   }
-  auto insert = [&](int64_t t, double dist) {
-    if (dist < bd[K - 1]) {  // sorted insertion; equal distances keep the earlier (lower) index
-      const int32_t jj = static_cast<int32_t>(t);
-#pragma unroll
-      for (int k = K - 1; k >= 0; --k) {
-        const bool here = (k == 0) || !(dist < bd[k - 1]);
-        if (dist < bd[k]) {
-          if (here) {
-            bd[k] = dist;
-            bi[k] = jj;
-          } else {
-            bd[k] = bd[k - 1];
-            bi[k] = bi[k - 1];
-          }
-        }
-      }
-    }
-  };
+  // equal distances keep the earlier (lower) index
+  auto insert = [&](int64_t t, double dist) { knn_insert_first<K>(bd, bi, dist, static_cast<int32_t>(t)); };
   int64_t t = j0;
   for (; t + MATCH_UNR <= j1; t += MATCH_UNR) {
     double dist[MATCH_UNR];

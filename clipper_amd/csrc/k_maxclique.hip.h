@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_slices.hip.h"
 
 namespace clipper_hip {
@@ -88,28 +89,7 @@ struct McAdjSrc {
 constexpr int MC_PEEL_THREADS = 1024;
 constexpr int MC_PEEL_FCAP = 2048;  // vertices peeled per round at most (the rest wait for the next round)
 
-// ---- wave helpers (one wave = one workgroup of 64 lanes in the HEU / EXACT kernels) ---------------------------
-__device__ __forceinline__ unsigned long long mc_wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int mc_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int mc_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const int t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
+// ---- helpers (one wave = one workgroup of 64 lanes in the HEU / EXACT kernels; the folds are k_wave.hip.h's) ----
 __device__ __forceinline__ unsigned long long mc_load_key(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -193,7 +173,7 @@ __device__ __forceinline__ void mc_degree_row(const uint64_t* __restrict__ G, in
                                               int32_t* __restrict__ deg, int lane) {
   int d = 0;
   for (int64_t w = lane; w < nw; w += 64) d += __popcll(G[v * nw + w]);
-  d = mc_wave_sum(d);
+  d = wave_sum(d);
   if (lane == 0) deg[v] = d;
 }
 
@@ -304,7 +284,7 @@ __device__ __forceinline__ int mc_greedy_loop(const uint64_t* __restrict__ G, in
       C[w] = word;
     }
     work += nw / 64 + 1;
-    bk = mc_wave_max_u64(bk);
+    bk = wave_max(bk);
     __syncthreads();
     if (bk == 0) break;
     u = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(bk & 0xFFFFFFFFull));
@@ -350,7 +330,7 @@ __device__ __forceinline__ void mc_seed_clique(const McProb& P, uint64_t* mc_lds
     const uint64_t* row = G + static_cast<int64_t>(given[i]) * nw;
     int d = 0;
     for (int64_t w = lane; w < nw; w += 64) d += __popcll(row[w] & S[w]);
-    d = mc_wave_sum(d);
+    d = wave_sum(d);
     if (lane == 0) __hip_atomic_store(degS + i, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __threadfence();
@@ -365,7 +345,7 @@ __device__ __forceinline__ void mc_seed_clique(const McProb& P, uint64_t* mc_lds
           (static_cast<unsigned long long>(mc_load_i32(degS + i) + 1) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(x));
       bk = kx > bk ? kx : bk;
     }
-    bk = mc_wave_max_u64(bk);
+    bk = wave_max(bk);
     if (bk == 0) break;
     u = static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(bk & 0xFFFFFFFFull));
     if (lane == 0) P.out[kept] = u;
@@ -480,7 +460,7 @@ __device__ __forceinline__ void mc_exact(const McProb& P_, int slot, long long b
         stk[w] = keep;
         cnt += __popcll(keep);
       }
-      cnt = mc_wave_sum(cnt);
+      cnt = wave_sum(cnt);
       work += nw / 64 + 1;
       inc = mc_load_key(&ctl->key);
       if (((static_cast<unsigned long long>(cnt + 1) << 32) | rk) <= inc) {
@@ -501,7 +481,7 @@ __device__ __forceinline__ void mc_exact(const McProb& P_, int slot, long long b
       Q[w] = x;
       if (x) hi = static_cast<int>(w) + 1;
     }
-    hi = mc_wave_max(hi);
+    hi = wave_max(hi);
     __syncthreads();
     int ncol = 0, last = -1, qlo = 0;
     ++nodes;
@@ -557,7 +537,7 @@ __device__ __forceinline__ void mc_exact(const McProb& P_, int slot, long long b
     }
     if (room)
       for (int64_t w = hi + lane; w < nw; w += 64) P[nw + w] = 0;
-    cnt = mc_wave_sum(cnt);
+    cnt = wave_sum(cnt);
     if (lane == 0) path[1 + L] = last;
     __threadfence_block();
     if (cnt == 0) {
@@ -711,7 +691,7 @@ __global__ __launch_bounds__(64) void k_mc_collect(const McProb* __restrict__ pr
   int who = -1;
   for (int j = lane; j < P.nslots; j += 64)
     if (P.slots[j].rec_key == key) who = j;
-  who = mc_wave_max(who);
+  who = wave_max(who);
   const int omega = static_cast<int>(key >> 32);
   if (who >= 0) {
     const int32_t* rec = P.recs + static_cast<int64_t>(who) * (P.D + 1);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_slices.hip.h"
 
 namespace clipper_hip {
@@ -264,12 +265,7 @@ __device__ __forceinline__ void rs_solve(const ResidentArgs& A, int unit) {
     bytes_t = reinterpret_cast<const uint32_t*>(src_t)[2];
   }
   if (wave == 0) {
-    uint32_t inc = bytes_t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t2 = __shfl_up(inc, o);
-      if (lane >= o) inc += t2;
-    }
+    const uint32_t inc = wave_scan_incl(bytes_t);
     tab[lane] = inc - bytes_t;
     if (lane == 63) words[0] = inc;
   }

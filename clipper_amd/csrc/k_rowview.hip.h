@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_affinity.hip.h"
 #include "k_csc.hip.h"
 #include "k_solver.hip.h"
@@ -43,8 +44,7 @@ __global__ __launch_bounds__(256) void k_rv_flags(const SolverState* __restrict_
     if (i < mp) flags[i] = live ? 1 : 0;
     n += live ? 1u : 0u;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
   __syncthreads();
   if (threadIdx.x == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -56,29 +56,10 @@ __global__ __launch_bounds__(1024) void k_rv_scan(uint32_t* __restrict__ blk, in
                                                    int32_t* __restrict__ count_out) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int b0 = 0; b0 < nb; b0 += 1024) {
-    const int i = b0 + threadIdx.x;
-    const uint32_t v = (i < nb) ? blk[i] : 0;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(inc, o);
-      if ((threadIdx.x & 63) >= o) inc += t;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t off = carry_s;
-    for (int w = 0; w < (threadIdx.x >> 6); ++w) off += wsum[w];
-    if (i < nb) blk[i] = off + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = off + inc;
-    __syncthreads();
-  }
+  const uint32_t total = block_scan_array<1024>(blk, nb, blk, wsum, &carry_s);
   if (threadIdx.x == 0) {
-    blk[nb] = carry_s;
-    __hip_atomic_store(count_out, static_cast<int32_t>(carry_s), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    blk[nb] = total;
+    __hip_atomic_store(count_out, static_cast<int32_t>(total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -128,12 +109,7 @@ __global__ __launch_bounds__(1024) void k_rv_list_one(const SolverState* __restr
   uint32_t n = 0, inc = 0;
   if (t < 256) {
     n = t < nwords ? static_cast<uint32_t>(__popcll(word[t])) : 0u;
-    inc = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t x = __shfl_up(inc, o);
-      if (lane >= o) inc += x;
-    }
+    inc = wave_scan_incl(n);
     if (lane == 63) wsum[wave] = inc;
   }
   __syncthreads();
@@ -178,17 +154,7 @@ __global__ __launch_bounds__(256) void k_rv_scatter(const uint8_t* __restrict__ 
     f[k] = (base + k < m && flags[base + k]) ? 1u : 0u;
     n += f[k];
   }
-  uint32_t inc = n;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o);
-    if ((threadIdx.x & 63) >= o) inc += t;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  uint32_t off = blk[blockIdx.x];
-  for (int w = 0; w < (threadIdx.x >> 6); ++w) off += wsum[w];
-  uint32_t at = off + inc - n;
+  uint32_t at = blk[blockIdx.x] + block_scan_excl<4>(n, wsum);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (base + k < mp) viewpos[base + k] = f[k] ? static_cast<int32_t>(at) : -1;

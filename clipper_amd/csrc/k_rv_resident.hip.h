@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_resident.hip.h"
 
 namespace clipper_hip {
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
         const gbytes_t sp = src_chunk(have ? k : 0);
         int mq = have ? static_cast<int>(reinterpret_cast<const CLIPPER_GLOBAL uint32_t*>(sp)[1]) : 0;
         const int tq = have ? static_cast<int>(sp[16 + lsrc]) : 0;
-        mq = sl_wave_max(mq);
+        mq = wave_max(mq);
         bytes = 16 + 64 + sl_so_bytes(mq) + sl_steps_bytes(tq, mq, QB);
         if (lane == 0) sizes[t] = bytes;
         continue;
@@ -285,12 +286,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
   __syncthreads();
   if (wave == 0) {
     const uint32_t bytes_t = (lane < nslices && nslices <= RVR_TMAX) ? sizes[lane] : 0u;
-    uint32_t inc = bytes_t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t2 = __shfl_up(inc, o);
-      if (lane >= o) inc += t2;
-    }
+    const uint32_t inc = wave_scan_incl(bytes_t);
     tab[lane] = inc - bytes_t;
     if (lane == 63) words[0] = inc;
   }
@@ -315,7 +311,7 @@ __global__ __launch_bounds__(RVR_NT) void k_solve_view_resident(RvrArgs A) {
       const gbytes_t src = src_chunk(have ? k : 0);
       const int mq_own = have ? static_cast<int>(reinterpret_cast<const CLIPPER_GLOBAL uint32_t*>(src)[1]) : 0;
       const int tot_dst = have ? static_cast<int>(src[16 + lsrc]) : 0;
-      const int maxq = __builtin_amdgcn_readfirstlane(sl_wave_max(mq_own));
+      const int maxq = __builtin_amdgcn_readfirstlane(wave_max(mq_own));
       uint8_t* dp = sl + o;
       if (lane < 4) reinterpret_cast<uint32_t*>(dp)[lane] = (lane == 1) ? static_cast<uint32_t>(maxq) : 0u;
       dp[16 + lane] = static_cast<uint8_t>(tot_dst);

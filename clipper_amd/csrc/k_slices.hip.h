@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_solver.hip.h"
 
 namespace clipper_hip {
@@ -648,21 +649,6 @@ struct CscSource {
   }
 };
 
-// wave-level integer helpers (all 64 lanes active)
-__device__ __forceinline__ int sl_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(v, o);
-    v = v > t ? v : t;
-  }
-  return v;
-}
-__device__ __forceinline__ int sl_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // size (bytes) of the steps of a slice whose lanes have `tot` quads: wave-uniform
 __device__ __forceinline__ uint32_t sl_steps_bytes(int tot, int maxq, int QB) {
   uint32_t bytes = 0;
@@ -698,8 +684,8 @@ __global__ __launch_bounds__(256) void k_slice_count(Source S, int ncg, int nchu
     ent += S.count();
     tot += (S.count() + 3) >> 2;
   }
-  const int maxq = sl_wave_max(tot);
-  const int entries = sl_wave_sum(ent);
+  const int maxq = wave_max(tot);
+  const int entries = wave_sum(ent);
   const uint32_t bytes = 16 + H * 64 + sl_so_bytes(maxq) + sl_steps_bytes(tot, maxq, 4 * sizeof(VT));
   if (lane == 0) {
     sizes[s] = bytes >> 4;
@@ -720,50 +706,20 @@ __global__ __launch_bounds__(256) void k_slice_scan_local(const uint32_t* __rest
     v[j] = (base + j < n) ? sizes[base + j] : 0;
     run += v[j];
   }
-  // inclusive scan of `run` across the wave, then across the 4 waves
-  uint64_t inc = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(inc, o);
-    if ((threadIdx.x & 63) >= o) inc += t;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  uint64_t off = 0;
-  for (int w = 0; w < (threadIdx.x >> 6); ++w) off += wsum[w];
-  uint64_t excl = off + inc - run;
+  uint64_t excl = block_scan_excl<4>(run, wsum);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (base + j < n) Pre[base + j] = excl;
     excl += v[j];
   }
-  if (threadIdx.x == 255) blocksum[blockIdx.x] = off + inc;
+  if (threadIdx.x == 255) blocksum[blockIdx.x] = excl;
 }
 // one workgroup: exclusive scan of the block sums in place; total -> blocksum[nb]
 __global__ __launch_bounds__(256) void k_slice_scan_blocks(uint64_t* __restrict__ blocksum, int64_t nb) {
   __shared__ uint64_t carry;
   __shared__ uint64_t wsum[4];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < nb; b0 += 256) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint64_t v = (i < nb) ? blocksum[i] : 0;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t t = __shfl_up(inc, o);
-      if ((threadIdx.x & 63) >= o) inc += t;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t off = carry;
-    for (int w = 0; w < (threadIdx.x >> 6); ++w) off += wsum[w];
-    if (i < nb) blocksum[i] = off + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 255) carry = off + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blocksum[nb] = carry;
+  const uint64_t total = block_scan_array<256>(blocksum, nb, blocksum, wsum, &carry);
+  if (threadIdx.x == 0) blocksum[nb] = total;
 }
 __global__ __launch_bounds__(256) void k_slice_scan_add(uint64_t* __restrict__ Pre, int64_t n,
                                                          const uint64_t* __restrict__ blocksum) {
@@ -817,7 +773,7 @@ __global__ __launch_bounds__(SL_PACKW * 64) void k_slice_pack(Source S, int ncg,
     nq[h] = (S.count() + 3) >> 2;
     tot += nq[h];
   }
-  const int maxq = sl_wave_max(tot);
+  const int maxq = wave_max(tot);
   uint8_t* sp = data + 16 * Pre[s];
   uint32_t* so = reinterpret_cast<uint32_t*>(sp + 16 + H * 64);
   const int sob = sl_so_bytes(maxq);
@@ -866,7 +822,7 @@ __global__ __launch_bounds__(SL_PACKW * 64) void k_slice_pack(Source S, int ncg,
     }
     off += cnt * QB + ((cnt * 4 + 15) & ~15);
   }
-  const int nquads = sl_wave_sum(tot);
+  const int nquads = wave_sum(tot);
   if (wave == 0 && lane == 0) {
     uint32_t* hd = reinterpret_cast<uint32_t*>(sp);
     hd[0] = static_cast<uint32_t>(nquads);
@@ -962,8 +918,8 @@ __global__ __launch_bounds__(256) void k_slice_pack_staged(GroupSource<VT> S, in
   }
   const int n = cnt[0] + cnt[1] + cnt[2] + cnt[3];
   const int tot = (n + 3) >> 2;
-  const int maxq = sl_wave_max(tot);
-  const int nquads = sl_wave_sum(tot);
+  const int maxq = wave_max(tot);
+  const int nquads = wave_sum(tot);
   uint8_t* sp = data + 16 * Pre[s];
   sp[16 + lane] = static_cast<uint8_t>(tot);
   uint32_t* so = reinterpret_cast<uint32_t*>(sp + 16 + 64);
@@ -1018,27 +974,8 @@ __global__ __launch_bounds__(1024) void k_slice_scan_small(const uint32_t* __res
                                                             uint64_t* __restrict__ total) {
   __shared__ uint64_t wsum[16];
   __shared__ uint64_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < n; b0 += 1024) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint64_t v = (i < n) ? sizes[i] : 0;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t t = __shfl_up(inc, o);
-      if ((threadIdx.x & 63) >= o) inc += t;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t off = carry_s;
-    for (int w = 0; w < (threadIdx.x >> 6); ++w) off += wsum[w];
-    if (i < n) Pre[i] = off + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = off + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) total[0] = carry_s;
+  const uint64_t sum = block_scan_array<1024>(sizes, n, Pre, wsum, &carry_s);
+  if (threadIdx.x == 0) total[0] = sum;
 }
 
 // k_slice_expand — the dense store S[j][c] (row pitch ld, element ST) back from the slices of

@@ -5,10 +5,10 @@
 // A pass over digit p of n pairs, cut into tiles of SORT_TILE consecutive pairs:
 //   k_sort_hist     workgroup = tile: a 256-entry histogram of the tile's digits in LDS (integer atomics: a count does
 //                   not depend on arrival order), written to table[digit][tile] and added to the pass's 256 totals
-//   k_sort_scan     workgroup = digit: exclusive scan of the digit's row of the table (the pattern of k_kg_scan): entry
+//   k_row_scan      (k_wave.hip.h) workgroup = digit: exclusive scan of the digit's row of the table: entry
 //                   (d, t) becomes the number of pairs with digit d in the tiles before t. The 256 rows are scanned
 //                   side by side; what joins them, the scan of the 256 totals, every scatter workgroup does for
-//                   itself in LDS. So the first output place of tile t's pairs with digit d is
+//                   itself (block_scan_excl). So the first output place of tile t's pairs with digit d is
 //                   (pairs with a smaller digit) + (pairs with digit d in earlier tiles).
 //   k_sort_scatter  workgroup = tile: every pair to its place. The tile is striped over the workgroup, round r holds
 //                   pairs r * 256 .. r * 256 + 255 in thread order, and the rounds are ranked one after the other with a
@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "voxel_rules.hpp"
 
 namespace clipper_hip {
@@ -31,7 +32,6 @@ constexpr int SORT_THREADS = 256;                       // a workgroup of the ti
 constexpr int SORT_ROUNDS = 8;                          // pairs per thread
 constexpr int SORT_TILE = SORT_THREADS * SORT_ROUNDS;   // pairs per tile (reported in clipper_voxel_info_t.sort_tile)
 constexpr int SORT_WAVES = SORT_THREADS / 64;
-constexpr int SORT_SCAN_THREADS = 1024;
 
 // the lanes of this wave whose digit equals this lane's, among the lanes with `valid` set (garbage on the others)
 __device__ inline unsigned long long sort_peers(uint32_t digit, bool valid) {
@@ -68,37 +68,6 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_hist(const unsigned long 
   if (hist[t]) atomicAdd(&totals[t], hist[t]);
 }
 
-// Workgroup = row of n entries: out[i] = in[0] + ... + in[i - 1], i = 0..n-1, and with with_total (one row only) the sum
-// in out[n]. A thread adds up its own stretch, the stretches' sums are scanned in LDS, the thread writes its stretch.
-template <int = 0>
-__global__ __launch_bounds__(SORT_SCAN_THREADS) void k_sort_scan(const int32_t* __restrict__ in, int32_t n, int32_t* __restrict__ out,
-                                                                  int with_total) {
-  __shared__ int32_t part[SORT_SCAN_THREADS];
-  const int32_t t = static_cast<int32_t>(threadIdx.x);
-  in += static_cast<int64_t>(blockIdx.x) * n;
-  out += static_cast<int64_t>(blockIdx.x) * n;
-  const int32_t len = (n + SORT_SCAN_THREADS - 1) / SORT_SCAN_THREADS;
-  const int64_t b64 = static_cast<int64_t>(t) * len;
-  const int32_t b = b64 < n ? static_cast<int32_t>(b64) : n, e = b64 + len < n ? static_cast<int32_t>(b64 + len) : n;
-  int32_t s = 0;
-  for (int32_t i = b; i < e; ++i) s += in[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < SORT_SCAN_THREADS; o <<= 1) {
-    const int32_t v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int32_t run = part[t] - s;
-  for (int32_t i = b; i < e; ++i) {
-    const int32_t v = in[i];
-    out[i] = run;
-    run += v;
-  }
-  if (with_total && t == SORT_SCAN_THREADS - 1) out[n] = part[t];
-}
-
 template <int = 0>
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(const unsigned long long* __restrict__ keys,
                                                                 const int32_t* __restrict__ idx, int32_t n, int pass,
@@ -122,17 +91,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(const unsigned lo
   }
 #pragma unroll
   for (int w = 0; w < SORT_WAVES; ++w) wcnt[w][t] = 0;
-  // thread = digit: the pairs with a smaller digit (a scan of the 256 totals, in place), then those in earlier tiles
-  const int32_t mine = totals[t];
-  base[t] = mine;
+  // thread = digit: the pairs with a smaller digit (a scan of the 256 totals; base's first words are its scratch),
+  // then those in earlier tiles
+  const int32_t below = block_scan_excl<SORT_WAVES>(totals[t], base);
   __syncthreads();
-  for (int o = 1; o < SORT_RADIX; o <<= 1) {
-    const int32_t below = t >= o ? base[t - o] : 0;
-    __syncthreads();
-    base[t] += below;
-    __syncthreads();
-  }
-  base[t] += first[static_cast<int64_t>(t) * ntiles + tile] - mine;
+  base[t] = below + first[static_cast<int64_t>(t) * ntiles + tile];
   __syncthreads();
 
 #pragma unroll

@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave.hip.h"
 #include "k_rowview.hip.h"
 #include "k_slices.hip.h"
 #include "k_solver.hip.h"
@@ -110,13 +111,9 @@ __global__ __launch_bounds__(256) void k_sub_flags(const SolverState* __restrict
     if (i < mp) flags[i] = in ? 1 : 0;
     n += in ? 1u : 0u;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    n += __shfl_xor(n, o);
-    const int t = __shfl_xor(mx, o);
-    mx = t > mx ? t : mx;
-    insum += __shfl_xor(insum, o);
-  }
+  n = wave_sum(n);
+  mx = wave_max(mx);
+  insum = wave_sum(insum);
   if ((threadIdx.x & 63) == 0) {
     wsum[threadIdx.x >> 6] = n;
     wmax[threadIdx.x >> 6] = mx;

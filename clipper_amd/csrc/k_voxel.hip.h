@@ -6,7 +6,7 @@
 //   k_vx_keys      thread = point: (cell number, original index). The indices ascend, and the sort is stable: behind
 //                  it the members of a voxel stand in ascending original index.
 //   k_vx_heads     workgroup = tile of the sorted pairs: how many of them differ from their predecessor (the heads)
-//   (k_sort_scan   over the tiles' head counts: the first output row of each tile, and n_out behind the last)
+//   (k_row_scan    over the tiles' head counts: the first output row of each tile, and n_out behind the last)
 //   k_vx_rows      workgroup = tile: the output row of every sorted position (the heads before it, itself included,
 //                  less one), the first position of every row (start[row], and start[n_out] = n), and the trace
 //   k_vx_partials  thread = sorted position: the first member of a chunk of a voxel with more than VOXEL_CHUNK

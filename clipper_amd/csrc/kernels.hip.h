@@ -25,6 +25,8 @@
 //   k_affinity_sym: the same scores as k_affinity_*, upper block triangle + mirrored stores
 //
 // Files (all in namespace clipper_hip):
+//   k_wave.hip.h      the integer folds and scans of a wave and a workgroup every other file uses (wave_sum, wave_max,
+//                     wave_scan_incl, block_scan_excl, block_scan_array) and the front end's scan kernel k_row_scan
 //   k_solver.hip.h    solver state, the update rules of findDenseClique (cl_project, cl_norm, cl_grad, the penalty
 //                     terms, the live sub-problem's margins), decide (the head of every pass launch), k_init,
 //                     k_tail, k_scal_fold
@@ -50,6 +52,7 @@
 //   k_voxel.hip.h     voxel down-sampling over that sort: one centroid (and normal) per occupied voxel, bit for bit
 #pragma once
 
+#include "k_wave.hip.h"
 #include "k_solver.hip.h"
 #include "k_gemv.hip.h"
 #include "k_csc.hip.h"

@@ -19,7 +19,7 @@
 
 namespace clipper_hip {
 
-constexpr double KNN_GRID_EMPTY = 1.0e300;  // the distance of an empty list entry (k_knn.hip.h's KNN_INF)
+constexpr double KNN_GRID_EMPTY = 1.0e300;  // the distance of an empty list entry, on every route
 
 // The grid over the searched cloud: per axis the cloud's minimum, one factor and the number of slabs. The cells are
 // numbered (z * dim[1] + y) * dim[0] + x, so that a run of cells along x is a run of cell numbers. The slab tables of
@@ -92,6 +92,30 @@ KNN_GRID_HD void knn_grid_insert(double (&bd)[K], int32_t (&bi)[K], double d, in
   }
   bd[0] = at ? d : bd[0];
   bi[0] = at ? j : bi[0];
+}
+
+// The brute-force routes' rule (k_knn.hip.h, k_match.hip.h): their candidates DO arrive in ascending index order, so
+// "strict <, the earlier one stays in front" gives the same (distance, index) order for one comparison per entry
+// instead of two; tests/cpp/test_knn_grid_rules.cpp holds the two rules against each other on such streams.
+template <int K>
+KNN_GRID_HD void knn_insert_first(double (&bd)[K], int32_t (&bi)[K], double dist, int32_t j) {
+  if (dist < bd[K - 1]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = K - 1; k >= 0; --k) {
+      const bool here = (k == 0) || !(dist < bd[k - 1]);
+      if (dist < bd[k]) {
+        if (here) {
+          bd[k] = dist;
+          bi[k] = j;
+        } else {
+          bd[k] = bd[k - 1];
+          bi[k] = bi[k - 1];
+        }
+      }
+    }
+  }
 }
 
 // ---- the walk over the rings -----------------------------------------------------------------------------------------

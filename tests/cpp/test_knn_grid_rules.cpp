@@ -187,7 +187,34 @@ void check(const char* name, const Cloud& Q, const Cloud& P, double max_visit_sh
   check_k<32>(name, Q, P, 1.0);
 }
 
+// The brute-force rule (strict <, the earlier index stays in front) and the lexicographic rule leave the same list when
+// the candidates arrive in ascending index order: streams with exact ties (distances drawn from `levels` values) and
+// with fewer than K candidates, compared after every candidate.
+template <int K>
+void check_insert_rules(Rng& r, int n, size_t levels) {
+  double fd[K], gd[K];
+  int32_t fi[K], gi[K];
+  knn_grid_clear(fd, fi);
+  knn_grid_clear(gd, gi);
+  bool same = true;
+  for (int32_t j = 0; j < n && same; ++j) {
+    const double d = 0.25 * static_cast<double>(r.below(levels));
+    knn_insert_first<K>(fd, fi, d, j);
+    knn_grid_insert<K>(gd, gi, d, j);
+    same = std::memcmp(fd, gd, sizeof(fd)) == 0 && std::memcmp(fi, gi, sizeof(fi)) == 0;
+  }
+  std::printf("insertion rules K=%-2d %3d candidates, %zu distinct distances %s\n", K, n, levels, same ? "equal" : "DIFFERENT");
+  if (!same) ++failures;
+}
+
 int run_rules() {
+  Rng rules_rng(20250117);  // (its own stream: the clouds below keep theirs)
+  for (int n : {0, 1, 5, 64})             // fewer than K = 8 candidates, and many
+    for (size_t levels : {1, 3, 1000}) {  // every distance tied, ties in runs, hardly any
+      check_insert_rules<1>(rules_rng, n, levels);
+      check_insert_rules<2>(rules_rng, n, levels);
+      check_insert_rules<8>(rules_rng, n, levels);
+    }
   Rng r(20240611);
   const Cloud P = uniform_cloud(r, 700), Q = uniform_cloud(r, 150);
   check("uniform 150 x 700", Q, P, 0.5);

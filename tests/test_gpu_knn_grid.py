@@ -108,6 +108,27 @@ def test_grid_knn_edge_clouds_against_the_oracle(search_mode, case):
         _grid_ran(len(Q))
 
 
+SCAN_CHUNK = 1024  # cells one round of the cell table's scan takes (ROW_SCAN_THREADS, k_wave.hip.h)
+
+
+@pytest.mark.parametrize("cells", [SCAN_CHUNK - 1, SCAN_CHUNK, SCAN_CHUNK + 1, 2 * SCAN_CHUNK + 1])
+def test_grid_knn_cell_table_around_the_scan_chunk(search_mode, cells):
+    """A cloud with extent along x only plans dim = (floor(n1 / 4), 1, 1): n1 = 4 cells + 2 puts the cell table just
+    below, at and just above one chunk of its scan, and just above two, where the scan's carry goes from chunk to chunk.
+    The plan is read back, so the case cannot pass by missing the boundary."""
+    rng = np.random.default_rng(cells)
+    n1 = 4 * cells + 2
+    P1 = np.full((n1, 3), 0.5)
+    P1[:, 0] = rng.random(n1)
+    P0 = np.full((200, 3), 0.5)
+    P0[:, 0] = rng.random(200)
+    search_mode(abi.KNN_GRID)
+    for knn in (1, 4):
+        _check_against_oracle(P0, P1, knn)
+        st = _grid_ran(len(P0))
+        assert tuple(st.dim) == (cells, 1, 1)
+
+
 # ---- 2. against the brute-force route on the device, and the pruning cap ----------------------------------------------
 
 @pytest.fixture(scope="module")

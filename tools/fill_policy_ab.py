@@ -70,9 +70,9 @@ def child_kernels():
 def run_child(lib, part):
     env = dict(os.environ, CLIPPER_HIP_LIB=lib)
     env.pop("CLIPPER_HIP_AFFINITY", None)
-    if part == "kernels":
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True,
-                           timeout=300)
+    if part != "bench":  # (the tool that was started: tools/wave_primitives_ab.py brings a part of its own)
+        r = subprocess.run([sys.executable, os.path.abspath(sys.argv[0]), "--child", "--part", part], env=env,
+                           capture_output=True, text=True, timeout=300)
         line = next((l for l in r.stdout.splitlines() if l.startswith("AB_CHILD ")), None)
         if r.returncode != 0 or line is None:
             raise SystemExit(f"child failed ({r.returncode}) on {lib}:\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
@@ -86,7 +86,10 @@ def run_child(lib, part):
     return {"bench.py headline step (m=10000)": j["value"], "bench.py m=100000 step": j["scaling_probe"]["ms_per_step"]}
 
 
-def main():
+def main(parts=None, what="affinity fill: parent (A) against result (B), tools/fill_policy_ab.py",
+         out=os.path.join(ROOT, "profiles", "fill_policy_ab.json")):
+    """parts: name -> the function a child process runs (it prints one AB_CHILD line of row -> ms)"""
+    parts = parts or {"kernels": child_kernels}
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--a")
@@ -94,11 +97,11 @@ def main():
     ap.add_argument("--a-commit", default="")
     ap.add_argument("--b-commit", default="")
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--part", choices=["kernels", "bench"], default="kernels")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fill_policy_ab.json"))
+    ap.add_argument("--part", choices=[*parts, "bench"], default=next(iter(parts)))
+    ap.add_argument("--out", default=out)
     a = ap.parse_args()
     if a.child:
-        return child_kernels()
+        return parts[a.part]()
     libs = {"A": os.path.abspath(a.a), "B": os.path.abspath(a.b), "A2": os.path.abspath(a.a)}
     for lib in libs.values():  # one run of each that does not count: the code objects and the file cache warm
         run_child(lib, a.part)
@@ -120,7 +123,7 @@ def main():
                      "within_noise": mb <= ma + spread}
         if row in ROWS:
             rows[row]["kernel"] = ROWS[row][5]
-    rec = {"what": "affinity fill: parent (A) against result (B), tools/fill_policy_ab.py", "rows": {}}
+    rec = {"what": what, "rows": {}}
     if os.path.exists(a.out):
         rec = json.load(open(a.out))
     rec["parent_commit"], rec["result_commit"] = a.a_commit, a.b_commit

@@ -36,7 +36,7 @@ sys.path.insert(0, ROOT)
 
 from clipper_amd import _abi as abi  # noqa: E402
 
-GROUPS = {"search": ("k_knn_grid", "k_kg_sum", "k_knn_partial", "k_knn_merge", "k_kg_count", "k_kg_scan", "k_kg_scatter", "k_kg_init"),
+GROUPS = {"search": ("k_knn_grid", "k_kg_sum", "k_knn_partial", "k_knn_merge", "k_kg_count", "k_row_scan", "k_kg_scatter", "k_kg_init"),
           "accumulate": ("k_icp_accumulate",), "step": ("k_icp_step",), "transform": ("k_icp_transform",)}
 MODES = {"brute": abi.KNN_BRUTE, "grid": abi.KNN_GRID}
 METHODS = {"point": abi.ICP_POINT_TO_POINT, "plane": abi.ICP_POINT_TO_PLANE}
