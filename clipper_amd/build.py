@@ -2,6 +2,7 @@
 
   clipper_amd/lib/libclipper_hip.so   HIP kernels + C ABI, gfx950 only
   clipper_amd/lib/clipperpy*.so       pybind11 module over the C++ facade (if sources exist)
+  tools/_bin/wave_check               tests/hip/wave_check.hip: the device check of k_wave.hip.h, gfx950 only
 
 The built .so files are git-ignored but travel to the GPU box with the gpurun snapshot.
 """
@@ -18,6 +19,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 HIP_LIB = os.path.join(LIBDIR, "libclipper_hip.so")
+WAVE_CHECK_SRC = os.path.join(ROOT, "tests", "hip", "wave_check.hip")
+WAVE_CHECK = os.path.join(ROOT, "tools", "_bin", "wave_check")  # (git-ignored, like every built file)
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # -ffp-contract=off: fp64 expressions round as written, fma only where spelled out (shared
@@ -78,9 +81,20 @@ def build_pymodule(force: bool = False) -> str | None:
     return out
 
 
+def build_wave_check(force: bool = False) -> str:
+    """tests/hip/wave_check.hip: k_wave.hip.h's folds and scans on the device against host loops. A program of its own
+    over kernels.hip.h with the library's flags (no -shared): it links no library and adds nothing to the ABI. Built
+    here so that the GPU test (tests/test_gpu_wave_primitives.py) compiles nothing."""
+    os.makedirs(os.path.dirname(WAVE_CHECK), exist_ok=True)
+    if force or not _newer(WAVE_CHECK, hip_sources() + [WAVE_CHECK_SRC]):
+        _run([HIPCC, *[f for f in HIP_FLAGS if f not in ("-shared", "-fPIC")], "-I", CSRC, "-o", WAVE_CHECK, WAVE_CHECK_SRC])
+    return WAVE_CHECK
+
+
 def build_all(force: bool = False):
     build_hip(force)
     build_pymodule(force)
+    build_wave_check(force)
 
 
 if __name__ == "__main__":

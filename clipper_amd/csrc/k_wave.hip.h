@@ -78,7 +78,9 @@ __device__ __forceinline__ T block_scan_excl(T v, T* wsum, Op op = Op(), T unit 
 // out[i] (and out2[i], if given) = in[0] + ... + in[i - 1] for i = 0..n-1, in chunks of THREADS elements with a carry;
 // returns the sum of all of them, in every thread. in == out is allowed (in place). wsum: THREADS / 64 words of LDS,
 // carry: one. CONTAINS BARRIERS: the whole workgroup must reach it, with the same n. A thread's next element is in
-// flight while the workgroup scans the current chunk.
+// flight while the workgroup scans the current chunk. n = 0 is allowed: nothing is read or written, 0 is returned.
+// Held on the device by tests/hip/wave_check.hip at every instantiation a kernel uses, n = 0 .. 3 THREADS, in place
+// against out of place, the total in every thread, 64-bit prefixes past 2^32 inside a chunk and across the carry.
 template <int THREADS, typename TIn, typename TOut, typename I>
 __device__ __forceinline__ TOut block_scan_array(const TIn* in, I n, TOut* out, TOut* wsum, TOut* carry,
                                                  TOut* out2 = nullptr) {
