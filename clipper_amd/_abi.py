@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_solve_staged", "clipper_hip_debug_stamps", "clipper_hip_comm_init_callback",
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
+    "clipper_hip_debug_live_resources",
     "clipper_hip_max_clique", "clipper_hip_core_numbers", "clipper_hip_sdp", "clipper_hip_sdp_solve",
     "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
@@ -374,6 +375,8 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_precision_recall.argtypes = [ip, i64, ip, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.clipper_hip_estimate_rigid_transform.argtypes = [dp, i64, dp, i64, ip, i64, dp]
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
+    if hasattr(L, "clipper_hip_debug_live_resources"):  # (absent from an older build named by CLIPPER_HIP_LIB: the A/B tools)
+        L.clipper_hip_debug_live_resources.argtypes = [C.POINTER(i64)]
     L.clipper_hip_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_core_numbers.argtypes = [vp, ip]
     L.clipper_hip_sdp.argtypes = [vp, C.POINTER(SdpParams), dp, dp, dp, dp, C.POINTER(SdpInfo)]
@@ -897,6 +900,16 @@ def debug_occupy(device: int, workgroups: int, lds_bytes: int, milliseconds: flo
     rc = load_library().clipper_hip_debug_occupy(device, workgroups, lds_bytes, float(milliseconds))
     if rc < 0:
         raise ClipperError(f"clipper_hip_debug_occupy: {rc} ({_last_error()})")
+
+
+def debug_live_resources() -> dict:
+    """Test infrastructure: what the library holds in this process right now (device buffers, their bytes, pinned
+    buffers, events) and the allocations and event creations it has made so far."""
+    out = (C.c_int64 * 5)()
+    rc = load_library().clipper_hip_debug_live_resources(out)
+    if rc < 0:
+        raise ClipperError(f"clipper_hip_debug_live_resources: {rc} ({_last_error()})")
+    return dict(zip(("device_buffers", "device_bytes", "pinned_buffers", "events", "allocations"), map(int, out)))
 
 
 def _last_error() -> str:

@@ -1,5 +1,6 @@
-// clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_state.hpp (context, shards,
-// RCCL binding), host_call.hpp (the frame of a stand-alone call: device, temporaries, copies), host_solver.hpp (planning,
+// clipper_hip.hip — the C ABI declared in include/clipper_hip.h. One translation unit: host_buf.hpp (the owners of
+// device memory, pinned memory and events: the only callers of the runtime's allocation functions), host_state.hpp
+// (context, shards, RCCL binding), host_call.hpp (the frame of a stand-alone call: device, temporaries, copies), host_solver.hpp (planning,
 // dispatch, one iteration), host_matrix.hpp (compressed copy, affinity driver), host_solve.hpp (the solve of one context),
 // host_maxclique.hpp (the maximum cliques of a context or a batch), host_matrix_io.hpp (the fills, matrix set / get,
 // mat-vecs; the last driver of a context: it holds its kernels' place in the code object), behind it the stand-alone
@@ -43,6 +44,11 @@
 #include "host_csc_input.hpp"
 
 using namespace clipper_hip;
+
+#include "host_buf.hpp"
+using clipper_hip_buf::DevBuf;
+using clipper_hip_buf::Event;
+using clipper_hip_buf::PinnedBuf;
 
 #include "host_state.hpp"
 #include "host_call.hpp"
@@ -527,10 +533,10 @@ int clipper_hip_set_profiling(clipper_hip_t* h, int on) try {
     HIPCHK(hipSetDevice(h->sh[0].device));
     h->ev_pairs.resize(2 * MAX_EVENT_PAIRS);
     h->ev_launch_index.assign(MAX_EVENT_PAIRS, 0);
-    for (auto& e : h->ev_pairs) HIPCHK(hipEventCreate(&e));
+    for (auto& e : h->ev_pairs) HIPCHK(e.create());
     h->ev_xchg.resize(2 * MAX_EVENT_PAIRS);
     h->ev_xchg_used.assign(MAX_EVENT_PAIRS, 0);
-    for (auto& e : h->ev_xchg) HIPCHK(hipEventCreate(&e));
+    for (auto& e : h->ev_xchg) HIPCHK(e.create());
   }
   return 0;
 } CLIPPER_HIP_GUARD_INT
@@ -560,6 +566,13 @@ int clipper_hip_debug_occupy(int device, int workgroups, int lds_bytes, double m
   if (workgroups < 1 || lds_bytes < 0 || lds_bytes > static_cast<int>(RS_LDS_MAX) || !(milliseconds >= 0.0) || milliseconds > 2000.0)
     return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   return debug_occupy(device, workgroups, lds_bytes, milliseconds);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_debug_live_resources(int64_t out[5]) try {
+  if (!out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  const clipper_hip_buf::LiveCounts& c = clipper_hip_buf::live();
+  out[0] = c.dev_bufs, out[1] = c.dev_bytes, out[2] = c.pinned_bufs, out[3] = c.events, out[4] = c.allocs;
+  return 0;
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int64_t* hbm_bytes) try {
@@ -599,15 +612,9 @@ void clipper_hip_batch_destroy(clipper_hip_batch_t* b) try {
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
   for (Ctx* c : b->kids) destroy_ctx(c);  // (they borrow the batch's stream: it goes last)
-  if (b->hstage) hipHostFree(b->hstage);
-  if (b->dstage) hipFree(b->dstage);
-  if (b->hfill) hipHostFree(b->hfill);
-  if (b->dfill) hipFree(b->dfill);
-  if (b->hmc.p) hipHostFree(b->hmc.p);
-  for (hipEvent_t e : b->ev_fill)
-    if (e) hipEventDestroy(e);
-  if (b->stream) hipStreamDestroy(b->stream);
-  delete b;
+  const hipStream_t st = b->stream;
+  delete b;  // its staging buffers and events
+  if (st) hipStreamDestroy(st);
 } CLIPPER_HIP_GUARD_VOID
 
 int clipper_hip_batch_solve_euclidean(clipper_hip_batch_t* b, const clipper_batch_problem_t* p, int32_t n, int d,

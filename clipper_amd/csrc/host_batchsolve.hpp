@@ -39,20 +39,16 @@ struct clipper_hip_batch {
   std::vector<Result> res;  // of the last call
   int launches = 0, n_batched = 0, n_alone = 0;
   double t_fill = 0.0, t_launch = 0.0, t_alone = 0.0, t_round = 0.0;
-  uint8_t* hstage = nullptr;  // pinned staging of the inputs, then of the launch tables
-  size_t hstage_cap = 0;
-  uint8_t* dstage = nullptr;  // its device copy
-  size_t dstage_cap = 0;
-  uint8_t* hfill = nullptr;  // pinned staging of a custom fill's problems and tiles (kind 3)
-  size_t hfill_cap = 0;
-  uint8_t* dfill = nullptr;  // its device copy
-  size_t dfill_cap = 0;
-  hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around a custom fill's launch
+  PinnedBuf<uint8_t> hstage;  // staging of the inputs, then of the launch tables
+  DevBuf<uint8_t> dstage;     // its device copy
+  PinnedBuf<uint8_t> hfill;   // staging of a custom fill's problems and tiles (kind 3)
+  DevBuf<uint8_t> dfill;      // its device copy
+  Event ev_fill[2];           // around a custom fill's launch
   double t_fill_begin = 0.0, t_fill_launch = 0.0, t_fill_build = 0.0;  // kind 3: the parts of t_fill (ms)
   bool solved = false;                  // a solve call has succeeded: `res` and the children describe its problems
   std::unique_ptr<SdpBatchState> sdp;   // the last clipper_hip_batch_sdp (host_sdpbatch.hpp), until the next call
   int mc_launches = 0, mc_batched = 0, mc_alone = 0;  // the last clipper_hip_batch_max_clique (host_maxclique.hpp)
-  PinnedBuf hmc;  // its staging buffer, kept from call to call
+  PinnedBuf<uint8_t> hmc;  // its staging buffer, kept from call to call
 };
 
 namespace {
@@ -60,25 +56,13 @@ namespace {
 using Batch = clipper_hip_batch;
 
 // a pinned buffer and its device copy of at least `bytes` each (contents lost when they grow)
-int stage_grow(uint8_t*& hbuf, size_t& hcap, uint8_t*& dbuf, size_t& dcap, size_t bytes) {
-  if (bytes > hcap) {
-    if (hbuf) HIPCHK(hipHostFree(hbuf));
-    hbuf = nullptr;
-    hcap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hbuf), bytes, hipHostMallocDefault));
-    hcap = bytes;
-  }
-  if (bytes > dcap) {
-    if (dbuf) HIPCHK(hipFree(dbuf));
-    dbuf = nullptr;
-    dcap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dbuf), bytes));
-    dcap = bytes;
-  }
+int stage_grow(PinnedBuf<uint8_t>& hbuf, DevBuf<uint8_t>& dbuf, size_t bytes) {
+  HIPCHK(hbuf.grow(bytes));
+  HIPCHK(dbuf.grow(bytes));
   return 0;
 }
 
-int batch_grow(Batch* b, size_t bytes) { return stage_grow(b->hstage, b->hstage_cap, b->dstage, b->dstage_cap, bytes); }
+int batch_grow(Batch* b, size_t bytes) { return stage_grow(b->hstage, b->dstage, bytes); }
 
 // what lives for one batch_solve call: its arguments, and
 struct BatchCall {
@@ -145,9 +129,9 @@ int batch_fill_custom(Batch* b, const BatchCall& K) {
 
   // the problems and the tile table: one copy, one launch
   const size_t pbytes = static_cast<size_t>(round_up(static_cast<int64_t>(n) * sizeof(CustomFillProblem), 256));
-  if (int rc = stage_grow(b->hfill, b->hfill_cap, b->dfill, b->dfill_cap, pbytes + ntiles * sizeof(CustomFillTile)))
+  if (int rc = stage_grow(b->hfill, b->dfill, pbytes + ntiles * sizeof(CustomFillTile)))
     return rc;
-  CustomFillProblem* probs = reinterpret_cast<CustomFillProblem*>(b->hfill);
+  CustomFillProblem* probs = reinterpret_cast<CustomFillProblem*>(b->hfill.p);
   CustomFillTile* tiles = reinterpret_cast<CustomFillTile*>(b->hfill + pbytes);
   size_t t = 0;
   for (int32_t i = 0; i < n; ++i) {
@@ -160,12 +144,12 @@ int batch_fill_custom(Batch* b, const BatchCall& K) {
   }
   HIPCHK(hipMemcpyAsync(b->dfill, b->hfill, pbytes + ntiles * sizeof(CustomFillTile), hipMemcpyHostToDevice, b->stream));
   if (!b->ev_fill[0]) {
-    HIPCHK(hipEventCreate(&b->ev_fill[0]));
-    HIPCHK(hipEventCreate(&b->ev_fill[1]));
+    HIPCHK(b->ev_fill[0].create());
+    HIPCHK(b->ev_fill[1].create());
   }
   const auto t1 = std::chrono::high_resolution_clock::now();
   {
-    const CustomFillProblem* dprobs = reinterpret_cast<const CustomFillProblem*>(b->dfill);
+    const CustomFillProblem* dprobs = b->dfill.as<const CustomFillProblem>();
     const CustomFillTile* dtiles = reinterpret_cast<const CustomFillTile*>(b->dfill + pbytes);
     int rows = AFF_ROWS_PER_BLK;
     CustomParams prm = cf.prm;
@@ -378,7 +362,7 @@ int batch_launch_resident(Batch* b, BatchCall& K) {
     for (int k : l.items)
       for (int u = 0; u < items[static_cast<size_t>(k)].units; ++u) tab[e++] = ResidentLaunchEntry{k, u};
   HIPCHK(hipMemcpyAsync(b->dstage, b->hstage, tb, hipMemcpyHostToDevice, b->stream));
-  const ResidentArgs* dargs = reinterpret_cast<const ResidentArgs*>(b->dstage);
+  const ResidentArgs* dargs = b->dstage.as<const ResidentArgs>();
   const ResidentLaunchEntry* dtab = reinterpret_cast<const ResidentLaunchEntry*>(b->dstage + args_bytes);
   size_t e0 = 0;
   for (const auto& l : L) {
@@ -440,7 +424,7 @@ int batch_round(Batch* b, const BatchCall& K) {
     Batch::Result& R = b->res[static_cast<size_t>(i)];
     Ctx* c = b->kids[static_cast<size_t>(i)];
     if (R.route == 1) {
-      c->u_host.assign(c->u_pinned, c->u_pinned + c->m);
+      c->u_host.assign(c->u_pinned.p, c->u_pinned.p + c->m);
       if (int rc = round_nodes(c, K.P->rounding, c->u_host, R.info.score, R.nodes)) return rc;
       c->nodes = R.nodes;
       R.u = c->u_host;

@@ -26,18 +26,15 @@ int use_device(int device) {
 // device temporaries of one call, released when it goes out of scope: on every path (hipFree waits for the device, so
 // nothing the call queued is in flight once they are gone: host arrays declared before it outlive every copy)
 struct DevTemps {
-  std::vector<std::pair<int, void*>> v;
-  ~DevTemps() {
-    for (auto& p : v) {
-      hipSetDevice(p.first);
-      hipFree(p.second);
-    }
-  }
+  std::vector<DevBuf<void>> v;
   // n bytes on device dev (current): 0, or CLIPPER_HIP_E_NOMEM with the report made
   template <typename T>
   int alloc(int dev, T*& p, size_t n) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16)));
-    v.emplace_back(dev, p);
+    DevBuf<void> b;
+    HIPCHK(b.alloc(std::max<size_t>(n, 16)));
+    b.device = dev;
+    p = b.as<T>();
+    v.push_back(std::move(b));
     return 0;
   }
   // several at once, as (pointer, bytes) pairs in order: stops at the first that fails

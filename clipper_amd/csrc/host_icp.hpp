@@ -16,13 +16,8 @@ namespace {
 
 // what the loop needs besides device memory: a pinned record and two events, released on every path
 struct IcpHostState {
-  IcpRecord* rec = nullptr;
-  hipEvent_t a = nullptr, b = nullptr;
-  ~IcpHostState() {
-    if (rec) hipHostFree(rec);
-    if (a) hipEventDestroy(a);
-    if (b) hipEventDestroy(b);
-  }
+  PinnedBuf<IcpRecord> rec;
+  Event a, b;
 };
 
 template <int METHOD>
@@ -71,9 +66,9 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     return rc;
   if (gen)  // (behind the buffers every method has: theirs keep their places)
     if (int rc = tmp.alloc(device, dCs, s1 * 6 * sizeof(double), dCt, static_cast<size_t>(nt) * 6 * sizeof(double))) return rc;
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hs.rec), sizeof(IcpRecord)));
-  HIPCHK(hipEventCreate(&hs.a));
-  HIPCHK(hipEventCreate(&hs.b));
+  HIPCHK(hs.rec.alloc(1));
+  HIPCHK(hs.a.create());
+  HIPCHK(hs.b.create());
 
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
   IcpRecord first{};

@@ -16,7 +16,7 @@ thread_local clipper_hip_knn_stats_t g_knn_stats{-1, {0, 0, 0}, 0, 0, CLIPPER_HI
 // two events around the kernels of the calling thread's last search, kept from call to call on one device; read by
 // clipper_hip_knn_last_search, after the searching call has returned (every caller of the seam waits for its stream)
 struct KnnEvents {
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   int device = -1;
   bool pending = false;
 };
@@ -26,11 +26,9 @@ inline bool knn_events_begin(int device, hipStream_t st) {
   KnnEvents& ev = g_knn_events;
   ev.pending = false;
   if (ev.device != device || !ev.a || !ev.b) {
-    if (ev.a) hipEventDestroy(ev.a);
-    if (ev.b) hipEventDestroy(ev.b);
-    ev.a = ev.b = nullptr;
+    ev.a.reset(), ev.b.reset();
     ev.device = device;
-    if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return false;
+    if (ev.a.create() != hipSuccess || ev.b.create() != hipSuccess) return false;
   }
   return hipEventRecord(ev.a, st) == hipSuccess;
 }

@@ -47,8 +47,7 @@ int ensure_dense(Ctx* h, bool from_csc) {
   for (auto& s : h->sh) {
     if (s.S) continue;
     HIPCHK(hipSetDevice(s.device));
-    if (hipMalloc(&s.S, s.bytes_S) != hipSuccess) {
-      s.S = nullptr;
+    if (s.S.alloc(s.bytes_S) != hipSuccess) {
       (void)hipGetLastError();
       return fail(CLIPPER_HIP_E_NOMEM, "dense store of %zu bytes (this call needs one) does not fit",
                   s.bytes_S);
@@ -59,7 +58,7 @@ int ensure_dense(Ctx* h, bool from_csc) {
       dispatch_vt(h, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((k_slice_expand<T, SL_H, T>), grid, block, 0, s.stream, slice_view(h, s),
-                           static_cast<T*>(s.S), h->W, h->m);
+                           s.S.as<T>(), h->W, h->m);
       });
       HIPCHK(hipStreamSynchronize(s.stream));
     }
@@ -70,32 +69,16 @@ int ensure_dense(Ctx* h, bool from_csc) {
 // the explicit constraint store of every local shard (C != pattern(M)) released
 void drop_explicit_c(Ctx* h) {
   for (auto& s : h->sh) {
-    if (!s.Cs) continue;
     hipSetDevice(s.device);
-    hipFree(s.Cs);
-    s.Cs = nullptr;
+    s.Cs.reset();
   }
 }
 
 void drop_dense(Ctx* h) {
   for (auto& s : h->sh) {
-    if (!s.S) continue;
     hipSetDevice(s.device);
-    hipFree(s.S);
-    s.S = nullptr;
+    s.S.reset();
   }
-}
-
-// a device array of at least `need` elements: reallocated (contents lost) when `cap` is smaller
-template <typename T>
-int grow_dev(T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return 0;
-  if (p) hipFree(p);
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(need, 1) * sizeof(T)));
-  cap = need;
-  return 0;
 }
 
 // A small copy between pinned host memory and the device: a k_copy_words launch of `grid` workgroups through the
@@ -122,35 +105,26 @@ unsigned copy_grid(size_t bytes) { return static_cast<unsigned>(std::min<size_t>
 // over all columns, host_rowview.hpp)
 int slices_arrays(Ctx* h, Shard& sh, SliceStore& s, int64_t nrows, int64_t wcols = -1) {
   HIPCHK(hipSetDevice(sh.device));
-  if (!sh.cctl) HIPCHK(hipMalloc(&sh.cctl, CSC_ARENAS * sizeof(CscBuildCtl)));
+  if (!sh.cctl) HIPCHK(sh.cctl.alloc(CSC_ARENAS));
   s.s_ncg = static_cast<int>((wcols > 0 ? wcols : h->W) / SL_W);
   s.s_nchunks = static_cast<int>(ceil_div(nrows, SL_SUB * SL_H));
   const size_t nsl = static_cast<size_t>(s.s_ncg) * s.s_nchunks;
-  if (nsl > s.scap_slices) {
-    for (void** p : {reinterpret_cast<void**>(&s.sSizes), reinterpret_cast<void**>(&s.sLq),
-                     reinterpret_cast<void**>(&s.sPre), reinterpret_cast<void**>(&s.sBlk)}) {
-      if (*p) hipFree(*p);
-      *p = nullptr;
-    }
-    s.scap_slices = 0;
-    HIPCHK(hipMalloc(&s.sSizes, nsl * sizeof(uint32_t)));
-    // (room behind the directory words for the arena counters of a direct emission: one read-back)
-    HIPCHK(hipMalloc(&s.sLq, round_up(nsl, 32) * sizeof(uint32_t) + CSC_ARENAS * sizeof(CscBuildCtl)));
-    HIPCHK(hipMalloc(&s.sPre, nsl * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&s.sBlk, (ceil_div(nsl, SCAN_BLK) + 4) * sizeof(uint64_t)));
-    s.scap_slices = nsl;
+  // (room behind the directory words for the arena counters of a direct emission: one read-back)
+  const size_t dir_bytes = round_up(nsl, 32) * sizeof(uint32_t) + CSC_ARENAS * sizeof(CscBuildCtl);
+  if (nsl > s.sSizes.cap || !s.sBlk) {  // the four go together, then come together (sBlk last: without it the group is not whole)
+    s.sSizes.reset(), s.sLq.reset(), s.sPre.reset(), s.sBlk.reset();
+    HIPCHK(s.sSizes.alloc(nsl));
+    HIPCHK(s.sLq.alloc_bytes(dir_bytes));
+    HIPCHK(s.sPre.alloc(nsl));
+    HIPCHK(s.sBlk.alloc(ceil_div(nsl, SCAN_BLK) + 4));
   }
-  if (nsl > h->csc_hcap_slices) {
-    if (h->csc_hLq) hipHostFree(h->csc_hLq);
-    h->csc_hLq = nullptr;
-    h->csc_hcap_slices = 0;
-    HIPCHK(hipHostMalloc(&h->csc_hLq, round_up(nsl, 32) * sizeof(uint32_t) + CSC_ARENAS * sizeof(CscBuildCtl),
-                         hipHostMallocDefault));
-    h->csc_hcap_slices = nsl;
+  if (nsl > h->csc_hLq_slices || !h->csc_hLq) {
+    h->csc_hLq_slices = 0;
+    HIPCHK(h->csc_hLq.alloc_bytes(dir_bytes));
+    h->csc_hLq_slices = nsl;
   }
-  if (!h->csc_hctl)
-    HIPCHK(hipHostMalloc(&h->csc_hctl, 2 * CSC_ARENAS * sizeof(CscBuildCtl), hipHostMallocDefault));
-  if (!h->csc_htotal) HIPCHK(hipHostMalloc(&h->csc_htotal, 2 * sizeof(uint64_t), hipHostMallocDefault));
+  if (!h->csc_hctl) HIPCHK(h->csc_hctl.alloc(2 * CSC_ARENAS));
+  if (!h->csc_htotal) HIPCHK(h->csc_htotal.alloc(2));
   return 0;
 }
 int slices_arrays(Ctx* h, Shard& s) { return slices_arrays(h, s, s, h->m); }
@@ -173,7 +147,7 @@ int emit_prepare(Ctx* h, Shard& sh, SliceStore& s, int64_t nrows, SliceOut& out,
   out = SliceOut{};
   if (!csc_applies(h)) return 0;
   if (int rc = slices_arrays(h, sh, s, nrows, wcols)) return rc;
-  const size_t units = s.scap_bytes >= SL_TAILPAD ? (s.scap_bytes - SL_TAILPAD) / 16 : 0;
+  const size_t units = s.sdata.cap >= SL_TAILPAD ? (s.sdata.cap - SL_TAILPAD) / 16 : 0;
   CscBuildCtl* init = arena_init(h, units);
   // the counters live right behind this build's directory words: both come back in ONE copy
   CscBuildCtl* ectl = reinterpret_cast<CscBuildCtl*>(
@@ -224,14 +198,9 @@ int emit_check(Ctx* h, Shard& sh, SliceStore& s, bool whole, bool& again, bool p
   }
   if (over) {
     const size_t need = worst * CSC_ARENAS;  // every arena as large as the fullest one
-    if (s.sdata) hipFree(s.sdata);
-    s.sdata = nullptr;
-    s.scap_bytes = 0;
     const size_t units = (need + need / 8 + 256 * CSC_ARENAS) / CSC_ARENAS * CSC_ARENAS;
-    const size_t cap = units * 16 + SL_TAILPAD;
-    HIPCHK(hipMalloc(&s.sdata, cap));
+    HIPCHK(s.sdata.alloc(units * 16 + SL_TAILPAD));
     HIPCHK(hipMemsetAsync(s.sdata + units * 16, 0, SL_TAILPAD, sh.stream));
-    s.scap_bytes = cap;
     again = true;
     return 0;
   }
@@ -256,22 +225,17 @@ int groups_prepare(Ctx* h, Shard& s, GroupOut<VT>& out) {
   h->csc_nblocks = static_cast<int>(ceil_div(h->m, GR_RB));
   h->csc_nstrips = static_cast<int>(ceil_div(h->W, GR_CW));
   const size_t G = static_cast<size_t>(h->csc_nstrips) * static_cast<size_t>(h->csc_nblocks);
-  if (G > s.gcap_groups) {
-    if (s.gOff) hipFree(s.gOff);
-    if (s.gPre) hipFree(s.gPre);
-    s.gOff = nullptr;
-    s.gPre = nullptr;
-    s.gcap_groups = 0;
-    HIPCHK(hipMalloc(&s.gOff, G * GR_OFFS * sizeof(uint16_t)));
-    HIPCHK(hipMalloc(&s.gPre, G * sizeof(uint64_t)));
-    s.gcap_groups = G;
+  if (G > s.gPre.cap) {
+    s.gOff.reset(), s.gPre.reset();
+    HIPCHK(s.gOff.alloc(G * GR_OFFS));
+    HIPCHK(s.gPre.alloc(G));
   }
   if (int rc = slices_arrays(h, s)) return rc;
-  HIPCHK(hipMemcpyAsync(s.cctl, arena_init(h, s.gcap_units), CSC_ARENAS * sizeof(CscBuildCtl), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(s.cctl, arena_init(h, s.gcap_units()), CSC_ARENAS * sizeof(CscBuildCtl), hipMemcpyHostToDevice,
                         s.stream));
   out.Goff = s.gOff;
   out.Gpre = s.gPre;
-  out.vals = static_cast<VT*>(s.gvals);
+  out.vals = s.gvals.as<VT>();
   out.rows = s.grows;
   out.ctl = s.cctl;
   out.nblocks = h->csc_nblocks;
@@ -299,7 +263,7 @@ int slices_enqueue(Ctx* h, Shard& s, const Source& src, const CscBuildCtl* ctl) 
     hipLaunchKernelGGL(k_slice_scan_add, dim3(static_cast<unsigned>(nblk)), b256, 0, s.stream, s.sPre,
                        nsl, s.sBlk);
   }
-  const uint64_t cap_units = s.scap_bytes >= SL_TAILPAD ? (s.scap_bytes - SL_TAILPAD) / 16 : 0;
+  const uint64_t cap_units = s.sdata.cap >= SL_TAILPAD ? (s.sdata.cap - SL_TAILPAD) / 16 : 0;
   int heavy_only = 0;
   if constexpr (std::is_same<Source, GroupSource<VT>>::value && SL_H == 1) {
     // the common case through LDS (coalesced), only the slices of dense blocks by per-lane gathers
@@ -326,7 +290,7 @@ GroupSource<VT> group_source(const Ctx* h, const Shard& s) {
   GroupSource<VT> g{};
   g.Goff = s.gOff;
   g.Gpre = s.gPre;
-  g.vals = static_cast<const VT*>(s.gvals);
+  g.vals = s.gvals.as<const VT>();
   g.rows = s.grows;
   g.nblocks = h->csc_nblocks;
   g.ncols = static_cast<int64_t>(h->csc_nstrips) * GR_CW;
@@ -346,17 +310,11 @@ int slices_plan(Ctx* h, Shard& sh, SliceStore& s, bool whole) {
   s.s_entries = plan.entries;
   const int nslots = plan.nslots;
   const size_t nw = plan.work.size();
-  if (nw > h->csc_hcap_work) {
-    if (h->csc_hwork) hipHostFree(h->csc_hwork);
-    h->csc_hwork = nullptr;
-    h->csc_hcap_work = 0;
-    HIPCHK(hipHostMalloc(&h->csc_hwork, (nw + 1024) * sizeof(SliceWork), hipHostMallocDefault));
-    h->csc_hcap_work = nw + 1024;
-  }
+  if (nw > h->csc_hwork.cap) HIPCHK(h->csc_hwork.alloc(nw + 1024));
   std::memcpy(h->csc_hwork, plan.work.data(), nw * sizeof(SliceWork));
   HIPCHK(hipSetDevice(sh.device));
-  int rc = grow_dev(s.swork, s.scap_work, nw);
-  if (rc) return rc;
+  HIPCHK(s.swork.grow(std::max<size_t>(nw, 1)));
+  int rc;
   const size_t bytes = nw * sizeof(SliceWork);  // 32 bytes each
   if ((rc = copy_small(sh.stream, h->csc_hwork, s.swork, bytes, true, copy_grid(bytes), 1u << 20))) return rc;
   // the pinned staging is shared by every store and shard of the context: the copy has to be
@@ -366,10 +324,9 @@ int slices_plan(Ctx* h, Shard& sh, SliceStore& s, bool whole) {
   const size_t NSLOT = static_cast<size_t>(nslot(h->V));
   if (static_cast<size_t>(nslots) > sh.part_tiles) {
     HIPCHK(hipStreamSynchronize(sh.stream));
-    HIPCHK(hipFree(sh.part));
-    sh.part = nullptr;
+    sh.part_tiles = 0;
+    HIPCHK(sh.part.alloc((static_cast<size_t>(nslots) + 8) * NSLOT * static_cast<size_t>(h->W)));
     sh.part_tiles = static_cast<size_t>(nslots) + 8;
-    HIPCHK(hipMalloc(&sh.part, sh.part_tiles * NSLOT * static_cast<size_t>(h->W) * sizeof(double)));
   }
   s.s_nwork = static_cast<int>(nw);
   s.s_nslots = nslots;
@@ -393,27 +350,18 @@ int slices_check(Ctx* h, Shard& s, bool with_groups, bool& again) {
     }
     if (over) {
       const size_t need = worst * CSC_ARENAS;  // every arena as large as the fullest one
-      if (s.gvals) hipFree(s.gvals);
-      if (s.grows) hipFree(s.grows);
-      s.gvals = nullptr;
-      s.grows = nullptr;
-      s.gcap_units = 0;
+      s.gvals.reset(), s.grows.reset();
       const size_t units = (need + need / 8 + 64 * CSC_ARENAS) / CSC_ARENAS * CSC_ARENAS;
-      HIPCHK(hipMalloc(&s.gvals, units * 4 * sizeof(VT)));
-      HIPCHK(hipMalloc(&s.grows, units * 4));
-      s.gcap_units = units;
+      HIPCHK(s.gvals.alloc(units * 4 * sizeof(VT)));
+      HIPCHK(s.grows.alloc(units * 4));
       again = true;
     }
   }
   const uint64_t bytes = h->csc_htotal[0] * 16;
-  if (bytes + SL_TAILPAD > s.scap_bytes) {
-    if (s.sdata) hipFree(s.sdata);
-    s.sdata = nullptr;
-    s.scap_bytes = 0;
+  if (bytes + SL_TAILPAD > s.sdata.cap) {
     const size_t cap = static_cast<size_t>(bytes) + static_cast<size_t>(bytes) / 16 + SL_TAILPAD + 4096;
-    HIPCHK(hipMalloc(&s.sdata, cap));
+    HIPCHK(s.sdata.alloc(cap));
     HIPCHK(hipMemsetAsync(s.sdata + bytes, 0, cap - bytes, s.stream));
-    s.scap_bytes = cap;
     again = true;
   }
   if (again) return 0;
@@ -438,7 +386,7 @@ int build_wait(Shard& s, const char* what) {
 template <typename VT>
 int groups_enqueue(Ctx* h, Shard& s, const GroupOut<VT>& O) {
   dim3 grid(h->csc_nstrips, static_cast<unsigned>(ceil_div(h->csc_nblocks, 2))), block(256);
-  hipLaunchKernelGGL((k_groups_from_dense<VT>), grid, block, 0, s.stream, static_cast<const VT*>(s.S), h->W, h->m, O);
+  hipLaunchKernelGGL((k_groups_from_dense<VT>), grid, block, 0, s.stream, s.S.as<const VT>(), h->W, h->m, O);
   return slices_enqueue<VT>(h, s, group_source<VT>(h, s), s.cctl);
 }
 
@@ -519,8 +467,8 @@ int run_affinity_rect(Ctx* h, double& kernel_ms) {
   Shard& s0 = h->sh[0];
   HIPCHK(hipSetDevice(s0.device));
   if (!h->ev_aff[0]) {
-    HIPCHK(hipEventCreate(&h->ev_aff[0]));
-    HIPCHK(hipEventCreate(&h->ev_aff[1]));
+    HIPCHK(h->ev_aff[0].create());
+    HIPCHK(h->ev_aff[1].create());
   }
   std::vector<char> pending(h->sh.size(), 1);
   kernel_ms = 0.0;
@@ -638,8 +586,8 @@ int run_affinity(Ctx* h, bool emits, Launch launch, bool* queued = nullptr) {
   Shard& s0 = h->sh[0];
   HIPCHK(hipSetDevice(s0.device));
   if (!h->ev_aff[0]) {
-    HIPCHK(hipEventCreate(&h->ev_aff[0]));
-    HIPCHK(hipEventCreate(&h->ev_aff[1]));
+    HIPCHK(h->ev_aff[0].create());
+    HIPCHK(h->ev_aff[1].create());
   }
   if (emit && queued) {
     *queued = true;
@@ -751,11 +699,11 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
     if (int rc = ensure_dense(h, true)) return rc;
   for (auto& s : h->sh) {
     HIPCHK(hipSetDevice(s.device));
-    int32_t* didx = nullptr;
-    double* dout = nullptr;
+    DevBuf<int32_t> didx;
+    DevBuf<double> dout;
     const size_t nidx = from_slices ? pos.size() : static_cast<size_t>(k);
-    HIPCHK(hipMalloc(&didx, nidx * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&dout, tmp.size() * sizeof(double)));
+    HIPCHK(didx.alloc(nidx));
+    HIPCHK(dout.alloc(tmp.size()));
     HIPCHK(hipMemcpyAsync(didx, from_slices ? pos.data() : S.data(), nidx * sizeof(int32_t),
                           hipMemcpyHostToDevice, s.stream));
     HIPCHK(hipMemsetAsync(dout, 0, tmp.size() * sizeof(double), s.stream));
@@ -772,7 +720,7 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
       dim3 grid(static_cast<unsigned>(ceil_div(static_cast<int64_t>(k) * k, 256))), block(256);
       dispatch_vt(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((k_gather_sub<T>), grid, block, 0, s.stream, static_cast<const T*>(s.S), h->W, c0, h->W, didx,
+        hipLaunchKernelGGL((k_gather_sub<T>), grid, block, 0, s.stream, s.S.as<const T>(), h->W, c0, h->W, didx,
                            k, dout);
       });
     }
@@ -780,8 +728,8 @@ int densest_subgraph_of(Ctx* h, const std::vector<int32_t>& S, std::vector<int32
     HIPCHK(hipMemcpyAsync(tmp.data(), dout, tmp.size() * sizeof(double), hipMemcpyDeviceToHost,
                           s.stream));
     HIPCHK(hipStreamSynchronize(s.stream));
-    hipFree(didx);
-    hipFree(dout);
+    didx.reset();
+    dout.reset();
     for (size_t e = 0; e < tmp.size(); ++e) Wsub[e] += tmp[e];  // disjoint column sets
   }
   if (h->csc_valid) drop_dense(h);  // a copy materialised for this gather only: M lives in the slices

@@ -49,12 +49,12 @@ int fill_builtin(Ctx* h, const FillInvariant& inv, bool* queued) {
         const dim3 grid(static_cast<unsigned>(ceil_div(W, 1024)), static_cast<unsigned>(ceil_div(mm, AFF_ROWS_PER_BLK)));
         if constexpr (Inv::PD > 0) {
           if (compact) {
-            hipLaunchKernelGGL((k_affinity_compact<T, Inv>), grid, dim3(256), 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
+            hipLaunchKernelGGL((k_affinity_compact<T, Inv>), grid, dim3(256), 0, s.stream, s.S.as<T>(), W, mm, c0,
                                AFF_ROWS_PER_BLK, s.P1, s.P2, s.P1f, s.P2f, pstride, A0, A1, prm, thr);
             return;
           }
         }
-        hipLaunchKernelGGL((k_affinity_plain<T, Inv>), grid, dim3(256), 0, s.stream, static_cast<T*>(s.S), W, mm, c0,
+        hipLaunchKernelGGL((k_affinity_plain<T, Inv>), grid, dim3(256), 0, s.stream, s.S.as<T>(), W, mm, c0,
                            AFF_ROWS_PER_BLK, d, s.P1, s.P2, pstride, A0, A1, prm);
       });
       if (sym) h->csc_emitted = (h->csc_out.Pre != nullptr);
@@ -151,7 +151,7 @@ int set_dense(Ctx* h, const double* M, const double* C, int64_t m) {
     const int64_t c0 = static_cast<int64_t>(s.slot) * W;
     dispatch_vt(h, [&](auto t) {
       using T = decltype(t);
-      hipLaunchKernelGGL((k_from_dense_upper<T>), grid, block, 0, s.stream, static_cast<T*>(s.S), W, m, c0, dM[k],
+      hipLaunchKernelGGL((k_from_dense_upper<T>), grid, block, 0, s.stream, s.S.as<T>(), W, m, c0, dM[k],
                          dC[k], static_cast<T*>(Cs), flag);
     });
   };
@@ -191,7 +191,7 @@ int set_dense(Ctx* h, const double* M, const double* C, int64_t m) {
     for (size_t k = 0; k < h->sh.size(); ++k) {
       Shard& s = h->sh[k];
       HIPCHK(hipSetDevice(s.device));
-      HIPCHK(hipMalloc(&s.Cs, s.bytes_S));
+      HIPCHK(s.Cs.alloc(s.bytes_S));
       from_dense(k, s.Cs, nullptr);
     }
   }
@@ -266,7 +266,7 @@ int sparse_to_dense(Ctx* h, const clipper_csc::CscRef& M, const clipper_csc::Csc
     HIPCHK(hipSetDevice(s.device));
     if ((rc = scatter(s, s.S, M))) return rc;
     if (h->explicitC) {
-      HIPCHK(hipMalloc(&s.Cs, s.bytes_S));
+      HIPCHK(s.Cs.alloc(s.bytes_S));
       if ((rc = scatter(s, s.Cs, C))) return rc;
     }
   }
@@ -393,12 +393,8 @@ int view_matvec(Ctx* h, const int32_t* rows, int64_t nrows, const double* x, dou
   HIPCHK(hipStreamSynchronize(s.stream));
   v.valid = false;
   int rc;
-  {
-    size_t r0 = v.cap_rows, r1 = v.cap_rows;
-    if ((rc = grow_dev(v.rowmap[0], r0, static_cast<size_t>(h->mp)))) return rc;
-    if ((rc = grow_dev(v.rowmap[1], r1, static_cast<size_t>(h->mp)))) return rc;
-    v.cap_rows = static_cast<size_t>(h->mp);
-  }
+  HIPCHK(v.rowmap[0].grow(static_cast<size_t>(h->mp)));
+  HIPCHK(v.rowmap[1].grow(static_cast<size_t>(h->mp)));
   HIPCHK(hipMemcpyAsync(v.rowmap[0], rows, static_cast<size_t>(nrows) * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
   if ((rc = emit_rect(h, s, v.st, v.rowmap[0], nrows, -1, -1, true, 3, "row view"))) return rc;
   if ((rc = stage_x(h, s, x))) return rc;
@@ -425,9 +421,9 @@ int bench_matvec(Ctx* h, int reps, double* avg_us) {
     if (int rc = ensure_dense(h, true)) return rc;
   Shard& s = h->sh[0];
   HIPCHK(hipSetDevice(s.device));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  Event e0, e1;  // (gone on every path out of here)
+  HIPCHK(e0.create());
+  HIPCHK(e1.create());
   for (int w = 0; w < 3; ++w) launch_plain(h, s, s.X[0]);
   HIPCHK(hipEventRecord(e0, s.stream));
   for (int r = 0; r < reps; ++r) launch_plain(h, s, s.X[0]);
@@ -435,8 +431,6 @@ int bench_matvec(Ctx* h, int reps, double* avg_us) {
   HIPCHK(hipStreamSynchronize(s.stream));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
   *avg_us = static_cast<double>(ms) * 1e3 / reps;
   h->tm.gemv_bytes = algorithmic_gemv_bytes(h, /*dense=*/!h->csc_valid);
   return 0;

@@ -37,14 +37,11 @@ static_assert(sizeof(McProb) % 8 == 0 && sizeof(McCtl) % 8 == 0 && sizeof(McSlot
 
 // a device slab and the pinned mirror of its host-visible tail [host_begin, bytes)
 struct McSlab {
-  uint8_t *dev = nullptr, *host = nullptr;
+  DevBuf<uint8_t> dev;
+  uint8_t* host = nullptr;
   size_t host_begin = 0;
-  ~McSlab() {
-    if (dev) hipFree(dev);
-  }
   int alloc(size_t bytes) {
-    if (hipMalloc(reinterpret_cast<void**>(&dev), std::max<size_t>(bytes, 8)) != hipSuccess) {
-      dev = nullptr;
+    if (dev.alloc(std::max<size_t>(bytes, 8)) != hipSuccess) {
       (void)hipGetLastError();
       return fail(CLIPPER_HIP_E_NOMEM, "max clique: device allocation of %zu bytes failed", bytes);
     }
@@ -93,7 +90,7 @@ int mc_check_scope(const Ctx* h) {
 // `method` mc_check_method) and share a device, a value type and the stream `st`. R[k] is cs[k]'s result; `launches`
 // counts the kernel launches. An error that is one problem's leaves its index in `fault`. seeds: null, or a checked
 // vertex list per problem (mc_check_seed) and `method` may be CLIPPER_HIP_MC_SEED_ONLY.
-int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStream_t st, int device, PinnedBuf& stage,
+int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStream_t st, int device, PinnedBuf<uint8_t>& stage,
            int& launches, std::vector<McResult>& R, size_t& fault, const McSeeds* seeds = nullptr) {
   namespace plan = clipper_mc_plan;
   using clk = std::chrono::steady_clock;
@@ -125,7 +122,7 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
   McSlab g, x;  // the graph part, the search part
   if (int rc = g.alloc(L.bytes)) return rc;
   const size_t ghost = L.bytes - L.host_begin;
-  if (int rc = pinned_grow(stage, ghost + plan::search_host_bound(cap, nb, sizeof(McSlot)))) return rc;
+  HIPCHK(stage.grow(ghost + plan::search_host_bound(cap, nb, sizeof(McSlot))));
   g.host = stage.p;
   g.host_begin = L.host_begin;
   x.host = stage.p + ghost;

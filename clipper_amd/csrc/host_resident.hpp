@@ -13,20 +13,6 @@ bool rs_debug() {
   return on;
 }
 
-void resident_free(Ctx* h) {
-  Resident& r = h->res;
-  if (r.host_plan) hipHostFree(r.host_plan);
-  if (r.xb) hipFree(r.xb);
-  if (r.ctl) hipFree(r.ctl);
-  const int vf = r.V_forced;
-  const bool xo = r.xcd_off;
-  const int hm = r.home;
-  r = Resident{};
-  r.V_forced = vf;
-  r.xcd_off = xo;
-  r.home = hm;
-}
-
 // Decide whether the current slices fit the resident solver and lay out its units (host_plan.hpp).
 // Called when a build's directory (csc_hLq) is on the host. Leaves r.ready = false when the problem
 // does not fit.
@@ -64,15 +50,7 @@ int resident_plan(Ctx* h, Shard& s) {
   const size_t off_wc = off_np + static_cast<size_t>(round_up(static_cast<int64_t>(npieces.size()), 16));
   const size_t off_pc = off_wc + static_cast<size_t>(round_up(static_cast<int64_t>(wave_cg.size()), 16));
   const size_t plan_bytes = off_pc + pieces.size() * sizeof(uint32_t) + 64;
-  if (plan_bytes > r.host_plan_cap) {
-    if (r.host_plan) hipHostFree(r.host_plan);
-    r.host_plan = nullptr;
-    r.host_plan_cap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r.host_plan), plan_bytes + 4096,
-                         hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r.host_plan_dev), r.host_plan, 0));
-    r.host_plan_cap = plan_bytes + 4096;
-  }
+  if (plan_bytes > r.host_plan.cap) HIPCHK(r.host_plan.alloc(plan_bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
   std::memcpy(r.host_plan, units.data(), units.size() * sizeof(ResidentUnit));
   std::memcpy(r.host_plan + off_nsl, nsl.data(), static_cast<size_t>(ncg));
   std::memcpy(r.host_plan + off_np, npieces.data(), npieces.size());
@@ -83,15 +61,12 @@ int resident_plan(Ctx* h, Shard& s) {
   r.off_pc = off_pc;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   const size_t xb_bytes = 2ull * maxslots * (V + 1) * static_cast<size_t>(mp) * 2 * sizeof(unsigned long long);
-  if (xb_bytes > r.xb_cap) {
-    if (r.xb) HIPCHK(hipFree(r.xb));
-    r.xb = nullptr;
-    HIPCHK(hipMalloc(&r.xb, xb_bytes));
-    r.xb_cap = xb_bytes;
+  if (xb_bytes > r.xb.bytes()) {  // (a growth that fails leaves no buffer and no capacity: the next plan allocates)
+    HIPCHK(r.xb.alloc(xb_bytes / sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(r.xb, 0, xb_bytes, s.stream));  // no granule may carry a future epoch
   }
   if (!r.ctl) {  // the error word and the two counters of the one-XCD mode
-    HIPCHK(hipMalloc(&r.ctl, 4 * sizeof(unsigned long long)));
+    HIPCHK(r.ctl.alloc(4));
     HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), s.stream));
   }
   r.V = V;
@@ -165,12 +140,12 @@ ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   Shard& s = h->sh[0];
   ResidentArgs a;
   a.M = slice_view(h, s);
-  a.units = reinterpret_cast<const ResidentUnit*>(r.host_plan_dev);
+  a.units = reinterpret_cast<const ResidentUnit*>(r.host_plan.dev);
   a.nunits = r.nunits;
-  a.nslots_of_cg = r.host_plan_dev + static_cast<size_t>(r.nunits) * sizeof(ResidentUnit);
-  a.npieces = r.host_plan_dev + r.off_np;
-  a.wave_cg = r.host_plan_dev + r.off_wc;
-  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan_dev + r.off_pc);
+  a.nslots_of_cg = r.host_plan.dev + static_cast<size_t>(r.nunits) * sizeof(ResidentUnit);
+  a.npieces = r.host_plan.dev + r.off_np;
+  a.wave_cg = r.host_plan.dev + r.off_wc;
+  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan.dev + r.off_pc);
   a.maxslots = r.maxslots;
   a.m = h->m;
   a.mp = h->mp;
@@ -179,11 +154,11 @@ ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   a.u0 = s.u0;
   a.xb = r.xb;
   a.epoch0 = r.epoch;
-  a.err = reinterpret_cast<uint32_t*>(r.ctl);
+  a.err = r.ctl.as<uint32_t>();
   a.lds_slices = r.lds_slices;
   a.u_dev = s.pt;  // point slot (0, 0), array u
-  a.host_u = h->u_pinned_dev;
-  a.host = h->mirror_dev;
+  a.host_u = h->u_pinned.dev;
+  a.host = h->mirror.dev;
   a.shared = s.shared;
   a.stamps = h->stamps_dev;
   a.ctrs = r.ctl + 1;
@@ -208,7 +183,7 @@ int epoch_wrap(unsigned long long& epoch, void* xb, size_t bytes, hipStream_t st
 int resident_finished(Ctx* h, int64_t iters) {
   Resident& r = h->res;
   r.epoch += static_cast<unsigned long long>(iters) + 8ull;
-  return epoch_wrap(r.epoch, r.xb, r.xb_cap, h->sh[0].stream);
+  return epoch_wrap(r.epoch, r.xb, r.xb.bytes(), h->sh[0].stream);
 }
 
 // a launch that gave up (the stream has drained): its error word; the word, the counters and the granules cleared.
@@ -218,7 +193,7 @@ int resident_gave_up(Ctx* h, uint32_t& err) {
   err = 0;
   HIPCHK(hipMemcpy(&err, r.ctl, sizeof(err), hipMemcpyDeviceToHost));
   HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), h->sh[0].stream));
-  HIPCHK(hipMemsetAsync(r.xb, 0, r.xb_cap, h->sh[0].stream));
+  HIPCHK(hipMemsetAsync(r.xb, 0, r.xb.bytes(), h->sh[0].stream));
   r.epoch += 1ull << 20;
   r.last_error = static_cast<int>(err);
   return 0;

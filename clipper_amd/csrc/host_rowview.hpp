@@ -140,39 +140,6 @@ void rowview_drop(Ctx* h) {
   h->vres.ready = false;
 }
 
-void rowview_free(Shard& s) {
-  auto fr = [](auto*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-  };
-  RowView& v = s.rv;
-  fr(v.st.sSizes);
-  fr(v.st.sLq);
-  fr(v.st.sPre);
-  fr(v.st.sBlk);
-  fr(v.st.sdata);
-  fr(v.st.swork);
-  v.st = SliceStore{};
-  fr(v.full.sSizes);
-  fr(v.full.sLq);
-  fr(v.full.sPre);
-  fr(v.full.sBlk);
-  fr(v.full.sdata);
-  fr(v.full.swork);
-  v.full = SliceStore{};
-  v.full_valid = false;
-  fr(v.rowmap[0]);
-  fr(v.rowmap[1]);
-  fr(v.in_view[0]);
-  fr(v.in_view[1]);
-  fr(v.blk);
-  fr(v.viewpos);
-  fr(v.desc);
-  v.cap_rows = v.cap_flags = v.cap_blk = v.cap_pos = 0;
-  v.valid = false;
-  v.nrows = 0;
-}
-
 // a view can exist at all: slices with C == pattern(M); column shards: the
 // bytes of all shards are known (the policy's cost model must be the same on every rank)
 bool rowview_possible(const Ctx* h) {
@@ -278,34 +245,25 @@ int rowview_build_shard(Ctx* h, Shard& s, bool& built) {
   const int64_t m = h->m, mp = h->mp;
   const int nblk = static_cast<int>(ceil_div(m, RV_BLK));
   int rc;
-  {
-    size_t c0 = v.cap_flags, c1 = v.cap_flags;
-    if ((rc = grow_dev(v.in_view[0], c0, static_cast<size_t>(mp)))) return rc;
-    if ((rc = grow_dev(v.in_view[1], c1, static_cast<size_t>(mp)))) return rc;
-    v.cap_flags = static_cast<size_t>(mp);
-    size_t r0 = v.cap_rows, r1 = v.cap_rows;
-    if ((rc = grow_dev(v.rowmap[0], r0, static_cast<size_t>(mp)))) return rc;
-    if ((rc = grow_dev(v.rowmap[1], r1, static_cast<size_t>(mp)))) return rc;
-    v.cap_rows = static_cast<size_t>(mp);
-    if ((rc = grow_dev(v.blk, v.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
-    if ((rc = grow_dev(v.viewpos, v.cap_pos, static_cast<size_t>(mp)))) return rc;
-  }
-  if (!h->rv_count) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->rv_count), 64, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->rv_count_dev), h->rv_count, 0));
-  }
+  HIPCHK(v.in_view[0].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.in_view[1].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.rowmap[0].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.rowmap[1].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.blk.grow(static_cast<size_t>(nblk) + 2));
+  HIPCHK(v.viewpos.grow(static_cast<size_t>(mp)));
+  if (!h->rv_count) HIPCHK(h->rv_count.alloc_bytes(64, hipHostMallocMapped | hipHostMallocCoherent));
   const int next = v.cur ^ 1;
   *h->rv_count = -1;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   if (mp <= RV_ONE_MAX) {  // flags, scan and scatter by one workgroup: one launch instead of three
     hipLaunchKernelGGL((k_rv_list_one<V>), dim3(1), dim3(1024), 0, s.stream, s.st + h->par, s.pt, mp, m, v.in_view[next],
-                       v.rowmap[next], static_cast<int64_t>(v.cap_rows), v.viewpos, h->rv_count_dev);
+                       v.rowmap[next], mp, v.viewpos, h->rv_count.dev);
   } else {
     hipLaunchKernelGGL((k_rv_flags<V>), dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream,
                        s.st + h->par, s.pt, mp, m, v.in_view[next], v.blk);
-    hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(1024), 0, s.stream, v.blk, nblk, h->rv_count_dev);
+    hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(1024), 0, s.stream, v.blk, nblk, h->rv_count.dev);
     hipLaunchKernelGGL(k_rv_scatter, dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream,
-                       v.in_view[next], m, v.blk, v.rowmap[next], static_cast<int64_t>(v.cap_rows), v.viewpos, mp);
+                       v.in_view[next], m, v.blk, v.rowmap[next], mp, v.viewpos, mp);
   }
   static const bool host_timing = std::getenv("CLIPPER_HIP_HOST_TIMING") != nullptr;
   auto lap = [&](const char* what) {
@@ -434,17 +392,16 @@ int rowview_build_shard(Ctx* h, Shard& s, bool& built) {
 // the descriptor a pass on the view reads, to the device
 int rowview_put_descriptor(Ctx* h, Shard& s) {
   RowView& v = s.rv;
-  if (!v.desc) HIPCHK(hipMalloc(reinterpret_cast<void**>(&v.desc), sizeof(SliceView)));
+  if (!v.desc) HIPCHK(v.desc.alloc(1));
   if (!h->rv_desc_host) {  // two staging slots, used in turn: a view whose work list is planned behind the resident
                            // launch sends a second descriptor while the copy of the first may still be queued
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->rv_desc_host), 2 * sizeof(SliceView), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->rv_desc_host_dev), h->rv_desc_host, 0));
+    HIPCHK(h->rv_desc_host.alloc(2, hipHostMallocMapped | hipHostMallocCoherent));
   }
   const int slot = (h->rv_desc_slot ^= 1);
   h->rv_desc_host[slot] = row_view(h, s);
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(64), 0, s.stream, reinterpret_cast<const uint4*>(h->rv_desc_host_dev + slot),
-                     reinterpret_cast<uint4*>(v.desc), static_cast<int64_t>(sizeof(SliceView) / 16));
+  hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(64), 0, s.stream, reinterpret_cast<const uint4*>(h->rv_desc_host.dev + slot),
+                     v.desc.as<uint4>(), static_cast<int64_t>(sizeof(SliceView) / 16));
   // the pinned staging slot is the context's: the copy has to be through before the next shard of an
   // in-process group writes ITS descriptor there
   if (h->sh.size() > 1) HIPCHK(hipStreamSynchronize(s.stream));

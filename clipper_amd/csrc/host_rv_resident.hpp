@@ -4,25 +4,6 @@
 
 namespace {
 
-void rvr_free(Ctx* h) {
-  ViewResident& r = h->vres;
-  if (r.host_plan) hipHostFree(r.host_plan);
-  if (r.xb) hipFree(r.xb);
-  if (r.ctl) hipFree(r.ctl);
-  if (r.giveup_host) hipHostFree(r.giveup_host);
-  if (r.backup) hipFree(r.backup);
-  for (hipEvent_t e : r.ev)
-    if (e) hipEventDestroy(e);
-  const unsigned long long ep = r.epoch;
-  const int tu = r.target_units, cd = r.cooldown, cn = r.cooldown_next, mu = r.max_units_device;
-  r = ViewResident{};
-  r.epoch = ep;
-  r.target_units = tu;
-  r.cooldown = cd;
-  r.cooldown_next = cn;
-  r.max_units_device = mu;
-}
-
 // Start of a solve: the give-up words of the previous one are gone, a back-off counts down.
 void rvr_begin_solve(Ctx* h) {
   ViewResident& r = h->vres;
@@ -170,14 +151,7 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
   const size_t off_wc = off_np + static_cast<size_t>(round_up(static_cast<int64_t>(plan.npieces.size()), 16));
   const size_t off_pc = off_wc + static_cast<size_t>(round_up(static_cast<int64_t>(plan.wave_cg.size()), 16));
   const size_t bytes = off_pc + plan.pieces.size() * sizeof(uint32_t) + 64;
-  if (bytes > r.host_plan_cap) {
-    if (r.host_plan) hipHostFree(r.host_plan);
-    r.host_plan = nullptr;
-    r.host_plan_cap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r.host_plan), bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r.host_plan_dev), r.host_plan, 0));
-    r.host_plan_cap = bytes + 4096;
-  }
+  if (bytes > r.host_plan.cap) HIPCHK(r.host_plan.alloc(bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
   std::memcpy(r.host_plan, plan.units.data(), plan.units.size() * sizeof(RvrUnit));
   std::memcpy(r.host_plan + off_np, plan.npieces.data(), plan.npieces.size());
   std::memcpy(r.host_plan + off_wc, plan.wave_cg.data(), plan.wave_cg.size());
@@ -193,17 +167,15 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
   r.off_pc = off_pc;
   const size_t xb_bytes = static_cast<size_t>(rvr_xb_granules(6)) * sizeof(unsigned long long);
   if (!r.xb) {
-    HIPCHK(hipMalloc(&r.xb, xb_bytes));
+    HIPCHK(r.xb.alloc(xb_bytes / sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(r.xb, 0, xb_bytes, s.stream));  // no granule may carry a future epoch
-    r.xb_bytes = xb_bytes;
   }
   if (!r.ctl) {
-    HIPCHK(hipMalloc(&r.ctl, RVR_GIVEUP_SLOTS * 64));
+    HIPCHK(r.ctl.alloc(RVR_GIVEUP_SLOTS * 16));
     HIPCHK(hipMemsetAsync(r.ctl, 0, RVR_GIVEUP_SLOTS * 64, s.stream));
   }
   if (!r.giveup_host) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r.giveup_host), RVR_GIVEUP_SLOTS * 4 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r.giveup_host_dev), r.giveup_host, 0));
+    HIPCHK(r.giveup_host.alloc(RVR_GIVEUP_SLOTS * 4, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(r.giveup_host, 0, RVR_GIVEUP_SLOTS * 4 * sizeof(uint32_t));
   }
   r.nunits = static_cast<int>(plan.units.size());
@@ -245,30 +217,30 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
   HIPCHK(hipSetDevice(s.device));
   RvrArgs a{};
   a.R = r.on_replica ? row_view_full(h, s) : row_view(h, s);
-  a.units = reinterpret_cast<const RvrUnit*>(r.host_plan_dev);
+  a.units = reinterpret_cast<const RvrUnit*>(r.host_plan.dev);
   a.nunits = r.nunits;
-  a.npieces = r.host_plan_dev + r.off_np;
-  a.wave_cg = r.host_plan_dev + r.off_wc;
-  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan_dev + r.off_pc);
+  a.npieces = r.host_plan.dev + r.off_np;
+  a.wave_cg = r.host_plan.dev + r.off_wc;
+  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan.dev + r.off_pc);
   a.viewpos = s.rv.viewpos;
   a.st = s.st + h->par;
   a.shared = s.shared;
-  a.host = h->mirror_dev;
-  a.host_u = h->u_pinned_dev;
+  a.host = h->mirror.dev;
+  a.host_u = h->u_pinned.dev;
   a.marks = h->profiling ? s.marks : nullptr;
-  a.kind = (a.marks && !h->multiproc) ? h->kind_dev : nullptr;  // (as solve_args: a multi-process solve copies the marks itself)
+  a.kind = (a.marks && !h->multiproc) ? h->kind.dev : nullptr;  // (as solve_args: a multi-process solve copies the marks itself)
   a.marks_n = h->launch_counter;  // (profiling: launch index = the device's iteration count)
   a.prm = prm;
   a.m = h->m;
   a.mp = h->mp;
   a.pt = s.pt;
   a.xb = r.xb;
-  if (int rc = epoch_wrap(r.epoch, r.xb, r.xb_bytes, s.stream)) return rc;
+  if (int rc = epoch_wrap(r.epoch, r.xb, r.xb.bytes(), s.stream)) return rc;
   a.epoch0 = r.epoch;
   r.epoch += 1ull << 20;  // whatever this launch publishes (even if it gives up half-way) lies below the next one's
   const bool own_ctl = r.launches_this_solve < RVR_GIVEUP_SLOTS;  // (its block was zeroed by the build's k_rv_resume)
   a.ctl = r.ctl + (own_ctl ? 16 * r.launches_this_solve : 0);
-  a.giveup_host = (r.giveup_host_dev && r.launches_this_solve < RVR_GIVEUP_SLOTS) ? r.giveup_host_dev + 4 * r.launches_this_solve : nullptr;
+  a.giveup_host = (r.giveup_host.dev && r.launches_this_solve < RVR_GIVEUP_SLOTS) ? r.giveup_host.dev + 4 * r.launches_this_solve : nullptr;
   a.lds_slices = r.lds_slices;
   // The longest a unit waits for the others' granules of ONE exchange, on the 100 MHz wall clock: 2 ms — a hundred
   // iterations' worth (an iteration is 14 us, the first exchange comes 25 us into the launch). A unit that is not
@@ -291,7 +263,7 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
   const bool timed = h->profiling_level >= 2 && r.ev_n < 16;
   if (timed) {
     for (int k = 0; k < 2; ++k)
-      if (!r.ev[2 * r.ev_n + k]) HIPCHK(hipEventCreate(&r.ev[2 * r.ev_n + k]));
+      if (!r.ev[2 * r.ev_n + k]) HIPCHK(r.ev[2 * r.ev_n + k].create());
     HIPCHK(hipEventRecord(r.ev[2 * r.ev_n], s.stream));
   }
   int lr = 1;
@@ -378,9 +350,8 @@ int rvr_replica_handover(Ctx* h, const SolverParams& prm) {
       local_rc = rvr_plan(h, s, true);
       mine = !local_rc && r.ready;
     }
-    if (mine && !r.backup && hipMalloc(reinterpret_cast<void**>(&r.backup), sizeof(SolverState) + sizeof(SolveShared)) != hipSuccess) {
+    if (mine && !r.backup && r.backup.alloc(sizeof(SolverState) + sizeof(SolveShared)) != hipSuccess) {
       (void)hipGetLastError();
-      r.backup = nullptr;
       local_rc = fail(CLIPPER_HIP_E_NOMEM, "resident solver on a view: no memory for the state's backup");
       mine = false;
     }

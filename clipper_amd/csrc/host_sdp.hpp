@@ -10,25 +10,16 @@ namespace {
 
 constexpr int SDP_ITERS_PER_LAUNCH = 8;  // bounded work per launch (~ms at n = 128)
 
-// Device buffers of one call. Workgroup route: every pointer is an allocation of its own. Wide route: `slab` is the
+// Device buffers of one call. Workgroup route: every pointer is an allocation of its own (`own`). Wide route: `slab` is the
 // only allocation; M ... mu, ctl and src (when the call uploads host matrices) point into it (host_sdpwide_plan.hpp's
 // regions, src behind them) and `wide` is the driver's view of it.
 struct SdpBufs {
   double *M = nullptr, *mask = nullptr, *X = nullptr, *Z = nullptr, *U = nullptr, *Q = nullptr, *T = nullptr,
          *mu = nullptr, *src = nullptr;
   SdpCtl* ctl = nullptr;
-  uint8_t* slab = nullptr;
+  DevBuf<uint8_t> slab;
+  DevBuf<void> own[10];  // M ... mu, ctl, src
   SdpWide wide{};
-  ~SdpBufs() {
-    if (slab) {
-      hipFree(slab);
-      return;
-    }
-    for (void* p : {static_cast<void*>(M), static_cast<void*>(mask), static_cast<void*>(X), static_cast<void*>(Z),
-                    static_cast<void*>(U), static_cast<void*>(Q), static_cast<void*>(T), static_cast<void*>(mu),
-                    static_cast<void*>(src), static_cast<void*>(ctl)})
-      if (p) hipFree(p);
-  }
 };
 
 // `route`: the setting the call read (g_sdp_route); it decides the scope limit
@@ -64,7 +55,7 @@ int sdp_alloc(SdpBufs& b, int64_t n, const clipper_sdp_params_t* P, int taken, b
   const size_t src_bytes = with_src ? 2 * static_cast<size_t>(n * n) * sizeof(double) : 0;
   if (taken == CLIPPER_HIP_SDP_ROUTE_WIDE) {
     const clipper_sdpw_plan::Regions r = clipper_sdpw_plan::make_regions(static_cast<int32_t>(n));
-    if (int rc = sdpw_alloc(&b.slab, r.bytes + src_bytes, (long long)n)) return rc;
+    if (int rc = sdpw_alloc(b.slab, r.bytes + src_bytes, (long long)n)) return rc;
     if (with_src) b.src = reinterpret_cast<double*>(b.slab + r.bytes);
     auto at = [&](size_t off) { return reinterpret_cast<double*>(b.slab + off); };
     b.wide = sdpw_view(SdpArgs{at(r.M), at(r.mask), at(r.X), at(r.Z), at(r.U), at(r.Q[0]), at(r.T), at(r.mu), nullptr,
@@ -85,16 +76,23 @@ int sdp_alloc(SdpBufs& b, int64_t n, const clipper_sdp_params_t* P, int taken, b
   }
   const int64_t np = n + (n & 1);
   const size_t nn = static_cast<size_t>(n * n), pp = static_cast<size_t>(np * np);
+  int k = 0;
   for (auto pr : {std::make_pair(&b.M, nn), std::make_pair(&b.mask, nn), std::make_pair(&b.X, nn),
                   std::make_pair(&b.Z, nn), std::make_pair(&b.U, nn), std::make_pair(&b.Q, pp),
                   std::make_pair(&b.T, pp), std::make_pair(&b.mu, static_cast<size_t>(np))})
-    if (hipMalloc(reinterpret_cast<void**>(pr.first), pr.second * sizeof(double)) != hipSuccess) {
-      *pr.first = nullptr;
+  {
+    if (b.own[k].alloc(pr.second * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
       return fail(CLIPPER_HIP_E_NOMEM, "sdp: device allocation of %zu bytes failed", pr.second * sizeof(double));
     }
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&b.ctl), sizeof(SdpCtl)));
-  if (with_src) HIPCHK(hipMalloc(reinterpret_cast<void**>(&b.src), src_bytes));
+    *pr.first = b.own[k++].as<double>();
+  }
+  HIPCHK(b.own[8].alloc(sizeof(SdpCtl)));
+  b.ctl = b.own[8].as<SdpCtl>();
+  if (with_src) {
+    HIPCHK(b.own[9].alloc(src_bytes));
+    b.src = b.own[9].as<double>();
+  }
   return 0;
 }
 
@@ -254,7 +252,7 @@ int sdp_ctx_impl(Ctx* h, const clipper_sdp_params_t* P, double* X_out, double* Y
   const dim3 grid(static_cast<unsigned>(ceil_div(n * n, 256))), block(256);
   dispatch_vt(h, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_sdp_gather<T>, grid, block, 0, s.stream, static_cast<const T*>(s.S),
+    hipLaunchKernelGGL(k_sdp_gather<T>, grid, block, 0, s.stream, s.S.as<const T>(),
                        static_cast<const T*>(srcC), !h->explicitC, static_cast<int64_t>(h->W), int64_t{1},
                        static_cast<int32_t>(n), 1.0, b.M, b.mask);
   });

@@ -27,9 +27,9 @@ namespace {
 
 struct SdpBatchState {
   int device = 0;
-  uint8_t* slab = nullptr;  // the plan's regions, then the launch tables
-  uint8_t* work = nullptr;  // the wide route's work regions, shared by its problems in turn
-  SdpCtl* ctl = nullptr;    // device, one per problem
+  DevBuf<uint8_t> slab;  // the plan's regions, then the launch tables
+  DevBuf<uint8_t> work;  // the wide route's work regions, shared by its problems in turn
+  DevBuf<SdpCtl> ctl;    // device, one per problem
   clipper_sdp_plan::Plan plan;
   std::vector<int32_t> n;
   std::vector<SdpCtl> c;              // the last copy of the control array
@@ -42,12 +42,6 @@ struct SdpBatchState {
   const int32_t* nodes(size_t i) const { return reinterpret_cast<const int32_t*>(out.data() + (plan.at[i].nodes - plan.out_begin)); }
   template <typename T>
   T* dev(size_t off) const { return reinterpret_cast<T*>(slab + off); }
-  ~SdpBatchState() {
-    if (slab || ctl || work) hipSetDevice(device);
-    if (slab) hipFree(slab);
-    if (work) hipFree(work);
-    if (ctl) hipFree(ctl);
-  }
 };
 
 // The optional outputs of problem i of a finished call: X, Y (n x n, from the device), lambdas (ascending), evec1.
@@ -107,14 +101,14 @@ int sdp_batch_run(SdpBatchState& S, hipStream_t st, const clipper_sdp_params_t* 
   if (slab_bytes + ctl_bytes + work_bytes > free_b)
     return fail(CLIPPER_HIP_E_NOMEM, "sdp batch: %zu problems need %zu bytes of device memory, %zu are free", count,
                 slab_bytes + ctl_bytes + work_bytes, free_b);
-  for (auto pr : {std::make_pair(reinterpret_cast<void**>(&S.slab), slab_bytes),
-                  std::make_pair(reinterpret_cast<void**>(&S.ctl), ctl_bytes),
-                  std::make_pair(reinterpret_cast<void**>(&S.work), work_bytes)})
-    if (pr.second && hipMalloc(pr.first, pr.second) != hipSuccess) {
-      *pr.first = nullptr;
-      (void)hipGetLastError();
-      return fail(CLIPPER_HIP_E_NOMEM, "sdp batch: device allocation of %zu bytes failed", pr.second);
-    }
+  auto room = [](auto& buf, size_t bytes) {
+    if (bytes == 0 || buf.alloc_bytes(bytes) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(CLIPPER_HIP_E_NOMEM, "sdp batch: device allocation of %zu bytes failed", bytes);
+  };
+  if (int rc = room(S.slab, slab_bytes)) return rc;
+  if (int rc = room(S.ctl, ctl_bytes)) return rc;
+  if (int rc = room(S.work, work_bytes)) return rc;
 
   // ---- 3. the tables, the uploaded matrices, the gather --------------------------------------------------------------
   std::vector<uint8_t> tab(off_list - off_args);

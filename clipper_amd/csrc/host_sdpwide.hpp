@@ -175,14 +175,13 @@ int sdpw_solve(hipStream_t st, const SdpWide& w, const clipper_sdp_params_t* P,
 }
 
 // `bytes` of device memory for the wide route, checked against what is free
-int sdpw_alloc(uint8_t** slab, size_t bytes, long long n) {
+int sdpw_alloc(DevBuf<uint8_t>& slab, size_t bytes, long long n) {
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   if (bytes > free_b)
     return fail(CLIPPER_HIP_E_NOMEM, "sdp: the wide route needs %zu bytes of device memory at n = %lld, %zu are free",
                 bytes, n, free_b);
-  if (hipMalloc(reinterpret_cast<void**>(slab), bytes) != hipSuccess) {
-    *slab = nullptr;
+  if (slab.alloc(bytes) != hipSuccess) {
     (void)hipGetLastError();
     return fail(CLIPPER_HIP_E_NOMEM, "sdp: device allocation of %zu bytes failed", bytes);
   }

@@ -20,40 +20,25 @@ void destroy_ctx(Ctx* h) {
   }
   if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
   sub_free(h);  // (the live sub-problem's context borrows this one's stream: before the stream goes)
-  for (auto& s : h->sh) {
-    free_shard_buffers(s);
-    if (s.ev_reduced) hipEventDestroy(s.ev_reduced);
-    if (s.ev_copied) hipEventDestroy(s.ev_copied);
-    if (s.stream && !h->borrowed_stream) hipStreamDestroy(s.stream);
+  std::vector<std::pair<int, hipStream_t>> streams;  // (this context's own: a borrowed one stays)
+  for (auto& s : h->sh)
+    if (s.stream && !h->borrowed_stream) streams.emplace_back(s.device, s.stream);
+  const int dev0 = h->sh.empty() ? -1 : h->sh[0].device;
+  h->sh.clear();  // every shard's buffers and events, before its stream
+  for (auto& ds : streams) {
+    hipSetDevice(ds.first);
+    hipStreamDestroy(ds.second);
   }
-  if (!h->sh.empty()) hipSetDevice(h->sh[0].device);
-  for (hipEvent_t e : h->ev_pairs) hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_xchg) hipEventDestroy(e);
-  for (hipEvent_t e : {h->ev_poll[0], h->ev_poll[1], h->ev_aff[0], h->ev_aff[1]})
-    if (e) hipEventDestroy(e);
-  for (void* p : std::initializer_list<void*>{h->host_state, h->mirror, h->kind, h->u_pinned, h->xchg_send, h->xchg_recv,
-                                              h->csc_hLq, h->csc_hctl, h->csc_htotal, h->csc_hwork, h->rv_count, h->rv_desc_host,
-                                              h->mc_stage.p})
-    if (p) hipHostFree(p);
-  if (h->stamps_dev) hipFree(h->stamps_dev);
-  resident_free(h);
-  rvr_free(h);
-  delete h;
+  if (dev0 >= 0) hipSetDevice(dev0);
+  delete h;  // the context's own events and pinned arrays, the resident solvers' buffers
 }
 
 // the pinned staging of the final u (the device writes it), large enough for this context's m
 int ensure_u_pinned(Ctx* h) {
-  const size_t vbytes = static_cast<size_t>(h->m) * sizeof(double);
-  if (h->u_pinned_cap >= vbytes) return 0;
-  if (h->u_pinned) hipHostFree(h->u_pinned);
-  h->u_pinned = nullptr;
-  h->u_pinned_dev = nullptr;
-  h->u_pinned_cap = 0;
+  if (h->u_pinned.cap >= static_cast<size_t>(h->m)) return 0;
+  h->u_pinned.reset();
   HIPCHK(hipSetDevice(h->sh[0].device));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->u_pinned), vbytes,
-                       hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->u_pinned_dev), h->u_pinned, 0));
-  h->u_pinned_cap = vbytes;
+  HIPCHK(h->u_pinned.alloc(static_cast<size_t>(h->m), hipHostMallocMapped | hipHostMallocCoherent));
   return 0;
 }
 
@@ -364,7 +349,7 @@ int solve_finish(Ctx* h, int rounding, const SolveShared& fin, double* u_out, cl
     HIPCHK(hipGetLastError());
   }
   std::vector<double>& u = h->u_host;  // (kept from solve to solve: no allocation on the way out)
-  u.assign(h->u_pinned, h->u_pinned + m);
+  u.assign(h->u_pinned.p, h->u_pinned.p + m);
   std::vector<int32_t> nodes;
   if ((rc = round_nodes(h, rounding, u, fin.F, nodes))) return rc;
   h->nodes = nodes;

@@ -6,55 +6,14 @@ namespace {
 
 using Ctx = clipper_hip_ctx;
 
-void rowview_free(Shard& s);
 void rowview_drop(Ctx* h);
 void sub_free(Ctx* h);
 
-int free_shard_buffers(Shard& s) {
-  hipSetDevice(s.device);
-  auto fr = [](auto*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-  };
-  fr(s.S);
-  fr(s.Cs);
-  fr(s.part);
-  fr(s.u0);
-  fr(s.pt);
-  fr(s.cab);
-  fr(s.X[0]);
-  fr(s.X[1]);
-  fr(s.ab);
-  fr(s.scal);
-  fr(s.st);
-  fr(s.shared);
-  fr(s.marks);
-  fr(s.gOff);
-  fr(s.gPre);
-  fr(s.gvals);
-  fr(s.grows);
-  fr(s.cctl);
-  s.gcap_units = s.gcap_groups = 0;
-  fr(s.sSizes);
-  fr(s.sLq);
-  fr(s.sPre);
-  fr(s.sBlk);
-  fr(s.sdata);
-  fr(s.swork);
-  s.scap_slices = s.scap_bytes = s.scap_work = 0;
-  rowview_free(s);
-  s.part_tiles = 0;
-  fr(s.P1);
-  fr(s.P2);
-  fr(s.P1f);
-  fr(s.P2f);
-  s.capPf = 0;
-  fr(s.Adev);
-  fr(s.dD1);
-  fr(s.dD2);
-  s.capP = s.capA = s.capD1 = s.capD2 = 0;
-  s.bytes_S = 0;
-  return 0;
+// everything a shard holds for one problem size goes: the solver's arrays, the groups, the slices, the row view, the
+// staged inputs (each freed on its own device); the shard's device, slot, stream and events stay
+void drop_shard_buffers(Shard& s) {
+  static_cast<ShardBufs&>(s) = ShardBufs{};
+  static_cast<SliceStore&>(s) = SliceStore{};
 }
 
 // CLIPPER_HIP_STORE_F32_CSC / _F64_CSC (C == pattern(M) is checked per matrix): M lives in the
@@ -123,34 +82,34 @@ int ensure_problem(Ctx* h, int64_t m) {
   if (same) return 0;
   sub_free(h);  // (the live sub-problem of another problem size: its context and lists go with the buffers)
   for (auto& s : h->sh) {
-    free_shard_buffers(s);
+    drop_shard_buffers(s);
     HIPCHK(hipSetDevice(s.device));
     const size_t bytesS = static_cast<size_t>(m) * static_cast<size_t>(W) * h->esize();
     s.bytes_S = bytesS;
     // CLIPPER_HIP_STORE_F32_CSC keeps M compressed: the dense store exists only while a path
     // that needs it is in use (ensure_dense)
-    if (!h->compressed) HIPCHK(hipMalloc(&s.S, bytesS));
-    const size_t nvec = static_cast<size_t>(P * W) * sizeof(double);
+    if (!h->compressed) HIPCHK(s.S.alloc(bytesS));
+    const size_t nv = static_cast<size_t>(P * W), nvec = nv * sizeof(double);
     const size_t V = static_cast<size_t>(h->V);
-    HIPCHK(hipMalloc(&s.u0, nvec));
+    HIPCHK(s.u0.alloc(nv));
     const size_t NSLOT = static_cast<size_t>(nslot(h->V));
-    HIPCHK(hipMalloc(&s.pt, 2 * V * 2 * nvec));
-    HIPCHK(hipMalloc(&s.cab, 2 * nvec));
+    HIPCHK(s.pt.alloc(2 * V * 2 * nv));
+    HIPCHK(s.cab.alloc(2 * nv));
     for (int k = 0; k < 2; ++k) {
-      HIPCHK(hipMalloc(&s.X[k], (V + 1) * VS * nvec));
+      HIPCHK(s.X[k].alloc((V + 1) * VS * nv));
       HIPCHK(hipMemsetAsync(s.X[k], 0, (V + 1) * VS * nvec, s.stream));
     }
     const size_t Q = static_cast<size_t>(tail_q(h->V));
     const size_t nwg = static_cast<size_t>(ceil_div(m, TAIL_THREADS));
-    HIPCHK(hipMalloc(&s.scal, (nwg + ceil_div(nwg, SCAL_FOLD) + 1) * Q * sizeof(double)));
-    HIPCHK(hipMalloc(&s.ab, NSLOT * nvec));
+    HIPCHK(s.scal.alloc((nwg + ceil_div(nwg, SCAL_FOLD) + 1) * Q));
+    HIPCHK(s.ab.alloc(NSLOT * nv));
     HIPCHK(hipMemsetAsync(s.ab, 0, NSLOT * nvec, s.stream));
     s.part_tiles = static_cast<size_t>(max_tiles(h));
-    HIPCHK(hipMalloc(&s.part, s.part_tiles * NSLOT * W * sizeof(double)));
-    HIPCHK(hipMalloc(&s.st, 2 * sizeof(SolverState)));
+    HIPCHK(s.part.alloc(s.part_tiles * NSLOT * W));
+    HIPCHK(s.st.alloc(2));
     HIPCHK(hipMemsetAsync(s.st, 0, 2 * sizeof(SolverState), s.stream));
-    HIPCHK(hipMalloc(&s.shared, sizeof(SolveShared)));
-    HIPCHK(hipMalloc(&s.marks, KIND_CAP));
+    HIPCHK(s.shared.alloc(1));
+    HIPCHK(s.marks.alloc(KIND_CAP));
     HIPCHK(hipMemsetAsync(s.marks, 0, KIND_CAP, s.stream));
     HIPCHK(hipMemsetAsync(s.shared, 0, sizeof(SolveShared), s.stream));
   }
@@ -171,7 +130,7 @@ void launch_pass_tv(Ctx* h, Shard& s, const SolveArgs& a) {
   constexpr int UNR = gemv_unr(V, sizeof(T), HASC);
   dim3 grid(h->nstrips, h->ntiles), block(GEMV_NW * 64);
   hipLaunchKernelGGL((k_gemv<T, HASC, V, GEMV_NW, UNR>), grid, block, 0, s.stream,
-                     static_cast<const T*>(s.S), static_cast<const T*>(s.Cs), h->rows_per_tile, a);
+                     s.S.as<const T>(), s.Cs.as<const T>(), h->rows_per_tile, a);
 }
 
 template <typename T, bool HASC>
@@ -179,7 +138,7 @@ void launch_plain_t(Ctx* h, Shard& s, const double* X) {
   constexpr int UNR = gemv_unr(1, sizeof(T), HASC);
   dim3 grid(h->nstrips, h->ntiles), block(GEMV_NW * 64);
   hipLaunchKernelGGL((k_gemv_plain<T, HASC, GEMV_NW, UNR>), grid, block, 0, s.stream,
-                     static_cast<const T*>(s.S), static_cast<const T*>(s.Cs), h->W, h->m,
+                     s.S.as<const T>(), s.Cs.as<const T>(), h->W, h->m,
                      h->rows_per_tile, X, s.part);
 }
 
@@ -274,14 +233,10 @@ int exchange(Ctx* h, int nslots) {
     Shard& s = h->sh[0];
     HIPCHK(hipSetDevice(s.device));
     const size_t need = static_cast<size_t>(h->world) * blk;
-    if (need > h->xchg_cap) {
-      if (h->xchg_send) hipHostFree(h->xchg_send);
-      if (h->xchg_recv) hipHostFree(h->xchg_recv);
-      h->xchg_send = h->xchg_recv = nullptr;
-      h->xchg_cap = 0;
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->xchg_send), blk, hipHostMallocDefault));
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->xchg_recv), need, hipHostMallocDefault));
-      h->xchg_cap = need;
+    if (need > h->xchg_recv.cap * sizeof(double)) {  // both go, then both come (the gathered blocks last: their capacity decides)
+      h->xchg_send.reset(), h->xchg_recv.reset();
+      HIPCHK(h->xchg_send.alloc(static_cast<size_t>(blk_elems)));
+      HIPCHK(h->xchg_recv.alloc(static_cast<size_t>(h->world * blk_elems)));
     }
     HIPCHK(hipMemcpyAsync(h->xchg_send, s.ab + static_cast<int64_t>(s.slot) * blk_elems, blk,
                           hipMemcpyDeviceToHost, s.stream));
@@ -340,7 +295,7 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par, bool de
   a.st_cur = s.st + par;
   a.st_next = s.st + (par ^ 1);
   a.shared = s.shared;
-  a.host = (&s == &h->sh[0]) ? h->mirror_dev : nullptr;
+  a.host = (&s == &h->sh[0]) ? h->mirror.dev : nullptr;
   a.prm = prm;
   a.m = h->m;
   a.W = h->W;
@@ -363,8 +318,8 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par, bool de
     a.nwg_in = static_cast<int>(ceil_div(a.nwg, SCAL_FOLD));
   }
   a.marks = (h->profiling && &s == &h->sh[0]) ? s.marks : nullptr;
-  a.kind = (a.marks && !h->multiproc) ? h->kind_dev : nullptr;
-  a.host_u = (!h->multiproc && &s == &h->sh[0]) ? h->u_pinned_dev : nullptr;
+  a.kind = (a.marks && !h->multiproc) ? h->kind.dev : nullptr;
+  a.host_u = (!h->multiproc && &s == &h->sh[0]) ? h->u_pinned.dev : nullptr;
   a.stamps = (&s == &h->sh[0]) ? h->stamps_dev : nullptr;
   a.stamps_wide = h->stamps_rows > 4096 ? 1 : 0;
   // the row view, while one is in use (one shard)
@@ -384,10 +339,10 @@ SolveArgs solve_args(Ctx* h, Shard& s, const SolverParams& prm, int par, bool de
   a.colmap = nullptr;
   if (h->parent != nullptr) {  // these launches run ON a sub-problem: they report where the parent's would
     Ctx* p = h->parent;
-    a.host = p->mirror_dev;
-    a.host_u = p->u_pinned_dev;
+    a.host = p->mirror.dev;
+    a.host_u = p->u_pinned.dev;
     a.marks = p->profiling ? p->sh[0].marks : nullptr;
-    a.kind = a.marks ? p->kind_dev : nullptr;
+    a.kind = a.marks ? p->kind.dev : nullptr;
     a.stamps = p->stamps_dev;
     a.stamps_wide = p->stamps_rows > 4096 ? 1 : 0;
     a.sub_state = 2;
@@ -577,8 +532,8 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
       return nullptr;
     }
     if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s.ev_reduced, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming) != hipSuccess) {
+        s.ev_reduced.create(hipEventDisableTiming) != hipSuccess ||
+        s.ev_copied.create(hipEventDisableTiming) != hipSuccess) {
       fail(CLIPPER_HIP_E_HIP, "cannot create stream/events on device %d", s.device);
       destroy_ctx(h);
       return nullptr;
@@ -601,27 +556,20 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, h->sh[0].device) == hipSuccess)
     h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->host_state), 2 * sizeof(SolveShared),
-                    hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_poll[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_poll[1], hipEventDisableTiming) != hipSuccess) {
+  if (h->host_state.alloc(2) != hipSuccess || h->ev_poll[0].create(hipEventDisableTiming) != hipSuccess ||
+      h->ev_poll[1].create(hipEventDisableTiming) != hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate pinned solver state");
     destroy_ctx(h);
     return nullptr;
   }
   // progress record the deciding workgroup writes straight into host memory (coherent, mapped)
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->mirror), sizeof(HostMirror),
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->mirror_dev), h->mirror, 0) !=
-          hipSuccess) {
+  if (h->mirror.alloc(1, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate the pinned progress record");
     destroy_ctx(h);
     return nullptr;
   }
   std::memset(h->mirror, 0, sizeof(HostMirror));
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->kind), KIND_CAP,
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->kind_dev), h->kind, 0) != hipSuccess) {
+  if (h->kind.alloc(KIND_CAP, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     fail(CLIPPER_HIP_E_HIP, "cannot allocate the pinned iteration marks");
     destroy_ctx(h);
     return nullptr;
@@ -630,8 +578,7 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
   if (const char* e = std::getenv("CLIPPER_HIP_STAMPS")) {  // measurement only; 2 = every workgroup of a pass
     h->stamps_rows = std::atoi(e) == 2 ? 16384 : 4096;
     const size_t bytes = static_cast<size_t>(h->stamps_rows) * 4 * sizeof(long long);
-    if (hipMalloc(&h->stamps_dev, bytes) == hipSuccess) (void)hipMemset(h->stamps_dev, 0, bytes);
-    else h->stamps_dev = nullptr;
+    if (h->stamps_dev.alloc_bytes(bytes) == hipSuccess) (void)hipMemset(h->stamps_dev, 0, bytes);
   }
   // CLIPPER_HIP_WINDOW = 1 | 4 | 6 | 8: line-search candidates multiplied per pass over M
   if (const char* w = std::getenv("CLIPPER_HIP_WINDOW")) {
@@ -647,35 +594,21 @@ Ctx* make_ctx(const int* devices, int nlocal, int storage, int world, int first_
 }
 
 // uploads D (d x n, column-major) and gathers the per-association point table on device
-template <typename T>
-int ensure_cap(T*& p, size_t& cap, size_t bytes) {
-  if (bytes <= cap && p) return 0;
-  if (p) hipFree(p);
-  p = nullptr;
-  cap = 0;
-  HIPCHK(hipMalloc(&p, bytes));
-  cap = bytes;
-  return 0;
-}
-
 // dev != null: the same inputs already on the device (a batch's staging, host_batchsolve.hpp) — copied in stream
 // order, no wait
 int upload_points(Ctx* h, Shard& s, const double* D1, const double* D2, int d, int64_t n1,
                   int64_t n2, int64_t pstride, const StagedInputs* dev = nullptr) {
   const size_t b1 = static_cast<size_t>(d) * n1 * sizeof(double);
   const size_t b2 = static_cast<size_t>(d) * n2 * sizeof(double);
-  const size_t bp = static_cast<size_t>(d) * pstride * sizeof(double);
   const size_t ba = static_cast<size_t>(2 * h->m) * sizeof(int32_t);
-  int rc;
-  if ((rc = ensure_cap(s.dD1, s.capD1, b1))) return rc;
-  if ((rc = ensure_cap(s.dD2, s.capD2, b2))) return rc;
-  size_t capP2 = s.capP;
-  if ((rc = ensure_cap(s.P1, s.capP, bp))) return rc;
-  if ((rc = ensure_cap(s.P2, capP2, bp))) return rc;
-  if ((rc = ensure_cap(s.Adev, s.capA, ba))) return rc;
-  size_t capPf2 = s.capPf;
-  if ((rc = ensure_cap(s.P1f, s.capPf, bp / 2))) return rc;
-  if ((rc = ensure_cap(s.P2f, capPf2, bp / 2))) return rc;
+  const size_t np = static_cast<size_t>(d) * pstride;
+  HIPCHK(s.dD1.grow(static_cast<size_t>(d) * n1));
+  HIPCHK(s.dD2.grow(static_cast<size_t>(d) * n2));
+  HIPCHK(s.P1.grow(np));
+  HIPCHK(s.P2.grow(np));
+  HIPCHK(s.Adev.grow(static_cast<size_t>(2 * h->m)));
+  HIPCHK(s.P1f.grow(np));
+  HIPCHK(s.P2f.grow(np));
   if (dev) {
     HIPCHK(hipMemcpyAsync(s.dD1, dev->D1, b1, hipMemcpyDeviceToDevice, s.stream));
     HIPCHK(hipMemcpyAsync(s.dD2, dev->D2, b2, hipMemcpyDeviceToDevice, s.stream));

@@ -50,21 +50,6 @@ int guard_fail(int code, const char* what) noexcept {
                   __LINE__);                                                          \
   } while (0)
 
-// a pinned host buffer that only grows (contents lost when it does); freed by whoever owns it
-struct PinnedBuf {
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-};
-int pinned_grow(PinnedBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return 0;
-  if (b.p) HIPCHK(hipHostFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b.p), bytes, hipHostMallocDefault));
-  b.cap = bytes;
-  return 0;
-}
-
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -136,13 +121,12 @@ int load_rccl() {
 
 // ---- one set of slices (k_slices.hip.h): the data, its directory, the work list of a pass ----
 struct SliceStore {
-  uint32_t* sSizes = nullptr;   // [nslices] size / 16
-  uint32_t* sLq = nullptr;      // [nslices] maxq | entries << 8
-  uint64_t* sPre = nullptr;     // [nslices]
-  uint64_t* sBlk = nullptr;     // scan block sums [nblk + 1]; the last one = total units
-  uint8_t* sdata = nullptr;
-  SliceWork* swork = nullptr;
-  size_t scap_slices = 0, scap_bytes = 0, scap_work = 0;
+  DevBuf<uint32_t> sSizes;   // [nslices] size / 16 (its capacity is the slices the four directory arrays hold)
+  DevBuf<uint32_t> sLq;      // [nslices] maxq | entries << 8
+  DevBuf<uint64_t> sPre;     // [nslices]
+  DevBuf<uint64_t> sBlk;     // scan block sums [nblk + 1]; the last one = total units
+  DevBuf<uint8_t> sdata;
+  DevBuf<SliceWork> swork;
   int s_ncg = 0, s_nchunks = 0;
   int s_nwork = 0;        // workgroups of a pass
   int s_nslots = 0;       // partial-sum slots per column (what the tail adds)
@@ -153,13 +137,12 @@ struct SliceStore {
 // ---- the row view of M (k_solver.hip.h, LIVE ROWS; host_rowview.hpp) ---------------------------
 struct RowView {
   SliceStore st;               // the slices of M[rows, :] (this shard's columns)
-  int32_t* rowmap[2] = {nullptr, nullptr};  // [cap_rows] association of view row r': in use / being built
-  uint8_t* in_view[2] = {nullptr, nullptr};  // [mp] row flags: of the view in use / of the one being built
+  DevBuf<int32_t> rowmap[2];   // [mp] association of view row r': in use / being built
+  DevBuf<uint8_t> in_view[2];  // [mp] row flags: of the view in use / of the one being built
   int cur = 0;                 // which of the two the view in use owns
-  SliceView* desc = nullptr;   // device copy of the view's descriptor (what a pass on the view reads)
-  uint32_t* blk = nullptr;     // [nblk + 2] per-block live counts, then their offsets
-  int32_t* viewpos = nullptr;  // [mp] position of a row of M in the view being built, or -1
-  size_t cap_rows = 0, cap_flags = 0, cap_blk = 0, cap_pos = 0;
+  DevBuf<SliceView> desc;      // device copy of the view's descriptor (what a pass on the view reads)
+  DevBuf<uint32_t> blk;        // [nblk + 2] per-block live counts, then their offsets
+  DevBuf<int32_t> viewpos;     // [mp] position of a row of M in the view being built, or -1
   int64_t nrows = 0;
   bool valid = false;
   bool plan_pending = false;    // the work list of the streamed pass is not planned yet (the resident solver took the view)
@@ -171,42 +154,43 @@ struct RowView {
 };
 
 // ---- one column slice of M on one device ------------------------------------------------
-struct Shard : SliceStore {
-  int device = 0;
-  int slot = 0;  // global shard index: owns columns [slot*W, slot*W + W)
-  hipStream_t stream = nullptr;
-  void* S = nullptr;   // m x W, element = float | double
-  void* Cs = nullptr;  // explicit constraint matrix, same shape (only when C != pattern(M))
-  double* part = nullptr;  // [ntiles][2][W]
-  double* u0 = nullptr;
-  double* pt = nullptr;    // point slots [2][V][2][mp]
-  double* cab = nullptr;   // (a, b) of the last pair-mode pass [2][mp]
-  double* X[2] = {nullptr, nullptr};  // candidate tables [V+1][mp][VS], see SolveArgs
-  double* ab = nullptr;    // [P][NSLOT][W]
-  double* scal = nullptr;  // [nwg][Q] partial scalars of k_tail
-  SolverState* st = nullptr;      // ST[2], see SolverState
-  uint8_t* marks = nullptr;       // [KIND_CAP] per-iteration pass marks (profiling), see SolveArgs
-  SolveShared* shared = nullptr;
+// what a shard holds for the problem size it is allocated for: dropped as a whole when the size changes (ensure_problem)
+struct ShardBufs {
+  DevBuf<void> S;   // m x W, element = float | double
+  DevBuf<void> Cs;  // explicit constraint matrix, same shape (only when C != pattern(M))
+  DevBuf<double> part;  // [ntiles][2][W]
+  DevBuf<double> u0;
+  DevBuf<double> pt;    // point slots [2][V][2][mp]
+  DevBuf<double> cab;   // (a, b) of the last pair-mode pass [2][mp]
+  DevBuf<double> X[2];  // candidate tables [V+1][mp][VS], see SolveArgs
+  DevBuf<double> ab;    // [P][NSLOT][W]
+  DevBuf<double> scal;  // [nwg][Q] partial scalars of k_tail
+  DevBuf<SolverState> st;      // ST[2], see SolverState
+  DevBuf<uint8_t> marks;       // [KIND_CAP] per-iteration pass marks (profiling), see SolveArgs
+  DevBuf<SolveShared> shared;
   // affinity inputs (staged once, reused while the sizes fit)
-  double *P1 = nullptr, *P2 = nullptr;  // gathered point tables [d][pstride]
-  float *P1f = nullptr, *P2f = nullptr; // the same, rounded to fp32 (prefilter input)
-  size_t capPf = 0;
-  int32_t* Adev = nullptr;              // [2][m]
-  double *dD1 = nullptr, *dD2 = nullptr;  // raw D1, D2 as uploaded
-  size_t capP = 0, capA = 0, capD1 = 0, capD2 = 0;
-  hipEvent_t ev_reduced = nullptr, ev_copied = nullptr;
+  DevBuf<double> P1, P2;    // gathered point tables [d][pstride]
+  DevBuf<float> P1f, P2f;   // the same, rounded to fp32 (prefilter input)
+  DevBuf<int32_t> Adev;     // [2][m]
+  DevBuf<double> dD1, dD2;  // raw D1, D2 as uploaded
   size_t bytes_S = 0;
   size_t part_tiles = 0;  // row tiles `part` has room for
   // compressed storage of M (CLIPPER_HIP_STORE_F32_CSC / _F64_CSC), see k_csc.hip.h, k_slices.hip.h
   // -- groups: what the fill kernels emit (transient input of the packers, kept for reuse)
-  uint16_t* gOff = nullptr;     // [ngroups][GR_OFFS]
-  uint64_t* gPre = nullptr;     // [ngroups]
-  void* gvals = nullptr;        // float | double [4 * gcap_units]
-  uint8_t* grows = nullptr;     // [4 * gcap_units]
-  CscBuildCtl* cctl = nullptr;  // [CSC_ARENAS]
-  size_t gcap_units = 0, gcap_groups = 0;
+  DevBuf<uint16_t> gOff;     // [ngroups][GR_OFFS]
+  DevBuf<uint64_t> gPre;     // [ngroups]
+  DevBuf<void> gvals;        // float | double [4 * gcap_units]
+  DevBuf<uint8_t> grows;     // [4 * gcap_units]
+  DevBuf<CscBuildCtl> cctl;  // [CSC_ARENAS]
+  size_t gcap_units() const { return grows.cap / 4; }
   // -- slices: what the passes stream: the SliceStore this shard IS (all rows), and the row view
   RowView rv;
+};
+struct Shard : SliceStore, ShardBufs {
+  int device = 0;
+  int slot = 0;  // global shard index: owns columns [slot*W, slot*W + W)
+  hipStream_t stream = nullptr;
+  Event ev_reduced, ev_copied;
 };
 
 // inputs of a problem that are on the device already (a batch stages all its problems with one copy): D1, D2 as the
@@ -224,13 +208,10 @@ struct Resident {
   int last_error = 0;
   int V = 0, E = 0, nunits = 0, maxslots = 0;
   uint32_t lds_slices = 0, lds_total = 0;
-  uint8_t* host_plan = nullptr;      // pinned + mapped: units, then slots per column group
-  uint8_t* host_plan_dev = nullptr;
-  size_t host_plan_cap = 0;
+  PinnedBuf<uint8_t> host_plan;      // mapped: units, then slots per column group
   size_t off_np = 0, off_wc = 0, off_pc = 0;  // where the piece counts / the wave map / the pieces start in the plan
-  unsigned long long* xb = nullptr;  // exchange buffer [2][maxslots][V+1][mp][2] (granules)
-  size_t xb_cap = 0;
-  unsigned long long* ctl = nullptr;  // [4]: the error word, the two counters of the one-XCD mode
+  DevBuf<unsigned long long> xb;     // exchange buffer [2][maxslots][V+1][mp][2] (granules)
+  DevBuf<unsigned long long> ctl;    // [4]: the error word, the two counters of the one-XCD mode
   unsigned long long epoch = 0;
   int V_forced = 0;                  // (a window other than 1: measured 2.3 x slower per pass)
   bool xcd_off = false;              // the one-XCD mode was refused once (or CLIPPER_HIP_RESIDENT_XCD=0)
@@ -242,13 +223,10 @@ struct ViewResident {
   bool ready = false;        // the view in use fits: `plan` is valid
   int nunits = 0;
   uint32_t lds_slices = 0;
-  uint8_t* host_plan = nullptr;      // pinned + mapped: units, piece counts, wave map, pieces
-  uint8_t* host_plan_dev = nullptr;
-  size_t host_plan_cap = 0;
+  PinnedBuf<uint8_t> host_plan;      // mapped: units, piece counts, wave map, pieces
   size_t off_np = 0, off_wc = 0, off_pc = 0;
-  unsigned long long* xb = nullptr;  // exchange buffer (granules), zero at allocation
-  size_t xb_bytes = 0;
-  uint32_t* ctl = nullptr;           // [RVR_GIVEUP_SLOTS][16]: per launch of a solve [0] error word, [1] arrivals at the exit, [4..5] unit 0's start
+  DevBuf<unsigned long long> xb;     // exchange buffer (granules), zero at allocation
+  DevBuf<uint32_t> ctl;              // [RVR_GIVEUP_SLOTS][16]: per launch of a solve [0] error word, [1] arrivals at the exit, [4..5] unit 0's start
   unsigned long long epoch = 0;      // every launch takes 2^20 epochs
   int target_units = 0;              // CLIPPER_HIP_VIEW_RESIDENT_WGS (0: automatic)
   // Launches that gave up (an exchange that timed out: a unit that did not become resident in time — another tenant
@@ -256,17 +234,16 @@ struct ViewResident {
   // launch of the solve; the host reads them when the solve is over, counts, and BACKS OFF: the next `cooldown` solves
   // of this context stream their views, twice as many after every solve with a give-up (at most 64), one again
   // after a solve whose launches all ran.
-  uint32_t* giveup_host = nullptr;   // pinned + mapped [RVR_GIVEUP_SLOTS][4]: per launch of the solve {error word, iterations,
+  PinnedBuf<uint32_t> giveup_host;   // mapped [RVR_GIVEUP_SLOTS][4]: per launch of the solve {error word, iterations,
                                      // duration in wall-clock ticks (lo, hi)} — RvrArgs::giveup_host
-  hipEvent_t ev[2 * 16] = {};        // profiling level 2: event pairs around the launches of a solve
+  Event ev[2 * 16];                  // profiling level 2: event pairs around the launches of a solve
   int ev_n = 0;
   uint64_t plan_entries = 0;         // stored entries of the view the plan is of
-  uint32_t* giveup_host_dev = nullptr;
   int launches_this_solve = 0;
   int cooldown = 0, cooldown_next = 1;
   int max_units_device = -1;         // workgroups of the kernel the device holds at once (occupancy query; -1: not asked yet)
   bool on_replica = false;           // the plan is of RowView::full (column shards), not of the shard's own view
-  uint8_t* backup = nullptr;         // column shards: SolverState + SolveShared as they were before a launch, restored on
+  DevBuf<uint8_t> backup;            // column shards: SolverState + SolveShared as they were before a launch, restored on
                                      // the ranks whose launch ran when another rank's gave up (all ranks go on alike)
 };
 constexpr int RVR_GIVEUP_SLOTS = 16;
@@ -275,19 +252,19 @@ constexpr int RVR_GIVEUP_SLOTS = 16;
 // CLIPPER problem of their own — a child context on the parent's device and stream, kept from solve to solve
 constexpr int SUB_MAX_ENTRIES = 4;   // hand-overs per solve (each leave costs a host round trip)
 constexpr int64_t SUB_MIN_M = 12000; // full problems below this keep their views (the resident solver on a view takes them)
-struct SubProblem {
+struct SubBufs {  // its lists: dropped as a whole (sub_free)
+  DevBuf<int32_t> cnt;     // [mp] entries of every column among the view's rows (an upper bound: quads x 4)
+  DevBuf<uint8_t> flags;   // [mp] 1 = the association is in the sub-problem
+  DevBuf<int32_t> colmap;  // [mp] sub-problem index -> association
+  DevBuf<int32_t> pos;     // [mp] association -> sub-problem index, or -1
+  DevBuf<uint32_t> blk;    // block counts / offsets of the list build
+  DevBuf<int32_t> nout_acc;  // device counter of k_sub_leave
+  PinnedBuf<SubRecord> rec;  // mapped: what the selection found
+};
+struct SubProblem : SubBufs {
   struct clipper_hip_ctx* ctx = nullptr;        // M[S,S] as slices
   struct clipper_hip_ctx* ctx_dense = nullptr;  // M[S,S] as a dense fp32 store (where it is mostly non-zero: the inlier block)
   struct clipper_hip_ctx* use = nullptr;        // the one the solve is handed over to
-  int32_t* cnt = nullptr;     // [mp] entries of every column among the view's rows (an upper bound: quads x 4)
-  uint8_t* flags = nullptr;   // [mp] 1 = the association is in the sub-problem
-  int32_t* colmap = nullptr;  // [mp] sub-problem index -> association
-  int32_t* pos = nullptr;     // [mp] association -> sub-problem index, or -1
-  uint32_t* blk = nullptr;    // block counts / offsets of the list build
-  int32_t* nout_acc = nullptr;  // device counter of k_sub_leave
-  size_t cap = 0, cap_blk = 0;
-  SubRecord* rec = nullptr;   // pinned + mapped: what the selection found
-  SubRecord* rec_dev = nullptr;
   bool ready = false;    // a sub-problem of the view in use stands ready: the decision may ask for the hand-over
   bool active = false;   // the solve's launches run on it
   int entries = 0;       // hand-overs of this solve
@@ -339,9 +316,8 @@ struct clipper_hip_ctx {
   // exchange through the caller (clipper_hip_comm_init_callback) instead of RCCL
   clipper_hip_allgather_fn xchg_fn = nullptr;
   void* xchg_user = nullptr;
-  double* xchg_send = nullptr;  // pinned staging of this rank's block / of the gathered blocks
-  double* xchg_recv = nullptr;
-  size_t xchg_cap = 0;
+  PinnedBuf<double> xchg_send;  // staging of this rank's block / of the gathered blocks
+  PinnedBuf<double> xchg_recv;
 
   int64_t m = 0;  // associations / matrix dimension
   int64_t W = 0;  // shard pitch
@@ -353,11 +329,11 @@ struct clipper_hip_ctx {
   bool csc_emitted = false;  // the fill kernel of this build wrote the groups itself
   CscOut csc_out{};          // what that kernel was given
   int csc_nblocks = 0, csc_nstrips = 0;  // 64-row blocks, 128-column strips of the groups
-  uint32_t* csc_hLq = nullptr;     // pinned host copy of sLq
-  CscBuildCtl* csc_hctl = nullptr; // pinned host copy of the build's counters
-  uint64_t* csc_htotal = nullptr;  // pinned: total slice units of the last count
-  SliceWork* csc_hwork = nullptr;  // pinned staging of the work list
-  size_t csc_hcap_slices = 0, csc_hcap_work = 0;
+  PinnedBuf<uint32_t> csc_hLq;      // host copy of sLq
+  PinnedBuf<CscBuildCtl> csc_hctl;  // host copy of the build's counters
+  PinnedBuf<uint64_t> csc_htotal;   // total slice units of the last count
+  PinnedBuf<SliceWork> csc_hwork;   // staging of the work list
+  size_t csc_hLq_slices = 0;        // slices csc_hLq was sized for (its bytes round them up and carry a trailer)
   int staged_d = 0;          // dimension of the staged point tables (0 = nothing staged)
   double staged_maxabs = 0;  // max |coordinate| of D1, D2: bounds the fp32 prefilter's error
   bool plain_affinity = false;  // CLIPPER_HIP_AFFINITY=plain: non-compacting fill kernels
@@ -371,18 +347,14 @@ struct clipper_hip_ctx {
   std::vector<int32_t> A;  // column-major m x 2 (host copy)
   std::vector<int32_t> nodes;
   std::vector<double> u_host;  // the last solve's u on the host (rounding works on it)
-  PinnedBuf mc_stage;          // the staging buffer of this context's maximum-clique calls (host_maxclique.hpp)
+  PinnedBuf<uint8_t> mc_stage;          // the staging buffer of this context's maximum-clique calls (host_maxclique.hpp)
 
-  SolveShared* host_state = nullptr;  // pinned, 2 slots (multi-process snapshots)
-  hipEvent_t ev_poll[2] = {nullptr, nullptr};
-  hipEvent_t ev_aff[2] = {nullptr, nullptr};  // timing of the affinity build
-  HostMirror* mirror = nullptr;      // pinned + coherent: progress record written by the device
-  HostMirror* mirror_dev = nullptr;  // its device address
-  uint8_t* kind = nullptr;           // pinned + coherent: per-iteration pass / transition marks
-  uint8_t* kind_dev = nullptr;       // (profiling only), written by the device
-  double* u_pinned = nullptr;        // pinned staging of the final u (the device writes it)
-  double* u_pinned_dev = nullptr;    // its device address
-  size_t u_pinned_cap = 0;
+  PinnedBuf<SolveShared> host_state;  // 2 slots (multi-process snapshots)
+  Event ev_poll[2];
+  Event ev_aff[2];                   // timing of the affinity build
+  PinnedBuf<HostMirror> mirror;      // mapped + coherent: progress record written by the device
+  PinnedBuf<uint8_t> kind;           // mapped + coherent: per-iteration pass / transition marks (profiling only)
+  PinnedBuf<double> u_pinned;        // mapped staging of the final u (the device writes it)
   int V = 6;               // line-search window: candidate vectors per pass
   int V_forced = 0;        // CLIPPER_HIP_WINDOW
   int64_t mp = 0;          // rows of a candidate table
@@ -403,11 +375,9 @@ struct clipper_hip_ctx {
   bool rv_fresh = false;      // the next iteration is the first after a view was built
   int rv_mode = 0;            // 0 = automatic, 1 = never (clipper_hip_set_row_view / CLIPPER_HIP_ROW_VIEW=0),
                               // 2 = views, but never the resident solver on one (CLIPPER_HIP_VIEW_RESIDENT=0)
-  SliceView* rv_desc_host = nullptr;     // pinned + mapped staging of a view's descriptor (two slots, used in turn)
+  PinnedBuf<SliceView> rv_desc_host;  // mapped staging of a view's descriptor (two slots, used in turn)
   int rv_desc_slot = 0;
-  SliceView* rv_desc_host_dev = nullptr;
-  int32_t* rv_count = nullptr;      // pinned + mapped: rows of the view being built
-  int32_t* rv_count_dev = nullptr;
+  PinnedBuf<int32_t> rv_count;        // mapped: rows of the view being built
   clipper_hip_view_stats_t rv_stats{};
   // the live sub-problem: this context's (`sub`), or the context this one IS the sub-problem of (`parent`: its
   // launches report into the parent's progress record and borrow the parent's stream)
@@ -416,13 +386,13 @@ struct clipper_hip_ctx {
   bool adaptive_window = true;   // CLIPPER_HIP_ADAPTIVE_WINDOW=0: every window pass multiplies all V candidates
   int sub_mode = 0;           // 0 = automatic, 1 = never (clipper_hip_set_subproblem / CLIPPER_HIP_SUBPROBLEM=0), 2 = always as slices
 
-  long long* stamps_dev = nullptr;  // CLIPPER_HIP_STAMPS=1: [4096][4], see SolveArgs::stamps; =2: [16384][4]
+  DevBuf<long long> stamps_dev;     // CLIPPER_HIP_STAMPS=1: [4096][4], see SolveArgs::stamps; =2: [16384][4]
   int stamps_rows = 4096;
   bool profiling = false;
   int profiling_level = 0;
-  std::vector<hipEvent_t> ev_pairs;  // 2*MAX_EVENT_PAIRS, created by clipper_hip_set_profiling
+  std::vector<Event> ev_pairs;  // 2*MAX_EVENT_PAIRS, created by clipper_hip_set_profiling
   std::vector<int64_t> ev_launch_index;  // which mat-vec launch of the solve each pair timed
-  std::vector<hipEvent_t> ev_xchg;       // 2*MAX_EVENT_PAIRS: around the exchange of the same iterations
+  std::vector<Event> ev_xchg;       // 2*MAX_EVENT_PAIRS: around the exchange of the same iterations
   std::vector<char> ev_xchg_used;
   int ev_used = 0;
   int64_t launch_counter = 0;

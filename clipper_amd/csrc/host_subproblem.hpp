@@ -38,20 +38,7 @@ void sub_free(Ctx* h) {
     }
   }
   sp.use = nullptr;
-  if (!h->sh.empty()) hipSetDevice(h->sh[0].device);
-  auto fr = [](auto*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-  };
-  fr(sp.cnt);
-  fr(sp.flags);
-  fr(sp.colmap);
-  fr(sp.pos);
-  fr(sp.blk);
-  fr(sp.nout_acc);
-  if (sp.rec) hipHostFree(sp.rec);
-  sp.rec = sp.rec_dev = nullptr;
-  sp.cap = sp.cap_blk = 0;
+  static_cast<SubBufs&>(sp) = SubBufs{};
   sp.ready = sp.active = false;
 }
 
@@ -70,14 +57,12 @@ int sub_stage(Ctx* h, Ctx* c, int64_t nS) {
   if (rc) return rc;
   const int d = h->staged_d;
   const int64_t qs = round_up(nS, 64);
-  const size_t bp = static_cast<size_t>(d) * qs * sizeof(double);
-  size_t capP2 = cs.capP;
-  if ((rc = ensure_cap(cs.P1, cs.capP, bp))) return rc;
-  if ((rc = ensure_cap(cs.P2, capP2, bp))) return rc;
-  size_t capPf2 = cs.capPf;
-  if ((rc = ensure_cap(cs.P1f, cs.capPf, bp / 2))) return rc;
-  if ((rc = ensure_cap(cs.P2f, capPf2, bp / 2))) return rc;
-  if ((rc = ensure_cap(cs.Adev, cs.capA, static_cast<size_t>(2 * nS) * sizeof(int32_t)))) return rc;
+  const size_t np = static_cast<size_t>(d) * qs;
+  HIPCHK(cs.P1.grow(np));
+  HIPCHK(cs.P2.grow(np));
+  HIPCHK(cs.P1f.grow(np));
+  HIPCHK(cs.P2f.grow(np));
+  HIPCHK(cs.Adev.grow(static_cast<size_t>(2 * nS)));
   dim3 grid(static_cast<unsigned>(ceil_div(qs, 256))), block(256);
   hipLaunchKernelGGL(k_sub_gather_points, grid, block, 0, s.stream, s.P1, s.P1f, d, h->staged_pstride, s.Adev, h->m,
                      h->sub.colmap, nS, qs, cs.P1, cs.P1f, cs.Adev, 0);
@@ -105,25 +90,17 @@ int sub_prepare_v(Ctx* h) {
   const int64_t m = h->m, mp = h->mp;
   const int nblk = static_cast<int>(ceil_div(m, RV_BLK));
   int rc;
-  if (static_cast<size_t>(mp) > sp.cap) {
-    for (void** p : {reinterpret_cast<void**>(&sp.cnt), reinterpret_cast<void**>(&sp.flags), reinterpret_cast<void**>(&sp.colmap),
-                     reinterpret_cast<void**>(&sp.pos)}) {
-      if (*p) hipFree(*p);
-      *p = nullptr;
-    }
-    sp.cap = 0;
-    HIPCHK(hipMalloc(&sp.cnt, static_cast<size_t>(mp) * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&sp.flags, static_cast<size_t>(mp)));
-    HIPCHK(hipMalloc(&sp.colmap, static_cast<size_t>(mp) * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&sp.pos, static_cast<size_t>(mp) * sizeof(int32_t)));
-    sp.cap = static_cast<size_t>(mp);
+  if (static_cast<size_t>(mp) > sp.pos.cap) {  // the four lists go together, then come together (`pos` is made last: its capacity is theirs)
+    sp.cnt.reset(), sp.flags.reset(), sp.colmap.reset(), sp.pos.reset();
+    HIPCHK(sp.cnt.alloc(static_cast<size_t>(mp)));
+    HIPCHK(sp.flags.alloc(static_cast<size_t>(mp)));
+    HIPCHK(sp.colmap.alloc(static_cast<size_t>(mp)));
+    HIPCHK(sp.pos.alloc(static_cast<size_t>(mp)));
   }
-  if ((rc = grow_dev(sp.blk, sp.cap_blk, static_cast<size_t>(nblk) + 2))) return rc;
-  if (!sp.nout_acc) HIPCHK(hipMalloc(&sp.nout_acc, 8 * sizeof(int32_t)));
-  if (!sp.rec) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&sp.rec), 64, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&sp.rec_dev), sp.rec, 0));
-  }
+  HIPCHK(sp.blk.grow(static_cast<size_t>(nblk) + 2));
+  if (!sp.nout_acc) HIPCHK(sp.nout_acc.alloc(8));
+  static_assert(sizeof(SubRecord) <= 64, "the record fits its 64 pinned bytes");
+  if (!sp.rec) HIPCHK(sp.rec.alloc_bytes(64, hipHostMallocMapped | hipHostMallocCoherent));
   sp.rec->nS = -1;
   sp.rec->ncol = -1;
   sp.rec->n0 = -1;
@@ -133,10 +110,10 @@ int sub_prepare_v(Ctx* h) {
   hipLaunchKernelGGL(k_sub_colcount, dim3(static_cast<unsigned>(ceil_div(RV.ncg, 4))), dim3(256), 0, s.stream, RV, sp.cnt, mp);
   hipLaunchKernelGGL((k_sub_flags<V>), dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream, s.st + h->par, sp.cnt,
                      v.in_view[v.cur], m, mp, sp.flags, sp.blk, sp.nout_acc);
-  hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(1024), 0, s.stream, sp.blk, nblk, &sp.rec_dev->nS);
+  hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(1024), 0, s.stream, sp.blk, nblk, &sp.rec.dev->nS);
   hipLaunchKernelGGL(k_rv_scatter, dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream, sp.flags, m, sp.blk, sp.colmap,
-                     static_cast<int64_t>(sp.cap), sp.pos, mp);
-  hipLaunchKernelGGL(k_sub_publish, dim3(1), dim3(64), 0, s.stream, sp.nout_acc, sp.rec_dev);
+                     static_cast<int64_t>(sp.pos.cap), sp.pos, mp);
+  hipLaunchKernelGGL(k_sub_publish, dim3(1), dim3(64), 0, s.stream, sp.nout_acc, sp.rec.dev);
   HIPCHK(hipStreamSynchronize(s.stream));
   HIPCHK(hipGetLastError());
   std::atomic_thread_fence(std::memory_order_acquire);

@@ -13,11 +13,7 @@ namespace {
 
 // four events (around the kernels, and around the sort's passes among them), released on every path
 struct VoxelEvents {
-  hipEvent_t a = nullptr, b = nullptr, sa = nullptr, sb = nullptr;
-  ~VoxelEvents() {
-    for (hipEvent_t e : {a, b, sa, sb})
-      if (e) hipEventDestroy(e);
-  }
+  Event a, b, sa, sb;
 };
 
 // Every argument has been checked; n >= 1.
@@ -49,10 +45,10 @@ int voxel_run(int device, const double* P, const double* N, int64_t n_, const cl
                          dtrace, (trace_out ? nn : 0) * sizeof(int32_t), dmax, sizeof(int32_t),
                          totals, static_cast<size_t>(8 * SORT_RADIX) * sizeof(int32_t)))
     return rc;
-  HIPCHK(hipEventCreate(&ev.a));
-  HIPCHK(hipEventCreate(&ev.b));
-  HIPCHK(hipEventCreate(&ev.sa));
-  HIPCHK(hipEventCreate(&ev.sb));
+  HIPCHK(ev.a.create());
+  HIPCHK(ev.b.create());
+  HIPCHK(ev.sa.create());
+  HIPCHK(ev.sb.create());
 
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
   if (int rc = copy_up(dP, P, n3, st)) return rc;

@@ -756,6 +756,11 @@ int clipper_hip_debug_stamps(clipper_hip_t* h, int64_t* out, int capacity);
  * solvers' time-outs (tests/test_gpu_rv_resident.py runs it in a second process). */
 int clipper_hip_debug_occupy(int device, int workgroups, int lds_bytes, double milliseconds);
 
+/* Test infrastructure: what this process's library holds right now, as its owning types count it
+ * (csrc/host_buf.hpp): out[0] live device buffers, out[1] their bytes, out[2] live pinned host buffers, out[3] live
+ * events, out[4] allocations and event creations made so far. Touches no device. */
+int clipper_hip_debug_live_resources(int64_t out[5]);
+
 int clipper_hip_device_info(const clipper_hip_t* h, char* name64, int* cus, int64_t* hbm_bytes);
 
 /* ---- batched solves: many independent small problems in one call -----------------

@@ -103,3 +103,23 @@ def test_env_knobs_are_the_documented_ones():
     table = doc[doc.index("Environment knobs"):]
     listed = set(re.findall(r"`(CLIPPER_HIP_[A-Z0-9_]+)`", table))
     assert read == listed, (sorted(read - listed), sorted(listed - read))
+
+
+def test_only_the_owning_types_allocate():
+    """Device memory, pinned memory and events are owned by the types of csrc/host_buf.hpp (DevBuf, PinnedBuf, Event):
+    no other source of the library calls the runtime's allocation, free, event-creation or event-destruction
+    functions, so nothing can be allocated without an owner that releases it. Source scan, comments left out."""
+    csrc = os.path.join(ROOT, "clipper_amd", "csrc")
+    raw = re.compile(r"\bhip(Malloc|Free|HostMalloc|HostFree|EventCreate\w*|EventDestroy)\s*\(")
+    bad = []
+    for dp, _, fs in os.walk(csrc):
+        for f in fs:
+            if f.endswith((".hip", ".h", ".hpp", ".cpp")) and f != "host_buf.hpp":
+                text = open(os.path.join(dp, f), errors="ignore").read()
+                text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+                for n, line in enumerate(text.split("\n"), 1):
+                    if raw.search(line.split("//")[0]):
+                        bad.append(f"{f}:{n}")
+    assert not bad, f"raw allocation calls outside host_buf.hpp: {bad}"
+    own = open(os.path.join(csrc, "host_buf.hpp")).read()
+    assert all(f"hip{name}(" in own for name in ("Malloc", "Free", "HostMalloc", "HostFree", "EventCreate", "EventDestroy"))

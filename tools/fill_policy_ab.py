@@ -83,7 +83,10 @@ def run_child(lib, part):
     if r.returncode != 0 or line is None:
         raise SystemExit(f"bench.py failed ({r.returncode}) on {lib}:\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
     j = json.loads(line)
-    return {"bench.py headline step (m=10000)": j["value"], "bench.py m=100000 step": j["scaling_probe"]["ms_per_step"]}
+    rows = {"bench.py headline step (m=10000)": j["value"], "bench.py m=100000 step": j["scaling_probe"]["ms_per_step"]}
+    if "ms_per_step_host_buffers" in j:  # (the same step with its inputs in host memory: what the host side costs)
+        rows["bench.py headline step from host buffers (m=10000)"] = j["ms_per_step_host_buffers"]
+    return rows
 
 
 def main(parts=None, what="affinity fill: parent (A) against result (B), tools/fill_policy_ab.py",
