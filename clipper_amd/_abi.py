@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_knn_set_search", "clipper_hip_knn_search", "clipper_hip_knn_last_search",
     "clipper_hip_icp", "clipper_hip_evaluate_registration", "clipper_hip_voxel_downsample",
     "clipper_hip_icp_generalized", "clipper_hip_estimate_covariances",
+    "clipper_hip_ransac_correspondences", "clipper_hip_ransac_needed",
 ]
 
 
@@ -252,6 +253,30 @@ class IcpInfo(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+RANSAC_CONVERGED, RANSAC_MAX_HYPOTHESES, RANSAC_NO_MODEL = 0, 1, 2  # CLIPPER_RANSAC_*: clipper_ransac_info_t.status
+
+
+class RansacParams(C.Structure):
+    """clipper_ransac_params_t"""
+    _fields_ = [("max_distance", C.c_double), ("edge_similarity", C.c_double), ("confidence", C.c_double),
+                ("max_hypotheses", C.c_int64), ("hypotheses_per_round", C.c_int32), ("n_sample", C.c_int32),
+                ("refine_iterations", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+    def __init__(self, max_distance=0.0, n_sample=3, edge_similarity=0.9, max_hypotheses=100000, confidence=0.999, seed=0,
+                 refine_iterations=1, hypotheses_per_round=4096):
+        super().__init__(float(max_distance), float(edge_similarity), float(confidence), int(max_hypotheses),
+                         int(hypotheses_per_round), int(n_sample), int(refine_iterations), 0, int(seed) & (2 ** 64 - 1))
+
+
+class RansacInfo(C.Structure):
+    """clipper_ransac_info_t: how the rounds ended (status: RANSAC_*), the accepted polish steps, the hypotheses formed
+    and the ones scored, the winner's number, count and sample, the count / fitness / inlier_rmse under T_out and the
+    device time. `inliers` (a boolean mask over the associations) is attached by the Python facade."""
+    _fields_ = [("status", C.c_int32), ("refined", C.c_int32), ("evaluated", C.c_int64), ("checked", C.c_int64),
+                ("best_hypothesis", C.c_int64), ("best_count", C.c_int64), ("count", C.c_int64), ("fitness", C.c_double),
+                ("inlier_rmse", C.c_double), ("sample", C.c_int32 * 8), ("device_ms", C.c_double)]
+
+
 class VoxelInfo(C.Structure):
     """clipper_voxel_info_t: the grid of a voxel_down_sample (voxels per axis), the 8-bit passes of its radix sort, the
     pairs per workgroup of a pass, the chunk length of the sums (512), the members of the fullest voxel, the device time
@@ -374,6 +399,11 @@ def load_library(path: str = LIB_PATH):
                                                                  ip, ip, C.POINTER(i64)]
     L.clipper_hip_precision_recall.argtypes = [ip, i64, ip, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.clipper_hip_estimate_rigid_transform.argtypes = [dp, i64, dp, i64, ip, i64, dp]
+    if hasattr(L, "clipper_hip_ransac_correspondences"):  # (absent from an older build named by CLIPPER_HIP_LIB)
+        L.clipper_hip_ransac_correspondences.argtypes = [C.c_int, dp, i64, dp, i64, ip, i64, C.POINTER(RansacParams), dp,
+                                                         C.POINTER(C.c_uint8), C.POINTER(RansacInfo)]
+        L.clipper_hip_ransac_needed.argtypes = [i64, i64, C.c_int32, C.c_double]
+        L.clipper_hip_ransac_needed.restype = i64
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
     if hasattr(L, "clipper_hip_debug_live_resources"):  # (absent from an older build named by CLIPPER_HIP_LIB: the A/B tools)
         L.clipper_hip_debug_live_resources.argtypes = [C.POINTER(i64)]
@@ -888,6 +918,35 @@ def estimate_rigid_transform(D1, D2, A) -> np.ndarray:
     _status(L.clipper_hip_estimate_rigid_transform(_dp(D1), D1.shape[1], _dp(D2), D2.shape[1], _ip(a), A.shape[0],
                                                    _dp(T)))
     return T.reshape(4, 4).T.copy()
+
+
+def ransac_correspondences(D1, D2, A, max_distance, n_sample=3, edge_similarity=0.9, max_hypotheses=100000,
+                           confidence=0.999, seed=0, refine_iterations=1, hypotheses_per_round=4096, device=0):
+    """clipper_hip_ransac_correspondences: the rigid transform most of the associations A (m x 2) between D1 and D2
+    (3 x n, columns = points, the layouts of estimate_rigid_transform) agree on, by RANSAC on the device. Returns
+    (T 4 x 4, info): info.status is RANSAC_*, info.inliers the boolean mask of the associations within max_distance
+    under T."""
+    L = load_library()
+    D1, D2 = _f64_colmajor(D1), _f64_colmajor(D2)
+    if D1.ndim != 2 or D1.shape[0] != 3 or D2.ndim != 2 or D2.shape[0] != 3:
+        raise ValueError("D1 and D2 must be 3 x n")
+    A = np.asarray(A, dtype=np.int32).reshape(-1, 2)
+    a = np.ascontiguousarray(A.T).reshape(-1)
+    prm = RansacParams(max_distance, n_sample, edge_similarity, max_hypotheses, confidence, seed, refine_iterations,
+                       hypotheses_per_round)
+    T = np.zeros(16, dtype=np.float64)
+    mask = np.zeros(max(A.shape[0], 1), dtype=np.uint8)
+    info = RansacInfo()
+    _status(L.clipper_hip_ransac_correspondences(device, _dp(D1), D1.shape[1], _dp(D2), D2.shape[1], _ip(a), A.shape[0],
+                                                 C.byref(prm), _dp(T), mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 C.byref(info)))
+    info.inliers = mask[:A.shape[0]].astype(bool)
+    return T.reshape(4, 4).T.copy(), info
+
+
+def ransac_needed(count: int, m: int, n_sample: int = 3, confidence: float = 0.999) -> int:
+    """clipper_hip_ransac_needed: the hypotheses after which RANSAC stops CONVERGED with `count` inliers among m"""
+    return int(_status(load_library().clipper_hip_ransac_needed(count, m, n_sample, confidence)))
 
 
 def device_count() -> int:

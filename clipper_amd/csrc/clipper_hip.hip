@@ -71,6 +71,7 @@ using clipper_hip_buf::PinnedBuf;
 #include "host_match.hpp"
 #include "host_features.hpp"
 #include "host_icp.hpp"
+#include "host_ransac.hpp"
 #include "host_voxel.hpp"
 
 extern "C" {
@@ -447,6 +448,21 @@ int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n
                                       const double* T, double max_distance, double* fitness, double* inlier_rmse,
                                       int64_t* count, int32_t* corr_out) try {
   return evaluate_registration(device, P_src, n_src, P_tgt, n_tgt, T, max_distance, fitness, inlier_rmse, count, corr_out);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- RANSAC over putative associations (host_ransac.hpp) ------------------------------------------
+
+int clipper_hip_ransac_correspondences(int device, const double* D1, int64_t n1, const double* D2, int64_t n2,
+                                       const int32_t* A, int64_t m, const clipper_ransac_params_t* params,
+                                       double* T_out, uint8_t* inlier_out, clipper_ransac_info_t* info) try {
+  return ransac_correspondences(device, D1, n1, D2, n2, A, m, params, T_out, inlier_out, info);
+} CLIPPER_HIP_GUARD_INT
+
+int64_t clipper_hip_ransac_needed(int64_t count, int64_t m, int32_t n_sample, double confidence) try {
+  if (m < 1 || count < 0 || count > m || n_sample < RANSAC_MIN_SAMPLE || n_sample > RANSAC_MAX_SAMPLE ||
+      !(confidence > 0.0 && confidence < 1.0))
+    return fail(CLIPPER_HIP_E_INVALID, "ransac_needed: count in 0..m, m >= 1, n_sample in 3..8 and confidence in (0, 1) are needed");
+  return ransac_needed(count, m, n_sample, confidence);
 } CLIPPER_HIP_GUARD_INT
 
 // ---- voxel down-sampling of a point cloud (host_voxel.hpp) --------------------------------------

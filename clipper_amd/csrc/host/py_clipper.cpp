@@ -350,6 +350,49 @@ PYBIND11_MODULE(clipperpy, m) {
       "(fitness, inlier_rmse, count) of the alignment T (4 x 4) of src onto tgt (3 x n) on the GPU: a source point is an "
       "inlier when its nearest target point lies within max_distance.");
 
+  // the consensus estimator over putative associations, on the device
+  m_utils.def(
+      "ransac_correspondences",
+      [](const clipper::MatrixXd& D1, const clipper::MatrixXd& D2, const clipper::Association& A, double max_distance,
+         int n_sample, double edge_similarity, int64_t max_hypotheses, double confidence, uint64_t seed, int refine_iterations,
+         int hypotheses_per_round, int device) {
+        namespace reg = clipper::registration;
+        reg::RansacParams prm;
+        prm.max_distance = max_distance;
+        prm.n_sample = n_sample;
+        prm.edge_similarity = edge_similarity;
+        prm.max_hypotheses = max_hypotheses;
+        prm.confidence = confidence;
+        prm.seed = seed;
+        prm.refine_iterations = refine_iterations;
+        prm.hypotheses_per_round = hypotheses_per_round;
+        const reg::RansacInfo r = reg::ransac_correspondences(D1, D2, A, prm, device);
+        clipper::MatrixXd T(4, 4);
+        for (int i = 0; i < 16; ++i) T.data()[i] = r.T[i];
+        py::array_t<bool> mask(static_cast<py::ssize_t>(r.inliers.size()));
+        for (size_t k = 0; k < r.inliers.size(); ++k) mask.mutable_at(static_cast<py::ssize_t>(k)) = r.inliers[k] != 0;
+        py::dict info;
+        info["status"] = static_cast<int>(r.status);
+        info["refined"] = r.refined;
+        info["evaluated"] = r.evaluated;
+        info["checked"] = r.checked;
+        info["best_hypothesis"] = r.best_hypothesis;
+        info["best_count"] = r.best_count;
+        info["count"] = r.count;
+        info["fitness"] = r.fitness;
+        info["inlier_rmse"] = r.inlier_rmse;
+        info["sample"] = std::vector<int32_t>(r.sample.begin(), r.sample.end());
+        info["device_ms"] = r.device_ms;
+        info["inliers"] = mask;
+        return py::make_tuple(T, info);
+      },
+      "D1"_a, "D2"_a, "A"_a, "max_distance"_a, "n_sample"_a = 3, "edge_similarity"_a = 0.9, "max_hypotheses"_a = 100000,
+      "confidence"_a = 0.999, "seed"_a = 0, "refine_iterations"_a = 1, "hypotheses_per_round"_a = 4096, "device"_a = 0,
+      "RANSAC over the putative associations A (m x 2) between D1 and D2 (3 x n, one point per column) on the GPU: the "
+      "rigid transform most associations agree on within max_distance. Returns (T, info): info holds status (0 converged, "
+      "1 max hypotheses, 2 no model), inliers (a boolean mask over A), count, fitness, inlier_rmse, best_hypothesis, "
+      "best_count, sample, evaluated, checked, refined and device_ms. The same inputs and seed give the same bytes.");
+
   // the route of the d = 3 nearest-neighbour search behind them ("The grid route of the search"): process-wide
   py::enum_<clipper::registration::KnnSearch>(m_utils, "KnnSearch")
       .value("Brute", clipper::registration::KnnSearch::Brute)

@@ -47,6 +47,8 @@
 //   k_knn_grid.hip.h  the same lists as k_knn.hip.h through a uniform grid over the searched cloud (d = 3)
 //   k_icp.hip.h       the ICP refinement over that grid: transform, the sums of each metric, the step on one thread; the
 //                     per-point covariances of the generalized metric
+//   k_ransac.hip.h    RANSAC over putative associations: hypotheses, their compaction in order, the score of survivors x
+//                     correspondences as integer counts, the best by one key, the polish by ICP's sums and step
 //   k_features.hip.h  surface normals and FPFH descriptors of a point cloud (what the matcher and PointNormalDistance take)
 //   k_sort.hip.h      a stable LSD radix sort of (u64 key, i32 index) pairs, 8-bit digits
 //   k_voxel.hip.h     voxel down-sampling over that sort: one centroid (and normal) per occupied voxel, bit for bit
@@ -70,5 +72,6 @@
 #include "k_features.hip.h"
 #include "k_knn_grid.hip.h"
 #include "k_icp.hip.h"
+#include "k_ransac.hip.h"
 #include "k_sort.hip.h"
 #include "k_voxel.hip.h"

@@ -152,6 +152,24 @@ def estimate_rigid_transform(D1: np.ndarray, D2: np.ndarray, A: np.ndarray) -> n
     return T
 
 
+def ransac_correspondences(D1: np.ndarray, D2: np.ndarray, A: np.ndarray, max_distance: float, n_sample: int = 3,
+                           edge_similarity: float = 0.9, max_hypotheses: int = 100000, confidence: float = 0.999,
+                           seed: int = 0, refine_iterations: int = 1, hypotheses_per_round: int = 4096, device: int = 0):
+    """RANSAC over the putative associations A (m x 2), on the GPU (clipper_hip_ransac_correspondences): the rigid
+    transform T (4 x 4) with D2[:, A[k,1]] ~ R D1[:, A[k,0]] + t that most associations agree on within max_distance.
+    D1, D2: 3 x n as for estimate_rigid_transform. A hypothesis fits n_sample associations whose edge lengths agree
+    within edge_similarity in both clouds; its score is its inlier count; the rounds of hypotheses_per_round stop at
+    `confidence` or at max_hypotheses; the winner is polished refine_iterations times over its inliers. The same
+    inputs and seed give the same bytes. Returns (T, info): info.status (clipper_amd._abi.RANSAC_*), info.inliers (a
+    boolean mask over A), info.count, info.fitness, info.inlier_rmse, info.best_hypothesis, info.best_count,
+    info.sample, info.evaluated, info.checked, info.refined."""
+    from . import _abi as abi
+    return abi.ransac_correspondences(np.asarray(D1, dtype=np.float64), np.asarray(D2, dtype=np.float64), A, max_distance,
+                                      n_sample=n_sample, edge_similarity=edge_similarity, max_hypotheses=max_hypotheses,
+                                      confidence=confidence, seed=seed, refine_iterations=refine_iterations,
+                                      hypotheses_per_round=hypotheses_per_round, device=device)
+
+
 def transform_error(T: np.ndarray, That: np.ndarray):
     """(rotation error [rad], translation error) of an estimate against the truth."""
     E = np.linalg.inv(T) @ That

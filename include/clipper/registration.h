@@ -6,9 +6,10 @@
  *        consumes the selected associations (examples/python/ex4_bunny.ipynb), the feature
  *        matcher that produces the putative ones, and the stage in front of it: raw cloud ->
  *        normals -> FPFH descriptors, and the step behind it: ICP over the whole clouds (icp,
- *        evaluate_registration). Thin C++ wrappers over the C ABI (include/clipper_hip.h);
+ *        evaluate_registration), and the consensus estimator beside the solve (ransac_correspondences).
+ *        Thin C++ wrappers over the C ABI (include/clipper_hip.h);
  *        match_descriptors, voxel_down_sample, estimate_normals, compute_fpfh, icp, estimate_covariances,
- *        icp_generalized and evaluate_registration work on the device.
+ *        icp_generalized, evaluate_registration and ransac_correspondences work on the device.
  */
 #pragma once
 
@@ -322,6 +323,61 @@ inline RegistrationQuality evaluate_registration(const invariants::Data& src, co
     throw std::invalid_argument(clipper_hip_last_error());
   if (correspondences) correspondences->resize(static_cast<size_t>(src.cols()));
   return q;
+}
+
+/// The parameters of ransac_correspondences (clipper_ransac_params_t)
+struct RansacParams {
+  double max_distance = 0.0;        ///< an association is an inlier within this distance under T; must be set (> 0)
+  int n_sample = 3;                 ///< 3..8 associations per hypothesis
+  double edge_similarity = 0.9;     ///< [0, 1): the edges of a sample must agree within this ratio in both clouds; 0 = off
+  int64_t max_hypotheses = 100000;  ///< 1..2^31 - 1
+  double confidence = 0.999;        ///< (0, 1): stop once an all-inlier sample has been drawn with this probability
+  uint64_t seed = 0;                ///< the same inputs and seed give the same bytes
+  int refine_iterations = 1;        ///< 0..10 point-to-point steps over the winner's inliers
+  int hypotheses_per_round = 4096;  ///< 256..65536, a multiple of 256
+};
+
+enum class RansacStatus { Converged = 0, MaxHypotheses = 1, NoModel = 2 };
+
+/// What ransac_correspondences returns (clipper_ransac_info_t with T and the mask)
+struct RansacInfo {
+  double T[16];                  ///< column-major 4 x 4; the identity with NoModel
+  std::vector<uint8_t> inliers;  ///< per association: within max_distance under T
+  RansacStatus status;
+  int refined;
+  int64_t evaluated, checked, best_hypothesis, best_count, count;
+  double fitness, inlier_rmse;
+  std::array<int32_t, 8> sample;
+  double device_ms;
+};
+
+/// RANSAC over the putative associations A (m x 2) between D1 and D2 (3 x n), on the device: the rigid transform most
+/// associations agree on within max_distance, its inliers and how the search ended (clipper_hip_ransac_correspondences).
+inline RansacInfo ransac_correspondences(const invariants::Data& D1, const invariants::Data& D2, const Association& A,
+                                         const RansacParams& params, int device = 0) {
+  if (D1.rows() != 3 || D2.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  if (A.rows() > 0 && A.cols() != 2) throw std::invalid_argument("associations must be m x 2");
+  clipper_ransac_params_t prm{params.max_distance, params.edge_similarity, params.confidence, params.max_hypotheses,
+                              params.hypotheses_per_round, params.n_sample, params.refine_iterations, 0, params.seed};
+  clipper_ransac_info_t info{};
+  RansacInfo r{};
+  r.inliers.assign(static_cast<size_t>(A.rows() > 0 ? A.rows() : 1), 0);
+  if (clipper_hip_ransac_correspondences(device, D1.data(), D1.cols(), D2.data(), D2.cols(), A.data(), A.rows(), &prm, r.T,
+                                         r.inliers.data(), &info))
+    throw std::invalid_argument(clipper_hip_last_error());
+  r.inliers.resize(static_cast<size_t>(A.rows()));
+  r.status = static_cast<RansacStatus>(info.status);
+  r.refined = info.refined;
+  r.evaluated = info.evaluated;
+  r.checked = info.checked;
+  r.best_hypothesis = info.best_hypothesis;
+  r.best_count = info.best_count;
+  r.count = info.count;
+  r.fitness = info.fitness;
+  r.inlier_rmse = info.inlier_rmse;
+  for (int a = 0; a < 8; ++a) r.sample[static_cast<size_t>(a)] = info.sample[a];
+  r.device_ms = info.device_ms;
+  return r;
 }
 
 }  // namespace registration

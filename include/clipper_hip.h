@@ -621,6 +621,56 @@ int clipper_hip_evaluate_registration(int device, const double* P_src, int64_t n
                                       const double* T, double max_distance, double* fitness, double* inlier_rmse,
                                       int64_t* count, int32_t* corr_out);
 
+/* RANSAC OVER PUTATIVE ASSOCIATIONS: a consensus estimate of the rigid transform with D2[:, A(k,1)] ~ T D1[:, A(k,0)]
+ * from the m associations A (column-major m x 2), on the device. D1: 3 x n1, D2: 3 x n2, column-major. Hypothesis h
+ * draws n_sample distinct associations by a counter-based integer draw (a function of seed, h and the attempt alone),
+ * is dropped when an edge of its sample has zero length in either cloud or the squared lengths differ by more than
+ * edge_similarity^2, is fitted as clipper_hip_estimate_rigid_transform fits, and scores the NUMBER of associations with
+ * |T p - b|^2 <= max_distance^2; the best is the largest count, among equal counts the smallest h. Hypotheses run in
+ * rounds of hypotheses_per_round; after a round the call stops CONVERGED when evaluated >=
+ * clipper_hip_ransac_needed(best count, m, n_sample, confidence), MAX_HYPOTHESES when evaluated >= max_hypotheses,
+ * NO_MODEL (T_out the identity) when the hypotheses run out with a best count below 3. The winner is polished up to
+ * refine_iterations times by ICP's point-to-point step over its inliers, a step being kept while the count does not
+ * fall. Every floating-point sum has one fixed order and nothing is fused, and the score is an integer: what the call
+ * returns is a function of its inputs alone (the rules in full: clipper_amd/csrc/ransac_rules.hpp).
+ * Stand-alone: needs no context. */
+typedef struct clipper_ransac_params_t {
+  double  max_distance;          /* positive and finite */
+  double  edge_similarity;       /* [0, 1); facades default to 0.9 */
+  double  confidence;            /* (0, 1); facades default to 0.999 */
+  int64_t max_hypotheses;        /* 1 .. 2^31 - 1; facades default to 100000 */
+  int32_t hypotheses_per_round;  /* 256 .. 65536, a multiple of 256; facades default to 4096 */
+  int32_t n_sample;              /* 3 .. 8; facades default to 3 */
+  int32_t refine_iterations;     /* 0 .. 10; facades default to 1 */
+  int32_t reserved;              /* 0 */
+  uint64_t seed;
+} clipper_ransac_params_t;
+enum { CLIPPER_RANSAC_CONVERGED = 0, CLIPPER_RANSAC_MAX_HYPOTHESES = 1, CLIPPER_RANSAC_NO_MODEL = 2 };
+typedef struct clipper_ransac_info_t {
+  int32_t status;           /* CLIPPER_RANSAC_* */
+  int32_t refined;          /* accepted polish steps */
+  int64_t evaluated;        /* hypotheses formed: a multiple of hypotheses_per_round */
+  int64_t checked;          /* of those, the ones that passed both checks and were scored */
+  int64_t best_hypothesis;  /* the winner's number (-1: NO_MODEL) */
+  int64_t best_count;       /* its count, before the polish */
+  int64_t count;            /* inliers, fitness = count / m and inlier_rmse = sqrt(sum sqd / count) under T_out */
+  double  fitness;
+  double  inlier_rmse;
+  int32_t sample[8];        /* the winner's sample: rows of A, -1 past n_sample */
+  double  device_ms;        /* between two events around the device work */
+} clipper_ransac_info_t;
+
+/* T_out: column-major 4 x 4. inlier_out (m flags, may be NULL): the associations within max_distance under T_out.
+ * Refused (CLIPPER_HIP_E_INVALID, before any device work, the offending value named): a parameter outside its range,
+ * m < n_sample, a row of A outside the clouds, a non-finite coordinate of a point that A refers to. */
+int clipper_hip_ransac_correspondences(int device, const double* D1, int64_t n1, const double* D2, int64_t n2,
+                                       const int32_t* A, int64_t m, const clipper_ransac_params_t* params,
+                                       double* T_out, uint8_t* inlier_out, clipper_ransac_info_t* info);
+/* The stop rule, host only: ceil(log(1 - confidence) / log(1 - (count / m)^n_sample)); 1 when (count / m)^n_sample >= 1,
+ * INT64_MAX when 1 - (count / m)^n_sample rounds to 1. <0 (CLIPPER_HIP_E_INVALID): an argument out of range (count in
+ * 0..m, m >= 1, n_sample in 3..8, confidence in (0, 1)). */
+int64_t clipper_hip_ransac_needed(int64_t count, int64_t m, int32_t n_sample, double confidence);
+
 /* VOXEL DOWN-SAMPLING: the step in front of the normals, on the device. The cloud P (3 x n column-major as
  * `clipper::Data`, n >= 0) is cut into cubes of edge voxel_size whose origin is the cloud's own minimum corner lo (the
  * exact per-axis minimum; not Open3D's min - voxel_size / 2): the voxel of x on axis a is floor((x_a - lo_a) * inv)
