@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_icp", "clipper_hip_evaluate_registration", "clipper_hip_voxel_downsample",
     "clipper_hip_icp_generalized", "clipper_hip_estimate_covariances",
     "clipper_hip_ransac_correspondences", "clipper_hip_ransac_needed",
+    "clipper_hip_icp_robust", "clipper_hip_icp_generalized_robust",
 ]
 
 
@@ -253,6 +254,25 @@ class IcpInfo(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+# CLIPPER_ICP_LOSS_*: clipper_icp_robust_t.loss
+ICP_LOSS_NONE, ICP_LOSS_HUBER, ICP_LOSS_CAUCHY, ICP_LOSS_TUKEY, ICP_LOSS_GEMAN_MCCLURE = 0, 1, 2, 3, 4
+
+
+class IcpRobust(C.Structure):
+    """clipper_icp_robust_t: the loss (ICP_LOSS_*), its scale (a distance; not read without a loss) and the trimmed
+    fraction kept of the points within max_distance (1 = no trimming)"""
+    _fields_ = [("loss", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("trim", C.c_double)]
+
+    def __init__(self, loss=ICP_LOSS_NONE, scale=0.0, trim=1.0):
+        super().__init__(int(loss), 0, float(scale), float(trim))
+
+
+class IcpRobustInfo(C.Structure):
+    """clipper_icp_robust_info_t, of the last history row: the points within max_distance before trimming, the sum of
+    the weights (point-to-point; 0 otherwise) and the trimming threshold tau"""
+    _fields_ = [("within", C.c_int64), ("weight_sum", C.c_double), ("trim_sqd", C.c_double)]
+
+
 RANSAC_CONVERGED, RANSAC_MAX_HYPOTHESES, RANSAC_NO_MODEL = 0, 1, 2  # CLIPPER_RANSAC_*: clipper_ransac_info_t.status
 
 
@@ -382,6 +402,11 @@ def load_library(path: str = LIB_PATH):
                                   C.POINTER(IcpInfo), dp]
     L.clipper_hip_icp_generalized.argtypes = [C.c_int, dp, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams), dp,
                                               C.POINTER(IcpInfo), dp]
+    L.clipper_hip_icp_robust.argtypes = [C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams),
+                                         C.POINTER(IcpRobust), dp, C.POINTER(IcpInfo), C.POINTER(IcpRobustInfo), dp]
+    L.clipper_hip_icp_generalized_robust.argtypes = [C.c_int, dp, dp, C.c_int64, dp, dp, C.c_int64, dp, C.POINTER(IcpParams),
+                                                     C.POINTER(IcpRobust), dp, C.POINTER(IcpInfo), C.POINTER(IcpRobustInfo),
+                                                     dp]
     L.clipper_hip_estimate_covariances.argtypes = [C.c_int, dp, C.c_int64, nbp, C.c_double, dp, ip]
     L.clipper_hip_evaluate_registration.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, dp, C.c_double,
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
@@ -1291,6 +1316,59 @@ def icp_generalized(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance: float
         raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
     info.history = hist[:info.iterations + 1].copy()
     return T.reshape(4, 4).T.copy(), info
+
+
+def _robust_result(T, info, rinfo, hist):
+    """(T 4 x 4, info) of a robust call: info as icp's, with the three fields of clipper_icp_robust_info_t attached"""
+    info.history = hist[:info.iterations + 1].copy()
+    info.within, info.weight_sum, info.trim_sqd = int(rinfo.within), float(rinfo.weight_sum), float(rinfo.trim_sqd)
+    return T.reshape(4, 4).T.copy(), info
+
+
+def icp_robust(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None, max_distance: float = 0.0,
+               max_iterations: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, loss: int = ICP_LOSS_NONE,
+               scale: float = 0.0, trim: float = 1.0, device: int = 0):
+    """clipper_hip_icp_robust: icp with a robust loss (ICP_LOSS_*, `scale` a distance) weighing every pair by its
+    residual, and / or trimming: each iteration keeps the fraction `trim` of the points within max_distance with the
+    smallest distances (ties at the threshold all kept). count, fitness, rmse and the history are over the kept points.
+    Returns (T 4 x 4, info) as icp does, info also carrying within, weight_sum and trim_sqd of the last row."""
+    L = load_library()
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Nt = None if N_tgt is None else _cloud(N_tgt, "N_tgt")
+    if Nt is not None and Nt.shape[1] != Pt.shape[1]:
+        raise ValueError("P_tgt and N_tgt must hold the same number of points")
+    t0, t0p = _transform_arg(T_init, "T_init")
+    prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
+    rb, rinfo = IcpRobust(loss, scale, trim), IcpRobustInfo()
+    T = np.zeros(16, dtype=np.float64)
+    info = IcpInfo()
+    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+    rc = L.clipper_hip_icp_robust(device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1], t0p,
+                                  C.byref(prm), C.byref(rb), _dp(T), C.byref(info), C.byref(rinfo), _dp(hist))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return _robust_result(T, info, rinfo, hist)
+
+
+def icp_generalized_robust(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance: float = 0.0, max_iterations: int = 30,
+                           rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, loss: int = ICP_LOSS_NONE, scale: float = 0.0,
+                           trim: float = 1.0, device: int = 0):
+    """clipper_hip_icp_generalized_robust: icp_generalized with icp_robust's loss and trimming; the residual a loss
+    weighs is d^T M d of the pair. Returns (T 4 x 4, info) as icp_robust does."""
+    L = load_library()
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Cs, Ct = _covariances(C_src, "C_src", Ps.shape[1]), _covariances(C_tgt, "C_tgt", Pt.shape[1])
+    t0, t0p = _transform_arg(T_init, "T_init")
+    prm = IcpParams(ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse)
+    rb, rinfo = IcpRobust(loss, scale, trim), IcpRobustInfo()
+    T = np.zeros(16, dtype=np.float64)
+    info = IcpInfo()
+    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+    rc = L.clipper_hip_icp_generalized_robust(device, _dp(Ps), _dp(Cs), Ps.shape[1], _dp(Pt), _dp(Ct), Pt.shape[1], t0p,
+                                              C.byref(prm), C.byref(rb), _dp(T), C.byref(info), C.byref(rinfo), _dp(hist))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    return _robust_result(T, info, rinfo, hist)
 
 
 def evaluate_registration(P_src, P_tgt, T=None, max_distance: float = 0.0, device: int = 0, return_correspondences: bool = False):

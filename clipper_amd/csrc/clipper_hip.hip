@@ -439,6 +439,21 @@ int clipper_hip_icp_generalized(int device, const double* P_src, const double* C
   return icp_generalized(device, P_src, C_src, n_src, P_tgt, C_tgt, n_tgt, T_init, params, T_out, info, history);
 } CLIPPER_HIP_GUARD_INT
 
+int clipper_hip_icp_robust(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
+                           int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
+                           const clipper_icp_robust_t* robust, double* T_out, clipper_icp_info_t* info,
+                           clipper_icp_robust_info_t* robust_info, double* history) try {
+  return icp_robust(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init, params, robust, T_out, info, robust_info, history);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_icp_generalized_robust(int device, const double* P_src, const double* C_src, int64_t n_src,
+                                       const double* P_tgt, const double* C_tgt, int64_t n_tgt, const double* T_init,
+                                       const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+                                       clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) try {
+  return icp_generalized_robust(device, P_src, C_src, n_src, P_tgt, C_tgt, n_tgt, T_init, params, robust, T_out, info,
+                                robust_info, history);
+} CLIPPER_HIP_GUARD_INT
+
 int clipper_hip_estimate_covariances(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb, double epsilon,
                                      double* C_out, int32_t* count_out) try {
   return estimate_covariances(device, P, n, nb, epsilon, C_out, count_out);

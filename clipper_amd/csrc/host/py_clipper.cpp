@@ -221,6 +221,24 @@ static py::tuple icp_tuple(const clipper::registration::IcpResult& r) {
   return py::make_tuple(T, info);
 }
 
+// utils.icp_robust and utils.icp_generalized_robust: the same tuple, info also holding the robust call's three fields
+static py::tuple icp_robust_tuple(const clipper::registration::IcpRobustResult& r) {
+  py::tuple out = icp_tuple(r);
+  py::dict info = out[1].cast<py::dict>();
+  info["within"] = r.within;
+  info["weight_sum"] = r.weight_sum;
+  info["trim_sqd"] = r.trim_sqd;
+  return out;
+}
+
+static clipper::registration::IcpRobust icp_robust_of(const std::string& loss, double scale, double trim) {
+  namespace reg = clipper::registration;
+  static const char* const names[] = {"none", "huber", "cauchy", "tukey", "geman_mcclure"};
+  for (int l = 0; l < 5; ++l)
+    if (loss == names[l]) return reg::IcpRobust{static_cast<reg::IcpLoss>(l), scale, trim};
+  throw std::invalid_argument("loss must be one of \"none\", \"huber\", \"cauchy\", \"tukey\", \"geman_mcclure\"");
+}
+
 PYBIND11_MODULE(clipperpy, m) {
   m.doc() = "A graph-theoretic framework for robust data association (MI355X hot path)";
   m.attr("__version__") = CLIPPER_VERSION;
@@ -339,6 +357,50 @@ PYBIND11_MODULE(clipperpy, m) {
       "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6,
       "Generalized ICP on the GPU: refine the alignment T_init (4 x 4) of src onto tgt (3 x n) with the plane-to-plane "
       "metric over the clouds' covariances (6 x n, e.g. estimate_covariances'). Returns (T, info) as icp does.");
+  // robust losses and trimming: icp and icp_generalized with a defence against bad pairs
+  m_utils.def(
+      "icp_robust",
+      [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T_init, const std::string& method,
+         const clipper::MatrixXd& normals, double max_distance, int max_iterations, double rel_fitness, double rel_rmse,
+         const std::string& loss, double scale, double trim) {
+        namespace reg = clipper::registration;
+        if (method != "point" && method != "plane") throw std::invalid_argument("method must be \"point\" or \"plane\"");
+        if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
+        reg::IcpParams prm;
+        prm.method = method == "plane" ? reg::IcpMethod::PointToPlane : reg::IcpMethod::PointToPoint;
+        prm.max_distance = max_distance;
+        prm.max_iterations = max_iterations;
+        prm.rel_fitness = rel_fitness;
+        prm.rel_rmse = rel_rmse;
+        const reg::IcpRobustResult r = reg::icp_robust(src, tgt, prm, icp_robust_of(loss, scale, trim), T_init.data(), normals);
+        return icp_robust_tuple(r);
+      },
+      "src"_a, "tgt"_a, "T_init"_a, "method"_a = "point", "normals"_a = clipper::MatrixXd(3, 0), "max_distance"_a = 0.0,
+      "max_iterations"_a = 30, "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6, "loss"_a = "none", "scale"_a = 0.0, "trim"_a = 1.0,
+      "icp with a robust loss (\"huber\", \"cauchy\", \"tukey\", \"geman_mcclure\"; scale: a distance) weighing every pair by "
+      "its residual, and / or trimming: each iteration keeps the fraction trim of the points within max_distance with the "
+      "smallest distances. Returns (T, info) as icp does, info also holding within, weight_sum and trim_sqd. \"tukey\" and "
+      "\"geman_mcclure\" give pairs far beyond the scale no weight: start them close to the answer.");
+  m_utils.def(
+      "icp_generalized_robust",
+      [](const clipper::MatrixXd& src, const clipper::MatrixXd& src_cov, const clipper::MatrixXd& tgt,
+         const clipper::MatrixXd& tgt_cov, const clipper::MatrixXd& T_init, double max_distance, int max_iterations,
+         double rel_fitness, double rel_rmse, const std::string& loss, double scale, double trim) {
+        namespace reg = clipper::registration;
+        if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
+        reg::IcpParams prm;
+        prm.method = reg::IcpMethod::Generalized;
+        prm.max_distance = max_distance;
+        prm.max_iterations = max_iterations;
+        prm.rel_fitness = rel_fitness;
+        prm.rel_rmse = rel_rmse;
+        const reg::IcpRobustResult r =
+            reg::icp_generalized_robust(src, src_cov, tgt, tgt_cov, prm, icp_robust_of(loss, scale, trim), T_init.data());
+        return icp_robust_tuple(r);
+      },
+      "src"_a, "src_cov"_a, "tgt"_a, "tgt_cov"_a, "T_init"_a, "max_distance"_a = 0.0, "max_iterations"_a = 30,
+      "rel_fitness"_a = 1e-6, "rel_rmse"_a = 1e-6, "loss"_a = "none", "scale"_a = 0.0, "trim"_a = 1.0,
+      "icp_generalized with icp_robust's loss and trimming; the residual a loss weighs is d^T M d of the pair.");
   m_utils.def(
       "evaluate_registration",
       [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T, double max_distance) {

@@ -1,4 +1,4 @@
-// host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized and clipper_hip_evaluate_registration
+// host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized, their robust forms and clipper_hip_evaluate_registration
 // ("ICP over a kept search grid" and "Generalized ICP"), and of clipper_hip_estimate_covariances,
 // the stage that makes the generalized metric's covariances. Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
 // built once and queried every iteration with k_knn_grid<1>; the source is binned by the target's grid once, at
@@ -30,17 +30,44 @@ void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns
                      dhist);
 }
 
+// the round of the robust entry points: the weighted sums against the selection's control block, the robust layout's step
+template <int METHOD>
+void icp_round_robust(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt,
+                      const double* dCs, const double* dCt, int32_t nt, double d2, const double (&o)[3],
+                      const clipper_icp::Robust& rb, const IcpSelect* dctl, double* dpart, int32_t nb, const IcpStop& stop,
+                      int k, double* dsums, double* dT, IcpRecord* drec, double* dhist, hipStream_t st) {
+  hipLaunchKernelGGL((k_icp_accumulate_robust<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt,
+                     dNt, dCs, dCt, dT, nt, d2, o[0], o[1], o[2], rb.loss, rb.scale, rb.scale * rb.scale, dctl, dpart);
+  hipLaunchKernelGGL((k_icp_step_robust<METHOD>), dim3(1), dim3(256), 0, st, dpart, nb, stop, k, o[0], o[1], o[2], dsums, dT,
+                     drec, dhist);
+}
+
+// The trimming threshold of the round under the current lists: two launches per digit, nothing read by the host.
+void icp_select(const int32_t* oi, const double* od, int32_t ns, double d2, double trim, IcpSelect* dctl, uint32_t* dtot,
+                hipStream_t st) {
+  const dim3 tiles(static_cast<unsigned>(ceil_div(ns, SELECT_TILE)));
+  for (int pass = 0; pass < ICP_SELECT_PASSES; ++pass) {
+    hipLaunchKernelGGL(k_select_hist<>, tiles, dim3(SELECT_THREADS), 0, st, oi, od, ns, d2, pass, dctl, dtot);
+    hipLaunchKernelGGL(k_select_pick<>, dim3(1), dim3(SELECT_THREADS), 0, st, dtot, pass, trim, dctl);
+  }
+}
+
 // Every argument has been checked. T0: column-major 4 x 4. history: (max_iterations + 1) x 3 or null; corr_out: ns or null.
 // Nt: the target's normals (point-to-plane alone); Cs, Ct: the covariances of the source and the target, 6 x n
-// (generalized alone): uploaded once each.
+// (generalized alone): uploaded once each. rb: the robust settings (clipper_hip_icp_robust and
+// clipper_hip_icp_generalized_robust; null: the plain rounds, whose launches and buffers are untouched by it), rinfo: what
+// they report besides info. With rb the selection runs between the search and the sums when trim < 1, then the weighted
+// round; the control block stays on the device.
 int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, const double* Cs, const double* Ct,
             int64_t nt_, const double* T0, const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info,
-            double* history, int32_t* corr_out) {
+            double* history, int32_t* corr_out, const clipper_icp::Robust* rb = nullptr,
+            clipper_icp_robust_info_t* rinfo = nullptr) {
   if (int rc = use_device(device)) return rc;
 
   const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
   const bool plane = prm.method == ICP_POINT_TO_PLANE, gen = prm.method == ICP_GENERALIZED;
-  const int terms = icp_terms(prm.method);
+  const int terms = rb ? icp_robust_terms(prm.method) : icp_terms(prm.method);
+  const bool trimmed = rb && rb->trim < 1.0;
   const int32_t nb = static_cast<int32_t>(ceil_div(ns, ICP_BLOCK));
   const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
   const size_t nrows = static_cast<size_t>(prm.max_iterations) + 1;
@@ -51,6 +78,8 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   int32_t *oi = nullptr, *perm = nullptr, *visited = nullptr;
   unsigned long long* dsum = nullptr;
   IcpRecord* drec = nullptr;
+  IcpSelect* dctl = nullptr;
+  uint32_t* dtot = nullptr;
   DevTemps tmp;
   IcpHostState hs;
   const size_t s1 = static_cast<size_t>(ns);
@@ -66,6 +95,8 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     return rc;
   if (gen)  // (behind the buffers every method has: theirs keep their places)
     if (int rc = tmp.alloc(device, dCs, s1 * 6 * sizeof(double), dCt, static_cast<size_t>(nt) * 6 * sizeof(double))) return rc;
+  if (rb)  // (behind every buffer of the plain call)
+    if (int rc = tmp.alloc(device, dctl, sizeof(IcpSelect), dtot, ICP_SELECT_RADIX * sizeof(uint32_t))) return rc;
   HIPCHK(hs.rec.alloc(1));
   HIPCHK(hs.a.create());
   HIPCHK(hs.b.create());
@@ -101,6 +132,13 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   icp_origin(lo, hi, o);
 
   const double d2 = prm.max_distance * prm.max_distance;
+  IcpSelect sel{};  // without trimming, for the whole call: every point within max_distance is kept
+  sel.tau = d2;
+  sel.any = 1;
+  if (rb) {
+    HIPCHK(hipMemcpyAsync(dctl, &sel, sizeof(IcpSelect), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dtot, 0, ICP_SELECT_RADIX * sizeof(uint32_t), st));
+  }
   const IcpStop stop{prm.max_iterations, static_cast<int64_t>(ns), prm.rel_fitness, prm.rel_rmse};
   const dim3 sb(static_cast<unsigned>(ceil_div(ns, 256)));
   // CLIPPER_HIP_ICP_REBIN=1 (measurement only: tools/icp_probe.py) bins the moved source anew every iteration
@@ -126,7 +164,14 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     } else if (int rc = knn_brute_query(1, 3, dq, ns, dPt, nt, bs, od, oi, st)) {
       return rc;
     }
-    if (gen)
+    if (trimmed) icp_select(oi, od, ns, d2, rb->trim, dctl, dtot, st);
+    if (rb && gen)
+      icp_round_robust<ICP_GENERALIZED>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    else if (rb && plane)
+      icp_round_robust<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    else if (rb)
+      icp_round_robust<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    else if (gen)
       icp_round<ICP_GENERALIZED>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
     else if (plane)
       icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
@@ -144,6 +189,11 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   unsigned long long cand = 0;
   HIPCHK(hipMemcpyAsync(&cand, dsum, sizeof(cand), hipMemcpyDeviceToHost, st));
   if (T_out) HIPCHK(hipMemcpyAsync(T_out, dT, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  double wsum = 0.0;  // (of the last row: position ICP_POINT_WEIGHT_SUM of the sums the last step folded)
+  if (rb) {
+    HIPCHK(hipMemcpyAsync(&sel, dctl, sizeof(IcpSelect), hipMemcpyDeviceToHost, st));
+    if (!plane && !gen) HIPCHK(hipMemcpyAsync(&wsum, dsums + ICP_POINT_WEIGHT_SUM, sizeof(double), hipMemcpyDeviceToHost, st));
+  }
   if (history) HIPCHK(hipMemcpyAsync(history, dhist, nrows * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
   std::vector<int32_t> hi_(corr_out ? static_cast<size_t>(ns) : 0);
   std::vector<double> hd_(hi_.size());
@@ -165,6 +215,11 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     for (int a = 0; a < 3; ++a) info->dim[a] = route == CLIPPER_HIP_KNN_GRID ? ix.g.dim[a] : 0;
     info->candidates = static_cast<int64_t>(cand);
     info->device_ms = static_cast<double>(ms);
+  }
+  if (rinfo) {
+    rinfo->within = trimmed ? sel.within : hs.rec->count;  // (untrimmed: every point within max_distance is kept)
+    rinfo->weight_sum = wsum;
+    rinfo->trim_sqd = sel.tau;
   }
   return 0;
 }
@@ -206,6 +261,54 @@ int icp_generalized(int device, const double* P_src, const double* C_src, int64_
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_generalized: %s", why.c_str());
   return icp_run(device, P_src, n_src, P_tgt, nullptr, C_src, C_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
                  history, nullptr);
+}
+
+clipper_icp::Robust icp_robust_of(const clipper_icp_robust_t* r) {
+  return r ? clipper_icp::Robust{r->loss, r->reserved, r->scale, r->trim} : clipper_icp::Robust{0, 0, 0.0, 1.0};
+}
+
+// clipper_hip_icp with robust settings: its checks, then the settings', then icp_run's robust rounds
+int icp_robust(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt, int64_t n_tgt,
+               const double* T_init, const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+               clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) {
+  namespace ci = clipper_icp;
+  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
+                                           params->rel_rmse}
+                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  const ci::Robust rb = icp_robust_of(robust);
+  std::string why = !T_out ? "null T_out" : "";
+  if (why.empty()) why = ci::check_not_generalized(params ? &h : nullptr);
+  if (why.empty()) why = ci::check_params(params ? &h : nullptr);
+  if (why.empty()) why = ci::check_robust(robust ? &rb : nullptr);
+  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
+  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
+  if (why.empty()) why = ci::check_transform("T_init", T_init);
+  if (why.empty()) why = ci::check_target_normals(h.method, N_tgt, n_tgt);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_robust: %s", why.c_str());
+  return icp_run(device, P_src, n_src, P_tgt, N_tgt, nullptr, nullptr, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
+                 history, nullptr, &rb, robust_info);
+}
+
+int icp_generalized_robust(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt,
+                           const double* C_tgt, int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
+                           const clipper_icp_robust_t* robust, double* T_out, clipper_icp_info_t* info,
+                           clipper_icp_robust_info_t* robust_info, double* history) {
+  namespace ci = clipper_icp;
+  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
+                                           params->rel_rmse}
+                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  const ci::Robust rb = icp_robust_of(robust);
+  std::string why = !T_out ? "null T_out" : "";
+  if (why.empty()) why = ci::check_generalized_params(params ? &h : nullptr);
+  if (why.empty()) why = ci::check_robust(robust ? &rb : nullptr);
+  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
+  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
+  if (why.empty()) why = ci::check_transform("T_init", T_init);
+  if (why.empty()) why = ci::check_covariances("source", C_src, n_src);
+  if (why.empty()) why = ci::check_covariances("target", C_tgt, n_tgt);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_generalized_robust: %s", why.c_str());
+  return icp_run(device, P_src, n_src, P_tgt, nullptr, C_src, C_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
+                 history, nullptr, &rb, robust_info);
 }
 
 // The covariances of the generalized metric: host_features.hpp's features_run with the one kernel behind the search

@@ -1,5 +1,6 @@
 // host_icp_check.hpp — ICP and the evaluation of a registration, the part that needs no device: the argument checks of
-// clipper_hip_icp, clipper_hip_icp_generalized, clipper_hip_estimate_covariances and clipper_hip_evaluate_registration.
+// clipper_hip_icp, clipper_hip_icp_generalized, their robust forms (clipper_hip_icp_robust,
+// clipper_hip_icp_generalized_robust), clipper_hip_estimate_covariances and clipper_hip_evaluate_registration.
 // Pure host code (no HIP): tests/cpp/test_icp_rules.cpp and tests/cpp/test_gicp_rules.cpp compile it with g++ alone. A refusal comes back as its message (empty: accepted) and names the offending value; the caller
 // hands it to fail(). Every check runs before any device work.
 #pragma once
@@ -108,6 +109,24 @@ inline std::string check_covariances(const char* what, const double* C, int64_t 
         return format("%s covariances: the matrix of point %lld is not positive definite (leading minor %d = %.17g)", what,
                       static_cast<long long>(p), k + 1, minor[k]);
   }
+  return {};
+}
+
+// clipper_icp_robust_t, as the checks read it
+struct Robust {
+  int loss, reserved;
+  double scale, trim;
+};
+
+// the robust settings of clipper_hip_icp_robust and clipper_hip_icp_generalized_robust. scale is read only with a loss.
+inline std::string check_robust(const Robust* r) {
+  if (!r) return "null robust";
+  if (r->loss < clipper_hip::ICP_LOSS_NONE || r->loss > clipper_hip::ICP_LOSS_GEMAN_MCCLURE)
+    return format("unknown loss %d (the losses are 0..%d)", r->loss, clipper_hip::ICP_LOSS_GEMAN_MCCLURE);
+  if (r->reserved != 0) return format("robust: reserved must be 0 (reserved = %d)", r->reserved);
+  if (r->loss != clipper_hip::ICP_LOSS_NONE && !(std::isfinite(r->scale) && r->scale > 0.0))
+    return format("scale must be positive and finite with a loss (scale = %g)", r->scale);
+  if (!(r->trim > 0.0 && r->trim <= 1.0)) return format("trim must be in (0, 1] (trim = %g)", r->trim);
   return {};
 }
 

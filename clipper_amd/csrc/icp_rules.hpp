@@ -8,7 +8,9 @@
 // written (the build runs with -ffp-contract=off), no floating-point atomics anywhere, so that T_out and the history
 // are functions of the inputs alone. No HIP: builds with g++ as well (tests/cpp/test_icp_rules.cpp runs whole ICPs over
 // this header, tests/cpp/test_gicp_rules.cpp generalized ones); tests/icp_model.py and tests/gicp_model.py restate the
-// same contract in numpy.
+// same contract in numpy. The robust losses and the trimming of clipper_hip_icp_robust are additions at the end of each
+// part (the weight of a pair, the weighted terms, the rank select of the trimming threshold): the plain rules keep their
+// names and bits; tests/cpp/test_icp_robust_rules.cpp runs them, tests/icp_robust_model.py restates them.
 #pragma once
 
 #include <math.h>
@@ -211,6 +213,48 @@ ICP_HD void icp_generalized_terms(const double (&q)[3], const double (&b)[3], co
   t[29] = sqd;
 }
 
+// ---- robust losses: the weight of a kept pair, the weighted terms --------------------------------------------------------
+// e: the squared residual of the pair, a value the term functions above already form: sqd (point-to-point), r * r
+// (point-to-plane, position 28), d . e (generalized, position 28). k2 = scale * scale, evaluated once by the caller.
+// Each weight is written in exactly this order. A non-number e leaves non-numbers in the sums (w * t of terms that are
+// non-numbers themselves), and the pivot and determinant tests end the call DEGENERATE: no rule of its own. Tukey and
+// Geman-McClure redescend: a pair far beyond the scale weighs nothing, so from a far start they may not converge.
+constexpr int ICP_LOSS_NONE = 0, ICP_LOSS_HUBER = 1, ICP_LOSS_CAUCHY = 2, ICP_LOSS_TUKEY = 3, ICP_LOSS_GEMAN_MCCLURE = 4;
+
+ICP_HD double icp_weight(int loss, double e, double scale, double k2) {
+  if (loss == ICP_LOSS_HUBER) return e <= k2 ? 1.0 : scale / sqrt(e);
+  if (loss == ICP_LOSS_CAUCHY) return 1.0 / (1.0 + e / k2);
+  if (loss == ICP_LOSS_TUKEY) {
+    if (!(e < k2)) return 0.0;
+    const double u = 1.0 - e / k2;
+    return u * u;
+  }
+  if (loss == ICP_LOSS_GEMAN_MCCLURE) {
+    const double g = k2 / (k2 + e);
+    return g * g;
+  }
+  return 1.0;
+}
+
+// The robust layouts. Every term becomes w * t[a] but the count (position 0) and the last term (sum sqd): count, fitness
+// and rmse stay head counts and plain distances. Point-to-plane and generalized keep their 30 positions; point-to-point
+// gains the sum of the weights: positions 0..15 as in icp_point_terms, 16 = sum w, 17 = sum sqd (still the last). With
+// w = 1.0 every product is exact and sum w equals the count: the plain sums, bit for bit.
+constexpr int ICP_POINT_ROBUST_TERMS = 18, ICP_POINT_WEIGHT_SUM = 16;
+constexpr int icp_robust_terms(int method) { return method == ICP_POINT_TO_POINT ? ICP_POINT_ROBUST_TERMS : ICP_PLANE_TERMS; }
+
+ICP_HD void icp_point_terms_weighted(const double (&t)[ICP_POINT_TERMS], double w, double (&out)[ICP_POINT_ROBUST_TERMS]) {
+  out[0] = t[0];
+  for (int a = 1; a < 16; ++a) out[a] = w * t[a];
+  out[ICP_POINT_WEIGHT_SUM] = w;
+  out[17] = t[16];
+}
+
+// point-to-plane and generalized, in place
+ICP_HD void icp_plane_terms_weighted(double w, double (&t)[ICP_PLANE_TERMS]) {
+  for (int a = 1; a < ICP_PLANE_TERMS - 1; ++a) t[a] = w * t[a];
+}
+
 // ---- the order of addition ------------------------------------------------------------------------------------------
 // Work item i of a workgroup of ICP_BLOCK holds source point (block * ICP_BLOCK + i) in its original order (+0.0 past
 // the end); the workgroup folds by the halving tree, stride 128 down to 1: v[i] = v[i] + v[i + s] for i < s; v[0] is
@@ -319,8 +363,8 @@ ICP_HD void icp_about_origin(const double* R, const double (&v)[3], const double
 // ---- the step, point-to-point ---------------------------------------------------------------------------------------
 // S: the 17 sums. Centroids mq = sum(q - o) / n, mb = sum(b - o) / n; H_rc = S_rc - sum(b - o)_r * mq_c (the centred
 // cross-covariance sum (b - mb)(q - mq)^T); dR = its rotation; the shift is mb - dR mq, about o. false: DEGENERATE.
-ICP_HD bool icp_step_point(const double* S, const double (&o)[3], double* dT) {
-  const double n = S[0];
+// icp_step_point_by: the same step with the centroids divided by `n` (the robust layout: the sum of the weights).
+ICP_HD bool icp_step_point_by(const double* S, double n, const double (&o)[3], double* dT) {
   const double mq[3] = {S[1] / n, S[2] / n, S[3] / n};
   const double mb[3] = {S[4] / n, S[5] / n, S[6] / n};
   double H[9], R[9];
@@ -332,6 +376,8 @@ ICP_HD bool icp_step_point(const double* S, const double (&o)[3], double* dT) {
   icp_about_origin(R, v, o, dT);
   return fabs(icp_det3(R) - 1.0) <= ICP_DET_TOL;
 }
+
+ICP_HD bool icp_step_point(const double* S, const double (&o)[3], double* dT) { return icp_step_point_by(S, S[0], o, dT); }
 
 // ---- the step, point-to-plane and generalized: the 6 x 6 step ----------------------------------------------------------
 // the Cayley map of the rotation vector w: a = w / 2, K = skew(a), R = I + 2 / (1 + |a|^2) (K + K^2), K^2 = a a^T - |a|^2 I.
@@ -457,11 +503,14 @@ struct IcpStop {
 // changes below their bounds), TOO_FEW, MAX_ITERATIONS (k == max_iterations), DEGENERATE (the step refuses, or the
 // updated T would hold a value that is not finite); else T <- dT T and the loop goes on. rec carries iteration k - 1's
 // fitness and rmse in, and this iteration's out. T is touched only where the loop goes on.
-template <int METHOD>
-ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (&o)[3], double* T, IcpRecord& rec, double* row) {
+// ROBUST: S is in the robust layout (icp_robust_terms), whose point-to-point centroids divide by the sum of the weights.
+template <int METHOD, bool ROBUST>
+ICP_HD void icp_iterate_over(const IcpStop& p, int k, const double* S, const double (&o)[3], double* T, IcpRecord& rec,
+                             double* row) {
+  constexpr int TERMS = ROBUST ? icp_robust_terms(METHOD) : icp_terms(METHOD);
   const double cnt = S[0];
   const double fitness = cnt / static_cast<double>(p.n_src);
-  const double rmse = cnt > 0.0 ? sqrt(S[icp_terms(METHOD) - 1] / cnt) : 0.0;
+  const double rmse = cnt > 0.0 ? sqrt(S[TERMS - 1] / cnt) : 0.0;
   if (row) {
     row[0] = cnt;
     row[1] = fitness;
@@ -473,7 +522,10 @@ ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (
   else if (k >= p.max_iterations) status = ICP_MAX_ITERATIONS;
   else {
     double dT[16], N[16];
-    const bool ok = METHOD == ICP_POINT_TO_POINT ? icp_step_point(S, o, dT) : icp_step_plane(S, o, dT);
+    bool ok;
+    if constexpr (METHOD != ICP_POINT_TO_POINT) ok = icp_step_plane(S, o, dT);
+    else if constexpr (ROBUST) ok = icp_step_point_by(S, S[ICP_POINT_WEIGHT_SUM], o, dT);
+    else ok = icp_step_point(S, o, dT);
     for (int i = 0; i < 16; ++i) N[i] = T[i];
     icp_compose(dT, N);
     bool finite = true;
@@ -488,6 +540,68 @@ ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (
   rec.count = static_cast<int64_t>(cnt);
   rec.fitness = fitness;
   rec.rmse = rmse;
+}
+
+template <int METHOD>
+ICP_HD void icp_iterate(const IcpStop& p, int k, const double* S, const double (&o)[3], double* T, IcpRecord& rec, double* row) {
+  icp_iterate_over<METHOD, false>(p, k, S, o, T, rec, row);
+}
+
+// ---- trimming: the threshold by an exact rank select ------------------------------------------------------------------
+// Each iteration, under the current T: within = the source points whose K = 1 entry passes icp_inlier;
+// keep = (int64_t)(trim * (double)within); tau = the keep-th smallest sqd among them, by value; a point is kept iff it
+// passes icp_inlier and sqd <= tau (every point equal to tau is kept, so the count may exceed keep). keep == 0 keeps
+// nothing (the round ends TOO_FEW); trim == 1.0 skips the selection: kept = within. sqd of a candidate is non-negative
+// and finite, so its bit pattern as uint64_t orders as its value: the select is a most-significant-digit-first radix
+// select on those 64 bits, ICP_SELECT_PASSES digits of ICP_SELECT_BITS. Pass p: the histogram of digit p over the
+// candidates whose higher digits equal the prefix found so far, then the digit at which the running count first
+// reaches the remaining rank (1-based). Every digit width gives the same tau.
+constexpr int ICP_SELECT_BITS = 8, ICP_SELECT_RADIX = 1 << ICP_SELECT_BITS, ICP_SELECT_PASSES = 64 / ICP_SELECT_BITS;
+
+ICP_HD int64_t icp_trim_keep(double trim, int64_t within) { return static_cast<int64_t>(trim * static_cast<double>(within)); }
+
+// digit `pass` of a key, the most significant first
+ICP_HD uint32_t icp_select_digit(uint64_t key, int pass) {
+  return static_cast<uint32_t>(key >> (64 - ICP_SELECT_BITS * (pass + 1))) & (ICP_SELECT_RADIX - 1);
+}
+// do the digits of `key` above digit `pass` equal `prefix` (those digits, right-aligned)?
+ICP_HD bool icp_select_candidate(uint64_t key, uint64_t prefix, int pass) {
+  return pass == 0 || (key >> (64 - ICP_SELECT_BITS * pass)) == prefix;
+}
+// Is this the digit of the rank-th smallest candidate? before: the candidates with a smaller digit, count: with this one.
+// Exactly one digit answers true when 1 <= rank <= the sum of the counts; the rank among its candidates is rank - before.
+ICP_HD bool icp_select_hit(int64_t before, int64_t count, int64_t rank) { return before < rank && rank <= before + count; }
+
+// The per-digit step: hist (ICP_SELECT_RADIX counts) and rank in; the digit and the rank among its candidates out.
+// (The pick kernel asks icp_select_hit of every digit at once, `before` coming from an exclusive scan.)
+ICP_HD void icp_select_step(const uint32_t* hist, int64_t rank, int& digit, int64_t& next) {
+  int64_t before = 0;
+  digit = ICP_SELECT_RADIX - 1;
+  next = 0;
+  for (int d = 0; d < ICP_SELECT_RADIX; ++d) {
+    if (icp_select_hit(before, static_cast<int64_t>(hist[d]), rank)) {
+      digit = d;
+      next = rank - before;
+      return;
+    }
+    before += static_cast<int64_t>(hist[d]);
+  }
+}
+
+// The control block of the selection on the device (64 bytes): the weighted sums read tau and any from it, never from
+// the host. Without trimming it holds tau = max_distance^2, any = 1 for the whole call.
+struct alignas(64) IcpSelect {
+  uint64_t prefix;  // the digits found so far, right-aligned
+  int64_t rank;     // the remaining rank, 1-based
+  int64_t within, keep;
+  double tau;       // the threshold once the last pass has run; 0 when nothing is kept
+  int32_t any;      // keep > 0
+  int32_t pad[5];
+};
+static_assert(sizeof(IcpSelect) == 64, "the control block of the selection is 64 bytes");
+
+ICP_HD bool icp_kept(int32_t j, double sqd, double d2, double tau, int32_t any) {
+  return icp_inlier(j, sqd, d2) && any != 0 && sqd <= tau;
 }
 
 }  // namespace clipper_hip

@@ -12,6 +12,8 @@
 //   k_icp_step<M>        one workgroup: thread t adds partials t, t + 256, ... per term, the same tree; thread 0 runs
 //                        icp_iterate (the step, the stop test, the update of T) and writes the record and the
 //                        history row. T stays on the device.
+//   k_icp_accumulate_robust<M>, k_icp_step_robust<M>   the same two over the robust layout (clipper_hip_icp_robust):
+//                        a kept pair's terms weighed by its loss; kept against tau of k_select.hip.h's control block
 //   k_icp_covariances    thread = one point, as k_feat_normals: the neighbourhood's covariance, its smallest
 //                        eigenvector in registers, the six entries of I - (1 - epsilon) nv nv^T
 // No floating-point atomics: every sum has one order.
@@ -89,6 +91,33 @@ __device__ inline void icp_block_fold(const double (&v)[TERMS], double* __restri
 // oi / od: the K = 1 lists (n_src entries); q: the transformed source (n_src x 3); B / Nb: the target and its normals
 // (n_tgt x 3; Nb for point-to-plane alone); Ca / Cb / T: the covariances of the source and the target (n x 6) and the
 // current transform (generalized alone); part: gridDim.x x TERMS
+//
+// the plain terms of the pair (source point i, target point j) of METHOD: what both accumulate kernels load and form
+template <int METHOD>
+__device__ inline void icp_pair_terms(int32_t i, int32_t j, double sqd, const double* __restrict__ q,
+                                      const double* __restrict__ B, const double* __restrict__ Nb,
+                                      const double* __restrict__ Ca, const double* __restrict__ Cb,
+                                      const double* __restrict__ T, const double (&o)[3], double (&t)[icp_terms(METHOD)]) {
+  const double qq[3] = {q[static_cast<int64_t>(i) * 3], q[static_cast<int64_t>(i) * 3 + 1], q[static_cast<int64_t>(i) * 3 + 2]};
+  const double b[3] = {B[static_cast<int64_t>(j) * 3], B[static_cast<int64_t>(j) * 3 + 1], B[static_cast<int64_t>(j) * 3 + 2]};
+  if constexpr (METHOD == ICP_POINT_TO_PLANE) {
+    const double nn[3] = {Nb[static_cast<int64_t>(j) * 3], Nb[static_cast<int64_t>(j) * 3 + 1], Nb[static_cast<int64_t>(j) * 3 + 2]};
+    icp_plane_terms(qq, b, nn, sqd, o, t);
+  } else if constexpr (METHOD == ICP_GENERALIZED) {
+    double ca[6], cb[6], Tl[12];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      ca[a] = Ca[static_cast<int64_t>(i) * 6 + a];
+      cb[a] = Cb[static_cast<int64_t>(j) * 6 + a];
+    }
+#pragma unroll
+    for (int a = 0; a < 12; ++a) Tl[a] = T[a];  // (the rotation: entries 0..2, 4..6, 8..10)
+    icp_generalized_terms(qq, b, ca, cb, Tl, sqd, o, t);
+  } else {
+    icp_point_terms(qq, b, sqd, o, t);
+  }
+}
+
 template <int METHOD>
 __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restrict__ oi, const double* __restrict__ od,
                                                          const double* __restrict__ q, int32_t n_src,
@@ -106,23 +135,44 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restric
     const double sqd = od[i];
     if (icp_inlier(j, sqd, d2) && j < n_tgt) {
       const double o[3] = {o0, o1, o2};
-      const double qq[3] = {q[static_cast<int64_t>(i) * 3], q[static_cast<int64_t>(i) * 3 + 1], q[static_cast<int64_t>(i) * 3 + 2]};
-      const double b[3] = {B[static_cast<int64_t>(j) * 3], B[static_cast<int64_t>(j) * 3 + 1], B[static_cast<int64_t>(j) * 3 + 2]};
-      if constexpr (METHOD == ICP_POINT_TO_PLANE) {
-        const double nn[3] = {Nb[static_cast<int64_t>(j) * 3], Nb[static_cast<int64_t>(j) * 3 + 1], Nb[static_cast<int64_t>(j) * 3 + 2]};
-        icp_plane_terms(qq, b, nn, sqd, o, t);
-      } else if constexpr (METHOD == ICP_GENERALIZED) {
-        double ca[6], cb[6], Tl[12];
+      icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, t);
+    }
+  }
+  icp_block_fold<TERMS>(t, part + static_cast<int64_t>(blockIdx.x) * TERMS);
+}
+
+// The weighted sums of clipper_hip_icp_robust: k_icp_accumulate's thread and fold over the robust layout
+// (icp_robust_terms). A point is kept by icp_kept against tau of the selection's control block on the device (without
+// trimming: max_distance^2); its plain terms are weighed by icp_weight of its squared residual. loss, scale and
+// k2 = scale * scale are run-time arguments.
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_icp_accumulate_robust(const int32_t* __restrict__ oi, const double* __restrict__ od,
+                                                                const double* __restrict__ q, int32_t n_src,
+                                                                const double* __restrict__ B, const double* __restrict__ Nb,
+                                                                const double* __restrict__ Ca, const double* __restrict__ Cb,
+                                                                const double* __restrict__ T, int32_t n_tgt, double d2,
+                                                                double o0, double o1, double o2, int loss, double scale,
+                                                                double k2, const IcpSelect* __restrict__ ctl,
+                                                                double* __restrict__ part) {
+  constexpr int TERMS = icp_robust_terms(METHOD);
+  const int32_t i = static_cast<int32_t>(blockIdx.x) * 256 + static_cast<int32_t>(threadIdx.x);
+  const double tau = ctl->tau;
+  const int32_t any = ctl->any;
+  double t[TERMS];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          ca[a] = Ca[static_cast<int64_t>(i) * 6 + a];
-          cb[a] = Cb[static_cast<int64_t>(j) * 6 + a];
-        }
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Tl[a] = T[a];  // (the rotation: entries 0..2, 4..6, 8..10)
-        icp_generalized_terms(qq, b, ca, cb, Tl, sqd, o, t);
+  for (int a = 0; a < TERMS; ++a) t[a] = 0.0;
+  if (i < n_src) {
+    const int32_t j = oi[i];
+    const double sqd = od[i];
+    if (icp_kept(j, sqd, d2, tau, any) && j < n_tgt) {
+      const double o[3] = {o0, o1, o2};
+      if constexpr (METHOD == ICP_POINT_TO_POINT) {
+        double p[ICP_POINT_TERMS];
+        icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, p);
+        icp_point_terms_weighted(p, icp_weight(loss, sqd, scale, k2), t);
       } else {
-        icp_point_terms(qq, b, sqd, o, t);
+        icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, t);
+        icp_plane_terms_weighted(icp_weight(loss, t[28], scale, k2), t);
       }
     }
   }
@@ -130,12 +180,12 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restric
 }
 
 // part: nb x TERMS; sums: TERMS doubles of device memory (the folded sums, kept for the host's evaluate); T: 16; rec and
-// history (may be null) on the device
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ part, int32_t nb, IcpStop stop, int k, double o0,
-                                                   double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
-                                                   IcpRecord* __restrict__ rec, double* __restrict__ history) {
-  constexpr int TERMS = icp_terms(METHOD);
+// history (may be null) on the device. ROBUST: the robust layout and its step (k_icp_accumulate_robust's partials).
+template <int METHOD, bool ROBUST>
+__device__ inline void icp_step_body(const double* __restrict__ part, int32_t nb, const IcpStop& stop, int k, double o0,
+                                     double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
+                                     IcpRecord* __restrict__ rec, double* __restrict__ history) {
+  constexpr int TERMS = ROBUST ? icp_robust_terms(METHOD) : icp_terms(METHOD);
   double v[TERMS];
 #pragma unroll
   for (int a = 0; a < TERMS; ++a) v[a] = 0.0;
@@ -153,7 +203,7 @@ __global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ par
   IcpRecord r = *rec;
   const double o[3] = {o0, o1, o2};
   double row[3];
-  icp_iterate<METHOD>(stop, k, S, o, Tl, r, row);
+  icp_iterate_over<METHOD, ROBUST>(stop, k, S, o, Tl, r, row);
 #pragma unroll
   for (int a = 0; a < 16; ++a) T[a] = Tl[a];
   *rec = r;
@@ -162,6 +212,21 @@ __global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ par
     history[static_cast<int64_t>(k) * 3 + 1] = row[1];
     history[static_cast<int64_t>(k) * 3 + 2] = row[2];
   }
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ part, int32_t nb, IcpStop stop, int k, double o0,
+                                                   double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
+                                                   IcpRecord* __restrict__ rec, double* __restrict__ history) {
+  icp_step_body<METHOD, false>(part, nb, stop, k, o0, o1, o2, sums, T, rec, history);
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_icp_step_robust(const double* __restrict__ part, int32_t nb, IcpStop stop, int k,
+                                                          double o0, double o1, double o2, double* __restrict__ sums,
+                                                          double* __restrict__ T, IcpRecord* __restrict__ rec,
+                                                          double* __restrict__ history) {
+  icp_step_body<METHOD, true>(part, nb, stop, k, o0, o1, o2, sums, T, rec, history);
 }
 
 // C[i] = the regularised covariance of point i (six doubles: xx, xy, xz, yy, yz, zz) over the first knn entries of its

@@ -52,6 +52,7 @@
 //   k_features.hip.h  surface normals and FPFH descriptors of a point cloud (what the matcher and PointNormalDistance take)
 //   k_sort.hip.h      a stable LSD radix sort of (u64 key, i32 index) pairs, 8-bit digits
 //   k_voxel.hip.h     voxel down-sampling over that sort: one centroid (and normal) per occupied voxel, bit for bit
+//   k_select.hip.h    the exact rank select of trimmed ICP: an MSD radix select over the bits of the squared distances
 #pragma once
 
 #include "k_wave.hip.h"
@@ -75,3 +76,4 @@
 #include "k_ransac.hip.h"
 #include "k_sort.hip.h"
 #include "k_voxel.hip.h"
+#include "k_select.hip.h"

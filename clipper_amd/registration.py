@@ -290,22 +290,45 @@ def compute_fpfh(P: np.ndarray, N: np.ndarray | None = None, knn: int = 32, radi
 
 
 _ICP_METHODS = {"point": 0, "plane": 1}  # clipper_amd._abi.ICP_POINT_TO_POINT / ICP_POINT_TO_PLANE
+_ICP_LOSSES = {"none": 0, "huber": 1, "cauchy": 2, "tukey": 3, "geman_mcclure": 4}  # clipper_amd._abi.ICP_LOSS_*
+
+
+def _icp_robust_args(loss, scale, trim):
+    """None when (loss, scale, trim) are the defaults: the call then takes the plain entry point. Else the keywords of
+    the robust one."""
+    if loss not in _ICP_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_ICP_LOSSES)}")
+    if loss == "none" and scale == 0.0 and trim == 1.0:
+        return None
+    return dict(loss=_ICP_LOSSES[loss], scale=scale, trim=trim)
 
 
 def icp(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None, method: str = "point",
         normals: np.ndarray | None = None, max_distance: float = 0.0, max_iterations: int = 30, rel_fitness: float = 1e-6,
-        rel_rmse: float = 1e-6, device: int = 0, search: str | None = None):
+        rel_rmse: float = 1e-6, device: int = 0, search: str | None = None, loss: str = "none", scale: float = 0.0,
+        trim: float = 1.0):
     """Local refinement of a registration, on the GPU (clipper_hip_icp): ICP from the alignment T_init (4 x 4, None =
     identity) of the cloud src onto tgt (n x 3, rows = points), e.g. the estimate_rigid_transform of a solve's selected
     associations. method "point" (point-to-point) or "plane" (point-to-plane over `normals`, the target's unit normals
     n_tgt x 3, e.g. estimate_normals(tgt)). A moved source point corresponds to its nearest target point and counts as
     an inlier within max_distance. Returns (T 4 x 4, info): info.status (clipper_amd._abi.ICP_*), info.iterations,
     info.count, info.fitness, info.inlier_rmse, info.history ((iterations + 1) x 3: count, fitness, rmse), info.route.
-    search: as in ground_truth_associations; the result does not depend on it."""
+    search: as in ground_truth_associations; the result does not depend on it.
+    Against bad pairs (partial overlap, clutter): loss "huber", "cauchy", "tukey" or "geman_mcclure" weighs every pair by
+    its residual against `scale` (a distance), and trim < 1 keeps, each iteration, that fraction of the points within
+    max_distance with the smallest distances (clipper_hip_icp_robust; info then also carries within, weight_sum and
+    trim_sqd). "tukey" and "geman_mcclure" give pairs far beyond the scale no weight: start them close to the answer."""
     from . import _abi as abi
     if method not in _ICP_METHODS:
         raise ValueError(f"method must be one of {sorted(_ICP_METHODS)}")
+    robust = _icp_robust_args(loss, scale, trim)
     with _knn_search(search):
+        if robust is not None:
+            return abi.icp_robust(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T_init=T_init,
+                                  method=_ICP_METHODS[method],
+                                  N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T,
+                                  max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness,
+                                  rel_rmse=rel_rmse, device=device, **robust)
         return abi.icp(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T_init=T_init,
                        method=_ICP_METHODS[method], N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T,
                        max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
@@ -329,13 +352,16 @@ def estimate_covariances(P: np.ndarray, knn: int = 20, radius: float = 0.0, epsi
 def icp_generalized(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None,
                     source_covariances: np.ndarray | None = None, target_covariances: np.ndarray | None = None,
                     covariance_knn: int = 20, epsilon: float = 1e-3, max_distance: float = 0.0, max_iterations: int = 30,
-                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0, search: str | None = None):
+                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0, search: str | None = None,
+                    loss: str = "none", scale: float = 0.0, trim: float = 1.0):
     """Generalized ICP (the plane-to-plane metric), on the GPU (clipper_hip_icp_generalized): icp's loop, correspondences
     and stop rule, with every inlier pair weighed by the inverse of the sum of its two covariances: what refines
     voxel-down-sampled scans, where no source point has an exact partner. src, tgt: n x 3, rows = points. The
     covariances (n x 6 rows of xx, xy, xz, yy, yz, zz) left None are estimated in the call by
-    estimate_covariances(cloud, covariance_knn, epsilon=epsilon). Returns (T 4 x 4, info) as icp does."""
+    estimate_covariances(cloud, covariance_knn, epsilon=epsilon). Returns (T 4 x 4, info) as icp does. loss, scale,
+    trim: as in icp (clipper_hip_icp_generalized_robust); the residual a loss weighs is d^T M d of the pair."""
     from . import _abi as abi
+    robust = _icp_robust_args(loss, scale, trim)
     src, tgt = np.asarray(src, dtype=np.float64), np.asarray(tgt, dtype=np.float64)
     covs = []
     for name, cloud, cv in (("source_covariances", src, source_covariances), ("target_covariances", tgt, target_covariances)):
@@ -346,6 +372,10 @@ def icp_generalized(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None 
             raise ValueError(f"{name} must be n x 6, one row per point")
         covs.append(cv.T)
     with _knn_search(search):
+        if robust is not None:
+            return abi.icp_generalized_robust(src.T, covs[0], tgt.T, covs[1], T_init=T_init, max_distance=max_distance,
+                                              max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
+                                              device=device, **robust)
         return abi.icp_generalized(src.T, covs[0], tgt.T, covs[1], T_init=T_init, max_distance=max_distance,
                                    max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, device=device)
 

@@ -9,7 +9,8 @@
  *        evaluate_registration), and the consensus estimator beside the solve (ransac_correspondences).
  *        Thin C++ wrappers over the C ABI (include/clipper_hip.h);
  *        match_descriptors, voxel_down_sample, estimate_normals, compute_fpfh, icp, estimate_covariances,
- *        icp_generalized, evaluate_registration and ransac_correspondences work on the device.
+ *        icp_generalized, icp_robust, icp_generalized_robust, evaluate_registration and ransac_correspondences work
+ *        on the device.
  */
 #pragma once
 
@@ -301,6 +302,77 @@ inline IcpResult icp_generalized(const invariants::Data& src, const invariants::
                                   T_init, &prm, r.T, &info, hist.data()))
     throw std::invalid_argument(clipper_hip_last_error());
   detail::fill_icp_result(info, hist, r);
+  return r;
+}
+
+/// The losses of icp_robust and icp_generalized_robust (clipper_icp_robust_t.loss)
+enum class IcpLoss { None = 0, Huber = 1, Cauchy = 2, Tukey = 3, GemanMcClure = 4 };
+
+/// clipper_icp_robust_t: the defaults are the plain call
+struct IcpRobust {
+  IcpLoss loss = IcpLoss::None;
+  double scale = 0.0;  ///< of the residual (a distance); positive and finite with a loss
+  double trim = 1.0;   ///< in (0, 1]: the fraction kept, each iteration, of the points within max_distance
+};
+
+/// IcpResult and clipper_icp_robust_info_t (of the last history row)
+struct IcpRobustResult : IcpResult {
+  int64_t within = 0;       ///< points within max_distance, before trimming
+  double weight_sum = 0.0;  ///< the sum of the weights (point-to-point; 0 otherwise)
+  double trim_sqd = 0.0;    ///< the trimming threshold: max_distance^2 untrimmed, 0 when nothing was kept
+};
+
+/// icp with a robust loss and / or trimming (clipper_hip_icp_robust): every pair weighs by its residual against
+/// robust.scale, and each iteration keeps the fraction robust.trim of the points within max_distance with the smallest
+/// distances. count, fitness, inlier_rmse and the history are over the kept points. Tukey and GemanMcClure give pairs far
+/// beyond the scale no weight: start them close to the answer. A bad setting throws with its value in the message.
+inline IcpRobustResult icp_robust(const invariants::Data& src, const invariants::Data& tgt, const IcpParams& params,
+                                  const IcpRobust& robust, const double* T_init = nullptr,
+                                  const invariants::Data& normals = invariants::Data(), int device = 0) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  const bool has_normals = normals.cols() > 0;
+  if (has_normals && (normals.rows() != 3 || normals.cols() != tgt.cols()))
+    throw std::invalid_argument("normals must be 3 x n, one per target point");
+  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
+                                 params.rel_fitness, params.rel_rmse};
+  const clipper_icp_robust_t rb{static_cast<int32_t>(robust.loss), 0, robust.scale, robust.trim};
+  IcpRobustResult r{};
+  clipper_icp_info_t info{};
+  clipper_icp_robust_info_t ri{};
+  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
+  if (clipper_hip_icp_robust(device, src.data(), src.cols(), tgt.data(), has_normals ? normals.data() : nullptr, tgt.cols(),
+                             T_init, &prm, &rb, r.T, &info, &ri, hist.data()))
+    throw std::invalid_argument(clipper_hip_last_error());
+  detail::fill_icp_result(info, hist, r);
+  r.within = ri.within;
+  r.weight_sum = ri.weight_sum;
+  r.trim_sqd = ri.trim_sqd;
+  return r;
+}
+
+/// icp_generalized with icp_robust's loss and trimming (clipper_hip_icp_generalized_robust); the residual a loss weighs
+/// is d^T M d of the pair.
+inline IcpRobustResult icp_generalized_robust(const invariants::Data& src, const invariants::Data& src_cov,
+                                              const invariants::Data& tgt, const invariants::Data& tgt_cov,
+                                              const IcpParams& params, const IcpRobust& robust,
+                                              const double* T_init = nullptr, int device = 0) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  if (src_cov.rows() != 6 || src_cov.cols() != src.cols() || tgt_cov.rows() != 6 || tgt_cov.cols() != tgt.cols())
+    throw std::invalid_argument("covariances must be 6 x n, one column per point");
+  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
+                                 params.rel_fitness, params.rel_rmse};
+  const clipper_icp_robust_t rb{static_cast<int32_t>(robust.loss), 0, robust.scale, robust.trim};
+  IcpRobustResult r{};
+  clipper_icp_info_t info{};
+  clipper_icp_robust_info_t ri{};
+  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
+  if (clipper_hip_icp_generalized_robust(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(),
+                                         tgt.cols(), T_init, &prm, &rb, r.T, &info, &ri, hist.data()))
+    throw std::invalid_argument(clipper_hip_last_error());
+  detail::fill_icp_result(info, hist, r);
+  r.within = ri.within;
+  r.weight_sum = ri.weight_sum;
+  r.trim_sqd = ri.trim_sqd;
   return r;
 }
 

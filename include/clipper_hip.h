@@ -606,6 +606,47 @@ int clipper_hip_icp_generalized(int device, const double* P_src, const double* C
                                 const double* C_tgt, int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
                                 double* T_out, clipper_icp_info_t* info, double* history);
 
+/* ROBUST LOSSES AND TRIMMED ICP: clipper_hip_icp and clipper_hip_icp_generalized with a defence against bad pairs. Every
+ * argument they share means what it means there. A pair within max_distance has the squared residual e: sqd
+ * (point-to-point), ((q - b) . n)^2 (point-to-plane), d^T M d (generalized), and with k2 = scale * scale the weight
+ *   NONE 1;  HUBER e <= k2 ? 1 : scale / sqrt(e);  CAUCHY 1 / (1 + e / k2);  TUKEY e < k2 ? (1 - e / k2)^2 : 0;
+ *   GEMAN_MCCLURE (k2 / (k2 + e))^2
+ * which multiplies every term the pair adds to the step's sums (point-to-point's centroids divide by the sum of the
+ * weights). count, fitness, rmse, the history and the stop rule stay head counts and plain distances. TRIMMING
+ * (trim < 1): each iteration, with `within` the points within max_distance, keep = (int64_t)(trim * (double)within) and
+ * tau the keep-th smallest sqd among them (an exact rank select on the device), a point is kept iff it is within
+ * max_distance and sqd <= tau: every point equal to tau is kept; keep == 0 keeps nothing and the call ends TOO_FEW.
+ * count, fitness, rmse and the history are then over the kept points, and the loss acts on them alone. trim == 1
+ * selects nothing. With NONE and trim 1 every bit returned equals the plain call's. A round whose weights are all zero
+ * ends the call DEGENERATE with the previous T. TUKEY and GEMAN_MCCLURE redescend: a pair far beyond the scale weighs
+ * (next to) nothing, so from a start far from the answer they may not converge where HUBER, CAUCHY and trimming do
+ * (DESIGN.md section 9). The rules in full: clipper_amd/csrc/icp_rules.hpp. */
+enum { CLIPPER_ICP_LOSS_NONE = 0, CLIPPER_ICP_LOSS_HUBER = 1, CLIPPER_ICP_LOSS_CAUCHY = 2, CLIPPER_ICP_LOSS_TUKEY = 3,
+       CLIPPER_ICP_LOSS_GEMAN_MCCLURE = 4 };
+typedef struct clipper_icp_robust_t {
+  int32_t loss;      /* CLIPPER_ICP_LOSS_* */
+  int32_t reserved;  /* 0 */
+  double  scale;     /* of the residual (a distance), positive and finite; not read with CLIPPER_ICP_LOSS_NONE */
+  double  trim;      /* in (0, 1]; 1 = no trimming */
+} clipper_icp_robust_t;
+typedef struct clipper_icp_robust_info_t { /* of the last history row */
+  int64_t within;      /* points within max_distance, before trimming */
+  double  weight_sum;  /* the sum of the weights of the kept pairs: point-to-point alone (the other two layouts do not
+                          carry it): 0 for point-to-plane and generalized */
+  double  trim_sqd;    /* tau; max_distance^2 with trim == 1, 0 when nothing was kept */
+} clipper_icp_robust_info_t;
+
+/* robust: never NULL; loss outside 0..4, reserved != 0, a scale that is not positive and finite with a loss, and a trim
+ * outside (0, 1] are refused before any device work, the value named. robust_info may be NULL. */
+int clipper_hip_icp_robust(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
+                           int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
+                           const clipper_icp_robust_t* robust, double* T_out, clipper_icp_info_t* info,
+                           clipper_icp_robust_info_t* robust_info, double* history);
+int clipper_hip_icp_generalized_robust(int device, const double* P_src, const double* C_src, int64_t n_src,
+                                       const double* P_tgt, const double* C_tgt, int64_t n_tgt, const double* T_init,
+                                       const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+                                       clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history);
+
 /* The covariances clipper_hip_icp_generalized takes: C_out (6 x n), per point of the cloud P (3 x n) the matrix
  * I - (1 - epsilon) nv nv^T (eigenvalues epsilon, 1, 1) as xx, xy, xz, yy, yz, zz, nv being the unit eigenvector of the
  * smallest eigenvalue of the covariance of the point's neighbourhood: clipper_hip_estimate_normals' neighbourhood and
