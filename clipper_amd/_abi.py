@@ -66,7 +66,17 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_icp_generalized", "clipper_hip_estimate_covariances",
     "clipper_hip_ransac_correspondences", "clipper_hip_ransac_needed",
     "clipper_hip_icp_robust", "clipper_hip_icp_generalized_robust",
+    "clipper_hip_cloud_create", "clipper_hip_cloud_destroy", "clipper_hip_cloud_count", "clipper_hip_cloud_download",
+    "clipper_hip_cloud_info", "clipper_hip_cloud_set_descriptors", "clipper_hip_pairs_create", "clipper_hip_pairs_destroy",
+    "clipper_hip_pairs_count", "clipper_hip_pairs_has_sqd", "clipper_hip_pairs_download", "clipper_hip_cloud_voxel_downsample",
+    "clipper_hip_cloud_estimate_normals", "clipper_hip_cloud_compute_fpfh", "clipper_hip_cloud_fpfh_from_points",
+    "clipper_hip_cloud_estimate_covariances", "clipper_hip_cloud_match", "clipper_hip_stage_inputs_clouds",
+    "clipper_hip_cloud_gather_points", "clipper_hip_cloud_icp", "clipper_hip_cloud_evaluate_registration",
 ]
+
+# CLIPPER_HIP_CLOUD_*: what clipper_hip_cloud_download copies down
+(CLOUD_POINTS, CLOUD_NORMALS, CLOUD_DESCRIPTORS, CLOUD_SPFH, CLOUD_COVARIANCES, CLOUD_NORMAL_COUNTS, CLOUD_FPFH_COUNTS,
+ CLOUD_COVARIANCE_COUNTS, CLOUD_VOXEL_COUNTS, CLOUD_VOXEL_TRACE) = range(10)
 
 
 # int fn(void* user, const void* sendbuf, void* recvbuf, size_t bytes) — clipper_hip_allgather_fn
@@ -305,6 +315,15 @@ class VoxelInfo(C.Structure):
                 ("max_count", C.c_int32), ("reserved", C.c_int32), ("kernels_ms", C.c_double), ("sort_ms", C.c_double)]
 
 
+class CloudInfo(C.Structure):
+    """clipper_hip_cloud_info_t: what a cloud on the device holds: its points, the entries of the voxel trace, its
+    device, which attachments exist (descriptor_dim 0: no descriptors), how often the search grid over it was built
+    (0 or 1: it is kept) and that grid's cells per axis."""
+    _fields_ = [("n", C.c_int64), ("trace_n", C.c_int64), ("device", C.c_int32), ("has_normals", C.c_int32),
+                ("descriptor_dim", C.c_int32), ("has_spfh", C.c_int32), ("has_covariances", C.c_int32),
+                ("has_voxel_counts", C.c_int32), ("grid_builds", C.c_int32), ("grid_dim", C.c_int32 * 3)]
+
+
 class BatchProblem(C.Structure):
     """clipper_batch_problem_t (include/clipper_hip.h): one problem of a batched solve (host buffers)."""
 
@@ -412,6 +431,35 @@ def load_library(path: str = LIB_PATH):
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
     L.clipper_hip_voxel_downsample.argtypes = [C.c_int, dp, dp, C.c_int64, C.c_double, dp, dp, ip, ip,
                                                C.POINTER(C.c_int64), C.POINTER(VoxelInfo)]
+    if hasattr(L, "clipper_hip_cloud_create"):  # (absent from an older build named by CLIPPER_HIP_LIB: the A/B tools)
+        vpp = C.POINTER(vp)
+        L.clipper_hip_cloud_create.argtypes = [C.c_int, dp, dp, i64, vpp]
+        L.clipper_hip_cloud_destroy.argtypes = [vp]
+        L.clipper_hip_cloud_destroy.restype = None
+        L.clipper_hip_cloud_count.argtypes = [vp]
+        L.clipper_hip_cloud_count.restype = i64
+        L.clipper_hip_cloud_download.argtypes = [vp, C.c_int, vp]
+        L.clipper_hip_cloud_info.argtypes = [vp, C.POINTER(CloudInfo)]
+        L.clipper_hip_cloud_set_descriptors.argtypes = [vp, dp, C.c_int]
+        L.clipper_hip_pairs_create.argtypes = [C.c_int, ip, dp, i64, vpp]
+        L.clipper_hip_pairs_destroy.argtypes = [vp]
+        L.clipper_hip_pairs_destroy.restype = None
+        L.clipper_hip_pairs_count.argtypes = [vp]
+        L.clipper_hip_pairs_count.restype = i64
+        L.clipper_hip_pairs_has_sqd.argtypes = [vp]
+        L.clipper_hip_pairs_download.argtypes = [vp, ip, dp]
+        L.clipper_hip_cloud_voxel_downsample.argtypes = [vp, C.c_double, C.c_int, vpp, C.POINTER(VoxelInfo)]
+        L.clipper_hip_cloud_estimate_normals.argtypes = [vp, nbp, dp]
+        L.clipper_hip_cloud_compute_fpfh.argtypes = [vp, nbp]
+        L.clipper_hip_cloud_fpfh_from_points.argtypes = [vp, nbp, dp, nbp]
+        L.clipper_hip_cloud_estimate_covariances.argtypes = [vp, nbp, C.c_double]
+        L.clipper_hip_cloud_match.argtypes = [vp, vp, C.POINTER(MatchParams), vpp, ip, dp]
+        L.clipper_hip_stage_inputs_clouds.argtypes = [vp, vp, vp, vp, C.c_int]
+        L.clipper_hip_cloud_gather_points.argtypes = [vp, ip, i64, dp]
+        L.clipper_hip_cloud_icp.argtypes = [vp, vp, dp, C.POINTER(IcpParams), C.POINTER(IcpRobust), dp, C.POINTER(IcpInfo),
+                                            C.POINTER(IcpRobustInfo), dp]
+        L.clipper_hip_cloud_evaluate_registration.argtypes = [vp, vp, dp, C.c_double, C.POINTER(C.c_double),
+                                                              C.POINTER(C.c_double), C.POINTER(C.c_int64), ip]
     L.clipper_hip_set_profiling.argtypes = [vp, C.c_int]
     L.clipper_hip_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.clipper_hip_bench_matvec.argtypes = [vp, C.c_int, dp]
@@ -620,6 +668,11 @@ class HipClipper:
         self._check(self.L.clipper_hip_stage_inputs(
             self.h, _dp(D1), D1.shape[0], D1.shape[1], _dp(D2), D2.shape[1],
             _ip(Ac) if Ac is not None else None, m))
+
+    def stage_inputs_clouds(self, c0, c1, pairs, with_normals: bool = False):
+        """stage_inputs from two DeviceClouds and a DevicePairs (clipper_hip_stage_inputs_clouds): D1 / D2 are the
+        clouds' points, with_normals each point followed by its normal (d = 6, for affinity_pointnormal_staged)"""
+        self._check(self.L.clipper_hip_stage_inputs_clouds(self.h, c0.h, c1.h, pairs.h, int(bool(with_normals))))
 
     def affinity_euclidean_staged(self, sigma=0.01, epsilon=0.06, mindist=0.0):
         self._check(self.L.clipper_hip_affinity_euclidean_staged(
@@ -1425,6 +1478,230 @@ def voxel_down_sample(P, voxel_size: float, N=None, device: int = 0, return_coun
     if return_info:
         out.append(info)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+class _Handle:
+    """an owning handle of the C ABI: close() (idempotent), a context manager, and a __del__ that tolerates the
+    interpreter shutting down; using it after close() raises ClipperError instead of handing NULL to the library"""
+    _destroy = ""
+    _what = "handle"
+
+    def __init__(self, h):
+        self.L = load_library()
+        self._h = h
+
+    @property
+    def h(self):
+        if not getattr(self, "_h", None):
+            raise ClipperError(f"this {self._what} is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            getattr(self.L, self._destroy)(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (module globals may be gone at interpreter shutdown)
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+        return rc
+
+
+class DevicePairs(_Handle):
+    """clipper_hip_pairs_t: an association list on the device (m x 2 int32, with one squared distance per row where it
+    came from DeviceCloud.match). DevicePairs(A[, sqd]) uploads one; len() is m; download() brings it back."""
+    _destroy, _what = "clipper_hip_pairs_destroy", "DevicePairs"
+
+    def __init__(self, A=None, sqd=None, device: int = 0, _h=False):
+        super().__init__(_h or None)
+        if _h is not False:  # (a handle a call of the library made: adopted)
+            return
+        Ac, m = _assoc_colmajor(() if A is None else A)
+        sq = None if sqd is None else np.ascontiguousarray(sqd, dtype=np.float64).reshape(-1)
+        if sq is not None and sq.size != m:
+            raise ValueError("sqd must hold one squared distance per row of A")
+        h = C.c_void_p()
+        self._check(self.L.clipper_hip_pairs_create(device, _ip(Ac) if Ac is not None else None,
+                                                    None if sq is None else _dp(sq), m, C.byref(h)))
+        self._h = h
+
+    def __len__(self):
+        return int(self._check(self.L.clipper_hip_pairs_count(self.h)))
+
+    @property
+    def has_sqd(self) -> bool:
+        """whether the pairs carry one squared distance per row (clipper_hip_pairs_has_sqd)"""
+        return bool(self._check(self.L.clipper_hip_pairs_has_sqd(self.h)))
+
+    def download(self, with_sqd: bool | None = None):
+        """A (m x 2 int32), or (A, sqd) with with_sqd (default: whenever the pairs carry distances)"""
+        m = len(self)
+        buf = np.zeros(2 * max(m, 1), dtype=np.int32)
+        sqd = np.zeros(max(m, 1), dtype=np.float64)
+        if with_sqd is None:
+            with_sqd = self.has_sqd
+        self._check(self.L.clipper_hip_pairs_download(self.h, _ip(buf), _dp(sqd) if with_sqd else None))
+        A = np.stack([buf[:m], buf[m:2 * m]], axis=1).astype(np.int32)
+        return (A, sqd[:m].copy()) if with_sqd else A
+
+
+class DeviceCloud(_Handle):
+    """clipper_hip_cloud_t: a point cloud that lives on the device, carrying what the stages compute about it. P: 3 x n
+    (columns = points as `clipper::Data`), normals: 3 x n unit normals or None. The methods mirror the stand-alone
+    calls of this module and give their bits; nothing crosses the bus but what is asked for. Not safe for concurrent
+    mutation. Usable as a context manager; close() frees the device memory (twice is harmless)."""
+    _destroy, _what = "clipper_hip_cloud_destroy", "DeviceCloud"
+
+    def __init__(self, P=None, normals=None, device: int = 0, _h=False):
+        super().__init__(_h or None)
+        if _h is not False:  # (a handle a call of the library made: adopted)
+            return
+        Pc = _cloud(np.zeros((3, 0)) if P is None else P)
+        n = Pc.shape[1]
+        Nc = None if normals is None else _cloud(normals, "normals")
+        if Nc is not None and Nc.shape[1] != n:
+            raise ValueError("P and normals must hold the same number of points")
+        h = C.c_void_p()
+        self._check(self.L.clipper_hip_cloud_create(device, _dp(Pc) if n else None, None if Nc is None else _dp(Nc), n,
+                                                    C.byref(h)))
+        self._h = h
+
+    def __len__(self):
+        return int(self._check(self.L.clipper_hip_cloud_count(self.h)))
+
+    def info(self) -> CloudInfo:
+        out = CloudInfo()
+        self._check(self.L.clipper_hip_cloud_info(self.h, C.byref(out)))
+        return out
+
+    def _download(self, what, rows, dtype=np.float64, count=None):
+        n = len(self) if count is None else count
+        shape = (rows, max(n, 1)) if rows else (max(n, 1),)
+        out = np.zeros(shape, dtype=dtype, order="F")
+        self._check(self.L.clipper_hip_cloud_download(self.h, what, out.ctypes.data_as(C.c_void_p)))
+        return np.asfortranarray(out[:, :n]) if rows else out[:n].copy()
+
+    def points(self):
+        return self._download(CLOUD_POINTS, 3)
+
+    def normals(self):
+        return self._download(CLOUD_NORMALS, 3)
+
+    def descriptors(self):
+        return self._download(CLOUD_DESCRIPTORS, max(int(self.info().descriptor_dim), 1))
+
+    def spfh(self):
+        return self._download(CLOUD_SPFH, FPFH_DIM)
+
+    def covariances(self):
+        return self._download(CLOUD_COVARIANCES, 6)
+
+    def counts(self, what: int):
+        """the int32 attachment `what`: CLOUD_NORMAL_COUNTS, _FPFH_COUNTS, _COVARIANCE_COUNTS, _VOXEL_COUNTS, _VOXEL_TRACE"""
+        return self._download(what, 0, np.int32, int(self.info().trace_n) if what == CLOUD_VOXEL_TRACE else None)
+
+    def set_descriptors(self, F):
+        Fc = _f64_colmajor(F)
+        if Fc.ndim != 2 or Fc.shape[1] != len(self):
+            raise ValueError("F must be d x n")
+        self._check(self.L.clipper_hip_cloud_set_descriptors(self.h, _dp(Fc), Fc.shape[0]))
+        return self
+
+    def voxel_down_sample(self, voxel_size: float, return_trace: bool = False, return_info: bool = False):
+        """a NEW DeviceCloud of the centroids (and the normalised normal sums); counts(CLOUD_VOXEL_COUNTS) and, with
+        return_trace, counts(CLOUD_VOXEL_TRACE) are attached to it"""
+        h, info = C.c_void_p(), VoxelInfo()
+        self._check(self.L.clipper_hip_cloud_voxel_downsample(self.h, float(voxel_size), int(bool(return_trace)), C.byref(h),
+                                                              C.byref(info)))
+        out = DeviceCloud(_h=h)
+        return (out, info) if return_info else out
+
+    def estimate_normals(self, knn: int = 16, radius: float = 0.0, viewpoint=None):
+        v, vptr = _viewpoint(viewpoint)
+        nb = Neighborhood(knn, radius)
+        self._check(self.L.clipper_hip_cloud_estimate_normals(self.h, C.byref(nb), vptr))
+        return self
+
+    def compute_fpfh(self, knn: int = 32, radius: float = 0.0):
+        nb = Neighborhood(knn, radius)
+        self._check(self.L.clipper_hip_cloud_compute_fpfh(self.h, C.byref(nb)))
+        return self
+
+    def fpfh_from_points(self, normal_knn: int = 16, normal_radius: float = 0.0, viewpoint=None, knn: int = 32,
+                         radius: float = 0.0):
+        v, vptr = _viewpoint(viewpoint)
+        nnb, fnb = Neighborhood(normal_knn, normal_radius), Neighborhood(knn, radius)
+        self._check(self.L.clipper_hip_cloud_fpfh_from_points(self.h, C.byref(nnb), vptr, C.byref(fnb)))
+        return self
+
+    def estimate_covariances(self, knn: int = 20, radius: float = 0.0, epsilon: float = 1e-3):
+        nb = Neighborhood(knn, radius)
+        self._check(self.L.clipper_hip_cloud_estimate_covariances(self.h, C.byref(nb), float(epsilon)))
+        return self
+
+    def match(self, other: "DeviceCloud", knn: int = 1, mutual: bool = True, ratio: float = 0.0, max_sqdist: float = 0.0,
+              return_lists: bool = False):
+        """match_descriptors of this cloud's descriptors against `other`'s, the filters run on the device: DevicePairs,
+        with return_lists also the forward lists (idx n0 x knn int32, sqd n0 x knn)"""
+        prm = MatchParams(int(knn), int(bool(mutual)), float(ratio), float(max_sqdist))
+        n0 = len(self)
+        idx = np.zeros((n0, max(int(knn), 0)), dtype=np.int32) if return_lists else None
+        lsq = np.zeros((n0, max(int(knn), 0)), dtype=np.float64) if return_lists else None
+        h = C.c_void_p()
+        self._check(self.L.clipper_hip_cloud_match(self.h, other.h, C.byref(prm), C.byref(h),
+                                                   _ip(idx) if return_lists else None, _dp(lsq) if return_lists else None))
+        pairs = DevicePairs(_h=h)
+        return (pairs, idx, lsq) if return_lists else pairs
+
+    def gather_points(self, idx):
+        """the points idx names, 3 x k, in the order of the list"""
+        ic = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        out = np.zeros((3, max(ic.size, 1)), dtype=np.float64, order="F")
+        self._check(self.L.clipper_hip_cloud_gather_points(self.h, _ip(ic), ic.size, _dp(out)))
+        return np.asfortranarray(out[:, :ic.size])
+
+    def icp(self, target: "DeviceCloud", T_init=None, method: int = ICP_POINT_TO_POINT, max_distance: float = 0.0,
+            max_iterations: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, loss: int | None = None,
+            scale: float = 0.0, trim: float = 1.0):
+        """icp / icp_generalized (and, with a loss given — ICP_LOSS_NONE for trimming alone — their robust forms) of this
+        cloud onto `target`, whose search grid is built at the first call and kept. Returns (T 4 x 4, info) as they do."""
+        t0, t0p = _transform_arg(T_init, "T_init")
+        prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
+        robust = loss is not None
+        rb, rinfo = IcpRobust(loss if robust else ICP_LOSS_NONE, scale, trim), IcpRobustInfo()
+        T = np.zeros(16, dtype=np.float64)
+        info = IcpInfo()
+        hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+        self._check(self.L.clipper_hip_cloud_icp(self.h, target.h, t0p, C.byref(prm), C.byref(rb) if robust else None, _dp(T),
+                                                 C.byref(info), C.byref(rinfo) if robust else None, _dp(hist)))
+        if robust:
+            return _robust_result(T, info, rinfo, hist)
+        info.history = hist[:info.iterations + 1].copy()
+        return T.reshape(4, 4).T.copy(), info
+
+    def evaluate_registration(self, target: "DeviceCloud", T=None, max_distance: float = 0.0,
+                              return_correspondences: bool = False):
+        t, tp = _transform_arg(T, "T")
+        fit, rmse, cnt = C.c_double(), C.c_double(), C.c_int64()
+        ns = len(self)
+        corr = np.zeros(max(ns, 1), dtype=np.int32) if return_correspondences else None
+        self._check(self.L.clipper_hip_cloud_evaluate_registration(self.h, target.h, tp, float(max_distance), C.byref(fit),
+                                                                   C.byref(rmse), C.byref(cnt),
+                                                                   _ip(corr) if return_correspondences else None))
+        out = (fit.value, rmse.value, cnt.value)
+        return out + (corr[:ns],) if return_correspondences else out
 
 
 class HipBatch:

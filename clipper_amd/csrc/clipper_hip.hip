@@ -30,6 +30,7 @@
 #include <type_traits>
 #include <utility>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <exception>
@@ -73,6 +74,7 @@ using clipper_hip_buf::PinnedBuf;
 #include "host_icp.hpp"
 #include "host_ransac.hpp"
 #include "host_voxel.hpp"
+#include "host_cloud.hpp"
 
 extern "C" {
 
@@ -486,6 +488,103 @@ int clipper_hip_voxel_downsample(int device, const double* P, const double* N, i
                                  double* P_out, double* N_out, int32_t* count_out, int32_t* trace_out, int64_t* n_out,
                                  clipper_voxel_info_t* info) try {
   return voxel_downsample(device, P, N, n, voxel_size, P_out, N_out, count_out, trace_out, n_out, info);
+} CLIPPER_HIP_GUARD_INT
+
+// ---- clouds and association lists that live on the device (host_cloud.hpp) ------------------------
+
+int clipper_hip_cloud_create(int device, const double* P, const double* N, int64_t n, clipper_hip_cloud_t** out) try {
+  return cloud_create(device, P, N, n, out);
+} CLIPPER_HIP_GUARD_INT
+
+void clipper_hip_cloud_destroy(clipper_hip_cloud_t* cloud) try {
+  delete cloud;
+} CLIPPER_HIP_GUARD_VOID
+
+int64_t clipper_hip_cloud_count(const clipper_hip_cloud_t* cloud) try {
+  if (!cloud) return fail(CLIPPER_HIP_E_INVALID, "cloud_count: null handle");
+  return cloud->n;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_download(const clipper_hip_cloud_t* cloud, int what, void* out) try {
+  return cloud_download(cloud, what, out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_info(const clipper_hip_cloud_t* cloud, clipper_hip_cloud_info_t* out) try {
+  return cloud_info(cloud, out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_set_descriptors(clipper_hip_cloud_t* cloud, const double* F, int d) try {
+  return cloud_set_descriptors(cloud, F, d);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_pairs_create(int device, const int32_t* A, const double* sqd, int64_t m, clipper_hip_pairs_t** out) try {
+  return pairs_create(device, A, sqd, m, out);
+} CLIPPER_HIP_GUARD_INT
+
+void clipper_hip_pairs_destroy(clipper_hip_pairs_t* pairs) try {
+  delete pairs;
+} CLIPPER_HIP_GUARD_VOID
+
+int64_t clipper_hip_pairs_count(const clipper_hip_pairs_t* pairs) try {
+  if (!pairs) return fail(CLIPPER_HIP_E_INVALID, "pairs_count: null handle");
+  return pairs->m;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_pairs_has_sqd(const clipper_hip_pairs_t* pairs) try {
+  if (!pairs) return fail(CLIPPER_HIP_E_INVALID, "pairs_has_sqd: null handle");
+  return pairs->has_sqd ? 1 : 0;
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_pairs_download(const clipper_hip_pairs_t* pairs, int32_t* A_out, double* sqd_out) try {
+  return pairs_download(pairs, A_out, sqd_out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_voxel_downsample(clipper_hip_cloud_t* in, double voxel_size, int want_trace,
+                                       clipper_hip_cloud_t** out, clipper_voxel_info_t* info) try {
+  return cloud_voxel_downsample(in, voxel_size, want_trace, out, info);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_estimate_normals(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb, const double* viewpoint) try {
+  return cloud_features(cloud, "cloud_estimate_normals", nb, viewpoint, nullptr, true, false);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_compute_fpfh(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb) try {
+  return cloud_features(cloud, "cloud_compute_fpfh", nullptr, nullptr, nb, false, true);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_fpfh_from_points(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* normal_nb,
+                                       const double* viewpoint, const clipper_neighborhood_t* feature_nb) try {
+  return cloud_features(cloud, "cloud_fpfh_from_points", normal_nb, viewpoint, feature_nb, true, true);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_estimate_covariances(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb, double epsilon) try {
+  return cloud_estimate_covariances(cloud, nb, epsilon);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_match(const clipper_hip_cloud_t* c0, const clipper_hip_cloud_t* c1, const clipper_match_params_t* params,
+                            clipper_hip_pairs_t** out, int32_t* nn_idx_out, double* nn_sqd_out) try {
+  return cloud_match(c0, c1, params, out, nn_idx_out, nn_sqd_out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_stage_inputs_clouds(clipper_hip_t* h, const clipper_hip_cloud_t* c0, const clipper_hip_cloud_t* c1,
+                                    const clipper_hip_pairs_t* pairs, int with_normals) try {
+  return stage_inputs_clouds(h, c0, c1, pairs, with_normals);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_gather_points(const clipper_hip_cloud_t* cloud, const int32_t* idx, int64_t k, double* out) try {
+  return cloud_gather_points(cloud, idx, k, out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_icp(const clipper_hip_cloud_t* src, clipper_hip_cloud_t* tgt, const double* T_init,
+                          const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+                          clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) try {
+  return cloud_icp(src, tgt, T_init, params, robust, T_out, info, robust_info, history);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_cloud_evaluate_registration(const clipper_hip_cloud_t* src, clipper_hip_cloud_t* tgt, const double* T,
+                                            double max_distance, double* fitness, double* inlier_rmse, int64_t* count,
+                                            int32_t* corr_out) try {
+  return cloud_evaluate_registration(src, tgt, T, max_distance, fitness, inlier_rmse, count, corr_out);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_set_window(clipper_hip_t* h, int window) try {

@@ -5,6 +5,7 @@
 // is a call into libclipper_hip.so. Nothing here is a CPU implementation of that path:
 // if the GPU library reports an error, the facade throws.
 #include "clipper/clipper.h"
+#include "clipper/device_cloud.h"
 #include "clipper/invariants/device.h"
 #include "clipper/sdp.h"
 
@@ -288,6 +289,46 @@ void CLIPPER::scorePairwiseConsistency(const invariants::Data& D1, const invaria
           "scorePairwiseConsistency[DeviceInvariant]");
   } else {
     scoreCustomInvariantOnHost(D1, D2);
+  }
+  clipper_hip_timings_t tm;
+  if (clipper_hip_get_timings(h_, &tm) == 0) stats_.affinity_kernel_ms = tm.affinity_kernel_ms;
+}
+
+// from clouds that live on the device: staged there, filled by the same kernels
+void CLIPPER::scorePairwiseConsistency(const registration::DeviceCloud& c1, const registration::DeviceCloud& c2,
+                                       const registration::DevicePairs& pairs) {
+  auto euclid = std::dynamic_pointer_cast<invariants::EuclideanDistance>(invariant_);
+  auto pointn = std::dynamic_pointer_cast<invariants::PointNormalDistance>(invariant_);
+  const bool exact_euclid = euclid && typeid(*invariant_) == typeid(invariants::EuclideanDistance);
+  const bool exact_pointn = pointn && typeid(*invariant_) == typeid(invariants::PointNormalDistance);
+  auto device = std::dynamic_pointer_cast<invariants::DeviceInvariant>(invariant_);
+  const bool exact_device = device && typeid(*invariant_) == typeid(invariants::DeviceInvariant);
+  if (!exact_euclid && !exact_pointn && !exact_device)
+    throw std::invalid_argument("clipper: an invariant evaluated on the host needs host data (download the clouds)");
+  check(clipper_hip_stage_inputs_clouds(handle(), c1.handle(), c2.handle(), pairs.handle(), exact_pointn ? 1 : 0),
+        "scorePairwiseConsistency[clouds]");
+  if (exact_euclid) {
+    const auto& p = euclid->params();
+    check(clipper_hip_affinity_euclidean_staged(h_, p.sigma, p.epsilon, p.mindist, params_.affinityeps),
+          "scorePairwiseConsistency[EuclideanDistance, clouds]");
+  } else if (exact_pointn) {
+    const auto& p = pointn->params();
+    check(clipper_hip_affinity_pointnormal_staged(h_, p.sigp, p.epsp, p.sign, p.epsn, params_.affinityeps),
+          "scorePairwiseConsistency[PointNormalDistance, clouds]");
+  } else {
+    clipper_hip_invariant* inv = device->handle(3);
+    const auto& p = device->params();
+    check(clipper_hip_affinity_custom_staged(h_, inv, p.empty() ? nullptr : p.data(), static_cast<int>(p.size()),
+                                             params_.affinityeps),
+          "scorePairwiseConsistency[DeviceInvariant, clouds]");
+  }
+  const int64_t m = clipper_hip_num_associations(h_);
+  Association buf(m > 0 ? m : 1, 2);
+  check(clipper_hip_get_associations(h_, buf.data()), "get_associations");
+  A_ = Association(m, 2);
+  for (int64_t r = 0; r < m; ++r) {
+    A_(r, 0) = buf.data()[r];
+    A_(r, 1) = buf.data()[m + r];
   }
   clipper_hip_timings_t tm;
   if (clipper_hip_get_timings(h_, &tm) == 0) stats_.affinity_kernel_ms = tm.affinity_kernel_ms;

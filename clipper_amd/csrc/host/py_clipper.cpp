@@ -15,6 +15,7 @@
 
 #include "clipper/batch.h"
 #include "clipper/clipper.h"
+#include "clipper/device_cloud.h"
 #include "clipper/invariants/device.h"
 #include "clipper/registration.h"
 #include "clipper/sdp.h"
@@ -465,6 +466,146 @@ PYBIND11_MODULE(clipperpy, m) {
               "the grid from a measured cloud size on. Every route returns the same lists, bit for bit.");
   m_utils.def("knn_search", &clipper::registration::knnSearch);
 
+  // clouds and association lists that live on the device (include/clipper/device_cloud.h): the front end without
+  // crossing the bus between its stages. close() frees the device memory (twice is harmless); a closed handle raises.
+  {
+    namespace reg = clipper::registration;
+    py::class_<reg::DevicePairs>(m_utils, "DevicePairs")
+        .def(py::init([](const clipper::Association& A, const std::vector<double>& sqd, int device) {
+               return new reg::DevicePairs(A, sqd, device);
+             }),
+             "A"_a, "sqd"_a = std::vector<double>{}, "device"_a = 0)
+        .def("__len__", &reg::DevicePairs::size)
+        .def_property_readonly("has_sqd", &reg::DevicePairs::hasSqd)
+        .def("download", [](const reg::DevicePairs& p) { return p.download(); })
+        .def("download_with_sqd",
+             [](const reg::DevicePairs& p) {
+               std::vector<double> sqd;
+               clipper::Association A = p.download(&sqd);
+               return py::make_tuple(A, py::array_t<double>(static_cast<py::ssize_t>(sqd.size()), sqd.data()));
+             })
+        .def("close", &reg::DevicePairs::close)
+        .def("__enter__", [](py::object self) { return self; })
+        .def("__exit__", [](reg::DevicePairs& p, const py::args&) { p.close(); });
+    py::class_<reg::DeviceCloud>(m_utils, "DeviceCloud")
+        .def(py::init([](const clipper::MatrixXd& P, const clipper::MatrixXd& normals, int device) {
+               return new reg::DeviceCloud(P, normals, device);
+             }),
+             "P"_a, "normals"_a = clipper::MatrixXd(3, 0), "device"_a = 0)
+        .def("__len__", &reg::DeviceCloud::size)
+        .def("points", &reg::DeviceCloud::points)
+        .def("normals", &reg::DeviceCloud::normals)
+        .def("descriptors", &reg::DeviceCloud::descriptors)
+        .def("spfh", &reg::DeviceCloud::spfh)
+        .def("covariances", &reg::DeviceCloud::covariances)
+        .def("grid_builds", [](const reg::DeviceCloud& c) { return c.info().grid_builds; })
+        .def("info",
+             [](const reg::DeviceCloud& c) {
+               const clipper_hip_cloud_info_t i = c.info();
+               py::dict d;
+               d["n"] = i.n;
+               d["trace_n"] = i.trace_n;
+               d["device"] = i.device;
+               d["has_normals"] = i.has_normals != 0;
+               d["descriptor_dim"] = i.descriptor_dim;
+               d["has_spfh"] = i.has_spfh != 0;
+               d["has_covariances"] = i.has_covariances != 0;
+               d["has_voxel_counts"] = i.has_voxel_counts != 0;
+               d["grid_builds"] = i.grid_builds;
+               d["grid_dim"] = py::make_tuple(i.grid_dim[0], i.grid_dim[1], i.grid_dim[2]);
+               return d;
+             })
+        .def("counts",
+             [](const reg::DeviceCloud& c, const std::string& what) {
+               static const char* const names[] = {"normals", "fpfh", "covariances", "voxel", "voxel_trace"};
+               static const int whats[] = {CLIPPER_HIP_CLOUD_NORMAL_COUNTS, CLIPPER_HIP_CLOUD_FPFH_COUNTS,
+                                           CLIPPER_HIP_CLOUD_COVARIANCE_COUNTS, CLIPPER_HIP_CLOUD_VOXEL_COUNTS,
+                                           CLIPPER_HIP_CLOUD_VOXEL_TRACE};
+               for (int k = 0; k < 5; ++k)
+                 if (what == names[k]) {
+                   const std::vector<int32_t> v = c.counts(whats[k]);
+                   return py::array_t<int32_t>(static_cast<py::ssize_t>(v.size()), v.data());
+                 }
+               throw std::invalid_argument("what must be \"normals\", \"fpfh\", \"covariances\", \"voxel\" or \"voxel_trace\"");
+             },
+             "what"_a)
+        .def("fpfh_from_points",
+             [](reg::DeviceCloud& c, int normal_knn, double normal_radius, const std::vector<double>& viewpoint, int knn,
+                double radius) {
+               if (!viewpoint.empty() && viewpoint.size() != 3) throw std::invalid_argument("viewpoint must have 3 coordinates");
+               c.computeFpfh(reg::Neighborhood{normal_knn, normal_radius}, viewpoint.empty() ? nullptr : viewpoint.data(),
+                             reg::Neighborhood{knn, radius});
+             },
+             "normal_knn"_a = 16, "normal_radius"_a = 0.0, "viewpoint"_a = std::vector<double>{}, "knn"_a = 32, "radius"_a = 0.0)
+        .def("evaluate_registration",
+             [](const reg::DeviceCloud& c, reg::DeviceCloud& target, const py::object& T, double max_distance) {
+               clipper::MatrixXd T0;
+               if (!T.is_none()) {
+                 T0 = T.cast<clipper::MatrixXd>();
+                 if (T0.rows() != 4 || T0.cols() != 4) throw std::invalid_argument("T must be 4 x 4");
+               }
+               int64_t count = 0;
+               const std::pair<double, double> fr = c.evaluateRegistration(target, T.is_none() ? nullptr : T0.data(), max_distance, &count);
+               return py::make_tuple(fr.first, fr.second, count);
+             },
+             "target"_a, "T"_a = py::none(), "max_distance"_a = 0.0)
+        .def("set_descriptors", [](reg::DeviceCloud& c, const clipper::MatrixXd& F) { c.setDescriptors(F); }, "F"_a)
+        .def("voxel_down_sample",
+             [](reg::DeviceCloud& c, double voxel_size, bool return_trace) {
+               return new reg::DeviceCloud(c.voxelDownSample(voxel_size, return_trace));
+             },
+             "voxel_size"_a, "return_trace"_a = false, py::return_value_policy::take_ownership)
+        .def("estimate_normals",
+             [](reg::DeviceCloud& c, int knn, double radius, const std::vector<double>& viewpoint) {
+               if (!viewpoint.empty() && viewpoint.size() != 3) throw std::invalid_argument("viewpoint must have 3 coordinates");
+               c.estimateNormals(reg::Neighborhood{knn, radius}, viewpoint.empty() ? nullptr : viewpoint.data());
+             },
+             "knn"_a = 16, "radius"_a = 0.0, "viewpoint"_a = std::vector<double>{})
+        .def("compute_fpfh", [](reg::DeviceCloud& c, int knn, double radius) { c.computeFpfh(reg::Neighborhood{knn, radius}); },
+             "knn"_a = 32, "radius"_a = 0.0)
+        .def("estimate_covariances",
+             [](reg::DeviceCloud& c, int knn, double radius, double epsilon) {
+               c.estimateCovariances(reg::Neighborhood{knn, radius}, epsilon);
+             },
+             "knn"_a = 20, "radius"_a = 0.0, "epsilon"_a = 1e-3)
+        .def("match",
+             [](const reg::DeviceCloud& c, const reg::DeviceCloud& other, int knn, bool mutual, double ratio, double max_sqdist) {
+               reg::MatchParams prm;
+               prm.knn = knn;
+               prm.mutual = mutual;
+               prm.ratio = ratio;
+               prm.max_sqdist = max_sqdist;
+               return new reg::DevicePairs(c.match(other, prm));
+             },
+             "other"_a, "knn"_a = 1, "mutual"_a = true, "ratio"_a = 0.0, "max_sqdist"_a = 0.0,
+             py::return_value_policy::take_ownership)
+        .def("gather_points", &reg::DeviceCloud::gatherPoints, "idx"_a)
+        .def("icp",
+             [](const reg::DeviceCloud& c, reg::DeviceCloud& target, const std::string& method, double max_distance,
+                int max_iterations, const py::object& T_init, const py::object& loss, double scale, double trim) {
+               if (method != "point" && method != "plane" && method != "generalized")
+                 throw std::invalid_argument("method must be \"point\", \"plane\" or \"generalized\"");
+               reg::IcpParams prm;
+               prm.method = method == "plane" ? reg::IcpMethod::PointToPlane
+                                              : (method == "generalized" ? reg::IcpMethod::Generalized : reg::IcpMethod::PointToPoint);
+               prm.max_distance = max_distance;
+               prm.max_iterations = max_iterations;
+               clipper::MatrixXd T0;
+               if (!T_init.is_none()) {
+                 T0 = T_init.cast<clipper::MatrixXd>();
+                 if (T0.rows() != 4 || T0.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
+               }
+               const double* t0 = T_init.is_none() ? nullptr : T0.data();
+               if (loss.is_none()) return icp_tuple(c.icp(target, prm, t0));
+               return icp_robust_tuple(c.icp(target, prm, icp_robust_of(loss.cast<std::string>(), scale, trim), t0));
+             },
+             "target"_a, "method"_a = "point", "max_distance"_a = 0.0, "max_iterations"_a = 30, "T_init"_a = py::none(),
+             "loss"_a = py::none(), "scale"_a = 0.0, "trim"_a = 1.0)
+        .def("close", &reg::DeviceCloud::close)
+        .def("__enter__", [](py::object self) { return self; })
+        .def("__exit__", [](reg::DeviceCloud& c, const py::args&) { c.close(); });
+  }
+
   // The reference fills `clipperpy.dsd` with pybind_utils (py_clipper.cpp:127-128; pybind_dsd is
   // never called), so that is what existing scripts see; the exact DSD solver is out of scope.
   py::module m_dsd = m.def_submodule("dsd");
@@ -591,8 +732,17 @@ PYBIND11_MODULE(clipperpy, m) {
            // for as long as the CLIPPER object holds its C++ half
            py::keep_alive<1, 2>())
       .def("__repr__", [](const clipper::CLIPPER&) { return "<CLIPPER>"; })
-      .def("score_pairwise_consistency", &clipper::CLIPPER::scorePairwiseConsistency,
+      .def("score_pairwise_consistency",
+           static_cast<void (clipper::CLIPPER::*)(const clipper::invariants::Data&, const clipper::invariants::Data&,
+                                                  const clipper::Association&)>(&clipper::CLIPPER::scorePairwiseConsistency),
            "D1"_a.noconvert(), "D2"_a.noconvert(), "A"_a.noconvert())
+      .def("score_pairwise_consistency",
+           static_cast<void (clipper::CLIPPER::*)(const clipper::registration::DeviceCloud&,
+                                                  const clipper::registration::DeviceCloud&,
+                                                  const clipper::registration::DevicePairs&)>(
+               &clipper::CLIPPER::scorePairwiseConsistency),
+           "c1"_a, "c2"_a, "pairs"_a,
+           "The same from two utils.DeviceCloud and a utils.DevicePairs: staged and scored on the GPU from device data.")
       .def("solve", &clipper::CLIPPER::solve, "u0"_a.noconvert() = clipper::VectorXd())
       .def("solve_as_maximum_clique",
            [](clipper::CLIPPER& c, const clipper::maxclique::Params& params, const py::object& seed) {

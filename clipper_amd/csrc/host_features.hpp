@@ -19,37 +19,26 @@ void feat_spfh_run(const double* dP, const double* dN, int64_t n, const int32_t*
                      n, oi, od, stride, knn, use_r, r2, dS, dcnt);
 }
 
-// nnb: the neighbourhood of the normals stage (null: the normals are N_in); fnb: the feature stage's (null: none).
-// Every argument has been checked. Outputs may be null where the entry points allow it.
-int features_run(int device, const double* P, const double* N_in, int64_t n, const clipper_features::Neighborhood* nnb,
-                 const double* view, const clipper_features::Neighborhood* fnb, double* N_out, int32_t* ncnt_out,
-                 double* F_out, double* spfh_out, int32_t* fcnt_out) {
-  if (int rc = use_device(device)) return rc;
-
+// THE BODY of the stages, on device pointers: dP the cloud (n x 3); nnb: the neighbourhood of the normals stage, which
+// writes dN (n x 3) and dcn (n) and reads the viewpoint dV (null: none) — with nnb null dN holds the normals already;
+// fnb: the feature stage's (null: none), which writes dS, dF (n x 33 each) and dcf (n). The lists of the search join
+// tmp; everything is queued on st (the grid route of the search has waited inside it); kept as knn_lists'. The
+// host-buffer calls (below) and the calls on clouds (host_cloud.hpp) both run this.
+int features_body(int device, const double* dP, int64_t n, const clipper_features::Neighborhood* nnb, const double* dV,
+                  const clipper_features::Neighborhood* fnb, double* dN, int32_t* dcn, double* dS, double* dF,
+                  int32_t* dcf, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
   const int K = clipper_features::list_k(std::max(nnb ? nnb->knn : 0, fnb ? fnb->knn : 0));
-  const size_t n3 = static_cast<size_t>(n) * 3, nf = fnb ? static_cast<size_t>(n) * FEAT_DIM : 0;
-  const size_t no = static_cast<size_t>(n) * K, nn = static_cast<size_t>(n);
-  double *dP = nullptr, *dN = nullptr, *dV = nullptr, *od = nullptr, *dS = nullptr, *dF = nullptr;
-  int32_t *oi = nullptr, *dcn = nullptr, *dcf = nullptr;
-  DevTemps tmp;
-  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dN, n3 * sizeof(double), dV, 3 * sizeof(double),
-                         od, no * sizeof(double), oi, no * sizeof(int32_t), dS, nf * sizeof(double), dF, nf * sizeof(double),
-                         dcn, nn * sizeof(int32_t), dcf, nn * sizeof(int32_t)))
-    return rc;
-  hipStream_t st = nullptr;  // the default stream: a stand-alone call
-  if (int rc = copy_up(dP, P, n3, st)) return rc;
-  if (!nnb)
-    if (int rc = copy_up(dN, N_in, n3, st)) return rc;
-  if (nnb && view)
-    if (int rc = copy_up(dV, view, 3, st)) return rc;
+  const size_t no = static_cast<size_t>(n) * K;
+  double* od = nullptr;
+  int32_t* oi = nullptr;
+  if (int rc = tmp.alloc(device, od, no * sizeof(double), oi, no * sizeof(int32_t))) return rc;
   // the cloud's nearest-neighbour lists in itself, K in {4, 8, 16, 32}, by the route of the process-wide mode
-  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
+  // (kept: the cloud's own grid index where its owner keeps one)
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, kept)) return rc;
   if (nnb) {
     const int use_r = nnb->radius > 0.0;
     hipLaunchKernelGGL(k_feat_normals<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
-                       nnb->knn, use_r, nnb->radius * nnb->radius, view ? dV : nullptr, dN, dcn);
-    if (int rc = copy_down(N_out, dN, n3, st)) return rc;
-    if (int rc = copy_down(ncnt_out, dcn, nn, st)) return rc;
+                       nnb->knn, use_r, nnb->radius * nnb->radius, dV, dN, dcn);
   }
   if (fnb) {
     const int use_r = fnb->radius > 0.0;
@@ -61,6 +50,37 @@ int features_run(int device, const double* P, const double* N_in, int64_t n, con
       return fail(CLIPPER_HIP_E_INTERNAL, "no SPFH kernel for %d slots", slots);
     hipLaunchKernelGGL(k_feat_fpfh<>, dim3(static_cast<unsigned>(ceil_div(n, FEAT_FPFH_POINTS))), dim3(256), 0, st, dS, n,
                        oi, od, K, fnb->knn, use_r, r2, dF);
+  }
+  return 0;
+}
+
+// nnb: the neighbourhood of the normals stage (null: the normals are N_in); fnb: the feature stage's (null: none).
+// Every argument has been checked. Outputs may be null where the entry points allow it.
+int features_run(int device, const double* P, const double* N_in, int64_t n, const clipper_features::Neighborhood* nnb,
+                 const double* view, const clipper_features::Neighborhood* fnb, double* N_out, int32_t* ncnt_out,
+                 double* F_out, double* spfh_out, int32_t* fcnt_out) {
+  if (int rc = use_device(device)) return rc;
+
+  const size_t n3 = static_cast<size_t>(n) * 3, nf = fnb ? static_cast<size_t>(n) * FEAT_DIM : 0;
+  const size_t nn = static_cast<size_t>(n);
+  double *dP = nullptr, *dN = nullptr, *dV = nullptr, *dS = nullptr, *dF = nullptr;
+  int32_t *dcn = nullptr, *dcf = nullptr;
+  DevTemps tmp;
+  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dN, n3 * sizeof(double), dV, 3 * sizeof(double),
+                         dS, nf * sizeof(double), dF, nf * sizeof(double), dcn, nn * sizeof(int32_t), dcf, nn * sizeof(int32_t)))
+    return rc;
+  hipStream_t st = nullptr;  // the default stream: a stand-alone call
+  if (int rc = copy_up(dP, P, n3, st)) return rc;
+  if (!nnb)
+    if (int rc = copy_up(dN, N_in, n3, st)) return rc;
+  if (nnb && view)
+    if (int rc = copy_up(dV, view, 3, st)) return rc;
+  if (int rc = features_body(device, dP, n, nnb, (nnb && view) ? dV : nullptr, fnb, dN, dcn, dS, dF, dcf, st, tmp)) return rc;
+  if (nnb) {
+    if (int rc = copy_down(N_out, dN, n3, st)) return rc;
+    if (int rc = copy_down(ncnt_out, dcn, nn, st)) return rc;
+  }
+  if (fnb) {
     if (int rc = copy_down(F_out, dF, nf, st)) return rc;
     if (int rc = copy_down(spfh_out, dS, nf, st)) return rc;
     if (int rc = copy_down(fcnt_out, dcf, nn, st)) return rc;

@@ -52,39 +52,44 @@ void icp_select(const int32_t* oi, const double* od, int32_t ns, double d2, doub
   }
 }
 
-// Every argument has been checked. T0: column-major 4 x 4. history: (max_iterations + 1) x 3 or null; corr_out: ns or null.
-// Nt: the target's normals (point-to-plane alone); Cs, Ct: the covariances of the source and the target, 6 x n
-// (generalized alone): uploaded once each. rb: the robust settings (clipper_hip_icp_robust and
-// clipper_hip_icp_generalized_robust; null: the plain rounds, whose launches and buffers are untouched by it), rinfo: what
-// they report besides info. With rb the selection runs between the search and the sums when trim < 1, then the weighted
-// round; the control block stays on the device.
-int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const double* Nt, const double* Cs, const double* Ct,
-            int64_t nt_, const double* T0, const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info,
-            double* history, int32_t* corr_out, const clipper_icp::Robust* rb = nullptr,
-            clipper_icp_robust_info_t* rinfo = nullptr) {
-  if (int rc = use_device(device)) return rc;
+// where the inputs of a call lie on the device: the source Ps (ns x 3), the target Pt (nt x 3), Nt: the target's normals
+// (point-to-plane alone), Cs, Ct: the covariances of the source and the target, 6 x n (generalized alone). A cloud that
+// lives on the device (host_cloud.hpp) also hands over what it keeps of the target between calls: its search index
+// (grid route) or its bounding box (brute-force route); null: made for this call, in its temporaries.
+struct IcpInputs {
+  const double *Ps = nullptr, *Pt = nullptr, *Nt = nullptr, *Cs = nullptr, *Ct = nullptr;
+  const KnnGridIndex* index = nullptr;
+  const double *lo = nullptr, *hi = nullptr;
+};
 
+// THE BODY of every ICP entry point and of evaluate_registration, on device pointers. Every argument has been checked
+// and the device is current. T0: column-major 4 x 4 (host). history: (max_iterations + 1) x 3 or null; corr_out: ns or
+// null. rb: the robust settings (clipper_hip_icp_robust and clipper_hip_icp_generalized_robust; null: the plain rounds,
+// whose launches and buffers are untouched by it), rinfo: what they report besides info. With rb the selection runs
+// between the search and the sums when trim < 1, then the weighted round; the control block stays on the device.
+// The host-buffer calls (icp_run) and the calls on clouds (host_cloud.hpp) both run this.
+int icp_body(int device, const IcpInputs& in, int64_t ns_, int64_t nt_, const double* T0, const clipper_icp::Params& prm,
+             double* T_out, clipper_icp_info_t* info, double* history, int32_t* corr_out, const clipper_icp::Robust* rb,
+             clipper_icp_robust_info_t* rinfo, DevTemps& tmp) {
   const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
   const bool plane = prm.method == ICP_POINT_TO_PLANE, gen = prm.method == ICP_GENERALIZED;
   const int terms = rb ? icp_robust_terms(prm.method) : icp_terms(prm.method);
   const bool trimmed = rb && rb->trim < 1.0;
   const int32_t nb = static_cast<int32_t>(ceil_div(ns, ICP_BLOCK));
-  const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
+  const size_t s3 = static_cast<size_t>(ns) * 3;
   const size_t nrows = static_cast<size_t>(prm.max_iterations) + 1;
   const int route = knn_route(g_knn_search.load(), 3, ns, nt);
+  const double *dPs = in.Ps, *dPt = in.Pt, *dNt = in.Nt, *dCs = in.Cs, *dCt = in.Ct;
 
-  double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dCs = nullptr, *dCt = nullptr, *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr,
-         *dT = nullptr, *dhist = nullptr;
+  double *dq = nullptr, *od = nullptr, *dpart = nullptr, *dsums = nullptr, *dT = nullptr, *dhist = nullptr;
   int32_t *oi = nullptr, *perm = nullptr, *visited = nullptr;
   unsigned long long* dsum = nullptr;
   IcpRecord* drec = nullptr;
   IcpSelect* dctl = nullptr;
   uint32_t* dtot = nullptr;
-  DevTemps tmp;
   IcpHostState hs;
   const size_t s1 = static_cast<size_t>(ns);
-  if (int rc = tmp.alloc(device, dPs, s3 * sizeof(double), dPt, t3 * sizeof(double), dNt, (plane ? t3 : 0) * sizeof(double),
-                         dq, s3 * sizeof(double), od, s1 * sizeof(double), oi, s1 * sizeof(int32_t),
+  if (int rc = tmp.alloc(device, dq, s3 * sizeof(double), od, s1 * sizeof(double), oi, s1 * sizeof(int32_t),
                          dpart, static_cast<size_t>(nb) * terms * sizeof(double), dsums, ICP_PLANE_TERMS * sizeof(double),
                          dT, 16 * sizeof(double), dhist, nrows * 3 * sizeof(double), drec, sizeof(IcpRecord)))
     return rc;
@@ -93,8 +98,6 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
     if (int rc = knn_brute_alloc(device, 1, ns, nt, bs, tmp)) return rc;
   if (int rc = tmp.alloc(device, perm, s1 * sizeof(int32_t), visited, s1 * sizeof(int32_t), dsum, sizeof(unsigned long long)))
     return rc;
-  if (gen)  // (behind the buffers every method has: theirs keep their places)
-    if (int rc = tmp.alloc(device, dCs, s1 * 6 * sizeof(double), dCt, static_cast<size_t>(nt) * 6 * sizeof(double))) return rc;
   if (rb)  // (behind every buffer of the plain call)
     if (int rc = tmp.alloc(device, dctl, sizeof(IcpSelect), dtot, ICP_SELECT_RADIX * sizeof(uint32_t))) return rc;
   HIPCHK(hs.rec.alloc(1));
@@ -105,30 +108,35 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   IcpRecord first{};
   first.status = ICP_RUNNING;
   *hs.rec = first;
-  HIPCHK(hipMemcpyAsync(dPs, Ps, s3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dPt, Pt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
-  if (plane) HIPCHK(hipMemcpyAsync(dNt, Nt, t3 * sizeof(double), hipMemcpyHostToDevice, st));
-  if (gen) {
-    HIPCHK(hipMemcpyAsync(dCs, Cs, s1 * 6 * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dCt, Ct, static_cast<size_t>(nt) * 6 * sizeof(double), hipMemcpyHostToDevice, st));
-  }
   HIPCHK(hipMemcpyAsync(dT, T0, 16 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(drec, hs.rec, sizeof(IcpRecord), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dhist, 0, nrows * 3 * sizeof(double), st));
   HIPCHK(hipMemsetAsync(dsum, 0, sizeof(unsigned long long), st));
 
-  // the target's index (grid route) or its bounding box alone: the origin of the sums is the box's centre on both routes
-  KnnGridIndex ix;
+  // the target's index (grid route) or its bounding box alone: the origin of the sums is the box's centre on both
+  // routes. What the caller keeps of the target is taken as it is; else it is made here, for this call.
+  KnnGridIndex built;
+  const KnnGridIndex* ixp = in.index;
   double lo[3], hi[3], o[3];
   if (route == CLIPPER_HIP_KNN_GRID) {
-    if (int rc = knn_grid_build(device, dPt, nt, ix, st, tmp)) return rc;
+    if (!ixp) {
+      if (int rc = knn_grid_build(device, dPt, nt, built, st, tmp)) return rc;
+      ixp = &built;
+    }
     for (int a = 0; a < 3; ++a) {
-      lo[a] = ix.lo[a];
-      hi[a] = ix.hi[a];
+      lo[a] = ixp->lo[a];
+      hi[a] = ixp->hi[a];
+    }
+  } else if (in.lo && in.hi) {
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = in.lo[a];
+      hi[a] = in.hi[a];
     }
   } else if (int rc = knn_grid_bounds(device, dPt, nt, lo, hi, st, tmp)) {
     return rc;
   }
+  const KnnGridIndex none;
+  const KnnGridIndex& ix = ixp ? *ixp : none;  // (read on the grid route alone)
   icp_origin(lo, hi, o);
 
   const double d2 = prm.max_distance * prm.max_distance;
@@ -224,6 +232,36 @@ int icp_run(int device, const double* Ps, int64_t ns_, const double* Pt, const d
   return 0;
 }
 
+// The host-buffer frame around the body: both clouds, and what the method reads of them, go to the device once.
+// Nt / Cs / Ct as IcpInputs'. Every argument has been checked.
+int icp_run(int device, const double* Ps, int64_t ns, const double* Pt, const double* Nt, const double* Cs, const double* Ct,
+            int64_t nt, const double* T0, const clipper_icp::Params& prm, double* T_out, clipper_icp_info_t* info,
+            double* history, int32_t* corr_out, const clipper_icp::Robust* rb = nullptr,
+            clipper_icp_robust_info_t* rinfo = nullptr) {
+  if (int rc = use_device(device)) return rc;
+  const bool plane = prm.method == ICP_POINT_TO_PLANE, gen = prm.method == ICP_GENERALIZED;
+  const size_t s3 = static_cast<size_t>(ns) * 3, t3 = static_cast<size_t>(nt) * 3;
+  const size_t s6 = gen ? static_cast<size_t>(ns) * 6 : 0, t6 = gen ? static_cast<size_t>(nt) * 6 : 0;
+  double *dPs = nullptr, *dPt = nullptr, *dNt = nullptr, *dCs = nullptr, *dCt = nullptr;
+  DevTemps tmp;
+  if (int rc = tmp.alloc(device, dPs, s3 * sizeof(double), dPt, t3 * sizeof(double), dNt, (plane ? t3 : 0) * sizeof(double)))
+    return rc;
+  if (gen)
+    if (int rc = tmp.alloc(device, dCs, s6 * sizeof(double), dCt, t6 * sizeof(double))) return rc;
+  hipStream_t st = nullptr;  // the default stream: a stand-alone call
+  if (int rc = copy_up(dPs, Ps, s3, st)) return rc;
+  if (int rc = copy_up(dPt, Pt, t3, st)) return rc;
+  if (plane)
+    if (int rc = copy_up(dNt, Nt, t3, st)) return rc;
+  if (gen) {
+    if (int rc = copy_up(dCs, Cs, s6, st)) return rc;
+    if (int rc = copy_up(dCt, Ct, t6, st)) return rc;
+  }
+  IcpInputs in;
+  in.Ps = dPs, in.Pt = dPt, in.Nt = dNt, in.Cs = dCs, in.Ct = dCt;
+  return icp_body(device, in, ns, nt, T0, prm, T_out, info, history, corr_out, rb, rinfo, tmp);
+}
+
 const double ICP_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 int icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt, int64_t n_tgt,
@@ -311,28 +349,38 @@ int icp_generalized_robust(int device, const double* P_src, const double* C_src,
                  history, nullptr, &rb, robust_info);
 }
 
+// THE BODY of the covariance stage, on device pointers: dP the cloud (n x 3), dC (n x 6) and dcn (n) its outputs. The
+// lists of the search join tmp; everything is queued on st. The host-buffer call (below) and the call on a cloud
+// (host_cloud.hpp) both run this.
+int covariances_body(int device, const double* dP, int64_t n, const clipper_features::Neighborhood& nb, double epsilon,
+                     double* dC, int32_t* dcn, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
+  const int K = clipper_features::list_k(nb.knn);
+  const size_t no = static_cast<size_t>(n) * K;
+  double* od = nullptr;
+  int32_t* oi = nullptr;
+  if (int rc = tmp.alloc(device, od, no * sizeof(double), oi, no * sizeof(int32_t))) return rc;
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, kept)) return rc;
+  const int use_r = nb.radius > 0.0;
+  const double w = 1.0 - epsilon;
+  hipLaunchKernelGGL(k_icp_covariances<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
+                     nb.knn, use_r, nb.radius * nb.radius, w, dC, dcn);
+  return 0;
+}
+
 // The covariances of the generalized metric: host_features.hpp's features_run with the one kernel behind the search
 // changed. Every argument has been checked.
 int covariances_run(int device, const double* P, int64_t n, const clipper_features::Neighborhood& nb, double epsilon,
                     double* C_out, int32_t* count_out) {
   if (int rc = use_device(device)) return rc;
 
-  const int K = clipper_features::list_k(nb.knn);
-  const size_t n3 = static_cast<size_t>(n) * 3, n6 = static_cast<size_t>(n) * 6;
-  const size_t no = static_cast<size_t>(n) * K, nn = static_cast<size_t>(n);
-  double *dP = nullptr, *dC = nullptr, *od = nullptr;
-  int32_t *oi = nullptr, *dcn = nullptr;
+  const size_t n3 = static_cast<size_t>(n) * 3, n6 = static_cast<size_t>(n) * 6, nn = static_cast<size_t>(n);
+  double *dP = nullptr, *dC = nullptr;
+  int32_t* dcn = nullptr;
   DevTemps tmp;
-  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dC, n6 * sizeof(double), od, no * sizeof(double),
-                         oi, no * sizeof(int32_t), dcn, nn * sizeof(int32_t)))
-    return rc;
+  if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dC, n6 * sizeof(double), dcn, nn * sizeof(int32_t))) return rc;
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
   if (int rc = copy_up(dP, P, n3, st)) return rc;
-  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp)) return rc;
-  const int use_r = nb.radius > 0.0;
-  const double w = 1.0 - epsilon;
-  hipLaunchKernelGGL(k_icp_covariances<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
-                     nb.knn, use_r, nb.radius * nb.radius, w, dC, dcn);
+  if (int rc = covariances_body(device, dP, n, nb, epsilon, dC, dcn, st, tmp)) return rc;
   if (int rc = copy_down(C_out, dC, n6, st)) return rc;
   if (int rc = copy_down(count_out, dcn, nn, st)) return rc;
   HIPCHK(hipStreamSynchronize(st));  // the one wait of the call

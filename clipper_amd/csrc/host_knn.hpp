@@ -66,12 +66,13 @@ int knn_brute_lists(int device, int K, int d, const double* dP0, int64_t n0, con
 
 // The seam. dP0: n0 x d, dP1: n1 x d on the device; od / oi: n0 x K, the caller's; K in {1, 2, 4, 8, 16, 32}. The
 // route's temporaries join tmp. Returns 0 with the kernels queued on st (the grid route has waited for them), or <0.
+// kept: the grid index of dP1 where its owner keeps one (read on the grid route alone; null: built for the call).
 int knn_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
-              int32_t* oi, hipStream_t st, DevTemps& tmp) {
+              int32_t* oi, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
   const int route = knn_route(g_knn_search.load(), d, n0, n1);
   g_knn_stats = clipper_hip_knn_stats_t{route, {0, 0, 0}, n0, 0, CLIPPER_HIP_KNN_AUTO_MIN_N, 0.0};
   const bool timed = knn_events_begin(device, st);
-  const int rc = route == CLIPPER_HIP_KNN_GRID ? knn_grid_lists(device, K, dP0, n0, dP1, n1, od, oi, st, tmp)
+  const int rc = route == CLIPPER_HIP_KNN_GRID ? knn_grid_lists(device, K, dP0, n0, dP1, n1, od, oi, st, tmp, kept)
                                                : knn_brute_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp);
   knn_events_end(timed && rc == 0, st);
   return rc;

@@ -167,13 +167,15 @@ void knn_grid_sum_visited(const int32_t* visited, int32_t n0, unsigned long long
 
 // The grid route: the build over dP1, dP0 binned by the same grid (skipped when the cloud is searched in itself), the
 // query, the statistics. One host wait in the build (the bounding box comes back for the plan) and one at the end
-// (the candidate count). Temporaries are tmp's.
+// (the candidate count). Temporaries are tmp's. kept: the index of dP1 its owner holds already (a cloud that lives on the
+// device, host_cloud.hpp; the index depends on the cloud alone, not on K): nothing is built, the first wait falls away.
 int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const double* dP1, int64_t n1_, double* od, int32_t* oi,
-                   hipStream_t st, DevTemps& tmp) {
+                   hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
   const int32_t n0 = static_cast<int32_t>(n0_), n1 = static_cast<int32_t>(n1_);
   const bool self = dP0 == dP1 && n0 == n1;
   KnnGridIndex ix;
-  if (int rc = knn_grid_build(device, dP1, n1, ix, st, tmp)) return rc;
+  if (kept) ix = *kept;
+  else if (int rc = knn_grid_build(device, dP1, n1, ix, st, tmp)) return rc;
   KgPoint* Q = ix.S;
   if (!self) {
     KnnGridQueries q;

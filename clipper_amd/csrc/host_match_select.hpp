@@ -19,18 +19,12 @@
 #include <string>
 #include <vector>
 
+#include "match_rules.hpp"
+
 namespace clipper_match {
 
 constexpr int MAX_D = 64;    // coordinates per descriptor
 constexpr int MAX_KNN = 8;   // neighbours per point
-
-// clipper_match_params_t, as the filters read it
-struct Params {
-  int knn;
-  int mutual;
-  double ratio;
-  double max_sqdist;
-};
 
 // nearest-neighbour lists of n queries, row-major n x stride
 struct Lists {
@@ -89,27 +83,19 @@ inline std::vector<double> pad_rows(const double* F, int64_t n, int d, int dp) {
 // how long the forward lists must be: the ratio test reads the second neighbour
 inline int forward_len(const Params& prm) { return prm.ratio > 0.0 ? 2 : prm.knn; }
 
-// the filters (see the head of this file). fwd: forward_len(prm) entries per query; bwd: knn entries per point of the
-// other set, read only when prm.mutual is set.
+// the filters (see the head of this file; the per-query and per-entry rules are match_rules.hpp's, which the device's
+// k_match_select shares). fwd: forward_len(prm) entries per query; bwd: knn entries per point of the other set, read
+// only when prm.mutual is set.
 inline Rows select(const Params& prm, const Lists& fwd, const Lists& bwd) {
   Rows out;
-  const double r2 = prm.ratio * prm.ratio;
   for (int64_t i = 0; i < fwd.n; ++i) {
     const int32_t* nn = fwd.idx + i * fwd.stride;
     const double* sd = fwd.sqd + i * fwd.stride;
-    if (prm.ratio > 0.0 && !(nn[1] < 0 || sd[0] < r2 * sd[1])) continue;
+    if (!query_passes(prm, nn, sd)) continue;
     for (int k = 0; k < prm.knn; ++k) {
-      const int32_t j = nn[k];
-      if (j < 0) continue;
-      if (prm.max_sqdist > 0.0 && !(sd[k] <= prm.max_sqdist)) continue;
-      if (prm.mutual) {
-        const int32_t* bn = bwd.idx + static_cast<int64_t>(j) * bwd.stride;
-        bool found = false;
-        for (int c = 0; c < prm.knn && !found; ++c) found = (bn[c] == static_cast<int32_t>(i));
-        if (!found) continue;
-      }
+      if (!entry_kept(prm, i, k, nn, sd, bwd.idx, bwd.stride)) continue;
       out.i.push_back(static_cast<int32_t>(i));
-      out.j.push_back(j);
+      out.j.push_back(nn[k]);
       out.sqd.push_back(sd[k]);
     }
   }

@@ -653,7 +653,8 @@ int association_list(const int32_t* A, int64_t m_in, int64_t n1, int64_t n2, std
 // common front part of both affinity entry points: A handling + allocation + point tables
 int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, int64_t n2,
                  const int32_t* A, int64_t m_in, const StagedInputs* dev = nullptr) {
-  if (!h || !D1 || !D2 || d < 1 || n1 < 1 || n2 < 1)
+  const bool folded = dev && dev->maxabs >= 0.0;  // (the caller holds no host copy of the points)
+  if (!h || ((!D1 || !D2) && !folded) || d < 1 || n1 < 1 || n2 < 1)
     return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
   if (int rc = association_list(A, m_in, n1, n2, h->A)) return rc;
   const int64_t m = static_cast<int64_t>(h->A.size() / 2);
@@ -677,9 +678,9 @@ int stage_inputs(Ctx* h, const double* D1, int d, int64_t n1, const double* D2, 
   }
   h->staged_d = d;
   h->staged_pstride = pstride;
-  double mx = 0.0;
-  for (int64_t i = 0; i < static_cast<int64_t>(d) * n1; ++i) mx = std::max(mx, std::fabs(D1[i]));
-  for (int64_t i = 0; i < static_cast<int64_t>(d) * n2; ++i) mx = std::max(mx, std::fabs(D2[i]));
+  double mx = folded ? dev->maxabs : 0.0;
+  for (int64_t i = 0; !folded && i < static_cast<int64_t>(d) * n1; ++i) mx = std::max(mx, std::fabs(D1[i]));
+  for (int64_t i = 0; !folded && i < static_cast<int64_t>(d) * n2; ++i) mx = std::max(mx, std::fabs(D2[i]));
   h->staged_maxabs = mx;
   const char* mode = std::getenv("CLIPPER_HIP_AFFINITY");
   h->plain_affinity = (mode && std::strcmp(mode, "plain") == 0);

@@ -193,12 +193,14 @@ struct Shard : SliceStore, ShardBufs {
   Event ev_reduced, ev_copied;
 };
 
-// inputs of a problem that are on the device already (a batch stages all its problems with one copy): D1, D2 as the
-// caller gave them, A as stage_inputs holds it (m x 2, column-major)
+// inputs of a problem that are on the device already (a batch stages all its problems with one copy; clouds that live
+// there): D1, D2 as the caller gave them, A as stage_inputs holds it (m x 2, column-major). maxabs >= 0: max |coordinate|
+// of D1 and D2, folded by the caller on the device (stage_inputs then reads no host copy of them: they may be null)
 struct StagedInputs {
   const double* D1 = nullptr;
   const double* D2 = nullptr;
   const int32_t* A = nullptr;
+  double maxabs = -1.0;
 };
 
 // the resident solver (k_resident.hip.h): plan of the current slices and its buffers

@@ -13,6 +13,10 @@
 //                          MATCH_UNR candidates, whose distances are carried across the groups in MATCH_UNR VGPR pairs.
 //                          The additions of one candidate therefore stay in coordinate order.
 //   k_knn_merge<K>         (k_knn.hip.h) folds the S partial lists of a query in chunk order
+//   k_match_pad            the zero padding of the rows on the device (descriptors that are there already: a cloud's)
+//   k_match_select<EMIT>   the filters on the device (match_rules.hpp, the host's own rules): thread = one query; EMIT = 0
+//                          counts its kept entries, k_row_scan (k_wave.hip.h) turns the counts into offsets, EMIT = 1
+//                          writes the rows at them: i ascending, then k ascending, as clipper_match::select
 // Rows are PADDED WITH ZEROS to 8 G coordinates (by the host, before the copy): (0 - 0)^2 = 0 added to a non-negative
 // partial sum is exact, so the padding changes no bit, and for the same reason a narrower descriptor may run through a
 // wider instantiation. Instantiated: G in {1, 2, 4, 5, 8} x K in {1, 2, 4, 8} — d <= 8 (coordinates; one group), d <= 16,
@@ -28,6 +32,7 @@
 #include <stdint.h>
 
 #include "k_knn.hip.h"
+#include "match_rules.hpp"
 
 namespace clipper_hip {
 
@@ -115,6 +120,49 @@ __global__ __launch_bounds__(256) void k_match_partial(const double* __restrict_
       pi[o + k] = bi[k];
     }
   }
+}
+
+// out: n x dp, row p = the d numbers of row p of F (n x d), then zeros. Thread = one number of out.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_match_pad(const double* __restrict__ F, int64_t n, int d, int dp,
+                                                    double* __restrict__ out) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= n * dp) return;
+  const int64_t p = e / dp;
+  const int k = static_cast<int>(e - p * dp);
+  out[e] = k < d ? F[p * d + k] : 0.0;
+}
+
+// The filters. fi / fd: the forward lists, n0 x fstride; bi: the backward lists' indices, n1 x bstride (read only with
+// prm.mutual). EMIT = 0: cnt[i] = kept entries of query i. EMIT = 1: off[i] = the first row of query i (the exclusive
+// scan of cnt); rows (i, nn_k(i)) go to A (column-major m x 2) and sqd from there on, k ascending.
+template <int EMIT>
+__global__ __launch_bounds__(256) void k_match_select(clipper_match::Params prm, const int32_t* __restrict__ fi,
+                                                       const double* __restrict__ fd, int64_t n0, int fstride,
+                                                       const int32_t* __restrict__ bi, int bstride,
+                                                       int32_t* __restrict__ cnt, const int32_t* __restrict__ off,
+                                                       int64_t m, int32_t* __restrict__ A, double* __restrict__ sqd) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n0) return;
+  const int32_t* nn = fi + i * fstride;
+  const double* sd = fd + i * fstride;
+  int32_t kept = 0;
+  if (clipper_match::query_passes(prm, nn, sd)) {
+    const int64_t r0 = EMIT ? off[i] : 0;
+    for (int k = 0; k < prm.knn; ++k) {
+      if (!clipper_match::entry_kept(prm, i, k, nn, sd, bi, bstride)) continue;
+      if (EMIT) {
+        const int64_t r = r0 + kept;
+        if (r < m) {  // (always: m is the scan's total)
+          A[r] = static_cast<int32_t>(i);
+          A[m + r] = nn[k];
+          sqd[r] = sd[k];
+        }
+      }
+      ++kept;
+    }
+  }
+  if (!EMIT) cnt[i] = kept;
 }
 
 }  // namespace clipper_hip

@@ -53,6 +53,7 @@
 //   k_sort.hip.h      a stable LSD radix sort of (u64 key, i32 index) pairs, 8-bit digits
 //   k_voxel.hip.h     voxel down-sampling over that sort: one centroid (and normal) per occupied voxel, bit for bit
 //   k_select.hip.h    the exact rank select of trimmed ICP: an MSD radix select over the bits of the squared distances
+//   k_cloud.hip.h     clouds that live on the device: the gather of selected points, the point-then-normal table, max |x|
 #pragma once
 
 #include "k_wave.hip.h"
@@ -77,3 +78,4 @@
 #include "k_sort.hip.h"
 #include "k_voxel.hip.h"
 #include "k_select.hip.h"
+#include "k_cloud.hip.h"

@@ -232,6 +232,16 @@ def ground_truth_associations(pcd0: np.ndarray, pcd1: np.ndarray, radius: float,
         return abi.distance_based_correspondences(pcd0.T, pcd1.T, 1, radius, True, device=device)
 
 
+def __getattr__(name):
+    """DeviceCloud and DevicePairs: clouds and association lists that live on the device, carrying what the stages
+    below compute about them (clipper_amd._abi, which is loaded at first use like every device call of this module).
+    They take and return the C ABI's layout, 3 x n with columns = points."""
+    if name in ("DeviceCloud", "DevicePairs"):
+        from . import _abi as abi
+        return getattr(abi, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def match_descriptors(F0: np.ndarray, F1: np.ndarray, knn: int = 1, mutual: bool = True, ratio: float = 0.0,
                       max_sqdist: float = 0.0, device: int = 0):
     """Putative associations from feature descriptors, on the GPU (clipper_hip_match_descriptors).

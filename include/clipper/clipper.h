@@ -36,6 +36,11 @@ struct clipper_hip_ctx;  // opaque handle of the C ABI
 
 namespace clipper {
 
+namespace registration {
+class DeviceCloud;  // include/clipper/device_cloud.h: clouds and association lists that live on the device
+class DevicePairs;
+}  // namespace registration
+
 namespace maxclique {
 /// Mirror of the reference maxclique::Method / Params (maxclique.h:15-23). EXACT = ROBIN* (a maximum clique), HEU = the
 /// greedy clique of DESIGN.md 9, KCORE = ROBIN (the vertices of maximum core number). `threads` is accepted and
@@ -109,6 +114,14 @@ class CLIPPER {
   /// Affinity matrix of the m associations in A (all-to-all when A is empty). clipper.cpp:21-65
   void scorePairwiseConsistency(const invariants::Data& D1, const invariants::Data& D2,
                                 const Association& A = Association());
+
+  /// The same from clouds that live on the device (include/clipper/device_cloud.h): the point tables are gathered by
+  /// `pairs` on the device (clipper_hip_stage_inputs_clouds), then the built-in fill runs as above — the same matrix
+  /// as scorePairwiseConsistency(points of c1, points of c2, pairs.download()), bit for bit. EuclideanDistance scores
+  /// the points, PointNormalDistance the points and normals of both clouds, a DeviceInvariant compiled for d = 3 the
+  /// points; an invariant evaluated on the host needs host data (std::invalid_argument). One-shard contexts only.
+  void scorePairwiseConsistency(const registration::DeviceCloud& c1, const registration::DeviceCloud& c2,
+                                const registration::DevicePairs& pairs);
 
   /// Graduated projected gradient ascent (clipper.cpp:69-78, 172-323). Random u0 if empty.
   void solve(const VectorXd& u0 = VectorXd());

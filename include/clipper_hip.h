@@ -739,6 +739,110 @@ int clipper_hip_voxel_downsample(int device, const double* P, const double* N, i
                                  double* P_out, double* N_out, int32_t* count_out, int32_t* trace_out, int64_t* n_out,
                                  clipper_voxel_info_t* info);
 
+/* CLOUDS ON THE DEVICE: the front end from raw scan to refined transform without crossing the bus between its stages.
+ * clipper_hip_cloud_t owns n points (3 x n fp64, n >= 0) on one device and what the stages below have computed about
+ * it: unit normals, descriptors (any 1 <= d <= 64; FPFH has 33), SPFH, covariances, the neighbour counts of each stage,
+ * the members and the trace of the voxel stage that made it, and, built at the first search AGAINST it and kept, the
+ * search grid (CLIPPER_HIP_KNN_GRID route) or the bounding box (brute-force route). clipper_hip_pairs_t owns an
+ * association list on the device: m x 2 int32 column-major as `clipper::Association`, one squared distance per row
+ * where it came from the matcher.
+ * Every stage on handles runs the same device code as its host-buffer call above on the same route
+ * (clipper_hip_knn_set_search is read per call) and gives the same bits; only the copies and the host's filters are
+ * gone. What comes from the host is checked where it enters (create, set_descriptors) with the checks of the
+ * host-buffer calls, before any device work: finite coordinates, normals of squared length within [0.99, 1.01],
+ * n < 2^31. A stage that needs an attachment the cloud does not have returns CLIPPER_HIP_E_STATE. Creators return 0 and
+ * hand the handle out through their last pointer argument (NULL on failure); destroy takes NULL. All work runs on the
+ * default stream, and every call has waited for it when it returns. A handle is NOT safe for concurrent mutation:
+ * stages attach to it and searches build what it keeps; calls on one handle must not overlap.
+ * Not built: RANSAC on handles, the all-to-all hypothesis from clouds (pairs with m = 0 are refused at staging),
+ * column-sharded and multi-process contexts (CLIPPER_HIP_E_SCOPE), batches of clouds in one call, fp32 clouds, d = 2. */
+typedef struct clipper_hip_cloud clipper_hip_cloud_t;
+typedef struct clipper_hip_pairs clipper_hip_pairs_t;
+enum { CLIPPER_HIP_CLOUD_POINTS = 0,            /* 3 x n double                                              */
+       CLIPPER_HIP_CLOUD_NORMALS = 1,           /* 3 x n double                                              */
+       CLIPPER_HIP_CLOUD_DESCRIPTORS = 2,       /* d x n double (FPFH: 33 x n)                               */
+       CLIPPER_HIP_CLOUD_SPFH = 3,              /* 33 x n double                                             */
+       CLIPPER_HIP_CLOUD_COVARIANCES = 4,       /* 6 x n double                                              */
+       CLIPPER_HIP_CLOUD_NORMAL_COUNTS = 5,     /* n int32: cnt of estimate_normals                          */
+       CLIPPER_HIP_CLOUD_FPFH_COUNTS = 6,       /* n int32: cnt of compute_fpfh                              */
+       CLIPPER_HIP_CLOUD_COVARIANCE_COUNTS = 7, /* n int32: cnt of estimate_covariances                      */
+       CLIPPER_HIP_CLOUD_VOXEL_COUNTS = 8,      /* n int32: the members of each voxel (a voxel-made cloud)   */
+       CLIPPER_HIP_CLOUD_VOXEL_TRACE = 9 };     /* trace_n int32: the row of every point of the voxel stage's input */
+typedef struct clipper_hip_cloud_info_t {
+  int64_t n;
+  int64_t trace_n;          /* entries of CLIPPER_HIP_CLOUD_VOXEL_TRACE (0: none)                 */
+  int32_t device;
+  int32_t has_normals;
+  int32_t descriptor_dim;   /* 0: no descriptors                                                  */
+  int32_t has_spfh;
+  int32_t has_covariances;
+  int32_t has_voxel_counts;
+  int32_t grid_builds;      /* how often the search grid over this cloud was built: 0 or 1        */
+  int32_t grid_dim[3];      /* its cells along x, y, z (0 before it is built)                     */
+} clipper_hip_cloud_info_t;
+
+/* P: 3 x n column-major as `clipper::Data` (may be NULL with n == 0); N: unit normals, 3 x n, or NULL. */
+int clipper_hip_cloud_create(int device, const double* P, const double* N, int64_t n, clipper_hip_cloud_t** out);
+void clipper_hip_cloud_destroy(clipper_hip_cloud_t* cloud);
+int64_t clipper_hip_cloud_count(const clipper_hip_cloud_t* cloud);   /* n, or <0: error */
+/* `what`: one of CLIPPER_HIP_CLOUD_*; `out`: room for what the enumerator's comment says. An attachment that was never
+ * computed: CLIPPER_HIP_E_STATE. */
+int clipper_hip_cloud_download(const clipper_hip_cloud_t* cloud, int what, void* out);
+int clipper_hip_cloud_info(const clipper_hip_cloud_t* cloud, clipper_hip_cloud_info_t* out);
+/* Descriptors from elsewhere (FCGF, SpinNet, Predator: a network's), F: d x n column-major, every value finite,
+ * 1 <= d <= 64; they replace the cloud's descriptors. The rows are padded for the matcher on the device, once. */
+int clipper_hip_cloud_set_descriptors(clipper_hip_cloud_t* cloud, const double* F, int d);
+
+/* A: m x 2 column-major, no negative index (the ranges are checked against the clouds where the pairs are used);
+ * sqd: m, or NULL (clipper_hip_pairs_download then takes no sqd_out). m >= 0. */
+int clipper_hip_pairs_create(int device, const int32_t* A, const double* sqd, int64_t m, clipper_hip_pairs_t** out);
+void clipper_hip_pairs_destroy(clipper_hip_pairs_t* pairs);
+int64_t clipper_hip_pairs_count(const clipper_hip_pairs_t* pairs);   /* m, or <0: error */
+int clipper_hip_pairs_has_sqd(const clipper_hip_pairs_t* pairs);     /* 1: one squared distance per row, 0: none; <0: error */
+int clipper_hip_pairs_download(const clipper_hip_pairs_t* pairs, int32_t* A_out, double* sqd_out);
+
+/* clipper_hip_voxel_downsample on a cloud: *out is a NEW cloud whose points are the centroids and, when `in` has
+ * normals, whose normals are the normalised normal sums; the members per voxel (VOXEL_COUNTS) and, with want_trace,
+ * the trace (VOXEL_TRACE) are attached to it. One host read in the middle (the number of rows). `in` is not const: a
+ * cloud that a stage made gets its corners folded on the device at its first down-sampling, and keeps them. */
+int clipper_hip_cloud_voxel_downsample(clipper_hip_cloud_t* in, double voxel_size, int want_trace,
+                                       clipper_hip_cloud_t** out, clipper_voxel_info_t* info);
+/* clipper_hip_estimate_normals / _compute_fpfh / _fpfh_from_points / _estimate_covariances on a cloud: the result is
+ * attached to it (normals and NORMAL_COUNTS; descriptors, SPFH and FPFH_COUNTS; both; covariances and
+ * COVARIANCE_COUNTS). compute_fpfh needs normals (CLIPPER_HIP_E_STATE). Every stage searches the cloud in itself anew
+ * (the lists are not kept); on the grid route the search queries the cloud's kept grid, built at first use. */
+int clipper_hip_cloud_estimate_normals(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb, const double* viewpoint);
+int clipper_hip_cloud_compute_fpfh(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb);
+int clipper_hip_cloud_fpfh_from_points(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* normal_nb,
+                                       const double* viewpoint, const clipper_neighborhood_t* feature_nb);
+int clipper_hip_cloud_estimate_covariances(clipper_hip_cloud_t* cloud, const clipper_neighborhood_t* nb, double epsilon);
+/* clipper_hip_match_descriptors on two clouds' descriptors (the same d; CLIPPER_HIP_E_STATE without), with the filters
+ * run on the device: *out holds the rows of the host-buffer call, row for row and bit for bit, i ascending then k
+ * ascending, with their squared distances. nn_idx_out / nn_sqd_out (may be NULL): the forward lists, n0 x knn. */
+int clipper_hip_cloud_match(const clipper_hip_cloud_t* c0, const clipper_hip_cloud_t* c1, const clipper_match_params_t* params,
+                            clipper_hip_pairs_t** out, int32_t* nn_idx_out, double* nn_sqd_out);
+/* clipper_hip_stage_inputs from device data: D1 / D2 are the clouds' points (d = 3) or, with_normals, each point
+ * followed by its normal (d = 6, for the PointNormalDistance fill); A is `pairs` (m >= 1, every index within its
+ * cloud). The point tables are gathered with device-to-device traffic only; the pairs come down once (the solver's
+ * rounding reads A on the host). The _staged fills and solves then run unchanged. One-shard contexts on the clouds'
+ * device only (CLIPPER_HIP_E_SCOPE / CLIPPER_HIP_E_INVALID). */
+int clipper_hip_stage_inputs_clouds(clipper_hip_t* h, const clipper_hip_cloud_t* c0, const clipper_hip_cloud_t* c1,
+                                    const clipper_hip_pairs_t* pairs, int with_normals);
+/* The k points idx names (each within the cloud), in the order of the list, to `out` (3 x k): what
+ * clipper_hip_estimate_rigid_transform fits. */
+int clipper_hip_cloud_gather_points(const clipper_hip_cloud_t* cloud, const int32_t* idx, int64_t k, double* out);
+/* clipper_hip_icp / _icp_generalized / _icp_robust / _icp_generalized_robust on two clouds: params->method picks
+ * point-to-point, point-to-plane (needs the target's normals) or generalized (needs both clouds' covariances), else
+ * CLIPPER_HIP_E_STATE; robust and robust_info may be NULL (the plain rounds). The target's grid (or, on the
+ * brute-force route, its bounding box) is built at the first call against `tgt` and KEPT: a second ICP, evaluation or
+ * grid-route stage search against the same cloud builds nothing (clipper_hip_cloud_info: grid_builds stays 1). */
+int clipper_hip_cloud_icp(const clipper_hip_cloud_t* src, clipper_hip_cloud_t* tgt, const double* T_init,
+                          const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+                          clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history);
+int clipper_hip_cloud_evaluate_registration(const clipper_hip_cloud_t* src, clipper_hip_cloud_t* tgt, const double* T,
+                                            double max_distance, double* fitness, double* inlier_rmse, int64_t* count,
+                                            int32_t* corr_out);
+
 /* Line-search window: how many consecutive step sizes alpha, alpha*beta, ... of the
  * backtracking line search (clipper.cpp:234-251) one pass over M evaluates at once. The
  * trial sequence, the accepted trial and the result are those of the reference for every
