@@ -1296,6 +1296,46 @@ def _transform_arg(T, name):
     return t, _dp(t)
 
 
+def _icp_call(fn, lead, T_init, method, max_distance, max_iterations, rel_fitness, rel_rmse, robust=None, robust_slots=None):
+    """One ICP call of the C ABI. fn: the C function; lead: its arguments in front of T_init (the device and the clouds,
+    or two handles; a pointer made by _dp keeps its array alive); robust: (loss, scale, trim) or None; robust_slots:
+    whether fn takes the robust settings and their info at all (default: as robust is given; clipper_hip_cloud_icp takes
+    NULL for both). Returns (T 4 x 4, info) with info.history attached, and for a robust call within, weight_sum and
+    trim_sqd of clipper_icp_robust_info_t."""
+    t0, t0p = _transform_arg(T_init, "T_init")
+    prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
+    rb, rinfo = (IcpRobust(*robust), IcpRobustInfo()) if robust is not None else (None, None)
+    T = np.zeros(16, dtype=np.float64)
+    info = IcpInfo()
+    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
+    rbp, rip = (C.byref(rb), C.byref(rinfo)) if robust is not None else (None, None)
+    slots = (robust is not None) if robust_slots is None else robust_slots
+    mid, tail = ((rbp,), (rip,)) if slots else ((), ())
+    rc = fn(*lead, t0p, C.byref(prm), *mid, _dp(T), C.byref(info), *tail, _dp(hist))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
+    info.history = hist[:info.iterations + 1].copy()
+    if robust is not None:
+        info.within, info.weight_sum, info.trim_sqd = int(rinfo.within), float(rinfo.weight_sum), float(rinfo.trim_sqd)
+    return T.reshape(4, 4).T.copy(), info
+
+
+def _icp_clouds(device, P_src, P_tgt, N_tgt):
+    """the leading arguments of clipper_hip_icp and clipper_hip_icp_robust"""
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Nt = None if N_tgt is None else _cloud(N_tgt, "N_tgt")
+    if Nt is not None and Nt.shape[1] != Pt.shape[1]:
+        raise ValueError("P_tgt and N_tgt must hold the same number of points")
+    return device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1]
+
+
+def _gicp_clouds(device, P_src, C_src, P_tgt, C_tgt):
+    """the leading arguments of clipper_hip_icp_generalized and clipper_hip_icp_generalized_robust"""
+    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
+    Cs, Ct = _covariances(C_src, "C_src", Ps.shape[1]), _covariances(C_tgt, "C_tgt", Pt.shape[1])
+    return device, _dp(Ps), _dp(Cs), Ps.shape[1], _dp(Pt), _dp(Ct), Pt.shape[1]
+
+
 def icp(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None, max_distance: float = 0.0,
         max_iterations: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, device: int = 0):
     """clipper_hip_icp: refine the alignment T_init (4 x 4, None = identity) of the source cloud P_src onto the target
@@ -1303,22 +1343,8 @@ def icp(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None,
     ICP_POINT_TO_PLANE over the target's unit normals N_tgt (3 x n_tgt). A correspondence is the nearest target point
     of a moved source point, an inlier within max_distance. Returns (T 4 x 4, info): info.status is ICP_*,
     info.history the (iterations + 1) x 3 rows of (count, fitness, rmse), one per evaluated T."""
-    L = load_library()
-    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
-    Nt = None if N_tgt is None else _cloud(N_tgt, "N_tgt")
-    if Nt is not None and Nt.shape[1] != Pt.shape[1]:
-        raise ValueError("P_tgt and N_tgt must hold the same number of points")
-    t0, t0p = _transform_arg(T_init, "T_init")
-    prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
-    T = np.zeros(16, dtype=np.float64)
-    info = IcpInfo()
-    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
-    rc = L.clipper_hip_icp(device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1], t0p,
-                           C.byref(prm), _dp(T), C.byref(info), _dp(hist))
-    if rc < 0:
-        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
-    info.history = hist[:info.iterations + 1].copy()
-    return T.reshape(4, 4).T.copy(), info
+    return _icp_call(load_library().clipper_hip_icp, _icp_clouds(device, P_src, P_tgt, N_tgt), T_init, method, max_distance,
+                     max_iterations, rel_fitness, rel_rmse)
 
 
 def _covariances(Cv, name, n):
@@ -1355,27 +1381,8 @@ def icp_generalized(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance: float
     """clipper_hip_icp_generalized: icp with the plane-to-plane metric of generalized ICP over the per-point
     covariances C_src (6 x n_src) and C_tgt (6 x n_tgt), e.g. estimate_covariances' (positive definite, else refused).
     P_src, P_tgt: 3 x n, columns = points. Returns (T 4 x 4, info) as icp does."""
-    L = load_library()
-    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
-    Cs, Ct = _covariances(C_src, "C_src", Ps.shape[1]), _covariances(C_tgt, "C_tgt", Pt.shape[1])
-    t0, t0p = _transform_arg(T_init, "T_init")
-    prm = IcpParams(ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse)
-    T = np.zeros(16, dtype=np.float64)
-    info = IcpInfo()
-    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
-    rc = L.clipper_hip_icp_generalized(device, _dp(Ps), _dp(Cs), Ps.shape[1], _dp(Pt), _dp(Ct), Pt.shape[1], t0p,
-                                       C.byref(prm), _dp(T), C.byref(info), _dp(hist))
-    if rc < 0:
-        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
-    info.history = hist[:info.iterations + 1].copy()
-    return T.reshape(4, 4).T.copy(), info
-
-
-def _robust_result(T, info, rinfo, hist):
-    """(T 4 x 4, info) of a robust call: info as icp's, with the three fields of clipper_icp_robust_info_t attached"""
-    info.history = hist[:info.iterations + 1].copy()
-    info.within, info.weight_sum, info.trim_sqd = int(rinfo.within), float(rinfo.weight_sum), float(rinfo.trim_sqd)
-    return T.reshape(4, 4).T.copy(), info
+    return _icp_call(load_library().clipper_hip_icp_generalized, _gicp_clouds(device, P_src, C_src, P_tgt, C_tgt), T_init,
+                     ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse)
 
 
 def icp_robust(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tgt=None, max_distance: float = 0.0,
@@ -1385,22 +1392,8 @@ def icp_robust(P_src, P_tgt, T_init=None, method: int = ICP_POINT_TO_POINT, N_tg
     residual, and / or trimming: each iteration keeps the fraction `trim` of the points within max_distance with the
     smallest distances (ties at the threshold all kept). count, fitness, rmse and the history are over the kept points.
     Returns (T 4 x 4, info) as icp does, info also carrying within, weight_sum and trim_sqd of the last row."""
-    L = load_library()
-    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
-    Nt = None if N_tgt is None else _cloud(N_tgt, "N_tgt")
-    if Nt is not None and Nt.shape[1] != Pt.shape[1]:
-        raise ValueError("P_tgt and N_tgt must hold the same number of points")
-    t0, t0p = _transform_arg(T_init, "T_init")
-    prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
-    rb, rinfo = IcpRobust(loss, scale, trim), IcpRobustInfo()
-    T = np.zeros(16, dtype=np.float64)
-    info = IcpInfo()
-    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
-    rc = L.clipper_hip_icp_robust(device, _dp(Ps), Ps.shape[1], _dp(Pt), None if Nt is None else _dp(Nt), Pt.shape[1], t0p,
-                                  C.byref(prm), C.byref(rb), _dp(T), C.byref(info), C.byref(rinfo), _dp(hist))
-    if rc < 0:
-        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
-    return _robust_result(T, info, rinfo, hist)
+    return _icp_call(load_library().clipper_hip_icp_robust, _icp_clouds(device, P_src, P_tgt, N_tgt), T_init, method,
+                     max_distance, max_iterations, rel_fitness, rel_rmse, (loss, scale, trim))
 
 
 def icp_generalized_robust(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance: float = 0.0, max_iterations: int = 30,
@@ -1408,20 +1401,22 @@ def icp_generalized_robust(P_src, C_src, P_tgt, C_tgt, T_init=None, max_distance
                            trim: float = 1.0, device: int = 0):
     """clipper_hip_icp_generalized_robust: icp_generalized with icp_robust's loss and trimming; the residual a loss
     weighs is d^T M d of the pair. Returns (T 4 x 4, info) as icp_robust does."""
-    L = load_library()
-    Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
-    Cs, Ct = _covariances(C_src, "C_src", Ps.shape[1]), _covariances(C_tgt, "C_tgt", Pt.shape[1])
-    t0, t0p = _transform_arg(T_init, "T_init")
-    prm = IcpParams(ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse)
-    rb, rinfo = IcpRobust(loss, scale, trim), IcpRobustInfo()
-    T = np.zeros(16, dtype=np.float64)
-    info = IcpInfo()
-    hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
-    rc = L.clipper_hip_icp_generalized_robust(device, _dp(Ps), _dp(Cs), Ps.shape[1], _dp(Pt), _dp(Ct), Pt.shape[1], t0p,
-                                              C.byref(prm), C.byref(rb), _dp(T), C.byref(info), C.byref(rinfo), _dp(hist))
+    return _icp_call(load_library().clipper_hip_icp_generalized_robust, _gicp_clouds(device, P_src, C_src, P_tgt, C_tgt), T_init,
+                     ICP_GENERALIZED, max_distance, max_iterations, rel_fitness, rel_rmse, (loss, scale, trim))
+
+
+def _evaluate_call(fn, lead, n_src, T, max_distance, return_correspondences):
+    """One evaluation of a registration by the C ABI: fn and its arguments in front of T as _icp_call's. Returns
+    (fitness, inlier_rmse, count), with return_correspondences also the n_src correspondences."""
+    t, tp = _transform_arg(T, "T")
+    fit, rmse, cnt = C.c_double(), C.c_double(), C.c_int64()
+    corr = np.zeros(max(n_src, 1), dtype=np.int32) if return_correspondences else None
+    rc = fn(*lead, tp, float(max_distance), C.byref(fit), C.byref(rmse), C.byref(cnt),
+            _ip(corr) if return_correspondences else None)
     if rc < 0:
         raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
-    return _robust_result(T, info, rinfo, hist)
+    out = (fit.value, rmse.value, cnt.value)
+    return out + (corr[:n_src],) if return_correspondences else out
 
 
 def evaluate_registration(P_src, P_tgt, T=None, max_distance: float = 0.0, device: int = 0, return_correspondences: bool = False):
@@ -1430,16 +1425,8 @@ def evaluate_registration(P_src, P_tgt, T=None, max_distance: float = 0.0, devic
     of every source point's correspondence (n_src int32, -1 = no inlier)."""
     L = load_library()
     Ps, Pt = _cloud(P_src, "P_src"), _cloud(P_tgt, "P_tgt")
-    t, tp = _transform_arg(T, "T")
-    fit, rmse, cnt = C.c_double(), C.c_double(), C.c_int64()
-    corr = np.zeros(max(Ps.shape[1], 1), dtype=np.int32) if return_correspondences else None
-    rc = L.clipper_hip_evaluate_registration(device, _dp(Ps), Ps.shape[1], _dp(Pt), Pt.shape[1], tp, float(max_distance),
-                                             C.byref(fit), C.byref(rmse), C.byref(cnt),
-                                             _ip(corr) if return_correspondences else None)
-    if rc < 0:
-        raise ClipperError(f"clipper_hip error {rc}: {_last_error()}")
-    out = (fit.value, rmse.value, cnt.value)
-    return out + (corr[:Ps.shape[1]],) if return_correspondences else out
+    return _evaluate_call(L.clipper_hip_evaluate_registration, (device, _dp(Ps), Ps.shape[1], _dp(Pt), Pt.shape[1]), Ps.shape[1],
+                          T, max_distance, return_correspondences)
 
 
 def voxel_down_sample(P, voxel_size: float, N=None, device: int = 0, return_counts: bool = False,
@@ -1677,31 +1664,13 @@ class DeviceCloud(_Handle):
             scale: float = 0.0, trim: float = 1.0):
         """icp / icp_generalized (and, with a loss given — ICP_LOSS_NONE for trimming alone — their robust forms) of this
         cloud onto `target`, whose search grid is built at the first call and kept. Returns (T 4 x 4, info) as they do."""
-        t0, t0p = _transform_arg(T_init, "T_init")
-        prm = IcpParams(method, max_distance, max_iterations, rel_fitness, rel_rmse)
-        robust = loss is not None
-        rb, rinfo = IcpRobust(loss if robust else ICP_LOSS_NONE, scale, trim), IcpRobustInfo()
-        T = np.zeros(16, dtype=np.float64)
-        info = IcpInfo()
-        hist = np.zeros((max(int(max_iterations), 0) + 1, 3), dtype=np.float64)
-        self._check(self.L.clipper_hip_cloud_icp(self.h, target.h, t0p, C.byref(prm), C.byref(rb) if robust else None, _dp(T),
-                                                 C.byref(info), C.byref(rinfo) if robust else None, _dp(hist)))
-        if robust:
-            return _robust_result(T, info, rinfo, hist)
-        info.history = hist[:info.iterations + 1].copy()
-        return T.reshape(4, 4).T.copy(), info
+        return _icp_call(self.L.clipper_hip_cloud_icp, (self.h, target.h), T_init, method, max_distance, max_iterations,
+                         rel_fitness, rel_rmse, None if loss is None else (loss, scale, trim), robust_slots=True)
 
     def evaluate_registration(self, target: "DeviceCloud", T=None, max_distance: float = 0.0,
                               return_correspondences: bool = False):
-        t, tp = _transform_arg(T, "T")
-        fit, rmse, cnt = C.c_double(), C.c_double(), C.c_int64()
-        ns = len(self)
-        corr = np.zeros(max(ns, 1), dtype=np.int32) if return_correspondences else None
-        self._check(self.L.clipper_hip_cloud_evaluate_registration(self.h, target.h, tp, float(max_distance), C.byref(fit),
-                                                                   C.byref(rmse), C.byref(cnt),
-                                                                   _ip(corr) if return_correspondences else None))
-        out = (fit.value, rmse.value, cnt.value)
-        return out + (corr[:ns],) if return_correspondences else out
+        return _evaluate_call(self.L.clipper_hip_cloud_evaluate_registration, (self.h, target.h), len(self), T, max_distance,
+                              return_correspondences)
 
 
 class HipBatch:

@@ -432,28 +432,31 @@ int clipper_hip_fpfh_from_points(int device, const double* P, int64_t n, const c
 int clipper_hip_icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
                     int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
                     clipper_icp_info_t* info, double* history) try {
-  return icp(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init, params, T_out, info, history);
+  return icp_call("icp", clipper_icp::FAMILY_POINT_PLANE, clipper_icp::ROBUST_ABSENT, device,
+                  {P_src, n_src, P_tgt, n_tgt, N_tgt, nullptr, nullptr}, T_init, params, nullptr, T_out, info, nullptr, history);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_icp_generalized(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt,
                                 const double* C_tgt, int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
                                 double* T_out, clipper_icp_info_t* info, double* history) try {
-  return icp_generalized(device, P_src, C_src, n_src, P_tgt, C_tgt, n_tgt, T_init, params, T_out, info, history);
+  return icp_call("icp_generalized", clipper_icp::FAMILY_GENERALIZED, clipper_icp::ROBUST_ABSENT, device,
+                  {P_src, n_src, P_tgt, n_tgt, nullptr, C_src, C_tgt}, T_init, params, nullptr, T_out, info, nullptr, history);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_icp_robust(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt,
                            int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
                            const clipper_icp_robust_t* robust, double* T_out, clipper_icp_info_t* info,
                            clipper_icp_robust_info_t* robust_info, double* history) try {
-  return icp_robust(device, P_src, n_src, P_tgt, N_tgt, n_tgt, T_init, params, robust, T_out, info, robust_info, history);
+  return icp_call("icp_robust", clipper_icp::FAMILY_POINT_PLANE, clipper_icp::ROBUST_REQUIRED, device,
+                  {P_src, n_src, P_tgt, n_tgt, N_tgt, nullptr, nullptr}, T_init, params, robust, T_out, info, robust_info, history);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_icp_generalized_robust(int device, const double* P_src, const double* C_src, int64_t n_src,
                                        const double* P_tgt, const double* C_tgt, int64_t n_tgt, const double* T_init,
                                        const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
                                        clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) try {
-  return icp_generalized_robust(device, P_src, C_src, n_src, P_tgt, C_tgt, n_tgt, T_init, params, robust, T_out, info,
-                                robust_info, history);
+  return icp_call("icp_generalized_robust", clipper_icp::FAMILY_GENERALIZED, clipper_icp::ROBUST_REQUIRED, device,
+                  {P_src, n_src, P_tgt, n_tgt, nullptr, C_src, C_tgt}, T_init, params, robust, T_out, info, robust_info, history);
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_estimate_covariances(int device, const double* P, int64_t n, const clipper_neighborhood_t* nb, double epsilon,

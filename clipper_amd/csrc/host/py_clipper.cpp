@@ -240,6 +240,19 @@ static clipper::registration::IcpRobust icp_robust_of(const std::string& loss, d
   throw std::invalid_argument("loss must be one of \"none\", \"huber\", \"cauchy\", \"tukey\", \"geman_mcclure\"");
 }
 
+// the method string and the numeric keywords of an ICP binding as IcpParams. with_generalized: the call takes
+// "generalized" besides "point" and "plane" (DeviceCloud.icp; the generalized bindings pass that name themselves)
+static clipper::registration::IcpParams icp_params_of(const std::string& method, bool with_generalized, double max_distance,
+                                                      int max_iterations, double rel_fitness, double rel_rmse) {
+  namespace reg = clipper::registration;
+  static const char* const names[] = {"point", "plane", "generalized"};
+  for (int k = 0; k < (with_generalized ? 3 : 2); ++k)
+    if (method == names[k])
+      return reg::IcpParams{static_cast<reg::IcpMethod>(k), max_distance, max_iterations, rel_fitness, rel_rmse};
+  throw std::invalid_argument(with_generalized ? "method must be \"point\", \"plane\" or \"generalized\""
+                                               : "method must be \"point\" or \"plane\"");
+}
+
 PYBIND11_MODULE(clipperpy, m) {
   m.doc() = "A graph-theoretic framework for robust data association (MI355X hot path)";
   m.attr("__version__") = CLIPPER_VERSION;
@@ -311,14 +324,8 @@ PYBIND11_MODULE(clipperpy, m) {
       [](const clipper::MatrixXd& src, const clipper::MatrixXd& tgt, const clipper::MatrixXd& T_init, const std::string& method,
          const clipper::MatrixXd& normals, double max_distance, int max_iterations, double rel_fitness, double rel_rmse) {
         namespace reg = clipper::registration;
-        if (method != "point" && method != "plane") throw std::invalid_argument("method must be \"point\" or \"plane\"");
+        const reg::IcpParams prm = icp_params_of(method, false, max_distance, max_iterations, rel_fitness, rel_rmse);
         if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
-        reg::IcpParams prm;
-        prm.method = method == "plane" ? reg::IcpMethod::PointToPlane : reg::IcpMethod::PointToPoint;
-        prm.max_distance = max_distance;
-        prm.max_iterations = max_iterations;
-        prm.rel_fitness = rel_fitness;
-        prm.rel_rmse = rel_rmse;
         const reg::IcpResult r = reg::icp(src, tgt, prm, T_init.data(), normals);
         return icp_tuple(r);
       },
@@ -345,12 +352,7 @@ PYBIND11_MODULE(clipperpy, m) {
          double rel_fitness, double rel_rmse) {
         namespace reg = clipper::registration;
         if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
-        reg::IcpParams prm;
-        prm.method = reg::IcpMethod::Generalized;
-        prm.max_distance = max_distance;
-        prm.max_iterations = max_iterations;
-        prm.rel_fitness = rel_fitness;
-        prm.rel_rmse = rel_rmse;
+        const reg::IcpParams prm = icp_params_of("generalized", true, max_distance, max_iterations, rel_fitness, rel_rmse);
         const reg::IcpResult r = reg::icp_generalized(src, src_cov, tgt, tgt_cov, prm, T_init.data());
         return icp_tuple(r);
       },
@@ -365,14 +367,8 @@ PYBIND11_MODULE(clipperpy, m) {
          const clipper::MatrixXd& normals, double max_distance, int max_iterations, double rel_fitness, double rel_rmse,
          const std::string& loss, double scale, double trim) {
         namespace reg = clipper::registration;
-        if (method != "point" && method != "plane") throw std::invalid_argument("method must be \"point\" or \"plane\"");
+        const reg::IcpParams prm = icp_params_of(method, false, max_distance, max_iterations, rel_fitness, rel_rmse);
         if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
-        reg::IcpParams prm;
-        prm.method = method == "plane" ? reg::IcpMethod::PointToPlane : reg::IcpMethod::PointToPoint;
-        prm.max_distance = max_distance;
-        prm.max_iterations = max_iterations;
-        prm.rel_fitness = rel_fitness;
-        prm.rel_rmse = rel_rmse;
         const reg::IcpRobustResult r = reg::icp_robust(src, tgt, prm, icp_robust_of(loss, scale, trim), T_init.data(), normals);
         return icp_robust_tuple(r);
       },
@@ -389,12 +385,7 @@ PYBIND11_MODULE(clipperpy, m) {
          double rel_fitness, double rel_rmse, const std::string& loss, double scale, double trim) {
         namespace reg = clipper::registration;
         if (T_init.rows() != 4 || T_init.cols() != 4) throw std::invalid_argument("T_init must be 4 x 4");
-        reg::IcpParams prm;
-        prm.method = reg::IcpMethod::Generalized;
-        prm.max_distance = max_distance;
-        prm.max_iterations = max_iterations;
-        prm.rel_fitness = rel_fitness;
-        prm.rel_rmse = rel_rmse;
+        const reg::IcpParams prm = icp_params_of("generalized", true, max_distance, max_iterations, rel_fitness, rel_rmse);
         const reg::IcpRobustResult r =
             reg::icp_generalized_robust(src, src_cov, tgt, tgt_cov, prm, icp_robust_of(loss, scale, trim), T_init.data());
         return icp_robust_tuple(r);
@@ -583,13 +574,8 @@ PYBIND11_MODULE(clipperpy, m) {
         .def("icp",
              [](const reg::DeviceCloud& c, reg::DeviceCloud& target, const std::string& method, double max_distance,
                 int max_iterations, const py::object& T_init, const py::object& loss, double scale, double trim) {
-               if (method != "point" && method != "plane" && method != "generalized")
-                 throw std::invalid_argument("method must be \"point\", \"plane\" or \"generalized\"");
-               reg::IcpParams prm;
-               prm.method = method == "plane" ? reg::IcpMethod::PointToPlane
-                                              : (method == "generalized" ? reg::IcpMethod::Generalized : reg::IcpMethod::PointToPoint);
-               prm.max_distance = max_distance;
-               prm.max_iterations = max_iterations;
+               const reg::IcpParams def;  // (this binding has no keywords for the stop bounds: the facade's defaults)
+               const reg::IcpParams prm = icp_params_of(method, true, max_distance, max_iterations, def.rel_fitness, def.rel_rmse);
                clipper::MatrixXd T0;
                if (!T_init.is_none()) {
                  T0 = T_init.cast<clipper::MatrixXd>();

@@ -586,15 +586,10 @@ int cloud_icp(const Cloud* src, Cloud* tgt, const double* T_init, const clipper_
               double* history) {
   namespace ci = clipper_icp;
   if (!src || !tgt) return fail(CLIPPER_HIP_E_INVALID, "cloud_icp: null cloud handle");
-  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
-                                           params->rel_rmse}
-                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  const ci::Params h = icp_params_of(params);
   const ci::Robust rb = icp_robust_of(robust);
-  std::string why = !T_out ? "null T_out" : "";
-  if (why.empty())
-    why = (params && h.method == ICP_GENERALIZED) ? ci::check_generalized_params(&h) : ci::check_params(params ? &h : nullptr);
-  if (why.empty() && robust) why = ci::check_robust(&rb);
-  if (why.empty()) why = ci::check_transform("T_init", T_init);
+  const std::string why = ci::check_call(ci::FAMILY_BY_METHOD, ci::ROBUST_OPTIONAL, params ? &h : nullptr, robust ? &rb : nullptr,
+                                         T_out != nullptr, T_init, nullptr);
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "cloud_icp: %s", why.c_str());
   return cloud_icp_run("cloud_icp", src, tgt, T_init, h, robust ? &rb : nullptr, T_out, info, robust ? robust_info : nullptr,
                        history, nullptr);
@@ -611,9 +606,7 @@ int cloud_evaluate_registration(const Cloud* src, Cloud* tgt, const double* T, d
   clipper_icp_info_t info{};
   if (int rc = cloud_icp_run("cloud_evaluate_registration", src, tgt, T, h, nullptr, nullptr, &info, nullptr, nullptr, corr_out))
     return rc;
-  if (fitness) *fitness = info.fitness;
-  if (inlier_rmse) *inlier_rmse = info.inlier_rmse;
-  if (count) *count = info.count;
+  icp_evaluation_out(info, fitness, inlier_rmse, count);
   return 0;
 }
 

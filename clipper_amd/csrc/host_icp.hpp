@@ -1,13 +1,17 @@
-// host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized, their robust forms and clipper_hip_evaluate_registration
-// ("ICP over a kept search grid" and "Generalized ICP"), and of clipper_hip_estimate_covariances,
-// the stage that makes the generalized metric's covariances. Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
+// host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized, their robust forms and
+// clipper_hip_evaluate_registration ("ICP over a kept search grid", "Generalized ICP" and "Robust
+// losses and trimmed ICP"), and of clipper_hip_estimate_covariances, the stage that makes the generalized metric's
+// covariances. Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
 // built once and queried every iteration with k_knn_grid<1>; the source is binned by the target's grid once, at
 // T_init, and keeps that order for all iterations (a locality hint, never a correctness input: the lists go to the
 // rows of the original indices). T, the sums, the history and the candidate count stay on the device during the loop;
 // the host reads the 64-byte status record once per iteration through pinned memory to decide whether to queue the
 // next round: the only host wait of an iteration. The brute-force route queries one kept scratch (host_knn.hpp).
-// Stand-alone: needs no context. The checks are host_icp_check.hpp's, the arithmetic icp_rules.hpp's. Part of
-// clipper_hip.hip (one translation unit; included there last, after host_features.hpp).
+// Each layer is stated once: icp_call is the four host-buffer entry points (who, family, robust use), icp_run the
+// host-buffer frame, icp_body the loop on device pointers (also under host_cloud.hpp's calls), IcpRound what a round
+// reads, icp_queue_round the one dispatch to icp_round<METHOD, ROBUST>, the two launches.
+// Stand-alone: needs no context. The checks are host_icp_check.hpp's (check_call), the arithmetic icp_rules.hpp's. Part
+// of clipper_hip.hip (one translation unit; included there last, after host_features.hpp).
 #pragma once
 
 #include "host_icp_check.hpp"
@@ -20,26 +24,43 @@ struct IcpHostState {
   Event a, b;
 };
 
-template <int METHOD>
-void icp_round(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt,
-               const double* dCs, const double* dCt, int32_t nt, double d2, const double (&o)[3], double* dpart, int32_t nb,
-               const IcpStop& stop, int k, double* dsums, double* dT, IcpRecord* drec, double* dhist, hipStream_t st) {
-  hipLaunchKernelGGL((k_icp_accumulate<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt, dNt,
-                     dCs, dCt, dT, nt, d2, o[0], o[1], o[2], dpart);
-  hipLaunchKernelGGL((k_icp_step<METHOD>), dim3(1), dim3(256), 0, st, dpart, nb, stop, k, o[0], o[1], o[2], dsums, dT, drec,
-                     dhist);
+// what a round reads, filled once before the loop: the K = 1 lists, the moved source q, the clouds and what the method
+// reads of them (IcpInputs' Nt, Cs, Ct), d2 = max_distance^2, the origin of the sums, the robust settings and the
+// selection's control block (read by the robust rounds alone), the partials (nb x the layout's terms), the stop rule,
+// and where the step leaves the sums, T, the record and the history. All pointers: device memory.
+struct IcpRound {
+  const int32_t* oi;
+  const double *od, *q;
+  int32_t ns;
+  const double *Pt, *Nt, *Cs, *Ct;
+  int32_t nt;
+  double d2, o[3];
+  IcpRobustArgs rb;
+  double* part;
+  int32_t nb;
+  IcpStop stop;
+  double *sums, *T;
+  IcpRecord* rec;
+  double* hist;
+  hipStream_t st;
+};
+
+// round k: the sums and the step
+template <int METHOD, bool ROBUST>
+void icp_round(const IcpRound& r, int k) {
+  hipLaunchKernelGGL((k_icp_accumulate<METHOD, ROBUST>), dim3(static_cast<unsigned>(r.nb)), dim3(256), 0, r.st, r.oi, r.od, r.q,
+                     r.ns, r.Pt, r.Nt, r.Cs, r.Ct, r.T, r.nt, r.d2, r.o[0], r.o[1], r.o[2], r.rb, r.part);
+  hipLaunchKernelGGL((k_icp_step<METHOD, ROBUST>), dim3(1), dim3(256), 0, r.st, r.part, r.nb, r.stop, k, r.o[0], r.o[1], r.o[2],
+                     r.sums, r.T, r.rec, r.hist);
 }
 
-// the round of the robust entry points: the weighted sums against the selection's control block, the robust layout's step
-template <int METHOD>
-void icp_round_robust(const int32_t* oi, const double* od, const double* dq, int32_t ns, const double* dPt, const double* dNt,
-                      const double* dCs, const double* dCt, int32_t nt, double d2, const double (&o)[3],
-                      const clipper_icp::Robust& rb, const IcpSelect* dctl, double* dpart, int32_t nb, const IcpStop& stop,
-                      int k, double* dsums, double* dT, IcpRecord* drec, double* dhist, hipStream_t st) {
-  hipLaunchKernelGGL((k_icp_accumulate_robust<METHOD>), dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, oi, od, dq, ns, dPt,
-                     dNt, dCs, dCt, dT, nt, d2, o[0], o[1], o[2], rb.loss, rb.scale, rb.scale * rb.scale, dctl, dpart);
-  hipLaunchKernelGGL((k_icp_step_robust<METHOD>), dim3(1), dim3(256), 0, st, dpart, nb, stop, k, o[0], o[1], o[2], dsums, dT,
-                     drec, dhist);
+// the instantiation of the method; with rb the weighted sums against the control block and the robust layout's step
+void icp_queue_round(int method, const clipper_icp::Robust* rb, const IcpRound& r, int k) {
+  switch (method) {
+    case ICP_GENERALIZED: return rb ? icp_round<ICP_GENERALIZED, true>(r, k) : icp_round<ICP_GENERALIZED, false>(r, k);
+    case ICP_POINT_TO_PLANE: return rb ? icp_round<ICP_POINT_TO_PLANE, true>(r, k) : icp_round<ICP_POINT_TO_PLANE, false>(r, k);
+    default: return rb ? icp_round<ICP_POINT_TO_POINT, true>(r, k) : icp_round<ICP_POINT_TO_POINT, false>(r, k);
+  }
 }
 
 // The trimming threshold of the round under the current lists: two launches per digit, nothing read by the host.
@@ -73,7 +94,7 @@ int icp_body(int device, const IcpInputs& in, int64_t ns_, int64_t nt_, const do
              clipper_icp_robust_info_t* rinfo, DevTemps& tmp) {
   const int32_t ns = static_cast<int32_t>(ns_), nt = static_cast<int32_t>(nt_);
   const bool plane = prm.method == ICP_POINT_TO_PLANE, gen = prm.method == ICP_GENERALIZED;
-  const int terms = rb ? icp_robust_terms(prm.method) : icp_terms(prm.method);
+  const int terms = icp_layout_terms(prm.method, rb != nullptr);
   const bool trimmed = rb && rb->trim < 1.0;
   const int32_t nb = static_cast<int32_t>(ceil_div(ns, ICP_BLOCK));
   const size_t s3 = static_cast<size_t>(ns) * 3;
@@ -156,6 +177,13 @@ int icp_body(int device, const IcpInputs& in, int64_t ns_, int64_t nt_, const do
   if (route == CLIPPER_HIP_KNN_GRID)
     if (int rc = knn_grid_alloc_queries(device, ix, ns, gq, tmp)) return rc;
   KgPoint* const Q = gq.Q;  // (null on the brute-force route)
+  const IcpRobustArgs ra = rb ? IcpRobustArgs{rb->loss, rb->scale, rb->scale * rb->scale, dctl} : IcpRobustArgs{};
+  IcpRound rnd{};  // (filled by name: every member is a pointer or a number another one could stand in for)
+  rnd.oi = oi, rnd.od = od, rnd.q = dq, rnd.ns = ns;
+  rnd.Pt = dPt, rnd.Nt = dNt, rnd.Cs = dCs, rnd.Ct = dCt, rnd.nt = nt;
+  rnd.d2 = d2, rnd.o[0] = o[0], rnd.o[1] = o[1], rnd.o[2] = o[2], rnd.rb = ra;
+  rnd.part = dpart, rnd.nb = nb, rnd.stop = stop;
+  rnd.sums = dsums, rnd.T = dT, rnd.rec = drec, rnd.hist = dhist, rnd.st = st;
   HIPCHK(hipEventRecord(hs.a, st));
   int k = 0;
   for (;; ++k) {
@@ -173,18 +201,7 @@ int icp_body(int device, const IcpInputs& in, int64_t ns_, int64_t nt_, const do
       return rc;
     }
     if (trimmed) icp_select(oi, od, ns, d2, rb->trim, dctl, dtot, st);
-    if (rb && gen)
-      icp_round_robust<ICP_GENERALIZED>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
-    else if (rb && plane)
-      icp_round_robust<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
-    else if (rb)
-      icp_round_robust<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, *rb, dctl, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
-    else if (gen)
-      icp_round<ICP_GENERALIZED>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
-    else if (plane)
-      icp_round<ICP_POINT_TO_PLANE>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
-    else
-      icp_round<ICP_POINT_TO_POINT>(oi, od, dq, ns, dPt, dNt, dCs, dCt, nt, d2, o, dpart, nb, stop, k, dsums, dT, drec, dhist, st);
+    icp_queue_round(prm.method, rb, rnd, k);
     HIPCHK(hipMemcpyAsync(hs.rec, drec, sizeof(IcpRecord), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));  // the one wait of an iteration
     if (hs.rec->status != ICP_RUNNING || k >= prm.max_iterations) break;
@@ -264,89 +281,35 @@ int icp_run(int device, const double* Ps, int64_t ns, const double* Pt, const do
 
 const double ICP_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
-int icp(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt, int64_t n_tgt,
-        const double* T_init, const clipper_icp_params_t* params, double* T_out, clipper_icp_info_t* info, double* history) {
-  namespace ci = clipper_icp;
-  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
-                                           params->rel_rmse}
-                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
-  std::string why = !T_out ? "null T_out" : "";
-  if (why.empty()) why = ci::check_not_generalized(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_params(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
-  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
-  if (why.empty()) why = ci::check_transform("T_init", T_init);
-  if (why.empty()) why = ci::check_target_normals(h.method, N_tgt, n_tgt);
-  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp: %s", why.c_str());
-  return icp_run(device, P_src, n_src, P_tgt, N_tgt, nullptr, nullptr, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
-                 history, nullptr);
-}
-
-int icp_generalized(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt, const double* C_tgt,
-                    int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params, double* T_out,
-                    clipper_icp_info_t* info, double* history) {
-  namespace ci = clipper_icp;
-  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
-                                           params->rel_rmse}
-                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
-  std::string why = !T_out ? "null T_out" : "";
-  if (why.empty()) why = ci::check_generalized_params(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
-  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
-  if (why.empty()) why = ci::check_transform("T_init", T_init);
-  if (why.empty()) why = ci::check_covariances("source", C_src, n_src);
-  if (why.empty()) why = ci::check_covariances("target", C_tgt, n_tgt);
-  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_generalized: %s", why.c_str());
-  return icp_run(device, P_src, n_src, P_tgt, nullptr, C_src, C_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
-                 history, nullptr);
+clipper_icp::Params icp_params_of(const clipper_icp_params_t* params) {
+  if (!params) return clipper_icp::Params{0, 0, 0.0, 0.0, 0.0};
+  return clipper_icp::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness, params->rel_rmse};
 }
 
 clipper_icp::Robust icp_robust_of(const clipper_icp_robust_t* r) {
   return r ? clipper_icp::Robust{r->loss, r->reserved, r->scale, r->trim} : clipper_icp::Robust{0, 0, 0.0, 1.0};
 }
 
-// clipper_hip_icp with robust settings: its checks, then the settings', then icp_run's robust rounds
-int icp_robust(int device, const double* P_src, int64_t n_src, const double* P_tgt, const double* N_tgt, int64_t n_tgt,
-               const double* T_init, const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
-               clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) {
+// clipper_hip_icp, clipper_hip_icp_generalized and their robust forms (use: ROBUST_REQUIRED; else robust and robust_info
+// are not read): `who` names the call in a refusal, the family picks its parameter check and what it reads of c
+int icp_call(const char* who, clipper_icp::Family family, clipper_icp::RobustUse use, int device, const clipper_icp::HostClouds& c,
+             const double* T_init, const clipper_icp_params_t* params, const clipper_icp_robust_t* robust, double* T_out,
+             clipper_icp_info_t* info, clipper_icp_robust_info_t* robust_info, double* history) {
   namespace ci = clipper_icp;
-  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
-                                           params->rel_rmse}
-                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
+  const ci::Params h = icp_params_of(params);
   const ci::Robust rb = icp_robust_of(robust);
-  std::string why = !T_out ? "null T_out" : "";
-  if (why.empty()) why = ci::check_not_generalized(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_params(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_robust(robust ? &rb : nullptr);
-  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
-  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
-  if (why.empty()) why = ci::check_transform("T_init", T_init);
-  if (why.empty()) why = ci::check_target_normals(h.method, N_tgt, n_tgt);
-  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_robust: %s", why.c_str());
-  return icp_run(device, P_src, n_src, P_tgt, N_tgt, nullptr, nullptr, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
-                 history, nullptr, &rb, robust_info);
+  const bool with_rb = use != ci::ROBUST_ABSENT;
+  const std::string why = ci::check_call(family, use, params ? &h : nullptr, robust ? &rb : nullptr, T_out != nullptr, T_init, &c);
+  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s: %s", who, why.c_str());
+  return icp_run(device, c.P_src, c.n_src, c.P_tgt, c.N_tgt, c.C_src, c.C_tgt, c.n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out,
+                 info, history, nullptr, with_rb ? &rb : nullptr, with_rb ? robust_info : nullptr);
 }
 
-int icp_generalized_robust(int device, const double* P_src, const double* C_src, int64_t n_src, const double* P_tgt,
-                           const double* C_tgt, int64_t n_tgt, const double* T_init, const clipper_icp_params_t* params,
-                           const clipper_icp_robust_t* robust, double* T_out, clipper_icp_info_t* info,
-                           clipper_icp_robust_info_t* robust_info, double* history) {
-  namespace ci = clipper_icp;
-  const ci::Params h = params ? ci::Params{params->method, params->max_iterations, params->max_distance, params->rel_fitness,
-                                           params->rel_rmse}
-                              : ci::Params{0, 0, 0.0, 0.0, 0.0};
-  const ci::Robust rb = icp_robust_of(robust);
-  std::string why = !T_out ? "null T_out" : "";
-  if (why.empty()) why = ci::check_generalized_params(params ? &h : nullptr);
-  if (why.empty()) why = ci::check_robust(robust ? &rb : nullptr);
-  if (why.empty()) why = ci::check_cloud("source", P_src, n_src);
-  if (why.empty()) why = ci::check_cloud("target", P_tgt, n_tgt);
-  if (why.empty()) why = ci::check_transform("T_init", T_init);
-  if (why.empty()) why = ci::check_covariances("source", C_src, n_src);
-  if (why.empty()) why = ci::check_covariances("target", C_tgt, n_tgt);
-  if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "icp_generalized_robust: %s", why.c_str());
-  return icp_run(device, P_src, n_src, P_tgt, nullptr, C_src, C_tgt, n_tgt, T_init ? T_init : ICP_IDENTITY, h, T_out, info,
-                 history, nullptr, &rb, robust_info);
+// what the evaluation of a registration hands back of info (each output may be null)
+void icp_evaluation_out(const clipper_icp_info_t& info, double* fitness, double* inlier_rmse, int64_t* count) {
+  if (fitness) *fitness = info.fitness;
+  if (inlier_rmse) *inlier_rmse = info.inlier_rmse;
+  if (count) *count = info.count;
 }
 
 // THE BODY of the covariance stage, on device pointers: dP the cloud (n x 3), dC (n x 6) and dcn (n) its outputs. The
@@ -414,9 +377,7 @@ int evaluate_registration(int device, const double* P_src, int64_t n_src, const 
   if (int rc = icp_run(device, P_src, n_src, P_tgt, nullptr, nullptr, nullptr, n_tgt, T ? T : ICP_IDENTITY, h, nullptr, &info,
                        nullptr, corr_out))
     return rc;
-  if (fitness) *fitness = info.fitness;
-  if (inlier_rmse) *inlier_rmse = info.inlier_rmse;
-  if (count) *count = info.count;
+  icp_evaluation_out(info, fitness, inlier_rmse, count);
   return 0;
 }
 

@@ -1,8 +1,11 @@
 // host_icp_check.hpp — ICP and the evaluation of a registration, the part that needs no device: the argument checks of
 // clipper_hip_icp, clipper_hip_icp_generalized, their robust forms (clipper_hip_icp_robust,
-// clipper_hip_icp_generalized_robust), clipper_hip_estimate_covariances and clipper_hip_evaluate_registration.
-// Pure host code (no HIP): tests/cpp/test_icp_rules.cpp and tests/cpp/test_gicp_rules.cpp compile it with g++ alone. A refusal comes back as its message (empty: accepted) and names the offending value; the caller
-// hands it to fail(). Every check runs before any device work.
+// clipper_hip_icp_generalized_robust), clipper_hip_cloud_icp, clipper_hip_estimate_covariances and
+// clipper_hip_evaluate_registration. check_call at the end is a whole ICP call: every refusal of the five ICP entry
+// points in the order they are tried, told the call's family, its use of robust settings and whether its clouds are
+// host arrays. Pure host code (no HIP): tests/cpp/test_icp_rules.cpp, tests/cpp/test_gicp_rules.cpp and
+// tests/cpp/test_icp_call_checks.cpp compile it with g++ alone. A refusal comes back as its message (empty: accepted)
+// and names the offending value; the caller hands it to fail(). Every check runs before any device work.
 #pragma once
 
 #include <cmath>
@@ -135,6 +138,43 @@ inline std::string check_target_normals(int method, const double* N, int64_t n) 
   if (method != clipper_hip::ICP_POINT_TO_PLANE) return {};
   if (!N) return "point-to-plane needs the target's normals (N_tgt is null)";
   return clipper_features::check_normals(N, n);
+}
+
+// ---- a whole ICP call ---------------------------------------------------------------------------------------------------
+// which parameter check a call runs: clipper_hip_icp and its robust form take point-to-point and point-to-plane and name
+// the other call for the generalized method; clipper_hip_icp_generalized and its robust form take that method alone; a
+// call on cloud handles takes all three and checks the parameters by the method given
+enum Family { FAMILY_POINT_PLANE, FAMILY_GENERALIZED, FAMILY_BY_METHOD };
+// REQUIRED: a null robust is refused; OPTIONAL: checked when given; ABSENT: the call has none
+enum RobustUse { ROBUST_ABSENT, ROBUST_OPTIONAL, ROBUST_REQUIRED };
+
+// the clouds of a host-buffer call and what the methods read of them: N_tgt for point-to-plane, C_src / C_tgt (6 x n) for
+// generalized
+struct HostClouds {
+  const double* P_src;
+  int64_t n_src;
+  const double* P_tgt;
+  int64_t n_tgt;
+  const double *N_tgt, *C_src, *C_tgt;
+};
+
+// Every refusal of an ICP call that needs no device, in the order the entry points try them: T_out, the parameters, the
+// robust settings, the source, the target, T_init, then what the method reads of the clouds. host null: the clouds are
+// handles, valid by construction (their state is the caller's to check). Returns the first refusal, or empty.
+inline std::string check_call(Family family, RobustUse use, const Params* p, const Robust* r, bool has_T_out,
+                              const double* T_init, const HostClouds* host) {
+  if (!has_T_out) return "null T_out";
+  const bool gen = family == FAMILY_GENERALIZED || (family == FAMILY_BY_METHOD && p && p->method == clipper_hip::ICP_GENERALIZED);
+  std::string why = family == FAMILY_POINT_PLANE ? check_not_generalized(p) : std::string();
+  if (why.empty()) why = gen ? check_generalized_params(p) : check_params(p);
+  if (why.empty() && (use == ROBUST_REQUIRED || (use == ROBUST_OPTIONAL && r))) why = check_robust(r);
+  if (why.empty() && host) why = check_cloud("source", host->P_src, host->n_src);
+  if (why.empty() && host) why = check_cloud("target", host->P_tgt, host->n_tgt);
+  if (why.empty()) why = check_transform("T_init", T_init);
+  if (!why.empty() || !host) return why;
+  if (!gen) return check_target_normals(p->method, host->N_tgt, host->n_tgt);
+  why = check_covariances("source", host->C_src, host->n_src);
+  return why.empty() ? check_covariances("target", host->C_tgt, host->n_tgt) : why;
 }
 
 }  // namespace clipper_icp

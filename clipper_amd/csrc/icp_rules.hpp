@@ -242,6 +242,8 @@ ICP_HD double icp_weight(int loss, double e, double scale, double k2) {
 // w = 1.0 every product is exact and sum w equals the count: the plain sums, bit for bit.
 constexpr int ICP_POINT_ROBUST_TERMS = 18, ICP_POINT_WEIGHT_SUM = 16;
 constexpr int icp_robust_terms(int method) { return method == ICP_POINT_TO_POINT ? ICP_POINT_ROBUST_TERMS : ICP_PLANE_TERMS; }
+// the sums of a call: the plain layout, or the robust one
+constexpr int icp_layout_terms(int method, bool robust) { return robust ? icp_robust_terms(method) : icp_terms(method); }
 
 ICP_HD void icp_point_terms_weighted(const double (&t)[ICP_POINT_TERMS], double w, double (&out)[ICP_POINT_ROBUST_TERMS]) {
   out[0] = t[0];
@@ -507,7 +509,7 @@ struct IcpStop {
 template <int METHOD, bool ROBUST>
 ICP_HD void icp_iterate_over(const IcpStop& p, int k, const double* S, const double (&o)[3], double* T, IcpRecord& rec,
                              double* row) {
-  constexpr int TERMS = ROBUST ? icp_robust_terms(METHOD) : icp_terms(METHOD);
+  constexpr int TERMS = icp_layout_terms(METHOD, ROBUST);
   const double cnt = S[0];
   const double fitness = cnt / static_cast<double>(p.n_src);
   const double rmse = cnt > 0.0 ? sqrt(S[TERMS - 1] / cnt) : 0.0;

@@ -5,15 +5,15 @@
 //   k_icp_transform      thread = one place of the query order: source point perm[place] (or `place` itself) through
 //                        T, to row idx of q (n x 3) and, for the grid route, to place `place` of the binned queries
 //   k_icp_order          the permutation of a binned cloud (place -> original index), taken once at T_init
-//   k_icp_accumulate<M>  thread = source point i in its original order: the list entry, q, the target point (and
-//                        normal; generalized: the two covariances and the rotation of the device's T), the terms,
+//   k_icp_accumulate<M, ROBUST>  thread = source point i in its original order: the list entry, q, the target point
+//                        (and normal; generalized: the two covariances and the rotation of the device's T), the terms,
 //                        the halving tree in LDS, one partial per workgroup. The tree runs over LDS rows of one term
 //                        each, 8 terms at a time, so that a workgroup holds 16 KiB of LDS whatever the method.
-//   k_icp_step<M>        one workgroup: thread t adds partials t, t + 256, ... per term, the same tree; thread 0 runs
-//                        icp_iterate (the step, the stop test, the update of T) and writes the record and the
-//                        history row. T stays on the device.
-//   k_icp_accumulate_robust<M>, k_icp_step_robust<M>   the same two over the robust layout (clipper_hip_icp_robust):
-//                        a kept pair's terms weighed by its loss; kept against tau of k_select.hip.h's control block
+//   k_icp_step<M, ROBUST>  one workgroup: thread t adds partials t, t + 256, ... per term, the same tree; thread 0
+//                        runs icp_iterate_over (the step, the stop test, the update of T) and writes the record and
+//                        the history row. T stays on the device.
+//                        ROBUST (clipper_hip_icp_robust): the same two over the robust layout, a kept pair's terms
+//                        weighed by its loss; kept against tau of k_select.hip.h's control block
 //   k_icp_covariances    thread = one point, as k_feat_normals: the neighbourhood's covariance, its smallest
 //                        eigenvector in registers, the six entries of I - (1 - epsilon) nv nv^T
 // No floating-point atomics: every sum has one order.
@@ -92,7 +92,7 @@ __device__ inline void icp_block_fold(const double (&v)[TERMS], double* __restri
 // (n_tgt x 3; Nb for point-to-plane alone); Ca / Cb / T: the covariances of the source and the target (n x 6) and the
 // current transform (generalized alone); part: gridDim.x x TERMS
 //
-// the plain terms of the pair (source point i, target point j) of METHOD: what both accumulate kernels load and form
+// the plain terms of the pair (source point i, target point j) of METHOD: what every accumulate kernel loads and forms
 template <int METHOD>
 __device__ inline void icp_pair_terms(int32_t i, int32_t j, double sqd, const double* __restrict__ q,
                                       const double* __restrict__ B, const double* __restrict__ Nb,
@@ -118,61 +118,50 @@ __device__ inline void icp_pair_terms(int32_t i, int32_t j, double sqd, const do
   }
 }
 
-template <int METHOD>
+// what the robust accumulate reads besides the plain one's arguments, by value: loss, scale and k2 = scale * scale are
+// run-time settings; ctl is the selection's control block on the device. ROBUST == false never reads it.
+struct IcpRobustArgs {
+  int loss = 0;
+  double scale = 0.0, k2 = 0.0;
+  const IcpSelect* ctl = nullptr;
+};
+
+// ROBUST: the weighted sums of clipper_hip_icp_robust over the robust layout (icp_layout_terms). A point is kept by
+// icp_kept against tau of the control block (without trimming: max_distance^2) and its plain terms are weighed by
+// icp_weight of its squared residual. Else: kept by icp_inlier, the plain terms, nothing weighed.
+template <int METHOD, bool ROBUST>
 __global__ __launch_bounds__(256) void k_icp_accumulate(const int32_t* __restrict__ oi, const double* __restrict__ od,
                                                          const double* __restrict__ q, int32_t n_src,
                                                          const double* __restrict__ B, const double* __restrict__ Nb,
                                                          const double* __restrict__ Ca, const double* __restrict__ Cb,
                                                          const double* __restrict__ T, int32_t n_tgt, double d2, double o0,
-                                                         double o1, double o2, double* __restrict__ part) {
-  constexpr int TERMS = icp_terms(METHOD);
+                                                         double o1, double o2, IcpRobustArgs rb, double* __restrict__ part) {
+  constexpr int TERMS = icp_layout_terms(METHOD, ROBUST);
   const int32_t i = static_cast<int32_t>(blockIdx.x) * 256 + static_cast<int32_t>(threadIdx.x);
-  double t[TERMS];
-#pragma unroll
-  for (int a = 0; a < TERMS; ++a) t[a] = 0.0;
-  if (i < n_src) {
-    const int32_t j = oi[i];
-    const double sqd = od[i];
-    if (icp_inlier(j, sqd, d2) && j < n_tgt) {
-      const double o[3] = {o0, o1, o2};
-      icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, t);
-    }
+  double tau = 0.0;
+  int32_t any = 0;
+  if constexpr (ROBUST) {
+    tau = rb.ctl->tau;
+    any = rb.ctl->any;
   }
-  icp_block_fold<TERMS>(t, part + static_cast<int64_t>(blockIdx.x) * TERMS);
-}
-
-// The weighted sums of clipper_hip_icp_robust: k_icp_accumulate's thread and fold over the robust layout
-// (icp_robust_terms). A point is kept by icp_kept against tau of the selection's control block on the device (without
-// trimming: max_distance^2); its plain terms are weighed by icp_weight of its squared residual. loss, scale and
-// k2 = scale * scale are run-time arguments.
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_icp_accumulate_robust(const int32_t* __restrict__ oi, const double* __restrict__ od,
-                                                                const double* __restrict__ q, int32_t n_src,
-                                                                const double* __restrict__ B, const double* __restrict__ Nb,
-                                                                const double* __restrict__ Ca, const double* __restrict__ Cb,
-                                                                const double* __restrict__ T, int32_t n_tgt, double d2,
-                                                                double o0, double o1, double o2, int loss, double scale,
-                                                                double k2, const IcpSelect* __restrict__ ctl,
-                                                                double* __restrict__ part) {
-  constexpr int TERMS = icp_robust_terms(METHOD);
-  const int32_t i = static_cast<int32_t>(blockIdx.x) * 256 + static_cast<int32_t>(threadIdx.x);
-  const double tau = ctl->tau;
-  const int32_t any = ctl->any;
   double t[TERMS];
 #pragma unroll
   for (int a = 0; a < TERMS; ++a) t[a] = 0.0;
   if (i < n_src) {
     const int32_t j = oi[i];
     const double sqd = od[i];
-    if (icp_kept(j, sqd, d2, tau, any) && j < n_tgt) {
+    bool kept;
+    if constexpr (ROBUST) kept = icp_kept(j, sqd, d2, tau, any);
+    else kept = icp_inlier(j, sqd, d2);
+    if (kept && j < n_tgt) {
       const double o[3] = {o0, o1, o2};
-      if constexpr (METHOD == ICP_POINT_TO_POINT) {
+      if constexpr (ROBUST && METHOD == ICP_POINT_TO_POINT) {
         double p[ICP_POINT_TERMS];
         icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, p);
-        icp_point_terms_weighted(p, icp_weight(loss, sqd, scale, k2), t);
+        icp_point_terms_weighted(p, icp_weight(rb.loss, sqd, rb.scale, rb.k2), t);
       } else {
         icp_pair_terms<METHOD>(i, j, sqd, q, B, Nb, Ca, Cb, T, o, t);
-        icp_plane_terms_weighted(icp_weight(loss, t[28], scale, k2), t);
+        if constexpr (ROBUST) icp_plane_terms_weighted(icp_weight(rb.loss, t[28], rb.scale, rb.k2), t);
       }
     }
   }
@@ -180,12 +169,12 @@ __global__ __launch_bounds__(256) void k_icp_accumulate_robust(const int32_t* __
 }
 
 // part: nb x TERMS; sums: TERMS doubles of device memory (the folded sums, kept for the host's evaluate); T: 16; rec and
-// history (may be null) on the device. ROBUST: the robust layout and its step (k_icp_accumulate_robust's partials).
+// history (may be null) on the device. ROBUST: the robust layout and its step (k_icp_accumulate<METHOD, true>'s partials).
 template <int METHOD, bool ROBUST>
-__device__ inline void icp_step_body(const double* __restrict__ part, int32_t nb, const IcpStop& stop, int k, double o0,
-                                     double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
-                                     IcpRecord* __restrict__ rec, double* __restrict__ history) {
-  constexpr int TERMS = ROBUST ? icp_robust_terms(METHOD) : icp_terms(METHOD);
+__global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ part, int32_t nb, IcpStop stop, int k, double o0,
+                                                   double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
+                                                   IcpRecord* __restrict__ rec, double* __restrict__ history) {
+  constexpr int TERMS = icp_layout_terms(METHOD, ROBUST);
   double v[TERMS];
 #pragma unroll
   for (int a = 0; a < TERMS; ++a) v[a] = 0.0;
@@ -212,21 +201,6 @@ __device__ inline void icp_step_body(const double* __restrict__ part, int32_t nb
     history[static_cast<int64_t>(k) * 3 + 1] = row[1];
     history[static_cast<int64_t>(k) * 3 + 2] = row[2];
   }
-}
-
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_icp_step(const double* __restrict__ part, int32_t nb, IcpStop stop, int k, double o0,
-                                                   double o1, double o2, double* __restrict__ sums, double* __restrict__ T,
-                                                   IcpRecord* __restrict__ rec, double* __restrict__ history) {
-  icp_step_body<METHOD, false>(part, nb, stop, k, o0, o1, o2, sums, T, rec, history);
-}
-
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_icp_step_robust(const double* __restrict__ part, int32_t nb, IcpStop stop, int k,
-                                                          double o0, double o1, double o2, double* __restrict__ sums,
-                                                          double* __restrict__ T, IcpRecord* __restrict__ rec,
-                                                          double* __restrict__ history) {
-  icp_step_body<METHOD, true>(part, nb, stop, k, o0, o1, o2, sums, T, rec, history);
 }
 
 // C[i] = the regularised covariance of point i (six doubles: xx, xy, xz, yy, yz, zz) over the first knn entries of its

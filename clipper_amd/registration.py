@@ -332,17 +332,12 @@ def icp(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None = None, meth
     if method not in _ICP_METHODS:
         raise ValueError(f"method must be one of {sorted(_ICP_METHODS)}")
     robust = _icp_robust_args(loss, scale, trim)
+    kw = dict(T_init=T_init, method=_ICP_METHODS[method],
+              N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T, max_distance=max_distance,
+              max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, device=device, **(robust or {}))
     with _knn_search(search):
-        if robust is not None:
-            return abi.icp_robust(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T_init=T_init,
-                                  method=_ICP_METHODS[method],
-                                  N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T,
-                                  max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness,
-                                  rel_rmse=rel_rmse, device=device, **robust)
-        return abi.icp(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, T_init=T_init,
-                       method=_ICP_METHODS[method], N_tgt=None if normals is None else np.asarray(normals, dtype=np.float64).T,
-                       max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
-                       device=device)
+        call = abi.icp if robust is None else abi.icp_robust
+        return call(np.asarray(src, dtype=np.float64).T, np.asarray(tgt, dtype=np.float64).T, **kw)
 
 
 def estimate_covariances(P: np.ndarray, knn: int = 20, radius: float = 0.0, epsilon: float = 1e-3, device: int = 0,
@@ -381,13 +376,11 @@ def icp_generalized(src: np.ndarray, tgt: np.ndarray, T_init: np.ndarray | None 
         if cv.ndim != 2 or cv.shape != (len(cloud), 6):
             raise ValueError(f"{name} must be n x 6, one row per point")
         covs.append(cv.T)
+    kw = dict(T_init=T_init, max_distance=max_distance, max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
+              device=device, **(robust or {}))
     with _knn_search(search):
-        if robust is not None:
-            return abi.icp_generalized_robust(src.T, covs[0], tgt.T, covs[1], T_init=T_init, max_distance=max_distance,
-                                              max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse,
-                                              device=device, **robust)
-        return abi.icp_generalized(src.T, covs[0], tgt.T, covs[1], T_init=T_init, max_distance=max_distance,
-                                   max_iterations=max_iterations, rel_fitness=rel_fitness, rel_rmse=rel_rmse, device=device)
+        call = abi.icp_generalized if robust is None else abi.icp_generalized_robust
+        return call(src.T, covs[0], tgt.T, covs[1], **kw)
 
 
 def evaluate_registration(src: np.ndarray, tgt: np.ndarray, T: np.ndarray | None = None, max_distance: float = 0.0,

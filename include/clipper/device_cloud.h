@@ -195,30 +195,11 @@ class DeviceCloud {
   /// registration::icp / icp_generalized of this cloud onto `target`, whose search grid is built once and kept;
   /// params.method picks the metric (the target's normals, or both clouds' covariances, must be attached)
   IcpResult icp(DeviceCloud& target, const IcpParams& params, const double* T_init = nullptr) const {
-    const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                   params.rel_fitness, params.rel_rmse};
-    IcpResult r{};
-    clipper_icp_info_t info{};
-    std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-    detail::cloud_check(clipper_hip_cloud_icp(handle(), target.handle(), T_init, &prm, nullptr, r.T, &info, nullptr, hist.data()));
-    detail::fill_icp_result(info, hist, r);
-    return r;
+    return icp_as<IcpResult>(target, params, nullptr, T_init);
   }
   /// registration::icp_robust / icp_generalized_robust on clouds: the same with a loss and / or trimming
   IcpRobustResult icp(DeviceCloud& target, const IcpParams& params, const IcpRobust& robust, const double* T_init = nullptr) const {
-    const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                   params.rel_fitness, params.rel_rmse};
-    const clipper_icp_robust_t rb{static_cast<int32_t>(robust.loss), 0, robust.scale, robust.trim};
-    IcpRobustResult r{};
-    clipper_icp_info_t info{};
-    clipper_icp_robust_info_t ri{};
-    std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-    detail::cloud_check(clipper_hip_cloud_icp(handle(), target.handle(), T_init, &prm, &rb, r.T, &info, &ri, hist.data()));
-    detail::fill_icp_result(info, hist, r);
-    r.within = ri.within;
-    r.weight_sum = ri.weight_sum;
-    r.trim_sqd = ri.trim_sqd;
-    return r;
+    return icp_as<IcpRobustResult>(target, params, &robust, T_init);
   }
   /// registration::evaluate_registration: {fitness, inlier_rmse} and the inlier count of the alignment T
   std::pair<double, double> evaluateRegistration(DeviceCloud& target, const double* T, double max_distance,
@@ -230,6 +211,12 @@ class DeviceCloud {
   }
 
  private:
+  template <typename Result>
+  Result icp_as(DeviceCloud& target, const IcpParams& params, const IcpRobust* robust, const double* T_init) const {
+    return detail::run_icp<Result>(params, robust, detail::cloud_check, [&](const detail::IcpCallArgs& a) {
+      return clipper_hip_cloud_icp(handle(), target.handle(), T_init, a.prm, a.rb, a.T_out, a.info, a.ri, a.history);
+    });
+  }
   invariants::Data matrix(int what, int rows) const {
     const int64_t n = size();
     invariants::Data out(rows > 0 ? rows : 1, n > 0 ? n : 1);

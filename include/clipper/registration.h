@@ -234,7 +234,29 @@ struct IcpResult {
   std::vector<std::array<double, 3>> history;
 };
 
+/// The losses of icp_robust and icp_generalized_robust (clipper_icp_robust_t.loss)
+enum class IcpLoss { None = 0, Huber = 1, Cauchy = 2, Tukey = 3, GemanMcClure = 4 };
+
+/// clipper_icp_robust_t: the defaults are the plain call
+struct IcpRobust {
+  IcpLoss loss = IcpLoss::None;
+  double scale = 0.0;  ///< of the residual (a distance); positive and finite with a loss
+  double trim = 1.0;   ///< in (0, 1]: the fraction kept, each iteration, of the points within max_distance
+};
+
+/// IcpResult and clipper_icp_robust_info_t (of the last history row)
+struct IcpRobustResult : IcpResult {
+  int64_t within = 0;       ///< points within max_distance, before trimming
+  double weight_sum = 0.0;  ///< the sum of the weights (point-to-point; 0 otherwise)
+  double trim_sqd = 0.0;    ///< the trimming threshold: max_distance^2 untrimmed, 0 when nothing was kept
+};
+
 namespace detail {
+inline clipper_icp_params_t icp_params_c(const IcpParams& params) {
+  return {static_cast<int32_t>(params.method), params.max_iterations, params.max_distance, params.rel_fitness, params.rel_rmse};
+}
+inline clipper_icp_robust_t icp_robust_c(const IcpRobust& r) { return {static_cast<int32_t>(r.loss), 0, r.scale, r.trim}; }
+
 /// what an ICP call left in its info and history (rows of 3 doubles), into r (T is already there)
 inline void fill_icp_result(const clipper_icp_info_t& info, const std::vector<double>& hist, IcpResult& r) {
   r.status = static_cast<IcpStatus>(info.status);
@@ -247,6 +269,56 @@ inline void fill_icp_result(const clipper_icp_info_t& info, const std::vector<do
   r.device_ms = info.device_ms;
   for (int k = 0; k <= info.iterations; ++k) r.history.push_back({hist[3 * k], hist[3 * k + 1], hist[3 * k + 2]});
 }
+inline void fill_icp_robust(const clipper_icp_robust_info_t&, IcpResult&) {}
+inline void fill_icp_robust(const clipper_icp_robust_info_t& ri, IcpRobustResult& r) {
+  r.within = ri.within;
+  r.weight_sum = ri.weight_sum;
+  r.trim_sqd = ri.trim_sqd;
+}
+
+/// a refusal of the library as the free functions throw it
+inline void icp_check(int64_t rc) {
+  if (rc < 0) throw std::invalid_argument(clipper_hip_last_error());
+}
+
+/// the arguments every ICP call of the C ABI takes besides its clouds; rb and ri are null without robust settings
+struct IcpCallArgs {
+  const clipper_icp_params_t* prm;
+  const clipper_icp_robust_t* rb;
+  double* T_out;
+  clipper_icp_info_t* info;
+  clipper_icp_robust_info_t* ri;
+  double* history;
+};
+
+/// One ICP call into a Result (IcpResult; IcpRobustResult with robust given): owns the history buffer, runs `call`
+/// (which makes the C call on an IcpCallArgs and returns its status), hands a negative status to `check` (which throws
+/// with the library's message) and fills the result.
+template <typename Result, typename Call>
+Result run_icp(const IcpParams& params, const IcpRobust* robust, void (*check)(int64_t), Call&& call) {
+  const clipper_icp_params_t prm = icp_params_c(params);
+  const clipper_icp_robust_t rb = icp_robust_c(robust ? *robust : IcpRobust{});
+  Result r{};
+  clipper_icp_info_t info{};
+  clipper_icp_robust_info_t ri{};
+  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
+  check(call(IcpCallArgs{&prm, robust ? &rb : nullptr, r.T, &info, robust ? &ri : nullptr, hist.data()}));
+  fill_icp_result(info, hist, r);
+  fill_icp_robust(ri, r);
+  return r;
+}
+
+inline void check_icp_clouds(const invariants::Data& src, const invariants::Data& tgt, const invariants::Data& normals) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  if (normals.cols() > 0 && (normals.rows() != 3 || normals.cols() != tgt.cols()))
+    throw std::invalid_argument("normals must be 3 x n, one per target point");
+}
+inline void check_gicp_clouds(const invariants::Data& src, const invariants::Data& src_cov, const invariants::Data& tgt,
+                              const invariants::Data& tgt_cov) {
+  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
+  if (src_cov.rows() != 6 || src_cov.cols() != src.cols() || tgt_cov.rows() != 6 || tgt_cov.cols() != tgt.cols())
+    throw std::invalid_argument("covariances must be 6 x n, one column per point");
+}
 }  // namespace detail
 
 /// Local refinement of a registration on the device (clipper_hip_icp): ICP of the cloud src onto tgt (3 x n) from the
@@ -255,20 +327,11 @@ inline void fill_icp_result(const clipper_icp_info_t& info, const std::vector<do
 /// same on every search route and from run to run.
 inline IcpResult icp(const invariants::Data& src, const invariants::Data& tgt, const IcpParams& params,
                      const double* T_init = nullptr, const invariants::Data& normals = invariants::Data(), int device = 0) {
-  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
-  const bool has_normals = normals.cols() > 0;
-  if (has_normals && (normals.rows() != 3 || normals.cols() != tgt.cols()))
-    throw std::invalid_argument("normals must be 3 x n, one per target point");
-  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                 params.rel_fitness, params.rel_rmse};
-  IcpResult r{};
-  clipper_icp_info_t info{};
-  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-  if (clipper_hip_icp(device, src.data(), src.cols(), tgt.data(), has_normals ? normals.data() : nullptr, tgt.cols(), T_init,
-                      &prm, r.T, &info, hist.data()))
-    throw std::invalid_argument(clipper_hip_last_error());
-  detail::fill_icp_result(info, hist, r);
-  return r;
+  detail::check_icp_clouds(src, tgt, normals);
+  return detail::run_icp<IcpResult>(params, nullptr, detail::icp_check, [&](const detail::IcpCallArgs& a) {
+    return clipper_hip_icp(device, src.data(), src.cols(), tgt.data(), normals.cols() > 0 ? normals.data() : nullptr, tgt.cols(),
+                           T_init, a.prm, a.T_out, a.info, a.history);
+  });
 }
 
 /// The per-point covariances of generalized ICP for the cloud P (3 x n) on the device
@@ -290,37 +353,12 @@ inline invariants::Data estimate_covariances(const invariants::Data& P, const Ne
 inline IcpResult icp_generalized(const invariants::Data& src, const invariants::Data& src_cov, const invariants::Data& tgt,
                                  const invariants::Data& tgt_cov, const IcpParams& params, const double* T_init = nullptr,
                                  int device = 0) {
-  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
-  if (src_cov.rows() != 6 || src_cov.cols() != src.cols() || tgt_cov.rows() != 6 || tgt_cov.cols() != tgt.cols())
-    throw std::invalid_argument("covariances must be 6 x n, one column per point");
-  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                 params.rel_fitness, params.rel_rmse};
-  IcpResult r{};
-  clipper_icp_info_t info{};
-  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-  if (clipper_hip_icp_generalized(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(), tgt.cols(),
-                                  T_init, &prm, r.T, &info, hist.data()))
-    throw std::invalid_argument(clipper_hip_last_error());
-  detail::fill_icp_result(info, hist, r);
-  return r;
+  detail::check_gicp_clouds(src, src_cov, tgt, tgt_cov);
+  return detail::run_icp<IcpResult>(params, nullptr, detail::icp_check, [&](const detail::IcpCallArgs& a) {
+    return clipper_hip_icp_generalized(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(), tgt.cols(),
+                                       T_init, a.prm, a.T_out, a.info, a.history);
+  });
 }
-
-/// The losses of icp_robust and icp_generalized_robust (clipper_icp_robust_t.loss)
-enum class IcpLoss { None = 0, Huber = 1, Cauchy = 2, Tukey = 3, GemanMcClure = 4 };
-
-/// clipper_icp_robust_t: the defaults are the plain call
-struct IcpRobust {
-  IcpLoss loss = IcpLoss::None;
-  double scale = 0.0;  ///< of the residual (a distance); positive and finite with a loss
-  double trim = 1.0;   ///< in (0, 1]: the fraction kept, each iteration, of the points within max_distance
-};
-
-/// IcpResult and clipper_icp_robust_info_t (of the last history row)
-struct IcpRobustResult : IcpResult {
-  int64_t within = 0;       ///< points within max_distance, before trimming
-  double weight_sum = 0.0;  ///< the sum of the weights (point-to-point; 0 otherwise)
-  double trim_sqd = 0.0;    ///< the trimming threshold: max_distance^2 untrimmed, 0 when nothing was kept
-};
 
 /// icp with a robust loss and / or trimming (clipper_hip_icp_robust): every pair weighs by its residual against
 /// robust.scale, and each iteration keeps the fraction robust.trim of the points within max_distance with the smallest
@@ -329,25 +367,11 @@ struct IcpRobustResult : IcpResult {
 inline IcpRobustResult icp_robust(const invariants::Data& src, const invariants::Data& tgt, const IcpParams& params,
                                   const IcpRobust& robust, const double* T_init = nullptr,
                                   const invariants::Data& normals = invariants::Data(), int device = 0) {
-  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
-  const bool has_normals = normals.cols() > 0;
-  if (has_normals && (normals.rows() != 3 || normals.cols() != tgt.cols()))
-    throw std::invalid_argument("normals must be 3 x n, one per target point");
-  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                 params.rel_fitness, params.rel_rmse};
-  const clipper_icp_robust_t rb{static_cast<int32_t>(robust.loss), 0, robust.scale, robust.trim};
-  IcpRobustResult r{};
-  clipper_icp_info_t info{};
-  clipper_icp_robust_info_t ri{};
-  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-  if (clipper_hip_icp_robust(device, src.data(), src.cols(), tgt.data(), has_normals ? normals.data() : nullptr, tgt.cols(),
-                             T_init, &prm, &rb, r.T, &info, &ri, hist.data()))
-    throw std::invalid_argument(clipper_hip_last_error());
-  detail::fill_icp_result(info, hist, r);
-  r.within = ri.within;
-  r.weight_sum = ri.weight_sum;
-  r.trim_sqd = ri.trim_sqd;
-  return r;
+  detail::check_icp_clouds(src, tgt, normals);
+  return detail::run_icp<IcpRobustResult>(params, &robust, detail::icp_check, [&](const detail::IcpCallArgs& a) {
+    return clipper_hip_icp_robust(device, src.data(), src.cols(), tgt.data(), normals.cols() > 0 ? normals.data() : nullptr,
+                                  tgt.cols(), T_init, a.prm, a.rb, a.T_out, a.info, a.ri, a.history);
+  });
 }
 
 /// icp_generalized with icp_robust's loss and trimming (clipper_hip_icp_generalized_robust); the residual a loss weighs
@@ -356,24 +380,11 @@ inline IcpRobustResult icp_generalized_robust(const invariants::Data& src, const
                                               const invariants::Data& tgt, const invariants::Data& tgt_cov,
                                               const IcpParams& params, const IcpRobust& robust,
                                               const double* T_init = nullptr, int device = 0) {
-  if (src.rows() != 3 || tgt.rows() != 3) throw std::invalid_argument("points must be 3 x n");
-  if (src_cov.rows() != 6 || src_cov.cols() != src.cols() || tgt_cov.rows() != 6 || tgt_cov.cols() != tgt.cols())
-    throw std::invalid_argument("covariances must be 6 x n, one column per point");
-  const clipper_icp_params_t prm{static_cast<int32_t>(params.method), params.max_iterations, params.max_distance,
-                                 params.rel_fitness, params.rel_rmse};
-  const clipper_icp_robust_t rb{static_cast<int32_t>(robust.loss), 0, robust.scale, robust.trim};
-  IcpRobustResult r{};
-  clipper_icp_info_t info{};
-  clipper_icp_robust_info_t ri{};
-  std::vector<double> hist(3 * (static_cast<size_t>(params.max_iterations > 0 ? params.max_iterations : 0) + 1), 0.0);
-  if (clipper_hip_icp_generalized_robust(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(),
-                                         tgt.cols(), T_init, &prm, &rb, r.T, &info, &ri, hist.data()))
-    throw std::invalid_argument(clipper_hip_last_error());
-  detail::fill_icp_result(info, hist, r);
-  r.within = ri.within;
-  r.weight_sum = ri.weight_sum;
-  r.trim_sqd = ri.trim_sqd;
-  return r;
+  detail::check_gicp_clouds(src, src_cov, tgt, tgt_cov);
+  return detail::run_icp<IcpRobustResult>(params, &robust, detail::icp_check, [&](const detail::IcpCallArgs& a) {
+    return clipper_hip_icp_generalized_robust(device, src.data(), src_cov.data(), src.cols(), tgt.data(), tgt_cov.data(),
+                                              tgt.cols(), T_init, a.prm, a.rb, a.T_out, a.info, a.ri, a.history);
+  });
 }
 
 /// fitness, inlier rmse and inlier count of an alignment (clipper_hip_evaluate_registration)
