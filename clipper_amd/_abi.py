@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_solve_staged", "clipper_hip_debug_stamps", "clipper_hip_comm_init_callback",
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
-    "clipper_hip_debug_live_resources",
+    "clipper_hip_debug_live_resources", "clipper_hip_debug_mc_budgets", "clipper_hip_debug_mc_launches",
     "clipper_hip_max_clique", "clipper_hip_core_numbers", "clipper_hip_sdp", "clipper_hip_sdp_solve",
     "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
@@ -480,6 +480,8 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_debug_occupy.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
     if hasattr(L, "clipper_hip_debug_live_resources"):  # (absent from an older build named by CLIPPER_HIP_LIB: the A/B tools)
         L.clipper_hip_debug_live_resources.argtypes = [C.POINTER(i64)]
+    L.clipper_hip_debug_mc_budgets.argtypes = [C.c_longlong, C.c_longlong]
+    L.clipper_hip_debug_mc_launches.argtypes = [vp]
     L.clipper_hip_max_clique.argtypes = [vp, C.c_int, C.c_double, C.POINTER(MaxCliqueInfo)]
     L.clipper_hip_core_numbers.argtypes = [vp, ip]
     L.clipper_hip_sdp.argtypes = [vp, C.POINTER(SdpParams), dp, dp, dp, dp, C.POINTER(SdpInfo)]
@@ -846,6 +848,10 @@ class HipClipper:
         self.soln = Solution(t=info.t_total, ifinal=0, nodes=nodes, u=np.zeros(self.m), score=-1.0)
         return nodes, _sdp_result(n, X, Y, lam, ev, nodes, info)
 
+    def mc_launches(self) -> int:
+        """Test infrastructure: the kernel launches of this context's last max_clique or core_numbers call."""
+        return int(self._check(self.L.clipper_hip_debug_mc_launches(self.h)))
+
     def core_numbers(self) -> np.ndarray:
         """The core number of every vertex of the consistency graph."""
         n = int(self.L.clipper_hip_num_associations(self.h))
@@ -1037,6 +1043,14 @@ def debug_occupy(device: int, workgroups: int, lds_bytes: int, milliseconds: flo
     rc = load_library().clipper_hip_debug_occupy(device, workgroups, lds_bytes, float(milliseconds))
     if rc < 0:
         raise ClipperError(f"clipper_hip_debug_occupy: {rc} ({_last_error()})")
+
+
+def debug_mc_budgets(peel: int = 0, wave: int = 0) -> None:
+    """Test infrastructure: the row-word budgets of the maximum-clique launches (peel; HEU / EXACT wave), process-wide;
+    values <= 0 restore the library's constants. A smaller budget means more launches and the same results."""
+    rc = load_library().clipper_hip_debug_mc_budgets(int(peel), int(wave))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip_debug_mc_budgets: {rc} ({_last_error()})")
 
 
 def debug_live_resources() -> dict:

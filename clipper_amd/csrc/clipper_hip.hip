@@ -340,6 +340,15 @@ int clipper_hip_core_numbers(clipper_hip_t* h, int32_t* core_out) try {
   return core_numbers_impl(h, core_out);
 } CLIPPER_HIP_GUARD_INT
 
+int clipper_hip_debug_mc_budgets(long long peel_budget, long long wave_budget) try {
+  return debug_mc_budgets(peel_budget, wave_budget);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_debug_mc_launches(const clipper_hip_t* h) try {
+  if (!h) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return h->mc_launches;
+} CLIPPER_HIP_GUARD_INT
+
 // ---- the semidefinite relaxation (sdp::solve, host_sdp.hpp) ------------------------------------------------------
 
 int clipper_hip_sdp(clipper_hip_t* h, const clipper_sdp_params_t* params, double* X_out, double* Y_out,

@@ -27,6 +27,9 @@ namespace {
 constexpr int64_t MC_MAX_M = 655360;           // the EXACT kernel's two LDS bitsets: 2 x 8 x ceil(m / 64) <= 160 KiB
 constexpr long long MC_PEEL_BUDGET = 1ll << 24;  // row-word operations per peel launch (~ms)
 constexpr long long MC_WAVE_BUDGET = 1ll << 18;  // row-word operations per wave and HEU / EXACT launch (~tens of ms)
+// Test infrastructure (clipper_hip_debug_mc_budgets): the budgets the launches are given, process-wide. A smaller budget
+// cuts the same work into more launches and changes no result.
+std::atomic<long long> g_mc_peel_budget{MC_PEEL_BUDGET}, g_mc_wave_budget{MC_WAVE_BUDGET};
 constexpr int MC_WAVES_PER_CU = 8;
 constexpr int MC_PEEL_ONLY = -1;  // mc_run's method for clipper_hip_core_numbers: stop after the peel, keep `core`
 using McSeeds = std::vector<std::vector<int32_t>>;  // a seeded call's vertex list per problem (empty: not seeded)
@@ -237,7 +240,7 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
     if (rounds > L.m_max) return fail(CLIPPER_HIP_E_INTERNAL, "max clique: the core peel made no progress");
     if (int rc = put_work(work)) return rc;
     hipLaunchKernelGGL(k_mc_core_peel, dim3(static_cast<unsigned>(work.size())), dim3(MC_PEEL_THREADS), lds1, st, dprobs,
-                       dwork, MC_PEEL_BUDGET);
+                       dwork, g_mc_peel_budget.load());
     if (int rc = launched()) return rc;
     if (int rc = down(g, L.ctl, ctl_end)) return rc;
     work = plan::compact(work, [&](int32_t k) { return ctl[k].removed >= ms[static_cast<size_t>(k)]; });
@@ -313,10 +316,10 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
       // `active` of every problem: one call
       HIPCHK(hipMemset2DAsync(&dctl[0].active, sizeof(McCtl), 0, sizeof(int32_t), nb, st));
       hipLaunchKernelGGL(k_mc_exact, dim3(static_cast<unsigned>(rows)), dim3(64), 2 * lds1, st, dprobs, s.D<McItem>(tab),
-                         MC_WAVE_BUDGET);
+                         g_mc_wave_budget.load());
     } else {
       hipLaunchKernelGGL(k_mc_heu, dim3(static_cast<unsigned>(rows)), dim3(64), lds1, st, dprobs, s.D<McItem>(tab),
-                         MC_WAVE_BUDGET);
+                         g_mc_wave_budget.load());
     }
     if (int rc = launched()) return rc;
     return down(g, L.ctl, ctl_end);
@@ -477,15 +480,15 @@ int mc_run(const std::vector<Ctx*>& cs, int method, double time_limit_s, hipStre
   return 0;
 }
 
-// a lone call: the driver on {h}, with h's stream, device and staging buffer
+// a lone call: the driver on {h}, with h's stream, device and staging buffer; its launch count stays in the handle
 int mc_run_one(Ctx* h, int method, double time_limit_s, McResult& r, const McSeeds* seeds = nullptr) {
   if (int rc = mc_check_scope(h)) return rc;
   if (seeds)
     if (int rc = mc_check_seed((*seeds)[0].data(), static_cast<int64_t>((*seeds)[0].size()), h->m)) return rc;
   std::vector<McResult> R;
-  int launches = 0;
   size_t fault = 0;
-  if (int rc = mc_run({h}, method, time_limit_s, h->sh[0].stream, h->sh[0].device, h->mc_stage, launches, R, fault, seeds))
+  h->mc_launches = 0;
+  if (int rc = mc_run({h}, method, time_limit_s, h->sh[0].stream, h->sh[0].device, h->mc_stage, h->mc_launches, R, fault, seeds))
     return rc;
   r = std::move(R[0]);
   return 0;
@@ -513,6 +516,13 @@ int max_clique_seeded_impl(Ctx* h, int method, double time_limit_s, const int32_
   h->nodes = r.nodes;
   if (info) *info = r.info;
   if (sinfo) *sinfo = r.seed;
+  return 0;
+}
+
+// test infrastructure: values <= 0 restore the constants
+int debug_mc_budgets(long long peel, long long wave) {
+  g_mc_peel_budget.store(peel > 0 ? peel : MC_PEEL_BUDGET);
+  g_mc_wave_budget.store(wave > 0 ? wave : MC_WAVE_BUDGET);
   return 0;
 }
 

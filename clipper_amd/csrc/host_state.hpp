@@ -350,6 +350,7 @@ struct clipper_hip_ctx {
   std::vector<int32_t> nodes;
   std::vector<double> u_host;  // the last solve's u on the host (rounding works on it)
   PinnedBuf<uint8_t> mc_stage;          // the staging buffer of this context's maximum-clique calls (host_maxclique.hpp)
+  int mc_launches = 0;                  // the kernel launches of its last lone maximum-clique call (clipper_hip_debug_mc_launches)
 
   PinnedBuf<SolveShared> host_state;  // 2 slots (multi-process snapshots)
   Event ev_poll[2];

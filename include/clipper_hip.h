@@ -951,6 +951,15 @@ int clipper_hip_debug_stamps(clipper_hip_t* h, int64_t* out, int capacity);
  * solvers' time-outs (tests/test_gpu_rv_resident.py runs it in a second process). */
 int clipper_hip_debug_occupy(int device, int workgroups, int lds_bytes, double milliseconds);
 
+/* Test infrastructure: the work budgets of the maximum-clique launches, process-wide (host_maxclique.hpp): a peel
+ * launch ends after `peel_budget` row-word operations at a round's end, a HEU / EXACT wave after `wave_budget`, and the
+ * host resumes either with the next launch. Values <= 0 restore the constants (2^24 and 2^18). A smaller budget cuts the
+ * same work into more launches and changes no result: the tests run the resume paths with budgets of 1 and 64. */
+int clipper_hip_debug_mc_budgets(long long peel_budget, long long wave_budget);
+/* Test infrastructure: the kernel launches of the context's last lone maximum-clique call (clipper_hip_max_clique,
+ * clipper_hip_max_clique_seeded, clipper_hip_core_numbers); 0 before the first. */
+int clipper_hip_debug_mc_launches(const clipper_hip_t* h);
+
 /* Test infrastructure: what this process's library holds right now, as its owning types count it
  * (csrc/host_buf.hpp): out[0] live device buffers, out[1] their bytes, out[2] live pinned host buffers, out[3] live
  * events, out[4] allocations and event creations made so far. Touches no device. */

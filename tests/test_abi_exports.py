@@ -27,6 +27,18 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} is declared in clipper_hip.h but not exported"
 
 
+def test_maxclique_debug_entry_points():
+    """the launch budgets' setter and the launch count's getter (test infrastructure): declared,
+    bound, exported; neither needs a device"""
+    new = ("clipper_hip_debug_mc_budgets", "clipper_hip_debug_mc_launches")
+    assert all(n in _declared_functions() and n in abi.EXPORTED_SYMBOLS for n in new)
+    L = abi.load_library()
+    assert len(L.clipper_hip_debug_mc_budgets.argtypes) == 2 and len(L.clipper_hip_debug_mc_launches.argtypes) == 1
+    assert L.clipper_hip_debug_mc_launches(None) == -1  # CLIPPER_HIP_E_INVALID
+    assert L.clipper_hip_debug_mc_budgets(1, 1) == 0 and L.clipper_hip_debug_mc_budgets(0, 0) == 0
+    abi.debug_mc_budgets()  # (the constants again)
+
+
 def test_struct_layouts_match_header():
     # clipper_params_t: 3 doubles, 2 int32, double, int32 (+pad), 2 doubles, 2 int32
     # (sizes / offsets printed by a C program including include/clipper_hip.h)
