@@ -544,7 +544,7 @@ int64_t clipper_hip_pairs_count(const clipper_hip_pairs_t* pairs) try {
 
 int clipper_hip_pairs_has_sqd(const clipper_hip_pairs_t* pairs) try {
   if (!pairs) return fail(CLIPPER_HIP_E_INVALID, "pairs_has_sqd: null handle");
-  return pairs->has_sqd ? 1 : 0;
+  return pairs->sqd ? 1 : 0;
 } CLIPPER_HIP_GUARD_INT
 
 int clipper_hip_pairs_download(const clipper_hip_pairs_t* pairs, int32_t* A_out, double* sqd_out) try {

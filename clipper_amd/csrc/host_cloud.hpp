@@ -2,19 +2,22 @@
 // the two owning handles of the C ABI, clipper_hip_cloud_t and clipper_hip_pairs_t, and the stages of the front end on
 // them. A cloud is n points on one device with what the stages have computed about it attached: normals, descriptors
 // (and the zero-padded image the matcher's kernel reads, made once), SPFH, covariances, the neighbour counts of each
-// stage, the members and the trace of the voxel stage that made it, and, built on first use and KEPT, what a search
-// against it needs: the grid index (grid route: ICP, the evaluation and the self-search of the normals, FPFH and
-// covariance stages all query the one index; it depends on the cloud alone, not on K) and the bounding box
-// (brute-force route). The voxel stage also writes the corners of a stage-made input cloud on first use (lo, hi,
-// has_corners), and copies its rows from the body's n-sized temporaries into exact-sized buffers of the new cloud (a
-// second pass over the output, device to device). Every stage here runs the
-// BODY its host-buffer call runs (match_lists, features_body, covariances_body, voxel_body, icp_body, stage_inputs), on
-// the cloud's buffers instead of on copies made for the call: one statement of each stage, the same bits. The filters
-// of the matcher run on the device (k_match_select: match_rules.hpp, the host's own rules). What a stage attaches is
-// valid by construction; what comes from the host is checked once, at create / set_descriptors, by the checks of the
-// host-buffer calls. All buffers are DevBufs; all work is on the default stream, and every call has waited for it when
-// it returns. A cloud is not safe for concurrent mutation. Part of clipper_hip.hip (one translation unit; included
-// there last, after host_voxel.hpp).
+// stage, the members and the trace of the voxel stage that made it, and one KnnTarget (host_knn_grid.hpp): what a search
+// against it needs, made on first use by knn_target_ensure and KEPT. That is the grid index (grid route: ICP, the
+// evaluation and the self-search of the normals, FPFH and covariance stages all query the one index; it depends on the
+// cloud alone, not on K) and the bounding box (brute-force route). An attachment is PRESENT EXACTLY WHEN ITS DevBuf IS
+// OWNED: there is no flag beside a buffer (cloud_part is the one table of what each attachment is). The voxel stage also
+// writes the corners of a stage-made input cloud on first use (lo, hi, has_corners), and copies its rows from the
+// body's n-sized temporaries into exact-sized buffers of the new cloud (a second pass over the output, device to
+// device). Every stage here runs the BODY its host-buffer call runs (match_lists, features_body, covariances_body,
+// voxel_body, icp_body, stage_inputs), on the cloud's buffers instead of on copies made for the call: one statement of
+// each stage, the same bits; the bodies read the search mode, the stages do not. A stage computes into local buffers
+// and moves them into the cloud after its wait: a refused or failed stage leaves the cloud as it was. The filters of
+// the matcher run on the device (k_match_select: match_rules.hpp, the host's own rules). What a stage attaches is valid
+// by construction; what comes from the host is checked once, at create / set_descriptors, by the checks of the
+// host-buffer calls. All work is on the default stream, and every call has waited for it when it returns. A cloud is
+// not safe for concurrent mutation. Part of clipper_hip.hip (one translation unit; included there last, after
+// host_voxel.hpp).
 #pragma once
 
 struct clipper_hip_cloud {
@@ -27,26 +30,19 @@ struct clipper_hip_cloud {
   DevBuf<double> C;              // n x 6 covariances
   DevBuf<int32_t> ncnt, fcnt, ccnt;  // n each: the neighbours kept by the normals, the FPFH and the covariance stage
   DevBuf<int32_t> vcnt, vtrace;  // n: the members of each voxel; trace_n: the row of each point of the voxel stage's input
-  bool has_N = false, has_S = false, has_C = false, has_ncnt = false, has_fcnt = false, has_vcnt = false;
   int fd = 0, fG = 0;            // coordinates per descriptor (0: none), groups of 8 of the padded image
   int64_t trace_n = 0;           // 0: no trace
   // the corners of the cloud as the voxel stage plans with them: the host's scan at create, else the device's fold
   bool has_corners = false;
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  // what a search AGAINST this cloud needs, built on first use and kept (its arrays are keep's)
-  DevTemps keep;
-  KnnGridIndex ix;
-  bool has_grid = false, has_box = false;
-  int grid_builds = 0;
-  double blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};  // the bounding box as knn_grid_bounds folds it
+  KnnTarget target{true};        // what a search AGAINST this cloud needs: it outlives the calls
 };
 
 struct clipper_hip_pairs {
   int device = 0;
   int64_t m = 0;
   DevBuf<int32_t> A;   // m x 2 column-major as clipper::Association
-  DevBuf<double> sqd;  // m
-  bool has_sqd = false;
+  DevBuf<double> sqd;  // m, or none
 };
 
 namespace {
@@ -99,7 +95,6 @@ int cloud_create(int device, const double* P, const double* N, int64_t n, Cloud*
     if (int rc = cloud_alloc(c->N, n3)) return rc;
     if (n3)
       if (int rc = copy_up(c->N.get(), N, n3, st)) return rc;
-    c->has_N = true;
   }
   if (int rc = cloud_wait(st)) return rc;  // (the caller's arrays may go once this returns)
   for (int a = 0; a < 3; ++a) c->lo[a] = lo[a], c->hi[a] = hi[a];
@@ -131,7 +126,6 @@ int pairs_create(int device, const int32_t* A, const double* sqd, int64_t m, Pai
     if (int rc = cloud_alloc(p->sqd, mm)) return rc;
     if (mm)
       if (int rc = copy_up(p->sqd.get(), sqd, mm, st)) return rc;
-    p->has_sqd = true;
   }
   if (int rc = cloud_wait(st)) return rc;
   *out = p.release();
@@ -141,7 +135,7 @@ int pairs_create(int device, const int32_t* A, const double* sqd, int64_t m, Pai
 int pairs_download(const Pairs* p, int32_t* A_out, double* sqd_out) {
   if (!p) return fail(CLIPPER_HIP_E_INVALID, "pairs_download: null handle");
   if (p->m > 0 && !A_out) return fail(CLIPPER_HIP_E_INVALID, "pairs_download: null association buffer");
-  if (sqd_out && !p->has_sqd) return fail(CLIPPER_HIP_E_STATE, "pairs_download: these pairs carry no squared distances");
+  if (sqd_out && !p->sqd) return fail(CLIPPER_HIP_E_STATE, "pairs_download: these pairs carry no squared distances");
   if (p->m == 0) return 0;
   if (int rc = use_device(p->device)) return rc;
   hipStream_t st = nullptr;
@@ -151,31 +145,41 @@ int pairs_download(const Pairs* p, int32_t* A_out, double* sqd_out) {
   return cloud_wait(st);
 }
 
+// THE TABLE of a cloud's attachments: where CLIPPER_HIP_CLOUD_<what> lies, its bytes, and whether it is there (its
+// buffer is owned). Unknown `what`: {nullptr, 0, false} with known = false.
+struct CloudPart {
+  const void* p;
+  size_t bytes;
+  bool present, known;
+};
+CloudPart cloud_part(const Cloud* c, int what) {
+  const size_t n = static_cast<size_t>(c->n);
+  const auto part = [](const auto& buf, size_t count) {
+    return CloudPart{buf.get(), count * sizeof(*buf.get()), buf.get() != nullptr, true};
+  };
+  switch (what) {
+    case CLIPPER_HIP_CLOUD_POINTS: return part(c->P, n * 3);
+    case CLIPPER_HIP_CLOUD_NORMALS: return part(c->N, n * 3);
+    case CLIPPER_HIP_CLOUD_DESCRIPTORS: return part(c->F, n * c->fd);
+    case CLIPPER_HIP_CLOUD_SPFH: return part(c->S, n * FEAT_DIM);
+    case CLIPPER_HIP_CLOUD_COVARIANCES: return part(c->C, n * 6);
+    case CLIPPER_HIP_CLOUD_NORMAL_COUNTS: return part(c->ncnt, n);
+    case CLIPPER_HIP_CLOUD_FPFH_COUNTS: return part(c->fcnt, n);
+    case CLIPPER_HIP_CLOUD_COVARIANCE_COUNTS: return part(c->ccnt, n);
+    case CLIPPER_HIP_CLOUD_VOXEL_COUNTS: return part(c->vcnt, n);
+    case CLIPPER_HIP_CLOUD_VOXEL_TRACE: return part(c->vtrace, static_cast<size_t>(c->trace_n));
+    default: return CloudPart{nullptr, 0, false, false};
+  }
+}
+
 int cloud_download(const Cloud* c, int what, void* out) {
   if (!c || !out) return fail(CLIPPER_HIP_E_INVALID, "cloud_download: null %s", !c ? "handle" : "output array");
-  const void* src = nullptr;
-  size_t bytes = 0;
-  bool there = false;
-  const size_t n = static_cast<size_t>(c->n);
-  switch (what) {
-    case CLIPPER_HIP_CLOUD_POINTS: src = c->P.get(), bytes = n * 3 * sizeof(double), there = true; break;
-    case CLIPPER_HIP_CLOUD_NORMALS: src = c->N.get(), bytes = n * 3 * sizeof(double), there = c->has_N; break;
-    case CLIPPER_HIP_CLOUD_DESCRIPTORS: src = c->F.get(), bytes = n * c->fd * sizeof(double), there = c->fd > 0; break;
-    case CLIPPER_HIP_CLOUD_SPFH: src = c->S.get(), bytes = n * FEAT_DIM * sizeof(double), there = c->has_S; break;
-    case CLIPPER_HIP_CLOUD_COVARIANCES: src = c->C.get(), bytes = n * 6 * sizeof(double), there = c->has_C; break;
-    case CLIPPER_HIP_CLOUD_NORMAL_COUNTS: src = c->ncnt.get(), bytes = n * sizeof(int32_t), there = c->has_ncnt; break;
-    case CLIPPER_HIP_CLOUD_FPFH_COUNTS: src = c->fcnt.get(), bytes = n * sizeof(int32_t), there = c->has_fcnt; break;
-    case CLIPPER_HIP_CLOUD_COVARIANCE_COUNTS: src = c->ccnt.get(), bytes = n * sizeof(int32_t), there = c->has_C; break;
-    case CLIPPER_HIP_CLOUD_VOXEL_COUNTS: src = c->vcnt.get(), bytes = n * sizeof(int32_t), there = c->has_vcnt; break;
-    case CLIPPER_HIP_CLOUD_VOXEL_TRACE:
-      src = c->vtrace.get(), bytes = static_cast<size_t>(c->trace_n) * sizeof(int32_t), there = c->trace_n > 0;
-      break;
-    default: return fail(CLIPPER_HIP_E_INVALID, "cloud_download: unknown attachment %d", what);
-  }
-  if (!there) return fail(CLIPPER_HIP_E_STATE, "cloud_download: attachment %d was never computed for this cloud", what);
-  if (bytes == 0) return 0;
+  const CloudPart a = cloud_part(c, what);
+  if (!a.known) return fail(CLIPPER_HIP_E_INVALID, "cloud_download: unknown attachment %d", what);
+  if (!a.present) return fail(CLIPPER_HIP_E_STATE, "cloud_download: attachment %d was never computed for this cloud", what);
+  if (a.bytes == 0) return 0;
   if (int rc = use_device(c->device)) return rc;
-  HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, a.p, a.bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -184,13 +188,13 @@ int cloud_info(const Cloud* c, clipper_hip_cloud_info_t* out) {
   out->n = c->n;
   out->trace_n = c->trace_n;
   out->device = c->device;
-  out->has_normals = c->has_N;
+  out->has_normals = cloud_part(c, CLIPPER_HIP_CLOUD_NORMALS).present;
   out->descriptor_dim = c->fd;
-  out->has_spfh = c->has_S;
-  out->has_covariances = c->has_C;
-  out->grid_builds = c->grid_builds;
-  for (int a = 0; a < 3; ++a) out->grid_dim[a] = c->has_grid ? c->ix.g.dim[a] : 0;
-  out->has_voxel_counts = c->has_vcnt;
+  out->has_spfh = cloud_part(c, CLIPPER_HIP_CLOUD_SPFH).present;
+  out->has_covariances = cloud_part(c, CLIPPER_HIP_CLOUD_COVARIANCES).present;
+  out->grid_builds = c->target.grid_builds;
+  for (int a = 0; a < 3; ++a) out->grid_dim[a] = c->target.ix.S ? c->target.ix.g.dim[a] : 0;
+  out->has_voxel_counts = cloud_part(c, CLIPPER_HIP_CLOUD_VOXEL_COUNTS).present;
   return 0;
 }
 
@@ -223,48 +227,7 @@ int cloud_set_descriptors(Cloud* c, const double* F, int d) {
   if (int rc = cloud_wait(st)) return rc;
   c->F = std::move(dF), c->Fpad = std::move(dFp);
   c->fd = d, c->fG = match_groups(d);
-  c->has_S = c->has_fcnt = false;  // (they described the FPFH these replace)
-  return 0;
-}
-
-// ---- the kept search structures -----------------------------------------------------------------------------------------
-
-// what a search against c by `route` needs, built at the first call and kept. The build runs in temporaries of its own;
-// only the four arrays of the index move into the cloud (32 bytes per point and 8 per cell and slab), and only once the
-// build has succeeded: a failed build leaves the cloud as it was.
-int cloud_keep_target(Cloud* c, int route, hipStream_t st) {
-  const int32_t n = static_cast<int32_t>(c->n);
-  DevTemps tmp;
-  if (route == CLIPPER_HIP_KNN_GRID) {
-    if (c->has_grid) return 0;
-    KnnGridIndex ix;
-    if (int rc = knn_grid_build(c->device, c->P.get(), n, ix, st, tmp)) return rc;
-    HIPCHK(hipStreamSynchronize(st));  // (the build's temporaries go with tmp)
-    HIPCHK(hipGetLastError());
-    const void* kept[4] = {ix.S, ix.start, ix.smin, ix.pmax};
-    for (auto& b : tmp.v)
-      for (const void* k : kept)
-        if (b.get() == k) c->keep.v.push_back(std::move(b));
-    c->ix = ix;
-    c->has_grid = true;
-    c->grid_builds++;
-    return 0;
-  }
-  if (c->has_box) return 0;
-  double lo[3], hi[3];
-  if (int rc = knn_grid_bounds(c->device, c->P.get(), n, lo, hi, st, tmp)) return rc;
-  for (int a = 0; a < 3; ++a) c->blo[a] = lo[a], c->bhi[a] = hi[a];
-  c->has_box = true;
-  return 0;
-}
-
-// the cloud's own index for a search of the cloud in itself under the route of this call: built at first use and kept
-// (grid route), or null (brute-force route: nothing to keep)
-int cloud_self_index(Cloud* c, hipStream_t st, const KnnGridIndex*& kept) {
-  kept = nullptr;
-  if (knn_route(g_knn_search.load(), 3, c->n, c->n) != CLIPPER_HIP_KNN_GRID) return 0;
-  if (int rc = cloud_keep_target(c, CLIPPER_HIP_KNN_GRID, st)) return rc;
-  kept = &c->ix;
+  c->S.reset(), c->fcnt.reset();  // (they described the FPFH these replace)
   return 0;
 }
 
@@ -296,28 +259,24 @@ int cloud_voxel_downsample(Cloud* in, double voxel_size, int want_trace, Cloud**
   c->device = in->device;
   if (n == 0) {  // an empty cloud has no voxels
     if (int rc = cloud_alloc(c->P, 0)) return rc;
-    if (in->has_N) {
+    if (in->N)
       if (int rc = cloud_alloc(c->N, 0)) return rc;
-      c->has_N = true;
-    }
     *out = c.release();
     return 0;
   }
   VoxelResult R;
-  if (int rc = voxel_body(in->device, in->P.get(), in->has_N ? in->N.get() : nullptr, n, plan, want_trace != 0, R, st, tmp))
+  if (int rc = voxel_body(in->device, in->P.get(), in->N.get(), n, plan, want_trace != 0, R, st, tmp))
     return rc;
   const size_t nr = static_cast<size_t>(R.rows);
   c->n = R.rows;
   if (int rc = cloud_alloc(c->P, nr * 3)) return rc;
   if (int rc = copy_across(c->P.get(), R.dPo, nr * 3, st)) return rc;
-  if (in->has_N) {
+  if (in->N) {
     if (int rc = cloud_alloc(c->N, nr * 3)) return rc;
     if (int rc = copy_across(c->N.get(), R.dNo, nr * 3, st)) return rc;
-    c->has_N = true;
   }
   if (int rc = cloud_alloc(c->vcnt, nr)) return rc;
   if (int rc = copy_across(c->vcnt.get(), R.dcnt, nr, st)) return rc;
-  c->has_vcnt = true;
   if (want_trace) {
     if (int rc = cloud_alloc(c->vtrace, static_cast<size_t>(n))) return rc;
     if (int rc = copy_across(c->vtrace.get(), R.dtrace, static_cast<size_t>(n), st)) return rc;
@@ -342,7 +301,7 @@ int cloud_features(Cloud* c, const char* who, const clipper_neighborhood_t* norm
   if (why.empty()) why = cf::check_count(c->n);
   if (why.empty() && normals) why = cf::check_viewpoint(viewpoint);
   if (!why.empty()) return fail(CLIPPER_HIP_E_INVALID, "%s: %s", who, why.c_str());
-  if (!normals && !c->has_N) return fail(CLIPPER_HIP_E_STATE, "%s: the cloud has no normals (estimate them first)", who);
+  if (!normals && !c->N) return fail(CLIPPER_HIP_E_STATE, "%s: the cloud has no normals (estimate them first)", who);
   if (int rc = use_device(c->device)) return rc;
   hipStream_t st = nullptr;
   const size_t nn = static_cast<size_t>(c->n);
@@ -363,22 +322,16 @@ int cloud_features(Cloud* c, const char* who, const clipper_neighborhood_t* norm
     if (int rc = cloud_alloc(dF, nn * FEAT_DIM)) return rc;
     if (int rc = cloud_alloc(dcf, nn)) return rc;
   }
-  const KnnGridIndex* kept = nullptr;
-  if (int rc = cloud_self_index(c, st, kept)) return rc;
   if (int rc = features_body(c->device, c->P.get(), c->n, normals ? &hn : nullptr, dV, features ? &hf : nullptr,
-                             normals ? dN.get() : c->N.get(), dcn.get(), dS.get(), dF.get(), dcf.get(), st, tmp, kept))
+                             normals ? dN.get() : c->N.get(), dcn.get(), dS.get(), dF.get(), dcf.get(), st, tmp, c->target))
     return rc;
   if (features)
     if (int rc = cloud_pad_descriptors(c, dF, FEAT_DIM, dFp, st)) return rc;
   if (int rc = cloud_wait(st)) return rc;
-  if (normals) {
-    c->N = std::move(dN), c->ncnt = std::move(dcn);
-    c->has_N = c->has_ncnt = true;
-  }
+  if (normals) c->N = std::move(dN), c->ncnt = std::move(dcn);
   if (features) {
     c->F = std::move(dF), c->Fpad = std::move(dFp), c->S = std::move(dS), c->fcnt = std::move(dcf);
     c->fd = FEAT_DIM, c->fG = match_groups(FEAT_DIM);
-    c->has_S = c->has_fcnt = true;
   }
   return 0;
 }
@@ -399,12 +352,9 @@ int cloud_estimate_covariances(Cloud* c, const clipper_neighborhood_t* nb, doubl
   DevTemps tmp;
   if (int rc = cloud_alloc(dC, nn * 6)) return rc;
   if (int rc = cloud_alloc(dcn, nn)) return rc;
-  const KnnGridIndex* kept = nullptr;
-  if (int rc = cloud_self_index(c, st, kept)) return rc;
-  if (int rc = covariances_body(c->device, c->P.get(), c->n, h, epsilon, dC.get(), dcn.get(), st, tmp, kept)) return rc;
+  if (int rc = covariances_body(c->device, c->P.get(), c->n, h, epsilon, dC.get(), dcn.get(), st, tmp, c->target)) return rc;
   if (int rc = cloud_wait(st)) return rc;
   c->C = std::move(dC), c->ccnt = std::move(dcn);
-  c->has_C = true;
   return 0;
 }
 
@@ -451,7 +401,6 @@ int cloud_match(const Cloud* c0, const Cloud* c1, const clipper_match_params_t* 
   std::unique_ptr<Pairs> p(new Pairs);
   p->device = c0->device;
   p->m = rows;
-  p->has_sqd = true;
   const size_t mm = static_cast<size_t>(rows);
   if (int rc = cloud_alloc(p->A, 2 * mm)) return rc;
   if (int rc = cloud_alloc(p->sqd, mm)) return rc;
@@ -494,7 +443,7 @@ int stage_inputs_clouds(Ctx* h, const Cloud* c0, const Cloud* c1, const Pairs* p
   if (c0->n < 1 || c1->n < 1) return fail(CLIPPER_HIP_E_INVALID, "stage_inputs_clouds: a cloud has no points");
   if (pairs->m < 1)
     return fail(CLIPPER_HIP_E_INVALID, "stage_inputs_clouds: no associations (the all-to-all hypothesis is not built for clouds)");
-  if (with_normals && (!c0->has_N || !c1->has_N))
+  if (with_normals && (!c0->N || !c1->N))
     return fail(CLIPPER_HIP_E_STATE, "stage_inputs_clouds: with_normals needs the normals of both clouds");
   if (int rc = use_device(device)) return rc;
   hipStream_t st = nullptr;
@@ -555,7 +504,7 @@ int cloud_gather_points(const Cloud* c, const int32_t* idx, int64_t k, double* o
 }
 
 // icp_body on two clouds: the method picks point-to-point, point-to-plane (the target's normals) or generalized (both
-// clouds' covariances); robust may be null. The target's index or bounding box is the cloud's own, kept between calls.
+// clouds' covariances); robust may be null. The target's index or bounding box is its KnnTarget's, kept between calls.
 // T_out null with corr_out: clipper_hip_cloud_evaluate_registration.
 int cloud_icp_run(const char* who, const Cloud* src, Cloud* tgt, const double* T0, const clipper_icp::Params& prm,
                   const clipper_icp::Robust* rb, double* T_out, clipper_icp_info_t* info, clipper_icp_robust_info_t* rinfo,
@@ -563,20 +512,15 @@ int cloud_icp_run(const char* who, const Cloud* src, Cloud* tgt, const double* T
   if (src->device != tgt->device)
     return fail(CLIPPER_HIP_E_INVALID, "%s: the clouds live on devices %d and %d", who, src->device, tgt->device);
   if (src->n < 1 || tgt->n < 1) return fail(CLIPPER_HIP_E_INVALID, "%s: a cloud needs at least one point", who);
-  if (prm.method == ICP_POINT_TO_PLANE && !tgt->has_N)
+  if (prm.method == ICP_POINT_TO_PLANE && !tgt->N)
     return fail(CLIPPER_HIP_E_STATE, "%s: point-to-plane needs the target's normals (estimate them first)", who);
-  if (prm.method == ICP_GENERALIZED && (!src->has_C || !tgt->has_C))
+  if (prm.method == ICP_GENERALIZED && (!src->C || !tgt->C))
     return fail(CLIPPER_HIP_E_STATE, "%s: the generalized metric needs the covariances of both clouds (estimate them first)", who);
   if (int rc = use_device(tgt->device)) return rc;
-  hipStream_t st = nullptr;
-  const int route = knn_route(g_knn_search.load(), 3, src->n, tgt->n);
-  if (int rc = cloud_keep_target(tgt, route, st)) return rc;
   IcpInputs in;
-  in.Ps = src->P.get(), in.Pt = tgt->P.get();
+  in.Ps = src->P.get(), in.Pt = tgt->P.get(), in.target = &tgt->target;
   in.Nt = prm.method == ICP_POINT_TO_PLANE ? tgt->N.get() : nullptr;
   if (prm.method == ICP_GENERALIZED) in.Cs = src->C.get(), in.Ct = tgt->C.get();
-  if (route == CLIPPER_HIP_KNN_GRID) in.index = &tgt->ix;
-  else in.lo = tgt->blo, in.hi = tgt->bhi;
   DevTemps tmp;
   return icp_body(tgt->device, in, src->n, tgt->n, T0 ? T0 : ICP_IDENTITY, prm, T_out, info, history, corr_out, rb, rinfo, tmp);
 }

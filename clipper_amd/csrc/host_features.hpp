@@ -22,19 +22,18 @@ void feat_spfh_run(const double* dP, const double* dN, int64_t n, const int32_t*
 // THE BODY of the stages, on device pointers: dP the cloud (n x 3); nnb: the neighbourhood of the normals stage, which
 // writes dN (n x 3) and dcn (n) and reads the viewpoint dV (null: none) — with nnb null dN holds the normals already;
 // fnb: the feature stage's (null: none), which writes dS, dF (n x 33 each) and dcf (n). The lists of the search join
-// tmp; everything is queued on st (the grid route of the search has waited inside it); kept as knn_lists'. The
+// tmp; everything is queued on st (the grid route of the search has waited inside it); target as knn_lists'. The
 // host-buffer calls (below) and the calls on clouds (host_cloud.hpp) both run this.
 int features_body(int device, const double* dP, int64_t n, const clipper_features::Neighborhood* nnb, const double* dV,
                   const clipper_features::Neighborhood* fnb, double* dN, int32_t* dcn, double* dS, double* dF,
-                  int32_t* dcf, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
+                  int32_t* dcf, hipStream_t st, DevTemps& tmp, KnnTarget& target) {
   const int K = clipper_features::list_k(std::max(nnb ? nnb->knn : 0, fnb ? fnb->knn : 0));
   const size_t no = static_cast<size_t>(n) * K;
   double* od = nullptr;
   int32_t* oi = nullptr;
   if (int rc = tmp.alloc(device, od, no * sizeof(double), oi, no * sizeof(int32_t))) return rc;
   // the cloud's nearest-neighbour lists in itself, K in {4, 8, 16, 32}, by the route of the process-wide mode
-  // (kept: the cloud's own grid index where its owner keeps one)
-  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, kept)) return rc;
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, target)) return rc;
   if (nnb) {
     const int use_r = nnb->radius > 0.0;
     hipLaunchKernelGGL(k_feat_normals<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
@@ -75,7 +74,9 @@ int features_run(int device, const double* P, const double* N_in, int64_t n, con
     if (int rc = copy_up(dN, N_in, n3, st)) return rc;
   if (nnb && view)
     if (int rc = copy_up(dV, view, 3, st)) return rc;
-  if (int rc = features_body(device, dP, n, nnb, (nnb && view) ? dV : nullptr, fnb, dN, dcn, dS, dF, dcf, st, tmp)) return rc;
+  KnnTarget target;  // (of this call alone)
+  if (int rc = features_body(device, dP, n, nnb, (nnb && view) ? dV : nullptr, fnb, dN, dcn, dS, dF, dcf, st, tmp, target))
+    return rc;
   if (nnb) {
     if (int rc = copy_down(N_out, dN, n3, st)) return rc;
     if (int rc = copy_down(ncnt_out, dcn, nn, st)) return rc;

@@ -1,8 +1,9 @@
 // host_icp.hpp — the driver of clipper_hip_icp, clipper_hip_icp_generalized, their robust forms and
 // clipper_hip_evaluate_registration ("ICP over a kept search grid", "Generalized ICP" and "Robust
 // losses and trimmed ICP"), and of clipper_hip_estimate_covariances, the stage that makes the generalized metric's
-// covariances. Both clouds go to the device once; the target's search index (host_knn_grid.hpp's KnnGridIndex) is
-// built once and queried every iteration with k_knn_grid<1>; the source is binned by the target's grid once, at
+// covariances. Both clouds go to the device once; the target's search index belongs to a KnnTarget (host_knn_grid.hpp:
+// the frame's local, or a cloud's own), is made by knn_target_ensure at most once and queried every iteration with
+// k_knn_grid<1>; the body reads the process-wide mode once; the source is binned by the target's grid once, at
 // T_init, and keeps that order for all iterations (a locality hint, never a correctness input: the lists go to the
 // rows of the original indices). T, the sums, the history and the candidate count stay on the device during the loop;
 // the host reads the 64-byte status record once per iteration through pinned memory to decide whether to queue the
@@ -74,13 +75,12 @@ void icp_select(const int32_t* oi, const double* od, int32_t ns, double d2, doub
 }
 
 // where the inputs of a call lie on the device: the source Ps (ns x 3), the target Pt (nt x 3), Nt: the target's normals
-// (point-to-plane alone), Cs, Ct: the covariances of the source and the target, 6 x n (generalized alone). A cloud that
-// lives on the device (host_cloud.hpp) also hands over what it keeps of the target between calls: its search index
-// (grid route) or its bounding box (brute-force route); null: made for this call, in its temporaries.
+// (point-to-plane alone), Cs, Ct: the covariances of the source and the target, 6 x n (generalized alone). target: the
+// owner of what the search against Pt keeps, its index (grid route) or its bounding box (brute-force route): a cloud's
+// (host_cloud.hpp), kept between calls, or a local of the host-buffer frame.
 struct IcpInputs {
   const double *Ps = nullptr, *Pt = nullptr, *Nt = nullptr, *Cs = nullptr, *Ct = nullptr;
-  const KnnGridIndex* index = nullptr;
-  const double *lo = nullptr, *hi = nullptr;
+  KnnTarget* target = nullptr;
 };
 
 // THE BODY of every ICP entry point and of evaluate_registration, on device pointers. Every argument has been checked
@@ -134,31 +134,14 @@ int icp_body(int device, const IcpInputs& in, int64_t ns_, int64_t nt_, const do
   HIPCHK(hipMemsetAsync(dhist, 0, nrows * 3 * sizeof(double), st));
   HIPCHK(hipMemsetAsync(dsum, 0, sizeof(unsigned long long), st));
 
-  // the target's index (grid route) or its bounding box alone: the origin of the sums is the box's centre on both
-  // routes. What the caller keeps of the target is taken as it is; else it is made here, for this call.
-  KnnGridIndex built;
-  const KnnGridIndex* ixp = in.index;
-  double lo[3], hi[3], o[3];
-  if (route == CLIPPER_HIP_KNN_GRID) {
-    if (!ixp) {
-      if (int rc = knn_grid_build(device, dPt, nt, built, st, tmp)) return rc;
-      ixp = &built;
-    }
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = ixp->lo[a];
-      hi[a] = ixp->hi[a];
-    }
-  } else if (in.lo && in.hi) {
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = in.lo[a];
-      hi[a] = in.hi[a];
-    }
-  } else if (int rc = knn_grid_bounds(device, dPt, nt, lo, hi, st, tmp)) {
-    return rc;
-  }
-  const KnnGridIndex none;
-  const KnnGridIndex& ix = ixp ? *ixp : none;  // (read on the grid route alone)
-  icp_origin(lo, hi, o);
+  // the target's index (grid route) or its bounding box alone, taken as the target holds it or made now: the origin of
+  // the sums is the centre of the index's own box on the grid route, of the target's box on the brute-force route
+  KnnTarget& target = *in.target;
+  if (int rc = knn_target_ensure(target, route, device, dPt, nt, st, tmp)) return rc;
+  const KnnGridIndex& ix = target.ix;  // (read on the grid route alone)
+  double o[3];
+  if (route == CLIPPER_HIP_KNN_GRID) icp_origin(ix.lo, ix.hi, o);
+  else icp_origin(target.lo, target.hi, o);
 
   const double d2 = prm.max_distance * prm.max_distance;
   IcpSelect sel{};  // without trimming, for the whole call: every point within max_distance is kept
@@ -274,8 +257,9 @@ int icp_run(int device, const double* Ps, int64_t ns, const double* Pt, const do
     if (int rc = copy_up(dCs, Cs, s6, st)) return rc;
     if (int rc = copy_up(dCt, Ct, t6, st)) return rc;
   }
+  KnnTarget target;  // (of this call alone)
   IcpInputs in;
-  in.Ps = dPs, in.Pt = dPt, in.Nt = dNt, in.Cs = dCs, in.Ct = dCt;
+  in.Ps = dPs, in.Pt = dPt, in.Nt = dNt, in.Cs = dCs, in.Ct = dCt, in.target = &target;
   return icp_body(device, in, ns, nt, T0, prm, T_out, info, history, corr_out, rb, rinfo, tmp);
 }
 
@@ -316,13 +300,13 @@ void icp_evaluation_out(const clipper_icp_info_t& info, double* fitness, double*
 // lists of the search join tmp; everything is queued on st. The host-buffer call (below) and the call on a cloud
 // (host_cloud.hpp) both run this.
 int covariances_body(int device, const double* dP, int64_t n, const clipper_features::Neighborhood& nb, double epsilon,
-                     double* dC, int32_t* dcn, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
+                     double* dC, int32_t* dcn, hipStream_t st, DevTemps& tmp, KnnTarget& target) {
   const int K = clipper_features::list_k(nb.knn);
   const size_t no = static_cast<size_t>(n) * K;
   double* od = nullptr;
   int32_t* oi = nullptr;
   if (int rc = tmp.alloc(device, od, no * sizeof(double), oi, no * sizeof(int32_t))) return rc;
-  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, kept)) return rc;
+  if (int rc = knn_lists(device, K, 3, dP, n, dP, n, od, oi, st, tmp, target)) return rc;
   const int use_r = nb.radius > 0.0;
   const double w = 1.0 - epsilon;
   hipLaunchKernelGGL(k_icp_covariances<>, dim3(static_cast<unsigned>(ceil_div(n, 256))), dim3(256), 0, st, dP, n, oi, od, K,
@@ -343,7 +327,8 @@ int covariances_run(int device, const double* P, int64_t n, const clipper_featur
   if (int rc = tmp.alloc(device, dP, n3 * sizeof(double), dC, n6 * sizeof(double), dcn, nn * sizeof(int32_t))) return rc;
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
   if (int rc = copy_up(dP, P, n3, st)) return rc;
-  if (int rc = covariances_body(device, dP, n, nb, epsilon, dC, dcn, st, tmp)) return rc;
+  KnnTarget target;  // (of this call alone)
+  if (int rc = covariances_body(device, dP, n, nb, epsilon, dC, dcn, st, tmp, target)) return rc;
   if (int rc = copy_down(C_out, dC, n6, st)) return rc;
   if (int rc = copy_down(count_out, dcn, nn, st)) return rc;
   HIPCHK(hipStreamSynchronize(st));  // the one wait of the call

@@ -2,10 +2,11 @@
 // the brute-force route (a scratch of partial lists, allocated once, and a query over it, as the grid route has an
 // index and a query), the one seam through which clipper_hip_knn, clipper_hip_distance_based_correspondences and the
 // three feature entry points reach either route (knn_lists), and the drivers of the first two. The seam reads the
-// process-wide mode once, picks the route, allocates that route's temporaries and queues the kernels on the caller's
-// stream; the lists are on the device when it returns. Part of clipper_hip.hip (one translation unit; included there
-// behind host_matrix_io.hpp and in front of host_match.hpp, which shares the chunk rule: the search kernels come last
-// in the code object).
+// process-wide mode once (the only read of a searching call besides icp_body's), picks the route, allocates that
+// route's temporaries and queues the kernels on the caller's stream; the lists are on the device when it returns. What
+// outlasts the search is the KnnTarget's the caller hands in (host_knn_grid.hpp), never tmp's. Part of clipper_hip.hip
+// (one translation unit; included there behind host_matrix_io.hpp and in front of host_match.hpp, which shares the
+// chunk rule: the search kernels come last in the code object).
 #pragma once
 
 #include "host_knn_grid.hpp"
@@ -66,13 +67,13 @@ int knn_brute_lists(int device, int K, int d, const double* dP0, int64_t n0, con
 
 // The seam. dP0: n0 x d, dP1: n1 x d on the device; od / oi: n0 x K, the caller's; K in {1, 2, 4, 8, 16, 32}. The
 // route's temporaries join tmp. Returns 0 with the kernels queued on st (the grid route has waited for them), or <0.
-// kept: the grid index of dP1 where its owner keeps one (read on the grid route alone; null: built for the call).
+// target: what the owner of dP1 keeps of it (a cloud's, or a local of the call); the grid route makes sure of its index.
 int knn_lists(int device, int K, int d, const double* dP0, int64_t n0, const double* dP1, int64_t n1, double* od,
-              int32_t* oi, hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
+              int32_t* oi, hipStream_t st, DevTemps& tmp, KnnTarget& target) {
   const int route = knn_route(g_knn_search.load(), d, n0, n1);
   g_knn_stats = clipper_hip_knn_stats_t{route, {0, 0, 0}, n0, 0, CLIPPER_HIP_KNN_AUTO_MIN_N, 0.0};
   const bool timed = knn_events_begin(device, st);
-  const int rc = route == CLIPPER_HIP_KNN_GRID ? knn_grid_lists(device, K, dP0, n0, dP1, n1, od, oi, st, tmp, kept)
+  const int rc = route == CLIPPER_HIP_KNN_GRID ? knn_grid_lists(device, K, dP0, n0, dP1, n1, od, oi, st, tmp, target)
                                                : knn_brute_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp);
   knn_events_end(timed && rc == 0, st);
   return rc;
@@ -95,8 +96,9 @@ int knn_search(int device, const double* P0, int64_t n0, const double* P1, int64
   hipStream_t st = nullptr;  // the default stream: a stand-alone call
   if (int rc = copy_up(dP0, P0, c0, st)) return rc;
   if (int rc = copy_up(dP1, P1, c1, st)) return rc;
-  // the route under the process-wide mode (host_knn_grid.hpp): its temporaries join tmp
-  if (int rc = knn_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp)) return rc;
+  // the route under the process-wide mode (host_knn_grid.hpp): its temporaries join tmp, its index is target's
+  KnnTarget target;
+  if (int rc = knn_lists(device, K, d, dP0, n0, dP1, n1, od, oi, st, tmp, target)) return rc;
   std::vector<double> hd(no);
   std::vector<int32_t> hi(no);
   HIPCHK(hipMemcpy(hd.data(), od, no * sizeof(double), hipMemcpyDeviceToHost));

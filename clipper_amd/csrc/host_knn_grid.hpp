@@ -1,8 +1,11 @@
 // host_knn_grid.hpp — the grid route of the nearest-neighbour search ("The grid route of the
-// search"), the process-wide mode that picks the route and the statistics of the last search. The route is a build
-// (knn_grid_build: a KnnGridIndex, kept by callers that search one cloud many times) followed by a query
-// (knn_grid_query_lists); its tables are the caller's DevTemps'. Part of clipper_hip.hip (one translation unit;
-// included by host_knn.hpp, which holds the brute-force route and the seam over the two).
+// search"), the process-wide mode that picks the route, the statistics of the last search, and the owner of what a
+// search against a cloud keeps. The route is a build (knn_grid_build) followed by a query (knn_grid_query_lists). A
+// KnnGridIndex OWNS its four arrays (move-only, never copied; readers take it by const reference); a KnnTarget owns the
+// index, the brute-force route's bounding box and the build count of one searched cloud, and knn_target_ensure is the
+// one place that makes either. Call-scoped scratch (the build's, the queries', the lists') is the caller's DevTemps'.
+// Part of clipper_hip.hip (one translation unit; included by host_knn.hpp, which holds the brute-force route and the
+// seam over the two).
 #pragma once
 
 #include "host_knn_grid_plan.hpp"
@@ -74,16 +77,18 @@ void knn_grid_bin(const double* P, int32_t n, const KnnGrid& g, int32_t ncells, 
 }
 
 // The index of a searched cloud: the cloud in cell order (S), the cells' first places (start), the grid and the slab
-// tables. Built once (bounds, plan, bin, slabs: one host wait, for the bounding box), queried any number of times; its
-// arrays are tmp's. lo / hi: the exact bounding box (min and max do not depend on the order of reduction).
+// tables. Built once (bounds, plan, bin, slabs: one host wait, for the bounding box), queried any number of times. It
+// owns its arrays; it is there exactly when S is. lo / hi: the exact bounding box (min and max do not depend on the
+// order of reduction).
 struct KnnGridIndex {
-  KgPoint* S = nullptr;
-  int32_t* start = nullptr;
-  double *smin = nullptr, *pmax = nullptr;
+  DevBuf<KgPoint> S;
+  DevBuf<int32_t> start;
+  DevBuf<double> smin, pmax;
   KnnGrid g{};
   int32_t n1 = 0, ncells = 0;
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
 };
+static_assert(!std::is_copy_constructible<KnnGridIndex>::value, "an index owns its arrays: it is moved, never copied");
 
 // the exact bounding box of the cloud dP (n x 3): k_kg_bounds' partials folded on the host. One host wait.
 int knn_grid_bounds(int device, const double* dP, int32_t n, double (&lo)[3], double (&hi)[3], hipStream_t st, DevTemps& tmp) {
@@ -106,7 +111,8 @@ int knn_grid_bounds(int device, const double* dP, int32_t n, double (&lo)[3], do
   return 0;
 }
 
-// The build: bounds, plan, bin, slabs of the searched cloud dP1. The kernels behind the one wait are queued on st.
+// The build: bounds, plan, bin, slabs of the searched cloud dP1, into ix's own arrays; the scratch joins tmp. The
+// kernels behind the one wait are queued on st. Called by knn_target_ensure alone.
 int knn_grid_build(int device, const double* dP1, int32_t n1, KnnGridIndex& ix, hipStream_t st, DevTemps& tmp) {
   if (int rc = knn_grid_bounds(device, dP1, n1, ix.lo, ix.hi, st, tmp)) return rc;
   ix.g = knn_grid_plan(ix.lo, ix.hi, n1);
@@ -117,14 +123,54 @@ int knn_grid_build(int device, const double* dP1, int32_t n1, KnnGridIndex& ix, 
   int32_t *cell = nullptr, *counts = nullptr, *cursor = nullptr;
   unsigned long long *kmin = nullptr, *kmax = nullptr;
   const size_t np = static_cast<size_t>(n1), ns = static_cast<size_t>(nslab);
-  if (int rc = tmp.alloc(device, ix.S, np * sizeof(KgPoint), cell, np * sizeof(int32_t), counts, ne * sizeof(int32_t),
-                         ix.start, ne * sizeof(int32_t), cursor, ne * sizeof(int32_t), kmin, ns * sizeof(unsigned long long),
-                         kmax, ns * sizeof(unsigned long long), ix.smin, ns * sizeof(double), ix.pmax, ns * sizeof(double)))
+  HIPCHK(ix.S.alloc(np));
+  HIPCHK(ix.start.alloc(ne));
+  HIPCHK(ix.smin.alloc(ns));
+  HIPCHK(ix.pmax.alloc(ns));
+  if (int rc = tmp.alloc(device, cell, np * sizeof(int32_t), counts, ne * sizeof(int32_t), cursor, ne * sizeof(int32_t), kmin,
+                         ns * sizeof(unsigned long long), kmax, ns * sizeof(unsigned long long)))
     return rc;
   hipLaunchKernelGGL(k_kg_init<>, dim3(static_cast<unsigned>(std::min<int64_t>(1024, ceil_div(static_cast<int64_t>(ne), 256)))),
                      dim3(256), 0, st, counts, static_cast<int64_t>(ne), kmin, kmax, static_cast<int64_t>(nslab), nullptr);
   knn_grid_bin(dP1, n1, ix.g, ix.ncells, cell, counts, ix.start, cursor, kmin, kmax, ix.S, st);
-  hipLaunchKernelGGL(k_kg_slabs<>, dim3(6), dim3(256), 0, st, ix.g, kmin, kmax, ix.smin, ix.pmax);
+  hipLaunchKernelGGL(k_kg_slabs<>, dim3(6), dim3(256), 0, st, ix.g, kmin, kmax, ix.smin.get(), ix.pmax.get());
+  return 0;
+}
+
+// What a search against one cloud keeps: the index (grid route; there when ix.S is), the bounding box as
+// knn_grid_bounds folds it (brute-force route: the origin of ICP's sums), how often the index was built, and whether
+// the target outlives the call (a cloud's, host_cloud.hpp) or is a host-buffer call's local.
+struct KnnTarget {
+  KnnGridIndex ix;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  bool has_box = false;
+  int grid_builds = 0;
+  const bool outlives_call;
+  explicit KnnTarget(bool outlives = false) : outlives_call(outlives) {}
+};
+
+// Makes sure what `route` needs of the cloud dP (n x 3) is in t: the one statement of "build it unless it is there".
+// A call-local target gains no host wait beyond the bounding box's, and the scratch joins the call's tmp. A target
+// that outlives the call takes the index only once the build's kernels have been waited for and no error is pending;
+// the scratch is released here. A failed build leaves t as it was.
+int knn_target_ensure(KnnTarget& t, int route, int device, const double* dP, int32_t n, hipStream_t st, DevTemps& tmp) {
+  DevTemps own;
+  DevTemps& scratch = t.outlives_call ? own : tmp;
+  if (route != CLIPPER_HIP_KNN_GRID) {
+    if (t.has_box) return 0;
+    if (int rc = knn_grid_bounds(device, dP, n, t.lo, t.hi, st, scratch)) return rc;
+    t.has_box = true;
+    return 0;
+  }
+  if (t.ix.S) return 0;
+  KnnGridIndex ix;
+  if (int rc = knn_grid_build(device, dP, n, ix, st, scratch)) return rc;
+  if (t.outlives_call) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+  }
+  t.ix = std::move(ix);
+  t.grid_builds++;
   return 0;
 }
 
@@ -165,17 +211,16 @@ void knn_grid_sum_visited(const int32_t* visited, int32_t n0, unsigned long long
                      visited, static_cast<int64_t>(n0), dsum);
 }
 
-// The grid route: the build over dP1, dP0 binned by the same grid (skipped when the cloud is searched in itself), the
-// query, the statistics. One host wait in the build (the bounding box comes back for the plan) and one at the end
-// (the candidate count). Temporaries are tmp's. kept: the index of dP1 its owner holds already (a cloud that lives on the
-// device, host_cloud.hpp; the index depends on the cloud alone, not on K): nothing is built, the first wait falls away.
+// The grid route: the target's index made sure of, dP0 binned by the same grid (skipped when the cloud is searched
+// in itself), the query, the statistics. One host wait in the build (the bounding box comes back for the plan; none
+// where the target holds its index already: the index depends on the cloud alone, not on K) and one at the end (the
+// candidate count). Temporaries are tmp's.
 int knn_grid_lists(int device, int K, const double* dP0, int64_t n0_, const double* dP1, int64_t n1_, double* od, int32_t* oi,
-                   hipStream_t st, DevTemps& tmp, const KnnGridIndex* kept = nullptr) {
+                   hipStream_t st, DevTemps& tmp, KnnTarget& target) {
   const int32_t n0 = static_cast<int32_t>(n0_), n1 = static_cast<int32_t>(n1_);
   const bool self = dP0 == dP1 && n0 == n1;
-  KnnGridIndex ix;
-  if (kept) ix = *kept;
-  else if (int rc = knn_grid_build(device, dP1, n1, ix, st, tmp)) return rc;
+  if (int rc = knn_target_ensure(target, CLIPPER_HIP_KNN_GRID, device, dP1, n1, st, tmp)) return rc;
+  const KnnGridIndex& ix = target.ix;
   KgPoint* Q = ix.S;
   if (!self) {
     KnnGridQueries q;
