@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "clipper_hip_read_ply_xyz", "clipper_hip_generate_synthetic_correspondences",
     "clipper_hip_precision_recall", "clipper_hip_estimate_rigid_transform", "clipper_hip_debug_occupy",
     "clipper_hip_debug_live_resources", "clipper_hip_debug_mc_budgets", "clipper_hip_debug_mc_launches",
+    "clipper_hip_debug_sub_select", "clipper_hip_debug_sub_last", "clipper_hip_debug_sub_min_m",
     "clipper_hip_max_clique", "clipper_hip_core_numbers", "clipper_hip_sdp", "clipper_hip_sdp_solve",
     "clipper_hip_batch_create", "clipper_hip_batch_destroy", "clipper_hip_batch_solve_euclidean",
     "clipper_hip_batch_solve_pointnormal", "clipper_hip_batch_get_solution", "clipper_hip_batch_get_nodes",
@@ -139,6 +140,16 @@ class ViewStats(C.Structure):
         ("sub_entries", C.c_int64), ("sub_leaves", C.c_int64), ("sub_passes", C.c_int64),
         ("sub_rows", C.c_int64), ("sub_bytes", C.c_int64), ("sub_build_ms", C.c_double),
         ("sub_pass_avg_us", C.c_double), ("sub_pass_samples", C.c_int64), ("sub_dense", C.c_int64),
+    ]
+
+
+class SubSelection(C.Structure):
+    """clipper_hip_sub_selection_t (include/clipper_hip.h): the record of a selection of the live sub-problem."""
+
+    _fields_ = [
+        ("mp", C.c_int64), ("nS", C.c_int64), ("entries", C.c_int64), ("nrows", C.c_int64),
+        ("ncol", C.c_int32), ("n0", C.c_int32), ("s", C.c_double), ("N_used", C.c_double),
+        ("built", C.c_int32), ("entered", C.c_int32),
     ]
 
 
@@ -406,6 +417,10 @@ def load_library(path: str = LIB_PATH):
     L.clipper_hip_set_subproblem.argtypes = [vp, C.c_int]
     L.clipper_hip_get_view_stats.argtypes = [vp, C.POINTER(ViewStats)]
     L.clipper_hip_view_matvec.argtypes = [vp, ip, i64, dp, dp, dp]
+    u8p = C.POINTER(C.c_uint8)
+    L.clipper_hip_debug_sub_select.argtypes = [vp, ip, i64, C.c_double, i64, ip, u8p, ip, ip, C.POINTER(SubSelection)]
+    L.clipper_hip_debug_sub_last.argtypes = [vp, i64, ip, u8p, ip, ip, ip, C.POINTER(SubSelection)]
+    L.clipper_hip_debug_sub_min_m.argtypes = [C.c_longlong]
     L.clipper_hip_knn.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, ip, dp]
     L.clipper_hip_distance_based_correspondences.argtypes = [
         C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, ip, C.c_int64]
@@ -893,6 +908,32 @@ class HipClipper:
         self._check(self.L.clipper_hip_view_matvec(self.h, _ip(rows), rows.size, _dp(x), _dp(yM), _dp(yC)))
         return yM, yC
 
+    def _sub_selection(self, call, with_rows):
+        cap = (self.m + 63) // 64 * 64
+        cnt, colmap, pos, rows = (np.full(cap, -7, dtype=np.int32) for _ in range(4))
+        flags = np.full(cap, 7, dtype=np.uint8)
+        rec = SubSelection()
+        self._check(call(cap, _ip(cnt), flags.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(colmap), _ip(pos), _ip(rows), C.byref(rec)))
+        mp = int(rec.mp)
+        out = dict(cnt=cnt[:mp].copy(), flags=flags[:mp].copy(), colmap=colmap[:rec.nS].copy(), pos=pos[:mp].copy(),
+                   mp=mp, nS=int(rec.nS), ncol=int(rec.ncol), n0=int(rec.n0), entries=int(rec.entries), s=float(rec.s),
+                   nrows=int(rec.nrows))
+        if with_rows:
+            out.update(rows=rows[:rec.nrows].copy(), N_used=float(rec.N_used), built=bool(rec.built), entered=bool(rec.entered))
+        return out
+
+    def debug_sub_select(self, rows, s: float) -> dict:
+        """Test infrastructure: the selection of the live sub-problem alone, on a row view built for `rows` (ascending)
+        with sum(u) = s: cnt, flags, pos over [0, mp), colmap over [0, nS), and the record's nS, ncol, n0, entries."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        return self._sub_selection(lambda cap, cnt, flags, colmap, pos, _rows, rec: self.L.clipper_hip_debug_sub_select(
+            self.h, _ip(rows), rows.size, float(s), cap, cnt, flags, colmap, pos, rec), False)
+
+    def debug_sub_last(self) -> dict:
+        """Test infrastructure: the last selection of the last solve — the same, and the view's rows at that moment, the
+        sum(u) the kernel read, N as handed to the decision, whether the sub-problem was built and entered."""
+        return self._sub_selection(lambda cap, *a: self.L.clipper_hip_debug_sub_last(self.h, cap, *a), True)
+
     def view_stats(self) -> ViewStats:
         t = ViewStats()
         self._check(self.L.clipper_hip_get_view_stats(self.h, C.byref(t)))
@@ -1051,6 +1092,14 @@ def debug_mc_budgets(peel: int = 0, wave: int = 0) -> None:
     rc = load_library().clipper_hip_debug_mc_budgets(int(peel), int(wave))
     if rc < 0:
         raise ClipperError(f"clipper_hip_debug_mc_budgets: {rc} ({_last_error()})")
+
+
+def debug_sub_min_m(min_m: int = 0) -> None:
+    """Test infrastructure: the size threshold of the live sub-problem, process-wide; a value <= 0 restores the initial
+    one (12 000, or CLIPPER_HIP_SUBPROBLEM_MIN_M as the process started)."""
+    rc = load_library().clipper_hip_debug_sub_min_m(int(min_m))
+    if rc < 0:
+        raise ClipperError(f"clipper_hip_debug_sub_min_m: {rc} ({_last_error()})")
 
 
 def debug_live_resources() -> dict:

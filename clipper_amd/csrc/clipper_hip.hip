@@ -665,6 +665,23 @@ int clipper_hip_view_matvec(clipper_hip_t* h, const int32_t* rows, int64_t nrows
   return view_matvec(h, rows, nrows, x, yM, yC);
 } CLIPPER_HIP_GUARD_INT
 
+int clipper_hip_debug_sub_select(clipper_hip_t* h, const int32_t* rows, int64_t nrows, double s, int64_t capacity,
+                                 int32_t* cnt, uint8_t* flags, int32_t* colmap, int32_t* pos,
+                                 clipper_hip_sub_selection_t* out) try {
+  if (!h || !rows || nrows < 1 || !out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return sub_select_rows(h, rows, nrows, s, capacity, cnt, flags, colmap, pos, out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_debug_sub_last(clipper_hip_t* h, int64_t capacity, int32_t* cnt, uint8_t* flags, int32_t* colmap,
+                               int32_t* pos, int32_t* rows, clipper_hip_sub_selection_t* out) try {
+  if (!h || !out) return fail(CLIPPER_HIP_E_INVALID, "invalid argument");
+  return sub_last_selection(h, capacity, cnt, flags, colmap, pos, rows, out);
+} CLIPPER_HIP_GUARD_INT
+
+int clipper_hip_debug_sub_min_m(long long min_m) try {
+  return debug_sub_min_m(min_m);
+} CLIPPER_HIP_GUARD_INT
+
 // ---- measurement ---------------------------------------------------------------------------
 
 int clipper_hip_set_profiling(clipper_hip_t* h, int on) try {

@@ -8,7 +8,7 @@ namespace {
 
 // ---- the compressed storage (CLIPPER_HIP_STORE_F32_CSC / _F64_CSC): groups -> slices ----------
 bool csc_applies(const Ctx* h) { return csc_possible(h) && !h->explicitC; }
-constexpr int SL_H = 1;  // sub-blocks per chunk (R = 256 rows): see k_slices.hip.h / DESIGN.md
+constexpr int SL_H = 1;  // sub-blocks per chunk (R = SL_SUB * SL_H = 128 rows): see k_slices.hip.h / DESIGN.md
 
 // the descriptor of the slices in `st` for `nrows` rows through `rowmap` (null: the rows of M)
 SliceView store_view(const SliceStore& st, const int32_t* rowmap, int64_t nrows) {

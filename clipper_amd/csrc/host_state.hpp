@@ -258,12 +258,21 @@ struct SubBufs {  // its lists: dropped as a whole (sub_free)
   DevBuf<int32_t> cnt;     // [mp] entries of every column among the view's rows (an upper bound: quads x 4)
   DevBuf<uint8_t> flags;   // [mp] 1 = the association is in the sub-problem
   DevBuf<int32_t> colmap;  // [mp] sub-problem index -> association
+  DevBuf<uint8_t> view_kept;  // [mp] the view's row flags as the last selection read them (the view's own go with the next build)
   DevBuf<int32_t> pos;     // [mp] association -> sub-problem index, or -1
   DevBuf<uint32_t> blk;    // block counts / offsets of the list build
   DevBuf<int32_t> nout_acc;  // device counter of k_sub_leave
   PinnedBuf<SubRecord> rec;  // mapped: what the selection found
 };
+struct SubLast {  // what clipper_hip_debug_sub_last reports besides the lists: the solve's last selection
+  bool valid = false;    // the lists and the record are that selection's
+  bool built = false;    // ... a sub-problem was built from it
+  bool entered = false;  // ... and the solve was handed over to that one
+  int64_t nrows = 0;     // rows of the view it counted on
+  double N_used = 0.0;   // SubProblem::ncol as it was handed to the decision
+};
 struct SubProblem : SubBufs {
+  SubLast last;
   struct clipper_hip_ctx* ctx = nullptr;        // M[S,S] as slices
   struct clipper_hip_ctx* ctx_dense = nullptr;  // M[S,S] as a dense fp32 store (where it is mostly non-zero: the inlier block)
   struct clipper_hip_ctx* use = nullptr;        // the one the solve is handed over to

@@ -10,14 +10,26 @@
 
 namespace {
 
+// The size threshold: SUB_MIN_M, or CLIPPER_HIP_SUBPROBLEM_MIN_M of the environment as the process starts, until
+// clipper_hip_debug_sub_min_m (test infrastructure) sets another one, process-wide; a value <= 0 brings the initial one back.
+std::atomic<long long> g_sub_min_m{0};
+int64_t sub_min_m() {
+  static const int64_t initial = std::getenv("CLIPPER_HIP_SUBPROBLEM_MIN_M") ? std::atoll(std::getenv("CLIPPER_HIP_SUBPROBLEM_MIN_M")) : SUB_MIN_M;
+  const long long set = g_sub_min_m.load(std::memory_order_relaxed);
+  return set > 0 ? static_cast<int64_t>(set) : initial;
+}
+int debug_sub_min_m(long long min_m) {
+  g_sub_min_m.store(min_m > 0 ? min_m : 0, std::memory_order_relaxed);
+  return 0;
+}
+
 bool sub_enabled(const Ctx* h) {
   static const bool env_off = [] {
     const char* e = std::getenv("CLIPPER_HIP_SUBPROBLEM");
     return e && std::atoi(e) == 0;
   }();
-  static const int64_t min_m = std::getenv("CLIPPER_HIP_SUBPROBLEM_MIN_M") ? std::atoll(std::getenv("CLIPPER_HIP_SUBPROBLEM_MIN_M")) : SUB_MIN_M;
   return !env_off && h->sub_mode != 1 && h->parent == nullptr && h->sh.size() == 1 && h->world == 1 && !h->multiproc &&
-         h->csc_valid && !h->explicitC && h->m >= min_m && rect_fill_possible(h);
+         h->csc_valid && !h->explicitC && h->m >= sub_min_m() && rect_fill_possible(h);
 }
 
 void sub_begin_solve(Ctx* h) {
@@ -26,6 +38,7 @@ void sub_begin_solve(Ctx* h) {
   sp.entries = 0;
   sp.sub_passes = sp.leaves = 0;
   sp.build_ms = 0.0;
+  sp.last = SubLast{};
 }
 
 void sub_free(Ctx* h) {
@@ -40,6 +53,7 @@ void sub_free(Ctx* h) {
   sp.use = nullptr;
   static_cast<SubBufs&>(sp) = SubBufs{};
   sp.ready = sp.active = false;
+  sp.last = SubLast{};
 }
 
 // the child's point tables and association pairs, gathered on the device from the parent's (stage_inputs without
@@ -76,25 +90,20 @@ int sub_stage(Ctx* h, Ctx* c, int64_t nS) {
   return 0;
 }
 
-// Called when a row view has just been built (the stream is idle but for the lift of the hold): select S, and if it
-// is small enough build its problem. Synchronous — a few launches, one wait for the selection, the fill's own wait.
-template <int V>
-int sub_prepare_v(Ctx* h) {
+// THE SELECTION (k_subproblem.hip.h), stated once for a running solve (sub_prepare) and for the stand-alone call
+// (sub_select_rows): on the view RV, whose rows `in_view` flags, with sum(u) read from `sum_u` on the device —
+// cnt[0, mp), S as flags[0, mp), its ascending list colmap[0, nS) and the inverse pos[0, mp), the record. Synchronous:
+// a few launches and one wait.
+int sub_select(Ctx* h, Shard& s, const SliceView& RV, const uint8_t* in_view, const double* sum_u) {
   SubProblem& sp = h->sub;
-  sp.ready = false;
-  Shard& s = h->sh[0];
-  RowView& v = s.rv;
-  if (!sub_enabled(h) || !v.valid || h->vres.ready || sp.entries >= SUB_MAX_ENTRIES) return 0;
-  const auto t0 = std::chrono::high_resolution_clock::now();
-  HIPCHK(hipSetDevice(s.device));
   const int64_t m = h->m, mp = h->mp;
   const int nblk = static_cast<int>(ceil_div(m, RV_BLK));
-  int rc;
-  if (static_cast<size_t>(mp) > sp.pos.cap) {  // the four lists go together, then come together (`pos` is made last: its capacity is theirs)
-    sp.cnt.reset(), sp.flags.reset(), sp.colmap.reset(), sp.pos.reset();
+  if (static_cast<size_t>(mp) > sp.pos.cap) {  // the five lists go together, then come together (`pos` is made last: its capacity is theirs)
+    sp.cnt.reset(), sp.flags.reset(), sp.colmap.reset(), sp.view_kept.reset(), sp.pos.reset();
     HIPCHK(sp.cnt.alloc(static_cast<size_t>(mp)));
     HIPCHK(sp.flags.alloc(static_cast<size_t>(mp)));
     HIPCHK(sp.colmap.alloc(static_cast<size_t>(mp)));
+    HIPCHK(sp.view_kept.alloc(static_cast<size_t>(mp)));
     HIPCHK(sp.pos.alloc(static_cast<size_t>(mp)));
   }
   HIPCHK(sp.blk.grow(static_cast<size_t>(nblk) + 2));
@@ -104,12 +113,13 @@ int sub_prepare_v(Ctx* h) {
   sp.rec->nS = -1;
   sp.rec->ncol = -1;
   sp.rec->n0 = -1;
+  sp.last = SubLast{};
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  const SliceView RV = row_view(h, s);
+  static_assert(SL_H == 1, "k_sub_colcount reads the quads of sub-block 0 alone: with more sub-blocks per chunk it has to sum all of them");
   hipLaunchKernelGGL(k_sub_begin, dim3(1), dim3(64), 0, s.stream, sp.nout_acc);
   hipLaunchKernelGGL(k_sub_colcount, dim3(static_cast<unsigned>(ceil_div(RV.ncg, 4))), dim3(256), 0, s.stream, RV, sp.cnt, mp);
-  hipLaunchKernelGGL((k_sub_flags<V>), dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream, s.st + h->par, sp.cnt,
-                     v.in_view[v.cur], m, mp, sp.flags, sp.blk, sp.nout_acc);
+  hipLaunchKernelGGL(k_sub_flags, dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream, sum_u, sp.cnt, in_view, m, mp,
+                     sp.flags, sp.blk, sp.nout_acc, sp.view_kept);
   hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(1024), 0, s.stream, sp.blk, nblk, &sp.rec.dev->nS);
   hipLaunchKernelGGL(k_rv_scatter, dim3(static_cast<unsigned>(nblk)), dim3(256), 0, s.stream, sp.flags, m, sp.blk, sp.colmap,
                      static_cast<int64_t>(sp.pos.cap), sp.pos, mp);
@@ -117,6 +127,24 @@ int sub_prepare_v(Ctx* h) {
   HIPCHK(hipStreamSynchronize(s.stream));
   HIPCHK(hipGetLastError());
   std::atomic_thread_fence(std::memory_order_acquire);
+  return 0;
+}
+
+// Called when a row view has just been built (the stream is idle but for the lift of the hold): select S, and if it
+// is small enough build its problem. Synchronous — the selection's wait, the fill's own wait.
+int sub_prepare(Ctx* h) {
+  SubProblem& sp = h->sub;
+  sp.ready = false;
+  Shard& s = h->sh[0];
+  RowView& v = s.rv;
+  if (!sub_enabled(h) || !v.valid || h->vres.ready || sp.entries >= SUB_MAX_ENTRIES) return 0;
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  HIPCHK(hipSetDevice(s.device));
+  const int64_t m = h->m;
+  int rc;
+  if ((rc = sub_select(h, s, row_view(h, s), v.in_view[v.cur], &(s.st + h->par)->s))) return rc;
+  sp.last.valid = true;  // (the read-back of test infrastructure: clipper_hip_debug_sub_last)
+  sp.last.nrows = v.nrows;
   const int64_t nS = sp.rec->nS;
   static const bool host_timing = std::getenv("CLIPPER_HIP_HOST_TIMING") != nullptr;
   if (host_timing)
@@ -167,18 +195,14 @@ int sub_prepare_v(Ctx* h) {
   // to life (it is inside S: fine) and then adds at most one entry to any column — |S \ R| on top, once and for all
   sp.ncol = static_cast<double>(std::max(1, sp.rec->ncol)) + static_cast<double>(std::max<int64_t>(0, nS - v.nrows));
   sp.ready = true;
+  sp.last.built = true;
+  sp.last.N_used = sp.ncol;
   sp.build_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
   if (host_timing)
     std::fprintf(stderr, "[sub] ready: %lld associations, density %.2f -> %s (%.1f MB), prepared in %.2f ms\n",
                  static_cast<long long>(nS), density, c->csc_valid ? "slices" : "a dense fp32 store",
                  (c->csc_valid ? static_cast<double>(c->sh[0].s_bytes) : algorithmic_gemv_bytes(c)) * 1e-6, sp.build_ms);
   return 0;
-}
-
-int sub_prepare(Ctx* h) {
-  int rc = 0;
-  dispatch_window(h, [&](auto v) { rc = sub_prepare_v<decltype(v)::value>(h); });
-  return rc;
 }
 
 // HOLD_SUB_ENTER: the decision on the full problem found that no column outside S can come back to life. The hold is lifted,
@@ -201,6 +225,7 @@ int sub_enter(Ctx* h, const SolverParams& prm) {
   c->par = 0;
   c->rv_fresh = false;
   sp.active = true;
+  sp.last.entered = true;
   sp.entries += 1;
   sp.launches_since_entry = 0;
   sp.passes_at_entry = h->mirror->n_passes;
@@ -223,6 +248,92 @@ int sub_leave(Ctx* h) {
   sp.active = false;
   sp.leaves += 1;
   if (sp.entries >= SUB_MAX_ENTRIES) sp.ready = false;
+  return 0;
+}
+
+// ---- test infrastructure: the selection by itself, and the read-back of a solve's last one ------------------------
+
+// the lists and the record of the selection the buffers hold, to the host (arrays of `capacity` >= mp elements;
+// `rows`: the view's rows, from the flags k_sub_flags kept)
+int sub_copy_out(Ctx* h, int64_t capacity, int32_t* cnt, uint8_t* flags, int32_t* colmap, int32_t* pos, int32_t* rows,
+                 clipper_hip_sub_selection_t* out) {
+  SubProblem& sp = h->sub;
+  Shard& s = h->sh[0];
+  const int64_t m = h->m, mp = h->mp;
+  if (capacity < mp) return fail(CLIPPER_HIP_E_INVALID, "capacity %lld < %lld (the padded length)", static_cast<long long>(capacity), static_cast<long long>(mp));
+  const int64_t nS = sp.rec->nS;
+  if (nS < 0 || nS > m || sp.rec->n0 < 0 || sp.rec->ncol < 0) return fail(CLIPPER_HIP_E_HIP, "sub-problem: the selection's record did not arrive");
+  HIPCHK(hipSetDevice(s.device));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  int32_t acc[8];
+  HIPCHK(hipMemcpy(acc, sp.nout_acc, sizeof(acc), hipMemcpyDeviceToHost));
+  if (cnt) HIPCHK(hipMemcpy(cnt, sp.cnt, static_cast<size_t>(mp) * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (flags) HIPCHK(hipMemcpy(flags, sp.flags, static_cast<size_t>(mp), hipMemcpyDeviceToHost));
+  if (colmap && nS > 0) HIPCHK(hipMemcpy(colmap, sp.colmap, static_cast<size_t>(nS) * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (pos) HIPCHK(hipMemcpy(pos, sp.pos, static_cast<size_t>(mp) * sizeof(int32_t), hipMemcpyDeviceToHost));
+  int64_t nrows = 0;
+  std::vector<uint8_t> kept(static_cast<size_t>(mp));
+  HIPCHK(hipMemcpy(kept.data(), sp.view_kept, kept.size(), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < mp; ++i)
+    if (kept[static_cast<size_t>(i)]) {
+      if (rows) rows[nrows] = static_cast<int32_t>(i);
+      ++nrows;
+    }
+  *out = clipper_hip_sub_selection_t{};
+  out->mp = mp;
+  out->nS = nS;
+  out->entries = static_cast<int64_t>((static_cast<unsigned long long>(sp.rec->entries_hi) << 32) | sp.rec->entries_lo);
+  out->nrows = nrows;
+  out->ncol = sp.rec->ncol;
+  out->n0 = sp.rec->n0;
+  std::memcpy(&out->s, acc + 6, sizeof(double));
+  return 0;
+}
+
+// The selection alone, on the row view of the given rows (built as view_matvec builds it) with the caller's sum(u):
+// exactly the launches a solve makes between a view's build and the decision to build the sub-problem.
+int sub_select_rows(Ctx* h, const int32_t* rows, int64_t nrows, double sum_u, int64_t capacity, int32_t* cnt, uint8_t* flags,
+                    int32_t* colmap, int32_t* pos, clipper_hip_sub_selection_t* out) {
+  if (!h->has_matrix || !h->csc_valid || !csc_single(h) || h->explicitC || h->parent != nullptr || !rect_fill_possible(h))
+    return fail(CLIPPER_HIP_E_STATE, "the selection needs slices of a matrix scored from staged points on one device");
+  const int64_t m = h->m, mp = h->mp;
+  if (!(sum_u >= 0.0) || !std::isfinite(sum_u)) return fail(CLIPPER_HIP_E_INVALID, "sum(u) must be finite and not negative");
+  if (capacity < mp) return fail(CLIPPER_HIP_E_INVALID, "capacity %lld < %lld (the padded length)", static_cast<long long>(capacity), static_cast<long long>(mp));
+  for (int64_t r = 0; r < nrows; ++r)
+    if (rows[r] < 0 || rows[r] >= m || (r > 0 && rows[r] <= rows[r - 1]))
+      return fail(CLIPPER_HIP_E_INVALID, "rows must be ascending association indices");
+  Shard& s = h->sh[0];
+  RowView& v = s.rv;
+  HIPCHK(hipSetDevice(s.device));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  v.valid = false;  // (its store is overwritten: the view of a later solve is built anew)
+  h->sub.ready = false;
+  int rc;
+  HIPCHK(v.rowmap[0].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.rowmap[1].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.in_view[0].grow(static_cast<size_t>(mp)));
+  HIPCHK(v.in_view[1].grow(static_cast<size_t>(mp)));
+  std::vector<uint8_t> in_view(static_cast<size_t>(mp), 0);
+  for (int64_t r = 0; r < nrows; ++r) in_view[static_cast<size_t>(rows[r])] = 1;
+  HIPCHK(hipMemcpyAsync(v.rowmap[0], rows, static_cast<size_t>(nrows) * sizeof(int32_t), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(v.in_view[0], in_view.data(), in_view.size(), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(s.u0, &sum_u, sizeof(double), hipMemcpyHostToDevice, s.stream));  // (sum(u) rides in the u0 buffer)
+  h->u0_staged = false;
+  if ((rc = emit_rect(h, s, v.st, v.rowmap[0], nrows, -1, -1, true, 3, "row view"))) return rc;
+  if ((rc = sub_select(h, s, store_view(v.st, v.rowmap[0], nrows), v.in_view[0], s.u0))) return rc;
+  return sub_copy_out(h, capacity, cnt, flags, colmap, pos, nullptr, out);
+}
+
+// The last selection of the last solve: its lists and record, the view's rows at that moment, and what became of it.
+int sub_last_selection(Ctx* h, int64_t capacity, int32_t* cnt, uint8_t* flags, int32_t* colmap, int32_t* pos, int32_t* rows,
+                       clipper_hip_sub_selection_t* out) {
+  const SubLast last = h->sub.last;
+  if (!last.valid) return fail(CLIPPER_HIP_E_STATE, "the last solve made no selection (or a stand-alone one has overwritten it)");
+  if (int rc = sub_copy_out(h, capacity, cnt, flags, colmap, pos, rows, out)) return rc;
+  if (out->nrows != last.nrows) return fail(CLIPPER_HIP_E_INTERNAL, "sub-problem: the kept row flags are not the view's");
+  out->built = last.built ? 1 : 0;
+  out->entered = last.entered ? 1 : 0;
+  out->N_used = last.N_used;
   return 0;
 }
 

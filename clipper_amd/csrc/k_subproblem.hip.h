@@ -49,7 +49,9 @@ namespace clipper_hip {
 constexpr double SUB_THETA = 0.4;          // N0 = SUB_THETA * sum(u)^2: columns with more entries among the view's rows join S
 
 // cnt[c] = 4 x the quads column c holds in the view's slices: at least its stored entries among the view's rows.
-// One wave per column group, a lane per column, eight headers in flight.
+// One wave per column group, a lane per column, eight headers in flight. A slice's header carries one byte of quads
+// per lane and SUB-BLOCK (k_slices.hip.h: nq[h][lane] at byte 16 + 64 h); the byte read here is sub-block 0's, which
+// is the whole chunk only while a chunk is one sub-block (SL_H == 1: asserted where the host launches this).
 __global__ __launch_bounds__(256) void k_sub_colcount(SliceView RV, int32_t* __restrict__ cnt, int64_t mp) {
   const int lane = threadIdx.x & 63;
   const int cg = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -82,17 +84,22 @@ struct SubRecord {
 
 // flags[c] = c is in S: a row of the view, or a column with more than N0 entries among the view's rows;
 // blk[b] = members of block b (the input of k_rv_scan / k_rv_scatter); rec->ncol = max count outside S
-template <int V>
-__global__ __launch_bounds__(256) void k_sub_flags(const SolverState* __restrict__ st, const int32_t* __restrict__ cnt,
+// `sum_u`: sum(u) of the current (normalised) point — SolverState::s of a running solve, a value of the caller's for the
+// stand-alone selection (host_subproblem.hpp: sub_select). What it read stays behind for the read-back of a solve's
+// last selection: the value in acc[6..7], the view's row flags in `view_kept` (the view's own are overwritten by the
+// next build).
+__global__ __launch_bounds__(256) void k_sub_flags(const double* __restrict__ sum_u, const int32_t* __restrict__ cnt,
                                                     const uint8_t* __restrict__ in_view, int64_t m, int64_t mp,
                                                     uint8_t* __restrict__ flags, uint32_t* __restrict__ blk,
                                                     int32_t* __restrict__ acc /* device: [1] = max count outside S, [2] = N0,
-                                                                                 [4..5] = the counts of the columns IN S, summed (u64) */) {
+                                                                                 [4..5] = the counts of the columns IN S, summed (u64),
+                                                                                 [6..7] = sum(u) as read (fp64) */,
+                                                    uint8_t* __restrict__ view_kept) {
   __shared__ uint32_t wsum[4];
   __shared__ int wmax[4];
   __shared__ unsigned long long wcnt[4];
   unsigned long long insum = 0;
-  const double s = st->s;  // sum(u) of the current (normalised) point
+  const double s = *sum_u;
   const double n0d = floor(SUB_THETA * s * s);
   const int n0 = n0d < 2.0e9 ? static_cast<int>(n0d) : 2000000000;
   const int64_t base = static_cast<int64_t>(blockIdx.x) * RV_BLK + threadIdx.x * 4;
@@ -101,14 +108,18 @@ __global__ __launch_bounds__(256) void k_sub_flags(const SolverState* __restrict
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int64_t i = base + k;
-    bool in = false;
+    bool in = false, row = false;
     if (i < m) {
       const int c = cnt[i];
-      in = in_view[i] != 0 || c > n0;
+      row = in_view[i] != 0;
+      in = row || c > n0;
       if (!in) mx = c > mx ? c : mx;
       else insum += static_cast<unsigned long long>(c);
     }
-    if (i < mp) flags[i] = in ? 1 : 0;
+    if (i < mp) {
+      flags[i] = in ? 1 : 0;
+      view_kept[i] = row ? 1 : 0;
+    }
     n += in ? 1u : 0u;
   }
   n = wave_sum(n);
@@ -126,7 +137,10 @@ __global__ __launch_bounds__(256) void k_sub_flags(const SolverState* __restrict
     for (int w = 1; w < 4; ++w) b = wmax[w] > b ? wmax[w] : b;
     atomicMax(&acc[1], b);  // (zeroed by k_sub_begin)
     atomicAdd(reinterpret_cast<unsigned long long*>(acc + 4), wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3]);
-    if (blockIdx.x == 0) acc[2] = n0;
+    if (blockIdx.x == 0) {
+      acc[2] = n0;
+      *reinterpret_cast<double*>(acc + 6) = s;
+    }
   }
 }
 // the counters of a selection, zeroed in front of it / handed to the host (mapped memory) behind it

@@ -960,6 +960,40 @@ int clipper_hip_debug_mc_budgets(long long peel_budget, long long wave_budget);
  * clipper_hip_max_clique_seeded, clipper_hip_core_numbers); 0 before the first. */
 int clipper_hip_debug_mc_launches(const clipper_hip_t* h);
 
+/* Test infrastructure: the selection of the live sub-problem (csrc/k_subproblem.hip.h) by itself. What a selection
+ * leaves behind: cnt[c] = 4 x the quads column c holds in the slices of the row view (at least its stored entries among
+ * the view's rows; 0 for m <= c < mp), n0 = min(floor((0.4 s) s), 2e9), S = the view's rows and every column with
+ * cnt > n0 (flags[0, mp)), its ascending list colmap[0, nS), the inverse pos[0, mp) (-1 outside S), ncol = the largest
+ * cnt outside S, entries = the sum of cnt over S. */
+typedef struct {
+  int64_t mp;       /* the padded length of cnt, flags and pos */
+  int64_t nS;
+  int64_t entries;
+  int64_t nrows;    /* rows of the view */
+  int32_t ncol;
+  int32_t n0;
+  double s;         /* sum(u) as the selection read it */
+  /* clipper_hip_debug_sub_last alone (0 from clipper_hip_debug_sub_select): */
+  double N_used;    /* N of the decision's bound, max(1, ncol) + (nS - nrows); 0 when no sub-problem was built */
+  int32_t built;    /* a sub-problem was built from this selection */
+  int32_t entered;  /* ... and the solve was handed over to it */
+} clipper_hip_sub_selection_t;
+/* On a context whose matrix lives in slices and was scored from staged points with a built-in invariant: builds the row
+ * view of `rows` (ascending association indices, as clipper_hip_view_matvec does) and runs exactly the launches a solve
+ * makes to select S, with sum(u) = s (finite, >= 0). cnt, flags and pos take `capacity` >= mp = m rounded up to 64
+ * elements, colmap as well (nS of them are written); any of the four may be NULL. */
+int clipper_hip_debug_sub_select(clipper_hip_t* h, const int32_t* rows, int64_t nrows, double s, int64_t capacity,
+                                 int32_t* cnt, uint8_t* flags, int32_t* colmap, int32_t* pos,
+                                 clipper_hip_sub_selection_t* out);
+/* The last selection the last solve made (CLIPPER_HIP_E_STATE: it made none, or clipper_hip_debug_sub_select has
+ * overwritten it since): the same lists and record, the view's rows at that moment (rows: `capacity` elements, out->nrows
+ * written), the sum(u) the kernel read, N as handed to the decision, and whether the sub-problem was built and entered. */
+int clipper_hip_debug_sub_last(clipper_hip_t* h, int64_t capacity, int32_t* cnt, uint8_t* flags, int32_t* colmap,
+                               int32_t* pos, int32_t* rows, clipper_hip_sub_selection_t* out);
+/* The size threshold of the live sub-problem (12 000, or CLIPPER_HIP_SUBPROBLEM_MIN_M as the process started),
+ * process-wide: full problems below it are not handed over. A value <= 0 restores the initial one. */
+int clipper_hip_debug_sub_min_m(long long min_m);
+
 /* Test infrastructure: what this process's library holds right now, as its owning types count it
  * (csrc/host_buf.hpp): out[0] live device buffers, out[1] their bytes, out[2] live pinned host buffers, out[3] live
  * events, out[4] allocations and event creations made so far. Touches no device. */

@@ -39,6 +39,23 @@ def test_maxclique_debug_entry_points():
     abi.debug_mc_budgets()  # (the constants again)
 
 
+def test_subproblem_debug_entry_points():
+    """the stand-alone selection, the read-back of a solve's last selection and the size threshold's setter (test
+    infrastructure): declared, bound, exported; the setter needs no device, the other two refuse
+    a null context"""
+    new = ("clipper_hip_debug_sub_select", "clipper_hip_debug_sub_last", "clipper_hip_debug_sub_min_m")
+    assert all(n in _declared_functions() and n in abi.EXPORTED_SYMBOLS for n in new)
+    L = abi.load_library()
+    assert len(L.clipper_hip_debug_sub_select.argtypes) == 10 and len(L.clipper_hip_debug_sub_last.argtypes) == 8
+    rec = abi.SubSelection()
+    assert L.clipper_hip_debug_sub_select(None, None, 0, 0.0, 0, None, None, None, None, ctypes.byref(rec)) == -1
+    assert L.clipper_hip_debug_sub_last(None, 0, None, None, None, None, None, ctypes.byref(rec)) == -1
+    assert L.clipper_hip_debug_sub_min_m(1) == 0 and L.clipper_hip_debug_sub_min_m(0) == 0
+    abi.debug_sub_min_m()  # (the initial value again)
+    # clipper_hip_sub_selection_t: 4 int64, 2 int32, 2 doubles, 2 int32
+    assert ctypes.sizeof(abi.SubSelection) == 64 and abi.SubSelection.s.offset == 40 and abi.SubSelection.built.offset == 56
+
+
 def test_struct_layouts_match_header():
     # clipper_params_t: 3 doubles, 2 int32, double, int32 (+pad), 2 doubles, 2 int32
     # (sizes / offsets printed by a C program including include/clipper_hip.h)
