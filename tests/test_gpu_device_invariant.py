@@ -14,6 +14,7 @@ import clipper_amd
 from clipper_amd import _abi as abi
 from clipper_amd import synth
 from oracle import clipper_ref as ref
+from tests.custom_invariant_model import ASYM_SRC, asym_py  # asymmetric under i <-> j, + - * / sqrt fabs only
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,17 +64,6 @@ __device__ double clipper_invariant(const double* ai, const double* aj, const do
 }
 """
 
-# A formula the built-ins cannot express: asymmetric under i <-> j, uses params, + - * / sqrt fabs only
-ASYM_SRC = r"""
-__device__ double clipper_invariant(const double* ai, const double* aj, const double* bi, const double* bj,
-                                    const double* params) {
-  double s = 0.0;
-  for (int k = 0; k < CLIPPER_D; ++k) s = s + (ai[k] - bj[k]) * (aj[k] + params[1]);
-  const double t = sqrt(fabs(s) + params[2]);
-  return params[0] / (1.0 + t) - params[3];
-}
-"""
-
 # with exp; params[2] > 0: NaN for the pairs with ai[0] - bj[0] < -params[2] (0 * sqrt of a negative number)
 EXP_SRC = r"""
 __device__ double clipper_invariant(const double* ai, const double* aj, const double* bi, const double* bj,
@@ -87,16 +77,6 @@ __device__ double clipper_invariant(const double* ai, const double* aj, const do
   return params[2] > 0 ? v + 0.0 * sqrt(ai[0] - bj[0] + params[2]) : v;
 }
 """
-
-
-def _asym_py(d, p):
-    def f(ai, aj, bi, bj):
-        s = 0.0
-        for k in range(d):
-            s = s + (float(ai[k]) - float(bj[k])) * (float(aj[k]) + p[1])
-        t = math.sqrt(abs(s) + p[2])
-        return p[0] / (1.0 + t) - p[3]
-    return f
 
 
 def _exp_py(d, p):
@@ -260,7 +240,7 @@ def test_asymmetric_formula_is_the_host_loop_bit_for_bit(clipperpy, d):
         for D1, D2, A in (_problem(rng, d, 40, 30, m=350), _problem(rng, d, 18, 15)):
             # two fills with different params on one compiled handle
             for prm in (p1, p2):
-                Mh = _host_loop(clipperpy, _asym_py(d, prm), D1, D2, A)
+                Mh = _host_loop(clipperpy, asym_py(d, prm), D1, D2, A)
                 assert np.count_nonzero(Mh) > 0 and np.count_nonzero(Mh) < Mh.size - Mh.shape[0]
                 g = abi.HipClipper(storage=abi.STORE_F64)
                 g.affinity_custom(inv, D1, D2, A, prm)
@@ -271,7 +251,7 @@ def test_asymmetric_formula_is_the_host_loop_bit_for_bit(clipperpy, d):
             g = abi.HipClipper(storage=abi.STORE_F64_CSC)
             g.stage_inputs(D1, D2, A)
             g.affinity_custom_staged(inv, p1)
-            assert np.array_equal(g.get_affinity_matrix(), _host_loop(clipperpy, _asym_py(d, p1), D1, D2, A))
+            assert np.array_equal(g.get_affinity_matrix(), _host_loop(clipperpy, asym_py(d, p1), D1, D2, A))
             g.close()
 
 
