@@ -195,43 +195,24 @@ int batch_fill_custom(Batch* b, const BatchCall& K) {
   return 0;
 }
 
-template <typename VT, int V, int E>
-int batch_launch_t(Batch* b, unsigned grid, const ResidentLaunchEntry* table, const ResidentArgs* args) {
-  auto kern = k_solve_resident_batch<VT, V, E>;
-  static std::atomic<bool> attr_set[64] = {};  // per instantiation and device
-  const int dv = (b->device >= 0 && b->device < 64) ? b->device : 0;
-  if (!attr_set[dv]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(RS_LDS_MAX)) != hipSuccess) {
-      (void)hipGetLastError();
-      return 1;  // no 159 KB of LDS for a workgroup on this device: the problems are solved alone
-    }
-    attr_set[dv] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_NT), RS_LDS_MAX, b->stream, table, args);
-  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-    if (rs_debug()) std::fprintf(stderr, "[batch] launch failed: %s\n", hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+// Where the batch kernels stand in the code object: kernels stand there in the order they are first named (and the
+// order matters to this project: host_matrix_io.hpp), which for these was V = 1 first and double beside float — not
+// the order of with_resident_instance's cases, which is the lone kernels'. This is their first naming. Nothing reads it,
+// and it is not dead: without it the batch kernels move and the code object's .text changes (the section hashes of
+// NOTEBOOK.md, "The resident solvers' host side", are the check to repeat before touching it).
+[[maybe_unused]] void (*const batch_kernel_order[])(const ResidentLaunchEntry*, const ResidentArgs*) = {
+    k_solve_resident_batch<double, 1, 1>, k_solve_resident_batch<float, 1, 1>, k_solve_resident_batch<double, 1, 2>,
+    k_solve_resident_batch<float, 1, 2>,  k_solve_resident_batch<double, 1, 4>, k_solve_resident_batch<float, 1, 4>,
+    k_solve_resident_batch<double, 2, 1>, k_solve_resident_batch<float, 2, 1>, k_solve_resident_batch<double, 2, 2>,
+    k_solve_resident_batch<float, 2, 2>,  k_solve_resident_batch<double, 2, 4>, k_solve_resident_batch<float, 2, 4>};
 
-// key = VT (0: float, 1: double) * 100 + V * 10 + E
+// key = VT (0: float, 1: double) * 100 + V * 10 + E. 1: the launch did not go out (no such instance, no 159 KB of
+// LDS for a workgroup on this device): the problems are solved alone
 int batch_launch(Batch* b, int key, unsigned grid, const ResidentLaunchEntry* table, const ResidentArgs* args) {
-  const bool f64 = key >= 100;
-  switch (key % 100) {
-#define BATCH_CASE(V, E)                                                                            \
-  case V * 10 + E:                                                                                  \
-    return f64 ? batch_launch_t<double, V, E>(b, grid, table, args) : batch_launch_t<float, V, E>(b, grid, table, args);
-    BATCH_CASE(1, 1)
-    BATCH_CASE(1, 2)
-    BATCH_CASE(1, 4)
-    BATCH_CASE(2, 1)
-    BATCH_CASE(2, 2)
-    BATCH_CASE(2, 4)
-#undef BATCH_CASE
-    default: return 1;
-  }
+  return with_resident_instance(key >= 100, key % 100 / 10, key % 10, [&](auto vt, auto v, auto e) {
+    return resident_launch(k_solve_resident_batch<decltype(vt), decltype(v)::value, decltype(e)::value>, "batch", b->device,
+                           grid, b->stream, table, args);
+  });
 }
 
 // ---- 1. every problem checked before any device work; the children made ----------------------------------------------
@@ -322,8 +303,6 @@ int batch_fill(Batch* b, const BatchCall& K) {
 
 // ---- 4./5. the resident plans, packed into launches; one wait --------------------------------------------------------
 int batch_launch_resident(Batch* b, BatchCall& K) {
-  long long timeout_override = 0;  // (the lone solve's test knob)
-  if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
   std::vector<ResidentArgs> args;
   std::vector<clipper_batch::PackItem> items;
   for (int32_t i = 0; i < K.n; ++i) {
@@ -334,8 +313,8 @@ int batch_launch_resident(Batch* b, BatchCall& K) {
     }
     if (int rc = ensure_u_pinned(c)) return rc;
     ResidentArgs a = resident_args(c, K.prm, K.P->rescale_u0 != 0);
-    // the lone solve's placement-free wait: 5 ms for one pass's sums, ten times as long on a context's first launch
-    a.timeout_ticks = timeout_override ? timeout_override : 500000ll * (c->res.epoch == 0 ? 10 : 1);
+    // (the lone solve's placement-free wait, and its test knob)
+    a.timeout_ticks = resident_timeout_ticks(c, Places::free);
     std::memset(c->mirror, 0, sizeof(HostMirror));
     K.batched.push_back(i);
     args.push_back(a);
@@ -389,7 +368,7 @@ int batch_read_back(Batch* b, BatchCall& K) {
       Batch::Result& R = b->res[static_cast<size_t>(i)];
       R.route = 1;
       solve_info(R.info, mirror_result(hm));
-      if (int rc = resident_finished(c, hm->iters)) return rc;  // (the epochs as the lone solve moves them)
+      if (int rc = c->res.x.finished(hm->iters, c->sh[0].stream)) return rc;  // (the epochs as the lone solve moves them)
       c->last_solver = 1;
       continue;
     }

@@ -1,14 +1,17 @@
-// host_plan.hpp — the two planners that run on the host between a build and its first pass, as pure
+// host_plan.hpp — the planners that run on the host between a build and its first pass, as pure
 // functions of the slice directory (no HIP, no context): plan_pass (the work list of the streaming
-// pass on the slices) and plan_resident (units, pieces and wave map of the resident solver).
-// Included by clipper_hip.hip (host_matrix.hpp / host_resident.hpp) and by tests/cpp/test_planners.cpp,
-// which checks on the CPU that every plan covers every step of every slice exactly once.
+// pass on the slices), plan_resident and plan_view_resident (units, pieces and wave map of the resident solver, on M
+// and on a row view; deal_pieces is what the two share), and the plan image (PlanLayout, plan_pack): how either
+// resident plan lies in the memory its kernel reads. Included by clipper_hip.hip and by tests/cpp/test_planners.cpp,
+// which checks on the CPU that every plan covers every step of every slice exactly once, that the plans are what
+// they were, and that an image reads back as it was packed.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace clipper_plan {
@@ -179,6 +182,61 @@ inline uint32_t slice_bound(uint32_t lq, uint32_t quad_bytes, int so) {
   return 16 + 64 + so_bytes(static_cast<int>(maxq), so) + nquads * (quad_bytes + 4u) + maxq * 12u;
 }
 
+// The pieces of unit `ui`, which holds `nsl` slices of each of its `ncgs` column groups, slice s of group cgl being
+// a chain of steps_of(cgl, s) lock-step steps: waves to column groups in proportion to their steps (every group at
+// least one), then the steps of a group's slices dealt out to its waves in equal shares (the dense slices of an
+// inlier block are chains ten times as long as the others: cut, they end together). Writes the unit's part of
+// wave_cg, npieces and pieces = slice | q0 << 8 | q1 << 16; T and nw are scratch. False: the last wave of a group
+// would need more than K.pmax pieces — the plan does not fit the piece lists.
+template <class StepsOf>
+inline bool deal_pieces(size_t ui, int ncgs, int nsl, const ResidentConsts& K, StepsOf steps_of, std::vector<int>& T,
+                        std::vector<int>& nw, std::vector<uint8_t>& npieces, std::vector<uint8_t>& wave_cg,
+                        std::vector<uint32_t>& pieces) {
+  const size_t NWV = static_cast<size_t>(K.nwv), PM = static_cast<size_t>(K.pmax);
+  T.assign(NWV, 0);
+  nw.assign(NWV, 0);
+  for (int cgl = 0; cgl < ncgs; ++cgl) {
+    for (int s = 0; s < nsl; ++s) T[cgl] += steps_of(cgl, s);
+    nw[cgl] = 1;
+  }
+  for (int spare = K.nwv - ncgs; spare > 0; --spare) {
+    int best = 0;
+    for (int cgl = 1; cgl < ncgs; ++cgl)
+      if (static_cast<int64_t>(T[cgl]) * nw[best] > static_cast<int64_t>(T[best]) * nw[cgl]) best = cgl;
+    ++nw[best];
+  }
+  int wave = 0;
+  for (int cgl = 0; cgl < ncgs; ++cgl) {
+    const int nwc = nw[cgl];
+    const int target = std::max(1, (T[cgl] + nwc - 1) / nwc);
+    int scur = 0, qcur = 0;
+    for (int sub = 0; sub < nwc; ++sub, ++wave) {
+      const size_t wv = ui * NWV + static_cast<size_t>(wave);
+      wave_cg[wv] = static_cast<uint8_t>(cgl);
+      int rem = (sub == nwc - 1) ? (1 << 30) : target, n = 0;
+      while (rem > 0 && scur < nsl) {
+        const int mq = steps_of(cgl, scur);
+        if (qcur >= mq) {
+          ++scur;
+          qcur = 0;
+          continue;
+        }
+        if (n == K.pmax) {
+          if (sub == nwc - 1) return false;
+          break;
+        }
+        const int take = std::min(rem, mq - qcur);
+        pieces[wv * PM + static_cast<size_t>(n++)] = static_cast<uint32_t>(scur) | (static_cast<uint32_t>(qcur) << 8) |
+                                                     (static_cast<uint32_t>(qcur + take) << 16);
+        qcur += take;
+        rem -= take;
+      }
+      npieces[wv] = static_cast<uint8_t>(n);
+    }
+  }
+  return true;
+}
+
 struct ResidentPlan {
   bool ok = false;
   int V = 0, E = 0, maxslots = 1;
@@ -193,9 +251,7 @@ struct ResidentPlan {
 
 // Decides whether the slices fit the resident solver and lays out its units: a column group x a range
 // of chunks sized by slice_bound() so that a unit fits the LDS beside the x table; one unit when
-// everything fits one workgroup. Then the pieces: the steps of a column group's slices dealt out to
-// its waves in equal shares (the dense slices of an inlier block are chains ten times as long as the
-// others: cut, they end together), waves to column groups in proportion to their steps.
+// everything fits one workgroup. Then the pieces of every unit (deal_pieces).
 inline void plan_resident(const uint32_t* L, int ncg, int nchunks, int64_t m, int64_t mp, int esize,
                           int max_units, int v_forced, const ResidentConsts& K, ResidentPlan& out) {
   out = ResidentPlan{};
@@ -266,53 +322,15 @@ inline void plan_resident(const uint32_t* L, int ncg, int nchunks, int64_t m, in
   out.pieces.assign(units.size() * NWV * PM, 0u);
   out.npieces.assign(units.size() * NWV, 0);
   out.wave_cg.assign(units.size() * NWV, 255);
-  std::vector<int> T(NWV), nw(NWV);
+  std::vector<int> T, nw;
   for (size_t ui = 0; ui < units.size(); ++ui) {
     const Unit& U = units[ui];
-    // waves to column groups in proportion to their steps (every group at least one)
-    std::fill(T.begin(), T.end(), 0);
-    std::fill(nw.begin(), nw.end(), 0);
-    for (int cgl = 0; cgl < U.ncgs; ++cgl) {
-      const uint32_t* lrow = L + static_cast<size_t>(U.cg0 + cgl) * nchunks;
-      for (int k = U.k0; k < U.k1; ++k) T[cgl] += static_cast<int>(lrow[k] & 255u);
-      nw[cgl] = 1;
-    }
-    for (int spare = K.nwv - U.ncgs; spare > 0; --spare) {
-      int best = 0;
-      for (int cgl = 1; cgl < U.ncgs; ++cgl)
-        if (static_cast<int64_t>(T[cgl]) * nw[best] > static_cast<int64_t>(T[best]) * nw[cgl]) best = cgl;
-      ++nw[best];
-    }
-    int wave = 0;
-    for (int cgl = 0; cgl < U.ncgs; ++cgl) {
-      const uint32_t* lrow = L + static_cast<size_t>(U.cg0 + cgl) * nchunks;
-      const int target = std::max(1, (T[cgl] + nw[cgl] - 1) / nw[cgl]);
-      int kcur = U.k0, qcur = 0;
-      for (int sub = 0; sub < nw[cgl]; ++sub, ++wave) {
-        const size_t wv = ui * NWV + static_cast<size_t>(wave);
-        out.wave_cg[wv] = static_cast<uint8_t>(cgl);
-        int rem = (sub == nw[cgl] - 1) ? (1 << 30) : target, n = 0;
-        while (rem > 0 && kcur < U.k1) {
-          const int mq = static_cast<int>(lrow[kcur] & 255u);
-          if (qcur >= mq) {
-            ++kcur;
-            qcur = 0;
-            continue;
-          }
-          if (n == K.pmax) {
-            if (sub == nw[cgl] - 1) return;  // does not fit the piece lists: streaming launches (ok stays false)
-            break;
-          }
-          const int take = std::min(rem, mq - qcur);
-          out.pieces[wv * PM + static_cast<size_t>(n++)] = static_cast<uint32_t>(kcur - U.k0) |
-                                                           (static_cast<uint32_t>(qcur) << 8) |
-                                                           (static_cast<uint32_t>(qcur + take) << 16);
-          qcur += take;
-          rem -= take;
-        }
-        out.npieces[wv] = static_cast<uint8_t>(n);
-      }
-    }
+    // (a unit's slices are the chunks [k0, k1) of its column groups)
+    auto steps_of = [&](int cgl, int s) {
+      return static_cast<int>(L[static_cast<size_t>(U.cg0 + cgl) * nchunks + U.k0 + s] & 255u);
+    };
+    if (!deal_pieces(ui, U.ncgs, U.k1 - U.k0, K, steps_of, T, nw, out.npieces, out.wave_cg, out.pieces))
+      return;  // does not fit the piece lists: streaming launches (ok stays false)
   }
   out.ok = true;
 }
@@ -344,7 +362,7 @@ struct ViewResidentPlan {
 // Units of COMPLETE columns: a unit holds every chunk of its column groups (so that a column's sums never
 // leave the workgroup), as many groups as balance the ENTRIES (the LDS gathers of a pass go with them) up
 // to `target_units` workgroups; a group whose slices exceed a unit's LDS or its share of the entries (the
-// dense inlier block) is split by LANES into equal parts. Then the pieces, as plan_resident deals them.
+// dense inlier block) is split by LANES into equal parts. Then the pieces of every unit (deal_pieces).
 // xt_fixed: bytes of LDS a unit needs besides its slices.
 inline void plan_view_resident(const uint32_t* L, int ncg, int nchunks, int esize, int target_units, int max_units,
                                uint32_t fixed_bytes, const ResidentConsts& K, ViewResidentPlan& out) {
@@ -445,13 +463,8 @@ inline void plan_view_resident(const uint32_t* L, int ncg, int nchunks, int esiz
   out.pieces.assign(units.size() * NWV * PM, 0u);
   out.npieces.assign(units.size() * NWV, 0);
   out.wave_cg.assign(units.size() * NWV, 255);
-  std::vector<int>&T = out.T, &nw = out.nw;
-  T.assign(NWV, 0);
-  nw.assign(NWV, 0);
   for (size_t ui = 0; ui < units.size(); ++ui) {
     const ViewUnit& U = units[ui];
-    std::fill(T.begin(), T.end(), 0);
-    std::fill(nw.begin(), nw.end(), 0);
     // (a packed unit: its slices are the packed ones, as long as the longest of the chunks in each)
     const int G = U.pack > 1 ? U.pack : 1;
     const int nsl = (nchunks + G - 1) / G;
@@ -461,49 +474,54 @@ inline void plan_view_resident(const uint32_t* L, int ncg, int nchunks, int esiz
       for (int g = 0; g < G && sidx * G + g < nchunks; ++g) mq = std::max(mq, static_cast<int>(lrow[sidx * G + g] & 255u));
       return mq;
     };
-    for (int cgl = 0; cgl < U.ncgs; ++cgl) {
-      for (int k = 0; k < nsl; ++k) T[static_cast<size_t>(cgl)] += steps_of(cgl, k);
-      nw[static_cast<size_t>(cgl)] = 1;
-    }
-    for (int spare = K.nwv - U.ncgs; spare > 0; --spare) {  // waves to groups in proportion to their steps
-      int best = 0;
-      for (int cgl = 1; cgl < U.ncgs; ++cgl)
-        if (static_cast<int64_t>(T[static_cast<size_t>(cgl)]) * nw[static_cast<size_t>(best)] >
-            static_cast<int64_t>(T[static_cast<size_t>(best)]) * nw[static_cast<size_t>(cgl)])
-          best = cgl;
-      ++nw[static_cast<size_t>(best)];
-    }
-    int wave = 0;
-    for (int cgl = 0; cgl < U.ncgs; ++cgl) {
-      const int nwc = nw[static_cast<size_t>(cgl)];
-      const int target = std::max(1, (T[static_cast<size_t>(cgl)] + nwc - 1) / nwc);
-      int kcur = 0, qcur = 0;
-      for (int sub = 0; sub < nwc; ++sub, ++wave) {
-        const size_t wv = ui * NWV + static_cast<size_t>(wave);
-        out.wave_cg[wv] = static_cast<uint8_t>(cgl);
-        int rem = (sub == nwc - 1) ? (1 << 30) : target, n = 0;
-        while (rem > 0 && kcur < nsl) {
-          const int mq = steps_of(cgl, kcur);
-          if (qcur >= mq) {
-            ++kcur;
-            qcur = 0;
-            continue;
-          }
-          if (n == K.pmax) {
-            if (sub == nwc - 1) return;  // does not fit the piece lists: the streaming launches keep the view
-            break;
-          }
-          const int take = std::min(rem, mq - qcur);
-          out.pieces[wv * PM + static_cast<size_t>(n++)] = static_cast<uint32_t>(kcur) | (static_cast<uint32_t>(qcur) << 8) |
-                                                           (static_cast<uint32_t>(qcur + take) << 16);
-          qcur += take;
-          rem -= take;
-        }
-        out.npieces[wv] = static_cast<uint8_t>(n);
-      }
-    }
+    if (!deal_pieces(ui, U.ncgs, nsl, K, steps_of, out.T, out.nw, out.npieces, out.wave_cg, out.pieces))
+      return;  // does not fit the piece lists: the streaming launches keep the view
   }
   out.ok = true;
+}
+
+// ---- the plan image: a resident plan as its kernel reads it ----------------------------------------------------
+// What either resident solver puts into mapped pinned memory: the unit records (UNIT_BYTES each), an optional block of
+// bytes (the resident solver's slots per column group), the piece counts, the wave map and the pieces, every array
+// at a multiple of 16 bytes, 64 bytes of tail behind the last piece. Of the pieces only those in use are written
+// (a few per wave of the pmax places: a tenth of the table, into pinned memory); the kernels read a wave's pieces
+// below its count only (rs_wave_pass), so what lies behind it is never used.
+constexpr size_t UNIT_BYTES = 32;
+static_assert(sizeof(Unit) == UNIT_BYTES && sizeof(ViewUnit) == UNIT_BYTES, "both units are records of UNIT_BYTES");
+
+struct PlanLayout {
+  size_t nunits = 0, nslots = 0, nwaves = 0, pmax = 0;  // records, bytes of the optional block, waves, pieces per wave
+  size_t off_slots = 0, off_np = 0, off_wc = 0, off_pc = 0, bytes = 0;  // bytes: of the whole image, tail included
+  // the five arrays of an image at `base` (the host's pointer or its device alias)
+  template <class U>
+  const U* units(const uint8_t* base) const { return reinterpret_cast<const U*>(base); }
+  const uint8_t* slots(const uint8_t* base) const { return base + off_slots; }
+  const uint8_t* npieces(const uint8_t* base) const { return base + off_np; }
+  const uint8_t* wave_cg(const uint8_t* base) const { return base + off_wc; }
+  const uint32_t* pieces(const uint8_t* base) const { return reinterpret_cast<const uint32_t*>(base + off_pc); }
+};
+
+inline PlanLayout plan_layout(size_t nunits, size_t nslots, size_t nwaves, size_t pmax) {
+  auto up16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
+  PlanLayout A{nunits, nslots, nwaves, pmax};
+  A.off_slots = nunits * UNIT_BYTES;
+  A.off_np = A.off_slots + up16(nslots);
+  A.off_wc = A.off_np + up16(nwaves);
+  A.off_pc = A.off_wc + up16(nwaves);
+  A.bytes = A.off_pc + nwaves * pmax * sizeof(uint32_t) + 64;
+  return A;
+}
+
+// writes a plan into the A.bytes at `base` (slots: A.nslots bytes, may be null when there are none)
+inline void plan_pack(const PlanLayout& A, uint8_t* base, const void* units, const uint8_t* slots, const uint8_t* npieces,
+                      const uint8_t* wave_cg, const uint32_t* pieces) {
+  std::memcpy(base, units, A.nunits * UNIT_BYTES);
+  if (A.nslots) std::memcpy(base + A.off_slots, slots, A.nslots);
+  std::memcpy(base + A.off_np, npieces, A.nwaves);
+  std::memcpy(base + A.off_wc, wave_cg, A.nwaves);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(base + A.off_pc);
+  for (size_t wv = 0; wv < A.nwaves; ++wv)
+    for (size_t j = 0; j < npieces[wv]; ++j) dst[wv * A.pmax + j] = pieces[wv * A.pmax + j];
 }
 
 }  // namespace clipper_plan

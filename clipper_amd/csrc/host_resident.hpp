@@ -13,6 +13,17 @@ bool rs_debug() {
   return on;
 }
 
+// A plan of either planner into a context's image (slots: the optional block, null with nslots = 0): the buffer grown
+// where the plan does not fit, the plan packed, and all of it written before a launch can read it.
+template <class Plan>
+int plan_image_store(PlanImage& im, const Plan& P, const uint8_t* slots, size_t nslots, int pmax) {
+  im.at = clipper_plan::plan_layout(P.units.size(), nslots, P.npieces.size(), static_cast<size_t>(pmax));
+  if (im.at.bytes > im.buf.cap) HIPCHK(im.buf.alloc(im.at.bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
+  clipper_plan::plan_pack(im.at, im.buf, P.units.data(), slots, P.npieces.data(), P.wave_cg.data(), P.pieces.data());
+  std::atomic_thread_fence(std::memory_order_seq_cst);
+  return 0;
+}
+
 // Decide whether the current slices fit the resident solver and lay out its units (host_plan.hpp).
 // Called when a build's directory (csc_hLq) is on the host. Leaves r.ready = false when the problem
 // does not fit.
@@ -36,96 +47,97 @@ int resident_plan(Ctx* h, Shard& s) {
                  static_cast<long long>(h->m), ncg, nchunks, static_cast<unsigned long long>(plan.total_bound),
                  plan.V, plan.E, plan.units.size(), plan.ok ? 1 : 0);
   if (!plan.ok) return 0;
-  const int V = plan.V, E = plan.E, maxslots = plan.maxslots;
-  const int64_t mp = h->mp;
-  const std::vector<clipper_plan::Unit>& units = plan.units;
-  const std::vector<uint8_t>&nsl = plan.nsl, &npieces = plan.npieces, &wave_cg = plan.wave_cg;
-  const std::vector<uint32_t>& pieces = plan.pieces;
-  const uint32_t lds_slices = plan.lds_slices, lds_total = RS_LDS_MAX;
-
   HIPCHK(hipSetDevice(s.device));
-  // plan in mapped pinned memory: the kernel reads it through the bus once, nothing is copied
-  const size_t off_nsl = units.size() * sizeof(ResidentUnit);
-  const size_t off_np = off_nsl + static_cast<size_t>(round_up(ncg, 16));
-  const size_t off_wc = off_np + static_cast<size_t>(round_up(static_cast<int64_t>(npieces.size()), 16));
-  const size_t off_pc = off_wc + static_cast<size_t>(round_up(static_cast<int64_t>(wave_cg.size()), 16));
-  const size_t plan_bytes = off_pc + pieces.size() * sizeof(uint32_t) + 64;
-  if (plan_bytes > r.host_plan.cap) HIPCHK(r.host_plan.alloc(plan_bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
-  std::memcpy(r.host_plan, units.data(), units.size() * sizeof(ResidentUnit));
-  std::memcpy(r.host_plan + off_nsl, nsl.data(), static_cast<size_t>(ncg));
-  std::memcpy(r.host_plan + off_np, npieces.data(), npieces.size());
-  std::memcpy(r.host_plan + off_wc, wave_cg.data(), wave_cg.size());
-  r.off_wc = off_wc;
-  std::memcpy(r.host_plan + off_pc, pieces.data(), pieces.size() * sizeof(uint32_t));
-  r.off_np = off_np;
-  r.off_pc = off_pc;
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-  const size_t xb_bytes = 2ull * maxslots * (V + 1) * static_cast<size_t>(mp) * 2 * sizeof(unsigned long long);
-  if (xb_bytes > r.xb.bytes()) {  // (a growth that fails leaves no buffer and no capacity: the next plan allocates)
-    HIPCHK(r.xb.alloc(xb_bytes / sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(r.xb, 0, xb_bytes, s.stream));  // no granule may carry a future epoch
-  }
+  if (int rc = plan_image_store(r.plan, plan, plan.nsl.data(), plan.nsl.size(), RS_PMAX)) return rc;
+  if (int rc = r.x.ensure(2ull * plan.maxslots * (plan.V + 1) * static_cast<size_t>(h->mp) * 2, s.stream)) return rc;
   if (!r.ctl) {  // the error word and the two counters of the one-XCD mode
     HIPCHK(r.ctl.alloc(4));
     HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), s.stream));
   }
-  r.V = V;
-  r.E = E;
-  r.nunits = static_cast<int>(units.size());
-  r.maxslots = maxslots;
-  r.lds_slices = lds_slices;
-  r.lds_total = lds_total;
+  r.V = plan.V;
+  r.E = plan.E;
+  r.nunits = static_cast<int>(plan.units.size());
+  r.maxslots = plan.maxslots;
+  r.lds_slices = plan.lds_slices;
   r.ready = true;
   return 0;
 }
 
-template <typename VT, int V, int E>
-int resident_launch_t(Ctx* h, Shard& s, const ResidentArgs& a) {
-  const unsigned grid = static_cast<unsigned>(a.xcd_mode ? 8 * a.nunits : a.nunits);
-  Resident& r = h->res;
-  auto kern = k_solve_resident<VT, V, E>;
-  static std::atomic<bool> attr_set[64] = {};  // per instantiation and device (contexts may solve concurrently)
-  const int dv = (s.device >= 0 && s.device < 64) ? s.device : 0;
-  if (!attr_set[dv]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(RS_LDS_MAX));
-    if (e != hipSuccess) {
+// One launch of a kernel of the resident family (k_solve_resident, k_solve_resident_batch, k_solve_view_resident): a
+// workgroup of RS_NT threads with the whole dynamic LDS of a CU. 1: this device does not give a workgroup 159 KB of
+// LDS, or refuses the launch — not an error: the caller goes on without the resident solver.
+template <typename... P, typename... A>
+int resident_launch(void (*kern)(P...), const char* who, int device, unsigned grid, hipStream_t stream, const A&... args) {
+  static_assert(RVR_NT == RS_NT, "the view kernel's workgroup is the resident kernel's");
+  const void* fn = reinterpret_cast<const void*>(kern);
+  if (!raise_dynamic_lds(fn, device, static_cast<int>(RS_LDS_MAX))) {
+    if (rs_debug()) {  // (asked once more, for the runtime's reason: raise_dynamic_lds keeps none)
+      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(RS_LDS_MAX));
       (void)hipGetLastError();
-      if (rs_debug()) {
-        hipFuncAttributes fa{};
-        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-        int optin = 0, perblk = 0;
-        (void)hipDeviceGetAttribute(&perblk, hipDeviceAttributeMaxSharedMemoryPerBlock, s.device);
-        (void)hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, s.device);
-        std::fprintf(stderr, "[resident] hipFuncSetAttribute: %s (static LDS %zu, max dynamic %d, device per block %d, optin %d)\n",
-                     hipGetErrorString(e), fa.sharedSizeBytes, fa.maxDynamicSharedSizeBytes, perblk, optin);
-      }
-      return 1;  // this device does not give a workgroup 159 KB of LDS: not an error, no resident solver
+      hipFuncAttributes fa{};
+      (void)hipFuncGetAttributes(&fa, fn);
+      int optin = 0, perblk = 0;
+      (void)hipDeviceGetAttribute(&perblk, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+      (void)hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, device);
+      std::fprintf(stderr, "[%s] hipFuncSetAttribute: %s (static LDS %zu, max dynamic %d, device per block %d, optin %d)\n",
+                   who, hipGetErrorString(e), fa.sharedSizeBytes, fa.maxDynamicSharedSizeBytes, perblk, optin);
     }
-    attr_set[dv] = true;
+    return 1;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_NT), r.lds_total, s.stream, a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_NT), RS_LDS_MAX, stream, args...);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {  // refused: the streaming launches take over
-    if (rs_debug()) std::fprintf(stderr, "[resident] launch failed: %s\n", hipGetErrorString(e));
+    if (rs_debug()) std::fprintf(stderr, "[%s] launch failed: %s\n", who, hipGetErrorString(e));
     return 1;
   }
   return 0;
 }
 
-template <typename VT>
-int resident_launch_v(Ctx* h, Shard& s, const ResidentArgs& a) {
-  const Resident& r = h->res;
-  switch (r.V * 10 + r.E) {
-    case 21: return resident_launch_t<VT, 2, 1>(h, s, a);
-    case 22: return resident_launch_t<VT, 2, 2>(h, s, a);
-    case 24: return resident_launch_t<VT, 2, 4>(h, s, a);
-    case 11: return resident_launch_t<VT, 1, 1>(h, s, a);
-    case 12: return resident_launch_t<VT, 1, 2>(h, s, a);
-    case 14: return resident_launch_t<VT, 1, 4>(h, s, a);
-    default: return 1;
-  }
+// (value type, V, E) -> f(value type tag, V, E as integral constants), which names its kernel's instance; 1: there is
+// none. The lone launch (k_solve_resident) and the batched one (k_solve_resident_batch) both come through here.
+template <typename F>
+int with_resident_instance(bool f64, int V, int E, F&& f) {
+  auto of = [&](auto vt) {
+    using std::integral_constant;
+    switch (V * 10 + E) {
+      case 21: return f(vt, integral_constant<int, 2>{}, integral_constant<int, 1>{});
+      case 22: return f(vt, integral_constant<int, 2>{}, integral_constant<int, 2>{});
+      case 24: return f(vt, integral_constant<int, 2>{}, integral_constant<int, 4>{});
+      case 11: return f(vt, integral_constant<int, 1>{}, integral_constant<int, 1>{});
+      case 12: return f(vt, integral_constant<int, 1>{}, integral_constant<int, 2>{});
+      case 14: return f(vt, integral_constant<int, 1>{}, integral_constant<int, 4>{});
+      default: return 1;
+    }
+  };
+  return f64 ? of(double{}) : of(float{});
 }
+
+// The longest a unit waits for the other units' sums of ONE pass (one exchange), in ticks of the 100 MHz wall clock.
+// Placement-free: 5 ms — five hundred passes' worth (a pass is 3-11 us). Where the units share their places with whatever
+// else runs there — the one-XCD mode, whose units compete for one XCD's CUs; a view, whose launch sits inside a solve
+// (an iteration is 14 us, the first exchange comes 25 us into the launch) — 2 ms: rather launch again. A unit that is not
+// resident by then is behind another tenant's work: the streaming launches, which need no co-residency, take over.
+// (Round 4 waited 0.5 s — a thousand solves' worth — before a 0.3 ms solve went on; on a view 0.2 s before a 1.2 ms one.)
+constexpr long long RS_TIMEOUT_TICKS = 500000, RS_TIMEOUT_TICKS_SHARED = 200000;
+// (ten times as long for a context's first launch — a cold code object, a clock that ramps up or a profiler
+// that serialises kernels must not look like another tenant)
+constexpr long long RS_TIMEOUT_FIRST_LAUNCH = 10;
+enum class Places { free, shared };
+constexpr long long exchange_timeout_ticks(Places places, bool first_launch) {
+  return (places == Places::shared ? RS_TIMEOUT_TICKS_SHARED : RS_TIMEOUT_TICKS) * (first_launch ? RS_TIMEOUT_FIRST_LAUNCH : 1);
+}
+// The time-out of a launch of k_solve_resident or k_solve_resident_batch of context h. The test knob, read at every
+// call (tests set and unset it between solves of one process), overrides when it parses to a NON-ZERO value;
+// `overridden` then tells the lone solve not to repeat a one-XCD launch that timed out. (The view solver's knob
+// overrides whenever it is set, zero included: rvr_timeout_ticks, host_rv_resident.hpp. Tests rely on both.)
+long long resident_timeout_ticks(const Ctx* h, Places places, bool* overridden = nullptr) {
+  const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS");
+  const long long knob = e ? std::atoll(e) : 0;
+  if (overridden) *overridden = knob != 0;
+  return knob ? knob : exchange_timeout_ticks(places, h->res.x.epoch == 0);
+}
+
+// the context's values are doubles (dispatch_vt's criterion, for the instance tables below and of the view solver)
+bool stores_f64(const Ctx* h) { return h->storage == CLIPPER_HIP_STORE_F64; }
 
 // the current slices have a resident plan the next solve may launch
 bool resident_applies(const Ctx* h) {
@@ -140,20 +152,20 @@ ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   Shard& s = h->sh[0];
   ResidentArgs a;
   a.M = slice_view(h, s);
-  a.units = reinterpret_cast<const ResidentUnit*>(r.host_plan.dev);
+  a.units = r.plan.at.units<ResidentUnit>(r.plan.buf.dev);
   a.nunits = r.nunits;
-  a.nslots_of_cg = r.host_plan.dev + static_cast<size_t>(r.nunits) * sizeof(ResidentUnit);
-  a.npieces = r.host_plan.dev + r.off_np;
-  a.wave_cg = r.host_plan.dev + r.off_wc;
-  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan.dev + r.off_pc);
+  a.nslots_of_cg = r.plan.at.slots(r.plan.buf.dev);
+  a.npieces = r.plan.at.npieces(r.plan.buf.dev);
+  a.wave_cg = r.plan.at.wave_cg(r.plan.buf.dev);
+  a.pieces = r.plan.at.pieces(r.plan.buf.dev);
   a.maxslots = r.maxslots;
   a.m = h->m;
   a.mp = h->mp;
   a.prm = prm;
   a.rescale = rescale ? 1 : 0;
   a.u0 = s.u0;
-  a.xb = r.xb;
-  a.epoch0 = r.epoch;
+  a.xb = r.x.xb;
+  a.epoch0 = r.x.epoch;
   a.err = r.ctl.as<uint32_t>();
   a.lds_slices = r.lds_slices;
   a.u_dev = s.pt;  // point slot (0, 0), array u
@@ -168,24 +180,6 @@ ResidentArgs resident_args(Ctx* h, const SolverParams& prm, bool rescale) {
   return a;
 }
 
-// The epochs of the exchange granules (xb). Each clear is queued on the context's stream, ahead of the next launch
-// that reads the buffer: all of them go out on that stream (a batch's children borrow the batch's).
-// The granules carry the low 32 bits of the epoch: long before they wrap, start over on a clean buffer
-int epoch_wrap(unsigned long long& epoch, void* xb, size_t bytes, hipStream_t stream) {
-  if ((epoch & 0xffffffffull) > 0xf0000000ull) {
-    HIPCHK(hipMemsetAsync(xb, 0, bytes, stream));
-    epoch = (epoch & ~0xffffffffull) + (1ull << 32);
-  }
-  return 0;
-}
-
-// a launch that finished the solve after `iters` iterations
-int resident_finished(Ctx* h, int64_t iters) {
-  Resident& r = h->res;
-  r.epoch += static_cast<unsigned long long>(iters) + 8ull;
-  return epoch_wrap(r.epoch, r.xb, r.xb.bytes(), h->sh[0].stream);
-}
-
 // a launch that gave up (the stream has drained): its error word; the word, the counters and the granules cleared.
 // Whether the context tries again (r.failed) is the caller's.
 int resident_gave_up(Ctx* h, uint32_t& err) {
@@ -193,8 +187,7 @@ int resident_gave_up(Ctx* h, uint32_t& err) {
   err = 0;
   HIPCHK(hipMemcpy(&err, r.ctl, sizeof(err), hipMemcpyDeviceToHost));
   HIPCHK(hipMemsetAsync(r.ctl, 0, 4 * sizeof(unsigned long long), h->sh[0].stream));
-  HIPCHK(hipMemsetAsync(r.xb, 0, r.xb.bytes(), h->sh[0].stream));
-  r.epoch += 1ull << 20;
+  if (int rc = r.x.gave_up(h->sh[0].stream)) return rc;
   r.last_error = static_cast<int>(err);
   return 0;
 }
@@ -216,11 +209,10 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
   static std::atomic<int> next_home{0};
   if (r.home < 0) r.home = next_home.fetch_add(1) & 7;
   a.home = r.home;
-  long long timeout_override = 0;
   // test knobs: a home XCD that does not exist (the one-XCD launch must be refused and repeated in
   // the placement-free mode), a time-out of a few ticks (the streaming launches must take over)
   if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_HOME")) a.home = std::atoi(e);
-  if (const char* e = std::getenv("CLIPPER_HIP_RESIDENT_TIMEOUT_TICKS")) timeout_override = std::atoll(e);
+  bool timeout_overridden = false;
   // One-XCD mode: with at most 28 units (an XCD has 32 CUs) the launch is 8 x units workgroups and the
   // ones on XCD 0 do the work, exchanging through their common L2 (per pass ~2.5 us less). Refused
   // once (the hardware did not put enough workgroups there), it is not tried again.
@@ -229,20 +221,14 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
   volatile HostMirror* hm = h->mirror;
   for (int attempt = 0;; ++attempt) {
     a.xcd_mode = (!r.xcd_off && !xcd_env_off && r.nunits >= 2 && r.nunits <= 28) ? 1 : 0;
-    // longest wait for another unit's sums of ONE pass on the 100 MHz wall clock: 5 ms — five hundred passes' worth
-    // (a pass is 3-11 us); in the one-XCD mode 2 ms (its units compete for one XCD's CUs with whatever else runs
-    // there: rather launch again). A unit that is not resident by then is behind another tenant's work: the
-    // streaming launches take over, and this matrix is not tried again (r.failed). Round 4 waited 0.5 s — a thousand
-    // solves' worth — before a 0.3 ms solve went on.
-    // (ten times as long for a context's first launch — cold code object, clock ramp-up, a serialising profiler)
-    a.timeout_ticks = timeout_override ? timeout_override : (a.xcd_mode ? 200000ll : 500000ll) * (r.epoch == 0 ? 10 : 1);
-    a.epoch0 = r.epoch;
+    // (a launch that times out: the streaming launches take over, and this matrix is not tried again — r.failed)
+    a.timeout_ticks = resident_timeout_ticks(h, a.xcd_mode ? Places::shared : Places::free, &timeout_overridden);
+    a.epoch0 = r.x.epoch;
     std::memset(h->mirror, 0, sizeof(HostMirror));
     std::atomic_thread_fence(std::memory_order_seq_cst);
-    int lr = 1;
-    dispatch_vt(h, [&](auto tag) {
-      using VT = decltype(tag);
-      lr = resident_launch_v<VT>(h, s, a);
+    const unsigned grid = static_cast<unsigned>(a.xcd_mode ? 8 * a.nunits : a.nunits);
+    const int lr = with_resident_instance(stores_f64(h), r.V, r.E, [&](auto vt, auto v, auto e) {
+      return resident_launch(k_solve_resident<decltype(vt), decltype(v)::value, decltype(e)::value>, "resident", s.device, grid, s.stream, a);
     });
     if (lr != 0) {
       if (rs_debug()) std::fprintf(stderr, "[resident] launch refused (V=%d E=%d)\n", r.V, r.E);
@@ -266,7 +252,7 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
     uint32_t err = 0;
     if (int rc = resident_gave_up(h, err)) return rc;
     if (rs_debug()) std::fprintf(stderr, "[resident] gave up: error %u (one-XCD mode %d)\n", err, a.xcd_mode);
-    if ((err == RS_ERR_PLAN || err == RS_ERR_TIMEOUT) && a.xcd_mode && attempt == 0 && timeout_override == 0) {
+    if ((err == RS_ERR_PLAN || err == RS_ERR_TIMEOUT) && a.xcd_mode && attempt == 0 && !timeout_overridden) {
       r.xcd_off = true;  // placement-free mode from now on
       continue;
     }
@@ -275,7 +261,7 @@ int resident_solve(Ctx* h, const SolverParams& prm, bool rescale, SolveShared& f
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   fin = mirror_result(hm);
-  if (int rc = resident_finished(h, hm->iters)) return rc;
+  if (int rc = r.x.finished(hm->iters, s.stream)) return rc;
   if (rs_debug()) std::fprintf(stderr, "[resident] solved: units=%d one-XCD mode=%d passes=%lld\n", r.nunits, a.xcd_mode,
                                static_cast<long long>(fin.n_passes));
   ran = true;

@@ -79,6 +79,26 @@ bool rvr_replica_enabled(const Ctx* h) { return rvr_replica_gate(h) && rvr_local
 // could a view of this many rows go to the resident solver? (what rvr_plan checks before it looks at the directory)
 bool rvr_candidate(const Ctx* h, int64_t nrows) { return rvr_enabled(h) && nrows >= 1 && nrows <= RVR_MAXROWS; }
 
+// (value type, V of 6 or 4, FINE) -> f(the instance of k_solve_view_resident). FINE: the instance with the finer
+// stamps, only when stamps are on — same launch bounds and LDS, so the same residency. (The instances stand in the
+// code object in the order they are named here, which is the order it had: host_matrix_io.hpp on why that matters.)
+template <typename F>
+auto with_view_instance(bool f64, int V, bool fine, F&& f) {
+  if (!fine && f64) return V == 6 ? f(k_solve_view_resident<double, 6, false>) : f(k_solve_view_resident<double, 4, false>);
+  if (!fine) return V == 6 ? f(k_solve_view_resident<float, 6, false>) : f(k_solve_view_resident<float, 4, false>);
+  if (f64) return V == 6 ? f(k_solve_view_resident<double, 6, true>) : f(k_solve_view_resident<double, 4, true>);
+  return V == 6 ? f(k_solve_view_resident<float, 6, true>) : f(k_solve_view_resident<float, 4, true>);
+}
+
+// The time-out of a launch on a view: the shared-places wait of exchange_timeout_ticks (host_resident.hpp), 2 ms for one
+// exchange — a hundred iterations' worth. The test knob, read at every call, overrides WHENEVER it is set, zero
+// included. The first launch's ten-fold wait has never applied here: it used to be tested on the epoch after this
+// launch's 2^20 had been added to it, which is never 0. Kept as it was (NOTEBOOK.md, "The resident solvers' host side").
+long long rvr_timeout_ticks() {
+  const char* e = std::getenv("CLIPPER_HIP_VIEW_RESIDENT_TIMEOUT_TICKS");
+  return e ? std::atoll(e) : exchange_timeout_ticks(Places::shared, false);
+}
+
 // Called when a view has just been built and its directory (csc_hLq) is on the host: does it fit the
 // resident solver? Lays out the units (host_plan.hpp) into mapped pinned memory.
 int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
@@ -103,9 +123,7 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
   if (r.max_units_device < 0) {
     int per_cu = 0;
     hipError_t e = hipErrorUnknown;
-    dispatch_vt(h, [&](auto tag) {
-      using VT = decltype(tag);
-      auto kern = (h->V == 6) ? k_solve_view_resident<VT, 6, false> : k_solve_view_resident<VT, 4, false>;
+    with_view_instance(stores_f64(h), h->V, false, [&](auto kern) {
       if (raise_dynamic_lds(reinterpret_cast<const void*>(kern), s.device, static_cast<int>(RS_LDS_MAX)))
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), RVR_NT, RS_LDS_MAX);
     });
@@ -147,29 +165,8 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
     }
   }
   HIPCHK(hipSetDevice(s.device));
-  const size_t off_np = plan.units.size() * sizeof(RvrUnit);
-  const size_t off_wc = off_np + static_cast<size_t>(round_up(static_cast<int64_t>(plan.npieces.size()), 16));
-  const size_t off_pc = off_wc + static_cast<size_t>(round_up(static_cast<int64_t>(plan.wave_cg.size()), 16));
-  const size_t bytes = off_pc + plan.pieces.size() * sizeof(uint32_t) + 64;
-  if (bytes > r.host_plan.cap) HIPCHK(r.host_plan.alloc(bytes + 4096, hipHostMallocMapped | hipHostMallocCoherent));
-  std::memcpy(r.host_plan, plan.units.data(), plan.units.size() * sizeof(RvrUnit));
-  std::memcpy(r.host_plan + off_np, plan.npieces.data(), plan.npieces.size());
-  std::memcpy(r.host_plan + off_wc, plan.wave_cg.data(), plan.wave_cg.size());
-  {  // the pieces: only the ones in use (a few per wave of the pmax slots: a tenth of the table, into pinned memory)
-    uint32_t* dst = reinterpret_cast<uint32_t*>(r.host_plan + off_pc);
-    const uint32_t* src = plan.pieces.data();
-    for (size_t wv = 0; wv < plan.npieces.size(); ++wv)
-      for (int j = 0; j < plan.npieces[wv]; ++j) dst[wv * RVR_PMAX + j] = src[wv * RVR_PMAX + j];
-  }
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-  r.off_np = off_np;
-  r.off_wc = off_wc;
-  r.off_pc = off_pc;
-  const size_t xb_bytes = static_cast<size_t>(rvr_xb_granules(6)) * sizeof(unsigned long long);
-  if (!r.xb) {
-    HIPCHK(r.xb.alloc(xb_bytes / sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(r.xb, 0, xb_bytes, s.stream));  // no granule may carry a future epoch
-  }
+  if (int rc = plan_image_store(r.plan, plan, nullptr, 0, RVR_PMAX)) return rc;
+  if (int rc = r.x.ensure(static_cast<size_t>(rvr_xb_granules(6)), s.stream)) return rc;
   if (!r.ctl) {
     HIPCHK(r.ctl.alloc(RVR_GIVEUP_SLOTS * 16));
     HIPCHK(hipMemsetAsync(r.ctl, 0, RVR_GIVEUP_SLOTS * 64, s.stream));
@@ -182,19 +179,6 @@ int rvr_plan(Ctx* h, Shard& s, bool replica = false) {
   r.plan_entries = plan.entries;
   r.lds_slices = plan.lds_slices;
   r.ready = true;
-  return 0;
-}
-
-template <typename VT, int V>
-int rvr_launch_t(Ctx* h, Shard& s, const RvrArgs& a) {
-  // (the instance with the finer stamps only when stamps are on: same launch bounds and LDS, so the same residency)
-  auto kern = a.stamps ? k_solve_view_resident<VT, V, true> : k_solve_view_resident<VT, V, false>;
-  if (!raise_dynamic_lds(reinterpret_cast<const void*>(kern), s.device, static_cast<int>(RS_LDS_MAX))) return 1;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(a.nunits)), dim3(RVR_NT), RS_LDS_MAX, s.stream, a);
-  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-    if (rs_debug()) std::fprintf(stderr, "[view-resident] launch failed: %s\n", hipGetErrorString(e));
-    return 1;
-  }
   return 0;
 }
 
@@ -217,11 +201,11 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
   HIPCHK(hipSetDevice(s.device));
   RvrArgs a{};
   a.R = r.on_replica ? row_view_full(h, s) : row_view(h, s);
-  a.units = reinterpret_cast<const RvrUnit*>(r.host_plan.dev);
+  a.units = r.plan.at.units<RvrUnit>(r.plan.buf.dev);
   a.nunits = r.nunits;
-  a.npieces = r.host_plan.dev + r.off_np;
-  a.wave_cg = r.host_plan.dev + r.off_wc;
-  a.pieces = reinterpret_cast<const uint32_t*>(r.host_plan.dev + r.off_pc);
+  a.npieces = r.plan.at.npieces(r.plan.buf.dev);
+  a.wave_cg = r.plan.at.wave_cg(r.plan.buf.dev);
+  a.pieces = r.plan.at.pieces(r.plan.buf.dev);
   a.viewpos = s.rv.viewpos;
   a.st = s.st + h->par;
   a.shared = s.shared;
@@ -234,23 +218,15 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
   a.m = h->m;
   a.mp = h->mp;
   a.pt = s.pt;
-  a.xb = r.xb;
-  if (int rc = epoch_wrap(r.epoch, r.xb, r.xb.bytes(), s.stream)) return rc;
-  a.epoch0 = r.epoch;
-  r.epoch += 1ull << 20;  // whatever this launch publishes (even if it gives up half-way) lies below the next one's
+  a.xb = r.x.xb;
+  if (int rc = r.x.wrap(s.stream)) return rc;
+  a.epoch0 = r.x.epoch;
+  r.x.epoch += 1ull << 20;  // whatever this launch publishes (even if it gives up half-way) lies below the next one's
   const bool own_ctl = r.launches_this_solve < RVR_GIVEUP_SLOTS;  // (its block was zeroed by the build's k_rv_resume)
   a.ctl = r.ctl + (own_ctl ? 16 * r.launches_this_solve : 0);
   a.giveup_host = (r.giveup_host.dev && r.launches_this_solve < RVR_GIVEUP_SLOTS) ? r.giveup_host.dev + 4 * r.launches_this_solve : nullptr;
   a.lds_slices = r.lds_slices;
-  // The longest a unit waits for the others' granules of ONE exchange, on the 100 MHz wall clock: 2 ms — a hundred
-  // iterations' worth (an iteration is 14 us, the first exchange comes 25 us into the launch). A unit that is not
-  // resident by then is behind another tenant's work; the streaming launches, which need no co-residency, take over
-  // (round 4: 0.2 s — two hundred solves' worth of waiting before a 1.2 ms solve went on).
-  a.timeout_ticks = 200000ll;
-  // (the first launch of a context waits ten times as long — a cold code object, a clock that ramps up or a
-  // profiler that serialises kernels must not look like another tenant and send the context into its back-off)
-  if (r.epoch == 0) a.timeout_ticks = 2000000ll;
-  if (const char* e = std::getenv("CLIPPER_HIP_VIEW_RESIDENT_TIMEOUT_TICKS")) a.timeout_ticks = std::atoll(e);  // (test knob)
+  a.timeout_ticks = rvr_timeout_ticks();
   // (a launch owns 2^20 epochs, one per exchange: the budget stays below, so that nothing it publishes can carry a
   // tag of the next launch's range)
   a.max_exchanges = 1 << 18;
@@ -266,10 +242,8 @@ int rvr_enqueue(Ctx* h, const SolverParams& prm, bool& launched) {
       if (!r.ev[2 * r.ev_n + k]) HIPCHK(r.ev[2 * r.ev_n + k].create());
     HIPCHK(hipEventRecord(r.ev[2 * r.ev_n], s.stream));
   }
-  int lr = 1;
-  dispatch_vt(h, [&](auto tag) {
-    using VT = decltype(tag);
-    lr = (h->V == 6) ? rvr_launch_t<VT, 6>(h, s, a) : rvr_launch_t<VT, 4>(h, s, a);
+  const int lr = with_view_instance(stores_f64(h), h->V, a.stamps != nullptr, [&](auto kern) {
+    return resident_launch(kern, "view-resident", s.device, static_cast<unsigned>(a.nunits), s.stream, a);
   });
   if (lr != 0) {
     r.ready = false;  // this device does not take the launch: the streaming launches keep the view

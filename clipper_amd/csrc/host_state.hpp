@@ -203,18 +203,61 @@ struct StagedInputs {
   double maxabs = -1.0;
 };
 
+// A resident plan as its kernel reads it (clipper_plan::PlanLayout, host_plan.hpp), in mapped pinned memory: the kernel
+// reads it through the bus once, nothing is copied. Filled by plan_image_store (host_resident.hpp).
+struct PlanImage {
+  PinnedBuf<uint8_t> buf;
+  clipper_plan::PlanLayout at;
+};
+
+// The exchange granules of a resident solver and their epochs. A granule carries the low 32 bits of the epoch it was
+// written in, and no granule may carry an epoch a later launch waits for: the buffer is zero when it is new, cleared
+// long before the tag wraps, and cleared after a launch that gave up. Each clear is queued on the context's stream,
+// ahead of the next launch that reads the buffer: all of them go out on that stream (a batch's children borrow the
+// batch's).
+struct ExchangeBuf {
+  DevBuf<unsigned long long> xb;
+  unsigned long long epoch = 0;  // the first of the next launch; 0: the context has not launched yet
+
+  int clear(hipStream_t stream) {
+    HIPCHK(hipMemsetAsync(xb, 0, xb.bytes(), stream));
+    return 0;
+  }
+  // at least `granules`: the resident solver grows it with the problem, the view solver asks for its fixed size
+  // (a growth that fails leaves no buffer and no capacity: the next plan allocates)
+  int ensure(size_t granules, hipStream_t stream) {
+    if (granules * sizeof(unsigned long long) <= xb.bytes()) return 0;
+    HIPCHK(xb.alloc(granules));
+    return clear(stream);
+  }
+  // long before the tag wraps: start over on a clean buffer, at the next 2^32
+  int wrap(hipStream_t stream) {
+    if ((epoch & 0xffffffffull) <= 0xf0000000ull) return 0;
+    epoch = (epoch & ~0xffffffffull) + (1ull << 32);
+    return clear(stream);
+  }
+  // a launch of the resident solver that finished after `iters` iterations (one epoch each)
+  int finished(int64_t iters, hipStream_t stream) {
+    epoch += static_cast<unsigned long long>(iters) + 8ull;
+    return wrap(stream);
+  }
+  // a launch that gave up (the stream has drained): whatever it published is gone, the next one starts far above it
+  int gave_up(hipStream_t stream) {
+    epoch += 1ull << 20;
+    return clear(stream);
+  }
+};
+
 // the resident solver (k_resident.hip.h): plan of the current slices and its buffers
 struct Resident {
   bool ready = false;    // the current slices fit: `plan` is valid
   bool failed = false;   // a launch gave up on this matrix (the streaming solver took over)
   int last_error = 0;
   int V = 0, E = 0, nunits = 0, maxslots = 0;
-  uint32_t lds_slices = 0, lds_total = 0;
-  PinnedBuf<uint8_t> host_plan;      // mapped: units, then slots per column group
-  size_t off_np = 0, off_wc = 0, off_pc = 0;  // where the piece counts / the wave map / the pieces start in the plan
-  DevBuf<unsigned long long> xb;     // exchange buffer [2][maxslots][V+1][mp][2] (granules)
+  uint32_t lds_slices = 0;
+  PlanImage plan;                    // units, slots per column group, piece counts, wave map, pieces
+  ExchangeBuf x;                     // exchange buffer [2][maxslots][V+1][mp][2] (granules)
   DevBuf<unsigned long long> ctl;    // [4]: the error word, the two counters of the one-XCD mode
-  unsigned long long epoch = 0;
   int V_forced = 0;                  // (a window other than 1: measured 2.3 x slower per pass)
   bool xcd_off = false;              // the one-XCD mode was refused once (or CLIPPER_HIP_RESIDENT_XCD=0)
   int home = -1;                     // this context's home XCD in that mode
@@ -225,11 +268,9 @@ struct ViewResident {
   bool ready = false;        // the view in use fits: `plan` is valid
   int nunits = 0;
   uint32_t lds_slices = 0;
-  PinnedBuf<uint8_t> host_plan;      // mapped: units, piece counts, wave map, pieces
-  size_t off_np = 0, off_wc = 0, off_pc = 0;
-  DevBuf<unsigned long long> xb;     // exchange buffer (granules), zero at allocation
+  PlanImage plan;                    // units, piece counts, wave map, pieces
+  ExchangeBuf x;                     // exchange buffer (granules); every launch takes 2^20 epochs
   DevBuf<uint32_t> ctl;              // [RVR_GIVEUP_SLOTS][16]: per launch of a solve [0] error word, [1] arrivals at the exit, [4..5] unit 0's start
-  unsigned long long epoch = 0;      // every launch takes 2^20 epochs
   int target_units = 0;              // CLIPPER_HIP_VIEW_RESIDENT_WGS (0: automatic)
   // Launches that gave up (an exchange that timed out: a unit that did not become resident in time — another tenant
   // on the device —, an LDS plan the device refused). The kernel leaves its error word in pinned memory, one word per

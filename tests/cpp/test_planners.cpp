@@ -1,4 +1,4 @@
-// CPU test of the two host planners (clipper_amd/csrc/host_plan.hpp): on random slice directories —
+// CPU test of the host planners (clipper_amd/csrc/host_plan.hpp): on random slice directories —
 // sizes on and off the edges, empty slices, dense blocks whose chunks must be cut by step range —
 // every plan must cover every step of every slice exactly once.
 //   plan_pass      work list of the streaming pass: per strip, the chunks are covered once by whole-range
@@ -7,9 +7,15 @@
 //   plan_resident  units cover every (column group, chunk) once, slots are numbered 0..n-1 per group, a
 //                  unit's slices fit its LDS share by the planner's own bound, the pieces of a unit
 //                  partition the steps of each of its slices among waves mapped to that column group
+//   plan_view_resident  (at check_view_resident)
+//   plan identity  the plans of a fixed set of directories, folded into one hash per planner, are what they were
+//                  (at check_identity)
+//   plan image     every plan the test produces, packed (plan_pack) and read back through PlanLayout's accessors
+//                  (at check_image)
 //   g++ -std=c++17 -O1 -I clipper_amd/csrc tests/cpp/test_planners.cpp -o /tmp/t && /tmp/t
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <random>
 #include <set>
@@ -85,11 +91,51 @@ static size_t check_pass(const std::vector<uint32_t>& L, int ncg, int nchunks, i
   return P.work.size();
 }
 
+// The plan image (PlanLayout, plan_pack): every offset is a multiple of 16, the arrays follow one another without
+// overlap, the bytes asked for cover the last piece and the 64-byte tail, and nothing behind them is written; a plan
+// packed into the buffer reads back through the accessors: units, slots, piece counts, wave map, the pieces in use.
+// ONE buffer for every plan of the run, never cleared: a context packs plan after plan into the buffer it has.
+template <class U>
+static void check_image(const std::vector<U>& units, const std::vector<uint8_t>& slots, const std::vector<uint8_t>& npieces,
+                        const std::vector<uint8_t>& wave_cg, const std::vector<uint32_t>& pieces, size_t pmax) {
+  static std::vector<uint8_t> buf;
+  if (npieces.empty()) return;  // (a directory turned down before any piece was dealt: there is no plan to pack)
+  REQUIRE(!units.empty() && npieces.size() % units.size() == 0);
+  REQUIRE(wave_cg.size() == npieces.size() && pieces.size() == npieces.size() * pmax);
+  const PlanLayout A = plan_layout(units.size(), slots.size(), npieces.size(), pmax);
+  REQUIRE(A.off_slots % 16 == 0 && A.off_np % 16 == 0 && A.off_wc % 16 == 0 && A.off_pc % 16 == 0);
+  REQUIRE(A.off_slots >= units.size() * sizeof(U) && A.off_np >= A.off_slots + slots.size());
+  REQUIRE(A.off_wc >= A.off_np + npieces.size() && A.off_pc >= A.off_wc + wave_cg.size());
+  REQUIRE(A.bytes >= A.off_pc + pieces.size() * sizeof(uint32_t) + 64);
+  constexpr size_t GUARD = 64;
+  if (buf.size() < A.bytes + GUARD) buf.resize(A.bytes + GUARD);
+  std::memset(buf.data() + A.bytes, 0xA5, GUARD);
+  plan_pack(A, buf.data(), units.data(), slots.data(), npieces.data(), wave_cg.data(), pieces.data());
+  for (size_t g = 0; g < GUARD; ++g) REQUIRE(buf[A.bytes + g] == 0xA5);
+  const uint8_t* base = buf.data();
+  REQUIRE(units.empty() || std::memcmp(A.units<U>(base), units.data(), units.size() * sizeof(U)) == 0);
+  REQUIRE(slots.empty() || std::memcmp(A.slots(base), slots.data(), slots.size()) == 0);
+  REQUIRE(npieces.empty() || std::memcmp(A.npieces(base), npieces.data(), npieces.size()) == 0);
+  REQUIRE(wave_cg.empty() || std::memcmp(A.wave_cg(base), wave_cg.data(), wave_cg.size()) == 0);
+  for (size_t wv = 0; wv < npieces.size(); ++wv)
+    for (size_t j = 0; j < npieces[wv]; ++j) REQUIRE(A.pieces(base)[wv * pmax + j] == pieces[wv * pmax + j]);
+}
+static void check_image(const ResidentPlan& P, const ResidentConsts& K) {
+  check_image(P.units, P.nsl, P.npieces, P.wave_cg, P.pieces, static_cast<size_t>(K.pmax));
+}
+static void check_image(const ViewResidentPlan& P, const ResidentConsts& K) {
+  check_image(P.units, std::vector<uint8_t>(), P.npieces, P.wave_cg, P.pieces, static_cast<size_t>(K.pmax));
+}
+
+static const ResidentConsts K_RESIDENT{512, 8, 64, 12, 4, 159u * 1024u, 2 * 8 * 16 * 8, 64 * 4 + 64, 2048, 16};
+static const ResidentConsts K_VIEW{512, 8, 64, 12, 2, 159u * 1024u, 2 * 8 * 16 * 8 + 64 * 8, 64 * 8 + 64, 2048, 16};
+
 static bool check_resident(const std::vector<uint32_t>& L, int ncg, int nchunks, int64_t m, int esize, int max_units) {
-  const ResidentConsts K{512, 8, 64, 12, 4, 159u * 1024u, 2 * 8 * 16 * 8, 64 * 4 + 64, 2048, 16};
+  const ResidentConsts& K = K_RESIDENT;
   const int64_t mp = (m + 63) / 64 * 64;
   ResidentPlan P;
   plan_resident(L.data(), ncg, nchunks, m, mp, esize, max_units, 0, K, P);
+  check_image(P, K);
   if (!P.ok) return false;
   REQUIRE(P.V == 1 && (P.E == 1 || P.E == 2 || P.E == 4) && static_cast<int64_t>(P.E) * K.nt >= mp);
   REQUIRE(static_cast<int>(P.units.size()) <= std::max(max_units, 1));
@@ -164,9 +210,10 @@ static bool check_resident(const std::vector<uint32_t>& L, int ncg, int nchunks,
 // partition the steps of each of its slices among waves mapped to that column group.
 static bool check_view_resident(const std::vector<uint32_t>& L, int ncg, int nchunks, int esize, int target, int max_units,
                                 uint32_t fixed) {
-  const ResidentConsts K{512, 8, 64, 12, 2, 159u * 1024u, 2 * 8 * 16 * 8 + 64 * 8, 64 * 8 + 64, 2048, 16};
+  const ResidentConsts& K = K_VIEW;
   ViewResidentPlan P;
   plan_view_resident(L.data(), ncg, nchunks, esize, target, max_units, fixed, K, P);
+  check_image(P, K);
   if (!P.ok) return false;
   REQUIRE(static_cast<int>(P.units.size()) <= max_units && !P.units.empty());
   std::vector<std::vector<int>> lanes(ncg, std::vector<int>(64, 0));
@@ -243,7 +290,134 @@ static bool check_view_resident(const std::vector<uint32_t>& L, int ncg, int nch
   return true;
 }
 
+// ---- plan identity: the plans are, bit for bit, what they were ---------------------------------------------------------
+// Every plan of a fixed set of directories is folded into one 64-bit FNV-1a value per planner and compared with a
+// constant. The constants were printed by THIS code compiled against host_plan.hpp as it stood before the piece
+// dealer was stated once (deal_pieces) — the commit before the one that added this check. They are never to be
+// regenerated from the header under test: a change that moves them changes the association of every sum of the
+// resident solvers, and has to say so.
+// The directories come from raw std::mt19937 output (its sequence is fixed by the standard) and integer arithmetic only:
+// std::binomial_distribution, which directory() uses, is not specified bit for bit across standard libraries.
+struct Fnv {
+  uint64_t h = 14695981039346656037ull;
+  void bytes(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+  }
+  template <class T>
+  void value(T v) { bytes(&v, sizeof(v)); }
+  template <class T>
+  void array(const std::vector<T>& v) {
+    value<uint64_t>(v.size());
+    if (!v.empty()) bytes(v.data(), v.size() * sizeof(T));
+  }
+  // unit records, piece counts, wave map and the pieces in use
+  template <class U>
+  void tables(const std::vector<U>& units, const std::vector<uint8_t>& npieces, const std::vector<uint8_t>& wave_cg,
+              const std::vector<uint32_t>& pieces, size_t pmax) {
+    array(units);
+    array(npieces);
+    array(wave_cg);
+    for (size_t wv = 0; wv < npieces.size() && (wv + 1) * pmax <= pieces.size(); ++wv)
+      for (size_t j = 0; j < npieces[wv]; ++j) value<uint32_t>(pieces[wv * pmax + j]);
+  }
+};
+
+// column lengths uniform in [0, 2 * mean] (mean <= 64); the slices of the last dense_cgs column groups from chunk
+// dense_k0 on are a dense block (lengths 126 .. 128)
+static std::vector<uint32_t> directory_raw(std::mt19937& rng, int ncg, int nchunks, uint32_t mean, int dense_cgs, int dense_k0) {
+  std::vector<uint32_t> L(static_cast<size_t>(ncg) * nchunks);
+  for (int cg = 0; cg < ncg; ++cg)
+    for (int k = 0; k < nchunks; ++k) {
+      const bool dense = cg >= ncg - dense_cgs && k >= dense_k0;
+      uint32_t maxlen = 0, entries = 0;
+      for (int l = 0; l < 64; ++l) {
+        const uint32_t r = static_cast<uint32_t>(rng());
+        const uint32_t n = dense ? 128u - r % 3u : r % (2u * mean + 1u);
+        maxlen = std::max(maxlen, n);
+        entries += n;
+      }
+      L[static_cast<size_t>(cg) * nchunks + k] = (maxlen + 3u) / 4u | (entries << 8);
+    }
+  return L;
+}
+
+static void check_identity() {
+  std::mt19937 rng(950);
+  Fnv res, view;
+  int nres = 0, nres_ok = 0, nview = 0, nview_ok = 0;
+  // resident plans: one unit (m <= 512 where the slices fit), the edge (512, 513), many units (up to 2048), both value sizes
+  for (int m : {1, 64, 65, 300, 512, 513, 1000, 1500, 2047, 2048})
+    for (uint32_t mean : {0u, 1u, 7u, 26u, 64u})
+      for (int dense : {0, 1, 2}) {
+        const int ncg = (m + 63) / 64, nchunks = (m + 127) / 128;
+        const int dense_cgs = dense == 0 ? 0 : (dense == 1 ? std::max(1, ncg / 20) : (ncg + 1) / 2);
+        const int dense_k0 = dense == 0 ? nchunks : (dense == 1 ? nchunks - std::max(1, nchunks / 20) : nchunks / 2);
+        std::snprintf(g_case, sizeof(g_case), "identity m=%d mean=%u dense=%d", m, mean, dense);
+        const auto L = directory_raw(rng, ncg, nchunks, mean, dense_cgs, dense_k0);
+        for (int esize : {4, 8})
+          for (int max_units : {64, 200}) {
+            ResidentPlan P;
+            plan_resident(L.data(), ncg, nchunks, m, (m + 63) / 64 * 64, esize, max_units, 0, K_RESIDENT, P);
+            res.value<uint8_t>(P.ok ? 1 : 0);
+            res.value<int32_t>(P.V);
+            res.value<int32_t>(P.E);
+            res.value<int32_t>(P.maxslots);
+            res.value<uint32_t>(P.lds_slices);
+            res.value<uint64_t>(P.total_bound);
+            res.array(P.nsl);
+            res.tables(P.units, P.npieces, P.wave_cg, P.pieces, static_cast<size_t>(K_RESIDENT.pmax));
+            check_image(P, K_RESIDENT);
+            ++nres;
+            nres_ok += P.ok ? 1 : 0;
+          }
+      }
+  // views of up to 1024 rows over thousands of columns, a dense inlier block in the last column groups
+  auto plan_view = [&](const std::vector<uint32_t>& L, int ncg, int nchunks, int esize, int target) {
+    const uint32_t fixed = std::max<uint32_t>(nchunks * 128 * 6 * 8, 8 * 7 * 64 * 8) + K_VIEW.red_bytes + K_VIEW.tab_bytes;
+    ViewResidentPlan P;
+    plan_view_resident(L.data(), ncg, nchunks, esize, target, 248, fixed, K_VIEW, P);
+    view.value<uint8_t>(P.ok ? 1 : 0);
+    view.value<uint32_t>(P.lds_slices);
+    view.value<uint64_t>(P.entries);
+    view.tables(P.units, P.npieces, P.wave_cg, P.pieces, static_cast<size_t>(K_VIEW.pmax));
+    check_image(P, K_VIEW);
+    ++nview;
+    nview_ok += P.ok ? 1 : 0;
+  };
+  for (int ncg : {47, 79, 157, 196, 235})
+    for (int nchunks : {1, 3, 5, 8})
+      for (uint32_t mean : {1u, 10u, 32u}) {
+        std::snprintf(g_case, sizeof(g_case), "identity view ncg=%d nchunks=%d mean=%u", ncg, nchunks, mean);
+        const auto L = directory_raw(rng, ncg, nchunks, mean, std::max(1, ncg / 18), 0);
+        for (int esize : {4, 8})
+          for (int target : {40, 96, 170, 248}) plan_view(L, ncg, nchunks, esize, target);
+      }
+  std::snprintf(g_case, sizeof(g_case), "identity");
+  std::printf("plan identity: resident %d plans (%d fit) 0x%016llxull, view %d plans (%d fit) 0x%016llxull\n", nres, nres_ok,
+              static_cast<unsigned long long>(res.h), nview, nview_ok, static_cast<unsigned long long>(view.h));
+  REQUIRE(nres >= 200 && nview >= 200 && 4 * nres_ok > nres && 2 * nview_ok > nview);
+  REQUIRE(res.h == 0x1f15f6987c9eb4e7ull);
+  REQUIRE(view.h == 0x94512d42459c111cull);
+}
+
+// A context that solves problems of changing size packs a large plan, then a small one, into the same buffer (check_image
+// keeps one): the small one reads back right over what the large one left.
+static void check_image_reuse() {
+  std::mt19937 rng(951);
+  std::snprintf(g_case, sizeof(g_case), "image reuse");
+  ResidentPlan big, small;
+  const auto Lb = directory_raw(rng, 32, 16, 7, 2, 8), Ls = directory_raw(rng, 2, 1, 7, 0, 1);
+  plan_resident(Lb.data(), 32, 16, 2048, 2048, 4, 200, 0, K_RESIDENT, big);
+  plan_resident(Ls.data(), 2, 1, 100, 128, 4, 200, 0, K_RESIDENT, small);
+  REQUIRE(big.ok && small.ok && big.units.size() >= 32 && small.units.size() == 1);
+  check_image(big, K_RESIDENT);
+  check_image(small, K_RESIDENT);
+}
+
 int main() {
+  check_identity();
+  check_image_reuse();
   std::mt19937 rng(20260926);
   int npass = 0, nres = 0, nres_ok = 0;
   const int64_t sizes[] = {1, 2, 63, 64, 65, 100, 129, 300, 511, 512, 513, 777, 1000, 1500, 2047, 2048, 2500, 4000, 10000, 30000};

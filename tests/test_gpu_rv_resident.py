@@ -72,6 +72,33 @@ def test_headline_trials_and_ordered_list():
     g.close()
 
 
+def test_one_context_across_views_of_different_sizes():
+    """One context scores and solves problems of changing size in turn: its plan image (a large plan, then a small one,
+    in the same pinned buffer) and its exchange buffer (whose epochs go on from launch to launch) are reused. Each
+    solve is a fresh context's solve of the same problem, at the level the first test holds two contexts to."""
+    problems = [(10000, 0.95, 12345), (6000, 0.9, 6777), (10000, 0.95, 4), (6000, 0.9, 6777)]
+    fresh = {}
+    for key in dict.fromkeys(problems):
+        p = synth.make_euclidean_problem(key[0], key[1], seed=key[2])
+        gf = _ctx(p, abi.STORE_F32_CSC, 0)
+        fresh[key] = (p, gf.solve(p.u0), gf.view_stats().resident_launches)
+        gf.close()
+    g = abi.HipClipper(storage=abi.STORE_F32_CSC)
+    g.set_row_view(0)
+    for key in problems:
+        p, sf, launches = fresh[key]
+        g.score_pairwise_consistency_euclidean(p.D1, p.D2, p.A, **synth.EUCLID_BENCH_PARAMS)
+        s = g.solve(p.u0)
+        st = g.view_stats()
+        assert s.nodes.tolist() == sf.nodes.tolist(), key
+        assert s.ifinal == sf.ifinal, key
+        assert abs(s.score - sf.score) <= 1e-10 * abs(sf.score), key
+        assert np.allclose(s.u, sf.u, rtol=0, atol=1e-8), key
+        if launches >= 1:
+            assert st.resident_launches >= 1, (key, st.builds, st.rows, st.resident_launches)
+    g.close()
+
+
 @pytest.mark.parametrize("budget", [0, 1, 2, 3, 5, 9])
 def test_leaving_after_a_few_exchanges_hands_a_prepared_pass_back(budget, monkeypatch):
     """CLIPPER_HIP_VIEW_RESIDENT_MAX_EXCHANGES (test knob): the launch leaves after that many iterations — in

@@ -1,8 +1,9 @@
-"""CPU test of the two host planners (clipper_amd/csrc/host_plan.hpp): the work list of the streaming
-pass on the slices and the units / pieces of the resident solver are pure functions of the slice
+"""CPU test of the host planners (clipper_amd/csrc/host_plan.hpp): the work list of the streaming
+pass on the slices and the units / pieces of the resident solvers are pure functions of the slice
 directory; tests/cpp/test_planners.cpp (g++ only) checks on random directories that every plan covers
 every step of every slice exactly once, every partial-sum slot is written once, and a resident unit
-fits its share of LDS by the planner's own bound."""
+fits its share of LDS by the planner's own bound; that the plans of a fixed set of directories are bit
+for bit what they were; and that a plan packed into its image reads back as it was."""
 import os
 import subprocess
 
